@@ -20,6 +20,11 @@ reference's Rust, NOT the Rust itself) timed on this box's host cores on a bound
 outputs are also compared with the GPU's.  `e2e` (N = 1) is what a caller holding HOST numpy arrays gets from
 the compiled module's batch function -- upload, search, packed download and Python objects, pipelined in
 chunks -- with array paths and with the reference's list[int] paths; it is never `value`.
+
+A plain run does only what `value` needs: it sets up, warms up, times the K steps and prints the line.  `cpu_baseline`,
+`e2e`, `roofline`, the viterbi rooflines, the tie instrument and the other tie order's timing take runs of their own and
+are measured only with `--full` (null otherwise).  `--dump-outputs DIR` writes what the last timed step returned
+(dump_outputs()); the inputs are seeded, so two builds given the same arguments can be compared array for array.
 """
 import argparse
 import glob
@@ -72,6 +77,34 @@ def make_batch_peaky(seed, n_reads):
     np.exp(z, out=z)
     z /= z.sum(axis=1, keepdims=True)
     return z.reshape(n_reads, T, N).astype(np.float32)
+
+
+DUMP_BYTES = 56 << 20  # under the 64 MB a dump may take
+DUMP_READS = 1024
+
+
+def dump_outputs(dirname, rc):
+    """--dump-outputs: the host copy `rc` of what the last timed step returned, as DIR/<name>.npy.  out_len and status
+    are written whole (float64).  labels and qual (float32) and path (float64) are (reads, positions) arrays: they are
+    written for a fixed sample of reads (default_rng(0), at most DUMP_READS, in read order; all of them when the batch is
+    that small), with every position at or past the read's out_len set to -1, since what lies there is not part of the
+    result.  Returns {name: shape}."""
+    os.makedirs(dirname, exist_ok=True)
+    lens = np.asarray(rc.out_len).astype(np.int64)
+    B = len(lens)
+    rows = {k: np.asarray(getattr(rc, k)) for k in ("labels", "path", "qual") if getattr(rc, k) is not None}
+    per_read_bytes = sum(8 * a.shape[1] if k == "path" else 4 * a.shape[1] for k, a in rows.items())
+    n = int(max(1, min(B, DUMP_READS, (DUMP_BYTES - 16 * B) // max(per_read_bytes, 1))))
+    pick = np.arange(B) if n == B else np.sort(np.random.default_rng(0).choice(B, n, replace=False))
+    out = {"out_len": lens.astype(np.float64), "status": np.asarray(rc.status).astype(np.float64)}
+    for k, a in rows.items():
+        valid = np.arange(a.shape[1])[None, :] < lens[pick, None]
+        v = a[pick].astype(np.float64 if k == "path" else np.float32)
+        v[~valid] = -1
+        out[k] = v
+    for k, a in out.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
+    return {k: list(a.shape) for k, a in out.items()}
 
 
 def cpu_baseline(cfg, x_host, init_host, gpu_labels, gpu_path, gpu_len, budget_s):
@@ -561,7 +594,7 @@ def duplex_main(args, cfg, torch, dist, fcd, world, rank, local_rank, dev, distr
     elapsed = time.perf_counter() - t0
     k_ms, k_calls = h.timing_mean_ms()
     single_ms = None
-    if overlap:
+    if overlap and args.full:
         h.set_overlap(0)
         h.timing_reset()
         for _ in range(min(args.steps, 3)):
@@ -574,12 +607,14 @@ def duplex_main(args, cfg, torch, dist, fcd, world, rank, local_rank, dev, distr
     elapsed = float(t_max.item())
     if rank == 0:
         rc = r.cpu()
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, rc)
         ok = int((np.asarray(rc.status) == 0).sum())
         lens = np.asarray(rc.out_len).astype(np.int64)
         mean_L = float(lens.mean())
         # the CPU leg: the oracle (correctly rounded log-add, as the kernels define it) on a bounded sample, a pair per thread
         cpu = None
-        if world == 1:
+        if world == 1 and args.full:
             from concurrent.futures import ThreadPoolExecutor
             from oracle import oracle
             omode = (oracle.LOGSUMEXP if args.mode == "logsumexp" else oracle.MAXMODE) | oracle.MATH_CR
@@ -611,7 +646,7 @@ def duplex_main(args, cfg, torch, dist, fcd, world, rank, local_rank, dev, distr
         k_eff_ms = k_ms / in_flight if overlap else k_ms
         achieved = B * bytes_per_pair / (k_eff_ms * 1e-3) / 1e9
         prefix = "duplex_slots_kernel<%d" % (0 if args.mode == "logsumexp" else 1)
-        traffic, traffic_note = pmc_traffic(prefix) if (B == cfg["batch"]) else (None, None)
+        traffic, traffic_note = pmc_traffic(prefix) if (B == cfg["batch"] and args.full) else (None, None)
         out = {
             "metric": "pairs/s (2-D pair consensus, T=%d, N=5, beam=%d, band +-%d, %s)" % (Td, beam, band_w, args.mode),
             "value": world * B * args.steps / elapsed, "unit": "pairs/s", "n_gpus": world, "steps": args.steps,
@@ -625,7 +660,8 @@ def duplex_main(args, cfg, torch, dist, fcd, world, rank, local_rank, dev, distr
                        "logadd_mode": args.mode, "kernel": cfg["kernel_name"], "pairs_ok": ok, "mean_labels_per_pair": mean_L,
                        "overlap": overlap, "tie_order": fcd.tie_order(),
                        "parallelism": "pairs sharded x%d, no collective" % world if world > 1 else "single GPU"},
-            "roofline": {
+            "full": args.full,
+            "roofline": None if not args.full else {
                 "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                 "traffic": traffic, "traffic_source": traffic_note,
                 "kernel": "duplex search (log-space copies + kernel), %.3f ms per call (HIP events)%s, %d pairs x %.0f "
@@ -687,6 +723,11 @@ def main():
     ap.add_argument("--stub", action="store_true",
                     help="TEST ONLY (tests/test_bench_launcher.py): no GPU, no search -- the launcher, the rendezvous "
                          "(gloo), the barriers and the max-over-ranks clock with a sleeping stand-in for the step")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what `value` does not need: the CPU baseline and its output check, the e2e leg, "
+                         "the rooflines (viterbi included), the tie instrument and the other tie order")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` by itself: become the launcher of N ranks (one per GPU) of this very script
@@ -844,7 +885,7 @@ def main():
 
     # overlapping steps share the chip, so a launch's own duration above is longer than a launch alone: time that too
     single_ms = None
-    if overlap:
+    if overlap and args.full:
         handles[0].set_overlap(0)
         handles[0].timing_reset()
         for _ in range(min(args.steps, 4)):
@@ -865,72 +906,105 @@ def main():
 
     if rank == 0:
         rc = r.cpu()
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, rc)
         ok = int((rc.status == 0).sum())
         mean_L = float(rc.out_len.astype(np.float64).mean())
-        # posteriors in, u8 label + u32 time out (CRF: the dense T*S*N figure)
-        bytes_per_read = T * N * 4 * (4 if cfg["crf"] else 1) + 5.0 * mean_L
-        # Overlapping steps (fcd_set_overlap): `k_ms` is a launch's duration WHILE it shares the chip with the launches of the
-        # other internal streams -- on average k_ms * steps / elapsed of them at once -- so the kernel's rate is a launch's
-        # bytes over its share of that time, k_ms / launches_in_flight = elapsed / steps.  One launch at a time: k_ms itself.
-        in_flight = k_ms * args.steps / (elapsed * 1e3) if overlap else 1.0
-        k_eff_ms = k_ms / in_flight if overlap else k_ms
-        achieved = B * bytes_per_read / (k_eff_ms * 1e-3) / 1e9
-        # the CPU leg (and its output cross-check) runs on rank 0 at N = 1 only, as the contract asks
-        cpu = cpu_baseline(cfg, x_host, init_host, rc.labels, rc.path, rc.out_len, args.cpu_seconds) if world == 1 else None
-        # (the names carry further template arguments after S: counting / profiling / one-length flags)
-        prefix = cfg["kernel_prefix"] if args.kernel == 0 else {
-            1: "beam_generic_kernel", 2: "beam_wave_kernel<5, 6, 2, %d" % (4 if cfg["crf"] else 0),
-            3: "beam_wave_kernel<5, 8, 1, %d" % (4 if cfg["crf"] else 0), 4: "beam_lane_kernel<5, 2"}[args.kernel]
-        traffic, traffic_note = pmc_traffic(prefix) if default_shape else (None, None)
-        props = torch.cuda.get_device_properties(dev)
-        simds = props.multi_processor_count * 4
-        rpw = 1 if args.kernel in (1, 3) else 2
-        # outside the timed region: the tie instrument on the same batch (include/fcd.h)
-        if cfg["crf"]:
-            amb = fcd.crf_beam_search_batch_raw(x, init, beam, thr, count_ambiguous=True).cpu().ambiguous
-        else:
-            amb = fcd.beam_search_batch_raw(x, beam, thr, True, count_ambiguous=True).cpu().ambiguous
-        ties = {"reads_with_gt20_candidate_kept_tie": int((amb[:, 0] > 0).sum()),
-                "reads_with_result_changing_tie": int((amb[:, 1] > 0).sum()),
-                "reads_with_both": int(((amb[:, 0] > 0) & (amb[:, 1] > 0)).sum()),
-                "note": "a read with either counter at 0 decodes the same under any order of equal probabilities; on "
-                        "the others the kernels follow the restated order of Rust 1.78's sort_unstable_by "
-                        "(FCD_TIE_PDQ178, csrc/pdq178.h; tests/test_gpu_fullsize.py::test_config2_tie_instrument)"}
-        # outside the timed region (N = 1): the same launches under the OTHER selectable order of equal probabilities,
-        # so that one line from one box shows what the default order (Rust 1.78's) costs against the stable one
-        other_order = None
-        if world == 1:
-            mine_order = fcd.tie_order()
-            try:
-                alt = "stable" if mine_order == "pdq178" else "pdq178"
-                fcd.set_tie_order(alt)
-                for _ in range(2):
-                    search(0)
-                torch.cuda.synchronize()
-                handles[0].timing_reset()
-                for _ in range(args.steps):
-                    search(0)
-                torch.cuda.synchronize()
-                alt_ms, alt_calls = handles[0].timing_mean_ms()
-                other_order = {"tie_order": alt, "kernel_ms": alt_ms, "launches_timed": alt_calls,
-                               "reads_per_s_by_kernel_time": B / (alt_ms * 1e-3),
-                               "this_order_reads_per_s_by_kernel_time": B / ((single_ms or k_ms) * 1e-3)}
-            except Exception as e:  # never at the price of the bench line
-                other_order = {"error": str(e)}
-            finally:
-                fcd.set_tie_order(mine_order)
-        pdq = "1" if fcd.tie_order() == "pdq178" else "0"
-        uni = "1"  # (bench batches have one length: the UNI instantiation)
-        symbol = {2: "beam_wave_kernelILi5ELi6ELi2ELi0ELb0ELb0ELb%sELb0ELb%sE" % (uni, pdq),
-                  3: "beam_lane_kernelILi5ELi2ELb0ELb0ELb%sE" % pdq,
-                  4: "beam_wave_kernelILi5ELi6ELi2ELi4ELb0ELb0ELb%sELb0ELb%sE" % (uni, pdq)}.get(args.config)
-        occupancy = kernel_occupancy(symbol) if (symbol and args.kernel == 0) else None
-        vit = viterbi_roofline(fcd, torch, dev) if not args.no_viterbi else None
-        vit16 = viterbi_roofline(fcd, torch, dev, half=True) if not args.no_viterbi else None
-        valu = valu_issue_roofline(prefix, k_eff_ms, simds) if default_shape else None
-        e2e = None
-        if world == 1 and not args.no_e2e and args.streams == 1:
-            e2e = e2e_leg(fcd, cfg, x_host, init_host, rc)
+        cpu = e2e = vit = vit16 = ties = other_order = roofline = None  # (measured with --full only)
+        if args.full:
+            # posteriors in, u8 label + u32 time out (CRF: the dense T*S*N figure)
+            bytes_per_read = T * N * 4 * (4 if cfg["crf"] else 1) + 5.0 * mean_L
+            # Overlapping steps (fcd_set_overlap): `k_ms` is a launch's duration WHILE it shares the chip with the launches of the
+            # other internal streams -- on average k_ms * steps / elapsed of them at once -- so the kernel's rate is a launch's
+            # bytes over its share of that time, k_ms / launches_in_flight = elapsed / steps.  One launch at a time: k_ms itself.
+            in_flight = k_ms * args.steps / (elapsed * 1e3) if overlap else 1.0
+            k_eff_ms = k_ms / in_flight if overlap else k_ms
+            achieved = B * bytes_per_read / (k_eff_ms * 1e-3) / 1e9
+            # the CPU leg (and its output cross-check) runs on rank 0 at N = 1 only, as the contract asks
+            cpu = cpu_baseline(cfg, x_host, init_host, rc.labels, rc.path, rc.out_len, args.cpu_seconds) if world == 1 else None
+            # (the names carry further template arguments after S: counting / profiling / one-length flags)
+            prefix = cfg["kernel_prefix"] if args.kernel == 0 else {
+                1: "beam_generic_kernel", 2: "beam_wave_kernel<5, 6, 2, %d" % (4 if cfg["crf"] else 0),
+                3: "beam_wave_kernel<5, 8, 1, %d" % (4 if cfg["crf"] else 0), 4: "beam_lane_kernel<5, 2"}[args.kernel]
+            traffic, traffic_note = pmc_traffic(prefix) if default_shape else (None, None)
+            props = torch.cuda.get_device_properties(dev)
+            simds = props.multi_processor_count * 4
+            rpw = 1 if args.kernel in (1, 3) else 2
+            # outside the timed region: the tie instrument on the same batch (include/fcd.h)
+            if cfg["crf"]:
+                amb = fcd.crf_beam_search_batch_raw(x, init, beam, thr, count_ambiguous=True).cpu().ambiguous
+            else:
+                amb = fcd.beam_search_batch_raw(x, beam, thr, True, count_ambiguous=True).cpu().ambiguous
+            ties = {"reads_with_gt20_candidate_kept_tie": int((amb[:, 0] > 0).sum()),
+                    "reads_with_result_changing_tie": int((amb[:, 1] > 0).sum()),
+                    "reads_with_both": int(((amb[:, 0] > 0) & (amb[:, 1] > 0)).sum()),
+                    "note": "a read with either counter at 0 decodes the same under any order of equal probabilities; on "
+                            "the others the kernels follow the restated order of Rust 1.78's sort_unstable_by "
+                            "(FCD_TIE_PDQ178, csrc/pdq178.h; tests/test_gpu_fullsize.py::test_config2_tie_instrument)"}
+            # outside the timed region (N = 1): the same launches under the OTHER selectable order of equal probabilities,
+            # so that one line from one box shows what the default order (Rust 1.78's) costs against the stable one
+            other_order = None
+            if world == 1:
+                mine_order = fcd.tie_order()
+                try:
+                    alt = "stable" if mine_order == "pdq178" else "pdq178"
+                    fcd.set_tie_order(alt)
+                    for _ in range(2):
+                        search(0)
+                    torch.cuda.synchronize()
+                    handles[0].timing_reset()
+                    for _ in range(args.steps):
+                        search(0)
+                    torch.cuda.synchronize()
+                    alt_ms, alt_calls = handles[0].timing_mean_ms()
+                    other_order = {"tie_order": alt, "kernel_ms": alt_ms, "launches_timed": alt_calls,
+                                   "reads_per_s_by_kernel_time": B / (alt_ms * 1e-3),
+                                   "this_order_reads_per_s_by_kernel_time": B / ((single_ms or k_ms) * 1e-3)}
+                except Exception as e:  # never at the price of the bench line
+                    other_order = {"error": str(e)}
+                finally:
+                    fcd.set_tie_order(mine_order)
+            pdq = "1" if fcd.tie_order() == "pdq178" else "0"
+            uni = "1"  # (bench batches have one length: the UNI instantiation)
+            symbol = {2: "beam_wave_kernelILi5ELi6ELi2ELi0ELb0ELb0ELb%sELb0ELb%sE" % (uni, pdq),
+                      3: "beam_lane_kernelILi5ELi2ELb0ELb0ELb%sE" % pdq,
+                      4: "beam_wave_kernelILi5ELi6ELi2ELi4ELb0ELb0ELb%sELb0ELb%sE" % (uni, pdq)}.get(args.config)
+            occupancy = kernel_occupancy(symbol) if (symbol and args.kernel == 0) else None
+            vit = viterbi_roofline(fcd, torch, dev) if not args.no_viterbi else None
+            vit16 = viterbi_roofline(fcd, torch, dev, half=True) if not args.no_viterbi else None
+            valu = valu_issue_roofline(prefix, k_eff_ms, simds) if default_shape else None
+            e2e = None
+            if world == 1 and not args.no_e2e and args.streams == 1:
+                e2e = e2e_leg(fcd, cfg, x_host, init_host, rc)
+            roofline = {
+                "bound": "hbm",
+                "achieved": achieved,
+                "peak": HBM_PEAK_GBS,
+                "unit": "GB/s",
+                "frac": achieved / HBM_PEAK_GBS,
+                "traffic": traffic,
+                "traffic_source": traffic_note,
+                "kernel": "beam search kernel, %.3f ms per launch (HIP events)%s, %d reads x %.0f "
+                          "algorithmic B/read" % (k_ms, " with %.2f launches in flight on average = %.3f ms of the chip per launch"
+                                                  % (in_flight, k_eff_ms) if overlap else "", B, bytes_per_read),
+                "kernel_ms": k_ms, "launches_timed": k_calls, "launches_in_flight": in_flight,
+                # The search is a serial chain of T dependent steps per read: it is bound by instruction
+                # issue, not by HBM (SURVEY.md finding 5) -- priced here against the VALU issue peak.
+                "secondary_bound": valu if valu is not None else {
+                    "bound": "valu_issue", "achieved": None, "peak": simds * 2.4e9 / 2.0,
+                    "note": "no SQ counter summary of this kernel / shape on the current kernel sources under profiles/"},
+                # --overlap: `kernel_ms` is a launch's duration while it shares the chip with the launches of the other
+                # internal streams; what the chip sustains is a launch per `sustained_ms_per_launch`
+                "overlap": None if not overlap else {
+                    "streams": overlap, "sustained_ms_per_launch": elapsed / args.steps * 1e3,
+                    "achieved_one_launch_at_a_time": B * bytes_per_read / (single_ms * 1e-3) / 1e9 if single_ms else None,
+                    "single_launch_ms": single_ms,
+                    "single_launch_reads_per_s": B / (single_ms * 1e-3) if single_ms else None},
+                "wavefronts_per_simd": B / rpw / simds,
+                # (what the instantiation RESERVES: registers, LDS and the resident wavefronts per SIMD they allow)
+                "occupancy": occupancy,
+                "step_latency_us": (single_ms or k_ms) * 1e3 / T,  # (of a launch alone)
+            }
         out = {
             "metric": "reads/s (T=4000, N=5, beam=%d)" % beam,
             "value": world * B * args.steps / elapsed,
@@ -973,35 +1047,8 @@ def main():
                 "tie_order": fcd.tie_order(),  # include/fcd.h FCD_TIE_*: pdq178 = Rust 1.78's sort_unstable_by (default)
                 "other_tie_order": other_order,
             },
-            "roofline": {
-                "bound": "hbm",
-                "achieved": achieved,
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS,
-                "traffic": traffic,
-                "traffic_source": traffic_note,
-                "kernel": "beam search kernel, %.3f ms per launch (HIP events)%s, %d reads x %.0f "
-                          "algorithmic B/read" % (k_ms, " with %.2f launches in flight on average = %.3f ms of the chip per launch"
-                                                  % (in_flight, k_eff_ms) if overlap else "", B, bytes_per_read),
-                "kernel_ms": k_ms, "launches_timed": k_calls, "launches_in_flight": in_flight,
-                # The search is a serial chain of T dependent steps per read: it is bound by instruction
-                # issue, not by HBM (SURVEY.md finding 5) -- priced here against the VALU issue peak.
-                "secondary_bound": valu if valu is not None else {
-                    "bound": "valu_issue", "achieved": None, "peak": simds * 2.4e9 / 2.0,
-                    "note": "no SQ counter summary of this kernel / shape on the current kernel sources under profiles/"},
-                # --overlap: `kernel_ms` is a launch's duration while it shares the chip with the launches of the other
-                # internal streams; what the chip sustains is a launch per `sustained_ms_per_launch`
-                "overlap": None if not overlap else {
-                    "streams": overlap, "sustained_ms_per_launch": elapsed / args.steps * 1e3,
-                    "achieved_one_launch_at_a_time": B * bytes_per_read / (single_ms * 1e-3) / 1e9 if single_ms else None,
-                    "single_launch_ms": single_ms,
-                    "single_launch_reads_per_s": B / (single_ms * 1e-3) if single_ms else None},
-                "wavefronts_per_simd": B / rpw / simds,
-                # (what the instantiation RESERVES: registers, LDS and the resident wavefronts per SIMD they allow)
-                "occupancy": occupancy,
-                "step_latency_us": (single_ms or k_ms) * 1e3 / T,  # (of a launch alone)
-            },
+            "full": args.full,
+            "roofline": roofline,
             "cpu_baseline": cpu,
             "e2e": e2e,
             "viterbi_roofline": vit,

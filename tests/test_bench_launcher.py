@@ -48,3 +48,35 @@ def test_viterbi_clock_note_reads_the_committed_summary():
     assert note is not None and "error" not in note, note
     assert 0.9 < note["events_over_rocprofv3"] < 1.1
     assert os.path.exists(os.path.join(bench.ROOT, note["source"]))
+
+
+def test_dump_outputs_is_fixed_masked_and_bounded(tmp_path):
+    """--dump-outputs: per-read arrays whole, (reads, positions) arrays on a fixed sample of reads with everything at or past
+    a read's out_len set to -1 (so that what a step leaves there cannot make two identical results differ), under 64 MB."""
+    import numpy as np
+
+    import bench
+    from fast_ctc_decode_amd.api import BatchResult
+    rng = np.random.default_rng(3)
+    B, W = 4096, 4000
+    lens = rng.integers(0, W + 1, B).astype(np.int32)
+    labels = rng.integers(0, 5, (B, W)).astype(np.uint8)
+    path = rng.integers(0, W, (B, W)).astype(np.int32)
+    status = np.zeros(B, np.int32)
+    shapes = bench.dump_outputs(str(tmp_path / "a"), BatchResult(labels, path, lens, status))
+    assert shapes["out_len"] == [B] and shapes["labels"] == shapes["path"] == [bench.DUMP_READS, W]
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) < 64 << 20
+    got = {k: np.load(str(tmp_path / "a" / (k + ".npy"))) for k in shapes}
+    assert got["labels"].dtype == np.float32 and got["path"].dtype == np.float64 and got["out_len"].dtype == np.float64
+    assert np.array_equal(got["out_len"], lens)
+    # the same valid prefixes under different leftovers past out_len give the same files
+    junk = np.arange(W)[None, :] >= lens[:, None]
+    labels2, path2 = labels.copy(), path.copy()
+    labels2[junk] = 7
+    path2[junk] = -5
+    bench.dump_outputs(str(tmp_path / "b"), BatchResult(labels2, path2, lens, status))
+    for k in shapes:
+        assert np.array_equal(got[k], np.load(str(tmp_path / "b" / (k + ".npy")))), k
+    pick = np.sort(np.random.default_rng(0).choice(B, bench.DUMP_READS, replace=False))
+    assert np.array_equal(got["labels"] == -1, np.arange(W)[None, :] >= lens[pick, None])
+    assert np.array_equal(got["path"][got["path"] != -1], path[pick][np.arange(W)[None, :] < lens[pick, None]])
