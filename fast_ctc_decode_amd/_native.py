@@ -216,7 +216,7 @@ class Handle:
                 "no CPU fallback" % (device, rc))
         self.device = int(device)
         self.overlap = 0       # set_overlap
-        self._inflight = []    # tensors of overlapping calls not joined yet (api._torch_call)
+        self._inflight = []    # tensors of overlapping calls not joined yet (hold_in_flight)
 
     def check(self, rc):
         if rc != OK:
@@ -249,6 +249,15 @@ class Handle:
             self._inflight = []  # (later work on that stream is ordered behind them: the caching allocator may reuse them)
         else:
             self.check(self.lib.fcd_overlap_join_stream(self.ptr, C.c_void_p(stream_ptr)))
+
+    def hold_in_flight(self, *tensors):
+        """After a device call under set_overlap: the call may still run on an internal stream when these tensors lose
+        their last reference -- the handle keeps them until the next overlap_join() (BatchResult.cpu() joins by itself).
+        A caller that never joins: past 256 calls the current stream waits for them, and they go."""
+        if self.overlap:
+            self._inflight.append(tensors)
+            if len(self._inflight) > 256:
+                self.overlap_join()
 
     def overlap_last_slot(self):
         """The internal stream the latest overlapping call went to (-1: none); see overlap_join_slot."""

@@ -474,10 +474,7 @@ def beam_search_duplex_batch_raw(network_outputs_1, network_outputs_2, envelopes
             C.byref(res)))
         r = BatchResult(labels, None, out_len, status, ambiguous=amb)
         r._handle, r._keep = h, keep
-        if h.overlap:  # (see _torch_call)
-            h._inflight.append((keep, labels, out_len, status, amb))
-            if len(h._inflight) > 256:
-                h.overlap_join()
+        h.hold_in_flight(keep, labels, out_len, status, amb)
         return r
     x1 = _stack_host(network_outputs_1, 3)
     x2 = _stack_host(network_outputs_2, 3)
@@ -671,10 +668,7 @@ def crf_beam_search_duplex_batch_raw(network_outputs_1, init_states_1, network_o
             int(env.shape[1]), int(beam_size), float(beam_cut_threshold), int(mode), C.byref(res)))
         r = BatchResult(labels, None, out_len, status, ambiguous=amb)
         r._handle, r._keep = h, keep
-        if h.overlap:  # (see _torch_call)
-            h._inflight.append((keep, labels, out_len, status, amb))
-            if len(h._inflight) > 256:
-                h.overlap_join()
+        h.hold_in_flight(keep, labels, out_len, status, amb)
         return r
     x1 = _stack_host(network_outputs_1, 4)
     x2 = _stack_host(network_outputs_2, 4)
@@ -878,12 +872,7 @@ def _torch_call(fn_name, x, crf, lengths, extra_args, want_qual=False, want_path
     r = BatchResult(labels, path, out_len, status, qual, amb)
     r._handle = h
     r._keep = (x, lengths)
-    if h.overlap:
-        # Handle.set_overlap: the call may still run on an internal stream when these tensors lose their last
-        # reference -- the handle keeps them until the next overlap_join() (BatchResult.cpu() joins by itself)
-        h._inflight.append((r._keep, labels, path, qual, out_len, status, amb))
-        if len(h._inflight) > 256:  # (a caller that never joins: bound what is kept -- the current stream waits, they go)
-            h.overlap_join()
+    h.hold_in_flight(r._keep, labels, path, qual, out_len, status, amb)
     return r
 
 

@@ -154,28 +154,6 @@ ResultDesc to_desc(const fcd_result *o) {
     return ResultDesc{o->labels, o->path, o->qual, o->out_len, o->status, o->out_stride, o->ambiguous};
 }
 
-// Brackets the kernel launches of one search call with HIP events on the launch stream.
-struct Timer {
-    fcd_handle *h;
-    int slot;
-    hipStream_t st;
-    explicit Timer(fcd_handle *hh, hipStream_t on = nullptr, bool given = false) : h(hh), st(given ? on : hh->stream) {
-        slot = (int)(h->n_timed % fcd_handle::kTimingRing);
-        if ((int)h->ev0.size() <= slot) {
-            hipEvent_t a = nullptr, b = nullptr;
-            (void)hipEventCreate(&a);
-            (void)hipEventCreate(&b);
-            h->ev0.push_back(a);
-            h->ev1.push_back(b);
-        }
-        (void)hipEventRecord(h->ev0[slot], st);
-    }
-    void stop() {
-        (void)hipEventRecord(h->ev1[slot], st);
-        h->n_timed++;
-    }
-};
-
 int64_t workspace_budget(fcd_handle *h) {
     if (h->ws_limit > 0) return h->ws_limit;
     size_t free_b = 0, total_b = 0;
@@ -203,121 +181,171 @@ int overlap_join(fcd_handle *h, hipStream_t stream) {
     return FCD_OK;
 }
 
-// `S` (internal stream `own_slot`, or the handle's stream: -1) waits for every overlapping call in flight that writes any
-// of the output arrays of a call about to be enqueued on it; `mine` receives those arrays' address ranges.
-int overlap_order_behind(fcd_handle *h, hipStream_t S, int own_slot, const ResultDesc &o, int64_t n_reads,
-                         fcd_handle::Range mine[6], int *n_mine_out) {
-    int n_mine = 0;
-    auto add = [&](const void *ptr, size_t bytes) {
-        if (ptr && bytes) mine[n_mine++] = {reinterpret_cast<uintptr_t>(ptr), reinterpret_cast<uintptr_t>(ptr) + bytes};
-    };
-    const size_t rows = (size_t)n_reads * (size_t)o.out_stride;
-    add(o.labels, rows);
-    add(o.path, rows * 4);
-    add(o.qual, rows * 4);
-    add(o.out_len, (size_t)n_reads * 4);
-    add(o.status, (size_t)n_reads * 4);
-    add(o.ambiguous, (size_t)n_reads * 8);
-    *n_mine_out = n_mine;
-    for (int s = 0; s < fcd_handle::kMaxOverlap; ++s) {
-        if (!h->ov_stream[s] || !h->ov_used[s]) continue;
-        std::deque<fcd_handle::Flight> &fl = h->ov_flights[s];
-        while (!fl.empty() && hipEventQuery(fl.front().done) == hipSuccess) {  // finished calls go
-            h->ov_event_pool.push_back(fl.front().done);
-            fl.pop_front();
-        }
-        if (fl.empty()) {  // nothing in flight there any more
-            h->ov_used[s] = false;
-            continue;
-        }
-        if (s == own_slot) continue;  // (stream order)
-        // the YOUNGEST call in flight there that writes any of these arrays: the stream runs them in order
-        hipEvent_t wait_for = nullptr;
-        for (const fcd_handle::Flight &f : fl) {
-            bool clash = false;
-            for (int i = 0; i < f.n && !clash; ++i)
-                for (int k = 0; k < n_mine && !clash; ++k) clash = f.r[i].lo < mine[k].hi && mine[k].lo < f.r[i].hi;
-            if (clash) wait_for = f.done;
-        }
-        if (wait_for) FCD_HIP(h, hipStreamWaitEvent(S, wait_for, 0));
+// The stream, ordering, workspace and timing of one *_dev entry point; every entry point that enqueues work goes through
+// one, in this order:
+//   add()     the arrays the call reads or writes (result arrays, offsets: what an overlapping call may be writing)
+//   begin()   the stream: the handle's, or -- fcd_set_overlap, a call that may overlap -- the next internal stream, behind
+//             the handle's stream as it stands now.  Then ONE ordering rule: the stream waits for every overlapping call in
+//             flight that writes any of the add()ed arrays.  An exclusive call -- one that takes `arena` / `lnbuf` from
+//             their start -- waits for every call in flight instead (they hold regions of both).
+//   arena() / lnbuf()  workspace, only after begin(): an overlapping call's region of the buffer (one per internal
+//             stream), or the whole buffer for an exclusive call.  Growing a buffer drains the internal streams first.
+//   time()    starts the call's timing (fcd_last_kernel_ms) on its stream; finish() stops it.
+//   finish()  an overlapping call counts as in flight from here on: its stream, the arrays it writes, an event behind it.
+//             Every error return after begin() records it too (the destructor): whatever reached the internal stream.
+class CallScope {
+  public:
+    hipStream_t stream;
+    int slot = -1;  // internal stream of an overlapping call, -1: the handle's stream
+
+    explicit CallScope(fcd_handle *h) : stream(h->stream), h_(h) {}
+    CallScope(const CallScope &) = delete;
+    CallScope &operator=(const CallScope &) = delete;
+    ~CallScope() {
+        if (slot < 0 || finished_) return;
+        const std::string err = h_->err;  // (the error the call returns stays the one reported)
+        (void)record();
+        h_->err = err;
     }
-    return FCD_OK;
-}
 
-// every entry point that writes an fcd_result in the handle's stream: behind the overlapping calls that write it too
-int overlap_order_writer(fcd_handle *h, const fcd_result *out, int64_t n_reads) {
-    bool any = false;
-    for (int s = 0; s < fcd_handle::kMaxOverlap; ++s) any = any || h->ov_used[s];
-    if (!any) return FCD_OK;
-    fcd_handle::Range mine[6];
-    int n_mine = 0;
-    return overlap_order_behind(h, h->stream, -1, to_desc(out), n_reads, mine, &n_mine);
-}
-
-// an entry point about to use the handle's arena from its start, in the handle's stream: behind every overlapping call in
-// flight (they hold regions of it) -- which also covers the calls that write its output arrays
-int arena_exclusive(fcd_handle *h, const fcd_result *, int64_t) { return overlap_join(h, h->stream); }
-
-// The stream of the next overlapping call: behind the handle's stream as it stands now, and behind every call in flight
-// that writes any of this call's output arrays.
-int overlap_begin(fcd_handle *h, const ResultDesc &o, int64_t n_reads, int *slot_out) {
-    const int n = std::min(h->overlap_n, (int)fcd_handle::kMaxOverlap);
-    if (!h->ov_fork) FCD_HIP(h, hipEventCreateWithFlags(&h->ov_fork, hipEventDisableTiming));
-    for (int s = 0; s < n; ++s) {
-        if (h->ov_stream[s]) continue;
-        // The internal streams are created in the HIGH priority class: the runtime hands out the hardware queues of
-        // a class separately, so they get queues of their own whatever the process's other streams occupy (normal
-        // streams beyond GPU_MAX_HW_QUEUES = 4 share queues, and kernels that share a queue run one after the other:
-        // 262 k reads/s instead of 320 k on BASELINE config 3, profiles/r06v_*).  FCD_OVERLAP_PRIORITY=normal|low: A/B.
-        const char *pr = getenv("FCD_OVERLAP_PRIORITY");
-        int least = 0, greatest = 0;
-        const bool ranged = hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess;
-        if (ranged && (!pr || !strcmp(pr, "high") || !strcmp(pr, "low")))
-            FCD_HIP(h, hipStreamCreateWithPriority(&h->ov_stream[s], hipStreamNonBlocking, (pr && !strcmp(pr, "low")) ? least : greatest));
-        else
-            FCD_HIP(h, hipStreamCreateWithFlags(&h->ov_stream[s], hipStreamNonBlocking));
-        FCD_HIP(h, hipEventCreateWithFlags(&h->ov_last[s], hipEventDisableTiming));
+    void add(const void *ptr, size_t bytes) {
+        if (ptr && bytes && f_.n < fcd_handle::kMaxRanges)
+            f_.r[f_.n++] = {reinterpret_cast<uintptr_t>(ptr), reinterpret_cast<uintptr_t>(ptr) + bytes};
     }
-    const int slot = (int)(h->ov_seq % (uint64_t)n);
-    hipStream_t S = h->ov_stream[slot];
-    FCD_HIP(h, hipEventRecord(h->ov_fork, h->stream));
-    FCD_HIP(h, hipStreamWaitEvent(S, h->ov_fork, 0));
-    fcd_handle::Range mine[6];
-    int n_mine = 0;
-    int rc = overlap_order_behind(h, S, slot, o, n_reads, mine, &n_mine);
-    if (rc) return rc;
-    *slot_out = slot;
-    return FCD_OK;
-}
-
-// ... and the call has been enqueued on internal stream `slot`: from here on it counts as in flight (not earlier: a
-// call that has to grow a buffer waits for the others in between, which forgets what was in flight)
-int overlap_end(fcd_handle *h, int slot, const ResultDesc &o, int64_t n_reads) {
-    FCD_HIP(h, hipEventRecord(h->ov_last[slot], h->ov_stream[slot]));
-    fcd_handle::Flight f;
-    if (!h->ov_event_pool.empty()) {
-        f.done = h->ov_event_pool.back();
-        h->ov_event_pool.pop_back();
-    } else {
-        FCD_HIP(h, hipEventCreateWithFlags(&f.done, hipEventDisableTiming));
+    void add(const ResultDesc &o, int64_t n_reads) {
+        const size_t rows = (size_t)n_reads * (size_t)o.out_stride;
+        add(o.labels, rows);
+        add(o.path, rows * 4);
+        add(o.qual, rows * 4);
+        add(o.out_len, (size_t)n_reads * 4);
+        add(o.status, (size_t)n_reads * 4);
+        add(o.ambiguous, (size_t)n_reads * 8);
     }
-    FCD_HIP(h, hipEventRecord(f.done, h->ov_stream[slot]));
-    auto add = [&](const void *ptr, size_t bytes) {
-        if (ptr && bytes && f.n < 6) f.r[f.n++] = {reinterpret_cast<uintptr_t>(ptr), reinterpret_cast<uintptr_t>(ptr) + bytes};
-    };
-    const size_t rows = (size_t)n_reads * (size_t)o.out_stride;
-    add(o.labels, rows);
-    add(o.path, rows * 4);
-    add(o.qual, rows * 4);
-    add(o.out_len, (size_t)n_reads * 4);
-    add(o.status, (size_t)n_reads * 4);
-    add(o.ambiguous, (size_t)n_reads * 8);
-    h->ov_flights[slot].push_back(f);
-    h->ov_used[slot] = true;
-    h->ov_last_slot = slot;
-    h->ov_seq++;
-    return FCD_OK;
-}
+
+    int begin(bool may_overlap, bool exclusive) {
+        fcd_handle *h = h_;
+        if (may_overlap && h->overlap_n >= 2) {
+            n_ = std::min(h->overlap_n, (int)fcd_handle::kMaxOverlap);
+            if (!h->ov_fork) FCD_HIP(h, hipEventCreateWithFlags(&h->ov_fork, hipEventDisableTiming));
+            for (int s = 0; s < n_; ++s) {
+                if (h->ov_stream[s]) continue;
+                // The internal streams are created in the HIGH priority class: the runtime hands out the hardware queues of
+                // a class separately, so they get queues of their own whatever the process's other streams occupy (normal
+                // streams beyond GPU_MAX_HW_QUEUES = 4 share queues, and kernels that share a queue run one after the other:
+                // 262 k reads/s instead of 320 k on BASELINE config 3, profiles/r06v_*).  FCD_OVERLAP_PRIORITY=normal|low: A/B.
+                const char *pr = getenv("FCD_OVERLAP_PRIORITY");
+                int least = 0, greatest = 0;
+                const bool ranged = hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess;
+                if (ranged && (!pr || !strcmp(pr, "high") || !strcmp(pr, "low")))
+                    FCD_HIP(h, hipStreamCreateWithPriority(&h->ov_stream[s], hipStreamNonBlocking, (pr && !strcmp(pr, "low")) ? least : greatest));
+                else
+                    FCD_HIP(h, hipStreamCreateWithFlags(&h->ov_stream[s], hipStreamNonBlocking));
+                FCD_HIP(h, hipEventCreateWithFlags(&h->ov_last[s], hipEventDisableTiming));
+            }
+            const int s = (int)(h->ov_seq % (uint64_t)n_);
+            FCD_HIP(h, hipEventRecord(h->ov_fork, h->stream));
+            FCD_HIP(h, hipStreamWaitEvent(h->ov_stream[s], h->ov_fork, 0));
+            slot = s;
+            stream = h->ov_stream[s];
+        } else if (exclusive) {
+            exclusive_ = true;
+            return overlap_join(h, stream);
+        }
+        for (int s = 0; s < fcd_handle::kMaxOverlap; ++s) {
+            if (!h->ov_stream[s] || !h->ov_used[s]) continue;
+            std::deque<fcd_handle::Flight> &fl = h->ov_flights[s];
+            while (!fl.empty() && hipEventQuery(fl.front().done) == hipSuccess) {  // finished calls go
+                h->ov_event_pool.push_back(fl.front().done);
+                fl.pop_front();
+            }
+            if (fl.empty()) {  // nothing in flight there any more
+                h->ov_used[s] = false;
+                continue;
+            }
+            if (s == slot) continue;  // (stream order)
+            // the YOUNGEST call in flight there that writes any of these arrays: the stream runs them in order
+            hipEvent_t wait_for = nullptr;
+            for (const fcd_handle::Flight &f : fl) {
+                bool clash = false;
+                for (int i = 0; i < f.n && !clash; ++i)
+                    for (int k = 0; k < f_.n && !clash; ++k) clash = f.r[i].lo < f_.r[k].hi && f_.r[k].lo < f.r[i].hi;
+                if (clash) wait_for = f.done;
+            }
+            if (wait_for) FCD_HIP(h, hipStreamWaitEvent(stream, wait_for, 0));
+        }
+        return FCD_OK;
+    }
+
+    int regions() const { return slot >= 0 ? n_ : 1; }  // how many calls share a workspace buffer
+    int arena(size_t need, char **out) { return region(&h_->arena, &h_->arena_bytes, &h_->arena_region, need, out); }
+    int lnbuf(size_t need, char **out) { return region(&h_->lnbuf, &h_->lnbuf_bytes, &h_->lnbuf_region, need, out); }
+
+    void time() {
+        fcd_handle *h = h_;
+        timer_ = (int)(h->n_timed % fcd_handle::kTimingRing);
+        if ((int)h->ev0.size() <= timer_) {
+            hipEvent_t a = nullptr, b = nullptr;
+            (void)hipEventCreate(&a);
+            (void)hipEventCreate(&b);
+            h->ev0.push_back(a);
+            h->ev1.push_back(b);
+        }
+        (void)hipEventRecord(h->ev0[timer_], stream);
+    }
+
+    int finish() {
+        finished_ = true;
+        if (timer_ >= 0) {
+            (void)hipEventRecord(h_->ev1[timer_], stream);
+            h_->n_timed++;
+        }
+        return slot >= 0 ? record() : FCD_OK;
+    }
+
+  private:
+    fcd_handle *h_;
+    int n_ = 1;  // internal streams in use (an overlapping call)
+    bool exclusive_ = false, finished_ = false;
+    int timer_ = -1;
+    fcd_handle::Flight f_;  // the add()ed arrays; `done` once recorded
+
+    int region(void **buf, size_t *bytes, size_t *region_bytes, size_t need, char **out) {
+        if (slot < 0) {
+            if (!exclusive_) return fail(h_, FCD_E_INVALID, "internal error: workspace taken outside an exclusive call");
+            int rc = ensure(h_, buf, bytes, need);
+            if (rc) return rc;
+            *out = static_cast<char *>(*buf);
+            return FCD_OK;
+        }
+        need = (need + 255) & ~(size_t)255;
+        if (need > *region_bytes || *bytes < (size_t)n_ * *region_bytes) {
+            int rc = overlap_drain(h_);  // (calls in flight count on the old regions)
+            if (rc) return rc;
+            rc = ensure(h_, buf, bytes, (size_t)n_ * need);
+            if (rc) return rc;
+            *region_bytes = need;
+        }
+        *out = static_cast<char *>(*buf) + (size_t)slot * *region_bytes;
+        return FCD_OK;
+    }
+
+    int record() {
+        fcd_handle *h = h_;
+        FCD_HIP(h, hipEventRecord(h->ov_last[slot], stream));
+        if (!h->ov_event_pool.empty()) {
+            f_.done = h->ov_event_pool.back();
+            h->ov_event_pool.pop_back();
+        } else {
+            FCD_HIP(h, hipEventCreateWithFlags(&f_.done, hipEventDisableTiming));
+        }
+        FCD_HIP(h, hipEventRecord(f_.done, stream));
+        h->ov_flights[slot].push_back(f_);
+        h->ov_used[slot] = true;
+        h->ov_last_slot = slot;
+        h->ov_seq++;
+        return FCD_OK;
+    }
+};
 
 // Shared driver of search::beam_search and search::crf_beam_search on device buffers.
 int beam_dev(fcd_handle *h, const fcd_batch *in, const BeamArgs &a, int kernel,
@@ -420,6 +448,8 @@ int beam_dev(fcd_handle *h, const fcd_batch *in, const BeamArgs &a, int kernel,
         ar.first_stride = first_stride;
         return ar;
     };
+    CallScope sc(h);
+    sc.add(o, d.n_reads);
     if (two_pass) {
         // ---- slabs from the device-side pool (slab_pool.h): the arena is sized by what the chip holds at once, one
         // launch takes the whole job, and calls on the overlap streams share it ----
@@ -479,11 +509,9 @@ int beam_dev(fcd_handle *h, const fcd_batch *in, const BeamArgs &a, int kernel,
             g.p1 = (int)p1;
             g.p2 = (int)p2;
         }
-        int32_t *d_counter = nullptr;
-        if (retry_needed) {  // the overflow counters have their own small allocation: one per call, 64 calls round
+        if (retry_needed) {  // the overflow counters have their own small allocation: a word per stream (kMaxOverlap + 1 <= 64)
             rc = ensure(h, &h->retry_counter, &h->retry_counter_bytes, 256);
             if (rc) return rc;
-            d_counter = reinterpret_cast<int32_t *>(h->retry_counter) + (h->ov_seq & 63);
             if (!h->retry_host) {  // (page-locked: the copy back is a DMA nobody waits for)
                 if (hipHostMalloc(&h->retry_host, 64, hipHostMallocDefault) != hipSuccess) h->retry_host = nullptr;
                 if (h->retry_host && hipEventCreateWithFlags(&h->retry_ev, hipEventDisableTiming) != hipSuccess) {
@@ -502,16 +530,11 @@ int beam_dev(fcd_handle *h, const fcd_batch *in, const BeamArgs &a, int kernel,
         const size_t first_region = ((size_t)g.p1 * wave_bytes + 255) & ~(size_t)255;
         unsigned long long *const ring1 = reinterpret_cast<unsigned long long *>(h->pool_ctl);
         unsigned long long *const ring2 = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(h->pool_ctl) + slab_pool::bytes(g.p1));
-        // which stream: the handle's, or -- fcd_set_overlap -- the next internal one, behind the handle's stream as it
-        // stands now and behind whatever still writes this call's outputs
-        hipStream_t S = h->stream;
-        int slot = -1;
-        if (h->overlap_n >= 2) {
-            rc = overlap_begin(h, o, d.n_reads, &slot);
-            if (rc) return rc;
-            S = h->ov_stream[slot];
-        }
-        Timer tm(h, S, true);
+        // (the pool is not a region: calls on every stream share it, after its initialisation above on the handle's stream)
+        rc = sc.begin(true, false);
+        if (rc) return rc;
+        const hipStream_t S = sc.stream;
+        sc.time();
         WaveArena ar = wave_arena(base, (int64_t)g.p1 * rpw, cap_nodes);
         ar.pool = ring1;
         FCD_HIP(h, launch_beam_lane(d, 0, d.n_reads, args, ar, o, S));
@@ -520,6 +543,8 @@ int beam_dev(fcd_handle *h, const fcd_batch *in, const BeamArgs &a, int kernel,
             // this pass that finds no slab free waits for one (the pool is a queue), so ONE launch finishes the job
             // whatever happened in the first pass -- with nothing to do it is n wavefronts that read one status word and
             // leave.  Nobody waits for it: this entry point stays enqueue-only.
+            // (overflow counter: word 0 for the handle's stream, slot + 1 for an internal one -- a stream's calls run in order)
+            int32_t *const d_counter = reinterpret_cast<int32_t *>(h->retry_counter) + (sc.slot + 1);
             WaveArena rr = wave_arena(base + first_region, g.p2, cap_worst);
             rr.pool = ring2;
             rr.retry_counter = d_counter;
@@ -533,60 +558,32 @@ int beam_dev(fcd_handle *h, const fcd_batch *in, const BeamArgs &a, int kernel,
                 h->retry_n = d.n_reads;
             }
         }
-        tm.stop();
-        if (slot >= 0) return overlap_end(h, slot, o, d.n_reads);
-        h->ov_seq++;
-        return FCD_OK;
+        return sc.finish();
     }
-    // fcd_set_overlap: the call goes to the next internal stream and has a region of the arena to itself (calls on the
-    // same internal stream follow one another, so do their uses of its region)
-    const int regions = h->overlap_n >= 2 ? std::min(h->overlap_n, (int)fcd_handle::kMaxOverlap) : 1;
-    int64_t chunk = std::max<int64_t>(1, budget / regions / (int64_t)per_read);
-    chunk = std::min<int64_t>(chunk, d.n_reads);
-    size_t region = (size_t)chunk * per_read;
-    hipStream_t S = h->stream;
-    int slot = -1;
-    if (regions > 1) {
-        region = (region + 255) & ~(size_t)255;
-        if (region > h->arena_region || h->arena_bytes < (size_t)regions * h->arena_region) {
-            rc = overlap_drain(h);  // (calls in flight count on the old regions)
-            if (rc) return rc;
-            rc = ensure(h, &h->arena, &h->arena_bytes, (size_t)regions * region);
-            if (rc) return rc;
-            h->arena_region = region;
-        }
-        rc = overlap_begin(h, o, d.n_reads, &slot);
-        if (rc) return rc;
-        S = h->ov_stream[slot];
-    } else {
-        rc = arena_exclusive(h, out, d.n_reads);
-        if (rc) return rc;
-        rc = ensure(h, &h->arena, &h->arena_bytes, region);
-        if (rc) return rc;
-    }
-    char *const abase = reinterpret_cast<char *>(h->arena) + (slot >= 0 ? (size_t)slot * h->arena_region : 0);
-
-    Timer tm(h, S, true);
+    // the arena: a region of it per internal stream (calls on the same internal stream follow one another, so do their
+    // uses of its region), or all of it in stream order
+    rc = sc.begin(true, true);
+    if (rc) return rc;
+    const hipStream_t S = sc.stream;
+    const int64_t chunk = std::min<int64_t>(std::max<int64_t>(1, budget / sc.regions() / (int64_t)per_read), d.n_reads);
+    char *abase = nullptr;
+    rc = sc.arena((size_t)chunk * per_read, &abase);
+    if (rc) return rc;
+    sc.time();
     for (int64_t begin = 0; begin < d.n_reads; begin += chunk) {
         const int64_t n = std::min<int64_t>(chunk, d.n_reads - begin);
-        hipError_t e;
         if (use_wave || use_lane) {
             const WaveArena ar = wave_arena(abase, chunk, cap_nodes);
-            e = use_lane ? launch_beam_lane(d, begin, n, args, ar, o, S) : launch_beam_wave(d, begin, n, args, ar, o, S);
-            FCD_HIP(h, e);
-            continue;
+            FCD_HIP(h, use_lane ? launch_beam_lane(d, begin, n, args, ar, o, S) : launch_beam_wave(d, begin, n, args, ar, o, S));
         } else {
             GenericArena ar;
             ar.cap_nodes = cap_nodes;
             ar.rec = reinterpret_cast<int4 *>(abase);
             ar.rows = reinterpret_cast<int32_t *>(abase + (size_t)chunk * cap_nodes * sizeof(int4));
-            e = launch_beam_generic(d, begin, n, args, ar, o, S);
+            FCD_HIP(h, launch_beam_generic(d, begin, n, args, ar, o, S));
         }
-        FCD_HIP(h, e);
     }
-    tm.stop();
-    if (slot >= 0) return overlap_end(h, slot, o, d.n_reads);
-    return FCD_OK;
+    return sc.finish();
 }
 
 // ---- host staging -------------------------------------------------------------------------
@@ -932,12 +929,13 @@ int fcd_viterbi_search_dev(fcd_handle *h, const fcd_batch *in, int collapse_repe
     if (rc) return rc;
     if (in->n_reads == 0) return FCD_OK;
     FCD_DEVICE(h);
-    rc = overlap_order_writer(h, out, in->n_reads);
+    CallScope sc(h);
+    sc.add(to_desc(out), in->n_reads);
+    rc = sc.begin(false, false);
     if (rc) return rc;
-    Timer tm(h);
-    FCD_HIP(h, launch_viterbi(to_desc(in, false), collapse_repeats, to_desc(out), h->stream));
-    tm.stop();
-    return FCD_OK;
+    sc.time();
+    FCD_HIP(h, launch_viterbi(to_desc(in, false), collapse_repeats, to_desc(out), sc.stream));
+    return sc.finish();
 }
 
 int fcd_beam_search_dev(fcd_handle *h, const fcd_batch *in, int64_t beam_size,
@@ -1006,12 +1004,13 @@ int fcd_crf_greedy_search_dev(fcd_handle *h, const fcd_batch *in, const float *i
     if (!init || n_init < 1) return fail(h, FCD_E_INVALID, "init_state missing");
     if (in->n_reads == 0) return FCD_OK;
     FCD_DEVICE(h);
-    rc = overlap_order_writer(h, out, in->n_reads);
+    CallScope sc(h);
+    sc.add(to_desc(out), in->n_reads);
+    rc = sc.begin(false, false);
     if (rc) return rc;
-    Timer tm(h);
-    FCD_HIP(h, launch_crf_greedy(to_desc(in, true), init, n_init, init_stride, to_desc(out), h->stream));
-    tm.stop();
-    return FCD_OK;
+    sc.time();
+    FCD_HIP(h, launch_crf_greedy(to_desc(in, true), init, n_init, init_stride, to_desc(out), sc.stream));
+    return sc.finish();
 }
 
 namespace {
@@ -1058,32 +1057,18 @@ int duplex_dev(fcd_handle *h, const fcd_batch *in1, const fcd_batch *in2, const 
     // a region of the log-space buffer and of the arena to itself (beam_dev)
     const int64_t T1 = std::max<int64_t>(in1->T, 1), T2 = std::max<int64_t>(in2->T, 1);
     const size_t n1 = (size_t)B * T1 * S * N, n2 = (size_t)B * T2 * S * N;
-    const int regions = h->overlap_n >= 2 ? std::min(h->overlap_n, (int)fcd_handle::kMaxOverlap) : 1;
-    size_t ln_need = (n1 + n2) * 4 + 256;
-    hipStream_t St = h->stream;
-    int slot = -1;
-    if (regions > 1) {
-        ln_need = (ln_need + 255) & ~(size_t)255;
-        if (ln_need > h->lnbuf_region || h->lnbuf_bytes < (size_t)regions * h->lnbuf_region) {
-            rc = overlap_drain(h);
-            if (rc) return rc;
-            rc = ensure(h, &h->lnbuf, &h->lnbuf_bytes, (size_t)regions * ln_need);
-            if (rc) return rc;
-            h->lnbuf_region = ln_need;
-        }
-        rc = overlap_begin(h, to_desc(out), B, &slot);
-        if (rc) return rc;
-        St = h->ov_stream[slot];
-    } else {
-        rc = arena_exclusive(h, out, B);  // (behind every overlapping call in flight: they hold regions of both buffers)
-        if (rc) return rc;
-        rc = ensure(h, &h->lnbuf, &h->lnbuf_bytes, ln_need);
-        if (rc) return rc;
-    }
-    float *ln1 = reinterpret_cast<float *>(reinterpret_cast<char *>(h->lnbuf) + (slot >= 0 ? (size_t)slot * h->lnbuf_region : 0));
+    CallScope sc(h);
+    sc.add(to_desc(out), B);
+    rc = sc.begin(true, true);
+    if (rc) return rc;
+    const hipStream_t St = sc.stream;
+    char *lnbase = nullptr;
+    rc = sc.lnbuf((n1 + n2) * 4 + 256, &lnbase);
+    if (rc) return rc;
+    float *ln1 = reinterpret_cast<float *>(lnbase);
     float *ln2 = ln1 + n1;
     int *d_width = reinterpret_cast<int *>(ln2 + n2);
-    Timer tm(h, St, true);
+    sc.time();
     FCD_HIP(h, launch_ln_convert(static_cast<const float *>(in1->post), in1->dtype, B, in1->T, S, N, in1->stride_read, in1->stride_t,
                                  is_crf ? in1->stride_s : 0, in1->stride_n, ln1, logadd_mode == FCD_LOGADD_LOGSUMEXP_GLIBC235, St));
     FCD_HIP(h, launch_ln_convert(static_cast<const float *>(in2->post), in2->dtype, B, in2->T, S, N, in2->stride_read, in2->stride_t,
@@ -1117,22 +1102,10 @@ int duplex_dev(fcd_handle *h, const fcd_batch *in1, const fcd_batch *in2, const 
                                   : (size_t)cap_nodes * (sizeof(int4) + 8 + (size_t)NL * 4 + (size_t)Wcap * 12) +
                                         (((size_t)(in2->T + 1) * 4 + 64 + 15) & ~(size_t)15);
     const int64_t budget = workspace_budget(h);
-    int64_t chunk = std::max<int64_t>(1, budget / regions / (int64_t)per_pair);
-    chunk = std::min<int64_t>(chunk, B);
-    if (regions > 1) {
-        const size_t region = ((size_t)chunk * per_pair + 255) & ~(size_t)255;
-        if (region > h->arena_region || h->arena_bytes < (size_t)regions * h->arena_region) {
-            rc = overlap_drain(h);
-            if (rc) return rc;
-            rc = ensure(h, &h->arena, &h->arena_bytes, (size_t)regions * region);
-            if (rc) return rc;
-            h->arena_region = region;
-        }
-    } else {
-        rc = ensure(h, &h->arena, &h->arena_bytes, (size_t)chunk * per_pair);
-        if (rc) return rc;
-    }
-    char *const abase = reinterpret_cast<char *>(h->arena) + (slot >= 0 ? (size_t)slot * h->arena_region : 0);
+    const int64_t chunk = std::min<int64_t>(std::max<int64_t>(1, budget / sc.regions() / (int64_t)per_pair), B);
+    char *abase = nullptr;
+    rc = sc.arena((size_t)chunk * per_pair, &abase);
+    if (rc) return rc;
 
     DuplexArgs a;
     a.ln1 = ln1; a.ln2 = ln2; a.T1cap = in1->T; a.T2cap = in2->T;
@@ -1170,9 +1143,7 @@ int duplex_dev(fcd_handle *h, const fcd_batch *in1, const fcd_batch *in2, const 
         const int64_t n = std::min<int64_t>(chunk, B - begin);
         FCD_HIP(h, slots ? launch_duplex_slots(a, begin, n, St) : launch_duplex(a, begin, n, St));
     }
-    tm.stop();
-    if (slot >= 0) return overlap_end(h, slot, to_desc(out), B);
-    return FCD_OK;
+    return sc.finish();
 }
 }  // namespace
 
@@ -1331,15 +1302,20 @@ int fcd_duplex_envelope_dev(fcd_handle *h, int64_t n_pairs,
     if (env_stride < T1cap) return fail(h, FCD_E_INVALID, "envelope shorter than read 1");
     band = std::min<int64_t>(band, 1 << 20);
     FCD_DEVICE(h);
-    // the DP is sized by the longest labellings actually present, not by the time axes
-    int rc = ensure(h, &h->lnbuf, &h->lnbuf_bytes, 256);
+    // the workspace from its start: behind every overlapping call in flight (the first bytes of `lnbuf` are scratch)
+    CallScope sc(h);
+    int rc = sc.begin(false, true);
     if (rc) return rc;
-    uint32_t *d_max = reinterpret_cast<uint32_t *>(h->lnbuf);
+    // the DP is sized by the longest labellings actually present, not by the time axes
+    char *scratch = nullptr;
+    rc = sc.lnbuf(256, &scratch);
+    if (rc) return rc;
+    uint32_t *d_max = reinterpret_cast<uint32_t *>(scratch);
     uint32_t h_max[2] = {0, 0};
-    FCD_HIP(h, hipMemsetAsync(d_max, 0, 8, h->stream));
-    FCD_HIP(h, launch_max_u32(len1, len2, n_pairs, d_max, h->stream));
-    FCD_HIP(h, hipMemcpyAsync(h_max, d_max, 8, hipMemcpyDeviceToHost, h->stream));
-    FCD_HIP(h, hipStreamSynchronize(h->stream));
+    FCD_HIP(h, hipMemsetAsync(d_max, 0, 8, sc.stream));
+    FCD_HIP(h, launch_max_u32(len1, len2, n_pairs, d_max, sc.stream));
+    FCD_HIP(h, hipMemcpyAsync(h_max, d_max, 8, hipMemcpyDeviceToHost, sc.stream));
+    FCD_HIP(h, hipStreamSynchronize(sc.stream));
     const int64_t L1cap = std::max<int64_t>(1, std::min<int64_t>(h_max[0], T1cap));
     const int64_t L2cap = std::max<int64_t>(1, std::min<int64_t>(h_max[1], T2cap));
     if (L1cap + L2cap > 65535) return fail(h, FCD_E_UNSUPPORTED, "envelope estimator: more than 65535 labels in a pair");
@@ -1351,25 +1327,23 @@ int fcd_duplex_envelope_dev(fcd_handle *h, int64_t n_pairs,
     const size_t per_pair = (size_t)dirs_stride * 8 + anchor_bytes;
     int64_t chunk = std::max<int64_t>(1, workspace_budget(h) / (int64_t)per_pair);
     chunk = std::min<int64_t>(chunk, n_pairs);
-    rc = arena_exclusive(h, nullptr, 0);
-    if (rc) return rc;
-    rc = ensure(h, &h->arena, &h->arena_bytes, (size_t)chunk * per_pair);
+    char *abase = nullptr;
+    rc = sc.arena((size_t)chunk * per_pair, &abase);
     if (rc) return rc;
     EnvelopeArgs a;
     a.labels1 = labels1; a.labels2 = labels2; a.path1 = path1; a.path2 = path2;
     a.len1 = len1; a.len2 = len2; a.stride1 = stride1; a.stride2 = stride2;
     a.T1 = T1; a.T2 = T2; a.T1cap = T1cap; a.T2cap = T2cap; a.L2cap = L2cap; a.band = band;
     a.env = envelope; a.env_stride = env_stride;
-    a.dirs = reinterpret_cast<uint64_t *>(h->arena);
+    a.dirs = reinterpret_cast<uint64_t *>(abase);
     a.dirs_stride = dirs_stride;
     a.nchunk = std::max(nchunk, 1);
-    a.anchor = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(h->arena) + (size_t)chunk * dirs_stride * 8);
+    a.anchor = reinterpret_cast<int32_t *>(abase + (size_t)chunk * dirs_stride * 8);
     // anchor slabs are (T1cap + 1) ints apart inside their region
-    Timer tm(h);
+    sc.time();
     for (int64_t b0 = 0; b0 < n_pairs; b0 += chunk)
-        FCD_HIP(h, launch_envelope(a, b0, std::min<int64_t>(chunk, n_pairs - b0), h->stream));
-    tm.stop();
-    return FCD_OK;
+        FCD_HIP(h, launch_envelope(a, b0, std::min<int64_t>(chunk, n_pairs - b0), sc.stream));
+    return sc.finish();
 }
 
 int fcd_duplex_envelope_host(fcd_handle *h, int64_t n_pairs,
@@ -1474,8 +1448,13 @@ int fcd_result_offsets_dev(fcd_handle *h, const uint32_t *out_len, int64_t n_rea
     std::lock_guard<std::recursive_mutex> g(h->mu);
     if (n_reads < 0 || !offsets || (n_reads > 0 && !out_len) || out_stride < 0) return fail(h, FCD_E_INVALID, "bad argument");
     FCD_DEVICE(h);
-    FCD_HIP(h, launch_result_offsets(out_len, n_reads, out_stride, offsets, h->stream));
-    return FCD_OK;
+    CallScope sc(h);
+    sc.add(out_len, (size_t)n_reads * 4);
+    sc.add(offsets, (size_t)(n_reads + 1) * 8);
+    int rc = sc.begin(false, false);
+    if (rc) return rc;
+    FCD_HIP(h, launch_result_offsets(out_len, n_reads, out_stride, offsets, sc.stream));
+    return sc.finish();
 }
 
 int fcd_pack_results_dev(fcd_handle *h, const fcd_result *res, int64_t n_reads, int path_bytes,
@@ -1486,14 +1465,16 @@ int fcd_pack_results_dev(fcd_handle *h, const fcd_result *res, int64_t n_reads, 
         return fail(h, FCD_E_INVALID, "bad argument");
     if (n_reads > 0 && (!res->labels || !res->path || !res->out_len)) return fail(h, FCD_E_INVALID, "null labels/path/out_len");
     FCD_DEVICE(h);
-    if (n_reads == 0) {
-        FCD_HIP(h, hipMemsetAsync(buf, 0, 16, h->stream));
-        return FCD_OK;
-    }
     ResultDesc wire = to_desc(res);
     wire.qual = nullptr;  // the wire format carries labels, path, out_len, status
-    FCD_HIP(h, launch_pack(wire, n_reads, path_bytes, offsets, buf, h->stream));
-    return FCD_OK;
+    CallScope sc(h);
+    sc.add(wire, n_reads);
+    sc.add(offsets, (size_t)(n_reads + 1) * 8);
+    int rc = sc.begin(false, false);
+    if (rc) return rc;
+    if (n_reads == 0) FCD_HIP(h, hipMemsetAsync(buf, 0, 16, sc.stream));
+    else FCD_HIP(h, launch_pack(wire, n_reads, path_bytes, offsets, buf, sc.stream));
+    return sc.finish();
 }
 
 int fcd_unpack_results_dev(fcd_handle *h, const uint8_t *buf, int64_t n_reads, uint64_t *offsets,
@@ -1504,11 +1485,17 @@ int fcd_unpack_results_dev(fcd_handle *h, const uint8_t *buf, int64_t n_reads, u
     if (n_reads == 0) return FCD_OK;
     if (!out->labels || !out->out_len) return fail(h, FCD_E_INVALID, "null labels/out_len");
     FCD_DEVICE(h);
+    CallScope sc(h);
+    sc.add(to_desc(out), n_reads);
+    sc.add(buf, 16 + (size_t)n_reads * 8);
+    sc.add(offsets, (size_t)(n_reads + 1) * 8);
+    int rc = sc.begin(false, false);
+    if (rc) return rc;
     // the buffer's own out_len array (offset 16) gives the read offsets
     FCD_HIP(h, launch_result_offsets(reinterpret_cast<const uint32_t *>(buf + 16), n_reads, out->out_stride, offsets,
-                                     h->stream));
-    FCD_HIP(h, launch_unpack(buf, n_reads, offsets, to_desc(out), h->stream));
-    return FCD_OK;
+                                     sc.stream));
+    FCD_HIP(h, launch_unpack(buf, n_reads, offsets, to_desc(out), sc.stream));
+    return sc.finish();
 }
 
 int fcd_unpack_gathered_dev(fcd_handle *h, const uint8_t *gathered, int64_t stride, int world, const int64_t *first,
@@ -1520,8 +1507,14 @@ int fcd_unpack_gathered_dev(fcd_handle *h, const uint8_t *gathered, int64_t stri
     if (n_total == 0) return FCD_OK;
     if (!out->labels || !out->out_len) return fail(h, FCD_E_INVALID, "null labels/out_len");
     FCD_DEVICE(h);
-    FCD_HIP(h, launch_unpack_gathered(gathered, stride, world, first, n_total, offsets, to_desc(out), bad, h->stream));
-    return FCD_OK;
+    CallScope sc(h);
+    sc.add(to_desc(out), n_total);
+    sc.add(gathered, (size_t)stride * world);
+    sc.add(offsets, (size_t)(n_total + world) * 8);
+    int rc = sc.begin(false, false);
+    if (rc) return rc;
+    FCD_HIP(h, launch_unpack_gathered(gathered, stride, world, first, n_total, offsets, to_desc(out), bad, sc.stream));
+    return sc.finish();
 }
 
 }  // extern "C"

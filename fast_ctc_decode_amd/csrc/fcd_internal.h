@@ -277,8 +277,9 @@ struct fcd_handle {
         int64_t cap_nodes = 0, cap_worst = 0, first_stride = 0;
         int rpw = 0, row_words = 0, p1 = 0, p2 = 0;
     } pool_geom;
-    // fcd_set_overlap: wide-beam calls go round-robin to internal streams, ordered after the handle's stream as it stood
-    // at the call and not after one another; what each stream still runs writes the output ranges listed here
+    // fcd_set_overlap: the beam searches go round-robin to internal streams, ordered after the handle's stream as it stood
+    // at the call and not after one another; what each stream still runs writes the output ranges listed here.  Only
+    // capi.hip's CallScope and the handle-control entry points touch these (and `arena`, `lnbuf`).
     static constexpr int kMaxOverlap = 8;
     int overlap_n = 0;
     hipStream_t ov_stream[kMaxOverlap] = {};
@@ -288,16 +289,17 @@ struct fcd_handle {
     uint64_t ov_seq = 0;
     int ov_last_slot = -1;  // the internal stream the latest overlapping call went to
     struct Range { uintptr_t lo, hi; };
+    static constexpr int kMaxRanges = 10;  // arrays one call reads or writes (fcd_unpack_gathered_dev: 10)
     // the calls each internal stream has not finished yet, oldest first: what they write, and an event behind each (so that
     // a stream that never idles does not accumulate ranges: finished calls are dropped from the front)
     struct Flight {
         hipEvent_t done = nullptr;
-        Range r[6];
+        Range r[kMaxRanges];
         int n = 0;
     };
     std::deque<Flight> ov_flights[kMaxOverlap];
     std::vector<hipEvent_t> ov_event_pool;
-    void *retry_counter = nullptr;  // lane kernel, two-pass sizing: overflow counter of the retry rounds
+    void *retry_counter = nullptr;  // lane kernel, two-pass sizing: overflow counters of the retry pass, one word per stream
     size_t retry_counter_bytes = 0;
     void *retry_host = nullptr;     // page-locked word the first retry round's overflow count is copied to, read one call late
     hipEvent_t retry_ev = nullptr;  // ... recorded behind that copy

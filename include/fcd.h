@@ -199,10 +199,11 @@ int fcd_synchronize(fcd_handle *h);                      /* waits for the handle
  * arena whose slabs are handed out on the device, as many as the chip holds wavefronts (csrc/slab_pool.h); the other
  * kernels' calls get a region of the workspace per internal stream.  Results are complete once fcd_overlap_join(h) has
  * made the handle's stream wait for them (fcd_overlap_join_stream: any other hipStream_t), or after fcd_synchronize.
- * Any *_dev search on this handle whose output arrays overlap those of a call still in flight is ordered behind it;
- * READERS of such results (fcd_pack_results_dev, the caller's own kernels and copies) need the join, and the inputs of a
- * call must stay untouched until it is joined.  n = 0 (default): every call is in stream order; changing n joins what is
- * in flight.  The internal streams are created in the high priority class, whose hardware queues the runtime hands out
+ * Every *_dev entry point of this handle that reads or writes arrays an overlapping call in flight writes (a search into
+ * the same result arrays, fcd_result_offsets_dev / fcd_pack_results_dev / fcd_unpack_*_dev on its results) is ordered
+ * behind that call by the library.  The caller's own kernels and copies that read such results need the join, and the
+ * inputs of a call must stay untouched until it is joined.  n = 0 (default): every call is in stream order; changing n
+ * joins what is in flight.  The internal streams are created in the high priority class, whose hardware queues the runtime hands out
  * separately from those of the process's normal streams. */
 int fcd_set_overlap(fcd_handle *h, int streams);
 int fcd_overlap_join(fcd_handle *h);

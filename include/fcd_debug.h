@@ -41,10 +41,10 @@ int fcd_debug_pdq178_coop_sort_dev(fcd_handle *h, uint64_t *lists, int64_t n_lis
 int fcd_debug_pdq178_coop_profile(fcd_handle *h, uint64_t cycles[16], int reset);
 /* Developer instrument: wide-beam searches whose worst-case tree arena would exceed 8 GiB (or the workspace
  * limit) run a first pass in slabs of 1/divisor of the worst case (default 2; trees usually reach a third of
- * it) and decode the reads that outgrow their slab again in worst-case slabs carved from the same arena.  A
- * job in which more than a quarter of the reads overflow switches the handle to worst-case slabs for later
- * jobs.  A larger divisor makes the retry path run on small inputs (tests) and pins it; 0 restores the
- * adaptive default. */
+ * it) and decode the reads that outgrow their slab again in worst-case slabs, handed out from a second ring of
+ * the slab pool (csrc/slab_pool.h, an allocation of its own beside the tree arena).  A job in which more than a
+ * quarter of the reads overflow switches the handle to worst-case slabs for later jobs.  A larger divisor makes
+ * the retry path run on small inputs (tests) and pins it; 0 restores the adaptive default. */
 int fcd_debug_set_first_pass_divisor(fcd_handle *h, int divisor);
 /* Developer instrument: while `cycles` (DEVICE array [n_pairs][16] u32, indexed by the pair's position in the batch)
  * is set, the duplex searches on this handle record a cycle account per pair: shader cycles / 64 spent in

@@ -90,6 +90,41 @@ def test_hip_pack_kernels_match_the_host_layout(B, W):
     _assert_same_used(r, BatchResult(back.labels.cpu(), back.path.cpu(), back.out_len.cpu(), back.status.cpu()), W)
 
 
+def test_pack_of_overlapping_results_without_a_join():
+    """dist.result_total / dist.pack_result on results made under set_overlap(3) and never joined: the library orders its
+    offsets and pack calls behind the overlapping searches that write what they read (include/fcd.h), so the offsets and
+    packed bytes equal those of the stream-order results.  (A race: a library without that ordering may still pass a
+    lucky run.)"""
+    torch = pytest.importorskip("torch")
+
+    import fast_ctc_decode_amd as fcd
+    from fast_ctc_decode_amd import _native as nat
+    from fast_ctc_decode_amd import dist as fdist
+    from kat_cases import reference_style_rows
+
+    B, T = 256, 600
+    xs = [torch.from_numpy(reference_style_rows(np.random.default_rng(70 + i), B * T, 5).reshape(B, T, 5)).cuda()
+          for i in range(4)]
+
+    def packed(r):
+        offs, total = fdist.result_total(r)
+        nbytes = fdist.packed_nbytes(B, total, T)
+        buf = fdist.pack_result(r, offs, nbytes, out=torch.zeros(nbytes, dtype=torch.uint8, device=r.labels.device))
+        return offs.cpu(), buf.cpu()
+
+    want = [packed(fcd.beam_search_batch_raw(x, 32, 0.1, True)) for x in xs]
+    h = nat.default_handle()
+    h.set_overlap(3)
+    try:
+        rs = [fcd.beam_search_batch_raw(x, 32, 0.1, True) for x in xs]
+        got = [packed(r) for r in rs]
+    finally:
+        h.set_overlap(0)
+    for (go, gb), (wo, wb) in zip(got, want):
+        assert torch.equal(go, wo)
+        assert torch.equal(gb, wb)
+
+
 def test_c_abi_gather_over_rccl_world1():
     """csrc/comm.hip: fcd_comm_unique_id / fcd_comm_create (ncclCommInitRank through the dlopen'ed RCCL),
     fcd_gather_results_dev (offsets + pack, ncclAllReduce(MAX) of the size, ONE ncclGather, one-launch unpack) and

@@ -544,6 +544,44 @@ def test_duplex_overlapping_calls(fcd, mode):
         h.set_overlap(0)
 
 
+def test_envelope_between_overlapping_duplex_calls(fcd):
+    """fcd_duplex_envelope_dev between overlapping duplex calls: it takes the workspace from its start -- its few bytes
+    of scratch included -- only after every call in flight, so the long duplex batches still running on all three
+    internal streams (each on its region of the log-space buffer) and the envelope estimate do not touch each other's
+    bytes.  Every result equals stream order.  (A race: a library without that ordering may still pass a lucky run.)"""
+    torch = pytest.importorskip("torch")
+    if not torch.cuda.is_available():
+        pytest.skip("device tensors only")
+    from fast_ctc_decode_amd import _native as nat
+    shapes = [(8, 900, 880, 32)] * 3 + [(5, 130, 120, 16), (7, 90, 100, 12)]
+    data = []
+    for k, (B, T1, T2, w) in enumerate(shapes):
+        x1, x2 = pairs(800 + k, B, T1, T2)
+        data.append((torch.from_numpy(x1).cuda(), torch.from_numpy(x2).cuda(), np.stack([band(T1, T2, w)] * B)))
+    e1, e2 = (torch.from_numpy(a).cuda() for a in pairs(850, 6, 300, 290))
+
+    def run():
+        rs = [fcd.beam_search_duplex_batch_raw(x1, x2, e, 5, 0.1, True) for x1, x2, e in data[:3]]
+        env = fcd.estimate_envelope_batch(e1, e2, band=16)
+        rs += [fcd.beam_search_duplex_batch_raw(x1, x2, e, 5, 0.1, True) for x1, x2, e in data[3:]]
+        return [r.cpu() for r in rs], env.cpu().numpy()
+
+    want, want_env = run()
+    h = nat.default_handle()
+    h.set_overlap(3)
+    try:
+        got, got_env = run()
+    finally:
+        h.set_overlap(0)
+    np.testing.assert_array_equal(got_env, want_env)
+    for g, w in zip(got, want):
+        np.testing.assert_array_equal(g.status, w.status)
+        np.testing.assert_array_equal(g.out_len, w.out_len)
+        for i in range(len(g.out_len)):
+            n = int(g.out_len[i])
+            np.testing.assert_array_equal(g.labels[i, :n], w.labels[i, :n])
+
+
 def test_crf_duplex_device_tensors(fcd):
     """The zero-copy (torch ROCm tensor) entry of the CRF duplex search equals the host entry."""
     torch = pytest.importorskip("torch")

@@ -1,13 +1,15 @@
 """Differential soak of fcd_set_overlap on the GPU: a random sequence of device-tensor calls -- every beam kernel, wide
 beams through the slab pool (sometimes under a workspace limit that leaves a handful of slabs), duplex searches, viterbi
-in between, changes of the number of internal streams, results sometimes read at once and sometimes much later -- each
-compared with the same call made in stream order beforehand.  python tools/overlap_soak.py [CALLS] [SEED]"""
+in between, changes of the number of internal streams, results sometimes read at once and sometimes much later, the
+envelope estimator and the pack path of dist.py (offsets + pack, no join) on results still in flight -- each compared with
+the same call made in stream order beforehand.  python tools/overlap_soak.py [CALLS] [SEED]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 import fast_ctc_decode_amd as fcd
 from fast_ctc_decode_amd import _native as nat
+from fast_ctc_decode_amd import dist as fdist
 
 CALLS = int(sys.argv[1]) if len(sys.argv) > 1 else 300
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
@@ -20,8 +22,21 @@ def rows(*shape):
 
 
 def make_case():
-    kind = rng.choice(["wave", "wave1", "generic", "lane", "lane_pool", "duplex", "duplex_max"])
+    kind = rng.choice(["wave", "wave1", "generic", "lane", "lane_pool", "duplex", "duplex_max", "envelope", "pack"])
     B, T = int(rng.integers(1, 40)), int(rng.integers(20, 260))
+    if kind == "envelope":  # (the workspace from its start, behind every call in flight)
+        a, b = torch.from_numpy(rows(B, T, 5)).cuda(), torch.from_numpy(rows(B, T + int(rng.integers(-8, 9)), 5)).cuda()
+        bw = int(rng.integers(4, 40))
+        return kind, lambda: fcd.estimate_envelope_batch(a, b, band=bw), None
+    if kind == "pack":  # (an overlapping search read by the offsets and pack calls without a join)
+        x, beam = torch.from_numpy(rows(B, T, 5)).cuda(), int(rng.integers(2, 65))
+
+        def pack():
+            r = fcd.beam_search_batch_raw(x, beam, 0.05, True)
+            offs, total = fdist.result_total(r)
+            nbytes = fdist.packed_nbytes(B, total, T)
+            return fdist.pack_result(r, offs, nbytes, out=torch.zeros(nbytes, dtype=torch.uint8, device=x.device))
+        return kind, pack, None
     if kind in ("duplex", "duplex_max"):
         B, T = int(rng.integers(1, 12)), int(rng.integers(30, 140))
         T2 = T + int(rng.integers(-8, 9))
@@ -40,6 +55,8 @@ def make_case():
 
 
 def same(a, b):
+    if isinstance(a, torch.Tensor):
+        return torch.equal(a, b)
     if not (np.array_equal(a.status, b.status) and np.array_equal(a.out_len, b.out_len)):
         return False
     for i in range(len(a.out_len)):
