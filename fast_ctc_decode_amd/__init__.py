@@ -9,6 +9,7 @@ importing this package never touches a CPU fallback (there is none).
 """
 from .api import (  # noqa: F401
     BatchResult,
+    NBestResult,
     __version__,
     beam_search,
     beam_search_batch,
@@ -16,6 +17,8 @@ from .api import (  # noqa: F401
     beam_search_duplex,
     beam_search_duplex_batch,
     beam_search_duplex_batch_raw,
+    beam_search_nbest,
+    beam_search_nbest_batch_raw,
     set_duplex_logadd_mode,
     set_tie_order,
     tie_order,
@@ -29,6 +32,8 @@ from .api import (  # noqa: F401
     crf_beam_search_duplex,
     crf_beam_search_duplex_batch,
     crf_beam_search_duplex_batch_raw,
+    crf_beam_search_nbest,
+    crf_beam_search_nbest_batch_raw,
     crf_greedy_search,
     crf_greedy_search_batch,
     crf_greedy_search_batch_raw,

@@ -31,6 +31,8 @@ SYMBOLS = [
     "fcd_beam_search_dev", "fcd_beam_search_host", "fcd_beam_search_profile_dev",
     "fcd_crf_beam_search_dev", "fcd_crf_beam_search_dev_k", "fcd_crf_beam_search_host",
     "fcd_crf_beam_search_host_k",
+    "fcd_beam_search_nbest_dev", "fcd_beam_search_nbest_host", "fcd_crf_beam_search_nbest_dev",
+    "fcd_crf_beam_search_nbest_host",
     "fcd_crf_greedy_search_dev", "fcd_crf_greedy_search_host",
     "fcd_beam_search_duplex_dev", "fcd_beam_search_duplex_host",
     "fcd_crf_beam_search_duplex_dev", "fcd_crf_beam_search_duplex_host",
@@ -63,6 +65,11 @@ class Result(C.Structure):
         ("out_len", C.c_void_p), ("status", C.c_void_p), ("out_stride", C.c_int64),
         ("ambiguous", C.c_void_p),
     ]
+
+
+class NBest(C.Structure):
+    """fcd_nbest: n best hypotheses per read of the beam searches (include/fcd.h)."""
+    _fields_ = [("n_best", C.c_int64), ("score", C.c_void_p), ("n_hyp", C.c_void_p)]
 
 
 class Chunk(C.Structure):
@@ -158,6 +165,10 @@ def bind(lib):
     lib.fcd_beam_search_profile_dev.argtypes = [P, BP, i64, f32, i32, RP, P]
     lib.fcd_crf_beam_search_dev_k.argtypes = [P, BP, P, i64, i64, i64, f32, i32, RP]
     lib.fcd_crf_beam_search_host_k.argtypes = [P, BP, P, i64, i64, i64, f32, i32, RP]
+    NP = C.POINTER(NBest)
+    for sfx in ("dev", "host"):
+        getattr(lib, "fcd_beam_search_nbest_" + sfx).argtypes = [P, BP, i64, f32, i32, i32, NP, RP]
+        getattr(lib, "fcd_crf_beam_search_nbest_" + sfx).argtypes = [P, BP, P, i64, i64, i64, f32, i32, NP, RP]
     for sfx in ("dev", "host"):
         getattr(lib, "fcd_duplex_envelope_" + sfx).argtypes = [
             P, i64, P, P, P, i64, P, i64, P, P, P, i64, P, i64, i64, P, i64]

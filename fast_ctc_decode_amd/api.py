@@ -1040,3 +1040,214 @@ def crf_beam_search_batch(network_outputs, init_states, alphabet, beam_size=5,
         labels = r.labels[i, :n]
         out.append(("".join(alpha[l] for l in labels[::-1])[::-1], item[1]))
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# n best hypotheses of the beam searches (include/fcd.h, fcd_nbest) -- beyond the reference, which
+# returns beam[0] only (src/search.rs:165,300)
+# ---------------------------------------------------------------------------------------------
+def _check_n_best(n_best, beam_size):
+    if isinstance(n_best, bool) or not isinstance(n_best, (int, np.integer)):
+        raise TypeError("argument 'n_best': expected an integer")
+    if n_best < 1 or n_best > beam_size:
+        raise ValueError("n_best must be in 1 .. beam_size (%d), got %d" % (beam_size, n_best))
+    return int(n_best)
+
+
+class NBestResult:
+    """Raw outcome of an n-best beam search: hypothesis i of read r is labels[r, i, :out_len[r, i]] (path likewise),
+    its score score[r, i] = label_prob + gap_prob of beam entry i after the last step -- relative to the best entry,
+    not a log-likelihood.  n_hyp[r] hypotheses per read (0 when the read's search failed: status[r] says why).
+    Arrays are numpy for host inputs, torch tensors (same device) for device inputs."""
+
+    def __init__(self, labels, path, out_len, score, n_hyp, status, ambiguous=None, crf=False):
+        self.labels, self.path, self.out_len, self.score = labels, path, out_len, score
+        self.n_hyp, self.status, self.ambiguous = n_hyp, status, ambiguous
+        self.crf = crf  # strings follow crf_beam_search's character reversal (src/search.rs:146-156)
+
+    def cpu(self):
+        h = getattr(self, "_handle", None)
+        if h is not None and h.overlap and not isinstance(self.labels, np.ndarray):
+            import torch  # (as BatchResult.cpu: the copies wait for every overlapping call)
+            h.set_stream(torch.cuda.current_stream(self.labels.device).cuda_stream)
+            h.overlap_join()
+
+        def c(a):
+            return a if a is None or isinstance(a, np.ndarray) else a.cpu().numpy()
+        return NBestResult(c(self.labels), c(self.path), c(self.out_len), c(self.score), c(self.n_hyp), c(self.status),
+                           c(self.ambiguous), self.crf)
+
+    def hypotheses(self, alphabet, raise_on_error=True):
+        """-> per read, a list of (seq, path, score), best first (None for a failed read when not raise_on_error)."""
+        r = self.cpu()
+        alpha = _seq_to_vec(alphabet)
+        status = np.asarray(r.status)
+        if raise_on_error and (status != nat.ST_OK).any():
+            i = int(np.flatnonzero(status != nat.ST_OK)[0])
+            raise RuntimeError("read %d: %s" % (i, nat.status_string(int(status[i]))))
+        out = []
+        for i in range(len(status)):
+            if status[i] != nat.ST_OK:
+                out.append(None)
+                continue
+            hyps = []
+            for j in range(int(r.n_hyp[i])):
+                n = int(r.out_len[i, j])
+                labels = r.labels[i, j, :n]
+                if self.crf:
+                    seq = "".join(alpha[l] for l in labels[::-1])[::-1]
+                else:
+                    seq = "".join(alpha[l] for l in labels)
+                pth = r.path[i, j, :n].tolist() if r.path is not None else None
+                hyps.append((seq, pth, float(r.score[i, j])))
+            out.append(hyps)
+        return out
+
+
+def _nbest_torch(fn_name, x, crf, lengths, extra_args, n_best, handle=None, want_amb=False):
+    import torch
+
+    dcode = _torch_dtype_code(x)
+    h = handle if handle is not None else nat.default_handle(x.device.index or 0)
+    st = x.stride()
+    if crf:
+        B, T, S, N = x.shape
+        b = nat.Batch(x.data_ptr(), B, T, S, N, st[0], st[1], st[2], st[3], None, dcode)
+    else:
+        B, T, N = x.shape
+        b = nat.Batch(x.data_ptr(), B, T, 1, N, st[0], st[1], 0, st[2], None, dcode)
+    if lengths is not None:
+        lengths = torch.as_tensor(lengths, dtype=torch.int64, device=x.device).contiguous()
+        b.lengths = lengths.data_ptr()
+    w = max(int(T), 1)
+    # (the kernels write every row, score, n_hyp and status: no fill kernels in front of them)
+    labels = torch.empty((B, n_best, w), dtype=torch.uint8, device=x.device)
+    path = torch.empty((B, n_best, w), dtype=torch.int32, device=x.device)
+    out_len = torch.empty((B, n_best), dtype=torch.int32, device=x.device)
+    score = torch.empty((B, n_best), dtype=torch.float32, device=x.device)
+    meta = torch.empty((2, B), dtype=torch.int32, device=x.device)
+    n_hyp, status = meta[0], meta[1]
+    amb = torch.zeros((B, 2), dtype=torch.int32, device=x.device) if want_amb else None
+    res = nat.Result(labels.data_ptr(), path.data_ptr(), None, out_len.data_ptr(), status.data_ptr(), w,
+                     amb.data_ptr() if want_amb else None)
+    nb = nat.NBest(n_best, score.data_ptr(), n_hyp.data_ptr())
+    h.set_stream(torch.cuda.current_stream(x.device).cuda_stream)
+    h.check(getattr(h.lib, fn_name)(h.ptr, C.byref(b), *extra_args, C.byref(nb), C.byref(res)))
+    r = NBestResult(labels, path, out_len, score, n_hyp, status, amb, crf)
+    r._handle = h
+    r._keep = (x, lengths)
+    h.hold_in_flight(r._keep, labels, path, out_len, score, meta, amb)
+    return r
+
+
+class _HostNBest:
+    def __init__(self, B, T, n_best, want_amb=False):
+        w = max(int(T), 1)
+        self.labels = np.zeros((B, n_best, w), np.uint8)
+        self.path = np.zeros((B, n_best, w), np.uint32)
+        self.out_len = np.zeros((B, n_best), np.uint32)
+        self.score = np.zeros((B, n_best), np.float32)
+        self.n_hyp = np.zeros(B, np.uint32)
+        self.status = np.zeros(B, np.int32)
+        self.ambiguous = np.zeros((B, 2), np.uint32) if want_amb else None
+        self.res = nat.Result(self.labels.ctypes.data, self.path.ctypes.data, None, self.out_len.ctypes.data,
+                              self.status.ctypes.data, w, self.ambiguous.ctypes.data if want_amb else None)
+        self.nb = nat.NBest(n_best, self.score.ctypes.data, self.n_hyp.ctypes.data)
+
+    def result(self, crf):
+        return NBestResult(self.labels, self.path, self.out_len, self.score, self.n_hyp, self.status, self.ambiguous,
+                           crf)
+
+
+def _check_nbest_raw(n_best, beam_size):
+    beam_size = _usize(beam_size, "beam_size")
+    if beam_size == 0:
+        raise ValueError("beam_size cannot be 0")
+    return _check_n_best(n_best, beam_size), beam_size
+
+
+def beam_search_nbest_batch_raw(network_outputs, n_best, beam_size=5, beam_cut_threshold=0.0, collapse_repeats=True,
+                                lengths=None, kernel=nat.KERNEL_AUTO, handle=None, count_ambiguous=False,
+                                input_dtype=None):
+    """beam_search_batch_raw with the n best hypotheses of every read -> NBestResult (labels (B, n_best, T), path,
+    out_len (B, n_best), score (B, n_best), n_hyp (B,), status (B,)).  Hypothesis 0 is what beam_search_batch_raw
+    returns for the read."""
+    n_best, beam_size = _check_nbest_raw(n_best, beam_size)
+    args = (beam_size, float(beam_cut_threshold), int(bool(collapse_repeats)), int(kernel))
+    dev_x = _device_tensor(network_outputs)
+    if dev_x is not None:
+        return _nbest_torch("fcd_beam_search_nbest_dev", dev_x, False, lengths, args, n_best, handle=handle,
+                            want_amb=count_ambiguous)
+    network_outputs, lengths = _ragged(network_outputs, lengths, 3)
+    x = _stack_host(network_outputs, 3)
+    B, T, N = x.shape
+    h = nat.default_handle()
+    out = _HostNBest(B, T, n_best, want_amb=count_ambiguous)
+    l = _np_lengths(lengths, B)
+    b = _host_batch(x, False, l, input_dtype)
+    h.check(h.lib.fcd_beam_search_nbest_host(h.ptr, C.byref(b), *args, C.byref(out.nb), C.byref(out.res)))
+    return out.result(False)
+
+
+def crf_beam_search_nbest_batch_raw(network_outputs, init_states, n_best, beam_size=5, beam_cut_threshold=0.0,
+                                    lengths=None, kernel=nat.KERNEL_AUTO, handle=None, count_ambiguous=False,
+                                    input_dtype=None):
+    """crf_beam_search_batch_raw with the n best hypotheses of every read -> NBestResult (see
+    beam_search_nbest_batch_raw); strings from .hypotheses() follow crf_beam_search's character reversal."""
+    n_best, beam_size = _check_nbest_raw(n_best, beam_size)
+    dev_x = _device_tensor(network_outputs)
+    if dev_x is not None:
+        import torch
+        init = torch.as_tensor(init_states, dtype=torch.float32, device=dev_x.device).contiguous()
+        if init.ndim != 2 or init.shape[0] != dev_x.shape[0]:
+            raise ValueError("init_states must have shape (n_reads, n_init)")
+        r = _nbest_torch("fcd_crf_beam_search_nbest_dev", dev_x, True, lengths,
+                         (C.c_void_p(init.data_ptr()), int(init.shape[1]), int(init.shape[1]), beam_size,
+                          float(beam_cut_threshold), int(kernel)), n_best, handle=handle, want_amb=count_ambiguous)
+        r._keep = r._keep + (init,)
+        return r
+    x = _stack_host(network_outputs, 4)
+    init = np.ascontiguousarray(np.asarray(init_states, np.float32))
+    B, T, S, N = x.shape
+    if init.ndim != 2 or init.shape[0] != B:
+        raise ValueError("init_states must have shape (n_reads, n_init)")
+    h = nat.default_handle()
+    out = _HostNBest(B, T, n_best, want_amb=count_ambiguous)
+    l = _np_lengths(lengths, B)
+    b = _host_batch(x, True, l, input_dtype)
+    h.check(h.lib.fcd_crf_beam_search_nbest_host(h.ptr, C.byref(b), init.ctypes.data, init.shape[1], init.shape[1],
+                                                 beam_size, float(beam_cut_threshold), int(kernel), C.byref(out.nb),
+                                                 C.byref(out.res)))
+    return out.result(True)
+
+
+def beam_search_nbest(network_output, alphabet, n_best, beam_size=5, beam_cut_threshold=0.0, collapse_repeats=True):
+    """beam_search's search, returning its n best hypotheses: a list of (seq, path, score), best first, of length
+    min(n_best, final beam length).  Element 0's (seq, path) is beam_search's result.  score = label_prob + gap_prob
+    of the beam entry after the last step, relative to the best entry (<= 1 up to rounding; not a log-likelihood)."""
+    x = _as_f32(network_output, 2, "network_output")
+    alpha = _seq_to_vec(alphabet)
+    _check_beam_args(len(alpha), x.shape[1], beam_size, beam_cut_threshold)
+    n_best = _check_n_best(n_best, beam_size)
+    r = beam_search_nbest_batch_raw(_dense(x)[None], n_best, beam_size, beam_cut_threshold, collapse_repeats)
+    _raise_status(int(r.status[0]))
+    return r.hypotheses(alpha)[0]
+
+
+def crf_beam_search_nbest(network_output, init_state, alphabet, n_best, beam_size=5, beam_cut_threshold=0.0):
+    """crf_beam_search's search, returning its n best hypotheses as beam_search_nbest does; element 0's (seq, path) is
+    crf_beam_search's result."""
+    x = _as_f32(network_output, 3, "network_output")
+    init = _as_f32(init_state, 1, "init_state")
+    beam_size = _usize(beam_size, "beam_size")
+    alpha = _seq_to_vec(alphabet)
+    _check_greedy_alphabet(len(alpha), x.shape[2])
+    if x.size == 0 or init.size == 0:
+        raise RuntimeError("network_output/init_state is empty (the reference asserts and aborts here)")
+    if beam_size < 1:
+        raise RuntimeError(nat.status_string(nat.ST_RAN_OUT_OF_BEAM))  # truncate(0) -> empty beam
+    n_best = _check_n_best(n_best, beam_size)
+    r = crf_beam_search_nbest_batch_raw(_dense(x)[None], np.ascontiguousarray(init)[None], n_best, beam_size,
+                                        beam_cut_threshold)
+    _raise_status(int(r.status[0]))
+    return r.hypotheses(alpha)[0]

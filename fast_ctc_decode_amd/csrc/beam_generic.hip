@@ -32,6 +32,7 @@ struct GenericParams {
     GenericArena arena;
     ResultDesc out;
     int64_t read_begin;
+    NBestDesc nb;  // (last: fcd_internal.h)
 };
 
 // LDS carve-up (all 4-byte words unless noted).  BC = beam_size, NL = N-1, C = BC*N.
@@ -146,17 +147,30 @@ __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+template <bool NB>
 __device__ __forceinline__ void fail(const GenericParams &p, int64_t r, int code, int n_amb, int n_crit) {
     if (threadIdx.x == 0) {
         p.out.status[r] = code;
-        p.out.out_len[r] = 0;
+        if (!NB) p.out.out_len[r] = 0;
         if (p.out.ambiguous) {
             p.out.ambiguous[2 * r] = (uint32_t)n_amb;
             p.out.ambiguous[2 * r + 1] = (uint32_t)n_crit;
         }
+        if (NB) p.nb.n_hyp[r] = 0;
+    }
+    if (NB) {  // a failed read has no hypotheses: every one of its rows is empty
+        const int64_t nb = p.nb.n_best;
+        for (int64_t j = threadIdx.x; j < nb; j += 64) {
+            p.out.out_len[r * nb + j] = 0;
+            p.nb.score[r * nb + j] = 0.0f;
+        }
     }
 }
 
+// NB: the n-best layout (NBestDesc::n_best > 0): lanes 0 .. n_best-1 each trace back one entry of the final beam (rank
+// order) into rows r * n_best + i, with its score, and lane 0 writes the read's n_hyp.  A separate instantiation keeps
+// the single-result kernel as it is.
+template <bool NB>
 __global__ __launch_bounds__(64) void beam_generic_kernel(GenericParams p) {
     extern __shared__ __attribute__((aligned(16))) int smem[];
     const int lane = threadIdx.x;
@@ -345,11 +359,11 @@ __global__ __launch_bounds__(64) void beam_generic_kernel(GenericParams p) {
             any_nan = any_nan || (__ballot(valid && prob != prob) != 0ull);
         }
         bad_state = __ballot(bad_state) != 0ull;
-        if (bad_state) return fail(p, r, FCD_ST_BAD_STATE, n_amb, n_crit);
-        if (nn > p.arena.cap_nodes) return fail(p, r, FCD_ST_INTERNAL, n_amb, n_crit);
+        if (bad_state) return fail<NB>(p, r, FCD_ST_BAD_STATE, n_amb, n_crit);
+        if (nn > p.arena.cap_nodes) return fail<NB>(p, r, FCD_ST_INTERNAL, n_amb, n_crit);
         // search.rs:261-277: any NaN among >= 2 candidates -> IncomparableValues, then empty -> RanOutOfBeam
-        if (n_valid >= 2 && any_nan) return fail(p, r, FCD_ST_INCOMPARABLE, n_amb, n_crit);
-        if (n_valid == 0) return fail(p, r, FCD_ST_RAN_OUT_OF_BEAM, n_amb, n_crit);
+        if (n_valid >= 2 && any_nan) return fail<NB>(p, r, FCD_ST_INCOMPARABLE, n_amb, n_crit);
+        if (n_valid == 0) return fail<NB>(p, r, FCD_ST_RAN_OUT_OF_BEAM, n_amb, n_crit);
         wave_sync();
 
         // ---- phase B: the top beam_size candidates, in exact key order, build the next beam ----
@@ -560,7 +574,38 @@ __global__ __launch_bounds__(64) void beam_generic_kernel(GenericParams p) {
 
     // ---- walk the best labelling leaf -> root (:285-300), writing it in sequence order ----
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // drop L1 lines older than our own stores
-    if (lane == 0) {
+    if (NB) {
+        const int64_t nb = p.nb.n_best;
+        const int n_hyp = (int)(B < nb ? B : nb);
+        for (int64_t j = lane; j < nb; j += kWave) {
+            const int64_t row = r * nb + j;
+            if (j >= n_hyp) {
+                p.out.out_len[row] = 0;
+                p.nb.score[row] = 0.0f;
+                continue;
+            }
+            int node = L.b_node(cur)[j];
+            const int n = L.b_depth(cur)[j];
+            uint8_t *lab = p.out.labels + row * p.out.out_stride;
+            uint32_t *pth = p.out.path ? p.out.path + row * p.out.out_stride : nullptr;
+            for (int i = n - 1; i >= 0 && node >= 0; --i) {
+                const int4 q = rec[node];
+                lab[i] = (uint8_t)(q.z + 1);
+                if (pth) pth[i] = (uint32_t)q.y;
+                node = q.x;
+            }
+            p.out.out_len[row] = (uint32_t)n;
+            p.nb.score[row] = L.b_lp(cur)[j] + L.b_gp(cur)[j];  // SearchPoint::probability() (:278)
+        }
+        if (lane == 0) {
+            p.nb.n_hyp[r] = (uint32_t)n_hyp;
+            p.out.status[r] = FCD_ST_OK;
+            if (count_amb) {
+                p.out.ambiguous[2 * r] = (uint32_t)n_amb;
+                p.out.ambiguous[2 * r + 1] = (uint32_t)n_crit;
+            }
+        }
+    } else if (lane == 0) {
         int node = L.b_node(cur)[0];
         const int n = L.b_depth(cur)[0];
         uint8_t *lab = p.out.labels + r * p.out.out_stride;
@@ -592,11 +637,14 @@ size_t beam_generic_lds_bytes(int beam_size, int N, int tie_order) {
 
 hipError_t launch_beam_generic(const BatchDesc &in, int64_t read_begin, int64_t n_reads,
                                const BeamArgs &a, const GenericArena &arena, const ResultDesc &out,
-                               hipStream_t stream) {
+                               hipStream_t stream, const NBestDesc &nb) {
     if (n_reads <= 0) return hipSuccess;
-    GenericParams p{in, a, arena, out, read_begin};
+    GenericParams p{in, a, arena, out, read_begin, nb};
     const size_t lds = beam_generic_lds_bytes(a.beam_size, in.N, a.tie_order);
-    hipLaunchKernelGGL(beam_generic_kernel, dim3((unsigned)n_reads), dim3(64), lds, stream, p);
+    if (nb.n_best > 0)
+        hipLaunchKernelGGL(beam_generic_kernel<true>, dim3((unsigned)n_reads), dim3(64), lds, stream, p);
+    else
+        hipLaunchKernelGGL(beam_generic_kernel<false>, dim3((unsigned)n_reads), dim3(64), lds, stream, p);
     return hipGetLastError();
 }
 

@@ -69,6 +69,7 @@ struct LaneParams {
     WaveArena arena;
     ResultDesc out;
     int64_t read_begin;
+    NBestDesc nb;  // (last: fcd_internal.h)
 };
 
 __device__ __forceinline__ void wave_sync() {
@@ -145,7 +146,10 @@ __device__ __forceinline__ float rdlanef(float v, int l) {
 // in a table by rank; when a kept candidate ties with its successor among more than 20 candidates, the half builds
 // the node-ordered list of ALL its candidates in LDS, the wavefront replays Rust 1.78's quicksort on it (pdq178_wave.h)
 // and the ranks it produces replace the exact ones.
-template <int N, int RPW, bool AMB, bool CRF, bool PDQ>
+// NB: the n-best layout (NBestDesc::n_best > 0; beam_wave.hip): the first n_best entries -- lanes 0 .. n_best-1 of the
+// half, each with its own (node, depth, jump) -- are traced back one after the other into rows r * n_best + i.  A retry
+// pass rewrites every row of the reads it decodes again.  The slab goes back to the pool after the last walk.
+template <int N, int RPW, bool AMB, bool CRF, bool PDQ, bool NB = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void beam_lane_kernel(LaneParams p) {
     constexpr int NL = N - 1;
     constexpr int HALF = 64 / RPW;          // lanes (= beam slots) per read
@@ -286,7 +290,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void be
         if ((bad || state > s_mask) && T > 0) {
             if (q == 0) {
                 p.out.status[r] = FCD_ST_BAD_STATE;
-                p.out.out_len[r] = 0;
+                if (!NB) p.out.out_len[r] = 0;  // (n-best rows: the epilogue)
             }
             alive = false;
             state = 0;
@@ -406,7 +410,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void be
         if (f_nan || f_empty || f_cap) {
             if (q == 0) {
                 p.out.status[r] = f_cap ? FCD_ST_INTERNAL : (f_empty ? FCD_ST_RAN_OUT_OF_BEAM : FCD_ST_INCOMPARABLE);
-                p.out.out_len[r] = 0;
+                if (!NB) p.out.out_len[r] = 0;  // (n-best rows: the epilogue)
             }
             alive = false;
         }
@@ -978,100 +982,121 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void be
 
     // ---- walk the best labelling leaf -> root (:285-300), segment-parallel (see beam_wave.hip) ----
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    uint8_t *lab = p.out.labels + r * p.out.out_stride;
-    uint32_t *pth = p.out.path ? p.out.path + r * p.out.out_stride : nullptr;
+    // NB: hypothesis i is entry i (lane i of the half); nb <= beam_size <= HALF (capi.hip)
+    const int nb = NB ? (int)p.nb.n_best : 1;
+    const int n_hyp = NB ? (alive ? (B < nb ? B : nb) : 0) : 1;
+    uint8_t *lab = p.out.labels + (NB ? r * nb : r) * p.out.out_stride;
+    uint32_t *pth = p.out.path ? p.out.path + (NB ? r * nb : r) * p.out.out_stride : nullptr;
     if (q == 0 && alive) {
-        p.out.out_len[r] = (uint32_t)depth;
+        if (!NB) p.out.out_len[r] = (uint32_t)depth;
         p.out.status[r] = FCD_ST_OK;
     }
     if (AMB && q == 0 && has_read) {
         p.out.ambiguous[2 * r] = (uint32_t)n_amb;
         p.out.ambiguous[2 * r + 1] = (uint32_t)n_crit;
     }
+    if (NB && has_read) {  // lane q: row q's length and score (entry q's probability(), :278); rows past n_hyp are empty
+        if (q < nb) {
+            p.out.out_len[r * nb + q] = q < n_hyp ? (uint32_t)depth : 0u;
+            p.nb.score[r * nb + q] = q < n_hyp ? lp + gp : 0.0f;
+        }
+        if (q == 0) p.nb.n_hyp[r] = (uint32_t)n_hyp;
+    }
     int h0 = bperm(hbase, node);
-    int d0 = bperm(hbase, alive ? depth : 0);
-    const int j0 = bperm(hbase, jump);
-    while (ballot(d0 > 0) != 0ull) {
-        int cnt = 0, nh = h0, nd = d0;
-        if (q == 0) {
-            while (cnt < HALF && nd > 0) {
-                s_heads[hbase + cnt] = nh;
-                nh = (nd % kSeg != 0) ? j0 : *jmp_at(nh);
-                nd = ((nd - 1) / kSeg) * kSeg;
-                ++cnt;
-            }
-        }
-        cnt = bperm(hbase, cnt);
-        nh = bperm(hbase, nh);
-        nd = bperm(hbase, nd);
-        wave_sync();
-        if (q < cnt) {
-            const int d1 = ((d0 - 1) / kSeg) * kSeg;
-            const int ds = q == 0 ? d0 : d1 - (q - 1) * kSeg;
-            const int de = q == 0 ? d1 : ds - kSeg;
-            int h = s_heads[hbase + q];
-            int dd = ds;
-            // creation step of the segment's first node: the last t with first[t] <= h (binary search); every
-            // further node on the way up was created strictly earlier, usually a step or two: scan backwards
-            int tc = 0;
-            if (h >= 0) {
-                int lo = 0, hi = T - 1;
-                while (lo < hi) {
-                    const int mid = (lo + hi + 1) >> 1;
-                    if (*first_at(mid) <= h) lo = mid;
-                    else hi = mid - 1;
+    int d0 = bperm(hbase, alive && n_hyp > 0 ? depth : 0);
+    int j0 = bperm(hbase, jump);
+    for (int hy = 0;;) {  // (one pass without NB)
+        while (ballot(d0 > 0) != 0ull) {
+            int cnt = 0, nh = h0, nd = d0;
+            if (q == 0) {
+                while (cnt < HALF && nd > 0) {
+                    s_heads[hbase + cnt] = nh;
+                    nh = (nd % kSeg != 0) ? j0 : *jmp_at(nh);
+                    nd = ((nd - 1) / kSeg) * kSeg;
+                    ++cnt;
                 }
-                tc = lo;
             }
-            int fc = h >= 0 ? *first_at(tc) : 0;        // first[tc], kept in a register
-            auto time_of = [&](int id) -> uint32_t {  // tc: creation step of the node visited before (or of `id`)
-                while (fc > id) fc = *first_at(--tc);   // first[0] = 0 <= id: terminates
-                return (uint32_t)tc;
-            };
-            auto one = [&]() {  // emit position dd - 1, step to the parent
-                const int e = *rec_at(h);
-                lab[dd - 1] = (uint8_t)((e & 7) + 1);
-                if (pth) pth[dd - 1] = time_of(h);
-                h = (e >> 3) - 1;
-                --dd;
-            };
-            // aligned rows: four positions leave as one 4-byte label store and one 16-byte path store (beam_wave.hip)
-            const bool wide = (reinterpret_cast<uintptr_t>(lab) & 3) == 0 && (!pth || (reinterpret_cast<uintptr_t>(pth) & 15) == 0);
-            while (dd > de && h >= 0 && (!wide || (dd & 3) != 0)) one();
-            for (; dd - 4 >= de && h >= 0; dd -= 4) {
-                uint32_t lw = 0;
-                uint32_t tw[4];
-#pragma unroll
-                for (int j = 3; j >= 0; --j) {  // positions dd-1 (j = 3) ... dd-4 (j = 0)
+            cnt = bperm(hbase, cnt);
+            nh = bperm(hbase, nh);
+            nd = bperm(hbase, nd);
+            wave_sync();
+            if (q < cnt) {
+                const int d1 = ((d0 - 1) / kSeg) * kSeg;
+                const int ds = q == 0 ? d0 : d1 - (q - 1) * kSeg;
+                const int de = q == 0 ? d1 : ds - kSeg;
+                int h = s_heads[hbase + q];
+                int dd = ds;
+                // creation step of the segment's first node: the last t with first[t] <= h (binary search); every
+                // further node on the way up was created strictly earlier, usually a step or two: scan backwards
+                int tc = 0;
+                if (h >= 0) {
+                    int lo = 0, hi = T - 1;
+                    while (lo < hi) {
+                        const int mid = (lo + hi + 1) >> 1;
+                        if (*first_at(mid) <= h) lo = mid;
+                        else hi = mid - 1;
+                    }
+                    tc = lo;
+                }
+                int fc = h >= 0 ? *first_at(tc) : 0;        // first[tc], kept in a register
+                auto time_of = [&](int id) -> uint32_t {  // tc: creation step of the node visited before (or of `id`)
+                    while (fc > id) fc = *first_at(--tc);   // first[0] = 0 <= id: terminates
+                    return (uint32_t)tc;
+                };
+                auto one = [&]() {  // emit position dd - 1, step to the parent
                     const int e = *rec_at(h);
-                    lw |= (uint32_t)((e & 7) + 1) << (8 * j);
-                    tw[j] = pth ? time_of(h) : 0u;
+                    lab[dd - 1] = (uint8_t)((e & 7) + 1);
+                    if (pth) pth[dd - 1] = time_of(h);
                     h = (e >> 3) - 1;
+                    --dd;
+                };
+                // aligned rows: four positions leave as one 4-byte label store and one 16-byte path store (beam_wave.hip)
+                const bool wide = (reinterpret_cast<uintptr_t>(lab) & 3) == 0 && (!pth || (reinterpret_cast<uintptr_t>(pth) & 15) == 0);
+                while (dd > de && h >= 0 && (!wide || (dd & 3) != 0)) one();
+                for (; dd - 4 >= de && h >= 0; dd -= 4) {
+                    uint32_t lw = 0;
+                    uint32_t tw[4];
+    #pragma unroll
+                    for (int j = 3; j >= 0; --j) {  // positions dd-1 (j = 3) ... dd-4 (j = 0)
+                        const int e = *rec_at(h);
+                        lw |= (uint32_t)((e & 7) + 1) << (8 * j);
+                        tw[j] = pth ? time_of(h) : 0u;
+                        h = (e >> 3) - 1;
+                    }
+                    *reinterpret_cast<uint32_t *>(lab + dd - 4) = lw;
+                    if (pth) *reinterpret_cast<uint4 *>(pth + dd - 4) = make_uint4(tw[0], tw[1], tw[2], tw[3]);
                 }
-                *reinterpret_cast<uint32_t *>(lab + dd - 4) = lw;
-                if (pth) *reinterpret_cast<uint4 *>(pth + dd - 4) = make_uint4(tw[0], tw[1], tw[2], tw[3]);
+                while (dd > de && h >= 0) one();
             }
-            while (dd > de && h >= 0) one();
+            __builtin_amdgcn_wave_barrier();
+            h0 = nh;
+            d0 = nd;
         }
-        __builtin_amdgcn_wave_barrier();
-        h0 = nh;
-        d0 = nd;
+        if (!NB || ++hy >= nb) break;
+        lab += p.out.out_stride;  // the next hypothesis: entry hy, row r * nb + hy
+        if (pth) pth += p.out.out_stride;
+        h0 = bperm(hbase + hy, node);
+        d0 = bperm(hbase + hy, (alive && hy < n_hyp) ? depth : 0);
+        j0 = bperm(hbase + hy, jump);
     }
     if (p.arena.pool) slab_pool::push(p.arena.pool, pool_id, lane);
 }
 
-template <int N, bool AMB, bool CRF, bool PDQ>
+template <int N, bool AMB, bool CRF, bool PDQ, bool NB = false>
 hipError_t launch_nap(const LaneParams &p, int64_t n_reads, hipStream_t stream) {
     if (beam_lane_reads_per_wave(p.a.beam_size) == 2 && !p.arena.retry_counter) {  // two reads per wavefront
-        hipLaunchKernelGGL((beam_lane_kernel<N, 2, AMB, CRF, PDQ>), dim3((unsigned)((n_reads + 1) / 2)), dim3(64), 0, stream, p);
+        hipLaunchKernelGGL((beam_lane_kernel<N, 2, AMB, CRF, PDQ, NB>), dim3((unsigned)((n_reads + 1) / 2)), dim3(64), 0, stream, p);
     } else {
-        hipLaunchKernelGGL((beam_lane_kernel<N, 1, AMB, CRF, PDQ>), dim3((unsigned)n_reads), dim3(64), 0, stream, p);
+        hipLaunchKernelGGL((beam_lane_kernel<N, 1, AMB, CRF, PDQ, NB>), dim3((unsigned)n_reads), dim3(64), 0, stream, p);
     }
     return hipGetLastError();
 }
 
 template <int N, bool AMB, bool CRF>
 hipError_t launch_na(const LaneParams &p, int64_t n_reads, hipStream_t stream) {
+    if (p.nb.n_best > 0)  // n-best layout
+        return p.a.tie_order == FCD_TIE_PDQ178 ? launch_nap<N, AMB, CRF, true, true>(p, n_reads, stream)
+                                               : launch_nap<N, AMB, CRF, false, true>(p, n_reads, stream);
     return p.a.tie_order == FCD_TIE_PDQ178 ? launch_nap<N, AMB, CRF, true>(p, n_reads, stream)
                                            : launch_nap<N, AMB, CRF, false>(p, n_reads, stream);
 }
@@ -1102,14 +1127,17 @@ hipError_t lane_tie_prof_read(unsigned long long *out16, bool reset) {
 // ---- the device-side slab pool (slab_pool.h): how many wavefronts of an instantiation the chip holds, and the ring's set-up
 namespace {
 template <int N, bool AMB, bool CRF, bool PDQ>
-const void *kernel_nap(int rpw) {
+const void *kernel_nap(int rpw, bool nb) {
+    if (nb)
+        return rpw == 2 ? reinterpret_cast<const void *>(&beam_lane_kernel<N, 2, AMB, CRF, PDQ, true>)
+                        : reinterpret_cast<const void *>(&beam_lane_kernel<N, 1, AMB, CRF, PDQ, true>);
     return rpw == 2 ? reinterpret_cast<const void *>(&beam_lane_kernel<N, 2, AMB, CRF, PDQ>)
                     : reinterpret_cast<const void *>(&beam_lane_kernel<N, 1, AMB, CRF, PDQ>);
 }
 template <int N, bool CRF>
-const void *kernel_n(int rpw, bool amb, bool pdq) {
-    if (amb) return pdq ? kernel_nap<N, true, CRF, true>(rpw) : kernel_nap<N, true, CRF, false>(rpw);
-    return pdq ? kernel_nap<N, false, CRF, true>(rpw) : kernel_nap<N, false, CRF, false>(rpw);
+const void *kernel_n(int rpw, bool amb, bool pdq, bool nb) {
+    if (amb) return pdq ? kernel_nap<N, true, CRF, true>(rpw, nb) : kernel_nap<N, true, CRF, false>(rpw, nb);
+    return pdq ? kernel_nap<N, false, CRF, true>(rpw, nb) : kernel_nap<N, false, CRF, false>(rpw, nb);
 }
 __global__ void slab_pool_init_kernel(unsigned long long *pool, int slabs) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1125,23 +1153,23 @@ __global__ void slab_pool_init_kernel(unsigned long long *pool, int slabs) {
 
 int beam_lane_reads_per_wave(int beam_size) { return beam_size <= 32 ? 2 : 1; }
 
-int beam_lane_resident_waves(int beam_size, int N, int crf, bool first_pass, bool ambiguous, int tie_order) {
+int beam_lane_resident_waves(int beam_size, int N, int crf, bool first_pass, bool ambiguous, int tie_order, bool nbest) {
 #ifdef FCD_HIPEMU
-    (void)beam_size, (void)N, (void)crf, (void)first_pass, (void)ambiguous, (void)tie_order;
+    (void)beam_size, (void)N, (void)crf, (void)first_pass, (void)ambiguous, (void)tie_order, (void)nbest;
     return 3;  // (blocks run one after the other there: a small pool makes every later block reuse a slab)
 #else
     const int rpw = first_pass ? beam_lane_reads_per_wave(beam_size) : 1;
     const bool pdq = tie_order == FCD_TIE_PDQ178;
     const void *k = nullptr;
-    if (crf) k = kernel_n<5, true>(rpw, ambiguous, pdq);
+    if (crf) k = kernel_n<5, true>(rpw, ambiguous, pdq, nbest);
     else switch (N) {
-        case 2: k = kernel_n<2, false>(rpw, ambiguous, pdq); break;
-        case 3: k = kernel_n<3, false>(rpw, ambiguous, pdq); break;
-        case 4: k = kernel_n<4, false>(rpw, ambiguous, pdq); break;
-        case 5: k = kernel_n<5, false>(rpw, ambiguous, pdq); break;
-        case 6: k = kernel_n<6, false>(rpw, ambiguous, pdq); break;
-        case 7: k = kernel_n<7, false>(rpw, ambiguous, pdq); break;
-        case 8: k = kernel_n<8, false>(rpw, ambiguous, pdq); break;
+        case 2: k = kernel_n<2, false>(rpw, ambiguous, pdq, nbest); break;
+        case 3: k = kernel_n<3, false>(rpw, ambiguous, pdq, nbest); break;
+        case 4: k = kernel_n<4, false>(rpw, ambiguous, pdq, nbest); break;
+        case 5: k = kernel_n<5, false>(rpw, ambiguous, pdq, nbest); break;
+        case 6: k = kernel_n<6, false>(rpw, ambiguous, pdq, nbest); break;
+        case 7: k = kernel_n<7, false>(rpw, ambiguous, pdq, nbest); break;
+        case 8: k = kernel_n<8, false>(rpw, ambiguous, pdq, nbest); break;
     }
     int dev = 0;
     if (!k || hipGetDevice(&dev) != hipSuccess) return 256 * 4 * 8;  // (every wave slot of the chip)
@@ -1175,9 +1203,9 @@ bool beam_lane_supported(int beam_size, int N, int crf, int S) {
 }
 
 hipError_t launch_beam_lane(const BatchDesc &in, int64_t read_begin, int64_t n_reads, const BeamArgs &a,
-                            const WaveArena &arena, const ResultDesc &out, hipStream_t stream) {
+                            const WaveArena &arena, const ResultDesc &out, hipStream_t stream, const NBestDesc &nb) {
     if (n_reads <= 0) return hipSuccess;
-    LaneParams p{in, a, arena, out, read_begin};
+    LaneParams p{in, a, arena, out, read_begin, nb};
     p.in.n_reads = n_reads;
     if (a.crf) {
         if (!beam_lane_supported(a.beam_size, in.N, 1, in.S)) return hipErrorInvalidValue;

@@ -73,6 +73,7 @@ struct WaveParams {
     WaveArena arena;
     ResultDesc out;
     int64_t read_begin;
+    NBestDesc nb;  // (last: fcd_internal.h)
 };
 
 __device__ __forceinline__ int bperm(int src_lane, int v) {
@@ -123,7 +124,11 @@ constexpr int kSeg = 64;  // nodes per traceback segment (jump-pointer spacing)
 // reads on the BASELINE generator) the half builds the node-ordered candidate list in LDS, the wavefront replays the
 // quicksort on it (pdq178_wave.h) and the ranks it produces replace the exact ones.  Instantiated only for shapes
 // that can hold more than 20 candidates.
-template <int N, int GW, int RPW, int S, bool AMB, bool PROF = false, bool UNI = false, bool H16 = false, bool PDQ = false>
+// NB: the n-best layout (NBestDesc::n_best > 0): after the time loop the first n_best beam slots are traced back, each
+// from its own group's (node, depth, jump), into rows r * n_best + i, with their scores and the read's n_hyp.  The time
+// loop is the same; a separate instantiation keeps the single-result kernels as they are.
+template <int N, int GW, int RPW, int S, bool AMB, bool PROF = false, bool UNI = false, bool H16 = false, bool PDQ = false,
+          bool NB = false>
 __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_per_eu((RPW == 2 && !AMB) ? 4 : 1))) void beam_wave_kernel(WaveParams p) {
     constexpr bool CRF = S != 0;
     constexpr bool GATHER = S == kCrfGather;
@@ -271,7 +276,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_pe
         if ((bad || state >= (GATHER ? p.in.S : S)) && T > 0) {
             if (q == 0) {
                 p.out.status[r] = FCD_ST_BAD_STATE;
-                p.out.out_len[r] = 0;
+                if (!NB) p.out.out_len[r] = 0;  // (n-best rows: the epilogue)
             }
             alive = false;
             state = 0;
@@ -355,77 +360,93 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_pe
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     const int32_t *rec = rec_w + hoff;
     const int32_t *jmp = jmp_w + hoff;
-    uint8_t *lab = p.out.labels + r * p.out.out_stride;
-    uint32_t *pth = p.out.path ? p.out.path + r * p.out.out_stride : nullptr;
+    // NB: hypothesis i is beam slot i (group i); nb <= beam_size <= BCAP (capi.hip), so every source lane is in the half
+    const int nb = NB ? (int)p.nb.n_best : 1;
+    const int n_hyp = NB ? (alive ? (B < nb ? B : nb) : 0) : 1;
     if (q == 0 && alive) {
-        p.out.out_len[r] = (uint32_t)depth;
+        if (!NB) p.out.out_len[r] = (uint32_t)depth;
         p.out.status[r] = FCD_ST_OK;
     }
     if (AMB && q == 0 && has_read) {
         p.out.ambiguous[2 * r] = (uint32_t)n_amb;
         p.out.ambiguous[2 * r + 1] = (uint32_t)n_crit;
     }
+    if (NB) {  // lane q of the half: row q's length and score (slot q's probability(), :278); rows past n_hyp are empty
+        const int sq = hbase + (q < BCAP ? q : 0) * GW;
+        const float sc = bpermf(sq, lp) + bpermf(sq, gp);
+        const int dq = bperm(sq, depth);
+        if (has_read && q < nb) {
+            p.out.out_len[r * nb + q] = q < n_hyp ? (uint32_t)dq : 0u;
+            p.nb.score[r * nb + q] = q < n_hyp ? sc : 0.0f;
+        }
+        if (has_read && q == 0) p.nb.n_hyp[r] = (uint32_t)n_hyp;
+    }
     int *heads = s_heads[wave];
-    // beam[0] lives in group 0: every lane of the half takes ITS leaf and depth
-    int h0 = bperm(hbase, node);               // current chunk's first segment head
-    int d0 = bperm(hbase, alive ? depth : 0);  // its depth; 0 == nothing left
-    int j0 = bperm(hbase, jump);               // the leaf's own jump pointer (from its beam entry)
-    while (ballot(d0 > 0) != 0ull) {
-        // phase 1: one lane hops along the jump pointers, collecting up to HALF segment heads
-        int cnt = 0, nh = h0, nd = d0;
-        if (q == 0) {
-            while (cnt < HALF && nd > 0) {
-                heads[hbase + cnt] = nh;
-                // the leaf may sit at any depth and brings its jump pointer along; every later head
-                // sits at a multiple of 64 and has it stored
-                nh = (nd % kSeg != 0) ? j0 : jmp[nh];
-                nd = ((nd - 1) / kSeg) * kSeg;
-                ++cnt;
-            }
-        }
-        cnt = bperm(hbase, cnt);
-        nh = bperm(hbase, nh);
-        nd = bperm(hbase, nd);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        // phase 2: lane q walks segment q: depths (d_q, d_{q+1}]
-        if (q < cnt) {
-            const int d1 = ((d0 - 1) / kSeg) * kSeg;
-            const int ds = q == 0 ? d0 : d1 - (q - 1) * kSeg;
-            const int de = q == 0 ? d1 : ds - kSeg;
-            int h = heads[hbase + q];
-            int dd = ds;
-            auto one = [&]() {  // emit position dd - 1, step to the parent
-                const int e = rec[h];
-                lab[dd - 1] = (uint8_t)((e & 7) + 1);
-                if (pth) pth[dd - 1] = (uint32_t)(h >> KS);  // the step that created the node
-                h = (e >> 3) - 1;
-                --dd;
-            };
-            // A lane's 64 byte-sized label stores (and 64 path words), each to a line of its own, cost more than
-            // the pointer chase: when the rows are aligned, four positions are collected and leave as one 4-byte and
-            // one 16-byte store.  Only the leaf's segment can start off a multiple of four.
-            const bool wide = (reinterpret_cast<uintptr_t>(lab) & 3) == 0 && (!pth || (reinterpret_cast<uintptr_t>(pth) & 15) == 0);
-            while (dd > de && h >= 0 && (!wide || (dd & 3) != 0)) one();
-            for (; dd - 4 >= de && h >= 0; dd -= 4) {  // (de is a multiple of 64: whole groups down to the segment's end)
-                uint32_t lw = 0;
-                uint32_t tw[4];
-#pragma unroll
-                for (int j = 3; j >= 0; --j) {  // positions dd-1 (j = 3) ... dd-4 (j = 0)
-                    const int e = rec[h];
-                    lw |= (uint32_t)((e & 7) + 1) << (8 * j);
-                    tw[j] = (uint32_t)(h >> KS);
-                    h = (e >> 3) - 1;
+    for (int hy = 0; hy < (NB ? nb : 1); ++hy) {
+        uint8_t *lab = p.out.labels + (NB ? r * nb + hy : r) * p.out.out_stride;
+        uint32_t *pth = p.out.path ? p.out.path + (NB ? r * nb + hy : r) * p.out.out_stride : nullptr;
+        // beam[hy] lives in group hy: every lane of the half takes ITS leaf and depth
+        const int src = hbase + hy * GW;
+        int h0 = bperm(src, node);                               // current chunk's first segment head
+        int d0 = bperm(src, (alive && hy < n_hyp) ? depth : 0);  // its depth; 0 == nothing left
+        int j0 = bperm(src, jump);                               // the leaf's own jump pointer (from its beam entry)
+        while (ballot(d0 > 0) != 0ull) {
+            // phase 1: one lane hops along the jump pointers, collecting up to HALF segment heads
+            int cnt = 0, nh = h0, nd = d0;
+            if (q == 0) {
+                while (cnt < HALF && nd > 0) {
+                    heads[hbase + cnt] = nh;
+                    // the leaf may sit at any depth and brings its jump pointer along; every later head
+                    // sits at a multiple of 64 and has it stored
+                    nh = (nd % kSeg != 0) ? j0 : jmp[nh];
+                    nd = ((nd - 1) / kSeg) * kSeg;
+                    ++cnt;
                 }
-                *reinterpret_cast<uint32_t *>(lab + dd - 4) = lw;
-                if (pth) *reinterpret_cast<uint4 *>(pth + dd - 4) = make_uint4(tw[0], tw[1], tw[2], tw[3]);
             }
-            while (dd > de && h >= 0) one();
+            cnt = bperm(hbase, cnt);
+            nh = bperm(hbase, nh);
+            nd = bperm(hbase, nd);
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            // phase 2: lane q walks segment q: depths (d_q, d_{q+1}]
+            if (q < cnt) {
+                const int d1 = ((d0 - 1) / kSeg) * kSeg;
+                const int ds = q == 0 ? d0 : d1 - (q - 1) * kSeg;
+                const int de = q == 0 ? d1 : ds - kSeg;
+                int h = heads[hbase + q];
+                int dd = ds;
+                auto one = [&]() {  // emit position dd - 1, step to the parent
+                    const int e = rec[h];
+                    lab[dd - 1] = (uint8_t)((e & 7) + 1);
+                    if (pth) pth[dd - 1] = (uint32_t)(h >> KS);  // the step that created the node
+                    h = (e >> 3) - 1;
+                    --dd;
+                };
+                // A lane's 64 byte-sized label stores (and 64 path words), each to a line of its own, cost more than
+                // the pointer chase: when the rows are aligned, four positions are collected and leave as one 4-byte and
+                // one 16-byte store.  Only the leaf's segment can start off a multiple of four.
+                const bool wide = (reinterpret_cast<uintptr_t>(lab) & 3) == 0 && (!pth || (reinterpret_cast<uintptr_t>(pth) & 15) == 0);
+                while (dd > de && h >= 0 && (!wide || (dd & 3) != 0)) one();
+                for (; dd - 4 >= de && h >= 0; dd -= 4) {  // (de is a multiple of 64: whole groups down to the segment's end)
+                    uint32_t lw = 0;
+                    uint32_t tw[4];
+    #pragma unroll
+                    for (int j = 3; j >= 0; --j) {  // positions dd-1 (j = 3) ... dd-4 (j = 0)
+                        const int e = rec[h];
+                        lw |= (uint32_t)((e & 7) + 1) << (8 * j);
+                        tw[j] = (uint32_t)(h >> KS);
+                        h = (e >> 3) - 1;
+                    }
+                    *reinterpret_cast<uint32_t *>(lab + dd - 4) = lw;
+                    if (pth) *reinterpret_cast<uint4 *>(pth + dd - 4) = make_uint4(tw[0], tw[1], tw[2], tw[3]);
+                }
+                while (dd > de && h >= 0) one();
+            }
+            __builtin_amdgcn_wave_barrier();
+            h0 = nh;
+            d0 = nd;
         }
-        __builtin_amdgcn_wave_barrier();
-        h0 = nh;
-        d0 = nd;
     }
 }
 
@@ -433,6 +454,15 @@ template <int N, int GW, int RPW, int S, bool PDQ>
 hipError_t launch_tp(const WaveParams &p, int64_t n_reads, hipStream_t stream) {
     const int64_t waves = (n_reads + RPW - 1) / RPW;
     const unsigned blocks = (unsigned)((waves + kWavesPerBlock - 1) / kWavesPerBlock);
+    if (p.nb.n_best > 0) {  // n-best layout: the general instantiation (any element type, ragged lengths)
+        if (p.out.ambiguous)
+            hipLaunchKernelGGL((beam_wave_kernel<N, GW, RPW, S, true, false, false, true, PDQ, true>), dim3(blocks),
+                               dim3(64 * kWavesPerBlock), 0, stream, p);
+        else
+            hipLaunchKernelGGL((beam_wave_kernel<N, GW, RPW, S, false, false, false, true, PDQ, true>), dim3(blocks),
+                               dim3(64 * kWavesPerBlock), 0, stream, p);
+        return hipGetLastError();
+    }
     if (p.in.dtype != kF32) {  // half-precision posteriors: the general instantiations only
         if (p.out.ambiguous)
             hipLaunchKernelGGL((beam_wave_kernel<N, GW, RPW, S, true, false, false, true, PDQ>), dim3(blocks),
@@ -482,9 +512,9 @@ bool beam_wave_supported(int beam_size, int N, int crf, int S) {
 
 hipError_t launch_beam_wave(const BatchDesc &in, int64_t read_begin, int64_t n_reads,
                             const BeamArgs &a, const WaveArena &arena, const ResultDesc &out,
-                            hipStream_t stream) {
+                            hipStream_t stream, const NBestDesc &nb) {
     if (n_reads <= 0) return hipSuccess;
-    WaveParams p{in, a, arena, out, read_begin};
+    WaveParams p{in, a, arena, out, read_begin, nb};
     p.in.n_reads = n_reads;  // reads in this launch
     const bool two = a.beam_size <= 5 && in.N <= 5 && !a.force_one_read_per_wave;
     const bool wide = a.beam_size > 8;  // 9..12 beam slots: groups of five lanes

@@ -122,7 +122,7 @@
             if (f_nan || f_empty) {
                 if (q == 0) {
                     p.out.status[r] = f_empty ? FCD_ST_RAN_OUT_OF_BEAM : FCD_ST_INCOMPARABLE;
-                    p.out.out_len[r] = 0;
+                    if (!NB) p.out.out_len[r] = 0;  // (n-best rows: the epilogue)
                 }
                 alive = false;
                 if (UNI) n_valid = 0;  // the failed read keeps an empty beam from here on

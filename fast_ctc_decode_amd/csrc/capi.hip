@@ -134,6 +134,16 @@ int check_result(fcd_handle *h, const fcd_batch *in, const fcd_result *out, bool
     return FCD_OK;
 }
 
+// the n-best form (fcd_*_nbest_*): `out` has n_reads * n_best rows, `nb` the scores and hypothesis counts
+int check_result_nbest(fcd_handle *h, const fcd_batch *in, const fcd_result *out, const fcd_nbest *nb, int64_t beam_size) {
+    if (!nb) return fail(h, FCD_E_INVALID, "null n-best description");
+    if (nb->n_best < 1 || nb->n_best > beam_size) return fail(h, FCD_E_INVALID, "n_best must be in 1 .. beam_size");
+    int rc = check_result(h, in, out, true);
+    if (rc) return rc;
+    if (in->n_reads > 0 && (!nb->score || !nb->n_hyp)) return fail(h, FCD_E_INVALID, "null score/n_hyp");
+    return FCD_OK;
+}
+
 BatchDesc to_desc(const fcd_batch *in, bool crf) {
     BatchDesc d;
     d.post = static_cast<const float *>(in->post);  // (typed by `dtype`; the kernels convert on load)
@@ -212,14 +222,17 @@ class CallScope {
         if (ptr && bytes && f_.n < fcd_handle::kMaxRanges)
             f_.r[f_.n++] = {reinterpret_cast<uintptr_t>(ptr), reinterpret_cast<uintptr_t>(ptr) + bytes};
     }
-    void add(const ResultDesc &o, int64_t n_reads) {
-        const size_t rows = (size_t)n_reads * (size_t)o.out_stride;
+    void add(const ResultDesc &o, int64_t n_reads, const NBestDesc &nb = NBestDesc{}) {
+        const size_t n_rows = (size_t)n_reads * (size_t)(nb.n_best > 0 ? nb.n_best : 1);  // (n-best: n_best rows per read)
+        const size_t rows = n_rows * (size_t)o.out_stride;
         add(o.labels, rows);
         add(o.path, rows * 4);
         add(o.qual, rows * 4);
-        add(o.out_len, (size_t)n_reads * 4);
+        add(o.out_len, n_rows * 4);
         add(o.status, (size_t)n_reads * 4);
         add(o.ambiguous, (size_t)n_reads * 8);
+        add(nb.score, n_rows * 4);
+        add(nb.n_hyp, (size_t)n_reads * 4);
     }
 
     int begin(bool may_overlap, bool exclusive) {
@@ -347,13 +360,14 @@ class CallScope {
     }
 };
 
-// Shared driver of search::beam_search and search::crf_beam_search on device buffers.
+// Shared driver of search::beam_search and search::crf_beam_search on device buffers.  nb (nullable): the n-best
+// layout of fcd_*_nbest_dev -- the same kernels, chunking and retry, with n_best result rows per read.
 int beam_dev(fcd_handle *h, const fcd_batch *in, const BeamArgs &a, int kernel,
-             const fcd_result *out) {
+             const fcd_result *out, const fcd_nbest *nb = nullptr) {
     const bool crf = a.crf != 0;
     int rc = check_batch(h, in, crf);
     if (rc) return rc;
-    rc = check_result(h, in, out, true);
+    rc = nb ? check_result_nbest(h, in, out, nb, a.beam_size) : check_result(h, in, out, true);
     if (rc) return rc;
     if (a.beam_size < 1) return fail(h, FCD_E_INVALID, "beam_size cannot be 0");
     if (in->N < 2) return fail(h, FCD_E_UNSUPPORTED, "alphabet needs at least one label besides the blank");
@@ -362,6 +376,7 @@ int beam_dev(fcd_handle *h, const fcd_batch *in, const BeamArgs &a, int kernel,
 
     const BatchDesc d = to_desc(in, crf);
     const ResultDesc o = to_desc(out);
+    const NBestDesc nbd = nb ? NBestDesc{nb->score, nb->n_hyp, nb->n_best} : NBestDesc{};
     const int N = d.N, NL = N - 1;
     int64_t beam = a.beam_size;
     BeamArgs args = a;
@@ -449,7 +464,7 @@ int beam_dev(fcd_handle *h, const fcd_batch *in, const BeamArgs &a, int kernel,
         return ar;
     };
     CallScope sc(h);
-    sc.add(o, d.n_reads);
+    sc.add(o, d.n_reads, nbd);
     if (two_pass) {
         // ---- slabs from the device-side pool (slab_pool.h): the arena is sized by what the chip holds at once, one
         // launch takes the whole job, and calls on the overlap streams share it ----
@@ -467,14 +482,14 @@ int beam_dev(fcd_handle *h, const fcd_batch *in, const BeamArgs &a, int kernel,
         const size_t wave_bytes = (size_t)rpw * ((size_t)cap_nodes * node_bytes + first_bytes);
         const int64_t waves = (d.n_reads + rpw - 1) / rpw;
         const bool amb = o.ambiguous != nullptr;
-        int64_t p1_want = std::min<int64_t>(slab_pool::kMaxSlabs, beam_lane_resident_waves((int)beam, N, a.crf, true, amb, args.tie_order));
+        int64_t p1_want = std::min<int64_t>(slab_pool::kMaxSlabs, beam_lane_resident_waves((int)beam, N, a.crf, true, amb, args.tie_order, nb != nullptr));
         if (h->overlap_n < 2) p1_want = std::min<int64_t>(p1_want, waves);  // (overlapping calls: whatever the chip holds)
         // the retry pass: a few worst-case slabs however small the job -- never less than one: a read that overflowed
         // must be decodable -- and no more than a quarter of the workspace limit
         int64_t p2 = 0;
         if (retry_needed) {
             p2 = std::min<int64_t>(std::min<int64_t>(d.n_reads, kRetrySlabs),
-                                   beam_lane_resident_waves((int)beam, N, a.crf, false, amb, args.tie_order));
+                                   beam_lane_resident_waves((int)beam, N, a.crf, false, amb, args.tie_order, nb != nullptr));
             p2 = std::max<int64_t>(1, std::min<int64_t>(p2, budget / 4 / (int64_t)worst_read));
         }
         const int64_t left = budget - p2 * (int64_t)worst_read;
@@ -537,7 +552,7 @@ int beam_dev(fcd_handle *h, const fcd_batch *in, const BeamArgs &a, int kernel,
         sc.time();
         WaveArena ar = wave_arena(base, (int64_t)g.p1 * rpw, cap_nodes);
         ar.pool = ring1;
-        FCD_HIP(h, launch_beam_lane(d, 0, d.n_reads, args, ar, o, S));
+        FCD_HIP(h, launch_beam_lane(d, 0, d.n_reads, args, ar, o, S, nbd));
         if (retry_needed) {
             // every read that overflowed is decoded again in a worst-case slab, where it cannot overflow; a wavefront of
             // this pass that finds no slab free waits for one (the pool is a queue), so ONE launch finishes the job
@@ -549,7 +564,7 @@ int beam_dev(fcd_handle *h, const fcd_batch *in, const BeamArgs &a, int kernel,
             rr.pool = ring2;
             rr.retry_counter = d_counter;
             FCD_HIP(h, hipMemsetAsync(d_counter, 0, sizeof(int32_t), S));
-            FCD_HIP(h, launch_beam_lane(d, 0, d.n_reads, args, rr, o, S));
+            FCD_HIP(h, launch_beam_lane(d, 0, d.n_reads, args, rr, o, S, nbd));
             // how many reads overflowed is read back ONE CALL LATE: it only steers the sizing of later jobs
             if (h->retry_host && !h->retry_pending) {
                 FCD_HIP(h, hipMemcpyAsync(h->retry_host, d_counter, sizeof(int32_t), hipMemcpyDeviceToHost, S));
@@ -574,13 +589,13 @@ int beam_dev(fcd_handle *h, const fcd_batch *in, const BeamArgs &a, int kernel,
         const int64_t n = std::min<int64_t>(chunk, d.n_reads - begin);
         if (use_wave || use_lane) {
             const WaveArena ar = wave_arena(abase, chunk, cap_nodes);
-            FCD_HIP(h, use_lane ? launch_beam_lane(d, begin, n, args, ar, o, S) : launch_beam_wave(d, begin, n, args, ar, o, S));
+            FCD_HIP(h, use_lane ? launch_beam_lane(d, begin, n, args, ar, o, S, nbd) : launch_beam_wave(d, begin, n, args, ar, o, S, nbd));
         } else {
             GenericArena ar;
             ar.cap_nodes = cap_nodes;
             ar.rec = reinterpret_cast<int4 *>(abase);
             ar.rows = reinterpret_cast<int32_t *>(abase + (size_t)chunk * cap_nodes * sizeof(int4));
-            FCD_HIP(h, launch_beam_generic(d, begin, n, args, ar, o, S));
+            FCD_HIP(h, launch_beam_generic(d, begin, n, args, ar, o, S, nbd));
         }
     }
     return sc.finish();
@@ -991,6 +1006,37 @@ int fcd_crf_beam_search_dev_k(fcd_handle *h, const fcd_batch *in, const float *i
     a.n_init = n_init;
     a.init_stride = init_stride;
     return beam_dev(h, in, a, kernel, out);
+}
+
+int fcd_beam_search_nbest_dev(fcd_handle *h, const fcd_batch *in, int64_t beam_size, float beam_cut_threshold,
+                              int collapse_repeats, int kernel, const fcd_nbest *nb, const fcd_result *out) {
+    if (!h) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> g(h->mu);
+    if (beam_size < 1) return fail(h, FCD_E_INVALID, "beam_size cannot be 0");
+    BeamArgs a{};
+    a.beam_size = (int)std::min<int64_t>(beam_size, 1ll << 30);
+    a.thr = beam_cut_threshold;
+    a.collapse = collapse_repeats ? 1 : 0;
+    a.crf = 0;
+    return beam_dev(h, in, a, kernel, out, nb);
+}
+
+int fcd_crf_beam_search_nbest_dev(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init,
+                                  int64_t init_stride, int64_t beam_size, float beam_cut_threshold, int kernel,
+                                  const fcd_nbest *nb, const fcd_result *out) {
+    if (!h) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> g(h->mu);
+    if (beam_size < 1) return fail(h, FCD_E_INVALID, "beam_size cannot be 0");
+    if (!init || n_init < 1) return fail(h, FCD_E_INVALID, "init_state missing");
+    BeamArgs a{};
+    a.beam_size = (int)std::min<int64_t>(beam_size, 1ll << 30);
+    a.thr = beam_cut_threshold;
+    a.collapse = 0;
+    a.crf = 1;
+    a.init = init;
+    a.n_init = n_init;
+    a.init_stride = init_stride;
+    return beam_dev(h, in, a, kernel, out, nb);
 }
 
 int fcd_crf_greedy_search_dev(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init,
@@ -1547,7 +1593,8 @@ int host_upload(fcd_handle *h, const fcd_batch *in, const fcd_result *shape, con
     const int64_t B = in->n_reads;
     st->B = B;
     st->n_in = (size_t)span_elems(in, crf);
-    st->n_out = (size_t)B * (size_t)shape->out_stride;
+    st->n_rows = (size_t)B * (size_t)(c.n_best > 0 ? c.n_best : 1);
+    st->n_out = st->n_rows * (size_t)shape->out_stride;
     st->n_init = crf ? (size_t)((B - 1) * c.init_stride + c.n_init) : 0;
     size_t used = 0;
     auto reserve = [&](size_t bytes) {
@@ -1562,10 +1609,12 @@ int host_upload(fcd_handle *h, const fcd_batch *in, const fcd_result *shape, con
     st->o_lab = reserve(st->n_out);
     st->o_path = reserve(shape->path ? st->n_out * 4 : 0);
     st->o_qual = reserve(shape->qual ? st->n_out * 4 : 0);
-    st->o_olen = reserve((size_t)B * 4);
+    st->o_olen = reserve(st->n_rows * 4);
     st->o_stat = reserve((size_t)B * 4);
     st->want_amb = shape->ambiguous && (c.op == HostOp::Beam || c.op == HostOp::CrfBeam);
     st->o_amb = reserve(st->want_amb ? (size_t)B * 8 : 0);
+    st->o_score = reserve(c.n_best > 0 ? st->n_rows * 4 : 0);
+    st->o_nhyp = reserve(c.n_best > 0 ? (size_t)B * 4 : 0);
     st->used = used;
     const bool mirror = allow_mirror && used <= ((size_t)4 << 20);
     st->mirror = mirror;
@@ -1615,6 +1664,15 @@ int host_upload(fcd_handle *h, const fcd_batch *in, const fcd_result *shape, con
 int host_search(fcd_handle *h, const HostStage &st, const fcd_batch *din, const HostCall &c, const fcd_result *dout) {
     const float *dinit = reinterpret_cast<const float *>(reinterpret_cast<char *>(h->stage) + st.o_init);
     int rc = FCD_E_INVALID;
+    if (c.n_best > 0 && (c.op == HostOp::Beam || c.op == HostOp::CrfBeam)) {
+        char *base = reinterpret_cast<char *>(h->stage);
+        const fcd_nbest dnb{c.n_best, reinterpret_cast<float *>(base + st.o_score), reinterpret_cast<uint32_t *>(base + st.o_nhyp)};
+        rc = c.op == HostOp::Beam
+                 ? fcd_beam_search_nbest_dev(h, din, c.beam_size, c.thr, c.collapse, c.kernel, &dnb, dout)
+                 : fcd_crf_beam_search_nbest_dev(h, din, dinit, c.n_init, c.init_stride, c.beam_size, c.thr, c.kernel, &dnb, dout);
+        if (rc == FCD_OK && h->overlap_n >= 2) rc = overlap_join(h, h->stream);
+        return rc;
+    }
     switch (c.op) {
         case HostOp::Viterbi: return fcd_viterbi_search_dev(h, din, c.collapse, dout);
         case HostOp::Beam: rc = fcd_beam_search_dev(h, din, c.beam_size, c.thr, c.collapse, c.kernel, dout); break;
@@ -1629,8 +1687,9 @@ int host_search(fcd_handle *h, const HostStage &st, const fcd_batch *din, const 
 }
 
 // Copies the fixed-stride device result of a staged call into the caller's arrays and waits.
-int host_download(fcd_handle *h, const HostStage &st, const fcd_result &dout, const fcd_result *out) {
+int host_download(fcd_handle *h, const HostStage &st, const fcd_result &dout, const fcd_result *out, const fcd_nbest *nb) {
     const size_t B = (size_t)st.B;
+    const size_t rows = st.n_rows;
     if (st.mirror) {
         char *pin = reinterpret_cast<char *>(h->pin);
         char *base = reinterpret_cast<char *>(h->stage);
@@ -1639,18 +1698,27 @@ int host_download(fcd_handle *h, const HostStage &st, const fcd_result &dout, co
         memcpy(out->labels, pin + st.o_lab, st.n_out);
         if (out->path) memcpy(out->path, pin + st.o_path, st.n_out * 4);
         if (out->qual) memcpy(out->qual, pin + st.o_qual, st.n_out * 4);
-        memcpy(out->out_len, pin + st.o_olen, B * 4);
+        memcpy(out->out_len, pin + st.o_olen, rows * 4);
         if (out->status) memcpy(out->status, pin + st.o_stat, B * 4);
         if (st.want_amb) memcpy(out->ambiguous, pin + st.o_amb, B * 8);
+        if (nb) {
+            memcpy(nb->score, pin + st.o_score, rows * 4);
+            memcpy(nb->n_hyp, pin + st.o_nhyp, B * 4);
+        }
         return FCD_OK;
     }
     FCD_HIP(h, hipMemcpyAsync(out->labels, dout.labels, st.n_out, hipMemcpyDeviceToHost, h->stream));
     if (out->path) FCD_HIP(h, hipMemcpyAsync(out->path, dout.path, st.n_out * 4, hipMemcpyDeviceToHost, h->stream));
     if (out->qual) FCD_HIP(h, hipMemcpyAsync(out->qual, dout.qual, st.n_out * 4, hipMemcpyDeviceToHost, h->stream));
-    FCD_HIP(h, hipMemcpyAsync(out->out_len, dout.out_len, B * 4, hipMemcpyDeviceToHost, h->stream));
+    FCD_HIP(h, hipMemcpyAsync(out->out_len, dout.out_len, rows * 4, hipMemcpyDeviceToHost, h->stream));
     if (out->status) FCD_HIP(h, hipMemcpyAsync(out->status, dout.status, B * 4, hipMemcpyDeviceToHost, h->stream));
     if (st.want_amb)
         FCD_HIP(h, hipMemcpyAsync(out->ambiguous, dout.ambiguous, B * 8, hipMemcpyDeviceToHost, h->stream));
+    if (nb) {
+        char *base = reinterpret_cast<char *>(h->stage);
+        FCD_HIP(h, hipMemcpyAsync(nb->score, base + st.o_score, rows * 4, hipMemcpyDeviceToHost, h->stream));
+        FCD_HIP(h, hipMemcpyAsync(nb->n_hyp, base + st.o_nhyp, B * 4, hipMemcpyDeviceToHost, h->stream));
+    }
     FCD_HIP(h, hipStreamSynchronize(h->stream));
     return FCD_OK;
 }
@@ -1677,6 +1745,28 @@ int run_host(fcd_handle *h, const fcd_batch *in, const fcd_result *out, const Ho
     if (rc == FCD_OK) rc = host_search(h, st, &din, c, &dout);
     if (rc) return rc;
     return host_download(h, st, dout, out);
+}
+
+// the n-best forms: stage, decode, copy back -- never the chunk pipeline of hostjob.hip
+int run_host_nbest(fcd_handle *h, const fcd_batch *in, const fcd_result *out, const fcd_nbest *nb, const HostCall &c) {
+    if (!h) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> whole_call(h->mu);
+    if (c.beam_size < 1) return fail(h, FCD_E_INVALID, "beam_size cannot be 0");
+    int rc = host_check(h, in, out, c);
+    if (rc) return rc;
+    rc = check_result_nbest(h, in, out, nb, c.beam_size);
+    if (rc) return rc;
+    if (in->n_reads == 0) return FCD_OK;
+    FCD_DEVICE(h);
+    HostCall cn = c;
+    cn.n_best = nb->n_best;
+    HostStage st;
+    fcd_batch din{};
+    fcd_result dout{};
+    rc = host_upload(h, in, out, cn, true, &st, &din, &dout);
+    if (rc == FCD_OK) rc = host_search(h, st, &din, cn, &dout);
+    if (rc) return rc;
+    return host_download(h, st, dout, out, nb);
 }
 
 }  // namespace
@@ -1719,6 +1809,29 @@ int fcd_crf_beam_search_host_k(fcd_handle *h, const fcd_batch *in, const float *
     c.n_init = n_init;
     c.init_stride = init_stride;
     return run_host(h, in, out, c);
+}
+
+int fcd_beam_search_nbest_host(fcd_handle *h, const fcd_batch *in, int64_t beam_size, float beam_cut_threshold,
+                               int collapse_repeats, int kernel, const fcd_nbest *nb, const fcd_result *out) {
+    HostCall c{HostOp::Beam};
+    c.collapse = collapse_repeats;
+    c.beam_size = beam_size;
+    c.thr = beam_cut_threshold;
+    c.kernel = kernel;
+    return run_host_nbest(h, in, out, nb, c);
+}
+
+int fcd_crf_beam_search_nbest_host(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init,
+                                   int64_t init_stride, int64_t beam_size, float beam_cut_threshold, int kernel,
+                                   const fcd_nbest *nb, const fcd_result *out) {
+    HostCall c{HostOp::CrfBeam};
+    c.beam_size = beam_size;
+    c.thr = beam_cut_threshold;
+    c.kernel = kernel;
+    c.init = init;
+    c.n_init = n_init;
+    c.init_stride = init_stride;
+    return run_host_nbest(h, in, out, nb, c);
 }
 
 int fcd_crf_greedy_search_host(fcd_handle *h, const fcd_batch *in, const float *init,

@@ -38,6 +38,16 @@ struct ResultDesc {
     uint32_t *ambiguous;  // nullable: per-read count of unpinned tie steps (beam searches only)
 };
 
+// n-best layout of the beam searches (fcd_*_nbest_*), read by the kernels only after the time loop.  n_best = 0: one
+// row per read (every other entry point).  n_best > 0: labels / path / out_len of the ResultDesc and score have
+// n_reads * n_best rows, hypothesis i of read r in row r * n_best + i; n_hyp, status and ambiguous stay per read.
+// (The LAST member of the beam kernels' parameter blocks: the fields before it keep their kernel-argument offsets.)
+struct NBestDesc {
+    float *score;
+    uint32_t *n_hyp;
+    int64_t n_best;
+};
+
 // Parameters of the 1D beam searches (search::beam_search / search::crf_beam_search).
 struct BeamArgs {
     int beam_size;
@@ -87,24 +97,25 @@ struct WaveArena {
 size_t beam_generic_lds_bytes(int beam_size, int N, int tie_order);  // (the quicksort's list and scratch only under FCD_TIE_PDQ178 above 20 candidates)
 hipError_t launch_beam_generic(const BatchDesc &in, int64_t read_begin, int64_t n_reads,
                                const BeamArgs &a, const GenericArena &arena, const ResultDesc &out,
-                               hipStream_t stream);
+                               hipStream_t stream, const NBestDesc &nb = NBestDesc{});
 
 int beam_lane_reads_per_wave(int beam_size);  // of a first pass (a retry pass: one)
 // wavefronts of the instantiation the current device holds at once: the size of a slab pool nobody ever waits for
-int beam_lane_resident_waves(int beam_size, int N, int crf, bool first_pass, bool ambiguous, int tie_order);
+int beam_lane_resident_waves(int beam_size, int N, int crf, bool first_pass, bool ambiguous, int tie_order,
+                             bool nbest = false);
 hipError_t slab_pool_init(unsigned long long *pool, int slabs, hipStream_t stream);  // `pool`: slab_pool::bytes(slabs) of device memory
 bool beam_wave_supported(int beam_size, int N, int crf, int S);
 // node ids of the wave kernel are (time step << shift) | index among the step's new nodes: slots per step = 1 << shift
 int beam_wave_id_shift(int beam_size, int N, int force_one_read_per_wave);
 hipError_t launch_beam_wave(const BatchDesc &in, int64_t read_begin, int64_t n_reads,
                             const BeamArgs &a, const WaveArena &arena, const ResultDesc &out,
-                            hipStream_t stream);
+                            hipStream_t stream, const NBestDesc &nb = NBestDesc{});
 
 // one beam entry per lane: beam_size <= 64, N <= 8 (CRF: N = 5, S a power of two >= 4); uses the wave arena layout
 bool beam_lane_supported(int beam_size, int N, int crf, int S);
 hipError_t launch_beam_lane(const BatchDesc &in, int64_t read_begin, int64_t n_reads,
                             const BeamArgs &a, const WaveArena &arena, const ResultDesc &out,
-                            hipStream_t stream);
+                            hipStream_t stream, const NBestDesc &nb = NBestDesc{});
 
 hipError_t launch_viterbi(const BatchDesc &in, int collapse, const ResultDesc &out,
                           hipStream_t stream);
@@ -221,12 +232,13 @@ struct HostCall {
     int kernel = FCD_KERNEL_AUTO;
     const float *init = nullptr;  // host pointer
     int64_t n_init = 0, init_stride = 0;
+    int64_t n_best = 0;  // Beam / CrfBeam: > 0 = the n-best layout (fcd_*_nbest_host; never through the chunk pipeline)
 };
 
 // where one staged host call lives inside fcd_handle::stage (byte offsets)
 struct HostStage {
-    size_t o_in, o_len, o_init, o_lab, o_path, o_qual, o_olen, o_stat, o_amb, used;
-    size_t n_in, n_out, n_init;
+    size_t o_in, o_len, o_init, o_lab, o_path, o_qual, o_olen, o_stat, o_amb, o_score, o_nhyp, used;
+    size_t n_in, n_out, n_init, n_rows;  // n_rows: result rows (n_reads, or n_reads * n_best)
     int64_t B;
     bool want_amb, mirror;
 };
@@ -235,7 +247,9 @@ int host_check(fcd_handle *h, const fcd_batch *in, const fcd_result *out, const 
 int host_upload(fcd_handle *h, const fcd_batch *in, const fcd_result *shape, const HostCall &c, bool allow_mirror,
                 HostStage *st, fcd_batch *din, fcd_result *dout);
 int host_search(fcd_handle *h, const HostStage &st, const fcd_batch *din, const HostCall &c, const fcd_result *dout);
-int host_download(fcd_handle *h, const HostStage &st, const fcd_result &dout, const fcd_result *out);
+// (nb: the caller's score / n_hyp arrays of an n-best call)
+int host_download(fcd_handle *h, const HostStage &st, const fcd_result &dout, const fcd_result *out,
+                  const fcd_nbest *nb = nullptr);
 // large host batches: chunks on internal lanes, upload || search || packed download (hostjob.hip)
 bool host_job_wanted(fcd_handle *h, const fcd_batch *in, const HostCall &c);
 int host_job_run_fixed(fcd_handle *h, const fcd_batch *in, const fcd_result *out, const HostCall &c);

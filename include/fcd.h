@@ -267,6 +267,38 @@ int fcd_crf_beam_search_host_k(fcd_handle *h, const fcd_batch *in, const float *
                                int64_t init_stride, int64_t beam_size, float beam_cut_threshold,
                                int kernel, const fcd_result *out);
 
+/* ---- n best hypotheses of search::beam_search / search::crf_beam_search (src/search.rs:159-301, :38-157) ----
+ * NOT a reference function: the reference returns beam[0] only (src/search.rs:165,300).  These run the same search
+ * and, after the last row's truncation and division by the top probability (:278-282 / :125-131), trace back the
+ * first n_hyp = min(n_best, beam length) entries of the final beam, in its rank order (the tie order in force,
+ * FCD_TIE_*), each read off the suffix tree exactly as the reference reads beam[0] (:285-300 / :133-156).
+ *   out   : n_reads * n_best rows of labels / path (nullable) / out_len; hypothesis i of read r is row r * n_best + i,
+ *           and hypothesis 0 is, byte for byte, what fcd_beam_search_* / fcd_crf_beam_search_* return for the read.
+ *           status and ambiguous (nullable) stay per read.  Rows i >= n_hyp[r] get out_len 0 and score 0.
+ *   score : [n_reads * n_best] f32, entry i's label_prob + gap_prob (SearchPoint::probability(), src/search.rs:26-28):
+ *           RELATIVE to the best entry of the last step (<= 1 up to rounding; hypothesis 0's need not be exactly 1),
+ *           not a log-likelihood of the read.
+ *   n_hyp : [n_reads] u32; 0 for a read whose search fails (its status says why).
+ * Hypotheses are distinct labellings (the search merges by tree node).  Everything listed is written by the call:
+ * uninitialised arrays are fine.  n_best outside 1 .. beam_size is FCD_E_INVALID.  The _dev forms share the kernel
+ * choice, workspace chunking, wide-beam retry pass and fcd_set_overlap behaviour of fcd_beam_search_dev; the _host
+ * forms stage the batch, decode and copy back in one piece (not through the chunk pipeline of the host jobs). */
+typedef struct fcd_nbest {
+    int64_t n_best;     /* 1 .. beam_size */
+    float *score;       /* [n_reads * n_best] */
+    uint32_t *n_hyp;    /* [n_reads] */
+} fcd_nbest;
+int fcd_beam_search_nbest_dev(fcd_handle *h, const fcd_batch *in, int64_t beam_size, float beam_cut_threshold,
+                              int collapse_repeats, int kernel, const fcd_nbest *nb, const fcd_result *out);
+int fcd_beam_search_nbest_host(fcd_handle *h, const fcd_batch *in, int64_t beam_size, float beam_cut_threshold,
+                               int collapse_repeats, int kernel, const fcd_nbest *nb, const fcd_result *out);
+int fcd_crf_beam_search_nbest_dev(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init,
+                                  int64_t init_stride, int64_t beam_size, float beam_cut_threshold, int kernel,
+                                  const fcd_nbest *nb, const fcd_result *out);
+int fcd_crf_beam_search_nbest_host(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init,
+                                   int64_t init_stride, int64_t beam_size, float beam_cut_threshold, int kernel,
+                                   const fcd_nbest *nb, const fcd_result *out);
+
 /* ---- search::crf_greedy_search (src/search.rs:385-423) ---- */
 int fcd_crf_greedy_search_dev(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init,
                               int64_t init_stride, const fcd_result *out);
