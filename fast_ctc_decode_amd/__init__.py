@@ -9,6 +9,8 @@ importing this package never touches a CPU fallback (there is none).
 """
 from .api import (  # noqa: F401
     BatchResult,
+    BeamSearchSession,
+    CrfBeamSearchSession,
     NBestResult,
     __version__,
     beam_search,

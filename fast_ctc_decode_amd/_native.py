@@ -47,6 +47,9 @@ SYMBOLS = [
     "fcd_comm_synchronize", "fcd_unpack_gathered_dev",
     "fcd_viterbi_search_host_begin", "fcd_beam_search_host_begin", "fcd_crf_beam_search_host_begin",
     "fcd_crf_greedy_search_host_begin", "fcd_viterbi_search_host_ptrs_begin", "fcd_beam_search_host_ptrs_begin", "fcd_set_host_pipeline", "fcd_job_chunks", "fcd_job_next", "fcd_job_end",
+    "fcd_beam_session_create", "fcd_crf_beam_session_create", "fcd_beam_session_push_dev", "fcd_beam_session_push_host",
+    "fcd_beam_session_result_dev", "fcd_beam_session_result_host", "fcd_beam_session_restart", "fcd_beam_session_steps",
+    "fcd_beam_session_bytes", "fcd_beam_session_destroy",
 ]
 JOB_PATH, JOB_QUAL, JOB_AMBIGUOUS, JOB_DONE = 1, 2, 4, 1
 
@@ -211,6 +214,16 @@ def bind(lib):
     lib.fcd_job_chunks.argtypes = [P, C.POINTER(i64), C.POINTER(i32)]
     lib.fcd_job_next.argtypes = [P, C.POINTER(Chunk)]
     lib.fcd_job_end.argtypes = [P]
+    lib.fcd_beam_session_create.argtypes = [P, i64, i64, i64, i64, f32, i32, i32, i32, PP]
+    lib.fcd_crf_beam_session_create.argtypes = [P, i64, i64, i64, P, i64, i64, i64, f32, i32, i32, PP]
+    for sfx in ("dev", "host"):
+        getattr(lib, "fcd_beam_session_push_" + sfx).argtypes = [P, BP, RP]
+        getattr(lib, "fcd_beam_session_result_" + sfx).argtypes = [P, RP]
+    lib.fcd_beam_session_restart.argtypes = [P, P, i64, P]
+    lib.fcd_beam_session_steps.argtypes = [P, P]
+    lib.fcd_beam_session_bytes.argtypes = [P]
+    lib.fcd_beam_session_bytes.restype = i64
+    lib.fcd_beam_session_destroy.argtypes = [P]
     return lib
 
 

@@ -1251,3 +1251,230 @@ def crf_beam_search_nbest(network_output, init_state, alphabet, n_best, beam_siz
                                         beam_cut_threshold)
     _raise_status(int(r.status[0]))
     return r.hypotheses(alpha)[0]
+
+
+# ---------------------------------------------------------------------------------------------
+# beam-search sessions (include/fcd.h, fcd_beam_session_*): the 1-D beam searches advanced over rows as they arrive
+# ---------------------------------------------------------------------------------------------
+class _CrfBatchResult(BatchResult):
+    """A BatchResult whose strings follow crf_beam_search_batch's character handling (multi-character labels reversed)."""
+
+    def cpu(self):
+        r = BatchResult.cpu(self)
+        return _CrfBatchResult(r.labels, r.path, r.out_len, r.status, r.qual, r.ambiguous)
+
+    def sequences(self, alphabet, raise_on_error=True, paths="list"):
+        r = self.cpu()
+        alpha = _seq_to_vec(alphabet)
+        out = BatchResult.sequences(r, alpha, raise_on_error, paths)
+        for i, item in enumerate(out):
+            if item is not None:
+                labels = r.labels[i, :int(r.out_len[i])]
+                out[i] = ("".join(alpha[l] for l in labels[::-1])[::-1], item[1])
+        return out
+
+
+class BeamSearchSession:
+    """A fixed set of n_reads read slots whose search::beam_search advances over the rows pushed to it (include/fcd.h,
+    fcd_beam_session_*).  The result of a slot is, at any time, exactly what beam_search_batch_raw returns for all the rows
+    pushed to it since creation or its restart; a failed slot stays failed.
+
+        s = BeamSearchSession(n_reads, n_labels, max_steps, beam_size=5, beam_cut_threshold=0.1)
+        s.push(chunk)                      # (n_reads, T_c, N): torch ROCm tensor, DLPack device array or numpy
+        r = s.push(chunk, lengths, result=True)   # the result after the push, from the same launch
+        r = s.result()                     # BatchResult, out_stride = max_steps; .cpu(), .sequences(alphabet)
+        s.restart([3, 7])                  # slots 3 and 7 start a new read
+
+    Device chunks run on torch's current stream and return torch tensors; numpy chunks are uploaded by the library and
+    return numpy arrays (result(host=...) chooses; by default it follows the last push).  `lengths` is a host sequence
+    (a device tensor is copied to the host first, which synchronises).  The session keeps the device chunks it was given
+    until their push has run.  max_steps: the most rows a slot takes between restarts; a push past it raises ValueError and
+    changes nothing.  Memory: one device allocation made at creation (nbytes)."""
+    _crf = False
+
+    def __init__(self, n_reads, n_labels, max_steps, beam_size=5, beam_cut_threshold=0.0, collapse_repeats=True,
+                 count_ambiguous=False, kernel=nat.KERNEL_AUTO, device=0, handle=None):
+        self._open(n_reads, n_labels, 1, max_steps, count_ambiguous, device, handle)
+        self._h.check(self._lib.fcd_beam_session_create(
+            self._h.ptr, self.n_reads, self.n_labels, self.max_steps, int(beam_size), float(beam_cut_threshold),
+            int(bool(collapse_repeats)), int(kernel), int(bool(count_ambiguous)), C.byref(self._ptr)))
+
+    def _open(self, n_reads, n_labels, n_states, max_steps, count_ambiguous, device, handle):
+        self._h = handle if handle is not None else nat.default_handle(device)
+        self._lib = self._h.lib
+        self._ptr = C.c_void_p()
+        self.n_reads, self.n_labels, self.n_states = int(n_reads), int(n_labels), int(n_states)
+        self.max_steps = int(max_steps)
+        self.count_ambiguous = bool(count_ambiguous)
+        self._host_mode = None  # the kind of the last push's chunk
+        self._held = []         # (event, tensors) of device pushes that may not have run yet
+
+    def _check_rc(self, rc):
+        if rc == nat.E_INVALID:
+            msg = self._lib.fcd_last_error(self._h.ptr)
+            raise ValueError(msg.decode() if msg else "invalid argument")
+        self._h.check(rc)
+
+    def _lengths(self, lengths):
+        if lengths is None:
+            return None
+        if hasattr(lengths, "cpu"):
+            lengths = lengths.cpu()  # (a device tensor: synchronises)
+        l = np.ascontiguousarray(np.asarray(lengths), np.int64)
+        if l.shape != (self.n_reads,):
+            raise ValueError("lengths must have shape (n_reads,)")
+        return l
+
+    def _init_rows(self, init_states, n):
+        if hasattr(init_states, "cpu"):
+            init_states = init_states.cpu()
+        init = np.ascontiguousarray(np.asarray(init_states, np.float32))
+        if init.ndim != 2 or init.shape[0] != n or init.shape[1] < 1:
+            raise ValueError("init_states must have shape (%d, n_init)" % n)
+        return init
+
+    def _result_arrays(self, host, like=None):
+        B, W = self.n_reads, self.max_steps
+        if host:
+            out = _HostOut(B, W, want_amb=self.count_ambiguous)
+            return out.res, (out.labels, out.path, out.out_len, out.status, None, out.ambiguous)
+        import torch
+        dev = like.device if like is not None else torch.device("cuda", self._h.device)
+        labels = torch.empty((B, W), dtype=torch.uint8, device=dev)
+        path = torch.empty((B, W), dtype=torch.int32, device=dev)
+        meta = torch.empty((2, B), dtype=torch.int32, device=dev)
+        amb = torch.empty((B, 2), dtype=torch.int32, device=dev) if self.count_ambiguous else None
+        res = nat.Result(labels.data_ptr(), path.data_ptr(), None, meta[0].data_ptr(), meta[1].data_ptr(), W,
+                         amb.data_ptr() if amb is not None else None)
+        self._h.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+        return res, (labels, path, meta[0], meta[1], None, amb)
+
+    def _wrap(self, arrays):
+        r = (_CrfBatchResult if self._crf else BatchResult)(*arrays)
+        return r
+
+    def _hold(self, tensors):
+        import torch
+        self._held = [(e, t) for e, t in self._held if not e.query()]
+        e = torch.cuda.Event()
+        e.record(torch.cuda.current_stream(tensors[0].device))
+        self._held.append((e, tensors))
+
+    def push(self, chunk, lengths=None, result=False, input_dtype=None):
+        """Slot r takes the first lengths[r] rows of `chunk` (all of them if lengths is None; 0 leaves it untouched).
+        result=True: returns the BatchResult after the push (one launch), else None."""
+        if not self._ptr:
+            raise ValueError("the session is closed")
+        l = self._lengths(lengths)
+        ndim = 4 if self._crf else 3
+        dev_x = _device_tensor(chunk)
+        if dev_x is None:
+            x = _dense(np.asarray(chunk))
+            if x.ndim != ndim or x.dtype not in (np.float32, np.float16, np.uint16):
+                raise TypeError("expected a float32 (or float16 / bfloat16-bits uint16) array of rank %d" % ndim)
+            if x.shape[0] != self.n_reads:
+                raise ValueError("the chunk must have n_reads = %d rows of reads" % self.n_reads)
+            b = _host_batch(x, self._crf, l, input_dtype)
+            res, arrays = self._result_arrays(True) if result else (None, None)
+            self._check_rc(self._lib.fcd_beam_session_push_host(self._ptr, C.byref(b), C.byref(res) if result else None))
+            self._host_mode = True
+            return self._wrap(arrays) if result else None
+        import torch
+        x = dev_x
+        if x.dim() != ndim or x.shape[0] != self.n_reads:
+            raise ValueError("expected a (n_reads, T_c, %s) device tensor" % ("S, N" if self._crf else "N"))
+        st = x.stride()
+        if self._crf:
+            b = nat.Batch(x.data_ptr(), x.shape[0], x.shape[1], x.shape[2], x.shape[3], st[0], st[1], st[2], st[3], None,
+                          _torch_dtype_code(x))
+        else:
+            b = nat.Batch(x.data_ptr(), x.shape[0], x.shape[1], 1, x.shape[2], st[0], st[1], 0, st[2], None,
+                          _torch_dtype_code(x))
+        if l is not None:
+            b.lengths = l.ctypes.data
+        if result:
+            res, arrays = self._result_arrays(False, x)
+        else:
+            res, arrays = None, None
+            self._h.set_stream(torch.cuda.current_stream(x.device).cuda_stream)
+        self._check_rc(self._lib.fcd_beam_session_push_dev(self._ptr, C.byref(b), C.byref(res) if result else None))
+        self._hold((x,))
+        self._host_mode = False
+        return self._wrap(arrays) if result else None
+
+    def result(self, host=None):
+        """BatchResult of every slot's prefix (the session does not change).  host=None: numpy arrays if the last push
+        was a numpy chunk (or, before any push, if no ROCm device is visible to torch), torch tensors otherwise."""
+        if not self._ptr:
+            raise ValueError("the session is closed")
+        if host is None:
+            host = self._host_mode
+            if host is None:
+                try:
+                    import torch
+                    host = not torch.cuda.is_available()
+                except ImportError:
+                    host = True
+        res, arrays = self._result_arrays(bool(host))
+        fn = self._lib.fcd_beam_session_result_host if host else self._lib.fcd_beam_session_result_dev
+        self._check_rc(fn(self._ptr, C.byref(res)))
+        return self._wrap(arrays)
+
+    def restart(self, slots, init_states=None):
+        """The listed slots go back to the root with 0 steps (CRF: each with a new init row, init_states[j] for slots[j])."""
+        s = np.ascontiguousarray(np.asarray(slots, np.int64).reshape(-1))
+        init = None
+        if self._crf:
+            if init_states is None:
+                raise ValueError("a CRF session restarts a slot with a new init row")
+            init = self._init_rows(init_states, len(s))
+            if init.shape[1] != self._n_init:
+                raise ValueError("init rows must have %d entries" % self._n_init)
+        self._check_rc(self._lib.fcd_beam_session_restart(self._ptr, s.ctypes.data, len(s),
+                                                          init.ctypes.data if init is not None else None))
+
+    @property
+    def steps(self):
+        """rows each slot has taken since creation or its restart (numpy int64, n_reads)"""
+        out = np.zeros(self.n_reads, np.int64)
+        self._h.check(self._lib.fcd_beam_session_steps(self._ptr, out.ctypes.data))
+        return out
+
+    @property
+    def nbytes(self):
+        return int(self._lib.fcd_beam_session_bytes(self._ptr))
+
+    def close(self):
+        if self._ptr:
+            self._lib.fcd_beam_session_destroy(self._ptr)
+            self._ptr = C.c_void_p()
+            self._held = []
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class CrfBeamSearchSession(BeamSearchSession):
+    """BeamSearchSession of search::crf_beam_search: chunks are (n_reads, T_c, S, N); init_states (n_reads, n_init) are
+    the slots' first init rows (a NaN row, or a state the table does not hold, fails the slot at its first non-empty
+    push).  Strings follow crf_beam_search_batch's character handling."""
+    _crf = True
+
+    def __init__(self, n_reads, n_states, n_labels, init_states, max_steps, beam_size=5, beam_cut_threshold=0.0,
+                 count_ambiguous=False, kernel=nat.KERNEL_AUTO, device=0, handle=None):
+        self._open(n_reads, n_labels, n_states, max_steps, count_ambiguous, device, handle)
+        init = self._init_rows(init_states, self.n_reads)
+        self._n_init = init.shape[1]
+        self._check_rc(self._lib.fcd_crf_beam_session_create(
+            self._h.ptr, self.n_reads, self.n_states, self.n_labels, init.ctypes.data, self._n_init, self.max_steps,
+            int(beam_size), float(beam_cut_threshold), int(kernel), int(bool(count_ambiguous)), C.byref(self._ptr)))

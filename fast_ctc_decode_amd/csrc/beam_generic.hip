@@ -32,7 +32,8 @@ struct GenericParams {
     GenericArena arena;
     ResultDesc out;
     int64_t read_begin;
-    NBestDesc nb;  // (last: fcd_internal.h)
+    NBestDesc nb;
+    SessionDesc ses;  // (last: fcd_internal.h)
 };
 
 // LDS carve-up (all 4-byte words unless noted).  BC = beam_size, NL = N-1, C = BC*N.
@@ -167,10 +168,33 @@ __device__ __forceinline__ void fail(const GenericParams &p, int64_t r, int code
     }
 }
 
+// SES, a beam-search session: a failed slot keeps its status and tie counters in its state block (header words 1 to 4);
+// `out` gets them only when a result is asked for (out.status given).
+__device__ __forceinline__ void fail_ses(const GenericParams &p, int32_t *blk, int64_t r, int code, int n_amb, int n_crit) {
+    if (threadIdx.x == 0) {
+        blk[1] = 0;
+        blk[2] = code;
+        blk[3] = n_amb;
+        blk[4] = n_crit;
+        if (p.out.status) {
+            p.out.status[r] = code;
+            p.out.out_len[r] = 0;
+            if (p.out.ambiguous) {
+                p.out.ambiguous[2 * r] = (uint32_t)n_amb;
+                p.out.ambiguous[2 * r + 1] = (uint32_t)n_crit;
+            }
+        }
+    }
+}
+
 // NB: the n-best layout (NBestDesc::n_best > 0): lanes 0 .. n_best-1 each trace back one entry of the final beam (rank
 // order) into rows r * n_best + i, with its score, and lane 0 writes the read's n_hyp.  A separate instantiation keeps
 // the single-result kernel as it is.
-template <bool NB>
+// SES: a beam-search session (fcd_beam_session_*).  Beam buffer 0 is loaded from the slot's state block (the Lds beam
+// layout, beam_stride words, behind kSesHeader words: B, alive, status, tie counters, step offset t0, node count) instead
+// of being set to the root; the time loop runs on the chunk's rows at absolute time t0 + t (the `time` field of the
+// records); the final beam and the header go back, and the traceback runs only when out.labels is given.
+template <bool NB, bool SES = false>
 __global__ __launch_bounds__(64) void beam_generic_kernel(GenericParams p) {
     extern __shared__ __attribute__((aligned(16))) int smem[];
     const int lane = threadIdx.x;
@@ -196,7 +220,23 @@ __global__ __launch_bounds__(64) void beam_generic_kernel(GenericParams p) {
     // ---- initial beam: search.rs:170-175 / :54-59 ----
     int cur = 0;
     int B = 1;
-    if (lane == 0) {
+    int32_t *const ses_blk = SES ? p.ses.state + r * p.ses.block_words : nullptr;
+    const int64_t t0 = SES ? (int64_t)ses_blk[5] : 0;
+    if (SES) {
+        if (!ses_blk[1]) {  // failed in an earlier launch: stays as it failed
+            if (p.out.labels && lane == 0) {
+                p.out.status[r] = ses_blk[2];
+                p.out.out_len[r] = 0;
+                if (p.out.ambiguous) {
+                    p.out.ambiguous[2 * r] = (uint32_t)ses_blk[3];
+                    p.out.ambiguous[2 * r + 1] = (uint32_t)ses_blk[4];
+                }
+            }
+            return;
+        }
+        B = ses_blk[0];
+        for (int j = lane; j < L.beam_stride; j += kWave) L.beam0[j] = ses_blk[kSesHeader + j];
+    } else if (lane == 0) {
         int st0 = 0;
         float lp0 = 0.0f, gp0 = 1.0f;
         bool bad = false;
@@ -224,7 +264,8 @@ __global__ __launch_bounds__(64) void beam_generic_kernel(GenericParams p) {
         L.b_state(0)[0] = bad ? -1 : st0;
         L.b_depth(0)[0] = 0;
     }
-    for (int j = lane; j < NL; j += kWave) L.b_child(0)[j] = -1;
+    if (!SES)
+        for (int j = lane; j < NL; j += kWave) L.b_child(0)[j] = -1;
     if (!crf && T > 0)
         for (int j = lane; j < N; j += kWave) L.row[j] = load_post(post, j * st_n, dt);
     // row t+1 travels in a register while step t runs, so its HBM latency is never waited for
@@ -233,10 +274,14 @@ __global__ __launch_bounds__(64) void beam_generic_kernel(GenericParams p) {
     float next_row = (row_in_reg && lane < N && T > 1) ? load_post(post, st_t + lane * st_n, dt) : 0.0f;
     wave_sync();
 
-    int nn = 0;  // nodes in this read's tree (wave-uniform)
+    int nn = SES ? ses_blk[6] : 0;  // nodes in this read's tree (wave-uniform)
     // tie instrument (fcd_result.ambiguous; two counters, semantics in include/fcd.h)
-    const bool count_amb = p.out.ambiguous != nullptr;
-    int n_amb = 0, n_crit = 0;
+    const bool count_amb = SES ? p.ses.count_amb != 0 : p.out.ambiguous != nullptr;
+    int n_amb = SES ? ses_blk[3] : 0, n_crit = SES ? ses_blk[4] : 0;
+    auto stop = [&](int code) {
+        if (SES) fail_ses(p, ses_blk, r, code, n_amb, n_crit);
+        else fail<NB>(p, r, code, n_amb, n_crit);
+    };
     const bool pdq = p.a.tie_order == FCD_TIE_PDQ178;  // equal probabilities above 20 candidates: Rust 1.78's order
 
     for (int64_t t = 0; t < T; ++t) {
@@ -339,7 +384,7 @@ __global__ __launch_bounds__(64) void beam_generic_kernel(GenericParams p) {
                 cid = nn + popc64(m_new & lanemask_lt());
                 if (cid < p.arena.cap_nodes) {
                     const int l = k - 1;
-                    rec[cid] = make_int4(node, (int)t, l, b_depth[i] + 1);
+                    rec[cid] = make_int4(node, (int)(t0 + t), l, b_depth[i] + 1);
                     for (int j = 0; j < NL; ++j) rows[(int64_t)cid * NL + j] = -1;
                     if (node >= 0) rows[(int64_t)node * NL + l] = cid;
                     b_child[i * NL + l] = cid;
@@ -359,11 +404,11 @@ __global__ __launch_bounds__(64) void beam_generic_kernel(GenericParams p) {
             any_nan = any_nan || (__ballot(valid && prob != prob) != 0ull);
         }
         bad_state = __ballot(bad_state) != 0ull;
-        if (bad_state) return fail<NB>(p, r, FCD_ST_BAD_STATE, n_amb, n_crit);
-        if (nn > p.arena.cap_nodes) return fail<NB>(p, r, FCD_ST_INTERNAL, n_amb, n_crit);
+        if (bad_state) return stop(FCD_ST_BAD_STATE);
+        if (nn > p.arena.cap_nodes) return stop(FCD_ST_INTERNAL);
         // search.rs:261-277: any NaN among >= 2 candidates -> IncomparableValues, then empty -> RanOutOfBeam
-        if (n_valid >= 2 && any_nan) return fail<NB>(p, r, FCD_ST_INCOMPARABLE, n_amb, n_crit);
-        if (n_valid == 0) return fail<NB>(p, r, FCD_ST_RAN_OUT_OF_BEAM, n_amb, n_crit);
+        if (n_valid >= 2 && any_nan) return stop(FCD_ST_INCOMPARABLE);
+        if (n_valid == 0) return stop(FCD_ST_RAN_OUT_OF_BEAM);
         wave_sync();
 
         // ---- phase B: the top beam_size candidates, in exact key order, build the next beam ----
@@ -572,6 +617,20 @@ __global__ __launch_bounds__(64) void beam_generic_kernel(GenericParams p) {
         wave_sync();
     }
 
+    if (SES) {  // the final beam and the header go back (a slot that took no row is left as it is)
+        if (T > 0) {
+            const int *src = L.b_node(cur);
+            for (int j = lane; j < L.beam_stride; j += kWave) ses_blk[kSesHeader + j] = src[j];
+            if (lane == 0) {
+                ses_blk[0] = B;
+                ses_blk[3] = n_amb;
+                ses_blk[4] = n_crit;
+                ses_blk[5] = (int)(t0 + T);
+                ses_blk[6] = nn;
+            }
+        }
+        if (!p.out.labels) return;  // no result asked for
+    }
     // ---- walk the best labelling leaf -> root (:285-300), writing it in sequence order ----
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // drop L1 lines older than our own stores
     if (NB) {
@@ -618,7 +677,7 @@ __global__ __launch_bounds__(64) void beam_generic_kernel(GenericParams p) {
         }
         p.out.out_len[r] = (uint32_t)n;
         p.out.status[r] = FCD_ST_OK;
-        if (count_amb) {
+        if (SES ? p.out.ambiguous != nullptr : count_amb) {
             p.out.ambiguous[2 * r] = (uint32_t)n_amb;
             p.out.ambiguous[2 * r + 1] = (uint32_t)n_crit;
         }
@@ -637,11 +696,13 @@ size_t beam_generic_lds_bytes(int beam_size, int N, int tie_order) {
 
 hipError_t launch_beam_generic(const BatchDesc &in, int64_t read_begin, int64_t n_reads,
                                const BeamArgs &a, const GenericArena &arena, const ResultDesc &out,
-                               hipStream_t stream, const NBestDesc &nb) {
+                               hipStream_t stream, const NBestDesc &nb, const SessionDesc &ses) {
     if (n_reads <= 0) return hipSuccess;
-    GenericParams p{in, a, arena, out, read_begin, nb};
+    GenericParams p{in, a, arena, out, read_begin, nb, ses};
     const size_t lds = beam_generic_lds_bytes(a.beam_size, in.N, a.tie_order);
-    if (nb.n_best > 0)
+    if (ses.state)
+        hipLaunchKernelGGL((beam_generic_kernel<false, true>), dim3((unsigned)n_reads), dim3(64), lds, stream, p);
+    else if (nb.n_best > 0)
         hipLaunchKernelGGL(beam_generic_kernel<true>, dim3((unsigned)n_reads), dim3(64), lds, stream, p);
     else
         hipLaunchKernelGGL(beam_generic_kernel<false>, dim3((unsigned)n_reads), dim3(64), lds, stream, p);

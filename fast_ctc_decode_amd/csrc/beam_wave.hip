@@ -73,7 +73,8 @@ struct WaveParams {
     WaveArena arena;
     ResultDesc out;
     int64_t read_begin;
-    NBestDesc nb;  // (last: fcd_internal.h)
+    NBestDesc nb;
+    SessionDesc ses;  // (last: fcd_internal.h)
 };
 
 __device__ __forceinline__ int bperm(int src_lane, int v) {
@@ -127,8 +128,13 @@ constexpr int kSeg = 64;  // nodes per traceback segment (jump-pointer spacing)
 // NB: the n-best layout (NBestDesc::n_best > 0): after the time loop the first n_best beam slots are traced back, each
 // from its own group's (node, depth, jump), into rows r * n_best + i, with their scores and the read's n_hyp.  The time
 // loop is the same; a separate instantiation keeps the single-result kernels as they are.
+// SES: a beam-search session (fcd_beam_session_*; instantiated in beam_wave_session.hip).  The prologue loads the slot's
+// saved state (SessionDesc: B, alive, status, tie counters, step offset t0, and every lane's node, lp, gp, tipf, depth,
+// jump, child and state, verbatim) instead of the root; the time loop runs unchanged on the chunk's rows at absolute time
+// t0 + t (node ids, hence `path`); the epilogue stores the state back and traces back only when out.labels is given.
+// A failure is kept in the state, not written to `out`: later launches leave the slot alone.
 template <int N, int GW, int RPW, int S, bool AMB, bool PROF = false, bool UNI = false, bool H16 = false, bool PDQ = false,
-          bool NB = false>
+          bool NB = false, bool SES = false>
 __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_per_eu((RPW == 2 && !AMB) ? 4 : 1))) void beam_wave_kernel(WaveParams p) {
     constexpr bool CRF = S != 0;
     constexpr bool GATHER = S == kCrfGather;
@@ -257,7 +263,34 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_pe
     int B = (UNI && !has_read) ? 0 : 1;
     bool alive = has_read;
     int state = 0;
-    if (CRF && has_read) {
+    int t0 = 0;                // SES: steps the slot took in earlier launches
+    int ses_st = FCD_ST_OK;    // SES: why the slot failed
+    int32_t *const ses_blk = SES ? p.ses.state + r * p.ses.block_words : nullptr;
+    if (SES) {
+        if (has_read) {
+            const int32_t *lw = ses_blk + kSesHeader + lane;
+            node = lw[0];
+            lp = __int_as_float(lw[64]);
+            gp = __int_as_float(lw[128]);
+            tipf = lw[192];
+            depth = lw[256];
+            jump = lw[320];
+            child = lw[384];
+            state = lw[448];
+            B = ses_blk[0];
+            alive = ses_blk[1] != 0;
+            ses_st = ses_blk[2];
+            n_amb = ses_blk[3];
+            n_crit = ses_blk[4];
+            t0 = ses_blk[5];
+            if (!alive) T = 0;  // a failed slot stays as it failed
+            if (CRF && ses_blk[6] && T > 0) {  // a bad init row fails the first non-empty push (as the root block below)
+                ses_st = FCD_ST_BAD_STATE;
+                alive = false;
+                state = 0;
+            }
+        }
+    } else if (CRF && has_read) {
         // search.rs:54-59: state = argmax(init), label_prob = max(init), gap_prob = init[0];
         // ndarray-stats: first maximum wins, NaN -> Err -> unwrap() panics
         const float *init = p.a.init + r * p.a.init_stride;
@@ -356,6 +389,38 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_pe
         o[7] = (uint32_t)Tmax;
     }
 
+    if (SES) {
+        // ---- the state goes back verbatim (a slot that took no row is left as it is) ----
+        if (has_read && T > 0) {
+            int32_t *lw = ses_blk + kSesHeader + lane;
+            lw[0] = node;
+            lw[64] = __float_as_int(lp);
+            lw[128] = __float_as_int(gp);
+            lw[192] = tipf;
+            lw[256] = depth;
+            lw[320] = jump;
+            lw[384] = child;
+            lw[448] = state;
+            if (q == 0) {
+                ses_blk[0] = B;
+                ses_blk[1] = alive ? 1 : 0;
+                ses_blk[2] = ses_st;
+                ses_blk[3] = n_amb;
+                ses_blk[4] = n_crit;
+                ses_blk[5] = t0 + T;
+                ses_blk[6] = 0;
+            }
+        }
+        if (!p.out.labels) return;  // no result asked for
+        if (q == 0 && has_read) {
+            p.out.out_len[r] = alive ? (uint32_t)depth : 0u;
+            p.out.status[r] = alive ? FCD_ST_OK : ses_st;
+            if (AMB && p.out.ambiguous) {
+                p.out.ambiguous[2 * r] = (uint32_t)n_amb;
+                p.out.ambiguous[2 * r + 1] = (uint32_t)n_crit;
+            }
+        }
+    }
     // ---- walk the best labelling leaf -> root (:285-300), segment-parallel ----
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     const int32_t *rec = rec_w + hoff;
@@ -363,11 +428,11 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_pe
     // NB: hypothesis i is beam slot i (group i); nb <= beam_size <= BCAP (capi.hip), so every source lane is in the half
     const int nb = NB ? (int)p.nb.n_best : 1;
     const int n_hyp = NB ? (alive ? (B < nb ? B : nb) : 0) : 1;
-    if (q == 0 && alive) {
+    if (!SES && q == 0 && alive) {
         if (!NB) p.out.out_len[r] = (uint32_t)depth;
         p.out.status[r] = FCD_ST_OK;
     }
-    if (AMB && q == 0 && has_read) {
+    if (!SES && AMB && q == 0 && has_read) {
         p.out.ambiguous[2 * r] = (uint32_t)n_amb;
         p.out.ambiguous[2 * r + 1] = (uint32_t)n_crit;
     }
@@ -450,6 +515,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_pe
     }
 }
 
+#ifndef FCD_BEAM_WAVE_KERNEL_ONLY  // (beam_wave_session.hip takes the kernel template alone)
 template <int N, int GW, int RPW, int S, bool PDQ>
 hipError_t launch_tp(const WaveParams &p, int64_t n_reads, hipStream_t stream) {
     const int64_t waves = (n_reads + RPW - 1) / RPW;
@@ -495,9 +561,11 @@ hipError_t launch_t(const WaveParams &p, int64_t n_reads, hipStream_t stream) {
     if (CAN_TIE && p.a.tie_order == FCD_TIE_PDQ178) return launch_tp<N, GW, RPW, S, CAN_TIE>(p, n_reads, stream);
     return launch_tp<N, GW, RPW, S, false>(p, n_reads, stream);
 }
+#endif
 
 }  // namespace
 
+#ifndef FCD_BEAM_WAVE_KERNEL_ONLY
 int beam_wave_id_shift(int beam_size, int N, int force_one_read_per_wave) {
     return (beam_size <= 5 && N <= 5 && !force_one_read_per_wave) ? 5 : 6;  // KS of the instantiation launch_beam_wave picks
 }
@@ -554,5 +622,6 @@ hipError_t launch_beam_wave(const BatchDesc &in, int64_t read_begin, int64_t n_r
 
 // this translation unit's copy of the replay's std-form word (pdq178.h), on the current device
 FCD_PDQ178_DEFINE_STD_FORM_SETTER(beam_wave_set_pdq178_std_form)
+#endif
 
 }  // namespace fcd

@@ -6,6 +6,7 @@
 // loop-exit unification, and the kernel is bound by the LATENCY of its dependent chain: every instruction and every
 // wait on the path shows.)
         const bool act = UNI ? alive : (alive && t < T);
+        const int tks = SES ? (t0 + t) << KS : t << KS;  // first node id of the step (SES: absolute time)
         float pk = GATHER ? rowv : pk_next;
         const float pr0 = pk;
         const float ptip = ptip_next;
@@ -49,7 +50,7 @@
         // created in this step gets (t << KS) + q here -- above every existing index and increasing with the
         // lane, exactly like the index it is about to receive -- so the key does not wait for the numbering below.
         // (A NaN key is garbage but non-zero: it only ever ranks when it is the read's lone candidate, :262.)
-        const int idk = is_self ? node : (is_new ? (t << KS) + q : cid);
+        const int idk = is_self ? node : (is_new ? tks + q : cid);
         const uint64_t key = (UNI ? valid : (valid && act)) ? make_key(prob, idk) : 0ull;
         keys[lane] = key;
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -69,7 +70,7 @@
         } else {
             pre_new = __builtin_popcount(w_new & ((1u << q) - 1u));
         }
-        const int newid = (t << KS) + pre_new;  // < cap: the host sizes every slab for (T << KS) ids (capi.hip)
+        const int newid = tks + pre_new;  // < cap: the host sizes every slab for (T << KS) ids (capi.hip)
         // (beam_lane.hip writes a node's record when it first ENTERS THE BEAM -- a sixth of the stores.  Tried here, r05:
         // the stores ride for free under the LDS reads above, while next to the survivor gather they cost the PDQ
         // instantiation 8 B of scratch and 1 % -- the write traffic is not what bounds this kernel.)
@@ -120,7 +121,9 @@
             const bool f_nan = act && n_valid >= 2 && any_nan;  // a lone NaN is never compared (:262)
             const bool f_empty = act && n_valid == 0;
             if (f_nan || f_empty) {
-                if (q == 0) {
+                if (SES) {
+                    ses_st = f_empty ? FCD_ST_RAN_OUT_OF_BEAM : FCD_ST_INCOMPARABLE;
+                } else if (q == 0) {
                     p.out.status[r] = f_empty ? FCD_ST_RAN_OUT_OF_BEAM : FCD_ST_INCOMPARABLE;
                     if (!NB) p.out.out_len[r] = 0;  // (n-best rows: the epilogue)
                 }

@@ -53,6 +53,7 @@ hipError_t apply_pdq178_std_form(int bits) {
     hipError_t e = beam_wave_set_pdq178_std_form(bits);
     if (e == hipSuccess) e = beam_lane_set_pdq178_std_form(bits);
     if (e == hipSuccess) e = beam_generic_set_pdq178_std_form(bits);
+    if (e == hipSuccess) e = beam_wave_session_set_pdq178_std_form(bits);
     if (e == hipSuccess) e = tieorder_set_pdq178_std_form(bits);
     return e;
 }
@@ -663,6 +664,10 @@ int fcd_destroy(fcd_handle *h) {
         std::lock_guard<std::recursive_mutex> g(h->mu);
         if (h->job_active) {  // its lane threads still write buffers this call would free: fcd_job_end comes first
             h->err = "a host job is running on this handle (fcd_job_end it first)";
+            return FCD_E_INVALID;
+        }
+        if (h->live_sessions > 0) {  // their pushes run on this handle's stream
+            h->err = "beam-search sessions are open on this handle (fcd_beam_session_destroy them first)";
             return FCD_E_INVALID;
         }
     }
@@ -1855,6 +1860,396 @@ uint32_t fcd_phred(float prob, float qscale, float qbias) {
     else if (rq >= 4294967296.0f) u = 4294967295u;
     else u = (uint32_t)rq;
     return u + 33u;
+}
+
+}  // extern "C"
+
+// ---- beam-search sessions (include/fcd.h, fcd_beam_session_*) ------------------------------
+struct fcd_beam_session {
+    fcd_handle *h = nullptr;
+    int64_t n = 0, N = 0, S = 1, max_steps = 0, beam = 0, n_init = 0;
+    float thr = 0.0f;
+    int collapse = 1, crf = 0, wave = 0, force1 = 0, tie_order = FCD_TIE_PDQ178;
+    void *mem = nullptr;  // the one device allocation: state blocks | staged lengths | slot list | init rows | tree slabs
+    size_t bytes = 0;
+    SessionDesc ses{};
+    int64_t *d_len = nullptr, *d_slots = nullptr;
+    float *d_init = nullptr;
+    WaveArena war{};
+    GenericArena gar{};
+    std::vector<int64_t> steps;  // rows taken by each slot since creation or its restart (host side: the max_steps check)
+    char *pin = nullptr;         // page-locked staging of lengths / slot lists / init rows, reused only once its copy is done
+    hipEvent_t pin_ev = nullptr;
+    bool pin_busy = false;
+};
+
+namespace {
+
+size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// host bytes -> device, in stream order, through the session's page-locked buffer
+int ses_stage(fcd_beam_session *s, hipStream_t stream, const void *src0, size_t n0, void *dst0, const void *src1 = nullptr,
+              size_t n1 = 0, void *dst1 = nullptr) {
+    fcd_handle *h = s->h;
+    if (s->pin_busy) {
+        FCD_HIP(h, hipEventSynchronize(s->pin_ev));
+        s->pin_busy = false;
+    }
+    memcpy(s->pin, src0, n0);
+    FCD_HIP(h, hipMemcpyAsync(dst0, s->pin, n0, hipMemcpyHostToDevice, stream));
+    if (n1) {
+        memcpy(s->pin + align256(n0), src1, n1);
+        FCD_HIP(h, hipMemcpyAsync(dst1, s->pin + align256(n0), n1, hipMemcpyHostToDevice, stream));
+    }
+    FCD_HIP(h, hipEventRecord(s->pin_ev, stream));
+    s->pin_busy = true;
+    return FCD_OK;
+}
+
+int ses_check_out(fcd_beam_session *s, const fcd_result *out) {
+    fcd_handle *h = s->h;
+    if (!out->labels || !out->out_len || !out->status) return fail(h, FCD_E_INVALID, "null labels/out_len/status");
+    if (out->out_stride < s->max_steps) return fail(h, FCD_E_INVALID, "out_stride must be >= max_steps");
+    if (out->ambiguous && !s->ses.count_amb)
+        return fail(h, FCD_E_INVALID, "the session was created without count_ambiguous: it has no tie counters to report");
+    return FCD_OK;
+}
+
+// one launch of the session's kernel on `chunk` (device posteriors; nullptr: no rows, a result only)
+int ses_launch(fcd_beam_session *s, const fcd_batch *chunk, const fcd_result *out) {
+    fcd_handle *h = s->h;
+    const int64_t Tc = chunk ? chunk->T : 0;
+    std::vector<int64_t> take((size_t)s->n, 0);
+    if (chunk) {
+        for (int64_t r = 0; r < s->n; ++r) {
+            int64_t t = chunk->lengths ? chunk->lengths[r] : Tc;
+            t = t < 0 ? 0 : (t < Tc ? t : Tc);  // (as the kernels clamp lengths)
+            if (s->steps[(size_t)r] + t > s->max_steps)
+                return fail(h, FCD_E_INVALID, "the push would take a slot past max_steps (nothing was enqueued)");
+            take[(size_t)r] = t;
+        }
+    }
+    FCD_DEVICE(h);
+    BatchDesc d{};
+    if (chunk) {
+        d = to_desc(chunk, s->crf != 0);
+    } else {
+        d.N = (int)s->N;
+        d.S = (int)s->S;
+        d.dtype = FCD_DTYPE_F32;
+    }
+    d.n_reads = s->n;
+    const ResultDesc o = out ? to_desc(out) : ResultDesc{};
+    CallScope sc(h);
+    if (out) sc.add(o, s->n);
+    if (chunk && Tc > 0) sc.add(chunk->post, (size_t)span_elems(chunk, s->crf != 0) * (chunk->dtype == FCD_DTYPE_F32 ? 4 : 2));
+    sc.add(s->mem, s->bytes);
+    int rc = sc.begin(false, false);  // the handle's stream: a session's pushes stay in order
+    if (rc) return rc;
+    sc.time();
+    if (chunk && chunk->lengths) {
+        rc = ses_stage(s, sc.stream, chunk->lengths, (size_t)s->n * 8, s->d_len);
+        if (rc) return rc;
+        d.lengths = s->d_len;
+    }
+    BeamArgs a{};
+    a.beam_size = (int)s->beam;
+    a.thr = s->thr;
+    a.collapse = s->collapse;
+    a.crf = s->crf;
+    a.n_init = s->n_init;
+    a.force_one_read_per_wave = s->force1;
+    a.tie_order = s->tie_order;
+    if (s->wave) FCD_HIP(h, launch_beam_wave_session(d, s->n, a, s->war, o, s->ses, sc.stream));
+    else FCD_HIP(h, launch_beam_generic(d, 0, s->n, a, s->gar, o, sc.stream, NBestDesc{}, s->ses));
+    rc = sc.finish();
+    if (rc) return rc;
+    for (int64_t r = 0; r < s->n; ++r) s->steps[(size_t)r] += take[(size_t)r];
+    return FCD_OK;
+}
+
+int ses_restart(fcd_beam_session *s, const int64_t *slots, int64_t n, const float *init) {
+    fcd_handle *h = s->h;
+    if (n < 0 || n > s->n || (n > 0 && !slots)) return fail(h, FCD_E_INVALID, "bad slot list");
+    if (s->crf && n > 0 && !init) return fail(h, FCD_E_INVALID, "a CRF restart needs an init row per slot");
+    std::vector<char> seen((size_t)s->n, 0);  // (one restart block per entry: a slot listed twice would be written twice at once)
+    for (int64_t j = 0; j < n; ++j) {
+        if (slots[j] < 0 || slots[j] >= s->n) return fail(h, FCD_E_INVALID, "slot out of range");
+        if (seen[(size_t)slots[j]]++) return fail(h, FCD_E_INVALID, "a slot is listed twice");
+    }
+    if (n == 0) return FCD_OK;
+    FCD_DEVICE(h);
+    CallScope sc(h);
+    sc.add(s->mem, s->bytes);
+    int rc = sc.begin(false, false);
+    if (rc) return rc;
+    const size_t n_init_bytes = s->crf ? (size_t)n * (size_t)s->n_init * 4 : 0;
+    rc = ses_stage(s, sc.stream, slots, (size_t)n * 8, s->d_slots, init, n_init_bytes, s->d_init);
+    if (rc) return rc;
+    FCD_HIP(h, launch_session_restart(s->ses, s->d_slots, n, s->wave != 0, (int)s->beam, (int)s->N, s->crf, (int)s->S,
+                                      s->d_init, s->n_init, sc.stream));
+    rc = sc.finish();
+    if (rc) return rc;
+    for (int64_t j = 0; j < n; ++j) s->steps[(size_t)slots[j]] = 0;
+    return FCD_OK;
+}
+
+void ses_free(fcd_beam_session *s) {
+    if (s->mem) (void)hipFree(s->mem);
+    if (s->pin) (void)hipHostFree(s->pin);
+    if (s->pin_ev) (void)hipEventDestroy(s->pin_ev);
+    delete s;
+}
+
+int ses_create(fcd_handle *h, int64_t n_reads, int64_t S, int64_t N, int crf, const float *init, int64_t n_init,
+               int64_t max_steps, int64_t beam_size, float thr, int collapse, int kernel, int count_ambiguous,
+               fcd_beam_session **out) {
+    if (!h || !out) return FCD_E_INVALID;
+    *out = nullptr;
+    std::lock_guard<std::recursive_mutex> g(h->mu);
+    if (n_reads < 1 || max_steps < 1) return fail(h, FCD_E_INVALID, "n_reads and max_steps must be >= 1");
+    if (beam_size < 1) return fail(h, FCD_E_INVALID, "beam_size cannot be 0");
+    if (N < 2) return fail(h, FCD_E_UNSUPPORTED, "alphabet needs at least one label besides the blank");
+    if (N > 256) return fail(h, FCD_E_UNSUPPORTED, "alphabets above 256 labels are unsupported (u8 labels)");
+    if (max_steps >= (1ll << 28)) return fail(h, FCD_E_UNSUPPORTED, "max_steps must be < 2^28");
+    if (crf && (S < 1 || !init || n_init < 1)) return fail(h, FCD_E_INVALID, "a CRF session needs S >= 1 and an init row per slot");
+    if (kernel == FCD_KERNEL_LANE) return fail(h, FCD_E_UNSUPPORTED, "sessions do not run on the lane kernel (wide beams take the generic kernel)");
+    if (kernel < FCD_KERNEL_AUTO || kernel > FCD_KERNEL_LANE) return fail(h, FCD_E_INVALID, "unknown kernel");
+    const int beam = (int)std::min<int64_t>(beam_size, 1 << 20);
+    const int NL = (int)N - 1;
+    const int tie = effective_tie_order(h);
+    // kernel choice (as beam_dev): the wave kernel where it holds the shape and node ids of max_steps rows fit 25 bits
+    bool wave = false;
+    int shift = 0;
+    if (kernel != FCD_KERNEL_GENERIC) {
+        const bool ok = beam_wave_supported(beam, (int)N, crf, (int)S);
+        shift = beam_wave_id_shift(beam, (int)N, kernel == FCD_KERNEL_WAVE1);
+        wave = ok && (max_steps << shift) + 16 < (1ll << 25);
+        if (!wave && kernel != FCD_KERNEL_AUTO)
+            return fail(h, FCD_E_UNSUPPORTED, ok ? "wave kernel: max_steps too large" : "wave kernel: needs beam_size <= 8 and N <= 7, or beam_size <= 12 and N <= 5 (CRF: N = 5, S a power of two >= 4)");
+    }
+    int64_t cap, block_words;
+    size_t slab_bytes;
+    if (wave) {
+        cap = ((max_steps << shift) + 8 + 3) & ~3ll;
+        slab_bytes = (size_t)cap * (4 + 4 + (NL <= 4 ? 4 : 8) * 4);
+        block_words = kSesWaveWords;
+    } else {
+        if (beam > (1 << 16)) return fail(h, FCD_E_UNSUPPORTED, "beam_size above 65536");
+        if (beam_generic_lds_bytes(beam, (int)N, tie) > 64 * 1024)
+            return fail(h, FCD_E_UNSUPPORTED, "beam_size * alphabet too large for the LDS-resident kernel");
+        cap = max_steps * beam * NL + 8;
+        if (cap >= (1ll << 30)) return fail(h, FCD_E_UNSUPPORTED, "tree arena above 2^30 nodes per slot");
+        slab_bytes = (size_t)cap * (sizeof(int4) + (size_t)NL * 4);
+        block_words = ses_generic_words(beam, N);
+    }
+    const size_t o_len = align256((size_t)n_reads * block_words * 4);
+    const size_t o_slots = o_len + align256((size_t)n_reads * 8);
+    const size_t o_init = o_slots + align256((size_t)n_reads * 8);
+    const size_t o_slab = o_init + align256(crf ? (size_t)n_reads * n_init * 4 : 0);
+    const size_t bytes = o_slab + (size_t)n_reads * slab_bytes;
+    DeviceGuard dev_guard(h->device);
+    FCD_HIP(h, dev_guard.err);
+    fcd_beam_session *s = new fcd_beam_session();
+    s->h = h;
+    s->n = n_reads;
+    s->N = N;
+    s->S = crf ? S : 1;
+    s->max_steps = max_steps;
+    s->beam = beam;
+    s->n_init = crf ? n_init : 0;
+    s->thr = thr;
+    s->collapse = crf ? 0 : (collapse ? 1 : 0);
+    s->crf = crf;
+    s->wave = wave ? 1 : 0;
+    s->force1 = kernel == FCD_KERNEL_WAVE1 ? 1 : 0;
+    s->tie_order = tie;
+    s->steps.assign((size_t)n_reads, 0);
+    if (hipMalloc(&s->mem, bytes) != hipSuccess) {
+        s->mem = nullptr;
+        ses_free(s);
+        return fail(h, FCD_E_NOMEM, "hipMalloc of the session's state and tree slabs failed");
+    }
+    s->bytes = bytes;
+    const size_t pin_bytes = align256((size_t)n_reads * 8) + (size_t)n_reads * std::max<int64_t>(s->n_init, 1) * 4;
+    if (hipHostMalloc(reinterpret_cast<void **>(&s->pin), pin_bytes, hipHostMallocDefault) != hipSuccess) {
+        s->pin = nullptr;
+        ses_free(s);
+        return fail(h, FCD_E_NOMEM, "hipHostMalloc of the session's staging buffer failed");
+    }
+    if (hipEventCreateWithFlags(&s->pin_ev, hipEventDisableTiming) != hipSuccess) {
+        s->pin_ev = nullptr;
+        ses_free(s);
+        return fail(h, FCD_E_HIP, "hipEventCreate failed");
+    }
+    char *base = static_cast<char *>(s->mem);
+    s->ses.state = reinterpret_cast<int32_t *>(base);
+    s->ses.block_words = block_words;
+    s->ses.count_amb = count_ambiguous ? 1 : 0;
+    s->d_len = reinterpret_cast<int64_t *>(base + o_len);
+    s->d_slots = reinterpret_cast<int64_t *>(base + o_slots);
+    s->d_init = reinterpret_cast<float *>(base + o_init);
+    if (wave) {
+        s->war.cap_nodes = cap;
+        s->war.row_words = NL <= 4 ? 4 : 8;
+        s->war.rec = reinterpret_cast<int32_t *>(base + o_slab);
+        s->war.jmp = s->war.rec + (size_t)n_reads * cap;
+        s->war.rows = s->war.jmp + (size_t)n_reads * cap;
+    } else {
+        s->gar.cap_nodes = cap;
+        s->gar.rec = reinterpret_cast<int4 *>(base + o_slab);
+        s->gar.rows = reinterpret_cast<int32_t *>(base + o_slab + (size_t)n_reads * cap * sizeof(int4));
+    }
+    // every slot starts at the root
+    std::vector<int64_t> all((size_t)n_reads);
+    for (int64_t r = 0; r < n_reads; ++r) all[(size_t)r] = r;
+    int rc = ses_restart(s, all.data(), n_reads, init);
+    if (rc == FCD_OK && hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(h, FCD_E_HIP, "session initialisation failed");
+    if (rc) {
+        ses_free(s);
+        return rc;
+    }
+    h->live_sessions++;
+    *out = s;
+    return FCD_OK;
+}
+
+// the *_host forms: posteriors and results through the handle's staging buffer, synchronous
+int ses_host(fcd_beam_session *s, const fcd_batch *chunk, const fcd_result *out) {
+    fcd_handle *h = s->h;
+    const size_t n = (size_t)s->n, w = (size_t)s->max_steps;
+    const size_t in_bytes = chunk ? (size_t)span_elems(chunk, s->crf != 0) * (chunk->dtype == FCD_DTYPE_F32 ? 4 : 2) : 0;
+    const size_t o_lab = align256(in_bytes), o_path = o_lab + align256(n * w), o_olen = o_path + align256(n * w * 4);
+    const size_t o_stat = o_olen + align256(n * 4), o_amb = o_stat + align256(n * 4), used = o_amb + n * 8;
+    FCD_DEVICE(h);
+    int rc = ensure(h, &h->stage, &h->stage_bytes, used);
+    if (rc) return rc;
+    char *base = static_cast<char *>(h->stage);
+    fcd_batch din{};
+    if (chunk) {
+        din = *chunk;
+        din.post = base;
+        if (in_bytes) FCD_HIP(h, hipMemcpyAsync(base, chunk->post, in_bytes, hipMemcpyHostToDevice, h->stream));
+    }
+    fcd_result dout{};
+    if (out) {
+        dout.labels = reinterpret_cast<uint8_t *>(base + o_lab);
+        dout.path = out->path ? reinterpret_cast<uint32_t *>(base + o_path) : nullptr;
+        dout.out_len = reinterpret_cast<uint32_t *>(base + o_olen);
+        dout.status = reinterpret_cast<int32_t *>(base + o_stat);
+        dout.ambiguous = out->ambiguous ? reinterpret_cast<uint32_t *>(base + o_amb) : nullptr;
+        dout.out_stride = (int64_t)w;
+    }
+    rc = ses_launch(s, chunk ? &din : nullptr, out ? &dout : nullptr);
+    if (rc) return rc;
+    if (out) {
+        const hipStream_t st = h->stream;
+        auto rows = [&](void *dst, const char *src, size_t elem) -> hipError_t {
+            if ((size_t)out->out_stride == w) return hipMemcpyAsync(dst, src, n * w * elem, hipMemcpyDeviceToHost, st);
+            for (size_t r = 0; r < n; ++r) {
+                hipError_t e = hipMemcpyAsync(static_cast<char *>(dst) + r * out->out_stride * elem, src + r * w * elem, w * elem,
+                                              hipMemcpyDeviceToHost, st);
+                if (e != hipSuccess) return e;
+            }
+            return hipSuccess;
+        };
+        FCD_HIP(h, rows(out->labels, base + o_lab, 1));
+        if (out->path) FCD_HIP(h, rows(out->path, base + o_path, 4));
+        FCD_HIP(h, hipMemcpyAsync(out->out_len, base + o_olen, n * 4, hipMemcpyDeviceToHost, st));
+        FCD_HIP(h, hipMemcpyAsync(out->status, base + o_stat, n * 4, hipMemcpyDeviceToHost, st));
+        if (out->ambiguous) FCD_HIP(h, hipMemcpyAsync(out->ambiguous, base + o_amb, n * 8, hipMemcpyDeviceToHost, st));
+    }
+    FCD_HIP(h, hipStreamSynchronize(h->stream));
+    return FCD_OK;
+}
+
+int ses_check_chunk(fcd_beam_session *s, const fcd_batch *chunk) {
+    fcd_handle *h = s->h;
+    int rc = check_batch(h, chunk, s->crf != 0);
+    if (rc) return rc;
+    if (chunk->n_reads != s->n) return fail(h, FCD_E_INVALID, "chunk->n_reads must be the session's n_reads");
+    if (chunk->N != s->N || (s->crf && chunk->S != s->S)) return fail(h, FCD_E_INVALID, "chunk shape differs from the session's");
+    return FCD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fcd_beam_session_create(fcd_handle *h, int64_t n_reads, int64_t N, int64_t max_steps, int64_t beam_size,
+                            float beam_cut_threshold, int collapse_repeats, int kernel, int count_ambiguous,
+                            fcd_beam_session **out) {
+    return ses_create(h, n_reads, 1, N, 0, nullptr, 0, max_steps, beam_size, beam_cut_threshold, collapse_repeats, kernel,
+                      count_ambiguous, out);
+}
+
+int fcd_crf_beam_session_create(fcd_handle *h, int64_t n_reads, int64_t S, int64_t N, const float *init, int64_t n_init,
+                                int64_t max_steps, int64_t beam_size, float beam_cut_threshold, int kernel,
+                                int count_ambiguous, fcd_beam_session **out) {
+    return ses_create(h, n_reads, S, N, 1, init, n_init, max_steps, beam_size, beam_cut_threshold, 0, kernel,
+                      count_ambiguous, out);
+}
+
+int fcd_beam_session_push_dev(fcd_beam_session *s, const fcd_batch *chunk, const fcd_result *out) {
+    if (!s) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> g(s->h->mu);
+    int rc = ses_check_chunk(s, chunk);
+    if (rc) return rc;
+    if (out && (rc = ses_check_out(s, out))) return rc;
+    return ses_launch(s, chunk, out);
+}
+
+int fcd_beam_session_push_host(fcd_beam_session *s, const fcd_batch *chunk, const fcd_result *out) {
+    if (!s) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> g(s->h->mu);
+    int rc = ses_check_chunk(s, chunk);
+    if (rc) return rc;
+    if (out && (rc = ses_check_out(s, out))) return rc;
+    return ses_host(s, chunk, out);
+}
+
+int fcd_beam_session_result_dev(fcd_beam_session *s, const fcd_result *out) {
+    if (!s) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> g(s->h->mu);
+    if (!out) return fail(s->h, FCD_E_INVALID, "null result");
+    int rc = ses_check_out(s, out);
+    if (rc) return rc;
+    return ses_launch(s, nullptr, out);
+}
+
+int fcd_beam_session_result_host(fcd_beam_session *s, const fcd_result *out) {
+    if (!s) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> g(s->h->mu);
+    if (!out) return fail(s->h, FCD_E_INVALID, "null result");
+    int rc = ses_check_out(s, out);
+    if (rc) return rc;
+    return ses_host(s, nullptr, out);
+}
+
+int fcd_beam_session_restart(fcd_beam_session *s, const int64_t *slots, int64_t n, const float *init) {
+    if (!s) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> g(s->h->mu);
+    return ses_restart(s, slots, n, init);
+}
+
+int fcd_beam_session_steps(const fcd_beam_session *s, int64_t *steps) {
+    if (!s || !steps) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> g(s->h->mu);
+    memcpy(steps, s->steps.data(), (size_t)s->n * 8);
+    return FCD_OK;
+}
+
+int64_t fcd_beam_session_bytes(const fcd_beam_session *s) { return s ? (int64_t)s->bytes : 0; }
+
+int fcd_beam_session_destroy(fcd_beam_session *s) {
+    if (!s) return FCD_OK;
+    fcd_handle *h = s->h;
+    std::lock_guard<std::recursive_mutex> g(h->mu);
+    DeviceGuard dev_guard(h->device);
+    (void)hipStreamSynchronize(h->stream);  // (its last launches may still read the state)
+    ses_free(s);
+    h->live_sessions--;
+    return FCD_OK;
 }
 
 }  // extern "C"

@@ -48,6 +48,22 @@ struct NBestDesc {
     int64_t n_best;
 };
 
+// Beam-search sessions (fcd_beam_session_*): the saved search of every slot, read by the SES instantiations of the wave
+// and generic kernels only -- state == nullptr everywhere else.  (The LAST member of the beam kernels' parameter blocks,
+// behind NBestDesc: the fields before it keep their kernel-argument offsets.)
+// Slot r's block of block_words i32 starts at state + r * block_words; its first kSesHeader words are
+//   [0] beam length B  [1] alive  [2] status once failed  [3] [4] the two tie counters  [5] steps taken (t0)
+//   [6] wave kernel: a bad CRF init waits for the slot's first non-empty push / generic kernel: nodes in the tree
+// followed by the kernel's own form of the beam (beam_wave.hip, beam_generic.hip).
+constexpr int kSesHeader = 8;
+constexpr int kSesWaveWords = kSesHeader + 8 * 64;  // eight registers of each of the 64 lanes, verbatim
+struct SessionDesc {
+    int32_t *state;
+    int64_t block_words;
+    int count_amb;  // the session counts ties (fcd_result.ambiguous), whether or not this launch reports them
+};
+inline int64_t ses_generic_words(int64_t beam_size, int64_t N) { return kSesHeader + beam_size * (7 + (N - 1)); }
+
 // Parameters of the 1D beam searches (search::beam_search / search::crf_beam_search).
 struct BeamArgs {
     int beam_size;
@@ -97,7 +113,7 @@ struct WaveArena {
 size_t beam_generic_lds_bytes(int beam_size, int N, int tie_order);  // (the quicksort's list and scratch only under FCD_TIE_PDQ178 above 20 candidates)
 hipError_t launch_beam_generic(const BatchDesc &in, int64_t read_begin, int64_t n_reads,
                                const BeamArgs &a, const GenericArena &arena, const ResultDesc &out,
-                               hipStream_t stream, const NBestDesc &nb = NBestDesc{});
+                               hipStream_t stream, const NBestDesc &nb = NBestDesc{}, const SessionDesc &ses = SessionDesc{});
 
 int beam_lane_reads_per_wave(int beam_size);  // of a first pass (a retry pass: one)
 // wavefronts of the instantiation the current device holds at once: the size of a slab pool nobody ever waits for
@@ -110,6 +126,12 @@ int beam_wave_id_shift(int beam_size, int N, int force_one_read_per_wave);
 hipError_t launch_beam_wave(const BatchDesc &in, int64_t read_begin, int64_t n_reads,
                             const BeamArgs &a, const WaveArena &arena, const ResultDesc &out,
                             hipStream_t stream, const NBestDesc &nb = NBestDesc{});
+// the session instantiations of the wave kernel (beam_wave_session.hip): n_reads = the session's slots, from slot 0
+hipError_t launch_beam_wave_session(const BatchDesc &in, int64_t n_reads, const BeamArgs &a, const WaveArena &arena,
+                                    const ResultDesc &out, const SessionDesc &ses, hipStream_t stream);
+// sessions: the root state of the listed slots (session.hip).  CRF: from init rows [n_slots][n_init], row j for slots[j]
+hipError_t launch_session_restart(const SessionDesc &ses, const int64_t *slots, int64_t n_slots, bool wave, int beam_size,
+                                  int N, int crf, int S, const float *init, int64_t n_init, hipStream_t stream);
 
 // one beam entry per lane: beam_size <= 64, N <= 8 (CRF: N = 5, S a power of two >= 4); uses the wave arena layout
 bool beam_lane_supported(int beam_size, int N, int crf, int S);
@@ -216,6 +238,7 @@ hipError_t coop_prof_read(unsigned long long *out16, bool reset);  // developer 
 hipError_t beam_wave_set_pdq178_std_form(int bits);
 hipError_t beam_lane_set_pdq178_std_form(int bits);
 hipError_t beam_generic_set_pdq178_std_form(int bits);
+hipError_t beam_wave_session_set_pdq178_std_form(int bits);
 hipError_t tieorder_set_pdq178_std_form(int bits);
 hipError_t lane_tie_prof_read(unsigned long long *out16, bool reset);  // ... of a -DFCD_LANE_TIE_PROF build of beam_lane.hip
 // the tie order searches on this handle use (capi.hip)
@@ -322,6 +345,7 @@ struct fcd_handle {
     // chunk lanes of the pipelined host path (hostjob.hip): sub-handles with their own stream and workspace
     std::vector<fcd_host_lane *> lanes;
     bool job_active = false;  // a host job owns the lanes from begin to end
+    int live_sessions = 0;    // fcd_beam_session_create .. _destroy
     bool is_lane = false;
     uint32_t *duplex_prof = nullptr;  // fcd_debug_set_duplex_profile
     int duplex_kernel = 0;            // fcd_debug_set_duplex_kernel: 0 automatic, 1 the any-shape kernel (duplex.hip), 2 the slot-resident one

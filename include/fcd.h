@@ -299,6 +299,54 @@ int fcd_crf_beam_search_nbest_host(fcd_handle *h, const fcd_batch *in, const flo
                                    int64_t init_stride, int64_t beam_size, float beam_cut_threshold, int kernel,
                                    const fcd_nbest *nb, const fcd_result *out);
 
+/* ---- beam-search sessions: search::beam_search / search::crf_beam_search on rows as they arrive ----
+ * (src/search.rs:159-301, :38-157.)  Both searches are causal: step t reads row t, the beam and the prefix tree, nothing
+ * else.  A session is a fixed set of n_reads read SLOTS with a fixed search shape (N, S, beam_size, beam_cut_threshold,
+ * collapse_repeats, max_steps = the most rows a slot takes between restarts; the tie order in force on the handle and the
+ * kernel are frozen at create).  Each slot's search advances over the rows pushed to it and can be read back at any time.
+ *   push   : chunk->n_reads == n_reads, T_c rows; slot r takes the first lengths[r] rows (all T_c if lengths is NULL, 0
+ *            leaves it untouched).  chunk->lengths is a HOST pointer here (the one exception to the _dev convention: the
+ *            session keeps a host-side step count per slot, and stages the lengths to the device in stream order from a
+ *            page-locked buffer it does not reuse before the copy has completed).  Any strides and f32 / f16 / bf16,
+ *            which may change from push to push.  A push that would take a slot past max_steps is FCD_E_INVALID before
+ *            anything is enqueued, the session unchanged.  out (nullable): the result after the push, from the same launch.
+ *   result : for every slot, exactly what fcd_beam_search_dev / fcd_crf_beam_search_dev return for the slot's PREFIX (all
+ *            rows pushed since create or its restart, concatenated): labels, path (row indices into the prefix), out_len,
+ *            status and -- count_ambiguous sessions only, out->ambiguous given -- the two tie counters over the prefix.
+ *            out_stride >= max_steps.  Before the first push: a read of length 0.  The session does not change.
+ *   A slot that fails (FCD_ST_INCOMPARABLE, FCD_ST_RAN_OUT_OF_BEAM, CRF FCD_ST_BAD_STATE -- a bad init row at its first
+ *   non-empty push) stays failed: later pushes leave it alone, as the one-shot search fails every longer prefix.
+ *   restart: slots[0 .. n) (host) go back to the root with 0 steps; CRF: init (host) holds n rows of n_init, row j for
+ *            slots[j].  create: init (host) holds n_reads rows of n_init.
+ * Kernel: FCD_KERNEL_AUTO takes the wave kernel where it holds the shape and (max_steps << id shift) + 16 < 2^25, else the
+ * LDS-resident kernel; WAVE / WAVE1 / GENERIC force one; FCD_KERNEL_LANE is FCD_E_UNSUPPORTED (wide beams run on the
+ * generic kernel).  Memory: ONE device allocation made at create (FCD_E_NOMEM if it fails), outside the handle's workspace
+ * and its limit; fcd_beam_session_bytes says how large.  Per slot: wave kernel 2080 B of state + cap * (8 + 4 * row
+ * words) B of tree, cap = (max_steps << s) + 8 rounded up to 4, s = 5 at beam <= 5 and N <= 5 (WAVE1: 6) else 6, row
+ * words 4 (N <= 5) or 8; generic kernel (32 + 4 * beam_size * (N + 6)) B of state + (max_steps * beam_size * (N-1) + 8) *
+ * (16 + 4 * (N-1)) B of tree; plus 16 B (lengths, slot list) and, CRF, 4 * n_init B.
+ * Ordering: every enqueuing call runs on the handle's current stream (never on the fcd_set_overlap internal streams: a
+ * session's pushes stay in order), behind overlapping calls in flight that write arrays it reads or writes.  The
+ * session's state and staged lengths are ordered by that stream alone: a caller that changes the handle's stream between
+ * two session calls must order the two streams itself.  fcd_destroy
+ * is FCD_E_INVALID while the handle has live sessions.  The _host forms take host posteriors / results and return when
+ * the results are in place.  Not covered: the lane kernel, n-best results, viterbi / greedy and the duplex searches. */
+typedef struct fcd_beam_session fcd_beam_session;
+int fcd_beam_session_create(fcd_handle *h, int64_t n_reads, int64_t N, int64_t max_steps, int64_t beam_size,
+                            float beam_cut_threshold, int collapse_repeats, int kernel, int count_ambiguous,
+                            fcd_beam_session **out);
+int fcd_crf_beam_session_create(fcd_handle *h, int64_t n_reads, int64_t S, int64_t N, const float *init, int64_t n_init,
+                                int64_t max_steps, int64_t beam_size, float beam_cut_threshold, int kernel,
+                                int count_ambiguous, fcd_beam_session **out);
+int fcd_beam_session_push_dev(fcd_beam_session *s, const fcd_batch *chunk, const fcd_result *out);
+int fcd_beam_session_push_host(fcd_beam_session *s, const fcd_batch *chunk, const fcd_result *out);
+int fcd_beam_session_result_dev(fcd_beam_session *s, const fcd_result *out);
+int fcd_beam_session_result_host(fcd_beam_session *s, const fcd_result *out);
+int fcd_beam_session_restart(fcd_beam_session *s, const int64_t *slots, int64_t n, const float *init);
+int fcd_beam_session_steps(const fcd_beam_session *s, int64_t *steps);  /* [n_reads] rows taken since create / restart */
+int64_t fcd_beam_session_bytes(const fcd_beam_session *s);
+int fcd_beam_session_destroy(fcd_beam_session *s);
+
 /* ---- search::crf_greedy_search (src/search.rs:385-423) ---- */
 int fcd_crf_greedy_search_dev(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init,
                               int64_t init_stride, const fcd_result *out);
