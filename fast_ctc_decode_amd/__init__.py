@@ -37,6 +37,8 @@ from .api import (  # noqa: F401
     crf_beam_search_nbest,
     crf_beam_search_nbest_batch_raw,
     crf_greedy_search,
+    ctc_score,
+    ctc_score_batch_raw,
     crf_greedy_search_batch,
     crf_greedy_search_batch_raw,
     estimate_envelope,

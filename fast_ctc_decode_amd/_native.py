@@ -50,6 +50,7 @@ SYMBOLS = [
     "fcd_beam_session_create", "fcd_crf_beam_session_create", "fcd_beam_session_push_dev", "fcd_beam_session_push_host",
     "fcd_beam_session_result_dev", "fcd_beam_session_result_host", "fcd_beam_session_restart", "fcd_beam_session_steps",
     "fcd_beam_session_bytes", "fcd_beam_session_destroy",
+    "fcd_ctc_score_dev", "fcd_ctc_score_host",
 ]
 JOB_PATH, JOB_QUAL, JOB_AMBIGUOUS, JOB_DONE = 1, 2, 4, 1
 
@@ -73,6 +74,12 @@ class Result(C.Structure):
 class NBest(C.Structure):
     """fcd_nbest: n best hypotheses per read of the beam searches (include/fcd.h)."""
     _fields_ = [("n_best", C.c_int64), ("score", C.c_void_p), ("n_hyp", C.c_void_p)]
+
+
+class Labellings(C.Structure):
+    """fcd_labellings: the labellings fcd_ctc_score_* scores, in fcd_result / fcd_nbest layout (include/fcd.h)."""
+    _fields_ = [("labels", C.c_void_p), ("len", C.c_void_p), ("n_valid", C.c_void_p), ("path", C.c_void_p),
+                ("n_hyp", C.c_int64), ("stride", C.c_int64)]
 
 
 class Chunk(C.Structure):
@@ -224,6 +231,8 @@ def bind(lib):
     lib.fcd_beam_session_bytes.argtypes = [P]
     lib.fcd_beam_session_bytes.restype = i64
     lib.fcd_beam_session_destroy.argtypes = [P]
+    for sfx in ("dev", "host"):
+        getattr(lib, "fcd_ctc_score_" + sfx).argtypes = [P, BP, C.POINTER(Labellings), i32, i64, P]
     return lib
 
 

@@ -781,6 +781,19 @@ class BatchResult:
         return BatchResult(c(self.labels), c(self.path), c(self.out_len), c(self.status), c(self.qual),
                            c(self.ambiguous))
 
+    def ctc_score(self, network_outputs, collapse_repeats=True, lengths=None, band=0, input_dtype=None):
+        """ln P(labelling | posteriors) of every read's result, float64 (n_reads, 1): ctc_score_batch_raw on this
+        result's own arrays (device results stay on the device; no host round trip).  `network_outputs`, `lengths`
+        and `collapse_repeats` as given to the search.  A failed read has an empty labelling and scores as one.
+        CRF results are refused (transition-scored models: a different lattice)."""
+        if isinstance(self, _CrfBatchResult) or getattr(network_outputs, "ndim", 3) != 3:
+            raise ValueError("ctc_score covers the plain CTC searches, not CRF results")
+        if band and self.path is None:
+            raise ValueError("a band needs the result's path")
+        return ctc_score_batch_raw(network_outputs, self.labels, self.out_len, collapse_repeats, lengths,
+                                   self.path if band else None, band, None, input_dtype,
+                                   getattr(self, "_handle", None))
+
     def sequences(self, alphabet, raise_on_error=True, paths="list"):
         """-> list of (str, path) per read, exactly what the single-read functions return.
 
@@ -1077,6 +1090,15 @@ class NBestResult:
         return NBestResult(c(self.labels), c(self.path), c(self.out_len), c(self.score), c(self.n_hyp), c(self.status),
                            c(self.ambiguous), self.crf)
 
+    def ctc_score(self, network_outputs, collapse_repeats=True, lengths=None, band=0, input_dtype=None):
+        """ln P(labelling | posteriors) of every hypothesis, float64 (n_reads, n_best); NaN where i >= n_hyp[r].
+        ctc_score_batch_raw on this result's own arrays (n_hyp as n_valid); CRF results are refused."""
+        if self.crf or getattr(network_outputs, "ndim", 3) != 3:
+            raise ValueError("ctc_score covers the plain CTC searches, not CRF results")
+        return ctc_score_batch_raw(network_outputs, self.labels, self.out_len, collapse_repeats, lengths,
+                                   self.path if band else None, band, self.n_hyp, input_dtype,
+                                   getattr(self, "_handle", None))
+
     def hypotheses(self, alphabet, raise_on_error=True):
         """-> per read, a list of (seq, path, score), best first (None for a failed read when not raise_on_error)."""
         r = self.cpu()
@@ -1251,6 +1273,132 @@ def crf_beam_search_nbest(network_output, init_state, alphabet, n_best, beam_siz
                                         beam_cut_threshold)
     _raise_status(int(r.status[0]))
     return r.hypotheses(alpha)[0]
+
+
+# ---------------------------------------------------------------------------------------------
+# CTC forward log-likelihood of given labellings (include/fcd.h, fcd_ctc_score_*)
+# ---------------------------------------------------------------------------------------------
+def _score_shapes(labels_shape, B):
+    if len(labels_shape) == 2:
+        n_hyp, stride = 1, labels_shape[1]
+    elif len(labels_shape) == 3:
+        n_hyp, stride = labels_shape[1], labels_shape[2]
+    else:
+        raise ValueError("labels must have shape (n_reads, stride) or (n_reads, n_hyp, stride)")
+    if labels_shape[0] != B:
+        raise ValueError("labels must have one row (or n_hyp rows) per read")
+    if n_hyp < 1:
+        raise ValueError("n_hyp must be at least 1")
+    return int(n_hyp), int(stride)
+
+
+def _check_band(band, paths):
+    if isinstance(band, bool) or not isinstance(band, (int, np.integer)):
+        raise TypeError("argument 'band': expected an integer")
+    if band < 0:
+        raise ValueError("band must be at least 0")
+    if band > 0 and paths is None:
+        raise ValueError("a band needs paths (the row at which each label was emitted)")
+    return int(band)
+
+
+def ctc_score_batch_raw(network_outputs, labels, label_lengths, collapse_repeats=True, lengths=None, paths=None,
+                        band=0, n_valid=None, input_dtype=None, handle=None):
+    """CTC forward log-likelihood ln P(y | x) of labellings y against the (B,T,N) posteriors x: the sum over every
+    alignment, not the beam search's pruned estimate -- float64, comparable between reads (include/fcd.h,
+    fcd_ctc_score_*).  -> (B, n_hyp) float64.
+
+    labels (B, stride) or (B, n_hyp, stride) uint8 label indices 1 .. N-1 and label_lengths (B,) / (B, n_hyp), as the
+    searches return them (BatchResult / NBestResult: .labels, .out_len).  band=0 scores the exact lattice; band=W > 0
+    only the alignments within W labels of `paths` (same shape as labels: the row each label was emitted at) -- a
+    lower bound that rises with W, at a cost that no longer grows with the labelling's length.  n_valid (B,): rows
+    i >= n_valid[r] are not scored (NaN).  Device tensors in: a torch tensor on the same device, enqueued on torch's
+    current stream, not synchronised.  numpy in: numpy out."""
+    band = _check_band(band, paths)
+    dev_x = _device_tensor(network_outputs)
+    if dev_x is not None:
+        import torch
+        x = dev_x
+        if x.ndim != 3:
+            raise ValueError("expected (n_reads, T, N) posteriors")
+        B, T, N = x.shape
+        dev = x.device
+        h = handle if handle is not None else nat.default_handle(dev.index or 0)
+
+        def as_dev(a, dtype):
+            if isinstance(a, np.ndarray) and a.dtype == np.uint32:
+                a = a.view(np.int32)  # (the same 32 bits: the searches' device results are int32 tensors)
+            a = torch.as_tensor(a, device=dev)
+            return (a if a.dtype == dtype else a.to(dtype)).contiguous()
+        lab = as_dev(labels, torch.uint8)
+        n_hyp, stride = _score_shapes(tuple(lab.shape), B)
+        ylen = as_dev(label_lengths, torch.int32)
+        if ylen.numel() != B * n_hyp:
+            raise ValueError("label_lengths must have one entry per labelling")
+        pth = as_dev(paths, torch.int32) if band else None
+        if pth is not None and tuple(pth.shape) != tuple(lab.shape):
+            raise ValueError("paths must have the shape of labels")
+        nv = as_dev(n_valid, torch.int32) if n_valid is not None else None
+        if nv is not None and nv.numel() != B:
+            raise ValueError("n_valid must have shape (n_reads,)")
+        st = x.stride()
+        b = nat.Batch(x.data_ptr(), B, T, 1, N, st[0], st[1], 0, st[2], None, _torch_dtype_code(x))
+        if lengths is not None:
+            lengths = torch.as_tensor(lengths, dtype=torch.int64, device=dev).contiguous()
+            if lengths.numel() != B:
+                raise ValueError("lengths must have shape (n_reads,)")
+            b.lengths = lengths.data_ptr()
+        out = torch.empty((B, n_hyp), dtype=torch.float64, device=dev)
+        y = nat.Labellings(lab.data_ptr(), ylen.data_ptr(), nv.data_ptr() if nv is not None else None,
+                           pth.data_ptr() if pth is not None else None, n_hyp, stride)
+        h.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+        h.check(h.lib.fcd_ctc_score_dev(h.ptr, C.byref(b), C.byref(y), int(bool(collapse_repeats)), band,
+                                        C.c_void_p(out.data_ptr())))
+        return out
+    network_outputs, lengths = _ragged(network_outputs, lengths, 3)
+    x = _stack_host(network_outputs, 3)
+    B, T, N = x.shape
+    lab = np.ascontiguousarray(np.asarray(labels), np.uint8)
+    n_hyp, stride = _score_shapes(lab.shape, B)
+    ylen = np.ascontiguousarray(np.asarray(label_lengths), np.uint32)
+    if ylen.size != B * n_hyp:
+        raise ValueError("label_lengths must have one entry per labelling")
+    pth = np.ascontiguousarray(np.asarray(paths), np.uint32) if band else None
+    if pth is not None and pth.shape != lab.shape:
+        raise ValueError("paths must have the shape of labels")
+    nv = np.ascontiguousarray(np.asarray(n_valid), np.uint32) if n_valid is not None else None
+    if nv is not None and nv.shape != (B,):
+        raise ValueError("n_valid must have shape (n_reads,)")
+    h = nat.default_handle()
+    l = _np_lengths(lengths, B)
+    b = _host_batch(x, False, l, input_dtype)
+    out = np.empty((B, n_hyp), np.float64)
+    y = nat.Labellings(lab.ctypes.data, ylen.ctypes.data, nv.ctypes.data if nv is not None else None,
+                       pth.ctypes.data if pth is not None else None, n_hyp, stride)
+    h.check(h.lib.fcd_ctc_score_host(h.ptr, C.byref(b), C.byref(y), int(bool(collapse_repeats)), band,
+                                     out.ctypes.data))
+    return out
+
+
+def ctc_score(network_output, sequence, alphabet, collapse_repeats=True):
+    """ln P(sequence | network_output): the CTC forward log-likelihood of one string against one (T, N) float32
+    posterior matrix, exact (every alignment), as a float.  alphabet[0] is the blank; every label must be one
+    character (a multi-character alphabet cannot be split back unambiguously: ValueError)."""
+    x = _as_f32(network_output, 2, "network_output")
+    alpha = _seq_to_vec(alphabet)
+    _check_greedy_alphabet(len(alpha), x.shape[1])
+    if not isinstance(sequence, str):
+        raise TypeError("argument 'sequence': expected str")
+    if any(len(a) != 1 for a in alpha[1:]):
+        raise ValueError("ctc_score needs single-character labels")
+    index = {a: i for i, a in enumerate(alpha) if i > 0}
+    try:
+        y = [index[c] for c in sequence]
+    except KeyError as e:
+        raise ValueError("sequence holds %r, which is not a label of the alphabet" % e.args[0])
+    lab = np.zeros((1, max(len(y), 1)), np.uint8)
+    lab[0, :len(y)] = y
+    return float(ctc_score_batch_raw(_dense(x)[None], lab, np.array([len(y)], np.uint32), collapse_repeats)[0, 0])
 
 
 # ---------------------------------------------------------------------------------------------

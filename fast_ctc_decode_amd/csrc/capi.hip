@@ -1568,6 +1568,90 @@ int fcd_unpack_gathered_dev(fcd_handle *h, const uint8_t *gathered, int64_t stri
     return sc.finish();
 }
 
+// ---- CTC forward log-likelihood of given labellings (ctc_score.hip) ----
+static int ctc_score_check(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int64_t band, const double *logp) {
+    int rc = check_batch(h, in, false);
+    if (rc) return rc;
+    if (in->S != 1) return fail(h, FCD_E_INVALID, "ctc_score: S must be 1 (CRF models are not scored)");
+    if (!y) return fail(h, FCD_E_INVALID, "null labellings");
+    if (y->n_hyp < 1) return fail(h, FCD_E_INVALID, "n_hyp must be >= 1");
+    if (band < 0) return fail(h, FCD_E_INVALID, "band must be >= 0");
+    if (band > 0 && !y->path) return fail(h, FCD_E_INVALID, "a band needs the labellings' path");
+    if (y->stride < 0) return fail(h, FCD_E_INVALID, "negative stride");
+    if (in->n_reads > 0 && (!y->labels || !y->len || !logp)) return fail(h, FCD_E_INVALID, "null labels/len/logp");
+    if (in->n_reads * y->n_hyp >= (1ll << 31)) return fail(h, FCD_E_UNSUPPORTED, "more than 2^31 labellings in one call");
+    if (!ctc_score_supported(in->T, y->stride, band))
+        return fail(h, FCD_E_UNSUPPORTED, band > 0 ? "ctc_score: the band's window does not fit the 160 KiB of LDS: use a narrower band"
+                                                   : "ctc_score: the exact lattice does not fit the 160 KiB of LDS: use a band");
+    return FCD_OK;
+}
+
+int fcd_ctc_score_dev(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int collapse_repeats, int64_t band,
+                      double *logp) {
+    if (!h) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> g(h->mu);
+    int rc = ctc_score_check(h, in, y, band, logp);
+    if (rc) return rc;
+    if (in->n_reads == 0) return FCD_OK;
+    FCD_DEVICE(h);
+    const size_t n_rows = (size_t)in->n_reads * (size_t)y->n_hyp;
+    CallScope sc(h);
+    sc.add(y->labels, n_rows * (size_t)y->stride);
+    sc.add(y->len, n_rows * 4);
+    sc.add(y->n_valid, (size_t)in->n_reads * 4);
+    sc.add(y->path, n_rows * (size_t)y->stride * 4);
+    sc.add(logp, n_rows * 8);
+    rc = sc.begin(false, false);
+    if (rc) return rc;
+    const ScoreDesc yd{y->labels, y->len, y->n_valid, band > 0 ? y->path : nullptr, y->n_hyp, y->stride};
+    sc.time();
+    FCD_HIP(h, launch_ctc_score(to_desc(in, false), yd, collapse_repeats != 0, std::min<int64_t>(band, 1ll << 28), logp, sc.stream));
+    return sc.finish();
+}
+
+int fcd_ctc_score_host(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int collapse_repeats, int64_t band,
+                       double *logp) {
+    if (!h) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> whole_call(h->mu);  // staging .. copy-back, see run_host
+    int rc = ctc_score_check(h, in, y, band, logp);
+    if (rc) return rc;
+    if (in->n_reads == 0) return FCD_OK;
+    if (in->stride_read < 0 || in->stride_t < 0 || in->stride_n < 0) return fail(h, FCD_E_INVALID, "negative stride");
+    FCD_DEVICE(h);
+    const size_t B = (size_t)in->n_reads, n_rows = B * (size_t)y->n_hyp, esz = in->dtype == FCD_DTYPE_F32 ? 4 : 2;
+    // the posteriors keep their strides: the span from the first to the last addressed element is staged as it is
+    const size_t span = in->T > 0 ? (size_t)((in->n_reads - 1) * in->stride_read + (in->T - 1) * in->stride_t +
+                                             (in->N - 1) * in->stride_n + 1) : 0;
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t o_in = 0, o_len = o_in + al(span * esz), o_lab = o_len + al(B * 8);
+    const size_t o_ylen = o_lab + al(n_rows * (size_t)y->stride), o_nv = o_ylen + al(n_rows * 4);
+    const size_t o_path = o_nv + al(B * 4), o_out = o_path + (band > 0 ? al(n_rows * (size_t)y->stride * 4) : 0);
+    const size_t total = o_out + al(n_rows * 8);
+    rc = ensure(h, &h->stage, &h->stage_bytes, total);
+    if (rc) return rc;
+    char *d = reinterpret_cast<char *>(h->stage);
+    if (span) FCD_HIP(h, hipMemcpyAsync(d + o_in, in->post, span * esz, hipMemcpyHostToDevice, h->stream));
+    if (in->lengths) FCD_HIP(h, hipMemcpyAsync(d + o_len, in->lengths, B * 8, hipMemcpyHostToDevice, h->stream));
+    if (y->stride) FCD_HIP(h, hipMemcpyAsync(d + o_lab, y->labels, n_rows * (size_t)y->stride, hipMemcpyHostToDevice, h->stream));
+    FCD_HIP(h, hipMemcpyAsync(d + o_ylen, y->len, n_rows * 4, hipMemcpyHostToDevice, h->stream));
+    if (y->n_valid) FCD_HIP(h, hipMemcpyAsync(d + o_nv, y->n_valid, B * 4, hipMemcpyHostToDevice, h->stream));
+    if (band > 0 && y->stride)
+        FCD_HIP(h, hipMemcpyAsync(d + o_path, y->path, n_rows * (size_t)y->stride * 4, hipMemcpyHostToDevice, h->stream));
+    fcd_batch din = *in;
+    din.post = d + o_in;
+    din.lengths = in->lengths ? reinterpret_cast<const int64_t *>(d + o_len) : nullptr;
+    fcd_labellings dy = *y;
+    dy.labels = reinterpret_cast<const uint8_t *>(d + o_lab);
+    dy.len = reinterpret_cast<const uint32_t *>(d + o_ylen);
+    dy.n_valid = y->n_valid ? reinterpret_cast<const uint32_t *>(d + o_nv) : nullptr;
+    dy.path = band > 0 ? reinterpret_cast<const uint32_t *>(d + o_path) : nullptr;
+    rc = fcd_ctc_score_dev(h, &din, &dy, collapse_repeats, band, reinterpret_cast<double *>(d + o_out));
+    if (rc) return rc;
+    FCD_HIP(h, hipMemcpyAsync(logp, d + o_out, n_rows * 8, hipMemcpyDeviceToHost, h->stream));
+    FCD_HIP(h, hipStreamSynchronize(h->stream));
+    return FCD_OK;
+}
+
 }  // extern "C"
 
 // ---- *_host: stage host buffers through device memory, run the *_dev path, copy back -------

@@ -225,6 +225,21 @@ hipError_t launch_unpack_gathered(const uint8_t *gathered, int64_t stride, int w
                                   int64_t n_total, uint64_t *offsets, const ResultDesc &out, int32_t *bad,
                                   hipStream_t stream);
 
+// CTC forward scoring of given labellings (ctc_score.hip; fcd_labellings in include/fcd.h); all pointers device memory
+struct ScoreDesc {
+    const uint8_t *labels;
+    const uint32_t *len;
+    const uint32_t *n_valid;  // nullable
+    const uint32_t *path;     // nullable when band == 0
+    int64_t n_hyp;
+    int64_t stride;
+};
+// the most states a live window of such a call can hold, and whether the kernels hold it (LDS: 160 KiB per workgroup)
+int64_t ctc_score_window_states(int64_t T, int64_t stride, int64_t band);
+bool ctc_score_supported(int64_t T, int64_t stride, int64_t band);
+hipError_t launch_ctc_score(const BatchDesc &in, const ScoreDesc &y, int collapse, int64_t band, double *logp,
+                            hipStream_t stream);
+
 hipError_t launch_logspace_probe(const float *a, const float *b, float *out_add, float *out_ln,
                                  int64_t n, int mode, hipStream_t stream);
 hipError_t launch_glibc235_apply(int which, const float *x, float *y, int64_t n, hipStream_t stream);

@@ -347,6 +347,45 @@ int fcd_beam_session_steps(const fcd_beam_session *s, int64_t *steps);  /* [n_re
 int64_t fcd_beam_session_bytes(const fcd_beam_session *s);
 int fcd_beam_session_destroy(fcd_beam_session *s);
 
+/* ---- CTC forward log-likelihood of given labellings (csrc/ctc_score.hip) ----
+ * NOT a reference function.  logp[r * n_hyp + i] = ln P(y | x) = ln of the sum, over every alignment of labelling y
+ * (hypothesis i of read r) to the T_r rows of the read, of the product of the posteriors along it: the unpruned, unmerged
+ * sum of the recurrences search::beam_search walks (src/search.rs:186-241), float64, comparable between reads.
+ * Extended sequence z of 2L + 1 states, z[2k] = blank, z[2k+1] = y[k]; rows converted to f32 exactly as the searches do:
+ *   start   alpha_0[0] = p[0][0], alpha_0[1] = p[0][y_0], else 0
+ *   blank   alpha_t[s] = (alpha_{t-1}[s] + alpha_{t-1}[s-1]) * p[t][0]
+ *   label   collapse_repeats = 1: (alpha_{t-1}[s] + alpha_{t-1}[s-1] + [s >= 3, z[s] != z[s-2]] alpha_{t-1}[s-2]) * p[t][z[s]]
+ *           collapse_repeats = 0: (alpha_{t-1}[s-1] + [s >= 3] alpha_{t-1}[s-2]) * p[t][z[s]]  (every non-blank row emits)
+ *   result  ln(alpha_{T_r-1}[2L] + alpha_{T_r-1}[2L-1])
+ * L = 0: ln prod p[t][0].  T_r = 0: 0.0 for L = 0, else -inf.  P = 0 (L > T_r, ...): -inf.  A label outside 1 .. N-1 (or
+ * len > stride): NaN.  A NaN posterior in a cell that contributes: NaN.  Rows i >= n_valid[r]: not scored, NaN.
+ * band = 0: the exact lattice.  band = W >= 1: with k(t) = #{k : path[k] <= t} (path ascending, as the searches return it),
+ * only the states max(0, 2 (k(t) - W) - 2) <= s <= min(2L, 2 (k(t) + W)) are live at row t, every other state counts as 0
+ * there: the sum over the alignments that stay inside the window, a lower bound that rises with W.
+ * Numerics: alpha in f32 probability space, rescaled by exact powers of two every row with an integer exponent total,
+ * ln(m) + E ln 2 formed in float64, no logarithm per step; |error| <= about 3 T_r 2^-24 nats.  A cell below 2^-246 of its
+ * row's largest live cell may be dropped (the result is then a lower bound).  Posteriors outside [0, 1], infinities and
+ * negative values give some value, nothing more.
+ * in->S must be 1 (CRF models are scored on transitions: out of scope); in->lengths as everywhere (device / host pointer).
+ * Limits (FCD_E_UNSUPPORTED): the widest possible window, min(4 band + 3, 2 min(T, stride) + 1) states, lives in
+ * registers up to 510 states and double-buffered in LDS (160 KiB) beyond: about 18000 states, i.e. exact scoring of
+ * labellings up to ~9000 labels -- use a band beyond that.
+ * _dev: device pointers, enqueued on the handle's stream in stream order, behind overlapping searches in flight
+ * (fcd_set_overlap) that still write the arrays it reads.  _host: host pointers; stages, runs and copies back in one piece.
+ * FCD_E_INVALID before anything is enqueued: band < 0, band > 0 without path, n_hyp < 1, S != 1. */
+typedef struct fcd_labellings {
+    const uint8_t  *labels;   /* [n_reads * n_hyp * stride], row r * n_hyp + i: fcd_result.labels as the searches write it */
+    const uint32_t *len;      /* [n_reads * n_hyp]: fcd_result.out_len */
+    const uint32_t *n_valid;  /* [n_reads], nullable (fcd_nbest.n_hyp): rows i >= n_valid[r] are not scored, logp = NaN */
+    const uint32_t *path;     /* same shape as labels; required when band > 0, else nullable */
+    int64_t n_hyp;            /* rows per read: 1 for a plain result, n_best for an n-best one */
+    int64_t stride;           /* out_stride */
+} fcd_labellings;
+int fcd_ctc_score_dev(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int collapse_repeats, int64_t band,
+                      double *logp);
+int fcd_ctc_score_host(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int collapse_repeats, int64_t band,
+                       double *logp);
+
 /* ---- search::crf_greedy_search (src/search.rs:385-423) ---- */
 int fcd_crf_greedy_search_dev(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init,
                               int64_t init_stride, const fcd_result *out);
