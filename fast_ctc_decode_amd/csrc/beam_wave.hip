@@ -94,8 +94,17 @@ __device__ __forceinline__ int perm(int dst_lane, int v) {
 
 constexpr int kWavesPerBlock = 4;
 constexpr int kCrfGather = -1;
-constexpr int kFifo = 8;  // registers in the row FIFO
+constexpr int kFifo = 6;  // registers in the row FIFO
 constexpr int kSeg = 64;  // nodes per traceback segment (jump-pointer spacing)
+
+// Wavefronts per SIMD the register allocator is asked to leave room for (amdgpu_waves_per_eu on the kernel below; the value
+// is spelt out there: the emulator's host compiler does not take a function call inside an attribute it does not know).
+// Two reads per wavefront: 5, i.e. at most 96 VGPRs, since the rank's comparands are streamed (beam_wave_step.inc), the row
+// FIFO is six registers deep and the read's index is formed again after the time loop instead of being carried through
+// it.  The exact-rank instantiations then hold 70-92 VGPRs; the PDQ ones of equal-length launches (UNI: the headline) 95,
+// with the loop-carried state parked in LDS around the inlined quicksort of the rare tie branch.  No scratch in either.
+// The other PDQ instantiations (ragged lengths, 16-bit posteriors, n-best) answer a budget of 96 with 8 bytes of scratch,
+// which the time loop must not have, and stay at 4 wavefronts; so do the session instantiations.
 
 // S == 0: search::beam_search.  S > 0: search::crf_beam_search (:38-157) with S transition states:
 // the row is probs[t, state, :] of the entry's state, there is no repeat-stay, and an extension
@@ -135,7 +144,7 @@ constexpr int kSeg = 64;  // nodes per traceback segment (jump-pointer spacing)
 // A failure is kept in the state, not written to `out`: later launches leave the slot alone.
 template <int N, int GW, int RPW, int S, bool AMB, bool PROF = false, bool UNI = false, bool H16 = false, bool PDQ = false,
           bool NB = false, bool SES = false>
-__global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_per_eu((RPW == 2 && !AMB) ? 4 : 1))) void beam_wave_kernel(WaveParams p) {
+__global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_per_eu((RPW == 2 && !AMB) ? ((SES || (PDQ && !UNI)) ? 4 : 5) : 1))) void beam_wave_kernel(WaveParams p) {
     constexpr bool CRF = S != 0;
     constexpr bool GATHER = S == kCrfGather;
     constexpr int NL = N - 1;
@@ -153,7 +162,10 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_pe
     constexpr bool HAS_SCRATCH = N <= GW - 1;
     constexpr int NIDLE = HALF - BCAP * GW;
     static_assert(HAS_SCRATCH || NIDLE >= 1, "no lane left to absorb idle pushes");
-    __shared__ uint64_t s_keys[kWavesPerBlock][64];
+    __shared__ __attribute__((aligned(16))) uint64_t s_keys[kWavesPerBlock][64];  // (a slot's keys leave two per 16-byte read)
+    // the rank's comparands are streamed through a few registers (beam_wave_step.inc) instead of all being loaded first
+    constexpr bool STREAM = RPW == 2 && GW == 6 && !AMB;
+    static_assert(!STREAM || (GW % 2 == 0 && HALF % 2 == 0), "a slot's first key sits on 16 bytes");
     __shared__ int s_heads[kWavesPerBlock][64];
     // survivor table, per half: entry r = (byte address of the lane whose candidate took rank r) | that candidate's depth << 8
     // (PDQ: one entry per candidate rank, and as many tie words behind them -- per half)
@@ -162,6 +174,10 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_pe
     // PDQ: the node-ordered candidate list and the quicksort's tables of a tie-flagged step
     __shared__ uint64_t s_list[PDQ ? kWavesPerBlock : 1][64];
     __shared__ pdq178::WaveScratch<1> s_ws[PDQ ? kWavesPerBlock : 1];
+    // PDQ, two reads per wavefront: where loop-carried state waits while the quicksort of a tie-flagged step runs
+    constexpr bool PARK = PDQ && RPW == 2;
+    constexpr int kPark = kFifo + 18;
+    __shared__ int s_park[PARK ? kWavesPerBlock : 1][PARK ? kPark * 64 : 1];
     static_assert(!PDQ || BCAP * N > 20, "the tie order only matters above 20 candidates");
     static_assert(!PDQ || BCAP * N <= HALF - 2, "the last two entries of a half's table are never written (i_src below)");
     int n_amb = 0, n_crit = 0;
@@ -217,7 +233,16 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_pe
 
     const int64_t local = ((int64_t)blockIdx.x * kWavesPerBlock + wave) * RPW + (lane / HALF);
     const bool has_read = local < p.in.n_reads;  // n_reads here = reads in this launch
-    const int64_t r = p.read_begin + (has_read ? local : 0);
+    int64_t r = p.read_begin + (has_read ? local : 0);
+    // The read's index again, from a thread number the optimiser cannot see through: the time loop needs it only when a read
+    // fails, and the epilogue forms it afresh -- kept, it and the 64-bit offsets derived from it (status, length and label
+    // rows) are six registers carried through every step.
+    auto read_index_again = [&]() __attribute__((always_inline)) -> int64_t {
+        int tid = (int)threadIdx.x;
+        FCD_OPAQUE_V(tid);
+        const int64_t loc = ((int64_t)blockIdx.x * kWavesPerBlock + (tid >> 6)) * RPW + ((tid & 63) / HALF);
+        return p.read_begin + (loc < p.in.n_reads ? loc : 0);
+    };
 
     int T = 0;
     if (has_read) {
@@ -382,6 +407,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_pe
 #include "beam_wave_step.inc"
         }
     }
+    if (!SES) r = read_index_again();
     if (PROF && lane == 0 && p.a.prof) {
         uint32_t *o = p.a.prof + ((int64_t)blockIdx.x * kWavesPerBlock + wave) * 8;
 #pragma unroll

@@ -39,9 +39,9 @@
         const bool svalid = grp && is_self && (blank || stay || has_inc);
 
         const bool valid = svalid || (cvalid && !merged);  // svalid / cvalid already carry is_self / is_child
-        const float clp = is_self ? slp : contrib;
-        const float cgp = is_self ? sgp : 0.0f;
-        const float prob = clp + cgp;
+        float clp = is_self ? slp : contrib;  // (not const: PARK)
+        float cgp = is_self ? sgp : 0.0f;
+        float prob = clp + cgp;
 
         const bool is_new = cvalid && !exists;
 
@@ -51,15 +51,44 @@
         // lane, exactly like the index it is about to receive -- so the key does not wait for the numbering below.
         // (A NaN key is garbage but non-zero: it only ever ranks when it is the read's lone candidate, :262.)
         const int idk = is_self ? node : (is_new ? tks + q : cid);
-        const uint64_t key = (UNI ? valid : (valid && act)) ? make_key(prob, idk) : 0ull;
+        uint64_t key = (UNI ? valid : (valid && act)) ? make_key(prob, idk) : 0ull;
         keys[lane] = key;
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         constexpr int NC = BCAP * N;  // comparand u = (slot u / N, column u % N)
         uint64_t kk[NC];
+        // STREAM: the comparands are not all fetched up front (2 * NC registers, the largest live set of the step and what
+        // held the kernel at four wavefronts per SIMD) but in blocks of four, kAhead blocks before the block that counts
+        // them.  A slot's keys are contiguous and start on 16 bytes, so its columns leave two per ds_read_b128 -- the
+        // paired columns of all slots first, an odd last column of every slot (one ds_read_b64 each) after them; the order
+        // in which larger keys are counted is immaterial.
+        constexpr int NPR = (N / 2) * 2;   // columns of a slot that travel in pairs
+        constexpr int NP = BCAP * NPR;     // comparands v < NP: (slot v / NPR, column v % NPR); v >= NP: (slot v - NP, column N - 1)
+        constexpr int NBLK = (NC + 3) / 4;
+        constexpr int kAhead = 2;
+        auto load_blk = [&](int j) __attribute__((always_inline)) {
 #pragma unroll
-        for (int u = 0; u < NC; ++u) kk[u] = keys[hbase + (u / N) * GW + (u % N)];
+            for (int v = 4 * j; v < 4 * j + 4 && v < NC; ++v) {
+                if (v < NP) {
+                    if ((v & 1) == 0) {
+                        uint64_t two[2];
+                        __builtin_memcpy(two, __builtin_assume_aligned(&keys[hbase + (v / NPR) * GW + (v % NPR)], 16), 16);
+                        kk[v] = two[0];
+                        kk[v + 1] = two[1];
+                    }
+                } else {
+                    kk[v] = keys[hbase + (v - NP) * GW + (N - 1)];
+                }
+            }
+        };
+        if (STREAM) {
+#pragma unroll
+            for (int j = 0; j < kAhead && j < NBLK; ++j) load_blk(j);
+        } else {
+#pragma unroll
+            for (int u = 0; u < NC; ++u) kk[u] = keys[hbase + (u / N) * GW + (u % N)];
+        }
 
         // ---- tree.rs:125-145 add_node: ids in (beam order, label order) == lane order; runs under the LDS reads ----
         const uint64_t m_new = ballot(is_new);
@@ -79,7 +108,7 @@
             // a segment head (depth % 64 == 0) records where the next head up the tree is
             if ((depth + 1) % kSeg == 0) *at32(jmp_w, hoff + (uint32_t)newid) = (depth % kSeg == 0) ? node : jump;
         }
-        const int child_in = is_new ? newid : child;  // (the entry as the rest of the step sees it)
+        int child_in = is_new ? newid : child;  // (the entry as the rest of the step sees it)
         int id = is_self ? node : (is_new ? newid : cid);
         stamp_i(2, id);  // own candidate, key, node numbering, record stores
 
@@ -93,6 +122,26 @@
                 n_eq += (kk[u] != 0ull && (uint32_t)(kk[u] >> 32) == (uint32_t)(key >> 32)) ? 1 : 0;
                 n_gt += ((uint32_t)(kk[u] >> 32) > (uint32_t)(key >> 32)) ? 1 : 0;
             }
+        } else if (STREAM) {
+            // four independent compare-and-count chains (device_utils.h); the scheduling barriers keep the loads of block
+            // j + kAhead behind the count of block j - 1 (left alone, the scheduler hoists every load to the top again)
+            int r0, r1, r2, r3;
+            static_assert(!STREAM || NC >= 4, "at least one block of four comparands");
+#pragma unroll
+            for (int j = 0; j < NBLK; ++j) {
+                __builtin_amdgcn_sched_barrier(0);
+                if (j + kAhead < NBLK) load_blk(j + kAhead);
+                if (j == 0) {
+                    FCD_RANK4_FIRST(key, kk[0], kk[1], kk[2], kk[3], r0, r1, r2, r3);
+                } else if (4 * j + 4 <= NC) {
+                    FCD_RANK4(key, kk[4 * j], kk[4 * j + 1], kk[4 * j + 2], kk[4 * j + 3], r0, r1, r2, r3);
+                } else {
+#pragma unroll
+                    for (int u = 4 * j; u < NC; ++u) r0 += (kk[u] > key) ? 1 : 0;
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            rank = (r0 + r1) + (r2 + r3);
         } else {
             // four independent compare-and-count chains (device_utils.h)
             int r0, r1, r2, r3;
@@ -124,8 +173,9 @@
                 if (SES) {
                     ses_st = f_empty ? FCD_ST_RAN_OUT_OF_BEAM : FCD_ST_INCOMPARABLE;
                 } else if (q == 0) {
-                    p.out.status[r] = f_empty ? FCD_ST_RAN_OUT_OF_BEAM : FCD_ST_INCOMPARABLE;
-                    if (!NB) p.out.out_len[r] = 0;  // (n-best rows: the epilogue)
+                    const int64_t rr = read_index_again();
+                    p.out.status[rr] = f_empty ? FCD_ST_RAN_OUT_OF_BEAM : FCD_ST_INCOMPARABLE;
+                    if (!NB) p.out.out_len[rr] = 0;  // (n-best rows: the epilogue)
                 }
                 alive = false;
                 if (UNI) n_valid = 0;  // the failed read keeps an empty beam from here on
@@ -192,13 +242,13 @@
         // the table's LDS round trip instead of under it (r06: +2.4 % of the kernel when they moved ahead of it in r04,
         // found by bisection on one box -- profiles/r06b_headline_bisect.txt).
         const int tipfc = is_self ? tipf : (k << 2);
-        const int statec = (CRF && !is_self) ? (GATHER ? ((state * NL) & s_mask) + l : (state * NL) % (S > 0 ? S : 1) + l)
+        int statec = (CRF && !is_self) ? (GATHER ? ((state * NL) & s_mask) + l : (state * NL) % (S > 0 ? S : 1) + l)
                                              : state;  // :97
-        const int jumpc = is_self ? jump : ((depth % kSeg == 0) ? node : jump);
+        int jumpc = is_self ? jump : ((depth % kSeg == 0) ? node : jump);
         // 0 self, 1 a child entering the beam for the first time, 2 a child that has been there before (EVER:
         // its row is in HBM); read off the entry BEFORE it is marked below
         const int kind = is_child ? 1 + ((child_in >> 30) & 1) : 0;
-        const int meta = kind | tipfc | (depc << 5);
+        int meta = kind | tipfc | (depc << 5);
         auto settle_gather = [&]() __attribute__((always_inline)) {
             {
                 // a child entry whose node is a beam entry follows it to its new slot (or learns it left);
@@ -258,8 +308,17 @@
                 if (m_tied != 0ull) {
                     const bool mine = RPW == 1 ? true : (hbase ? (m_tied >> 32) != 0ull : (uint32_t)m_tied != 0u);
                     __builtin_amdgcn_s_setprio(3);  // (a straggler in the making keeps the issue priority: see beam_lane.hip)
-                    uint64_t *list = s_list[wave] + hbase;
-                    int *newrank = s_heads[wave];  // (free until the traceback)
+                    // (the lane and wavefront numbers as the rare block sees them: opaque copies, so that the dozen LDS
+                    // addresses and lane masks the quicksort derives from them are formed HERE -- hoisted out of the time
+                    // loop they were carried through it, and at five wavefronts per SIMD spilled)
+                    int lane_r = lane, wave_r = wave;
+                    if (PARK) {
+                        FCD_OPAQUE_V(lane_r);
+                        FCD_OPAQUE_V(wave_r);
+                    }
+                    const int q_r = lane_r & (HALF - 1), hbase_r = lane_r - q_r;
+                    uint64_t *list = s_list[wave_r] + hbase_r;
+                    int *newrank = s_heads[wave_r];  // (free until the traceback)
                     // the list sort_unstable_by is handed: the merged candidates in ascending node order (:245-260)
                     int pos = 0;
                     if (RPW == 1) {
@@ -275,7 +334,7 @@
                     for (int ii = 0; ii < BCAP; ++ii) {  // a beam slot's N keys per trip: their loads travel together
                         uint64_t ku[N];
 #pragma unroll
-                        for (int c = 0; c < N; ++c) ku[c] = keys[hbase + ii * GW + c];
+                        for (int c = 0; c < N; ++c) ku[c] = s_keys[wave_r][hbase_r + ii * GW + c];
 #pragma unroll
                         for (int c = 0; c < N; ++c)
                             pos += (ku[c] != 0ull && (uint32_t)ku[c] > (uint32_t)key) ? 1 : 0;  // low word: larger = smaller node
@@ -296,27 +355,81 @@
                         const int back = perm(lane < n_list ? (int)rt : 63, lane);
                         if (cand) rank = back;
                     } else {
-                    if (mine && key != 0ull) list[pos] = (key & 0xFFFFFFFF00000000ull) | (uint32_t)lane;
+                    if (mine && key != 0ull) list[pos] = (key & 0xFFFFFFFF00000000ull) | (uint32_t)lane_r;
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                     __builtin_amdgcn_wave_barrier();
                     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
                     // two reads per wavefront: the whole wavefront replays the quicksort on a flagged half's list, one half
                     // after the other (pdq178_wave.h; both halves flagged in the same step is rarer still)
+                    // The quicksort is inlined and must not set the register budget of the whole kernel: what it does not
+                    // touch -- the row FIFO, the prefetched row values and what the candidates hand to their new slots --
+                    // waits in LDS meanwhile (as in beam_lane.hip).
+                    int *const park = s_park[PARK ? wave_r : 0] + lane_r;
+                    if (PARK) {
+#pragma unroll
+                        for (int j = 0; j < kFifo; ++j) park[64 * j] = __float_as_int(win[j]);
+                        park[64 * kFifo] = __float_as_int(incoming);
+                        park[64 * (kFifo + 1)] = __float_as_int(pk_next);
+                        park[64 * (kFifo + 2)] = __float_as_int(ptip_next);
+                        park[64 * (kFifo + 3)] = __float_as_int(clp);
+                        park[64 * (kFifo + 4)] = __float_as_int(cgp);
+                        park[64 * (kFifo + 5)] = meta;
+                        park[64 * (kFifo + 6)] = jumpc;
+                        park[64 * (kFifo + 7)] = id;
+                        park[64 * (kFifo + 8)] = child_in;
+                        park[64 * (kFifo + 9)] = statec;
+                        park[64 * (kFifo + 10)] = __float_as_int(prob);
+                        park[64 * (kFifo + 11)] = node;
+                        park[64 * (kFifo + 12)] = depth;
+                        park[64 * (kFifo + 13)] = tipf;
+                        park[64 * (kFifo + 14)] = state;
+                        park[64 * (kFifo + 15)] = (int)(uint32_t)key;
+                        park[64 * (kFifo + 16)] = (int)(uint32_t)(key >> 32);
+                        park[64 * (kFifo + 17)] = rank;
+                    }
 #pragma unroll 1
                     for (int hs = 0; hs < RPW; ++hs) {
                         const bool flagged = (hs ? (m_tied >> 32) != 0ull : (uint32_t)m_tied != 0u);
                         if (!flagged) continue;
                         const int len_h = __builtin_amdgcn_readlane(n_valid, hs * HALF);
-                        pdq178::wave_sort_inline<1>(s_list[wave] + hs * HALF, len_h, beam_size, &s_ws[wave], lane);
+                        pdq178::wave_sort_inline<1>(s_list[wave_r] + hs * HALF, len_h, beam_size, &s_ws[wave_r], lane_r);
+                    }
+                    if (PARK) {
+#pragma unroll
+                        for (int j = 0; j < kFifo; ++j) win[j] = __int_as_float(park[64 * j]);
+                        incoming = __int_as_float(park[64 * kFifo]);
+                        pk_next = __int_as_float(park[64 * (kFifo + 1)]);
+                        ptip_next = __int_as_float(park[64 * (kFifo + 2)]);
+                        clp = __int_as_float(park[64 * (kFifo + 3)]);
+                        cgp = __int_as_float(park[64 * (kFifo + 4)]);
+                        meta = park[64 * (kFifo + 5)];
+                        jumpc = park[64 * (kFifo + 6)];
+                        id = park[64 * (kFifo + 7)];
+                        child_in = park[64 * (kFifo + 8)];
+                        statec = park[64 * (kFifo + 9)];
+                        prob = __int_as_float(park[64 * (kFifo + 10)]);
+                        node = park[64 * (kFifo + 11)];
+                        depth = park[64 * (kFifo + 12)];
+                        tipf = park[64 * (kFifo + 13)];
+                        state = park[64 * (kFifo + 14)];
+                        rank = park[64 * (kFifo + 17)];
+                        key = (uint64_t)(uint32_t)park[64 * (kFifo + 15)] | ((uint64_t)(uint32_t)park[64 * (kFifo + 16)] << 32);
                     }
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                     __builtin_amdgcn_wave_barrier();
                     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                    if (mine && q < n_valid) newrank[(int)(uint32_t)list[q]] = q;
+                    if (PARK) {  // (formed again rather than kept across the quicksort)
+                        FCD_OPAQUE_V(lane_r);
+                        FCD_OPAQUE_V(wave_r);
+                    }
+                    const int q_s = lane_r & (HALF - 1);
+                    const uint64_t *list_s = s_list[wave_r] + (lane_r - q_s);
+                    newrank = s_heads[wave_r];
+                    if (mine && q_s < n_valid) newrank[(int)(uint32_t)list_s[q_s]] = q_s;
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                     __builtin_amdgcn_wave_barrier();
                     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                    if (mine && key != 0ull) rank = newrank[lane];
+                    if (mine && key != 0ull) rank = newrank[lane_r];
                     }
                     settle_table();
                     settle_gather();
