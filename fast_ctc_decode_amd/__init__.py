@@ -37,6 +37,9 @@ from .api import (  # noqa: F401
     crf_beam_search_nbest,
     crf_beam_search_nbest_batch_raw,
     crf_greedy_search,
+    AlignResult,
+    ctc_align,
+    ctc_align_batch_raw,
     ctc_score,
     ctc_score_batch_raw,
     crf_greedy_search_batch,

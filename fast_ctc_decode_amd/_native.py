@@ -51,6 +51,7 @@ SYMBOLS = [
     "fcd_beam_session_result_dev", "fcd_beam_session_result_host", "fcd_beam_session_restart", "fcd_beam_session_steps",
     "fcd_beam_session_bytes", "fcd_beam_session_destroy",
     "fcd_ctc_score_dev", "fcd_ctc_score_host",
+    "fcd_ctc_align_dev", "fcd_ctc_align_host", "fcd_debug_set_align_workspace_cap",
 ]
 JOB_PATH, JOB_QUAL, JOB_AMBIGUOUS, JOB_DONE = 1, 2, 4, 1
 
@@ -82,6 +83,11 @@ class Labellings(C.Structure):
                 ("n_hyp", C.c_int64), ("stride", C.c_int64)]
 
 
+class Alignment(C.Structure):
+    """fcd_alignment: what fcd_ctc_align_* writes (include/fcd.h)."""
+    _fields_ = [("start", C.c_void_p), ("count", C.c_void_p), ("qual", C.c_void_p), ("logp", C.c_void_p)]
+
+
 class Chunk(C.Structure):
     _fields_ = [
         ("read_begin", C.c_int64), ("n_reads", C.c_int64), ("out_len", C.c_void_p), ("status", C.c_void_p),
@@ -91,7 +97,11 @@ class Chunk(C.Structure):
 
 
 class NativeError(RuntimeError):
-    pass
+    """code: the C ABI's return value (E_*) where the error came from a call, else None"""
+
+    def __init__(self, msg, code=None):
+        super().__init__(msg)
+        self.code = code
 
 
 _lib = None
@@ -233,6 +243,8 @@ def bind(lib):
     lib.fcd_beam_session_destroy.argtypes = [P]
     for sfx in ("dev", "host"):
         getattr(lib, "fcd_ctc_score_" + sfx).argtypes = [P, BP, C.POINTER(Labellings), i32, i64, P]
+        getattr(lib, "fcd_ctc_align_" + sfx).argtypes = [P, BP, C.POINTER(Labellings), i32, i64, C.POINTER(Alignment)]
+    lib.fcd_debug_set_align_workspace_cap.argtypes = [P, i64]
     return lib
 
 
@@ -254,7 +266,7 @@ class Handle:
     def check(self, rc):
         if rc != OK:
             msg = self.lib.fcd_last_error(self.ptr)
-            raise NativeError("libfcd_hip error %d: %s" % (rc, msg.decode() if msg else ""))
+            raise NativeError("libfcd_hip error %d: %s" % (rc, msg.decode() if msg else ""), rc)
 
     def set_stream(self, stream_ptr):
         """Launch on this hipStream_t handle; 0/None is the HIP null stream (torch's default)."""
@@ -330,6 +342,10 @@ class Handle:
         """(include/fcd_debug.h) which form of the two routines std changed in 2023 the quicksort replay follows:
         process-wide, written to this handle's device at once; 0 = Rust 1.78 as recalled (default), 3 = rustc 1.65"""
         self.check(self.lib.fcd_debug_set_pdq178_std_form(self.ptr, int(bits)))
+
+    def set_align_workspace_cap(self, nbytes):
+        """(include/fcd_debug.h) back-pointer bytes one launch of ctc_align may take; 0 = the default"""
+        self.check(self.lib.fcd_debug_set_align_workspace_cap(self.ptr, int(nbytes)))
 
     def release_workspace(self):
         """Give the tree arena / staging memory back to the device (the next call allocates afresh)."""

@@ -229,8 +229,12 @@ def viterbi_search(network_output, alphabet, qstring=False, qscale=1.0, qbias=0.
 
 
 def beam_search(network_output, alphabet, beam_size=5, beam_cut_threshold=0.0,
-                collapse_repeats=True):
-    """CTC prefix beam search.  Mirrors src/lib.rs:318-365 -> search.rs:159-301."""
+                collapse_repeats=True, *, qstring=False, qscale=1.0, qbias=0.0):
+    """CTC prefix beam search.  Mirrors src/lib.rs:318-365 -> search.rs:159-301.
+
+    qstring=True (not in the reference, whose beam search has no qualities) appends a quality string to the sequence
+    as viterbi_search does: each label's mean posterior over the rows the best alignment of the result gives it
+    (ctc_align_batch_raw; the exact lattice where it fits, a band of 64 labels around the search's path otherwise)."""
     x = _as_f32(network_output, 2, "network_output")
     alpha = _seq_to_vec(alphabet)
     _check_beam_args(len(alpha), x.shape[1], beam_size, beam_cut_threshold)
@@ -249,7 +253,16 @@ def beam_search(network_output, alphabet, beam_size=5, beam_cut_threshold=0.0,
                                            C.byref(out.res)))
     _raise_status(int(out.status[0]))
     n = int(out.out_len[0])
-    return "".join(alpha[l] for l in out.labels[0, :n]), [int(p) for p in out.path[0, :n]]
+    seq = "".join(alpha[l] for l in out.labels[0, :n])
+    if qstring and n:
+        try:
+            al = ctc_align_batch_raw(x[None], out.labels, out.out_len, collapse_repeats)
+        except nat.NativeError as e:
+            if e.code != nat.E_UNSUPPORTED:  # (refused before anything is staged: the exact lattice does not fit)
+                raise
+            al = ctc_align_batch_raw(x[None], out.labels, out.out_len, collapse_repeats, paths=out.path, band=64)
+        seq += al.qstrings(out.out_len, qscale, qbias)[0][0]
+    return seq, [int(p) for p in out.path[0, :n]]
 
 
 def crf_beam_search(network_output, init_state, alphabet, beam_size=5, beam_cut_threshold=0.0):
@@ -794,6 +807,18 @@ class BatchResult:
                                    self.path if band else None, band, None, input_dtype,
                                    getattr(self, "_handle", None))
 
+    def ctc_align(self, network_outputs, collapse_repeats=True, lengths=None, band=0, input_dtype=None):
+        """The best alignment of every read's result to its rows -> AlignResult, arrays (n_reads, 1, stride):
+        ctc_align_batch_raw on this result's own arrays (device results stay on the device).  Arguments as ctc_score.
+        CRF results are refused (transition-scored models: a different lattice)."""
+        if isinstance(self, _CrfBatchResult) or getattr(network_outputs, "ndim", 3) != 3:
+            raise ValueError("ctc_align covers the plain CTC searches, not CRF results")
+        if band and self.path is None:
+            raise ValueError("a band needs the result's path")
+        return ctc_align_batch_raw(network_outputs, self.labels, self.out_len, collapse_repeats, lengths,
+                                   self.path if band else None, band, None, input_dtype,
+                                   getattr(self, "_handle", None))
+
     def sequences(self, alphabet, raise_on_error=True, paths="list"):
         """-> list of (str, path) per read, exactly what the single-read functions return.
 
@@ -1099,6 +1124,15 @@ class NBestResult:
                                    self.path if band else None, band, self.n_hyp, input_dtype,
                                    getattr(self, "_handle", None))
 
+    def ctc_align(self, network_outputs, collapse_repeats=True, lengths=None, band=0, input_dtype=None):
+        """The best alignment of every hypothesis -> AlignResult, arrays (n_reads, n_best, stride); logp NaN and count 0
+        where i >= n_hyp[r].  ctc_align_batch_raw on this result's own arrays; CRF results are refused."""
+        if self.crf or getattr(network_outputs, "ndim", 3) != 3:
+            raise ValueError("ctc_align covers the plain CTC searches, not CRF results")
+        return ctc_align_batch_raw(network_outputs, self.labels, self.out_len, collapse_repeats, lengths,
+                                   self.path if band else None, band, self.n_hyp, input_dtype,
+                                   getattr(self, "_handle", None))
+
     def hypotheses(self, alphabet, raise_on_error=True):
         """-> per read, a list of (seq, path, score), best first (None for a failed read when not raise_on_error)."""
         r = self.cpu()
@@ -1302,19 +1336,9 @@ def _check_band(band, paths):
     return int(band)
 
 
-def ctc_score_batch_raw(network_outputs, labels, label_lengths, collapse_repeats=True, lengths=None, paths=None,
-                        band=0, n_valid=None, input_dtype=None, handle=None):
-    """CTC forward log-likelihood ln P(y | x) of labellings y against the (B,T,N) posteriors x: the sum over every
-    alignment, not the beam search's pruned estimate -- float64, comparable between reads (include/fcd.h,
-    fcd_ctc_score_*).  -> (B, n_hyp) float64.
-
-    labels (B, stride) or (B, n_hyp, stride) uint8 label indices 1 .. N-1 and label_lengths (B,) / (B, n_hyp), as the
-    searches return them (BatchResult / NBestResult: .labels, .out_len).  band=0 scores the exact lattice; band=W > 0
-    only the alignments within W labels of `paths` (same shape as labels: the row each label was emitted at) -- a
-    lower bound that rises with W, at a cost that no longer grows with the labelling's length.  n_valid (B,): rows
-    i >= n_valid[r] are not scored (NaN).  Device tensors in: a torch tensor on the same device, enqueued on torch's
-    current stream, not synchronised.  numpy in: numpy out."""
-    band = _check_band(band, paths)
+def _lattice_inputs(network_outputs, labels, label_lengths, lengths, paths, band, n_valid, input_dtype, handle):
+    """The argument handling ctc_score_batch_raw and ctc_align_batch_raw share.  -> (handle, nat.Batch, nat.Labellings,
+    (B, n_hyp, stride), device or None for numpy input, the arrays the two structs point into)."""
     dev_x = _device_tensor(network_outputs)
     if dev_x is not None:
         import torch
@@ -1348,13 +1372,10 @@ def ctc_score_batch_raw(network_outputs, labels, label_lengths, collapse_repeats
             if lengths.numel() != B:
                 raise ValueError("lengths must have shape (n_reads,)")
             b.lengths = lengths.data_ptr()
-        out = torch.empty((B, n_hyp), dtype=torch.float64, device=dev)
         y = nat.Labellings(lab.data_ptr(), ylen.data_ptr(), nv.data_ptr() if nv is not None else None,
                            pth.data_ptr() if pth is not None else None, n_hyp, stride)
         h.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-        h.check(h.lib.fcd_ctc_score_dev(h.ptr, C.byref(b), C.byref(y), int(bool(collapse_repeats)), band,
-                                        C.c_void_p(out.data_ptr())))
-        return out
+        return h, b, y, (B, n_hyp, stride), dev, (x, lab, ylen, pth, nv, lengths)
     network_outputs, lengths = _ragged(network_outputs, lengths, 3)
     x = _stack_host(network_outputs, 3)
     B, T, N = x.shape
@@ -1369,12 +1390,36 @@ def ctc_score_batch_raw(network_outputs, labels, label_lengths, collapse_repeats
     nv = np.ascontiguousarray(np.asarray(n_valid), np.uint32) if n_valid is not None else None
     if nv is not None and nv.shape != (B,):
         raise ValueError("n_valid must have shape (n_reads,)")
-    h = nat.default_handle()
+    h = nat.default_handle()  # (host arrays: the calling thread's own handle, whatever handle the search ran on)
     l = _np_lengths(lengths, B)
     b = _host_batch(x, False, l, input_dtype)
-    out = np.empty((B, n_hyp), np.float64)
     y = nat.Labellings(lab.ctypes.data, ylen.ctypes.data, nv.ctypes.data if nv is not None else None,
                        pth.ctypes.data if pth is not None else None, n_hyp, stride)
+    return h, b, y, (B, n_hyp, stride), None, (x, lab, ylen, pth, nv, l)
+
+
+def ctc_score_batch_raw(network_outputs, labels, label_lengths, collapse_repeats=True, lengths=None, paths=None,
+                        band=0, n_valid=None, input_dtype=None, handle=None):
+    """CTC forward log-likelihood ln P(y | x) of labellings y against the (B,T,N) posteriors x: the sum over every
+    alignment, not the beam search's pruned estimate -- float64, comparable between reads (include/fcd.h,
+    fcd_ctc_score_*).  -> (B, n_hyp) float64.
+
+    labels (B, stride) or (B, n_hyp, stride) uint8 label indices 1 .. N-1 and label_lengths (B,) / (B, n_hyp), as the
+    searches return them (BatchResult / NBestResult: .labels, .out_len).  band=0 scores the exact lattice; band=W > 0
+    only the alignments within W labels of `paths` (same shape as labels: the row each label was emitted at) -- a
+    lower bound that rises with W, at a cost that no longer grows with the labelling's length.  n_valid (B,): rows
+    i >= n_valid[r] are not scored (NaN).  Device tensors in: a torch tensor on the same device, enqueued on torch's
+    current stream, not synchronised.  numpy in: numpy out."""
+    band = _check_band(band, paths)
+    h, b, y, (B, n_hyp, stride), dev, keep = _lattice_inputs(network_outputs, labels, label_lengths, lengths, paths, band,
+                                                             n_valid, input_dtype, handle)
+    if dev is not None:
+        import torch
+        out = torch.empty((B, n_hyp), dtype=torch.float64, device=dev)
+        h.check(h.lib.fcd_ctc_score_dev(h.ptr, C.byref(b), C.byref(y), int(bool(collapse_repeats)), band,
+                                        C.c_void_p(out.data_ptr())))
+        return out
+    out = np.empty((B, n_hyp), np.float64)
     h.check(h.lib.fcd_ctc_score_host(h.ptr, C.byref(b), C.byref(y), int(bool(collapse_repeats)), band,
                                      out.ctypes.data))
     return out
@@ -1387,18 +1432,102 @@ def ctc_score(network_output, sequence, alphabet, collapse_repeats=True):
     x = _as_f32(network_output, 2, "network_output")
     alpha = _seq_to_vec(alphabet)
     _check_greedy_alphabet(len(alpha), x.shape[1])
-    if not isinstance(sequence, str):
-        raise TypeError("argument 'sequence': expected str")
-    if any(len(a) != 1 for a in alpha[1:]):
-        raise ValueError("ctc_score needs single-character labels")
-    index = {a: i for i, a in enumerate(alpha) if i > 0}
-    try:
-        y = [index[c] for c in sequence]
-    except KeyError as e:
-        raise ValueError("sequence holds %r, which is not a label of the alphabet" % e.args[0])
+    y = _sequence_labels(sequence, alpha, "ctc_score")
     lab = np.zeros((1, max(len(y), 1)), np.uint8)
     lab[0, :len(y)] = y
     return float(ctc_score_batch_raw(_dense(x)[None], lab, np.array([len(y)], np.uint32), collapse_repeats)[0, 0])
+
+
+# ---------------------------------------------------------------------------------------------
+# CTC forced alignment of given labellings (include/fcd.h, fcd_ctc_align_*)
+# ---------------------------------------------------------------------------------------------
+class AlignResult:
+    """Outcome of ctc_align_batch_raw: for label k of hypothesis i of read r, start[r, i, k] is the first row the best
+    alignment spends in it, count[r, i, k] how many (consecutive) rows, qual[r, i, k] the mean posterior of the label
+    over them (float32: what viterbi_search turns into its quality string); logp[r, i] (float64) is ln of the
+    alignment's probability -- NaN / -inf where there is none, and count is 0 there (include/fcd.h).  Entries
+    k >= the labelling's length are 0.  numpy for host inputs, torch tensors (same device) for device inputs."""
+
+    def __init__(self, start, count, qual, logp):
+        self.start, self.count, self.qual, self.logp = start, count, qual, logp
+
+    def cpu(self):
+        def c(a):
+            return a if isinstance(a, np.ndarray) else a.cpu().numpy()
+        start, count = c(self.start), c(self.count)
+        if start.dtype != np.uint32:  # (device results are int32 tensors: the same 32 bits)
+            start, count = start.view(np.uint32), count.view(np.uint32)
+        return AlignResult(start, count, c(self.qual), c(self.logp))
+
+    def qstrings(self, out_len, qscale=1.0, qbias=0.0):
+        """-> per read, per hypothesis, the phred quality string of its first out_len[r, i] labels (fcd_phred: the
+        reference's phred(), src/search.rs:21-36); "" for a labelling without an alignment."""
+        r = self.cpu()
+        n = np.asarray(out_len if isinstance(out_len, np.ndarray) or not hasattr(out_len, "cpu") else out_len.cpu().numpy())
+        n = n.reshape(r.logp.shape)
+        return [[_qual_chars(r.qual[b, i, :int(n[b, i])], qscale, qbias) if np.isfinite(r.logp[b, i]) else ""
+                 for i in range(r.logp.shape[1])] for b in range(r.logp.shape[0])]
+
+
+def ctc_align_batch_raw(network_outputs, labels, label_lengths, collapse_repeats=True, lengths=None, paths=None,
+                        band=0, n_valid=None, input_dtype=None, handle=None):
+    """CTC forced alignment: the best single alignment of every labelling to its read's rows -- which rows belong to each
+    label, the label's quality as viterbi_search defines it, and ln of the alignment's probability (include/fcd.h,
+    fcd_ctc_align_*).  -> AlignResult with start, count, qual (B, n_hyp, stride) and logp (B, n_hyp).
+
+    Arguments as ctc_score_batch_raw: band=0 aligns in the exact lattice, band=W > 0 within W labels of `paths`.
+    Device tensors in: torch tensors on the same device, enqueued on torch's current stream, not synchronised.
+    numpy in: numpy out."""
+    band = _check_band(band, paths)
+    h, b, y, (B, n_hyp, stride), dev, keep = _lattice_inputs(network_outputs, labels, label_lengths, lengths, paths, band,
+                                                             n_valid, input_dtype, handle)
+    if dev is not None:
+        import torch
+        start = torch.zeros((B, n_hyp, stride), dtype=torch.int32, device=dev)
+        count = torch.zeros((B, n_hyp, stride), dtype=torch.int32, device=dev)
+        qual = torch.zeros((B, n_hyp, stride), dtype=torch.float32, device=dev)
+        logp = torch.empty((B, n_hyp), dtype=torch.float64, device=dev)
+        out = nat.Alignment(start.data_ptr(), count.data_ptr(), qual.data_ptr(), logp.data_ptr())
+        h.check(h.lib.fcd_ctc_align_dev(h.ptr, C.byref(b), C.byref(y), int(bool(collapse_repeats)), band, C.byref(out)))
+        return AlignResult(start, count, qual, logp)
+    start = np.zeros((B, n_hyp, stride), np.uint32)
+    count = np.zeros((B, n_hyp, stride), np.uint32)
+    qual = np.zeros((B, n_hyp, stride), np.float32)
+    logp = np.empty((B, n_hyp), np.float64)
+    out = nat.Alignment(start.ctypes.data, count.ctypes.data, qual.ctypes.data, logp.ctypes.data)
+    h.check(h.lib.fcd_ctc_align_host(h.ptr, C.byref(b), C.byref(y), int(bool(collapse_repeats)), band, C.byref(out)))
+    return AlignResult(start, count, qual, logp)
+
+
+def _sequence_labels(sequence, alpha, what):
+    if not isinstance(sequence, str):
+        raise TypeError("argument 'sequence': expected str")
+    if any(len(a) != 1 for a in alpha[1:]):
+        raise ValueError("%s needs single-character labels" % what)
+    index = {a: i for i, a in enumerate(alpha) if i > 0}
+    try:
+        return [index[c] for c in sequence]
+    except KeyError as e:
+        raise ValueError("sequence holds %r, which is not a label of the alphabet" % e.args[0])
+
+
+def ctc_align(network_output, sequence, alphabet, collapse_repeats=True):
+    """The best alignment of one string to one (T, N) float32 posterior matrix, exact lattice: -> (spans, quals, logp)
+    with spans = [(start, count)] per character, quals = the mean posterior of each over its rows, logp = ln of the
+    alignment's probability.  No alignment (more characters than rows, ...): ([], [], -inf)."""
+    x = _as_f32(network_output, 2, "network_output")
+    alpha = _seq_to_vec(alphabet)
+    _check_greedy_alphabet(len(alpha), x.shape[1])
+    y = _sequence_labels(sequence, alpha, "ctc_align")
+    lab = np.zeros((1, max(len(y), 1)), np.uint8)
+    lab[0, :len(y)] = y
+    r = ctc_align_batch_raw(_dense(x)[None], lab, np.array([len(y)], np.uint32), collapse_repeats)
+    logp = float(r.logp[0, 0])
+    if not np.isfinite(logp):
+        return [], [], logp
+    n = len(y)
+    return ([(int(s), int(c)) for s, c in zip(r.start[0, 0, :n], r.count[0, 0, :n])],
+            [float(q) for q in r.qual[0, 0, :n]], logp)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -1569,7 +1569,9 @@ int fcd_unpack_gathered_dev(fcd_handle *h, const uint8_t *gathered, int64_t stri
 }
 
 // ---- CTC forward log-likelihood of given labellings (ctc_score.hip) ----
-static int ctc_score_check(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int64_t band, const double *logp) {
+// (shared with fcd_ctc_align_*, whose `out` is its start array: the same lattice, the same limits)
+static int ctc_score_check(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int64_t band, const void *logp,
+                           const char *null_msg = "null labels/len/logp") {
     int rc = check_batch(h, in, false);
     if (rc) return rc;
     if (in->S != 1) return fail(h, FCD_E_INVALID, "ctc_score: S must be 1 (CRF models are not scored)");
@@ -1578,7 +1580,7 @@ static int ctc_score_check(fcd_handle *h, const fcd_batch *in, const fcd_labelli
     if (band < 0) return fail(h, FCD_E_INVALID, "band must be >= 0");
     if (band > 0 && !y->path) return fail(h, FCD_E_INVALID, "a band needs the labellings' path");
     if (y->stride < 0) return fail(h, FCD_E_INVALID, "negative stride");
-    if (in->n_reads > 0 && (!y->labels || !y->len || !logp)) return fail(h, FCD_E_INVALID, "null labels/len/logp");
+    if (in->n_reads > 0 && (!y->labels || !y->len || !logp)) return fail(h, FCD_E_INVALID, null_msg);
     if (in->n_reads * y->n_hyp >= (1ll << 31)) return fail(h, FCD_E_UNSUPPORTED, "more than 2^31 labellings in one call");
     if (!ctc_score_supported(in->T, y->stride, band))
         return fail(h, FCD_E_UNSUPPORTED, band > 0 ? "ctc_score: the band's window does not fit the 160 KiB of LDS: use a narrower band"
@@ -1648,6 +1650,125 @@ int fcd_ctc_score_host(fcd_handle *h, const fcd_batch *in, const fcd_labellings 
     rc = fcd_ctc_score_dev(h, &din, &dy, collapse_repeats, band, reinterpret_cast<double *>(d + o_out));
     if (rc) return rc;
     FCD_HIP(h, hipMemcpyAsync(logp, d + o_out, n_rows * 8, hipMemcpyDeviceToHost, h->stream));
+    FCD_HIP(h, hipStreamSynchronize(h->stream));
+    return FCD_OK;
+}
+
+// ---- CTC forced alignment of given labellings (ctc_align.hip) ----
+static int ctc_align_check(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int64_t band, const fcd_alignment *out) {
+    if (!h) return FCD_E_INVALID;
+    if (!out) return fail(h, FCD_E_INVALID, "null alignment");
+    int rc = ctc_score_check(h, in, y, band, out->start, "null labels/len/start");
+    if (rc) return rc;
+    if (in->n_reads > 0 && !out->count) return fail(h, FCD_E_INVALID, "null count");
+    return FCD_OK;
+}
+
+int fcd_debug_set_align_workspace_cap(fcd_handle *h, int64_t bytes) {
+    if (!h || bytes < 0) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> g(h->mu);
+    h->align_ws_cap = bytes;
+    return FCD_OK;
+}
+
+int fcd_ctc_align_dev(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int collapse_repeats, int64_t band,
+                      const fcd_alignment *out) {
+    if (!h) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> g(h->mu);
+    int rc = ctc_align_check(h, in, y, band, out);
+    if (rc) return rc;
+    if (in->n_reads == 0) return FCD_OK;
+    FCD_DEVICE(h);
+    const size_t n_rows = (size_t)in->n_reads * (size_t)y->n_hyp, cells = n_rows * (size_t)y->stride;
+    // the back-pointers: whole reads per launch, as many as the cap holds (at least one), every launch in the same memory
+    const size_t row_bytes = ctc_align_row_bytes(in->T, y->stride, band);
+    const int64_t cap = h->align_ws_cap > 0 ? h->align_ws_cap : std::min<int64_t>(4ll << 30, workspace_budget(h));
+    const int64_t read_bytes = (int64_t)(row_bytes * (size_t)y->n_hyp);
+    const int64_t group = std::max<int64_t>(1, std::min<int64_t>(in->n_reads, cap / read_bytes));
+    const size_t o_logp = (size_t)group * (size_t)read_bytes;
+    CallScope sc(h);
+    sc.add(y->labels, cells);
+    sc.add(y->len, n_rows * 4);
+    sc.add(y->n_valid, (size_t)in->n_reads * 4);
+    sc.add(y->path, cells * 4);
+    sc.add(out->start, cells * 4);
+    sc.add(out->count, cells * 4);
+    sc.add(out->qual, cells * 4);
+    sc.add(out->logp, n_rows * 8);
+    rc = sc.begin(false, true);  // (exclusive: the workspace from its start, behind every overlapping call in flight)
+    if (rc) return rc;
+    char *ws = nullptr;
+    rc = sc.arena(o_logp + (out->logp ? 0 : n_rows * 8), &ws);
+    if (rc) return rc;
+    double *logp = out->logp ? out->logp : reinterpret_cast<double *>(ws + o_logp);
+    const int64_t esz = in->dtype == FCD_DTYPE_F32 ? 4 : 2;
+    sc.time();
+    for (int64_t r0 = 0; r0 < in->n_reads; r0 += group) {
+        const int64_t row0 = r0 * y->n_hyp;
+        BatchDesc d = to_desc(in, false);
+        d.post = reinterpret_cast<const float *>(reinterpret_cast<const char *>(in->post) + r0 * in->stride_read * esz);
+        d.lengths = in->lengths ? in->lengths + r0 : nullptr;
+        d.n_reads = std::min(group, in->n_reads - r0);
+        const ScoreDesc yd{y->labels + row0 * y->stride, y->len + row0, y->n_valid ? y->n_valid + r0 : nullptr,
+                           band > 0 ? y->path + row0 * y->stride : nullptr, y->n_hyp, y->stride};
+        const AlignOut od{out->start + row0 * y->stride, out->count + row0 * y->stride,
+                          out->qual ? out->qual + row0 * y->stride : nullptr, logp + row0};
+        FCD_HIP(h, launch_ctc_align(d, yd, collapse_repeats != 0, std::min<int64_t>(band, 1ll << 28), od,
+                                    reinterpret_cast<unsigned char *>(ws), sc.stream));
+    }
+    return sc.finish();
+}
+
+int fcd_ctc_align_host(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int collapse_repeats, int64_t band,
+                       const fcd_alignment *out) {
+    if (!h) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> whole_call(h->mu);  // staging .. copy-back, see run_host
+    int rc = ctc_align_check(h, in, y, band, out);
+    if (rc) return rc;
+    if (in->n_reads == 0) return FCD_OK;
+    if (in->stride_read < 0 || in->stride_t < 0 || in->stride_n < 0) return fail(h, FCD_E_INVALID, "negative stride");
+    FCD_DEVICE(h);
+    const size_t B = (size_t)in->n_reads, n_rows = B * (size_t)y->n_hyp, esz = in->dtype == FCD_DTYPE_F32 ? 4 : 2;
+    const size_t cells = n_rows * (size_t)y->stride;
+    const size_t span = in->T > 0 ? (size_t)((in->n_reads - 1) * in->stride_read + (in->T - 1) * in->stride_t +
+                                             (in->N - 1) * in->stride_n + 1) : 0;
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t o_in = 0, o_len = o_in + al(span * esz), o_lab = o_len + al(B * 8);
+    const size_t o_ylen = o_lab + al(cells), o_nv = o_ylen + al(n_rows * 4);
+    const size_t o_path = o_nv + al(B * 4), o_start = o_path + (band > 0 ? al(cells * 4) : 0);
+    const size_t o_count = o_start + al(cells * 4), o_qual = o_count + al(cells * 4), o_out = o_qual + al(cells * 4);
+    const size_t total = o_out + al(n_rows * 8);
+    rc = ensure(h, &h->stage, &h->stage_bytes, total);
+    if (rc) return rc;
+    char *d = reinterpret_cast<char *>(h->stage);
+    if (span) FCD_HIP(h, hipMemcpyAsync(d + o_in, in->post, span * esz, hipMemcpyHostToDevice, h->stream));
+    if (in->lengths) FCD_HIP(h, hipMemcpyAsync(d + o_len, in->lengths, B * 8, hipMemcpyHostToDevice, h->stream));
+    if (y->stride) FCD_HIP(h, hipMemcpyAsync(d + o_lab, y->labels, cells, hipMemcpyHostToDevice, h->stream));
+    FCD_HIP(h, hipMemcpyAsync(d + o_ylen, y->len, n_rows * 4, hipMemcpyHostToDevice, h->stream));
+    if (y->n_valid) FCD_HIP(h, hipMemcpyAsync(d + o_nv, y->n_valid, B * 4, hipMemcpyHostToDevice, h->stream));
+    if (band > 0 && y->stride)
+        FCD_HIP(h, hipMemcpyAsync(d + o_path, y->path, cells * 4, hipMemcpyHostToDevice, h->stream));
+    // (entries the kernel does not write -- k >= len -- come back as 0)
+    FCD_HIP(h, hipMemsetAsync(d + o_start, 0, o_out - o_start, h->stream));
+    fcd_batch din = *in;
+    din.post = d + o_in;
+    din.lengths = in->lengths ? reinterpret_cast<const int64_t *>(d + o_len) : nullptr;
+    fcd_labellings dy = *y;
+    dy.labels = reinterpret_cast<const uint8_t *>(d + o_lab);
+    dy.len = reinterpret_cast<const uint32_t *>(d + o_ylen);
+    dy.n_valid = y->n_valid ? reinterpret_cast<const uint32_t *>(d + o_nv) : nullptr;
+    dy.path = band > 0 ? reinterpret_cast<const uint32_t *>(d + o_path) : nullptr;
+    const fcd_alignment dout{reinterpret_cast<uint32_t *>(d + o_start), reinterpret_cast<uint32_t *>(d + o_count),
+                             out->qual ? reinterpret_cast<float *>(d + o_qual) : nullptr,
+                             out->logp ? reinterpret_cast<double *>(d + o_out) : nullptr};
+    rc = fcd_ctc_align_dev(h, &din, &dy, collapse_repeats, band, &dout);
+    if (rc) return rc;
+    if (cells) {
+        FCD_HIP(h, hipMemcpyAsync(out->start, d + o_start, cells * 4, hipMemcpyDeviceToHost, h->stream));
+        FCD_HIP(h, hipMemcpyAsync(out->count, d + o_count, cells * 4, hipMemcpyDeviceToHost, h->stream));
+        if (out->qual) FCD_HIP(h, hipMemcpyAsync(out->qual, d + o_qual, cells * 4, hipMemcpyDeviceToHost, h->stream));
+    }
+    if (out->logp) FCD_HIP(h, hipMemcpyAsync(out->logp, d + o_out, n_rows * 8, hipMemcpyDeviceToHost, h->stream));
     FCD_HIP(h, hipStreamSynchronize(h->stream));
     return FCD_OK;
 }

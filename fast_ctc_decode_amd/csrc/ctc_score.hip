@@ -25,171 +25,10 @@
 
 #include <algorithm>
 
-#include "device_utils.h"
-#include "fcd_internal.h"
+#include "ctc_lattice.h"
 
 namespace fcd {
 namespace {
-
-constexpr int kTarget = 120;          // the row maximum is kept in [2^119, 2^120): three of them sum below 2^127
-constexpr int kNoExp = -(1 << 24);    // "exponent" of a cell that takes no part in the row maximum (0, inf, NaN)
-constexpr int kTileElems = 1024;      // posteriors staged per tile
-constexpr int kTileRows = 64;         // ... at most this many rows (one lane per row finds k(t))
-constexpr int kLdsCells = 20;         // LDS kernel: cells per work-item and step
-constexpr int kMiscWords = 32;        // [0..15] per-wave maxima, [16] bad-label flag, [18] [19] the two final cells
-
-struct ScoreParams {
-    BatchDesc in;
-    ScoreDesc y;
-    int collapse;
-    int band;
-    double *logp;
-    int cap;      // LDS kernel: states per alpha buffer
-    int lab_cap;  // labels the LDS copy of a labelling holds
-};
-
-struct Lds {
-    float *pm;
-    int *pe;
-    int *krow;
-    int *misc;
-    uint16_t *lab;
-    float *alpha;
-};
-
-__device__ __forceinline__ Lds carve(unsigned char *smem, int lab_cap) {
-    Lds l;
-    l.pm = reinterpret_cast<float *>(smem);
-    l.pe = reinterpret_cast<int *>(smem + kTileElems * 4);
-    l.krow = reinterpret_cast<int *>(smem + kTileElems * 8);
-    l.misc = l.krow + kTileRows;
-    l.lab = reinterpret_cast<uint16_t *>(l.misc + kMiscWords);
-    l.alpha = reinterpret_cast<float *>(reinterpret_cast<unsigned char *>(l.lab) + (((size_t)lab_cap * 2 + 15) & ~(size_t)15));
-    return l;
-}
-
-size_t lds_bytes(int lab_cap, int cap) {
-    return (size_t)kTileElems * 8 + (kTileRows + kMiscWords) * 4 + (((size_t)lab_cap * 2 + 15) & ~(size_t)15) + (size_t)cap * 8;
-}
-
-// what one row of the lattice needs to know about itself
-struct Row {
-    const float *post;  // the read's first element
-    const uint8_t *labels;
-    const uint32_t *path;
-    int Tr, L, N, rows_per_tile;
-};
-
-// Everything before the time loop.  Returns false when the row's result is already written (every work-item agrees).
-__device__ __forceinline__ bool prologue(const ScoreParams &p, const Lds &lds, Row *rw) {
-    const int tid = threadIdx.x, bd = blockDim.x;
-    const int64_t row = blockIdx.x;
-    const int64_t read = row / p.y.n_hyp;
-    const int64_t hyp = row - read * p.y.n_hyp;
-    const double nan = (double)NAN;
-    if (p.y.n_valid && hyp >= (int64_t)p.y.n_valid[read]) {  // not a hypothesis of this read
-        if (tid == 0) p.logp[row] = nan;
-        return false;
-    }
-    int64_t Tr = p.in.lengths ? p.in.lengths[read] : p.in.T;
-    Tr = Tr < 0 ? 0 : (Tr > p.in.T ? p.in.T : Tr);
-    const uint32_t len = p.y.len[row];
-    if ((int64_t)len > p.y.stride) {  // longer than its row: not a labelling
-        if (tid == 0) p.logp[row] = nan;
-        return false;
-    }
-    const int L = (int)len;
-    const uint8_t *labels = p.y.labels + row * p.y.stride;
-    if (tid == 0) lds.misc[16] = 0;
-    __syncthreads();
-    bool bad = false;
-    for (int k = tid; k < L; k += bd) {
-        const int y = labels[k], yp = k ? labels[k - 1] : 0;
-        bad |= y < 1 || y >= p.in.N;
-        if (k < p.lab_cap) lds.lab[k] = (uint16_t)(y | ((k > 0 && y != yp) ? 0x100 : 0));
-    }
-    if (bad) lds.misc[16] = 1;
-    __syncthreads();
-    double early = 0.0;
-    bool done = true;
-    if (lds.misc[16]) early = nan;                             // a label outside 1 .. N-1
-    else if (Tr == 0) early = L == 0 ? 0.0 : -(double)INFINITY;
-    else if ((int64_t)L > Tr) early = -(double)INFINITY;      // more labels than rows: no alignment
-    else done = false;
-    if (done) {
-        if (tid == 0) p.logp[row] = early;
-        return false;
-    }
-    rw->post = post_at(p.in.post, read * p.in.stride_read, p.in.dtype);
-    rw->labels = labels;
-    rw->path = p.y.path ? p.y.path + row * p.y.stride : nullptr;
-    rw->Tr = (int)Tr;
-    rw->L = L;
-    rw->N = p.in.N;
-    rw->rows_per_tile = min(kTileRows, kTileElems / p.in.N);
-    return true;
-}
-
-// rows t0 .. t0 + rc of the read into the tile, split into mantissa and exponent; banded: k(t) of each of them
-__device__ __forceinline__ void fill_tile(const ScoreParams &p, const Lds &lds, const Row &rw, int t0, int rc) {
-    const int tid = threadIdx.x, bd = blockDim.x;
-    __syncthreads();  // the previous tile's readers are done
-    for (int e = tid; e < rc * rw.N; e += bd) {
-        const int i = e / rw.N, j = e - i * rw.N;
-        const float v = load_post(rw.post, (int64_t)(t0 + i) * p.in.stride_t + (int64_t)j * p.in.stride_n, p.in.dtype);
-        int ex = 0;
-        float m = v;
-        if (v - v == 0.0f) m = frexpf(v, &ex);  // (finite; an infinity or a NaN stays what it is, exponent 0)
-        lds.pm[e] = m;
-        lds.pe[e] = ex;
-    }
-    if (p.band > 0 && tid < rc) {  // k(t) = #{k : path[k] <= t}
-        const uint32_t t = (uint32_t)(t0 + tid);
-        int lo = 0, hi = rw.L;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (rw.path[mid] <= t) lo = mid + 1;
-            else hi = mid;
-        }
-        lds.krow[tid] = lo;
-    }
-    __syncthreads();
-}
-
-// live states of row t: the band around the path, cut to what can be reached and can still reach the end
-__device__ __forceinline__ void window(const ScoreParams &p, const Lds &lds, const Row &rw, int t, int i, int *lo, int *hi) {
-    int l = 0, h = 2 * rw.L;
-    if (p.band > 0) {
-        const int k = lds.krow[i];
-        l = max(0, 2 * (k - p.band) - 2);
-        h = min(h, 2 * (k + p.band));
-    }
-    *hi = min(h, 2 * t + 1);
-    *lo = max(l, 2 * rw.L - 2 * (rw.Tr - 1 - t) - 2);
-}
-
-__device__ __forceinline__ int finite_exp(float u) {  // exponent of a positive finite value, kNoExp for anything else
-    int e;
-    (void)frexpf(u, &e);
-    return (u > 0.0f && u - u == 0.0f) ? e : kNoExp;
-}
-
-__device__ __forceinline__ int wave_imax(int x) {
-    int t = x;
-#define FCD_DPP_IMAX(CTRL, RM) t = max(t, __builtin_amdgcn_update_dpp(t, t, CTRL, RM, 0xf, false));
-    FCD_DPP_IMAX(0x111, 0xf)  // row_shr:1
-    FCD_DPP_IMAX(0x112, 0xf)  // row_shr:2
-    FCD_DPP_IMAX(0x114, 0xf)  // row_shr:4
-    FCD_DPP_IMAX(0x118, 0xf)  // row_shr:8   -> lane 15 of every row holds the row's maximum
-    FCD_DPP_IMAX(0x142, 0xa)  // row_bcast:15 into rows 1 and 3
-    FCD_DPP_IMAX(0x143, 0xc)  // row_bcast:31 into rows 2 and 3 -> lane 63 holds the maximum
-#undef FCD_DPP_IMAX
-    return __builtin_amdgcn_readlane(t, 63);
-}
-
-__device__ __forceinline__ float from_prev_lane(float x) {  // wave_ror:1 -- lane l receives lane (l - 1) & 63
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x13C, 0xf, 0xf, false));
-}
 
 __device__ __forceinline__ void write_result(const ScoreParams &p, float c0, float c1, int64_t eacc) {
     const double m = (double)c0 + (double)c1;
@@ -197,49 +36,6 @@ __device__ __forceinline__ void write_result(const ScoreParams &p, float c0, flo
 }
 
 // ---- the register-resident window ----
-// What a lane needs for one row: read from LDS a row ahead of its use (nothing here depends on alpha).
-template <int K>
-struct StepIn {
-    float pm0, pm[K / 2];
-    int pe0, pe[K / 2];
-    uint32_t in_mask;    // bit r: the lane's state r lies in the row's window
-    uint32_t skip_mask;  // bit r (odd r): the s-2 term enters
-    int lo, hi;
-};
-
-template <int K>
-__device__ __forceinline__ int slot_state(int lane, int r, int lo) {  // the state >= lo that lives in slot lane * K + r
-    constexpr int C = 64 * K;
-    const int s = lo / C * C + lane * K + r;
-    return s < lo ? s + C : s;
-}
-
-template <int K>
-__device__ __forceinline__ StepIn<K> load_step(const ScoreParams &p, const Lds &lds, const Row &rw, int t, int i) {
-    StepIn<K> in;
-    const int lane = threadIdx.x;
-    window(p, lds, rw, t, i, &in.lo, &in.hi);
-    in.pm0 = lds.pm[i * rw.N];
-    in.pe0 = lds.pe[i * rw.N];
-    in.in_mask = 0;
-    in.skip_mask = 0;
-#pragma unroll
-    for (int r = 0; r < K; ++r) {
-        const int s = slot_state<K>(lane, r, in.lo);
-        const bool live = s <= in.hi;
-        in.in_mask |= (live ? 1u : 0u) << r;
-        if (r & 1) {
-            const int info = lds.lab[live ? (s >> 1) : 0];  // (a dead slot reads a valid address and is masked below)
-            const int y = live ? (info & 0xFF) : 0;
-            in.pm[r / 2] = lds.pm[i * rw.N + y];
-            in.pe[r / 2] = lds.pe[i * rw.N + y];
-            const bool skip = live && s >= 3 && (!p.collapse || (info & 0x100));
-            in.skip_mask |= (skip ? 1u : 0u) << r;
-        }
-    }
-    return in;
-}
-
 template <int K>
 __global__ __launch_bounds__(64) void score_reg_kernel(ScoreParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];

@@ -239,6 +239,17 @@ int64_t ctc_score_window_states(int64_t T, int64_t stride, int64_t band);
 bool ctc_score_supported(int64_t T, int64_t stride, int64_t band);
 hipError_t launch_ctc_score(const BatchDesc &in, const ScoreDesc &y, int collapse, int64_t band, double *logp,
                             hipStream_t stream);
+// CTC forced alignment of given labellings (ctc_align.hip; fcd_alignment in include/fcd.h): what ctc_score supports.
+// bp: ctc_align_row_bytes() of device memory per labelling of the launch (the back-pointers); logp must not be null.
+struct AlignOut {
+    uint32_t *start;
+    uint32_t *count;
+    float *qual;  // nullable
+    double *logp;
+};
+size_t ctc_align_row_bytes(int64_t T, int64_t stride, int64_t band);
+hipError_t launch_ctc_align(const BatchDesc &in, const ScoreDesc &y, int collapse, int64_t band, const AlignOut &out,
+                            unsigned char *bp, hipStream_t stream);
 
 hipError_t launch_logspace_probe(const float *a, const float *b, float *out_add, float *out_ln,
                                  int64_t n, int mode, hipStream_t stream);
@@ -361,6 +372,7 @@ struct fcd_handle {
     std::vector<fcd_host_lane *> lanes;
     bool job_active = false;  // a host job owns the lanes from begin to end
     int live_sessions = 0;    // fcd_beam_session_create .. _destroy
+    int64_t align_ws_cap = 0; // fcd_debug_set_align_workspace_cap: back-pointer bytes one launch of fcd_ctc_align_* may take, 0 = default
     bool is_lane = false;
     uint32_t *duplex_prof = nullptr;  // fcd_debug_set_duplex_profile
     int duplex_kernel = 0;            // fcd_debug_set_duplex_kernel: 0 automatic, 1 the any-shape kernel (duplex.hip), 2 the slot-resident one

@@ -386,6 +386,46 @@ int fcd_ctc_score_dev(fcd_handle *h, const fcd_batch *in, const fcd_labellings *
 int fcd_ctc_score_host(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int collapse_repeats, int64_t band,
                        double *logp);
 
+/* ---- CTC forced alignment of given labellings (csrc/ctc_align.hip) ----
+ * NOT a reference function.  The BEST single alignment through the lattice fcd_ctc_score_* sums over -- same extended
+ * sequence z, same transitions under collapse_repeats, same live window under `band`: the state sequence s_0 .. s_{T_r-1}
+ * (s_0 in {0, 1}, s_t - s_{t-1} in {0, 1, 2}, 2 only where the score's s-2 term enters, 0 never on a label when
+ * collapse_repeats = 0) that maximises prod_t p[t][z[s_t]] and ends in state 2L or 2L - 1.  It gives every label its rows,
+ * and from them a quality defined as search::viterbi_search defines its own (src/search.rs:337-376): a beam result plus
+ * this call is a FASTQ record.  Aligning viterbi_search's own labelling returns its path and its qualities bit for bit.
+ * Arithmetic: f32 with an unbounded exponent; a cell is max(candidates) * p, ONE f32 rounding; rows are rescaled by powers
+ * of two only (exact); a cell below 2^-160 of its row's maximum may be dropped.
+ * Ties: candidates are taken in the order stay (s), s-1, s-2, and a later one replaces an earlier one only if it is
+ * strictly greater; at the end state 2L is taken unless 2L - 1 is strictly greater.
+ * Per labelling row (row = r * n_hyp + i), label k < len:
+ *   start[row * stride + k]  the first row spent in state 2k + 1
+ *   count[row * stride + k]  the rows spent in it (consecutive; exactly 1 when collapse_repeats = 0)
+ *   qual [row * stride + k]  (p[start][y_k] + ... + p[start + count - 1][y_k]) / (float)count, summed in f32 in ascending row
+ *                            order, no fused multiply-add: viterbi_search's label_prob_total / label_prob_count.  Nullable.
+ *   logp [row]               ln of the alignment's probability, ln(m) + E ln 2 in float64.  Nullable.
+ * Rows without an alignment, tested in this order: i >= n_valid[r], len > stride, a label outside 1 .. N-1: logp = NaN;
+ * T_r = 0 < L or L > T_r: logp = -inf; a NaN, infinite or negative posterior ANYWHERE in the read's first T_r rows (found
+ * while the rows are staged; a comparison-based search has no sensible order for them): logp = NaN; no alignment inside
+ * the window or repeats that need more rows than there are: logp = -inf.  In all of them count = 0 for every
+ * k < min(len, stride) and start / qual are left alone.  L = 0: logp = sum_t ln p[t][0], nothing else is written.
+ * Entries k >= len are never written by _dev; _host returns them as 0.
+ * band: as fcd_ctc_score_*; the best alignment among those that stay inside the window, so logp rises with W.
+ * Shapes, limits, in->S, in->lengths, stream order and the FCD_E_INVALID / FCD_E_UNSUPPORTED cases are fcd_ctc_score_*'s;
+ * start and count must not be null.  _dev is enqueue-only on the handle's stream, behind every overlapping search in
+ * flight (fcd_set_overlap).  Its back-pointers (2 bits per row and slot for windows up to 510 states: 64 or 128 bytes a
+ * row; a byte per row and state beyond) live in the handle's workspace: the labellings are launched in groups of whole
+ * reads that fit 4 GiB of it, one after the other on the stream, no host wait in between. */
+typedef struct fcd_alignment {
+    uint32_t *start;  /* [n_reads * n_hyp * stride] */
+    uint32_t *count;  /* [n_reads * n_hyp * stride] */
+    float    *qual;   /* [n_reads * n_hyp * stride], nullable */
+    double   *logp;   /* [n_reads * n_hyp], nullable */
+} fcd_alignment;
+int fcd_ctc_align_dev(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int collapse_repeats, int64_t band,
+                      const fcd_alignment *out);
+int fcd_ctc_align_host(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int collapse_repeats, int64_t band,
+                       const fcd_alignment *out);
+
 /* ---- search::crf_greedy_search (src/search.rs:385-423) ---- */
 int fcd_crf_greedy_search_dev(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init,
                               int64_t init_stride, const fcd_result *out);

@@ -46,6 +46,10 @@ int fcd_debug_pdq178_coop_profile(fcd_handle *h, uint64_t cycles[16], int reset)
  * quarter of the reads overflow switches the handle to worst-case slabs for later jobs.  A larger divisor makes
  * the retry path run on small inputs (tests) and pins it; 0 restores the adaptive default. */
 int fcd_debug_set_first_pass_divisor(fcd_handle *h, int divisor);
+/* Test hook: the back-pointer bytes one launch of fcd_ctc_align_* may take from the workspace (default 4 GiB; 0 restores
+ * it).  The labellings of a call are launched in groups of whole reads that fit, at least one read a group: a tiny cap
+ * makes a tiny batch run as several groups.  Results do not depend on it. */
+int fcd_debug_set_align_workspace_cap(fcd_handle *h, int64_t bytes);
 /* Developer instrument: while `cycles` (DEVICE array [n_pairs][16] u32, indexed by the pair's position in the batch)
  * is set, the duplex searches on this handle record a cycle account per pair: shader cycles / 64 spent in
  * [0] envelope + forward-vector extension, [1] LDS tiles, [2] expansion without the window builds, [3] window
