@@ -30,7 +30,8 @@
 //   * survivors publish (lane, depth) by rank in a small LDS table: one round trip later every lane knows
 //     its source lane, where the best candidate sits and the minimum depth of the new beam; the survivors are
 //     gathered into rank order with ds_bpermute and divided by the top probability (:278-282, IEEE f32
-//     division: one per lane, the two quotients shared inside each group).
+//     division: one per lane, the two quotients shared inside each group; two reads per wavefront: divided on the
+//     source lanes BEFORE the gather, DSRC below, so that the quotients are what is gathered).
 //
 // Node ids are (time step << KS) | index among the nodes created in that step: creation order, as the reference's
 // tie-break needs, with the creation time -- what `path` reports -- readable off the id itself.
@@ -87,6 +88,10 @@ __device__ __forceinline__ float bpermf(int src_lane, float v) {
 // that the access is base (scalar registers) + offset (one vector register) with no 64-bit vector arithmetic
 __device__ __forceinline__ int32_t *at32(int32_t *base, uint32_t idx) {
     return reinterpret_cast<int32_t *>(reinterpret_cast<char *>(base) + (idx << 2));
+}
+// the probability a sort key was made of (device_utils.h make_key: its high word), -0.0 read as +0.0
+__device__ __forceinline__ float key_prob(uint32_t w) {
+    return __uint_as_float(w ^ ((w & 0x80000000u) ? 0x80000000u : 0xFFFFFFFFu));
 }
 __device__ __forceinline__ int perm(int dst_lane, int v) {
     return __builtin_amdgcn_ds_permute(dst_lane << 2, v);
@@ -171,12 +176,22 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_pe
     // (PDQ: one entry per candidate rank, and as many tie words behind them -- per half)
     __shared__ int s_srcs[kWavesPerBlock][PDQ ? 128 : RPW * 16];
     constexpr int kTie = HALF;
+    // DSRC (two reads per wavefront): the renormalising divisions (:278-282) happen on the SOURCE lanes, before the
+    // survivors are gathered -- what is gathered are the quotients, and the group no longer has to share them through a
+    // further LDS round trip at the end of the step.  The layout it needs: a spare lane per group (it divides the gap
+    // probability of the slot's own candidate) and an idle lane per half (it divides 0, a child candidate's gap
+    // probability).  The divisor comes back with the survivor table: rank 0's probability word sits kTop entries
+    // behind the table (PDQ: the tie words).
+    constexpr bool DSRC = RPW == 2 && GW == 6;
+    static_assert(!DSRC || (HAS_SCRATCH && NIDLE >= 1), "a spare lane per group and an idle lane per half");
+    constexpr int kTop = PDQ ? kTie : 8;
+    static_assert(PDQ || !DSRC || (BCAP <= kTop && kTop + BCAP <= 16), "the probability words follow the entries");
     // PDQ: the node-ordered candidate list and the quicksort's tables of a tie-flagged step
     __shared__ uint64_t s_list[PDQ ? kWavesPerBlock : 1][64];
     __shared__ pdq178::WaveScratch<1> s_ws[PDQ ? kWavesPerBlock : 1];
     // PDQ, two reads per wavefront: where loop-carried state waits while the quicksort of a tie-flagged step runs
     constexpr bool PARK = PDQ && RPW == 2;
-    constexpr int kPark = kFifo + 18;
+    constexpr int kPark = kFifo + 16;
     __shared__ int s_park[PARK ? kWavesPerBlock : 1][PARK ? kPark * 64 : 1];
     static_assert(!PDQ || BCAP * N > 20, "the tie order only matters above 20 candidates");
     static_assert(!PDQ || BCAP * N <= HALF - 2, "the last two entries of a half's table are never written (i_src below)");
@@ -211,6 +226,10 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_pe
     const int l = k - 1;
     const int grp0 = hbase + i * GW;         // lane 0 of my group
     const int dummy = HAS_SCRATCH ? (idle ? lane : grp0 + GW - 1) : hbase + BCAP * GW + (q % (NIDLE > 0 ? NIDLE : 1));
+    // a candidate's survivor-table entry, low byte: its lane's byte address; DSRC: bit 0 set on a child lane
+    const int ent_lo = (lane << 2) | ((DSRC && !is_self) ? 1 : 0);
+    const bool spare = !idle && k == GW - 1;     // DSRC: divides its group's gap probability
+    const int zero_a = (hbase + BCAP * GW) << 2;  // DSRC: byte address of the half's first idle lane (0 / top)
     const int beam_size = p.a.beam_size;
     const bool collapse = !CRF && p.a.collapse != 0;
     const float thr = p.a.thr;

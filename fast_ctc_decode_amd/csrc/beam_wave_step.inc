@@ -39,9 +39,9 @@
         const bool svalid = grp && is_self && (blank || stay || has_inc);
 
         const bool valid = svalid || (cvalid && !merged);  // svalid / cvalid already carry is_self / is_child
-        float clp = is_self ? slp : contrib;  // (not const: PARK)
-        float cgp = is_self ? sgp : 0.0f;
-        float prob = clp + cgp;
+        const float clp = is_self ? slp : contrib;
+        const float cgp = is_self ? sgp : 0.0f;
+        const float prob = clp + cgp;
 
         const bool is_new = cvalid && !exists;
 
@@ -194,10 +194,11 @@
         // to the new slot followed by a broadcast to its group were two dependent ones).
         const int depc = depth + (is_child ? 1 : 0);
         bool sel;
-        int selflag, fate, own, src_a, e_min, top_a;
+        int selflag, fate, own, src_a, e_min, top_a, gp_a;
         int child_s;  // the entry after this step's bookkeeping
         int n_node, n_meta, n_state, n_jump, n_child;
         float n_lp, n_gp, top;
+        float dv = 0.0f;  // DSRC: what this lane divides by the top probability (not const: PARK)
         uint32_t tie0 = 0, tie1 = 1;
         // Everything that depends on the ranks: survivor table, fate of the child entries, row eviction, the gather of
         // the survivors into rank order.  PDQ: it runs on the exact ranks first; the tie table comes back with the
@@ -211,13 +212,20 @@
             // never used as sources, and as depths they are not looked at), and next to it, kTie words further on, its
             // probability (orderable bits): rank i ties with rank i + 1 when the two words are equal.  One
             // ds_write2_b32 under the mask the step already holds -- no test of the rank at all.
+            // DSRC: the exact-rank instantiations leave the probability word next to the entry as well (the same
+            // ds_write2_b32) -- rank 0's is the step's divisor, and it comes back with the table's own round trip.
             if (PDQ) {
                 if (valid && go) {
-                    srcs[rank] = (lane << 2) | (depc << 8);
+                    srcs[rank] = ent_lo | (depc << 8);
                     srcs[kTie + rank] = (int)(uint32_t)(key >> 32);
                 }
+            } else if (DSRC) {
+                if (sel) {
+                    srcs[rank] = ent_lo | (depc << 8);
+                    srcs[kTop + rank] = (int)(uint32_t)(key >> 32);
+                }
             } else {
-                if (sel) srcs[rank] = (lane << 2) | (depc << 8);
+                if (sel) srcs[rank] = ent_lo | (depc << 8);
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
@@ -226,9 +234,19 @@
             own = bperm(grp0, selflag);  // ... and this group's own candidate?
             // every lane of new group i learns its source lane (stale beyond the new beam: unused), where the best
             // candidate sits, and the SMALLEST DEPTH in the new beam: a stale entry can only lower it
-            src_a = srcs[PDQ ? i_src : i] & 0xFF;  // byte address, as ds_bpermute wants it
+            const int e_src = srcs[PDQ ? i_src : i];
+            src_a = e_src & (DSRC ? 0xFC : 0xFF);  // byte address, as ds_bpermute wants it
             e_min = srcs[0];
             top_a = e_min & 0xFF;
+            if (DSRC) {
+                // beam[0].probability() (:278) is rank 0's candidate probability: read off its sort key (read again by a
+                // step that settles twice: a tie never changes rank 0's probability, but no register is trusted across
+                // the rare block).  The gap quotient of the new slot waits on the source group's spare lane when the
+                // source is a slot's own lane, and on the half's first idle lane (0 / top) when it is a child lane:
+                // bit 0 of the entry says which.
+                top = key_prob((uint32_t)srcs[kTop]);
+                gp_a = (e_src & 1) ? zero_a : src_a + ((GW - 1) << 2);
+            }
 #pragma unroll
             for (int j = 1; j < BCAP; ++j) e_min = min(e_min, srcs[j]);
             if (PDQ) {
@@ -249,6 +267,10 @@
         // its row is in HBM); read off the entry BEFORE it is marked below
         const int kind = is_child ? 1 + ((child_in >> 30) & 1) : 0;
         int meta = kind | tipfc | (depc << 5);
+        // DSRC: every lane divides what it holds, HERE, before the gather: a candidate lane its label probability, a
+        // group's spare lane the gap probability of the slot's own candidate (it received the blank column like the
+        // slot's own lane and computed the same sgp), the half's idle lanes 0 -- a child candidate's gap probability.
+        if (DSRC) dv = spare ? sgp : (idle ? 0.0f : clp);
         auto settle_gather = [&]() __attribute__((always_inline)) {
             {
                 // a child entry whose node is a beam entry follows it to its new slot (or learns it left);
@@ -269,6 +291,19 @@
             }
             stamp_i(4, child_s);  // fate of every child entry, row eviction
             // ---- gather the survivors into rank order ----
+            if (DSRC) {
+                // the gathers that do not wait for the division travel under it; what is gathered last are the two
+                // IEEE quotients themselves (:279-282) -- the new slot's label and gap probability, final
+                n_meta = __builtin_amdgcn_ds_bpermute(src_a, meta);
+                n_node = __builtin_amdgcn_ds_bpermute(src_a, id);
+                n_state = CRF ? __builtin_amdgcn_ds_bpermute(src_a, statec) : 0;
+                n_jump = __builtin_amdgcn_ds_bpermute(src_a, jumpc);
+                n_child = __builtin_amdgcn_ds_bpermute(src_a + (k << 2), child_s);  // meaningful when the source is a self lane
+                stamp_i(5, n_meta);  // survivors gathered into rank order
+                const float quot = dv / top;
+                n_lp = __int_as_float(__builtin_amdgcn_ds_bpermute(src_a, __float_as_int(quot)));
+                n_gp = __int_as_float(__builtin_amdgcn_ds_bpermute(gp_a, __float_as_int(quot)));
+            } else {
             n_node = __builtin_amdgcn_ds_bpermute(src_a, id);
             n_lp = __int_as_float(__builtin_amdgcn_ds_bpermute(src_a, __float_as_int(clp)));
             n_gp = __int_as_float(__builtin_amdgcn_ds_bpermute(src_a, __float_as_int(cgp)));
@@ -278,6 +313,7 @@
             n_child = __builtin_amdgcn_ds_bpermute(src_a + (k << 2), child_s);  // meaningful when the source is a self lane
             top = __int_as_float(__builtin_amdgcn_ds_bpermute(top_a, __float_as_int(prob)));  // beam[0].probability() :278 = its candidate's label + gap probability
             stamp_f(5, n_lp);  // survivors gathered into rank order
+            }
         };
         settle_gather();
         int n_kind;
@@ -371,21 +407,19 @@
                         park[64 * kFifo] = __float_as_int(incoming);
                         park[64 * (kFifo + 1)] = __float_as_int(pk_next);
                         park[64 * (kFifo + 2)] = __float_as_int(ptip_next);
-                        park[64 * (kFifo + 3)] = __float_as_int(clp);
-                        park[64 * (kFifo + 4)] = __float_as_int(cgp);
-                        park[64 * (kFifo + 5)] = meta;
-                        park[64 * (kFifo + 6)] = jumpc;
-                        park[64 * (kFifo + 7)] = id;
-                        park[64 * (kFifo + 8)] = child_in;
-                        park[64 * (kFifo + 9)] = statec;
-                        park[64 * (kFifo + 10)] = __float_as_int(prob);
-                        park[64 * (kFifo + 11)] = node;
-                        park[64 * (kFifo + 12)] = depth;
-                        park[64 * (kFifo + 13)] = tipf;
-                        park[64 * (kFifo + 14)] = state;
-                        park[64 * (kFifo + 15)] = (int)(uint32_t)key;
-                        park[64 * (kFifo + 16)] = (int)(uint32_t)(key >> 32);
-                        park[64 * (kFifo + 17)] = rank;
+                        park[64 * (kFifo + 3)] = __float_as_int(dv);  // (all the second settle needs of clp, cgp and prob)
+                        park[64 * (kFifo + 4)] = meta;
+                        park[64 * (kFifo + 5)] = jumpc;
+                        park[64 * (kFifo + 6)] = id;
+                        park[64 * (kFifo + 7)] = child_in;
+                        park[64 * (kFifo + 8)] = statec;
+                        park[64 * (kFifo + 9)] = node;
+                        park[64 * (kFifo + 10)] = depth;
+                        park[64 * (kFifo + 11)] = tipf;
+                        park[64 * (kFifo + 12)] = state;
+                        park[64 * (kFifo + 13)] = (int)(uint32_t)key;
+                        park[64 * (kFifo + 14)] = (int)(uint32_t)(key >> 32);
+                        park[64 * (kFifo + 15)] = rank;
                     }
 #pragma unroll 1
                     for (int hs = 0; hs < RPW; ++hs) {
@@ -400,20 +434,18 @@
                         incoming = __int_as_float(park[64 * kFifo]);
                         pk_next = __int_as_float(park[64 * (kFifo + 1)]);
                         ptip_next = __int_as_float(park[64 * (kFifo + 2)]);
-                        clp = __int_as_float(park[64 * (kFifo + 3)]);
-                        cgp = __int_as_float(park[64 * (kFifo + 4)]);
-                        meta = park[64 * (kFifo + 5)];
-                        jumpc = park[64 * (kFifo + 6)];
-                        id = park[64 * (kFifo + 7)];
-                        child_in = park[64 * (kFifo + 8)];
-                        statec = park[64 * (kFifo + 9)];
-                        prob = __int_as_float(park[64 * (kFifo + 10)]);
-                        node = park[64 * (kFifo + 11)];
-                        depth = park[64 * (kFifo + 12)];
-                        tipf = park[64 * (kFifo + 13)];
-                        state = park[64 * (kFifo + 14)];
-                        rank = park[64 * (kFifo + 17)];
-                        key = (uint64_t)(uint32_t)park[64 * (kFifo + 15)] | ((uint64_t)(uint32_t)park[64 * (kFifo + 16)] << 32);
+                        dv = __int_as_float(park[64 * (kFifo + 3)]);
+                        meta = park[64 * (kFifo + 4)];
+                        jumpc = park[64 * (kFifo + 5)];
+                        id = park[64 * (kFifo + 6)];
+                        child_in = park[64 * (kFifo + 7)];
+                        statec = park[64 * (kFifo + 8)];
+                        node = park[64 * (kFifo + 9)];
+                        depth = park[64 * (kFifo + 10)];
+                        tipf = park[64 * (kFifo + 11)];
+                        state = park[64 * (kFifo + 12)];
+                        rank = park[64 * (kFifo + 15)];
+                        key = (uint64_t)(uint32_t)park[64 * (kFifo + 13)] | ((uint64_t)(uint32_t)park[64 * (kFifo + 14)] << 32);
                     }
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                     __builtin_amdgcn_wave_barrier();
@@ -467,12 +499,19 @@
         }
         if (CRF && (UNI || go)) state = n_state;  // < S: (s*4) % 4 + l = l for (N, S) = (5, 4); masked when GATHER
         if (UNI || go) tipf = n_meta & 0x1C;
-        if (GATHER) rowv = gather_row(t + 1);  // in flight during the divisions below
+        if (GATHER) rowv = gather_row(t + 1);  // in flight during the divisions below (DSRC: behind the quotients' gather)
         else fetch_row(pk_next, ptip_next);    // (the FIFO was already advanced to step t + 1 above)
-        // Every lane of a group would compute the same two IEEE quotients: lane k = 1 divides the gap
-        // probability, the others the label probability -- one division per lane -- and the group shares them.
-        const float quot = (k == 1 ? n_gp : n_lp) / top;
-        const float q_lp = bpermf(grp0, quot), q_gp = bpermf(grp0 + 1, quot);
+        float q_lp, q_gp;
+        if (DSRC) {  // divided at the source, before the gather
+            q_lp = n_lp;
+            q_gp = n_gp;
+        } else {
+            // Every lane of a group would compute the same two IEEE quotients: lane k = 1 divides the gap
+            // probability, the others the label probability -- one division per lane -- and the group shares them.
+            const float quot = (k == 1 ? n_gp : n_lp) / top;
+            q_lp = bpermf(grp0, quot);
+            q_gp = bpermf(grp0 + 1, quot);
+        }
         if (UNI || go) {
             node = n_node;
             lp = q_lp;
