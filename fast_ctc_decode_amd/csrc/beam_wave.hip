@@ -26,7 +26,8 @@
 //     reference's sort-by-node + fold (:245-260), order-independent because at most two non-zero
 //     f32 addends ever meet;
 //   * new tree nodes get ids in the reference's creation order via ballot + prefix popcount;
-//   * pruning ranks the candidates exactly on a 64-bit key (probability desc, node asc);
+//   * pruning ranks the candidates exactly on a 64-bit key (probability desc, node asc); two reads per wavefront: on
+//     the key's probability word alone (R32 below), the node word only where kept candidates share a probability;
 //   * survivors publish (lane, depth) by rank in a small LDS table: one round trip later every lane knows
 //     its source lane, where the best candidate sits and the minimum depth of the new beam; the survivors are
 //     gathered into rank order with ds_bpermute and divided by the top probability (:278-282, IEEE f32
@@ -106,7 +107,8 @@ constexpr int kSeg = 64;  // nodes per traceback segment (jump-pointer spacing)
 // is spelt out there: the emulator's host compiler does not take a function call inside an attribute it does not know).
 // Two reads per wavefront: 5, i.e. at most 96 VGPRs, since the rank's comparands are streamed (beam_wave_step.inc), the row
 // FIFO is six registers deep and the read's index is formed again after the time loop instead of being carried through
-// it.  The exact-rank instantiations then hold 70-92 VGPRs; the PDQ ones of equal-length launches (UNI: the headline) 95,
+// it.  The exact-rank instantiations then hold 68-86 VGPRs (R32: the comparands are 32-bit words, four to a 16-byte read);
+// the PDQ ones of equal-length launches (UNI: the headline) 94 -- not the 80 a sixth wavefront needs --,
 // with the loop-carried state parked in LDS around the inlined quicksort of the rare tie branch.  No scratch in either.
 // The other PDQ instantiations (ragged lengths, 16-bit posteriors, n-best) answer a budget of 96 with 8 bytes of scratch,
 // which the time loop must not have, and stay at 4 wavefronts; so do the session instantiations.
@@ -171,6 +173,15 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_pe
     // the rank's comparands are streamed through a few registers (beam_wave_step.inc) instead of all being loaded first
     constexpr bool STREAM = RPW == 2 && GW == 6 && !AMB;
     static_assert(!STREAM || (GW % 2 == 0 && HALF % 2 == 0), "a slot's first key sits on 16 bytes");
+    // R32: the rank is taken on the PROBABILITY WORD of the key alone (beam_wave_step.inc).  The 64-bit key table becomes two
+    // tables of 32-bit words in the same 512 bytes: a half's probability words, compacted to slot * N + column (kHalfW words
+    // per half, a multiple of four: four comparands per 16-byte read), and kNodeTab words further on, in the same order, the
+    // node words -- read only where kept candidates share a probability, and by the PDQ list builder.  A lane that holds
+    // no candidate (a group's spare lanes, a half's idle lanes) writes its two zeros to a word behind the second half.
+    constexpr bool R32 = STREAM;
+    constexpr int kHalfW = (BCAP * N + 3) / 4 * 4;
+    constexpr int kNodeTab = 64;
+    static_assert(!R32 || 2 * kHalfW < kNodeTab, "both halves' words and the word for idle writes fit ahead of the node table");
     __shared__ int s_heads[kWavesPerBlock][64];
     // survivor table, per half: entry r = (byte address of the lane whose candidate took rank r) | that candidate's depth << 8
     // (PDQ: one entry per candidate rank, and as many tie words behind them -- per half)
@@ -234,6 +245,9 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_pe
     const bool collapse = !CRF && p.a.collapse != 0;
     const float thr = p.a.thr;
     uint64_t *keys = s_keys[wave];
+    uint32_t *const kwords = reinterpret_cast<uint32_t *>(s_keys[wave]);  // R32: the two word tables
+    const int hw = hbase ? kHalfW : 0;                                    // R32: this half's first word
+    const int kslot = (!idle && k < N) ? hw + i * N + k : 2 * kHalfW;     // R32: where this lane's candidate leaves its words
     int *srcs = s_srcs[wave] + (hbase ? (PDQ ? 2 * HALF : 16) : 0);
     // smallest candidate count from which "rank i ties with rank i + 1" is the quicksort's business: more than 20
     // candidates, rank i kept, rank i + 1 present (never, for a lane outside the beam's groups)

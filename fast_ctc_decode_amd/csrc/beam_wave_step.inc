@@ -49,10 +49,20 @@
         // The key needs a node index only to break probability ties, and only its ORDER matters: a node
         // created in this step gets (t << KS) + q here -- above every existing index and increasing with the
         // lane, exactly like the index it is about to receive -- so the key does not wait for the numbering below.
-        // (A NaN key is garbage but non-zero: it only ever ranks when it is the read's lone candidate, :262.)
+        // (A NaN key is garbage but non-zero: it only ever ranks when it is the read's lone candidate, :262.  Its
+        // probability word may be 0 -- the negative NaN with an all-ones payload -- so "is a candidate" stays key != 0.)
         const int idk = is_self ? node : (is_new ? tks + q : cid);
         uint64_t key = (UNI ? valid : (valid && act)) ? make_key(prob, idk) : 0ull;
-        keys[lane] = key;
+        // R32: the probability word and the node word go to two tables (beam_wave.hip), one ds_write2_b32; the rank below
+        // is taken on the probability word alone, and candidates of equal probability are told apart only in the step's
+        // rare branch, when the survivor table shows that two KEPT ones met (settle_table).
+        const uint32_t kp = (uint32_t)(key >> 32);
+        if (R32) {
+            kwords[kslot] = kp;
+            kwords[kslot + kNodeTab] = (uint32_t)key;
+        } else {
+            keys[lane] = key;
+        }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -67,7 +77,22 @@
         constexpr int NP = BCAP * NPR;     // comparands v < NP: (slot v / NPR, column v % NPR); v >= NP: (slot v - NP, column N - 1)
         constexpr int NBLK = (NC + 3) / 4;
         constexpr int kAhead = 2;
+        // R32: the half's probability words are contiguous -- block j is words 4j .. 4j + 3, one ds_read_b128 (the last block
+        // what is left: one word when N = 5)
+        uint32_t kw[NC];
         auto load_blk = [&](int j) __attribute__((always_inline)) {
+            if (R32) {
+                if (4 * j + 4 <= NC) {
+                    uint32_t four[4];
+                    __builtin_memcpy(four, __builtin_assume_aligned(&kwords[hw + 4 * j], 16), 16);
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) kw[4 * j + v] = four[v];
+                } else {
+#pragma unroll
+                    for (int v = 4 * j; v < NC; ++v) kw[v] = kwords[hw + v];
+                }
+                return;
+            }
 #pragma unroll
             for (int v = 4 * j; v < 4 * j + 4 && v < NC; ++v) {
                 if (v < NP) {
@@ -131,7 +156,16 @@
             for (int j = 0; j < NBLK; ++j) {
                 __builtin_amdgcn_sched_barrier(0);
                 if (j + kAhead < NBLK) load_blk(j + kAhead);
-                if (j == 0) {
+                if (R32) {  // r32 = #(probability word > own): candidates of equal probability share it
+                    if (j == 0) {
+                        FCD_RANK4_32_FIRST(kp, kw[0], kw[1], kw[2], kw[3], r0, r1, r2, r3);
+                    } else if (4 * j + 4 <= NC) {
+                        FCD_RANK4_32(kp, kw[4 * j], kw[4 * j + 1], kw[4 * j + 2], kw[4 * j + 3], r0, r1, r2, r3);
+                    } else {
+#pragma unroll
+                        for (int u = 4 * j; u < NC; ++u) r0 += (kw[u] > kp) ? 1 : 0;
+                    }
+                } else if (j == 0) {
                     FCD_RANK4_FIRST(key, kk[0], kk[1], kk[2], kk[3], r0, r1, r2, r3);
                 } else if (4 * j + 4 <= NC) {
                     FCD_RANK4(key, kk[4 * j], kk[4 * j + 1], kk[4 * j + 2], kk[4 * j + 3], r0, r1, r2, r3);
@@ -200,6 +234,7 @@
         float n_lp, n_gp, top;
         float dv = 0.0f;  // DSRC: what this lane divides by the top probability (not const: PARK)
         uint32_t tie0 = 0, tie1 = 1;
+        bool clash = false;  // R32: this lane's entry of the survivor table was overwritten by a candidate of equal probability
         // Everything that depends on the ranks: survivor table, fate of the child entries, row eviction, the gather of
         // the survivors into rank order.  PDQ: it runs on the exact ranks first; the tie table comes back with the
         // same LDS round trip and is looked at only when the gather has landed -- a flagged step (rare) replaces the
@@ -214,22 +249,36 @@
             // ds_write2_b32 under the mask the step already holds -- no test of the rank at all.
             // DSRC: the exact-rank instantiations leave the probability word next to the entry as well (the same
             // ds_write2_b32) -- rank 0's is the step's divisor, and it comes back with the table's own round trip.
+            const int ent = ent_lo | (depc << 8);
             if (PDQ) {
                 if (valid && go) {
-                    srcs[rank] = ent_lo | (depc << 8);
+                    srcs[rank] = ent;
                     srcs[kTie + rank] = (int)(uint32_t)(key >> 32);
                 }
             } else if (DSRC) {
                 if (sel) {
-                    srcs[rank] = ent_lo | (depc << 8);
+                    srcs[rank] = ent;
                     srcs[kTop + rank] = (int)(uint32_t)(key >> 32);
                 }
             } else {
-                if (sel) srcs[rank] = ent_lo | (depc << 8);
+                if (sel) srcs[rank] = ent;
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            // R32: candidates of equal probability hold the same rank here, the smallest of their exact ranks, and wrote
+            // the same entry: all but one of them find another lane's entry there (ent_lo: entries of different lanes
+            // differ) and the ranks behind theirs hold stale data.  Only a KEPT rank is looked at: equal candidates share
+            // their r32, so a tie inside the beam or across its boundary has every member below beam_size, and one wholly
+            // below the boundary (PDQ: those candidates write as well) changes nothing the step uses.  Without a clash
+            // every kept candidate's r32 IS its exact rank, every other candidate's exact rank is >= its r32 >= beam_size,
+            // and no two of the table's first beam_size + 1 probability words are equal.
+            // (Every lane reads, a lane that wrote nothing anywhere inside its half's table: the read-back then travels with
+            // the table's other reads instead of waiting alone under a mask of its own.)
+            if (R32) {
+                const int back = srcs[PDQ ? rank : (rank & 15)];
+                clash = sel && back != ent;
+            }
             fate = bperm(hbase + mslot * GW, selflag);
             own = bperm(grp0, selflag);  // ... and this group's own candidate?
             // every lane of new group i learns its source lane (stale beyond the new beam: unused), where the best
@@ -329,18 +378,48 @@
         // bare compare), and -- PDQ -- ranks i and i + 1 hold one probability, rank i is kept and rank i + 1 exists:
         // sort_unstable_by's order of the two is pdqsort's business once the list is longer than 20 (:262).  tie_lim
         // folds "i < beam_size", "i + 1 < n_valid" and "n_valid > 20" into one compare: equal probabilities among FEW
-        // candidates are common on peaky posteriors (a third of such reads meet one) and must not take the rare path.
+        // candidates are common on peaky posteriors (a third of such reads meet one) and must not take the QUICKSORT'S path.
+        // (R32 takes the branch for them, to recount: 0.5 % of a wavefront's steps on peaky rows, one step in 512 000 on the
+        // benchmark's -- DESIGN.md section 4 -- each for some 60 instructions and the second settling.)
         // (A half that is not running, or has just failed, has no candidates or loses nothing by re-ranking them.)
         // Masks, not lane flags: a flag used again inside the rare block would be materialised in a register.
         const uint64_t m_k2 = ballot(n_kind == 2);
-        const uint64_t m_hint = PDQ ? (ballot(tie0 == tie1) & ballot(tie_lim < n_valid)) : 0ull;
-        if (__builtin_expect((m_k2 | m_hint) != 0ull, 0)) {
+        // R32: a third -- kept candidates of equal probability met in the survivor table.  The halves recount their EXACT
+        // ranks from the two word tables (rank = #(greater probability word) + #(equal word, greater node word): an empty
+        // slot's words are 0, 0 and count for nobody; a lane's own neither) and settle again; nothing of the first pass was
+        // committed.  (Its eviction stores: `own`, `fate` and e_min came from a table with a hole -- a store it made that
+        // the second pass does not is the harmless one described above, and one it skipped the second pass makes.)  The
+        // PDQ hint needs no first-pass test at all: two equal words among the first beam_size + 1 ranks ARE a clash, so it is
+        // read off the settled table, where no hole can raise or hide it.
+        const uint64_t m_clash = R32 ? ballot(clash) : 0ull;
+        const uint64_t m_hint = (PDQ && !R32) ? (ballot(tie0 == tie1) & ballot(tie_lim < n_valid)) : 0ull;
+        if (__builtin_expect((m_k2 | m_hint | m_clash) != 0ull, 0)) {
+            uint64_t m_tied = m_hint;
+            if (R32 && m_clash != 0ull) {
+                const uint32_t kn = (uint32_t)key;
+                int ex = 0;
+#pragma unroll 1
+                for (int ii = 0; ii < BCAP; ++ii) {  // a beam slot's N candidates per trip
+                    uint32_t pu[N], nu[N];
+#pragma unroll
+                    for (int c = 0; c < N; ++c) {
+                        pu[c] = kwords[hw + ii * N + c];
+                        nu[c] = kwords[hw + ii * N + c + kNodeTab];
+                    }
+#pragma unroll
+                    for (int c = 0; c < N; ++c) ex += (pu[c] > kp || (pu[c] == kp && nu[c] > kn)) ? 1 : 0;
+                }
+                rank = ex;
+                settle_table();
+                settle_gather();
+                kinds();
+                if (PDQ) m_tied = ballot(tie0 == tie1) & ballot(tie_lim < n_valid);
+            }
             if (PDQ) {
                 // Nothing of the step is committed yet: the ranks are replaced by the quicksort's (pdq178_wave.h) and
                 // everything that depends on them runs again.  (An eviction store of the first pass that the second does
                 // not repeat leaves a row in HBM nobody reads before it is written again: rows are read back only after
                 // their node's LAST eviction.)
-                const uint64_t m_tied = m_hint;
                 if (m_tied != 0ull) {
                     const bool mine = RPW == 1 ? true : (hbase ? (m_tied >> 32) != 0ull : (uint32_t)m_tied != 0u);
                     __builtin_amdgcn_s_setprio(3);  // (a straggler in the making keeps the issue priority: see beam_lane.hip)
@@ -368,6 +447,15 @@
                     } else {
 #pragma unroll 1
                     for (int ii = 0; ii < BCAP; ++ii) {  // a beam slot's N keys per trip: their loads travel together
+                        if (R32) {  // the node table (an empty slot's word is 0 and exceeds nothing)
+                            const uint32_t *nt = reinterpret_cast<const uint32_t *>(s_keys[wave_r]) + (hbase_r ? kHalfW : 0) + kNodeTab;
+                            uint32_t nu[N];
+#pragma unroll
+                            for (int c = 0; c < N; ++c) nu[c] = nt[ii * N + c];
+#pragma unroll
+                            for (int c = 0; c < N; ++c) pos += nu[c] > (uint32_t)key ? 1 : 0;  // larger = smaller node
+                            continue;
+                        }
                         uint64_t ku[N];
 #pragma unroll
                         for (int c = 0; c < N; ++c) ku[c] = s_keys[wave_r][hbase_r + ii * GW + c];

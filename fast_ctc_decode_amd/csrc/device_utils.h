@@ -102,6 +102,48 @@ __device__ __forceinline__ int32_t load_i32_l2(const int32_t *p) {
     } while (0)
 #endif
 
+// The same two blocks on 32-bit words: r_j += (w_j > word).  The two-reads-per-wavefront kernels rank on the probability
+// word of the key alone (beam_wave_step.inc, R32) -- half the comparand bytes, and the node word only where two kept
+// candidates share a probability.
+#ifdef FCD_HIPEMU  // (lockstep emulation, tests/hipemu: plain C++)
+#define FCD_RANK4_32(word, wa, wb, wc, wd, r0, r1, r2, r3) \
+    do { (r0) += (wa) > (word); (r1) += (wb) > (word); (r2) += (wc) > (word); (r3) += (wd) > (word); } while (0)
+#define FCD_RANK4_32_FIRST(word, wa, wb, wc, wd, r0, r1, r2, r3) \
+    do { (r0) = (wa) > (word); (r1) = (wb) > (word); (r2) = (wc) > (word); (r3) = (wd) > (word); } while (0)
+#else
+#define FCD_RANK4_32(word, wa, wb, wc, wd, r0, r1, r2, r3)                                     \
+    do {                                                                                       \
+        uint64_t m0__, m1__, m2__, m3__;                                                       \
+        asm("v_cmp_gt_u32_e64 %4, %9, %8\n\t"                                                  \
+            "v_cmp_gt_u32_e64 %5, %10, %8\n\t"                                                 \
+            "v_cmp_gt_u32_e64 %6, %11, %8\n\t"                                                 \
+            "v_cmp_gt_u32_e64 %7, %12, %8\n\t"                                                 \
+            "v_addc_co_u32_e64 %0, vcc, 0, %0, %4\n\t"                                         \
+            "v_addc_co_u32_e64 %1, vcc, 0, %1, %5\n\t"                                         \
+            "v_addc_co_u32_e64 %2, vcc, 0, %2, %6\n\t"                                         \
+            "v_addc_co_u32_e64 %3, vcc, 0, %3, %7"                                              \
+            : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3), "=&s"(m0__), "=&s"(m1__), "=&s"(m2__), "=&s"(m3__) \
+            : "v"(word), "v"(wa), "v"(wb), "v"(wc), "v"(wd)                                    \
+            : "vcc");                                                                          \
+    } while (0)
+#define FCD_RANK4_32_FIRST(word, wa, wb, wc, wd, r0, r1, r2, r3)                               \
+    do {                                                                                       \
+        uint64_t m0__, m1__, m2__, m3__;                                                       \
+        const int zero__ = 0;                                                                  \
+        asm("v_cmp_gt_u32_e64 %4, %9, %8\n\t"                                                  \
+            "v_cmp_gt_u32_e64 %5, %10, %8\n\t"                                                 \
+            "v_cmp_gt_u32_e64 %6, %11, %8\n\t"                                                 \
+            "v_cmp_gt_u32_e64 %7, %12, %8\n\t"                                                 \
+            "v_addc_co_u32_e64 %0, vcc, 0, %13, %4\n\t"                                        \
+            "v_addc_co_u32_e64 %1, vcc, 0, %13, %5\n\t"                                        \
+            "v_addc_co_u32_e64 %2, vcc, 0, %13, %6\n\t"                                        \
+            "v_addc_co_u32_e64 %3, vcc, 0, %13, %7"                                             \
+            : "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(r3), "=&s"(m0__), "=&s"(m1__), "=&s"(m2__), "=&s"(m3__) \
+            : "v"(word), "v"(wa), "v"(wb), "v"(wc), "v"(wd), "v"(zero__)                       \
+            : "vcc");                                                                          \
+    } while (0)
+#endif
+
 // Makes a value opaque to the optimiser and pins it in vector registers (the duplex kernel's coefficient table).
 // (tests/hipemu predefines FCD_OPAQUE_V as a no-op.)
 #ifndef FCD_OPAQUE_V
