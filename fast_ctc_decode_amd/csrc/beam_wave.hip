@@ -105,13 +105,18 @@ constexpr int kSeg = 64;  // nodes per traceback segment (jump-pointer spacing)
 
 // Wavefronts per SIMD the register allocator is asked to leave room for (amdgpu_waves_per_eu on the kernel below; the value
 // is spelt out there: the emulator's host compiler does not take a function call inside an attribute it does not know).
-// Two reads per wavefront: 5, i.e. at most 96 VGPRs, since the rank's comparands are streamed (beam_wave_step.inc), the row
-// FIFO is six registers deep and the read's index is formed again after the time loop instead of being carried through
-// it.  The exact-rank instantiations then hold 68-86 VGPRs (R32: the comparands are 32-bit words, four to a 16-byte read);
-// the PDQ ones of equal-length launches (UNI: the headline) 94 -- not the 80 a sixth wavefront needs --,
-// with the loop-carried state parked in LDS around the inlined quicksort of the rare tie branch.  No scratch in either.
-// The other PDQ instantiations (ragged lengths, 16-bit posteriors, n-best) answer a budget of 96 with 8 bytes of scratch,
-// which the time loop must not have, and stay at 4 wavefronts; so do the session instantiations.
+// The attribute only bounds the allocator: what runs is what the registers (512 per SIMD lane, granules of 8) and the LDS
+// (160 KiB per CU, a workgroup = one wavefront per SIMD) admit.
+// Two reads per wavefront, equal lengths, register row FIFO (UNI, S >= 0: the headline family): 6, i.e. at most 80 VGPRs
+// and at most 27 264 B of LDS per workgroup.  The exact-rank instantiations hold 70-76 VGPRs and 3 584 B.  The PDQ ones
+// hold 80 VGPRs and 22 528 B: the quicksort of the rare tie branch runs in registers on a half's <= 25 candidates
+// (pdq178_reg.h with a compile-time length bound: no ninther, no shifting insertion sort, no list or position tables in
+// LDS), with fifteen words per lane parked in LDS around it.  No scratch in either.  (At 7, i.e. 72 VGPRs, the PDQ ones
+// spill: 32 B in the prologue of S = 0, 16 B in S = 4.)
+// The other two-reads-per-wavefront instantiations keep 5: ragged lengths, 16-bit posteriors and n-best exact-rank ones
+// hold 68-78 VGPRs, the row-gather CRF one with PDQ 94 with the loop-carried state parked in LDS around the inlined
+// through-LDS quicksort.  The other PDQ instantiations (ragged lengths, 16-bit posteriors, n-best) answer a budget of 96
+// with 8 bytes of scratch, which the time loop must not have, and stay at 4 wavefronts; so do the session instantiations.
 
 // S == 0: search::beam_search.  S > 0: search::crf_beam_search (:38-157) with S transition states:
 // the row is probs[t, state, :] of the entry's state, there is no repeat-stay, and an extension
@@ -151,7 +156,7 @@ constexpr int kSeg = 64;  // nodes per traceback segment (jump-pointer spacing)
 // A failure is kept in the state, not written to `out`: later launches leave the slot alone.
 template <int N, int GW, int RPW, int S, bool AMB, bool PROF = false, bool UNI = false, bool H16 = false, bool PDQ = false,
           bool NB = false, bool SES = false>
-__global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_per_eu((RPW == 2 && !AMB) ? ((SES || (PDQ && !UNI)) ? 4 : 5) : 1))) void beam_wave_kernel(WaveParams p) {
+__global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_per_eu((RPW == 2 && !AMB) ? ((SES || (PDQ && !UNI)) ? 4 : ((UNI && !NB && S >= 0) ? 6 : 5)) : 1))) void beam_wave_kernel(WaveParams p) {
     constexpr bool CRF = S != 0;
     constexpr bool GATHER = S == kCrfGather;
     constexpr int NL = N - 1;
@@ -199,11 +204,19 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_pe
     static_assert(PDQ || !DSRC || (BCAP <= kTop && kTop + BCAP <= 16), "the probability words follow the entries");
     // PDQ: the node-ordered candidate list and the quicksort's tables of a tie-flagged step
     __shared__ uint64_t s_list[PDQ ? kWavesPerBlock : 1][64];
-    __shared__ pdq178::WaveScratch<1> s_ws[PDQ ? kWavesPerBlock : 1];
+    // RSORT: the headline family (two reads per wavefront, equal lengths) replays the quicksort of a tie-flagged step in
+    // registers (pdq178_reg.h): a half's list has at most BCAP * N <= 64 elements, one per lane.  s_list is then only the
+    // spill area of the replay's serial fall-backs, and there are no position tables.
+    constexpr bool RSORT = PDQ && RPW == 2 && GW == 6 && UNI && !AMB && !NB && !SES && S >= 0;
+    static_assert(!RSORT || BCAP * N <= 62, "a half's candidates fit the lanes of the wavefront");
+    __shared__ pdq178::WaveScratch<1> s_ws[(PDQ && !RSORT) ? kWavesPerBlock : 1];
     // PDQ, two reads per wavefront: where loop-carried state waits while the quicksort of a tie-flagged step runs
-    constexpr bool PARK = PDQ && RPW == 2;
-    constexpr int kPark = kFifo + 16;
-    __shared__ int s_park[PARK ? kWavesPerBlock : 1][PARK ? kPark * 64 : 1];
+    constexpr bool PARK = PDQ && RPW == 2 && !RSORT;
+    // (RSORT parks fewer words: the prefetched row values are dead in the rare block -- the step fetches the next ones
+    // behind it --, the sort key is read back from the word tables, and the rank stays in its register)
+    constexpr bool RPARK = RSORT;
+    constexpr int kPark = RSORT ? kFifo + 9 : kFifo + 16;
+    __shared__ int s_park[(PARK || RPARK) ? kWavesPerBlock : 1][(PARK || RPARK) ? kPark * 64 : 1];
     static_assert(!PDQ || BCAP * N > 20, "the tie order only matters above 20 candidates");
     static_assert(!PDQ || BCAP * N <= HALF - 2, "the last two entries of a half's table are never written (i_src below)");
     int n_amb = 0, n_crit = 0;

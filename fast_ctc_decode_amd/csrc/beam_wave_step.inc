@@ -427,7 +427,7 @@
                     // addresses and lane masks the quicksort derives from them are formed HERE -- hoisted out of the time
                     // loop they were carried through it, and at five wavefronts per SIMD spilled)
                     int lane_r = lane, wave_r = wave;
-                    if (PARK) {
+                    if (PARK || RSORT) {
                         FCD_OPAQUE_V(lane_r);
                         FCD_OPAQUE_V(wave_r);
                     }
@@ -478,6 +478,57 @@
                                          s_list[wave], lane);
                         const int back = perm(lane < n_list ? (int)rt : 63, lane);
                         if (cand) rank = back;
+                    } else if (RSORT) {
+                        // Two reads per wavefront, equal lengths (the headline): a half never holds more than BCAP * N
+                        // candidates, so its list fits the lanes of the wavefront and the quicksort runs in registers, as
+                        // above -- one flagged half after the other, the list of half hs in lanes 0 .. n_list - 1.  No list
+                        // in LDS and no partition path through it.
+                        // What the quicksort does not touch and the second settling (or the next step) needs waits in LDS
+                        // meanwhile, so that the replay does not set the register budget of the whole kernel.
+                        static_assert(!RSORT || NC <= 62, "lane 63 is the idle target of the pushes");
+                        int *const park = s_park[RPARK ? wave_r : 0] + lane_r;
+                        if (RPARK) {
+#pragma unroll
+                        for (int j = 0; j < kFifo; ++j) park[64 * j] = __float_as_int(win[j]);
+                        park[64 * kFifo] = __float_as_int(incoming);
+                        park[64 * (kFifo + 1)] = __float_as_int(dv);  // (all the second settle needs of clp, cgp and prob)
+                        park[64 * (kFifo + 2)] = meta;
+                        park[64 * (kFifo + 3)] = jumpc;
+                        park[64 * (kFifo + 4)] = id;
+                        park[64 * (kFifo + 5)] = child_in;
+                        park[64 * (kFifo + 6)] = node;
+                        park[64 * (kFifo + 7)] = depth;
+                        park[64 * (kFifo + 8)] = statec;
+                        }
+#pragma unroll 1
+                        for (int hs = 0; hs < RPW; ++hs) {
+                            const bool flagged = (hs ? (m_tied >> 32) != 0ull : (uint32_t)m_tied != 0u);
+                            if (!flagged) continue;
+                            const bool cand = key != 0ull && (lane_r >= HALF) == (hs != 0);
+                            uint32_t rk = (uint32_t)perm(cand ? pos : 63, (int)(uint32_t)(key >> 32));
+                            uint32_t rt = (uint32_t)perm(cand ? pos : 63, lane_r);
+                            const int n_list = __builtin_amdgcn_readlane(n_valid, hs * HALF);
+                            pdq178::reg_sort<NC>(rk, rt, n_list, beam_size, false, 0u, 32 - __builtin_clz((unsigned)n_list), true, true,
+                                                 s_list[wave_r], lane_r);
+                            const int back = perm(lane_r < n_list ? (int)rt : 63, lane_r);
+                            if (cand) rank = back;
+                        }
+                        if (RPARK) {
+#pragma unroll
+                        for (int j = 0; j < kFifo; ++j) win[j] = __int_as_float(park[64 * j]);
+                        incoming = __int_as_float(park[64 * kFifo]);
+                        dv = __int_as_float(park[64 * (kFifo + 1)]);
+                        meta = park[64 * (kFifo + 2)];
+                        jumpc = park[64 * (kFifo + 3)];
+                        id = park[64 * (kFifo + 4)];
+                        child_in = park[64 * (kFifo + 5)];
+                        node = park[64 * (kFifo + 6)];
+                        depth = park[64 * (kFifo + 7)];
+                        statec = park[64 * (kFifo + 8)];
+                        }
+                        // the lane's own key, from the two word tables it wrote at the top of the step (a lane without a
+                        // candidate reads the idle word: 0, 0)
+                        if (R32) key = ((uint64_t)kwords[kslot] << 32) | kwords[kslot + kNodeTab];
                     } else {
                     if (mine && key != 0ull) list[pos] = (key & 0xFFFFFFFF00000000ull) | (uint32_t)lane_r;
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");

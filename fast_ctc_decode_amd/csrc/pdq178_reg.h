@@ -64,7 +64,9 @@ __device__ __forceinline__ int perm(int dst_lane, int v) { return __builtin_amdg
 // as far as its first `keep` positions go -- as the continuation of a quicksort: `has_pred` / `pred_key` = the
 // predecessor pivot of the segment (recurse's `pred`), `limit`, `wbal`, `wpar` = its limit and was_balanced /
 // was_partitioned (a fresh list: no predecessor, the bit length of n, true, true).  Called by all 64 lanes with the
-// same arguments; `spill` = n elements of LDS scratch for the serial fall-backs.
+// same arguments; `spill` = n elements of LDS scratch for the serial fall-backs.  MAXN = a compile-time bound of n: below
+// 50 there is no ninther and partial_insertion_sort never shifts, so neither is instantiated.
+template <int MAXN = 64>
 __device__ __forceinline__ void reg_sort(uint32_t &key, uint32_t &tag, const int n_in, const int keep_in, const bool has_pred,
                                          const uint32_t pred_key, const int limit_in, const bool wbal_in, const bool wpar_in,
                                          elem_t *spill_generic, const int lane) {
@@ -127,7 +129,7 @@ __device__ __forceinline__ void reg_sort(uint32_t &key, uint32_t &tag, const int
                 --limit;
             }
             // ---- choose_pivot ----
-            const bool ninther = len >= 50;
+            const bool ninther = MAXN >= 50 && len >= 50;
             const int ia = len / 4, ib = ia * 2, ic = ia * 3;
             uint32_t e[9];
 #pragma unroll
@@ -182,7 +184,7 @@ __device__ __forceinline__ void reg_sort(uint32_t &key, uint32_t &tag, const int
                 const uint64_t desc = __builtin_amdgcn_ballot_w64(lane > base && lane < base + len && key > prevk);
                 if (desc == 0ull) {
                     finished = true;
-                } else if (len >= 50) {  // it goes on to shift elements about: the serial routine (rare)
+                } else if (MAXN >= 50 && len >= 50) {  // it goes on to shift elements about: the serial routine (rare)
                     to_lds();
                     int done = 0;
                     if (lane == 0) done = partial_insertion_sort(spill + base, len) ? 1 : 0;
