@@ -37,6 +37,10 @@ from .api import (  # noqa: F401
     crf_beam_search_nbest,
     crf_beam_search_nbest_batch_raw,
     crf_greedy_search,
+    crf_align,
+    crf_align_batch_raw,
+    crf_score,
+    crf_score_batch_raw,
     AlignResult,
     ctc_align,
     ctc_align_batch_raw,

@@ -265,8 +265,13 @@ def beam_search(network_output, alphabet, beam_size=5, beam_cut_threshold=0.0,
     return seq, [int(p) for p in out.path[0, :n]]
 
 
-def crf_beam_search(network_output, init_state, alphabet, beam_size=5, beam_cut_threshold=0.0):
-    """Mirrors src/lib.rs:252-286 -> search.rs:38-157 (this wrapper validates only the alphabet)."""
+def crf_beam_search(network_output, init_state, alphabet, beam_size=5, beam_cut_threshold=0.0, *, qstring=False,
+                    qscale=1.0, qbias=0.0):
+    """Mirrors src/lib.rs:252-286 -> search.rs:38-157 (this wrapper validates only the alphabet).
+
+    qstring=True (not in the reference, whose CRF beam search has no qualities) appends one phred character per label,
+    as crf_greedy_search does: the posterior of each label's emission in the best alignment of the result
+    (crf_align_batch_raw; the whole lattice where it fits, a band of 64 labels around the search's path otherwise)."""
     x = _as_f32(network_output, 3, "network_output")
     init = _as_f32(init_state, 1, "init_state")
     beam_size = _usize(beam_size, "beam_size")
@@ -295,6 +300,14 @@ def crf_beam_search(network_output, init_state, alphabet, beam_size=5, beam_cut_
     labels = out.labels[0, :n]
     # search.rs:146-156: labels are appended leaf->root and the CHARACTERS reversed at the end
     seq = "".join(alpha[l] for l in labels[::-1])[::-1]
+    if qstring and n:
+        try:
+            al = crf_align_batch_raw(x[None], init[None], out.labels, out.out_len)
+        except nat.NativeError as e:
+            if e.code != nat.E_UNSUPPORTED:  # (refused before anything is staged: the whole lattice does not fit)
+                raise
+            al = crf_align_batch_raw(x[None], init[None], out.labels, out.out_len, paths=out.path, band=64)
+        seq += al.qstrings(out.out_len, qscale, qbias)[0][0]
     return seq, [int(p) for p in out.path[0, :n]]
 
 
@@ -819,6 +832,27 @@ class BatchResult:
                                    self.path if band else None, band, None, input_dtype,
                                    getattr(self, "_handle", None))
 
+    def crf_score(self, network_outputs, init_states, lengths=None, band=0, input_dtype=None):
+        """ln P(labelling | posteriors) under the CRF model of every read's result, float64 (n_reads, 1):
+        crf_score_batch_raw on this result's own arrays.  For the results of the CRF searches, with the (B,T,S,N)
+        posteriors and init rows they decoded (a session: the concatenated posteriors); plain CTC results are refused."""
+        if getattr(network_outputs, "ndim", 4) != 4:
+            raise ValueError("crf_score covers the results of the CRF searches, (n_reads, T, S, N) posteriors, not plain CTC results")
+        if band and self.path is None:
+            raise ValueError("a band needs the result's path")
+        return crf_score_batch_raw(network_outputs, init_states, self.labels, self.out_len, lengths,
+                                   self.path if band else None, band, None, input_dtype, getattr(self, "_handle", None))
+
+    def crf_align(self, network_outputs, init_states, lengths=None, band=0, input_dtype=None):
+        """The best alignment of every read's result under the CRF model -> AlignResult, arrays (n_reads, 1, stride):
+        crf_align_batch_raw on this result's own arrays.  Arguments as crf_score."""
+        if getattr(network_outputs, "ndim", 4) != 4:
+            raise ValueError("crf_align covers the results of the CRF searches, (n_reads, T, S, N) posteriors, not plain CTC results")
+        if band and self.path is None:
+            raise ValueError("a band needs the result's path")
+        return crf_align_batch_raw(network_outputs, init_states, self.labels, self.out_len, lengths,
+                                   self.path if band else None, band, None, input_dtype, getattr(self, "_handle", None))
+
     def sequences(self, alphabet, raise_on_error=True, paths="list"):
         """-> list of (str, path) per read, exactly what the single-read functions return.
 
@@ -1133,6 +1167,24 @@ class NBestResult:
                                    self.path if band else None, band, self.n_hyp, input_dtype,
                                    getattr(self, "_handle", None))
 
+    def crf_score(self, network_outputs, init_states, lengths=None, band=0, input_dtype=None):
+        """ln P(labelling | posteriors) under the CRF model of every hypothesis, float64 (n_reads, n_best); NaN where
+        i >= n_hyp[r].  crf_score_batch_raw on this result's own arrays; plain CTC results are refused."""
+        if not self.crf or getattr(network_outputs, "ndim", 4) != 4:
+            raise ValueError("crf_score covers the results of the CRF searches, not plain CTC results")
+        return crf_score_batch_raw(network_outputs, init_states, self.labels, self.out_len, lengths,
+                                   self.path if band else None, band, self.n_hyp, input_dtype,
+                                   getattr(self, "_handle", None))
+
+    def crf_align(self, network_outputs, init_states, lengths=None, band=0, input_dtype=None):
+        """The best alignment of every hypothesis under the CRF model -> AlignResult, arrays (n_reads, n_best, stride);
+        logp NaN and count 0 where i >= n_hyp[r].  crf_align_batch_raw on this result's own arrays."""
+        if not self.crf or getattr(network_outputs, "ndim", 4) != 4:
+            raise ValueError("crf_align covers the results of the CRF searches, not plain CTC results")
+        return crf_align_batch_raw(network_outputs, init_states, self.labels, self.out_len, lengths,
+                                   self.path if band else None, band, self.n_hyp, input_dtype,
+                                   getattr(self, "_handle", None))
+
     def hypotheses(self, alphabet, raise_on_error=True):
         """-> per read, a list of (seq, path, score), best first (None for a failed read when not raise_on_error)."""
         r = self.cpu()
@@ -1336,16 +1388,20 @@ def _check_band(band, paths):
     return int(band)
 
 
-def _lattice_inputs(network_outputs, labels, label_lengths, lengths, paths, band, n_valid, input_dtype, handle):
-    """The argument handling ctc_score_batch_raw and ctc_align_batch_raw share.  -> (handle, nat.Batch, nat.Labellings,
-    (B, n_hyp, stride), device or None for numpy input, the arrays the two structs point into)."""
+def _lattice_inputs(network_outputs, labels, label_lengths, lengths, paths, band, n_valid, input_dtype, handle,
+                    init_states=None):
+    """The argument handling ctc_score_batch_raw, ctc_align_batch_raw and their CRF counterparts share.  -> (handle,
+    nat.Batch, nat.Labellings, (B, n_hyp, stride), device or None for numpy input, the arrays the two structs point into);
+    init_states given (the CRF calls: (B, T, S, N) posteriors): the init rows (B, n_init) are the last of those arrays."""
+    crf = init_states is not None
+    nd = 4 if crf else 3
     dev_x = _device_tensor(network_outputs)
     if dev_x is not None:
         import torch
         x = dev_x
-        if x.ndim != 3:
-            raise ValueError("expected (n_reads, T, N) posteriors")
-        B, T, N = x.shape
+        if x.ndim != nd:
+            raise ValueError("expected (n_reads, T, S, N) posteriors" if crf else "expected (n_reads, T, N) posteriors")
+        B, T, N = x.shape[0], x.shape[1], x.shape[-1]
         dev = x.device
         h = handle if handle is not None else nat.default_handle(dev.index or 0)
 
@@ -1366,7 +1422,14 @@ def _lattice_inputs(network_outputs, labels, label_lengths, lengths, paths, band
         if nv is not None and nv.numel() != B:
             raise ValueError("n_valid must have shape (n_reads,)")
         st = x.stride()
-        b = nat.Batch(x.data_ptr(), B, T, 1, N, st[0], st[1], 0, st[2], None, _torch_dtype_code(x))
+        init = None
+        if crf:
+            init = torch.as_tensor(init_states, dtype=torch.float32, device=dev).contiguous()
+            if init.ndim != 2 or init.shape[0] != B or init.shape[1] < 1:
+                raise ValueError("init_states must have shape (n_reads, n_init)")
+            b = nat.Batch(x.data_ptr(), B, T, x.shape[2], N, st[0], st[1], st[2], st[3], None, _torch_dtype_code(x))
+        else:
+            b = nat.Batch(x.data_ptr(), B, T, 1, N, st[0], st[1], 0, st[2], None, _torch_dtype_code(x))
         if lengths is not None:
             lengths = torch.as_tensor(lengths, dtype=torch.int64, device=dev).contiguous()
             if lengths.numel() != B:
@@ -1375,10 +1438,10 @@ def _lattice_inputs(network_outputs, labels, label_lengths, lengths, paths, band
         y = nat.Labellings(lab.data_ptr(), ylen.data_ptr(), nv.data_ptr() if nv is not None else None,
                            pth.data_ptr() if pth is not None else None, n_hyp, stride)
         h.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-        return h, b, y, (B, n_hyp, stride), dev, (x, lab, ylen, pth, nv, lengths)
-    network_outputs, lengths = _ragged(network_outputs, lengths, 3)
-    x = _stack_host(network_outputs, 3)
-    B, T, N = x.shape
+        return h, b, y, (B, n_hyp, stride), dev, (x, lab, ylen, pth, nv, lengths, init)
+    network_outputs, lengths = _ragged(network_outputs, lengths, nd)
+    x = _stack_host(network_outputs, nd)
+    B, T, N = x.shape[0], x.shape[1], x.shape[-1]
     lab = np.ascontiguousarray(np.asarray(labels), np.uint8)
     n_hyp, stride = _score_shapes(lab.shape, B)
     ylen = np.ascontiguousarray(np.asarray(label_lengths), np.uint32)
@@ -1392,10 +1455,15 @@ def _lattice_inputs(network_outputs, labels, label_lengths, lengths, paths, band
         raise ValueError("n_valid must have shape (n_reads,)")
     h = nat.default_handle()  # (host arrays: the calling thread's own handle, whatever handle the search ran on)
     l = _np_lengths(lengths, B)
-    b = _host_batch(x, False, l, input_dtype)
+    init = None
+    if crf:
+        init = np.ascontiguousarray(np.asarray(init_states, np.float32))
+        if init.ndim != 2 or init.shape[0] != B or init.shape[1] < 1:
+            raise ValueError("init_states must have shape (n_reads, n_init)")
+    b = _host_batch(x, crf, l, input_dtype)
     y = nat.Labellings(lab.ctypes.data, ylen.ctypes.data, nv.ctypes.data if nv is not None else None,
                        pth.ctypes.data if pth is not None else None, n_hyp, stride)
-    return h, b, y, (B, n_hyp, stride), None, (x, lab, ylen, pth, nv, l)
+    return h, b, y, (B, n_hyp, stride), None, (x, lab, ylen, pth, nv, l, init)
 
 
 def ctc_score_batch_raw(network_outputs, labels, label_lengths, collapse_repeats=True, lengths=None, paths=None,
@@ -1528,6 +1596,121 @@ def ctc_align(network_output, sequence, alphabet, collapse_repeats=True):
     n = len(y)
     return ([(int(s), int(c)) for s, c in zip(r.start[0, 0, :n], r.count[0, 0, :n])],
             [float(q) for q in r.qual[0, 0, :n]], logp)
+
+
+# ---------------------------------------------------------------------------------------------
+# CRF scoring and forced alignment of given labellings (include/fcd.h, fcd_crf_score_* / fcd_crf_align_*)
+# ---------------------------------------------------------------------------------------------
+def crf_score_batch_raw(network_outputs, init_states, labels, label_lengths, lengths=None, paths=None, band=0,
+                        n_valid=None, input_dtype=None, handle=None):
+    """ln of the sum, over every alignment of labelling y to the rows of its read, of the product of the (B,T,S,N) CRF
+    posteriors along it, the model state following the labelling from the init row's first maximum as crf_beam_search's
+    does (include/fcd.h, fcd_crf_score_*).  -> (B, n_hyp) float64, comparable between the hypotheses of a read and
+    between reads.
+
+    labels / label_lengths / paths / band / n_valid as ctc_score_batch_raw; init_states (B, n_init).  band=0 scores the
+    whole lattice (labellings up to 511 labels), band=W > 0 the alignments within W labels of `paths` (W <= 255).
+    Device tensors in: a torch tensor on the same device, enqueued on torch's current stream, not synchronised.
+    numpy in: numpy out."""
+    band = _check_band(band, paths)
+    h, b, y, (B, n_hyp, stride), dev, keep = _lattice_inputs(network_outputs, labels, label_lengths, lengths, paths, band,
+                                                             n_valid, input_dtype, handle, init_states)
+    init = keep[-1]
+    if dev is not None:
+        import torch
+        out = torch.empty((B, n_hyp), dtype=torch.float64, device=dev)
+        h.check(h.lib.fcd_crf_score_dev(h.ptr, C.byref(b), C.c_void_p(init.data_ptr()), int(init.shape[1]),
+                                        int(init.shape[1]), C.byref(y), band, C.c_void_p(out.data_ptr())))
+        return out
+    out = np.empty((B, n_hyp), np.float64)
+    h.check(h.lib.fcd_crf_score_host(h.ptr, C.byref(b), init.ctypes.data, init.shape[1], init.shape[1], C.byref(y), band,
+                                     out.ctypes.data))
+    return out
+
+
+def crf_align_batch_raw(network_outputs, init_states, labels, label_lengths, lengths=None, paths=None, band=0,
+                        n_valid=None, input_dtype=None, handle=None):
+    """The best single alignment of every labelling under the CRF model: the row each label is emitted at (start; count
+    is 1), the posterior of that emission (qual: what crf_greedy_search turns into its quality string) and ln of the
+    alignment's probability (include/fcd.h, fcd_crf_align_*).  -> AlignResult, arrays (B, n_hyp, stride) and logp
+    (B, n_hyp).  Arguments as crf_score_batch_raw."""
+    band = _check_band(band, paths)
+    h, b, y, (B, n_hyp, stride), dev, keep = _lattice_inputs(network_outputs, labels, label_lengths, lengths, paths, band,
+                                                             n_valid, input_dtype, handle, init_states)
+    init = keep[-1]
+    if dev is not None:
+        import torch
+        start = torch.zeros((B, n_hyp, stride), dtype=torch.int32, device=dev)
+        count = torch.zeros((B, n_hyp, stride), dtype=torch.int32, device=dev)
+        qual = torch.zeros((B, n_hyp, stride), dtype=torch.float32, device=dev)
+        logp = torch.empty((B, n_hyp), dtype=torch.float64, device=dev)
+        out = nat.Alignment(start.data_ptr(), count.data_ptr(), qual.data_ptr(), logp.data_ptr())
+        h.check(h.lib.fcd_crf_align_dev(h.ptr, C.byref(b), C.c_void_p(init.data_ptr()), int(init.shape[1]),
+                                        int(init.shape[1]), C.byref(y), band, C.byref(out)))
+        return AlignResult(start, count, qual, logp)
+    start = np.zeros((B, n_hyp, stride), np.uint32)
+    count = np.zeros((B, n_hyp, stride), np.uint32)
+    qual = np.zeros((B, n_hyp, stride), np.float32)
+    logp = np.empty((B, n_hyp), np.float64)
+    out = nat.Alignment(start.ctypes.data, count.ctypes.data, qual.ctypes.data, logp.ctypes.data)
+    h.check(h.lib.fcd_crf_align_host(h.ptr, C.byref(b), init.ctypes.data, init.shape[1], init.shape[1], C.byref(y), band,
+                                     C.byref(out)))
+    return AlignResult(start, count, qual, logp)
+
+
+def _crf_sequence_labels(sequence, alpha, what):
+    """The labels behind a string crf_beam_search built: it joins the labels' strings leaf to root and reverses the
+    CHARACTERS (src/search.rs:146-156), so a multi-character label appears reversed."""
+    if not isinstance(sequence, str):
+        raise TypeError("argument 'sequence': expected str")
+    index = {}
+    for i, a in enumerate(alpha):
+        if i > 0 and a:
+            index.setdefault(a[::-1], i)
+    width = sorted({len(a) for a in index}, reverse=True)
+    out, pos = [], 0
+    while pos < len(sequence):
+        for w in width:  # (the longest label first: an alphabet whose labels prefix one another is read greedily)
+            lab = index.get(sequence[pos:pos + w])
+            if lab is not None:
+                out.append(lab)
+                pos += w
+                break
+        else:
+            raise ValueError("%s: sequence holds %r, which is not a label of the alphabet" % (what, sequence[pos]))
+    return out
+
+
+def _crf_one_read(network_output, init_state, sequence, alphabet, what):
+    x = _as_f32(network_output, 3, "network_output")
+    init = _as_f32(init_state, 1, "init_state")
+    alpha = _seq_to_vec(alphabet)
+    _check_greedy_alphabet(len(alpha), x.shape[2])
+    if init.size == 0:
+        raise RuntimeError("init_state is empty")
+    y = _crf_sequence_labels(sequence, alpha, what)
+    lab = np.zeros((1, max(len(y), 1)), np.uint8)
+    lab[0, :len(y)] = y
+    return _dense(x)[None], np.ascontiguousarray(init)[None], lab, np.array([len(y)], np.uint32), len(y)
+
+
+def crf_score(network_output, init_state, sequence, alphabet):
+    """ln P(sequence | network_output) under the CRF model: every alignment of one string (as crf_beam_search returns
+    it) to one (T, S, N) float32 posterior array, exact, as a float.  More than 511 labels: RuntimeError."""
+    x, init, lab, n, _ = _crf_one_read(network_output, init_state, sequence, alphabet, "crf_score")
+    return float(crf_score_batch_raw(x, init, lab, n)[0, 0])
+
+
+def crf_align(network_output, init_state, sequence, alphabet):
+    """The best alignment of one string to one (T, S, N) float32 posterior array under the CRF model, exact:
+    -> (rows, quals, logp), the row each label is emitted at, the posterior of that emission and ln of the alignment's
+    probability.  No alignment: ([], [], -inf or NaN).  More than 511 labels: RuntimeError."""
+    x, init, lab, n, L = _crf_one_read(network_output, init_state, sequence, alphabet, "crf_align")
+    r = crf_align_batch_raw(x, init, lab, n)
+    logp = float(r.logp[0, 0])
+    if not np.isfinite(logp):
+        return [], [], logp
+    return [int(s) for s in r.start[0, 0, :L]], [float(q) for q in r.qual[0, 0, :L]], logp
 
 
 # ---------------------------------------------------------------------------------------------

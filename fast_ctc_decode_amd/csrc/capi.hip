@@ -1773,6 +1773,188 @@ int fcd_ctc_align_host(fcd_handle *h, const fcd_batch *in, const fcd_labellings 
     return FCD_OK;
 }
 
+// ---- the lattice of given labellings under a CRF model (crf_lattice.hip) ----
+// (shared by fcd_crf_score_* and fcd_crf_align_*, whose `out` is its start array)
+static int crf_lattice_check(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init, int64_t init_stride,
+                             const fcd_labellings *y, int64_t band, const void *out, const char *null_msg) {
+    int rc = check_batch(h, in, true);
+    if (rc) return rc;
+    if (!init || n_init < 1) return fail(h, FCD_E_INVALID, "init_state missing");
+    if (init_stride < 0) return fail(h, FCD_E_INVALID, "negative stride");
+    if (!y) return fail(h, FCD_E_INVALID, "null labellings");
+    if (y->n_hyp < 1) return fail(h, FCD_E_INVALID, "n_hyp must be >= 1");
+    if (band < 0) return fail(h, FCD_E_INVALID, "band must be >= 0");
+    if (band > 0 && !y->path) return fail(h, FCD_E_INVALID, "a band needs the labellings' path");
+    if (y->stride < 0) return fail(h, FCD_E_INVALID, "negative stride");
+    if (in->n_reads > 0 && (!y->labels || !y->len || !out)) return fail(h, FCD_E_INVALID, null_msg);
+    if (in->n_reads * y->n_hyp >= (1ll << 31)) return fail(h, FCD_E_UNSUPPORTED, "more than 2^31 labellings in one call");
+    switch (crf_lattice_unsupported(in->T, in->S, y->stride, std::min<int64_t>(band, 1ll << 28))) {
+    case 1: return fail(h, FCD_E_UNSUPPORTED, band > 0 ? "crf lattice: the band's window exceeds 512 states: use a narrower band"
+                                                       : "crf lattice: the exact lattice exceeds 512 states: use a band");
+    case 2: return fail(h, FCD_E_UNSUPPORTED, "crf lattice: S must be below 2^24 - 1");
+    case 3: return fail(h, FCD_E_UNSUPPORTED, "crf lattice: labellings beyond 15263 labels do not fit the 64 KiB of LDS: use a smaller stride");
+    default: return FCD_OK;
+    }
+}
+
+int fcd_crf_score_dev(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init, int64_t init_stride,
+                      const fcd_labellings *y, int64_t band, double *logp) {
+    if (!h) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> g(h->mu);
+    int rc = crf_lattice_check(h, in, init, n_init, init_stride, y, band, logp, "null labels/len/logp");
+    if (rc) return rc;
+    if (in->n_reads == 0) return FCD_OK;
+    FCD_DEVICE(h);
+    const size_t n_rows = (size_t)in->n_reads * (size_t)y->n_hyp;
+    CallScope sc(h);
+    sc.add(y->labels, n_rows * (size_t)y->stride);
+    sc.add(y->len, n_rows * 4);
+    sc.add(y->n_valid, (size_t)in->n_reads * 4);
+    sc.add(y->path, n_rows * (size_t)y->stride * 4);
+    sc.add(logp, n_rows * 8);
+    rc = sc.begin(false, false);
+    if (rc) return rc;
+    const ScoreDesc yd{y->labels, y->len, y->n_valid, band > 0 ? y->path : nullptr, y->n_hyp, y->stride};
+    sc.time();
+    FCD_HIP(h, launch_crf_score(to_desc(in, true), yd, init, n_init, init_stride, std::min<int64_t>(band, 1ll << 28), logp, sc.stream));
+    return sc.finish();
+}
+
+int fcd_crf_align_dev(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init, int64_t init_stride,
+                      const fcd_labellings *y, int64_t band, const fcd_alignment *out) {
+    if (!h) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> g(h->mu);
+    if (!out) return fail(h, FCD_E_INVALID, "null alignment");
+    int rc = crf_lattice_check(h, in, init, n_init, init_stride, y, band, out->start, "null labels/len/start");
+    if (rc) return rc;
+    if (in->n_reads > 0 && !out->count) return fail(h, FCD_E_INVALID, "null count");
+    if (in->n_reads == 0) return FCD_OK;
+    FCD_DEVICE(h);
+    const size_t n_rows = (size_t)in->n_reads * (size_t)y->n_hyp, cells = n_rows * (size_t)y->stride;
+    // the back-pointers: whole reads per launch, as many as the cap holds (at least one), every launch in the same memory
+    const int64_t bnd = std::min<int64_t>(band, 1ll << 28);
+    const size_t row_bytes = crf_align_row_bytes(in->T, y->stride, bnd);
+    const int64_t cap = h->align_ws_cap > 0 ? h->align_ws_cap : std::min<int64_t>(4ll << 30, workspace_budget(h));
+    const int64_t read_bytes = (int64_t)(row_bytes * (size_t)y->n_hyp);
+    const int64_t group = std::max<int64_t>(1, std::min<int64_t>(in->n_reads, cap / read_bytes));
+    const size_t o_logp = (size_t)group * (size_t)read_bytes;
+    CallScope sc(h);
+    sc.add(y->labels, cells);
+    sc.add(y->len, n_rows * 4);
+    sc.add(y->n_valid, (size_t)in->n_reads * 4);
+    sc.add(y->path, cells * 4);
+    sc.add(out->start, cells * 4);
+    sc.add(out->count, cells * 4);
+    sc.add(out->qual, cells * 4);
+    sc.add(out->logp, n_rows * 8);
+    rc = sc.begin(false, true);  // (exclusive: the workspace from its start, behind every overlapping call in flight)
+    if (rc) return rc;
+    char *ws = nullptr;
+    rc = sc.arena(o_logp + (out->logp ? 0 : n_rows * 8), &ws);
+    if (rc) return rc;
+    double *logp = out->logp ? out->logp : reinterpret_cast<double *>(ws + o_logp);
+    const int64_t esz = in->dtype == FCD_DTYPE_F32 ? 4 : 2;
+    sc.time();
+    for (int64_t r0 = 0; r0 < in->n_reads; r0 += group) {
+        const int64_t row0 = r0 * y->n_hyp;
+        BatchDesc d = to_desc(in, true);
+        d.post = reinterpret_cast<const float *>(reinterpret_cast<const char *>(in->post) + r0 * in->stride_read * esz);
+        d.lengths = in->lengths ? in->lengths + r0 : nullptr;
+        d.n_reads = std::min(group, in->n_reads - r0);
+        const ScoreDesc yd{y->labels + row0 * y->stride, y->len + row0, y->n_valid ? y->n_valid + r0 : nullptr,
+                           band > 0 ? y->path + row0 * y->stride : nullptr, y->n_hyp, y->stride};
+        const AlignOut od{out->start + row0 * y->stride, out->count + row0 * y->stride,
+                          out->qual ? out->qual + row0 * y->stride : nullptr, logp + row0};
+        FCD_HIP(h, launch_crf_align(d, yd, init + r0 * init_stride, n_init, init_stride, bnd, od,
+                                    reinterpret_cast<unsigned char *>(ws), sc.stream));
+    }
+    return sc.finish();
+}
+
+// host staging of fcd_crf_score_host / fcd_crf_align_host: out == nullptr scores into logp
+static int crf_lattice_host(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init, int64_t init_stride,
+                            const fcd_labellings *y, int64_t band, double *logp, const fcd_alignment *out) {
+    if (in->stride_read < 0 || in->stride_t < 0 || in->stride_s < 0 || in->stride_n < 0)
+        return fail(h, FCD_E_INVALID, "negative stride");
+    FCD_DEVICE(h);
+    const size_t B = (size_t)in->n_reads, n_rows = B * (size_t)y->n_hyp, esz = in->dtype == FCD_DTYPE_F32 ? 4 : 2;
+    const size_t cells = n_rows * (size_t)y->stride;
+    // the posteriors keep their strides: the span from the first to the last addressed element is staged as it is
+    const size_t span = in->T > 0 ? (size_t)((in->n_reads - 1) * in->stride_read + (in->T - 1) * in->stride_t +
+                                             (in->S - 1) * in->stride_s + (in->N - 1) * in->stride_n + 1) : 0;
+    const size_t init_span = (size_t)((in->n_reads - 1) * init_stride + n_init);
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t o_in = 0, o_init = o_in + al(span * esz), o_len = o_init + al(init_span * 4), o_lab = o_len + al(B * 8);
+    const size_t o_ylen = o_lab + al(cells), o_nv = o_ylen + al(n_rows * 4);
+    const size_t o_path = o_nv + al(B * 4), o_start = o_path + (band > 0 ? al(cells * 4) : 0);
+    const size_t o_count = o_start + (out ? al(cells * 4) : 0), o_qual = o_count + (out ? al(cells * 4) : 0);
+    const size_t o_out = o_qual + (out ? al(cells * 4) : 0);
+    const size_t total = o_out + al(n_rows * 8);
+    int rc = ensure(h, &h->stage, &h->stage_bytes, total);
+    if (rc) return rc;
+    char *d = reinterpret_cast<char *>(h->stage);
+    if (span) FCD_HIP(h, hipMemcpyAsync(d + o_in, in->post, span * esz, hipMemcpyHostToDevice, h->stream));
+    FCD_HIP(h, hipMemcpyAsync(d + o_init, init, init_span * 4, hipMemcpyHostToDevice, h->stream));
+    if (in->lengths) FCD_HIP(h, hipMemcpyAsync(d + o_len, in->lengths, B * 8, hipMemcpyHostToDevice, h->stream));
+    if (y->stride) FCD_HIP(h, hipMemcpyAsync(d + o_lab, y->labels, cells, hipMemcpyHostToDevice, h->stream));
+    FCD_HIP(h, hipMemcpyAsync(d + o_ylen, y->len, n_rows * 4, hipMemcpyHostToDevice, h->stream));
+    if (y->n_valid) FCD_HIP(h, hipMemcpyAsync(d + o_nv, y->n_valid, B * 4, hipMemcpyHostToDevice, h->stream));
+    if (band > 0 && y->stride)
+        FCD_HIP(h, hipMemcpyAsync(d + o_path, y->path, cells * 4, hipMemcpyHostToDevice, h->stream));
+    // (entries the kernel does not write -- k >= len -- come back as 0)
+    if (out && o_out > o_start) FCD_HIP(h, hipMemsetAsync(d + o_start, 0, o_out - o_start, h->stream));
+    fcd_batch din = *in;
+    din.post = d + o_in;
+    din.lengths = in->lengths ? reinterpret_cast<const int64_t *>(d + o_len) : nullptr;
+    fcd_labellings dy = *y;
+    dy.labels = reinterpret_cast<const uint8_t *>(d + o_lab);
+    dy.len = reinterpret_cast<const uint32_t *>(d + o_ylen);
+    dy.n_valid = y->n_valid ? reinterpret_cast<const uint32_t *>(d + o_nv) : nullptr;
+    dy.path = band > 0 ? reinterpret_cast<const uint32_t *>(d + o_path) : nullptr;
+    const float *dinit = reinterpret_cast<const float *>(d + o_init);
+    if (!out) {
+        rc = fcd_crf_score_dev(h, &din, dinit, n_init, init_stride, &dy, band, reinterpret_cast<double *>(d + o_out));
+        if (rc) return rc;
+        FCD_HIP(h, hipMemcpyAsync(logp, d + o_out, n_rows * 8, hipMemcpyDeviceToHost, h->stream));
+    } else {
+        const fcd_alignment dout{reinterpret_cast<uint32_t *>(d + o_start), reinterpret_cast<uint32_t *>(d + o_count),
+                                 out->qual ? reinterpret_cast<float *>(d + o_qual) : nullptr,
+                                 out->logp ? reinterpret_cast<double *>(d + o_out) : nullptr};
+        rc = fcd_crf_align_dev(h, &din, dinit, n_init, init_stride, &dy, band, &dout);
+        if (rc) return rc;
+        if (cells) {
+            FCD_HIP(h, hipMemcpyAsync(out->start, d + o_start, cells * 4, hipMemcpyDeviceToHost, h->stream));
+            FCD_HIP(h, hipMemcpyAsync(out->count, d + o_count, cells * 4, hipMemcpyDeviceToHost, h->stream));
+            if (out->qual) FCD_HIP(h, hipMemcpyAsync(out->qual, d + o_qual, cells * 4, hipMemcpyDeviceToHost, h->stream));
+        }
+        if (out->logp) FCD_HIP(h, hipMemcpyAsync(out->logp, d + o_out, n_rows * 8, hipMemcpyDeviceToHost, h->stream));
+    }
+    FCD_HIP(h, hipStreamSynchronize(h->stream));
+    return FCD_OK;
+}
+
+int fcd_crf_score_host(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init, int64_t init_stride,
+                       const fcd_labellings *y, int64_t band, double *logp) {
+    if (!h) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> whole_call(h->mu);  // staging .. copy-back, see run_host
+    int rc = crf_lattice_check(h, in, init, n_init, init_stride, y, band, logp, "null labels/len/logp");
+    if (rc) return rc;
+    if (in->n_reads == 0) return FCD_OK;
+    return crf_lattice_host(h, in, init, n_init, init_stride, y, band, logp, nullptr);
+}
+
+int fcd_crf_align_host(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init, int64_t init_stride,
+                       const fcd_labellings *y, int64_t band, const fcd_alignment *out) {
+    if (!h) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> whole_call(h->mu);
+    if (!out) return fail(h, FCD_E_INVALID, "null alignment");
+    int rc = crf_lattice_check(h, in, init, n_init, init_stride, y, band, out->start, "null labels/len/start");
+    if (rc) return rc;
+    if (in->n_reads > 0 && !out->count) return fail(h, FCD_E_INVALID, "null count");
+    if (in->n_reads == 0) return FCD_OK;
+    return crf_lattice_host(h, in, init, n_init, init_stride, y, band, nullptr, out);
+}
+
 }  // extern "C"
 
 // ---- *_host: stage host buffers through device memory, run the *_dev path, copy back -------

@@ -250,6 +250,17 @@ struct AlignOut {
 size_t ctc_align_row_bytes(int64_t T, int64_t stride, int64_t band);
 hipError_t launch_ctc_align(const BatchDesc &in, const ScoreDesc &y, int collapse, int64_t band, const AlignOut &out,
                             unsigned char *bp, hipStream_t stream);
+// The lattice of given labellings under a CRF model (crf_lattice.hip; fcd_crf_score_* / fcd_crf_align_* in include/fcd.h).
+// crf_lattice_unsupported: 0 = the kernels hold the call; 1 = the window exceeds the 512 register-resident states,
+// 2 = S beyond the 24-bit state word, 3 = the labelling's LDS copy (4 bytes per state) exceeds 64 KiB.
+// bp: crf_align_row_bytes() of device memory per labelling of the launch; out.logp must not be null.
+int64_t crf_lattice_window_states(int64_t T, int64_t stride, int64_t band);
+int crf_lattice_unsupported(int64_t T, int64_t S, int64_t stride, int64_t band);
+size_t crf_align_row_bytes(int64_t T, int64_t stride, int64_t band);
+hipError_t launch_crf_score(const BatchDesc &in, const ScoreDesc &y, const float *init, int64_t n_init, int64_t init_stride,
+                            int64_t band, double *logp, hipStream_t stream);
+hipError_t launch_crf_align(const BatchDesc &in, const ScoreDesc &y, const float *init, int64_t n_init, int64_t init_stride,
+                            int64_t band, const AlignOut &out, unsigned char *bp, hipStream_t stream);
 
 hipError_t launch_logspace_probe(const float *a, const float *b, float *out_add, float *out_ln,
                                  int64_t n, int mode, hipStream_t stream);

@@ -426,6 +426,55 @@ int fcd_ctc_align_dev(fcd_handle *h, const fcd_batch *in, const fcd_labellings *
 int fcd_ctc_align_host(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int collapse_repeats, int64_t band,
                        const fcd_alignment *out);
 
+/* ---- CRF scoring and forced alignment of given labellings (csrc/crf_lattice.hip) ----
+ * NOT reference functions.  The lattice of a GIVEN labelling under a CRF model -- the recurrence search::crf_beam_search
+ * walks (src/search.rs:62-100), unpruned and unmerged, for one labelling -- walked forward as a sum (score) and as a max with
+ * traceback (align).  Batch (n_reads, T, S, N) as fcd_batch describes it: any strides, f32 / f16 / bf16 (converted to f32
+ * exactly), ragged lengths.  init: [n_reads * init_stride] f32, n_init entries used per read, as fcd_crf_beam_search_*.
+ * A labelling y of L labels in 1 .. N-1; nb = N - 1.
+ * State trajectory: sigma_0 = the index of the FIRST maximum of the read's init row (src/search.rs:58,404; a NaN counts
+ *   as -inf); sigma_{k+1} = (sigma_k * nb) mod S + (y_k - 1) (:97,414).  It depends on init and y only.
+ * Reading rule: P(t, k, j) = p[t][sigma_k][j]; where sigma_k lies outside 0 .. S-1 (S = 5, N = 4 gets there) P reads as 0
+ *   and nothing is read out of bounds: such a state is a dead end, except as the final state entered at the last row.
+ * Lattice: states k = 0 .. L, the labels emitted so far; no repeat-collapsing (a CRF has none).
+ *   alpha_{-1}[0] = 1;  alpha_t[k] = alpha_{t-1}[k] * P(t,k,0) + alpha_{t-1}[k-1] * P(t,k-1,y_{k-1})
+ *   crf_score = ln alpha_{T_r-1}[L], float64.  The init probabilities do not enter: the search's start value
+ *   max(init) + init[0] is a common factor of all hypotheses of a read.
+ * Alignment: the strictly increasing emission rows e_0 < ... < e_{L-1} that maximise the product (max where the score has
+ *   +).  Label k: start[k] = e_k, count[k] = 1, qual[k] = P(e_k, k, y_k) -- what crf_greedy_search feeds to phred (:412-413);
+ *   logp = ln of the product, float64.  Ties: the stay candidate is kept unless the advance candidate is strictly greater.
+ * Arithmetic: f32 with an unbounded exponent, rows rescaled by exact powers of two; each of the two candidates of a cell is
+ *   ONE product with one rounding, the score's sum a third; no fused multiply-add; ln(m) + E ln 2 in float64.  |error| of
+ *   the score <= about 3 T_r 2^-24 nats.  A cell below 2^-160 of its row's maximum may be dropped.
+ * band = 0: the whole lattice.  band = W >= 1 (needs y->path, ascending): with k(t) = #{k : path[k] <= t}, only the states
+ *   max(0, k(t) - W) <= k <= min(L, k(t) + W) are live at row t; the window is also cut to what can be reached (k <= t + 1)
+ *   and can still reach the end (k >= L - (T_r - 1 - t)), which changes no result.  Score: a lower bound that rises with W;
+ *   align: the best alignment inside the window.
+ * Rows without a value, tested in this order: i >= n_valid[r], len > stride, a label outside 1 .. N-1: NaN; T_r = 0: 0.0 for
+ *   L = 0, else -inf; L > T_r: -inf; score: a NaN in a contributing cell: NaN; align: a NaN, infinite or negative value among
+ *   the values that enter a live cell (P(t,k,0) into cell k, P(t,k,y_k) into cell k + 1, both cells live at row t): NaN --
+ *   not "anywhere in the read" as fcd_ctc_align_*: scanning S * N values a row would defeat the gather; no alignment: -inf.
+ *   In all align cases without an alignment count = 0 is written for k < min(len, stride), start / qual are left alone.
+ *   L = 0: logp = sum_t ln P(t,0,0), nothing else is written.  Entries k >= len: never written by _dev, 0 from _host.
+ * Limits (FCD_E_UNSUPPORTED): the widest possible window, min(2 band + 1, min(T, stride) + 1) states, lives in registers:
+ *   up to 512 states ("use a band" beyond: exact alignment up to 511 labels); S < 2^24 - 1; min(T, stride) <= 15263 (the
+ *   labelling and its trajectory live in 64 KiB of LDS).  S = 1024 and 4096 are ordinary shapes: rows of more than 1024
+ *   values are gathered from global memory instead of being staged.
+ * FCD_E_INVALID before anything is enqueued or written: band < 0, band > 0 without path, n_hyp < 1, S < 1, null init or
+ *   n_init < 1, null start / count, null out / logp.
+ * _dev: device pointers, enqueue-only on the handle's stream (never on the fcd_set_overlap internal streams), behind
+ *   overlapping searches in flight that still write the arrays it reads.  Align keeps one back-pointer bit per row and
+ *   slot (8, 16, 32 or 64 bytes a row) in the handle's workspace and launches groups of whole reads that fit 4 GiB of it.
+ * _host: host pointers; stages, runs and copies back in one piece. */
+int fcd_crf_score_dev(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init, int64_t init_stride,
+                      const fcd_labellings *y, int64_t band, double *logp);
+int fcd_crf_score_host(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init, int64_t init_stride,
+                       const fcd_labellings *y, int64_t band, double *logp);
+int fcd_crf_align_dev(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init, int64_t init_stride,
+                      const fcd_labellings *y, int64_t band, const fcd_alignment *out);
+int fcd_crf_align_host(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init, int64_t init_stride,
+                       const fcd_labellings *y, int64_t band, const fcd_alignment *out);
+
 /* ---- search::crf_greedy_search (src/search.rs:385-423) ---- */
 int fcd_crf_greedy_search_dev(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init,
                               int64_t init_stride, const fcd_result *out);
