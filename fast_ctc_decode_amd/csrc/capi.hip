@@ -615,6 +615,70 @@ int64_t span_elems(const fcd_batch *in, bool crf) {
     return s;
 }
 
+// The staging buffer of one *_host call: the host arrays the call ships to the device and back, each 256-byte aligned in
+// h->stage, all on the handle's stream.  in() / out() name them, then commit() sizes the buffer and enqueues the uploads
+// and the zero-fills; only then at() gives device addresses (ensure may move the buffer); fetch() after the device call
+// copies the outputs back and waits.  A null host array takes no room and stays null on the device: the kernels branch
+// on it.  An empty one keeps an address (the *_dev checks refuse null arrays) and is never copied.
+class Staging {
+  public:
+    explicit Staging(fcd_handle *h) : h_(h) {}
+    int in(const void *host, size_t bytes) { return put(const_cast<void *>(host), bytes, kIn); }
+    int out(void *host, size_t bytes, bool zeroed = false) { return put(host, bytes, zeroed ? kOutZeroed : kOut); }
+
+    int commit() {
+        fcd_handle *h = h_;
+        int rc = ensure(h, &h->stage, &h->stage_bytes, used_);
+        if (rc) return rc;
+        char *base = static_cast<char *>(h->stage);
+        for (const Array &a : a_)
+            if (a.kind == kIn && a.bytes) FCD_HIP(h, hipMemcpyAsync(base + a.off, a.host, a.bytes, hipMemcpyHostToDevice, h->stream));
+        // (outputs zeroed next to one another: one fill, padding included)
+        for (size_t i = 0; i < a_.size(); ++i) {
+            if (a_[i].kind != kOutZeroed) continue;
+            size_t last = i;
+            while (last + 1 < a_.size() && a_[last + 1].kind == kOutZeroed) ++last;
+            const size_t n = a_[last].off + a_[last].bytes - a_[i].off;
+            if (n) FCD_HIP(h, hipMemsetAsync(base + a_[i].off, 0, n, h->stream));
+            i = last;
+        }
+        return FCD_OK;
+    }
+
+    template <class T>
+    T *at(int id) const {
+        return id < 0 ? nullptr : reinterpret_cast<T *>(static_cast<char *>(h_->stage) + a_[id].off);
+    }
+
+    int fetch() {
+        fcd_handle *h = h_;
+        char *base = static_cast<char *>(h->stage);
+        for (const Array &a : a_)
+            if (a.kind != kIn && a.bytes) FCD_HIP(h, hipMemcpyAsync(a.host, base + a.off, a.bytes, hipMemcpyDeviceToHost, h->stream));
+        FCD_HIP(h, hipStreamSynchronize(h->stream));
+        return FCD_OK;
+    }
+
+  private:
+    enum Kind { kIn, kOut, kOutZeroed };
+    struct Array {
+        void *host;
+        size_t off, bytes;
+        Kind kind;
+    };
+    fcd_handle *h_;
+    std::vector<Array> a_;
+    size_t used_ = 0;
+
+    int put(void *host, size_t bytes, Kind kind) {  // -> what at() takes; -1: null
+        if (!host) return -1;
+        const size_t off = (used_ + 255) & ~(size_t)255;
+        used_ = off + bytes;
+        a_.push_back({host, off, bytes, kind});
+        return (int)a_.size() - 1;
+    }
+};
+
 }  // namespace
 
 namespace fcd {
@@ -1227,92 +1291,60 @@ int duplex_host(fcd_handle *h, const fcd_batch *in1, const fcd_batch *in2, const
     if (!h) return FCD_E_INVALID;
     std::lock_guard<std::recursive_mutex> whole_call(h->mu);  // staging .. copy-back, see run_host
     const bool is_crf = crf != nullptr;
-    {
-        std::lock_guard<std::recursive_mutex> g(h->mu);
-        int rc = check_batch(h, in1, is_crf);
-        if (rc) return rc;
-        rc = check_batch(h, in2, is_crf);
-        if (rc) return rc;
-        if (in1->n_reads != in2->n_reads) return fail(h, FCD_E_INVALID, "pair counts differ");
-        if (!out || !envelope) return fail(h, FCD_E_INVALID, "null result/envelope");
-        if (in1->stride_read < 0 || in1->stride_t < 0 || in1->stride_n < 0 || in2->stride_read < 0 ||
-            in2->stride_t < 0 || in2->stride_n < 0 || (is_crf && (in1->stride_s < 0 || in2->stride_s < 0)))
-            return fail(h, FCD_E_UNSUPPORTED, "negative strides: pass a contiguous copy");
-        if (is_crf && (!crf->init1 || !crf->init2 || crf->n1 < 1 || crf->n2 < 1))
-            return fail(h, FCD_E_INVALID, "init_state missing");
-    }
+    int rc = check_batch(h, in1, is_crf);
+    if (rc) return rc;
+    rc = check_batch(h, in2, is_crf);
+    if (rc) return rc;
+    if (in1->n_reads != in2->n_reads) return fail(h, FCD_E_INVALID, "pair counts differ");
+    if (!out || !envelope) return fail(h, FCD_E_INVALID, "null result/envelope");
+    if (in1->stride_read < 0 || in1->stride_t < 0 || in1->stride_n < 0 || in2->stride_read < 0 ||
+        in2->stride_t < 0 || in2->stride_n < 0 || (is_crf && (in1->stride_s < 0 || in2->stride_s < 0)))
+        return fail(h, FCD_E_UNSUPPORTED, "negative strides: pass a contiguous copy");
+    if (is_crf && (!crf->init1 || !crf->init2 || crf->n1 < 1 || crf->n2 < 1))
+        return fail(h, FCD_E_INVALID, "init_state missing");
     const int64_t B = in1->n_reads;
     if (B == 0) return FCD_OK;
     if (!out->labels || !out->out_len || !out->status) return fail(h, FCD_E_INVALID, "null output array");
     FCD_DEVICE(h);  // staging, search and copy-back all run on the handle's device
-    const size_t e1 = (size_t)span_elems(in1, is_crf), e2 = (size_t)span_elems(in2, is_crf);
-    const size_t n_env = (size_t)B * (size_t)env_stride * 2;
-    const size_t n_out = (size_t)B * (size_t)out->out_stride;
-    const size_t ni1 = is_crf ? (size_t)((B - 1) * crf->s1 + crf->n1) : 0;
-    const size_t ni2 = is_crf ? (size_t)((B - 1) * crf->s2 + crf->n2) : 0;
-    size_t used = 0;
-    auto reserve = [&](size_t bytes) {
-        size_t off = (used + 255) & ~(size_t)255;
-        used = off + std::max<size_t>(bytes, 8);
-        return off;
-    };
-    const size_t z1 = in1->dtype == FCD_DTYPE_F32 ? 4 : 2, z2 = in2->dtype == FCD_DTYPE_F32 ? 4 : 2;
-    const size_t o1 = reserve(e1 * z1), o2 = reserve(e2 * z2), oe = reserve(n_env * 8);
-    const size_t ol1 = reserve(in1->lengths ? (size_t)B * 8 : 0);
-    const size_t ol2 = reserve(in2->lengths ? (size_t)B * 8 : 0);
-    const size_t oi1 = reserve(ni1 * 4), oi2 = reserve(ni2 * 4);
-    const size_t olab = reserve(n_out), oolen = reserve((size_t)B * 4), ostat = reserve((size_t)B * 4);
-    const size_t oamb = reserve(out->ambiguous ? (size_t)B * 8 : 0);
-    {
-        std::lock_guard<std::recursive_mutex> g(h->mu);
-        int rc = ensure(h, &h->stage, &h->stage_bytes, used);
-        if (rc) return rc;
-        char *base = reinterpret_cast<char *>(h->stage);
-        if (e1) FCD_HIP(h, hipMemcpyAsync(base + o1, in1->post, e1 * z1, hipMemcpyHostToDevice, h->stream));
-        if (e2) FCD_HIP(h, hipMemcpyAsync(base + o2, in2->post, e2 * z2, hipMemcpyHostToDevice, h->stream));
-        FCD_HIP(h, hipMemcpyAsync(base + oe, envelope, n_env * 8, hipMemcpyHostToDevice, h->stream));
-        if (in1->lengths)
-            FCD_HIP(h, hipMemcpyAsync(base + ol1, in1->lengths, (size_t)B * 8, hipMemcpyHostToDevice, h->stream));
-        if (in2->lengths)
-            FCD_HIP(h, hipMemcpyAsync(base + ol2, in2->lengths, (size_t)B * 8, hipMemcpyHostToDevice, h->stream));
-        if (is_crf) {
-            FCD_HIP(h, hipMemcpyAsync(base + oi1, crf->init1, ni1 * 4, hipMemcpyHostToDevice, h->stream));
-            FCD_HIP(h, hipMemcpyAsync(base + oi2, crf->init2, ni2 * 4, hipMemcpyHostToDevice, h->stream));
-        }
-    }
-    char *base = reinterpret_cast<char *>(h->stage);
+    Staging st(h);
+    const int i_post1 = st.in(in1->post, (size_t)span_elems(in1, is_crf) * (in1->dtype == FCD_DTYPE_F32 ? 4 : 2));
+    const int i_post2 = st.in(in2->post, (size_t)span_elems(in2, is_crf) * (in2->dtype == FCD_DTYPE_F32 ? 4 : 2));
+    const int i_env = st.in(envelope, (size_t)B * (size_t)env_stride * 16);
+    const int i_len1 = st.in(in1->lengths, (size_t)B * 8);
+    const int i_len2 = st.in(in2->lengths, (size_t)B * 8);
+    const int i_init1 = is_crf ? st.in(crf->init1, (size_t)((B - 1) * crf->s1 + crf->n1) * 4) : -1;
+    const int i_init2 = is_crf ? st.in(crf->init2, (size_t)((B - 1) * crf->s2 + crf->n2) * 4) : -1;
+    const int i_lab = st.out(out->labels, (size_t)B * (size_t)out->out_stride);
+    const int i_olen = st.out(out->out_len, (size_t)B * 4);
+    const int i_stat = st.out(out->status, (size_t)B * 4);
+    const int i_amb = st.out(out->ambiguous, (size_t)B * 8);
+    rc = st.commit();
+    if (rc) return rc;
     fcd_batch d1 = *in1, d2 = *in2;
-    d1.post = reinterpret_cast<const float *>(base + o1);
-    d2.post = reinterpret_cast<const float *>(base + o2);
-    d1.lengths = in1->lengths ? reinterpret_cast<const int64_t *>(base + ol1) : nullptr;
-    d2.lengths = in2->lengths ? reinterpret_cast<const int64_t *>(base + ol2) : nullptr;
+    d1.post = st.at<char>(i_post1);
+    d2.post = st.at<char>(i_post2);
+    d1.lengths = st.at<int64_t>(i_len1);
+    d2.lengths = st.at<int64_t>(i_len2);
     fcd_result dout{};
-    dout.labels = reinterpret_cast<uint8_t *>(base + olab);
-    dout.out_len = reinterpret_cast<uint32_t *>(base + oolen);
-    dout.status = reinterpret_cast<int32_t *>(base + ostat);
+    dout.labels = st.at<uint8_t>(i_lab);
+    dout.out_len = st.at<uint32_t>(i_olen);
+    dout.status = st.at<int32_t>(i_stat);
     dout.out_stride = out->out_stride;
-    dout.ambiguous = out->ambiguous ? reinterpret_cast<uint32_t *>(base + oamb) : nullptr;
+    dout.ambiguous = st.at<uint32_t>(i_amb);
     CrfInit dc;
     if (is_crf) {
         dc = *crf;
-        dc.init1 = reinterpret_cast<const float *>(base + oi1);
-        dc.init2 = reinterpret_cast<const float *>(base + oi2);
+        dc.init1 = st.at<float>(i_init1);
+        dc.init2 = st.at<float>(i_init2);
     }
-    int rc = duplex_dev(h, &d1, &d2, is_crf ? &dc : nullptr, reinterpret_cast<const uint64_t *>(base + oe),
-                        env_stride, beam_size, beam_cut_threshold, collapse_repeats, logadd_mode, &dout);
+    rc = duplex_dev(h, &d1, &d2, is_crf ? &dc : nullptr, st.at<uint64_t>(i_env), env_stride, beam_size,
+                    beam_cut_threshold, collapse_repeats, logadd_mode, &dout);
     if (rc) return rc;
-    std::lock_guard<std::recursive_mutex> g(h->mu);
-    if (h->overlap_n >= 2) {  // (fcd_set_overlap: the search may sit on an internal stream; the copies below are in the handle's)
+    if (h->overlap_n >= 2) {  // (fcd_set_overlap: the search may sit on an internal stream; the copies back are in the handle's)
         rc = overlap_join(h, h->stream);
         if (rc) return rc;
     }
-    FCD_HIP(h, hipMemcpyAsync(out->labels, dout.labels, n_out, hipMemcpyDeviceToHost, h->stream));
-    FCD_HIP(h, hipMemcpyAsync(out->out_len, dout.out_len, (size_t)B * 4, hipMemcpyDeviceToHost, h->stream));
-    FCD_HIP(h, hipMemcpyAsync(out->status, dout.status, (size_t)B * 4, hipMemcpyDeviceToHost, h->stream));
-    if (out->ambiguous)
-        FCD_HIP(h, hipMemcpyAsync(out->ambiguous, dout.ambiguous, (size_t)B * 8, hipMemcpyDeviceToHost, h->stream));
-    FCD_HIP(h, hipStreamSynchronize(h->stream));
-    return FCD_OK;
+    return st.fetch();
 }
 }  // namespace
 
@@ -1412,40 +1444,20 @@ int fcd_duplex_envelope_host(fcd_handle *h, int64_t n_pairs,
     if (stride1 < T1cap || stride2 < T2cap || env_stride < T1cap) return fail(h, FCD_E_INVALID, "strides shorter than the reads");
     FCD_DEVICE(h);
     // one device slab: labels, paths, lengths, row counts of both reads, then the envelope
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_l1 = 0, o_l2 = o_l1 + al((size_t)n_pairs * stride1);
-    const size_t o_p1 = o_l2 + al((size_t)n_pairs * stride2), o_p2 = o_p1 + al((size_t)n_pairs * stride1 * 4);
-    const size_t o_n1 = o_p2 + al((size_t)n_pairs * stride2 * 4), o_n2 = o_n1 + al((size_t)n_pairs * 4);
-    const size_t o_t1 = o_n2 + al((size_t)n_pairs * 4), o_t2 = o_t1 + al((size_t)n_pairs * 8);
-    const size_t o_env = o_t2 + al((size_t)n_pairs * 8);
-    const size_t total = o_env + (size_t)n_pairs * env_stride * 16;
-    char *d = nullptr;
-    {
-        std::lock_guard<std::recursive_mutex> g(h->mu);
-        int rc = ensure(h, &h->stage, &h->stage_bytes, total);
-        if (rc) return rc;
-        d = reinterpret_cast<char *>(h->stage);
-        FCD_HIP(h, hipMemcpyAsync(d + o_l1, labels1, (size_t)n_pairs * stride1, hipMemcpyHostToDevice, h->stream));
-        FCD_HIP(h, hipMemcpyAsync(d + o_l2, labels2, (size_t)n_pairs * stride2, hipMemcpyHostToDevice, h->stream));
-        FCD_HIP(h, hipMemcpyAsync(d + o_p1, path1, (size_t)n_pairs * stride1 * 4, hipMemcpyHostToDevice, h->stream));
-        FCD_HIP(h, hipMemcpyAsync(d + o_p2, path2, (size_t)n_pairs * stride2 * 4, hipMemcpyHostToDevice, h->stream));
-        FCD_HIP(h, hipMemcpyAsync(d + o_n1, len1, (size_t)n_pairs * 4, hipMemcpyHostToDevice, h->stream));
-        FCD_HIP(h, hipMemcpyAsync(d + o_n2, len2, (size_t)n_pairs * 4, hipMemcpyHostToDevice, h->stream));
-        if (T1) FCD_HIP(h, hipMemcpyAsync(d + o_t1, T1, (size_t)n_pairs * 8, hipMemcpyHostToDevice, h->stream));
-        if (T2) FCD_HIP(h, hipMemcpyAsync(d + o_t2, T2, (size_t)n_pairs * 8, hipMemcpyHostToDevice, h->stream));
-        FCD_HIP(h, hipMemsetAsync(d + o_env, 0, (size_t)n_pairs * env_stride * 16, h->stream));
-    }
-    int rc = fcd_duplex_envelope_dev(
-        h, n_pairs, reinterpret_cast<uint8_t *>(d + o_l1), reinterpret_cast<uint32_t *>(d + o_p1),
-        reinterpret_cast<uint32_t *>(d + o_n1), stride1, T1 ? reinterpret_cast<int64_t *>(d + o_t1) : nullptr, T1cap,
-        reinterpret_cast<uint8_t *>(d + o_l2), reinterpret_cast<uint32_t *>(d + o_p2),
-        reinterpret_cast<uint32_t *>(d + o_n2), stride2, T2 ? reinterpret_cast<int64_t *>(d + o_t2) : nullptr, T2cap,
-        band, reinterpret_cast<uint64_t *>(d + o_env), env_stride);
+    Staging st(h);
+    const int i_l1 = st.in(labels1, (size_t)n_pairs * stride1), i_l2 = st.in(labels2, (size_t)n_pairs * stride2);
+    const int i_p1 = st.in(path1, (size_t)n_pairs * stride1 * 4), i_p2 = st.in(path2, (size_t)n_pairs * stride2 * 4);
+    const int i_n1 = st.in(len1, (size_t)n_pairs * 4), i_n2 = st.in(len2, (size_t)n_pairs * 4);
+    const int i_t1 = st.in(T1, (size_t)n_pairs * 8), i_t2 = st.in(T2, (size_t)n_pairs * 8);
+    const int i_env = st.out(envelope, (size_t)n_pairs * env_stride * 16, true);
+    int rc = st.commit();
     if (rc) return rc;
-    std::lock_guard<std::recursive_mutex> g(h->mu);
-    FCD_HIP(h, hipMemcpyAsync(envelope, d + o_env, (size_t)n_pairs * env_stride * 16, hipMemcpyDeviceToHost, h->stream));
-    FCD_HIP(h, hipStreamSynchronize(h->stream));
-    return FCD_OK;
+    rc = fcd_duplex_envelope_dev(h, n_pairs, st.at<uint8_t>(i_l1), st.at<uint32_t>(i_p1), st.at<uint32_t>(i_n1), stride1,
+                                 st.at<int64_t>(i_t1), T1cap, st.at<uint8_t>(i_l2), st.at<uint32_t>(i_p2),
+                                 st.at<uint32_t>(i_n2), stride2, st.at<int64_t>(i_t2), T2cap, band, st.at<uint64_t>(i_env),
+                                 env_stride);
+    if (rc) return rc;
+    return st.fetch();
 }
 
 int fcd_logspace_probe_dev(fcd_handle *h, const float *a, const float *b, float *out_add,
@@ -1568,102 +1580,8 @@ int fcd_unpack_gathered_dev(fcd_handle *h, const uint8_t *gathered, int64_t stri
     return sc.finish();
 }
 
-// ---- CTC forward log-likelihood of given labellings (ctc_score.hip) ----
-// (shared with fcd_ctc_align_*, whose `out` is its start array: the same lattice, the same limits)
-static int ctc_score_check(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int64_t band, const void *logp,
-                           const char *null_msg = "null labels/len/logp") {
-    int rc = check_batch(h, in, false);
-    if (rc) return rc;
-    if (in->S != 1) return fail(h, FCD_E_INVALID, "ctc_score: S must be 1 (CRF models are not scored)");
-    if (!y) return fail(h, FCD_E_INVALID, "null labellings");
-    if (y->n_hyp < 1) return fail(h, FCD_E_INVALID, "n_hyp must be >= 1");
-    if (band < 0) return fail(h, FCD_E_INVALID, "band must be >= 0");
-    if (band > 0 && !y->path) return fail(h, FCD_E_INVALID, "a band needs the labellings' path");
-    if (y->stride < 0) return fail(h, FCD_E_INVALID, "negative stride");
-    if (in->n_reads > 0 && (!y->labels || !y->len || !logp)) return fail(h, FCD_E_INVALID, null_msg);
-    if (in->n_reads * y->n_hyp >= (1ll << 31)) return fail(h, FCD_E_UNSUPPORTED, "more than 2^31 labellings in one call");
-    if (!ctc_score_supported(in->T, y->stride, band))
-        return fail(h, FCD_E_UNSUPPORTED, band > 0 ? "ctc_score: the band's window does not fit the 160 KiB of LDS: use a narrower band"
-                                                   : "ctc_score: the exact lattice does not fit the 160 KiB of LDS: use a band");
-    return FCD_OK;
-}
-
-int fcd_ctc_score_dev(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int collapse_repeats, int64_t band,
-                      double *logp) {
-    if (!h) return FCD_E_INVALID;
-    std::lock_guard<std::recursive_mutex> g(h->mu);
-    int rc = ctc_score_check(h, in, y, band, logp);
-    if (rc) return rc;
-    if (in->n_reads == 0) return FCD_OK;
-    FCD_DEVICE(h);
-    const size_t n_rows = (size_t)in->n_reads * (size_t)y->n_hyp;
-    CallScope sc(h);
-    sc.add(y->labels, n_rows * (size_t)y->stride);
-    sc.add(y->len, n_rows * 4);
-    sc.add(y->n_valid, (size_t)in->n_reads * 4);
-    sc.add(y->path, n_rows * (size_t)y->stride * 4);
-    sc.add(logp, n_rows * 8);
-    rc = sc.begin(false, false);
-    if (rc) return rc;
-    const ScoreDesc yd{y->labels, y->len, y->n_valid, band > 0 ? y->path : nullptr, y->n_hyp, y->stride};
-    sc.time();
-    FCD_HIP(h, launch_ctc_score(to_desc(in, false), yd, collapse_repeats != 0, std::min<int64_t>(band, 1ll << 28), logp, sc.stream));
-    return sc.finish();
-}
-
-int fcd_ctc_score_host(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int collapse_repeats, int64_t band,
-                       double *logp) {
-    if (!h) return FCD_E_INVALID;
-    std::lock_guard<std::recursive_mutex> whole_call(h->mu);  // staging .. copy-back, see run_host
-    int rc = ctc_score_check(h, in, y, band, logp);
-    if (rc) return rc;
-    if (in->n_reads == 0) return FCD_OK;
-    if (in->stride_read < 0 || in->stride_t < 0 || in->stride_n < 0) return fail(h, FCD_E_INVALID, "negative stride");
-    FCD_DEVICE(h);
-    const size_t B = (size_t)in->n_reads, n_rows = B * (size_t)y->n_hyp, esz = in->dtype == FCD_DTYPE_F32 ? 4 : 2;
-    // the posteriors keep their strides: the span from the first to the last addressed element is staged as it is
-    const size_t span = in->T > 0 ? (size_t)((in->n_reads - 1) * in->stride_read + (in->T - 1) * in->stride_t +
-                                             (in->N - 1) * in->stride_n + 1) : 0;
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_in = 0, o_len = o_in + al(span * esz), o_lab = o_len + al(B * 8);
-    const size_t o_ylen = o_lab + al(n_rows * (size_t)y->stride), o_nv = o_ylen + al(n_rows * 4);
-    const size_t o_path = o_nv + al(B * 4), o_out = o_path + (band > 0 ? al(n_rows * (size_t)y->stride * 4) : 0);
-    const size_t total = o_out + al(n_rows * 8);
-    rc = ensure(h, &h->stage, &h->stage_bytes, total);
-    if (rc) return rc;
-    char *d = reinterpret_cast<char *>(h->stage);
-    if (span) FCD_HIP(h, hipMemcpyAsync(d + o_in, in->post, span * esz, hipMemcpyHostToDevice, h->stream));
-    if (in->lengths) FCD_HIP(h, hipMemcpyAsync(d + o_len, in->lengths, B * 8, hipMemcpyHostToDevice, h->stream));
-    if (y->stride) FCD_HIP(h, hipMemcpyAsync(d + o_lab, y->labels, n_rows * (size_t)y->stride, hipMemcpyHostToDevice, h->stream));
-    FCD_HIP(h, hipMemcpyAsync(d + o_ylen, y->len, n_rows * 4, hipMemcpyHostToDevice, h->stream));
-    if (y->n_valid) FCD_HIP(h, hipMemcpyAsync(d + o_nv, y->n_valid, B * 4, hipMemcpyHostToDevice, h->stream));
-    if (band > 0 && y->stride)
-        FCD_HIP(h, hipMemcpyAsync(d + o_path, y->path, n_rows * (size_t)y->stride * 4, hipMemcpyHostToDevice, h->stream));
-    fcd_batch din = *in;
-    din.post = d + o_in;
-    din.lengths = in->lengths ? reinterpret_cast<const int64_t *>(d + o_len) : nullptr;
-    fcd_labellings dy = *y;
-    dy.labels = reinterpret_cast<const uint8_t *>(d + o_lab);
-    dy.len = reinterpret_cast<const uint32_t *>(d + o_ylen);
-    dy.n_valid = y->n_valid ? reinterpret_cast<const uint32_t *>(d + o_nv) : nullptr;
-    dy.path = band > 0 ? reinterpret_cast<const uint32_t *>(d + o_path) : nullptr;
-    rc = fcd_ctc_score_dev(h, &din, &dy, collapse_repeats, band, reinterpret_cast<double *>(d + o_out));
-    if (rc) return rc;
-    FCD_HIP(h, hipMemcpyAsync(logp, d + o_out, n_rows * 8, hipMemcpyDeviceToHost, h->stream));
-    FCD_HIP(h, hipStreamSynchronize(h->stream));
-    return FCD_OK;
-}
-
-// ---- CTC forced alignment of given labellings (ctc_align.hip) ----
-static int ctc_align_check(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int64_t band, const fcd_alignment *out) {
-    if (!h) return FCD_E_INVALID;
-    if (!out) return fail(h, FCD_E_INVALID, "null alignment");
-    int rc = ctc_score_check(h, in, y, band, out->start, "null labels/len/start");
-    if (rc) return rc;
-    if (in->n_reads > 0 && !out->count) return fail(h, FCD_E_INVALID, "null count");
-    return FCD_OK;
-}
-
+// ---- the lattice of given labellings: CTC forward score (ctc_score.hip), CTC forced alignment (ctc_align.hip) and both
+// under a CRF model (crf_lattice.hip) ----
 int fcd_debug_set_align_workspace_cap(fcd_handle *h, int64_t bytes) {
     if (!h || bytes < 0) return FCD_E_INVALID;
     std::lock_guard<std::recursive_mutex> g(h->mu);
@@ -1671,31 +1589,103 @@ int fcd_debug_set_align_workspace_cap(fcd_handle *h, int64_t bytes) {
     return FCD_OK;
 }
 
-int fcd_ctc_align_dev(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int collapse_repeats, int64_t band,
-                      const fcd_alignment *out) {
-    if (!h) return FCD_E_INVALID;
-    std::lock_guard<std::recursive_mutex> g(h->mu);
-    int rc = ctc_align_check(h, in, y, band, out);
+namespace {
+// One fcd_{ctc,crf}_{score,align}_{dev,host} call: the score writes `logp`, the alignment `out`.
+struct LatticeCall {
+    bool crf, align;
+    const fcd_batch *in;
+    const fcd_labellings *y;
+    int64_t band;
+    int collapse;  // (CTC; a CRF model emits at every label)
+    const float *init;  // (CRF)
+    int64_t n_init, init_stride;
+    double *logp;
+    const fcd_alignment *out;
+};
+
+int lattice_check(fcd_handle *h, const LatticeCall &c) {
+    if (c.align && !c.out) return fail(h, FCD_E_INVALID, "null alignment");
+    const fcd_batch *in = c.in;
+    const fcd_labellings *y = c.y;
+    int rc = check_batch(h, in, c.crf);
     if (rc) return rc;
-    if (in->n_reads == 0) return FCD_OK;
-    FCD_DEVICE(h);
+    if (c.crf) {
+        if (!c.init || c.n_init < 1) return fail(h, FCD_E_INVALID, "init_state missing");
+        if (c.init_stride < 0) return fail(h, FCD_E_INVALID, "negative stride");
+    } else if (in->S != 1) {
+        return fail(h, FCD_E_INVALID, "ctc_score: S must be 1 (CRF models are not scored)");
+    }
+    if (!y) return fail(h, FCD_E_INVALID, "null labellings");
+    if (y->n_hyp < 1) return fail(h, FCD_E_INVALID, "n_hyp must be >= 1");
+    if (c.band < 0) return fail(h, FCD_E_INVALID, "band must be >= 0");
+    if (c.band > 0 && !y->path) return fail(h, FCD_E_INVALID, "a band needs the labellings' path");
+    if (y->stride < 0) return fail(h, FCD_E_INVALID, "negative stride");
+    if (in->n_reads > 0 && (!y->labels || !y->len || !(c.align ? (const void *)c.out->start : (const void *)c.logp)))
+        return fail(h, FCD_E_INVALID, c.align ? "null labels/len/start" : "null labels/len/logp");
+    if (in->n_reads * y->n_hyp >= (1ll << 31)) return fail(h, FCD_E_UNSUPPORTED, "more than 2^31 labellings in one call");
+    if (c.crf) {
+        switch (crf_lattice_unsupported(in->T, in->S, y->stride, std::min<int64_t>(c.band, 1ll << 28))) {
+        case 1: return fail(h, FCD_E_UNSUPPORTED, c.band > 0 ? "crf lattice: the band's window exceeds 512 states: use a narrower band"
+                                                             : "crf lattice: the exact lattice exceeds 512 states: use a band");
+        case 2: return fail(h, FCD_E_UNSUPPORTED, "crf lattice: S must be below 2^24 - 1");
+        case 3: return fail(h, FCD_E_UNSUPPORTED, "crf lattice: labellings beyond 15263 labels do not fit the 64 KiB of LDS: use a smaller stride");
+        default: break;
+        }
+    } else if (!ctc_score_supported(in->T, y->stride, c.band)) {
+        return fail(h, FCD_E_UNSUPPORTED, c.band > 0 ? "ctc_score: the band's window does not fit the 160 KiB of LDS: use a narrower band"
+                                                     : "ctc_score: the exact lattice does not fit the 160 KiB of LDS: use a band");
+    }
+    if (c.align && in->n_reads > 0 && !c.out->count) return fail(h, FCD_E_INVALID, "null count");
+    return FCD_OK;
+}
+
+void add_labellings(CallScope &sc, const LatticeCall &c, size_t n_rows) {
+    sc.add(c.y->labels, n_rows * (size_t)c.y->stride);
+    sc.add(c.y->len, n_rows * 4);
+    sc.add(c.y->n_valid, (size_t)c.in->n_reads * 4);
+    sc.add(c.y->path, n_rows * (size_t)c.y->stride * 4);
+}
+
+// (the drivers: a checked call with reads in it, on the handle's device)
+int lattice_score(fcd_handle *h, const LatticeCall &c) {
+    const fcd_batch *in = c.in;
+    const fcd_labellings *y = c.y;
+    const size_t n_rows = (size_t)in->n_reads * (size_t)y->n_hyp;
+    CallScope sc(h);
+    add_labellings(sc, c, n_rows);
+    sc.add(c.logp, n_rows * 8);
+    int rc = sc.begin(false, false);
+    if (rc) return rc;
+    const ScoreDesc yd{y->labels, y->len, y->n_valid, c.band > 0 ? y->path : nullptr, y->n_hyp, y->stride};
+    const int64_t bnd = std::min<int64_t>(c.band, 1ll << 28);
+    sc.time();
+    if (c.crf)
+        FCD_HIP(h, launch_crf_score(to_desc(in, true), yd, c.init, c.n_init, c.init_stride, bnd, c.logp, sc.stream));
+    else
+        FCD_HIP(h, launch_ctc_score(to_desc(in, false), yd, c.collapse, bnd, c.logp, sc.stream));
+    return sc.finish();
+}
+
+int lattice_align(fcd_handle *h, const LatticeCall &c) {
+    const fcd_batch *in = c.in;
+    const fcd_labellings *y = c.y;
+    const fcd_alignment *out = c.out;
     const size_t n_rows = (size_t)in->n_reads * (size_t)y->n_hyp, cells = n_rows * (size_t)y->stride;
     // the back-pointers: whole reads per launch, as many as the cap holds (at least one), every launch in the same memory
-    const size_t row_bytes = ctc_align_row_bytes(in->T, y->stride, band);
+    // (the CTC kernels size their rows by the band as given, the CRF kernels by the band the launch gets)
+    const int64_t bnd = std::min<int64_t>(c.band, 1ll << 28);
+    const size_t row_bytes = c.crf ? crf_align_row_bytes(in->T, y->stride, bnd) : ctc_align_row_bytes(in->T, y->stride, c.band);
     const int64_t cap = h->align_ws_cap > 0 ? h->align_ws_cap : std::min<int64_t>(4ll << 30, workspace_budget(h));
     const int64_t read_bytes = (int64_t)(row_bytes * (size_t)y->n_hyp);
     const int64_t group = std::max<int64_t>(1, std::min<int64_t>(in->n_reads, cap / read_bytes));
     const size_t o_logp = (size_t)group * (size_t)read_bytes;
     CallScope sc(h);
-    sc.add(y->labels, cells);
-    sc.add(y->len, n_rows * 4);
-    sc.add(y->n_valid, (size_t)in->n_reads * 4);
-    sc.add(y->path, cells * 4);
+    add_labellings(sc, c, n_rows);
     sc.add(out->start, cells * 4);
     sc.add(out->count, cells * 4);
     sc.add(out->qual, cells * 4);
     sc.add(out->logp, n_rows * 8);
-    rc = sc.begin(false, true);  // (exclusive: the workspace from its start, behind every overlapping call in flight)
+    int rc = sc.begin(false, true);  // (exclusive: the workspace from its start, behind every overlapping call in flight)
     if (rc) return rc;
     char *ws = nullptr;
     rc = sc.arena(o_logp + (out->logp ? 0 : n_rows * 8), &ws);
@@ -1705,254 +1695,134 @@ int fcd_ctc_align_dev(fcd_handle *h, const fcd_batch *in, const fcd_labellings *
     sc.time();
     for (int64_t r0 = 0; r0 < in->n_reads; r0 += group) {
         const int64_t row0 = r0 * y->n_hyp;
-        BatchDesc d = to_desc(in, false);
+        BatchDesc d = to_desc(in, c.crf);
         d.post = reinterpret_cast<const float *>(reinterpret_cast<const char *>(in->post) + r0 * in->stride_read * esz);
         d.lengths = in->lengths ? in->lengths + r0 : nullptr;
         d.n_reads = std::min(group, in->n_reads - r0);
         const ScoreDesc yd{y->labels + row0 * y->stride, y->len + row0, y->n_valid ? y->n_valid + r0 : nullptr,
-                           band > 0 ? y->path + row0 * y->stride : nullptr, y->n_hyp, y->stride};
+                           c.band > 0 ? y->path + row0 * y->stride : nullptr, y->n_hyp, y->stride};
         const AlignOut od{out->start + row0 * y->stride, out->count + row0 * y->stride,
                           out->qual ? out->qual + row0 * y->stride : nullptr, logp + row0};
-        FCD_HIP(h, launch_ctc_align(d, yd, collapse_repeats != 0, std::min<int64_t>(band, 1ll << 28), od,
-                                    reinterpret_cast<unsigned char *>(ws), sc.stream));
+        unsigned char *bp = reinterpret_cast<unsigned char *>(ws);
+        if (c.crf)
+            FCD_HIP(h, launch_crf_align(d, yd, c.init + r0 * c.init_stride, c.n_init, c.init_stride, bnd, od, bp, sc.stream));
+        else
+            FCD_HIP(h, launch_ctc_align(d, yd, c.collapse, bnd, od, bp, sc.stream));
     }
     return sc.finish();
+}
+
+int lattice_dev(fcd_handle *h, const LatticeCall &c) {
+    int rc = lattice_check(h, c);
+    if (rc) return rc;
+    if (c.in->n_reads == 0) return FCD_OK;
+    FCD_DEVICE(h);
+    return c.align ? lattice_align(h, c) : lattice_score(h, c);
+}
+
+// host arrays: staged in the order post, init, lengths, the labellings, the outputs; the device call runs on the handle's
+// stream (no fcd_set_overlap), so the copy-back needs no join
+int lattice_host(fcd_handle *h, const LatticeCall &c) {
+    int rc = lattice_check(h, c);
+    if (rc) return rc;
+    const fcd_batch *in = c.in;
+    const fcd_labellings *y = c.y;
+    if (in->n_reads == 0) return FCD_OK;
+    if (in->stride_read < 0 || in->stride_t < 0 || (c.crf && in->stride_s < 0) || in->stride_n < 0)
+        return fail(h, FCD_E_INVALID, "negative stride");
+    FCD_DEVICE(h);
+    const size_t B = (size_t)in->n_reads, n_rows = B * (size_t)y->n_hyp, cells = n_rows * (size_t)y->stride;
+    Staging st(h);
+    // the posteriors keep their strides: the span from the first to the last addressed element is staged as it is
+    const int i_post = st.in(in->post, (size_t)span_elems(in, c.crf) * (in->dtype == FCD_DTYPE_F32 ? 4 : 2));
+    const int i_init = st.in(c.crf ? c.init : nullptr, (size_t)((in->n_reads - 1) * c.init_stride + c.n_init) * 4);
+    const int i_len = st.in(in->lengths, B * 8);
+    const int i_lab = st.in(y->labels, cells);
+    const int i_ylen = st.in(y->len, n_rows * 4);
+    const int i_nv = st.in(y->n_valid, B * 4);
+    const int i_path = st.in(c.band > 0 ? y->path : nullptr, cells * 4);
+    // (alignment entries the kernel does not write -- k >= len -- come back as 0)
+    const int i_start = c.align ? st.out(c.out->start, cells * 4, true) : -1;
+    const int i_count = c.align ? st.out(c.out->count, cells * 4, true) : -1;
+    const int i_qual = c.align ? st.out(c.out->qual, cells * 4, true) : -1;
+    const int i_logp = st.out(c.align ? c.out->logp : c.logp, n_rows * 8);
+    rc = st.commit();
+    if (rc) return rc;
+    fcd_batch din = *in;
+    din.post = st.at<char>(i_post);
+    din.lengths = st.at<int64_t>(i_len);
+    fcd_labellings dy = *y;
+    dy.labels = st.at<uint8_t>(i_lab);
+    dy.len = st.at<uint32_t>(i_ylen);
+    dy.n_valid = st.at<uint32_t>(i_nv);
+    dy.path = st.at<uint32_t>(i_path);
+    const fcd_alignment dout{st.at<uint32_t>(i_start), st.at<uint32_t>(i_count), st.at<float>(i_qual), st.at<double>(i_logp)};
+    LatticeCall d = c;
+    d.in = &din;
+    d.y = &dy;
+    d.init = st.at<float>(i_init);
+    d.logp = st.at<double>(i_logp);
+    d.out = &dout;
+    rc = c.align ? lattice_align(h, d) : lattice_score(h, d);
+    if (rc) return rc;
+    return st.fetch();
+}
+}  // namespace
+
+int fcd_ctc_score_dev(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int collapse_repeats, int64_t band,
+                      double *logp) {
+    if (!h) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> g(h->mu);
+    return lattice_dev(h, LatticeCall{false, false, in, y, band, collapse_repeats != 0, nullptr, 0, 0, logp, nullptr});
+}
+
+int fcd_ctc_score_host(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int collapse_repeats, int64_t band,
+                       double *logp) {
+    if (!h) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> whole_call(h->mu);  // staging .. copy-back, see run_host
+    return lattice_host(h, LatticeCall{false, false, in, y, band, collapse_repeats != 0, nullptr, 0, 0, logp, nullptr});
+}
+
+int fcd_ctc_align_dev(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int collapse_repeats, int64_t band,
+                      const fcd_alignment *out) {
+    if (!h) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> g(h->mu);
+    return lattice_dev(h, LatticeCall{false, true, in, y, band, collapse_repeats != 0, nullptr, 0, 0, nullptr, out});
 }
 
 int fcd_ctc_align_host(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int collapse_repeats, int64_t band,
                        const fcd_alignment *out) {
     if (!h) return FCD_E_INVALID;
     std::lock_guard<std::recursive_mutex> whole_call(h->mu);  // staging .. copy-back, see run_host
-    int rc = ctc_align_check(h, in, y, band, out);
-    if (rc) return rc;
-    if (in->n_reads == 0) return FCD_OK;
-    if (in->stride_read < 0 || in->stride_t < 0 || in->stride_n < 0) return fail(h, FCD_E_INVALID, "negative stride");
-    FCD_DEVICE(h);
-    const size_t B = (size_t)in->n_reads, n_rows = B * (size_t)y->n_hyp, esz = in->dtype == FCD_DTYPE_F32 ? 4 : 2;
-    const size_t cells = n_rows * (size_t)y->stride;
-    const size_t span = in->T > 0 ? (size_t)((in->n_reads - 1) * in->stride_read + (in->T - 1) * in->stride_t +
-                                             (in->N - 1) * in->stride_n + 1) : 0;
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_in = 0, o_len = o_in + al(span * esz), o_lab = o_len + al(B * 8);
-    const size_t o_ylen = o_lab + al(cells), o_nv = o_ylen + al(n_rows * 4);
-    const size_t o_path = o_nv + al(B * 4), o_start = o_path + (band > 0 ? al(cells * 4) : 0);
-    const size_t o_count = o_start + al(cells * 4), o_qual = o_count + al(cells * 4), o_out = o_qual + al(cells * 4);
-    const size_t total = o_out + al(n_rows * 8);
-    rc = ensure(h, &h->stage, &h->stage_bytes, total);
-    if (rc) return rc;
-    char *d = reinterpret_cast<char *>(h->stage);
-    if (span) FCD_HIP(h, hipMemcpyAsync(d + o_in, in->post, span * esz, hipMemcpyHostToDevice, h->stream));
-    if (in->lengths) FCD_HIP(h, hipMemcpyAsync(d + o_len, in->lengths, B * 8, hipMemcpyHostToDevice, h->stream));
-    if (y->stride) FCD_HIP(h, hipMemcpyAsync(d + o_lab, y->labels, cells, hipMemcpyHostToDevice, h->stream));
-    FCD_HIP(h, hipMemcpyAsync(d + o_ylen, y->len, n_rows * 4, hipMemcpyHostToDevice, h->stream));
-    if (y->n_valid) FCD_HIP(h, hipMemcpyAsync(d + o_nv, y->n_valid, B * 4, hipMemcpyHostToDevice, h->stream));
-    if (band > 0 && y->stride)
-        FCD_HIP(h, hipMemcpyAsync(d + o_path, y->path, cells * 4, hipMemcpyHostToDevice, h->stream));
-    // (entries the kernel does not write -- k >= len -- come back as 0)
-    FCD_HIP(h, hipMemsetAsync(d + o_start, 0, o_out - o_start, h->stream));
-    fcd_batch din = *in;
-    din.post = d + o_in;
-    din.lengths = in->lengths ? reinterpret_cast<const int64_t *>(d + o_len) : nullptr;
-    fcd_labellings dy = *y;
-    dy.labels = reinterpret_cast<const uint8_t *>(d + o_lab);
-    dy.len = reinterpret_cast<const uint32_t *>(d + o_ylen);
-    dy.n_valid = y->n_valid ? reinterpret_cast<const uint32_t *>(d + o_nv) : nullptr;
-    dy.path = band > 0 ? reinterpret_cast<const uint32_t *>(d + o_path) : nullptr;
-    const fcd_alignment dout{reinterpret_cast<uint32_t *>(d + o_start), reinterpret_cast<uint32_t *>(d + o_count),
-                             out->qual ? reinterpret_cast<float *>(d + o_qual) : nullptr,
-                             out->logp ? reinterpret_cast<double *>(d + o_out) : nullptr};
-    rc = fcd_ctc_align_dev(h, &din, &dy, collapse_repeats, band, &dout);
-    if (rc) return rc;
-    if (cells) {
-        FCD_HIP(h, hipMemcpyAsync(out->start, d + o_start, cells * 4, hipMemcpyDeviceToHost, h->stream));
-        FCD_HIP(h, hipMemcpyAsync(out->count, d + o_count, cells * 4, hipMemcpyDeviceToHost, h->stream));
-        if (out->qual) FCD_HIP(h, hipMemcpyAsync(out->qual, d + o_qual, cells * 4, hipMemcpyDeviceToHost, h->stream));
-    }
-    if (out->logp) FCD_HIP(h, hipMemcpyAsync(out->logp, d + o_out, n_rows * 8, hipMemcpyDeviceToHost, h->stream));
-    FCD_HIP(h, hipStreamSynchronize(h->stream));
-    return FCD_OK;
-}
-
-// ---- the lattice of given labellings under a CRF model (crf_lattice.hip) ----
-// (shared by fcd_crf_score_* and fcd_crf_align_*, whose `out` is its start array)
-static int crf_lattice_check(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init, int64_t init_stride,
-                             const fcd_labellings *y, int64_t band, const void *out, const char *null_msg) {
-    int rc = check_batch(h, in, true);
-    if (rc) return rc;
-    if (!init || n_init < 1) return fail(h, FCD_E_INVALID, "init_state missing");
-    if (init_stride < 0) return fail(h, FCD_E_INVALID, "negative stride");
-    if (!y) return fail(h, FCD_E_INVALID, "null labellings");
-    if (y->n_hyp < 1) return fail(h, FCD_E_INVALID, "n_hyp must be >= 1");
-    if (band < 0) return fail(h, FCD_E_INVALID, "band must be >= 0");
-    if (band > 0 && !y->path) return fail(h, FCD_E_INVALID, "a band needs the labellings' path");
-    if (y->stride < 0) return fail(h, FCD_E_INVALID, "negative stride");
-    if (in->n_reads > 0 && (!y->labels || !y->len || !out)) return fail(h, FCD_E_INVALID, null_msg);
-    if (in->n_reads * y->n_hyp >= (1ll << 31)) return fail(h, FCD_E_UNSUPPORTED, "more than 2^31 labellings in one call");
-    switch (crf_lattice_unsupported(in->T, in->S, y->stride, std::min<int64_t>(band, 1ll << 28))) {
-    case 1: return fail(h, FCD_E_UNSUPPORTED, band > 0 ? "crf lattice: the band's window exceeds 512 states: use a narrower band"
-                                                       : "crf lattice: the exact lattice exceeds 512 states: use a band");
-    case 2: return fail(h, FCD_E_UNSUPPORTED, "crf lattice: S must be below 2^24 - 1");
-    case 3: return fail(h, FCD_E_UNSUPPORTED, "crf lattice: labellings beyond 15263 labels do not fit the 64 KiB of LDS: use a smaller stride");
-    default: return FCD_OK;
-    }
+    return lattice_host(h, LatticeCall{false, true, in, y, band, collapse_repeats != 0, nullptr, 0, 0, nullptr, out});
 }
 
 int fcd_crf_score_dev(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init, int64_t init_stride,
                       const fcd_labellings *y, int64_t band, double *logp) {
     if (!h) return FCD_E_INVALID;
     std::lock_guard<std::recursive_mutex> g(h->mu);
-    int rc = crf_lattice_check(h, in, init, n_init, init_stride, y, band, logp, "null labels/len/logp");
-    if (rc) return rc;
-    if (in->n_reads == 0) return FCD_OK;
-    FCD_DEVICE(h);
-    const size_t n_rows = (size_t)in->n_reads * (size_t)y->n_hyp;
-    CallScope sc(h);
-    sc.add(y->labels, n_rows * (size_t)y->stride);
-    sc.add(y->len, n_rows * 4);
-    sc.add(y->n_valid, (size_t)in->n_reads * 4);
-    sc.add(y->path, n_rows * (size_t)y->stride * 4);
-    sc.add(logp, n_rows * 8);
-    rc = sc.begin(false, false);
-    if (rc) return rc;
-    const ScoreDesc yd{y->labels, y->len, y->n_valid, band > 0 ? y->path : nullptr, y->n_hyp, y->stride};
-    sc.time();
-    FCD_HIP(h, launch_crf_score(to_desc(in, true), yd, init, n_init, init_stride, std::min<int64_t>(band, 1ll << 28), logp, sc.stream));
-    return sc.finish();
-}
-
-int fcd_crf_align_dev(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init, int64_t init_stride,
-                      const fcd_labellings *y, int64_t band, const fcd_alignment *out) {
-    if (!h) return FCD_E_INVALID;
-    std::lock_guard<std::recursive_mutex> g(h->mu);
-    if (!out) return fail(h, FCD_E_INVALID, "null alignment");
-    int rc = crf_lattice_check(h, in, init, n_init, init_stride, y, band, out->start, "null labels/len/start");
-    if (rc) return rc;
-    if (in->n_reads > 0 && !out->count) return fail(h, FCD_E_INVALID, "null count");
-    if (in->n_reads == 0) return FCD_OK;
-    FCD_DEVICE(h);
-    const size_t n_rows = (size_t)in->n_reads * (size_t)y->n_hyp, cells = n_rows * (size_t)y->stride;
-    // the back-pointers: whole reads per launch, as many as the cap holds (at least one), every launch in the same memory
-    const int64_t bnd = std::min<int64_t>(band, 1ll << 28);
-    const size_t row_bytes = crf_align_row_bytes(in->T, y->stride, bnd);
-    const int64_t cap = h->align_ws_cap > 0 ? h->align_ws_cap : std::min<int64_t>(4ll << 30, workspace_budget(h));
-    const int64_t read_bytes = (int64_t)(row_bytes * (size_t)y->n_hyp);
-    const int64_t group = std::max<int64_t>(1, std::min<int64_t>(in->n_reads, cap / read_bytes));
-    const size_t o_logp = (size_t)group * (size_t)read_bytes;
-    CallScope sc(h);
-    sc.add(y->labels, cells);
-    sc.add(y->len, n_rows * 4);
-    sc.add(y->n_valid, (size_t)in->n_reads * 4);
-    sc.add(y->path, cells * 4);
-    sc.add(out->start, cells * 4);
-    sc.add(out->count, cells * 4);
-    sc.add(out->qual, cells * 4);
-    sc.add(out->logp, n_rows * 8);
-    rc = sc.begin(false, true);  // (exclusive: the workspace from its start, behind every overlapping call in flight)
-    if (rc) return rc;
-    char *ws = nullptr;
-    rc = sc.arena(o_logp + (out->logp ? 0 : n_rows * 8), &ws);
-    if (rc) return rc;
-    double *logp = out->logp ? out->logp : reinterpret_cast<double *>(ws + o_logp);
-    const int64_t esz = in->dtype == FCD_DTYPE_F32 ? 4 : 2;
-    sc.time();
-    for (int64_t r0 = 0; r0 < in->n_reads; r0 += group) {
-        const int64_t row0 = r0 * y->n_hyp;
-        BatchDesc d = to_desc(in, true);
-        d.post = reinterpret_cast<const float *>(reinterpret_cast<const char *>(in->post) + r0 * in->stride_read * esz);
-        d.lengths = in->lengths ? in->lengths + r0 : nullptr;
-        d.n_reads = std::min(group, in->n_reads - r0);
-        const ScoreDesc yd{y->labels + row0 * y->stride, y->len + row0, y->n_valid ? y->n_valid + r0 : nullptr,
-                           band > 0 ? y->path + row0 * y->stride : nullptr, y->n_hyp, y->stride};
-        const AlignOut od{out->start + row0 * y->stride, out->count + row0 * y->stride,
-                          out->qual ? out->qual + row0 * y->stride : nullptr, logp + row0};
-        FCD_HIP(h, launch_crf_align(d, yd, init + r0 * init_stride, n_init, init_stride, bnd, od,
-                                    reinterpret_cast<unsigned char *>(ws), sc.stream));
-    }
-    return sc.finish();
-}
-
-// host staging of fcd_crf_score_host / fcd_crf_align_host: out == nullptr scores into logp
-static int crf_lattice_host(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init, int64_t init_stride,
-                            const fcd_labellings *y, int64_t band, double *logp, const fcd_alignment *out) {
-    if (in->stride_read < 0 || in->stride_t < 0 || in->stride_s < 0 || in->stride_n < 0)
-        return fail(h, FCD_E_INVALID, "negative stride");
-    FCD_DEVICE(h);
-    const size_t B = (size_t)in->n_reads, n_rows = B * (size_t)y->n_hyp, esz = in->dtype == FCD_DTYPE_F32 ? 4 : 2;
-    const size_t cells = n_rows * (size_t)y->stride;
-    // the posteriors keep their strides: the span from the first to the last addressed element is staged as it is
-    const size_t span = in->T > 0 ? (size_t)((in->n_reads - 1) * in->stride_read + (in->T - 1) * in->stride_t +
-                                             (in->S - 1) * in->stride_s + (in->N - 1) * in->stride_n + 1) : 0;
-    const size_t init_span = (size_t)((in->n_reads - 1) * init_stride + n_init);
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_in = 0, o_init = o_in + al(span * esz), o_len = o_init + al(init_span * 4), o_lab = o_len + al(B * 8);
-    const size_t o_ylen = o_lab + al(cells), o_nv = o_ylen + al(n_rows * 4);
-    const size_t o_path = o_nv + al(B * 4), o_start = o_path + (band > 0 ? al(cells * 4) : 0);
-    const size_t o_count = o_start + (out ? al(cells * 4) : 0), o_qual = o_count + (out ? al(cells * 4) : 0);
-    const size_t o_out = o_qual + (out ? al(cells * 4) : 0);
-    const size_t total = o_out + al(n_rows * 8);
-    int rc = ensure(h, &h->stage, &h->stage_bytes, total);
-    if (rc) return rc;
-    char *d = reinterpret_cast<char *>(h->stage);
-    if (span) FCD_HIP(h, hipMemcpyAsync(d + o_in, in->post, span * esz, hipMemcpyHostToDevice, h->stream));
-    FCD_HIP(h, hipMemcpyAsync(d + o_init, init, init_span * 4, hipMemcpyHostToDevice, h->stream));
-    if (in->lengths) FCD_HIP(h, hipMemcpyAsync(d + o_len, in->lengths, B * 8, hipMemcpyHostToDevice, h->stream));
-    if (y->stride) FCD_HIP(h, hipMemcpyAsync(d + o_lab, y->labels, cells, hipMemcpyHostToDevice, h->stream));
-    FCD_HIP(h, hipMemcpyAsync(d + o_ylen, y->len, n_rows * 4, hipMemcpyHostToDevice, h->stream));
-    if (y->n_valid) FCD_HIP(h, hipMemcpyAsync(d + o_nv, y->n_valid, B * 4, hipMemcpyHostToDevice, h->stream));
-    if (band > 0 && y->stride)
-        FCD_HIP(h, hipMemcpyAsync(d + o_path, y->path, cells * 4, hipMemcpyHostToDevice, h->stream));
-    // (entries the kernel does not write -- k >= len -- come back as 0)
-    if (out && o_out > o_start) FCD_HIP(h, hipMemsetAsync(d + o_start, 0, o_out - o_start, h->stream));
-    fcd_batch din = *in;
-    din.post = d + o_in;
-    din.lengths = in->lengths ? reinterpret_cast<const int64_t *>(d + o_len) : nullptr;
-    fcd_labellings dy = *y;
-    dy.labels = reinterpret_cast<const uint8_t *>(d + o_lab);
-    dy.len = reinterpret_cast<const uint32_t *>(d + o_ylen);
-    dy.n_valid = y->n_valid ? reinterpret_cast<const uint32_t *>(d + o_nv) : nullptr;
-    dy.path = band > 0 ? reinterpret_cast<const uint32_t *>(d + o_path) : nullptr;
-    const float *dinit = reinterpret_cast<const float *>(d + o_init);
-    if (!out) {
-        rc = fcd_crf_score_dev(h, &din, dinit, n_init, init_stride, &dy, band, reinterpret_cast<double *>(d + o_out));
-        if (rc) return rc;
-        FCD_HIP(h, hipMemcpyAsync(logp, d + o_out, n_rows * 8, hipMemcpyDeviceToHost, h->stream));
-    } else {
-        const fcd_alignment dout{reinterpret_cast<uint32_t *>(d + o_start), reinterpret_cast<uint32_t *>(d + o_count),
-                                 out->qual ? reinterpret_cast<float *>(d + o_qual) : nullptr,
-                                 out->logp ? reinterpret_cast<double *>(d + o_out) : nullptr};
-        rc = fcd_crf_align_dev(h, &din, dinit, n_init, init_stride, &dy, band, &dout);
-        if (rc) return rc;
-        if (cells) {
-            FCD_HIP(h, hipMemcpyAsync(out->start, d + o_start, cells * 4, hipMemcpyDeviceToHost, h->stream));
-            FCD_HIP(h, hipMemcpyAsync(out->count, d + o_count, cells * 4, hipMemcpyDeviceToHost, h->stream));
-            if (out->qual) FCD_HIP(h, hipMemcpyAsync(out->qual, d + o_qual, cells * 4, hipMemcpyDeviceToHost, h->stream));
-        }
-        if (out->logp) FCD_HIP(h, hipMemcpyAsync(out->logp, d + o_out, n_rows * 8, hipMemcpyDeviceToHost, h->stream));
-    }
-    FCD_HIP(h, hipStreamSynchronize(h->stream));
-    return FCD_OK;
+    return lattice_dev(h, LatticeCall{true, false, in, y, band, 0, init, n_init, init_stride, logp, nullptr});
 }
 
 int fcd_crf_score_host(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init, int64_t init_stride,
                        const fcd_labellings *y, int64_t band, double *logp) {
     if (!h) return FCD_E_INVALID;
     std::lock_guard<std::recursive_mutex> whole_call(h->mu);  // staging .. copy-back, see run_host
-    int rc = crf_lattice_check(h, in, init, n_init, init_stride, y, band, logp, "null labels/len/logp");
-    if (rc) return rc;
-    if (in->n_reads == 0) return FCD_OK;
-    return crf_lattice_host(h, in, init, n_init, init_stride, y, band, logp, nullptr);
+    return lattice_host(h, LatticeCall{true, false, in, y, band, 0, init, n_init, init_stride, logp, nullptr});
+}
+
+int fcd_crf_align_dev(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init, int64_t init_stride,
+                      const fcd_labellings *y, int64_t band, const fcd_alignment *out) {
+    if (!h) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> g(h->mu);
+    return lattice_dev(h, LatticeCall{true, true, in, y, band, 0, init, n_init, init_stride, nullptr, out});
 }
 
 int fcd_crf_align_host(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init, int64_t init_stride,
                        const fcd_labellings *y, int64_t band, const fcd_alignment *out) {
     if (!h) return FCD_E_INVALID;
-    std::lock_guard<std::recursive_mutex> whole_call(h->mu);
-    if (!out) return fail(h, FCD_E_INVALID, "null alignment");
-    int rc = crf_lattice_check(h, in, init, n_init, init_stride, y, band, out->start, "null labels/len/start");
-    if (rc) return rc;
-    if (in->n_reads > 0 && !out->count) return fail(h, FCD_E_INVALID, "null count");
-    if (in->n_reads == 0) return FCD_OK;
-    return crf_lattice_host(h, in, init, n_init, init_stride, y, band, nullptr, out);
+    std::lock_guard<std::recursive_mutex> whole_call(h->mu);  // staging .. copy-back, see run_host
+    return lattice_host(h, LatticeCall{true, true, in, y, band, 0, init, n_init, init_stride, nullptr, out});
 }
 
 }  // extern "C"

@@ -63,6 +63,71 @@ def check(got, x32, lengths, labels, paths, out_len, n_valid, collapse, band, ro
     return refs
 
 
+def host_abi_optional_pointers(fcd, S=None):
+    """fcd_ctc_align_host (S None) / fcd_crf_align_host (S states) through ctypes, at every combination of the pointers the
+    C ABI makes optional: lengths and n_valid null or given, band 0 without path and band 2 with it, and qual / logp null
+    singly and together -- on time-major posteriors, B = 3, T = 7, N = 5, two hypotheses in rows of 8.  The call with
+    qual and logp goes through check() (the restatement); a call without one of them must give the other arrays bit for
+    bit and leave nothing else written.  Entries k >= len come back 0, whatever the caller's arrays held."""
+    import ctypes as C
+    import itertools
+    from types import SimpleNamespace
+    from fast_ctc_decode_amd import _native as nat
+    B, T, N, n_hyp, stride = 3, 7, 5, 2, 8
+    rng = np.random.default_rng(31 + (S or 0))
+    if S is None:
+        x, init, row = SC.posteriors(rng, B, T, N), None, N
+    else:
+        import crf_lattice_cases as CC
+        x, init, row = CC.posteriors(rng, B, T, S, N), rng.random((B, S)).astype(np.float32), S * N
+    xt = np.ascontiguousarray(np.moveaxis(x, 0, 1))  # (T, B, ..): reads are `row` elements apart, rows B * row
+    lengths, n_valid = np.array([T, 4, 6], np.int64), np.array([2, 1, 2], np.uint32)
+    labels, paths = np.zeros((B, n_hyp, stride), np.uint8), np.zeros((B, n_hyp, stride), np.uint32)
+    lens = np.zeros((B, n_hyp), np.uint32)
+    for b in range(B):
+        for i in range(n_hyp):
+            L = 1 + (b + i) % 3
+            labels[b, i, :L] = [1 + (k + b + i) % (N - 1) for k in range(L)]  # (neighbours differ: L rows do)
+            paths[b, i, :L] = np.sort(rng.choice(4, L, replace=False))        # (inside the shortest read)
+            lens[b, i] = L
+    h = nat.default_handle()
+
+    def run(with_len, with_nv, band, qual=True, logp=True):
+        r = SimpleNamespace(start=np.full((B, n_hyp, stride), 77, np.uint32), count=np.full((B, n_hyp, stride), 77, np.uint32),
+                            qual=np.full((B, n_hyp, stride), 77.0, np.float32), logp=np.full((B, n_hyp), 77.0))
+        b_ = nat.Batch(xt.ctypes.data, B, T, S or 1, N, row, B * row, 0 if S is None else N, 1,
+                       lengths.ctypes.data if with_len else None)
+        y_ = nat.Labellings(labels.ctypes.data, lens.ctypes.data, n_valid.ctypes.data if with_nv else None,
+                            paths.ctypes.data if band else None, n_hyp, stride)
+        out = nat.Alignment(r.start.ctypes.data, r.count.ctypes.data, r.qual.ctypes.data if qual else None,
+                            r.logp.ctypes.data if logp else None)
+        if S is None:
+            rc = h.lib.fcd_ctc_align_host(h.ptr, C.byref(b_), C.byref(y_), 1, band, C.byref(out))
+        else:
+            rc = h.lib.fcd_crf_align_host(h.ptr, C.byref(b_), init.ctypes.data, S, S, C.byref(y_), band, C.byref(out))
+        assert rc == nat.OK, h.lib.fcd_last_error(h.ptr)
+        return r
+
+    for with_len, with_nv, band in itertools.product((False, True), (False, True), (0, 2)):
+        where = (with_len, with_nv, band)
+        full = run(with_len, with_nv, band)
+        ls, nv = lengths if with_len else None, n_valid if with_nv else None
+        if S is None:
+            check(full, x, ls, labels, paths, lens, nv, True, band)
+        else:
+            CC.check(full, None, x, init, ls, labels, paths, lens, nv, band)
+        assert np.isfinite(full.logp[:, 0]).all() and (full.count[:, 0, 0] >= 1).all(), where  # (alignments, not refusals)
+        for b in range(B):
+            for i in range(n_hyp):
+                n = int(lens[b, i])
+                assert not full.start[b, i, n:].any() and not full.count[b, i, n:].any() and not full.qual[b, i, n:].any(), where
+        for qual, logp in ((False, True), (True, False), (False, False)):
+            part = run(with_len, with_nv, band, qual, logp)
+            assert np.array_equal(part.start, full.start) and np.array_equal(part.count, full.count), where + (qual, logp)
+            assert np.array_equal(part.qual.view(np.uint32), full.qual.view(np.uint32)) if qual else (part.qual == 77).all()
+            assert np.array_equal(part.logp, full.logp, equal_nan=True) if logp else (part.logp == 77).all()
+
+
 def _device_inputs(c, device):
     """(xin, conv, kw) of a ctc_score_cases case for numpy (device None) or torch tensors on `device`"""
     kw = {}

@@ -3,7 +3,8 @@ emulation) through crf_score_batch_raw / crf_align_batch_raw on numpy, against t
 tests/crf_lattice_reference.py: the grid of tests/crf_lattice_cases.py (S of 1 .. 1024, alphabets of 2 .. 5, 1 .. 1100 rows,
 ragged lengths, f16 / bf16 input, time-major strides, 1 .. 5 hypotheses with n_valid, exact mode and bands 1 .. 128, every
 K, both staging regimes, the ring wrapped in every K), parity with crf_greedy_search on its own output, every edge case of
-include/fcd.h, the argument errors at both layers, the workspace cap forcing several launches, the results' own methods
+include/fcd.h, the argument errors at both layers, every combination of the C ABI's optional pointers
+through fcd_crf_align_host, the workspace cap forcing several launches, the results' own methods
 and crf_beam_search(qstring=True).  The -m gpu twin is tests/test_gpu_crf_lattice.py."""
 import ctypes as C
 import math
@@ -13,7 +14,7 @@ import pytest
 
 import crf_lattice_cases as CC
 import crf_lattice_reference as R
-from ctc_align_cases import logp_same
+from ctc_align_cases import host_abi_optional_pointers, logp_same
 from emu_util import emulated_kernels
 
 
@@ -125,6 +126,10 @@ def test_edge_cases(fcd):
     got = fcd.crf_align_batch_raw(xl, init[:1], yl, [15], paths=pl, band=1)
     assert got.logp[0, 0] == -math.inf and (got.count == 0).all()
     assert fcd.crf_score_batch_raw(xl, init[:1], yl, [15], paths=pl, band=1)[0, 0] == -math.inf
+
+
+def test_host_abi_optional_pointers(fcd):
+    host_abi_optional_pointers(fcd, S=4)
 
 
 def test_single_read_functions(fcd):

@@ -3,7 +3,7 @@ emulation) through ctc_align_batch_raw on numpy, against the restatement tests/c
 tests/ctc_score_cases.py (alphabets of 2 .. 12 labels, 9 .. 300 rows, ragged lengths, f16 / bf16 input, time-major strides,
 1 .. 5 hypotheses with n_valid, both collapse_repeats values, exact mode and bands 1 / 4 / 64 / 128, windows that live in
 registers at 2, 4, 6, 8 states per lane and in LDS), every edge case of include/fcd.h, the argument errors at both layers,
-the workspace cap forcing several launches, the results' own ctc_align, beam_search(qstring=True), and parity with
+every combination of the C ABI's optional pointers through fcd_ctc_align_host, the workspace cap forcing several launches, the results' own ctc_align, beam_search(qstring=True), and parity with
 viterbi_search on its own output.  What is compared and how: tests/ctc_align_cases.py.  The -m gpu twin is
 tests/test_gpu_ctc_align.py."""
 import ctypes as C
@@ -106,6 +106,10 @@ def test_edge_cases(fcd):
     ref = A.ctc_align(xl[0], yl[0], True, 1, pl[0])
     assert AC.logp_same(got.logp[0, 0], ref["logp"])
     AC.check(got, xl, None, yl[:, None], pl[:, None], np.array([[15]]), None, True, 1)
+
+
+def test_host_abi_optional_pointers(fcd):
+    AC.host_abi_optional_pointers(fcd)
 
 
 def test_single_read_function(fcd):

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import crf_lattice_cases as CC
+from ctc_align_cases import host_abi_optional_pointers
 
 pytestmark = pytest.mark.gpu
 
@@ -39,6 +40,10 @@ def test_cases_on_numpy(fcd, cases, name):
 def test_greedy_parity(fcd, T):
     CC.greedy_parity(fcd, T, "f16", device="cuda")
     CC.greedy_parity(fcd, T, "f32")
+
+
+def test_host_abi_optional_pointers(fcd):
+    host_abi_optional_pointers(fcd, S=4)
 
 
 def test_edge_cases(fcd):

@@ -40,6 +40,10 @@ def test_greedy_parity(fcd, T, dtype):
     AC.greedy_parity(fcd, T, dtype)
 
 
+def test_host_abi_optional_pointers(fcd):
+    AC.host_abi_optional_pointers(fcd)
+
+
 def test_results_align_themselves_on_the_device(fcd):
     import torch
     rng = np.random.default_rng(11)
