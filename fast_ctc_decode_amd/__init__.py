@@ -44,6 +44,9 @@ from .api import (  # noqa: F401
     AlignResult,
     ctc_align,
     ctc_align_batch_raw,
+    PosteriorResult,
+    ctc_posterior,
+    ctc_posterior_batch_raw,
     ctc_score,
     ctc_score_batch_raw,
     crf_greedy_search_batch,

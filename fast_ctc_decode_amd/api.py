@@ -832,6 +832,18 @@ class BatchResult:
                                    self.path if band else None, band, None, input_dtype,
                                    getattr(self, "_handle", None))
 
+    def ctc_posterior(self, network_outputs, collapse_repeats=True, lengths=None, band=0, input_dtype=None):
+        """The substitution posteriors of every read's result -> PosteriorResult, post (n_reads, 1, stride, N-1):
+        ctc_posterior_batch_raw on this result's own arrays (device results stay on the device).  Arguments as
+        ctc_score.  CRF results are refused (transition-scored models: a different lattice)."""
+        if isinstance(self, _CrfBatchResult) or getattr(network_outputs, "ndim", 3) != 3:
+            raise ValueError("ctc_posterior covers the plain CTC searches, not CRF results")
+        if band and self.path is None:
+            raise ValueError("a band needs the result's path")
+        return ctc_posterior_batch_raw(network_outputs, self.labels, self.out_len, collapse_repeats, lengths,
+                                       self.path if band else None, band, None, input_dtype,
+                                       getattr(self, "_handle", None))
+
     def crf_score(self, network_outputs, init_states, lengths=None, band=0, input_dtype=None):
         """ln P(labelling | posteriors) under the CRF model of every read's result, float64 (n_reads, 1):
         crf_score_batch_raw on this result's own arrays.  For the results of the CRF searches, with the (B,T,S,N)
@@ -1166,6 +1178,15 @@ class NBestResult:
         return ctc_align_batch_raw(network_outputs, self.labels, self.out_len, collapse_repeats, lengths,
                                    self.path if band else None, band, self.n_hyp, input_dtype,
                                    getattr(self, "_handle", None))
+
+    def ctc_posterior(self, network_outputs, collapse_repeats=True, lengths=None, band=0, input_dtype=None):
+        """The substitution posteriors of every hypothesis -> PosteriorResult, post (n_reads, n_best, stride, N-1); logp
+        NaN where i >= n_hyp[r].  ctc_posterior_batch_raw on this result's own arrays; CRF results are refused."""
+        if self.crf or getattr(network_outputs, "ndim", 3) != 3:
+            raise ValueError("ctc_posterior covers the plain CTC searches, not CRF results")
+        return ctc_posterior_batch_raw(network_outputs, self.labels, self.out_len, collapse_repeats, lengths,
+                                       self.path if band else None, band, self.n_hyp, input_dtype,
+                                       getattr(self, "_handle", None))
 
     def crf_score(self, network_outputs, init_states, lengths=None, band=0, input_dtype=None):
         """ln P(labelling | posteriors) under the CRF model of every hypothesis, float64 (n_reads, n_best); NaN where
@@ -1596,6 +1617,88 @@ def ctc_align(network_output, sequence, alphabet, collapse_repeats=True):
     n = len(y)
     return ([(int(s), int(c)) for s, c in zip(r.start[0, 0, :n], r.count[0, 0, :n])],
             [float(q) for q in r.qual[0, 0, :n]], logp)
+
+
+# ---------------------------------------------------------------------------------------------
+# CTC forward-backward substitution posteriors of given labellings (include/fcd.h, fcd_ctc_posterior_*)
+# ---------------------------------------------------------------------------------------------
+class PosteriorResult:
+    """Outcome of ctc_posterior_batch_raw: post[r, i, k, c - 1] is the posterior that label c stands at position k of
+    hypothesis i of read r, the rest of the labelling held fixed -- P(y[k:=c] | x) over its sum over c, float32, all
+    alignments counted (include/fcd.h); logp[r, i] (float64) is ln P(y | x), ctc_score's value.  NaN for every position of
+    a labelling whose P is not positive and finite; entries k >= the labelling's length are 0.  numpy for host inputs,
+    torch tensors (same device) for device inputs."""
+
+    def __init__(self, post, logp):
+        self.post, self.logp = post, logp
+
+    def cpu(self):
+        def c(a):
+            return a if isinstance(a, np.ndarray) else a.cpu().numpy()
+        return PosteriorResult(c(self.post), c(self.logp))
+
+    def conf(self, labels):
+        """-> (B, n_hyp, stride) float32 numpy: the called label's share, post[r, i, k, labels[r, i, k] - 1]; 0 where the
+        entry of `labels` is no label (the padding behind a labelling)."""
+        post = self.cpu().post
+        lab = labels if isinstance(labels, np.ndarray) or not hasattr(labels, "cpu") else labels.cpu().numpy()
+        lab = np.asarray(lab).astype(np.int64).reshape(post.shape[:3])
+        ok = (lab >= 1) & (lab <= post.shape[3])
+        col = np.where(ok, lab - 1, 0)
+        return np.where(ok, np.take_along_axis(post, col[..., None], 3)[..., 0], np.float32(0.0)).astype(np.float32)
+
+    def qstrings(self, labels, out_len, qscale=1.0, qbias=0.0):
+        """-> per read, per hypothesis, the phred quality string of its first out_len[r, i] labels, from conf through the
+        conversion AlignResult.qstrings uses (fcd_phred); "" for a labelling without a posterior."""
+        logp = self.cpu().logp
+        conf = self.conf(labels)
+        n = np.asarray(out_len if isinstance(out_len, np.ndarray) or not hasattr(out_len, "cpu") else out_len.cpu().numpy())
+        n = n.reshape(logp.shape)
+        return [[_qual_chars(conf[b, i, :int(n[b, i])], qscale, qbias) if np.isfinite(logp[b, i]) else ""
+                 for i in range(logp.shape[1])] for b in range(logp.shape[0])]
+
+
+def ctc_posterior_batch_raw(network_outputs, labels, label_lengths, collapse_repeats=True, lengths=None, paths=None,
+                            band=0, n_valid=None, input_dtype=None, handle=None):
+    """CTC forward-backward substitution posteriors: for every position of every labelling, the posterior over which
+    label stands there with the rest of the labelling held fixed, summed over every alignment in one forward and one
+    backward walk (include/fcd.h, fcd_ctc_posterior_*).  -> PosteriorResult with post (B, n_hyp, stride, N-1) float32
+    and logp (B, n_hyp) float64.
+
+    Arguments as ctc_score_batch_raw: band=0 walks the exact lattice, band=W > 0 the window within W labels of `paths`.
+    Limits: windows of at most 510 states (bands up to 126, exact mode up to 254 rows or labels) and N - 1 <= 8.
+    Device tensors in: torch tensors on the same device, enqueued on torch's current stream, not synchronised.
+    numpy in: numpy out."""
+    band = _check_band(band, paths)
+    h, b, y, (B, n_hyp, stride), dev, keep = _lattice_inputs(network_outputs, labels, label_lengths, lengths, paths, band,
+                                                             n_valid, input_dtype, handle)
+    nc = int(b.N) - 1
+    if dev is not None:
+        import torch
+        post = torch.zeros((B, n_hyp, stride, nc), dtype=torch.float32, device=dev)
+        logp = torch.empty((B, n_hyp), dtype=torch.float64, device=dev)
+        out = nat.Posterior(post.data_ptr(), logp.data_ptr())
+        h.check(h.lib.fcd_ctc_posterior_dev(h.ptr, C.byref(b), C.byref(y), int(bool(collapse_repeats)), band, C.byref(out)))
+        return PosteriorResult(post, logp)
+    post = np.zeros((B, n_hyp, stride, nc), np.float32)
+    logp = np.empty((B, n_hyp), np.float64)
+    out = nat.Posterior(post.ctypes.data, logp.ctypes.data)
+    h.check(h.lib.fcd_ctc_posterior_host(h.ptr, C.byref(b), C.byref(y), int(bool(collapse_repeats)), band, C.byref(out)))
+    return PosteriorResult(post, logp)
+
+
+def ctc_posterior(network_output, sequence, alphabet, collapse_repeats=True):
+    """The substitution posteriors of one string against one (T, N) float32 posterior matrix, exact lattice:
+    -> (post, logp) with post an (L, N-1) float32 array (row k: the posterior over alphabet[1:] at character k) and
+    logp = ln P(sequence | network_output).  Argument checks as ctc_score."""
+    x = _as_f32(network_output, 2, "network_output")
+    alpha = _seq_to_vec(alphabet)
+    _check_greedy_alphabet(len(alpha), x.shape[1])
+    y = _sequence_labels(sequence, alpha, "ctc_posterior")
+    lab = np.zeros((1, max(len(y), 1)), np.uint8)
+    lab[0, :len(y)] = y
+    r = ctc_posterior_batch_raw(_dense(x)[None], lab, np.array([len(y)], np.uint32), collapse_repeats)
+    return r.post[0, 0, :len(y)].copy(), float(r.logp[0, 0])
 
 
 # ---------------------------------------------------------------------------------------------

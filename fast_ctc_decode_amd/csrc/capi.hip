@@ -7,6 +7,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <functional>
 #include <atomic>
 #include <vector>
 
@@ -1580,8 +1581,8 @@ int fcd_unpack_gathered_dev(fcd_handle *h, const uint8_t *gathered, int64_t stri
     return sc.finish();
 }
 
-// ---- the lattice of given labellings: CTC forward score (ctc_score.hip), CTC forced alignment (ctc_align.hip) and both
-// under a CRF model (crf_lattice.hip) ----
+// ---- the lattice of given labellings: CTC forward score (ctc_score.hip), CTC forced alignment (ctc_align.hip), both
+// under a CRF model (crf_lattice.hip), and the CTC substitution posteriors (ctc_posterior.hip) ----
 int fcd_debug_set_align_workspace_cap(fcd_handle *h, int64_t bytes) {
     if (!h || bytes < 0) return FCD_E_INVALID;
     std::lock_guard<std::recursive_mutex> g(h->mu);
@@ -1590,7 +1591,8 @@ int fcd_debug_set_align_workspace_cap(fcd_handle *h, int64_t bytes) {
 }
 
 namespace {
-// One fcd_{ctc,crf}_{score,align}_{dev,host} call: the score writes `logp`, the alignment `out`.
+// One fcd_{ctc,crf}_{score,align}_{dev,host} or fcd_ctc_posterior_{dev,host} call: the score writes `logp`, the alignment
+// `out`, the posteriors `post`.
 struct LatticeCall {
     bool crf, align;
     const fcd_batch *in;
@@ -1601,10 +1603,13 @@ struct LatticeCall {
     int64_t n_init, init_stride;
     double *logp;
     const fcd_alignment *out;
+    bool posterior = false;
+    const fcd_posterior *post = nullptr;
 };
 
 int lattice_check(fcd_handle *h, const LatticeCall &c) {
     if (c.align && !c.out) return fail(h, FCD_E_INVALID, "null alignment");
+    if (c.posterior && !c.post) return fail(h, FCD_E_INVALID, "null posterior");
     const fcd_batch *in = c.in;
     const fcd_labellings *y = c.y;
     int rc = check_batch(h, in, c.crf);
@@ -1620,8 +1625,9 @@ int lattice_check(fcd_handle *h, const LatticeCall &c) {
     if (c.band < 0) return fail(h, FCD_E_INVALID, "band must be >= 0");
     if (c.band > 0 && !y->path) return fail(h, FCD_E_INVALID, "a band needs the labellings' path");
     if (y->stride < 0) return fail(h, FCD_E_INVALID, "negative stride");
-    if (in->n_reads > 0 && (!y->labels || !y->len || !(c.align ? (const void *)c.out->start : (const void *)c.logp)))
-        return fail(h, FCD_E_INVALID, c.align ? "null labels/len/start" : "null labels/len/logp");
+    if (in->n_reads > 0 && (!y->labels || !y->len ||
+                            !(c.posterior ? (const void *)c.post->post : c.align ? (const void *)c.out->start : (const void *)c.logp)))
+        return fail(h, FCD_E_INVALID, c.posterior ? "null labels/len/post" : c.align ? "null labels/len/start" : "null labels/len/logp");
     if (in->n_reads * y->n_hyp >= (1ll << 31)) return fail(h, FCD_E_UNSUPPORTED, "more than 2^31 labellings in one call");
     if (c.crf) {
         switch (crf_lattice_unsupported(in->T, in->S, y->stride, std::min<int64_t>(c.band, 1ll << 28))) {
@@ -1636,6 +1642,15 @@ int lattice_check(fcd_handle *h, const LatticeCall &c) {
                                                      : "ctc_score: the exact lattice does not fit the 160 KiB of LDS: use a band");
     }
     if (c.align && in->n_reads > 0 && !c.out->count) return fail(h, FCD_E_INVALID, "null count");
+    if (c.posterior) {
+        switch (ctc_posterior_unsupported(in->T, y->stride, c.band, in->N)) {
+        case 1: return fail(h, FCD_E_UNSUPPORTED, c.band > 0 ? "ctc_posterior: the band's window exceeds 510 states: use a narrower band"
+                                                             : "ctc_posterior: the exact lattice exceeds 510 states: use a band");
+        case 2: return fail(h, FCD_E_UNSUPPORTED, "ctc_posterior: more than 8 labels besides the blank");
+        case 3: return fail(h, FCD_E_UNSUPPORTED, "ctc_posterior: labellings beyond 28480 labels do not fit the 64 KiB of LDS: use a smaller stride");
+        default: break;
+        }
+    }
     return FCD_OK;
 }
 
@@ -1666,31 +1681,29 @@ int lattice_score(fcd_handle *h, const LatticeCall &c) {
     return sc.finish();
 }
 
-int lattice_align(fcd_handle *h, const LatticeCall &c) {
+// What lattice_align and lattice_posterior share: per-labelling workspace (back-pointers, stored forward rows) of
+// row_bytes each.  Whole reads per launch, as many as `cap` bytes hold (at least one), every launch in the same memory, one
+// after the other on the stream; logp lent from the workspace when the caller wants none.  add_outputs(sc): the arrays the
+// call writes; launch(d, yd, r0, row0, logp, ws, stream): one group -- reads r0 .., labellings row0 .., its slice of logp.
+using GroupLaunch = std::function<hipError_t(const BatchDesc &, const ScoreDesc &, int64_t, int64_t, double *, unsigned char *, hipStream_t)>;
+int lattice_grouped(fcd_handle *h, const LatticeCall &c, size_t row_bytes, int64_t cap, double *out_logp,
+                    const std::function<void(CallScope &)> &add_outputs, const GroupLaunch &launch) {
     const fcd_batch *in = c.in;
     const fcd_labellings *y = c.y;
-    const fcd_alignment *out = c.out;
-    const size_t n_rows = (size_t)in->n_reads * (size_t)y->n_hyp, cells = n_rows * (size_t)y->stride;
-    // the back-pointers: whole reads per launch, as many as the cap holds (at least one), every launch in the same memory
-    // (the CTC kernels size their rows by the band as given, the CRF kernels by the band the launch gets)
-    const int64_t bnd = std::min<int64_t>(c.band, 1ll << 28);
-    const size_t row_bytes = c.crf ? crf_align_row_bytes(in->T, y->stride, bnd) : ctc_align_row_bytes(in->T, y->stride, c.band);
-    const int64_t cap = h->align_ws_cap > 0 ? h->align_ws_cap : std::min<int64_t>(4ll << 30, workspace_budget(h));
+    const size_t n_rows = (size_t)in->n_reads * (size_t)y->n_hyp;
     const int64_t read_bytes = (int64_t)(row_bytes * (size_t)y->n_hyp);
     const int64_t group = std::max<int64_t>(1, std::min<int64_t>(in->n_reads, cap / read_bytes));
     const size_t o_logp = (size_t)group * (size_t)read_bytes;
     CallScope sc(h);
     add_labellings(sc, c, n_rows);
-    sc.add(out->start, cells * 4);
-    sc.add(out->count, cells * 4);
-    sc.add(out->qual, cells * 4);
-    sc.add(out->logp, n_rows * 8);
+    add_outputs(sc);
+    sc.add(out_logp, n_rows * 8);
     int rc = sc.begin(false, true);  // (exclusive: the workspace from its start, behind every overlapping call in flight)
     if (rc) return rc;
     char *ws = nullptr;
-    rc = sc.arena(o_logp + (out->logp ? 0 : n_rows * 8), &ws);
+    rc = sc.arena(o_logp + (out_logp ? 0 : n_rows * 8), &ws);
     if (rc) return rc;
-    double *logp = out->logp ? out->logp : reinterpret_cast<double *>(ws + o_logp);
+    double *logp = out_logp ? out_logp : reinterpret_cast<double *>(ws + o_logp);
     const int64_t esz = in->dtype == FCD_DTYPE_F32 ? 4 : 2;
     sc.time();
     for (int64_t r0 = 0; r0 < in->n_reads; r0 += group) {
@@ -1701,15 +1714,51 @@ int lattice_align(fcd_handle *h, const LatticeCall &c) {
         d.n_reads = std::min(group, in->n_reads - r0);
         const ScoreDesc yd{y->labels + row0 * y->stride, y->len + row0, y->n_valid ? y->n_valid + r0 : nullptr,
                            c.band > 0 ? y->path + row0 * y->stride : nullptr, y->n_hyp, y->stride};
-        const AlignOut od{out->start + row0 * y->stride, out->count + row0 * y->stride,
-                          out->qual ? out->qual + row0 * y->stride : nullptr, logp + row0};
-        unsigned char *bp = reinterpret_cast<unsigned char *>(ws);
-        if (c.crf)
-            FCD_HIP(h, launch_crf_align(d, yd, c.init + r0 * c.init_stride, c.n_init, c.init_stride, bnd, od, bp, sc.stream));
-        else
-            FCD_HIP(h, launch_ctc_align(d, yd, c.collapse, bnd, od, bp, sc.stream));
+        FCD_HIP(h, launch(d, yd, r0, row0, logp + row0, reinterpret_cast<unsigned char *>(ws), sc.stream));
     }
     return sc.finish();
+}
+
+int lattice_align(fcd_handle *h, const LatticeCall &c) {
+    const fcd_batch *in = c.in;
+    const fcd_labellings *y = c.y;
+    const fcd_alignment *out = c.out;
+    const size_t cells = (size_t)in->n_reads * (size_t)y->n_hyp * (size_t)y->stride;
+    // (the CTC kernels size their rows by the band as given, the CRF kernels by the band the launch gets)
+    const int64_t bnd = std::min<int64_t>(c.band, 1ll << 28);
+    const size_t row_bytes = c.crf ? crf_align_row_bytes(in->T, y->stride, bnd) : ctc_align_row_bytes(in->T, y->stride, c.band);
+    const int64_t cap = h->align_ws_cap > 0 ? h->align_ws_cap : std::min<int64_t>(4ll << 30, workspace_budget(h));
+    return lattice_grouped(
+        h, c, row_bytes, cap, out->logp,
+        [&](CallScope &sc) {
+            sc.add(out->start, cells * 4);
+            sc.add(out->count, cells * 4);
+            sc.add(out->qual, cells * 4);
+        },
+        [&](const BatchDesc &d, const ScoreDesc &yd, int64_t r0, int64_t row0, double *logp, unsigned char *bp, hipStream_t stream) {
+            const AlignOut od{out->start + row0 * y->stride, out->count + row0 * y->stride,
+                              out->qual ? out->qual + row0 * y->stride : nullptr, logp};
+            return c.crf ? launch_crf_align(d, yd, c.init + r0 * c.init_stride, c.n_init, c.init_stride, bnd, od, bp, stream)
+                         : launch_ctc_align(d, yd, c.collapse, bnd, od, bp, stream);
+        });
+}
+
+int lattice_posterior(fcd_handle *h, const LatticeCall &c) {
+    const fcd_batch *in = c.in;
+    const fcd_labellings *y = c.y;
+    const fcd_posterior *out = c.post;
+    const size_t per_row = (size_t)y->stride * ((size_t)in->N - 1);  // post entries of one labelling
+    const int64_t bnd = std::min<int64_t>(c.band, 1ll << 28);
+    return lattice_grouped(
+        h, c, ctc_posterior_row_bytes(in->T, y->stride, c.band), std::min<int64_t>(4ll << 30, workspace_budget(h)), out->logp,
+        [&](CallScope &sc) { sc.add(out->post, (size_t)in->n_reads * (size_t)y->n_hyp * per_row * 4); },
+        [&](const BatchDesc &d, const ScoreDesc &yd, int64_t, int64_t row0, double *logp, unsigned char *alpha, hipStream_t stream) {
+            return launch_ctc_posterior(d, yd, c.collapse, bnd, out->post + (size_t)row0 * per_row, logp, alpha, stream);
+        });
+}
+
+int lattice_run(fcd_handle *h, const LatticeCall &c) {
+    return c.posterior ? lattice_posterior(h, c) : (c.align ? lattice_align(h, c) : lattice_score(h, c));
 }
 
 int lattice_dev(fcd_handle *h, const LatticeCall &c) {
@@ -1717,7 +1766,7 @@ int lattice_dev(fcd_handle *h, const LatticeCall &c) {
     if (rc) return rc;
     if (c.in->n_reads == 0) return FCD_OK;
     FCD_DEVICE(h);
-    return c.align ? lattice_align(h, c) : lattice_score(h, c);
+    return lattice_run(h, c);
 }
 
 // host arrays: staged in the order post, init, lengths, the labellings, the outputs; the device call runs on the handle's
@@ -1745,7 +1794,9 @@ int lattice_host(fcd_handle *h, const LatticeCall &c) {
     const int i_start = c.align ? st.out(c.out->start, cells * 4, true) : -1;
     const int i_count = c.align ? st.out(c.out->count, cells * 4, true) : -1;
     const int i_qual = c.align ? st.out(c.out->qual, cells * 4, true) : -1;
-    const int i_logp = st.out(c.align ? c.out->logp : c.logp, n_rows * 8);
+    // (posterior entries the kernel does not write -- k >= len -- come back as 0)
+    const int i_sub = c.posterior ? st.out(c.post->post, cells * ((size_t)in->N - 1) * 4, true) : -1;
+    const int i_logp = st.out(c.posterior ? c.post->logp : (c.align ? c.out->logp : c.logp), n_rows * 8);
     rc = st.commit();
     if (rc) return rc;
     fcd_batch din = *in;
@@ -1763,7 +1814,9 @@ int lattice_host(fcd_handle *h, const LatticeCall &c) {
     d.init = st.at<float>(i_init);
     d.logp = st.at<double>(i_logp);
     d.out = &dout;
-    rc = c.align ? lattice_align(h, d) : lattice_score(h, d);
+    const fcd_posterior dpost{st.at<float>(i_sub), st.at<double>(i_logp)};
+    d.post = &dpost;
+    rc = lattice_run(h, d);
     if (rc) return rc;
     return st.fetch();
 }
@@ -1795,6 +1848,20 @@ int fcd_ctc_align_host(fcd_handle *h, const fcd_batch *in, const fcd_labellings 
     if (!h) return FCD_E_INVALID;
     std::lock_guard<std::recursive_mutex> whole_call(h->mu);  // staging .. copy-back, see run_host
     return lattice_host(h, LatticeCall{false, true, in, y, band, collapse_repeats != 0, nullptr, 0, 0, nullptr, out});
+}
+
+int fcd_ctc_posterior_dev(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int collapse_repeats, int64_t band,
+                          const fcd_posterior *out) {
+    if (!h) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> g(h->mu);
+    return lattice_dev(h, LatticeCall{false, false, in, y, band, collapse_repeats != 0, nullptr, 0, 0, nullptr, nullptr, true, out});
+}
+
+int fcd_ctc_posterior_host(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int collapse_repeats, int64_t band,
+                           const fcd_posterior *out) {
+    if (!h) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> whole_call(h->mu);  // staging .. copy-back, see run_host
+    return lattice_host(h, LatticeCall{false, false, in, y, band, collapse_repeats != 0, nullptr, 0, 0, nullptr, nullptr, true, out});
 }
 
 int fcd_crf_score_dev(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init, int64_t init_stride,

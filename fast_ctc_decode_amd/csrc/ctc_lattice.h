@@ -1,7 +1,7 @@
-// ctc_lattice.h -- what the two walks of the CTC lattice of a GIVEN labelling share: ctc_score.hip (forward: the sum over
-// the alignments) and ctc_align.hip (Viterbi: the best alignment).  Parameter block, LDS layout, everything before the
-// time loop, the staging of the posteriors (split into mantissa and exponent), the live window of a row, the integer
-// row maximum and the wave rotation.  Included by those two translation units only.
+// ctc_lattice.h -- what the walks of the CTC lattice of a GIVEN labelling share: ctc_score.hip (forward: the sum over
+// the alignments), ctc_align.hip (Viterbi: the best alignment) and ctc_posterior.hip (forward and backward).  Parameter
+// block, LDS layout, everything before the time loop, the staging of the posteriors (split into mantissa and exponent),
+// the live window of a row, the integer row maximum and the wave rotation.  Included by those translation units only.
 #pragma once
 
 #include <math.h>
@@ -17,8 +17,10 @@ constexpr int kNoExp = -(1 << 24);    // "exponent" of a cell that takes no part
 constexpr int kTileElems = 1024;      // posteriors staged per tile
 constexpr int kTileRows = 64;         // ... at most this many rows (one lane per row finds k(t))
 constexpr int kLdsCells = 20;         // LDS kernel: cells per work-item and step
-constexpr int kMiscWords = 32;        // [0..15] per-wave maxima, [16] bad-label flag, [17] kBadPost, [18] [19] the two final cells
+constexpr int kMiscWords = 32;        // [0..15] per-wave maxima, [16] bad-label flag, [17] kBadPost, [18] [19] the two final cells,
+                                      // [20] kKrowBefore
 constexpr int kBadPost = 17;          // misc word of ctc_align.hip: the read holds a posterior no comparison can order
+constexpr int kKrowBefore = 20;       // misc word of ctc_posterior.hip: k(t) of the row before the tile
 
 struct ScoreParams {
     BatchDesc in;
@@ -138,16 +140,21 @@ __device__ __forceinline__ void fill_tile(const ScoreParams &p, const Lds &lds, 
     __syncthreads();
 }
 
-// live states of row t: the band around the path, cut to what can be reached and can still reach the end
-__device__ __forceinline__ void window(const ScoreParams &p, const Lds &lds, const Row &rw, int t, int i, int *lo, int *hi) {
+// live states of row t: the band around the path (k = k(t), read only when banded), cut to what can be reached and can
+// still reach the end
+__device__ __forceinline__ void window_k(const ScoreParams &p, const Row &rw, int t, int k, int *lo, int *hi) {
     int l = 0, h = 2 * rw.L;
     if (p.band > 0) {
-        const int k = lds.krow[i];
         l = max(0, 2 * (k - p.band) - 2);
         h = min(h, 2 * (k + p.band));
     }
     *hi = min(h, 2 * t + 1);
     *lo = max(l, 2 * rw.L - 2 * (rw.Tr - 1 - t) - 2);
+}
+
+// ... of row t, the tile's row i
+__device__ __forceinline__ void window(const ScoreParams &p, const Lds &lds, const Row &rw, int t, int i, int *lo, int *hi) {
+    window_k(p, rw, t, p.band > 0 ? lds.krow[i] : 0, lo, hi);
 }
 
 __device__ __forceinline__ int finite_exp(float u) {  // exponent of a positive finite value, kNoExp for anything else

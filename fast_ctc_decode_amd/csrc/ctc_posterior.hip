@@ -1,0 +1,381 @@
+// ctc_posterior.hip -- CTC forward-backward substitution posteriors of given labellings (fcd_ctc_posterior_*;
+// include/fcd.h): post[k][c] = P(y[k:=c] | x) / sum_c' P(y[k:=c'] | x) for every label position k and every label c, from
+// ONE forward and ONE backward walk of the lattice ctc_score.hip sums over.  NOT a reference function.
+//
+// Two launches, one wavefront per labelling each, the register-resident window of ctc_score.hip (K consecutive states
+// per lane, state s in slot s mod 64K):
+//   post_fwd_kernel<K>       ctc_score's forward step, unchanged (its logp is ctc_score's bit for bit).  Every row's live
+//                            cells go to the workspace by SLOT, scaled by 2^-kAlphaDown (exact), and the row's exponent
+//                            next to them: T * 64K floats, then T exponent words, per labelling.
+//   post_back_kernel<K, NC>  walks the rows from T_r - 1 down.  b_t[s] = p[t][z[s]] * beta_t[s] obeys the mirror image of
+//                            the forward step, b_t[s] = (b_{t+1}[s] + b_{t+1}[s+1] + b_{t+1}[s+2]) * p[t][z[s]] under the
+//                            same transition rules ("row T_r": all mass on state 2L), so a cell is again at most two sums
+//                            and one product.  A label state s = 2k + 1 also carries, for each label c <= NC,
+//                              w_t(c)  = (w_{t+1}(c) [collapse] + b_{t+1}[s+1] + [c != y_{k+1} or no collapse] b_{t+1}[s+2]) * p[t][c]
+//                                        the backward value of state s had its label been c, and
+//                              acc(c) += (alpha_{t-1}[s-1] + [s >= 3, c != y_{k-1} or no collapse] alpha_{t-1}[s-2]) * w_t(c)
+//                            summed over the rows s is live at: P(y[k:=c] | x) up to a scale all c share.  When s leaves the
+//                            window (or after row 0) the lane divides by the sum over c and stores post[k][.].
+// Scales.  b and w share one integer exponent per row (the row's largest b or w lands in [2^(kTargetB-1), 2^kTargetB));
+// alpha has the forward pass's.  A term of acc therefore has the wave-uniform exponent X_t = Ea(t-1) + Eb(t); acc is kept
+// at the largest X seen so far, kAccDown bits below it so that the sum over the rows cannot overflow: a term is scaled by
+// the power of two 2^(X_t - Xmax - kAccDown), acc by 2^(Xmax_old - Xmax_new) when Xmax rises.  Both exact.
+// Every term is non-negative; one rounding per product and per sum; no fused multiply-add (-ffp-contract=off).
+#include <math.h>
+
+#include <algorithm>
+
+#include "ctc_lattice.h"
+
+namespace fcd {
+namespace {
+
+constexpr int kAlphaDown = 60;   // stored alpha: row maximum in [2^59, 2^60) -- times w (below 2^60) stays finite
+constexpr int kTargetB = 60;     // b, w: row maximum in [2^59, 2^60)
+constexpr int kAccDown = 40;     // a term (below 2^121) enters acc below 2^81: 2^46 rows sum below 2^127
+
+struct PostParams {
+    ScoreParams s;        // (s.logp is never null: the launcher lends scratch when the caller wants none)
+    float *post;          // [labellings of this launch * stride * (N - 1)]
+    float *alpha;         // the stored forward rows, alpha_words per labelling of this launch
+    int64_t alpha_words;
+};
+
+// ---- pass 1: ctc_score's score_reg_kernel, storing what it computes ----
+template <int K>
+__global__ __launch_bounds__(64) void post_fwd_kernel(PostParams q) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr int C = 64 * K;
+    const ScoreParams &p = q.s;
+    const Lds lds = carve(smem, p.lab_cap);
+    Row rw;
+    if (!prologue(p, lds, &rw)) return;
+    const int lane = threadIdx.x;
+    float *am = q.alpha + (int64_t)blockIdx.x * q.alpha_words;
+    int *ae = reinterpret_cast<int *>(am + (int64_t)p.in.T * C);
+    float a[K];
+#pragma unroll
+    for (int r = 0; r < K; ++r) a[r] = 0.0f;
+    if (lane == 0) a[0] = 1.0f;  // "row -1": all mass on state 0
+    int64_t eacc = 0;
+    int lo_prev = 0, lo = 0, hi = 0;
+    for (int t0 = 0; t0 < rw.Tr; t0 += rw.rows_per_tile) {
+        const int rc = min(rw.rows_per_tile, rw.Tr - t0);
+        fill_tile(p, lds, rw, t0, rc);
+        StepIn<K> in = load_step<K>(p, lds, rw, t0, 0);
+        for (int i = 0; i < rc; ++i) {
+            StepIn<K> nx = in;
+            if (i + 1 < rc) nx = load_step<K>(p, lds, rw, t0 + i + 1, i + 1);
+            lo = in.lo;
+            hi = in.hi;
+            if (hi - lo_prev >= C) {  // the window jumped: slots it re-enters start from 0
+#pragma unroll
+                for (int r = 0; r < K; ++r)
+                    if (slot_state<K>(lane, r, lo_prev) <= hi - C) a[r] = 0.0f;
+            }
+            const float p1 = from_prev_lane(a[K - 1]), p2 = from_prev_lane(a[K - 2]);
+            float u[K];
+            int ex[K];
+            int emax = kNoExp;
+#pragma unroll
+            for (int r = 0; r < K; ++r) {
+                const float x1 = r >= 1 ? a[r - 1] : p1;
+                const float x2 = r >= 2 ? a[r - 2] : (r == 1 ? p1 : p2);
+                float sum;
+                if (r & 1) {
+                    sum = p.collapse ? a[r] + x1 : x1;
+                    sum += ((in.skip_mask >> r) & 1) ? x2 : 0.0f;
+                    u[r] = sum * in.pm[r / 2];
+                    ex[r] = in.pe[r / 2];
+                } else {
+                    sum = a[r] + x1;
+                    u[r] = sum * in.pm0;
+                    ex[r] = in.pe0;
+                }
+                const int e = finite_exp(u[r]);
+                emax = max(emax, ((in.in_mask >> r) & 1) && e != kNoExp ? e + ex[r] : kNoExp);
+            }
+            emax = wave_imax(emax);
+            const int sh = emax == kNoExp ? 0 : kTarget - emax;
+            eacc -= sh;
+            float *row = am + (int64_t)(t0 + i) * C + lane * K;
+#pragma unroll
+            for (int r = 0; r < K; ++r) {
+                a[r] = ((in.in_mask >> r) & 1) ? ldexpf(u[r], min(max(ex[r] + sh, -512), 512)) : 0.0f;
+                if ((in.in_mask >> r) & 1) row[r] = ldexpf(a[r], -kAlphaDown);
+            }
+            if (lane == 0) ae[t0 + i] = (int)(eacc + kAlphaDown);
+            lo_prev = lo;
+            in = nx;
+        }
+    }
+    if (lane == 0) lds.misc[18] = lds.misc[19] = 0;
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < K; ++r) {
+        const int s = slot_state<K>(lane, r, lo);
+        if (s <= hi && s == 2 * rw.L) lds.misc[18] = __float_as_int(a[r]);
+        if (s <= hi && s == 2 * rw.L - 1) lds.misc[19] = __float_as_int(a[r]);
+    }
+    __syncthreads();
+    if (lane == 0) {
+        const double m = (double)__int_as_float(lds.misc[18]) + (double)__int_as_float(lds.misc[19]);
+        p.logp[blockIdx.x] = log(m) + (double)eacc * 0.693147180559945309417232121458;
+    }
+}
+
+// ---- pass 2 ----
+// a labelling without a positive finite P(y | x): NaN for the labels the row holds
+__device__ __forceinline__ void no_posterior(const PostParams &q) {
+    const int64_t row = blockIdx.x, nc = q.s.in.N - 1;
+    const int64_t n = min((int64_t)q.s.y.len[row], q.s.y.stride) * nc;
+    for (int64_t e = threadIdx.x; e < n; e += blockDim.x) q.post[row * q.s.y.stride * nc + e] = NAN;
+}
+
+template <int NC>
+__device__ __forceinline__ void store_post(float *post, int k, int nc, const float (&acc)[NC]) {
+    float sum = acc[0];
+#pragma unroll
+    for (int c = 1; c < NC; ++c)
+        if (c < nc) sum += acc[c];
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+        if (c < nc) post[(int64_t)k * nc + c] = acc[c] / sum;  // (0 / 0 and x / NaN: NaN, as the contract wants it)
+}
+
+__device__ __forceinline__ float from_next_lane(float x) {  // wave_rol:1 -- lane l receives lane (l + 1) & 63
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x134, 0xf, 0xf, false));
+}
+
+template <int K, int NC>
+__global__ __launch_bounds__(64) void post_back_kernel(PostParams q) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr int C = 64 * K, H = K / 2;
+    const ScoreParams &p = q.s;
+    const Lds lds = carve(smem, p.lab_cap);
+    Row rw;
+    if (!prologue(p, lds, &rw)) {  // (the forward launch wrote this row's logp already; the same value again)
+        no_posterior(q);
+        return;
+    }
+    const double lp = p.logp[blockIdx.x];
+    if (lp - lp != 0.0) {  // P = 0, or a NaN on the way
+        no_posterior(q);
+        return;
+    }
+    if (rw.L == 0) return;
+    const int lane = threadIdx.x, nc = rw.N - 1, L = rw.L;
+    const float *am = q.alpha + (int64_t)blockIdx.x * q.alpha_words;
+    const int *ae = reinterpret_cast<const int *>(am + (int64_t)p.in.T * C);
+    float *post = q.post + (int64_t)blockIdx.x * p.y.stride * nc;
+    float b[K], w[H][NC], acc[H][NC];
+#pragma unroll
+    for (int r = 0; r < K; ++r) b[r] = 0.0f;
+#pragma unroll
+    for (int h = 0; h < H; ++h)
+#pragma unroll
+        for (int c = 0; c < NC; ++c) w[h][c] = acc[h][c] = 0.0f;
+    int64_t eb = 0, xmax = 0;
+    bool first = true, any = false;
+    int lo = 0, hi = 0, lo_n = 0, hi_n = 0;
+    for (int t0 = (rw.Tr - 1) / rw.rows_per_tile * rw.rows_per_tile; t0 >= 0; t0 -= rw.rows_per_tile) {
+        const int rc = min(rw.rows_per_tile, rw.Tr - t0);
+        fill_tile(p, lds, rw, t0, rc);
+        if (p.band > 0 && t0 > 0) {  // k(t0 - 1): the window of the alpha row that row t0 reads
+            if (lane == 0) {
+                int a0 = 0, a1 = L;
+                while (a0 < a1) {
+                    const int mid = (a0 + a1) >> 1;
+                    if (rw.path[mid] <= (uint32_t)(t0 - 1)) a0 = mid + 1;
+                    else a1 = mid;
+                }
+                lds.misc[kKrowBefore] = a0;
+            }
+            __syncthreads();
+        }
+        for (int i = rc - 1; i >= 0; --i) {
+            const int t = t0 + i;
+            window(p, lds, rw, t, i, &lo, &hi);
+            // alpha_{t-1}, by slot; row -1: all mass on state 0, exponent 0
+            int lo_p = 0, hi_p = 0;
+            float av[K];
+            int64_t x_t = 0;
+            if (t > 0) {
+                window_k(p, rw, t - 1, p.band > 0 ? (i > 0 ? lds.krow[i - 1] : lds.misc[kKrowBefore]) : 0, &lo_p, &hi_p);
+                const float *row = am + (int64_t)(t - 1) * C + lane * K;
+#pragma unroll
+                for (int r = 0; r < K; ++r) av[r] = slot_state<K>(lane, r, lo_p) <= hi_p ? row[r] : 0.0f;
+                x_t = ae[t - 1];
+            } else {
+#pragma unroll
+                for (int r = 0; r < K; ++r) av[r] = (lane == 0 && r == 0) ? 1.0f : 0.0f;
+            }
+            const float av_prev = from_prev_lane(av[K - 1]);
+            if (first) {  // "row T_r": all mass on state 2L
+#pragma unroll
+                for (int r = 0; r < K; ++r) b[r] = slot_state<K>(lane, r, lo) == 2 * L ? 1.0f : 0.0f;
+                first = false;
+                lo_n = lo;
+            } else {  // the label states that were live at row t + 1 and are not at row t: their labels are complete
+#pragma unroll
+                for (int r = 1; r < K; r += 2) {
+                    const int s = slot_state<K>(lane, r, lo_n);
+                    if (s > hi) {  // (b stays: row t still reads b_{t+1} of the states above its window)
+                        if (s <= hi_n) store_post<NC>(post, s >> 1, nc, acc[r / 2]);
+#pragma unroll
+                        for (int c = 0; c < NC; ++c) w[r / 2][c] = acc[r / 2][c] = 0.0f;
+                    }
+                }
+            }
+            const float n1 = from_next_lane(b[0]), n2 = from_next_lane(b[1]);
+            const float pm0 = lds.pm[i * rw.N];
+            const int pe0 = lds.pe[i * rw.N];
+            float pmc[NC];
+            int pec[NC];
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                pmc[c] = lds.pm[i * rw.N + min(c + 1, nc)];
+                pec[c] = lds.pe[i * rw.N + min(c + 1, nc)];
+            }
+            float u[K], uw[H][NC], e1[H], e2[H];
+            int ex[K], yprev[H];
+            uint32_t live = 0;
+            int emax = kNoExp;
+#pragma unroll
+            for (int r = 0; r < K; ++r) {
+                const int s = slot_state<K>(lane, r, lo);
+                const bool in = s <= hi;
+                live |= (in ? 1u : 0u) << r;
+                // b_{t+1} of s, s + 1, s + 2: a state below row t + 1's window is not what its slot holds
+                const float y0 = s >= lo_n ? b[r] : 0.0f;
+                const float y1 = s + 1 >= lo_n ? (r + 1 < K ? b[r + 1] : n1) : 0.0f;
+                const float y2 = s + 2 >= lo_n ? (r + 2 < K ? b[r + 2] : (r + 2 == K ? n1 : n2)) : 0.0f;
+                if (r & 1) {
+                    const int h = r / 2, k = in ? (s >> 1) : 0;  // (a dead slot reads valid addresses and is masked below)
+                    const int info = lds.lab[k], inext = lds.lab[min(k + 1, L - 1)], iprev = lds.lab[max(k - 1, 0)];
+                    const int y = in ? (info & 0xFF) : 0;
+                    const int ynext = k + 1 < L ? (inext & 0xFF) : 0;  // (0: no label c equals it)
+                    yprev[h] = k > 0 ? (iprev & 0xFF) : 0;
+                    float sum = p.collapse ? y0 + y1 : y1;
+                    sum += (k + 1 < L && (!p.collapse || (inext & 0x100))) ? y2 : 0.0f;
+                    u[r] = sum * lds.pm[i * rw.N + y];
+                    ex[r] = lds.pe[i * rw.N + y];
+#pragma unroll
+                    for (int c = 0; c < NC; ++c) {
+                        float exit = p.collapse ? w[h][c] + y1 : y1;
+                        exit += (p.collapse && c + 1 == ynext) ? 0.0f : y2;  // (b[s + 2] is 0 beyond state 2L)
+                        uw[h][c] = exit * pmc[c];
+                        const int e = finite_exp(uw[h][c]);
+                        emax = max(emax, in && c < nc && e != kNoExp ? e + pec[c] : kNoExp);
+                    }
+                    // what enters state s from row t - 1 (a state above that row's window is not in its slot)
+                    const float x1 = av[r >= 1 ? r - 1 : 0], x2 = r >= 2 ? av[r - 2] : av_prev;
+                    e1[h] = (in && s - 1 <= hi_p) ? x1 : 0.0f;
+                    e2[h] = (in && s >= 3 && s - 2 <= hi_p) ? x2 : 0.0f;
+                } else {
+                    u[r] = (y0 + y1) * pm0;
+                    ex[r] = pe0;
+                }
+                const int e = finite_exp(u[r]);
+                emax = max(emax, in && e != kNoExp ? e + ex[r] : kNoExp);
+            }
+            emax = wave_imax(emax);
+            const int sh = emax == kNoExp ? 0 : kTargetB - emax;
+            eb -= sh;
+            x_t += eb;  // the exponent of this row's terms
+            if (!any || x_t > xmax) {
+                if (any) {
+                    const int d = (int)max(xmax - x_t, (int64_t)-512);
+#pragma unroll
+                    for (int h = 0; h < H; ++h)
+#pragma unroll
+                        for (int c = 0; c < NC; ++c) acc[h][c] = ldexpf(acc[h][c], d);
+                }
+                xmax = x_t;
+                any = true;
+            }
+            const int dt = (int)max(x_t - xmax, (int64_t)-512) - kAccDown;
+#pragma unroll
+            for (int r = 0; r < K; ++r) {
+                const bool in = (live >> r) & 1;
+                b[r] = in ? ldexpf(u[r], min(max(ex[r] + sh, -512), 512)) : 0.0f;
+                if (r & 1) {
+                    const int h = r / 2;
+#pragma unroll
+                    for (int c = 0; c < NC; ++c) {
+                        w[h][c] = (in && c < nc) ? ldexpf(uw[h][c], min(max(pec[c] + sh, -512), 512)) : 0.0f;
+                        const float entry = e1[h] + ((p.collapse && c + 1 == yprev[h]) ? 0.0f : e2[h]);
+                        const float term = entry * w[h][c];
+                        acc[h][c] += ldexpf(term, dt);
+                    }
+                }
+            }
+            lo_n = lo;
+            hi_n = hi;
+        }
+    }
+    // the labels whose state is live at row 0
+#pragma unroll
+    for (int r = 1; r < K; r += 2) {
+        const int s = slot_state<K>(lane, r, lo);
+        if (s <= hi) store_post<NC>(post, s >> 1, nc, acc[r / 2]);
+    }
+}
+
+int reg_states_per_lane(int64_t T, int64_t stride, int64_t band) {  // 0: the window does not fit the registers
+    const int64_t states = ctc_score_window_states(T, stride, band);
+    return states + 2 <= 128 ? 2 : (states + 2 <= 256 ? 4 : (states + 2 <= 384 ? 6 : (states + 2 <= 512 ? 8 : 0)));
+}
+
+template <int K>
+void launch_both(const PostParams &q, int nc, dim3 grid, size_t lds, hipStream_t stream) {
+    hipLaunchKernelGGL(post_fwd_kernel<K>, grid, dim3(64), lds, stream, q);
+    if (nc <= 4) hipLaunchKernelGGL((post_back_kernel<K, 4>), grid, dim3(64), lds, stream, q);
+    else hipLaunchKernelGGL((post_back_kernel<K, 8>), grid, dim3(64), lds, stream, q);
+}
+
+}  // namespace
+
+// 0 = the kernels hold the call; 1 = the widest window exceeds the 510 register-resident states; 2 = more than 8 labels;
+// 3 = the labelling's LDS copy and the tile exceed the 64 KiB a launch gets without asking for more
+int ctc_posterior_unsupported(int64_t T, int64_t stride, int64_t band, int64_t N) {
+    if (reg_states_per_lane(T, stride, band) == 0) return 1;
+    if (N - 1 > 8) return 2;
+    return lds_bytes((int)std::max<int64_t>(std::min<int64_t>(std::min(T, stride), 1 << 20), 1), 0) > 64 * 1024 ? 3 : 0;
+}
+
+// stored forward rows of one labelling (every one of a call has T rows' worth): T * 64K cells, then T exponent words
+size_t ctc_posterior_row_bytes(int64_t T, int64_t stride, int64_t band) {
+    const size_t k = (size_t)reg_states_per_lane(T, stride, band);
+    return ((size_t)std::max<int64_t>(T, 1) * (64 * k + 1) * 4 + 255) & ~(size_t)255;
+}
+
+hipError_t launch_ctc_posterior(const BatchDesc &in, const ScoreDesc &y, int collapse, int64_t band, float *post,
+                                double *logp, unsigned char *alpha, hipStream_t stream) {
+    const int64_t rows = in.n_reads * y.n_hyp;
+    if (rows <= 0) return hipSuccess;
+    PostParams q;
+    q.s.in = in;
+    q.s.y = y;
+    q.s.collapse = collapse;
+    q.s.band = (int)band;
+    q.s.logp = logp;
+    q.s.cap = 0;
+    q.s.lab_cap = (int)std::max<int64_t>(std::min(in.T, y.stride), 1);
+    q.post = post;
+    q.alpha = reinterpret_cast<float *>(alpha);
+    q.alpha_words = (int64_t)(ctc_posterior_row_bytes(in.T, y.stride, band) / 4);
+    const dim3 grid((unsigned)rows);
+    const size_t lds = lds_bytes(q.s.lab_cap, 0);
+    const int nc = in.N - 1;
+    switch (reg_states_per_lane(in.T, y.stride, band)) {
+    case 2: launch_both<2>(q, nc, grid, lds, stream); break;
+    case 4: launch_both<4>(q, nc, grid, lds, stream); break;
+    case 6: launch_both<6>(q, nc, grid, lds, stream); break;
+    case 8: launch_both<8>(q, nc, grid, lds, stream); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+}  // namespace fcd

@@ -250,6 +250,14 @@ struct AlignOut {
 size_t ctc_align_row_bytes(int64_t T, int64_t stride, int64_t band);
 hipError_t launch_ctc_align(const BatchDesc &in, const ScoreDesc &y, int collapse, int64_t band, const AlignOut &out,
                             unsigned char *bp, hipStream_t stream);
+// CTC forward-backward substitution posteriors of given labellings (ctc_posterior.hip; fcd_posterior in include/fcd.h).
+// ctc_posterior_unsupported: 0 = the kernels hold the call; 1 = the widest window exceeds the 510 register-resident states,
+// 2 = more than 8 labels, 3 = min(T, stride) beyond the 28480 labels whose LDS copy fits 64 KiB next to the tile.  alpha: ctc_posterior_row_bytes() of device memory per labelling of the launch (the stored
+// forward rows); post: [labellings * stride * (N - 1)]; logp must not be null.
+int ctc_posterior_unsupported(int64_t T, int64_t stride, int64_t band, int64_t N);
+size_t ctc_posterior_row_bytes(int64_t T, int64_t stride, int64_t band);
+hipError_t launch_ctc_posterior(const BatchDesc &in, const ScoreDesc &y, int collapse, int64_t band, float *post,
+                                double *logp, unsigned char *alpha, hipStream_t stream);
 // The lattice of given labellings under a CRF model (crf_lattice.hip; fcd_crf_score_* / fcd_crf_align_* in include/fcd.h).
 // crf_lattice_unsupported: 0 = the kernels hold the call; 1 = the window exceeds the 512 register-resident states,
 // 2 = S beyond the 24-bit state word, 3 = the labelling's LDS copy (4 bytes per state) exceeds 64 KiB.

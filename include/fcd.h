@@ -426,6 +426,52 @@ int fcd_ctc_align_dev(fcd_handle *h, const fcd_batch *in, const fcd_labellings *
 int fcd_ctc_align_host(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int collapse_repeats, int64_t band,
                        const fcd_alignment *out);
 
+/* ---- CTC forward-backward substitution posteriors of given labellings (csrc/ctc_posterior.hip) ----
+ * NOT a reference function.  For a labelling y of L labels (hypothesis i of read r, row = r * n_hyp + i), label position
+ * k < L and label c in 1 .. N-1, let y[k:=c] be y with label k replaced by c.  With P as fcd_ctc_score_* defines it -- same
+ * extended sequence, same transitions under collapse_repeats, and under `band` the live window derived from y's OWN path
+ * for every variant --
+ *   sub[k][c]  = P(y[k:=c] | x)
+ *   post[k][c] = sub[k][c] / sum_{c' = 1 .. N-1} sub[k][c']      float32, entry ((row * stride + k) * (N-1) + c-1)
+ *   conf[k]    = post[k][y_k]
+ * post[k][.] is the posterior over what label stands at position k with the rest of the labelling held fixed, conf[k] the
+ * called label's share of it, 1 - conf[k] a substitution error probability: the number a FASTQ quality, a variant caller
+ * or a polisher wants, which fcd_ctc_align_*'s qual (the network's sharpness along ONE alignment) is not.  Deletions and
+ * insertions are out of scope.
+ * Computed without rescoring any variant, from one forward and one backward walk.  alpha: fcd_ctc_score_*'s forward values.
+ * beta, on the same lattice and window: beta_{T_r-1}[2L] = beta_{T_r-1}[2L-1] = 1; beta_t[q] = sum over the successors s of
+ * q that are live at row t+1 of p[t+1][z[s]] * beta_{t+1}[s].  For s = 2k + 1, over the rows t at which s is live:
+ *   exit_t(c)  = [k = L-1 and t = T_r-1] + p[t+1][0] * beta_{t+1}[s+1]
+ *              + [s+2 <= 2L and (no collapse or c != y_{k+1})] * p[t+1][y_{k+1}] * beta_{t+1}[s+2]
+ *              + [collapse] * w_{t+1}(c)                                 (the stay; w = 0 where s is not live)
+ *   w_t(c)     = p[t][c] * exit_t(c)
+ *   entry_t(c) = t = 0: [k = 0];  else alpha_{t-1}[s-1] + [s >= 3 and (no collapse or c != y_{k-1})] * alpha_{t-1}[s-2]
+ *   sub[k][c]  = sum_t entry_t(c) * w_t(c)                              (c = y_k gives P(y | x) for every k)
+ * Numerics: f32 probability space; rows rescaled by exact powers of two with integer exponents (one per forward row, one
+ * per backward row, one for the accumulators); every term non-negative, one rounding per product and per sum, no fused
+ * multiply-add.  |post - exact| <= about 12 T_r 2^-24 * post.  A cell below 2^-160 of its row's maximum may be dropped.
+ * logp (nullable): ln P(y | x), fcd_ctc_score_*'s value (the same forward recurrence).
+ * Rows without a value: logp follows fcd_ctc_score_*'s rules for that row (NaN, -inf, 0.0); whenever P(y | x) is not a
+ * positive finite number every post entry for k < min(len, stride) is NaN.  A position whose sum over c is 0 or NaN: NaN.
+ * Entries k >= len are never written by _dev; _host returns them as 0.  L = 0 writes logp only.
+ * Shapes, dtypes, strides, in->S = 1, in->lengths, n_valid, stream order and the FCD_E_INVALID cases are
+ * fcd_ctc_score_*'s; a null out or out->post is one more.
+ * Limits (FCD_E_UNSUPPORTED): register-resident windows only -- the widest possible window, min(4 band + 3,
+ * 2 min(T, stride) + 1) states, must not exceed 510 (bands up to 126; exact mode up to min(T, stride) = 254: "use a band"
+ * beyond) -- N - 1 <= 8 labels, and min(T, stride) <= 28480 (the labelling's copy shares 64 KiB of LDS with the tile).
+ * _dev is enqueue-only on the handle's stream, behind every overlapping search in flight (fcd_set_overlap).  The forward
+ * rows (4 bytes per slot, 128 / 256 / 384 / 512 slots a row for windows up to 126 / 254 / 382 / 510 states, plus an exponent
+ * word; only the live cells are written) live in the handle's workspace: the labellings are launched in groups of whole
+ * reads that fit 4 GiB of it (or fcd_set_workspace_limit), one after the other on the stream, no host wait in between. */
+typedef struct fcd_posterior {
+    float  *post;   /* [n_reads * n_hyp * stride * (N-1)], entry ((row * stride + k) * (N-1) + c-1) */
+    double *logp;   /* [n_reads * n_hyp], nullable: ln P(y | x), fcd_ctc_score's value within its tolerance */
+} fcd_posterior;
+int fcd_ctc_posterior_dev(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int collapse_repeats, int64_t band,
+                          const fcd_posterior *out);
+int fcd_ctc_posterior_host(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int collapse_repeats, int64_t band,
+                           const fcd_posterior *out);
+
 /* ---- CRF scoring and forced alignment of given labellings (csrc/crf_lattice.hip) ----
  * NOT reference functions.  The lattice of a GIVEN labelling under a CRF model -- the recurrence search::crf_beam_search
  * walks (src/search.rs:62-100), unpruned and unmerged, for one labelling -- walked forward as a sum (score) and as a max with
