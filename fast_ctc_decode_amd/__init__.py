@@ -44,6 +44,9 @@ from .api import (  # noqa: F401
     AlignResult,
     ctc_align,
     ctc_align_batch_raw,
+    EditResult,
+    ctc_edits,
+    ctc_edits_batch_raw,
     PosteriorResult,
     ctc_posterior,
     ctc_posterior_batch_raw,

@@ -53,6 +53,7 @@ SYMBOLS = [
     "fcd_ctc_score_dev", "fcd_ctc_score_host",
     "fcd_ctc_align_dev", "fcd_ctc_align_host", "fcd_debug_set_align_workspace_cap",
     "fcd_ctc_posterior_dev", "fcd_ctc_posterior_host",
+    "fcd_ctc_edits_dev", "fcd_ctc_edits_host",
     "fcd_crf_score_dev", "fcd_crf_score_host", "fcd_crf_align_dev", "fcd_crf_align_host",
 ]
 JOB_PATH, JOB_QUAL, JOB_AMBIGUOUS, JOB_DONE = 1, 2, 4, 1
@@ -93,6 +94,11 @@ class Alignment(C.Structure):
 class Posterior(C.Structure):
     """fcd_posterior: what fcd_ctc_posterior_* writes (include/fcd.h)."""
     _fields_ = [("post", C.c_void_p), ("logp", C.c_void_p)]
+
+
+class Edits(C.Structure):
+    """fcd_edits: what fcd_ctc_edits_* writes (include/fcd.h)."""
+    _fields_ = [("deletion", C.c_void_p), ("insertion", C.c_void_p), ("logp", C.c_void_p)]
 
 
 class Chunk(C.Structure):
@@ -252,6 +258,7 @@ def bind(lib):
         getattr(lib, "fcd_ctc_score_" + sfx).argtypes = [P, BP, C.POINTER(Labellings), i32, i64, P]
         getattr(lib, "fcd_ctc_align_" + sfx).argtypes = [P, BP, C.POINTER(Labellings), i32, i64, C.POINTER(Alignment)]
         getattr(lib, "fcd_ctc_posterior_" + sfx).argtypes = [P, BP, C.POINTER(Labellings), i32, i64, C.POINTER(Posterior)]
+        getattr(lib, "fcd_ctc_edits_" + sfx).argtypes = [P, BP, C.POINTER(Labellings), i32, i64, C.POINTER(Edits)]
     lib.fcd_debug_set_align_workspace_cap.argtypes = [P, i64]
     for sfx in ("dev", "host"):
         getattr(lib, "fcd_crf_score_" + sfx).argtypes = [P, BP, P, i64, i64, C.POINTER(Labellings), i64, P]

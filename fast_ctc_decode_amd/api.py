@@ -844,6 +844,18 @@ class BatchResult:
                                        self.path if band else None, band, None, input_dtype,
                                        getattr(self, "_handle", None))
 
+    def ctc_edits(self, network_outputs, collapse_repeats=True, lengths=None, band=0, input_dtype=None):
+        """The deletion and insertion likelihoods of every read's result -> EditResult, deletion (n_reads, 1, stride),
+        insertion (n_reads, 1, stride + 1, N-1): ctc_edits_batch_raw on this result's own arrays (device results stay on
+        the device).  Arguments as ctc_score.  CRF results are refused (transition-scored models: a different lattice)."""
+        if isinstance(self, _CrfBatchResult) or getattr(network_outputs, "ndim", 3) != 3:
+            raise ValueError("ctc_edits covers the plain CTC searches, not CRF results")
+        if band and self.path is None:
+            raise ValueError("a band needs the result's path")
+        return ctc_edits_batch_raw(network_outputs, self.labels, self.out_len, collapse_repeats, lengths,
+                                   self.path if band else None, band, None, input_dtype,
+                                   getattr(self, "_handle", None))
+
     def crf_score(self, network_outputs, init_states, lengths=None, band=0, input_dtype=None):
         """ln P(labelling | posteriors) under the CRF model of every read's result, float64 (n_reads, 1):
         crf_score_batch_raw on this result's own arrays.  For the results of the CRF searches, with the (B,T,S,N)
@@ -1187,6 +1199,16 @@ class NBestResult:
         return ctc_posterior_batch_raw(network_outputs, self.labels, self.out_len, collapse_repeats, lengths,
                                        self.path if band else None, band, self.n_hyp, input_dtype,
                                        getattr(self, "_handle", None))
+
+    def ctc_edits(self, network_outputs, collapse_repeats=True, lengths=None, band=0, input_dtype=None):
+        """The deletion and insertion likelihoods of every hypothesis -> EditResult, deletion (n_reads, n_best, stride),
+        insertion (n_reads, n_best, stride + 1, N-1); logp NaN where i >= n_hyp[r].  ctc_edits_batch_raw on this result's
+        own arrays; CRF results are refused."""
+        if self.crf or getattr(network_outputs, "ndim", 3) != 3:
+            raise ValueError("ctc_edits covers the plain CTC searches, not CRF results")
+        return ctc_edits_batch_raw(network_outputs, self.labels, self.out_len, collapse_repeats, lengths,
+                                   self.path if band else None, band, self.n_hyp, input_dtype,
+                                   getattr(self, "_handle", None))
 
     def crf_score(self, network_outputs, init_states, lengths=None, band=0, input_dtype=None):
         """ln P(labelling | posteriors) under the CRF model of every hypothesis, float64 (n_reads, n_best); NaN where
@@ -1699,6 +1721,119 @@ def ctc_posterior(network_output, sequence, alphabet, collapse_repeats=True):
     lab[0, :len(y)] = y
     r = ctc_posterior_batch_raw(_dense(x)[None], lab, np.array([len(y)], np.uint32), collapse_repeats)
     return r.post[0, 0, :len(y)].copy(), float(r.logp[0, 0])
+
+
+# ---------------------------------------------------------------------------------------------
+# CTC deletion and insertion likelihoods of given labellings (include/fcd.h, fcd_ctc_edits_*)
+# ---------------------------------------------------------------------------------------------
+EDIT_NONE, EDIT_DELETION, EDIT_INSERTION, EDIT_SUBSTITUTION = 0, 1, 2, 3
+
+
+def _host_array(a):
+    return np.asarray(a if isinstance(a, np.ndarray) or not hasattr(a, "cpu") else a.cpu().numpy())
+
+
+class EditResult:
+    """Outcome of ctc_edits_batch_raw, float32 log-ratios against the labelling itself (include/fcd.h): deletion[r, i, k] =
+    ln P(y without label k | x) - ln P(y | x) and insertion[r, i, g, c - 1] = ln P(y with label c inserted before label g,
+    g = L: at the end | x) - ln P(y | x) for hypothesis i of read r, all alignments counted -- a positive entry is an edit
+    that explains the read better than y.  logp[r, i] (float64) is ln P(y | x), ctc_score's value.  -inf: a variant without
+    an alignment; NaN for every entry of a labelling whose P is not positive and finite; entries beyond the labelling are
+    0.  numpy for host inputs, torch tensors (same device) for device inputs."""
+
+    def __init__(self, deletion, insertion, logp):
+        self.deletion, self.insertion, self.logp = deletion, insertion, logp
+
+    def cpu(self):
+        def c(a):
+            return a if isinstance(a, np.ndarray) else a.cpu().numpy()
+        return EditResult(c(self.deletion), c(self.insertion), c(self.logp))
+
+    def best(self, out_len, posterior=None, labels=None):
+        """The best single edit of every labelling -> (kind, position, label, log_ratio), numpy arrays of shape
+        (n_reads, n_hyp): kind EDIT_NONE / EDIT_DELETION (of label `position`) / EDIT_INSERTION (of `label` before label
+        `position`) / EDIT_SUBSTITUTION (of label `position` by `label`), label 0 for a deletion, log_ratio float64.
+        With a PosteriorResult of the same labellings and their `labels`, substitutions take part: their log-ratio is
+        ln(post[k][c] / post[k][y_k]).  EDIT_NONE with 0.0 when no edit has a positive log-ratio; NaN entries take no
+        part; among equal ones the first in the order deletions, insertions, substitutions, each by position, then
+        label."""
+        r = self.cpu()
+        B, H, S = r.deletion.shape
+        nc = r.insertion.shape[3]
+        n = _host_array(out_len).astype(np.int64).reshape(B, H)
+        with np.errstate(all="ignore"):
+            d = np.where((np.arange(S) < n[..., None]) & ~np.isnan(r.deletion), r.deletion.astype(np.float64), -np.inf)
+            ok = (np.arange(S + 1) <= n[..., None])[..., None] & ~np.isnan(r.insertion)
+            parts = [d, np.where(ok, r.insertion.astype(np.float64), -np.inf).reshape(B, H, -1)]
+            if posterior is not None:
+                if labels is None:
+                    raise ValueError("substitutions need the labels next to the PosteriorResult")
+                post = posterior.cpu().post.astype(np.float64)
+                lab = _host_array(labels).astype(np.int64).reshape(B, H, S)
+                own = (lab >= 1) & (lab <= nc) & (np.arange(S) < n[..., None])
+                conf = np.take_along_axis(post, np.where(own, lab - 1, 0)[..., None], 3)
+                sub = np.log(post) - np.log(conf)
+                keep = own[..., None] & (np.arange(nc) != (lab - 1)[..., None]) & ~np.isnan(sub)
+                parts.append(np.where(keep, sub, -np.inf).reshape(B, H, -1))
+        every = np.concatenate(parts, 2)
+        idx = every.argmax(2) if every.shape[2] else np.zeros((B, H), np.int64)
+        val = np.take_along_axis(every, idx[..., None], 2)[..., 0] if every.shape[2] else np.full((B, H), -np.inf)
+        n_ins = (S + 1) * nc
+        kind = np.where(idx < S, EDIT_DELETION, np.where(idx < S + n_ins, EDIT_INSERTION, EDIT_SUBSTITUTION))
+        rest = np.where(kind == EDIT_INSERTION, idx - S, idx - S - n_ins)
+        pos = np.where(kind == EDIT_DELETION, idx, rest // max(nc, 1))
+        lab_out = np.where(kind == EDIT_DELETION, 0, rest % max(nc, 1) + 1)
+        none = ~(val > 0.0)
+        return (np.where(none, EDIT_NONE, kind).astype(np.int32), np.where(none, 0, pos).astype(np.int32),
+                np.where(none, 0, lab_out).astype(np.int32), np.where(none, 0.0, val))
+
+
+def ctc_edits_batch_raw(network_outputs, labels, label_lengths, collapse_repeats=True, lengths=None, paths=None,
+                        band=0, n_valid=None, input_dtype=None, handle=None):
+    """CTC deletion and insertion likelihoods: for every label of every labelling how much better or worse the read is
+    explained without it, and for every gap and every label how much better or worse with that label inserted there, as
+    log-ratios against the labelling itself, summed over every alignment in one forward and one backward walk
+    (include/fcd.h, fcd_ctc_edits_*).  With ctc_posterior_batch_raw's substitutions: every labelling one edit away.
+    -> EditResult with deletion (B, n_hyp, stride), insertion (B, n_hyp, stride + 1, N-1) float32 and logp (B, n_hyp)
+    float64.
+
+    Arguments as ctc_score_batch_raw: band=0 walks the exact lattice, band=W > 0 the window within W labels of `paths`.
+    Limits: windows of at most 510 states (bands up to 126, exact mode up to 254 rows or labels) and N - 1 <= 8.
+    Device tensors in: torch tensors on the same device, enqueued on torch's current stream, not synchronised.
+    numpy in: numpy out."""
+    band = _check_band(band, paths)
+    h, b, y, (B, n_hyp, stride), dev, keep = _lattice_inputs(network_outputs, labels, label_lengths, lengths, paths, band,
+                                                             n_valid, input_dtype, handle)
+    nc = int(b.N) - 1
+    if dev is not None:
+        import torch
+        dele = torch.zeros((B, n_hyp, stride), dtype=torch.float32, device=dev)
+        ins = torch.zeros((B, n_hyp, stride + 1, nc), dtype=torch.float32, device=dev)
+        logp = torch.empty((B, n_hyp), dtype=torch.float64, device=dev)
+        out = nat.Edits(dele.data_ptr(), ins.data_ptr(), logp.data_ptr())
+        h.check(h.lib.fcd_ctc_edits_dev(h.ptr, C.byref(b), C.byref(y), int(bool(collapse_repeats)), band, C.byref(out)))
+        return EditResult(dele, ins, logp)
+    dele = np.zeros((B, n_hyp, stride), np.float32)
+    ins = np.zeros((B, n_hyp, stride + 1, nc), np.float32)
+    logp = np.empty((B, n_hyp), np.float64)
+    out = nat.Edits(dele.ctypes.data, ins.ctypes.data, logp.ctypes.data)
+    h.check(h.lib.fcd_ctc_edits_host(h.ptr, C.byref(b), C.byref(y), int(bool(collapse_repeats)), band, C.byref(out)))
+    return EditResult(dele, ins, logp)
+
+
+def ctc_edits(network_output, sequence, alphabet, collapse_repeats=True):
+    """The deletion and insertion likelihoods of one string against one (T, N) float32 posterior matrix, exact lattice:
+    -> (deletion, insertion, logp) with deletion an (L,) and insertion an (L + 1, N-1) float32 array of log-ratios
+    (insertion[g, c - 1]: alphabet[c] inserted before character g) and logp = ln P(sequence | network_output).  Argument
+    checks as ctc_score."""
+    x = _as_f32(network_output, 2, "network_output")
+    alpha = _seq_to_vec(alphabet)
+    _check_greedy_alphabet(len(alpha), x.shape[1])
+    y = _sequence_labels(sequence, alpha, "ctc_edits")
+    lab = np.zeros((1, max(len(y), 1)), np.uint8)
+    lab[0, :len(y)] = y
+    r = ctc_edits_batch_raw(_dense(x)[None], lab, np.array([len(y)], np.uint32), collapse_repeats)
+    return r.deletion[0, 0, :len(y)].copy(), r.insertion[0, 0, :len(y) + 1].copy(), float(r.logp[0, 0])
 
 
 # ---------------------------------------------------------------------------------------------

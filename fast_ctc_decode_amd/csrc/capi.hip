@@ -1582,7 +1582,7 @@ int fcd_unpack_gathered_dev(fcd_handle *h, const uint8_t *gathered, int64_t stri
 }
 
 // ---- the lattice of given labellings: CTC forward score (ctc_score.hip), CTC forced alignment (ctc_align.hip), both
-// under a CRF model (crf_lattice.hip), and the CTC substitution posteriors (ctc_posterior.hip) ----
+// under a CRF model (crf_lattice.hip), and the CTC substitution posteriors and edit likelihoods (ctc_posterior.hip) ----
 int fcd_debug_set_align_workspace_cap(fcd_handle *h, int64_t bytes) {
     if (!h || bytes < 0) return FCD_E_INVALID;
     std::lock_guard<std::recursive_mutex> g(h->mu);
@@ -1591,8 +1591,8 @@ int fcd_debug_set_align_workspace_cap(fcd_handle *h, int64_t bytes) {
 }
 
 namespace {
-// One fcd_{ctc,crf}_{score,align}_{dev,host} or fcd_ctc_posterior_{dev,host} call: the score writes `logp`, the alignment
-// `out`, the posteriors `post`.
+// One fcd_{ctc,crf}_{score,align}_{dev,host}, fcd_ctc_posterior_{dev,host} or fcd_ctc_edits_{dev,host} call: the score
+// writes `logp`, the alignment `out`, the posteriors `post`, the edit likelihoods `edits`.
 struct LatticeCall {
     bool crf, align;
     const fcd_batch *in;
@@ -1605,11 +1605,14 @@ struct LatticeCall {
     const fcd_alignment *out;
     bool posterior = false;
     const fcd_posterior *post = nullptr;
+    bool edit = false;
+    const fcd_edits *edits = nullptr;
 };
 
 int lattice_check(fcd_handle *h, const LatticeCall &c) {
     if (c.align && !c.out) return fail(h, FCD_E_INVALID, "null alignment");
     if (c.posterior && !c.post) return fail(h, FCD_E_INVALID, "null posterior");
+    if (c.edit && !c.edits) return fail(h, FCD_E_INVALID, "ctc_edits: null output");
     const fcd_batch *in = c.in;
     const fcd_labellings *y = c.y;
     int rc = check_batch(h, in, c.crf);
@@ -1626,8 +1629,11 @@ int lattice_check(fcd_handle *h, const LatticeCall &c) {
     if (c.band > 0 && !y->path) return fail(h, FCD_E_INVALID, "a band needs the labellings' path");
     if (y->stride < 0) return fail(h, FCD_E_INVALID, "negative stride");
     if (in->n_reads > 0 && (!y->labels || !y->len ||
-                            !(c.posterior ? (const void *)c.post->post : c.align ? (const void *)c.out->start : (const void *)c.logp)))
-        return fail(h, FCD_E_INVALID, c.posterior ? "null labels/len/post" : c.align ? "null labels/len/start" : "null labels/len/logp");
+                            !(c.edit ? (const void *)c.edits->deletion : c.posterior ? (const void *)c.post->post
+                              : c.align ? (const void *)c.out->start : (const void *)c.logp)))
+        return fail(h, FCD_E_INVALID, c.edit ? "ctc_edits: null labels/len/deletion" : c.posterior ? "null labels/len/post"
+                                      : c.align ? "null labels/len/start" : "null labels/len/logp");
+    if (c.edit && in->n_reads > 0 && !c.edits->insertion) return fail(h, FCD_E_INVALID, "ctc_edits: null insertion");
     if (in->n_reads * y->n_hyp >= (1ll << 31)) return fail(h, FCD_E_UNSUPPORTED, "more than 2^31 labellings in one call");
     if (c.crf) {
         switch (crf_lattice_unsupported(in->T, in->S, y->stride, std::min<int64_t>(c.band, 1ll << 28))) {
@@ -1642,12 +1648,13 @@ int lattice_check(fcd_handle *h, const LatticeCall &c) {
                                                      : "ctc_score: the exact lattice does not fit the 160 KiB of LDS: use a band");
     }
     if (c.align && in->n_reads > 0 && !c.out->count) return fail(h, FCD_E_INVALID, "null count");
-    if (c.posterior) {
+    if (c.edit || c.posterior) {  // (one set of limits: both walk ctc_posterior.hip's register-resident window)
+        const std::string who = c.edit ? "ctc_edits" : "ctc_posterior";
         switch (ctc_posterior_unsupported(in->T, y->stride, c.band, in->N)) {
-        case 1: return fail(h, FCD_E_UNSUPPORTED, c.band > 0 ? "ctc_posterior: the band's window exceeds 510 states: use a narrower band"
-                                                             : "ctc_posterior: the exact lattice exceeds 510 states: use a band");
-        case 2: return fail(h, FCD_E_UNSUPPORTED, "ctc_posterior: more than 8 labels besides the blank");
-        case 3: return fail(h, FCD_E_UNSUPPORTED, "ctc_posterior: labellings beyond 28480 labels do not fit the 64 KiB of LDS: use a smaller stride");
+        case 1: return fail(h, FCD_E_UNSUPPORTED, (who + (c.band > 0 ? ": the band's window exceeds 510 states: use a narrower band"
+                                                                     : ": the exact lattice exceeds 510 states: use a band")).c_str());
+        case 2: return fail(h, FCD_E_UNSUPPORTED, (who + ": more than 8 labels besides the blank").c_str());
+        case 3: return fail(h, FCD_E_UNSUPPORTED, (who + ": labellings beyond 28480 labels do not fit the 64 KiB of LDS: use a smaller stride").c_str());
         default: break;
         }
     }
@@ -1757,7 +1764,27 @@ int lattice_posterior(fcd_handle *h, const LatticeCall &c) {
         });
 }
 
+int lattice_edits(fcd_handle *h, const LatticeCall &c) {
+    const fcd_batch *in = c.in;
+    const fcd_labellings *y = c.y;
+    const fcd_edits *out = c.edits;
+    const size_t nc = (size_t)in->N - 1, n_rows = (size_t)in->n_reads * (size_t)y->n_hyp;
+    const size_t del_row = (size_t)y->stride, ins_row = ((size_t)y->stride + 1) * nc;  // entries of one labelling
+    const int64_t bnd = std::min<int64_t>(c.band, 1ll << 28);
+    return lattice_grouped(
+        h, c, ctc_posterior_row_bytes(in->T, y->stride, c.band), std::min<int64_t>(4ll << 30, workspace_budget(h)), out->logp,
+        [&](CallScope &sc) {
+            sc.add(out->deletion, n_rows * del_row * 4);
+            sc.add(out->insertion, n_rows * ins_row * 4);
+        },
+        [&](const BatchDesc &d, const ScoreDesc &yd, int64_t, int64_t row0, double *logp, unsigned char *alpha, hipStream_t stream) {
+            return launch_ctc_edits(d, yd, c.collapse, bnd, out->deletion + (size_t)row0 * del_row,
+                                    out->insertion + (size_t)row0 * ins_row, logp, alpha, stream);
+        });
+}
+
 int lattice_run(fcd_handle *h, const LatticeCall &c) {
+    if (c.edit) return lattice_edits(h, c);
     return c.posterior ? lattice_posterior(h, c) : (c.align ? lattice_align(h, c) : lattice_score(h, c));
 }
 
@@ -1796,7 +1823,10 @@ int lattice_host(fcd_handle *h, const LatticeCall &c) {
     const int i_qual = c.align ? st.out(c.out->qual, cells * 4, true) : -1;
     // (posterior entries the kernel does not write -- k >= len -- come back as 0)
     const int i_sub = c.posterior ? st.out(c.post->post, cells * ((size_t)in->N - 1) * 4, true) : -1;
-    const int i_logp = st.out(c.posterior ? c.post->logp : (c.align ? c.out->logp : c.logp), n_rows * 8);
+    // (edit entries the kernel does not write -- k >= len, g > len -- come back as 0)
+    const int i_del = c.edit ? st.out(c.edits->deletion, cells * 4, true) : -1;
+    const int i_ins = c.edit ? st.out(c.edits->insertion, (cells + n_rows) * ((size_t)in->N - 1) * 4, true) : -1;
+    const int i_logp = st.out(c.edit ? c.edits->logp : c.posterior ? c.post->logp : (c.align ? c.out->logp : c.logp), n_rows * 8);
     rc = st.commit();
     if (rc) return rc;
     fcd_batch din = *in;
@@ -1816,6 +1846,8 @@ int lattice_host(fcd_handle *h, const LatticeCall &c) {
     d.out = &dout;
     const fcd_posterior dpost{st.at<float>(i_sub), st.at<double>(i_logp)};
     d.post = &dpost;
+    const fcd_edits dedits{st.at<float>(i_del), st.at<float>(i_ins), st.at<double>(i_logp)};
+    d.edits = &dedits;
     rc = lattice_run(h, d);
     if (rc) return rc;
     return st.fetch();
@@ -1862,6 +1894,20 @@ int fcd_ctc_posterior_host(fcd_handle *h, const fcd_batch *in, const fcd_labelli
     if (!h) return FCD_E_INVALID;
     std::lock_guard<std::recursive_mutex> whole_call(h->mu);  // staging .. copy-back, see run_host
     return lattice_host(h, LatticeCall{false, false, in, y, band, collapse_repeats != 0, nullptr, 0, 0, nullptr, nullptr, true, out});
+}
+
+int fcd_ctc_edits_dev(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int collapse_repeats, int64_t band,
+                      const fcd_edits *out) {
+    if (!h) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> g(h->mu);
+    return lattice_dev(h, LatticeCall{false, false, in, y, band, collapse_repeats != 0, nullptr, 0, 0, nullptr, nullptr, false, nullptr, true, out});
+}
+
+int fcd_ctc_edits_host(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int collapse_repeats, int64_t band,
+                       const fcd_edits *out) {
+    if (!h) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> whole_call(h->mu);  // staging .. copy-back, see run_host
+    return lattice_host(h, LatticeCall{false, false, in, y, band, collapse_repeats != 0, nullptr, 0, 0, nullptr, nullptr, false, nullptr, true, out});
 }
 
 int fcd_crf_score_dev(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init, int64_t init_stride,

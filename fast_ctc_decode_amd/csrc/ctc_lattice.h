@@ -30,6 +30,7 @@ struct ScoreParams {
     double *logp;
     int cap;      // LDS kernel: states per alpha buffer
     int lab_cap;  // labels the LDS copy of a labelling holds
+    int slack = 0;  // states by which window_k's two reachability cuts are relaxed (ctc_posterior.hip's edit walk: 2)
 };
 
 struct Lds {
@@ -141,15 +142,16 @@ __device__ __forceinline__ void fill_tile(const ScoreParams &p, const Lds &lds, 
 }
 
 // live states of row t: the band around the path (k = k(t), read only when banded), cut to what can be reached and can
-// still reach the end
+// still reach the end -- in the labelling itself; p.slack more states on either side for a walk that also follows
+// labellings one label shorter (their alignments reach a state a row earlier and may leave it a row later)
 __device__ __forceinline__ void window_k(const ScoreParams &p, const Row &rw, int t, int k, int *lo, int *hi) {
     int l = 0, h = 2 * rw.L;
     if (p.band > 0) {
         l = max(0, 2 * (k - p.band) - 2);
         h = min(h, 2 * (k + p.band));
     }
-    *hi = min(h, 2 * t + 1);
-    *lo = max(l, 2 * rw.L - 2 * (rw.Tr - 1 - t) - 2);
+    *hi = min(h, 2 * t + 1 + p.slack);
+    *lo = max(l, 2 * rw.L - 2 * (rw.Tr - 1 - t) - 2 - p.slack);
 }
 
 // ... of row t, the tile's row i

@@ -4,7 +4,9 @@
 //
 // Two launches, one wavefront per labelling each, the register-resident window of ctc_score.hip (K consecutive states
 // per lane, state s in slot s mod 64K):
-//   post_fwd_kernel<K>       ctc_score's forward step, unchanged (its logp is ctc_score's bit for bit).  Every row's live
+//   post_fwd_kernel<K>       ctc_score's forward step (under fcd_ctc_posterior_* its logp is ctc_score's bit for bit; under
+//                            fcd_ctc_edits_* the relaxed window can move a row's scale, and the value is ctc_score's within
+//                            its tolerance -- that much is tested, not the bits).  Every row's live
 //                            cells go to the workspace by SLOT, scaled by 2^-kAlphaDown (exact), and the row's exponent
 //                            next to them: T * 64K floats, then T exponent words, per labelling.
 //   post_back_kernel<K, NC>  walks the rows from T_r - 1 down.  b_t[s] = p[t][z[s]] * beta_t[s] obeys the mirror image of
@@ -21,6 +23,21 @@
 // at the largest X seen so far, kAccDown bits below it so that the sum over the rows cannot overflow: a term is scaled by
 // the power of two 2^(X_t - Xmax - kAccDown), acc by 2^(Xmax_old - Xmax_new) when Xmax rises.  Both exact.
 // Every term is non-negative; one rounding per product and per sum; no fused multiply-add (-ffp-contract=off).
+//
+// fcd_ctc_edits_* (the deletion and insertion likelihoods of the same labellings) is the same pair of launches with another
+// second pass:
+//   edit_back_kernel<K, NC>  the same walk, the same b.  A label state s = 2k + 1 carries ONE accumulator,
+//                              accD += (alpha_{t-1}[s-1] + [k >= 1, y_{k-1} != y_{k+1} or no collapse] alpha_{t-1}[s-2]) * b_t[s+2]
+//                            -- the alignments that step over label k --, a blank state s = 2g carries for each label c
+//                              u_t(c)   = (u_{t+1}(c) [collapse] + b_{t+1}[s] + [c != y_g or no collapse] b_{t+1}[s+1]) * p[t][c]
+//                                         the backward value of a label c standing in gap g, and
+//                              accI(c) += (alpha_{t-1}[s] + [s >= 1, c != y_{g-1} or no collapse] alpha_{t-1}[s-1]) * u_t(c)
+//                            When s leaves the window (or after row 0) the lane stores ln(acc) - ln P(y | x).
+// A labelling one label shorter reaches a state a row earlier and may leave it a row later than y's own alignments do, so
+// both launches relax window_k's two reachability cuts by two states (ScoreParams::slack); the band's window, and with it
+// the number of slots, is what it was.  No alignment of y passes through such a cell, so a NaN or an infinity there must not
+// reach y's own values: where nothing enters a cell outside the unrelaxed cuts (the sum is exactly 0) the posterior is not
+// multiplied in (core_states); likewise u where nothing leaves the gap, and a term where nothing enters it.
 #include <math.h>
 
 #include <algorithm>
@@ -36,10 +53,26 @@ constexpr int kAccDown = 40;     // a term (below 2^121) enters acc below 2^81: 
 
 struct PostParams {
     ScoreParams s;        // (s.logp is never null: the launcher lends scratch when the caller wants none)
-    float *post;          // [labellings of this launch * stride * (N - 1)]
+    float *post;          // [labellings of this launch * stride * (N - 1)]                  (fcd_ctc_posterior_*)
+    float *del, *ins;     // [.. * stride], [.. * (stride + 1) * (N - 1)]                     (fcd_ctc_edits_*)
     float *alpha;         // the stored forward rows, alpha_words per labelling of this launch
     int64_t alpha_words;
 };
+
+// bit r: the lane's state r (the one >= lo) lies inside window_k's unrelaxed cuts -- a cell an alignment of y can pass
+// through.  p.slack = 0: every live state.
+template <int K>
+__device__ __forceinline__ uint32_t core_states(const ScoreParams &p, const Row &rw, int lane, int t, int lo) {
+    if (p.slack == 0) return ~0u;
+    const int top = 2 * t + 1, bottom = 2 * rw.L - 2 * (rw.Tr - 1 - t) - 2;
+    uint32_t m = 0;
+#pragma unroll
+    for (int r = 0; r < K; ++r) {
+        const int s = slot_state<K>(lane, r, lo);
+        m |= (s <= top && s >= bottom ? 1u : 0u) << r;
+    }
+    return m;
+}
 
 // ---- pass 1: ctc_score's score_reg_kernel, storing what it computes ----
 template <int K>
@@ -74,6 +107,7 @@ __global__ __launch_bounds__(64) void post_fwd_kernel(PostParams q) {
                     if (slot_state<K>(lane, r, lo_prev) <= hi - C) a[r] = 0.0f;
             }
             const float p1 = from_prev_lane(a[K - 1]), p2 = from_prev_lane(a[K - 2]);
+            const uint32_t core = core_states<K>(p, rw, lane, t0 + i, lo);
             float u[K];
             int ex[K];
             int emax = kNoExp;
@@ -92,6 +126,7 @@ __global__ __launch_bounds__(64) void post_fwd_kernel(PostParams q) {
                     u[r] = sum * in.pm0;
                     ex[r] = in.pe0;
                 }
+                if (!((core >> r) & 1) && sum == 0.0f) u[r] = 0.0f;  // (nothing enters a cell y's alignments never see)
                 const int e = finite_exp(u[r]);
                 emax = max(emax, ((in.in_mask >> r) & 1) && e != kNoExp ? e + ex[r] : kNoExp);
             }
@@ -322,6 +357,237 @@ __global__ __launch_bounds__(64) void post_back_kernel(PostParams q) {
     }
 }
 
+// ---- pass 2 of fcd_ctc_edits_* ----
+// ln(v * 2^e) - lp, what the outputs hold: the logarithm of the mantissa in f32 (in [ln 0.5, 0): its rounding is below
+// 2^-24), the exponents and the labelling's own ln P in float64.  v = 0: -inf; a NaN: NaN.
+__device__ __forceinline__ float log_ratio(float v, int64_t e, double lp) {
+    if (v == 0.0f) return -INFINITY;
+    if (!(v > 0.0f) || v - v != 0.0f) return NAN;
+    int ex;
+    const float m = frexpf(v, &ex);
+    return (float)((double)logf(m) + (double)(e + ex) * 0.693147180559945309417232121458 - lp);
+}
+
+// every entry the row owns -- k < min(len, stride), g <= min(len, stride) -- set to v
+__device__ __forceinline__ void fill_edits(const PostParams &q, float v) {
+    const int64_t row = blockIdx.x, nc = q.s.in.N - 1;
+    const int64_t n = min((int64_t)q.s.y.len[row], q.s.y.stride);
+    for (int64_t e = threadIdx.x; e < n; e += blockDim.x) q.del[row * q.s.y.stride + e] = v;
+    for (int64_t e = threadIdx.x; e < (n + 1) * nc; e += blockDim.x) q.ins[row * (q.s.y.stride + 1) * nc + e] = v;
+}
+
+template <int NC>
+__device__ __forceinline__ void store_ins(float *ins, int g, int nc, const float (&acc)[NC], int64_t e, double lp) {
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+        if (c < nc) ins[(int64_t)g * nc + c] = log_ratio(acc[c], e, lp);
+}
+
+template <int K, int NC>
+__global__ __launch_bounds__(64) void edit_back_kernel(PostParams q) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr int C = 64 * K, H = K / 2;
+    const ScoreParams &p = q.s;
+    const Lds lds = carve(smem, p.lab_cap);
+    Row rw;
+    const bool walk = prologue(p, lds, &rw);  // (the forward launch wrote this row's logp already; the same value again)
+    const double lp = p.logp[blockIdx.x];
+    if (lp - lp != 0.0) {  // P = 0, a NaN on the way, or not a labelling
+        fill_edits(q, NAN);
+        return;
+    }
+    fill_edits(q, -INFINITY);  // an edit no row carries has probability 0
+    if (!walk) return;         // (T_r = 0 and L = 0: P(y | x) = 1, and no insertion has an alignment)
+    __syncthreads();           // the fill is in place before another lane's flush writes over it
+    const int lane = threadIdx.x, nc = rw.N - 1, L = rw.L, Lm = max(L - 1, 0);
+    const float *am = q.alpha + (int64_t)blockIdx.x * q.alpha_words;
+    const int *ae = reinterpret_cast<const int *>(am + (int64_t)p.in.T * C);
+    float *del = q.del + (int64_t)blockIdx.x * p.y.stride;
+    float *ins = q.ins + (int64_t)blockIdx.x * (p.y.stride + 1) * nc;
+    float b[K], u[H][NC], accI[H][NC], accD[H];
+#pragma unroll
+    for (int r = 0; r < K; ++r) b[r] = 0.0f;
+#pragma unroll
+    for (int h = 0; h < H; ++h) {
+        accD[h] = 0.0f;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) u[h][c] = accI[h][c] = 0.0f;
+    }
+    int64_t eb = 0, xmax = 0;
+    bool first = true, any = false;
+    int lo = 0, hi = 0, lo_n = 0, hi_n = 0;
+    for (int t0 = (rw.Tr - 1) / rw.rows_per_tile * rw.rows_per_tile; t0 >= 0; t0 -= rw.rows_per_tile) {
+        const int rc = min(rw.rows_per_tile, rw.Tr - t0);
+        fill_tile(p, lds, rw, t0, rc);
+        if (p.band > 0 && t0 > 0) {  // k(t0 - 1): the window of the alpha row that row t0 reads
+            if (lane == 0) {
+                int a0 = 0, a1 = L;
+                while (a0 < a1) {
+                    const int mid = (a0 + a1) >> 1;
+                    if (rw.path[mid] <= (uint32_t)(t0 - 1)) a0 = mid + 1;
+                    else a1 = mid;
+                }
+                lds.misc[kKrowBefore] = a0;
+            }
+            __syncthreads();
+        }
+        for (int i = rc - 1; i >= 0; --i) {
+            const int t = t0 + i;
+            window(p, lds, rw, t, i, &lo, &hi);
+            // alpha_{t-1}, by slot; row -1: all mass on state 0, exponent 0
+            int lo_p = 0, hi_p = 0;
+            float av[K];
+            int64_t x_t = 0;
+            if (t > 0) {
+                window_k(p, rw, t - 1, p.band > 0 ? (i > 0 ? lds.krow[i - 1] : lds.misc[kKrowBefore]) : 0, &lo_p, &hi_p);
+                const float *row = am + (int64_t)(t - 1) * C + lane * K;
+#pragma unroll
+                for (int r = 0; r < K; ++r) av[r] = slot_state<K>(lane, r, lo_p) <= hi_p ? row[r] : 0.0f;
+                x_t = ae[t - 1];
+            } else {
+#pragma unroll
+                for (int r = 0; r < K; ++r) av[r] = (lane == 0 && r == 0) ? 1.0f : 0.0f;
+            }
+            const float av_prev = from_prev_lane(av[K - 1]);
+            if (first) {  // "row T_r": all mass on state 2L
+#pragma unroll
+                for (int r = 0; r < K; ++r) b[r] = slot_state<K>(lane, r, lo) == 2 * L ? 1.0f : 0.0f;
+                first = false;
+                lo_n = lo;
+                // the last label's deletion: the two final states of the shortened labelling, off the last forward row
+                if (lane == 0 && L >= 1) {
+                    const float *row = am + (int64_t)t * C;
+                    float v = 0.0f;
+                    if (2 * L - 1 >= lo && 2 * L - 1 <= hi) {
+                        if (2 * L - 2 >= lo) v = row[(2 * L - 2) % C];
+                        if (L >= 2 && 2 * L - 3 >= lo) v += row[(2 * L - 3) % C];
+                    }
+                    del[L - 1] = log_ratio(v, ae[t], lp);
+                }
+            } else {  // the states that were live at row t + 1 and are not at row t: their edits are complete
+#pragma unroll
+                for (int r = 0; r < K; ++r) {
+                    const int s = slot_state<K>(lane, r, lo_n), h = r / 2;
+                    if (s > hi) {  // (b stays: row t still reads b_{t+1} of the states above its window)
+                        if (r & 1) {
+                            if (s <= hi_n && (s >> 1) != L - 1) del[s >> 1] = log_ratio(accD[h], xmax + kAccDown, lp);
+                            accD[h] = 0.0f;
+                        } else {
+                            if (s <= hi_n) store_ins<NC>(ins, s >> 1, nc, accI[h], xmax + kAccDown, lp);
+#pragma unroll
+                            for (int c = 0; c < NC; ++c) u[h][c] = accI[h][c] = 0.0f;
+                        }
+                    }
+                }
+            }
+            const float n1 = from_next_lane(b[0]), n2 = from_next_lane(b[1]);
+            const float pm0 = lds.pm[i * rw.N];
+            const int pe0 = lds.pe[i * rw.N];
+            float pmc[NC];
+            int pec[NC];
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                pmc[c] = lds.pm[i * rw.N + min(c + 1, nc)];
+                pec[c] = lds.pe[i * rw.N + min(c + 1, nc)];
+            }
+            const uint32_t core = core_states<K>(p, rw, lane, t, lo);
+            float ub[K], uu[H][NC], eD[H], e1[H], e2[H];
+            int ex[K], yprev[H];
+            uint32_t live = 0;
+            int emax = kNoExp;
+#pragma unroll
+            for (int r = 0; r < K; ++r) {
+                const int s = slot_state<K>(lane, r, lo), h = r / 2;
+                const bool in = s <= hi;
+                live |= (in ? 1u : 0u) << r;
+                // b_{t+1} of s, s + 1, s + 2: a state below row t + 1's window is not what its slot holds
+                const float y0 = s >= lo_n ? b[r] : 0.0f;
+                const float y1 = s + 1 >= lo_n ? (r + 1 < K ? b[r + 1] : n1) : 0.0f;
+                const float y2 = s + 2 >= lo_n ? (r + 2 < K ? b[r + 2] : (r + 2 == K ? n1 : n2)) : 0.0f;
+                if (r & 1) {
+                    const int k = in ? (s >> 1) : 0;  // (a dead slot reads valid addresses and is masked below)
+                    const int info = lds.lab[k], inext = lds.lab[min(k + 1, Lm)], iprev = lds.lab[max(k - 1, 0)];
+                    const int y = in ? (info & 0xFF) : 0;
+                    float sum = p.collapse ? y0 + y1 : y1;
+                    sum += (k + 1 < L && (!p.collapse || (inext & 0x100))) ? y2 : 0.0f;
+                    ub[r] = (!((core >> r) & 1) && sum == 0.0f) ? 0.0f : sum * lds.pm[i * rw.N + y];
+                    ex[r] = lds.pe[i * rw.N + y];
+                    // what steps over label k from row t - 1 (a state above that row's window is not in its slot)
+                    const float x1 = av[r >= 1 ? r - 1 : 0], x2 = r >= 2 ? av[r - 2] : av_prev;
+                    const bool skip = k >= 1 && k + 1 < L && (!p.collapse || ((iprev ^ inext) & 0xFF));
+                    eD[h] = ((in && s - 1 <= hi_p) ? x1 : 0.0f) + ((in && skip && s - 2 <= hi_p) ? x2 : 0.0f);
+                } else {
+                    ub[r] = (!((core >> r) & 1) && y0 + y1 == 0.0f) ? 0.0f : (y0 + y1) * pm0;
+                    ex[r] = pe0;
+                    const int g = in ? (s >> 1) : 0;
+                    const int ynext = g < L ? (lds.lab[min(g, Lm)] & 0xFF) : 0;  // (0: no label c equals it)
+                    yprev[h] = g > 0 ? (lds.lab[min(g - 1, Lm)] & 0xFF) : 0;
+#pragma unroll
+                    for (int c = 0; c < NC; ++c) {
+                        float exit = p.collapse ? u[h][c] + y0 : y0;
+                        exit += (p.collapse && c + 1 == ynext) ? 0.0f : y1;  // (b[s + 1] is 0 beyond state 2L)
+                        uu[h][c] = exit == 0.0f ? 0.0f : exit * pmc[c];  // (nothing leaves the gap: no alignment reads p[t][c])
+                        const int e = finite_exp(uu[h][c]);
+                        emax = max(emax, in && c < nc && e != kNoExp ? e + pec[c] : kNoExp);
+                    }
+                    // what enters the gap from row t - 1
+                    const float x0 = av[r], x1 = r >= 1 ? av[r - 1] : av_prev;
+                    e1[h] = (in && s <= hi_p) ? x0 : 0.0f;
+                    e2[h] = (in && s >= 1 && s - 1 <= hi_p) ? x1 : 0.0f;
+                }
+                const int e = finite_exp(ub[r]);
+                emax = max(emax, in && e != kNoExp ? e + ex[r] : kNoExp);
+            }
+            emax = wave_imax(emax);
+            const int sh = emax == kNoExp ? 0 : kTargetB - emax;
+            eb -= sh;
+            x_t += eb;  // the exponent of this row's terms
+            if (!any || x_t > xmax) {
+                if (any) {
+                    const int d = (int)max(xmax - x_t, (int64_t)-512);
+#pragma unroll
+                    for (int h = 0; h < H; ++h) {
+                        accD[h] = ldexpf(accD[h], d);
+#pragma unroll
+                        for (int c = 0; c < NC; ++c) accI[h][c] = ldexpf(accI[h][c], d);
+                    }
+                }
+                xmax = x_t;
+                any = true;
+            }
+            const int dt = (int)max(x_t - xmax, (int64_t)-512) - kAccDown;
+#pragma unroll
+            for (int r = 0; r < K; ++r) b[r] = ((live >> r) & 1) ? ldexpf(ub[r], min(max(ex[r] + sh, -512), 512)) : 0.0f;
+            const float m1 = from_next_lane(b[1]);  // b_t of the next lane's first label state
+#pragma unroll
+            for (int h = 0; h < H; ++h) {
+                const bool in = (live >> (2 * h)) & 1;
+                const float above = 2 * h + 3 < K ? b[min(2 * h + 3, K - 1)] : m1;  // b_t[s + 2] of the pair's label state s
+                accD[h] += eD[h] == 0.0f ? 0.0f : ldexpf(eD[h] * above, dt);  // (nothing enters: no alignment, whatever lies above)
+#pragma unroll
+                for (int c = 0; c < NC; ++c) {
+                    u[h][c] = (in && c < nc) ? ldexpf(uu[h][c], min(max(pec[c] + sh, -512), 512)) : 0.0f;
+                    const float entry = e1[h] + ((p.collapse && c + 1 == yprev[h]) ? 0.0f : e2[h]);
+                    accI[h][c] += entry == 0.0f ? 0.0f : ldexpf(entry * u[h][c], dt);
+                }
+            }
+            lo_n = lo;
+            hi_n = hi;
+        }
+    }
+    // the states that are live at row 0
+#pragma unroll
+    for (int r = 0; r < K; ++r) {
+        const int s = slot_state<K>(lane, r, lo), h = r / 2;
+        if (s > hi) continue;
+        if (r & 1) {
+            if ((s >> 1) != L - 1) del[s >> 1] = log_ratio(accD[h], xmax + kAccDown, lp);
+        } else {
+            store_ins<NC>(ins, s >> 1, nc, accI[h], xmax + kAccDown, lp);
+        }
+    }
+}
+
 int reg_states_per_lane(int64_t T, int64_t stride, int64_t band) {  // 0: the window does not fit the registers
     const int64_t states = ctc_score_window_states(T, stride, band);
     return states + 2 <= 128 ? 2 : (states + 2 <= 256 ? 4 : (states + 2 <= 384 ? 6 : (states + 2 <= 512 ? 8 : 0)));
@@ -350,10 +616,8 @@ size_t ctc_posterior_row_bytes(int64_t T, int64_t stride, int64_t band) {
     return ((size_t)std::max<int64_t>(T, 1) * (64 * k + 1) * 4 + 255) & ~(size_t)255;
 }
 
-hipError_t launch_ctc_posterior(const BatchDesc &in, const ScoreDesc &y, int collapse, int64_t band, float *post,
-                                double *logp, unsigned char *alpha, hipStream_t stream) {
-    const int64_t rows = in.n_reads * y.n_hyp;
-    if (rows <= 0) return hipSuccess;
+namespace {
+PostParams post_params(const BatchDesc &in, const ScoreDesc &y, int collapse, int64_t band, double *logp, unsigned char *alpha) {
     PostParams q;
     q.s.in = in;
     q.s.y = y;
@@ -362,9 +626,26 @@ hipError_t launch_ctc_posterior(const BatchDesc &in, const ScoreDesc &y, int col
     q.s.logp = logp;
     q.s.cap = 0;
     q.s.lab_cap = (int)std::max<int64_t>(std::min(in.T, y.stride), 1);
-    q.post = post;
+    q.post = q.del = q.ins = nullptr;
     q.alpha = reinterpret_cast<float *>(alpha);
     q.alpha_words = (int64_t)(ctc_posterior_row_bytes(in.T, y.stride, band) / 4);
+    return q;
+}
+
+template <int K>
+void launch_edits(const PostParams &q, int nc, dim3 grid, size_t lds, hipStream_t stream) {
+    hipLaunchKernelGGL(post_fwd_kernel<K>, grid, dim3(64), lds, stream, q);
+    if (nc <= 4) hipLaunchKernelGGL((edit_back_kernel<K, 4>), grid, dim3(64), lds, stream, q);
+    else hipLaunchKernelGGL((edit_back_kernel<K, 8>), grid, dim3(64), lds, stream, q);
+}
+}  // namespace
+
+hipError_t launch_ctc_posterior(const BatchDesc &in, const ScoreDesc &y, int collapse, int64_t band, float *post,
+                                double *logp, unsigned char *alpha, hipStream_t stream) {
+    const int64_t rows = in.n_reads * y.n_hyp;
+    if (rows <= 0) return hipSuccess;
+    PostParams q = post_params(in, y, collapse, band, logp, alpha);
+    q.post = post;
     const dim3 grid((unsigned)rows);
     const size_t lds = lds_bytes(q.s.lab_cap, 0);
     const int nc = in.N - 1;
@@ -373,6 +654,27 @@ hipError_t launch_ctc_posterior(const BatchDesc &in, const ScoreDesc &y, int col
     case 4: launch_both<4>(q, nc, grid, lds, stream); break;
     case 6: launch_both<6>(q, nc, grid, lds, stream); break;
     case 8: launch_both<8>(q, nc, grid, lds, stream); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_ctc_edits(const BatchDesc &in, const ScoreDesc &y, int collapse, int64_t band, float *deletion,
+                            float *insertion, double *logp, unsigned char *alpha, hipStream_t stream) {
+    const int64_t rows = in.n_reads * y.n_hyp;
+    if (rows <= 0) return hipSuccess;
+    PostParams q = post_params(in, y, collapse, band, logp, alpha);
+    q.s.slack = 2;  // (both launches: the stored forward rows hold the two states more that a deletion reads)
+    q.del = deletion;
+    q.ins = insertion;
+    const dim3 grid((unsigned)rows);
+    const size_t lds = lds_bytes(q.s.lab_cap, 0);
+    const int nc = in.N - 1;
+    switch (reg_states_per_lane(in.T, y.stride, band)) {
+    case 2: launch_edits<2>(q, nc, grid, lds, stream); break;
+    case 4: launch_edits<4>(q, nc, grid, lds, stream); break;
+    case 6: launch_edits<6>(q, nc, grid, lds, stream); break;
+    case 8: launch_edits<8>(q, nc, grid, lds, stream); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

@@ -258,6 +258,11 @@ int ctc_posterior_unsupported(int64_t T, int64_t stride, int64_t band, int64_t N
 size_t ctc_posterior_row_bytes(int64_t T, int64_t stride, int64_t band);
 hipError_t launch_ctc_posterior(const BatchDesc &in, const ScoreDesc &y, int collapse, int64_t band, float *post,
                                 double *logp, unsigned char *alpha, hipStream_t stream);
+// CTC deletion and insertion likelihoods of given labellings (ctc_posterior.hip; fcd_edits in include/fcd.h): the limits,
+// the workspace and the forward launch of launch_ctc_posterior.  deletion: [labellings * stride], insertion:
+// [labellings * (stride + 1) * (N - 1)]; logp must not be null.
+hipError_t launch_ctc_edits(const BatchDesc &in, const ScoreDesc &y, int collapse, int64_t band, float *deletion,
+                            float *insertion, double *logp, unsigned char *alpha, hipStream_t stream);
 // The lattice of given labellings under a CRF model (crf_lattice.hip; fcd_crf_score_* / fcd_crf_align_* in include/fcd.h).
 // crf_lattice_unsupported: 0 = the kernels hold the call; 1 = the window exceeds the 512 register-resident states,
 // 2 = S beyond the 24-bit state word, 3 = the labelling's LDS copy (4 bytes per state) exceeds 64 KiB.

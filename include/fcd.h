@@ -437,7 +437,7 @@ int fcd_ctc_align_host(fcd_handle *h, const fcd_batch *in, const fcd_labellings 
  * post[k][.] is the posterior over what label stands at position k with the rest of the labelling held fixed, conf[k] the
  * called label's share of it, 1 - conf[k] a substitution error probability: the number a FASTQ quality, a variant caller
  * or a polisher wants, which fcd_ctc_align_*'s qual (the network's sharpness along ONE alignment) is not.  Deletions and
- * insertions are out of scope.
+ * insertions are fcd_ctc_edits_*'s (below).
  * Computed without rescoring any variant, from one forward and one backward walk.  alpha: fcd_ctc_score_*'s forward values.
  * beta, on the same lattice and window: beta_{T_r-1}[2L] = beta_{T_r-1}[2L-1] = 1; beta_t[q] = sum over the successors s of
  * q that are live at row t+1 of p[t+1][z[s]] * beta_{t+1}[s].  For s = 2k + 1, over the rows t at which s is live:
@@ -471,6 +471,55 @@ int fcd_ctc_posterior_dev(fcd_handle *h, const fcd_batch *in, const fcd_labellin
                           const fcd_posterior *out);
 int fcd_ctc_posterior_host(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int collapse_repeats, int64_t band,
                            const fcd_posterior *out);
+
+/* ---- CTC deletion and insertion likelihoods of given labellings (csrc/ctc_posterior.hip) ----
+ * NOT a reference function.  What fcd_ctc_posterior_* leaves out: with its substitutions, the full edit-distance-1
+ * neighbourhood of a labelling, from one forward and one backward walk instead of L + (L+1)(N-1) rescorings.
+ * y is a labelling of L labels (hypothesis i of read r, row = r * n_hyp + i), z its 2L + 1 extended states, alpha
+ * fcd_ctc_score_*'s forward value, b_t[s] = p[t][z[s]] * beta_t[s] the backward value of fcd_ctc_posterior_* ("row T_r":
+ * all of b on state 2L; b is 0 above state 2L); "collapse" stands for collapse_repeats = 1.
+ * Deletion of label k, 0 <= k < L -- the carrying state is s = 2k + 1:
+ *   entry_t  = t = 0: [k = 0];  else alpha_{t-1}[2k] + [k >= 1 and (no collapse or y_{k-1} != y_{k+1})] alpha_{t-1}[2k-1]
+ *   D[k]     = sum_t entry_t * b_t[2k+3]                                 for k < L-1
+ *   D[L-1]   = alpha_{T_r-1}[2L-2] + [L >= 2] alpha_{T_r-1}[2L-3]         (the shortened labelling's two final states)
+ * Insertion of label c into gap g, 0 <= g <= L (before y_g; after the last label for g = L) -- the carrying state is the
+ * blank s = 2g, and the blank that follows the inserted label behaves exactly as y's state 2g does:
+ *   u_t(c)     = p[t][c] * ([collapse] u_{t+1}(c) + b_{t+1}[2g] + [g < L and (no collapse or c != y_g)] b_{t+1}[2g+1])
+ *   entry_t(c) = t = 0: [g = 0];  else alpha_{t-1}[2g] + [g >= 1 and (no collapse or c != y_{g-1})] alpha_{t-1}[2g-1]
+ *   I[g][c]    = sum_t entry_t(c) * u_t(c)
+ * band = 0: D[k] = P(y without label k | x) and I[g][c] = P(y with c inserted at g | x), as fcd_ctc_score_* defines P.
+ * band = W: alpha and b are y's own values on y's own window (fcd_ctc_score_*'s, from y's path); a state outside its row's
+ * window counts 0; the sums run over the rows at which the carrying state is live (D[L-1]: 0 unless state 2L-1 is live at
+ * row T_r-1); u is 0 where the carrying state is not live.  A lower bound that rises with W and equals the exact value once
+ * the window holds the whole lattice.
+ * Outputs, float32 log-ratios against the labelling itself -- a positive entry is an edit that explains the read better:
+ *   deletion [row * stride + k]                     = ln D[k]    - ln P(y | x)
+ *   insertion[(row * (stride+1) + g) * (N-1) + c-1] = ln I[g][c] - ln P(y | x)
+ *   logp[row] (nullable, float64)                   = ln P(y | x), fcd_ctc_score_*'s value
+ * Rows without a value: logp follows fcd_ctc_score_*'s rules; whenever P(y | x) is not a positive finite number every
+ * entry for k < min(len, stride) and g <= min(len, stride) is NaN.  A variant of probability 0 (L + 1 > T_r, repeats that
+ * need more rows than there are, ...): -inf.  A NaN posterior in a cell that only the variant reads: NaN -- in that
+ * variant's entry alone: a cell no alignment of y passes through (row 0 of y's second label, the last row of its last but
+ * one, ...) leaves logp and every entry whose variant has no alignment through it as they are.  L = 0 is a real
+ * case: gap 0 is written (I[0][c] = P([c] | x)), nothing goes to deletion.  Entries beyond the labelling are never written
+ * by _dev; _host returns them as 0.
+ * Numerics: fcd_ctc_posterior_*'s -- f32 probability space, exact power-of-two rescaling with integer exponents, every
+ * term non-negative, one rounding per product and per sum, no fused multiply-add; the log-ratio is formed in float64 from
+ * the accumulator's mantissa and its integer exponent.  |error| <= about 12 T_r 2^-24 + 2^-23 |value| nats.  A cell below
+ * 2^-160 of its row's maximum may be dropped: an entry below -100 ln 2 is a lower bound and may come back as -inf.
+ * Limits, shapes, dtypes, in->S = 1, in->lengths, n_valid, stream order, the grouping by workspace size and the
+ * FCD_E_INVALID / FCD_E_UNSUPPORTED cases are fcd_ctc_posterior_*'s (windows up to 510 states, N - 1 <= 8, min(T, stride)
+ * <= 28480; the messages name ctc_edits and the way out: "use a band"); a null out, out->deletion or out->insertion is one
+ * more FCD_E_INVALID. */
+typedef struct fcd_edits {
+    float  *deletion;   /* [n_reads * n_hyp * stride] */
+    float  *insertion;  /* [n_reads * n_hyp * (stride+1) * (N-1)], entry ((row * (stride+1) + g) * (N-1) + c-1) */
+    double *logp;       /* [n_reads * n_hyp], nullable: ln P(y | x), fcd_ctc_score's value within its tolerance */
+} fcd_edits;
+int fcd_ctc_edits_dev(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int collapse_repeats, int64_t band,
+                      const fcd_edits *out);
+int fcd_ctc_edits_host(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int collapse_repeats, int64_t band,
+                       const fcd_edits *out);
 
 /* ---- CRF scoring and forced alignment of given labellings (csrc/crf_lattice.hip) ----
  * NOT reference functions.  The lattice of a GIVEN labelling under a CRF model -- the recurrence search::crf_beam_search

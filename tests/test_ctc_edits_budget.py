@@ -1,0 +1,60 @@
+"""CPU-only: every instantiation of the edit-likelihood kernel (csrc/ctc_posterior.hip: edit_back_kernel, the backward pass
+of fcd_ctc_edits_* at 2, 4, 6, 8 states per lane, each for up to 4 and up to 8 labels), read off the gfx950 code object
+inside the built libfcd_hip.so as tests/test_ctc_posterior_budget.py reads its kernels: each appears once, uses no scratch
+and stays within the 256 VGPRs of a 64-lane workgroup's budget.  The counts it prints are the table in DESIGN.md."""
+import os
+import re
+import shutil
+import subprocess
+import tempfile
+
+import pytest
+
+LLVM = "/opt/rocm/lib/llvm/bin"
+KERNELS = {"edit_k%d_nc%d" % (k, nc): "edit_back_kernelILi%dELi%dEE" % (k, nc) for k in (2, 4, 6, 8) for nc in (4, 8)}
+
+
+@pytest.fixture(scope="module")
+def kernel_notes():
+    tools = [shutil.which("objcopy"), os.path.join(LLVM, "clang-offload-bundler"), os.path.join(LLVM, "llvm-readelf")]
+    if not all(t and os.path.exists(t) for t in tools):
+        pytest.skip("objcopy / the ROCm LLVM tools are not installed")
+    from fast_ctc_decode_amd import _native, build
+    build.build()
+    tmp = tempfile.mkdtemp(prefix="fcd_edit_budget_")
+    try:
+        subprocess.check_call(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", _native.LIB_PATH, tmp + "/fat.bin"])
+        blob = open(tmp + "/fat.bin", "rb").read()
+        starts = [m.start() for m in re.finditer(re.escape(b"__CLANG_OFFLOAD_BUNDLE__"), blob)] + [len(blob)]
+        notes = ""
+        for a, b in zip(starts, starts[1:]):
+            if b"edit_back_kernel" not in blob[a:b]:
+                continue
+            with open(tmp + "/one.bin", "wb") as f:
+                f.write(blob[a:b])
+            subprocess.check_call([LLVM + "/clang-offload-bundler", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
+                                   "--input=" + tmp + "/one.bin", "--output=" + tmp + "/dev.co", "--unbundle"])
+            notes += subprocess.check_output([LLVM + "/llvm-readelf", "--notes", tmp + "/dev.co"]).decode()
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+    return notes
+
+
+def _meta(notes, mangled):
+    found = []
+    for blk in re.split(r"\n\s*- \.agpr_count", notes)[1:]:
+        name = re.search(r"\.name:\s+(\S+)", blk)
+        if name and mangled in name.group(1):
+            found.append({k: int(re.search(r"\.%s:\s+(\d+)" % k, blk).group(1))
+                          for k in ("vgpr_count", "private_segment_fixed_size")})
+    return found
+
+
+@pytest.mark.parametrize("which", sorted(KERNELS))
+def test_instantiation_has_no_scratch(kernel_notes, which):
+    found = _meta(kernel_notes, KERNELS[which])
+    assert len(found) == 1, "expected exactly one %s in libfcd_hip.so, found %d" % (KERNELS[which], len(found))
+    m = found[0]
+    print("%s: vgpr_count %d, scratch %d B" % (which, m["vgpr_count"], m["private_segment_fixed_size"]))
+    assert m["private_segment_fixed_size"] == 0, "scratch in the time loop: %r" % m
+    assert m["vgpr_count"] <= 256, m
