@@ -217,6 +217,12 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_pe
     constexpr bool RPARK = RSORT;
     constexpr int kPark = RSORT ? kFifo + 9 : kFifo + 16;
     __shared__ int s_park[(PARK || RPARK) ? kWavesPerBlock : 1][(PARK || RPARK) ? kPark * 64 : 1];
+    // HL: the headline family (two reads per wavefront, equal lengths, S >= 0, single result).  Its step is bound by the
+    // number of vector instructions it issues, so it takes the forms of beam_wave_step.inc that trade vector instructions
+    // for scalar ones or for nothing: lane addresses carried as the BYTE addresses ds_permute / ds_bpermute want, "this
+    // half still runs" as a wave-uniform mask (alive_m) instead of a lane flag, the rank in one accumulator, the new nodes'
+    // ids by v_mbcnt.  Same values in every register the step commits; the other instantiations keep their code.
+    constexpr bool HL = RPW == 2 && GW == 6 && UNI && !AMB && !NB && !SES && !PROF && S >= 0;
     static_assert(!PDQ || BCAP * N > 20, "the tie order only matters above 20 candidates");
     static_assert(!PDQ || BCAP * N <= HALF - 2, "the last two entries of a half's table are never written (i_src below)");
     int n_amb = 0, n_crit = 0;
@@ -253,6 +259,10 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_pe
     // a candidate's survivor-table entry, low byte: its lane's byte address; DSRC: bit 0 set on a child lane
     const int ent_lo = (lane << 2) | ((DSRC && !is_self) ? 1 : 0);
     const bool spare = !idle && k == GW - 1;     // DSRC: divides its group's gap probability
+    // HL: the same lanes as byte addresses, and the two words the survivor hand-over adds per lane
+    const int dummy_a = dummy << 2, hbase_a = hbase << 2;
+    const int col_a = (hbase + (is_child ? k : 0)) << 2;  // this lane's column in a row of the FIFO's front register
+    const int kind1 = (k << 2) + 1;                        // a child lane's (tip label field | kind 1)
     const int zero_a = (hbase + BCAP * GW) << 2;  // DSRC: byte address of the half's first idle lane (0 / top)
     const int beam_size = p.a.beam_size;
     const bool collapse = !CRF && p.a.collapse != 0;
@@ -411,6 +421,8 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_pe
         return tt < T ? load_post(post_w, half_stride + (int64_t)tt * st_t + (int64_t)state * st_s + kcol * st_n, dt) : 0.0f;
     };
     float rowv = GATHER ? gather_row(0) : 0.0f;
+    // HL: the halves that still run, as a mask (bit = lane); `alive` is formed again behind the time loop
+    uint64_t alive_m = HL ? ballot(alive) : 0ull;
     // Drain the prologue loads HERE, with a wait the compiler's scoreboard sees: otherwise the loop
     // header inherits "win[0] may still be in flight" and gets an s_waitcnt vmcnt(0) on EVERY step,
     // which on gfx9-family counters also waits for the previous step's tree stores to be acked.
@@ -425,6 +437,12 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_pe
     // lane, and the tip's column -- are fetched one step AHEAD, as soon as the next beam's tips are known: the two
     // ds_bpermutes then travel under the divisions instead of heading the next step's dependent chain.
     auto fetch_row = [&](float &o_pk, float &o_ptip) {
+        if (HL) {  // byte addresses: the row's offset is wave-uniform, the lane's part does not change
+            const int row_a = (S > 0 ? gE + state * N : gE) << 2;
+            o_pk = __int_as_float(__builtin_amdgcn_ds_bpermute(row_a + col_a, __float_as_int(win[0])));
+            o_ptip = CRF ? 0.0f : __int_as_float(__builtin_amdgcn_ds_bpermute(row_a + tipf + hbase_a, __float_as_int(win[0])));
+            return;
+        }
         const int rbase = hbase + gE + (S > 0 ? state * N : 0);
         o_pk = bpermf(rbase + (is_child ? k : 0), win[0]);
         o_ptip = CRF ? 0.0f : __int_as_float(__builtin_amdgcn_ds_bpermute((rbase << 2) + tipf, __float_as_int(win[0])));
@@ -453,6 +471,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_pe
 #include "beam_wave_step.inc"
         }
     }
+    if (HL) alive = lane_in(alive_m, lane);
     if (!SES) r = read_index_again();
     if (PROF && lane == 0 && p.a.prof) {
         uint32_t *o = p.a.prof + ((int64_t)blockIdx.x * kWavesPerBlock + wave) * 8;

@@ -5,7 +5,8 @@
 // cost 7 % -- a loop with two exits gets a guard variable and a dozen scalar instructions per step from LLVM's
 // loop-exit unification, and the kernel is bound by the LATENCY of its dependent chain: every instruction and every
 // wait on the path shows.)
-        const bool act = UNI ? alive : (alive && t < T);
+        const bool act0 = UNI ? alive : (alive && t < T);
+        const bool act = act0;
         const int tks = SES ? (t0 + t) << KS : t << KS;  // first node id of the step (SES: absolute time)
         float pk = GATHER ? rowv : pk_next;
         const float pr0 = pk;
@@ -23,9 +24,13 @@
         const int mslot = (child >> kSlotShift) & kSlotMask;
         const bool cvalid = grp && is_child && pass && (exists || !rep || gp > 0.0f);  // :212-218
         const bool merged = cvalid && inbeam;  // the target's own lane 0 absorbs this extension
+        // HL: the target slot's own lane as a byte address, formed once for the push here and the look-up behind the rank
+        const int tgt_a = hbase_a + mslot * (GW << 2);
         const int dst = merged ? hbase + mslot * GW : dummy;
-        float inc = __int_as_float(perm(dst, __float_as_int(merged ? contrib : 0.0f)));
-        const int incv = perm(dst, merged ? 1 : 0);
+        const int dst_a = merged ? tgt_a : dummy_a;
+        float inc = __int_as_float(HL ? __builtin_amdgcn_ds_permute(dst_a, __float_as_int(merged ? contrib : 0.0f))
+                                      : perm(dst, __float_as_int(merged ? contrib : 0.0f)));
+        const int incv = HL ? __builtin_amdgcn_ds_permute(dst_a, merged ? 1 : 0) : perm(dst, merged ? 1 : 0);
         stamp_f(1, inc);  // extensions + the push into slots that are beam entries
 
         // ---- self lanes: blank (:191-198) + repeat-stay (:206-211) + incoming extension ----
@@ -121,10 +126,13 @@
         int pre_new;
         if (RPW == 1) {
             pre_new = popc64(m_new & lanemask_lt());
+        } else if (HL) {
+            pre_new = 0;  // (counted onto tks below)
         } else {
             pre_new = __builtin_popcount(w_new & ((1u << q) - 1u));
         }
-        const int newid = tks + pre_new;  // < cap: the host sizes every slab for (T << KS) ids (capi.hip)
+        // < cap: the host sizes every slab for (T << KS) ids (capi.hip)
+        const int newid = HL ? half_prefix_count(m_new, lane, tks) : tks + pre_new;
         // (beam_lane.hip writes a node's record when it first ENTERS THE BEAM -- a sixth of the stores.  Tried here, r05:
         // the stores ride for free under the LDS reads above, while next to the survivor gather they cost the PDQ
         // instantiation 8 B of scratch and 1 % -- the write traffic is not what bounds this kernel.)
@@ -150,13 +158,22 @@
         } else if (STREAM) {
             // four independent compare-and-count chains (device_utils.h); the scheduling barriers keep the loads of block
             // j + kAhead behind the count of block j - 1 (left alone, the scheduler hoists every load to the top again)
-            int r0, r1, r2, r3;
+            int r0, r1 = 0, r2 = 0, r3 = 0;
             static_assert(!STREAM || NC >= 4, "at least one block of four comparands");
 #pragma unroll
             for (int j = 0; j < NBLK; ++j) {
                 __builtin_amdgcn_sched_barrier(0);
                 if (j + kAhead < NBLK) load_blk(j + kAhead);
-                if (R32) {  // r32 = #(probability word > own): candidates of equal probability share it
+                if (R32 && HL) {  // the same count in ONE accumulator: the sum of four chains is three instructions more
+                    if (j == 0) {
+                        FCD_RANK4_32_ONE_FIRST(kp, kw[0], kw[1], kw[2], kw[3], r0);
+                    } else if (4 * j + 4 <= NC) {
+                        FCD_RANK4_32_ONE(kp, kw[4 * j], kw[4 * j + 1], kw[4 * j + 2], kw[4 * j + 3], r0);
+                    } else {
+#pragma unroll
+                        for (int u = 4 * j; u < NC; ++u) r0 += (kw[u] > kp) ? 1 : 0;
+                    }
+                } else if (R32) {  // r32 = #(probability word > own): candidates of equal probability share it
                     if (j == 0) {
                         FCD_RANK4_32_FIRST(kp, kw[0], kw[1], kw[2], kw[3], r0, r1, r2, r3);
                     } else if (4 * j + 4 <= NC) {
@@ -175,7 +192,7 @@
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
-            rank = (r0 + r1) + (r2 + r3);
+            rank = (R32 && HL) ? r0 : (r0 + r1) + (r2 + r3);
         } else {
             // four independent compare-and-count chains (device_utils.h)
             int r0, r1, r2, r3;
@@ -197,7 +214,11 @@
                                : __builtin_popcount(hbase ? (uint32_t)(m_valid >> 32) : (uint32_t)m_valid);
         // Everything that ends a read is rare: one wave-wide test, the bookkeeping behind it.
         const bool is_nan = valid && prob != prob;
-        if (ballot(act && (n_valid == 0 || is_nan)) != 0ull) {
+        // HL: the same test on masks, votes on bare compares joined in scalar registers -- a candidate is a NaN when its
+        // probability is one and its key is not 0 (valid <=> key != 0), a half runs when alive_m says so
+        if (HL ? ((((ballot(n_valid == 0)) | (ballot(prob != prob) & m_valid)) & alive_m) != 0ull)
+               : (ballot(act && (n_valid == 0 || is_nan)) != 0ull)) {
+            const bool act = HL ? lane_in(alive_m, lane) : act0;
             const uint64_t m_nan = ballot(is_nan);
             const bool any_nan = RPW == 1 ? m_nan != 0ull
                                           : (hbase ? (uint32_t)(m_nan >> 32) : (uint32_t)m_nan) != 0u;
@@ -211,9 +232,10 @@
                     p.out.status[rr] = f_empty ? FCD_ST_RAN_OUT_OF_BEAM : FCD_ST_INCOMPARABLE;
                     if (!NB) p.out.out_len[rr] = 0;  // (n-best rows: the epilogue)
                 }
-                alive = false;
+                if (!HL) alive = false;  // (HL: alive_m, below)
                 if (UNI) n_valid = 0;  // the failed read keeps an empty beam from here on
             }
+            if (HL) alive_m &= ~ballot(f_nan || f_empty);
         }
         const bool go = UNI ? true : (act && alive);  // this half completes the step
 
@@ -279,7 +301,7 @@
                 const int back = srcs[PDQ ? rank : (rank & 15)];
                 clash = sel && back != ent;
             }
-            fate = bperm(hbase + mslot * GW, selflag);
+            fate = HL ? __builtin_amdgcn_ds_bpermute(tgt_a, selflag) : bperm(hbase + mslot * GW, selflag);
             own = bperm(grp0, selflag);  // ... and this group's own candidate?
             // every lane of new group i learns its source lane (stale beyond the new beam: unused), where the best
             // candidate sits, and the SMALLEST DEPTH in the new beam: a stale entry can only lower it
@@ -294,7 +316,12 @@
                 // source is a slot's own lane, and on the half's first idle lane (0 / top) when it is a child lane:
                 // bit 0 of the entry says which.
                 top = key_prob((uint32_t)srcs[kTop]);
-                gp_a = (e_src & 1) ? zero_a : src_a + ((GW - 1) << 2);
+                if (HL) {  // (a bit-field select: bit 0 spread over the word picks between the two addresses)
+                    const int m_ch = (int)((uint32_t)e_src << 31) >> 31;
+                    gp_a = (m_ch & zero_a) | (~m_ch & (src_a + ((GW - 1) << 2)));
+                } else {
+                    gp_a = (e_src & 1) ? zero_a : src_a + ((GW - 1) << 2);
+                }
             }
 #pragma unroll
             for (int j = 1; j < BCAP; ++j) e_min = min(e_min, srcs[j]);
@@ -311,11 +338,14 @@
         const int tipfc = is_self ? tipf : (k << 2);
         int statec = (CRF && !is_self) ? (GATHER ? ((state * NL) & s_mask) + l : (state * NL) % (S > 0 ? S : 1) + l)
                                              : state;  // :97
-        int jumpc = is_self ? jump : ((depth % kSeg == 0) ? node : jump);
+        int jumpc = HL ? ((!is_self && depth % kSeg == 0) ? node : jump)  // (one select)
+                       : (is_self ? jump : ((depth % kSeg == 0) ? node : jump));
         // 0 self, 1 a child entering the beam for the first time, 2 a child that has been there before (EVER:
         // its row is in HBM); read off the entry BEFORE it is marked below
         const int kind = is_child ? 1 + ((child_in >> 30) & 1) : 0;
-        int meta = kind | tipfc | (depc << 5);
+        // HL: kind and tip label of a child lane are one constant plus the entry's EVER bit.  (A lane that is neither a slot's
+        // own nor a child lane holds no candidate: it is never a source, and what it packs here is never gathered.)
+        int meta = HL ? ((depc << 5) | (is_self ? tipf : kind1 + ((child_in >> 30) & 1))) : (kind | tipfc | (depc << 5));
         // DSRC: every lane divides what it holds, HERE, before the gather: a candidate lane its label probability, a
         // group's spare lane the gap probability of the slot's own candidate (it received the blank column like the
         // slot's own lane and computed the same sgp), the half's idle lanes 0 -- a child candidate's gap probability.

@@ -105,7 +105,14 @@ __device__ __forceinline__ int32_t load_i32_l2(const int32_t *p) {
 // The same two blocks on 32-bit words: r_j += (w_j > word).  The two-reads-per-wavefront kernels rank on the probability
 // word of the key alone (beam_wave_step.inc, R32) -- half the comparand bytes, and the node word only where two kept
 // candidates share a probability.
+// ..._ONE: all four compares feed ONE accumulator (the headline family, whose step is bound by the number of vector
+// instructions: four chains end in three adds, one chain in none; a consumer still sits four instructions behind its
+// producer, and with six wavefronts per SIMD the chain's own latency is covered by the other wavefronts).
 #ifdef FCD_HIPEMU  // (lockstep emulation, tests/hipemu: plain C++)
+#define FCD_RANK4_32_ONE(word, wa, wb, wc, wd, r) \
+    do { (r) += ((wa) > (word)) + ((wb) > (word)) + ((wc) > (word)) + ((wd) > (word)); } while (0)
+#define FCD_RANK4_32_ONE_FIRST(word, wa, wb, wc, wd, r) \
+    do { (r) = ((wa) > (word)) + ((wb) > (word)) + ((wc) > (word)) + ((wd) > (word)); } while (0)
 #define FCD_RANK4_32(word, wa, wb, wc, wd, r0, r1, r2, r3) \
     do { (r0) += (wa) > (word); (r1) += (wb) > (word); (r2) += (wc) > (word); (r3) += (wd) > (word); } while (0)
 #define FCD_RANK4_32_FIRST(word, wa, wb, wc, wd, r0, r1, r2, r3) \
@@ -142,7 +149,60 @@ __device__ __forceinline__ int32_t load_i32_l2(const int32_t *p) {
             : "v"(word), "v"(wa), "v"(wb), "v"(wc), "v"(wd), "v"(zero__)                       \
             : "vcc");                                                                          \
     } while (0)
+#define FCD_RANK4_32_ONE(word, wa, wb, wc, wd, r)                                              \
+    do {                                                                                       \
+        uint64_t m0__, m1__, m2__, m3__;                                                       \
+        asm("v_cmp_gt_u32_e64 %1, %6, %5\n\t"                                                  \
+            "v_cmp_gt_u32_e64 %2, %7, %5\n\t"                                                  \
+            "v_cmp_gt_u32_e64 %3, %8, %5\n\t"                                                  \
+            "v_cmp_gt_u32_e64 %4, %9, %5\n\t"                                                  \
+            "v_addc_co_u32_e64 %0, vcc, 0, %0, %1\n\t"                                         \
+            "v_addc_co_u32_e64 %0, vcc, 0, %0, %2\n\t"                                         \
+            "v_addc_co_u32_e64 %0, vcc, 0, %0, %3\n\t"                                         \
+            "v_addc_co_u32_e64 %0, vcc, 0, %0, %4"                                              \
+            : "+v"(r), "=&s"(m0__), "=&s"(m1__), "=&s"(m2__), "=&s"(m3__)                      \
+            : "v"(word), "v"(wa), "v"(wb), "v"(wc), "v"(wd)                                    \
+            : "vcc");                                                                          \
+    } while (0)
+#define FCD_RANK4_32_ONE_FIRST(word, wa, wb, wc, wd, r)                                        \
+    do {                                                                                       \
+        uint64_t m0__, m1__, m2__, m3__;                                                       \
+        const int zero__ = 0;                                                                  \
+        asm("v_cmp_gt_u32_e64 %1, %6, %5\n\t"                                                  \
+            "v_cmp_gt_u32_e64 %2, %7, %5\n\t"                                                  \
+            "v_cmp_gt_u32_e64 %3, %8, %5\n\t"                                                  \
+            "v_cmp_gt_u32_e64 %4, %9, %5\n\t"                                                  \
+            "v_addc_co_u32_e64 %0, vcc, 0, %10, %1\n\t"                                        \
+            "v_addc_co_u32_e64 %0, vcc, 0, %0, %2\n\t"                                         \
+            "v_addc_co_u32_e64 %0, vcc, 0, %0, %3\n\t"                                         \
+            "v_addc_co_u32_e64 %0, vcc, 0, %0, %4"                                              \
+            : "=&v"(r), "=&s"(m0__), "=&s"(m1__), "=&s"(m2__), "=&s"(m3__)                     \
+            : "v"(word), "v"(wa), "v"(wb), "v"(wc), "v"(wd), "v"(zero__)                       \
+            : "vcc");                                                                          \
+    } while (0)
 #endif
+
+// Set bits of a half's word of a wave-wide vote below this lane's place in its half, counted onto `base`: the lower half
+// counts in the low word (v_mbcnt_lo), the upper half in the high word (v_mbcnt_hi adds nothing for a lane below 32).
+__device__ __forceinline__ int half_prefix_count(uint64_t m, int lane, int base) {
+#ifdef FCD_HIPEMU  // (lockstep emulation, tests/hipemu: plain C++)
+    const uint32_t w = lane >= 32 ? (uint32_t)(m >> 32) : (uint32_t)m;
+    return base + __builtin_popcount(w & ((1u << (lane & 31)) - 1u));
+#else
+    const uint32_t lo = lane >= 32 ? 0u : (uint32_t)m;
+    return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo(lo, (uint32_t)base));
+#endif
+}
+
+// A wave-uniform mask (one bit per lane, as ballot() returns it) read as this lane's flag: the scalar register pair IS
+// the condition, nothing is computed.
+__device__ __forceinline__ bool lane_in(uint64_t m, int lane) {
+#ifdef FCD_HIPEMU  // (lockstep emulation, tests/hipemu: plain C++)
+    return ((m >> lane) & 1ull) != 0ull;
+#else
+    return __builtin_amdgcn_inverse_ballot_w64(m);
+#endif
+}
 
 // Makes a value opaque to the optimiser and pins it in vector registers (the duplex kernel's coefficient table).
 // (tests/hipemu predefines FCD_OPAQUE_V as a no-op.)
