@@ -39,6 +39,8 @@ from .api import (  # noqa: F401
     crf_greedy_search,
     crf_align,
     crf_align_batch_raw,
+    crf_posterior,
+    crf_posterior_batch_raw,
     crf_score,
     crf_score_batch_raw,
     AlignResult,

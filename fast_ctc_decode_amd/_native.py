@@ -55,6 +55,7 @@ SYMBOLS = [
     "fcd_ctc_posterior_dev", "fcd_ctc_posterior_host",
     "fcd_ctc_edits_dev", "fcd_ctc_edits_host",
     "fcd_crf_score_dev", "fcd_crf_score_host", "fcd_crf_align_dev", "fcd_crf_align_host",
+    "fcd_crf_posterior_dev", "fcd_crf_posterior_host",
 ]
 JOB_PATH, JOB_QUAL, JOB_AMBIGUOUS, JOB_DONE = 1, 2, 4, 1
 
@@ -92,7 +93,7 @@ class Alignment(C.Structure):
 
 
 class Posterior(C.Structure):
-    """fcd_posterior: what fcd_ctc_posterior_* writes (include/fcd.h)."""
+    """fcd_posterior: what fcd_ctc_posterior_* and fcd_crf_posterior_* write (include/fcd.h)."""
     _fields_ = [("post", C.c_void_p), ("logp", C.c_void_p)]
 
 
@@ -263,6 +264,7 @@ def bind(lib):
     for sfx in ("dev", "host"):
         getattr(lib, "fcd_crf_score_" + sfx).argtypes = [P, BP, P, i64, i64, C.POINTER(Labellings), i64, P]
         getattr(lib, "fcd_crf_align_" + sfx).argtypes = [P, BP, P, i64, i64, C.POINTER(Labellings), i64, C.POINTER(Alignment)]
+        getattr(lib, "fcd_crf_posterior_" + sfx).argtypes = [P, BP, P, i64, i64, C.POINTER(Labellings), i64, C.POINTER(Posterior)]
     return lib
 
 

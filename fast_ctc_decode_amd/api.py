@@ -877,6 +877,17 @@ class BatchResult:
         return crf_align_batch_raw(network_outputs, init_states, self.labels, self.out_len, lengths,
                                    self.path if band else None, band, None, input_dtype, getattr(self, "_handle", None))
 
+    def crf_posterior(self, network_outputs, init_states, lengths=None, band=0, input_dtype=None):
+        """The substitution posteriors under the CRF model of every read's result -> PosteriorResult, post
+        (n_reads, 1, stride, N-1): crf_posterior_batch_raw on this result's own arrays (device results stay on the
+        device).  Arguments as crf_score."""
+        if getattr(network_outputs, "ndim", 4) != 4:
+            raise ValueError("crf_posterior covers the results of the CRF searches, (n_reads, T, S, N) posteriors, not plain CTC results")
+        if band and self.path is None:
+            raise ValueError("a band needs the result's path")
+        return crf_posterior_batch_raw(network_outputs, init_states, self.labels, self.out_len, lengths,
+                                       self.path if band else None, band, None, input_dtype, getattr(self, "_handle", None))
+
     def sequences(self, alphabet, raise_on_error=True, paths="list"):
         """-> list of (str, path) per read, exactly what the single-read functions return.
 
@@ -1227,6 +1238,16 @@ class NBestResult:
         return crf_align_batch_raw(network_outputs, init_states, self.labels, self.out_len, lengths,
                                    self.path if band else None, band, self.n_hyp, input_dtype,
                                    getattr(self, "_handle", None))
+
+    def crf_posterior(self, network_outputs, init_states, lengths=None, band=0, input_dtype=None):
+        """The substitution posteriors under the CRF model of every hypothesis -> PosteriorResult, post
+        (n_reads, n_best, stride, N-1); logp NaN where i >= n_hyp[r].  crf_posterior_batch_raw on this result's own arrays;
+        plain CTC results are refused."""
+        if not self.crf or getattr(network_outputs, "ndim", 4) != 4:
+            raise ValueError("crf_posterior covers the results of the CRF searches, not plain CTC results")
+        return crf_posterior_batch_raw(network_outputs, init_states, self.labels, self.out_len, lengths,
+                                       self.path if band else None, band, self.n_hyp, input_dtype,
+                                       getattr(self, "_handle", None))
 
     def hypotheses(self, alphabet, raise_on_error=True):
         """-> per read, a list of (seq, path, score), best first (None for a failed read when not raise_on_error)."""
@@ -1645,9 +1666,9 @@ def ctc_align(network_output, sequence, alphabet, collapse_repeats=True):
 # CTC forward-backward substitution posteriors of given labellings (include/fcd.h, fcd_ctc_posterior_*)
 # ---------------------------------------------------------------------------------------------
 class PosteriorResult:
-    """Outcome of ctc_posterior_batch_raw: post[r, i, k, c - 1] is the posterior that label c stands at position k of
+    """Outcome of ctc_posterior_batch_raw and crf_posterior_batch_raw: post[r, i, k, c - 1] is the posterior that label c stands at position k of
     hypothesis i of read r, the rest of the labelling held fixed -- P(y[k:=c] | x) over its sum over c, float32, all
-    alignments counted (include/fcd.h); logp[r, i] (float64) is ln P(y | x), ctc_score's value.  NaN for every position of
+    alignments counted (include/fcd.h); logp[r, i] (float64) is ln P(y | x), ctc_score's (crf_score's) value.  NaN for every position of
     a labelling whose P is not positive and finite; entries k >= the labelling's length are 0.  numpy for host inputs,
     torch tensors (same device) for device inputs."""
 
@@ -1896,6 +1917,39 @@ def crf_align_batch_raw(network_outputs, init_states, labels, label_lengths, len
     return AlignResult(start, count, qual, logp)
 
 
+def crf_posterior_batch_raw(network_outputs, init_states, labels, label_lengths, lengths=None, paths=None, band=0,
+                            n_valid=None, input_dtype=None, handle=None):
+    """Forward-backward substitution posteriors under the CRF model: for every position of every labelling, the posterior
+    over which label stands there with the rest of the labelling held fixed -- each variant with its own model-state
+    trajectory -- summed over every alignment in one forward and one backward walk (include/fcd.h, fcd_crf_posterior_*).
+    -> PosteriorResult with post (B, n_hyp, stride, N-1) float32 and logp (B, n_hyp) float64, crf_score's value.
+
+    Arguments as crf_score_batch_raw.  Limits: S = (N - 1)^m and N - 1 <= 8; windows of up to 512 states where
+    m (N - 1) <= 8 (S = 4, 16 at N = 5; 256 states where N - 1 > 4), up to 192 states (band <= 95) where m (N - 1) <= 24
+    (S = 64, 1024, 4096 at N = 5).
+    Device tensors in: torch tensors on the same device, enqueued on torch's current stream, not synchronised.
+    numpy in: numpy out."""
+    band = _check_band(band, paths)
+    h, b, y, (B, n_hyp, stride), dev, keep = _lattice_inputs(network_outputs, labels, label_lengths, lengths, paths, band,
+                                                             n_valid, input_dtype, handle, init_states)
+    init = keep[-1]
+    nc = int(b.N) - 1
+    if dev is not None:
+        import torch
+        post = torch.zeros((B, n_hyp, stride, nc), dtype=torch.float32, device=dev)
+        logp = torch.empty((B, n_hyp), dtype=torch.float64, device=dev)
+        out = nat.Posterior(post.data_ptr(), logp.data_ptr())
+        h.check(h.lib.fcd_crf_posterior_dev(h.ptr, C.byref(b), C.c_void_p(init.data_ptr()), int(init.shape[1]),
+                                            int(init.shape[1]), C.byref(y), band, C.byref(out)))
+        return PosteriorResult(post, logp)
+    post = np.zeros((B, n_hyp, stride, nc), np.float32)
+    logp = np.empty((B, n_hyp), np.float64)
+    out = nat.Posterior(post.ctypes.data, logp.ctypes.data)
+    h.check(h.lib.fcd_crf_posterior_host(h.ptr, C.byref(b), init.ctypes.data, init.shape[1], init.shape[1], C.byref(y), band,
+                                         C.byref(out)))
+    return PosteriorResult(post, logp)
+
+
 def _crf_sequence_labels(sequence, alpha, what):
     """The labels behind a string crf_beam_search built: it joins the labels' strings leaf to root and reverses the
     CHARACTERS (src/search.rs:146-156), so a multi-character label appears reversed."""
@@ -1949,6 +2003,15 @@ def crf_align(network_output, init_state, sequence, alphabet):
     if not np.isfinite(logp):
         return [], [], logp
     return [int(s) for s in r.start[0, 0, :L]], [float(q) for q in r.qual[0, 0, :L]], logp
+
+
+def crf_posterior(network_output, init_state, sequence, alphabet):
+    """The substitution posteriors of one string (as crf_beam_search returns it) against one (T, S, N) float32 posterior
+    array under the CRF model, exact lattice: -> (post, logp) with post an (L, N-1) float32 array (row k: the posterior
+    over alphabet[1:] at label k) and logp = ln P(sequence | network_output).  Argument checks as crf_score."""
+    x, init, lab, n, L = _crf_one_read(network_output, init_state, sequence, alphabet, "crf_posterior")
+    r = crf_posterior_batch_raw(x, init, lab, n)
+    return r.post[0, 0, :L].copy(), float(r.logp[0, 0])
 
 
 # ---------------------------------------------------------------------------------------------

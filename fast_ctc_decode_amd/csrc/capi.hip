@@ -1582,7 +1582,8 @@ int fcd_unpack_gathered_dev(fcd_handle *h, const uint8_t *gathered, int64_t stri
 }
 
 // ---- the lattice of given labellings: CTC forward score (ctc_score.hip), CTC forced alignment (ctc_align.hip), both
-// under a CRF model (crf_lattice.hip), and the CTC substitution posteriors and edit likelihoods (ctc_posterior.hip) ----
+// under a CRF model (crf_lattice.hip), the CTC substitution posteriors and edit likelihoods (ctc_posterior.hip), and the
+// substitution posteriors under a CRF model (crf_posterior.hip) ----
 int fcd_debug_set_align_workspace_cap(fcd_handle *h, int64_t bytes) {
     if (!h || bytes < 0) return FCD_E_INVALID;
     std::lock_guard<std::recursive_mutex> g(h->mu);
@@ -1591,7 +1592,7 @@ int fcd_debug_set_align_workspace_cap(fcd_handle *h, int64_t bytes) {
 }
 
 namespace {
-// One fcd_{ctc,crf}_{score,align}_{dev,host}, fcd_ctc_posterior_{dev,host} or fcd_ctc_edits_{dev,host} call: the score
+// One fcd_{ctc,crf}_{score,align,posterior}_{dev,host} or fcd_ctc_edits_{dev,host} call: the score
 // writes `logp`, the alignment `out`, the posteriors `post`, the edit likelihoods `edits`.
 struct LatticeCall {
     bool crf, align;
@@ -1648,7 +1649,19 @@ int lattice_check(fcd_handle *h, const LatticeCall &c) {
                                                      : "ctc_score: the exact lattice does not fit the 160 KiB of LDS: use a band");
     }
     if (c.align && in->n_reads > 0 && !c.out->count) return fail(h, FCD_E_INVALID, "null count");
-    if (c.edit || c.posterior) {  // (one set of limits: both walk ctc_posterior.hip's register-resident window)
+    if (c.crf && c.posterior) {
+        int64_t fit = 0;
+        switch (crf_posterior_unsupported(in->T, in->S, in->N, y->stride, std::min<int64_t>(c.band, 1ll << 28), &fit)) {
+        case 1: return fail(h, FCD_E_UNSUPPORTED, (std::string("crf_posterior: a model state of this depth holds windows of ") +
+                                                   std::to_string(fit) + " states: use a band of at most " +
+                                                   std::to_string((fit - 1) / 2)).c_str());
+        case 2: return fail(h, FCD_E_UNSUPPORTED, "crf_posterior: more than 8 labels besides the blank");
+        case 4: return fail(h, FCD_E_UNSUPPORTED, "crf_posterior: S must be a power of N - 1 (the model state is the last labels)");
+        case 5: return fail(h, FCD_E_UNSUPPORTED, "crf_posterior: the model state holds more labels than the kernels carry "
+                                                  "(S = (N - 1)^m with m <= 6 and m (N - 1) <= 24, or m <= 4 at N = 3)");
+        default: break;
+        }
+    } else if (c.edit || c.posterior) {  // (one set of limits: both walk ctc_posterior.hip's register-resident window)
         const std::string who = c.edit ? "ctc_edits" : "ctc_posterior";
         switch (ctc_posterior_unsupported(in->T, y->stride, c.band, in->N)) {
         case 1: return fail(h, FCD_E_UNSUPPORTED, (who + (c.band > 0 ? ": the band's window exceeds 510 states: use a narrower band"
@@ -1756,11 +1769,15 @@ int lattice_posterior(fcd_handle *h, const LatticeCall &c) {
     const fcd_posterior *out = c.post;
     const size_t per_row = (size_t)y->stride * ((size_t)in->N - 1);  // post entries of one labelling
     const int64_t bnd = std::min<int64_t>(c.band, 1ll << 28);
+    // (the CTC kernels size their rows by the band as given, the CRF kernels by the band the launch gets)
+    const size_t row_bytes = c.crf ? crf_posterior_row_bytes(in->T, in->S, in->N, y->stride, bnd) : ctc_posterior_row_bytes(in->T, y->stride, c.band);
     return lattice_grouped(
-        h, c, ctc_posterior_row_bytes(in->T, y->stride, c.band), std::min<int64_t>(4ll << 30, workspace_budget(h)), out->logp,
+        h, c, row_bytes, std::min<int64_t>(4ll << 30, workspace_budget(h)), out->logp,
         [&](CallScope &sc) { sc.add(out->post, (size_t)in->n_reads * (size_t)y->n_hyp * per_row * 4); },
-        [&](const BatchDesc &d, const ScoreDesc &yd, int64_t, int64_t row0, double *logp, unsigned char *alpha, hipStream_t stream) {
-            return launch_ctc_posterior(d, yd, c.collapse, bnd, out->post + (size_t)row0 * per_row, logp, alpha, stream);
+        [&](const BatchDesc &d, const ScoreDesc &yd, int64_t r0, int64_t row0, double *logp, unsigned char *alpha, hipStream_t stream) {
+            float *post = out->post + (size_t)row0 * per_row;
+            return c.crf ? launch_crf_posterior(d, yd, c.init + r0 * c.init_stride, c.n_init, c.init_stride, bnd, post, logp, alpha, stream)
+                         : launch_ctc_posterior(d, yd, c.collapse, bnd, post, logp, alpha, stream);
         });
 }
 
@@ -1936,6 +1953,20 @@ int fcd_crf_align_host(fcd_handle *h, const fcd_batch *in, const float *init, in
     if (!h) return FCD_E_INVALID;
     std::lock_guard<std::recursive_mutex> whole_call(h->mu);  // staging .. copy-back, see run_host
     return lattice_host(h, LatticeCall{true, true, in, y, band, 0, init, n_init, init_stride, nullptr, out});
+}
+
+int fcd_crf_posterior_dev(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init, int64_t init_stride,
+                          const fcd_labellings *y, int64_t band, const fcd_posterior *out) {
+    if (!h) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> g(h->mu);
+    return lattice_dev(h, LatticeCall{true, false, in, y, band, 0, init, n_init, init_stride, nullptr, nullptr, true, out});
+}
+
+int fcd_crf_posterior_host(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init, int64_t init_stride,
+                           const fcd_labellings *y, int64_t band, const fcd_posterior *out) {
+    if (!h) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> whole_call(h->mu);  // staging .. copy-back, see run_host
+    return lattice_host(h, LatticeCall{true, false, in, y, band, 0, init, n_init, init_stride, nullptr, nullptr, true, out});
 }
 
 }  // extern "C"

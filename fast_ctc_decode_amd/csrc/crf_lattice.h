@@ -1,0 +1,276 @@
+// crf_lattice.h -- what the walks of the lattice of a GIVEN labelling under a CRF model share: crf_lattice.hip (forward
+// sum and best alignment) and crf_posterior.hip (forward and backward).  Parameter block, LDS layout, everything before
+// the time loop (the rows without a value, the labelling and its state trajectory), the staging of the posteriors, the
+// live window of a row and what a lane reads for one forward row.  Included by those translation units only.
+#pragma once
+
+#include <math.h>
+
+#include <algorithm>
+
+#include "ctc_lattice.h"
+
+namespace fcd {
+namespace {
+
+constexpr uint32_t kNoState = 0xFFFFFFu;  // sigma outside 0 .. S-1: every posterior of the state reads as 0
+struct CrfParams {
+    BatchDesc in;
+    ScoreDesc y;
+    const float *init;
+    int64_t n_init, init_stride;
+    int band;
+    int lab_cap;        // states (labels + 1) the LDS copy of a labelling holds
+    int pow_m;          // S == nb^pow_m with nb >= 2, pow_m >= 1: sigma_k is a function of the last pow_m labels; 0: serial scan
+    int staged;         // whole rows in LDS (S * N <= kTileElems)
+    int rows_per_tile;  // rows between two fills (staged: what the tile holds; gather: kTileRows)
+    double *logp;
+    // align only
+    uint32_t *start;
+    uint32_t *count;
+    float *qual;
+    unsigned char *bp;
+    int64_t bp_row_bytes;
+};
+
+struct CrfLds {
+    float *tile;     // kTileElems raw posteriors; the traceback's chunk afterwards
+    int *krow;
+    int *misc;       // [16] bad-label flag, [17] kBadPost, [18] the final cell
+    uint32_t *info;  // per state k: sigma_k (kNoState: outside the table) | y_k << 24 (0 for state L)
+};
+
+__device__ __forceinline__ CrfLds crf_carve(unsigned char *smem) {
+    CrfLds l;
+    l.tile = reinterpret_cast<float *>(smem);
+    l.krow = reinterpret_cast<int *>(smem + kTileElems * 4);
+    l.misc = l.krow + kTileRows;
+    l.info = reinterpret_cast<uint32_t *>(l.misc + kMiscWords);
+    return l;
+}
+
+inline size_t crf_lds_bytes(int lab_cap) { return (size_t)kTileElems * 4 + (kTileRows + kMiscWords) * 4 + (size_t)lab_cap * 4; }
+
+struct CrfRow {
+    const float *post;
+    const uint32_t *path;
+    int Tr, L;
+};
+
+__device__ __forceinline__ int int_from_prev_lane(int x) {  // wave_ror:1
+    return __builtin_amdgcn_update_dpp(0, x, 0x13C, 0xf, 0xf, false);
+}
+
+// Everything before the time loop: the rows without a value, the labelling and its state trajectory.  Returns false when
+// the row's result is already written (every lane agrees).
+__device__ __forceinline__ bool crf_prologue(const CrfParams &p, const CrfLds &lds, CrfRow *rw) {
+    const int lane = threadIdx.x;
+    const int64_t row = blockIdx.x;
+    const int64_t read = row / p.y.n_hyp;
+    const int64_t hyp = row - read * p.y.n_hyp;
+    const double nan = (double)NAN;
+    if (p.y.n_valid && hyp >= (int64_t)p.y.n_valid[read]) {
+        if (lane == 0) p.logp[row] = nan;
+        return false;
+    }
+    int64_t Tr = p.in.lengths ? p.in.lengths[read] : p.in.T;
+    Tr = Tr < 0 ? 0 : (Tr > p.in.T ? p.in.T : Tr);
+    const uint32_t len = p.y.len[row];
+    if ((int64_t)len > p.y.stride) {
+        if (lane == 0) p.logp[row] = nan;
+        return false;
+    }
+    const int L = (int)len;
+    const uint8_t *labels = p.y.labels + row * p.y.stride;
+    if (lane == 0) lds.misc[16] = 0;
+    __syncthreads();
+    bool bad = false;
+    for (int k = lane; k < L; k += 64) {
+        const int y = labels[k];
+        bad |= y < 1 || y >= p.in.N;
+    }
+    if (bad) lds.misc[16] = 1;
+    __syncthreads();
+    double early = 0.0;
+    bool done = true;
+    if (lds.misc[16]) early = nan;
+    else if (Tr == 0) early = L == 0 ? 0.0 : -(double)INFINITY;
+    else if ((int64_t)L > Tr) early = -(double)INFINITY;
+    else done = false;
+    if (done) {
+        if (lane == 0) p.logp[row] = early;
+        return false;
+    }
+    // sigma_0: the first maximum of the init row (src/search.rs:58,404)
+    const float *init = p.init + read * p.init_stride;
+    float bv = -INFINITY;
+    int bi = 0x7fffffff;
+    for (int64_t i = lane; i < p.n_init; i += 64) {
+        float v = init[i];
+        v = v != v ? -INFINITY : v;  // (a NaN counts as -inf)
+        if (bi == 0x7fffffff || v > bv) {
+            bv = v;
+            bi = (int)i;
+        }
+    }
+    for (int m = 1; m < 64; m <<= 1) {
+        const float ov = __shfl_xor(bv, m);
+        const int oi = __shfl_xor(bi, m);
+        if (oi != 0x7fffffff && (bi == 0x7fffffff || ov > bv || (ov == bv && oi < bi))) {
+            bv = ov;
+            bi = oi;
+        }
+    }
+    const int64_t S = p.in.S, nb = p.in.N - 1;
+    // the trajectory sigma_{k+1} = (sigma_k * nb) mod S + (y_k - 1) (:97,414): serial up to where the closed form starts
+    const int serial_end = p.pow_m > 0 ? min(p.pow_m - 1, L) : L;  // the last state of the serial scan
+    if (lane == 0) {
+        int64_t s = bi;
+        for (int k = 0; k <= serial_end; ++k) {
+            const uint32_t y = k < L ? labels[k] : 0u;
+            lds.info[k] = ((s >= 0 && s < S) ? (uint32_t)s : kNoState) | (y << 24);
+            if (k < L) s = (s * nb) % S + ((int64_t)y - 1);
+        }
+    }
+    for (int k = serial_end + 1 + lane; k <= L; k += 64) {  // (pow_m labels behind state k exist: k >= pow_m)
+        int64_t s = 0;
+        for (int j = k - p.pow_m; j < k; ++j) s = s * nb + ((int64_t)labels[j] - 1);
+        const uint32_t y = k < L ? labels[k] : 0u;
+        lds.info[k] = (uint32_t)s | (y << 24);
+    }
+    if (lane == 0) lds.misc[kBadPost] = 0;
+    __syncthreads();
+    rw->post = post_at(p.in.post, read * p.in.stride_read, p.in.dtype);
+    rw->path = p.y.path ? p.y.path + row * p.y.stride : nullptr;
+    rw->Tr = (int)Tr;
+    rw->L = L;
+    return true;
+}
+
+// rows t0 .. t0 + rc of the read into the tile (staged shapes); banded: k(t) of each of them
+__device__ __forceinline__ void crf_fill_tile(const CrfParams &p, const CrfLds &lds, const CrfRow &rw, int t0, int rc) {
+    const int lane = threadIdx.x;
+    __syncthreads();  // the previous tile's readers are done
+    if (p.staged) {
+        const int SN = p.in.S * p.in.N;
+        for (int e = lane; e < rc * SN; e += 64) {
+            const int i = e / SN, rem = e - i * SN;
+            const int s = rem / p.in.N, j = rem - s * p.in.N;
+            lds.tile[e] = load_post(rw.post, (int64_t)(t0 + i) * p.in.stride_t + (int64_t)s * p.in.stride_s + (int64_t)j * p.in.stride_n,
+                                    p.in.dtype);
+        }
+    }
+    if (p.band > 0 && lane < rc) {  // k(t) = #{k : path[k] <= t}
+        const uint32_t t = (uint32_t)(t0 + lane);
+        int lo = 0, hi = rw.L;
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (rw.path[mid] <= t) lo = mid + 1;
+            else hi = mid;
+        }
+        lds.krow[lane] = lo;
+    }
+    __syncthreads();
+}
+
+// live states of row t: the band around the path, cut to what can be reached and can still reach the end
+__device__ __forceinline__ void crf_window(const CrfParams &p, const CrfLds &lds, const CrfRow &rw, int t, int i, int *lo, int *hi) {
+    int l = 0, h = rw.L;
+    if (p.band > 0) {
+        const int k = lds.krow[i];
+        l = max(0, k - p.band);
+        h = min(h, k + p.band);
+    }
+    *hi = min(h, t + 1);
+    *lo = max(l, rw.L - (rw.Tr - 1 - t));
+}
+
+// What a lane needs for one row, read a row ahead of its use (nothing here depends on alpha).  Per slot r: the two
+// posteriors of the state the slot held in the PREVIOUS row, split, and whether their products enter a live cell.
+template <int K>
+struct CrfStep {
+    float pm0[K], pmy[K];
+    int pe0[K], pey[K];
+    uint32_t stay_mask;  // bit r: the slot holds the same state in both rows, live in both
+    uint32_t adv_mask;   // bit r: the state above the slot's previous one is live in this row
+    uint32_t bad;        // a value that enters a live cell is NaN, infinite or negative
+    int lo, hi;
+};
+
+__device__ __forceinline__ void crf_split(float v, float *m, int *e) {
+    int ex = 0;
+    float mm = v;
+    if (v - v == 0.0f) mm = frexpf(v, &ex);  // (finite; an infinity or a NaN stays what it is, exponent 0)
+    *m = mm;
+    *e = ex;
+}
+
+template <int K>
+__device__ __forceinline__ CrfStep<K> crf_load_step(const CrfParams &p, const CrfLds &lds, const CrfRow &rw, int t, int i,
+                                                    int lo_prev, int hi_prev) {
+    CrfStep<K> in;
+    const int lane = threadIdx.x;
+    crf_window(p, lds, rw, t, i, &in.lo, &in.hi);
+    in.stay_mask = in.adv_mask = in.bad = 0;
+    const int SN = p.in.S * p.in.N;
+#pragma unroll
+    for (int r = 0; r < K; ++r) {
+        const int kp = slot_state<K>(lane, r, lo_prev);
+        const bool src = kp <= hi_prev;
+        const uint32_t info = lds.info[src ? kp : 0];  // (a dead slot reads a valid address and is masked below)
+        const uint32_t sig = info & 0xFFFFFFu, y = info >> 24;
+        const bool stay = src && kp >= in.lo && kp <= in.hi;
+        const bool adv = src && kp < rw.L && kp + 1 >= in.lo && kp + 1 <= in.hi;
+        const bool table = sig != kNoState;
+        float v0 = 0.0f, vy = 0.0f;
+        if (p.staged) {
+            const int base = i * SN + (int)(table ? sig : 0u) * p.in.N;
+            if (stay && table) v0 = lds.tile[base];
+            if (adv && table) vy = lds.tile[base + (int)y];
+        } else {
+            const int64_t base = (int64_t)t * p.in.stride_t + (int64_t)(table ? sig : 0u) * p.in.stride_s;
+            if (stay && table) v0 = load_post(rw.post, base, p.in.dtype);
+            if (adv && table) vy = load_post(rw.post, base + (int64_t)y * p.in.stride_n, p.in.dtype);
+        }
+        in.bad |= (!(v0 >= 0.0f && v0 - v0 == 0.0f) || !(vy >= 0.0f && vy - vy == 0.0f)) ? 1u : 0u;
+        crf_split(v0, &in.pm0[r], &in.pe0[r]);
+        crf_split(vy, &in.pmy[r], &in.pey[r]);
+        in.stay_mask |= (stay ? 1u : 0u) << r;
+        in.adv_mask |= (adv ? 1u : 0u) << r;
+    }
+    return in;
+}
+
+CrfParams crf_params(const BatchDesc &in, const ScoreDesc &y, const float *init, int64_t n_init, int64_t init_stride,
+                     int64_t band) {
+    CrfParams p{};
+    p.in = in;
+    p.y = y;
+    p.init = init;
+    p.n_init = n_init;
+    p.init_stride = init_stride;
+    p.band = (int)band;
+    p.lab_cap = (int)std::min(in.T, y.stride) + 1;
+    const int64_t nb = in.N - 1, SN = (int64_t)in.S * in.N;
+    p.pow_m = 0;
+    if (nb >= 2) {
+        int m = 0;
+        int64_t v = 1;
+        while (v < in.S) {
+            v *= nb;
+            ++m;
+        }
+        if (v == in.S && m >= 1) p.pow_m = m;
+    }
+    p.staged = SN <= kTileElems;
+    p.rows_per_tile = p.staged ? (int)std::min<int64_t>(kTileRows, kTileElems / SN) : kTileRows;
+    return p;
+}
+
+int crf_states_per_lane(int64_t T, int64_t stride, int64_t band) {
+    const int64_t states = crf_lattice_window_states(T, stride, band);
+    return states <= 64 ? 1 : (states <= 128 ? 2 : (states <= 256 ? 4 : 8));
+}
+
+}  // namespace
+}  // namespace fcd

@@ -274,6 +274,16 @@ hipError_t launch_crf_score(const BatchDesc &in, const ScoreDesc &y, const float
                             int64_t band, double *logp, hipStream_t stream);
 hipError_t launch_crf_align(const BatchDesc &in, const ScoreDesc &y, const float *init, int64_t n_init, int64_t init_stride,
                             int64_t band, const AlignOut &out, unsigned char *bp, hipStream_t stream);
+// CRF forward-backward substitution posteriors of given labellings (crf_posterior.hip; fcd_crf_posterior_* in include/fcd.h),
+// on top of crf_lattice_unsupported.  crf_posterior_unsupported: 0 = the kernels hold the call; 1 = the window exceeds the
+// *max_states register-resident states of the chain's tier, 2 = more than 8 labels, 4 = S is no power of N - 1, 5 = a
+// history beyond the tiers (m > 6 or m (N - 1) > 24).  *max_states: 512 where m (N - 1) <= 8 and N - 1 <= 4, 256 where
+// m = 1 and N - 1 > 4, else 192.  alpha: crf_posterior_row_bytes() of device memory per labelling of the launch (the stored
+// forward rows); post: [labellings * stride * (N - 1)]; logp must not be null.
+int crf_posterior_unsupported(int64_t T, int64_t S, int64_t N, int64_t stride, int64_t band, int64_t *max_states);
+size_t crf_posterior_row_bytes(int64_t T, int64_t S, int64_t N, int64_t stride, int64_t band);
+hipError_t launch_crf_posterior(const BatchDesc &in, const ScoreDesc &y, const float *init, int64_t n_init, int64_t init_stride,
+                                int64_t band, float *post, double *logp, unsigned char *alpha, hipStream_t stream);
 
 hipError_t launch_logspace_probe(const float *a, const float *b, float *out_add, float *out_ln,
                                  int64_t n, int mode, hipStream_t stream);

@@ -570,6 +570,66 @@ int fcd_crf_align_dev(fcd_handle *h, const fcd_batch *in, const float *init, int
 int fcd_crf_align_host(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init, int64_t init_stride,
                        const fcd_labellings *y, int64_t band, const fcd_alignment *out);
 
+/* ---- CRF forward-backward substitution posteriors of given labellings (csrc/crf_posterior.hip) ----
+ * NOT a reference function.  Everything is as fcd_crf_score_* defines it: batch (n_reads, T, S, N), init, nb = N - 1, the
+ * trajectory sigma_0 = first maximum of the init row, sigma_{k+1} = (sigma_k * nb) mod S + (y_k - 1), the reading rule
+ * P(t, k, j) = p[t][sigma_k][j], the lattice k = 0 .. L, under band = W the window from y->path.
+ * For hypothesis i of read r (row = r * n_hyp + i), position k < L and label c in 1 .. N-1, y[k:=c] is y with label k
+ * replaced by c:
+ *   sub[k][c]  = exp(crf_score(y[k:=c])) -- the variant has ITS OWN trajectory, the same init row, and under a band the
+ *                window derived from y's own path (windows are in label counts: a variant's window is the same set of cells)
+ *   post[k][c] = sub[k][c] / sum_{c' = 1 .. N-1} sub[k][c']      float32, entry ((row * stride + k) * (N-1) + c-1)
+ *   conf[k]    = post[k][y_k]
+ *   logp       = ln P(y | x), fcd_crf_score_*'s value within its tolerance; float64, nullable
+ * What fcd_crf_align_*'s qual is not: how much better the called label explains the read than another label would, with all
+ * alignments counted.
+ * Shapes: S = nb^m with nb >= 2 and m >= 1, or S = 1.  The model state is then the last m labels as base-nb digits, no sigma
+ * ever leaves 0 .. S-1 after state 0, and the variant's trajectory is closed-form:
+ *   sigma'_{k+j} = sigma_{k+j} + (c - y_k) * nb^(j-1) for j = 1 .. m; it rejoins y's trajectory at state k + m + 1.
+ * S = 1 walks as m = 1: the trajectory rule gives sigma_{k+1} = y_k - 1 there -- the table's one row after label 1, outside
+ * the table (a dead end, as fcd_crf_score_* has it) after any other label, for y and for its variants alike.
+ * Computed without rescoring any variant.  Pass 1: fcd_crf_score_*'s forward recurrence, every row's cells stored.  Pass 2
+ * walks the rows backwards: beta_{T_r-1}[L] = 1, beta_t[k] = P(t+1,k,0) beta_{t+1}[k] + P(t+1,k,y_k) beta_{t+1}[k+1], and per
+ * state s the chain values V_s[j][c], j = 1 .. min(m, s) -- the backward value state s has in the variant that substituted c
+ * at position s - j:
+ *   V_s[j][c]_t = P'(t+1,s,0) V_s[j][c]_{t+1} + P'(t+1,s,y_s) V_{s+1}[j+1][c]_{t+1},  P' read from row
+ *   sigma_s + (c - y_{s-j}) nb^(j-1),  V_{s+1}[m+1][c] = beta[s+1];  at the last row the value is [s = L].
+ *   sub[k][c] = sum_t alpha_{t-1}[k] * P(t,k,c) * V_{k+1}[1][c]_t                 (c = y_k gives P(y | x) for every k)
+ * A chain that would pass state L ends there.
+ * Numerics: fcd_crf_score_*'s and fcd_ctc_posterior_*'s -- f32 probability space, exact power-of-two rescaling with integer
+ * exponents (one per forward row; one per backward row shared by beta and every V; one per position for its accumulators,
+ * counted from floor(log2 P(y | x)): it starts at 0, where the called label's sum is about 1, and rises with the largest
+ * term, so a variant may outweigh y by any factor -- y's share is then the 0 it rounds to), every term non-negative, one
+ * rounding per product and per sum, no fused multiply-add.  A cell below 2^-160 of its row's maximum may be dropped.  Error bound, by roundings along the longest chain: alpha_{t-1} carries 3 t (two products and a sum a row), V_t
+ * 3 (T_r - 1 - t), a term two products, the sum over the rows at most T_r -- a sub[k][c] is within (4 T_r - 1) 2^-24 of its
+ * value, relative; the ratio doubles that and adds the N - 2 sums of the denominator and the division:
+ *   |post - exact| <= (8 T_r + 6) 2^-24 * post.
+ * Rows without a value: logp follows fcd_crf_score_*'s order and values (i >= n_valid[r], len > stride, a bad label,
+ * T_r = 0, L > T_r, a NaN in a contributing cell).  Whenever P(y | x) is not a positive finite number every post entry for
+ * k < min(len, stride) is NaN.  A position whose sum over c is 0 or NaN is NaN; a NaN posterior that only a variant reads
+ * makes that position NaN and leaves logp alone.  Entries k >= len are never written by _dev and are 0 from _host.  L = 0
+ * writes logp only.
+ * FCD_E_INVALID: fcd_crf_score_*'s cases, and a null out or out->post.
+ * Limits (FCD_E_UNSUPPORTED; the message says which): fcd_crf_score_*'s, and
+ *   S that is no power of N - 1 (S = 5, N = 4);  N - 1 > 8;
+ *   the kernels are instantiated on (states per lane, m, nb) tiers -- a held state costs m nb registers --
+ *     m <= 2 and nb <= 4,  m <= 4 and nb <= 2   (m nb <= 8):    windows up to 512 states (1, 2, 4, 8 states per lane)
+ *     m <= 1 and 5 <= nb <= 8                   (m nb <= 8):    windows up to 256 states (band <= 127; 1, 2, 4 per lane:
+ *                                                               eight states of eight labels do not fit 256 VGPRs)
+ *     m <= 3 and nb <= 8,  m <= 6 and nb <= 4   (m nb <= 24):   windows up to 192 states (band <= 95; 1, 2, 3 per lane)
+ *   (S = 4, 16 at N = 5: the first row; S = 64, 1024, 4096 at N = 5: the third.)  Any other (m, nb) is unsupported, a wider
+ *   window too, with the band that fits in the message.
+ * _dev: device pointers, enqueue-only on the handle's stream, behind overlapping searches in flight that still write the
+ * arrays it reads.  The forward rows (4 bytes per slot, 64 / 128 / 256 / 512 slots a row for windows up to that many
+ * states -- 64 / 128 / 192 in the last row of the table -- plus an exponent word) live in the handle's workspace: the
+ * labellings are launched in groups of whole reads that fit 4 GiB of it (or fcd_set_workspace_limit), forward then backward
+ * per group, one after the other on the stream, no host wait in between.
+ * _host: host pointers; stages, runs and copies back in one piece. */
+int fcd_crf_posterior_dev(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init, int64_t init_stride,
+                          const fcd_labellings *y, int64_t band, const fcd_posterior *out);
+int fcd_crf_posterior_host(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init, int64_t init_stride,
+                           const fcd_labellings *y, int64_t band, const fcd_posterior *out);
+
 /* ---- search::crf_greedy_search (src/search.rs:385-423) ---- */
 int fcd_crf_greedy_search_dev(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init,
                               int64_t init_stride, const fcd_result *out);
