@@ -44,6 +44,7 @@ def build(force=False, opt="-O1"):
         return LIB
     os.makedirs(OUT, exist_ok=True)
     flags = ["g++", opt, "-g", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-w",
+             "-fno-pretty-templates",  # (the launch log, hip/hip_runtime.h: kernel names with every template argument)
              "-DFCD_HIPEMU=1", "-I", HERE, "-I", CSRC]
     procs, objs = [], []
     for s in _sources():

@@ -177,8 +177,19 @@ void launch(dim3 grid, dim3 block, size_t lds_bytes, F f) {
 #define gridDim (hipemu::ids().gdim)
 #define warpSize 64
 
-#define hipLaunchKernelGGL(kern, grid, block, lds, stream, ...) \
-    (hipemu::check_launch_stream(stream), hipemu::launch((grid), (block), (size_t)(lds), [=]() { kern(__VA_ARGS__); }))
+// The launch log (tests/test_instantiation_ledger_emu.py): every launch records WHICH instantiation it ran.  kname<&k>() is
+// the compiler's own spelling of the kernel's name with its template arguments (tests/hipemu/build.py compiles with
+// -fno-pretty-templates, so that gcc spells defaulted trailing arguments out as well); taking the address also keeps an
+// out-of-line copy of every kernel in libfcd_emu.so (the address goes to log_launch for that alone), so that `nm -C` lists
+// exactly the instantiations the sources launch.
+namespace hipemu {
+template <auto K> const char *kname() { return __PRETTY_FUNCTION__; }
+void log_launch(const char *pretty_name, const void *kernel);
+}  // namespace hipemu
+
+#define hipLaunchKernelGGL(kern, grid, block, lds, stream, ...)                              \
+    (hipemu::check_launch_stream(stream), hipemu::log_launch(hipemu::kname<&kern>(), reinterpret_cast<const void *>(&kern)), \
+     hipemu::launch((grid), (block), (size_t)(lds), [=]() { kern(__VA_ARGS__); }))
 
 // ---- device intrinsics ----------------------------------------------------------------------------
 static inline int __float_as_int(float f) { int i; memcpy(&i, &f, 4); return i; }

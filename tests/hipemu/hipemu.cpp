@@ -229,7 +229,38 @@ void launch_impl(dim3 grid, dim3 block, size_t lds_bytes, void (*tramp)(void *),
     }
 }
 
+// ---- the launch log: the names of the instantiations launched since the last reset, each once, in first-launch order
+static std::mutex g_log_mutex;
+static std::vector<const char *> g_log;  // (the strings are the kname<>() literals: compared by address first)
+
+void log_launch(const char *pretty_name, const void *) {
+    std::lock_guard<std::mutex> g(g_log_mutex);
+    for (const char *s : g_log)
+        if (s == pretty_name || !strcmp(s, pretty_name)) return;
+    g_log.push_back(pretty_name);
+}
+
 }  // namespace hipemu
+
+extern "C" void hipemu_launch_log_reset() {
+    std::lock_guard<std::mutex> g(hipemu::g_log_mutex);
+    hipemu::g_log.clear();
+}
+
+// Writes the logged names, one per line, into buf (NUL-terminated, cut at cap - 1 bytes); returns the bytes the whole
+// log needs, the NUL included -- call again with a larger buffer when that exceeds cap.
+extern "C" size_t hipemu_launch_log_read(char *buf, size_t cap) {
+    std::lock_guard<std::mutex> g(hipemu::g_log_mutex);
+    size_t need = 1, at = 0;
+    for (const char *s : hipemu::g_log) {
+        const size_t n = strlen(s);
+        need += n + 1;
+        for (size_t i = 0; i <= n; ++i)
+            if (buf && at + 1 < cap) buf[at++] = i < n ? s[i] : '\n';
+    }
+    if (buf && cap) buf[at] = 0;
+    return need;
+}
 
 // ---- host runtime stand-ins -------------------------------------------------------------------
 // Devices: FCD_EMU_DEVICES (default 1) emulated devices.  The current device is per host thread, as in HIP; streams
