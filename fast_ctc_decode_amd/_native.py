@@ -55,7 +55,7 @@ SYMBOLS = [
     "fcd_ctc_posterior_dev", "fcd_ctc_posterior_host",
     "fcd_ctc_edits_dev", "fcd_ctc_edits_host",
     "fcd_crf_score_dev", "fcd_crf_score_host", "fcd_crf_align_dev", "fcd_crf_align_host",
-    "fcd_crf_posterior_dev", "fcd_crf_posterior_host",
+    "fcd_crf_posterior_dev", "fcd_crf_posterior_host", "fcd_crf_edits_dev", "fcd_crf_edits_host",
 ]
 JOB_PATH, JOB_QUAL, JOB_AMBIGUOUS, JOB_DONE = 1, 2, 4, 1
 
@@ -98,7 +98,7 @@ class Posterior(C.Structure):
 
 
 class Edits(C.Structure):
-    """fcd_edits: what fcd_ctc_edits_* writes (include/fcd.h)."""
+    """fcd_edits: what fcd_ctc_edits_* and fcd_crf_edits_* write (include/fcd.h)."""
     _fields_ = [("deletion", C.c_void_p), ("insertion", C.c_void_p), ("logp", C.c_void_p)]
 
 
@@ -265,6 +265,7 @@ def bind(lib):
         getattr(lib, "fcd_crf_score_" + sfx).argtypes = [P, BP, P, i64, i64, C.POINTER(Labellings), i64, P]
         getattr(lib, "fcd_crf_align_" + sfx).argtypes = [P, BP, P, i64, i64, C.POINTER(Labellings), i64, C.POINTER(Alignment)]
         getattr(lib, "fcd_crf_posterior_" + sfx).argtypes = [P, BP, P, i64, i64, C.POINTER(Labellings), i64, C.POINTER(Posterior)]
+        getattr(lib, "fcd_crf_edits_" + sfx).argtypes = [P, BP, P, i64, i64, C.POINTER(Labellings), i64, C.POINTER(Edits)]
     return lib
 
 

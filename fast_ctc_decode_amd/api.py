@@ -888,6 +888,17 @@ class BatchResult:
         return crf_posterior_batch_raw(network_outputs, init_states, self.labels, self.out_len, lengths,
                                        self.path if band else None, band, None, input_dtype, getattr(self, "_handle", None))
 
+    def crf_edits(self, network_outputs, init_states, lengths=None, band=0, input_dtype=None):
+        """The deletion and insertion likelihoods under the CRF model of every read's result -> EditResult, deletion
+        (n_reads, 1, stride), insertion (n_reads, 1, stride + 1, N-1): crf_edits_batch_raw on this result's own arrays
+        (device results stay on the device).  Arguments as crf_score."""
+        if getattr(network_outputs, "ndim", 4) != 4:
+            raise ValueError("crf_edits covers the results of the CRF searches, (n_reads, T, S, N) posteriors, not plain CTC results")
+        if band and self.path is None:
+            raise ValueError("a band needs the result's path")
+        return crf_edits_batch_raw(network_outputs, init_states, self.labels, self.out_len, lengths,
+                                   self.path if band else None, band, None, input_dtype, getattr(self, "_handle", None))
+
     def sequences(self, alphabet, raise_on_error=True, paths="list"):
         """-> list of (str, path) per read, exactly what the single-read functions return.
 
@@ -1248,6 +1259,16 @@ class NBestResult:
         return crf_posterior_batch_raw(network_outputs, init_states, self.labels, self.out_len, lengths,
                                        self.path if band else None, band, self.n_hyp, input_dtype,
                                        getattr(self, "_handle", None))
+
+    def crf_edits(self, network_outputs, init_states, lengths=None, band=0, input_dtype=None):
+        """The deletion and insertion likelihoods under the CRF model of every hypothesis -> EditResult, deletion
+        (n_reads, n_best, stride), insertion (n_reads, n_best, stride + 1, N-1); logp NaN where i >= n_hyp[r].
+        crf_edits_batch_raw on this result's own arrays; plain CTC results are refused."""
+        if not self.crf or getattr(network_outputs, "ndim", 4) != 4:
+            raise ValueError("crf_edits covers the results of the CRF searches, not plain CTC results")
+        return crf_edits_batch_raw(network_outputs, init_states, self.labels, self.out_len, lengths,
+                                   self.path if band else None, band, self.n_hyp, input_dtype,
+                                   getattr(self, "_handle", None))
 
     def hypotheses(self, alphabet, raise_on_error=True):
         """-> per read, a list of (seq, path, score), best first (None for a failed read when not raise_on_error)."""
@@ -1755,7 +1776,7 @@ def _host_array(a):
 
 
 class EditResult:
-    """Outcome of ctc_edits_batch_raw, float32 log-ratios against the labelling itself (include/fcd.h): deletion[r, i, k] =
+    """Outcome of ctc_edits_batch_raw and crf_edits_batch_raw, float32 log-ratios against the labelling itself (include/fcd.h): deletion[r, i, k] =
     ln P(y without label k | x) - ln P(y | x) and insertion[r, i, g, c - 1] = ln P(y with label c inserted before label g,
     g = L: at the end | x) - ln P(y | x) for hypothesis i of read r, all alignments counted -- a positive entry is an edit
     that explains the read better than y.  logp[r, i] (float64) is ln P(y | x), ctc_score's value.  -inf: a variant without
@@ -1950,6 +1971,42 @@ def crf_posterior_batch_raw(network_outputs, init_states, labels, label_lengths,
     return PosteriorResult(post, logp)
 
 
+def crf_edits_batch_raw(network_outputs, init_states, labels, label_lengths, lengths=None, paths=None, band=0,
+                        n_valid=None, input_dtype=None, handle=None):
+    """CRF deletion and insertion likelihoods: for every label of every labelling how much better or worse the read is
+    explained without it, and for every gap and every label how much better or worse with that label inserted there --
+    each variant with its own model-state trajectory -- as log-ratios against the labelling itself, summed over every
+    alignment in one forward and two backward walks (include/fcd.h, fcd_crf_edits_*).  With crf_posterior_batch_raw's
+    substitutions: every labelling one edit away.
+    -> EditResult with deletion (B, n_hyp, stride), insertion (B, n_hyp, stride + 1, N-1) float32 and logp (B, n_hyp)
+    float64, crf_score's value within its tolerance.
+
+    Arguments and limits as crf_posterior_batch_raw.
+    Device tensors in: torch tensors on the same device, enqueued on torch's current stream, not synchronised.
+    numpy in: numpy out."""
+    band = _check_band(band, paths)
+    h, b, y, (B, n_hyp, stride), dev, keep = _lattice_inputs(network_outputs, labels, label_lengths, lengths, paths, band,
+                                                             n_valid, input_dtype, handle, init_states)
+    init = keep[-1]
+    nc = int(b.N) - 1
+    if dev is not None:
+        import torch
+        dele = torch.zeros((B, n_hyp, stride), dtype=torch.float32, device=dev)
+        ins = torch.zeros((B, n_hyp, stride + 1, nc), dtype=torch.float32, device=dev)
+        logp = torch.empty((B, n_hyp), dtype=torch.float64, device=dev)
+        out = nat.Edits(dele.data_ptr(), ins.data_ptr(), logp.data_ptr())
+        h.check(h.lib.fcd_crf_edits_dev(h.ptr, C.byref(b), C.c_void_p(init.data_ptr()), int(init.shape[1]),
+                                        int(init.shape[1]), C.byref(y), band, C.byref(out)))
+        return EditResult(dele, ins, logp)
+    dele = np.zeros((B, n_hyp, stride), np.float32)
+    ins = np.zeros((B, n_hyp, stride + 1, nc), np.float32)
+    logp = np.empty((B, n_hyp), np.float64)
+    out = nat.Edits(dele.ctypes.data, ins.ctypes.data, logp.ctypes.data)
+    h.check(h.lib.fcd_crf_edits_host(h.ptr, C.byref(b), init.ctypes.data, init.shape[1], init.shape[1], C.byref(y), band,
+                                     C.byref(out)))
+    return EditResult(dele, ins, logp)
+
+
 def _crf_sequence_labels(sequence, alpha, what):
     """The labels behind a string crf_beam_search built: it joins the labels' strings leaf to root and reverses the
     CHARACTERS (src/search.rs:146-156), so a multi-character label appears reversed."""
@@ -2012,6 +2069,16 @@ def crf_posterior(network_output, init_state, sequence, alphabet):
     x, init, lab, n, L = _crf_one_read(network_output, init_state, sequence, alphabet, "crf_posterior")
     r = crf_posterior_batch_raw(x, init, lab, n)
     return r.post[0, 0, :L].copy(), float(r.logp[0, 0])
+
+
+def crf_edits(network_output, init_state, sequence, alphabet):
+    """The deletion and insertion likelihoods of one string (as crf_beam_search returns it) against one (T, S, N) float32
+    posterior array under the CRF model, exact lattice: -> (deletion, insertion, logp) with deletion an (L,) and insertion
+    an (L + 1, N-1) float32 array of log-ratios (insertion[g, c - 1]: alphabet[c] inserted before label g) and logp =
+    ln P(sequence | network_output).  Argument checks as crf_score."""
+    x, init, lab, n, L = _crf_one_read(network_output, init_state, sequence, alphabet, "crf_edits")
+    r = crf_edits_batch_raw(x, init, lab, n)
+    return r.deletion[0, 0, :L].copy(), r.insertion[0, 0, :L + 1].copy(), float(r.logp[0, 0])
 
 
 # ---------------------------------------------------------------------------------------------

@@ -1592,7 +1592,7 @@ int fcd_debug_set_align_workspace_cap(fcd_handle *h, int64_t bytes) {
 }
 
 namespace {
-// One fcd_{ctc,crf}_{score,align,posterior}_{dev,host} or fcd_ctc_edits_{dev,host} call: the score
+// One fcd_{ctc,crf}_{score,align,posterior,edits}_{dev,host} call: the score
 // writes `logp`, the alignment `out`, the posteriors `post`, the edit likelihoods `edits`.
 struct LatticeCall {
     bool crf, align;
@@ -1613,7 +1613,7 @@ struct LatticeCall {
 int lattice_check(fcd_handle *h, const LatticeCall &c) {
     if (c.align && !c.out) return fail(h, FCD_E_INVALID, "null alignment");
     if (c.posterior && !c.post) return fail(h, FCD_E_INVALID, "null posterior");
-    if (c.edit && !c.edits) return fail(h, FCD_E_INVALID, "ctc_edits: null output");
+    if (c.edit && !c.edits) return fail(h, FCD_E_INVALID, c.crf ? "crf_edits: null output" : "ctc_edits: null output");
     const fcd_batch *in = c.in;
     const fcd_labellings *y = c.y;
     int rc = check_batch(h, in, c.crf);
@@ -1632,9 +1632,9 @@ int lattice_check(fcd_handle *h, const LatticeCall &c) {
     if (in->n_reads > 0 && (!y->labels || !y->len ||
                             !(c.edit ? (const void *)c.edits->deletion : c.posterior ? (const void *)c.post->post
                               : c.align ? (const void *)c.out->start : (const void *)c.logp)))
-        return fail(h, FCD_E_INVALID, c.edit ? "ctc_edits: null labels/len/deletion" : c.posterior ? "null labels/len/post"
+        return fail(h, FCD_E_INVALID, c.edit ? (c.crf ? "crf_edits: null labels/len/deletion" : "ctc_edits: null labels/len/deletion") : c.posterior ? "null labels/len/post"
                                       : c.align ? "null labels/len/start" : "null labels/len/logp");
-    if (c.edit && in->n_reads > 0 && !c.edits->insertion) return fail(h, FCD_E_INVALID, "ctc_edits: null insertion");
+    if (c.edit && in->n_reads > 0 && !c.edits->insertion) return fail(h, FCD_E_INVALID, c.crf ? "crf_edits: null insertion" : "ctc_edits: null insertion");
     if (in->n_reads * y->n_hyp >= (1ll << 31)) return fail(h, FCD_E_UNSUPPORTED, "more than 2^31 labellings in one call");
     if (c.crf) {
         switch (crf_lattice_unsupported(in->T, in->S, y->stride, std::min<int64_t>(c.band, 1ll << 28))) {
@@ -1649,16 +1649,18 @@ int lattice_check(fcd_handle *h, const LatticeCall &c) {
                                                      : "ctc_score: the exact lattice does not fit the 160 KiB of LDS: use a band");
     }
     if (c.align && in->n_reads > 0 && !c.out->count) return fail(h, FCD_E_INVALID, "null count");
-    if (c.crf && c.posterior) {
+    if (c.crf && (c.posterior || c.edit)) {
         int64_t fit = 0;
-        switch (crf_posterior_unsupported(in->T, in->S, in->N, y->stride, std::min<int64_t>(c.band, 1ll << 28), &fit)) {
-        case 1: return fail(h, FCD_E_UNSUPPORTED, (std::string("crf_posterior: a model state of this depth holds windows of ") +
+        const int64_t bnd = std::min<int64_t>(c.band, 1ll << 28);
+        const std::string who = c.edit ? "crf_edits" : "crf_posterior";
+        switch (crf_posterior_unsupported(in->T, in->S, in->N, y->stride, bnd, &fit)) {  // (one set of limits: the same kernels)
+        case 1: return fail(h, FCD_E_UNSUPPORTED, (who + ": a model state of this depth holds windows of " +
                                                    std::to_string(fit) + " states: use a band of at most " +
                                                    std::to_string((fit - 1) / 2)).c_str());
-        case 2: return fail(h, FCD_E_UNSUPPORTED, "crf_posterior: more than 8 labels besides the blank");
-        case 4: return fail(h, FCD_E_UNSUPPORTED, "crf_posterior: S must be a power of N - 1 (the model state is the last labels)");
-        case 5: return fail(h, FCD_E_UNSUPPORTED, "crf_posterior: the model state holds more labels than the kernels carry "
-                                                  "(S = (N - 1)^m with m <= 6 and m (N - 1) <= 24, or m <= 4 at N = 3)");
+        case 2: return fail(h, FCD_E_UNSUPPORTED, (who + ": more than 8 labels besides the blank").c_str());
+        case 4: return fail(h, FCD_E_UNSUPPORTED, (who + ": S must be a power of N - 1 (the model state is the last labels)").c_str());
+        case 5: return fail(h, FCD_E_UNSUPPORTED, (who + ": the model state holds more labels than the kernels carry "
+                                                   "(S = (N - 1)^m with m <= 6 and m (N - 1) <= 24, or m <= 4 at N = 3)").c_str());
         default: break;
         }
     } else if (c.edit || c.posterior) {  // (one set of limits: both walk ctc_posterior.hip's register-resident window)
@@ -1788,15 +1790,18 @@ int lattice_edits(fcd_handle *h, const LatticeCall &c) {
     const size_t nc = (size_t)in->N - 1, n_rows = (size_t)in->n_reads * (size_t)y->n_hyp;
     const size_t del_row = (size_t)y->stride, ins_row = ((size_t)y->stride + 1) * nc;  // entries of one labelling
     const int64_t bnd = std::min<int64_t>(c.band, 1ll << 28);
+    // (the CTC kernels size their rows by the band as given, the CRF kernels by the band the launch gets)
+    const size_t row_bytes = c.crf ? crf_posterior_row_bytes(in->T, in->S, in->N, y->stride, bnd) : ctc_posterior_row_bytes(in->T, y->stride, c.band);
     return lattice_grouped(
-        h, c, ctc_posterior_row_bytes(in->T, y->stride, c.band), std::min<int64_t>(4ll << 30, workspace_budget(h)), out->logp,
+        h, c, row_bytes, std::min<int64_t>(4ll << 30, workspace_budget(h)), out->logp,
         [&](CallScope &sc) {
             sc.add(out->deletion, n_rows * del_row * 4);
             sc.add(out->insertion, n_rows * ins_row * 4);
         },
-        [&](const BatchDesc &d, const ScoreDesc &yd, int64_t, int64_t row0, double *logp, unsigned char *alpha, hipStream_t stream) {
-            return launch_ctc_edits(d, yd, c.collapse, bnd, out->deletion + (size_t)row0 * del_row,
-                                    out->insertion + (size_t)row0 * ins_row, logp, alpha, stream);
+        [&](const BatchDesc &d, const ScoreDesc &yd, int64_t r0, int64_t row0, double *logp, unsigned char *alpha, hipStream_t stream) {
+            float *del = out->deletion + (size_t)row0 * del_row, *ins = out->insertion + (size_t)row0 * ins_row;
+            return c.crf ? launch_crf_edits(d, yd, c.init + r0 * c.init_stride, c.n_init, c.init_stride, bnd, del, ins, logp, alpha, stream)
+                         : launch_ctc_edits(d, yd, c.collapse, bnd, del, ins, logp, alpha, stream);
         });
 }
 
@@ -1967,6 +1972,20 @@ int fcd_crf_posterior_host(fcd_handle *h, const fcd_batch *in, const float *init
     if (!h) return FCD_E_INVALID;
     std::lock_guard<std::recursive_mutex> whole_call(h->mu);  // staging .. copy-back, see run_host
     return lattice_host(h, LatticeCall{true, false, in, y, band, 0, init, n_init, init_stride, nullptr, nullptr, true, out});
+}
+
+int fcd_crf_edits_dev(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init, int64_t init_stride,
+                      const fcd_labellings *y, int64_t band, const fcd_edits *out) {
+    if (!h) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> g(h->mu);
+    return lattice_dev(h, LatticeCall{true, false, in, y, band, 0, init, n_init, init_stride, nullptr, nullptr, false, nullptr, true, out});
+}
+
+int fcd_crf_edits_host(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init, int64_t init_stride,
+                       const fcd_labellings *y, int64_t band, const fcd_edits *out) {
+    if (!h) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> whole_call(h->mu);  // staging .. copy-back, see run_host
+    return lattice_host(h, LatticeCall{true, false, in, y, band, 0, init, n_init, init_stride, nullptr, nullptr, false, nullptr, true, out});
 }
 
 }  // extern "C"

@@ -24,6 +24,9 @@ struct CrfParams {
     int pow_m;          // S == nb^pow_m with nb >= 2, pow_m >= 1: sigma_k is a function of the last pow_m labels; 0: serial scan
     int staged;         // whole rows in LDS (S * N <= kTileElems)
     int rows_per_tile;  // rows between two fills (staged: what the tile holds; gather: kTileRows)
+    // the cone's margins, in states: a labelling one label shorter reaches the end from one state lower (forward) and is
+    // one state further at every row (backward).  0 everywhere but in the launches of fcd_crf_edits_* (crf_posterior.hip)
+    int cone_lo, cone_hi;
     double *logp;
     // align only
     uint32_t *start;
@@ -173,16 +176,21 @@ __device__ __forceinline__ void crf_fill_tile(const CrfParams &p, const CrfLds &
     __syncthreads();
 }
 
-// live states of row t: the band around the path, cut to what can be reached and can still reach the end
-__device__ __forceinline__ void crf_window(const CrfParams &p, const CrfLds &lds, const CrfRow &rw, int t, int i, int *lo, int *hi) {
+// live states of row t, k = k(t): the band around the path, cut to what can be reached and can still reach the end -- the
+// cone, widened by cone_hi states above and cone_lo below (never beyond the band's own bounds)
+__device__ __forceinline__ void crf_window_of(const CrfParams &p, const CrfRow &rw, int t, int k, int cone_lo, int cone_hi,
+                                              int *lo, int *hi) {
     int l = 0, h = rw.L;
     if (p.band > 0) {
-        const int k = lds.krow[i];
         l = max(0, k - p.band);
         h = min(h, k + p.band);
     }
-    *hi = min(h, t + 1);
-    *lo = max(l, rw.L - (rw.Tr - 1 - t));
+    *hi = min(h, t + 1 + cone_hi);
+    *lo = max(l, rw.L - (rw.Tr - 1 - t) - cone_lo);
+}
+
+__device__ __forceinline__ void crf_window(const CrfParams &p, const CrfLds &lds, const CrfRow &rw, int t, int i, int *lo, int *hi) {
+    crf_window_of(p, rw, t, p.band > 0 ? lds.krow[i] : 0, p.cone_lo, p.cone_hi, lo, hi);
 }
 
 // What a lane needs for one row, read a row ahead of its use (nothing here depends on alpha).  Per slot r: the two

@@ -30,6 +30,11 @@
 // A value enters a cell only where both its source and the cell are live in their rows' windows (crf_window): the windows
 // are in label counts, so every variant walks the cells y walks.
 //
+// fcd_crf_edits_* (the deletion and insertion likelihoods of the same labellings) is the same forward launch -- with the cone
+// kept one state wider below, CrfParams::cone_lo -- and two more walks compiled into crfp_back_kernel, selected by the
+// wave-uniform q.walk: crfp_back_walk<K, MM, NB, WALK> below says where they differ from the substitution walk.  Their
+// accumulators become float32 log-ratios against ln P(y | x) (crf_log_ratio), as ctc_posterior.hip's edit walk forms them.
+//
 // Scales.  beta and every V share one integer exponent per row.  The step is two passes over the row's posteriors: the
 // first takes only exponents -- the largest frexp(old) + frexp(posterior) over every product of the row, E, reduced as an
 // integer (wave_imax); a product is below 2^E and the largest at least 2^(E-2), so with every product rescaled by the exact
@@ -61,7 +66,10 @@ struct CrfPostParams {
     float *alpha;  // the stored forward rows, alpha_words per labelling of this launch
     int64_t alpha_words;
     int m;  // S == nb^m; S == 1: 1 (the one label sigma is made of, before the table cuts it)
+    int walk;  // what the backward launch walks (wave-uniform): kWalkSub, kWalkIns, kWalkDel
+    float *del, *ins;  // [.. * stride], [.. * (stride + 1) * (N - 1)]                          (fcd_crf_edits_*)
 };
+constexpr int kWalkSub = 0, kWalkIns = 1, kWalkDel = 2;
 
 // ---- pass 1: crf_lattice.hip's forward sum, storing what it computes ----
 template <int K>
@@ -161,13 +169,7 @@ __device__ __forceinline__ float crf_from_next_lane(float x) {  // wave_rol:1 --
 
 // crf_window with k(t) handed in (the row before the tile has no krow entry)
 __device__ __forceinline__ void crf_window_k(const CrfParams &p, const CrfRow &rw, int t, int k, int *lo, int *hi) {
-    int l = 0, h = rw.L;
-    if (p.band > 0) {
-        l = max(0, k - p.band);
-        h = min(h, k + p.band);
-    }
-    *hi = min(h, t + 1);
-    *lo = max(l, rw.L - (rw.Tr - 1 - t));
+    crf_window_of(p, rw, t, k, p.cone_lo, p.cone_hi, lo, hi);
 }
 
 // the posterior p[u][sig][col] of the tile's row i (staged shapes: from LDS; the others: from global memory)
@@ -193,44 +195,135 @@ __device__ __forceinline__ float crf_term(float old, float v, int sh) {
     return ldexpf(old * m, min(max(e + sh, -512), 512));
 }
 
-template <int K, int MM, int NB>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void crfp_back_kernel(CrfPostParams q) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+// ---- what the walks of fcd_crf_edits_* need next to the substitution walk's helpers ----
+// ln(v * 2^e) - lp, what the outputs hold: the logarithm of the mantissa in f32 (in [ln 0.5, 0): its rounding is below
+// 2^-24), the exponents and the labelling's own ln P in float64.  v = 0: -inf; a NaN: NaN.  (ctc_posterior.hip's.)
+__device__ __forceinline__ float crf_log_ratio(float v, int64_t e, double lp) {
+    if (v == 0.0f) return -INFINITY;
+    if (!(v > 0.0f) || v - v != 0.0f) return NAN;
+    int ex;
+    const float m = frexpf(v, &ex);
+    return (float)((double)logf(m) + (double)(e + ex) * 0.693147180559945309417232121458 - lp);
+}
+
+// every entry of the walk's output the row owns -- k < min(len, stride), g <= min(len, stride) -- set to v
+template <int WALK>
+__device__ __forceinline__ void crf_fill_edits(const CrfPostParams &q, float v) {
+    const int64_t row = blockIdx.x, nc = q.c.in.N - 1;
+    const int64_t n = min((int64_t)q.c.y.len[row], q.c.y.stride);
+    if constexpr (WALK == kWalkDel) {
+        for (int64_t e = threadIdx.x; e < n; e += 64) q.del[row * q.c.y.stride + e] = v;
+    } else {
+        for (int64_t e = threadIdx.x; e < (n + 1) * nc; e += 64) q.ins[row * (q.c.y.stride + 1) * nc + e] = v;
+    }
+}
+
+// a complete position leaves the registers: the substitution posteriors of label s; the insertions into gap s; the
+// deletion of label s - 1 (its accumulator rides in the slot of the state after it)
+template <int WALK, int NB, int CN>
+__device__ __forceinline__ void crf_store_position(const CrfPostParams &q, int s, int L, int nb, const float (&acc)[CN], int64_t e,
+                                                   double lp) {
+    const int64_t row = blockIdx.x;
+    if constexpr (WALK == kWalkSub) {
+        if (s < L) crf_store_post<NB>(q.post + row * q.c.y.stride * nb, s, nb, acc);
+    } else if constexpr (WALK == kWalkIns) {
+        float *ins = q.ins + (row * (q.c.y.stride + 1) + s) * nb;
+#pragma unroll
+        for (int c = 0; c < CN; ++c)
+            if (c < nb) ins[c] = crf_log_ratio(acc[c], e, lp);
+    } else {
+        if (s >= 1 && s < L) q.del[row * q.c.y.stride + s - 1] = crf_log_ratio(acc[0], e, lp);
+    }
+}
+
+// chain slot j of state s is in use: the variant substituted position s - 1 - j; inserted into gap s - j; deleted label
+// s - 2 - j (m: the labels of the model state)
+template <int WALK>
+__device__ __forceinline__ bool crf_chain_live(bool live, int j, int m, int s) {
+    if constexpr (WALK == kWalkSub) return live && j < m && j < s;
+    else if constexpr (WALK == kWalkIns) return live && j < m && j <= s;
+    else return live && j < m - 1 && j + 2 <= s;
+}
+
+// what the chain's posterior row depends on besides sigma_s: the label the variant replaced (substitution); the model
+// state the edit left from, sigma_{s-j} (insertion), sigma_{s-2-j} (deletion)
+template <int WALK>
+__device__ __forceinline__ int crf_chain_word(const CrfLds &lds, bool chain, int s, int j) {
+    const uint32_t w = lds.info[chain ? s - (WALK == kWalkSub ? 1 : (WALK == kWalkIns ? 0 : 2)) - j : 0];
+    return WALK == kWalkSub ? (int)(w >> 24) : (int)(w & 0xFFFFFFu);
+}
+
+// the part of an edit's posterior row that no label c changes (pw = nb^j): the digits of sigma_from that are still inside the
+// history, moved up past the edit, and the labels of y since -- insertion: j of them, below the inserted one; deletion: j + 1
+template <int WALK>
+__device__ __forceinline__ int crf_edit_row_base(const CrfParams &p, bool chain, int from, int sig, int pw, int nb) {
+    if (!chain || p.in.S == 1) return 0;  // (S == 1, insertion: the row is the label alone)
+    const int pwn = pw * nb;              // (chain: j < m, so nb^(j+1) divides S)
+    return (from % (p.in.S / pwn)) * pwn + (WALK == kWalkIns ? sig % pw : sig % pwn);
+}
+
+// One backward walk.  WALK = kWalkSub is the walk the head of the file describes.  The other two are fcd_crf_edits_*'s and
+// differ from it where `if constexpr` says so:
+//   kWalkIns  V[r][j][c] = U_s[j][c], the backward value state s has in the variant that inserted c into gap s - j, read
+//             from row (sigma_{s-j} nb^(j+1)) mod S + (c - 1) nb^j + sigma_s mod nb^j; U_{s+1}[m][c] = beta[s+1].  Gap g gains
+//             alpha_{u-1}[g] * P(u,g,c) * U_g[0][c]_u: its OWN slot's value.  Chains 0 <= s - j, positions 0 .. L; L = 0 walks.
+//   kWalkDel  V[r][j][0] = W_s[j], the value state s has in the variant that deleted label s - 2 - j, read from row
+//             (sigma_{s-2-j} nb^(j+1)) mod S + sigma_s mod nb^(j+1); W_{s+1}[m-1] = beta[s+1]: MM - 1 chain slots, one
+//             accumulator.  D[k] rides in the slot of state k + 1 and gains alpha_{u-1}[k] * P(u,k,y_{k+1}) * X_u[k+2], X = W[0]
+//             (m = 1: beta): alpha from the state below (the forward launch kept the cone one state wider below for it: the
+//             forward window is computed here next to the walk's own, which is one state wider ABOVE -- q.c.cone_hi), X from the
+//             slot above.  D[L-1] = alpha_{T_r-1}[L-1] comes off the last forward row.
+// An entry no row's window holds keeps what the fill wrote: NaN (substitution), -inf (the edits: probability 0).
+template <int K, int MM, int NB, int WALK>
+__device__ __forceinline__ void crfp_back_walk(const CrfPostParams &q, unsigned char *smem) {
     constexpr int C = 64 * K;
+    constexpr bool kSub = WALK == kWalkSub, kIns = WALK == kWalkIns, kDel = WALK == kWalkDel;
+    constexpr int JN = kDel ? MM - 1 : MM;  // chain slots in use
+    constexpr int J = JN > 0 ? JN : 1;
+    constexpr int CN = kDel ? 1 : NB;       // variants per chain slot, and accumulators per state
     // the widest instantiations: a slot's posteriors are read when its turn comes, not all slots' ahead of the first --
     // what the scheduler would otherwise hoist does not fit the 256 registers
     constexpr bool kSlotFence = K * MM * NB > 48;
     const CrfParams &p = q.c;
     const CrfLds lds = crf_carve(smem);
     CrfRow rw;
-    if (!crf_prologue(p, lds, &rw)) {  // (the forward launch wrote this row's logp already; the same value again)
-        crf_no_posterior(q);
-        return;
+    const bool walk = crf_prologue(p, lds, &rw);  // (the forward launch wrote this row's logp already; the same value again)
+    if constexpr (kSub) {
+        if (!walk) {
+            crf_no_posterior(q);
+            return;
+        }
     }
     const double lp = p.logp[blockIdx.x];
-    if (lp - lp != 0.0) {  // P = 0, or a NaN on the way
-        crf_no_posterior(q);
+    if (lp - lp != 0.0) {  // P = 0, or a NaN on the way (the edits: or not a labelling)
+        if constexpr (kSub) crf_no_posterior(q);
+        else crf_fill_edits<WALK>(q, NAN);
         return;
     }
-    if (rw.L == 0) return;
-    crf_no_posterior(q);  // a position no row's window holds keeps this
-    __syncthreads();      // the fill is in place before another lane's store writes over it
+    if constexpr (kSub) {
+        if (rw.L == 0) return;
+        crf_no_posterior(q);  // a position no row's window holds keeps this
+    } else {
+        crf_fill_edits<WALK>(q, -INFINITY);  // an edit no row carries has probability 0
+        if (!walk) return;                   // (T_r = 0 and L = 0: P(y | x) = 1, and no insertion has an alignment)
+        if (kDel && rw.L == 0) return;
+    }
+    __syncthreads();  // the fill is in place before another lane's store writes over it
     const int lane = threadIdx.x, nb = p.in.N - 1, L = rw.L, m = q.m;
     const float *am = q.alpha + (int64_t)blockIdx.x * q.alpha_words;
     const int *ae = reinterpret_cast<const int *>(am + (int64_t)p.in.T * C);
-    float *post = q.post + (int64_t)blockIdx.x * p.y.stride * nb;
-    float b[K], V[K][MM][NB], acc[K][NB];
+    float b[K], V[K][J][CN], acc[K][CN];
     int xa[K];  // the exponent of a slot's accumulators, above Xp
 #pragma unroll
     for (int r = 0; r < K; ++r) {
         b[r] = 0.0f;
         xa[r] = 0;
 #pragma unroll
-        for (int c = 0; c < NB; ++c) acc[r][c] = 0.0f;
+        for (int c = 0; c < CN; ++c) acc[r][c] = 0.0f;
 #pragma unroll
-        for (int j = 0; j < MM; ++j)
+        for (int j = 0; j < J; ++j)
 #pragma unroll
-            for (int c = 0; c < NB; ++c) V[r][j][c] = 0.0f;
+            for (int c = 0; c < CN; ++c) V[r][j][c] = 0.0f;
     }
     int64_t eb = 0;
     const int64_t xp = (int64_t)floor(lp * 1.44269504088896340735992468100189214);  // floor(log2 P(y | x))
@@ -255,10 +348,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void cr
             const int u = t0 + i;
             int lo_u, hi_u;  // the window of row u: the states whose "old" values the registers hold
             crf_window(p, lds, rw, u, i, &lo_u, &hi_u);
-            lo_p = hi_p = 0;  // the window of row u - 1 ("row -1": state 0): the states that get a value in this step
+            lo_p = 0;  // the window of row u - 1 ("row -1": state 0): the states that get a value in this step
+            hi_p = kDel ? min(L, 1) : 0;  // (the deletion walk's is a state wider above, at "row -1" too)
+            int lo_a = 0, hi_a = 0;  // (deletion) the forward window of row u - 1: the states alpha_{u-1} holds
             int64_t x_u = 0;
             if (u > 0) {
-                crf_window_k(p, rw, u - 1, p.band > 0 ? (i > 0 ? lds.krow[i - 1] : lds.misc[kKrowBefore]) : 0, &lo_p, &hi_p);
+                const int kp = p.band > 0 ? (i > 0 ? lds.krow[i - 1] : lds.misc[kKrowBefore]) : 0;
+                crf_window_k(p, rw, u - 1, kp, &lo_p, &hi_p);
+                if constexpr (kDel) crf_window_of(p, rw, u - 1, kp, 1, 0, &lo_a, &hi_a);
                 x_u = ae[u - 1];
             }
             const float *arow = am + (int64_t)max(u - 1, 0) * C + lane * K;  // alpha_{u-1}, by slot
@@ -268,19 +365,29 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void cr
                     const bool last = slot_state<K>(lane, r, lo_u) == L;
                     b[r] = last ? 1.0f : 0.0f;
 #pragma unroll
-                    for (int j = 0; j < MM; ++j)
+                    for (int j = 0; j < JN; ++j)
 #pragma unroll
-                        for (int c = 0; c < NB; ++c) V[r][j][c] = (last && (j >= m || j < L)) ? 1.0f : 0.0f;
+                        for (int c = 0; c < CN; ++c)
+                            V[r][j][c] = (last && (kSub ? (j >= m || j < L) : (kIns ? (j >= m || j <= L) : (j >= m - 1 || j + 2 <= L))))
+                                             ? 1.0f : 0.0f;
                 }
                 first = false;
+                if constexpr (kDel) {  // the last label's deletion: the shortened labelling's final state, off the last forward row
+                    if (lane == 0) {
+                        int la, ha;
+                        crf_window_of(p, rw, u, p.band > 0 ? lds.krow[i] : 0, 1, 0, &la, &ha);
+                        const float v = (L - 1 >= la && L - 1 <= ha) ? am[(int64_t)u * C + (L - 1) % C] : 0.0f;
+                        q.del[(int64_t)blockIdx.x * p.y.stride + L - 1] = crf_log_ratio(v, ae[u], lp);
+                    }
+                }
             } else {  // the states that were live at row u and are not at row u - 1: their positions are complete
 #pragma unroll
                 for (int r = 0; r < K; ++r) {
                     const int s = slot_state<K>(lane, r, lo_u);
                     if (s > hi_p) {  // (b and V stay: this step still reads them as the values of row u)
-                        if (s <= hi_u && s < L) crf_store_post<NB>(post, s, nb, acc[r]);
+                        if (s <= hi_u) crf_store_position<WALK, NB, CN>(q, s, L, nb, acc[r], xp + xa[r], lp);
 #pragma unroll
-                        for (int c = 0; c < NB; ++c) acc[r][c] = 0.0f;
+                        for (int c = 0; c < CN; ++c) acc[r][c] = 0.0f;
                         xa[r] = 0;
                     }
                 }
@@ -290,11 +397,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void cr
             {
                 // (the next lane's first slot, as it stands at row u; rotated once per pass, so that no copy lives across both)
                 const float nb0 = crf_from_next_lane(b[0]);
-                float nV[MM][NB];
+                float nV[J][CN];
 #pragma unroll
-                for (int j = 0; j < MM; ++j)
+                for (int j = 0; j < JN; ++j)
 #pragma unroll
-                    for (int c = 0; c < NB; ++c) nV[j][c] = crf_from_next_lane(V[0][j][c]);
+                    for (int c = 0; c < CN; ++c) nV[j][c] = crf_from_next_lane(V[0][j][c]);
 #pragma unroll
                 for (int r = 0; r < K; ++r) {
                     int ln = lane;
@@ -317,18 +424,21 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void cr
                     if (nxt && table) emax = max(emax, crf_term_exp(bn, crf_post_value(p, lds, rw, u, i, sig, y)));
                     int pw = 1;
 #pragma unroll
-                    for (int j = 0; j < MM; ++j) {
+                    for (int j = 0; j < JN; ++j) {
                         if (kSlotFence) __asm__ volatile("" ::: "memory");
-                        const bool chain = live && j < m && j < s;  // the variant substituted position s - 1 - j
-                        const int yk = (int)(lds.info[chain ? s - 1 - j : 0] >> 24);
+                        const bool chain = crf_chain_live<WALK>(live, j, m, s);
+                        const int yk = crf_chain_word<WALK>(lds, chain, s, j);
+                        const int base = kSub ? 0 : crf_edit_row_base<WALK>(p, chain, yk, sig, pw, nb);
 #pragma unroll
-                        for (int c = 0; c < NB; ++c) {
+                        for (int c = 0; c < CN; ++c) {
                             bool ok = chain && c < nb;
-                            const int sv = ok ? (p.in.S == 1 ? yk - 1 : sig) + (c + 1 - yk) * pw : 0;  // (S == 1: below, then c)
+                            int sv = 0;
+                            if constexpr (kSub) sv = ok ? (p.in.S == 1 ? yk - 1 : sig) + (c + 1 - yk) * pw : 0;  // (S == 1: below, then c)
+                            else sv = ok ? base + (kIns ? c * pw : 0) : 0;
                             ok = ok && sv < p.in.S;
                             const float vo = own ? V[r][j][c] : 0.0f;
-                            const float up = j + 1 < MM ? (r + 1 < K ? V[r + 1 < K ? r + 1 : 0][j + 1 < MM ? j + 1 : 0][c]
-                                                                     : nV[j + 1 < MM ? j + 1 : 0][c])
+                            const float up = j + 1 < JN ? (r + 1 < K ? V[r + 1 < K ? r + 1 : 0][j + 1 < JN ? j + 1 : 0][c]
+                                                                     : nV[j + 1 < JN ? j + 1 : 0][c])
                                                         : (r + 1 < K ? b[r + 1 < K ? r + 1 : 0] : nb0);
                             const float vn = nxt ? up : 0.0f;
                             if (ok && own) emax = max(emax, crf_term_exp(vo, crf_post_value(p, lds, rw, u, i, sv, 0)));
@@ -348,11 +458,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void cr
             // ---- the terms of acc, and the values of row u - 1, in place: slot r reads slots r and r + 1 only ----
             // the next lane's first slot, as it stands at row u
             const float nb0 = crf_from_next_lane(b[0]);
-            float nV[MM][NB];
+            float nV[J][CN];
 #pragma unroll
-            for (int j = 0; j < MM; ++j)
+            for (int j = 0; j < JN; ++j)
 #pragma unroll
-                for (int c = 0; c < NB; ++c) nV[j][c] = crf_from_next_lane(V[0][j][c]);
+                for (int c = 0; c < CN; ++c) nV[j][c] = crf_from_next_lane(V[0][j][c]);
 #pragma unroll
             for (int r = 0; r < K; ++r) {
                 int ln = lane;
@@ -371,27 +481,45 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void cr
                 const int sig = table ? (int)sg : 0;
                 const float bo = own ? b[r] : 0.0f;
                 const float bn = nxt ? (r + 1 < K ? b[r + 1 < K ? r + 1 : 0] : nb0) : 0.0f;
-                const float av = u > 0 ? (live ? arow[r] : 0.0f) : 1.0f;  // ("row -1": state 0, the one live state, holds 1)
+                float av;  // alpha_{u-1} of the state the term leaves from ("row -1": state 0, the one live state, holds 1)
+                if constexpr (kDel) {  // state s - 1, where the forward window holds it
+                    const bool below = live && s >= 1 && s - 1 >= lo_a && s - 1 <= hi_a;
+                    av = u > 0 ? (below ? am[(int64_t)(u - 1) * C + (s - 1) % C] : 0.0f) : (s == 1 ? 1.0f : 0.0f);
+                } else {
+                    av = u > 0 ? (live ? arow[r] : 0.0f) : 1.0f;
+                }
                 const float b0 = (own && table) ? crf_term(bo, crf_post_value(p, lds, rw, u, i, sig, 0), sh) : 0.0f;
                 const float b1 = (nxt && table) ? crf_term(bn, crf_post_value(p, lds, rw, u, i, sig, y), sh) : 0.0f;
                 const float b_new = b0 + b1;  // (b[r] itself is written last: the terms below read it as it stands at row u)
-                // what position s gains at this row: state s emits c, the variant's state s + 1 takes over
+                // what position s gains at this row: state s emits c, the variant's state s + 1 takes over (insertion: the
+                // variant's state lives in slot s itself; deletion: state s - 1 emits y_s, the variant goes on in slot s + 1)
                 // (the slot's exponent rises, its accumulators rescaled with it, before a term of 2^kAccTop or more enters: a
                 // variant that outweighs y by more than f32 holds takes the accumulators down with it instead of overflowing)
+                int sig_from = sig;
+                bool from_table = table;
+                if constexpr (kDel) {
+                    const uint32_t sb = lds.info[(live && s >= 1) ? s - 1 : 0] & 0xFFFFFFu;
+                    from_table = sb != kNoState;
+                    sig_from = from_table ? (int)sb : 0;
+                }
+                const bool gains = kSub ? nxt : (kIns ? own : (nxt && s >= 1 && s < L));
 #pragma unroll
-                for (int c = 0; c < NB; ++c) {
-                    if (c < nb && nxt) {
-                        const float vn = r + 1 < K ? V[r + 1 < K ? r + 1 : 0][0][c] : nV[0][c];
+                for (int c = 0; c < CN; ++c) {
+                    if (c < nb && gains) {
+                        float vn;
+                        if constexpr (kIns) vn = V[r][0][c];
+                        else if constexpr (kDel && JN == 0) vn = r + 1 < K ? b[r + 1 < K ? r + 1 : 0] : nb0;
+                        else vn = r + 1 < K ? V[r + 1 < K ? r + 1 : 0][0][c] : nV[0][c];
                         float pm;
                         int pe;
-                        crf_split(table ? crf_post_value(p, lds, rw, u, i, sig, c + 1) : 0.0f, &pm, &pe);
+                        crf_split(from_table ? crf_post_value(p, lds, rw, u, i, sig_from, kDel ? y : c + 1) : 0.0f, &pm, &pe);
                         const float term = (av * pm) * vn;
                         const int e = finite_exp(term);
                         if (e != kNoExp && e + dt + pe - kAccTop > xa[r]) {
                             const int up = e + dt + pe - kAccTop;
                             const int down = max(xa[r] - up, -512);
 #pragma unroll
-                            for (int c2 = 0; c2 < NB; ++c2) acc[r][c2] = ldexpf(acc[r][c2], down);
+                            for (int c2 = 0; c2 < CN; ++c2) acc[r][c2] = ldexpf(acc[r][c2], down);
                             xa[r] = up;
                         }
                         acc[r][c] += ldexpf(term, min(max(dt + pe - xa[r], -512), 512));
@@ -399,23 +527,26 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void cr
                 }
                 int pw = 1;
 #pragma unroll
-                for (int j = 0; j < MM; ++j) {
+                for (int j = 0; j < JN; ++j) {
                     if (kSlotFence) __asm__ volatile("" ::: "memory");
-                    const bool chain = live && j < m && j < s;
-                    const int yk = (int)(lds.info[chain ? s - 1 - j : 0] >> 24);
+                    const bool chain = crf_chain_live<WALK>(live, j, m, s);
+                    const int yk = crf_chain_word<WALK>(lds, chain, s, j);
+                    const int base = kSub ? 0 : crf_edit_row_base<WALK>(p, chain, yk, sig, pw, nb);
 #pragma unroll
-                    for (int c = 0; c < NB; ++c) {
+                    for (int c = 0; c < CN; ++c) {
                         bool ok = chain && c < nb;
-                        const int sv = ok ? (p.in.S == 1 ? yk - 1 : sig) + (c + 1 - yk) * pw : 0;  // (S == 1: below, then c)
+                        int sv = 0;
+                        if constexpr (kSub) sv = ok ? (p.in.S == 1 ? yk - 1 : sig) + (c + 1 - yk) * pw : 0;  // (S == 1: below, then c)
+                        else sv = ok ? base + (kIns ? c * pw : 0) : 0;
                         ok = ok && sv < p.in.S;
                         const float vo = own ? V[r][j][c] : 0.0f;
-                        const float up = j + 1 < MM ? (r + 1 < K ? V[r + 1 < K ? r + 1 : 0][j + 1 < MM ? j + 1 : 0][c]
-                                                                 : nV[j + 1 < MM ? j + 1 : 0][c])
+                        const float up = j + 1 < JN ? (r + 1 < K ? V[r + 1 < K ? r + 1 : 0][j + 1 < JN ? j + 1 : 0][c]
+                                                                 : nV[j + 1 < JN ? j + 1 : 0][c])
                                                     : (r + 1 < K ? b[r + 1 < K ? r + 1 : 0] : nb0);
                         const float vn = nxt ? up : 0.0f;
                         const float c0 = (ok && own) ? crf_term(vo, crf_post_value(p, lds, rw, u, i, sv, 0), sh) : 0.0f;
                         const float c1 = (ok && nxt) ? crf_term(vn, crf_post_value(p, lds, rw, u, i, sv, y), sh) : 0.0f;
-                        V[r][j][c] = j < m ? c0 + c1 : b_new;
+                        V[r][j][c] = j < (kDel ? m - 1 : m) ? c0 + c1 : b_new;
                     }
                     pw *= nb;
                 }
@@ -423,12 +554,21 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void cr
             }
         }
     }
-    // the positions whose state is live at "row -1": state 0
+    // the positions whose state is live at "row -1": state 0 (deletion: and state 1)
 #pragma unroll
     for (int r = 0; r < K; ++r) {
         const int s = slot_state<K>(lane, r, lo_p);
-        if (s <= hi_p && s < L) crf_store_post<NB>(post, s, nb, acc[r]);
+        if (s <= hi_p) crf_store_position<WALK, NB, CN>(q, s, L, nb, acc[r], xp + xa[r], lp);
     }
+}
+
+template <int K, int MM, int NB>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void crfp_back_kernel(CrfPostParams q) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    // (every instantiation carries all three walks within its 256 registers: a kernel's count is its widest walk's)
+    if (q.walk == kWalkIns) return crfp_back_walk<K, MM, NB, kWalkIns>(q, smem);
+    if (q.walk == kWalkDel) return crfp_back_walk<K, MM, NB, kWalkDel>(q, smem);
+    crfp_back_walk<K, MM, NB, kWalkSub>(q, smem);
 }
 
 // the chain tier that holds (m, nb), the narrowest alphabet first: 2 = {4, 2}, 1 = {2, 4} (up to 8 states per lane),
@@ -455,21 +595,23 @@ int crf_post_chain(int64_t S, int64_t nb) {
     return v == S ? m : -1;
 }
 
+// forward, then the backward walks of q[1 .. n_back] (crf_posterior: one; crf_edits: insertion, deletion), all on the rows
+// the forward launch stored
 template <int K, int MM, int NB>
-void launch_pair(const CrfPostParams &q, dim3 grid, size_t lds, hipStream_t stream) {
-    hipLaunchKernelGGL(crfp_fwd_kernel<K>, grid, dim3(64), lds, stream, q);
-    hipLaunchKernelGGL((crfp_back_kernel<K, MM, NB>), grid, dim3(64), lds, stream, q);
+void launch_pair(const CrfPostParams *q, int n_back, dim3 grid, size_t lds, hipStream_t stream) {
+    hipLaunchKernelGGL(crfp_fwd_kernel<K>, grid, dim3(64), lds, stream, q[0]);
+    for (int w = 1; w <= n_back; ++w) hipLaunchKernelGGL((crfp_back_kernel<K, MM, NB>), grid, dim3(64), lds, stream, q[w]);
 }
 
 // KMAX: the most states per lane the tier is instantiated at -- 8: 1, 2, 4, 8; 4: 1, 2, 4; 3: 1, 2, 3 (what fits 256 VGPRs
 // without scratch: eight states of eight labels do not)
 template <int MM, int NB, int KMAX>
-hipError_t launch_tier(const CrfPostParams &q, int k, dim3 grid, size_t lds, hipStream_t stream) {
-    if (k == 1) launch_pair<1, MM, NB>(q, grid, lds, stream);
-    else if (k == 2) launch_pair<2, MM, NB>(q, grid, lds, stream);
-    else if (KMAX == 3 && k == 3) launch_pair<KMAX == 3 ? 3 : 1, MM, NB>(q, grid, lds, stream);
-    else if (KMAX >= 4 && k == 4) launch_pair<KMAX >= 4 ? 4 : 1, MM, NB>(q, grid, lds, stream);
-    else if (KMAX >= 8 && k == 8) launch_pair<KMAX >= 8 ? 8 : 1, MM, NB>(q, grid, lds, stream);
+hipError_t launch_tier(const CrfPostParams *q, int n_back, int k, dim3 grid, size_t lds, hipStream_t stream) {
+    if (k == 1) launch_pair<1, MM, NB>(q, n_back, grid, lds, stream);
+    else if (k == 2) launch_pair<2, MM, NB>(q, n_back, grid, lds, stream);
+    else if (KMAX == 3 && k == 3) launch_pair<KMAX == 3 ? 3 : 1, MM, NB>(q, n_back, grid, lds, stream);
+    else if (KMAX >= 4 && k == 4) launch_pair<KMAX >= 4 ? 4 : 1, MM, NB>(q, n_back, grid, lds, stream);
+    else if (KMAX >= 8 && k == 8) launch_pair<KMAX >= 8 ? 8 : 1, MM, NB>(q, n_back, grid, lds, stream);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }
@@ -504,28 +646,59 @@ size_t crf_posterior_row_bytes(int64_t T, int64_t S, int64_t N, int64_t stride, 
     return ((size_t)std::max<int64_t>(T, 1) * (64 * k + 1) * 4 + 255) & ~(size_t)255;
 }
 
-hipError_t launch_crf_posterior(const BatchDesc &in, const ScoreDesc &y, const float *init, int64_t n_init, int64_t init_stride,
-                                int64_t band, float *post, double *logp, unsigned char *alpha, hipStream_t stream) {
+namespace {
+// q[0]: the forward launch; q[1 .. n_back]: the backward walks
+hipError_t launch_crf_walks(CrfPostParams *q, int n_back, const BatchDesc &in, const ScoreDesc &y, const float *init, int64_t n_init,
+                            int64_t init_stride, int64_t band, double *logp, unsigned char *alpha, hipStream_t stream) {
     const int64_t rows = in.n_reads * y.n_hyp;
     if (rows <= 0) return hipSuccess;
-    CrfPostParams q;
-    q.c = crf_params(in, y, init, n_init, init_stride, band);
-    q.c.logp = logp;
-    q.post = post;
-    q.alpha = reinterpret_cast<float *>(alpha);
-    q.alpha_words = (int64_t)(crf_posterior_row_bytes(in.T, in.S, in.N, y.stride, band) / 4);
-    q.m = crf_post_chain(in.S, in.N - 1);
+    const CrfParams c = crf_params(in, y, init, n_init, init_stride, band);
+    for (int w = 0; w <= n_back; ++w) {
+        const int lo = q[w].c.cone_lo, hi = q[w].c.cone_hi;
+        q[w].c = c;
+        q[w].c.cone_lo = lo;
+        q[w].c.cone_hi = hi;
+        q[w].c.logp = logp;
+        q[w].alpha = reinterpret_cast<float *>(alpha);
+        q[w].alpha_words = (int64_t)(crf_posterior_row_bytes(in.T, in.S, in.N, y.stride, band) / 4);
+        q[w].m = crf_post_chain(in.S, in.N - 1);
+    }
     const dim3 grid((unsigned)rows);
-    const size_t lds = crf_lds_bytes(q.c.lab_cap);
-    const int tier = crf_post_tier(q.m, in.N - 1), k = crf_post_states_per_lane(tier, in.T, y.stride, band);
+    const size_t lds = crf_lds_bytes(c.lab_cap);
+    const int tier = crf_post_tier(q[0].m, in.N - 1), k = crf_post_states_per_lane(tier, in.T, y.stride, band);
     switch (tier) {
-    case 0: return launch_tier<1, 8, 4>(q, k, grid, lds, stream);
-    case 1: return launch_tier<2, 4, 8>(q, k, grid, lds, stream);
-    case 2: return launch_tier<4, 2, 8>(q, k, grid, lds, stream);
-    case 3: return launch_tier<3, 8, 3>(q, k, grid, lds, stream);
-    case 4: return launch_tier<6, 4, 3>(q, k, grid, lds, stream);
+    case 0: return launch_tier<1, 8, 4>(q, n_back, k, grid, lds, stream);
+    case 1: return launch_tier<2, 4, 8>(q, n_back, k, grid, lds, stream);
+    case 2: return launch_tier<4, 2, 8>(q, n_back, k, grid, lds, stream);
+    case 3: return launch_tier<3, 8, 3>(q, n_back, k, grid, lds, stream);
+    case 4: return launch_tier<6, 4, 3>(q, n_back, k, grid, lds, stream);
     default: return hipErrorInvalidValue;
     }
+}
+}  // namespace
+
+hipError_t launch_crf_posterior(const BatchDesc &in, const ScoreDesc &y, const float *init, int64_t n_init, int64_t init_stride,
+                                int64_t band, float *post, double *logp, unsigned char *alpha, hipStream_t stream) {
+    CrfPostParams q[2] = {};
+    q[0].walk = q[1].walk = kWalkSub;
+    q[0].post = q[1].post = post;
+    return launch_crf_walks(q, 1, in, y, init, n_init, init_stride, band, logp, alpha, stream);
+}
+
+// forward (the cone one state wider below, for the deletions), the insertion walk, the deletion walk (one state wider
+// above): the stored forward rows are read by both walks
+hipError_t launch_crf_edits(const BatchDesc &in, const ScoreDesc &y, const float *init, int64_t n_init, int64_t init_stride,
+                            int64_t band, float *deletion, float *insertion, double *logp, unsigned char *alpha,
+                            hipStream_t stream) {
+    CrfPostParams q[3] = {};
+    q[0].walk = kWalkSub;
+    q[0].c.cone_lo = 1;
+    q[1].walk = kWalkIns;
+    q[2].walk = kWalkDel;
+    q[2].c.cone_hi = 1;
+    q[1].ins = q[2].ins = insertion;
+    q[1].del = q[2].del = deletion;
+    return launch_crf_walks(q, 2, in, y, init, n_init, init_stride, band, logp, alpha, stream);
 }
 
 }  // namespace fcd

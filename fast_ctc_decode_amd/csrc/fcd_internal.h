@@ -284,6 +284,12 @@ int crf_posterior_unsupported(int64_t T, int64_t S, int64_t N, int64_t stride, i
 size_t crf_posterior_row_bytes(int64_t T, int64_t S, int64_t N, int64_t stride, int64_t band);
 hipError_t launch_crf_posterior(const BatchDesc &in, const ScoreDesc &y, const float *init, int64_t n_init, int64_t init_stride,
                                 int64_t band, float *post, double *logp, unsigned char *alpha, hipStream_t stream);
+// CRF deletion and insertion likelihoods of the same labellings (crf_posterior.hip; fcd_crf_edits_* in include/fcd.h): the
+// same kernels and workspace (crf_posterior_row_bytes), and crf_posterior_unsupported's limits: every instantiation carries
+// the two walks.
+hipError_t launch_crf_edits(const BatchDesc &in, const ScoreDesc &y, const float *init, int64_t n_init, int64_t init_stride,
+                            int64_t band, float *deletion, float *insertion, double *logp, unsigned char *alpha,
+                            hipStream_t stream);
 
 hipError_t launch_logspace_probe(const float *a, const float *b, float *out_add, float *out_ln,
                                  int64_t n, int mode, hipStream_t stream);

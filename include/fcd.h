@@ -630,6 +630,59 @@ int fcd_crf_posterior_dev(fcd_handle *h, const fcd_batch *in, const float *init,
 int fcd_crf_posterior_host(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init, int64_t init_stride,
                            const fcd_labellings *y, int64_t band, const fcd_posterior *out);
 
+/* ---- CRF deletion and insertion likelihoods of given labellings (csrc/crf_posterior.hip) ----
+ * NOT a reference function.  What fcd_crf_posterior_* leaves out: with its substitutions, the full edit-distance-1
+ * neighbourhood of a labelling under a CRF model, from one forward and two backward walks instead of L + (L+1)(N-1)
+ * rescorings.  Everything is as fcd_crf_posterior_* has it: batch, init, nb = N - 1, S = nb^m or S = 1 (walked as m = 1),
+ * y's trajectory sigma_k, the reading rule P(u, sigma, j) = p[u][sigma][j] (0 for sigma outside 0 .. S-1), alpha and beta.
+ * A variant labelling walks ITS OWN trajectory: the rule sigma'_{k+1} = (sigma'_k nb) mod S + (y'_k - 1) from the same
+ * sigma_0.  It differs from y's only while the edit is inside the m-label history; the closed forms below are what the
+ * kernel reads, the rule is the definition (tests/crf_edits_reference.py pins both to the enumeration of every alignment).
+ * Deletion of label k, 0 <= k < L (y' = y without y_k).  y' has y's states 0 .. k; its state k emits y_{k+1} from row
+ * sigma_k; its state k+1+j lives in y's slot s = k+2+j, j = 0 .. m-2, with
+ *   sigma' = (sigma_k nb^(j+1)) mod S + (sigma_s mod nb^(j+1)),   and rejoins y's trajectory at slot k+m+1:
+ *   W_s[j]_{u-1} = P(u,sigma',0) W_s[j]_u + P(u,sigma',y_s) W_{s+1}[j+1]_u,   W_{s+1}[m-1] = beta[s+1];  last row: [s = L]
+ *   D[k]   = sum_u alpha_{u-1}[k] * P(u,sigma_k,y_{k+1}) * X_u[k+2]   for k < L-1,   X = W[0] (m = 1: X = beta)
+ *   D[L-1] = alpha_{T_r-1}[L-1]
+ * Insertion of label c before y_g, 0 <= g <= L (g = L: after the last label).  y' state g emits c from row sigma_g; its
+ * state g+1+j lives in y's slot s = g+j, j = 0 .. m-1, with
+ *   sigma' = (sigma_g nb^(j+1)) mod S + (c-1) nb^j + (sigma_s mod nb^j),   and rejoins at slot g+m:
+ *   U_s[j][c]_{u-1} = P(u,sigma',0) U_s[j][c]_u + P(u,sigma',y_s) U_{s+1}[j+1][c]_u,   U_{s+1}[m][c] = beta[s+1];
+ *   last row: [s = L];  a chain that would pass state L ends there
+ *   I[g][c] = sum_u alpha_{u-1}[g] * P(u,sigma_g,c) * U_g[0][c]_u            ("row -1" is state 0 holding 1)
+ * band = 0: D[k] = exp(crf_score(y without label k)) and I[g][c] = exp(crf_score(y with c at g)), exactly.  y's own cone
+ * (k <= t + 1, k >= L - (T_r - 1 - t)) is one state too narrow for the shortened labelling on both sides: the forward pass of
+ * this call keeps alpha for the state below it, the deletion walk keeps beta and W for the state above it.
+ * band = W: the band's own bounds (k(t) +- W from y's path) stay y's, the cone's margins lie inside them, everything lives in
+ * y's slots, and a slot outside its row's window counts 0.  The carrying state of D[k] is k + 1 (its accumulator rides there),
+ * of I[g][.] it is g: the sums run over the rows u at which the carrying state is inside the window of row u - 1 (deletion:
+ * the deletion walk's) and the value read -- X_u[k+2], U_g[0]_u -- inside that of row u.  A lower bound that rises with W and
+ * equals the exact value once the window holds the lattice (fcd_ctc_edits_*'s rule).
+ * Outputs: fcd_edits, float32 log-ratios against ln P(y | x); layout, never-written entries and _host's zeros as
+ * fcd_ctc_edits_*.  logp: fcd_crf_score_*'s value within its tolerance -- the extra state below the cone can move a row's
+ * shared exponent and with it the last bit of the float64 logarithm.
+ * Rows without a value: logp follows fcd_crf_score_*; whenever P(y | x) is not a positive finite number every entry for
+ * k < min(len, stride) and g <= min(len, stride) is NaN.  A variant of probability 0: -inf (every insertion at T_r = L).  A
+ * NaN posterior that only a variant reads: NaN in that variant's entry alone, logp as it is.  L = 0 writes gap 0
+ * (I[0][c] = P([c] | x)) and no deletion.
+ * Numerics: fcd_crf_posterior_*'s -- f32 probability space, exact power-of-two scales with integer exponents (one per forward
+ * row; one per backward row shared by beta and every chain value; one per slot for its accumulators, counted from
+ * floor(log2 P(y | x)), rising with the largest term), every term non-negative, one rounding per product and per sum, no
+ * fused multiply-add; the log-ratio is formed in float64 from the accumulator's mantissa (its logarithm in f32), its exponent
+ * and logp.  A cell below 2^-160 of its row's maximum may be dropped: an entry below -100 ln 2 may come back as -inf.
+ * Error bound, by roundings along the longest chain as fcd_crf_posterior_* counts them: alpha_{u-1} carries 3 u, a chain
+ * value 3 (T_r - 1 - u), a term two products, the sum over the rows at most T_r: a numerator is within (4 T_r - 1) 2^-24,
+ * relative; P(y | x) within 3 T_r 2^-24; the f32 logarithm and the store add 2^-23 |value|:
+ *   |error| <= 7 T_r 2^-24 + 2^-23 |value| nats.
+ * FCD_E_INVALID: fcd_crf_score_*'s cases, and a null out, out->deletion or out->insertion.
+ * Limits (FCD_E_UNSUPPORTED), workspace, grouping, stream order: fcd_crf_posterior_*'s, tier for tier -- every instantiation
+ * carries the two walks within its 256 registers; the messages name crf_edits and the band that fits.  The launches per
+ * group: forward, insertion walk, deletion walk; both walks read the stored forward rows. */
+int fcd_crf_edits_dev(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init, int64_t init_stride,
+                      const fcd_labellings *y, int64_t band, const fcd_edits *out);
+int fcd_crf_edits_host(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init, int64_t init_stride,
+                       const fcd_labellings *y, int64_t band, const fcd_edits *out);
+
 /* ---- search::crf_greedy_search (src/search.rs:385-423) ---- */
 int fcd_crf_greedy_search_dev(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init,
                               int64_t init_stride, const fcd_result *out);
