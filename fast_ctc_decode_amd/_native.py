@@ -56,6 +56,7 @@ SYMBOLS = [
     "fcd_ctc_edits_dev", "fcd_ctc_edits_host",
     "fcd_crf_score_dev", "fcd_crf_score_host", "fcd_crf_align_dev", "fcd_crf_align_host",
     "fcd_crf_posterior_dev", "fcd_crf_posterior_host", "fcd_crf_edits_dev", "fcd_crf_edits_host",
+    "fcd_crf_viterbi_search_dev", "fcd_crf_viterbi_search_host",
 ]
 JOB_PATH, JOB_QUAL, JOB_AMBIGUOUS, JOB_DONE = 1, 2, 4, 1
 
@@ -266,6 +267,7 @@ def bind(lib):
         getattr(lib, "fcd_crf_align_" + sfx).argtypes = [P, BP, P, i64, i64, C.POINTER(Labellings), i64, C.POINTER(Alignment)]
         getattr(lib, "fcd_crf_posterior_" + sfx).argtypes = [P, BP, P, i64, i64, C.POINTER(Labellings), i64, C.POINTER(Posterior)]
         getattr(lib, "fcd_crf_edits_" + sfx).argtypes = [P, BP, P, i64, i64, C.POINTER(Labellings), i64, C.POINTER(Edits)]
+        getattr(lib, "fcd_crf_viterbi_search_" + sfx).argtypes = [P, BP, P, i64, i64, RP, P]
     return lib
 
 

@@ -378,6 +378,79 @@ def crf_greedy_search_batch(network_outputs, init_states, alphabet, qstring=Fals
     return res
 
 
+def crf_viterbi_search(network_output, init_state, alphabet, qstring=False, qscale=1.0, qbias=0.0):
+    """The single most probable path through the CRF model's states over ALL labellings (include/fcd.h,
+    fcd_crf_viterbi_search_*; not a reference function) -> (seq, path), crf_greedy_search's arguments, validation and
+    messages.  qstring=True appends the phred characters of the emissions' posteriors, as crf_greedy_search does."""
+    x = _as_f32(network_output, 3, "network_output")
+    init = _as_f32(init_state, 1, "init_state")
+    alpha = _seq_to_vec(alphabet)
+    _check_greedy_alphabet(len(alpha), x.shape[2])
+    if x.size == 0 or init.size == 0:
+        raise RuntimeError("network_output/init_state is empty (the reference asserts and aborts here)")
+    x = _dense(x)
+    init = np.ascontiguousarray(init)
+    out = _HostOut(1, x.shape[0], want_qual=bool(qstring))
+    b = _host_batch(x[None], True)
+    h = nat.default_handle()
+    h.check(h.lib.fcd_crf_viterbi_search_host(h.ptr, C.byref(b), init.ctypes.data, init.shape[0], init.shape[0],
+                                              C.byref(out.res), None))
+    _raise_status(int(out.status[0]))
+    n = int(out.out_len[0])
+    seq = "".join(alpha[l] for l in out.labels[0, :n])
+    if qstring:
+        seq += _qual_chars(out.qual[0, :n], qscale, qbias)
+    return seq, [int(p) for p in out.path[0, :n]]
+
+
+def crf_viterbi_search_batch_raw(network_outputs, init_states, lengths=None, qual=False, input_dtype=None):
+    """(B,T,S,N) posteriors (numpy float32 / float16 / bfloat16 bits, or a torch ROCm tensor) + (B,n_init) initial state
+    scores -> the CRF searches' batch result (so .crf_score / .crf_align / .crf_posterior / .crf_edits work on it) of the
+    Viterbi search per read, with .logp: (B,) float64, ln of the path's probability.  Device inputs are enqueued on
+    torch's current stream and nothing waits."""
+    if _is_torch_cuda(network_outputs):
+        import torch
+        init = torch.as_tensor(init_states, dtype=torch.float32, device=network_outputs.device).contiguous()
+        if init.ndim != 2 or init.shape[0] != network_outputs.shape[0]:
+            raise ValueError("init_states must have shape (n_reads, n_init)")
+        logp = torch.empty((network_outputs.shape[0],), dtype=torch.float64, device=network_outputs.device)
+        r = _torch_call("fcd_crf_viterbi_search_dev", network_outputs, True, lengths,
+                        (C.c_void_p(init.data_ptr()), int(init.shape[1]), int(init.shape[1])), want_qual=qual,
+                        tail_args=(C.c_void_p(logp.data_ptr()),))
+        res = _CrfViterbiResult(r.labels, r.path, r.out_len, r.status, r.qual, logp=logp)
+        res._handle = r._handle
+        res._keep = r._keep + (init,)
+        res._handle.hold_in_flight(init, logp)
+        return res
+    x = _stack_host(network_outputs, 4)
+    init = np.ascontiguousarray(np.asarray(init_states, np.float32))
+    B, T, S, N = x.shape
+    if init.ndim != 2 or init.shape[0] != B:
+        raise ValueError("init_states must have shape (n_reads, n_init)")
+    h = nat.default_handle()
+    out = _HostOut(B, T, want_qual=qual)
+    logp = np.zeros(B, np.float64)
+    b = _host_batch(x, True, _np_lengths(lengths, B), input_dtype)
+    h.check(h.lib.fcd_crf_viterbi_search_host(h.ptr, C.byref(b), init.ctypes.data, init.shape[1], init.shape[1],
+                                              C.byref(out.res), logp.ctypes.data))
+    return _CrfViterbiResult(out.labels, out.path, out.out_len, out.status, out.qual, logp=logp)
+
+
+def crf_viterbi_search_batch(network_outputs, init_states, alphabet, qstring=False, qscale=1.0, qbias=0.0,
+                             lengths=None, paths="list"):
+    """Batched crf_viterbi_search: element i equals crf_viterbi_search(network_outputs[i], init_states[i], ...)."""
+    alpha = _seq_to_vec(alphabet)
+    x = network_outputs if _device_tensor(network_outputs) is not None else _stack_host(network_outputs, 4)
+    _check_greedy_alphabet(len(alpha), x.shape[-1])
+    r = crf_viterbi_search_batch_raw(x, init_states, lengths, qual=bool(qstring)).cpu()
+    res = BatchResult.sequences(r, alpha, paths=paths if paths is not None else "array")
+    if qstring:
+        res = [(s + _qual_chars(r.qual[i, :len(p)], qscale, qbias), p) for i, (s, p) in enumerate(res)]
+    if paths is None:
+        res = [(s, None) for s, _ in res]
+    return res
+
+
 _DEFAULT_LOGADD = [nat.LOGADD_LOGSUMEXP]
 
 
@@ -952,7 +1025,7 @@ def _torch_dtype_code(x):
 
 
 def _torch_call(fn_name, x, crf, lengths, extra_args, want_qual=False, want_path=True,
-                need_status=True, handle=None, want_amb=False):
+                need_status=True, handle=None, want_amb=False, tail_args=()):
     import torch
 
     # half-precision posteriors (what basecaller networks emit) are read as they are: the kernels convert in
@@ -986,7 +1059,7 @@ def _torch_call(fn_name, x, crf, lengths, extra_args, want_qual=False, want_path
                      status.data_ptr(), w, amb.data_ptr() if want_amb else None)
     h.set_stream(torch.cuda.current_stream(x.device).cuda_stream)
     fn = getattr(h.lib, fn_name)
-    h.check(fn(h.ptr, C.byref(b), *extra_args, C.byref(res)))
+    h.check(fn(h.ptr, C.byref(b), *extra_args, C.byref(res), *tail_args))
     r = BatchResult(labels, path, out_len, status, qual, amb)
     r._handle = h
     r._keep = (x, lengths)
@@ -2100,6 +2173,27 @@ class _CrfBatchResult(BatchResult):
                 labels = r.labels[i, :int(r.out_len[i])]
                 out[i] = ("".join(alpha[l] for l in labels[::-1])[::-1], item[1])
         return out
+
+
+class _CrfViterbiResult(_CrfBatchResult):
+    """crf_viterbi_search_batch_raw's result: a CRF batch result with logp, (n_reads,) float64 -- ln of the probability of
+    the best state path (NaN for a read that failed)."""
+
+    def __init__(self, labels, path, out_len, status, qual=None, ambiguous=None, logp=None):
+        _CrfBatchResult.__init__(self, labels, path, out_len, status, qual, ambiguous)
+        self.logp = logp
+
+    def sequences(self, alphabet, raise_on_error=True, paths="list"):
+        """-> list of (str, path) per read: crf_greedy_search's strings (labels joined in order), which is what
+        crf_viterbi_search and crf_viterbi_search_batch return -- not crf_beam_search_batch's handling of multi-character
+        labels, which the other CRF results follow."""
+        return BatchResult.sequences(self, alphabet, raise_on_error, paths)
+
+    def cpu(self):
+        r = BatchResult.cpu(self)  # (joins the handle's internal streams first)
+        lp = self.logp
+        return _CrfViterbiResult(r.labels, r.path, r.out_len, r.status, r.qual, r.ambiguous,
+                                 lp if lp is None or isinstance(lp, np.ndarray) else lp.cpu().numpy())
 
 
 class BeamSearchSession:

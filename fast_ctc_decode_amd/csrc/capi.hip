@@ -1129,6 +1129,112 @@ int fcd_crf_greedy_search_dev(fcd_handle *h, const fcd_batch *in, const float *i
     return sc.finish();
 }
 
+// ---- the Viterbi search under a CRF model (viterbi.hip): the best state path over all labellings ----
+namespace {
+int crf_viterbi_check(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init, int64_t init_stride,
+                      const fcd_result *out) {
+    int rc = check_batch(h, in, true);
+    if (rc) return rc;
+    rc = check_result(h, in, out, true);
+    if (rc) return rc;
+    if (!init || n_init < 1) return fail(h, FCD_E_INVALID, "init_state missing");
+    if (init_stride < 0) return fail(h, FCD_E_INVALID, "negative stride");
+    switch (crf_viterbi_unsupported(in->S, in->N)) {
+    case 1: return fail(h, FCD_E_UNSUPPORTED, "crf_viterbi_search: N must be in 2 .. 9");
+    case 2: return fail(h, FCD_E_UNSUPPORTED, "crf_viterbi_search: S must be a multiple of N - 1 (the states that reach a state are "
+                                              "s div (N - 1) + i S / (N - 1))");
+    case 3: return fail(h, FCD_E_UNSUPPORTED, "crf_viterbi_search: S must be below 2^24");
+    case 4: return fail(h, FCD_E_UNSUPPORTED, "crf_viterbi_search: N S 4 bytes of states and candidates do not fit the 160 KiB of LDS");
+    default: break;
+    }
+    return FCD_OK;
+}
+
+// Whole reads per launch, as many as the workspace cap holds back-pointers for (at least one), every launch in the same
+// memory, one after the other on the handle's stream (lattice_grouped's rule; the cap is fcd_crf_align_*'s).
+int crf_viterbi_run(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init, int64_t init_stride,
+                    const fcd_result *out, double *logp) {
+    const int64_t read_bytes = (int64_t)crf_viterbi_read_bytes(in->T, in->S);
+    const int64_t cap = h->align_ws_cap > 0 ? h->align_ws_cap : std::min<int64_t>(4ll << 30, workspace_budget(h));
+    const int64_t group = std::max<int64_t>(1, std::min<int64_t>(in->n_reads, cap / read_bytes));
+    CallScope sc(h);
+    sc.add(to_desc(out), in->n_reads);
+    sc.add(logp, (size_t)in->n_reads * 8);
+    int rc = sc.begin(false, true);  // (exclusive: the workspace from its start, behind every overlapping call in flight)
+    if (rc) return rc;
+    char *ws = nullptr;
+    rc = sc.arena((size_t)group * (size_t)read_bytes, &ws);
+    if (rc) return rc;
+    const int64_t esz = in->dtype == FCD_DTYPE_F32 ? 4 : 2;
+    sc.time();
+    for (int64_t r0 = 0; r0 < in->n_reads; r0 += group) {
+        BatchDesc d = to_desc(in, true);
+        d.post = reinterpret_cast<const float *>(reinterpret_cast<const char *>(in->post) + r0 * in->stride_read * esz);
+        d.lengths = in->lengths ? in->lengths + r0 : nullptr;
+        d.n_reads = std::min(group, in->n_reads - r0);
+        ResultDesc o = to_desc(out);
+        o.labels = out->labels + r0 * out->out_stride;
+        o.path = out->path ? out->path + r0 * out->out_stride : nullptr;
+        o.qual = out->qual ? out->qual + r0 * out->out_stride : nullptr;
+        o.out_len = out->out_len + r0;
+        o.status = out->status + r0;
+        FCD_HIP(h, launch_crf_viterbi(d, init + r0 * init_stride, n_init, init_stride, o, logp ? logp + r0 : nullptr,
+                                      reinterpret_cast<unsigned char *>(ws), sc.stream));
+    }
+    return sc.finish();
+}
+}  // namespace
+
+int fcd_crf_viterbi_search_dev(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init, int64_t init_stride,
+                               const fcd_result *out, double *logp) {
+    if (!h) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> g(h->mu);
+    int rc = crf_viterbi_check(h, in, init, n_init, init_stride, out);
+    if (rc) return rc;
+    if (in->n_reads == 0) return FCD_OK;
+    FCD_DEVICE(h);
+    return crf_viterbi_run(h, in, init, n_init, init_stride, out, logp);
+}
+
+// host arrays: staged in the order post, init, lengths, the outputs; the device call runs on the handle's stream
+int fcd_crf_viterbi_search_host(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init, int64_t init_stride,
+                                const fcd_result *out, double *logp) {
+    if (!h) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> whole_call(h->mu);  // staging .. copy-back, see run_host
+    int rc = crf_viterbi_check(h, in, init, n_init, init_stride, out);
+    if (rc) return rc;
+    if (in->n_reads == 0) return FCD_OK;
+    if (in->stride_read < 0 || in->stride_t < 0 || in->stride_s < 0 || in->stride_n < 0)
+        return fail(h, FCD_E_UNSUPPORTED, "negative strides: pass a contiguous copy");
+    FCD_DEVICE(h);
+    const size_t B = (size_t)in->n_reads, cells = B * (size_t)out->out_stride;
+    Staging st(h);
+    const int i_post = st.in(in->post, (size_t)span_elems(in, true) * (in->dtype == FCD_DTYPE_F32 ? 4 : 2));
+    const int i_init = st.in(init, (size_t)((in->n_reads - 1) * init_stride + n_init) * 4);
+    const int i_len = st.in(in->lengths, B * 8);
+    const int i_lab = st.out(out->labels, cells);
+    const int i_path = st.out(out->path, cells * 4);
+    const int i_qual = st.out(out->qual, cells * 4);
+    const int i_olen = st.out(out->out_len, B * 4);
+    const int i_stat = st.out(out->status, B * 4);
+    const int i_logp = st.out(logp, B * 8);
+    rc = st.commit();
+    if (rc) return rc;
+    fcd_batch din = *in;
+    din.post = st.at<char>(i_post);
+    din.lengths = st.at<int64_t>(i_len);
+    fcd_result dout = *out;
+    dout.labels = st.at<uint8_t>(i_lab);
+    dout.path = st.at<uint32_t>(i_path);
+    dout.qual = st.at<float>(i_qual);
+    dout.out_len = st.at<uint32_t>(i_olen);
+    dout.status = st.at<int32_t>(i_stat);
+    dout.ambiguous = nullptr;
+    rc = crf_viterbi_run(h, &din, st.at<float>(i_init), n_init, init_stride, &dout, st.at<double>(i_logp));
+    if (rc) return rc;
+    return st.fetch();
+}
+
 namespace {
 struct CrfInit {
     const float *init1 = nullptr, *init2 = nullptr;

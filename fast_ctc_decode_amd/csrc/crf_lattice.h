@@ -205,13 +205,7 @@ struct CrfStep {
     int lo, hi;
 };
 
-__device__ __forceinline__ void crf_split(float v, float *m, int *e) {
-    int ex = 0;
-    float mm = v;
-    if (v - v == 0.0f) mm = frexpf(v, &ex);  // (finite; an infinity or a NaN stays what it is, exponent 0)
-    *m = mm;
-    *e = ex;
-}
+// (crf_split: device_utils.h, shared with the CRF Viterbi search of viterbi.hip)
 
 template <int K>
 __device__ __forceinline__ CrfStep<K> crf_load_step(const CrfParams &p, const CrfLds &lds, const CrfRow &rw, int t, int i,

@@ -12,8 +12,7 @@
 namespace fcd {
 namespace {
 
-constexpr int kTarget = 120;          // the row maximum is kept in [2^119, 2^120): three of them sum below 2^127
-constexpr int kNoExp = -(1 << 24);    // "exponent" of a cell that takes no part in the row maximum (0, inf, NaN)
+// (kTarget and kNoExp: device_utils.h)
 constexpr int kTileElems = 1024;      // posteriors staged per tile
 constexpr int kTileRows = 64;         // ... at most this many rows (one lane per row finds k(t))
 constexpr int kLdsCells = 20;         // LDS kernel: cells per work-item and step
@@ -159,24 +158,7 @@ __device__ __forceinline__ void window(const ScoreParams &p, const Lds &lds, con
     window_k(p, rw, t, p.band > 0 ? lds.krow[i] : 0, lo, hi);
 }
 
-__device__ __forceinline__ int finite_exp(float u) {  // exponent of a positive finite value, kNoExp for anything else
-    int e;
-    (void)frexpf(u, &e);
-    return (u > 0.0f && u - u == 0.0f) ? e : kNoExp;
-}
-
-__device__ __forceinline__ int wave_imax(int x) {
-    int t = x;
-#define FCD_DPP_IMAX(CTRL, RM) t = max(t, __builtin_amdgcn_update_dpp(t, t, CTRL, RM, 0xf, false));
-    FCD_DPP_IMAX(0x111, 0xf)  // row_shr:1
-    FCD_DPP_IMAX(0x112, 0xf)  // row_shr:2
-    FCD_DPP_IMAX(0x114, 0xf)  // row_shr:4
-    FCD_DPP_IMAX(0x118, 0xf)  // row_shr:8   -> lane 15 of every row holds the row's maximum
-    FCD_DPP_IMAX(0x142, 0xa)  // row_bcast:15 into rows 1 and 3
-    FCD_DPP_IMAX(0x143, 0xc)  // row_bcast:31 into rows 2 and 3 -> lane 63 holds the maximum
-#undef FCD_DPP_IMAX
-    return __builtin_amdgcn_readlane(t, 63);
-}
+// (finite_exp and wave_imax: device_utils.h, shared with the CRF Viterbi search of viterbi.hip)
 
 __device__ __forceinline__ float from_prev_lane(float x) {  // wave_ror:1 -- lane l receives lane (l - 1) & 63
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x13C, 0xf, 0xf, false));

@@ -217,4 +217,37 @@ __device__ __forceinline__ bool lane_in(uint64_t m, int lane) {
 #define FCD_STAMP(t64, dep) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t64), "+v"(dep) : : "memory")
 #endif
 
+// ---- f32 with an unbounded exponent: what the lattice walks (ctc_lattice.h, crf_lattice.h) and the CRF Viterbi search
+// (viterbi.hip) share.  A row's cells are f32 values times one power of two per row; the row's largest exponent is reduced
+// as an integer and every cell rescaled exactly.
+constexpr int kTarget = 120;          // the row maximum is kept in [2^119, 2^120): three of them sum below 2^127
+constexpr int kNoExp = -(1 << 24);    // "exponent" of a cell that takes no part in the row maximum (0, inf, NaN)
+
+__device__ __forceinline__ int finite_exp(float u) {  // exponent of a positive finite value, kNoExp for anything else
+    int e;
+    (void)frexpf(u, &e);
+    return (u > 0.0f && u - u == 0.0f) ? e : kNoExp;
+}
+
+__device__ __forceinline__ int wave_imax(int x) {
+    int t = x;
+#define FCD_DPP_IMAX(CTRL, RM) t = max(t, __builtin_amdgcn_update_dpp(t, t, CTRL, RM, 0xf, false));
+    FCD_DPP_IMAX(0x111, 0xf)  // row_shr:1
+    FCD_DPP_IMAX(0x112, 0xf)  // row_shr:2
+    FCD_DPP_IMAX(0x114, 0xf)  // row_shr:4
+    FCD_DPP_IMAX(0x118, 0xf)  // row_shr:8   -> lane 15 of every row holds the row's maximum
+    FCD_DPP_IMAX(0x142, 0xa)  // row_bcast:15 into rows 1 and 3
+    FCD_DPP_IMAX(0x143, 0xc)  // row_bcast:31 into rows 2 and 3 -> lane 63 holds the maximum
+#undef FCD_DPP_IMAX
+    return __builtin_amdgcn_readlane(t, 63);
+}
+
+__device__ __forceinline__ void crf_split(float v, float *m, int *e) {
+    int ex = 0;
+    float mm = v;
+    if (v - v == 0.0f) mm = frexpf(v, &ex);  // (finite; an infinity or a NaN stays what it is, exponent 0)
+    *m = mm;
+    *e = ex;
+}
+
 }  // namespace fcd

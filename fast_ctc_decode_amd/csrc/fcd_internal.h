@@ -145,6 +145,14 @@ hipError_t launch_viterbi(const BatchDesc &in, int collapse, const ResultDesc &o
 hipError_t launch_crf_greedy(const BatchDesc &in, const float *init, int64_t n_init,
                              int64_t init_stride, const ResultDesc &out, hipStream_t stream);
 
+// The Viterbi search under a CRF model (fcd_crf_viterbi_search_* in include/fcd.h; the walk lives in viterbi.hip, inside
+// crf_greedy_kernel).  crf_viterbi_unsupported: 0 supported, 1 N outside 2 .. 9, 2 S no multiple of N - 1, 3 S beyond the
+// state word, 4 the state and candidate arrays beyond the LDS of a CU.  bp: crf_viterbi_read_bytes(T, S) bytes per read.
+int crf_viterbi_unsupported(int64_t S, int64_t N);
+size_t crf_viterbi_read_bytes(int64_t T, int64_t S);
+hipError_t launch_crf_viterbi(const BatchDesc &in, const float *init, int64_t n_init, int64_t init_stride,
+                              const ResultDesc &out, double *logp, unsigned char *bp, hipStream_t stream);
+
 // duplex::beam_search (src/duplex.rs:443-650) launch arguments; all pointers are device memory.
 struct DuplexArgs {
     const float *ln1, *ln2;  // log-space posteriors [pair][Tcap][N]

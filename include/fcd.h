@@ -689,6 +689,43 @@ int fcd_crf_greedy_search_dev(fcd_handle *h, const fcd_batch *in, const float *i
 int fcd_crf_greedy_search_host(fcd_handle *h, const fcd_batch *in, const float *init,
                                int64_t n_init, int64_t init_stride, const fcd_result *out);
 
+/* ---- the Viterbi search under a CRF model: the single most probable path through the model's states ----
+ * NOT a reference function.  The exact, unpruned decode over ALL labellings: fcd_crf_greedy_search_* follows the locally
+ * best label (a lower bound), fcd_crf_beam_search_* is a pruned sum over alignments, fcd_crf_align_* finds the best
+ * alignment of ONE labelling; this finds the best alignment over all of them -- no labelling's best alignment beats it.
+ * Batch and reading rule: (n_reads, T, S, N) posteriors, init rows and nb = N - 1 as fcd_crf_greedy_search_* /
+ * fcd_crf_align_* read them: f32 / f16 / bf16 converted exactly, any strides (time-major views included), in->lengths.
+ * Start: sigma_0 = the first maximum of the read's init row (the init probabilities do not enter, as in
+ * fcd_crf_score_*); v_{-1}[sigma_0] = 1, every other state 0.
+ * Step, for every state s':   v_t[s'] = max( v_{t-1}[s'] p_t[s'][0] ,  max_i v_{t-1}[s_i] p_t[s_i][j+1] )
+ *   j = s' mod nb,  q = S / nb,  s_i = s' div nb + i q,  i = 0 .. nb-1:  exactly the states with (s_i nb) mod S + j = s',
+ *   the searches' transition (src/search.rs:97,414).  The formula needs S mod nb = 0 (every S = nb^m, and other multiples).
+ * Ties: the stay candidate is kept unless an advance is strictly greater; among advances the lowest i unless a later one is
+ * strictly greater; the end state is the first maximum of v_{T_r-1}.
+ * Result, by traceback from the end state: path = the emitting rows in order, labels = their labels j + 1, qual[k] = the
+ * posterior of that emission p_t[s_i][j+1] (what fcd_crf_greedy_search_* feeds to phred), logp[read] = ln v_{T_r-1}[end],
+ * float64.  out->qual, out->path and logp are nullable; out->status is required; out->ambiguous is not written.  Entries
+ * of labels / path / qual at and beyond out_len are unspecified (the traceback parks emissions there).
+ * Edge cases: a NaN in the init row (or an init row no state follows from: sigma_0 >= S with T_r > 0): FCD_ST_BAD_STATE,
+ * out_len 0, logp NaN, as greedy.  T_r = 0: out_len 0, logp 0.0, FCD_ST_OK.  A NaN anywhere in rows 0 .. T_r-1 of the read:
+ * FCD_ST_INCOMPARABLE, out_len 0, logp NaN (every value of a read enters a live cell).  Infinite or negative posteriors:
+ * the call terminates and writes some result, nothing more.
+ * Arithmetic: fcd_crf_align_*'s -- f32 with an unbounded exponent (mantissa / exponent split, exact power-of-two rescaling
+ * per row), each candidate ONE product with one rounding, no fused multiply-add, ln(m) + E ln 2 in float64; a cell below
+ * 2^-160 of its row's maximum may be dropped.  Executable specification: tests/crf_viterbi_reference.py.
+ * Limits (FCD_E_UNSUPPORTED; the message says which): 2 <= N <= 9; S a multiple of N - 1; S < 2^24; N S 4 bytes of LDS
+ * per read (the states and their N - 1 advance candidates) within the 160 KiB of a CU (S = 4096 at N = 5: 80 KiB).
+ * Workspace: one back-pointer byte per state and row, T S bytes per read (rounded up to 256), from the handle's workspace;
+ * whole reads per launch, as many as min(4 GiB, the handle's workspace budget) holds, the launches one after the other in
+ * the same memory (fcd_debug_set_align_workspace_cap sets the cap for tests).
+ * _dev is enqueue-only on the handle's stream (never on fcd_set_overlap's internal streams) and ordered behind every
+ * overlapping call in flight; _host stages host arrays and returns when the results are in them.
+ * FCD_E_INVALID: null in / out / labels / out_len / status, out_stride < T, null init or n_init < 1, negative init_stride. */
+int fcd_crf_viterbi_search_dev(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init, int64_t init_stride,
+                               const fcd_result *out, double *logp);
+int fcd_crf_viterbi_search_host(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init, int64_t init_stride,
+                                const fcd_result *out, double *logp);
+
 /* ---- duplex::beam_search (src/duplex.rs:443-650) ----
  * (Two kernels serve the duplex searches since round 6, with identical results: the slot-resident one --
  * csrc/duplex_slots.hip -- wherever beam_size * N <= 64 and the live nodes' windows fit the LDS, the any-shape one --
