@@ -160,18 +160,21 @@
             // j + kAhead behind the count of block j - 1 (left alone, the scheduler hoists every load to the top again)
             int r0, r1 = 0, r2 = 0, r3 = 0;
             static_assert(!STREAM || NC >= 4, "at least one block of four comparands");
+            // HL: the count as a sum of clamped f32 differences (device_utils.h, FCD_RANKF4): own word scaled once
+            const float fown = (R32 && HL) ? fcd_rankf_own(kp) : 0.0f;
+            float facc;
 #pragma unroll
             for (int j = 0; j < NBLK; ++j) {
                 __builtin_amdgcn_sched_barrier(0);
                 if (j + kAhead < NBLK) load_blk(j + kAhead);
-                if (R32 && HL) {  // the same count in ONE accumulator: the sum of four chains is three instructions more
+                if (R32 && HL) {  // the same count in ONE accumulator, in f32: v_fma_f32 + v_add_f32 per comparand
                     if (j == 0) {
-                        FCD_RANK4_32_ONE_FIRST(kp, kw[0], kw[1], kw[2], kw[3], r0);
+                        FCD_RANKF4_FIRST(fown, kw[0], kw[1], kw[2], kw[3], facc);
                     } else if (4 * j + 4 <= NC) {
-                        FCD_RANK4_32_ONE(kp, kw[4 * j], kw[4 * j + 1], kw[4 * j + 2], kw[4 * j + 3], r0);
+                        FCD_RANKF4(fown, kw[4 * j], kw[4 * j + 1], kw[4 * j + 2], kw[4 * j + 3], facc);
                     } else {
 #pragma unroll
-                        for (int u = 4 * j; u < NC; ++u) r0 += (kw[u] > kp) ? 1 : 0;
+                        for (int u = 4 * j; u < NC; ++u) FCD_RANKF1(fown, kw[u], facc);
                     }
                 } else if (R32) {  // r32 = #(probability word > own): candidates of equal probability share it
                     if (j == 0) {
@@ -192,7 +195,7 @@
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
-            rank = (R32 && HL) ? r0 : (r0 + r1) + (r2 + r3);
+            rank = (R32 && HL) ? (int)facc : (r0 + r1) + (r2 + r3);  // (facc: a sum of 25 values in [0, 1])
         } else {
             // four independent compare-and-count chains (device_utils.h)
             int r0, r1, r2, r3;
@@ -421,7 +424,10 @@
         // the second pass does not is the harmless one described above, and one it skipped the second pass makes.)  The
         // PDQ hint needs no first-pass test at all: two equal words among the first beam_size + 1 ranks ARE a clash, so it is
         // read off the settled table, where no hole can raise or hide it.
-        const uint64_t m_clash = R32 ? ballot(clash) : 0ull;
+        // HL: a fourth -- a candidate whose probability word is outside the range on which the f32 count is exact (device_utils.h,
+        // fcd_rankf_outside: below 2^-76 and not 0, above 2^27, negative, a NaN).  The same recount: it is valid for every
+        // input and replaces whatever the first pass counted.
+        const uint64_t m_clash = R32 ? (HL ? (ballot(clash) | (ballot(fcd_rankf_outside(kp)) & m_valid)) : ballot(clash)) : 0ull;
         const uint64_t m_hint = (PDQ && !R32) ? (ballot(tie0 == tie1) & ballot(tie_lim < n_valid)) : 0ull;
         if (__builtin_expect((m_k2 | m_hint | m_clash) != 0ull, 0)) {
             uint64_t m_tied = m_hint;

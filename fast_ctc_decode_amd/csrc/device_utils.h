@@ -182,6 +182,74 @@ __device__ __forceinline__ int32_t load_i32_l2(const int32_t *p) {
     } while (0)
 #endif
 
+// The same count as FCD_RANK4_32_ONE in the cheapest instruction class (tools/microbench/issue_cost.hip,
+// profiles/r12a_issue_cost.txt: at six wavefronts per SIMD a compare into a scalar register pair and the add that reads it
+// as its carry hold the SIMD for 4.9 cycles each, v_fma_f32 and v_add_f32 for 2.6 - 2.8).  The word of a non-negative probability
+// p is bits(p) | 0x80000000: read as a float it is -p, an empty slot's word 0 is +0.0.  With A = as_float(own word) * 2^100,
+// t = clamp(fma(as_float(w), -2^100, A)) = clamp((p_w - p_own) * 2^100) is exactly 1 where w > own and exactly 0 elsewhere
+// WHILE every candidate word of the half is that of +0 or of a finite p in [2^-76, 2^27]: the smallest gap there is an ulp of 2^-76,
+// 2^-99, so a positive difference scales to >= 2 and nothing overflows, is subnormal or a NaN; an empty slot gives A <= 0.
+// The sum of the 25 t's is then the rank, an integer below 2^24.  fcd_rankf_outside() is the guard: a lane whose own word
+// leaves that range sends the step to the exact recount (beam_wave_step.inc, m_clash).  Outside it t is still in [0, 1]
+// (the clamp takes a NaN to 0), so the rank of a guarded step's first pass stays within the survivor table.  A candidate
+// of probability exactly 0 (word 0x80000000, -0.0: it differs from every positive p by at least 2^-76) is inside -- a slot
+// whose label probability is 0 and whose blank falls under the threshold leaves one, on ordinary
+// rows too.  (A lane without a candidate holds word 0 and is taken out of the vote by the mask of valid candidates.)
+constexpr uint32_t kRankfLo = 0x80000000u | (uint32_t)(127 - 76) << 23;  // word of 2^-76
+constexpr uint32_t kRankfHi = 0x80000000u | (uint32_t)(127 + 27) << 23;  // word of 2^27
+__device__ __forceinline__ float fcd_rankf_own(uint32_t word) { return __uint_as_float(word) * 0x1p100f; }
+__device__ __forceinline__ bool fcd_rankf_outside(uint32_t word) {
+    return word - kRankfLo > kRankfHi - kRankfLo && word != 0x80000000u;
+}
+#ifdef FCD_HIPEMU  // (lockstep emulation, tests/hipemu: plain C++)
+static inline float fcd_rankf_t(float a, uint32_t w) {
+    const float t = fmaf(__uint_as_float(w), -0x1p100f, a);
+    return t > 0.0f ? (t < 1.0f ? t : 1.0f) : 0.0f;  // v_fma_f32 ... clamp: [0, 1], a NaN -> 0
+}
+#define FCD_RANKF4(a, wa, wb, wc, wd, acc) \
+    do { (acc) += fcd_rankf_t(a, wa); (acc) += fcd_rankf_t(a, wb); (acc) += fcd_rankf_t(a, wc); (acc) += fcd_rankf_t(a, wd); } while (0)
+#define FCD_RANKF4_FIRST(a, wa, wb, wc, wd, acc) \
+    do { (acc) = fcd_rankf_t(a, wa) + fcd_rankf_t(a, wb); (acc) += fcd_rankf_t(a, wc); (acc) += fcd_rankf_t(a, wd); } while (0)
+#define FCD_RANKF1(a, w, acc) do { (acc) += fcd_rankf_t(a, w); } while (0)
+#else
+#define FCD_RANKF4(a, wa, wb, wc, wd, acc)                                                     \
+    do {                                                                                       \
+        float t0__, t1__, t2__, t3__;                                                          \
+        asm("v_fma_f32 %1, %6, %10, %5 clamp\n\t"                                              \
+            "v_fma_f32 %2, %7, %10, %5 clamp\n\t"                                              \
+            "v_fma_f32 %3, %8, %10, %5 clamp\n\t"                                              \
+            "v_fma_f32 %4, %9, %10, %5 clamp\n\t"                                              \
+            "v_add_f32 %0, %0, %1\n\t"                                                         \
+            "v_add_f32 %0, %0, %2\n\t"                                                         \
+            "v_add_f32 %0, %0, %3\n\t"                                                         \
+            "v_add_f32 %0, %0, %4"                                                             \
+            : "+v"(acc), "=&v"(t0__), "=&v"(t1__), "=&v"(t2__), "=&v"(t3__)                    \
+            : "v"(a), "v"(wa), "v"(wb), "v"(wc), "v"(wd), "s"(-0x1p100f));                     \
+    } while (0)
+// (the first block: the accumulator STARTS as the sum of two of its four -- one add fewer, nothing to clear)
+#define FCD_RANKF4_FIRST(a, wa, wb, wc, wd, acc)                                               \
+    do {                                                                                       \
+        float t0__, t1__, t2__, t3__;                                                          \
+        asm("v_fma_f32 %1, %6, %10, %5 clamp\n\t"                                              \
+            "v_fma_f32 %2, %7, %10, %5 clamp\n\t"                                              \
+            "v_fma_f32 %3, %8, %10, %5 clamp\n\t"                                              \
+            "v_fma_f32 %4, %9, %10, %5 clamp\n\t"                                              \
+            "v_add_f32 %0, %1, %2\n\t"                                                         \
+            "v_add_f32 %0, %0, %3\n\t"                                                         \
+            "v_add_f32 %0, %0, %4"                                                             \
+            : "=&v"(acc), "=&v"(t0__), "=&v"(t1__), "=&v"(t2__), "=&v"(t3__)                   \
+            : "v"(a), "v"(wa), "v"(wb), "v"(wc), "v"(wd), "s"(-0x1p100f));                     \
+    } while (0)
+#define FCD_RANKF1(a, w, acc)                                                                  \
+    do {                                                                                       \
+        float t0__;                                                                            \
+        asm("v_fma_f32 %1, %3, %4, %2 clamp\n\t"                                               \
+            "v_add_f32 %0, %0, %1"                                                             \
+            : "+v"(acc), "=&v"(t0__)                                                           \
+            : "v"(a), "v"(w), "s"(-0x1p100f));                                                 \
+    } while (0)
+#endif
+
 // Set bits of a half's word of a wave-wide vote below this lane's place in its half, counted onto `base`: the lower half
 // counts in the low word (v_mbcnt_lo), the upper half in the high word (v_mbcnt_hi adds nothing for a lane below 32).
 __device__ __forceinline__ int half_prefix_count(uint64_t m, int lane, int base) {
