@@ -51,7 +51,7 @@ SYMBOLS = [
     "fcd_beam_session_result_dev", "fcd_beam_session_result_host", "fcd_beam_session_restart", "fcd_beam_session_steps",
     "fcd_beam_session_bytes", "fcd_beam_session_destroy",
     "fcd_ctc_score_dev", "fcd_ctc_score_host",
-    "fcd_ctc_align_dev", "fcd_ctc_align_host", "fcd_debug_set_align_workspace_cap",
+    "fcd_ctc_align_dev", "fcd_ctc_align_host", "fcd_debug_set_align_workspace_cap", "fcd_debug_workspace_bytes",
     "fcd_ctc_posterior_dev", "fcd_ctc_posterior_host",
     "fcd_ctc_edits_dev", "fcd_ctc_edits_host",
     "fcd_crf_score_dev", "fcd_crf_score_host", "fcd_crf_align_dev", "fcd_crf_align_host",
@@ -262,6 +262,8 @@ def bind(lib):
         getattr(lib, "fcd_ctc_posterior_" + sfx).argtypes = [P, BP, C.POINTER(Labellings), i32, i64, C.POINTER(Posterior)]
         getattr(lib, "fcd_ctc_edits_" + sfx).argtypes = [P, BP, C.POINTER(Labellings), i32, i64, C.POINTER(Edits)]
     lib.fcd_debug_set_align_workspace_cap.argtypes = [P, i64]
+    lib.fcd_debug_workspace_bytes.argtypes = [P]
+    lib.fcd_debug_workspace_bytes.restype = i64
     for sfx in ("dev", "host"):
         getattr(lib, "fcd_crf_score_" + sfx).argtypes = [P, BP, P, i64, i64, C.POINTER(Labellings), i64, P]
         getattr(lib, "fcd_crf_align_" + sfx).argtypes = [P, BP, P, i64, i64, C.POINTER(Labellings), i64, C.POINTER(Alignment)]
@@ -369,6 +371,10 @@ class Handle:
     def set_align_workspace_cap(self, nbytes):
         """(include/fcd_debug.h) back-pointer bytes one launch of ctc_align may take; 0 = the default"""
         self.check(self.lib.fcd_debug_set_align_workspace_cap(self.ptr, int(nbytes)))
+
+    def workspace_bytes(self):
+        """(include/fcd_debug.h) bytes of device memory the handle's workspace holds right now"""
+        return int(self.lib.fcd_debug_workspace_bytes(self.ptr))
 
     def release_workspace(self):
         """Give the tree arena / staging memory back to the device (the next call allocates afresh)."""

@@ -888,6 +888,13 @@ int fcd_release_workspace(fcd_handle *h) {
     return FCD_OK;
 }
 
+int64_t fcd_debug_workspace_bytes(fcd_handle *h) {
+    if (!h) return -1;
+    std::lock_guard<std::recursive_mutex> g(h->mu);
+    return (int64_t)(h->arena_bytes + h->pool_arena_bytes + h->pool_ctl_bytes + h->stage_bytes + h->lnbuf_bytes +
+                     h->retry_counter_bytes);
+}
+
 int fcd_set_tie_order(fcd_handle *h, int order) {
     if (!h || (order != FCD_TIE_DEFAULT && order != FCD_TIE_PDQ178 && order != FCD_TIE_STABLE)) return FCD_E_INVALID;
     std::lock_guard<std::recursive_mutex> g(h->mu);

@@ -50,6 +50,11 @@ int fcd_debug_set_first_pass_divisor(fcd_handle *h, int divisor);
  * it).  The labellings of a call are launched in groups of whole reads that fit, at least one read a group: a tiny cap
  * makes a tiny batch run as several groups.  Results do not depend on it. */
 int fcd_debug_set_align_workspace_cap(fcd_handle *h, int64_t bytes);
+/* Test hook: the bytes of device memory the handle's workspace holds right now -- the tree arena and the lattice
+ * workspaces (one allocation that only grows), the wide-beam slab pool and its rings, the host-staging mirror, the duplex
+ * logarithm buffer and the overflow counters.  0 after fcd_release_workspace; -1 for NULL.  Tests read it to see that a
+ * workspace was one piece (>= the bytes a launch needs) or did not grow with a stride. */
+int64_t fcd_debug_workspace_bytes(fcd_handle *h);
 /* Developer instrument: while `cycles` (DEVICE array [n_pairs][16] u32, indexed by the pair's position in the batch)
  * is set, the duplex searches on this handle record a cycle account per pair: shader cycles / 64 spent in
  * [0] envelope + forward-vector extension, [1] LDS tiles, [2] expansion without the window builds, [3] window
