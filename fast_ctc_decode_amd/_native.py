@@ -17,6 +17,7 @@ ST_OK, ST_RAN_OUT_OF_BEAM, ST_INCOMPARABLE, ST_INVALID_ENVELOPE, ST_BAD_STATE, S
 KERNEL_AUTO, KERNEL_GENERIC, KERNEL_WAVE, KERNEL_WAVE1, KERNEL_LANE = 0, 1, 2, 3, 4
 LOGADD_LOGSUMEXP, LOGADD_MAX, LOGADD_LOGSUMEXP_GLIBC235 = 0, 1, 2
 DTYPE_F32, DTYPE_F16, DTYPE_BF16 = 0, 1, 2
+LAYOUT_SOURCE, LAYOUT_DEST = 0, 1  # fcd_crf_transition_probs_*: how the scores are indexed
 TIE_DEFAULT, TIE_PDQ178, TIE_STABLE = -1, 0, 1
 
 # every symbol include/fcd.h declares (tests/test_capi_symbols.py checks the .so against this
@@ -57,6 +58,7 @@ SYMBOLS = [
     "fcd_crf_score_dev", "fcd_crf_score_host", "fcd_crf_align_dev", "fcd_crf_align_host",
     "fcd_crf_posterior_dev", "fcd_crf_posterior_host", "fcd_crf_edits_dev", "fcd_crf_edits_host",
     "fcd_crf_viterbi_search_dev", "fcd_crf_viterbi_search_host",
+    "fcd_crf_transition_probs_dev", "fcd_crf_transition_probs_host",
 ]
 JOB_PATH, JOB_QUAL, JOB_AMBIGUOUS, JOB_DONE = 1, 2, 4, 1
 
@@ -101,6 +103,12 @@ class Posterior(C.Structure):
 class Edits(C.Structure):
     """fcd_edits: what fcd_ctc_edits_* and fcd_crf_edits_* write (include/fcd.h)."""
     _fields_ = [("deletion", C.c_void_p), ("insertion", C.c_void_p), ("logp", C.c_void_p)]
+
+
+class Transitions(C.Structure):
+    """fcd_transitions (include/fcd.h): the outputs of fcd_crf_transition_probs_*"""
+    _fields_ = [("probs", C.c_void_p), ("dtype", C.c_int32), ("stride_read", C.c_int64), ("stride_t", C.c_int64),
+                ("init", C.c_void_p), ("init_stride", C.c_int64), ("logz", C.c_void_p), ("status", C.c_void_p)]
 
 
 class Chunk(C.Structure):
@@ -270,6 +278,7 @@ def bind(lib):
         getattr(lib, "fcd_crf_posterior_" + sfx).argtypes = [P, BP, P, i64, i64, C.POINTER(Labellings), i64, C.POINTER(Posterior)]
         getattr(lib, "fcd_crf_edits_" + sfx).argtypes = [P, BP, P, i64, i64, C.POINTER(Labellings), i64, C.POINTER(Edits)]
         getattr(lib, "fcd_crf_viterbi_search_" + sfx).argtypes = [P, BP, P, i64, i64, RP, P]
+        getattr(lib, "fcd_crf_transition_probs_" + sfx).argtypes = [P, BP, i32, C.POINTER(Transitions)]
     return lib
 
 

@@ -451,6 +451,100 @@ def crf_viterbi_search_batch(network_outputs, init_states, alphabet, qstring=Fal
     return res
 
 
+class TransitionResult:
+    """crf_transition_probs_batch_raw's result: probs (B, T, S, N) transition posteriors (float32 or float16; a view of a
+    (T, B, S, N) array under time_major_out), init (B, S) float32, logz (B,) float64 (NaN for a failed read) and status
+    (B,) int32 -- numpy arrays, or torch tensors on the input's device.  probs and init are what every CRF entry point
+    takes as network_outputs and init_states."""
+
+    def __init__(self, probs, init, logz, status):
+        self.probs, self.init, self.logz, self.status = probs, init, logz, status
+
+    def cpu(self):
+        """-> a TransitionResult of numpy arrays (device results: waits for them)"""
+        if isinstance(self.status, np.ndarray):
+            return self
+        return TransitionResult(*(v.cpu().numpy() for v in (self.probs, self.init, self.logz, self.status)))
+
+
+_LAYOUT_CODES = {"source": nat.LAYOUT_SOURCE, "dest": nat.LAYOUT_DEST}
+
+
+def crf_transition_probs_batch_raw(scores, lengths=None, layout="source", out_dtype="float32", input_dtype=None,
+                                   time_major_out=False):
+    """(B,T,S,N) raw CRF scores -- a network's unnormalised log scores: numpy float32 / float16 / bfloat16 bits, or a torch
+    ROCm tensor, any strides (a permuted (T,B,S,N) tensor included) -> TransitionResult: the locally normalised transition
+    posteriors and the init row that every CRF entry point takes (include/fcd.h, fcd_crf_transition_probs_*: a backward
+    pass over all labellings and a local softmax, on the device).
+
+    layout: "source", scores[b][t][s][a] indexed by the state being left, as the result is; "dest", indexed by the state
+    being entered: scores[b][t][s'][0] stays, scores[b][t][s'][1 + i] enters s' from s' // (N-1) + i * (S // (N-1)).
+    out_dtype: "float32" or "float16" (the float32 value rounded to nearest; the searches read it as it is).
+    time_major_out: probs is stored as (T,B,S,N) and returned as its (B,T,S,N) view.  Rows at and beyond lengths[b] are
+    not written (zeros in a numpy result, uninitialised in a torch one).
+    Device tensors in: torch tensors out, enqueued on torch's current stream, nothing waits.  numpy in: numpy out."""
+    if layout not in _LAYOUT_CODES:
+        raise ValueError("layout must be 'source' or 'dest'")
+    if out_dtype not in ("float32", "float16"):
+        raise ValueError("out_dtype must be 'float32' or 'float16'")
+    code = nat.DTYPE_F32 if out_dtype == "float32" else nat.DTYPE_F16
+    if _is_torch_cuda(scores):
+        import torch
+        x = scores
+        if x.ndim != 4:
+            raise TypeError("expected a tensor of rank 4")
+        dcode = _torch_dtype_code(x)
+        B, T, S, N = x.shape
+        st = x.stride()
+        if any(s < 0 for s in st):
+            raise ValueError("negative strides: pass a contiguous copy")
+        h = nat.default_handle(x.device.index or 0)
+        b = nat.Batch(x.data_ptr(), B, T, S, N, st[0], st[1], st[2], st[3], None, dcode)
+        if lengths is not None:
+            lengths = torch.as_tensor(lengths, dtype=torch.int64, device=x.device).contiguous()
+            if tuple(lengths.shape) != (B,):
+                raise ValueError("lengths must have shape (n_reads,)")
+            b.lengths = lengths.data_ptr()
+        tdt = torch.float32 if code == nat.DTYPE_F32 else torch.float16
+        buf = torch.empty((T, B, S, N) if time_major_out else (B, T, S, N), dtype=tdt, device=x.device)
+        probs = buf.permute(1, 0, 2, 3) if time_major_out else buf
+        init = torch.empty((B, S), dtype=torch.float32, device=x.device)
+        logz = torch.empty((B,), dtype=torch.float64, device=x.device)
+        status = torch.empty((B,), dtype=torch.int32, device=x.device)
+        out = nat.Transitions(buf.data_ptr(), code, probs.stride(0) if B * T else S * N, probs.stride(1) if B * T else S * N,
+                              init.data_ptr(), S, logz.data_ptr(), status.data_ptr())
+        h.set_stream(torch.cuda.current_stream(x.device).cuda_stream)
+        h.check(h.lib.fcd_crf_transition_probs_dev(h.ptr, C.byref(b), _LAYOUT_CODES[layout], C.byref(out)))
+        h.hold_in_flight(x, lengths, buf, init, logz, status)
+        return TransitionResult(probs, init, logz, status)
+    x = _stack_host(scores, 4)
+    B, T, S, N = x.shape
+    h = nat.default_handle()
+    b = _host_batch(x, True, _np_lengths(lengths, B), input_dtype)
+    ndt = np.float32 if code == nat.DTYPE_F32 else np.float16
+    buf = np.zeros((T, B, S, N) if time_major_out else (B, T, S, N), ndt)
+    probs = buf.transpose(1, 0, 2, 3) if time_major_out else buf
+    init = np.zeros((B, S), np.float32)
+    logz = np.zeros(B, np.float64)
+    status = np.zeros(B, np.int32)
+    sr, stt = (S * N, B * S * N) if time_major_out else (T * S * N, S * N)
+    out = nat.Transitions(buf.ctypes.data, code, max(sr, S * N), max(stt, S * N), init.ctypes.data, S, logz.ctypes.data,
+                          status.ctypes.data)
+    h.check(h.lib.fcd_crf_transition_probs_host(h.ptr, C.byref(b), _LAYOUT_CODES[layout], C.byref(out)))
+    return TransitionResult(probs, init, logz, status)
+
+
+def crf_transition_probs(scores, layout="source"):
+    """One read: (T,S,N) raw CRF scores -> (probs (T,S,N) float32, init (S,) float32, logz float) -- what crf_greedy_search,
+    crf_beam_search and crf_viterbi_search take as network_output and init_state (crf_transition_probs_batch_raw has the
+    definition).  RuntimeError with the status string for a read that fails (a NaN or +inf score, or no path of positive
+    weight)."""
+    x = _as_f32(scores, 3, "scores")
+    r = crf_transition_probs_batch_raw(_dense(x)[None], layout=layout)
+    _raise_status(int(r.status[0]))
+    return r.probs[0], r.init[0], float(r.logz[0])
+
+
 _DEFAULT_LOGADD = [nat.LOGADD_LOGSUMEXP]
 
 

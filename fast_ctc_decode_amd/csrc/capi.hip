@@ -626,6 +626,7 @@ class Staging {
     explicit Staging(fcd_handle *h) : h_(h) {}
     int in(const void *host, size_t bytes) { return put(const_cast<void *>(host), bytes, kIn); }
     int out(void *host, size_t bytes, bool zeroed = false) { return put(host, bytes, zeroed ? kOutZeroed : kOut); }
+    int inout(void *host, size_t bytes) { return put(host, bytes, kInOut); }  // an output the call writes only parts of
 
     int commit() {
         fcd_handle *h = h_;
@@ -633,7 +634,8 @@ class Staging {
         if (rc) return rc;
         char *base = static_cast<char *>(h->stage);
         for (const Array &a : a_)
-            if (a.kind == kIn && a.bytes) FCD_HIP(h, hipMemcpyAsync(base + a.off, a.host, a.bytes, hipMemcpyHostToDevice, h->stream));
+            if ((a.kind == kIn || a.kind == kInOut) && a.bytes)
+                FCD_HIP(h, hipMemcpyAsync(base + a.off, a.host, a.bytes, hipMemcpyHostToDevice, h->stream));
         // (outputs zeroed next to one another: one fill, padding included)
         for (size_t i = 0; i < a_.size(); ++i) {
             if (a_[i].kind != kOutZeroed) continue;
@@ -661,7 +663,7 @@ class Staging {
     }
 
   private:
-    enum Kind { kIn, kOut, kOutZeroed };
+    enum Kind { kIn, kOut, kOutZeroed, kInOut };
     struct Array {
         void *host;
         size_t off, bytes;
@@ -1238,6 +1240,107 @@ int fcd_crf_viterbi_search_host(fcd_handle *h, const fcd_batch *in, const float 
     dout.status = st.at<int32_t>(i_stat);
     dout.ambiguous = nullptr;
     rc = crf_viterbi_run(h, &din, st.at<float>(i_init), n_init, init_stride, &dout, st.at<double>(i_logp));
+    if (rc) return rc;
+    return st.fetch();
+}
+
+// ---- CRF transition probabilities from raw scores (viterbi.hip): the (posteriors, init) pair of the CRF entry points ----
+namespace {
+int64_t transitions_span(const fcd_batch *in, const fcd_transitions *out) {  // elements of probs the call may write
+    if (in->n_reads == 0 || in->T == 0) return 0;
+    return (in->n_reads - 1) * out->stride_read + (in->T - 1) * out->stride_t + in->S * in->N;
+}
+
+int crf_transitions_check(fcd_handle *h, const fcd_batch *in, int layout, const fcd_transitions *out) {
+    int rc = check_batch(h, in, true);
+    if (rc) return rc;
+    if (!out) return fail(h, FCD_E_INVALID, "null transitions");
+    if (layout != FCD_LAYOUT_SOURCE && layout != FCD_LAYOUT_DEST) return fail(h, FCD_E_INVALID, "unknown score layout");
+    if (out->dtype != FCD_DTYPE_F32 && out->dtype != FCD_DTYPE_F16)
+        return fail(h, FCD_E_INVALID, "unknown dtype of the transition probabilities (float32 or float16)");
+    if (in->stride_read < 0 || in->stride_t < 0 || in->stride_s < 0 || in->stride_n < 0)
+        return fail(h, FCD_E_INVALID, "negative stride");
+    switch (crf_transitions_unsupported(in->S, in->N)) {
+    case 1: return fail(h, FCD_E_UNSUPPORTED, "crf_transition_probs: N must be in 2 .. 9");
+    case 2: return fail(h, FCD_E_UNSUPPORTED, "crf_transition_probs: S must be a multiple of N - 1 (symbol j + 1 moves state s to "
+                                              "(s (N - 1)) mod S + j)");
+    case 3: return fail(h, FCD_E_UNSUPPORTED, "crf_transition_probs: S must be below 2^24");
+    case 4: return fail(h, FCD_E_UNSUPPORTED, "crf_transition_probs: 8 S + 4608 bytes of backward rows and staging do not fit the 160 KiB of LDS");
+    default: break;
+    }
+    if (in->n_reads == 0) return FCD_OK;
+    if ((in->T > 0 && !out->probs) || !out->init || !out->status) return fail(h, FCD_E_INVALID, "null probs/init/status");
+    if (out->stride_read < in->S * in->N || out->stride_t < in->S * in->N)
+        return fail(h, FCD_E_INVALID, "stride_read and stride_t of the transition probabilities must be at least S N");
+    if (out->init_stride < in->S) return fail(h, FCD_E_INVALID, "init_stride must be at least S");
+    return FCD_OK;
+}
+
+int crf_transitions_run(fcd_handle *h, const fcd_batch *in, int layout, const fcd_transitions *out) {
+    const size_t B = (size_t)in->n_reads;
+    CallScope sc(h);
+    sc.add(out->probs, (size_t)transitions_span(in, out) * (out->dtype == FCD_DTYPE_F32 ? 4 : 2));
+    sc.add(out->init, ((B - 1) * (size_t)out->init_stride + (size_t)in->S) * 4);
+    sc.add(out->logz, B * 8);
+    sc.add(out->status, B * 4);
+    int rc = sc.begin(false, true);  // (behind every overlapping call in flight: one of them may be writing the scores)
+    if (rc) return rc;
+    TransitionsDesc d;
+    d.probs = out->probs;
+    d.dtype = out->dtype;
+    d.layout = layout;
+    d.stride_read = out->stride_read;
+    d.stride_t = out->stride_t;
+    d.init = out->init;
+    d.init_stride = out->init_stride;
+    d.logz = out->logz;
+    d.status = out->status;
+    sc.time();
+    FCD_HIP(h, launch_crf_transitions(to_desc(in, true), d, sc.stream));
+    return sc.finish();
+}
+}  // namespace
+
+int fcd_crf_transition_probs_dev(fcd_handle *h, const fcd_batch *scores, int layout, const fcd_transitions *out) {
+    if (!h) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> g(h->mu);
+    int rc = crf_transitions_check(h, scores, layout, out);
+    if (rc) return rc;
+    if (scores->n_reads == 0) return FCD_OK;
+    FCD_DEVICE(h);
+    return crf_transitions_run(h, scores, layout, out);
+}
+
+// host arrays: staged in the order scores, lengths, the outputs; probs travels both ways (rows t >= T_r are not written)
+int fcd_crf_transition_probs_host(fcd_handle *h, const fcd_batch *scores, int layout, const fcd_transitions *out) {
+    if (!h) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> whole_call(h->mu);  // staging .. copy-back, see run_host
+    int rc = crf_transitions_check(h, scores, layout, out);
+    if (rc) return rc;
+    const fcd_batch *in = scores;
+    if (in->n_reads == 0) return FCD_OK;
+    FCD_DEVICE(h);
+    const size_t B = (size_t)in->n_reads;
+    Staging st(h);
+    const int i_x = st.in(in->post, (size_t)span_elems(in, true) * (in->dtype == FCD_DTYPE_F32 ? 4 : 2));
+    const int i_len = st.in(in->lengths, B * 8);
+    const int i_probs = st.inout(out->probs, (size_t)transitions_span(in, out) * (out->dtype == FCD_DTYPE_F32 ? 4 : 2));
+    const size_t init_bytes = ((B - 1) * (size_t)out->init_stride + (size_t)in->S) * 4;
+    // (init rows with spare elements between them travel both ways too: the spare elements keep the caller's content)
+    const int i_init = out->init_stride > in->S ? st.inout(out->init, init_bytes) : st.out(out->init, init_bytes);
+    const int i_logz = st.out(out->logz, B * 8);
+    const int i_stat = st.out(out->status, B * 4);
+    rc = st.commit();
+    if (rc) return rc;
+    fcd_batch din = *in;
+    din.post = st.at<char>(i_x);
+    din.lengths = st.at<int64_t>(i_len);
+    fcd_transitions dout = *out;
+    dout.probs = st.at<char>(i_probs);
+    dout.init = st.at<float>(i_init);
+    dout.logz = st.at<double>(i_logz);
+    dout.status = st.at<int32_t>(i_stat);
+    rc = crf_transitions_run(h, &din, layout, &dout);
     if (rc) return rc;
     return st.fetch();
 }

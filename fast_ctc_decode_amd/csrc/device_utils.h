@@ -28,6 +28,27 @@ enum { kF32 = 0, kF16 = 1, kBF16 = 2 };
 __device__ __forceinline__ float f16_bits_to_f32(uint16_t h) { return FCD_F16_TO_F32(h); }
 __device__ __forceinline__ float bf16_bits_to_f32(uint16_t h) { return __uint_as_float((uint32_t)h << 16); }
 
+// binary32 -> binary16 bits, round to nearest even (v_cvt_f16_f32 under the default rounding mode)
+__device__ __forceinline__ uint16_t f32_to_f16_bits(float v) {
+#ifdef FCD_HIPEMU  // (lockstep emulation, tests/hipemu: its host compiler has no _Float16)
+    const uint32_t u = __float_as_uint(v), sign = (u >> 16) & 0x8000u, a = u & 0x7FFFFFFFu;
+    if (a >= 0x7F800000u) return (uint16_t)(sign | (a > 0x7F800000u ? 0x7E00u : 0x7C00u));  // NaN, infinity
+    if (a >= 0x477FF000u) return (uint16_t)(sign | 0x7C00u);                                // rounds to 2^16 or beyond
+    if (a < 0x33000000u) return (uint16_t)sign;                                             // at most 2^-25: to zero
+    const int e = (int)(a >> 23) - 127;
+    const uint32_t m = (a & 0x7FFFFFu) | 0x800000u;
+    const int shift = e >= -14 ? 13 : 13 + (-14 - e);  // (subnormal results lose -14 - e more bits)
+    uint32_t q = m >> shift;
+    const uint32_t rem = m & ((1u << shift) - 1u), half = 1u << (shift - 1);
+    if (rem > half || (rem == half && (q & 1u))) ++q;
+    // normal: q holds the implicit bit at 2^10, so adding (e + 14) << 10 gives exponent field e + 15 (a carry out of the
+    // mantissa lands in the exponent, as it should); subnormal: q is the field itself (a carry makes the least normal)
+    return (uint16_t)(sign | (e >= -14 ? ((uint32_t)(e + 14) << 10) + q : q));
+#else
+    return __builtin_bit_cast(uint16_t, (_Float16)v);
+#endif
+}
+
 // the address of element `offset` of a posterior array (a read's first element), still typed as float *
 __device__ __forceinline__ const float *post_at(const float *base, int64_t offset, int dtype) {
     return reinterpret_cast<const float *>(reinterpret_cast<const char *>(base) + offset * (dtype == kF32 ? 4 : 2));

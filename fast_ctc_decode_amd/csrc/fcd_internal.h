@@ -153,6 +153,23 @@ size_t crf_viterbi_read_bytes(int64_t T, int64_t S);
 hipError_t launch_crf_viterbi(const BatchDesc &in, const float *init, int64_t n_init, int64_t init_stride,
                               const ResultDesc &out, double *logp, unsigned char *bp, hipStream_t stream);
 
+// CRF transition probabilities from raw scores (fcd_crf_transition_probs_* in include/fcd.h; the walk lives in viterbi.hip,
+// inside crf_greedy_kernel).  `in` holds the scores; everything here is device memory.  crf_transitions_unsupported:
+// 0 supported, 1 N outside 2 .. 9, 2 S no multiple of N - 1, 3 S beyond the state word, 4 the two rows of the backward
+// vector and the store staging beyond the LDS of a CU.
+struct TransitionsDesc {
+    void *probs;          // f32 or f16 (dtype: kF32 / kF16); row t of read r at r * stride_read + t * stride_t, (S, N) dense
+    int dtype;
+    int layout;           // of the scores: FCD_LAYOUT_SOURCE / FCD_LAYOUT_DEST
+    int64_t stride_read, stride_t;
+    float *init;          // [n_reads * init_stride]
+    int64_t init_stride;
+    double *logz;         // [n_reads], nullable
+    int32_t *status;      // [n_reads]
+};
+int crf_transitions_unsupported(int64_t S, int64_t N);
+hipError_t launch_crf_transitions(const BatchDesc &in, const TransitionsDesc &out, hipStream_t stream);
+
 // duplex::beam_search (src/duplex.rs:443-650) launch arguments; all pointers are device memory.
 struct DuplexArgs {
     const float *ln1, *ln2;  // log-space posteriors [pair][Tcap][N]

@@ -477,11 +477,13 @@ __global__ __launch_bounds__(256) void viterbi_tm_kernel(BatchDesc in, int colla
 // back after the last row, 64 emissions at a time in registers, written to the END of the read's output rows and moved
 // to the front once their number is known -- no second pass over the posteriors.
 struct VitArgs {
-    int mode;               // 0: crf_greedy_search's walk (every launch of launch_crf_greedy); 1: the Viterbi walk
-    int lds_bytes;          // dynamic LDS of the launch (mode 1)
+    int mode;               // 0: crf_greedy_search's walk (every launch of launch_crf_greedy); 1: the Viterbi walk;
+                            // 2: the transition-probability walk (crf_transitions_walk)
+    int lds_bytes;          // dynamic LDS of the launch (modes 1 and 2)
     double *logp;           // [n_reads], nullable
     unsigned char *bp;      // back-pointers: bp_read_bytes per read, row t and state s at [t * S + s]
     int64_t bp_read_bytes;
+    TransitionsDesc tr;     // mode 2: the outputs and the input's layout
 };
 
 constexpr int kVitMaxN = 9;
@@ -788,13 +790,245 @@ __device__ __forceinline__ void crf_viterbi_walk(const BatchDesc &in, const floa
     }
 }
 
+// ---- CRF transition probabilities from raw scores (fcd_crf_transition_probs_*; include/fcd.h has the definition) ----
+// NOT a reference function: the step in front of every CRF entry point -- a backward pass over all labellings and a local
+// softmax, which turns a network's unnormalised log scores x into the (posteriors, init) pair the searches read.
+//
+// One wavefront per read, back to front.  The backward vector lives in LDS, two rows of S floats (row t is written while
+// row t + 1 is read) and is never stored.  A row is kept UNNORMALISED as it is written; its maximum c_t, a wave reduction,
+// is subtracted where the next row reads it (beta~[d] = beta[d] - c_t, the same f32 subtraction either way), and summed
+// in float64 for logZ.  Per state: y_a = x_a + beta~[d(s, a)], d(s, 0) = s, d(s, j + 1) = (s nb) mod S + j -- the nb advance
+// destinations are nb consecutive states --, m = max y, e_a = exp(y_a - m), the sum in the order a = 0 .. N - 1,
+// p_a = e_a / sum, beta = m + ln sum; a state whose candidates are all -inf is dead (p = 0, beta = -inf).
+// A row of at most 64 elements takes a lane per element (the candidates of a state meet through LDS; the store is one
+// contiguous run); larger rows a lane per state, 64 states at a time, whose 64 N probabilities are parked in LDS and
+// stored as contiguous runs across lanes.  Loads run ahead of the dependent chain: kTrAhead rows with a lane per element,
+// kTrRows chunks of 64 states with a lane per state (a chunk is N registers per lane).
+// Scores indexed by the state being ENTERED (FCD_LAYOUT_DEST) are a different offset per element at load time, nothing more.
+constexpr int kTrAhead = 4;
+constexpr int kTrRows = 2;
+constexpr int kTrStage = kWave * kVitMaxN;  // floats of one staging buffer: the probabilities of 64 states
+
+#ifdef FCD_HIPEMU  // (lockstep emulation, tests/hipemu: the plain libm forms)
+#define FCD_TR_EXP(x) expf(x)
+#define FCD_TR_LOG(x) logf(x)
+#else
+#define FCD_TR_EXP(x) __expf(x)
+#define FCD_TR_LOG(x) __logf(x)
+#endif
+
+__device__ __forceinline__ float wave_fmax(float x) {  // of values that are not NaN: through the order-preserving integer
+    int b = __float_as_int(x);
+    b ^= (b >> 31) & 0x7fffffff;
+    b = wave_imax(b);
+    b ^= (b >> 31) & 0x7fffffff;
+    return __int_as_float(b);
+}
+
+__device__ __forceinline__ void crf_transitions_walk(const BatchDesc &in, const VitArgs &va, float *lds) {
+    const int lane = threadIdx.x;
+    const int64_t r = blockIdx.x;
+    int64_t T = in.T;
+    if (in.lengths) {
+        int64_t t = in.lengths[r];
+        T = t < 0 ? 0 : (t < T ? t : T);
+    }
+    const int Tr = (int)T;
+    const int N = in.N, S = in.S, nb = N - 1, q = S / nb;
+    const int dt = in.dtype;
+    const TransitionsDesc &o = va.tr;
+    const bool dest = o.layout != 0, half_out = o.dtype == kF16;
+    const float *x = post_at(in.post, r * in.stride_read, dt);
+    float *pf = reinterpret_cast<float *>(o.probs) + (half_out ? 0 : r * o.stride_read);
+    uint16_t *ph = reinterpret_cast<uint16_t *>(o.probs) + (half_out ? r * o.stride_read : 0);
+    auto store_p = [&](int64_t off, float v) {
+        if (half_out) ph[off] = f32_to_f16_bits(v);
+        else pf[off] = v;
+    };
+    float *beta = lds, *stage = lds + 2 * (size_t)S;
+
+    for (int s = lane; s < S; s += kWave) beta[(size_t)(Tr & 1) * S + s] = 0.0f;  // beta~_T = 0
+    vit_lds_sync();
+    float cprev = 0.0f;     // the maximum of the row being read, not yet subtracted from it
+    double csum = 0.0;      // of the row maxima
+    bool badx = false;      // this lane met a NaN or +inf
+    bool no_path = false;   // a row without a live state (wave-uniform)
+    const int E = S * N;
+
+    if (E <= kWave) {  // ---- a lane per element e = s N + a ----
+        const bool act = lane < E;
+        const int e = act ? lane : 0, s = e / N, a = e - s * N;
+        const int sq = s / q, d = a == 0 ? s : (s - sq * q) * nb + a - 1;
+        const int64_t xoff = a == 0 ? (int64_t)s * in.stride_s
+                             : dest ? (int64_t)d * in.stride_s + (int64_t)(1 + sq) * in.stride_n
+                                    : (int64_t)s * in.stride_s + (int64_t)a * in.stride_n;
+        float ring[kTrAhead];
+#pragma unroll
+        for (int u = 0; u < kTrAhead; ++u)
+            ring[u] = (act && u < Tr) ? load_post(x, (int64_t)(Tr - 1 - u) * in.stride_t + xoff, dt) : 0.0f;
+        for (int k0 = 0; k0 < Tr; k0 += kTrAhead) {
+#pragma unroll
+            for (int u = 0; u < kTrAhead; ++u) {
+                const int t = Tr - 1 - (k0 + u);
+                if (t < 0) break;
+                const float xv = ring[u];
+                if (act && t - kTrAhead >= 0) ring[u] = load_post(x, (int64_t)(t - kTrAhead) * in.stride_t + xoff, dt);
+                badx = badx || !(xv < INFINITY);
+                const float *bn = beta + (size_t)((t + 1) & 1) * S;
+                const float y = xv + (bn[d] - cprev);
+                if (act) stage[e] = y;
+                vit_lds_sync();
+                const float *ys = stage + s * N;
+                float m = ys[0];
+                for (int j = 1; j < N; ++j) m = fmaxf(m, ys[j]);
+                const bool live = m > -INFINITY;
+                float sum = 0.0f;
+                for (int j = 0; j < N; ++j) sum += live ? FCD_TR_EXP(ys[j] - m) : 0.0f;
+                const float p = live ? FCD_TR_EXP(y - m) / sum : 0.0f;
+                const float b = live ? m + FCD_TR_LOG(sum) : -INFINITY;
+                if (act) store_p((int64_t)t * o.stride_t + e, p);
+                if (act && a == 0) beta[(size_t)(t & 1) * S + s] = b;
+                const float c = wave_fmax(act ? b : -INFINITY);
+                no_path = no_path || !(c > -INFINITY);
+                csum += (double)c;
+                cprev = c;
+                vit_lds_sync();
+            }
+        }
+    } else {  // ---- a lane per state, 64 states (a chunk) at a time; the items (row, chunk) in the order they are walked ----
+        const int nchunk = (S + kWave - 1) / kWave;
+        // state s = sq q + rq: its advances enter rq nb .. rq nb + nb - 1, and a `dest` input holds them in column 1 + sq
+        const int sq0 = lane / q, rq0 = lane - sq0 * q, stepq = kWave / q, stepr = kWave - stepq * q;
+        struct Cur {
+            int t, c, s, rq, sq;
+        };
+        auto cur_next = [&](Cur &k) {
+            if (++k.c == nchunk) {
+                k.c = 0;
+                --k.t;
+                k.s = lane;
+                k.rq = rq0;
+                k.sq = sq0;
+            } else {
+                k.s += kWave;
+                k.rq += stepr;
+                k.sq += stepq;
+                if (k.rq >= q) {
+                    k.rq -= q;
+                    ++k.sq;
+                }
+            }
+        };
+        auto load_row = [&](const Cur &k, float (&p)[kVitMaxN]) {
+#pragma unroll
+            for (int j = 0; j < kVitMaxN; ++j) p[j] = 0.0f;
+            if (k.t < 0 || k.s >= S) return;
+            const int64_t row = (int64_t)k.t * in.stride_t, o0 = row + (int64_t)k.s * in.stride_s;
+            const int64_t o1 = dest ? row + (int64_t)(k.rq * nb) * in.stride_s + (int64_t)(1 + k.sq) * in.stride_n : o0 + in.stride_n;
+            const int64_t da = dest ? in.stride_s : in.stride_n;
+            p[0] = load_post(x, o0, dt);
+#pragma unroll
+            for (int j = 1; j < kVitMaxN; ++j)
+                if (j < N) p[j] = load_post(x, o1 + (int64_t)(j - 1) * da, dt);
+        };
+        Cur lc{Tr - 1, 0, lane, rq0, sq0}, cc = lc;
+        float ring[kTrRows][kVitMaxN];
+#pragma unroll
+        for (int u = 0; u < kTrRows; ++u) {
+            load_row(lc, ring[u]);
+            cur_next(lc);
+        }
+        const int64_t items = (int64_t)Tr * nchunk;
+        float lmax = -INFINITY;  // this lane's largest beta of the row so far
+        int par = 0;             // staging buffer of the item
+        for (int64_t k0 = 0; k0 < items; k0 += kTrRows) {
+#pragma unroll
+            for (int u = 0; u < kTrRows; ++u) {
+                if (k0 + u >= items) break;
+                float y[kVitMaxN];
+#pragma unroll
+                for (int j = 0; j < kVitMaxN; ++j) y[j] = ring[u][j];
+                load_row(lc, ring[u]);
+                cur_next(lc);
+                const bool act = cc.s < S;
+                const int s = act ? cc.s : 0, base = act ? cc.rq * nb : 0;
+                const float *bn = beta + (size_t)((cc.t + 1) & 1) * S;
+                float *st = stage + par * kTrStage + lane * N;
+#pragma unroll
+                for (int j = 0; j < kVitMaxN; ++j) {
+                    if (j >= N) break;
+                    badx = badx || !(y[j] < INFINITY);
+                    y[j] += bn[j == 0 ? s : base + j - 1] - cprev;
+                }
+                float m = y[0];
+#pragma unroll
+                for (int j = 1; j < kVitMaxN; ++j) {
+                    if (j >= N) break;
+                    m = fmaxf(m, y[j]);
+                }
+                const bool live = m > -INFINITY;
+                float sum = 0.0f;
+#pragma unroll
+                for (int j = 0; j < kVitMaxN; ++j) {
+                    if (j >= N) break;
+                    y[j] = live ? FCD_TR_EXP(y[j] - m) : 0.0f;
+                    sum += y[j];
+                }
+                const float b = live ? m + FCD_TR_LOG(sum) : -INFINITY;
+                if (act) {
+                    beta[(size_t)(cc.t & 1) * S + s] = b;
+                    lmax = fmaxf(lmax, b);
+#pragma unroll
+                    for (int j = 0; j < kVitMaxN; ++j) {
+                        if (j >= N) break;
+                        st[j] = live ? y[j] / sum : 0.0f;
+                    }
+                }
+                if (cc.c == nchunk - 1) {  // the row is complete: its maximum
+                    const float c = wave_fmax(lmax);
+                    no_path = no_path || !(c > -INFINITY);
+                    csum += (double)c;
+                    cprev = c;
+                    lmax = -INFINITY;
+                }
+                vit_lds_sync();
+                // the chunk's probabilities, contiguous across lanes
+                const int s0 = cc.c * kWave, n_el = min(kWave, S - s0) * N;
+                const int64_t o0 = (int64_t)cc.t * o.stride_t + (int64_t)s0 * N;
+                const float *sp = stage + par * kTrStage;
+                for (int el = lane; el < n_el; el += kWave) store_p(o0 + el, sp[el]);
+                par ^= 1;
+                cur_next(cc);
+            }
+        }
+    }
+
+    // init[s] = exp(beta~_0[s]) / sum_s exp(beta~_0[s]); logZ = sum_t c_t + ln of that sum
+    const float *b0 = beta;
+    float zs = 0.0f;
+    for (int s = lane; s < S; s += kWave) zs += FCD_TR_EXP(b0[s] - cprev);
+    for (int m = 1; m < kWave; m <<= 1) zs += __shfl_xor(zs, m);
+    const bool failed = ballot(badx) != 0ull || no_path;
+    float *init = o.init + r * o.init_stride;
+    for (int s = lane; s < S; s += kWave) init[s] = FCD_TR_EXP(b0[s] - cprev) / zs;
+    if (lane == 0) {
+        o.status[r] = failed ? FCD_ST_INCOMPARABLE : FCD_ST_OK;
+        if (o.logz) o.logz[r] = failed ? (double)NAN : csum + log((double)zs);
+    }
+}
+
 // crf_greedy_search (:385-423): the state walk is a serial dependency; one wave per read,
 // lanes 0..N-1 hold the current state's row and reduce it with a first-maximum argmax.
-// va.mode (wave-uniform) = 1: the Viterbi walk above instead -- the one launch with dynamic LDS.
+// va.mode (wave-uniform) = 1: the Viterbi walk above instead, 2: the transition-probability walk -- the launches with
+// dynamic LDS.
 __global__ __launch_bounds__(64) void crf_greedy_kernel(BatchDesc in, const float *init_all,
                                                       int64_t n_init, int64_t init_stride,
                                                       ResultDesc out, VitArgs va) {
     extern __shared__ __attribute__((aligned(16))) float s_vit[];
+    if (va.mode == 2) {
+        crf_transitions_walk(in, va, s_vit);
+        return;
+    }
     if (va.mode) {
         crf_viterbi_walk(in, init_all, n_init, init_stride, out, va, s_vit);
         return;
@@ -1310,6 +1544,38 @@ hipError_t launch_crf_viterbi(const BatchDesc &in, const float *init, int64_t n_
 #endif
     hipLaunchKernelGGL(crf_greedy_kernel, dim3((unsigned)in.n_reads), dim3(64), (size_t)va.lds_bytes, stream, in, init, n_init,
                        init_stride, out, va);
+    return hipGetLastError();
+}
+
+namespace {
+size_t crf_transitions_lds_bytes(int64_t S) {  // two rows of the backward vector, two staging buffers
+    return ((size_t)2 * (size_t)S + 2 * kTrStage) * 4;
+}
+}  // namespace
+
+int crf_transitions_unsupported(int64_t S, int64_t N) {
+    if (N < 2 || N > kVitMaxN) return 1;
+    if (S % (N - 1) != 0) return 2;
+    if (S >= (1ll << 24)) return 3;
+    if (crf_transitions_lds_bytes(S) > 160 * 1024) return 4;
+    return 0;
+}
+
+hipError_t launch_crf_transitions(const BatchDesc &in, const TransitionsDesc &out, hipStream_t stream) {
+    if (in.n_reads <= 0) return hipSuccess;
+    VitArgs va{};
+    va.mode = 2;
+    va.lds_bytes = (int)crf_transitions_lds_bytes(in.S);
+    va.tr = out;
+#ifndef FCD_HIPEMU
+    if (va.lds_bytes > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(crf_greedy_kernel),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, va.lds_bytes);
+        if (e != hipSuccess) return e;
+    }
+#endif
+    hipLaunchKernelGGL(crf_greedy_kernel, dim3((unsigned)in.n_reads), dim3(64), (size_t)va.lds_bytes, stream, in,
+                       static_cast<const float *>(nullptr), (int64_t)0, (int64_t)0, ResultDesc{}, va);
     return hipGetLastError();
 }
 

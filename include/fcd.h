@@ -726,6 +726,65 @@ int fcd_crf_viterbi_search_dev(fcd_handle *h, const fcd_batch *in, const float *
 int fcd_crf_viterbi_search_host(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init, int64_t init_stride,
                                 const fcd_result *out, double *logp);
 
+/* ---- CRF transition probabilities: a network's raw scores -> the (posteriors, init) pair every CRF entry point reads ----
+ * NOT a reference function.  A CRF basecaller network emits unnormalised log scores; this is the backward pass over all
+ * labellings and the local softmax that turn them into transition posteriors and an init row, on the device.
+ * Input: `scores`, a (n_reads, T, S, N) batch of log scores, f32 / f16 / bf16 converted exactly, any non-negative strides
+ * (time-major views included), scores->lengths.  nb = N - 1.  Symbol 0 stays in state s; symbol j + 1 emits label j + 1 and
+ * moves to d(s, j + 1) = (s nb) mod S + j (src/search.rs:97,414); d(s, 0) = s.  Per read, with x[t][s][a] its scores:
+ *     beta_T[s]  = 0
+ *     y_t[s][a]  = x[t][s][a] + beta_{t+1}[d(s, a)]
+ *     beta_t[s]  = ln sum_a exp y_t[s][a]
+ *     p[t][s][a] = exp(y_t[s][a] - beta_t[s])                       out->probs: every row over a sums to 1
+ *     init[s]    = exp(beta_0[s] - logZ),  logZ = ln sum_s exp beta_0[s]     out->init, out->logz
+ * Property: for every start state s0 and every symbol sequence a_0 .. a_{T-1} with the states s_t it passes,
+ *     init[s0] prod_t p[t][s_t][a_t] = exp(sum_t x[t][s_t][a_t] - logZ):
+ * the locally normalised outputs reproduce the globally normalised model exactly, which is what gives the searches'
+ * products of posteriors their meaning.
+ * Layout of the scores:
+ *   FCD_LAYOUT_SOURCE  x[t][s][a] as above: indexed as the output is, by the state being LEFT.
+ *   FCD_LAYOUT_DEST    xd[t][s'][.] indexed by the state being ENTERED: xd[t][s'][0] stays at s'; xd[t][s'][1 + i] enters s'
+ *                      from s_i = s' div nb + i (S / nb), the s_i of fcd_crf_viterbi_search_*.  That is
+ *                      x[t][s][j + 1] = xd[t][(s nb) mod S + j][1 + (s nb) div S] and x[t][s][0] = xd[t][s][0]; the layout is
+ *                      defined by this formula alone.  A different offset per element at load time; no transposing pass.
+ *   The output is always source-indexed.
+ * Output (fcd_transitions):
+ *   probs  f32 (FCD_DTYPE_F32) or f16 (FCD_DTYPE_F16: the f32 value rounded to nearest even), element (r, t, s, a) at
+ *          probs[r stride_read + t stride_t + s N + a]: dense (S, N) rows, the caller's read and row strides in elements
+ *          (stride_read = S N, stride_t = n_reads S N is the time-major (T, B, S, N) tensor).  Rows t >= T_r are not written.
+ *   init   f32, [n_reads * init_stride], S per read;  logz  float64 per read, nullable;  status  FCD_ST_* per read.
+ * Arithmetic (f32; executable specification: tests/crf_transitions_reference.py): beta is renormalised by its row maximum
+ * at every step, beta~_t = beta_t - c_t with c_t = max_s beta_t[s] -- the outputs depend on differences only --, and
+ * logZ = sum_t c_t + ln sum_s exp beta~_0[s], accumulated in float64.  Per state m = max_a y, e_a = exp(y_a - m), the sum in
+ * the order a = 0 .. N - 1, p_a = e_a / sum, beta = m + ln sum.  init[s] = exp(beta~_0[s]) / sum_s exp(beta~_0[s]).  exp and ln
+ * are the device's fast forms (a few ulp).
+ * Edge cases: x = -inf is a forbidden transition, its p exactly 0.  A state whose N candidates are all -inf is dead: its p
+ * row is all zeros, its beta -inf; dead at row 0, its init is 0.  A read FAILS -- FCD_ST_INCOMPARABLE, logz NaN, its probs
+ * and init unspecified, the other reads unaffected -- if a row of beta~ has no live state (no path has positive weight) or
+ * a row t < T_r holds a NaN or +inf.  T_r = 0: init = 1 / S, logz = ln S, FCD_ST_OK.
+ * Limits (FCD_E_UNSUPPORTED; the message says which): 2 <= N <= 9; S a multiple of N - 1; S < 2^24; 8 S + 4608 bytes of LDS
+ * per read (two rows of beta~ and the store staging) within the 160 KiB of a CU.  No workspace: beta~ is never stored.
+ * _dev is enqueue-only on the handle's stream (never on fcd_set_overlap's internal streams) and ordered behind every
+ * overlapping call in flight; _host stages host arrays (probs included: rows t >= T_r keep the caller's content) and
+ * returns when the results are in them.
+ * FCD_E_INVALID: null scores / out / probs / init / status, an unknown layout or dtype, stride_read or stride_t below S N,
+ * init_stride below S. */
+enum { FCD_LAYOUT_SOURCE = 0, FCD_LAYOUT_DEST = 1 };
+
+typedef struct fcd_transitions {
+    void *probs;
+    int32_t dtype;       /* FCD_DTYPE_F32 or FCD_DTYPE_F16 */
+    int64_t stride_read;
+    int64_t stride_t;
+    float *init;
+    int64_t init_stride;
+    double *logz;        /* nullable */
+    int32_t *status;
+} fcd_transitions;
+
+int fcd_crf_transition_probs_dev(fcd_handle *h, const fcd_batch *scores, int layout, const fcd_transitions *out);
+int fcd_crf_transition_probs_host(fcd_handle *h, const fcd_batch *scores, int layout, const fcd_transitions *out);
+
 /* ---- duplex::beam_search (src/duplex.rs:443-650) ----
  * (Two kernels serve the duplex searches since round 6, with identical results: the slot-resident one --
  * csrc/duplex_slots.hip -- wherever beam_size * N <= 64 and the live nodes' windows fit the LDS, the any-shape one --
