@@ -59,6 +59,7 @@ SYMBOLS = [
     "fcd_crf_posterior_dev", "fcd_crf_posterior_host", "fcd_crf_edits_dev", "fcd_crf_edits_host",
     "fcd_crf_viterbi_search_dev", "fcd_crf_viterbi_search_host",
     "fcd_crf_transition_probs_dev", "fcd_crf_transition_probs_host",
+    "fcd_crf_marginals_dev", "fcd_crf_marginals_host",
 ]
 JOB_PATH, JOB_QUAL, JOB_AMBIGUOUS, JOB_DONE = 1, 2, 4, 1
 
@@ -109,6 +110,12 @@ class Transitions(C.Structure):
     """fcd_transitions (include/fcd.h): the outputs of fcd_crf_transition_probs_*"""
     _fields_ = [("probs", C.c_void_p), ("dtype", C.c_int32), ("stride_read", C.c_int64), ("stride_t", C.c_int64),
                 ("init", C.c_void_p), ("init_stride", C.c_int64), ("logz", C.c_void_p), ("status", C.c_void_p)]
+
+
+class Marginals(C.Structure):
+    """fcd_marginals (include/fcd.h): the outputs of fcd_crf_marginals_*"""
+    _fields_ = [("marg", C.c_void_p), ("stride_read", C.c_int64), ("stride_t", C.c_int64), ("emit", C.c_void_p),
+                ("emit_stride", C.c_int64), ("logz", C.c_void_p), ("status", C.c_void_p)]
 
 
 class Chunk(C.Structure):
@@ -279,6 +286,7 @@ def bind(lib):
         getattr(lib, "fcd_crf_edits_" + sfx).argtypes = [P, BP, P, i64, i64, C.POINTER(Labellings), i64, C.POINTER(Edits)]
         getattr(lib, "fcd_crf_viterbi_search_" + sfx).argtypes = [P, BP, P, i64, i64, RP, P]
         getattr(lib, "fcd_crf_transition_probs_" + sfx).argtypes = [P, BP, i32, C.POINTER(Transitions)]
+        getattr(lib, "fcd_crf_marginals_" + sfx).argtypes = [P, BP, i32, C.POINTER(Marginals)]
     return lib
 
 

@@ -545,6 +545,135 @@ def crf_transition_probs(scores, layout="source"):
     return r.probs[0], r.init[0], float(r.logz[0])
 
 
+class MarginalResult:
+    """crf_marginals_batch_raw's result: marginals (B, T, S, N) float32 edge marginals, source-indexed (a view of a
+    (T, B, S, N) array under time_major_out), emit (B, T, N) float32 label posteriors per row (None without emit), logz (B,)
+    float64 (NaN for a failed read) and status (B,) int32 -- numpy arrays, or torch tensors on the input's device."""
+
+    def __init__(self, marginals, emit, logz, status):
+        self.marginals, self.emit, self.logz, self.status = marginals, emit, logz, status
+
+    def cpu(self):
+        """-> a MarginalResult of numpy arrays (device results: waits for them)"""
+        if isinstance(self.status, np.ndarray):
+            return self
+        return MarginalResult(*(None if v is None else v.cpu().numpy() for v in (self.marginals, self.emit, self.logz, self.status)))
+
+
+def _crf_marginals_torch(x, lengths, layout, emit, time_major_out, zeroed=False):
+    """the device call on a rank-4 torch ROCm tensor -> (marginals, emit, logz, status), enqueued on the current stream"""
+    import torch
+    dcode = _torch_dtype_code(x)
+    B, T, S, N = x.shape
+    st = x.stride()
+    if any(s < 0 for s in st):
+        raise ValueError("negative strides: pass a contiguous copy")
+    h = nat.default_handle(x.device.index or 0)
+    b = nat.Batch(x.data_ptr(), B, T, S, N, st[0], st[1], st[2], st[3], None, dcode)
+    if lengths is not None:
+        lengths = torch.as_tensor(lengths, dtype=torch.int64, device=x.device).contiguous()
+        if tuple(lengths.shape) != (B,):
+            raise ValueError("lengths must have shape (n_reads,)")
+        b.lengths = lengths.data_ptr()
+    alloc = torch.zeros if zeroed else torch.empty
+    buf = alloc((T, B, S, N) if time_major_out else (B, T, S, N), dtype=torch.float32, device=x.device)
+    marg = buf.permute(1, 0, 2, 3) if time_major_out else buf
+    em = alloc((B, T, N), dtype=torch.float32, device=x.device) if emit else None
+    logz = torch.empty((B,), dtype=torch.float64, device=x.device)
+    status = torch.empty((B,), dtype=torch.int32, device=x.device)
+    out = nat.Marginals(buf.data_ptr(), marg.stride(0) if B * T else S * N, marg.stride(1) if B * T else S * N,
+                        em.data_ptr() if emit else None, T * N, logz.data_ptr(), status.data_ptr())
+    h.set_stream(torch.cuda.current_stream(x.device).cuda_stream)
+    h.check(h.lib.fcd_crf_marginals_dev(h.ptr, C.byref(b), _LAYOUT_CODES[layout], C.byref(out)))
+    h.hold_in_flight(x, lengths, buf, em, logz, status)
+    return marg, em, logz, status
+
+
+def crf_marginals_batch_raw(scores, lengths=None, layout="source", input_dtype=None, emit=True, time_major_out=False):
+    """(B,T,S,N) raw CRF scores, as crf_transition_probs_batch_raw takes them -> MarginalResult: the edge marginals over all
+    labellings (include/fcd.h, fcd_crf_marginals_*: the backward pass of crf_transition_probs and a forward pass over its
+    result, one kernel launch).  marginals[b][t][s][a] is the probability that the model leaves state s by symbol a at row
+    t, which is d logz[b] / d scores[b][t][s][a]; emit[b][t][a] is its sum over states, a (T, N) matrix of label posteriors
+    whose rows sum to 1.  logz and status are crf_transition_probs_batch_raw's, bit for bit.
+
+    layout: of the scores, "source" or "dest"; the result is always source-indexed.  emit=False: no emit array.
+    time_major_out: marginals is stored as (T,B,S,N) and returned as its (B,T,S,N) view.  Rows at and beyond lengths[b]
+    are not written (zeros in a numpy result, uninitialised in a torch one).
+    Device tensors in: torch tensors out, enqueued on torch's current stream, nothing waits.  numpy in: numpy out."""
+    if layout not in _LAYOUT_CODES:
+        raise ValueError("layout must be 'source' or 'dest'")
+    if _is_torch_cuda(scores):
+        if scores.ndim != 4:
+            raise TypeError("expected a tensor of rank 4")
+        return MarginalResult(*_crf_marginals_torch(scores, lengths, layout, emit, time_major_out))
+    x = _stack_host(scores, 4)
+    B, T, S, N = x.shape
+    h = nat.default_handle()
+    b = _host_batch(x, True, _np_lengths(lengths, B), input_dtype)
+    buf = np.zeros((T, B, S, N) if time_major_out else (B, T, S, N), np.float32)
+    marg = buf.transpose(1, 0, 2, 3) if time_major_out else buf
+    em = np.zeros((B, T, N), np.float32) if emit else None
+    logz = np.zeros(B, np.float64)
+    status = np.zeros(B, np.int32)
+    sr, stt = (S * N, B * S * N) if time_major_out else (T * S * N, S * N)
+    out = nat.Marginals(buf.ctypes.data, max(sr, S * N), max(stt, S * N), em.ctypes.data if emit else None, T * N,
+                        logz.ctypes.data, status.ctypes.data)
+    h.check(h.lib.fcd_crf_marginals_host(h.ptr, C.byref(b), _LAYOUT_CODES[layout], C.byref(out)))
+    return MarginalResult(marg, em, logz, status)
+
+
+def crf_marginals(scores, layout="source"):
+    """One read: (T,S,N) raw CRF scores -> (marginals (T,S,N) float32, emit (T,N) float32, logz float)
+    (crf_marginals_batch_raw has the definition).  RuntimeError with the status string for a read that fails (a NaN or +inf
+    score, or no path of positive weight)."""
+    x = _as_f32(scores, 3, "scores")
+    r = crf_marginals_batch_raw(_dense(x)[None], layout=layout)
+    _raise_status(int(r.status[0]))
+    return r.marginals[0], r.emit[0], float(r.logz[0])
+
+
+_CRF_LOGZ_FN = []
+
+
+def _crf_logz_function():
+    if _CRF_LOGZ_FN:
+        return _CRF_LOGZ_FN[0]
+    import torch
+
+    class CrfLogZ(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, scores, lengths):
+            # (zeroed: the kernel does not write rows at and beyond a read's length, and the gradient there is 0)
+            marg, _, logz, status = _crf_marginals_torch(scores.detach(), lengths, "source", False, False, zeroed=lengths is not None)
+            ctx.save_for_backward(marg, status)
+            ctx.scores_dtype = scores.dtype
+            return logz
+
+        @staticmethod
+        def backward(ctx, grad_logz):
+            marg, status = ctx.saved_tensors
+            g = grad_logz.to(torch.float32)[:, None, None, None] * marg
+            g = torch.where((status != 0)[:, None, None, None], torch.full_like(g, float("nan")), g)  # (selected on the device)
+            return g.to(ctx.scores_dtype), None
+
+    _CRF_LOGZ_FN.append(CrfLogZ.apply)
+    return CrfLogZ.apply
+
+
+def crf_logz(scores, lengths=None):
+    """(B,T,S,N) raw CRF scores, a torch ROCm tensor (float32 / float16 / bfloat16, any non-negative strides) in the
+    "source" layout -> logz (B,) float64, differentiable: the denominator of CRF-CTC training.  Its backward pass is
+    grad_out[:, None, None, None] * marginals (crf_marginals_batch_raw) in the dtype of `scores` -- the forward call has
+    already computed them, in the same kernel launch; rows at and beyond lengths[b] get gradient 0, a failed read (logz
+    NaN) a NaN gradient.  Nothing synchronises.  Out of scope: the "dest" layout, and the numerator of a training loss (a
+    labelling's own score and its gradient)."""
+    if not _is_torch_cuda(scores):
+        raise TypeError("crf_logz takes a torch ROCm tensor")
+    if scores.ndim != 4:
+        raise TypeError("expected a tensor of rank 4")
+    return _crf_logz_function()(scores, lengths)
+
+
 _DEFAULT_LOGADD = [nat.LOGADD_LOGSUMEXP]
 
 

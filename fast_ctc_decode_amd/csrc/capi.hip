@@ -1345,6 +1345,108 @@ int fcd_crf_transition_probs_host(fcd_handle *h, const fcd_batch *scores, int la
     return st.fetch();
 }
 
+// ---- CRF edge marginals (viterbi.hip): the transition walk into the caller's buffer and the forward pass over it ----
+namespace {
+int64_t marginals_span(const fcd_batch *in, const fcd_marginals *out) {  // elements of marg the call may write
+    if (in->n_reads == 0 || in->T == 0) return 0;
+    return (in->n_reads - 1) * out->stride_read + (in->T - 1) * out->stride_t + in->S * in->N;
+}
+
+int64_t emit_span(const fcd_batch *in, const fcd_marginals *out) {
+    if (in->n_reads == 0 || in->T == 0 || !out->emit) return 0;
+    return (in->n_reads - 1) * out->emit_stride + in->T * in->N;
+}
+
+int crf_marginals_check(fcd_handle *h, const fcd_batch *in, int layout, const fcd_marginals *out) {
+    int rc = check_batch(h, in, true);
+    if (rc) return rc;
+    if (!out) return fail(h, FCD_E_INVALID, "null marginals");
+    if (layout != FCD_LAYOUT_SOURCE && layout != FCD_LAYOUT_DEST) return fail(h, FCD_E_INVALID, "unknown score layout");
+    if (in->stride_read < 0 || in->stride_t < 0 || in->stride_s < 0 || in->stride_n < 0)
+        return fail(h, FCD_E_INVALID, "negative stride");
+    switch (crf_transitions_unsupported(in->S, in->N)) {
+    case 1: return fail(h, FCD_E_UNSUPPORTED, "crf_marginals: N must be in 2 .. 9");
+    case 2: return fail(h, FCD_E_UNSUPPORTED, "crf_marginals: S must be a multiple of N - 1 (symbol j + 1 moves state s to "
+                                              "(s (N - 1)) mod S + j)");
+    case 3: return fail(h, FCD_E_UNSUPPORTED, "crf_marginals: S must be below 2^24");
+    case 4: return fail(h, FCD_E_UNSUPPORTED, "crf_marginals: 8 S + 4608 bytes of occupancy rows and staging do not fit the 160 KiB of LDS");
+    default: break;
+    }
+    if (in->n_reads == 0) return FCD_OK;
+    if ((in->T > 0 && !out->marg) || !out->status) return fail(h, FCD_E_INVALID, "null marg/status");
+    if (out->stride_read < in->S * in->N || out->stride_t < in->S * in->N)
+        return fail(h, FCD_E_INVALID, "stride_read and stride_t of the marginals must be at least S N");
+    if (out->emit && out->emit_stride < in->T * in->N) return fail(h, FCD_E_INVALID, "emit_stride must be at least T N");
+    return FCD_OK;
+}
+
+int crf_marginals_run(fcd_handle *h, const fcd_batch *in, int layout, const fcd_marginals *out) {
+    const size_t B = (size_t)in->n_reads;
+    CallScope sc(h);
+    sc.add(out->marg, (size_t)marginals_span(in, out) * 4);
+    sc.add(out->emit, (size_t)emit_span(in, out) * 4);
+    sc.add(out->logz, B * 8);
+    sc.add(out->status, B * 4);
+    int rc = sc.begin(false, true);  // (behind every overlapping call in flight: one of them may be writing the scores)
+    if (rc) return rc;
+    TransitionsDesc d;
+    d.probs = out->marg;
+    d.dtype = FCD_DTYPE_F32;
+    d.layout = layout;
+    d.stride_read = out->stride_read;
+    d.stride_t = out->stride_t;
+    d.init = nullptr;  // (the init row stays in LDS)
+    d.init_stride = 0;
+    d.logz = out->logz;
+    d.status = out->status;
+    sc.time();
+    FCD_HIP(h, launch_crf_marginals(to_desc(in, true), d, out->emit, out->emit_stride, sc.stream));
+    return sc.finish();
+}
+}  // namespace
+
+int fcd_crf_marginals_dev(fcd_handle *h, const fcd_batch *scores, int layout, const fcd_marginals *out) {
+    if (!h) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> g(h->mu);
+    int rc = crf_marginals_check(h, scores, layout, out);
+    if (rc) return rc;
+    if (scores->n_reads == 0) return FCD_OK;
+    FCD_DEVICE(h);
+    return crf_marginals_run(h, scores, layout, out);
+}
+
+// host arrays: staged in the order scores, lengths, the outputs; marg and emit travel both ways (rows t >= T_r are not written)
+int fcd_crf_marginals_host(fcd_handle *h, const fcd_batch *scores, int layout, const fcd_marginals *out) {
+    if (!h) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> whole_call(h->mu);  // staging .. copy-back, see run_host
+    int rc = crf_marginals_check(h, scores, layout, out);
+    if (rc) return rc;
+    const fcd_batch *in = scores;
+    if (in->n_reads == 0) return FCD_OK;
+    FCD_DEVICE(h);
+    const size_t B = (size_t)in->n_reads;
+    Staging st(h);
+    const int i_x = st.in(in->post, (size_t)span_elems(in, true) * (in->dtype == FCD_DTYPE_F32 ? 4 : 2));
+    const int i_len = st.in(in->lengths, B * 8);
+    const int i_marg = st.inout(out->marg, (size_t)marginals_span(in, out) * 4);
+    const int i_emit = st.inout(out->emit, (size_t)emit_span(in, out) * 4);
+    const int i_logz = st.out(out->logz, B * 8);
+    const int i_stat = st.out(out->status, B * 4);
+    rc = st.commit();
+    if (rc) return rc;
+    fcd_batch din = *in;
+    din.post = st.at<char>(i_x);
+    din.lengths = st.at<int64_t>(i_len);
+    fcd_marginals dout = *out;
+    dout.marg = st.at<float>(i_marg);
+    dout.emit = st.at<float>(i_emit);
+    dout.logz = st.at<double>(i_logz);
+    dout.status = st.at<int32_t>(i_stat);
+    rc = crf_marginals_run(h, &din, layout, &dout);
+    if (rc) return rc;
+    return st.fetch();
+}
+
 namespace {
 struct CrfInit {
     const float *init1 = nullptr, *init2 = nullptr;

@@ -169,6 +169,11 @@ struct TransitionsDesc {
 };
 int crf_transitions_unsupported(int64_t S, int64_t N);
 hipError_t launch_crf_transitions(const BatchDesc &in, const TransitionsDesc &out, hipStream_t stream);
+// CRF edge marginals (fcd_crf_marginals_* in include/fcd.h): the transition walk with out.probs the marginals' f32 buffer and
+// out.init null, then the forward pass over that buffer in the same launch (mode 3).  emit [n_reads * emit_stride] is
+// nullable.  The limits are crf_transitions_unsupported's.
+hipError_t launch_crf_marginals(const BatchDesc &in, const TransitionsDesc &out, float *emit, int64_t emit_stride,
+                                hipStream_t stream, int mode = 3);
 
 // duplex::beam_search (src/duplex.rs:443-650) launch arguments; all pointers are device memory.
 struct DuplexArgs {

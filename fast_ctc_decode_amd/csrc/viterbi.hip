@@ -478,12 +478,16 @@ __global__ __launch_bounds__(256) void viterbi_tm_kernel(BatchDesc in, int colla
 // to the front once their number is known -- no second pass over the posteriors.
 struct VitArgs {
     int mode;               // 0: crf_greedy_search's walk (every launch of launch_crf_greedy); 1: the Viterbi walk;
-                            // 2: the transition-probability walk (crf_transitions_walk)
-    int lds_bytes;          // dynamic LDS of the launch (modes 1 and 2)
+                            // 2: the transition-probability walk (crf_transitions_walk); 3: that walk, then the forward
+                            // pass over what it stored (crf_marginals_forward)
+    int lds_bytes;          // dynamic LDS of the launch (modes 1, 2 and 3)
     double *logp;           // [n_reads], nullable
     unsigned char *bp;      // back-pointers: bp_read_bytes per read, row t and state s at [t * S + s]
     int64_t bp_read_bytes;
-    TransitionsDesc tr;     // mode 2: the outputs and the input's layout
+    TransitionsDesc tr;     // modes 2 and 3: the outputs and the input's layout (mode 3: probs is the marginals' buffer,
+                            // f32, and init is null -- the init row stays in LDS)
+    float *emit;            // mode 3: [n_reads * emit_stride], (T, N) dense per read, nullable
+    int64_t emit_stride;
 };
 
 constexpr int kVitMaxN = 9;
@@ -825,7 +829,9 @@ __device__ __forceinline__ float wave_fmax(float x) {  // of values that are not
     return __int_as_float(b);
 }
 
-__device__ __forceinline__ void crf_transitions_walk(const BatchDesc &in, const VitArgs &va, float *lds) {
+// -> whether the read failed (wave-uniform).  A null o.init (the marginals, mode 3) leaves the init row in LDS instead, over
+// beta~_0 at lds[0 .. S): every lane overwrites only the states it has just read.
+__device__ __forceinline__ bool crf_transitions_walk(const BatchDesc &in, const VitArgs &va, float *lds) {
     const int lane = threadIdx.x;
     const int64_t r = blockIdx.x;
     int64_t T = in.T;
@@ -1009,24 +1015,203 @@ __device__ __forceinline__ void crf_transitions_walk(const BatchDesc &in, const 
     for (int s = lane; s < S; s += kWave) zs += FCD_TR_EXP(b0[s] - cprev);
     for (int m = 1; m < kWave; m <<= 1) zs += __shfl_xor(zs, m);
     const bool failed = ballot(badx) != 0ull || no_path;
-    float *init = o.init + r * o.init_stride;
+    float *init = o.init ? o.init + r * o.init_stride : lds;
     for (int s = lane; s < S; s += kWave) init[s] = FCD_TR_EXP(b0[s] - cprev) / zs;
     if (lane == 0) {
         o.status[r] = failed ? FCD_ST_INCOMPARABLE : FCD_ST_OK;
         if (o.logz) o.logz[r] = failed ? (double)NAN : csum + log((double)zs);
     }
+    return failed;
+}
+
+// ---- CRF edge marginals over all labellings (fcd_crf_marginals_*; include/fcd.h has the definition) ----
+// NOT a reference function.  The forward half behind crf_transitions_walk, which has left p[t][s][a] in the marginals' buffer
+// (f32, the walk's own storage) and the init row in LDS.  (p, init) is the model restated as a Markov chain, so the forward
+// pass is a propagation of state occupancies without exp or ln:
+//     pi_0 = init;  marg[t][s][a] = pi_t[s] p[t][s][a];  pi_{t+1}[s'] = marg[t][s'][0] + sum_i marg[t][s_i][j + 1]
+// with s_i = s' div nb + i (S / nb), j = s' mod nb, the sum taken in that order, left to right, from the stay term on.
+// One wavefront per read, front to back, every row multiplied in place.  Rows of at most 64 elements: a lane per element,
+// pi_t[s] in a register of every lane of state s, the products meeting through a double-buffered LDS row.  Larger rows: a
+// lane per DESTINATION state s', 64 at a time, which gathers p[t][s'][0] and the nb elements p[t][s_i][j + 1] (s_i N + j + 1
+// = (s' div nb) N + j + 1 + i (S / nb) N: for consecutive s' the advances of one i are consecutive elements but for the
+// stay column), pi in two LDS rows of S floats.  (s', i) -> element is a bijection onto the row, so every element is loaded,
+// multiplied and stored exactly once, BY THE SAME LANE: a lane's store follows its own load of that element in program
+// order, and no other lane touches it, so a row's loads are consumed before it is overwritten without any further fence;
+// the loads running ahead (kTrAhead rows, kTrRows chunks) are of other elements.  That leaves the stores scattered rather
+// than staged: N runs per chunk, the advance runs dense but for every N-th element.
+// emit[t][a] = sum_s marg[t][s][a]: through the LDS row with a lane per element; with a lane per state, lane-private LDS
+// accumulators per advance column (the column a lane serves changes from chunk to chunk) and one shuffle reduction a row.
+__device__ __forceinline__ void crf_marginals_forward(const BatchDesc &in, const VitArgs &va, float *lds) {
+    const int lane = threadIdx.x;
+    const int64_t r = blockIdx.x;
+    int64_t T = in.T;
+    if (in.lengths) {
+        int64_t t = in.lengths[r];
+        T = t < 0 ? 0 : (t < T ? t : T);
+    }
+    const int Tr = (int)T;
+    const int N = in.N, S = in.S, nb = N - 1, q = S / nb;
+    const TransitionsDesc &o = va.tr;
+    float *mg = reinterpret_cast<float *>(o.probs) + r * o.stride_read;
+    float *em = va.emit ? va.emit + r * va.emit_stride : nullptr;
+    float *pi = lds, *stage = lds + 2 * (size_t)S;
+    const int E = S * N;
+
+    if (E <= kWave) {  // ---- a lane per element e = s N + a ----
+        const bool act = lane < E;
+        const int e = act ? lane : 0, s = e / N;
+        const int hi = s / nb, j = s - hi * nb;
+        float pv = pi[s];  // pi_t[s]
+        float ring[kTrAhead];
+#pragma unroll
+        for (int u = 0; u < kTrAhead; ++u) ring[u] = (act && u < Tr) ? mg[(int64_t)u * o.stride_t + e] : 0.0f;
+        int par = 0;
+        for (int k0 = 0; k0 < Tr; k0 += kTrAhead) {
+#pragma unroll
+            for (int u = 0; u < kTrAhead; ++u) {
+                const int t = k0 + u;
+                if (t >= Tr) break;
+                const float m = pv * ring[u];
+                if (act && t + kTrAhead < Tr) ring[u] = mg[(int64_t)(t + kTrAhead) * o.stride_t + e];
+                float *sg = stage + par * kTrStage;
+                if (act) {
+                    mg[(int64_t)t * o.stride_t + e] = m;
+                    sg[e] = m;
+                }
+                vit_lds_sync();
+                float nx = sg[s * N];
+                for (int i = 0; i < nb; ++i) nx += sg[(hi + i * q) * N + j + 1];
+                pv = nx;
+                if (em && lane < N) {
+                    float z = 0.0f;
+                    for (int k = 0; k < S; ++k) z += sg[k * N + lane];
+                    em[(int64_t)t * N + lane] = z;
+                }
+                par ^= 1;  // (row t + 2 writes this buffer again behind row t + 1's barrier: every lane has read it by then)
+            }
+        }
+        return;
+    }
+
+    // ---- a lane per destination state, 64 states (a chunk) at a time; the items (row, chunk) in the order they are walked ----
+    const int nchunk = (S + kWave - 1) / kWave;
+    // state s' = h nb + j: it is entered from h + i q by symbol j + 1
+    const int h0 = lane / nb, j0 = lane - h0 * nb, steph = kWave / nb, stepj = kWave - steph * nb;
+    const int qn = q * N;
+    struct Cur {
+        int t, c, s, h, j;
+    };
+    auto cur_next = [&](Cur &k) {
+        if (++k.c == nchunk) {
+            k.c = 0;
+            ++k.t;
+            k.s = lane;
+            k.h = h0;
+            k.j = j0;
+        } else {
+            k.s += kWave;
+            k.h += steph;
+            k.j += stepj;
+            if (k.j >= nb) {
+                k.j -= nb;
+                ++k.h;
+            }
+        }
+    };
+    auto load_row = [&](const Cur &k, float (&p)[kVitMaxN]) {
+#pragma unroll
+        for (int i = 0; i < kVitMaxN; ++i) p[i] = 0.0f;
+        if (k.t >= Tr || k.s >= S) return;
+        const float *row = mg + (int64_t)k.t * o.stride_t;
+        const float *adv = row + (k.h * N + k.j + 1);
+        p[0] = row[k.s * N];
+#pragma unroll
+        for (int i = 1; i < kVitMaxN; ++i)
+            if (i < N) p[i] = adv[(i - 1) * qn];
+    };
+    Cur lc{0, 0, lane, h0, j0}, cc = lc;
+    float ring[kTrRows][kVitMaxN];
+#pragma unroll
+    for (int u = 0; u < kTrRows; ++u) {
+        load_row(lc, ring[u]);
+        cur_next(lc);
+    }
+    float *acc = stage + lane;  // advance column j + 1 of the row so far: acc[j * kWave], this lane's own
+    if (em)
+        for (int i = 0; i < nb; ++i) acc[i * kWave] = 0.0f;
+    float e0 = 0.0f;  // the stay column
+    const int64_t items = (int64_t)Tr * nchunk;
+    for (int64_t k0 = 0; k0 < items; k0 += kTrRows) {
+#pragma unroll
+        for (int u = 0; u < kTrRows; ++u) {
+            if (k0 + u >= items) break;
+            float m[kVitMaxN];
+#pragma unroll
+            for (int i = 0; i < kVitMaxN; ++i) m[i] = ring[u][i];
+            load_row(lc, ring[u]);
+            cur_next(lc);
+            if (cc.s < S) {
+                const float *pt = pi + (size_t)(cc.t & 1) * S;
+                float *row = mg + (int64_t)cc.t * o.stride_t;
+                float *adv = row + (cc.h * N + cc.j + 1);
+                m[0] *= pt[cc.s];
+                row[cc.s * N] = m[0];
+                float nx = m[0], sa = 0.0f;
+#pragma unroll
+                for (int i = 1; i < kVitMaxN; ++i) {
+                    if (i >= N) break;
+                    m[i] *= pt[cc.h + (i - 1) * q];
+                    adv[(i - 1) * qn] = m[i];
+                    nx += m[i];
+                    sa += m[i];
+                }
+                pi[(size_t)((cc.t + 1) & 1) * S + cc.s] = nx;
+                if (em) {
+                    e0 += m[0];
+                    acc[cc.j * kWave] += sa;
+                }
+            }
+            if (cc.c == nchunk - 1) {  // the row is complete
+                if (em) {
+                    float mine = 0.0f;  // lane a ends up with column a
+                    for (int m2 = 1; m2 < kWave; m2 <<= 1) e0 += __shfl_xor(e0, m2);
+                    if (lane == 0) mine = e0;
+                    e0 = 0.0f;
+                    for (int i = 0; i < nb; ++i) {
+                        float v = acc[i * kWave];
+                        acc[i * kWave] = 0.0f;
+                        for (int m2 = 1; m2 < kWave; m2 <<= 1) v += __shfl_xor(v, m2);
+                        if (lane == i + 1) mine = v;
+                    }
+                    if (lane < N) em[(int64_t)cc.t * N + lane] = mine;
+                }
+                vit_lds_sync();  // pi_{t+1} is in place before row t + 1 reads it; its other row is free to be written
+            }
+            cur_next(cc);
+        }
+    }
 }
 
 // crf_greedy_search (:385-423): the state walk is a serial dependency; one wave per read,
 // lanes 0..N-1 hold the current state's row and reduce it with a first-maximum argmax.
-// va.mode (wave-uniform) = 1: the Viterbi walk above instead, 2: the transition-probability walk -- the launches with
-// dynamic LDS.
+// va.mode (wave-uniform) = 1: the Viterbi walk above instead, 2: the transition-probability walk, 3: that walk and the
+// marginals' forward pass behind it -- the launches with dynamic LDS.
 __global__ __launch_bounds__(64) void crf_greedy_kernel(BatchDesc in, const float *init_all,
                                                       int64_t n_init, int64_t init_stride,
                                                       ResultDesc out, VitArgs va) {
     extern __shared__ __attribute__((aligned(16))) float s_vit[];
-    if (va.mode == 2) {
-        crf_transitions_walk(in, va, s_vit);
+    if (va.mode >= 2) {
+        const bool failed = crf_transitions_walk(in, va, s_vit);
+        if (va.mode == 3 && !failed) {
+            // The forward pass reads p back from the marginals' buffer: global memory that OTHER lanes of this wavefront
+            // stored (the backward pass stores a chunk's elements as contiguous runs across lanes, the forward pass gathers
+            // them by destination state).  The release fence at device scope makes every lane's stores visible beyond the
+            // lane before any lane passes the wave barrier, the acquire fence behind it keeps the loads below from being
+            // served by anything older.  The init row in LDS needs the same between lanes at wavefront scope.
+            vit_global_sync();
+            vit_lds_sync();
+            crf_marginals_forward(in, va, s_vit);
+        }
         return;
     }
     if (va.mode) {
@@ -1562,11 +1747,19 @@ int crf_transitions_unsupported(int64_t S, int64_t N) {
 }
 
 hipError_t launch_crf_transitions(const BatchDesc &in, const TransitionsDesc &out, hipStream_t stream) {
+    return launch_crf_marginals(in, out, nullptr, 0, stream, 2);
+}
+
+// mode 3: out.probs is the marginals' buffer (f32), out.init null; mode 2 (launch_crf_transitions): emit unused
+hipError_t launch_crf_marginals(const BatchDesc &in, const TransitionsDesc &out, float *emit, int64_t emit_stride,
+                                hipStream_t stream, int mode) {
     if (in.n_reads <= 0) return hipSuccess;
     VitArgs va{};
-    va.mode = 2;
+    va.mode = mode;
     va.lds_bytes = (int)crf_transitions_lds_bytes(in.S);
     va.tr = out;
+    va.emit = emit;
+    va.emit_stride = emit_stride;
 #ifndef FCD_HIPEMU
     if (va.lds_bytes > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(crf_greedy_kernel),

@@ -785,6 +785,51 @@ typedef struct fcd_transitions {
 int fcd_crf_transition_probs_dev(fcd_handle *h, const fcd_batch *scores, int layout, const fcd_transitions *out);
 int fcd_crf_transition_probs_host(fcd_handle *h, const fcd_batch *scores, int layout, const fcd_transitions *out);
 
+/* ---- CRF edge marginals over all labellings: the forward pass behind fcd_crf_transition_probs_*, logZ and its gradient ----
+ * NOT a reference function.  How probable it is, over every labelling, that the model takes transition a out of state s at
+ * row t: the true posterior of an emission (the searches' qualities are the local conditional p[t][s][a], which ignores how
+ * likely the model is to be in s at all), summed over states a (T, N) matrix of label posteriors whose rows sum to 1, and
+ * exactly d logZ / d x, the denominator gradient of CRF-CTC training.
+ * Input: `scores` and `layout` as fcd_crf_transition_probs_* take them; x, nb, d(s, a), beta and logZ as defined there.  Every
+ * start state is allowed.  Per read:
+ *     alpha_0[s]      = 0
+ *     alpha_{t+1}[s'] = ln sum_{(s, a): d(s, a) = s'} exp(alpha_t[s] + x[t][s][a])
+ *     marg[t][s][a]   = exp(alpha_t[s] + x[t][s][a] + beta_{t+1}[d(s, a)] - logZ)      source-indexed, as probs is
+ *     emit[t][a]      = sum_s marg[t][s][a]
+ * Identities: sum_{s, a} marg[t] = 1 for every row t < T_r; sum_a marg[t][s][a] = exp(alpha_t[s] + beta_t[s] - logZ), the
+ * state occupancy; marg = d logZ / d x.
+ * Output (fcd_marginals):
+ *   marg   f32, element (r, t, s, a) at marg[r stride_read + t stride_t + s N + a]: dense (S, N) rows, the caller's read and
+ *          row strides in elements, as fcd_transitions.probs.  Required: it is the walk's own storage -- the backward pass
+ *          writes p into it, the forward pass multiplies it in place; there is no workspace.  Rows t >= T_r are not written.
+ *   emit   f32, nullable: element (r, t, a) at emit[r emit_stride + t N + a], emit_stride >= T N.  Rows t >= T_r are not
+ *          written.
+ *   logz   float64 per read, nullable: fcd_crf_transition_probs_*'s value, bit for bit;  status  FCD_ST_* per read.
+ * Arithmetic (f32; executable specification: tests/crf_marginals_reference.py): (p, init) of fcd_crf_transition_probs_* is the
+ * model restated as a Markov chain, so the forward pass propagates state occupancies and needs no exp or ln:
+ *     pi_0 = init;  marg[t][s][a] = pi_t[s] p[t][s][a];  pi_{t+1}[s'] = marg[t][s'][0] + sum_{i = 0 .. nb-1} marg[t][s_i][j + 1]
+ * with s_i = s' div nb + i (S / nb), j = s' mod nb, the sum taken left to right in that order from the stay term on.  emit is
+ * summed in f32 in an unspecified order.
+ * Edge cases: x = -inf gives marg exactly 0.  A failed read (fcd_crf_transition_probs_*'s rule) has FCD_ST_INCOMPARABLE, logz
+ * NaN, marg and emit unspecified; the other reads are unaffected.  T_r = 0: FCD_ST_OK, logz = ln S, nothing else written.
+ * Limits: those of fcd_crf_transition_probs_*, the LDS included (8 S + 4608 bytes per read).
+ * _dev is enqueue-only on the handle's stream, one kernel launch, ordered behind every overlapping call in flight; _host
+ * stages host arrays (marg and emit travel both ways: rows t >= T_r keep the caller's content).
+ * FCD_E_INVALID: null scores / out / marg / status, an unknown layout, stride_read or stride_t below S N, emit_stride below
+ * T N.  Out of scope: f16 marginals, marginals without the (T, S, N) buffer, the numerator of a training loss. */
+typedef struct fcd_marginals {
+    float *marg;
+    int64_t stride_read;
+    int64_t stride_t;
+    float *emit;         /* nullable */
+    int64_t emit_stride;
+    double *logz;        /* nullable */
+    int32_t *status;
+} fcd_marginals;
+
+int fcd_crf_marginals_dev(fcd_handle *h, const fcd_batch *scores, int layout, const fcd_marginals *out);
+int fcd_crf_marginals_host(fcd_handle *h, const fcd_batch *scores, int layout, const fcd_marginals *out);
+
 /* ---- duplex::beam_search (src/duplex.rs:443-650) ----
  * (Two kernels serve the duplex searches since round 6, with identical results: the slot-resident one --
  * csrc/duplex_slots.hip -- wherever beam_size * N <= 64 and the live nodes' windows fit the LDS, the any-shape one --
