@@ -1138,7 +1138,7 @@ int fcd_crf_greedy_search_dev(fcd_handle *h, const fcd_batch *in, const float *i
     return sc.finish();
 }
 
-// ---- the Viterbi search under a CRF model (viterbi.hip): the best state path over all labellings ----
+// ---- the Viterbi search under a CRF model (crf_viterbi.hip): the best state path over all labellings ----
 namespace {
 int crf_viterbi_check(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init, int64_t init_stride,
                       const fcd_result *out) {
@@ -1244,7 +1244,7 @@ int fcd_crf_viterbi_search_host(fcd_handle *h, const fcd_batch *in, const float 
     return st.fetch();
 }
 
-// ---- CRF transition probabilities from raw scores (viterbi.hip): the (posteriors, init) pair of the CRF entry points ----
+// ---- CRF transition probabilities from raw scores (crf_transitions.hip): the (posteriors, init) pair of the CRF entry points ----
 namespace {
 int64_t transitions_span(const fcd_batch *in, const fcd_transitions *out) {  // elements of probs the call may write
     if (in->n_reads == 0 || in->T == 0) return 0;
@@ -1345,7 +1345,7 @@ int fcd_crf_transition_probs_host(fcd_handle *h, const fcd_batch *scores, int la
     return st.fetch();
 }
 
-// ---- CRF edge marginals (viterbi.hip): the transition walk into the caller's buffer and the forward pass over it ----
+// ---- CRF edge marginals (crf_transitions.hip): the transition walk into the caller's buffer and the forward pass over it ----
 namespace {
 int64_t marginals_span(const fcd_batch *in, const fcd_marginals *out) {  // elements of marg the call may write
     if (in->n_reads == 0 || in->T == 0) return 0;

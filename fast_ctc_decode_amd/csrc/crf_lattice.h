@@ -205,7 +205,7 @@ struct CrfStep {
     int lo, hi;
 };
 
-// (crf_split: device_utils.h, shared with the CRF Viterbi search of viterbi.hip)
+// (crf_split: device_utils.h, shared with the CRF Viterbi search of crf_viterbi.hip)
 
 template <int K>
 __device__ __forceinline__ CrfStep<K> crf_load_step(const CrfParams &p, const CrfLds &lds, const CrfRow &rw, int t, int i,

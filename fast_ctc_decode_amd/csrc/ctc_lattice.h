@@ -158,7 +158,7 @@ __device__ __forceinline__ void window(const ScoreParams &p, const Lds &lds, con
     window_k(p, rw, t, p.band > 0 ? lds.krow[i] : 0, lo, hi);
 }
 
-// (finite_exp and wave_imax: device_utils.h, shared with the CRF Viterbi search of viterbi.hip)
+// (finite_exp and wave_imax: device_utils.h, shared with the CRF Viterbi search of crf_viterbi.hip)
 
 __device__ __forceinline__ float from_prev_lane(float x) {  // wave_ror:1 -- lane l receives lane (l - 1) & 63
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x13C, 0xf, 0xf, false));

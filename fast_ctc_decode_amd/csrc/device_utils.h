@@ -307,7 +307,7 @@ __device__ __forceinline__ bool lane_in(uint64_t m, int lane) {
 #endif
 
 // ---- f32 with an unbounded exponent: what the lattice walks (ctc_lattice.h, crf_lattice.h) and the CRF Viterbi search
-// (viterbi.hip) share.  A row's cells are f32 values times one power of two per row; the row's largest exponent is reduced
+// (crf_viterbi.hip) share.  A row's cells are f32 values times one power of two per row; the row's largest exponent is reduced
 // as an integer and every cell rescaled exactly.
 constexpr int kTarget = 120;          // the row maximum is kept in [2^119, 2^120): three of them sum below 2^127
 constexpr int kNoExp = -(1 << 24);    // "exponent" of a cell that takes no part in the row maximum (0, inf, NaN)
@@ -337,6 +337,59 @@ __device__ __forceinline__ void crf_split(float v, float *m, int *e) {
     if (v - v == 0.0f) mm = frexpf(v, &ex);  // (finite; an infinity or a NaN stays what it is, exponent 0)
     *m = mm;
     *e = ex;
+}
+
+__device__ __forceinline__ float wave_fmax(float x) {  // of values that are not NaN: through the order-preserving integer
+    int b = __float_as_int(x);
+    b ^= (b >> 31) & 0x7fffffff;
+    b = wave_imax(b);
+    b ^= (b >> 31) & 0x7fffffff;
+    return __int_as_float(b);
+}
+
+// ---- what the one-wavefront-per-read CRF walks share (viterbi.hip's crf_greedy_kernel, crf_viterbi.hip, crf_transitions.hip)
+constexpr int kVitMaxN = 9;  // labels of a state that the Viterbi, transition and marginal walks hold in registers
+
+__device__ __forceinline__ void vit_lds_sync() {  // LDS written by one lane, read by another, same wavefront
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ __forceinline__ void vit_global_sync() {  // global memory written by one lane, read by another
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+}
+
+// rows of read r: the batch's T, clamped by the read's own length where the batch has lengths
+__device__ __forceinline__ int64_t read_rows(int64_t T, const int64_t *lengths, int64_t r) {
+    if (lengths) {
+        int64_t t = lengths[r];
+        T = t < 0 ? 0 : (t < T ? t : T);
+    }
+    return T;
+}
+
+// init_state.argmax() (src/search.rs:399): the first maximum of an init row; *bad: the row is empty or holds a NaN (the
+// reference panics)
+__device__ __forceinline__ int init_first_max(const float *init, int64_t n_init, bool *bad_out) {
+    int state = 0;
+    bool bad = n_init <= 0;
+    if (!bad) {
+        float m = init[0];
+        bad = m != m;
+        for (int64_t j = 1; j < n_init && !bad; ++j) {
+            const float e = init[j];
+            if (e != e) bad = true;
+            if (e > m) {
+                m = e;
+                state = (int)j;
+            }
+        }
+    }
+    *bad_out = bad;
+    return state;
 }
 
 }  // namespace fcd

@@ -145,16 +145,24 @@ hipError_t launch_viterbi(const BatchDesc &in, int collapse, const ResultDesc &o
 hipError_t launch_crf_greedy(const BatchDesc &in, const float *init, int64_t n_init,
                              int64_t init_stride, const ResultDesc &out, hipStream_t stream);
 
-// The Viterbi search under a CRF model (fcd_crf_viterbi_search_* in include/fcd.h; the walk lives in viterbi.hip, inside
-// crf_greedy_kernel).  crf_viterbi_unsupported: 0 supported, 1 N outside 2 .. 9, 2 S no multiple of N - 1, 3 S beyond the
+// A kernel launched with more than 64 KiB of dynamic LDS has to be opted in first; below that there is nothing to do.
+inline hipError_t allow_dynamic_lds(const void *kernel, int bytes) {
+#ifndef FCD_HIPEMU  // (lockstep emulation, tests/hipemu: the LDS is host memory)
+    if (bytes > 64 * 1024) return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+#endif
+    return hipSuccess;
+}
+
+// The Viterbi search under a CRF model (fcd_crf_viterbi_search_* in include/fcd.h; crf_viterbi_kernel,
+// crf_viterbi.hip).  crf_viterbi_unsupported: 0 supported, 1 N outside 2 .. 9, 2 S no multiple of N - 1, 3 S beyond the
 // state word, 4 the state and candidate arrays beyond the LDS of a CU.  bp: crf_viterbi_read_bytes(T, S) bytes per read.
 int crf_viterbi_unsupported(int64_t S, int64_t N);
 size_t crf_viterbi_read_bytes(int64_t T, int64_t S);
 hipError_t launch_crf_viterbi(const BatchDesc &in, const float *init, int64_t n_init, int64_t init_stride,
                               const ResultDesc &out, double *logp, unsigned char *bp, hipStream_t stream);
 
-// CRF transition probabilities from raw scores (fcd_crf_transition_probs_* in include/fcd.h; the walk lives in viterbi.hip,
-// inside crf_greedy_kernel).  `in` holds the scores; everything here is device memory.  crf_transitions_unsupported:
+// CRF transition probabilities from raw scores (fcd_crf_transition_probs_* in include/fcd.h; crf_transitions_kernel,
+// crf_transitions.hip).  `in` holds the scores; everything here is device memory.  crf_transitions_unsupported:
 // 0 supported, 1 N outside 2 .. 9, 2 S no multiple of N - 1, 3 S beyond the state word, 4 the two rows of the backward
 // vector and the store staging beyond the LDS of a CU.
 struct TransitionsDesc {
@@ -169,11 +177,11 @@ struct TransitionsDesc {
 };
 int crf_transitions_unsupported(int64_t S, int64_t N);
 hipError_t launch_crf_transitions(const BatchDesc &in, const TransitionsDesc &out, hipStream_t stream);
-// CRF edge marginals (fcd_crf_marginals_* in include/fcd.h): the transition walk with out.probs the marginals' f32 buffer and
-// out.init null, then the forward pass over that buffer in the same launch (mode 3).  emit [n_reads * emit_stride] is
-// nullable.  The limits are crf_transitions_unsupported's.
+// CRF edge marginals (fcd_crf_marginals_* in include/fcd.h; crf_marginals_kernel, crf_transitions.hip): the transition walk
+// with out.probs the marginals' f32 buffer and out.init null, then the forward pass over that buffer in the same launch.
+// emit [n_reads * emit_stride] is nullable.  The limits are crf_transitions_unsupported's.
 hipError_t launch_crf_marginals(const BatchDesc &in, const TransitionsDesc &out, float *emit, int64_t emit_stride,
-                                hipStream_t stream, int mode = 3);
+                                hipStream_t stream);
 
 // duplex::beam_search (src/duplex.rs:443-650) launch arguments; all pointers are device memory.
 struct DuplexArgs {

@@ -10,8 +10,6 @@
 // following row per iteration.
 #include <math.h>
 
-#include <algorithm>
-
 #include "device_utils.h"
 #include "fcd_internal.h"
 
@@ -458,766 +456,11 @@ __global__ __launch_bounds__(256) void viterbi_tm_kernel(BatchDesc in, int colla
     }
 }
 
-// ---- the Viterbi search under a CRF model (fcd_crf_viterbi_search_*; include/fcd.h has the definition) ----
-// NOT a reference function: the exact, unpruned decode over all labellings -- the single most probable path through the
-// model's states, of which crf_greedy_search (:385-423) follows the locally best one.
-//
-// One wavefront per read, all S states live: v[s] is the best probability of any path that leaves state s behind after
-// the row, in LDS.  Per row the wavefront reads the S * N posteriors (S * N <= 64: a lane per element; beyond: lane l the
-// N posteriors of states l, l + 64, ..., consecutive lanes consecutive states), forms each product with its state's v, and
-// leaves the stay products in v[s] and writes the nb = N - 1 advance products to c[s * nb + j]; then lane l settles states
-// l, l + 64, ...  (v[s] is overwritten only once its readers are done: with a lane per element every lane reads v[s] before
-// the wave maximum and stores after it; with a lane per state a state's v[s] is read and written by its own lane only.)  The state s' that source s reaches with label j + 1 is (s nb) mod S + j
-// (:97,414), so c[s nb + j] = c[s' + i S] with i = (s nb) div S: destination s' reads c[s' + i S], i = 0 .. nb-1 -- both
-// sides contiguous across lanes, no cross-lane shuffle.  The LDS is the wavefront's own: a wait on its counter orders it.
-// Arithmetic: crf_lattice.hip's -- posteriors split into mantissa and exponent, ONE f32 product per candidate, every
-// cell rescaled by an exact power of two per row (the row's largest exponent is known to within one from the operands'
-// exponents, before any product is formed), ln(m) + E ln 2 in float64.
-// Back-pointers: one byte per state and row in the caller's workspace (0 stay, i + 1 advance i); the wavefront walks them
-// back after the last row, 64 emissions at a time in registers, written to the END of the read's output rows and moved
-// to the front once their number is known -- no second pass over the posteriors.
-struct VitArgs {
-    int mode;               // 0: crf_greedy_search's walk (every launch of launch_crf_greedy); 1: the Viterbi walk;
-                            // 2: the transition-probability walk (crf_transitions_walk); 3: that walk, then the forward
-                            // pass over what it stored (crf_marginals_forward)
-    int lds_bytes;          // dynamic LDS of the launch (modes 1, 2 and 3)
-    double *logp;           // [n_reads], nullable
-    unsigned char *bp;      // back-pointers: bp_read_bytes per read, row t and state s at [t * S + s]
-    int64_t bp_read_bytes;
-    TransitionsDesc tr;     // modes 2 and 3: the outputs and the input's layout (mode 3: probs is the marginals' buffer,
-                            // f32, and init is null -- the init row stays in LDS)
-    float *emit;            // mode 3: [n_reads * emit_stride], (T, N) dense per read, nullable
-    int64_t emit_stride;
-};
-
-constexpr int kVitMaxN = 9;
-constexpr int kVitMinLds = 4096;  // the traceback's chunk of back-pointers reuses the LDS: at least this much of it
-constexpr int kVitAhead = 4;      // S * N <= 64: rows whose loads are in flight
-
-__device__ __forceinline__ void vit_lds_sync() {  // LDS written by one lane, read by another, same wavefront
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ void vit_global_sync() {  // global memory written by one lane, read by another
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-}
-
-__device__ __forceinline__ void crf_viterbi_walk(const BatchDesc &in, const float *init_all, int64_t n_init,
-                                                 int64_t init_stride, const ResultDesc &out, const VitArgs &va,
-                                                 float *lds) {
-    const int lane = threadIdx.x;
-    const int64_t r = blockIdx.x;
-    int64_t T = in.T;
-    if (in.lengths) {
-        int64_t t = in.lengths[r];
-        T = t < 0 ? 0 : (t < T ? t : T);
-    }
-    const int Tr = (int)T;
-    const int N = in.N, S = in.S, nb = N - 1;
-    const int dt = in.dtype;
-    const float *post = post_at(in.post, r * in.stride_read, dt);
-    uint8_t *lab = out.labels + r * out.out_stride;
-    uint32_t *pth = out.path ? out.path + r * out.out_stride : nullptr;
-    float *qual = out.qual ? out.qual + r * out.out_stride : nullptr;
-
-    // sigma_0: the first maximum of the init row, as crf_greedy_search takes it (:399)
-    const float *init = init_all + r * init_stride;
-    int state = 0;
-    bool bad = n_init <= 0;
-    if (!bad) {
-        float m = init[0];
-        bad = m != m;
-        for (int64_t j = 1; j < n_init && !bad; ++j) {
-            const float e = init[j];
-            if (e != e) bad = true;
-            if (e > m) {
-                m = e;
-                state = (int)j;
-            }
-        }
-    }
-    if (bad || Tr == 0 || state >= S) {  // (an init row no state follows from; no rows: the empty path, probability 1)
-        const bool ok = !bad && Tr == 0;
-        if (lane == 0) {
-            out.out_len[r] = 0u;
-            out.status[r] = ok ? FCD_ST_OK : FCD_ST_BAD_STATE;
-            if (va.logp) va.logp[r] = ok ? 0.0 : (double)NAN;
-        }
-        return;
-    }
-
-    float *v = lds, *c = lds + S;
-    for (int s = lane; s < S; s += kWave) v[s] = s == state ? 1.0f : 0.0f;  // "row -1"
-    vit_lds_sync();
-    unsigned char *bp = va.bp + r * va.bp_read_bytes;
-    int64_t eacc = 0;  // the cells are v * 2^eacc
-    bool nan = false;
-    // A row of at most 64 elements is walked by ELEMENT: lane e takes element e = s N + j of the S * N row, so a small table
-    // still fills its lanes (S = 4, N = 5: 20 lanes with one product each, not 4 lanes with five).
-    const int E = S * N;
-    const uint32_t recip_n = 0xFFFFFFFFu / (uint32_t)N + 1u;  // e div N = (e * recip_n) >> 32 for e < 2^24
-    auto load_elem = [&](int t, int e) {
-        const int s = (int)(((uint64_t)(uint32_t)e * recip_n) >> 32), j = e - s * N;
-        return load_post(post, (int64_t)t * in.stride_t + (int64_t)s * in.stride_s + (int64_t)j * in.stride_n, dt);
-    };
-    // the largest exponent the product can have (it has that or one less); a NaN anywhere in the row is remembered
-    auto bound_of = [&](float a, float p) {
-        nan = nan || (p != p);
-        const int ea = finite_exp(a), ep = finite_exp(p);
-        return (ea != kNoExp && ep != kNoExp) ? ea + ep : kNoExp;
-    };
-    // the product, rescaled: the stay candidate of state s, or advance j - 1 at c[s * nb + j - 1]
-    auto spread = [&](int e, float a, float p, int sh) {
-        const int s = (int)(((uint64_t)(uint32_t)e * recip_n) >> 32), j = e - s * N;
-        float m;
-        int ex;
-        crf_split(p, &m, &ex);
-        const float val = ldexpf(a * m, min(max(ex + sh, -512), 512));
-        if (j == 0) v[s] = val;  // (the stay candidate takes v[s]'s place: its readers are done, see above)
-        else c[s * nb + (j - 1)] = val;
-    };
-    auto state_of = [&](int e) { return (int)(((uint64_t)(uint32_t)e * recip_n) >> 32); };
-    // destination s: the stay candidate is kept unless an advance is strictly greater, the lowest i among equals
-    auto settle = [&](int t) {
-        for (int s = lane; s < S; s += kWave) {
-            float best = v[s];
-            int b = 0;
-            for (int i = 0; i < nb; ++i) {
-                const float cand = c[s + i * S];
-                if (cand > best) {
-                    best = cand;
-                    b = i + 1;
-                }
-            }
-            v[s] = best;
-            bp[(int64_t)t * S + s] = (unsigned char)b;
-        }
-    };
-    auto shift_of = [&](int eb) {  // the row's power of two from its largest exponent bound
-        const int sh = eb == kNoExp ? 0 : kTarget - eb;
-        eacc -= sh;
-        return sh;
-    };
-
-    if (E <= kWave) {  // one element per lane, its posteriors of the next kVitAhead rows in flight
-        const bool act = lane < E;
-        const int e = act ? lane : 0, s = state_of(e);
-        float ring[kVitAhead];
-#pragma unroll
-        for (int u = 0; u < kVitAhead; ++u) ring[u] = (act && u < Tr) ? load_elem(u, e) : 0.0f;
-        for (int t0 = 0; t0 < Tr; t0 += kVitAhead) {
-#pragma unroll
-            for (int u = 0; u < kVitAhead; ++u) {
-                const int t = t0 + u;
-                if (t >= Tr) break;
-                const float p = ring[u];
-                if (act && t + kVitAhead < Tr) ring[u] = load_elem(t + kVitAhead, e);
-                const float a = act ? v[s] : 0.0f;
-                const int sh = shift_of(wave_imax(act ? bound_of(a, p) : kNoExp));
-                if (act) spread(e, a, p, sh);
-                vit_lds_sync();
-                settle(t);
-                vit_lds_sync();
-            }
-        }
-    } else {
-        // Larger rows are walked by STATE: lane l takes states l, l + 64, ... and forms a state's N products from one read
-        // of v[s], the label a compile-time index (consecutive lanes still read consecutive states of the row).
-        auto load_row = [&](int t, int s, float (&p)[kVitMaxN]) {
-            const float *pr = post_at(post, (int64_t)t * in.stride_t + (int64_t)s * in.stride_s, dt);
-#pragma unroll
-            for (int j = 0; j < kVitMaxN; ++j) p[j] = j < N ? load_post(pr, (int64_t)j * in.stride_n, dt) : 0.0f;
-        };
-        auto bound_row = [&](float a, const float (&p)[kVitMaxN]) {
-            float pm = p[0];
-            bool n = p[0] != p[0];
-#pragma unroll
-            for (int j = 1; j < kVitMaxN; ++j) {
-                n = n || (p[j] != p[j]);
-                pm = fmaxf(pm, p[j]);  // (the padding is 0.0: it moves no maximum that matters)
-            }
-            nan = nan || n;
-            const int ea = finite_exp(a), ep = finite_exp(pm);
-            return (ea != kNoExp && ep != kNoExp) ? ea + ep : kNoExp;
-        };
-        auto spread_row = [&](int s, float a, const float (&p)[kVitMaxN], int sh) {
-#pragma unroll
-            for (int j = 0; j < kVitMaxN; ++j) {
-                if (j >= N) break;
-                float m;
-                int ex;
-                crf_split(p[j], &m, &ex);
-                const float val = ldexpf(a * m, min(max(ex + sh, -512), 512));
-                if (j == 0) v[s] = val;  // (the stay candidate takes v[s]'s place: its readers are done, see above)
-                else c[s * nb + (j - 1)] = val;
-            }
-        };
-        if (S <= kWave) {  // one state per lane: its row in registers, the next row's loads in flight
-            const bool act = lane < S;
-            const int s = act ? lane : 0;
-            float cur[kVitMaxN], nxt[kVitMaxN];
-#pragma unroll
-            for (int j = 0; j < kVitMaxN; ++j) cur[j] = nxt[j] = 0.0f;
-            if (act) load_row(0, s, cur);
-            for (int t = 0; t < Tr; ++t) {
-                if (act && t + 1 < Tr) load_row(t + 1, s, nxt);
-                const float a = act ? v[s] : 0.0f;
-                const int sh = shift_of(wave_imax(act ? bound_row(a, cur) : kNoExp));
-                if (act) spread_row(s, a, cur, sh);
-                vit_lds_sync();
-                settle(t);
-                vit_lds_sync();
-#pragma unroll
-                for (int j = 0; j < kVitMaxN; ++j) cur[j] = nxt[j];
-            }
-        } else {  // S / 64 states per lane: the row is read twice (the second time from the cache), once per pass
-            for (int t = 0; t < Tr; ++t) {
-                int eb = kNoExp;
-                for (int s = lane; s < S; s += kWave) {
-                    float p[kVitMaxN];
-                    load_row(t, s, p);
-                    eb = max(eb, bound_row(v[s], p));
-                }
-                const int sh = shift_of(wave_imax(eb));
-                for (int s = lane; s < S; s += kWave) {
-                    float p[kVitMaxN];
-                    load_row(t, s, p);
-                    spread_row(s, v[s], p, sh);
-                }
-                vit_lds_sync();
-                settle(t);
-                vit_lds_sync();
-            }
-        }
-    }
-
-    // the end state: the first maximum of the last row
-    float bv = 0.0f;
-    int bi = 0x7fffffff;
-    for (int s = lane; s < S; s += kWave) {
-        const float x = v[s];
-        if (bi == 0x7fffffff || x > bv) {
-            bv = x;
-            bi = s;
-        }
-    }
-    for (int m = 1; m < kWave; m <<= 1) {
-        const float ov = __shfl_xor(bv, m);
-        const int oi = __shfl_xor(bi, m);
-        if (oi != 0x7fffffff && (bi == 0x7fffffff || ov > bv || (ov == bv && oi < bi))) {
-            bv = ov;
-            bi = oi;
-        }
-    }
-    if (ballot(nan) != 0ull) {  // every value of a read enters a live cell: no comparison orders a NaN
-        if (lane == 0) {
-            out.out_len[r] = 0u;
-            out.status[r] = FCD_ST_INCOMPARABLE;
-            if (va.logp) va.logp[r] = (double)NAN;
-        }
-        return;
-    }
-    int be = 0;
-    const double bm = frexp((double)bv, &be);  // ln(m) + E ln 2 with m in [0.5, 1)
-    const double logp = log(bm) + (double)(eacc + be) * 0.693147180559945309417232121458;
-
-    // ---- the walk back: chunks of whole rows of back-pointers through the LDS, every lane follows the one path ----
-    vit_global_sync();  // the back-pointers other lanes stored
-    unsigned char *sb = reinterpret_cast<unsigned char *>(lds);
-    uint32_t *sw = reinterpret_cast<uint32_t *>(lds);
-    const int rows_per_chunk = max(1, (va.lds_bytes - 8) / S);
-    const uint32_t recip = nb > 1 ? 0xFFFFFFFFu / (uint32_t)nb + 1u : 0u;  // s div nb = (s * recip) >> 32 for s < 2^24
-    const int q = S / nb;
-    int s = bi, k = 0;  // k: emissions found so far, the last one first; lane k mod 64 holds emission k
-    uint8_t my_lab = 0;
-    uint32_t my_row = 0;
-    float my_q = 0.0f;
-    auto flush = [&](int k0, int n) {  // emissions k0 .. k0 + n - 1 to the end of the rows: k lands at Tr - 1 - k
-        if (lane < n) {
-            const int at = Tr - 1 - (k0 + lane);
-            lab[at] = my_lab;
-            if (pth) pth[at] = my_row;
-            if (qual) qual[at] = my_q;
-        }
-    };
-    for (int c0 = (Tr - 1) / rows_per_chunk * rows_per_chunk; c0 >= 0; c0 -= rows_per_chunk) {
-        const int n = min(rows_per_chunk, Tr - c0);
-        const int64_t b0 = (int64_t)c0 * S, w0 = b0 & ~(int64_t)3;  // (whole words: a read's rows start 256-byte aligned)
-        const int n_words = (int)((b0 + (int64_t)n * S - w0 + 3) >> 2);
-        vit_lds_sync();  // the LDS's previous readers are done
-        for (int e = lane; e < n_words; e += kWave) sw[e] = reinterpret_cast<const uint32_t *>(bp + w0)[e];
-        vit_lds_sync();
-        const int skew = (int)(b0 - w0);
-        for (int i = n - 1; i >= 0; --i) {
-            const int b = __builtin_amdgcn_readfirstlane((int)sb[skew + i * S + s]);
-            if (b == 0) continue;
-            const int sd = nb > 1 ? (int)(((uint64_t)(uint32_t)s * recip) >> 32) : s;
-            const int j = s - sd * nb, src = sd + (b - 1) * q;
-            if ((k & 63) == lane) {
-                my_lab = (uint8_t)(j + 1);
-                my_row = (uint32_t)(c0 + i);
-                if (qual)
-                    my_q = load_post(post, (int64_t)(c0 + i) * in.stride_t + (int64_t)src * in.stride_s + (int64_t)(j + 1) * in.stride_n, dt);
-            }
-            s = src;
-            if ((++k & 63) == 0) flush(k - 64, 64);
-        }
-    }
-    if (k & 63) flush(k & ~63, k & 63);
-    // to the front, 64 at a time: every lane's load before any lane's store (the ranges overlap)
-    const int shift = Tr - k;
-    if (shift > 0 && k > 0) {
-        vit_global_sync();
-        for (int base = 0; base < k; base += kWave) {
-            const int i = base + lane;
-            const bool mine = i < k;
-            const uint8_t l = mine ? lab[i + shift] : (uint8_t)0;
-            const uint32_t p = (mine && pth) ? pth[i + shift] : 0u;
-            const float g = (mine && qual) ? qual[i + shift] : 0.0f;
-            __builtin_amdgcn_wave_barrier();
-            if (mine) {
-                lab[i] = l;
-                if (pth) pth[i] = p;
-                if (qual) qual[i] = g;
-            }
-            __builtin_amdgcn_wave_barrier();
-        }
-    }
-    if (lane == 0) {
-        out.out_len[r] = (uint32_t)k;
-        out.status[r] = FCD_ST_OK;
-        if (va.logp) va.logp[r] = logp;
-    }
-}
-
-// ---- CRF transition probabilities from raw scores (fcd_crf_transition_probs_*; include/fcd.h has the definition) ----
-// NOT a reference function: the step in front of every CRF entry point -- a backward pass over all labellings and a local
-// softmax, which turns a network's unnormalised log scores x into the (posteriors, init) pair the searches read.
-//
-// One wavefront per read, back to front.  The backward vector lives in LDS, two rows of S floats (row t is written while
-// row t + 1 is read) and is never stored.  A row is kept UNNORMALISED as it is written; its maximum c_t, a wave reduction,
-// is subtracted where the next row reads it (beta~[d] = beta[d] - c_t, the same f32 subtraction either way), and summed
-// in float64 for logZ.  Per state: y_a = x_a + beta~[d(s, a)], d(s, 0) = s, d(s, j + 1) = (s nb) mod S + j -- the nb advance
-// destinations are nb consecutive states --, m = max y, e_a = exp(y_a - m), the sum in the order a = 0 .. N - 1,
-// p_a = e_a / sum, beta = m + ln sum; a state whose candidates are all -inf is dead (p = 0, beta = -inf).
-// A row of at most 64 elements takes a lane per element (the candidates of a state meet through LDS; the store is one
-// contiguous run); larger rows a lane per state, 64 states at a time, whose 64 N probabilities are parked in LDS and
-// stored as contiguous runs across lanes.  Loads run ahead of the dependent chain: kTrAhead rows with a lane per element,
-// kTrRows chunks of 64 states with a lane per state (a chunk is N registers per lane).
-// Scores indexed by the state being ENTERED (FCD_LAYOUT_DEST) are a different offset per element at load time, nothing more.
-constexpr int kTrAhead = 4;
-constexpr int kTrRows = 2;
-constexpr int kTrStage = kWave * kVitMaxN;  // floats of one staging buffer: the probabilities of 64 states
-
-#ifdef FCD_HIPEMU  // (lockstep emulation, tests/hipemu: the plain libm forms)
-#define FCD_TR_EXP(x) expf(x)
-#define FCD_TR_LOG(x) logf(x)
-#else
-#define FCD_TR_EXP(x) __expf(x)
-#define FCD_TR_LOG(x) __logf(x)
-#endif
-
-__device__ __forceinline__ float wave_fmax(float x) {  // of values that are not NaN: through the order-preserving integer
-    int b = __float_as_int(x);
-    b ^= (b >> 31) & 0x7fffffff;
-    b = wave_imax(b);
-    b ^= (b >> 31) & 0x7fffffff;
-    return __int_as_float(b);
-}
-
-// -> whether the read failed (wave-uniform).  A null o.init (the marginals, mode 3) leaves the init row in LDS instead, over
-// beta~_0 at lds[0 .. S): every lane overwrites only the states it has just read.
-__device__ __forceinline__ bool crf_transitions_walk(const BatchDesc &in, const VitArgs &va, float *lds) {
-    const int lane = threadIdx.x;
-    const int64_t r = blockIdx.x;
-    int64_t T = in.T;
-    if (in.lengths) {
-        int64_t t = in.lengths[r];
-        T = t < 0 ? 0 : (t < T ? t : T);
-    }
-    const int Tr = (int)T;
-    const int N = in.N, S = in.S, nb = N - 1, q = S / nb;
-    const int dt = in.dtype;
-    const TransitionsDesc &o = va.tr;
-    const bool dest = o.layout != 0, half_out = o.dtype == kF16;
-    const float *x = post_at(in.post, r * in.stride_read, dt);
-    float *pf = reinterpret_cast<float *>(o.probs) + (half_out ? 0 : r * o.stride_read);
-    uint16_t *ph = reinterpret_cast<uint16_t *>(o.probs) + (half_out ? r * o.stride_read : 0);
-    auto store_p = [&](int64_t off, float v) {
-        if (half_out) ph[off] = f32_to_f16_bits(v);
-        else pf[off] = v;
-    };
-    float *beta = lds, *stage = lds + 2 * (size_t)S;
-
-    for (int s = lane; s < S; s += kWave) beta[(size_t)(Tr & 1) * S + s] = 0.0f;  // beta~_T = 0
-    vit_lds_sync();
-    float cprev = 0.0f;     // the maximum of the row being read, not yet subtracted from it
-    double csum = 0.0;      // of the row maxima
-    bool badx = false;      // this lane met a NaN or +inf
-    bool no_path = false;   // a row without a live state (wave-uniform)
-    const int E = S * N;
-
-    if (E <= kWave) {  // ---- a lane per element e = s N + a ----
-        const bool act = lane < E;
-        const int e = act ? lane : 0, s = e / N, a = e - s * N;
-        const int sq = s / q, d = a == 0 ? s : (s - sq * q) * nb + a - 1;
-        const int64_t xoff = a == 0 ? (int64_t)s * in.stride_s
-                             : dest ? (int64_t)d * in.stride_s + (int64_t)(1 + sq) * in.stride_n
-                                    : (int64_t)s * in.stride_s + (int64_t)a * in.stride_n;
-        float ring[kTrAhead];
-#pragma unroll
-        for (int u = 0; u < kTrAhead; ++u)
-            ring[u] = (act && u < Tr) ? load_post(x, (int64_t)(Tr - 1 - u) * in.stride_t + xoff, dt) : 0.0f;
-        for (int k0 = 0; k0 < Tr; k0 += kTrAhead) {
-#pragma unroll
-            for (int u = 0; u < kTrAhead; ++u) {
-                const int t = Tr - 1 - (k0 + u);
-                if (t < 0) break;
-                const float xv = ring[u];
-                if (act && t - kTrAhead >= 0) ring[u] = load_post(x, (int64_t)(t - kTrAhead) * in.stride_t + xoff, dt);
-                badx = badx || !(xv < INFINITY);
-                const float *bn = beta + (size_t)((t + 1) & 1) * S;
-                const float y = xv + (bn[d] - cprev);
-                if (act) stage[e] = y;
-                vit_lds_sync();
-                const float *ys = stage + s * N;
-                float m = ys[0];
-                for (int j = 1; j < N; ++j) m = fmaxf(m, ys[j]);
-                const bool live = m > -INFINITY;
-                float sum = 0.0f;
-                for (int j = 0; j < N; ++j) sum += live ? FCD_TR_EXP(ys[j] - m) : 0.0f;
-                const float p = live ? FCD_TR_EXP(y - m) / sum : 0.0f;
-                const float b = live ? m + FCD_TR_LOG(sum) : -INFINITY;
-                if (act) store_p((int64_t)t * o.stride_t + e, p);
-                if (act && a == 0) beta[(size_t)(t & 1) * S + s] = b;
-                const float c = wave_fmax(act ? b : -INFINITY);
-                no_path = no_path || !(c > -INFINITY);
-                csum += (double)c;
-                cprev = c;
-                vit_lds_sync();
-            }
-        }
-    } else {  // ---- a lane per state, 64 states (a chunk) at a time; the items (row, chunk) in the order they are walked ----
-        const int nchunk = (S + kWave - 1) / kWave;
-        // state s = sq q + rq: its advances enter rq nb .. rq nb + nb - 1, and a `dest` input holds them in column 1 + sq
-        const int sq0 = lane / q, rq0 = lane - sq0 * q, stepq = kWave / q, stepr = kWave - stepq * q;
-        struct Cur {
-            int t, c, s, rq, sq;
-        };
-        auto cur_next = [&](Cur &k) {
-            if (++k.c == nchunk) {
-                k.c = 0;
-                --k.t;
-                k.s = lane;
-                k.rq = rq0;
-                k.sq = sq0;
-            } else {
-                k.s += kWave;
-                k.rq += stepr;
-                k.sq += stepq;
-                if (k.rq >= q) {
-                    k.rq -= q;
-                    ++k.sq;
-                }
-            }
-        };
-        auto load_row = [&](const Cur &k, float (&p)[kVitMaxN]) {
-#pragma unroll
-            for (int j = 0; j < kVitMaxN; ++j) p[j] = 0.0f;
-            if (k.t < 0 || k.s >= S) return;
-            const int64_t row = (int64_t)k.t * in.stride_t, o0 = row + (int64_t)k.s * in.stride_s;
-            const int64_t o1 = dest ? row + (int64_t)(k.rq * nb) * in.stride_s + (int64_t)(1 + k.sq) * in.stride_n : o0 + in.stride_n;
-            const int64_t da = dest ? in.stride_s : in.stride_n;
-            p[0] = load_post(x, o0, dt);
-#pragma unroll
-            for (int j = 1; j < kVitMaxN; ++j)
-                if (j < N) p[j] = load_post(x, o1 + (int64_t)(j - 1) * da, dt);
-        };
-        Cur lc{Tr - 1, 0, lane, rq0, sq0}, cc = lc;
-        float ring[kTrRows][kVitMaxN];
-#pragma unroll
-        for (int u = 0; u < kTrRows; ++u) {
-            load_row(lc, ring[u]);
-            cur_next(lc);
-        }
-        const int64_t items = (int64_t)Tr * nchunk;
-        float lmax = -INFINITY;  // this lane's largest beta of the row so far
-        int par = 0;             // staging buffer of the item
-        for (int64_t k0 = 0; k0 < items; k0 += kTrRows) {
-#pragma unroll
-            for (int u = 0; u < kTrRows; ++u) {
-                if (k0 + u >= items) break;
-                float y[kVitMaxN];
-#pragma unroll
-                for (int j = 0; j < kVitMaxN; ++j) y[j] = ring[u][j];
-                load_row(lc, ring[u]);
-                cur_next(lc);
-                const bool act = cc.s < S;
-                const int s = act ? cc.s : 0, base = act ? cc.rq * nb : 0;
-                const float *bn = beta + (size_t)((cc.t + 1) & 1) * S;
-                float *st = stage + par * kTrStage + lane * N;
-#pragma unroll
-                for (int j = 0; j < kVitMaxN; ++j) {
-                    if (j >= N) break;
-                    badx = badx || !(y[j] < INFINITY);
-                    y[j] += bn[j == 0 ? s : base + j - 1] - cprev;
-                }
-                float m = y[0];
-#pragma unroll
-                for (int j = 1; j < kVitMaxN; ++j) {
-                    if (j >= N) break;
-                    m = fmaxf(m, y[j]);
-                }
-                const bool live = m > -INFINITY;
-                float sum = 0.0f;
-#pragma unroll
-                for (int j = 0; j < kVitMaxN; ++j) {
-                    if (j >= N) break;
-                    y[j] = live ? FCD_TR_EXP(y[j] - m) : 0.0f;
-                    sum += y[j];
-                }
-                const float b = live ? m + FCD_TR_LOG(sum) : -INFINITY;
-                if (act) {
-                    beta[(size_t)(cc.t & 1) * S + s] = b;
-                    lmax = fmaxf(lmax, b);
-#pragma unroll
-                    for (int j = 0; j < kVitMaxN; ++j) {
-                        if (j >= N) break;
-                        st[j] = live ? y[j] / sum : 0.0f;
-                    }
-                }
-                if (cc.c == nchunk - 1) {  // the row is complete: its maximum
-                    const float c = wave_fmax(lmax);
-                    no_path = no_path || !(c > -INFINITY);
-                    csum += (double)c;
-                    cprev = c;
-                    lmax = -INFINITY;
-                }
-                vit_lds_sync();
-                // the chunk's probabilities, contiguous across lanes
-                const int s0 = cc.c * kWave, n_el = min(kWave, S - s0) * N;
-                const int64_t o0 = (int64_t)cc.t * o.stride_t + (int64_t)s0 * N;
-                const float *sp = stage + par * kTrStage;
-                for (int el = lane; el < n_el; el += kWave) store_p(o0 + el, sp[el]);
-                par ^= 1;
-                cur_next(cc);
-            }
-        }
-    }
-
-    // init[s] = exp(beta~_0[s]) / sum_s exp(beta~_0[s]); logZ = sum_t c_t + ln of that sum
-    const float *b0 = beta;
-    float zs = 0.0f;
-    for (int s = lane; s < S; s += kWave) zs += FCD_TR_EXP(b0[s] - cprev);
-    for (int m = 1; m < kWave; m <<= 1) zs += __shfl_xor(zs, m);
-    const bool failed = ballot(badx) != 0ull || no_path;
-    float *init = o.init ? o.init + r * o.init_stride : lds;
-    for (int s = lane; s < S; s += kWave) init[s] = FCD_TR_EXP(b0[s] - cprev) / zs;
-    if (lane == 0) {
-        o.status[r] = failed ? FCD_ST_INCOMPARABLE : FCD_ST_OK;
-        if (o.logz) o.logz[r] = failed ? (double)NAN : csum + log((double)zs);
-    }
-    return failed;
-}
-
-// ---- CRF edge marginals over all labellings (fcd_crf_marginals_*; include/fcd.h has the definition) ----
-// NOT a reference function.  The forward half behind crf_transitions_walk, which has left p[t][s][a] in the marginals' buffer
-// (f32, the walk's own storage) and the init row in LDS.  (p, init) is the model restated as a Markov chain, so the forward
-// pass is a propagation of state occupancies without exp or ln:
-//     pi_0 = init;  marg[t][s][a] = pi_t[s] p[t][s][a];  pi_{t+1}[s'] = marg[t][s'][0] + sum_i marg[t][s_i][j + 1]
-// with s_i = s' div nb + i (S / nb), j = s' mod nb, the sum taken in that order, left to right, from the stay term on.
-// One wavefront per read, front to back, every row multiplied in place.  Rows of at most 64 elements: a lane per element,
-// pi_t[s] in a register of every lane of state s, the products meeting through a double-buffered LDS row.  Larger rows: a
-// lane per DESTINATION state s', 64 at a time, which gathers p[t][s'][0] and the nb elements p[t][s_i][j + 1] (s_i N + j + 1
-// = (s' div nb) N + j + 1 + i (S / nb) N: for consecutive s' the advances of one i are consecutive elements but for the
-// stay column), pi in two LDS rows of S floats.  (s', i) -> element is a bijection onto the row, so every element is loaded,
-// multiplied and stored exactly once, BY THE SAME LANE: a lane's store follows its own load of that element in program
-// order, and no other lane touches it, so a row's loads are consumed before it is overwritten without any further fence;
-// the loads running ahead (kTrAhead rows, kTrRows chunks) are of other elements.  That leaves the stores scattered rather
-// than staged: N runs per chunk, the advance runs dense but for every N-th element.
-// emit[t][a] = sum_s marg[t][s][a]: through the LDS row with a lane per element; with a lane per state, lane-private LDS
-// accumulators per advance column (the column a lane serves changes from chunk to chunk) and one shuffle reduction a row.
-__device__ __forceinline__ void crf_marginals_forward(const BatchDesc &in, const VitArgs &va, float *lds) {
-    const int lane = threadIdx.x;
-    const int64_t r = blockIdx.x;
-    int64_t T = in.T;
-    if (in.lengths) {
-        int64_t t = in.lengths[r];
-        T = t < 0 ? 0 : (t < T ? t : T);
-    }
-    const int Tr = (int)T;
-    const int N = in.N, S = in.S, nb = N - 1, q = S / nb;
-    const TransitionsDesc &o = va.tr;
-    float *mg = reinterpret_cast<float *>(o.probs) + r * o.stride_read;
-    float *em = va.emit ? va.emit + r * va.emit_stride : nullptr;
-    float *pi = lds, *stage = lds + 2 * (size_t)S;
-    const int E = S * N;
-
-    if (E <= kWave) {  // ---- a lane per element e = s N + a ----
-        const bool act = lane < E;
-        const int e = act ? lane : 0, s = e / N;
-        const int hi = s / nb, j = s - hi * nb;
-        float pv = pi[s];  // pi_t[s]
-        float ring[kTrAhead];
-#pragma unroll
-        for (int u = 0; u < kTrAhead; ++u) ring[u] = (act && u < Tr) ? mg[(int64_t)u * o.stride_t + e] : 0.0f;
-        int par = 0;
-        for (int k0 = 0; k0 < Tr; k0 += kTrAhead) {
-#pragma unroll
-            for (int u = 0; u < kTrAhead; ++u) {
-                const int t = k0 + u;
-                if (t >= Tr) break;
-                const float m = pv * ring[u];
-                if (act && t + kTrAhead < Tr) ring[u] = mg[(int64_t)(t + kTrAhead) * o.stride_t + e];
-                float *sg = stage + par * kTrStage;
-                if (act) {
-                    mg[(int64_t)t * o.stride_t + e] = m;
-                    sg[e] = m;
-                }
-                vit_lds_sync();
-                float nx = sg[s * N];
-                for (int i = 0; i < nb; ++i) nx += sg[(hi + i * q) * N + j + 1];
-                pv = nx;
-                if (em && lane < N) {
-                    float z = 0.0f;
-                    for (int k = 0; k < S; ++k) z += sg[k * N + lane];
-                    em[(int64_t)t * N + lane] = z;
-                }
-                par ^= 1;  // (row t + 2 writes this buffer again behind row t + 1's barrier: every lane has read it by then)
-            }
-        }
-        return;
-    }
-
-    // ---- a lane per destination state, 64 states (a chunk) at a time; the items (row, chunk) in the order they are walked ----
-    const int nchunk = (S + kWave - 1) / kWave;
-    // state s' = h nb + j: it is entered from h + i q by symbol j + 1
-    const int h0 = lane / nb, j0 = lane - h0 * nb, steph = kWave / nb, stepj = kWave - steph * nb;
-    const int qn = q * N;
-    struct Cur {
-        int t, c, s, h, j;
-    };
-    auto cur_next = [&](Cur &k) {
-        if (++k.c == nchunk) {
-            k.c = 0;
-            ++k.t;
-            k.s = lane;
-            k.h = h0;
-            k.j = j0;
-        } else {
-            k.s += kWave;
-            k.h += steph;
-            k.j += stepj;
-            if (k.j >= nb) {
-                k.j -= nb;
-                ++k.h;
-            }
-        }
-    };
-    auto load_row = [&](const Cur &k, float (&p)[kVitMaxN]) {
-#pragma unroll
-        for (int i = 0; i < kVitMaxN; ++i) p[i] = 0.0f;
-        if (k.t >= Tr || k.s >= S) return;
-        const float *row = mg + (int64_t)k.t * o.stride_t;
-        const float *adv = row + (k.h * N + k.j + 1);
-        p[0] = row[k.s * N];
-#pragma unroll
-        for (int i = 1; i < kVitMaxN; ++i)
-            if (i < N) p[i] = adv[(i - 1) * qn];
-    };
-    Cur lc{0, 0, lane, h0, j0}, cc = lc;
-    float ring[kTrRows][kVitMaxN];
-#pragma unroll
-    for (int u = 0; u < kTrRows; ++u) {
-        load_row(lc, ring[u]);
-        cur_next(lc);
-    }
-    float *acc = stage + lane;  // advance column j + 1 of the row so far: acc[j * kWave], this lane's own
-    if (em)
-        for (int i = 0; i < nb; ++i) acc[i * kWave] = 0.0f;
-    float e0 = 0.0f;  // the stay column
-    const int64_t items = (int64_t)Tr * nchunk;
-    for (int64_t k0 = 0; k0 < items; k0 += kTrRows) {
-#pragma unroll
-        for (int u = 0; u < kTrRows; ++u) {
-            if (k0 + u >= items) break;
-            float m[kVitMaxN];
-#pragma unroll
-            for (int i = 0; i < kVitMaxN; ++i) m[i] = ring[u][i];
-            load_row(lc, ring[u]);
-            cur_next(lc);
-            if (cc.s < S) {
-                const float *pt = pi + (size_t)(cc.t & 1) * S;
-                float *row = mg + (int64_t)cc.t * o.stride_t;
-                float *adv = row + (cc.h * N + cc.j + 1);
-                m[0] *= pt[cc.s];
-                row[cc.s * N] = m[0];
-                float nx = m[0], sa = 0.0f;
-#pragma unroll
-                for (int i = 1; i < kVitMaxN; ++i) {
-                    if (i >= N) break;
-                    m[i] *= pt[cc.h + (i - 1) * q];
-                    adv[(i - 1) * qn] = m[i];
-                    nx += m[i];
-                    sa += m[i];
-                }
-                pi[(size_t)((cc.t + 1) & 1) * S + cc.s] = nx;
-                if (em) {
-                    e0 += m[0];
-                    acc[cc.j * kWave] += sa;
-                }
-            }
-            if (cc.c == nchunk - 1) {  // the row is complete
-                if (em) {
-                    float mine = 0.0f;  // lane a ends up with column a
-                    for (int m2 = 1; m2 < kWave; m2 <<= 1) e0 += __shfl_xor(e0, m2);
-                    if (lane == 0) mine = e0;
-                    e0 = 0.0f;
-                    for (int i = 0; i < nb; ++i) {
-                        float v = acc[i * kWave];
-                        acc[i * kWave] = 0.0f;
-                        for (int m2 = 1; m2 < kWave; m2 <<= 1) v += __shfl_xor(v, m2);
-                        if (lane == i + 1) mine = v;
-                    }
-                    if (lane < N) em[(int64_t)cc.t * N + lane] = mine;
-                }
-                vit_lds_sync();  // pi_{t+1} is in place before row t + 1 reads it; its other row is free to be written
-            }
-            cur_next(cc);
-        }
-    }
-}
-
 // crf_greedy_search (:385-423): the state walk is a serial dependency; one wave per read,
 // lanes 0..N-1 hold the current state's row and reduce it with a first-maximum argmax.
-// va.mode (wave-uniform) = 1: the Viterbi walk above instead, 2: the transition-probability walk, 3: that walk and the
-// marginals' forward pass behind it -- the launches with dynamic LDS.
 __global__ __launch_bounds__(64) void crf_greedy_kernel(BatchDesc in, const float *init_all,
                                                       int64_t n_init, int64_t init_stride,
-                                                      ResultDesc out, VitArgs va) {
-    extern __shared__ __attribute__((aligned(16))) float s_vit[];
-    if (va.mode >= 2) {
-        const bool failed = crf_transitions_walk(in, va, s_vit);
-        if (va.mode == 3 && !failed) {
-            // The forward pass reads p back from the marginals' buffer: global memory that OTHER lanes of this wavefront
-            // stored (the backward pass stores a chunk's elements as contiguous runs across lanes, the forward pass gathers
-            // them by destination state).  The release fence at device scope makes every lane's stores visible beyond the
-            // lane before any lane passes the wave barrier, the acquire fence behind it keeps the loads below from being
-            // served by anything older.  The init row in LDS needs the same between lanes at wavefront scope.
-            vit_global_sync();
-            vit_lds_sync();
-            crf_marginals_forward(in, va, s_vit);
-        }
-        return;
-    }
-    if (va.mode) {
-        crf_viterbi_walk(in, init_all, n_init, init_stride, out, va, s_vit);
-        return;
-    }
+                                                      ResultDesc out) {
     const int lane = threadIdx.x;
     const int64_t r = blockIdx.x;
     int64_t T = in.T;
@@ -1232,22 +475,8 @@ __global__ __launch_bounds__(64) void crf_greedy_kernel(BatchDesc in, const floa
     uint32_t *pth = out.path ? out.path + r * out.out_stride : nullptr;
     float *qual = out.qual ? out.qual + r * out.out_stride : nullptr;
 
-    // init_state.argmax() :399 (first maximum; NaN -> the reference panics)
-    const float *init = init_all + r * init_stride;
-    int state = 0;
-    bool bad = n_init <= 0;
-    if (!bad) {
-        float m = init[0];
-        bad = m != m;
-        for (int64_t j = 1; j < n_init && !bad; ++j) {
-            const float e = init[j];
-            if (e != e) bad = true;
-            if (e > m) {
-                m = e;
-                state = (int)j;
-            }
-        }
-    }
+    bool bad;
+    int state = init_first_max(init_all + r * init_stride, n_init, &bad);
     int n_out = 0;
     for (int64_t t = 0; t < T && !bad; ++t) {
         if (state < 0 || state >= S) {
@@ -1689,86 +918,7 @@ hipError_t launch_crf_greedy(const BatchDesc &in, const float *init, int64_t n_i
     out2.out_len = out.out_len + done;
     out2.status = out.status ? out.status + done : nullptr;
     hipLaunchKernelGGL(crf_greedy_kernel, dim3((unsigned)in2.n_reads), dim3(64), 0, stream, in2, init + done * init_stride,
-                       n_init, init_stride, out2, VitArgs{});
-    return hipGetLastError();
-}
-
-namespace {
-size_t crf_viterbi_lds_bytes(int64_t S, int64_t N) {  // v and c, and never less than the traceback's chunk wants
-    return std::max<size_t>((size_t)N * (size_t)S * 4, kVitMinLds);
-}
-}  // namespace
-
-int crf_viterbi_unsupported(int64_t S, int64_t N) {
-    if (N < 2 || N > kVitMaxN) return 1;
-    if (S % (N - 1) != 0) return 2;
-    if (S >= (1ll << 24)) return 3;
-    if (crf_viterbi_lds_bytes(S, N) > 160 * 1024) return 4;
-    return 0;
-}
-
-size_t crf_viterbi_read_bytes(int64_t T, int64_t S) {
-    return ((size_t)std::max<int64_t>(T, 1) * (size_t)S + 255) & ~(size_t)255;
-}
-
-hipError_t launch_crf_viterbi(const BatchDesc &in, const float *init, int64_t n_init, int64_t init_stride,
-                              const ResultDesc &out, double *logp, unsigned char *bp, hipStream_t stream) {
-    if (in.n_reads <= 0) return hipSuccess;
-    VitArgs va{};
-    va.mode = 1;
-    va.lds_bytes = (int)crf_viterbi_lds_bytes(in.S, in.N);
-    va.logp = logp;
-    va.bp = bp;
-    va.bp_read_bytes = (int64_t)crf_viterbi_read_bytes(in.T, in.S);
-#ifndef FCD_HIPEMU
-    if (va.lds_bytes > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(crf_greedy_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, va.lds_bytes);
-        if (e != hipSuccess) return e;
-    }
-#endif
-    hipLaunchKernelGGL(crf_greedy_kernel, dim3((unsigned)in.n_reads), dim3(64), (size_t)va.lds_bytes, stream, in, init, n_init,
-                       init_stride, out, va);
-    return hipGetLastError();
-}
-
-namespace {
-size_t crf_transitions_lds_bytes(int64_t S) {  // two rows of the backward vector, two staging buffers
-    return ((size_t)2 * (size_t)S + 2 * kTrStage) * 4;
-}
-}  // namespace
-
-int crf_transitions_unsupported(int64_t S, int64_t N) {
-    if (N < 2 || N > kVitMaxN) return 1;
-    if (S % (N - 1) != 0) return 2;
-    if (S >= (1ll << 24)) return 3;
-    if (crf_transitions_lds_bytes(S) > 160 * 1024) return 4;
-    return 0;
-}
-
-hipError_t launch_crf_transitions(const BatchDesc &in, const TransitionsDesc &out, hipStream_t stream) {
-    return launch_crf_marginals(in, out, nullptr, 0, stream, 2);
-}
-
-// mode 3: out.probs is the marginals' buffer (f32), out.init null; mode 2 (launch_crf_transitions): emit unused
-hipError_t launch_crf_marginals(const BatchDesc &in, const TransitionsDesc &out, float *emit, int64_t emit_stride,
-                                hipStream_t stream, int mode) {
-    if (in.n_reads <= 0) return hipSuccess;
-    VitArgs va{};
-    va.mode = mode;
-    va.lds_bytes = (int)crf_transitions_lds_bytes(in.S);
-    va.tr = out;
-    va.emit = emit;
-    va.emit_stride = emit_stride;
-#ifndef FCD_HIPEMU
-    if (va.lds_bytes > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(crf_greedy_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, va.lds_bytes);
-        if (e != hipSuccess) return e;
-    }
-#endif
-    hipLaunchKernelGGL(crf_greedy_kernel, dim3((unsigned)in.n_reads), dim3(64), (size_t)va.lds_bytes, stream, in,
-                       static_cast<const float *>(nullptr), (int64_t)0, (int64_t)0, ResultDesc{}, va);
+                       n_init, init_stride, out2);
     return hipGetLastError();
 }
 

@@ -1,5 +1,5 @@
 """TEST INFRASTRUCTURE: what fcd_crf_marginals_* computes (include/fcd.h), restated in numpy -- the specification the kernel
-(csrc/viterbi.hip, crf_transitions_walk and crf_marginals_forward inside crf_greedy_kernel) is held to.
+(csrc/crf_transitions.hip, crf_marginals_kernel) is held to.
 
   marginals64(x)     the alpha / beta definition as the header states it, in float64 log space: the reference of every check.
                      It never forms p or init.

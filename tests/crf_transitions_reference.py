@@ -1,5 +1,5 @@
 """TEST INFRASTRUCTURE: what fcd_crf_transition_probs_* computes (include/fcd.h), restated in numpy -- the specification
-the kernel (csrc/viterbi.hip, crf_transitions_walk) is held to.
+the kernel (csrc/crf_transitions.hip, crf_transitions_walk) is held to.
 
   transitions64(x)   the formulas as the header states them, in float64, no renormalisation: the reference of every check
   transitions32(x)   the stated ARITHMETIC in float32: beta renormalised by its row maximum at every step, per state

@@ -118,7 +118,7 @@ def run_case(fcd, c, device=None, cross=True):
         assert al.qual[b, 0, :n].view(np.uint32).tolist() == np.asarray(rc.qual[b, :n]).view(np.uint32).tolist(), where
         assert same_logp(float(al.logp[b, 0]), float(rc.logp[b])), where + (al.logp[b, 0], rc.logp[b])
         assert sc[b, 0] >= rc.logp[b] - CC.tolerance(Tr), (c["name"], b, "crf_score", sc[b, 0], rc.logp[b])
-    # crf_greedy_search (the kernel the walk lives in) on the same inputs: what it always returned
+    # crf_greedy_search on the same inputs: what it always returned
     if c["dtype"] != "bf16":
         g = fcd.crf_greedy_search_batch_raw(xin, init, lengths, qual=True).cpu()
         for b in range(c["B"]):

@@ -1,5 +1,5 @@
 """TEST INFRASTRUCTURE: what fcd_crf_viterbi_search_* computes (include/fcd.h), restated in numpy straight from the
-definition -- the specification the kernel (csrc/viterbi.hip, crf_viterbi_walk) is held to -- and a float64 enumeration of
+definition -- the specification the kernel (csrc/crf_viterbi.hip, crf_viterbi_kernel) is held to -- and a float64 enumeration of
 every label sequence of a tiny case.
 
 sigma_0 = the first maximum of the init row; v_{-1}[sigma_0] = 1.  For every state s' with j = s' mod nb, q = S / nb,

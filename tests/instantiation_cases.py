@@ -25,14 +25,15 @@ of their case files.
 The GPU cannot say which kernel ran, so the GPU twin relies on the emulator build choosing as the device build does.
 Every FCD_HIPEMU branch under csrc/:
   inside device code or declarations, where no launch is decided -- plain-C++ forms of instructions (device_utils.h:111,
-  :188, :200; duplex_math.h:122; duplex_slots.hip:142), the LDS address-space qualifier (pdq178_reg.h:30, :50;
+  :188, :200; duplex_math.h:122; duplex_slots.hip:142; crf_transitions.hip:30), the LDS address-space qualifier (pdq178_reg.h:30, :50;
   pdq178_wave.h:53, :59), <stdio.h> for the kernels' abort messages (beam_wave.hip:49, beam_lane.hip:29), the emulator's
   pass counters (duplex_slots.hip:183, :1129), the LDS-DMA prefetch left out (duplex_slots.hip:798), LDS and device memory
   made garbage as on the GPU (beam_lane.hip:179, :932; beam_wave_step.inc:643), the all-pairs switch of the lane kernel's
   node order (beam_lane.hip:690);
   in host code --
-    ctc_score.hip:232, ctc_align.hip:430   hipFuncSetAttribute for more than 64 KiB of dynamic LDS is skipped: the launch
-                                           that follows is the same score_lds_kernel / align_lds_kernel;
+    ctc_score.hip:232, ctc_align.hip:430, fcd_internal.h:150 (allow_dynamic_lds)
+                                           hipFuncSetAttribute for more than 64 KiB of dynamic LDS is skipped: the launch
+                                           that follows is the same kernel;
     tieorder.hip:68, beam_lane.hip:1113    the cycle counters of the profiling builds read back as zeros (fcd_debug.h);
     duplex_slots.hip:1508                  a statistics line on stderr after the launch;
     beam_lane.hip:1157                     beam_lane_resident_waves returns 3: it sizes the slab pool of the two-pass
@@ -377,7 +378,7 @@ def _viterbi_check(fcd, view, up, lengths, input_dtype):
                 assert [ord(c) for c in got] == list(quals), i
 
 
-# viterbi_stream_kernel<N, dtype>: launch_viterbi's stream_ok (viterbi.hip:813, :853): C-contiguous rows, reads on 16-byte
+# viterbi_stream_kernel<N, dtype>: launch_viterbi's stream_ok (viterbi.hip:803, :843): C-contiguous rows, reads on 16-byte
 # boundaries (T * N a multiple of 8 elements), N in 2 .. 8.  T = 264: past the 256-row tile; five reads: two workgroups
 def viterbi_stream_case(fcd, args):
     N, dt = args
@@ -388,7 +389,7 @@ def viterbi_stream_case(fcd, args):
     _viterbi_check(fcd, xin[:, :72], x[:, :72], None, idt)
 
 
-# viterbi_tm_kernel<N, dtype>: tm_ok (viterbi.hip:817): (T, B, N) storage seen as a batch, at least 8 reads, rows of the
+# viterbi_tm_kernel<N, dtype>: tm_ok (viterbi.hip:807): (T, B, N) storage seen as a batch, at least 8 reads, rows of the
 # storage on 16-byte boundaries.  16 reads stored, 11 handed over: one group of eight, three on viterbi_kernel
 def viterbi_tm_case(fcd, args):
     N, dt = args
@@ -401,7 +402,7 @@ def viterbi_tm_case(fcd, args):
     _viterbi_check(fcd, view, x[:11], None, idt)
 
 
-def viterbi_case(fcd, args):  # viterbi_kernel: N outside 2 .. 8 (viterbi.hip:870)
+def viterbi_case(fcd, args):  # viterbi_kernel: N outside 2 .. 8 (viterbi.hip:860)
     x = _greedy_values(np.random.default_rng(60), (3, 65, 9))
     _viterbi_check(fcd, x, x, np.array([65, 62, 0], np.int64), None)
 
@@ -428,7 +429,7 @@ def _crf_greedy_check(fcd, view, init, lengths):
         assert "".join(oracle.phred(float(q)) for q in r.qual[i, :n]) == qs, i
 
 
-# crf_greedy_stream_kernel<S, TM>: launch_crf_greedy (viterbi.hip:880-914): float32, S in 1 .. 8, S * N <= 32; TM: (T, B, S, N)
+# crf_greedy_stream_kernel<S, TM>: launch_crf_greedy (viterbi.hip:870-908): float32, S in 1 .. 8, S * N <= 32; TM: (T, B, S, N)
 # storage with at least four reads.  N = 4 fits every S; TM: eight reads stored, six handed over (two on crf_greedy_kernel)
 def crf_greedy_stream_case(fcd, args):
     S, tm = args
@@ -445,10 +446,37 @@ def crf_greedy_stream_case(fcd, args):
         _crf_greedy_check(fcd, x[:5], init[:5], None)
 
 
-def crf_greedy_case(fcd, args):  # crf_greedy_kernel: S above 8 (viterbi.hip:932)
+def crf_greedy_case(fcd, args):  # crf_greedy_kernel: S above 8 (viterbi.hip:922)
     rng = np.random.default_rng(80)
     x = _greedy_values(rng, (3, 65, 9, 4))
     _crf_greedy_check(fcd, x, rng.random((3, 9), dtype=np.float32), np.array([65, 62, 0], np.int64))
+
+
+# ---- the CRF walks over all labellings: one kernel each, whose code forms are chosen at run time from S and N.  One entry
+# of the walk's own case table per form, the smallest that reaches it, checked by that table's run_case ------------------------
+def crf_viterbi_case(fcd, args):
+    """crf_viterbi_kernel (crf_viterbi.hip:117, :170, :188): a lane per element (S N <= 64), a lane per state (S <= 64),
+    several states per lane with two passes per row; T = 65 crosses the 64-emission flush of the walk back"""
+    import crf_viterbi_cases as VC
+    for S, N, T in ((4, 5, 65), (64, 5, 65), (256, 3, 65)):
+        case, = [c for c in VC.CASES if c[1:4] == (S, N, T)]
+        VC.run_case(fcd, VC.build_case(case))
+
+
+def crf_transitions_case(fcd, args):
+    """crf_transitions_kernel (crf_transitions.hip:64, :104): a lane per element, a lane per state with one chunk of 64
+    states, and with many"""
+    import crf_transitions_cases as TC
+    for name in ("s4_n5_t7_dest_f16in", "s64_n5_t7_bf16_padded", "s256_n5_t65_dest_tm"):
+        case, = [c for c in TC.CASES if c["name"] == name]
+        TC.run_case(fcd, case)
+
+
+def crf_marginals_case(fcd, args):
+    """crf_marginals_kernel (crf_transitions.hip:255, :291): the forward pass's forms, behind the same three of the walk"""
+    import crf_marginals_cases as MC
+    for name in ("s4_n5_t7_dest_f16", "s64_n5_t2_bf16_padded", "s256_n5_t65_dest_tm"):
+        MC.run_case(fcd, MC.by_name(name))
 
 
 # ---- the lattice walks: the run_case functions of their case files, at the T that selects the instantiation ----------
@@ -726,6 +754,9 @@ FAMILIES = {
     "viterbi_kernel": (_one, viterbi_case),
     "crf_greedy_stream_kernel": (lambda: [(s, tm) for s in range(1, 9) for tm in (False, True)], crf_greedy_stream_case),
     "crf_greedy_kernel": (_one, crf_greedy_case),
+    "crf_viterbi_kernel": (_one, crf_viterbi_case),
+    "crf_transitions_kernel": (_one, crf_transitions_case),
+    "crf_marginals_kernel": (_one, crf_marginals_case),
     "score_reg_kernel": (lambda: [(k,) for k in (2, 4, 6, 8)], score_reg_case),
     "score_lds_kernel": (_one, score_lds_case),
     "align_reg_kernel": (lambda: [(k,) for k in (2, 4, 6, 8)], align_reg_case),

@@ -1,5 +1,5 @@
-"""CPU-side check of the CRF edge marginals (csrc/viterbi.hip, crf_transitions_walk and crf_marginals_forward inside
-crf_greedy_kernel, compiled against tests/hipemu's lockstep wave64 emulation) through fcd_crf_marginals_host and
+"""CPU-side check of the CRF edge marginals (csrc/crf_transitions.hip, crf_marginals_kernel: crf_transitions_walk, then
+crf_marginals_forward; compiled against tests/hipemu's lockstep wave64 emulation) through fcd_crf_marginals_host and
 crf_marginals_batch_raw on numpy, against the float64 restatement tests/crf_marginals_reference.py: the whole table of
 tests/crf_marginals_cases.py, the edge cases of the definition, the argument errors at both layers and every limit, the
 nullable emit and logz, untouched rows and spare elements, the agreement with crf_transition_probs, and the launch log.
@@ -12,6 +12,7 @@ import pytest
 import crf_marginals_cases as MC
 import crf_transitions_reference as R
 from emu_util import emulated_kernels
+from instantiation_cases import canonical
 
 
 @pytest.fixture(scope="module")
@@ -46,7 +47,7 @@ def test_nullable_outputs_and_untouched_elements(fcd):
     MC.nullable_outputs(fcd)
 
 
-def test_launches_crf_greedy_kernel_only(env):
+def test_launches_crf_marginals_kernel_only(env):
     fcd, lib = env
     lib.hipemu_launch_log_reset()
     for S, N in ((4, 5), (64, 5), (130, 3)):
@@ -55,4 +56,4 @@ def test_launches_crf_greedy_kernel_only(env):
     buf = C.create_string_buffer(need)
     lib.hipemu_launch_log_read(buf, need)
     names = [l for l in buf.value.decode().splitlines() if l]
-    assert len(names) == 1 and "crf_greedy_kernel" in names[0], names
+    assert len(names) == 1 and canonical(names[0]) == "crf_marginals_kernel", names

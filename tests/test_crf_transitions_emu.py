@@ -1,4 +1,4 @@
-"""CPU-side check of the CRF transition-probability walk (csrc/viterbi.hip, crf_transitions_walk inside crf_greedy_kernel,
+"""CPU-side check of the CRF transition-probability walk (csrc/crf_transitions.hip, crf_transitions_kernel,
 compiled against tests/hipemu's lockstep wave64 emulation) through fcd_crf_transition_probs_host and
 crf_transition_probs_batch_raw on numpy, against the float64 restatement tests/crf_transitions_reference.py: the whole table of
 tests/crf_transitions_cases.py, the edge cases of the definition, the argument errors at both layers and every limit, the
@@ -12,6 +12,7 @@ import pytest
 import crf_transitions_cases as TC
 import crf_transitions_reference as R
 from emu_util import emulated_kernels
+from instantiation_cases import canonical
 
 
 @pytest.fixture(scope="module")
@@ -46,7 +47,7 @@ def test_nullable_outputs(fcd):
     TC.nullable_outputs(fcd)
 
 
-def test_launches_crf_greedy_kernel_only(env):
+def test_launches_crf_transitions_kernel_only(env):
     fcd, lib = env
     lib.hipemu_launch_log_reset()
     for S, N in ((4, 5), (64, 5), (130, 3)):
@@ -55,7 +56,7 @@ def test_launches_crf_greedy_kernel_only(env):
     buf = C.create_string_buffer(need)
     lib.hipemu_launch_log_read(buf, need)
     names = [l for l in buf.value.decode().splitlines() if l]
-    assert len(names) == 1 and "crf_greedy_kernel" in names[0], names
+    assert len(names) == 1 and canonical(names[0]) == "crf_transitions_kernel", names
 
 
 def test_viterbi_search_finds_the_best_path_of_the_scores(fcd):

@@ -1,4 +1,4 @@
-"""CPU-side check of the CRF Viterbi walk (csrc/viterbi.hip, crf_viterbi_walk inside crf_greedy_kernel, compiled against
+"""CPU-side check of the CRF Viterbi walk (csrc/crf_viterbi.hip, crf_viterbi_kernel, compiled against
 tests/hipemu's lockstep wave64 emulation) through crf_viterbi_search_batch_raw on numpy, against the restatement
 tests/crf_viterbi_reference.py: the grid of tests/crf_viterbi_cases.py (S = 4 .. 1024 and the non-power multiple 12, N = 2 /
 3 / 5 / 9, T = 1 .. 300 around the 64-emission flush of the traceback, ragged lengths with an empty read, f32 / f16 / bf16,

@@ -1,4 +1,4 @@
-"""-m gpu: the CRF edge marginals (csrc/viterbi.hip, crf_transitions_walk and crf_marginals_forward inside crf_greedy_kernel)
+"""-m gpu: the CRF edge marginals (csrc/crf_transitions.hip, crf_marginals_kernel)
 on the device.  The table of tests/crf_marginals_cases.py on torch device tensors (fcd_crf_marginals_dev and
 crf_marginals_batch_raw) against the float64 restatement (tests/crf_marginals_reference.py), the case whose LDS passes 64 KiB,
 the edge cases, the argument errors and limits, the nullable outputs, host and device entry points bit for bit, torch tensors

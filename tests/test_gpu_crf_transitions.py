@@ -1,4 +1,4 @@
-"""-m gpu: the CRF transition-probability walk (csrc/viterbi.hip, crf_transitions_walk inside crf_greedy_kernel) on the
+"""-m gpu: the CRF transition-probability walk (csrc/crf_transitions.hip, crf_transitions_kernel) on the
 device.  The table of tests/crf_transitions_cases.py on torch device tensors (fcd_crf_transition_probs_dev and
 crf_transition_probs_batch_raw) against the float64 restatement (tests/crf_transitions_reference.py), the case whose LDS
 passes 64 KiB (the launch that raises the kernel's limit), the edge cases, the argument errors and limits, the nullable logz,

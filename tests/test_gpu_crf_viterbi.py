@@ -1,4 +1,4 @@
-"""-m gpu: the CRF Viterbi walk (csrc/viterbi.hip, crf_viterbi_walk inside crf_greedy_kernel) on the device.  The table of
+"""-m gpu: the CRF Viterbi walk (csrc/crf_viterbi.hip, crf_viterbi_kernel) on the device.  The table of
 tests/crf_viterbi_cases.py on torch device tensors (fcd_crf_viterbi_search_dev) against the restatement
 (tests/crf_viterbi_reference.py) with the cross-checks against crf_align / crf_score / crf_greedy_search, one S = 4096,
 N = 5 f16 case (80 KiB of LDS: the launch that raises the kernel's limit), the edge cases, the argument errors, the C ABI's

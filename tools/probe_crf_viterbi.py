@@ -4,7 +4,7 @@ from the same run, on one GPU.
     python tools/probe_crf_viterbi.py [--passes 5] [--reads 4096] [--mid-reads 256] [--large-reads 64] [--out FILE]
 
 Three shapes: BASELINE config 4's (4096 x 4000 x 4 states x 5, float32), S = 64 (float32; crf_greedy_search runs on
-crf_greedy_kernel there, the kernel the Viterbi walk lives in) and S = 1024 (float16).  Milliseconds: the host clock around
+crf_greedy_kernel there, the serial walk) and S = 1024 (float16).  Milliseconds: the host clock around
 one device-resident call and a device synchronise; after one warm-up call, --passes such calls: the best of them as *_ms,
 all of them as *_all (their spread is the run-to-run margin).  --package-root DIR imports fast_ctc_decode_amd from another
 tree (a build of the parent commit, which has no Viterbi search: its columns are left out).  One JSON line."""

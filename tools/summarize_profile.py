@@ -39,7 +39,8 @@ WORK = _Work()
 
 def short(n):
     m = re.search(r"(beam_wave_kernel<[^>]*>|beam_lane_kernel<[^>]*>|beam_generic_kernel|viterbi_stream_kernel<[^>]*>|viterbi_kernel|"
-                  r"duplex_slots_kernel<[^>]*>|duplex_kernel<[^>]*>|crf_greedy_stream_kernel<[^>]*>|crf_greedy_kernel|envelope_kernel|ln_convert_kernel)", n)
+                  r"duplex_slots_kernel<[^>]*>|duplex_kernel<[^>]*>|crf_greedy_stream_kernel<[^>]*>|crf_greedy_kernel|"
+                  r"crf_viterbi_kernel|crf_transitions_kernel|crf_marginals_kernel|envelope_kernel|ln_convert_kernel)", n)
     return m.group(1) if m else None
 
 
