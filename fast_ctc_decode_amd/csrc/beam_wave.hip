@@ -423,6 +423,16 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_pe
     float rowv = GATHER ? gather_row(0) : 0.0f;
     // HL: the halves that still run, as a mask (bit = lane); `alive` is formed again behind the time loop
     uint64_t alive_m = HL ? ballot(alive) : 0ull;
+    // HL: the lane-constant masks the step's votes are joined with (beam_wave_step.inc)
+    const uint64_t child_m = HL ? ballot(is_child) : 0ull;
+    const uint64_t self_m = HL ? ballot(is_self) : 0ull;
+    const uint64_t collapse_m = (HL && collapse) ? ~0ull : 0ull;
+    // HL: the two bounds of the rank-domain guard (device_utils.h), held in scalar registers across the time loop
+    float rankf_lo = kRankfALo, rankf_hi = kRankfAHi;
+    if (HL) {
+        FCD_OPAQUE_S(rankf_lo);
+        FCD_OPAQUE_S(rankf_hi);
+    }
     // Drain the prologue loads HERE, with a wait the compiler's scoreboard sees: otherwise the loop
     // header inherits "win[0] may still be in flight" and gets an s_waitcnt vmcnt(0) on EVERY step,
     // which on gfx9-family counters also waits for the previous step's tree stores to be acked.

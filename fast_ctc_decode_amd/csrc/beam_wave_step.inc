@@ -12,18 +12,31 @@
         const float pr0 = pk;
         const float ptip = ptip_next;
         stamp_f(0, pk);  // loop overhead + posterior row
-        const bool grp = UNI ? i < B : (act && i < B);
+        // HL: the step's lane predicates are formed as MASKS -- a vote on each bare compare (one instruction, exec is all
+        // ones on this path), joined in scalar registers with the lane-constant masks balloted in front of the time loop
+        // (beam_wave.hip: child_m, self_m, collapse_m) -- and read back as lane flags with lane_in(), which costs nothing.
+        // A vote on a flag DERIVED from several compares costs two vector instructions (a 0 / 1 word and its compare with 0):
+        // that is what m_new, m_valid, the clash vote and the rank-domain guard were.
+        const uint64_t m_grp = HL ? ballot(i < B) : 0ull;
+        const uint64_t m_rep = HL ? (collapse_m & ballot((k << 2) == tipf)) : 0ull;
+        const uint64_t m_ex = HL ? ballot(child >= 0) : 0ull;
+        // (exists && IN-BEAM in one compare: the sign bit clear and the flag set)
+        const uint64_t m_ib = HL ? ballot((child & (kInBeam | (int)0x80000000)) == kInBeam) : 0ull;
+        const uint64_t m_cv = HL ? (m_grp & child_m & ballot(!(pk < thr)) & (m_ex | ~m_rep | ballot(gp > 0.0f))) : 0ull;
+        const uint64_t m_mg = m_cv & m_ib;
+        const bool grp = HL ? lane_in(m_grp, lane) : (UNI ? i < B : (act && i < B));
 
         // ---- child lanes: extension by label l (:200-239) ----
         const bool pass = !(pk < thr);  // :201 skips only when pr_b < thr
-        const bool rep = collapse && (k << 2) == tipf;  // l == tip
+        const bool rep = HL ? lane_in(m_rep, lane) : (collapse && (k << 2) == tipf);  // l == tip
         const float contrib = rep ? gp * pk : (lp + gp) * pk;
         const bool exists = child >= 0;
         const int cid = child & kIdMask;
-        const bool inbeam = exists && (child & kInBeam);
+        const bool inbeam = HL ? lane_in(m_ib, lane) : (exists && (child & kInBeam));
         const int mslot = (child >> kSlotShift) & kSlotMask;
-        const bool cvalid = grp && is_child && pass && (exists || !rep || gp > 0.0f);  // :212-218
-        const bool merged = cvalid && inbeam;  // the target's own lane 0 absorbs this extension
+        const bool cvalid = HL ? lane_in(m_cv, lane)
+                               : (grp && is_child && pass && (exists || !rep || gp > 0.0f));  // :212-218
+        const bool merged = HL ? lane_in(m_mg, lane) : (cvalid && inbeam);  // the target's own lane 0 absorbs this extension
         // HL: the target slot's own lane as a byte address, formed once for the push here and the look-up behind the rank
         const int tgt_a = hbase_a + mslot * (GW << 2);
         const int dst = merged ? hbase + mslot * GW : dummy;
@@ -34,21 +47,29 @@
         stamp_f(1, inc);  // extensions + the push into slots that are beam entries
 
         // ---- self lanes: blank (:191-198) + repeat-stay (:206-211) + incoming extension ----
-        const bool blank = pr0 > thr;
+        const uint64_t m_blank = HL ? ballot(pr0 > thr) : 0ull;
+        const uint64_t m_stay = HL ? (collapse_m & ballot(tipf != 0) & ballot(!(ptip < thr))) : 0ull;
+        const uint64_t m_inc = HL ? (self_m & ballot(incv != 0)) : 0ull;
+        // HL: the mask of this step's candidates.  The key below is formed under exactly this mask and make_key() is never
+        // 0, so it IS the vote "key != 0" (m_valid) the step takes behind the rank.
+        const uint64_t m_val = HL ? ((m_grp & self_m & (m_blank | m_stay | m_inc)) | (m_cv & ~m_ib)) : 0ull;
+        const bool blank = HL ? lane_in(m_blank, lane) : (pr0 > thr);
         const float gpn = (lp + gp) * pr0;
-        const bool stay = collapse && tipf != 0 && !(ptip < thr);
+        const bool stay = HL ? lane_in(m_stay, lane) : (collapse && tipf != 0 && !(ptip < thr));
         const float lpn = lp * ptip;
-        const bool has_inc = is_self && incv != 0;
+        const bool has_inc = HL ? lane_in(m_inc, lane) : (is_self && incv != 0);
         const float slp = (stay ? lpn : 0.0f) + (has_inc ? inc : 0.0f);
         const float sgp = blank ? gpn : 0.0f;
         const bool svalid = grp && is_self && (blank || stay || has_inc);
 
-        const bool valid = svalid || (cvalid && !merged);  // svalid / cvalid already carry is_self / is_child
+        // (svalid / cvalid already carry is_self / is_child)
+        const bool valid = HL ? lane_in(m_val, lane) : (svalid || (cvalid && !merged));
         const float clp = is_self ? slp : contrib;
         const float cgp = is_self ? sgp : 0.0f;
         const float prob = clp + cgp;
 
-        const bool is_new = cvalid && !exists;
+        const uint64_t m_isnew = m_cv & ~m_ex;  // (HL)
+        const bool is_new = HL ? lane_in(m_isnew, lane) : (cvalid && !exists);
 
         // ---- prune, first half: sort keys out, comparands back (exact rank on (probability desc, node asc)) ----
         // The key needs a node index only to break probability ties, and only its ORDER matters: a node
@@ -121,7 +142,7 @@
         }
 
         // ---- tree.rs:125-145 add_node: ids in (beam order, label order) == lane order; runs under the LDS reads ----
-        const uint64_t m_new = ballot(is_new);
+        const uint64_t m_new = HL ? m_isnew : ballot(is_new);
         const uint32_t w_new = RPW == 1 ? 0u : (hbase ? (uint32_t)(m_new >> 32) : (uint32_t)m_new);
         int pre_new;
         if (RPW == 1) {
@@ -136,17 +157,28 @@
         // (beam_lane.hip writes a node's record when it first ENTERS THE BEAM -- a sixth of the stores.  Tried here, r05:
         // the stores ride for free under the LDS reads above, while next to the survivor gather they cost the PDQ
         // instantiation 8 B of scratch and 1 % -- the write traffic is not what bounds this kernel.)
-        if (is_new) {
+        if (HL) {
+            // one exec region for the record store; the segment-head store (one depth in 64) waits behind a wave-uniform
+            // vote instead of a second region inside the first
+            if (is_new) *at32(rec_w, hoff + (uint32_t)newid) = ((node + 1) << 3) | l;
+            static_assert(kSeg == 64, "(depth + 1) % kSeg == 0 as a compare of the low six bits");
+            const uint64_t m_head = m_new & ballot((depth & (kSeg - 1)) == kSeg - 1);
+            if (__builtin_expect(m_head != 0ull, 0)) {
+                if (lane_in(m_head, lane)) *at32(jmp_w, hoff + (uint32_t)newid) = (depth % kSeg == 0) ? node : jump;
+            }
+        } else if (is_new) {
             *at32(rec_w, hoff + (uint32_t)newid) = ((node + 1) << 3) | l;
             // a segment head (depth % 64 == 0) records where the next head up the tree is
             if ((depth + 1) % kSeg == 0) *at32(jmp_w, hoff + (uint32_t)newid) = (depth % kSeg == 0) ? node : jump;
         }
         int child_in = is_new ? newid : child;  // (the entry as the rest of the step sees it)
-        int id = is_self ? node : (is_new ? newid : cid);
+        // (HL: a child lane's id is the id field of its entry as the step sees it -- a new id fits the field -- one select fewer)
+        int id = is_self ? node : (HL ? (child_in & kIdMask) : (is_new ? newid : cid));
         stamp_i(2, id);  // own candidate, key, node numbering, record stores
 
         // ---- prune, second half: count the larger keys ----
         int rank = 0;
+        const float fown_g = (R32 && HL) ? fcd_rankf_own(kp) : 0.0f;  // (HL: the count's own term; the guard votes on it as well)
         int n_eq = 0, n_gt = 0;  // AMB: candidates of exactly this probability (itself included) / of a greater one
         if (AMB) {
 #pragma unroll
@@ -161,7 +193,7 @@
             int r0, r1 = 0, r2 = 0, r3 = 0;
             static_assert(!STREAM || NC >= 4, "at least one block of four comparands");
             // HL: the count as a sum of clamped f32 differences (device_utils.h, FCD_RANKF4): own word scaled once
-            const float fown = (R32 && HL) ? fcd_rankf_own(kp) : 0.0f;
+            const float fown = fown_g;
             float facc;
 #pragma unroll
             for (int j = 0; j < NBLK; ++j) {
@@ -212,14 +244,19 @@
 
         // ---- search.rs:261-277 ----
         // (key != 0 <=> valid && act: a vote on a compare costs one instruction, a vote on a derived flag two)
-        const uint64_t m_valid = ballot(key != 0ull);
+        const uint64_t m_valid = HL ? m_val : ballot(key != 0ull);
         int n_valid = RPW == 1 ? popc64(m_valid)
                                : __builtin_popcount(hbase ? (uint32_t)(m_valid >> 32) : (uint32_t)m_valid);
         // Everything that ends a read is rare: one wave-wide test, the bookkeeping behind it.
         const bool is_nan = valid && prob != prob;
-        // HL: the same test on masks, votes on bare compares joined in scalar registers -- a candidate is a NaN when its
-        // probability is one and its key is not 0 (valid <=> key != 0), a half runs when alive_m says so
-        if (HL ? ((((ballot(n_valid == 0)) | (ballot(prob != prob) & m_valid)) & alive_m) != 0ull)
+        // HL: a candidate whose probability word is outside the range on which the f32 count is exact (device_utils.h,
+        // fcd_rankf_outside_m: three votes on bare compares of prob and of fown, which the count already holds).  It
+        // sends the step to the exact recount (m_clash, below).
+        const uint64_t m_guard = (R32 && HL) ? (fcd_rankf_outside_m(prob, fown_g, rankf_lo, rankf_hi) & m_valid) : 0ull;
+        // HL: the same test on masks -- a half runs when alive_m says so.  A NaN's word is outside the rank domain whatever
+        // its sign and payload (fcd_rankf_outside_m), so the guard's vote stands in for "some candidate is a NaN" here and the
+        // every-step path takes no vote on prob != prob: a guarded step without a NaN enters the block and leaves it unchanged.
+        if (HL ? ((((ballot(n_valid == 0)) | m_guard) & alive_m) != 0ull)
                : (ballot(act && (n_valid == 0 || is_nan)) != 0ull)) {
             const bool act = HL ? lane_in(alive_m, lane) : act0;
             const uint64_t m_nan = ballot(is_nan);
@@ -260,6 +297,7 @@
         float dv = 0.0f;  // DSRC: what this lane divides by the top probability (not const: PARK)
         uint32_t tie0 = 0, tie1 = 1;
         bool clash = false;  // R32: this lane's entry of the survivor table was overwritten by a candidate of equal probability
+        uint64_t m_sel = 0ull, m_clash_t = 0ull;  // HL: `sel` and `clash` as masks
         // Everything that depends on the ranks: survivor table, fate of the child entries, row eviction, the gather of
         // the survivors into rank order.  PDQ: it runs on the exact ranks first; the tie table comes back with the
         // same LDS round trip and is looked at only when the gather has landed -- a flagged step (rare) replaces the
@@ -267,6 +305,10 @@
         // in HBM nobody reads before it is written again: rows are read back only after their node's LAST eviction.)
         auto settle_table = [&]() __attribute__((always_inline)) {
             sel = valid && go && rank < beam_size;
+            if (HL) {  // (a statement of its own: folded into the line above it changed the code of every other instantiation)
+                m_sel = m_val & ballot(rank < beam_size);
+                sel = lane_in(m_sel, lane);
+            }
             selflag = sel ? (rank | 16) : 0;
             // PDQ: EVERY candidate leaves its entry (the table has room for all ranks; entries past the new beam are
             // never used as sources, and as depths they are not looked at), and next to it, kTie words further on, its
@@ -303,6 +345,7 @@
             if (R32) {
                 const int back = srcs[PDQ ? rank : (rank & 15)];
                 clash = sel && back != ent;
+                if (HL) m_clash_t = m_sel & ballot(back != ent);
             }
             fate = HL ? __builtin_amdgcn_ds_bpermute(tgt_a, selflag) : bperm(hbase + mslot * GW, selflag);
             own = bperm(grp0, selflag);  // ... and this group's own candidate?
@@ -341,7 +384,7 @@
         const int tipfc = is_self ? tipf : (k << 2);
         int statec = (CRF && !is_self) ? (GATHER ? ((state * NL) & s_mask) + l : (state * NL) % (S > 0 ? S : 1) + l)
                                              : state;  // :97
-        int jumpc = HL ? ((!is_self && depth % kSeg == 0) ? node : jump)  // (one select)
+        int jumpc = HL ? (lane_in(~self_m & ballot((depth & (kSeg - 1)) == 0), lane) ? node : jump)  // (one select, on a mask)
                        : (is_self ? jump : ((depth % kSeg == 0) ? node : jump));
         // 0 self, 1 a child entering the beam for the first time, 2 a child that has been there before (EVER:
         // its row is in HBM); read off the entry BEFORE it is marked below
@@ -360,7 +403,14 @@
                 const int followed = (child_in & kStored) | (fate << kSlotShift);
                 const int entered = id | kEver | (selflag << kSlotShift);
                 const bool upd = go && is_child;
-                child_s = (upd && inbeam) ? followed : ((upd && sel) ? entered : child_in);
+                if (HL) {
+                    // two selects on masks: no exec region and no branch is spent on the entry
+                    const uint64_t m_ent = child_m & m_sel;
+                    child_s = lane_in(m_ent, lane) ? entered : child_in;
+                    child_s = lane_in(child_m & m_ib, lane) ? followed : child_s;
+                } else {
+                    child_s = (upd && inbeam) ? followed : ((upd && sel) ? entered : child_in);
+                }
                 // A node's child row only has to exist in HBM while the node is OUT of the beam (it is read back if
                 // the node re-enters, below): write it once, when the node is evicted -- four lanes, 16 contiguous
                 // bytes.  And only if the node can come back at all: a node re-enters the beam as the extension of its
@@ -368,8 +418,13 @@
                 // deep as the node, and then none ever will (its ancestors have left for good, top-down from the
                 // root).  Three evicted rows in four are dead by this test and are never written.
                 const bool dead = (depth << 8) <= e_min;  // e_min = (minimum depth << 8) | a lane address
+                if (HL) {  // ONE exec region, its mask joined in scalar registers
+                    if (lane_in(child_m & m_grp & ballot(own == 0) & ballot((depth << 8) > e_min), lane))
+                        *at32(rows_w, (hoff + (uint32_t)(node + 1)) * RW + l) = child_s;
+                } else {
                 if (upd && grp && own == 0 && !dead)
                     *at32(rows_w, (hoff + (uint32_t)(node + 1)) * RW + l) = child_s;  // (beam-position bits and all: stripped when read back)
+                }
             }
             stamp_i(4, child_s);  // fate of every child entry, row eviction
             // ---- gather the survivors into rank order ----
@@ -427,7 +482,7 @@
         // HL: a fourth -- a candidate whose probability word is outside the range on which the f32 count is exact (device_utils.h,
         // fcd_rankf_outside: below 2^-76 and not 0, above 2^27, negative, a NaN).  The same recount: it is valid for every
         // input and replaces whatever the first pass counted.
-        const uint64_t m_clash = R32 ? (HL ? (ballot(clash) | (ballot(fcd_rankf_outside(kp)) & m_valid)) : ballot(clash)) : 0ull;
+        const uint64_t m_clash = R32 ? (HL ? (m_clash_t | m_guard) : ballot(clash)) : 0ull;
         const uint64_t m_hint = (PDQ && !R32) ? (ballot(tie0 == tie1) & ballot(tie_lim < n_valid)) : 0ull;
         if (__builtin_expect((m_k2 | m_hint | m_clash) != 0ull, 0)) {
             uint64_t m_tied = m_hint;

@@ -222,6 +222,32 @@ __device__ __forceinline__ float fcd_rankf_own(uint32_t word) { return __uint_as
 __device__ __forceinline__ bool fcd_rankf_outside(uint32_t word) {
     return word - kRankfLo > kRankfHi - kRankfLo && word != 0x80000000u;
 }
+// The same predicate as a wave-wide vote, on what the step holds anyway -- the candidate's probability p (make_key: its
+// word is that of p + 0.0) and A = fcd_rankf_own(word) -- as three votes on bare compares joined in scalar registers, no
+// arithmetic.  A = -p * 2^100 exactly for p >= 0 (a subnormal p scales to a normal A, p >= 2^28 to -inf), so
+//   word > kRankfHi (p > 2^27, +inf, a NaN of positive sign)         <=>  A < -2^127, -inf or a NaN:  !(A >= -2^127);
+//   word < kRankfLo with bit 31 set (0 <= p < 2^-76)                  <=>  -2^24 < A <= -0.0;
+//   word with bit 31 clear (p < 0, a NaN of negative sign)             =>  A >= +0.0 (its word read as a float is positive):
+// the second vote, A > -2^24, takes both of the last two and with them the word of +0, which the third, p != 0 (true of a
+// NaN), takes out again.  For every one of the 2^32 values of p it says what fcd_rankf_outside() says of p's word
+// (tests/test_headline_votes_emu.py walks them all; every word but 0x7FFFFFFF, which no p makes, is among them).  The two
+// bounds are parameters: the kernel keeps them in scalar registers across its time loop (FCD_OPAQUE_S) instead of
+// rebuilding two literals in every step.
+constexpr float kRankfALo = -0x1p24f;   // A of p = 2^-76
+constexpr float kRankfAHi = -0x1p127f;  // A of p = 2^27
+__device__ __forceinline__ bool fcd_rankf_outside_a(float p, float a, float a_lo, float a_hi) {  // (one lane)
+    return !(a >= a_hi) || (a > a_lo && p != 0.0f);
+}
+__device__ __forceinline__ uint64_t fcd_rankf_outside_m(float p, float a, float a_lo, float a_hi) {
+    return ballot(!(a >= a_hi)) | (ballot(a > a_lo) & ballot(p != 0.0f));
+}
+// Makes a wave-uniform value opaque to the optimiser and pins it in a scalar register: a constant the time loop reads in
+// every step stays there instead of being rebuilt from a literal.
+#ifdef FCD_HIPEMU  // (lockstep emulation, tests/hipemu: plain C++)
+#define FCD_OPAQUE_S(x) ((void)(x))
+#else
+#define FCD_OPAQUE_S(x) asm volatile("" : "+s"(x))
+#endif
 #ifdef FCD_HIPEMU  // (lockstep emulation, tests/hipemu: plain C++)
 static inline float fcd_rankf_t(float a, uint32_t w) {
     const float t = fmaf(__uint_as_float(w), -0x1p100f, a);

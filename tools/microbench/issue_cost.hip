@@ -58,6 +58,16 @@
 #define I_SALU(d, m, s)      "s_and_b64 %" #m ", %" #m ", exec\n\ts_xor_b64 %" #m ", %" #m ", exec\n\t"  // 2
 #define I_SALU_VALU(d, m, s) "s_and_b64 %" #m ", %" #m ", exec\n\tv_add_u32 %" #d ", %12, %" #d "\n\t" \
                              "s_xor_b64 %" #m ", %" #m ", exec\n\tv_add_u32 %" #d ", %13, %" #d "\n\t"  // 2 + 2
+// r14: the classes the vote, guard and child-fate forms of the headline step rest on
+#define I_MIN_U32(d, m, s)   "v_min_u32 %" #d ", %12, %" #d "\n\t"
+#define I_MAX_U32(d, m, s)   "v_max_u32 %" #d ", %12, %" #d "\n\t"
+#define I_CMP_CLASS(d, m, s) "v_cmp_class_f32_e64 %" #m ", %" #d ", 32\n\t"
+#define I_BFI(d, m, s)       "v_bfi_b32 %" #d ", %" #d ", %12, %13\n\t"
+#define I_BCNT1_CSEL(d, m, s) "s_bcnt1_i32_b64 %" #s ", %" #m "\n\tv_add_u32 %" #d ", %12, %" #d "\n\t" \
+                              "s_cselect_b32 %" #s ", %" #s ", 0\n\tv_add_u32 %" #d ", %13, %" #d "\n\t"  // 2 + 2
+// an exec region around one vector instruction whose s_cbranch_execz is not taken (the mask is exec itself)
+#define I_SAVEEXEC(d, m, s)  "s_and_saveexec_b64 %" #m ", exec\n\ts_cbranch_execz 1f\n\tv_add_u32 %" #d ", %12, %" #d "\n\t" \
+                             "1:\n\ts_or_b64 exec, exec, %" #m "\n\t"
 // the pair the rank count is made of today, consumer four instructions behind its producer
 #define I_CMP_ADDC_PAIR "v_cmp_gt_u32_e64 %4, %12, %0\n\tv_cmp_gt_u32_e64 %5, %12, %1\n\tv_cmp_gt_u32_e64 %6, %12, %2\n\tv_cmp_gt_u32_e64 %7, %12, %3\n\t" \
                         "v_addc_co_u32_e64 %0, vcc, 0, %0, %4\n\tv_addc_co_u32_e64 %1, vcc, 0, %1, %5\n\t"                                                   \
@@ -66,7 +76,8 @@
 enum {
     C_FMA, C_FMA_CLAMP, C_ADD_F32, C_MUL_F32, C_CVT_U32, C_ADD_U32, C_SUB_U32, C_AND, C_LSHL, C_ALIGNBIT, C_BFE, C_LSHL_ADD,
     C_AND_OR, C_BCNT, C_MIN3, C_CMP_VCC, C_CMP_U32, C_CMP_F32, C_CMP_U64, C_ADDC, C_CND_VCC, C_CND_SGPR, C_MBCNT, C_READLANE,
-    C_DPP, C_SALU, C_SALU_VALU, C_CMP_ADDC, C_FDIV, C_RANK_NOW, C_RANK_F, C_RANK_I, C_RANK_S, C_COUNT
+    C_DPP, C_SALU, C_SALU_VALU, C_MIN_U32, C_MAX_U32, C_CMP_CLASS, C_BFI, C_BCNT1_CSEL, C_SAVEEXEC, C_CMP_ADDC, C_FDIV, C_RANK_NOW,
+    C_RANK_F, C_RANK_I, C_RANK_S, C_RANK_P, C_COUNT
 };
 struct Cls { const char *name; int per_trip_ind, per_trip_dep; const char *unit; };
 // instructions (or units) one loop trip issues per wavefront
@@ -80,9 +91,13 @@ static const Cls kCls[C_COUNT] = {
     {"v_cndmask_b32 on vcc", 16, 16, "inst"}, {"v_cndmask_b32_e64 on sgpr pair", 16, 16, "inst"},
     {"v_mbcnt_lo + v_mbcnt_hi", 32, 32, "inst"}, {"v_readlane_b32", 16, 0, "inst"}, {"v_mov_b32 dpp row_shr:1", 16, 0, "inst"},
     {"s_and_b64 + s_xor_b64 alone", 32, 32, "inst"}, {"s_and/s_xor 1:1 with v_add_u32 (per v_add_u32)", 32, 32, "v_add"},
+    {"v_min_u32", 16, 16, "inst"}, {"v_max_u32", 16, 16, "inst"}, {"v_cmp_class_f32_e64 -> sgpr pair", 16, 16, "inst"},
+    {"v_bfi_b32", 16, 16, "inst"}, {"s_bcnt1_i32_b64/s_cselect_b32 1:1 with v_add_u32 (per v_add_u32)", 32, 32, "v_add"},
+    {"saveexec region, execz not taken, around one v_add_u32", 16, 16, "region"},
     {"v_cmp_gt_u32_e64 + v_addc pair (4 chains)", 16, 0, "inst"}, {"f32 IEEE division (compiler's sequence)", 16, 16, "division"},
     {"RANK now: 25 x (v_cmp_e64 + v_addc)", 1, 0, "block"}, {"RANK F: 25 x (v_fma clamp + v_add_f32) + cvt", 1, 0, "block"},
     {"RANK I: 25 x (v_sub + v_alignbit) + bcnt + sub", 1, 0, "block"}, {"RANK S: scalar full adder, 3 cmp + 2 addc + 5 salu", 1, 0, "block"},
+    {"RANK P: 12 x (v_pk_fma_f32 clamp + v_pk_add_f32) + 1 + halves + cvt", 1, 0, "block"},
 };
 
 #define T0 asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t0) : : "memory")
@@ -110,6 +125,8 @@ __global__ __launch_bounds__(256) void k(uint32_t *cyc, int trips, uint32_t a, f
     STREAM_CASE(C_CMP_U32, I_CMP_U32) STREAM_CASE(C_CMP_F32, I_CMP_F32) STREAM_CASE(C_CMP_U64, I_CMP_U64) STREAM_CASE(C_ADDC, I_ADDC)
     STREAM_CASE(C_CND_VCC, I_CND_VCC) STREAM_CASE(C_CND_SGPR, I_CND_SGPR) STREAM_CASE(C_MBCNT, I_MBCNT) STREAM_CASE(C_READLANE, I_READLANE)
     STREAM_CASE(C_DPP, I_DPP) STREAM_CASE(C_SALU, I_SALU) STREAM_CASE(C_SALU_VALU, I_SALU_VALU)
+    STREAM_CASE(C_MIN_U32, I_MIN_U32) STREAM_CASE(C_MAX_U32, I_MAX_U32) STREAM_CASE(C_CMP_CLASS, I_CMP_CLASS) STREAM_CASE(C_BFI, I_BFI)
+    STREAM_CASE(C_BCNT1_CSEL, I_BCNT1_CSEL) STREAM_CASE(C_SAVEEXEC, I_SAVEEXEC)
     if (C == C_CMP_ADDC) {
         for (int i = 0; i < trips; ++i) asm volatile(I_CMP_ADDC_PAIR I_CMP_ADDC_PAIR OPS);
     }
@@ -135,6 +152,9 @@ __global__ __launch_bounds__(256) void k(uint32_t *cyc, int trips, uint32_t a, f
 #pragma unroll
         for (int u = 0; u < 25; ++u) { kw[u] = 0xBF000000u + (a + u * 977u + threadIdx.x * 31u) % 4096u; asm volatile("" : "+v"(kw[u])); }
         uint32_t kp = 0xBF000000u + x0 % 4096u, r = 0;
+        uint64_t kw2[12];  // RANK P: the same comparands as register pairs
+#pragma unroll
+        for (int u = 0; u < 12; ++u) { kw2[u] = ((uint64_t)kw[2 * u + 1] << 32) | kw[2 * u]; if (C == C_RANK_P) asm volatile("" : "+v"(kw2[u])); }
         for (int i = 0; i < trips; ++i) {
             asm volatile("" : "+v"(kp));
             if (C == C_RANK_NOW) {  // FCD_RANK4_32_ONE_FIRST, 5 x FCD_RANK4_32_ONE, the 25th: compare into vcc, add with carry
@@ -174,6 +194,27 @@ __global__ __launch_bounds__(256) void k(uint32_t *cyc, int trips, uint32_t a, f
                                  : "v"(kp), "v"(kw[u]), "v"(kw[u + 1]), "v"(kw[u + 2]), "v"(kw[u + 3]), "v"(kw[u + 4]));
                 }
                 asm volatile("v_bcnt_u32_b32 %0, %1, 0\n\tv_sub_u32 %0, %0, %2" : "=&v"(r) : "v"(acc), "v"(y1));
+            } else if (C == C_RANK_P) {  // RANK F two comparands per instruction: packed f32 fma with clamp, packed add, the halves summed
+                float A, single, s_lo;
+                const float scale = -0x1p100f;
+                uint64_t acc2 = 0, A2, sc2;
+                asm volatile("v_mul_f32 %0, 0x71800000, %1" : "=v"(A) : "v"(kp));
+                A2 = ((uint64_t)__float_as_uint(A) << 32) | __float_as_uint(A);
+                sc2 = ((uint64_t)__float_as_uint(scale) << 32) | __float_as_uint(scale);
+                asm volatile("" : "+v"(A2), "+s"(sc2));
+#pragma unroll
+                for (int u = 0; u < 12; u += 4) {
+                    uint64_t ta, tb, tc, td;
+                    asm volatile("v_pk_fma_f32 %1, %6, %10, %5 clamp\n\tv_pk_fma_f32 %2, %7, %10, %5 clamp\n\t"
+                                 "v_pk_fma_f32 %3, %8, %10, %5 clamp\n\tv_pk_fma_f32 %4, %9, %10, %5 clamp\n\t"
+                                 "v_pk_add_f32 %0, %0, %1\n\tv_pk_add_f32 %0, %0, %2\n\tv_pk_add_f32 %0, %0, %3\n\tv_pk_add_f32 %0, %0, %4"
+                                 : "+v"(acc2), "=&v"(ta), "=&v"(tb), "=&v"(tc), "=&v"(td)
+                                 : "v"(A2), "v"(kw2[u]), "v"(kw2[u + 1]), "v"(kw2[u + 2]), "v"(kw2[u + 3]), "s"(sc2));
+                }
+                asm volatile("v_fma_f32 %0, %3, %4, %2 clamp\n\tv_add_f32 %1, %5, %6\n\tv_add_f32 %1, %1, %0"
+                             : "=&v"(single), "=&v"(s_lo)
+                             : "v"(A), "v"(kw[24]), "s"(scale), "v"((uint32_t)acc2), "v"((uint32_t)(acc2 >> 32)));
+                asm volatile("v_cvt_u32_f32 %0, %1" : "=v"(r) : "v"(s_lo));
             } else {  // C_RANK_S: three compare masks through a scalar full adder into carry-adds of weight 1 and 2
                 uint32_t r1 = 0, r2 = 0;
 #pragma unroll
