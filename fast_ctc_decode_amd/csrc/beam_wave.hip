@@ -101,6 +101,21 @@ __device__ __forceinline__ int perm(int dst_lane, int v) {
 constexpr int kWavesPerBlock = 4;
 constexpr int kCrfGather = -1;
 constexpr int kFifo = 6;  // registers in the row FIFO
+// The row FIFO moves up by one register: win[j] = win[j + 1], the last one takes `incoming`.  Six moves written out, every
+// register tied to itself: left to the register allocator, the moves of a rotation this short end up on the loop's latch -- the
+// whole FIFO shifted forward at the end of EVERY step, with a wait for the block in flight, and shifted back at the head of
+// five steps in six.
+__device__ __forceinline__ void fifo_shift(float (&win)[kFifo], float incoming) {
+    static_assert(kFifo == 6, "six moves");
+#ifdef FCD_HIPEMU  // (lockstep emulation, tests/hipemu: plain C++)
+    for (int j = 0; j + 1 < kFifo; ++j) win[j] = win[j + 1];
+    win[kFifo - 1] = incoming;
+#else
+    asm volatile("v_mov_b32 %0, %1\n\tv_mov_b32 %1, %2\n\tv_mov_b32 %2, %3\n\tv_mov_b32 %3, %4\n\tv_mov_b32 %4, %5\n\tv_mov_b32 %5, %6"
+                 : "+v"(win[0]), "+v"(win[1]), "+v"(win[2]), "+v"(win[3]), "+v"(win[4]), "+v"(win[5])
+                 : "v"(incoming));
+#endif
+}
 constexpr int kSeg = 64;  // nodes per traceback segment (jump-pointer spacing)
 
 // Wavefronts per SIMD the register allocator is asked to leave room for (amdgpu_waves_per_eu on the kernel below; the value
@@ -223,6 +238,10 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_pe
     // half still runs" as a wave-uniform mask (alive_m) instead of a lane flag, the rank in one accumulator, the new nodes'
     // ids by v_mbcnt.  Same values in every register the step commits; the other instantiations keep their code.
     constexpr bool HL = RPW == 2 && GW == 6 && UNI && !AMB && !NB && !SES && !PROF && S >= 0;
+    // HL: the probability word next to a survivor-table entry (PDQ: the tie word) is the candidate's prob + 0.0f as the source
+    // lane holds it, not its sort-key word: rank 0's is the step's divisor and is read as it is.  The key word is a bijection of
+    // it, so two tie words are equal exactly when the two key words were.
+    constexpr bool kRawTop = HL;
     static_assert(!PDQ || BCAP * N > 20, "the tie order only matters above 20 candidates");
     static_assert(!PDQ || BCAP * N <= HALF - 2, "the last two entries of a half's table are never written (i_src below)");
     int n_amb = 0, n_crit = 0;
@@ -281,8 +300,9 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_pe
     // has been in the beam before: read as a source it would vote "re-entering" in every step
     const int i_src = (!idle && i < p.a.beam_size) ? i : HALF - 2;
     if (PDQ) {  // tie words: pairwise different, bit 31 clear -- no candidate's probability word looks like that
+                // (kRawTop: the same 32 words taken back through the key's bijection -- negative NaNs of the largest payloads)
 #pragma unroll
-        for (int w = lane; w < 128; w += 64) s_srcs[wave][w] = ((w / HALF) & 1) ? (w % HALF) : 0x7FFFFF00;
+        for (int w = lane; w < 128; w += 64) s_srcs[wave][w] = ((w / HALF) & 1) ? (kRawTop ? ~(w % HALF) : (w % HALF)) : 0x7FFFFF00;
     } else if (lane < RPW * 16) {
         s_srcs[wave][lane] = 0x7FFFFF00;  // never the minimum depth; points at lane 0
     }
@@ -410,6 +430,15 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_pe
     for (int j = 0; j < kFifo; ++j) win[j] = GATHER ? 0.0f : load_block(j);
     // the block in flight joins the FIFO one rotation after its load was launched
     float incoming = GATHER ? 0.0f : load_block(kFifo);
+    // HL: the refill inside the time loop forms no product.  The lane carries the address of its element in the block the
+    // next rotation loads (64 bits, as an integer: it runs past the array behind the read's last row and is then not used as
+    // an address) and adds a wave-uniform step of RPR rows per rotation; "row < T" is the block's first row (scalar) against
+    // T - fg, which is 0 on a lane that holds no FIFO element -- and T is 0 for a half without a read.
+    static_assert(!HL || !H16, "the running address counts in binary32 elements");
+    const int64_t refill_step = (int64_t)RPR * st_t * (int64_t)sizeof(float);
+    uintptr_t refill_at = reinterpret_cast<uintptr_t>(post_w)
+        + (uintptr_t)((half_stride + (int64_t)((kFifo + 1) * RPR + fg) * st_t + fs * st_s + fc * st_n) * (int64_t)sizeof(float));
+    const int refill_rows = f_lane ? T - fg : 0;
     int g = 0;    // row within the front block (wave-uniform)
     int gE = 0;   // g * E, carried along instead of multiplied out
     int blk = 0;  // index of the front block (wave-uniform)
@@ -426,7 +455,11 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_pe
     // HL: the lane-constant masks the step's votes are joined with (beam_wave_step.inc)
     const uint64_t child_m = HL ? ballot(is_child) : 0ull;
     const uint64_t self_m = HL ? ballot(is_self) : 0ull;
-    const uint64_t collapse_m = (HL && collapse) ? ~0ull : 0ull;
+    // (all ones or zero.  Opaque: the optimiser knows the two values and joins a vote with it by s_and_b64 ..., exec and two
+    // s_cselect_b32 -- three scalar instructions per use where one s_and_b64 does)
+    int collapse_w = (HL && !CRF) ? __builtin_amdgcn_readfirstlane(collapse ? -1 : 0) : 0;
+    if (HL && !CRF) FCD_OPAQUE_S(collapse_w);  // (CRF: no repeat-stay at all, and every vote joined with the mask folds away)
+    const uint64_t collapse_m = ((uint64_t)(uint32_t)collapse_w << 32) | (uint32_t)collapse_w;
     // HL: the two bounds of the rank-domain guard (device_utils.h), held in scalar registers across the time loop
     float rankf_lo = kRankfALo, rankf_hi = kRankfAHi;
     if (HL) {
@@ -457,22 +490,40 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_pe
         o_pk = bpermf(rbase + (is_child ? k : 0), win[0]);
         o_ptip = CRF ? 0.0f : __int_as_float(__builtin_amdgcn_ds_bpermute((rbase << 2) + tipf, __float_as_int(win[0])));
     };
+    // HL: the time loop carries `depth` shifted up by 8 -- the form the survivor-table entry and the dead-row test want, and
+    // the hand-over word `meta` keeps its depth field at bit 8: no shift of the depth is left in the step.  (The entry already
+    // bounds the depth by 2^23.)
+    constexpr int kDsh = HL ? 8 : 0;
+    if (HL) depth <<= kDsh;
     float pk_next = 0.0f, ptip_next = 0.0f;
     if (!GATHER) fetch_row(pk_next, ptip_next);
     // the row FIFO moves on to step t + 1 (the values step t needs were fetched at the end of step t - 1)
     auto advance_fifo = [&]() __attribute__((always_inline)) {
         gE += E;
-        if (!GATHER && ++g == RPR) {
+        // (HL: one step in RPR -- said so, or the optimiser, once the refill is this short, hangs the test on the loop's latch
+        // and shifts the whole FIFO forth and back in every step)
+        if (HL ? __builtin_expect(++g == RPR, RPR == 1) : (!GATHER && ++g == RPR)) {
             g = 0;
             gE = 0;
+            if (HL && RPR > 1) {  // (a rotation in every step is left to the compiler)
+                // wait for the block launched one rotation ago BEFORE launching the next one, as below
+                __builtin_amdgcn_s_waitcnt(0x0F70);
+                fifo_shift(win, incoming);
+            } else {
 #pragma unroll
             for (int j = 0; j + 1 < kFifo; ++j) win[j] = win[j + 1];
             // wait for the block launched one rotation ago BEFORE launching the next one (vmcnt
             // counts in order: a wait placed after the new load would wait for it as well)
             __builtin_amdgcn_s_waitcnt(0x0F70);
             win[kFifo - 1] = incoming;
+            }
             ++blk;
-            incoming = load_block(blk + kFifo);
+            if (HL) {
+                incoming = (blk + kFifo) * RPR < refill_rows ? FCD_GLOBAL_F32(refill_at) : 0.0f;
+                refill_at += (uintptr_t)refill_step;
+            } else {
+                incoming = load_block(blk + kFifo);
+            }
         }
     };
     {
@@ -482,6 +533,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_pe
         }
     }
     if (HL) alive = lane_in(alive_m, lane);
+    if (HL) depth >>= kDsh;
     if (!SES) r = read_index_again();
     if (PROF && lane == 0 && p.a.prof) {
         uint32_t *o = p.a.prof + ((int64_t)blockIdx.x * kWavesPerBlock + wave) * 8;

@@ -78,7 +78,13 @@
         // (A NaN key is garbage but non-zero: it only ever ranks when it is the read's lone candidate, :262.  Its
         // probability word may be 0 -- the negative NaN with an all-ones payload -- so "is a candidate" stays key != 0.)
         const int idk = is_self ? node : (is_new ? tks + q : cid);
-        uint64_t key = (UNI ? valid : (valid && act)) ? make_key(prob, idk) : 0ull;
+        // kRawTop (HL): what the candidate leaves next to its survivor-table entry is its probability as make_key() takes it,
+        // prob + 0.0f -- formed once, in front of the key's exec region, for both (formed again from the key where a tie replay
+        // has parked the step's registers)
+        float pcanon = prob + 0.0f;
+        if (kRawTop) FCD_OPAQUE_VQ(pcanon);
+        int pword = kRawTop ? __float_as_int(pcanon) : 0;
+        uint64_t key = (UNI ? valid : (valid && act)) ? (kRawTop ? make_key_canonical(pcanon, idk) : make_key(prob, idk)) : 0ull;
         // R32: the probability word and the node word go to two tables (beam_wave.hip), one ds_write2_b32; the rank below
         // is taken on the probability word alone, and candidates of equal probability are told apart only in the step's
         // rare branch, when the survivor table shows that two KEPT ones met (settle_table).
@@ -162,9 +168,9 @@
             // vote instead of a second region inside the first
             if (is_new) *at32(rec_w, hoff + (uint32_t)newid) = ((node + 1) << 3) | l;
             static_assert(kSeg == 64, "(depth + 1) % kSeg == 0 as a compare of the low six bits");
-            const uint64_t m_head = m_new & ballot((depth & (kSeg - 1)) == kSeg - 1);
+            const uint64_t m_head = m_new & ballot((depth & ((kSeg - 1) << kDsh)) == ((kSeg - 1) << kDsh));
             if (__builtin_expect(m_head != 0ull, 0)) {
-                if (lane_in(m_head, lane)) *at32(jmp_w, hoff + (uint32_t)newid) = (depth % kSeg == 0) ? node : jump;
+                if (lane_in(m_head, lane)) *at32(jmp_w, hoff + (uint32_t)newid) = ((depth >> kDsh) % kSeg == 0) ? node : jump;
             }
         } else if (is_new) {
             *at32(rec_w, hoff + (uint32_t)newid) = ((node + 1) << 3) | l;
@@ -256,7 +262,8 @@
         // HL: the same test on masks -- a half runs when alive_m says so.  A NaN's word is outside the rank domain whatever
         // its sign and payload (fcd_rankf_outside_m), so the guard's vote stands in for "some candidate is a NaN" here and the
         // every-step path takes no vote on prob != prob: a guarded step without a NaN enters the block and leaves it unchanged.
-        if (HL ? ((((ballot(n_valid == 0)) | m_guard) & alive_m) != 0ull)
+        // (HL: marked unlikely, so that the block sits behind the loop and the every-step path falls through)
+        if (HL ? __builtin_expect((((ballot(n_valid == 0)) | m_guard) & alive_m) != 0ull, 0)
                : (ballot(act && (n_valid == 0 || is_nan)) != 0ull)) {
             const bool act = HL ? lane_in(alive_m, lane) : act0;
             const uint64_t m_nan = ballot(is_nan);
@@ -288,7 +295,7 @@
         // Survivor table: entry r = the lane whose candidate took rank r.  LDS executes a wavefront's operations
         // in order, so the store, the read-back and the two look-ups below share ONE round trip (a ds_permute
         // to the new slot followed by a broadcast to its group were two dependent ones).
-        const int depc = depth + (is_child ? 1 : 0);
+        const int depc = depth + (is_child ? (1 << kDsh) : 0);  // (HL: depth and depc are shifted up by kDsh = 8)
         bool sel;
         int selflag, fate, own, src_a, e_min, top_a, gp_a;
         int child_s;  // the entry after this step's bookkeeping
@@ -316,16 +323,16 @@
             // ds_write2_b32 under the mask the step already holds -- no test of the rank at all.
             // DSRC: the exact-rank instantiations leave the probability word next to the entry as well (the same
             // ds_write2_b32) -- rank 0's is the step's divisor, and it comes back with the table's own round trip.
-            const int ent = ent_lo | (depc << 8);
+            const int ent = ent_lo | (HL ? depc : depc << 8);
             if (PDQ) {
                 if (valid && go) {
                     srcs[rank] = ent;
-                    srcs[kTie + rank] = (int)(uint32_t)(key >> 32);
+                    srcs[kTie + rank] = kRawTop ? pword : (int)(uint32_t)(key >> 32);
                 }
             } else if (DSRC) {
                 if (sel) {
                     srcs[rank] = ent;
-                    srcs[kTop + rank] = (int)(uint32_t)(key >> 32);
+                    srcs[kTop + rank] = kRawTop ? pword : (int)(uint32_t)(key >> 32);
                 }
             } else {
                 if (sel) srcs[rank] = ent;
@@ -347,13 +354,25 @@
                 clash = sel && back != ent;
                 if (HL) m_clash_t = m_sel & ballot(back != ent);
             }
+            // (HL: the two look-ups are written behind the table's reads, below -- the reads of neighbouring words are merged
+            // only while no other LDS operation stands between them)
+            if (!HL) {
             fate = HL ? __builtin_amdgcn_ds_bpermute(tgt_a, selflag) : bperm(hbase + mslot * GW, selflag);
             own = bperm(grp0, selflag);  // ... and this group's own candidate?
+            }
             // every lane of new group i learns its source lane (stale beyond the new beam: unused), where the best
             // candidate sits, and the SMALLEST DEPTH in the new beam: a stale entry can only lower it
+            if (HL) {
+                // (the entries and the divisor first, in table order, ahead of every other LDS operation of the block: they
+                // then come back as one ds_read_b128 and one ds_read2_b32)
+                e_min = srcs[0];
+#pragma unroll
+                for (int j = 1; j < BCAP; ++j) e_min = min(e_min, srcs[j]);
+                top = __int_as_float(srcs[kTop]);
+            }
             const int e_src = srcs[PDQ ? i_src : i];
             src_a = e_src & (DSRC ? 0xFC : 0xFF);  // byte address, as ds_bpermute wants it
-            e_min = srcs[0];
+            if (!HL) e_min = srcs[0];
             top_a = e_min & 0xFF;
             if (DSRC) {
                 // beam[0].probability() (:278) is rank 0's candidate probability: read off its sort key (read again by a
@@ -361,16 +380,27 @@
                 // the rare block).  The gap quotient of the new slot waits on the source group's spare lane when the
                 // source is a slot's own lane, and on the half's first idle lane (0 / top) when it is a child lane:
                 // bit 0 of the entry says which.
-                top = key_prob((uint32_t)srcs[kTop]);
-                if (HL) {  // (a bit-field select: bit 0 spread over the word picks between the two addresses)
-                    const int m_ch = (int)((uint32_t)e_src << 31) >> 31;
+                // (kRawTop: the word IS the probability, stored by the lane that held it)
+                // (read behind the entries, below: the table then comes back as one ds_read_b128 and one ds_read2_b32)
+                if (!kRawTop) top = key_prob((uint32_t)srcs[kTop]);
+                if (HL) {
+                    // a bit-field select: bit 0 spread over the word (v_bfe_i32) picks between the two addresses (v_bfi_b32).
+                    // (Opaque: the optimiser otherwise rewrites it as v_and 1 / v_cmp_eq -> vcc / v_cndmask on vcc.)
+                    int m_ch = (int)((uint32_t)e_src << 31) >> 31;
+                    FCD_OPAQUE_VQ(m_ch);
                     gp_a = (m_ch & zero_a) | (~m_ch & (src_a + ((GW - 1) << 2)));
                 } else {
                     gp_a = (e_src & 1) ? zero_a : src_a + ((GW - 1) << 2);
                 }
             }
+            if (!HL) {
 #pragma unroll
             for (int j = 1; j < BCAP; ++j) e_min = min(e_min, srcs[j]);
+            }
+            if (HL) {
+                fate = __builtin_amdgcn_ds_bpermute(tgt_a, selflag);
+                own = bperm(grp0, selflag);
+            }
             if (PDQ) {
                 tie0 = (uint32_t)srcs[kTie + i_src];
                 tie1 = (uint32_t)srcs[kTie + i_src + 1];
@@ -384,14 +414,14 @@
         const int tipfc = is_self ? tipf : (k << 2);
         int statec = (CRF && !is_self) ? (GATHER ? ((state * NL) & s_mask) + l : (state * NL) % (S > 0 ? S : 1) + l)
                                              : state;  // :97
-        int jumpc = HL ? (lane_in(~self_m & ballot((depth & (kSeg - 1)) == 0), lane) ? node : jump)  // (one select, on a mask)
+        int jumpc = HL ? select_on_pair(~self_m & ballot((depth & ((kSeg - 1) << kDsh)) == 0), lane, node, jump)  // (one select, on a mask)
                        : (is_self ? jump : ((depth % kSeg == 0) ? node : jump));
         // 0 self, 1 a child entering the beam for the first time, 2 a child that has been there before (EVER:
         // its row is in HBM); read off the entry BEFORE it is marked below
         const int kind = is_child ? 1 + ((child_in >> 30) & 1) : 0;
         // HL: kind and tip label of a child lane are one constant plus the entry's EVER bit.  (A lane that is neither a slot's
         // own nor a child lane holds no candidate: it is never a source, and what it packs here is never gathered.)
-        int meta = HL ? ((depc << 5) | (is_self ? tipf : kind1 + ((child_in >> 30) & 1))) : (kind | tipfc | (depc << 5));
+        int meta = HL ? (depc | (is_self ? tipf : kind1 + ((child_in >> 30) & 1))) : (kind | tipfc | (depc << 5));
         // DSRC: every lane divides what it holds, HERE, before the gather: a candidate lane its label probability, a
         // group's spare lane the gap probability of the slot's own candidate (it received the blank column like the
         // slot's own lane and computed the same sgp), the half's idle lanes 0 -- a child candidate's gap probability.
@@ -417,11 +447,11 @@
                 // parent, so it needs a proper ancestor in the beam -- none exists once every beam entry is at least as
                 // deep as the node, and then none ever will (its ancestors have left for good, top-down from the
                 // root).  Three evicted rows in four are dead by this test and are never written.
-                const bool dead = (depth << 8) <= e_min;  // e_min = (minimum depth << 8) | a lane address
                 if (HL) {  // ONE exec region, its mask joined in scalar registers
-                    if (lane_in(child_m & m_grp & ballot(own == 0) & ballot((depth << 8) > e_min), lane))
+                    if (lane_in(child_m & m_grp & ballot(own == 0) & ballot(depth > e_min), lane))
                         *at32(rows_w, (hoff + (uint32_t)(node + 1)) * RW + l) = child_s;
                 } else {
+                const bool dead = (depth << 8) <= e_min;  // e_min = (minimum depth << 8) | a lane address
                 if (upd && grp && own == 0 && !dead)
                     *at32(rows_w, (hoff + (uint32_t)(node + 1)) * RW + l) = child_s;  // (beam-position bits and all: stripped when read back)
                 }
@@ -620,6 +650,7 @@
                         // the lane's own key, from the two word tables it wrote at the top of the step (a lane without a
                         // candidate reads the idle word: 0, 0)
                         if (R32) key = ((uint64_t)kwords[kslot] << 32) | kwords[kslot + kNodeTab];
+                        if (kRawTop) pword = __float_as_int(key_prob((uint32_t)(key >> 32)));
                     } else {
                     if (mine && key != 0ull) list[pos] = (key & 0xFFFFFFFF00000000ull) | (uint32_t)lane_r;
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -746,7 +777,7 @@
             node = n_node;
             lp = q_lp;
             gp = q_gp;
-            depth = n_meta >> 5;
+            depth = HL ? (n_meta & ~0xFF) : (n_meta >> 5);  // (HL: still shifted up by 8)
             jump = n_jump;
             child = n_child;
             B = Bn;

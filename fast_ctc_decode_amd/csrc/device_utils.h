@@ -61,15 +61,26 @@ __device__ __forceinline__ float load_post(const float *base, int64_t idx, int d
     return dtype == kF16 ? f16_bits_to_f32(h) : bf16_bits_to_f32(h);
 }
 
+// The float at a device address held as an integer (a lane's running address into the posteriors).  A GLOBAL load: through a
+// generic pointer it is a flat load, which counts on the LDS counter as well and turns every LDS wait behind it into a full one.
+#ifdef FCD_HIPEMU  // (lockstep emulation, tests/hipemu: plain C++)
+#define FCD_GLOBAL_F32(addr) (*reinterpret_cast<const float *>(addr))
+#else
+#define FCD_GLOBAL_F32(addr) (*(const __attribute__((address_space(1))) float *)(addr))
+#endif
+
 // Sort key for the prune step: descending probability, ties -> ascending node index
 // (src/search.rs:245 stable sort by node followed by :262-269 sort by probability; see
 // SURVEY.md 8a A4).  Larger key == earlier in the beam.  prob must not be NaN.
-__device__ __forceinline__ uint64_t make_key(float prob, int node) {
-    float p = prob + 0.0f;  // -0.0 -> +0.0 so that equal floats give equal keys
+// (p: the probability with -0.0 already taken to +0.0, prob + 0.0f)
+__device__ __forceinline__ uint64_t make_key_canonical(float p, int node) {
     uint32_t u = __float_as_uint(p);
     u ^= (u & 0x80000000u) ? 0xFFFFFFFFu : 0x80000000u;  // total order on non-NaN floats
     uint32_t lo = 0x7FFFFFFFu - (uint32_t)node;           // node >= -1; smaller node -> larger lo
     return ((uint64_t)u << 32) | lo;
+}
+__device__ __forceinline__ uint64_t make_key(float prob, int node) {
+    return make_key_canonical(prob + 0.0f, node);  // -0.0 -> +0.0 so that equal floats give equal keys
 }
 
 // Loads that must observe this wave's own earlier global stores made from other lanes:
@@ -319,10 +330,31 @@ __device__ __forceinline__ bool lane_in(uint64_t m, int lane) {
 #endif
 }
 
+// `yes` on the lanes of mask m, `no` elsewhere, as ONE v_cndmask_b32 whose mask is an SGPR pair.  Written out: left to the
+// register allocator, a mask that an s_and_b64 has just formed may land in VCC and the select take its VCC form, which
+// tools/microbench/issue_cost.hip prices apart from the SGPR-pair form.
+__device__ __forceinline__ int select_on_pair(uint64_t m, int lane, int yes, int no) {
+#ifdef FCD_HIPEMU  // (lockstep emulation, tests/hipemu: plain C++)
+    return ((m >> lane) & 1ull) != 0ull ? yes : no;
+#else
+    int r;
+    asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(no), "v"(yes), "s"(m));
+    return r;
+#endif
+}
+
 // Makes a value opaque to the optimiser and pins it in vector registers (the duplex kernel's coefficient table).
 // (tests/hipemu predefines FCD_OPAQUE_V as a no-op.)
 #ifndef FCD_OPAQUE_V
 #define FCD_OPAQUE_V(x) asm volatile("" : "+v"(x))
+#endif
+
+// The same without `volatile`: the value is opaque, but the statement is no barrier -- an `asm volatile` has unmodelled side
+// effects, and LDS reads on its two sides are not merged into one wider read.
+#ifdef FCD_HIPEMU  // (lockstep emulation, tests/hipemu: plain C++)
+#define FCD_OPAQUE_VQ(x) ((void)(x))
+#else
+#define FCD_OPAQUE_VQ(x) asm("" : "+v"(x))
 #endif
 
 // Cycle stamp for the instrumented (PROF) kernel instantiations: reads the shader clock once every input

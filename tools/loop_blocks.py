@@ -23,6 +23,10 @@ split is as good as the landmarks):
   gather + division         .. the last ds_bpermute_b32 in front of the kind field's v_and_b32 ..., 3, ...
   rare-branch vote          .. the scalar branch to the rare block
   commit                    .. the loop's backward branch
+A last line counts the forms priced one by one in profiles/r15a_issue_cost.txt: selects on VCC, 64-bit vector shifts and moves,
+scalar branches that are TAKEN on the every-step path (the forward branches it jumps with), and the rotation path -- its length
+and its integer multiplies -- wherever the compiler put it (skipped inline, or behind the loop).  LOOP_DUMP=file writes the
+every-step path and the blocks off it as text.
 Classes (profiles/r12a_issue_cost.txt, r14a_issue_cost.txt, six wavefronts per SIMD): cheap VALU = plain f32 arithmetic and
 32-bit add / sub / logic / move, about 1.2 - 1.4 ns; expensive VALU = every other vector ALU instruction (compares into a
 scalar pair, selects, shifts, carry forms, three-operand integer forms, conversions, the division's special forms), about
@@ -80,9 +84,12 @@ def every_step_path(ins):
     body = min(loops, key=len)
     lo, hi = body[0][0], body[-1][0]
     path, skip_to = [], None
+    skipped = []  # what each taken forward branch jumps over, in address order
+    outside = []
     for addr, op, args in body:
         if skip_to is not None:
             if addr < skip_to:
+                skipped[-1].append((addr, op, args))
                 continue
             skip_to = None
         path.append((addr, op, args))
@@ -90,7 +97,22 @@ def every_step_path(ins):
             t = target(addr, args)
             if addr < t <= hi:
                 skip_to = t
-    return path
+                skipped.append([])
+            elif t > hi:
+                # a block behind the loop that comes back into it (an unlikely block moved out of line): not on the every-step
+                # path and not a taken branch, but listed, so that the rotation path is found wherever it was placed
+                out = []
+                for x in ins:
+                    if x[0] < t:
+                        continue
+                    out.append(x)
+                    if x[1] == "s_branch":
+                        if lo <= target(x[0], x[2]) <= hi:
+                            outside.append(out)
+                        break
+                    if x[1] == "s_endpgm" or len(out) > 400:
+                        break
+    return path, skipped, outside
 
 
 def split(path):
@@ -146,7 +168,7 @@ def classify(op):
 def main():
     obj, pat = sys.argv[1], sys.argv[2]
     label = sys.argv[3] if len(sys.argv) > 3 else pat
-    path = every_step_path(kernel(disasm(obj), pat))
+    path, skipped, outside = every_step_path(kernel(disasm(obj), pat))
     ends = split(path)
     cols = ["cheap", "exp", "salu", "lds", "vmem", "saveexec", "branch", "all"]
     print("# %s: every-step path of the time loop, %d instructions" % (label, len(path)))
@@ -183,6 +205,27 @@ def main():
               len(v01), round_trips, sum(re.match(r"v_cmp\w*_[uif]64", op) is not None for op, _ in txt),
               sum(op == "s_mov_b32" and re.search(r"0x[0-9a-f]{5,}", a) is not None for op, a in txt)))
     print("# VALU %d (cheap %d + expensive %d), SALU %d" % (tot["cheap"] + tot["exp"], tot["cheap"], tot["exp"], tot["salu"]))
+    # Forms priced one by one in profiles/r15a_issue_cost.txt.  A VCC-form select: v_cndmask_b32 in its e32 / dpp / sdwa encoding
+    # (the mask is VCC by encoding) or an e64 whose pair operand is spelled vcc.  The rotation path: what the taken forward
+    # branch in front of the row FIFO's refill jumps over (the skipped region that holds the refill's global_load), or the
+    # block behind the loop that holds it when the rotation was moved out of line.
+    base = lambda op: re.sub(r"_(e32|e64|dpp|sdwa)$", "", op)
+    vcc_sel = sum(base(op) == "v_cndmask_b32" and (not op.endswith("_e64") or a.rstrip().endswith("vcc")) for op, a in txt)
+    wide = sum(re.match(r"v_(lshrrev|lshlrev|ashrrev|mov)_b64|v_ashrrev_i64", base(op)) is not None for op, _ in txt)
+    rot = next((r for r in skipped + outside if any(op.startswith(("global_load", "flat_load")) for _, op, _ in r)), [])
+    muls = sum(re.match(r"v_(mul_lo_u32|mul_hi_[ui]32|mad_[ui]64_[ui]32|mul_[ui]32_[ui]24|mad_[ui]32_[ui]24)", op) is not None
+               for _, op, _ in rot)
+    print("# VCC-form selects: %d; 64-bit vector shifts and moves: %d; taken scalar branches: %d;"
+          " rotation path: %d instructions, integer multiplies on it: %d" % (vcc_sel, wide, len(skipped), len(rot), muls))
+    import os
+    if os.environ.get("LOOP_DUMP"):  # the two paths as text, for reading next to the source
+        with open(os.environ["LOOP_DUMP"], "w") as f:
+            for a, op, ar in path:
+                f.write("%6x  %s %s\n" % (a, op, ar))
+            for r in skipped + outside:
+                f.write("---- jumped over / out of line ----\n")
+                for a, op, ar in r:
+                    f.write("%6x  %s %s\n" % (a, op, ar))
 
 
 main()

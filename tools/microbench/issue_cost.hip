@@ -8,7 +8,7 @@
 // A workgroup is four wavefronts, one per SIMD; a dummy dynamic LDS array lets exactly W workgroups share a CU.
 // The only store is one word per wavefront (its s_memtime interval).  HIP events around the launch give the wall time of the
 // same work, and with one wavefront per SIMD the shader clock.
-// About 360 launches (two per class, form and W) of 50 us to 2.4 ms: a third of a second of GPU time in all.
+// About 700 launches (two per class, form and W) of 50 us to 2.4 ms: two thirds of a second of GPU time in all.
 //   hipcc --offload-arch=gfx950 -O3 issue_cost.hip -o issue_cost      ./issue_cost [trips, default 1024]
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -68,6 +68,31 @@
 // an exec region around one vector instruction whose s_cbranch_execz is not taken (the mask is exec itself)
 #define I_SAVEEXEC(d, m, s)  "s_and_saveexec_b64 %" #m ", exec\n\ts_cbranch_execz 1f\n\tv_add_u32 %" #d ", %12, %" #d "\n\t" \
                              "1:\n\ts_or_b64 exec, exec, %" #m "\n\t"
+// r15: forms on the headline step's hot path that the rows above do not price.  The VCC select is priced three ways: behind a
+// vector compare that writes VCC, behind a scalar instruction that writes VCC (both as the kernel has them; the plain row above
+// never writes VCC inside its loop), and in the e64 encoding with VCC spelled as its pair operand.
+#define I_CMP_CND_VCC(d, m, s)  "v_cmp_gt_u32 vcc, %12, %" #d "\n\tv_cndmask_b32_e32 %" #d ", %12, %" #d ", vcc\n\t"  // 2
+#define I_SAND_CND_VCC(d, m, s) "s_and_b64 vcc, %" #m ", exec\n\tv_cndmask_b32_e32 %" #d ", %12, %" #d ", vcc\n\t"  // 2
+#define I_CMP_CND_SGPR(d, m, s) "v_cmp_gt_u32_e64 %" #m ", %12, %" #d "\n\tv_cndmask_b32_e64 %" #d ", %12, %" #d ", %" #m "\n\t"  // 2 (the pair to set the VCC pair against)
+#define I_CND_E64_VCC(d, m, s)  "v_cndmask_b32_e64 %" #d ", %12, %" #d ", vcc\n\t"
+#define I_MUL_LO(d, m, s)       "v_mul_lo_u32 %" #d ", %12, %" #d "\n\t"
+#define I_DIV_SCALE(d, m, s)    "v_div_scale_f32 %" #d ", vcc, %12, %12, %" #d "\n\t"
+#define I_RCP(d, m, s)          "v_rcp_f32 %" #d ", %" #d "\n\t"
+#define I_DIV_FMAS(d, m, s)     "v_div_fmas_f32 %" #d ", %" #d ", %12, %13\n\t"
+#define I_DIV_FIXUP(d, m, s)    "v_div_fixup_f32 %" #d ", %" #d ", %12, %13\n\t"
+// a scalar compare and its branch to the next instruction: taken (the compare holds) against not taken
+#define I_BR_TAKEN(d, m, s)     "s_cmp_eq_u32 %" #s ", %" #s "\n\ts_cbranch_scc1 1f\n\t1:\n\t"  // 2
+#define I_BR_NOT(d, m, s)       "s_cmp_lg_u32 %" #s ", %" #s "\n\ts_cbranch_scc1 1f\n\t1:\n\t"  // 2
+// 64-bit forms: %0-%3 four 64-bit VGPR accumulators, %4-%7 four SGPR pairs, %8 %9 two 32-bit VGPR inputs, %10 a 64-bit VGPR input
+#define OPS64 : "+v"(w0), "+v"(w1), "+v"(w2), "+v"(w3), "+s"(m0), "+s"(m1), "+s"(m2), "+s"(m3) : "v"(y0), "v"(y1), "v"(z0) : "vcc", "scc"
+#define IND4_64(M) M(0, 4) M(1, 5) M(2, 6) M(3, 7)
+#define IND16_64(M) IND4_64(M) IND4_64(M) IND4_64(M) IND4_64(M)
+#define DEP16_64(M) M(0, 4) M(0, 4) M(0, 4) M(0, 4) M(0, 4) M(0, 4) M(0, 4) M(0, 4) M(0, 4) M(0, 4) M(0, 4) M(0, 4) M(0, 4) M(0, 4) M(0, 4) M(0, 4)
+#define J_LSHR_B64_S(d, m)  "v_lshrrev_b64 %" #d ", %8, %" #m "\n\t"   // scalar pair source, as the step has it (no chain through it)
+#define J_LSHR_B64_V(d, m)  "v_lshrrev_b64 %" #d ", 1, %" #d "\n\t"
+#define J_MOV_B64(d, m)     "v_mov_b64 %" #d ", %" #m "\n\t"
+#define J_MAD_U64(d, m)     "v_mad_u64_u32 %" #d ", %" #m ", %8, %9, %" #d "\n\t"
+#define J_LSHL_ADD_U64(d, m) "v_lshl_add_u64 %" #d ", %" #d ", 2, %10\n\t"
 // the pair the rank count is made of today, consumer four instructions behind its producer
 #define I_CMP_ADDC_PAIR "v_cmp_gt_u32_e64 %4, %12, %0\n\tv_cmp_gt_u32_e64 %5, %12, %1\n\tv_cmp_gt_u32_e64 %6, %12, %2\n\tv_cmp_gt_u32_e64 %7, %12, %3\n\t" \
                         "v_addc_co_u32_e64 %0, vcc, 0, %0, %4\n\tv_addc_co_u32_e64 %1, vcc, 0, %1, %5\n\t"                                                   \
@@ -77,7 +102,9 @@ enum {
     C_FMA, C_FMA_CLAMP, C_ADD_F32, C_MUL_F32, C_CVT_U32, C_ADD_U32, C_SUB_U32, C_AND, C_LSHL, C_ALIGNBIT, C_BFE, C_LSHL_ADD,
     C_AND_OR, C_BCNT, C_MIN3, C_CMP_VCC, C_CMP_U32, C_CMP_F32, C_CMP_U64, C_ADDC, C_CND_VCC, C_CND_SGPR, C_MBCNT, C_READLANE,
     C_DPP, C_SALU, C_SALU_VALU, C_MIN_U32, C_MAX_U32, C_CMP_CLASS, C_BFI, C_BCNT1_CSEL, C_SAVEEXEC, C_CMP_ADDC, C_FDIV, C_RANK_NOW,
-    C_RANK_F, C_RANK_I, C_RANK_S, C_RANK_P, C_COUNT
+    C_RANK_F, C_RANK_I, C_RANK_S, C_RANK_P,
+    C_CMP_CND_VCC, C_SAND_CND_VCC, C_CMP_CND_SGPR, C_CND_E64_VCC, C_MUL_LO, C_DIV_SCALE, C_RCP, C_DIV_FMAS, C_DIV_FIXUP, C_BR_TAKEN, C_BR_NOT,
+    C_LSHR_B64_S, C_LSHR_B64_V, C_MOV_B64, C_MAD_U64, C_LSHL_ADD_U64, C_COUNT
 };
 struct Cls { const char *name; int per_trip_ind, per_trip_dep; const char *unit; };
 // instructions (or units) one loop trip issues per wavefront
@@ -98,6 +125,14 @@ static const Cls kCls[C_COUNT] = {
     {"RANK now: 25 x (v_cmp_e64 + v_addc)", 1, 0, "block"}, {"RANK F: 25 x (v_fma clamp + v_add_f32) + cvt", 1, 0, "block"},
     {"RANK I: 25 x (v_sub + v_alignbit) + bcnt + sub", 1, 0, "block"}, {"RANK S: scalar full adder, 3 cmp + 2 addc + 5 salu", 1, 0, "block"},
     {"RANK P: 12 x (v_pk_fma_f32 clamp + v_pk_add_f32) + 1 + halves + cvt", 1, 0, "block"},
+    {"v_cmp_gt_u32 -> vcc + v_cndmask_b32_e32 on vcc (per pair)", 16, 16, "pair"},
+    {"s_and_b64 vcc + v_cndmask_b32_e32 on vcc (per pair)", 16, 16, "pair"},
+    {"v_cmp_gt_u32_e64 -> sgpr pair + v_cndmask_b32_e64 on it (per pair)", 16, 16, "pair"},
+    {"v_cndmask_b32_e64 with vcc as its pair operand", 16, 16, "inst"}, {"v_mul_lo_u32", 16, 16, "inst"},
+    {"v_div_scale_f32", 16, 16, "inst"}, {"v_rcp_f32", 16, 16, "inst"}, {"v_div_fmas_f32", 16, 16, "inst"}, {"v_div_fixup_f32", 16, 16, "inst"},
+    {"s_cmp + s_cbranch_scc1 taken (per pair)", 16, 0, "pair"}, {"s_cmp + s_cbranch_scc1 not taken (per pair)", 16, 0, "pair"},
+    {"v_lshrrev_b64 <- sgpr pair", 16, 0, "inst"}, {"v_lshrrev_b64 <- vgpr pair", 16, 16, "inst"}, {"v_mov_b64 <- sgpr pair", 16, 0, "inst"},
+    {"v_mad_u64_u32", 16, 16, "inst"}, {"v_lshl_add_u64", 16, 16, "inst"},
 };
 
 #define T0 asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t0) : : "memory")
@@ -106,6 +141,12 @@ static const Cls kCls[C_COUNT] = {
     if (C == ID) {                                                                                  \
         if (!DEP) { for (int i = 0; i < trips; ++i) asm volatile(IND16(M) OPS); }                   \
         else { for (int i = 0; i < trips; ++i) asm volatile(DEP16(M) OPS); }                        \
+    }
+
+#define STREAM_CASE64(ID, M)                                                                        \
+    if (C == ID) {                                                                                  \
+        if (!DEP) { for (int i = 0; i < trips; ++i) asm volatile(IND16_64(M) OPS64); }              \
+        else { for (int i = 0; i < trips; ++i) asm volatile(DEP16_64(M) OPS64); }                   \
     }
 
 template <int C, bool DEP>
@@ -127,6 +168,15 @@ __global__ __launch_bounds__(256) void k(uint32_t *cyc, int trips, uint32_t a, f
     STREAM_CASE(C_DPP, I_DPP) STREAM_CASE(C_SALU, I_SALU) STREAM_CASE(C_SALU_VALU, I_SALU_VALU)
     STREAM_CASE(C_MIN_U32, I_MIN_U32) STREAM_CASE(C_MAX_U32, I_MAX_U32) STREAM_CASE(C_CMP_CLASS, I_CMP_CLASS) STREAM_CASE(C_BFI, I_BFI)
     STREAM_CASE(C_BCNT1_CSEL, I_BCNT1_CSEL) STREAM_CASE(C_SAVEEXEC, I_SAVEEXEC)
+    STREAM_CASE(C_CMP_CND_VCC, I_CMP_CND_VCC) STREAM_CASE(C_SAND_CND_VCC, I_SAND_CND_VCC) STREAM_CASE(C_CMP_CND_SGPR, I_CMP_CND_SGPR)
+    STREAM_CASE(C_CND_E64_VCC, I_CND_E64_VCC) STREAM_CASE(C_MUL_LO, I_MUL_LO) STREAM_CASE(C_DIV_SCALE, I_DIV_SCALE) STREAM_CASE(C_RCP, I_RCP)
+    STREAM_CASE(C_DIV_FMAS, I_DIV_FMAS) STREAM_CASE(C_DIV_FIXUP, I_DIV_FIXUP) STREAM_CASE(C_BR_TAKEN, I_BR_TAKEN) STREAM_CASE(C_BR_NOT, I_BR_NOT)
+    if (C >= C_LSHR_B64_S && C <= C_LSHL_ADD_U64) {
+        uint64_t w0 = z0, w1 = z1, w2 = z0 + 5, w3 = z1 + 7;
+        STREAM_CASE64(C_LSHR_B64_S, J_LSHR_B64_S) STREAM_CASE64(C_LSHR_B64_V, J_LSHR_B64_V) STREAM_CASE64(C_MOV_B64, J_MOV_B64)
+        STREAM_CASE64(C_MAD_U64, J_MAD_U64) STREAM_CASE64(C_LSHL_ADD_U64, J_LSHL_ADD_U64)
+        asm volatile("" : : "v"(w0), "v"(w1), "v"(w2), "v"(w3));
+    }
     if (C == C_CMP_ADDC) {
         for (int i = 0; i < trips; ++i) asm volatile(I_CMP_ADDC_PAIR I_CMP_ADDC_PAIR OPS);
     }
@@ -146,7 +196,7 @@ __global__ __launch_bounds__(256) void k(uint32_t *cyc, int trips, uint32_t a, f
         }
         asm volatile("" : : "v"(f0), "v"(f1), "v"(f2), "v"(f3));
     }
-    if (C >= C_RANK_NOW) {
+    if (C >= C_RANK_NOW && C <= C_RANK_P) {
         // 25 comparand words in registers (in the domain of every form: words of positive finite probabilities) and the lane's own
         uint32_t kw[25];
 #pragma unroll
