@@ -1,7 +1,9 @@
 // crf_lattice.h -- what the walks of the lattice of a GIVEN labelling under a CRF model share: crf_lattice.hip (forward
 // sum and best alignment) and crf_posterior.hip (forward and backward).  Parameter block, LDS layout, everything before
 // the time loop (the rows without a value, the labelling and its state trajectory), the staging of the posteriors, the
-// live window of a row and what a lane reads for one forward row.  Included by those translation units only.
+// live window of a row, what a lane reads for one forward row -- and the FORWARD WALK itself (crf_forward_walk: sum, max
+// with back-pointer ballots, sum with stored rows).  What this lattice has in common with the CTC one (k(t), the rotations,
+// ln P, the stored rows, the backward walks' stores) is ctc_lattice.h's.  Included by those translation units only.
 #pragma once
 
 #include <math.h>
@@ -163,16 +165,7 @@ __device__ __forceinline__ void crf_fill_tile(const CrfParams &p, const CrfLds &
                                     p.in.dtype);
         }
     }
-    if (p.band > 0 && lane < rc) {  // k(t) = #{k : path[k] <= t}
-        const uint32_t t = (uint32_t)(t0 + lane);
-        int lo = 0, hi = rw.L;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (rw.path[mid] <= t) lo = mid + 1;
-            else hi = mid;
-        }
-        lds.krow[lane] = lo;
-    }
+    if (p.band > 0 && lane < rc) lds.krow[lane] = labels_up_to(rw.path, rw.L, (uint32_t)(t0 + lane));
     __syncthreads();
 }
 
@@ -241,6 +234,99 @@ __device__ __forceinline__ CrfStep<K> crf_load_step(const CrfParams &p, const Cr
         in.adv_mask |= (adv ? 1u : 0u) << r;
     }
     return in;
+}
+
+// The forward walk, from "row -1" to the final cell: the step and the numerics the head of crf_lattice.hip describes.
+//   kCrfSum    the sum over the alignments (fcd_crf_score_*)
+//   kCrfMax    the best alignment: max for +, and per row K 64-bit ballots "the advance won" in bp; a NaN, infinite or
+//              negative posterior that entered a live cell is flagged in misc[kBadPost] (fcd_crf_align_*)
+//   kCrfStore  the sum, and every row left for a backward walk (crf_posterior.hip): its cells in am by SLOT, scaled by
+//              2^-kAlphaDown (a slot outside the row's window holds 0), its exponent in ae
+// Returns the final cell alpha[L] of the last row (0 outside its window), the same in every lane, at the scale 2^*eacc_out:
+// ln P = ln_p(m, eacc).
+constexpr int kCrfSum = 0, kCrfMax = 1, kCrfStore = 2;
+
+template <int MODE, int K>
+__device__ __forceinline__ float crf_forward_walk(const CrfParams &p, const CrfLds &lds, const CrfRow &rw, uint64_t *bp, float *am,
+                                                  int *ae, int64_t *eacc_out) {
+    constexpr int C = 64 * K;
+    constexpr bool MAX = MODE == kCrfMax;
+    const int lane = threadIdx.x;
+    float a[K];  // alpha of the state each of the lane's K slots holds, scaled by 2^-eacc
+#pragma unroll
+    for (int r = 0; r < K; ++r) a[r] = 0.0f;
+    if (lane == 0) a[0] = 1.0f;  // "row -1": state 0, the one live state
+    int64_t eacc = 0;
+    int lo = 0, hi = 0;
+    uint32_t bad = 0;
+    for (int t0 = 0; t0 < rw.Tr; t0 += p.rows_per_tile) {
+        const int rc = min(p.rows_per_tile, rw.Tr - t0);
+        crf_fill_tile(p, lds, rw, t0, rc);
+        CrfStep<K> in = crf_load_step<K>(p, lds, rw, t0, 0, lo, hi);
+        for (int i = 0; i < rc; ++i) {
+            CrfStep<K> nx = in;
+            if (i + 1 < rc) nx = crf_load_step<K>(p, lds, rw, t0 + i + 1, i + 1, in.lo, in.hi);
+            lo = in.lo;
+            hi = in.hi;
+            if constexpr (MAX) bad |= in.bad;
+            float s[K], v[K];
+#pragma unroll
+            for (int r = 0; r < K; ++r) {
+                s[r] = ((in.stay_mask >> r) & 1) ? a[r] * in.pm0[r] : 0.0f;
+                v[r] = ((in.adv_mask >> r) & 1) ? a[r] * in.pmy[r] : 0.0f;
+            }
+            const float v_in = from_prev_lane(v[K - 1]);
+            const int e_in = int_from_prev_lane(in.pey[K - 1]);
+            float ua[K];
+            int ea[K];
+            int emax = kNoExp;
+#pragma unroll
+            for (int r = 0; r < K; ++r) {
+                ua[r] = r >= 1 ? v[r - 1] : v_in;
+                ea[r] = r >= 1 ? in.pey[r - 1] : e_in;
+                const int e0 = finite_exp(s[r]), e1 = finite_exp(ua[r]);
+                emax = max(emax, e0 != kNoExp ? e0 + in.pe0[r] : kNoExp);
+                emax = max(emax, e1 != kNoExp ? e1 + ea[r] : kNoExp);
+            }
+            emax = wave_imax(emax);
+            const int sh = emax == kNoExp ? 0 : kTarget - emax;
+            eacc -= sh;
+            uint64_t mine = 0;
+            float *row = MODE == kCrfStore ? am + (int64_t)(t0 + i) * C + lane * K : nullptr;
+#pragma unroll
+            for (int r = 0; r < K; ++r) {
+                const float c0 = ldexpf(s[r], min(max(in.pe0[r] + sh, -512), 512));
+                const float c1 = ldexpf(ua[r], min(max(ea[r] + sh, -512), 512));
+                if constexpr (MAX) {
+                    const bool up = c1 > c0;  // the stay candidate is kept unless the advance is strictly greater
+                    a[r] = up ? c1 : c0;
+                    const uint64_t word = __ballot(up);
+                    if (lane == r) mine = word;
+                } else {
+                    a[r] = c0 + c1;
+                }
+                if constexpr (MODE == kCrfStore) row[r] = ldexpf(a[r], -kAlphaDown);
+            }
+            if constexpr (MAX) {
+                if (lane < K) bp[(int64_t)(t0 + i) * K + lane] = mine;
+            }
+            if constexpr (MODE == kCrfStore) {
+                if (lane == 0) ae[t0 + i] = (int)(eacc + kAlphaDown);
+            }
+            in = nx;
+        }
+    }
+    if (lane == 0) lds.misc[18] = 0;
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < K; ++r) {
+        const int k = slot_state<K>(lane, r, lo);
+        if (k <= hi && k == rw.L) lds.misc[18] = __float_as_int(a[r]);
+    }
+    if (MAX && bad) lds.misc[kBadPost] = 1;
+    __syncthreads();
+    *eacc_out = eacc;
+    return __int_as_float(lds.misc[18]);
 }
 
 CrfParams crf_params(const BatchDesc &in, const ScoreDesc &y, const float *init, int64_t n_init, int64_t init_stride,

@@ -40,7 +40,9 @@ __device__ __forceinline__ void crf_no_alignment(const CrfParams &p) {
     for (int64_t k = threadIdx.x; k < n; k += 64) p.count[row * p.y.stride + k] = 0u;
 }
 
-// MAX = false: the forward sum (fcd_crf_score_*); MAX = true: the best alignment with back-pointers (fcd_crf_align_*)
+// MAX = false: the forward sum (fcd_crf_score_*); MAX = true: the best alignment with back-pointers (fcd_crf_align_*).
+// The time loop is crf_forward_walk of crf_lattice.h (crf_posterior.hip's forward launch runs its third mode); the
+// traceback and the qualities are here.
 template <bool MAX, int K>
 __global__ __launch_bounds__(64) void crf_lattice_kernel(CrfParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -53,74 +55,9 @@ __global__ __launch_bounds__(64) void crf_lattice_kernel(CrfParams p) {
     }
     const int lane = threadIdx.x;
     uint64_t *bp = MAX ? reinterpret_cast<uint64_t *>(p.bp + (int64_t)blockIdx.x * p.bp_row_bytes) : nullptr;
-    float a[K];  // alpha of the state each of the lane's K slots holds, scaled by 2^-eacc
-#pragma unroll
-    for (int r = 0; r < K; ++r) a[r] = 0.0f;
-    if (lane == 0) a[0] = 1.0f;  // "row -1": state 0, the one live state
-    int64_t eacc = 0;
-    int lo = 0, hi = 0;
-    uint32_t bad = 0;
-    for (int t0 = 0; t0 < rw.Tr; t0 += p.rows_per_tile) {
-        const int rc = min(p.rows_per_tile, rw.Tr - t0);
-        crf_fill_tile(p, lds, rw, t0, rc);
-        CrfStep<K> in = crf_load_step<K>(p, lds, rw, t0, 0, lo, hi);
-        for (int i = 0; i < rc; ++i) {
-            CrfStep<K> nx = in;
-            if (i + 1 < rc) nx = crf_load_step<K>(p, lds, rw, t0 + i + 1, i + 1, in.lo, in.hi);
-            lo = in.lo;
-            hi = in.hi;
-            bad |= in.bad;
-            float s[K], v[K];
-#pragma unroll
-            for (int r = 0; r < K; ++r) {
-                s[r] = ((in.stay_mask >> r) & 1) ? a[r] * in.pm0[r] : 0.0f;
-                v[r] = ((in.adv_mask >> r) & 1) ? a[r] * in.pmy[r] : 0.0f;
-            }
-            const float v_in = from_prev_lane(v[K - 1]);
-            const int e_in = int_from_prev_lane(in.pey[K - 1]);
-            float ua[K];
-            int ea[K];
-            int emax = kNoExp;
-#pragma unroll
-            for (int r = 0; r < K; ++r) {
-                ua[r] = r >= 1 ? v[r - 1] : v_in;
-                ea[r] = r >= 1 ? in.pey[r - 1] : e_in;
-                const int e0 = finite_exp(s[r]), e1 = finite_exp(ua[r]);
-                emax = max(emax, e0 != kNoExp ? e0 + in.pe0[r] : kNoExp);
-                emax = max(emax, e1 != kNoExp ? e1 + ea[r] : kNoExp);
-            }
-            emax = wave_imax(emax);
-            const int sh = emax == kNoExp ? 0 : kTarget - emax;
-            eacc -= sh;
-            uint64_t mine = 0;
-#pragma unroll
-            for (int r = 0; r < K; ++r) {
-                const float c0 = ldexpf(s[r], min(max(in.pe0[r] + sh, -512), 512));
-                const float c1 = ldexpf(ua[r], min(max(ea[r] + sh, -512), 512));
-                if (MAX) {
-                    const bool up = c1 > c0;  // the stay candidate is kept unless the advance is strictly greater
-                    a[r] = up ? c1 : c0;
-                    const uint64_t word = __ballot(up);
-                    if (lane == r) mine = word;
-                } else {
-                    a[r] = c0 + c1;
-                }
-            }
-            if (MAX && lane < K) bp[(int64_t)(t0 + i) * K + lane] = mine;
-            in = nx;
-        }
-    }
-    if (lane == 0) lds.misc[18] = 0;
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < K; ++r) {
-        const int k = slot_state<K>(lane, r, lo);
-        if (k <= hi && k == rw.L) lds.misc[18] = __float_as_int(a[r]);
-    }
-    if (MAX && bad) lds.misc[kBadPost] = 1;
-    __syncthreads();
-    const float m = __int_as_float(lds.misc[18]);
-    const double ln = log((double)m) + (double)eacc * 0.693147180559945309417232121458;
+    int64_t eacc;
+    const float m = crf_forward_walk<MAX ? kCrfMax : kCrfSum, K>(p, lds, rw, bp, nullptr, nullptr, &eacc);
+    const double ln = ln_p((double)m, eacc);
     if (!MAX) {
         if (lane == 0) p.logp[blockIdx.x] = ln;
         return;

@@ -33,7 +33,7 @@
 // fcd_crf_edits_* (the deletion and insertion likelihoods of the same labellings) is the same forward launch -- with the cone
 // kept one state wider below, CrfParams::cone_lo -- and two more walks compiled into crfp_back_kernel, selected by the
 // wave-uniform q.walk: crfp_back_walk<K, MM, NB, WALK> below says where they differ from the substitution walk.  Their
-// accumulators become float32 log-ratios against ln P(y | x) (crf_log_ratio), as ctc_posterior.hip's edit walk forms them.
+// accumulators become float32 log-ratios against ln P(y | x) (log_ratio of ctc_lattice.h), as ctc_posterior.hip's edit walk forms them.
 //
 // Scales.  beta and every V share one integer exponent per row.  The step is two passes over the row's posteriors: the
 // first takes only exponents -- the largest frexp(old) + frexp(posterior) over every product of the row, E, reduced as an
@@ -56,7 +56,7 @@
 namespace fcd {
 namespace {
 
-constexpr int kAlphaDown = 60;  // stored alpha: row maximum in [2^59, 2^60)
+// (kAlphaDown, the scale of the stored alpha: ctc_lattice.h)
 constexpr int kTargetB = 59;    // beta, V: row maximum in [2^57, 2^60)
 constexpr int kAccTop = 64;     // a term enters its accumulator below 2^64: 2^46 rows sum below 2^110
 
@@ -71,7 +71,7 @@ struct CrfPostParams {
 };
 constexpr int kWalkSub = 0, kWalkIns = 1, kWalkDel = 2;
 
-// ---- pass 1: crf_lattice.hip's forward sum, storing what it computes ----
+// ---- pass 1: crf_lattice.hip's forward sum, storing what it computes (crf_forward_walk of crf_lattice.h) ----
 template <int K>
 __global__ __launch_bounds__(64) void crfp_fwd_kernel(CrfPostParams q) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -80,68 +80,10 @@ __global__ __launch_bounds__(64) void crfp_fwd_kernel(CrfPostParams q) {
     const CrfLds lds = crf_carve(smem);
     CrfRow rw;
     if (!crf_prologue(p, lds, &rw)) return;
-    const int lane = threadIdx.x;
     float *am = q.alpha + (int64_t)blockIdx.x * q.alpha_words;
-    int *ae = reinterpret_cast<int *>(am + (int64_t)p.in.T * C);
-    float a[K];
-#pragma unroll
-    for (int r = 0; r < K; ++r) a[r] = 0.0f;
-    if (lane == 0) a[0] = 1.0f;  // "row -1": state 0, the one live state
-    int64_t eacc = 0;
-    int lo = 0, hi = 0;
-    for (int t0 = 0; t0 < rw.Tr; t0 += p.rows_per_tile) {
-        const int rc = min(p.rows_per_tile, rw.Tr - t0);
-        crf_fill_tile(p, lds, rw, t0, rc);
-        CrfStep<K> in = crf_load_step<K>(p, lds, rw, t0, 0, lo, hi);
-        for (int i = 0; i < rc; ++i) {
-            CrfStep<K> nx = in;
-            if (i + 1 < rc) nx = crf_load_step<K>(p, lds, rw, t0 + i + 1, i + 1, in.lo, in.hi);
-            lo = in.lo;
-            hi = in.hi;
-            float s[K], v[K];
-#pragma unroll
-            for (int r = 0; r < K; ++r) {
-                s[r] = ((in.stay_mask >> r) & 1) ? a[r] * in.pm0[r] : 0.0f;
-                v[r] = ((in.adv_mask >> r) & 1) ? a[r] * in.pmy[r] : 0.0f;
-            }
-            const float v_in = from_prev_lane(v[K - 1]);
-            const int e_in = int_from_prev_lane(in.pey[K - 1]);
-            float ua[K];
-            int ea[K];
-            int emax = kNoExp;
-#pragma unroll
-            for (int r = 0; r < K; ++r) {
-                ua[r] = r >= 1 ? v[r - 1] : v_in;
-                ea[r] = r >= 1 ? in.pey[r - 1] : e_in;
-                const int e0 = finite_exp(s[r]), e1 = finite_exp(ua[r]);
-                emax = max(emax, e0 != kNoExp ? e0 + in.pe0[r] : kNoExp);
-                emax = max(emax, e1 != kNoExp ? e1 + ea[r] : kNoExp);
-            }
-            emax = wave_imax(emax);
-            const int sh = emax == kNoExp ? 0 : kTarget - emax;
-            eacc -= sh;
-            float *row = am + (int64_t)(t0 + i) * C + lane * K;
-#pragma unroll
-            for (int r = 0; r < K; ++r) {
-                const float c0 = ldexpf(s[r], min(max(in.pe0[r] + sh, -512), 512));
-                const float c1 = ldexpf(ua[r], min(max(ea[r] + sh, -512), 512));
-                a[r] = c0 + c1;
-                row[r] = ldexpf(a[r], -kAlphaDown);  // (a slot outside the row's window holds 0)
-            }
-            if (lane == 0) ae[t0 + i] = (int)(eacc + kAlphaDown);
-            in = nx;
-        }
-    }
-    if (lane == 0) lds.misc[18] = 0;
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < K; ++r) {
-        const int k = slot_state<K>(lane, r, lo);
-        if (k <= hi && k == rw.L) lds.misc[18] = __float_as_int(a[r]);
-    }
-    __syncthreads();
-    const float m = __int_as_float(lds.misc[18]);
-    if (lane == 0) p.logp[blockIdx.x] = log((double)m) + (double)eacc * 0.693147180559945309417232121458;
+    int64_t eacc;
+    const float m = crf_forward_walk<kCrfStore, K>(p, lds, rw, nullptr, am, reinterpret_cast<int *>(am + (int64_t)p.in.T * C), &eacc);
+    if (threadIdx.x == 0) p.logp[blockIdx.x] = ln_p((double)m, eacc);
 }
 
 // ---- pass 2 ----
@@ -152,20 +94,7 @@ __device__ __forceinline__ void crf_no_posterior(const CrfPostParams &q) {
     for (int64_t e = threadIdx.x; e < n; e += 64) q.post[row * q.c.y.stride * nc + e] = NAN;
 }
 
-template <int NB>
-__device__ __forceinline__ void crf_store_post(float *post, int k, int nb, const float (&acc)[NB]) {
-    float sum = acc[0];
-#pragma unroll
-    for (int c = 1; c < NB; ++c)
-        if (c < nb) sum += acc[c];
-#pragma unroll
-    for (int c = 0; c < NB; ++c)
-        if (c < nb) post[(int64_t)k * nb + c] = acc[c] / sum;  // (0 / 0 and x / NaN: NaN, as the contract wants it)
-}
-
-__device__ __forceinline__ float crf_from_next_lane(float x) {  // wave_rol:1 -- lane l receives lane (l + 1) & 63
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x134, 0xf, 0xf, false));
-}
+// (store_post, from_next_lane, log_ratio: ctc_lattice.h)
 
 // crf_window with k(t) handed in (the row before the tile has no krow entry)
 __device__ __forceinline__ void crf_window_k(const CrfParams &p, const CrfRow &rw, int t, int k, int *lo, int *hi) {
@@ -196,16 +125,6 @@ __device__ __forceinline__ float crf_term(float old, float v, int sh) {
 }
 
 // ---- what the walks of fcd_crf_edits_* need next to the substitution walk's helpers ----
-// ln(v * 2^e) - lp, what the outputs hold: the logarithm of the mantissa in f32 (in [ln 0.5, 0): its rounding is below
-// 2^-24), the exponents and the labelling's own ln P in float64.  v = 0: -inf; a NaN: NaN.  (ctc_posterior.hip's.)
-__device__ __forceinline__ float crf_log_ratio(float v, int64_t e, double lp) {
-    if (v == 0.0f) return -INFINITY;
-    if (!(v > 0.0f) || v - v != 0.0f) return NAN;
-    int ex;
-    const float m = frexpf(v, &ex);
-    return (float)((double)logf(m) + (double)(e + ex) * 0.693147180559945309417232121458 - lp);
-}
-
 // every entry of the walk's output the row owns -- k < min(len, stride), g <= min(len, stride) -- set to v
 template <int WALK>
 __device__ __forceinline__ void crf_fill_edits(const CrfPostParams &q, float v) {
@@ -225,14 +144,14 @@ __device__ __forceinline__ void crf_store_position(const CrfPostParams &q, int s
                                                    double lp) {
     const int64_t row = blockIdx.x;
     if constexpr (WALK == kWalkSub) {
-        if (s < L) crf_store_post<NB>(q.post + row * q.c.y.stride * nb, s, nb, acc);
+        if (s < L) store_post<NB>(q.post + row * q.c.y.stride * nb, s, nb, acc);
     } else if constexpr (WALK == kWalkIns) {
         float *ins = q.ins + (row * (q.c.y.stride + 1) + s) * nb;
 #pragma unroll
         for (int c = 0; c < CN; ++c)
-            if (c < nb) ins[c] = crf_log_ratio(acc[c], e, lp);
+            if (c < nb) ins[c] = log_ratio(acc[c], e, lp);
     } else {
-        if (s >= 1 && s < L) q.del[row * q.c.y.stride + s - 1] = crf_log_ratio(acc[0], e, lp);
+        if (s >= 1 && s < L) q.del[row * q.c.y.stride + s - 1] = log_ratio(acc[0], e, lp);
     }
 }
 
@@ -332,18 +251,7 @@ __device__ __forceinline__ void crfp_back_walk(const CrfPostParams &q, unsigned 
     for (int t0 = (rw.Tr - 1) / p.rows_per_tile * p.rows_per_tile; t0 >= 0; t0 -= p.rows_per_tile) {
         const int rc = min(p.rows_per_tile, rw.Tr - t0);
         crf_fill_tile(p, lds, rw, t0, rc);
-        if (p.band > 0 && t0 > 0) {  // k(t0 - 1): the window of the row before the tile
-            if (lane == 0) {
-                int a0 = 0, a1 = L;
-                while (a0 < a1) {
-                    const int mid = (a0 + a1) >> 1;
-                    if (rw.path[mid] <= (uint32_t)(t0 - 1)) a0 = mid + 1;
-                    else a1 = mid;
-                }
-                lds.misc[kKrowBefore] = a0;
-            }
-            __syncthreads();
-        }
+        stage_krow_before(lds.misc, rw.path, L, p.band, t0);  // the window of the row before the tile
         for (int i = rc - 1; i >= 0; --i) {
             const int u = t0 + i;
             int lo_u, hi_u;  // the window of row u: the states whose "old" values the registers hold
@@ -353,7 +261,7 @@ __device__ __forceinline__ void crfp_back_walk(const CrfPostParams &q, unsigned 
             int lo_a = 0, hi_a = 0;  // (deletion) the forward window of row u - 1: the states alpha_{u-1} holds
             int64_t x_u = 0;
             if (u > 0) {
-                const int kp = p.band > 0 ? (i > 0 ? lds.krow[i - 1] : lds.misc[kKrowBefore]) : 0;
+                const int kp = krow_before(lds.krow, lds.misc, p.band, i);
                 crf_window_k(p, rw, u - 1, kp, &lo_p, &hi_p);
                 if constexpr (kDel) crf_window_of(p, rw, u - 1, kp, 1, 0, &lo_a, &hi_a);
                 x_u = ae[u - 1];
@@ -377,7 +285,7 @@ __device__ __forceinline__ void crfp_back_walk(const CrfPostParams &q, unsigned 
                         int la, ha;
                         crf_window_of(p, rw, u, p.band > 0 ? lds.krow[i] : 0, 1, 0, &la, &ha);
                         const float v = (L - 1 >= la && L - 1 <= ha) ? am[(int64_t)u * C + (L - 1) % C] : 0.0f;
-                        q.del[(int64_t)blockIdx.x * p.y.stride + L - 1] = crf_log_ratio(v, ae[u], lp);
+                        q.del[(int64_t)blockIdx.x * p.y.stride + L - 1] = log_ratio(v, ae[u], lp);
                     }
                 }
             } else {  // the states that were live at row u and are not at row u - 1: their positions are complete
@@ -396,12 +304,12 @@ __device__ __forceinline__ void crfp_back_walk(const CrfPostParams &q, unsigned 
             int emax = kNoExp;
             {
                 // (the next lane's first slot, as it stands at row u; rotated once per pass, so that no copy lives across both)
-                const float nb0 = crf_from_next_lane(b[0]);
+                const float nb0 = from_next_lane(b[0]);
                 float nV[J][CN];
 #pragma unroll
                 for (int j = 0; j < JN; ++j)
 #pragma unroll
-                    for (int c = 0; c < CN; ++c) nV[j][c] = crf_from_next_lane(V[0][j][c]);
+                    for (int c = 0; c < CN; ++c) nV[j][c] = from_next_lane(V[0][j][c]);
 #pragma unroll
                 for (int r = 0; r < K; ++r) {
                     int ln = lane;
@@ -457,12 +365,12 @@ __device__ __forceinline__ void crfp_back_walk(const CrfPostParams &q, unsigned 
             __asm__ volatile("" ::: "memory");
             // ---- the terms of acc, and the values of row u - 1, in place: slot r reads slots r and r + 1 only ----
             // the next lane's first slot, as it stands at row u
-            const float nb0 = crf_from_next_lane(b[0]);
+            const float nb0 = from_next_lane(b[0]);
             float nV[J][CN];
 #pragma unroll
             for (int j = 0; j < JN; ++j)
 #pragma unroll
-                for (int c = 0; c < CN; ++c) nV[j][c] = crf_from_next_lane(V[0][j][c]);
+                for (int c = 0; c < CN; ++c) nV[j][c] = from_next_lane(V[0][j][c]);
 #pragma unroll
             for (int r = 0; r < K; ++r) {
                 int ln = lane;
@@ -643,7 +551,7 @@ int crf_posterior_unsupported(int64_t T, int64_t S, int64_t N, int64_t stride, i
 // stored forward rows of one labelling (every one of a call has T rows' worth): T * 64K cells, then T exponent words
 size_t crf_posterior_row_bytes(int64_t T, int64_t S, int64_t N, int64_t stride, int64_t band) {
     const size_t k = (size_t)crf_post_states_per_lane(crf_post_tier(crf_post_chain(S, N - 1), (int)(N - 1)), T, stride, band);
-    return ((size_t)std::max<int64_t>(T, 1) * (64 * k + 1) * 4 + 255) & ~(size_t)255;
+    return stored_rows_bytes(T, k);
 }
 
 namespace {

@@ -58,16 +58,7 @@ __device__ __forceinline__ void fill_tile_checked(const ScoreParams &p, const Ld
         lds.pe[e] = ex;
     }
     if (bad) lds.misc[kBadPost] = 1;
-    if (p.band > 0 && tid < rc) {  // k(t) = #{k : path[k] <= t}
-        const uint32_t t = (uint32_t)(t0 + tid);
-        int lo = 0, hi = rw.L;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (rw.path[mid] <= t) lo = mid + 1;
-            else hi = mid;
-        }
-        lds.krow[tid] = lo;
-    }
+    if (p.band > 0 && tid < rc) lds.krow[tid] = labels_up_to(rw.path, rw.L, (uint32_t)(t0 + tid));
     __syncthreads();
 }
 
@@ -104,7 +95,7 @@ __device__ __forceinline__ int finish(const AlignParams &q, const Lds &lds, cons
     const bool odd = c1 > c0;  // state 2L unless 2L - 1 is strictly greater
     const float m = odd ? c1 : c0;
     if (threadIdx.x == 0)
-        q.s.logp[blockIdx.x] = bad ? (double)NAN : log((double)m) + (double)eacc * 0.693147180559945309417232121458;
+        q.s.logp[blockIdx.x] = bad ? (double)NAN : ln_p((double)m, eacc);
     if (bad || !(m > 0.0f) || m - m != 0.0f) return -1;
     return 2 * rw.L - (odd ? 1 : 0);
 }

@@ -1,7 +1,10 @@
 // ctc_lattice.h -- what the walks of the CTC lattice of a GIVEN labelling share: ctc_score.hip (forward: the sum over
 // the alignments), ctc_align.hip (Viterbi: the best alignment) and ctc_posterior.hip (forward and backward).  Parameter
 // block, LDS layout, everything before the time loop, the staging of the posteriors (split into mantissa and exponent),
-// the live window of a row, the integer row maximum and the wave rotation.  Included by those translation units only.
+// the live window of a row, the integer row maximum and the wave rotations.  The pieces the CRF lattice (crf_lattice.h,
+// which includes this file) has in common with it live here too:
+// k(t) of a decoded path (labels_up_to, stage_krow_before), the ln P result (ln_p), the stored forward rows (kAlphaDown,
+// stored_rows_bytes) and what the backward walks end in (store_post, log_ratio).
 #pragma once
 
 #include <math.h>
@@ -114,6 +117,31 @@ __device__ __forceinline__ bool prologue(const ScoreParams &p, const Lds &lds, R
     return true;
 }
 
+// k(t) = #{k : path[k] <= t}: the labels the decoded path has emitted up to row t
+__device__ __forceinline__ int labels_up_to(const uint32_t *path, int L, uint32_t t) {
+    int lo = 0, hi = L;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (path[mid] <= t) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// A backward walk's row t0 reads the window of the row BEFORE its tile, which has no krow entry: k(t0 - 1) goes to
+// misc[kKrowBefore] once per tile (after fill_tile) ...
+__device__ __forceinline__ void stage_krow_before(int *misc, const uint32_t *path, int L, int band, int t0) {
+    if (band > 0 && t0 > 0) {
+        if (threadIdx.x == 0) misc[kKrowBefore] = labels_up_to(path, L, (uint32_t)(t0 - 1));
+        __syncthreads();
+    }
+}
+
+// ... and k(t - 1) of the tile's row i is read from there or from the row's predecessor in the tile (0 unbanded)
+__device__ __forceinline__ int krow_before(const int *krow, const int *misc, int band, int i) {
+    return band > 0 ? (i > 0 ? krow[i - 1] : misc[kKrowBefore]) : 0;
+}
+
 // rows t0 .. t0 + rc of the read into the tile, split into mantissa and exponent; banded: k(t) of each of them
 __device__ __forceinline__ void fill_tile(const ScoreParams &p, const Lds &lds, const Row &rw, int t0, int rc) {
     const int tid = threadIdx.x, bd = blockDim.x;
@@ -127,16 +155,7 @@ __device__ __forceinline__ void fill_tile(const ScoreParams &p, const Lds &lds, 
         lds.pm[e] = m;
         lds.pe[e] = ex;
     }
-    if (p.band > 0 && tid < rc) {  // k(t) = #{k : path[k] <= t}
-        const uint32_t t = (uint32_t)(t0 + tid);
-        int lo = 0, hi = rw.L;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (rw.path[mid] <= t) lo = mid + 1;
-            else hi = mid;
-        }
-        lds.krow[tid] = lo;
-    }
+    if (p.band > 0 && tid < rc) lds.krow[tid] = labels_up_to(rw.path, rw.L, (uint32_t)(t0 + tid));
     __syncthreads();
 }
 
@@ -162,6 +181,10 @@ __device__ __forceinline__ void window(const ScoreParams &p, const Lds &lds, con
 
 __device__ __forceinline__ float from_prev_lane(float x) {  // wave_ror:1 -- lane l receives lane (l - 1) & 63
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x13C, 0xf, 0xf, false));
+}
+
+__device__ __forceinline__ float from_next_lane(float x) {  // wave_rol:1 -- lane l receives lane (l + 1) & 63
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x134, 0xf, 0xf, false));
 }
 
 template <int K>
@@ -206,6 +229,43 @@ __device__ __forceinline__ StepIn<K> load_step(const ScoreParams &p, const Lds &
         }
     }
     return in;
+}
+
+// ---- what a forward walk leaves: ln P, and (stored) its rows for a backward walk ----
+constexpr double kLn2 = 0.693147180559945309417232121458;
+
+// ln(m * 2^eacc), in float64
+__device__ __forceinline__ double ln_p(double m, int64_t eacc) { return log(m) + (double)eacc * kLn2; }
+
+constexpr int kAlphaDown = 60;  // stored alpha: row maximum in [2^59, 2^60) -- times a backward value (below 2^60) stays finite
+
+// stored forward rows of one labelling at k states per lane (every labelling of a call has T rows' worth): T * 64k cells
+// by SLOT, scaled by 2^-kAlphaDown (exact), then T exponent words
+inline size_t stored_rows_bytes(int64_t T, size_t k) {
+    return ((size_t)(T > 1 ? T : 1) * (64 * k + 1) * 4 + 255) & ~(size_t)255;
+}
+
+// ---- what a backward walk ends in ----
+// post[k][.] = acc / sum over the labels
+template <int NC>
+__device__ __forceinline__ void store_post(float *post, int k, int nc, const float (&acc)[NC]) {
+    float sum = acc[0];
+#pragma unroll
+    for (int c = 1; c < NC; ++c)
+        if (c < nc) sum += acc[c];
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+        if (c < nc) post[(int64_t)k * nc + c] = acc[c] / sum;  // (0 / 0 and x / NaN: NaN, as the contract wants it)
+}
+
+// ln(v * 2^e) - lp, what the edit outputs hold: the logarithm of the mantissa in f32 (in [ln 0.5, 0): its rounding is below
+// 2^-24), the exponents and the labelling's own ln P in float64.  v = 0: -inf; a NaN: NaN.
+__device__ __forceinline__ float log_ratio(float v, int64_t e, double lp) {
+    if (v == 0.0f) return -INFINITY;
+    if (!(v > 0.0f) || v - v != 0.0f) return NAN;
+    int ex;
+    const float m = frexpf(v, &ex);
+    return (float)((double)logf(m) + (double)(e + ex) * kLn2 - lp);
 }
 
 }  // namespace

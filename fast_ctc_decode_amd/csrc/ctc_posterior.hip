@@ -47,7 +47,7 @@
 namespace fcd {
 namespace {
 
-constexpr int kAlphaDown = 60;   // stored alpha: row maximum in [2^59, 2^60) -- times w (below 2^60) stays finite
+// (kAlphaDown, the scale of the stored alpha: ctc_lattice.h)
 constexpr int kTargetB = 60;     // b, w: row maximum in [2^59, 2^60)
 constexpr int kAccDown = 40;     // a term (below 2^121) enters acc below 2^81: 2^46 rows sum below 2^127
 
@@ -154,8 +154,7 @@ __global__ __launch_bounds__(64) void post_fwd_kernel(PostParams q) {
     }
     __syncthreads();
     if (lane == 0) {
-        const double m = (double)__int_as_float(lds.misc[18]) + (double)__int_as_float(lds.misc[19]);
-        p.logp[blockIdx.x] = log(m) + (double)eacc * 0.693147180559945309417232121458;
+        p.logp[blockIdx.x] = ln_p((double)__int_as_float(lds.misc[18]) + (double)__int_as_float(lds.misc[19]), eacc);
     }
 }
 
@@ -167,20 +166,90 @@ __device__ __forceinline__ void no_posterior(const PostParams &q) {
     for (int64_t e = threadIdx.x; e < n; e += blockDim.x) q.post[row * q.s.y.stride * nc + e] = NAN;
 }
 
-template <int NC>
-__device__ __forceinline__ void store_post(float *post, int k, int nc, const float (&acc)[NC]) {
-    float sum = acc[0];
-#pragma unroll
-    for (int c = 1; c < NC; ++c)
-        if (c < nc) sum += acc[c];
-#pragma unroll
-    for (int c = 0; c < NC; ++c)
-        if (c < nc) post[(int64_t)k * nc + c] = acc[c] / sum;  // (0 / 0 and x / NaN: NaN, as the contract wants it)
+// every entry of the edit outputs the row owns -- k < min(len, stride), g <= min(len, stride) -- set to v
+__device__ __forceinline__ void fill_edits(const PostParams &q, float v) {
+    const int64_t row = blockIdx.x, nc = q.s.in.N - 1;
+    const int64_t n = min((int64_t)q.s.y.len[row], q.s.y.stride);
+    for (int64_t e = threadIdx.x; e < n; e += blockDim.x) q.del[row * q.s.y.stride + e] = v;
+    for (int64_t e = threadIdx.x; e < (n + 1) * nc; e += blockDim.x) q.ins[row * (q.s.y.stride + 1) * nc + e] = v;
 }
 
-__device__ __forceinline__ float from_next_lane(float x) {  // wave_rol:1 -- lane l receives lane (l + 1) & 63
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x134, 0xf, 0xf, false));
+// ---- the backward walk's scaffolding: what post_back_kernel and edit_back_kernel do alike, written once.  The two kernels
+// below keep their own loops and what a slot carries and flushes, so that their recurrences read side by side. ----
+// the first row of the last tile: the tiles are walked from there down
+__device__ __forceinline__ int last_tile(const Row &rw) { return (rw.Tr - 1) / rw.rows_per_tile * rw.rows_per_tile; }
+
+// rows t0 .. t0 + rc staged, and k(t0 - 1) next to them: the window of the alpha row that row t0 reads
+__device__ __forceinline__ void fill_back_tile(const ScoreParams &p, const Lds &lds, const Row &rw, int t0, int rc) {
+    fill_tile(p, lds, rw, t0, rc);
+    stage_krow_before(lds.misc, rw.path, rw.L, p.band, t0);
 }
+
+// "row T_r": all mass on state 2L
+template <int K>
+__device__ __forceinline__ void start_beyond_last_row(float (&b)[K], int lo, int L) {
+#pragma unroll
+    for (int r = 0; r < K; ++r) b[r] = slot_state<K>((int)threadIdx.x, r, lo) == 2 * L ? 1.0f : 0.0f;
+}
+
+// the posteriors of the labels 1 .. nc of the tile's row i, split (a label beyond nc reads the last one and is masked)
+template <int NC>
+__device__ __forceinline__ void label_posts(const Lds &lds, int at, int nc, float (&pmc)[NC], int (&pec)[NC]) {
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+        pmc[c] = lds.pm[at + min(c + 1, nc)];
+        pec[c] = lds.pe[at + min(c + 1, nc)];
+    }
+}
+
+// b_{t+1} of s, s + 1, s + 2, s the state of slot r: a state below row t + 1's window (lo_n) is not what its slot holds;
+// n1, n2: the next lane's first two slots
+struct Above {
+    float y0, y1, y2;
+};
+
+template <int K>
+__device__ __forceinline__ Above b_above(const float (&b)[K], int r, int s, int lo_n, float n1, float n2) {
+    Above y;
+    y.y0 = s >= lo_n ? b[r] : 0.0f;
+    y.y1 = s + 1 >= lo_n ? (r + 1 < K ? b[r + 1 < K ? r + 1 : 0] : n1) : 0.0f;
+    y.y2 = s + 2 >= lo_n ? (r + 2 < K ? b[r + 2 < K ? r + 2 : 0] : (r + 2 == K ? n1 : n2)) : 0.0f;
+    return y;
+}
+
+// what the label state of label k passes down, before its posterior: b[s] [collapse] + b[s+1] + [y_{k+1} != y_k or no
+// collapse] b[s+2]; inext: the labelling's word of label k + 1
+__device__ __forceinline__ float label_state_sum(int collapse, const Above &y, int k, int L, int inext) {
+    float sum = collapse ? y.y0 + y.y1 : y.y1;
+    sum += (k + 1 < L && (!collapse || (inext & 0x100))) ? y.y2 : 0.0f;
+    return sum;
+}
+
+// The row's scale: its largest b or w lands in [2^(kTargetB-1), 2^kTargetB).  Returns the shift; eb follows it, and x_t
+// (alpha_{t-1}'s exponent on entry) becomes the exponent of this row's terms
+__device__ __forceinline__ int back_row_shift(int emax, int64_t &eb, int64_t &x_t) {
+    emax = wave_imax(emax);
+    const int sh = emax == kNoExp ? 0 : kTargetB - emax;
+    eb -= sh;
+    x_t += eb;
+    return sh;
+}
+
+// acc is kept at the largest X seen so far: where x_t exceeds it, rescale(d) brings the accumulators down by 2^d (d < 0)
+template <class F>
+__device__ __forceinline__ void raise_xmax(int64_t x_t, int64_t &xmax, bool &any, F rescale) {
+    if (!any || x_t > xmax) {
+        if (any) rescale((int)max(xmax - x_t, (int64_t)-512));
+        xmax = x_t;
+        any = true;
+    }
+}
+
+// the power of two a term of this row enters acc by
+__device__ __forceinline__ int term_shift(int64_t x_t, int64_t xmax) { return (int)max(x_t - xmax, (int64_t)-512) - kAccDown; }
+
+// u * 2^(e + sh): a cell at the row's scale
+__device__ __forceinline__ float at_row_scale(float u, int e, int sh) { return ldexpf(u, min(max(e + sh, -512), 512)); }
 
 template <int K, int NC>
 __global__ __launch_bounds__(64) void post_back_kernel(PostParams q) {
@@ -213,21 +282,9 @@ __global__ __launch_bounds__(64) void post_back_kernel(PostParams q) {
     int64_t eb = 0, xmax = 0;
     bool first = true, any = false;
     int lo = 0, hi = 0, lo_n = 0, hi_n = 0;
-    for (int t0 = (rw.Tr - 1) / rw.rows_per_tile * rw.rows_per_tile; t0 >= 0; t0 -= rw.rows_per_tile) {
+    for (int t0 = last_tile(rw); t0 >= 0; t0 -= rw.rows_per_tile) {
         const int rc = min(rw.rows_per_tile, rw.Tr - t0);
-        fill_tile(p, lds, rw, t0, rc);
-        if (p.band > 0 && t0 > 0) {  // k(t0 - 1): the window of the alpha row that row t0 reads
-            if (lane == 0) {
-                int a0 = 0, a1 = L;
-                while (a0 < a1) {
-                    const int mid = (a0 + a1) >> 1;
-                    if (rw.path[mid] <= (uint32_t)(t0 - 1)) a0 = mid + 1;
-                    else a1 = mid;
-                }
-                lds.misc[kKrowBefore] = a0;
-            }
-            __syncthreads();
-        }
+        fill_back_tile(p, lds, rw, t0, rc);
         for (int i = rc - 1; i >= 0; --i) {
             const int t = t0 + i;
             window(p, lds, rw, t, i, &lo, &hi);
@@ -236,7 +293,7 @@ __global__ __launch_bounds__(64) void post_back_kernel(PostParams q) {
             float av[K];
             int64_t x_t = 0;
             if (t > 0) {
-                window_k(p, rw, t - 1, p.band > 0 ? (i > 0 ? lds.krow[i - 1] : lds.misc[kKrowBefore]) : 0, &lo_p, &hi_p);
+                window_k(p, rw, t - 1, krow_before(lds.krow, lds.misc, p.band, i), &lo_p, &hi_p);
                 const float *row = am + (int64_t)(t - 1) * C + lane * K;
 #pragma unroll
                 for (int r = 0; r < K; ++r) av[r] = slot_state<K>(lane, r, lo_p) <= hi_p ? row[r] : 0.0f;
@@ -246,9 +303,8 @@ __global__ __launch_bounds__(64) void post_back_kernel(PostParams q) {
                 for (int r = 0; r < K; ++r) av[r] = (lane == 0 && r == 0) ? 1.0f : 0.0f;
             }
             const float av_prev = from_prev_lane(av[K - 1]);
-            if (first) {  // "row T_r": all mass on state 2L
-#pragma unroll
-                for (int r = 0; r < K; ++r) b[r] = slot_state<K>(lane, r, lo) == 2 * L ? 1.0f : 0.0f;
+            if (first) {
+                start_beyond_last_row<K>(b, lo, L);
                 first = false;
                 lo_n = lo;
             } else {  // the label states that were live at row t + 1 and are not at row t: their labels are complete
@@ -267,11 +323,7 @@ __global__ __launch_bounds__(64) void post_back_kernel(PostParams q) {
             const int pe0 = lds.pe[i * rw.N];
             float pmc[NC];
             int pec[NC];
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                pmc[c] = lds.pm[i * rw.N + min(c + 1, nc)];
-                pec[c] = lds.pe[i * rw.N + min(c + 1, nc)];
-            }
+            label_posts<NC>(lds, i * rw.N, nc, pmc, pec);
             float u[K], uw[H][NC], e1[H], e2[H];
             int ex[K], yprev[H];
             uint32_t live = 0;
@@ -281,24 +333,19 @@ __global__ __launch_bounds__(64) void post_back_kernel(PostParams q) {
                 const int s = slot_state<K>(lane, r, lo);
                 const bool in = s <= hi;
                 live |= (in ? 1u : 0u) << r;
-                // b_{t+1} of s, s + 1, s + 2: a state below row t + 1's window is not what its slot holds
-                const float y0 = s >= lo_n ? b[r] : 0.0f;
-                const float y1 = s + 1 >= lo_n ? (r + 1 < K ? b[r + 1] : n1) : 0.0f;
-                const float y2 = s + 2 >= lo_n ? (r + 2 < K ? b[r + 2] : (r + 2 == K ? n1 : n2)) : 0.0f;
+                const Above y = b_above<K>(b, r, s, lo_n, n1, n2);
                 if (r & 1) {
                     const int h = r / 2, k = in ? (s >> 1) : 0;  // (a dead slot reads valid addresses and is masked below)
                     const int info = lds.lab[k], inext = lds.lab[min(k + 1, L - 1)], iprev = lds.lab[max(k - 1, 0)];
-                    const int y = in ? (info & 0xFF) : 0;
+                    const int yk = in ? (info & 0xFF) : 0;
                     const int ynext = k + 1 < L ? (inext & 0xFF) : 0;  // (0: no label c equals it)
                     yprev[h] = k > 0 ? (iprev & 0xFF) : 0;
-                    float sum = p.collapse ? y0 + y1 : y1;
-                    sum += (k + 1 < L && (!p.collapse || (inext & 0x100))) ? y2 : 0.0f;
-                    u[r] = sum * lds.pm[i * rw.N + y];
-                    ex[r] = lds.pe[i * rw.N + y];
+                    u[r] = label_state_sum(p.collapse, y, k, L, inext) * lds.pm[i * rw.N + yk];
+                    ex[r] = lds.pe[i * rw.N + yk];
 #pragma unroll
                     for (int c = 0; c < NC; ++c) {
-                        float exit = p.collapse ? w[h][c] + y1 : y1;
-                        exit += (p.collapse && c + 1 == ynext) ? 0.0f : y2;  // (b[s + 2] is 0 beyond state 2L)
+                        float exit = p.collapse ? w[h][c] + y.y1 : y.y1;
+                        exit += (p.collapse && c + 1 == ynext) ? 0.0f : y.y2;  // (b[s + 2] is 0 beyond state 2L)
                         uw[h][c] = exit * pmc[c];
                         const int e = finite_exp(uw[h][c]);
                         emax = max(emax, in && c < nc && e != kNoExp ? e + pec[c] : kNoExp);
@@ -308,37 +355,29 @@ __global__ __launch_bounds__(64) void post_back_kernel(PostParams q) {
                     e1[h] = (in && s - 1 <= hi_p) ? x1 : 0.0f;
                     e2[h] = (in && s >= 3 && s - 2 <= hi_p) ? x2 : 0.0f;
                 } else {
-                    u[r] = (y0 + y1) * pm0;
+                    u[r] = (y.y0 + y.y1) * pm0;
                     ex[r] = pe0;
                 }
                 const int e = finite_exp(u[r]);
                 emax = max(emax, in && e != kNoExp ? e + ex[r] : kNoExp);
             }
-            emax = wave_imax(emax);
-            const int sh = emax == kNoExp ? 0 : kTargetB - emax;
-            eb -= sh;
-            x_t += eb;  // the exponent of this row's terms
-            if (!any || x_t > xmax) {
-                if (any) {
-                    const int d = (int)max(xmax - x_t, (int64_t)-512);
+            const int sh = back_row_shift(emax, eb, x_t);
+            raise_xmax(x_t, xmax, any, [&](int d) {
 #pragma unroll
-                    for (int h = 0; h < H; ++h)
+                for (int h = 0; h < H; ++h)
 #pragma unroll
-                        for (int c = 0; c < NC; ++c) acc[h][c] = ldexpf(acc[h][c], d);
-                }
-                xmax = x_t;
-                any = true;
-            }
-            const int dt = (int)max(x_t - xmax, (int64_t)-512) - kAccDown;
+                    for (int c = 0; c < NC; ++c) acc[h][c] = ldexpf(acc[h][c], d);
+            });
+            const int dt = term_shift(x_t, xmax);
 #pragma unroll
             for (int r = 0; r < K; ++r) {
                 const bool in = (live >> r) & 1;
-                b[r] = in ? ldexpf(u[r], min(max(ex[r] + sh, -512), 512)) : 0.0f;
+                b[r] = in ? at_row_scale(u[r], ex[r], sh) : 0.0f;
                 if (r & 1) {
                     const int h = r / 2;
 #pragma unroll
                     for (int c = 0; c < NC; ++c) {
-                        w[h][c] = (in && c < nc) ? ldexpf(uw[h][c], min(max(pec[c] + sh, -512), 512)) : 0.0f;
+                        w[h][c] = (in && c < nc) ? at_row_scale(uw[h][c], pec[c], sh) : 0.0f;
                         const float entry = e1[h] + ((p.collapse && c + 1 == yprev[h]) ? 0.0f : e2[h]);
                         const float term = entry * w[h][c];
                         acc[h][c] += ldexpf(term, dt);
@@ -358,24 +397,6 @@ __global__ __launch_bounds__(64) void post_back_kernel(PostParams q) {
 }
 
 // ---- pass 2 of fcd_ctc_edits_* ----
-// ln(v * 2^e) - lp, what the outputs hold: the logarithm of the mantissa in f32 (in [ln 0.5, 0): its rounding is below
-// 2^-24), the exponents and the labelling's own ln P in float64.  v = 0: -inf; a NaN: NaN.
-__device__ __forceinline__ float log_ratio(float v, int64_t e, double lp) {
-    if (v == 0.0f) return -INFINITY;
-    if (!(v > 0.0f) || v - v != 0.0f) return NAN;
-    int ex;
-    const float m = frexpf(v, &ex);
-    return (float)((double)logf(m) + (double)(e + ex) * 0.693147180559945309417232121458 - lp);
-}
-
-// every entry the row owns -- k < min(len, stride), g <= min(len, stride) -- set to v
-__device__ __forceinline__ void fill_edits(const PostParams &q, float v) {
-    const int64_t row = blockIdx.x, nc = q.s.in.N - 1;
-    const int64_t n = min((int64_t)q.s.y.len[row], q.s.y.stride);
-    for (int64_t e = threadIdx.x; e < n; e += blockDim.x) q.del[row * q.s.y.stride + e] = v;
-    for (int64_t e = threadIdx.x; e < (n + 1) * nc; e += blockDim.x) q.ins[row * (q.s.y.stride + 1) * nc + e] = v;
-}
-
 template <int NC>
 __device__ __forceinline__ void store_ins(float *ins, int g, int nc, const float (&acc)[NC], int64_t e, double lp) {
 #pragma unroll
@@ -416,21 +437,9 @@ __global__ __launch_bounds__(64) void edit_back_kernel(PostParams q) {
     int64_t eb = 0, xmax = 0;
     bool first = true, any = false;
     int lo = 0, hi = 0, lo_n = 0, hi_n = 0;
-    for (int t0 = (rw.Tr - 1) / rw.rows_per_tile * rw.rows_per_tile; t0 >= 0; t0 -= rw.rows_per_tile) {
+    for (int t0 = last_tile(rw); t0 >= 0; t0 -= rw.rows_per_tile) {
         const int rc = min(rw.rows_per_tile, rw.Tr - t0);
-        fill_tile(p, lds, rw, t0, rc);
-        if (p.band > 0 && t0 > 0) {  // k(t0 - 1): the window of the alpha row that row t0 reads
-            if (lane == 0) {
-                int a0 = 0, a1 = L;
-                while (a0 < a1) {
-                    const int mid = (a0 + a1) >> 1;
-                    if (rw.path[mid] <= (uint32_t)(t0 - 1)) a0 = mid + 1;
-                    else a1 = mid;
-                }
-                lds.misc[kKrowBefore] = a0;
-            }
-            __syncthreads();
-        }
+        fill_back_tile(p, lds, rw, t0, rc);
         for (int i = rc - 1; i >= 0; --i) {
             const int t = t0 + i;
             window(p, lds, rw, t, i, &lo, &hi);
@@ -439,7 +448,7 @@ __global__ __launch_bounds__(64) void edit_back_kernel(PostParams q) {
             float av[K];
             int64_t x_t = 0;
             if (t > 0) {
-                window_k(p, rw, t - 1, p.band > 0 ? (i > 0 ? lds.krow[i - 1] : lds.misc[kKrowBefore]) : 0, &lo_p, &hi_p);
+                window_k(p, rw, t - 1, krow_before(lds.krow, lds.misc, p.band, i), &lo_p, &hi_p);
                 const float *row = am + (int64_t)(t - 1) * C + lane * K;
 #pragma unroll
                 for (int r = 0; r < K; ++r) av[r] = slot_state<K>(lane, r, lo_p) <= hi_p ? row[r] : 0.0f;
@@ -449,9 +458,8 @@ __global__ __launch_bounds__(64) void edit_back_kernel(PostParams q) {
                 for (int r = 0; r < K; ++r) av[r] = (lane == 0 && r == 0) ? 1.0f : 0.0f;
             }
             const float av_prev = from_prev_lane(av[K - 1]);
-            if (first) {  // "row T_r": all mass on state 2L
-#pragma unroll
-                for (int r = 0; r < K; ++r) b[r] = slot_state<K>(lane, r, lo) == 2 * L ? 1.0f : 0.0f;
+            if (first) {
+                start_beyond_last_row<K>(b, lo, L);
                 first = false;
                 lo_n = lo;
                 // the last label's deletion: the two final states of the shortened labelling, off the last forward row
@@ -485,11 +493,7 @@ __global__ __launch_bounds__(64) void edit_back_kernel(PostParams q) {
             const int pe0 = lds.pe[i * rw.N];
             float pmc[NC];
             int pec[NC];
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                pmc[c] = lds.pm[i * rw.N + min(c + 1, nc)];
-                pec[c] = lds.pe[i * rw.N + min(c + 1, nc)];
-            }
+            label_posts<NC>(lds, i * rw.N, nc, pmc, pec);
             const uint32_t core = core_states<K>(p, rw, lane, t, lo);
             float ub[K], uu[H][NC], eD[H], e1[H], e2[H];
             int ex[K], yprev[H];
@@ -500,32 +504,28 @@ __global__ __launch_bounds__(64) void edit_back_kernel(PostParams q) {
                 const int s = slot_state<K>(lane, r, lo), h = r / 2;
                 const bool in = s <= hi;
                 live |= (in ? 1u : 0u) << r;
-                // b_{t+1} of s, s + 1, s + 2: a state below row t + 1's window is not what its slot holds
-                const float y0 = s >= lo_n ? b[r] : 0.0f;
-                const float y1 = s + 1 >= lo_n ? (r + 1 < K ? b[r + 1] : n1) : 0.0f;
-                const float y2 = s + 2 >= lo_n ? (r + 2 < K ? b[r + 2] : (r + 2 == K ? n1 : n2)) : 0.0f;
+                const Above y = b_above<K>(b, r, s, lo_n, n1, n2);
                 if (r & 1) {
                     const int k = in ? (s >> 1) : 0;  // (a dead slot reads valid addresses and is masked below)
                     const int info = lds.lab[k], inext = lds.lab[min(k + 1, Lm)], iprev = lds.lab[max(k - 1, 0)];
-                    const int y = in ? (info & 0xFF) : 0;
-                    float sum = p.collapse ? y0 + y1 : y1;
-                    sum += (k + 1 < L && (!p.collapse || (inext & 0x100))) ? y2 : 0.0f;
-                    ub[r] = (!((core >> r) & 1) && sum == 0.0f) ? 0.0f : sum * lds.pm[i * rw.N + y];
-                    ex[r] = lds.pe[i * rw.N + y];
+                    const int yk = in ? (info & 0xFF) : 0;
+                    const float sum = label_state_sum(p.collapse, y, k, L, inext);
+                    ub[r] = (!((core >> r) & 1) && sum == 0.0f) ? 0.0f : sum * lds.pm[i * rw.N + yk];
+                    ex[r] = lds.pe[i * rw.N + yk];
                     // what steps over label k from row t - 1 (a state above that row's window is not in its slot)
                     const float x1 = av[r >= 1 ? r - 1 : 0], x2 = r >= 2 ? av[r - 2] : av_prev;
                     const bool skip = k >= 1 && k + 1 < L && (!p.collapse || ((iprev ^ inext) & 0xFF));
                     eD[h] = ((in && s - 1 <= hi_p) ? x1 : 0.0f) + ((in && skip && s - 2 <= hi_p) ? x2 : 0.0f);
                 } else {
-                    ub[r] = (!((core >> r) & 1) && y0 + y1 == 0.0f) ? 0.0f : (y0 + y1) * pm0;
+                    ub[r] = (!((core >> r) & 1) && y.y0 + y.y1 == 0.0f) ? 0.0f : (y.y0 + y.y1) * pm0;
                     ex[r] = pe0;
                     const int g = in ? (s >> 1) : 0;
                     const int ynext = g < L ? (lds.lab[min(g, Lm)] & 0xFF) : 0;  // (0: no label c equals it)
                     yprev[h] = g > 0 ? (lds.lab[min(g - 1, Lm)] & 0xFF) : 0;
 #pragma unroll
                     for (int c = 0; c < NC; ++c) {
-                        float exit = p.collapse ? u[h][c] + y0 : y0;
-                        exit += (p.collapse && c + 1 == ynext) ? 0.0f : y1;  // (b[s + 1] is 0 beyond state 2L)
+                        float exit = p.collapse ? u[h][c] + y.y0 : y.y0;
+                        exit += (p.collapse && c + 1 == ynext) ? 0.0f : y.y1;  // (b[s + 1] is 0 beyond state 2L)
                         uu[h][c] = exit == 0.0f ? 0.0f : exit * pmc[c];  // (nothing leaves the gap: no alignment reads p[t][c])
                         const int e = finite_exp(uu[h][c]);
                         emax = max(emax, in && c < nc && e != kNoExp ? e + pec[c] : kNoExp);
@@ -538,26 +538,18 @@ __global__ __launch_bounds__(64) void edit_back_kernel(PostParams q) {
                 const int e = finite_exp(ub[r]);
                 emax = max(emax, in && e != kNoExp ? e + ex[r] : kNoExp);
             }
-            emax = wave_imax(emax);
-            const int sh = emax == kNoExp ? 0 : kTargetB - emax;
-            eb -= sh;
-            x_t += eb;  // the exponent of this row's terms
-            if (!any || x_t > xmax) {
-                if (any) {
-                    const int d = (int)max(xmax - x_t, (int64_t)-512);
+            const int sh = back_row_shift(emax, eb, x_t);
+            raise_xmax(x_t, xmax, any, [&](int d) {
 #pragma unroll
-                    for (int h = 0; h < H; ++h) {
-                        accD[h] = ldexpf(accD[h], d);
+                for (int h = 0; h < H; ++h) {
+                    accD[h] = ldexpf(accD[h], d);
 #pragma unroll
-                        for (int c = 0; c < NC; ++c) accI[h][c] = ldexpf(accI[h][c], d);
-                    }
+                    for (int c = 0; c < NC; ++c) accI[h][c] = ldexpf(accI[h][c], d);
                 }
-                xmax = x_t;
-                any = true;
-            }
-            const int dt = (int)max(x_t - xmax, (int64_t)-512) - kAccDown;
+            });
+            const int dt = term_shift(x_t, xmax);
 #pragma unroll
-            for (int r = 0; r < K; ++r) b[r] = ((live >> r) & 1) ? ldexpf(ub[r], min(max(ex[r] + sh, -512), 512)) : 0.0f;
+            for (int r = 0; r < K; ++r) b[r] = ((live >> r) & 1) ? at_row_scale(ub[r], ex[r], sh) : 0.0f;
             const float m1 = from_next_lane(b[1]);  // b_t of the next lane's first label state
 #pragma unroll
             for (int h = 0; h < H; ++h) {
@@ -566,7 +558,7 @@ __global__ __launch_bounds__(64) void edit_back_kernel(PostParams q) {
                 accD[h] += eD[h] == 0.0f ? 0.0f : ldexpf(eD[h] * above, dt);  // (nothing enters: no alignment, whatever lies above)
 #pragma unroll
                 for (int c = 0; c < NC; ++c) {
-                    u[h][c] = (in && c < nc) ? ldexpf(uu[h][c], min(max(pec[c] + sh, -512), 512)) : 0.0f;
+                    u[h][c] = (in && c < nc) ? at_row_scale(uu[h][c], pec[c], sh) : 0.0f;
                     const float entry = e1[h] + ((p.collapse && c + 1 == yprev[h]) ? 0.0f : e2[h]);
                     accI[h][c] += entry == 0.0f ? 0.0f : ldexpf(entry * u[h][c], dt);
                 }
@@ -593,13 +585,6 @@ int reg_states_per_lane(int64_t T, int64_t stride, int64_t band) {  // 0: the wi
     return states + 2 <= 128 ? 2 : (states + 2 <= 256 ? 4 : (states + 2 <= 384 ? 6 : (states + 2 <= 512 ? 8 : 0)));
 }
 
-template <int K>
-void launch_both(const PostParams &q, int nc, dim3 grid, size_t lds, hipStream_t stream) {
-    hipLaunchKernelGGL(post_fwd_kernel<K>, grid, dim3(64), lds, stream, q);
-    if (nc <= 4) hipLaunchKernelGGL((post_back_kernel<K, 4>), grid, dim3(64), lds, stream, q);
-    else hipLaunchKernelGGL((post_back_kernel<K, 8>), grid, dim3(64), lds, stream, q);
-}
-
 }  // namespace
 
 // 0 = the kernels hold the call; 1 = the widest window exceeds the 510 register-resident states; 2 = more than 8 labels;
@@ -613,7 +598,7 @@ int ctc_posterior_unsupported(int64_t T, int64_t stride, int64_t band, int64_t N
 // stored forward rows of one labelling (every one of a call has T rows' worth): T * 64K cells, then T exponent words
 size_t ctc_posterior_row_bytes(int64_t T, int64_t stride, int64_t band) {
     const size_t k = (size_t)reg_states_per_lane(T, stride, band);
-    return ((size_t)std::max<int64_t>(T, 1) * (64 * k + 1) * 4 + 255) & ~(size_t)255;
+    return stored_rows_bytes(T, k);
 }
 
 namespace {
@@ -632,52 +617,50 @@ PostParams post_params(const BatchDesc &in, const ScoreDesc &y, int collapse, in
     return q;
 }
 
-template <int K>
-void launch_edits(const PostParams &q, int nc, dim3 grid, size_t lds, hipStream_t stream) {
+// the forward launch, then the backward one: EDIT picks the kernel, the window K, the alphabet NC
+template <bool EDIT, int K>
+void launch_pair(const PostParams &q, dim3 grid, size_t lds, hipStream_t stream) {
     hipLaunchKernelGGL(post_fwd_kernel<K>, grid, dim3(64), lds, stream, q);
-    if (nc <= 4) hipLaunchKernelGGL((edit_back_kernel<K, 4>), grid, dim3(64), lds, stream, q);
-    else hipLaunchKernelGGL((edit_back_kernel<K, 8>), grid, dim3(64), lds, stream, q);
+    if constexpr (EDIT) {
+        if (q.s.in.N - 1 <= 4) hipLaunchKernelGGL((edit_back_kernel<K, 4>), grid, dim3(64), lds, stream, q);
+        else hipLaunchKernelGGL((edit_back_kernel<K, 8>), grid, dim3(64), lds, stream, q);
+    } else {
+        if (q.s.in.N - 1 <= 4) hipLaunchKernelGGL((post_back_kernel<K, 4>), grid, dim3(64), lds, stream, q);
+        else hipLaunchKernelGGL((post_back_kernel<K, 8>), grid, dim3(64), lds, stream, q);
+    }
+}
+
+template <bool EDIT>
+hipError_t launch_walks(const PostParams &q, int64_t band, hipStream_t stream) {
+    const dim3 grid((unsigned)(q.s.in.n_reads * q.s.y.n_hyp));
+    const size_t lds = lds_bytes(q.s.lab_cap, 0);
+    switch (reg_states_per_lane(q.s.in.T, q.s.y.stride, band)) {
+    case 2: launch_pair<EDIT, 2>(q, grid, lds, stream); break;
+    case 4: launch_pair<EDIT, 4>(q, grid, lds, stream); break;
+    case 6: launch_pair<EDIT, 6>(q, grid, lds, stream); break;
+    case 8: launch_pair<EDIT, 8>(q, grid, lds, stream); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
 }
 }  // namespace
 
 hipError_t launch_ctc_posterior(const BatchDesc &in, const ScoreDesc &y, int collapse, int64_t band, float *post,
                                 double *logp, unsigned char *alpha, hipStream_t stream) {
-    const int64_t rows = in.n_reads * y.n_hyp;
-    if (rows <= 0) return hipSuccess;
+    if (in.n_reads * y.n_hyp <= 0) return hipSuccess;
     PostParams q = post_params(in, y, collapse, band, logp, alpha);
     q.post = post;
-    const dim3 grid((unsigned)rows);
-    const size_t lds = lds_bytes(q.s.lab_cap, 0);
-    const int nc = in.N - 1;
-    switch (reg_states_per_lane(in.T, y.stride, band)) {
-    case 2: launch_both<2>(q, nc, grid, lds, stream); break;
-    case 4: launch_both<4>(q, nc, grid, lds, stream); break;
-    case 6: launch_both<6>(q, nc, grid, lds, stream); break;
-    case 8: launch_both<8>(q, nc, grid, lds, stream); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return launch_walks<false>(q, band, stream);
 }
 
 hipError_t launch_ctc_edits(const BatchDesc &in, const ScoreDesc &y, int collapse, int64_t band, float *deletion,
                             float *insertion, double *logp, unsigned char *alpha, hipStream_t stream) {
-    const int64_t rows = in.n_reads * y.n_hyp;
-    if (rows <= 0) return hipSuccess;
+    if (in.n_reads * y.n_hyp <= 0) return hipSuccess;
     PostParams q = post_params(in, y, collapse, band, logp, alpha);
     q.s.slack = 2;  // (both launches: the stored forward rows hold the two states more that a deletion reads)
     q.del = deletion;
     q.ins = insertion;
-    const dim3 grid((unsigned)rows);
-    const size_t lds = lds_bytes(q.s.lab_cap, 0);
-    const int nc = in.N - 1;
-    switch (reg_states_per_lane(in.T, y.stride, band)) {
-    case 2: launch_edits<2>(q, nc, grid, lds, stream); break;
-    case 4: launch_edits<4>(q, nc, grid, lds, stream); break;
-    case 6: launch_edits<6>(q, nc, grid, lds, stream); break;
-    case 8: launch_edits<8>(q, nc, grid, lds, stream); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return launch_walks<true>(q, band, stream);
 }
 
 }  // namespace fcd

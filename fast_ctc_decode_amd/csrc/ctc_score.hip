@@ -31,8 +31,7 @@ namespace fcd {
 namespace {
 
 __device__ __forceinline__ void write_result(const ScoreParams &p, float c0, float c1, int64_t eacc) {
-    const double m = (double)c0 + (double)c1;
-    p.logp[blockIdx.x] = log(m) + (double)eacc * 0.693147180559945309417232121458;
+    p.logp[blockIdx.x] = ln_p((double)c0 + (double)c1, eacc);
 }
 
 // ---- the register-resident window ----

@@ -31,7 +31,7 @@ Every FCD_HIPEMU branch under csrc/:
   made garbage as on the GPU (beam_lane.hip:179, :932; beam_wave_step.inc:643), the all-pairs switch of the lane kernel's
   node order (beam_lane.hip:690);
   in host code --
-    ctc_score.hip:232, ctc_align.hip:430, fcd_internal.h:150 (allow_dynamic_lds)
+    ctc_score.hip:231, ctc_align.hip:421, fcd_internal.h:150 (allow_dynamic_lds)
                                            hipFuncSetAttribute for more than 64 KiB of dynamic LDS is skipped: the launch
                                            that follows is the same kernel;
     tieorder.hip:68, beam_lane.hip:1113    the cycle counters of the profiling builds read back as zeros (fcd_debug.h);
@@ -480,7 +480,7 @@ def crf_marginals_case(fcd, args):
 
 
 # ---- the lattice walks: the run_case functions of their case files, at the T that selects the instantiation ----------
-# CTC (ctc_score.hip:221-239, ctc_align.hip:378-437, ctc_posterior.hip:591-680): an exact window holds 2 T + 1 states (the
+# CTC (ctc_score.hip:220-238, ctc_align.hip:369-428, ctc_posterior.hip:583-664): an exact window holds 2 T + 1 states (the
 # labellings' stride is T), and K = 2 / 4 / 6 / 8 states per lane hold 126 / 254 / 382 / 510; more goes to LDS
 CTC_T = {2: 30, 4: 63, 6: 127, 8: 191, 0: 255}  # (the smallest T of each K but the first; 0: the LDS kernels)
 
@@ -517,17 +517,17 @@ def post_fwd_case(fcd, args):
     CP.run_case(fcd, _ctc_case(fcd, args[0], 3, "post"))
 
 
-def post_back_case(fcd, args):  # <K, NC>: NC = 4 up to four labels, 8 above (ctc_posterior.hip:599)
+def post_back_case(fcd, args):  # <K, NC>: NC = 4 up to four labels, 8 above (ctc_posterior.hip:628)
     import ctc_posterior_cases as CP
     CP.run_case(fcd, _ctc_case(fcd, args[0], 3 if args[1] == 4 else 6, "post"))
 
 
-def edit_back_case(fcd, args):  # (ctc_posterior.hip:638)
+def edit_back_case(fcd, args):  # (ctc_posterior.hip:625)
     import ctc_edits_cases as CE
     CE.run_case(fcd, _ctc_case(fcd, args[0], 3 if args[1] == 4 else 6, "edits"))
 
 
-# CRF (crf_lattice.h:270, crf_lattice.hip:171): an exact window holds T + 1 states; K = 1 / 2 / 4 / 8 hold 64 / 128 / 256 / 512
+# CRF (crf_lattice.h:358, crf_lattice.hip:108): an exact window holds T + 1 states; K = 1 / 2 / 4 / 8 hold 64 / 128 / 256 / 512
 CRF_T = {1: 40, 2: 64, 4: 128, 8: 256}
 
 
@@ -554,7 +554,7 @@ def crf_lattice_case(fcd, args):
         assert math.isfinite(want) and abs(score[b, 0] - want) <= CC.tolerance(Tr), (b, score[b, 0], want)
 
 
-# crfp_back_kernel<K, MM, NB> (crf_posterior.hip:436-443, :478-485, :521-527): the tier follows from the chain m (S = nb^m)
+# crfp_back_kernel<K, MM, NB> (crf_posterior.hip:344-351, :386-393, :429-435): the tier follows from the chain m (S = nb^m)
 # and the labels nb = N - 1; tiers of MM 1 / 2 / 4 hold K = 1, 2, 4 (, 8) as crf_lattice, those of MM 3 / 6 hold 1, 2, 3
 # states per lane at up to 64 / 128 / 192 states
 CRFP_TIER = {(1, 8): (8, 9), (2, 4): (16, 5), (4, 2): (8, 3), (3, 8): (64, 5), (6, 4): (1024, 5)}  # (MM, NB) -> (S, N)
