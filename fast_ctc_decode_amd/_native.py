@@ -60,6 +60,7 @@ SYMBOLS = [
     "fcd_crf_viterbi_search_dev", "fcd_crf_viterbi_search_host",
     "fcd_crf_transition_probs_dev", "fcd_crf_transition_probs_host",
     "fcd_crf_marginals_dev", "fcd_crf_marginals_host",
+    "fcd_crf_occupancy_dev", "fcd_crf_occupancy_host",
 ]
 JOB_PATH, JOB_QUAL, JOB_AMBIGUOUS, JOB_DONE = 1, 2, 4, 1
 
@@ -104,6 +105,12 @@ class Posterior(C.Structure):
 class Edits(C.Structure):
     """fcd_edits: what fcd_ctc_edits_* and fcd_crf_edits_* write (include/fcd.h)."""
     _fields_ = [("deletion", C.c_void_p), ("insertion", C.c_void_p), ("logp", C.c_void_p)]
+
+
+class Occupancy(C.Structure):
+    """fcd_occupancy: what fcd_crf_occupancy_* writes (include/fcd.h)."""
+    _fields_ = [("occ", C.c_void_p), ("stride_row", C.c_int64), ("stride_t", C.c_int64), ("scale", C.c_float),
+                ("accumulate", C.c_int32), ("logp", C.c_void_p)]
 
 
 class Transitions(C.Structure):
@@ -284,6 +291,7 @@ def bind(lib):
         getattr(lib, "fcd_crf_align_" + sfx).argtypes = [P, BP, P, i64, i64, C.POINTER(Labellings), i64, C.POINTER(Alignment)]
         getattr(lib, "fcd_crf_posterior_" + sfx).argtypes = [P, BP, P, i64, i64, C.POINTER(Labellings), i64, C.POINTER(Posterior)]
         getattr(lib, "fcd_crf_edits_" + sfx).argtypes = [P, BP, P, i64, i64, C.POINTER(Labellings), i64, C.POINTER(Edits)]
+        getattr(lib, "fcd_crf_occupancy_" + sfx).argtypes = [P, BP, P, i64, i64, C.POINTER(Labellings), i64, C.POINTER(Occupancy)]
         getattr(lib, "fcd_crf_viterbi_search_" + sfx).argtypes = [P, BP, P, i64, i64, RP, P]
         getattr(lib, "fcd_crf_transition_probs_" + sfx).argtypes = [P, BP, i32, C.POINTER(Transitions)]
         getattr(lib, "fcd_crf_marginals_" + sfx).argtypes = [P, BP, i32, C.POINTER(Marginals)]

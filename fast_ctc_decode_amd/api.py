@@ -665,13 +665,86 @@ def crf_logz(scores, lengths=None):
     "source" layout -> logz (B,) float64, differentiable: the denominator of CRF-CTC training.  Its backward pass is
     grad_out[:, None, None, None] * marginals (crf_marginals_batch_raw) in the dtype of `scores` -- the forward call has
     already computed them, in the same kernel launch; rows at and beyond lengths[b] get gradient 0, a failed read (logz
-    NaN) a NaN gradient.  Nothing synchronises.  Out of scope: the "dest" layout, and the numerator of a training loss (a
-    labelling's own score and its gradient)."""
+    NaN) a NaN gradient.  Nothing synchronises.  Out of scope: the "dest" layout.  The numerator of a training loss -- a
+    labelling's own score and its gradient -- is crf_occupancy_batch_raw's, and crf_ctc_loss is the whole loss."""
     if not _is_torch_cuda(scores):
         raise TypeError("crf_logz takes a torch ROCm tensor")
     if scores.ndim != 4:
         raise TypeError("expected a tensor of rank 4")
     return _crf_logz_function()(scores, lengths)
+
+
+_CRF_CTC_LOSS_FN = []
+
+
+def _crf_ctc_loss_function():
+    if _CRF_CTC_LOSS_FN:
+        return _CRF_CTC_LOSS_FN[0]
+    import torch
+
+    class CrfCtcLoss(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, scores, labels, label_lengths, lengths, start_states):
+            x = scores.detach()
+            tr = crf_transition_probs_batch_raw(x, lengths)
+            # (zeroed: neither launch writes rows at and beyond a read's length, and the gradient there is 0)
+            grad, _, _, status = _crf_marginals_torch(x, lengths, "source", False, False, zeroed=lengths is not None)
+            if start_states is None:
+                init, start = tr.init, tr.init.max(dim=1).values  # (sigma_0: the first maximum, as every CRF walk takes it)
+            else:
+                at = torch.as_tensor(start_states, device=x.device).to(torch.int64).reshape(-1, 1)
+                init = torch.zeros_like(tr.init).scatter_(1, at, 1.0)
+                start = tr.init.gather(1, at)[:, 0]
+            # grad = marginals - occupancy, the gradient of logz - ln(sum over the labelling's alignments of exp(score))
+            occ = crf_occupancy_batch_raw(tr.probs, init, labels, label_lengths, lengths, out=grad, scale=-1.0, accumulate=True)
+            logp = occ.logp[:, 0]
+            loss = -(logp + torch.log(start.to(torch.float64)))
+            # (a labelling whose lattice the occupancy walk gave up comes back with logp NaN: its loss and gradient are NaN)
+            loss = torch.where(status != 0, torch.full_like(loss, float("nan")), loss)  # (selected on the device)
+            ctx.save_for_backward(grad, status, logp)
+            ctx.scores_dtype = scores.dtype
+            return loss
+
+        @staticmethod
+        def backward(ctx, grad_loss):
+            grad, status, logp = ctx.saved_tensors
+            g = grad_loss.to(torch.float32)[:, None, None, None] * grad
+            bad = (status != 0) | ~torch.isfinite(logp)
+            g = torch.where(bad[:, None, None, None], torch.full_like(g, float("nan")), g)  # (selected on the device)
+            return g.to(ctx.scores_dtype), None, None, None, None
+
+    _CRF_CTC_LOSS_FN.append(CrfCtcLoss.apply)
+    return CrfCtcLoss.apply
+
+
+def crf_ctc_loss(scores, labels, label_lengths, lengths=None, start_states=None):
+    """The CRF-CTC training loss.  scores: (B,T,S,N) raw CRF scores, a torch ROCm tensor (float32 / float16 / bfloat16) in
+    the "source" layout; labels (B, Lmax) uint8 with values 1 .. N-1, label_lengths (B,); lengths (B,) rows per read.
+    -> loss (B,) float64, differentiable:  loss_b = -ln P(y_b, sigma_0 | x_b) = logz - ln(sum over the alignments of y_b from
+    sigma_0 of exp(score)).  sigma_0 is the model's most probable start state (the first maximum of the init row
+    crf_transition_probs_batch_raw returns), or start_states[b] ((B,) integers in 0 .. S-1) where given.
+
+    Forward: crf_transition_probs_batch_raw (posteriors, init, logz), crf_marginals_batch_raw (the gradient of logz) and
+    crf_occupancy_batch_raw, which subtracts the labelling's edge occupancies from the marginals in place and returns
+    ln P(y | x, sigma_0).  Backward: grad_out[:, None, None, None] * (marginals - occupancy) in the dtype of `scores`; 0 on
+    rows at and beyond lengths[b]; NaN for a read whose scores fail (loss NaN), whose labelling has no alignment (loss
+    +inf: more labels than rows) or whose lattice the walk gave up (loss NaN).  Nothing synchronises.
+    The lattice walks keep one float32 exponent per row.  A long read that does not support its labelling (near-uniform or
+    random scores against a labelling with many rows per label, as an untrained network gives on a long chunk) puts the
+    forward and backward maxima at opposite ends of the lattice and the cells that carry the probability out of range.  The
+    occupancy walk checks every row's terms against 1 and gives such a labelling up: its loss and gradient are NaN, not
+    wrong.  Chunks of 600 to 1000 rows with about half as many labels are inside the range (INTEGRATION.md section 2m has the
+    measured boundary); train on chunks of that size.
+    Cost of composing existing launches: the backward pass over all labellings runs twice (once for the posteriors, once
+    inside the marginals launch), and two (B,T,S,N) float32 buffers are held (the posteriors until the call returns, the
+    gradient until backward).  Limits: crf_occupancy_batch_raw's, exact lattice: labellings up to 511 labels."""
+    if not _is_torch_cuda(scores):
+        raise TypeError("crf_ctc_loss takes a torch ROCm tensor")
+    if scores.ndim != 4:
+        raise TypeError("expected a tensor of rank 4")
+    if getattr(labels, "ndim", 2) != 2:
+        raise ValueError("labels must have shape (n_reads, Lmax): one labelling per read")
+    return _crf_ctc_loss_function()(scores, labels, label_lengths, lengths, start_states)
 
 
 _DEFAULT_LOGADD = [nat.LOGADD_LOGSUMEXP]
@@ -1195,6 +1268,18 @@ class BatchResult:
         return crf_edits_batch_raw(network_outputs, init_states, self.labels, self.out_len, lengths,
                                    self.path if band else None, band, None, input_dtype, getattr(self, "_handle", None))
 
+    def crf_occupancy(self, network_outputs, init_states, lengths=None, band=0, input_dtype=None):
+        """The edge occupancies under the CRF model of every read's result -> OccupancyResult, occupancy
+        (n_reads, 1, T, S, N): crf_occupancy_batch_raw on this result's own arrays (device results stay on the device).
+        Arguments as crf_score."""
+        if getattr(network_outputs, "ndim", 4) != 4:
+            raise ValueError("crf_occupancy covers the results of the CRF searches, (n_reads, T, S, N) posteriors, not plain CTC results")
+        if band and self.path is None:
+            raise ValueError("a band needs the result's path")
+        return crf_occupancy_batch_raw(network_outputs, init_states, self.labels, self.out_len, lengths,
+                                       self.path if band else None, band, None, input_dtype=input_dtype,
+                                       handle=getattr(self, "_handle", None))
+
     def sequences(self, alphabet, raise_on_error=True, paths="list"):
         """-> list of (str, path) per read, exactly what the single-read functions return.
 
@@ -1565,6 +1650,16 @@ class NBestResult:
         return crf_edits_batch_raw(network_outputs, init_states, self.labels, self.out_len, lengths,
                                    self.path if band else None, band, self.n_hyp, input_dtype,
                                    getattr(self, "_handle", None))
+
+    def crf_occupancy(self, network_outputs, init_states, lengths=None, band=0, input_dtype=None):
+        """The edge occupancies under the CRF model of every hypothesis -> OccupancyResult, occupancy
+        (n_reads, n_best, T, S, N), zeros and logp NaN where i >= n_hyp[r].  crf_occupancy_batch_raw on this result's own
+        arrays; plain CTC results are refused."""
+        if not self.crf or getattr(network_outputs, "ndim", 4) != 4:
+            raise ValueError("crf_occupancy covers the results of the CRF searches, not plain CTC results")
+        return crf_occupancy_batch_raw(network_outputs, init_states, self.labels, self.out_len, lengths,
+                                       self.path if band else None, band, self.n_hyp, input_dtype=input_dtype,
+                                       handle=getattr(self, "_handle", None))
 
     def hypotheses(self, alphabet, raise_on_error=True):
         """-> per read, a list of (seq, path, score), best first (None for a failed read when not raise_on_error)."""
@@ -2303,6 +2398,103 @@ def crf_edits_batch_raw(network_outputs, init_states, labels, label_lengths, len
     return EditResult(dele, ins, logp)
 
 
+class OccupancyResult:
+    """crf_occupancy_batch_raw's result: occupancy (B, n_hyp, T, S, N) float32 -- scale times the probability, over the
+    alignments of labelling (b, i), that the model leaves state s by symbol a at row t (the caller's `out` where one was
+    given; a view of a (T, B, n_hyp, S, N) array under time_major_out) -- and logp (B, n_hyp) float64, crf_score's value.
+    numpy arrays, or torch tensors on the input's device."""
+
+    def __init__(self, occupancy, logp):
+        self.occupancy, self.logp = occupancy, logp
+
+    def cpu(self):
+        """-> an OccupancyResult of numpy arrays (device results: waits for them)"""
+        if isinstance(self.logp, np.ndarray):
+            return self
+        return OccupancyResult(self.occupancy.cpu().numpy(), self.logp.cpu().numpy())
+
+
+def _occupancy_block(out, shape5, elem_strides):
+    """the caller's buffer as fcd_occupancy sees it -> (stride_row, stride_t); shape5 = (B, n_hyp, T, S, N)"""
+    B, n_hyp, T, S, N = shape5
+    if tuple(out.shape) == (B, T, S, N) and n_hyp == 1:
+        st = (elem_strides[0], elem_strides[0]) + tuple(elem_strides[1:])
+    elif tuple(out.shape) == shape5:
+        st = tuple(elem_strides)
+    else:
+        raise ValueError("out must have shape (n_reads, n_hyp, T, S, N) (or (n_reads, T, S, N) for one labelling per read)")
+    if B * n_hyp * T == 0:
+        return S * N, S * N
+    if (N > 1 and st[4] != 1) or (S > 1 and st[3] != N):
+        raise ValueError("out: the (S, N) rows must be dense")
+    if any(v < 0 for v in st) or (T > 1 and st[2] < S * N) or (n_hyp > 1 and B > 1 and st[0] != n_hyp * st[1]):
+        raise ValueError("out: labelling blocks must be evenly spaced, rows at least S * N floats apart")
+    return (st[1] if n_hyp > 1 or B == 1 else st[0]), max(st[2], S * N)
+
+
+def crf_occupancy_batch_raw(network_outputs, init_states, labels, label_lengths, lengths=None, paths=None, band=0,
+                            n_valid=None, out=None, scale=1.0, accumulate=False, time_major_out=False, input_dtype=None,
+                            handle=None):
+    """The edge occupancies of every labelling's own lattice under the CRF model: occupancy[b][i][t][s][a] is the
+    probability, over the alignments of labelling (b, i) to its read, that the model leaves state s by symbol a at row t
+    -- a soft alignment, and the labelled counterpart of crf_marginals_batch_raw's marginals: for raw
+    scores x and (network_outputs, init_states) = crf_transition_probs_batch_raw(x), occupancy - marginals is the gradient
+    of ln P(labelling, start state | x) (include/fcd.h, fcd_crf_occupancy_*; crf_ctc_loss is that composition).
+    -> OccupancyResult with occupancy (B, n_hyp, T, S, N) float32 and logp (B, n_hyp) float64, crf_score's value bit for
+    bit.  For every labelling with a finite logp every row t < lengths[b] sums to 1.  The walks keep one float32 exponent
+    per row: a long read that does not support its labelling (near-uniform posteriors, many rows per label) is outside what
+    they hold; the walk checks every row's sum and gives such a labelling up -- logp NaN and NaN in its rows -- rather than
+    return occupancies that do not add up (include/fcd.h has the rule and the measured range).
+
+    Arguments as crf_score_batch_raw; any S it takes, N - 1 <= 8, windows up to 512 states, S * N up to about 39800.
+    out: a float32 buffer of that shape (or (B, T, S, N) when n_hyp is 1) with dense (S, N) rows, written in place and
+    returned; required with accumulate=True.  The call writes scale * occupancy, or adds it to what `out` holds with
+    accumulate=True.  Rows at and beyond lengths[b], the blocks of labellings without a positive finite probability and
+    of i >= n_valid[b] are not touched (zeros where the call allocates).  time_major_out: the array the call allocates is
+    (T, B, n_hyp, S, N) and its (B, n_hyp, T, S, N) view is returned.
+    Device tensors in: torch tensors on the same device, enqueued on torch's current stream, not synchronised.
+    numpy in: numpy out."""
+    band = _check_band(band, paths)
+    if accumulate and out is None:
+        raise ValueError("accumulate=True needs the buffer to add to: pass out")
+    if out is not None and time_major_out:
+        raise ValueError("time_major_out shapes the array the call allocates: pass either out or time_major_out")
+    h, b, y, (B, n_hyp, stride), dev, keep = _lattice_inputs(network_outputs, labels, label_lengths, lengths, paths, band,
+                                                             n_valid, input_dtype, handle, init_states)
+    init = keep[-1]
+    T, S, N = int(b.T), int(b.S), int(b.N)
+    shape5 = (B, n_hyp, T, S, N)
+    if dev is not None:
+        import torch
+        if out is None:
+            buf = torch.zeros((T, B, n_hyp, S, N) if time_major_out else shape5, dtype=torch.float32, device=dev)
+            occ = buf.permute(1, 2, 0, 3, 4) if time_major_out else buf
+        else:
+            if not _is_torch_cuda(out) or out.device != dev or out.dtype != torch.float32:
+                raise TypeError("out must be a float32 tensor on the inputs' device")
+            occ = out
+        sr, stt = _occupancy_block(occ, shape5, occ.stride())
+        logp = torch.empty((B, n_hyp), dtype=torch.float64, device=dev)
+        o = nat.Occupancy(occ.data_ptr(), sr, stt, float(scale), int(bool(accumulate)), logp.data_ptr())
+        h.check(h.lib.fcd_crf_occupancy_dev(h.ptr, C.byref(b), C.c_void_p(init.data_ptr()), int(init.shape[1]),
+                                            int(init.shape[1]), C.byref(y), band, C.byref(o)))
+        h.hold_in_flight(occ, logp, *keep)
+        return OccupancyResult(occ, logp)
+    if out is None:
+        buf = np.zeros((T, B, n_hyp, S, N) if time_major_out else shape5, np.float32)
+        occ = buf.transpose(1, 2, 0, 3, 4) if time_major_out else buf
+    else:
+        if not isinstance(out, np.ndarray) or out.dtype != np.float32 or not out.flags.writeable:
+            raise TypeError("out must be a writable float32 numpy array")
+        occ = out
+    sr, stt = _occupancy_block(occ, shape5, tuple(v // 4 for v in occ.strides))
+    logp = np.empty((B, n_hyp), np.float64)
+    o = nat.Occupancy(occ.ctypes.data, sr, stt, float(scale), int(bool(accumulate)), logp.ctypes.data)
+    h.check(h.lib.fcd_crf_occupancy_host(h.ptr, C.byref(b), init.ctypes.data, init.shape[1], init.shape[1], C.byref(y), band,
+                                         C.byref(o)))
+    return OccupancyResult(occ, logp)
+
+
 def _crf_sequence_labels(sequence, alpha, what):
     """The labels behind a string crf_beam_search built: it joins the labels' strings leaf to root and reverses the
     CHARACTERS (src/search.rs:146-156), so a multi-character label appears reversed."""
@@ -2375,6 +2567,20 @@ def crf_edits(network_output, init_state, sequence, alphabet):
     x, init, lab, n, L = _crf_one_read(network_output, init_state, sequence, alphabet, "crf_edits")
     r = crf_edits_batch_raw(x, init, lab, n)
     return r.deletion[0, 0, :L].copy(), r.insertion[0, 0, :L + 1].copy(), float(r.logp[0, 0])
+
+
+def crf_occupancy(network_output, init_state, sequence, alphabet):
+    """The edge occupancies of one string (as crf_beam_search returns it) against one (T, S, N) float32 posterior array
+    under the CRF model, exact lattice: -> (occupancy, logp) with occupancy a (T, S, N) float32 array (entry [t][s][a]: the
+    probability, over the string's alignments, of leaving state s by alphabet[a] at row t; every row sums to 1) and logp =
+    ln P(sequence | network_output).  RuntimeError where the string has no alignment of positive finite probability.
+    Argument checks as crf_score."""
+    x, init, lab, n, _ = _crf_one_read(network_output, init_state, sequence, alphabet, "crf_occupancy")
+    r = crf_occupancy_batch_raw(x, init, lab, n)
+    logp = float(r.logp[0, 0])
+    if not np.isfinite(logp):
+        raise RuntimeError("crf_occupancy: the sequence has no alignment of positive finite probability (ln P = %r)" % logp)
+    return r.occupancy[0, 0].copy(), logp
 
 
 # ---------------------------------------------------------------------------------------------

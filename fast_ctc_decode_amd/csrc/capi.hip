@@ -1926,12 +1926,21 @@ struct LatticeCall {
     const fcd_posterior *post = nullptr;
     bool edit = false;
     const fcd_edits *edits = nullptr;
+    bool occupancy = false;  // (CRF)
+    const fcd_occupancy *occ = nullptr;
 };
+
+// floats from the first to the last element the call may address in out->occ (0: none)
+size_t occupancy_span(const fcd_batch *in, const fcd_labellings *y, const fcd_occupancy *o) {
+    if (in->n_reads <= 0 || in->T <= 0) return 0;
+    return (size_t)((in->n_reads * y->n_hyp - 1) * o->stride_row + (in->T - 1) * o->stride_t + in->S * in->N);
+}
 
 int lattice_check(fcd_handle *h, const LatticeCall &c) {
     if (c.align && !c.out) return fail(h, FCD_E_INVALID, "null alignment");
     if (c.posterior && !c.post) return fail(h, FCD_E_INVALID, "null posterior");
     if (c.edit && !c.edits) return fail(h, FCD_E_INVALID, c.crf ? "crf_edits: null output" : "ctc_edits: null output");
+    if (c.occupancy && !c.occ) return fail(h, FCD_E_INVALID, "crf_occupancy: null output");
     const fcd_batch *in = c.in;
     const fcd_labellings *y = c.y;
     int rc = check_batch(h, in, c.crf);
@@ -1948,9 +1957,9 @@ int lattice_check(fcd_handle *h, const LatticeCall &c) {
     if (c.band > 0 && !y->path) return fail(h, FCD_E_INVALID, "a band needs the labellings' path");
     if (y->stride < 0) return fail(h, FCD_E_INVALID, "negative stride");
     if (in->n_reads > 0 && (!y->labels || !y->len ||
-                            !(c.edit ? (const void *)c.edits->deletion : c.posterior ? (const void *)c.post->post
+                            !(c.occupancy ? (const void *)c.occ->occ : c.edit ? (const void *)c.edits->deletion : c.posterior ? (const void *)c.post->post
                               : c.align ? (const void *)c.out->start : (const void *)c.logp)))
-        return fail(h, FCD_E_INVALID, c.edit ? (c.crf ? "crf_edits: null labels/len/deletion" : "ctc_edits: null labels/len/deletion") : c.posterior ? "null labels/len/post"
+        return fail(h, FCD_E_INVALID, c.occupancy ? "crf_occupancy: null labels/len/occ" : c.edit ? (c.crf ? "crf_edits: null labels/len/deletion" : "ctc_edits: null labels/len/deletion") : c.posterior ? "null labels/len/post"
                                       : c.align ? "null labels/len/start" : "null labels/len/logp");
     if (c.edit && in->n_reads > 0 && !c.edits->insertion) return fail(h, FCD_E_INVALID, c.crf ? "crf_edits: null insertion" : "ctc_edits: null insertion");
     if (in->n_reads * y->n_hyp >= (1ll << 31)) return fail(h, FCD_E_UNSUPPORTED, "more than 2^31 labellings in one call");
@@ -1967,7 +1976,23 @@ int lattice_check(fcd_handle *h, const LatticeCall &c) {
                                                      : "ctc_score: the exact lattice does not fit the 160 KiB of LDS: use a band");
     }
     if (c.align && in->n_reads > 0 && !c.out->count) return fail(h, FCD_E_INVALID, "null count");
-    if (c.crf && (c.posterior || c.edit)) {
+    if (c.occupancy) {
+        if (c.occ->stride_row < 0 || c.occ->stride_t < in->S * in->N)
+            return fail(h, FCD_E_INVALID, "crf_occupancy: stride_t must hold a dense (S, N) row, stride_row must not be negative");
+        if (c.occ->accumulate != 0 && c.occ->accumulate != 1) return fail(h, FCD_E_INVALID, "crf_occupancy: accumulate must be 0 or 1");
+        {  // every labelling's block to itself: whole blocks apart (read-major), or rows apart with the blocks interleaved (time-major)
+            const int64_t rows = in->n_reads * y->n_hyp, SN = in->S * in->N, sr = c.occ->stride_row, st = c.occ->stride_t;
+            const bool apart = sr >= (in->T - 1) * st + SN, interleaved = sr >= SN && st >= (rows - 1) * sr + SN;
+            if (rows > 1 && in->T > 0 && !apart && !interleaved)
+                return fail(h, FCD_E_INVALID, "crf_occupancy: the labellings' blocks overlap (stride_row, stride_t)");
+        }
+        switch (crf_occupancy_unsupported(in->T, in->S, in->N, y->stride)) {
+        case 2: return fail(h, FCD_E_UNSUPPORTED, "crf_occupancy: more than 8 labels besides the blank");
+        case 6: return fail(h, FCD_E_UNSUPPORTED, "crf_occupancy: the labelling and the S * N accumulation row do not fit the 160 KiB "
+                                                  "of LDS (4 (min(T, stride) + 1) + 4 S N + 4480 bytes)");
+        default: break;
+        }
+    } else if (c.crf && (c.posterior || c.edit)) {
         int64_t fit = 0;
         const int64_t bnd = std::min<int64_t>(c.band, 1ll << 28);
         const std::string who = c.edit ? "crf_edits" : "crf_posterior";
@@ -2123,7 +2148,22 @@ int lattice_edits(fcd_handle *h, const LatticeCall &c) {
         });
 }
 
+int lattice_occupancy(fcd_handle *h, const LatticeCall &c) {
+    const fcd_batch *in = c.in;
+    const fcd_labellings *y = c.y;
+    const fcd_occupancy *out = c.occ;
+    const int64_t bnd = std::min<int64_t>(c.band, 1ll << 28);
+    return lattice_grouped(
+        h, c, crf_occupancy_row_bytes(in->T, y->stride, bnd), std::min<int64_t>(4ll << 30, workspace_budget(h)), out->logp,
+        [&](CallScope &sc) { sc.add(out->occ, occupancy_span(in, y, out) * 4); },
+        [&](const BatchDesc &d, const ScoreDesc &yd, int64_t r0, int64_t row0, double *logp, unsigned char *alpha, hipStream_t stream) {
+            const OccupancyDesc od{out->occ + row0 * out->stride_row, out->stride_row, out->stride_t, out->scale, out->accumulate};
+            return launch_crf_occupancy(d, yd, c.init + r0 * c.init_stride, c.n_init, c.init_stride, bnd, od, logp, alpha, stream);
+        });
+}
+
 int lattice_run(fcd_handle *h, const LatticeCall &c) {
+    if (c.occupancy) return lattice_occupancy(h, c);
     if (c.edit) return lattice_edits(h, c);
     return c.posterior ? lattice_posterior(h, c) : (c.align ? lattice_align(h, c) : lattice_score(h, c));
 }
@@ -2166,7 +2206,9 @@ int lattice_host(fcd_handle *h, const LatticeCall &c) {
     // (edit entries the kernel does not write -- k >= len, g > len -- come back as 0)
     const int i_del = c.edit ? st.out(c.edits->deletion, cells * 4, true) : -1;
     const int i_ins = c.edit ? st.out(c.edits->insertion, (cells + n_rows) * ((size_t)in->N - 1) * 4, true) : -1;
-    const int i_logp = st.out(c.edit ? c.edits->logp : c.posterior ? c.post->logp : (c.align ? c.out->logp : c.logp), n_rows * 8);
+    // (the occupancies are added to what the block holds, and most of it may stay untouched: it travels both ways)
+    const int i_occ = c.occupancy ? st.inout(c.occ->occ, occupancy_span(in, y, c.occ) * 4) : -1;
+    const int i_logp = st.out(c.occupancy ? c.occ->logp : c.edit ? c.edits->logp : c.posterior ? c.post->logp : (c.align ? c.out->logp : c.logp), n_rows * 8);
     rc = st.commit();
     if (rc) return rc;
     fcd_batch din = *in;
@@ -2188,6 +2230,13 @@ int lattice_host(fcd_handle *h, const LatticeCall &c) {
     d.post = &dpost;
     const fcd_edits dedits{st.at<float>(i_del), st.at<float>(i_ins), st.at<double>(i_logp)};
     d.edits = &dedits;
+    fcd_occupancy docc{};
+    if (c.occupancy) {
+        docc = *c.occ;
+        docc.occ = st.at<float>(i_occ);
+        docc.logp = st.at<double>(i_logp);
+        d.occ = &docc;
+    }
     rc = lattice_run(h, d);
     if (rc) return rc;
     return st.fetch();
@@ -2304,6 +2353,26 @@ int fcd_crf_edits_host(fcd_handle *h, const fcd_batch *in, const float *init, in
     if (!h) return FCD_E_INVALID;
     std::lock_guard<std::recursive_mutex> whole_call(h->mu);  // staging .. copy-back, see run_host
     return lattice_host(h, LatticeCall{true, false, in, y, band, 0, init, n_init, init_stride, nullptr, nullptr, false, nullptr, true, out});
+}
+
+int fcd_crf_occupancy_dev(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init, int64_t init_stride,
+                          const fcd_labellings *y, int64_t band, const fcd_occupancy *out) {
+    if (!h) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> g(h->mu);
+    LatticeCall c{true, false, in, y, band, 0, init, n_init, init_stride, nullptr, nullptr};
+    c.occupancy = true;
+    c.occ = out;
+    return lattice_dev(h, c);
+}
+
+int fcd_crf_occupancy_host(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init, int64_t init_stride,
+                           const fcd_labellings *y, int64_t band, const fcd_occupancy *out) {
+    if (!h) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> whole_call(h->mu);  // staging .. copy-back, see run_host
+    LatticeCall c{true, false, in, y, band, 0, init, n_init, init_stride, nullptr, nullptr};
+    c.occupancy = true;
+    c.occ = out;
+    return lattice_host(h, c);
 }
 
 }  // extern "C"

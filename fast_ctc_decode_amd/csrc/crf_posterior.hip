@@ -35,6 +35,9 @@
 // wave-uniform q.walk: crfp_back_walk<K, MM, NB, WALK> below says where they differ from the substitution walk.  Their
 // accumulators become float32 log-ratios against ln P(y | x) (log_ratio of ctc_lattice.h), as ctc_posterior.hip's edit walk forms them.
 //
+// fcd_crf_occupancy_* (the edge occupancies of the labelling's own lattice) is the forward launch at crf_lattice.hip's K and a
+// fourth walk, crfp_occ_walk below, compiled into crfp_back_kernel<K, 2, 4> only: beta alone, no chains, any S.
+//
 // Scales.  beta and every V share one integer exponent per row.  The step is two passes over the row's posteriors: the
 // first takes only exponents -- the largest frexp(old) + frexp(posterior) over every product of the row, E, reduced as an
 // integer (wave_imax); a product is below 2^E and the largest at least 2^(E-2), so with every product rescaled by the exact
@@ -68,8 +71,13 @@ struct CrfPostParams {
     int m;  // S == nb^m; S == 1: 1 (the one label sigma is made of, before the table cuts it)
     int walk;  // what the backward launch walks (wave-uniform): kWalkSub, kWalkIns, kWalkDel
     float *del, *ins;  // [.. * stride], [.. * (stride + 1) * (N - 1)]                          (fcd_crf_edits_*)
+    // (fcd_crf_occupancy_*) a (T, S, N) block per labelling of this launch, at row * occ_stride_row + t * occ_stride_t
+    float *occ;
+    int64_t occ_stride_row, occ_stride_t;
+    float occ_scale;
+    int occ_clear;  // accumulate = 0: rows t < T_r of a labelling with a value are zeroed before the walk adds to them
 };
-constexpr int kWalkSub = 0, kWalkIns = 1, kWalkDel = 2;
+constexpr int kWalkSub = 0, kWalkIns = 1, kWalkDel = 2, kWalkOcc = 3;
 
 // ---- pass 1: crf_lattice.hip's forward sum, storing what it computes (crf_forward_walk of crf_lattice.h) ----
 template <int K>
@@ -470,10 +478,169 @@ __device__ __forceinline__ void crfp_back_walk(const CrfPostParams &q, unsigned 
     }
 }
 
+// ---- the edge occupancies of the labelling's own lattice (fcd_crf_occupancy_*; include/fcd.h) ----
+// The fourth walk, compiled into crfp_back_kernel<K, 2, 4> only: beta alone, no chain values, so it needs no S == nb^m.
+// Step u = T_r - 1 .. 0, with beta_u in the registers and alpha_{u-1} in the stored rows:
+//   stay[s] = alpha_{u-1}[s] * P(u,s,0)   * beta_u[s]     / P        into entry (sigma_s, 0)
+//   adv[s]  = alpha_{u-1}[s] * P(u,s,y_s) * beta_u[s + 1] / P        into entry (sigma_s, y_s)
+// each the mantissa products (two roundings), the exact power of two 2^(Ea(u-1) + Eb(u) + e - floor(log2 P)) and the division
+// by P's mantissa (one rounding); then beta_{u-1} in place, as the substitution walk forms it.  Several states of a row may
+// share an entry (sigma is the last m labels: a homopolymer run shares one): the row's terms are added up in an S * N float
+// row of LDS behind the labelling's trajectory, and the first lane to exchange an entry for 0 holds its sum and adds
+// scale * sum to the output -- one lane per touched entry, no global atomics; an entry nobody touches is never read or
+// written.  The kernel always adds: with q.occ_clear the walk zeroes rows t < T_r of its block first (a labelling without a
+// positive finite P(y | x) has returned by then: its block keeps what it held).
+// The lattice the rows cannot hold.  alpha and beta keep one exponent per row; where a long read does not support its
+// labelling their maxima sit at opposite ends of the window and the cells that carry the probability fall out of range.
+// The terms of a row sum to 1 exactly, each is within (6 T_r + W + 1) 2^-24 of its value and the wave's sum adds 2 K + 6
+// roundings, so a row whose computed terms are further than kOccLost(T_r) = 2 (6 T_r + 64 K + 2 K + 8) 2^-24 from 1 has lost
+// cells (or P has, in the forward walk): the walk then gives up -- logp = NaN and NaN in every row t < T_r of the block --
+// rather than hand out occupancies that do not add up.
+// the sum of a non-negative value over the wavefront, the same in every lane (wave_imax's network with + for max)
+__device__ __forceinline__ float wave_fsum(float x) {
+    float t = x;
+#define FCD_DPP_FSUM(CTRL, RM) t = t + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(t), CTRL, RM, 0xf, false));
+    FCD_DPP_FSUM(0x111, 0xf)  // row_shr:1
+    FCD_DPP_FSUM(0x112, 0xf)  // row_shr:2
+    FCD_DPP_FSUM(0x114, 0xf)  // row_shr:4
+    FCD_DPP_FSUM(0x118, 0xf)  // row_shr:8   -> lane 15 of every row holds the row's sum
+    FCD_DPP_FSUM(0x142, 0xa)  // row_bcast:15 into rows 1 and 3
+    FCD_DPP_FSUM(0x143, 0xc)  // row_bcast:31 into rows 2 and 3 -> lane 63 holds the sum
+#undef FCD_DPP_FSUM
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t), 63));
+}
+
+template <int K>
+__device__ __forceinline__ void crfp_occ_walk(const CrfPostParams &q, unsigned char *smem) {
+    constexpr int C = 64 * K;
+    const CrfParams &p = q.c;
+    const CrfLds lds = crf_carve(smem);
+    float *sum = reinterpret_cast<float *>(lds.info + p.lab_cap);  // [S * N], behind crf_lds_bytes(lab_cap)
+    CrfRow rw;
+    if (!crf_prologue(p, lds, &rw)) return;
+    const double lp = p.logp[blockIdx.x];
+    if (lp - lp != 0.0) return;  // P = 0, or a NaN on the way: nothing of the block is written
+    const int lane = threadIdx.x, L = rw.L, N = p.in.N, SN = p.in.S * N;
+    float *out = q.occ + (int64_t)blockIdx.x * q.occ_stride_row;
+    for (int e = lane; e < SN; e += 64) sum[e] = 0.0f;
+    if (q.occ_clear) {
+        if (q.occ_stride_t == (int64_t)SN) {
+            for (int64_t e = lane; e < (int64_t)rw.Tr * SN; e += 64) out[e] = 0.0f;
+        } else {
+            for (int t = 0; t < rw.Tr; ++t)
+                for (int e = lane; e < SN; e += 64) out[(int64_t)t * q.occ_stride_t + e] = 0.0f;
+        }
+    }
+    __syncthreads();  // the zeros are in place before another lane adds to them
+    const float *am = q.alpha + (int64_t)blockIdx.x * q.alpha_words;
+    const int *ae = reinterpret_cast<const int *>(am + (int64_t)p.in.T * C);
+    float b[K];
+#pragma unroll
+    for (int r = 0; r < K; ++r) b[r] = 0.0f;
+    int64_t eb = 0;
+    const int64_t xp = (int64_t)floor(lp * 1.44269504088896340735992468100189214);  // floor(log2 P(y | x))
+    const float pman = (float)exp(lp - (double)xp * kLn2);                          // P / 2^xp, in [1, 2]
+    const float lost = 2.0f * (6.0f * (float)rw.Tr + (float)(C + 2 * K + 8)) * 5.9604644775390625e-8f;  // kOccLost(T_r)
+    bool first = true;
+    for (int t0 = (rw.Tr - 1) / p.rows_per_tile * p.rows_per_tile; t0 >= 0; t0 -= p.rows_per_tile) {
+        const int rc = min(p.rows_per_tile, rw.Tr - t0);
+        crf_fill_tile(p, lds, rw, t0, rc);
+        stage_krow_before(lds.misc, rw.path, L, p.band, t0);  // the window of the row before the tile
+        for (int i = rc - 1; i >= 0; --i) {
+            const int u = t0 + i;
+            int lo_u, hi_u;  // the window of row u: the states whose beta the registers hold
+            crf_window(p, lds, rw, u, i, &lo_u, &hi_u);
+            int lo_p = 0, hi_p = 0;  // the window of row u - 1 ("row -1": state 0): the states the terms leave from
+            int64_t x_u = 0;
+            if (u > 0) {
+                crf_window_k(p, rw, u - 1, krow_before(lds.krow, lds.misc, p.band, i), &lo_p, &hi_p);
+                x_u = ae[u - 1];
+            }
+            const float *arow = am + (int64_t)max(u - 1, 0) * C + lane * K;  // alpha_{u-1}, by slot
+            if (first) {  // row T_r - 1: state L
+#pragma unroll
+                for (int r = 0; r < K; ++r) b[r] = slot_state<K>(lane, r, lo_u) == L ? 1.0f : 0.0f;
+                first = false;
+            }
+            // ---- the row's posteriors and the exponents: the largest frexp(beta) + frexp(posterior) over its products ----
+            const float nb0 = from_next_lane(b[0]);  // the next lane's first slot, as it stands at row u
+            float p0[K], py[K], bo[K], bn[K], av[K];
+            int ent[K], ys[K];
+            int emax = kNoExp;
+#pragma unroll
+            for (int r = 0; r < K; ++r) {
+                const int s = slot_state<K>(lane, r, lo_p);
+                const bool live = s <= hi_p;
+                const bool own = live && s >= lo_u && s <= hi_u;          // state s holds a value at row u
+                const bool nxt = live && s + 1 >= lo_u && s + 1 <= hi_u;  // state s + 1 does (s < L: hi_u <= L)
+                const uint32_t info = lds.info[live ? s : 0];  // (a dead slot reads a valid address and is masked below)
+                const uint32_t sg = info & 0xFFFFFFu;
+                const bool table = sg != kNoState;
+                const int sig = table ? (int)sg : 0;
+                ys[r] = (int)(info >> 24);
+                ent[r] = sig * N;
+                bo[r] = own ? b[r] : 0.0f;
+                bn[r] = nxt ? (r + 1 < K ? b[r + 1 < K ? r + 1 : 0] : nb0) : 0.0f;
+                p0[r] = (own && table) ? crf_post_value(p, lds, rw, u, i, sig, 0) : 0.0f;
+                py[r] = (nxt && table) ? crf_post_value(p, lds, rw, u, i, sig, ys[r]) : 0.0f;
+                av[r] = u > 0 ? (live ? arow[r] : 0.0f) : 1.0f;  // ("row -1": state 0, the one live state, holds 1)
+                emax = max(emax, crf_term_exp(bo[r], p0[r]));
+                emax = max(emax, crf_term_exp(bn[r], py[r]));
+            }
+            emax = wave_imax(emax);
+            const int sh = emax == kNoExp ? 0 : kTargetB - emax;
+            x_u += eb;  // the exponent of this step's terms: alpha of row u - 1 times beta of row u
+            const int dt = (int)min(max(x_u - xp, (int64_t)-(1 << 20)), (int64_t)(1 << 20));
+            eb -= sh;
+            // ---- the occupancies of row u, then beta of row u - 1 in place ----
+            float stay[K], adv[K];
+            float mass = 0.0f;
+#pragma unroll
+            for (int r = 0; r < K; ++r) {
+                float m0, my;
+                int e0, ey;
+                crf_split(p0[r], &m0, &e0);
+                crf_split(py[r], &my, &ey);
+                stay[r] = ldexpf((av[r] * m0) * bo[r], min(max(dt + e0, -512), 512)) / pman;
+                adv[r] = ldexpf((av[r] * my) * bn[r], min(max(dt + ey, -512), 512)) / pman;
+                mass += stay[r] + adv[r];
+                if (stay[r] > 0.0f) atomicAdd(&sum[ent[r]], stay[r]);
+                if (adv[r] > 0.0f) atomicAdd(&sum[ent[r] + ys[r]], adv[r]);
+                b[r] = crf_term(bo[r], p0[r], sh) + crf_term(bn[r], py[r], sh);
+            }
+            mass = wave_fsum(mass);
+            if (!(fabsf(mass - 1.0f) <= lost)) {  // (wave-uniform) the rows cannot hold this lattice
+                __syncthreads();
+                for (int t = 0; t < rw.Tr; ++t)
+                    for (int e = lane; e < SN; e += 64) out[(int64_t)t * q.occ_stride_t + e] = NAN;
+                if (lane == 0) p.logp[blockIdx.x] = (double)NAN;
+                return;
+            }
+            __syncthreads();  // every term of the row is in its entry
+            float *orow = out + (int64_t)u * q.occ_stride_t;
+#pragma unroll
+            for (int r = 0; r < K; ++r) {
+                if (stay[r] > 0.0f) {
+                    const float v = atomicExch(&sum[ent[r]], 0.0f);  // the first lane here takes the sum and leaves the entry clear
+                    if (v != 0.0f) orow[ent[r]] = orow[ent[r]] + q.occ_scale * v;
+                }
+                if (adv[r] > 0.0f) {
+                    const float v = atomicExch(&sum[ent[r] + ys[r]], 0.0f);
+                    if (v != 0.0f) orow[ent[r] + ys[r]] = orow[ent[r] + ys[r]] + q.occ_scale * v;
+                }
+            }
+            __syncthreads();  // ... and clear again before the next row adds
+        }
+    }
+}
+
 template <int K, int MM, int NB>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void crfp_back_kernel(CrfPostParams q) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    // (every instantiation carries all three walks within its 256 registers: a kernel's count is its widest walk's)
+    // (every instantiation carries these three walks within its 256 registers: a kernel's count is its widest walk's)
+    if constexpr (MM == 2 && NB == 4) {  // (the occupancy walk rides in these four only)
+        if (q.walk == kWalkOcc) return crfp_occ_walk<K>(q, smem);
+    }
     if (q.walk == kWalkIns) return crfp_back_walk<K, MM, NB, kWalkIns>(q, smem);
     if (q.walk == kWalkDel) return crfp_back_walk<K, MM, NB, kWalkDel>(q, smem);
     crfp_back_walk<K, MM, NB, kWalkSub>(q, smem);
@@ -607,6 +774,64 @@ hipError_t launch_crf_edits(const BatchDesc &in, const ScoreDesc &y, const float
     q[1].ins = q[2].ins = insertion;
     q[1].del = q[2].del = deletion;
     return launch_crf_walks(q, 2, in, y, init, n_init, init_stride, band, logp, alpha, stream);
+}
+
+// ---- fcd_crf_occupancy_*: crfp_fwd_kernel<K>, then the occupancy walk in crfp_back_kernel<K, 2, 4> ----
+namespace {
+constexpr size_t kOccLdsLimit = 160 * 1024;  // what a workgroup is granted on gfx950
+
+size_t crf_occupancy_lds_bytes(int64_t T, int64_t S, int64_t N, int64_t stride) {
+    return crf_lds_bytes((int)std::min<int64_t>(std::min(T, stride) + 1, 1 << 24)) + (size_t)S * (size_t)N * 4;
+}
+
+template <int K>
+hipError_t launch_occupancy_pair(const CrfPostParams *q, dim3 grid, size_t lds_fwd, size_t lds_back, hipStream_t stream) {
+    const hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(crfp_back_kernel<K, 2, 4>), (int)lds_back);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(crfp_fwd_kernel<K>, grid, dim3(64), lds_fwd, stream, q[0]);
+    hipLaunchKernelGGL((crfp_back_kernel<K, 2, 4>), grid, dim3(64), lds_back, stream, q[1]);
+    return hipGetLastError();
+}
+}  // namespace
+
+// 0 = the kernels hold the call; 2 = more than 8 labels, 6 = the labelling and the S * N row exceed the LDS of a workgroup
+int crf_occupancy_unsupported(int64_t T, int64_t S, int64_t N, int64_t stride) {
+    if (N - 1 > 8) return 2;
+    if (S > (1 << 24) || crf_occupancy_lds_bytes(T, S, N, stride) > kOccLdsLimit) return 6;
+    return 0;
+}
+
+size_t crf_occupancy_row_bytes(int64_t T, int64_t stride, int64_t band) {
+    return stored_rows_bytes(T, (size_t)crf_states_per_lane(T, stride, band));
+}
+
+hipError_t launch_crf_occupancy(const BatchDesc &in, const ScoreDesc &y, const float *init, int64_t n_init, int64_t init_stride,
+                                int64_t band, const OccupancyDesc &out, double *logp, unsigned char *alpha, hipStream_t stream) {
+    const int64_t rows = in.n_reads * y.n_hyp;
+    if (rows <= 0) return hipSuccess;
+    CrfPostParams q[2] = {};
+    for (int w = 0; w < 2; ++w) {
+        q[w].c = crf_params(in, y, init, n_init, init_stride, band);
+        q[w].c.logp = logp;
+        q[w].alpha = reinterpret_cast<float *>(alpha);
+        q[w].alpha_words = (int64_t)(crf_occupancy_row_bytes(in.T, y.stride, band) / 4);
+        q[w].m = 1;  // (no chain values: the walk never asks)
+        q[w].walk = w ? kWalkOcc : kWalkSub;
+        q[w].occ = out.occ;
+        q[w].occ_stride_row = out.stride_row;
+        q[w].occ_stride_t = out.stride_t;
+        q[w].occ_scale = out.scale;
+        q[w].occ_clear = out.accumulate ? 0 : 1;
+    }
+    const dim3 grid((unsigned)rows);
+    const size_t lds_fwd = crf_lds_bytes(q[0].c.lab_cap), lds_back = lds_fwd + (size_t)in.S * (size_t)in.N * 4;
+    switch (crf_states_per_lane(in.T, y.stride, band)) {
+    case 1: return launch_occupancy_pair<1>(q, grid, lds_fwd, lds_back, stream);
+    case 2: return launch_occupancy_pair<2>(q, grid, lds_fwd, lds_back, stream);
+    case 4: return launch_occupancy_pair<4>(q, grid, lds_fwd, lds_back, stream);
+    case 8: return launch_occupancy_pair<8>(q, grid, lds_fwd, lds_back, stream);
+    default: return hipErrorInvalidValue;
+    }
 }
 
 }  // namespace fcd

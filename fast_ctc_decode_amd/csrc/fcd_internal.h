@@ -328,6 +328,21 @@ hipError_t launch_crf_posterior(const BatchDesc &in, const ScoreDesc &y, const f
 hipError_t launch_crf_edits(const BatchDesc &in, const ScoreDesc &y, const float *init, int64_t n_init, int64_t init_stride,
                             int64_t band, float *deletion, float *insertion, double *logp, unsigned char *alpha,
                             hipStream_t stream);
+// CRF edge occupancies of the same labellings' own lattices (crf_posterior.hip; fcd_crf_occupancy_* in include/fcd.h), on top
+// of crf_lattice_unsupported: crfp_fwd_kernel<K> and a fourth walk inside crfp_back_kernel<K, 2, 4>, K = 1, 2, 4, 8 as the
+// score's.  crf_occupancy_unsupported: 0 = the kernels hold the call; 2 = more than 8 labels, 6 = the labelling's LDS copy
+// plus the S * N accumulation row exceed the 160 KiB of a workgroup.  alpha: crf_occupancy_row_bytes() per labelling of the
+// launch; out.occ: the first labelling's block; logp must not be null.
+struct OccupancyDesc {
+    float *occ;
+    int64_t stride_row, stride_t;
+    float scale;
+    int accumulate;
+};
+int crf_occupancy_unsupported(int64_t T, int64_t S, int64_t N, int64_t stride);
+size_t crf_occupancy_row_bytes(int64_t T, int64_t stride, int64_t band);
+hipError_t launch_crf_occupancy(const BatchDesc &in, const ScoreDesc &y, const float *init, int64_t n_init, int64_t init_stride,
+                                int64_t band, const OccupancyDesc &out, double *logp, unsigned char *alpha, hipStream_t stream);
 
 hipError_t launch_logspace_probe(const float *a, const float *b, float *out_add, float *out_ln,
                                  int64_t n, int mode, hipStream_t stream);

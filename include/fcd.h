@@ -683,6 +683,72 @@ int fcd_crf_edits_dev(fcd_handle *h, const fcd_batch *in, const float *init, int
 int fcd_crf_edits_host(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init, int64_t init_stride,
                        const fcd_labellings *y, int64_t band, const fcd_edits *out);
 
+/* ---- CRF edge occupancies of given labellings (csrc/crf_posterior.hip) ----
+ * NOT a reference function.  The gradient half of a CRF-CTC loss's numerator, and a soft alignment of a called sequence:
+ * the probability, over the alignments of labelling y, that the model leaves state s by symbol a at row t -- the labelled
+ * counterpart of fcd_crf_marginals_*'s marg, with  d ln P(y, sigma_0 | x) / d x[t][s][a] = occ[t][s][a] - marg[t][s][a]
+ * for raw scores x whose (posteriors, init) fcd_crf_transition_probs_* made.
+ * Everything is as fcd_crf_score_* defines it: batch (n_reads, T, S, N), nb = N - 1, sigma_0 the first maximum of the init
+ * row, sigma_{k+1} = (sigma_k nb) mod S + (y_k - 1), a sigma outside the table reads as 0, the lattice k = 0 .. L, under
+ * band = W the window from y->path.  alpha is fcd_crf_score_*'s, beta fcd_crf_posterior_*'s: beta_{T_r-1}[L] = 1,
+ * beta_{u-1}[k] = P(u,k,0) beta_u[k] + P(u,k,y_k) beta_u[k+1], and P = alpha_{T_r-1}[L].  For a row t < T_r:
+ *   stay_t[k] = alpha_{t-1}[k] * p[t][sigma_k][0]   * beta_t[k]   / P
+ *   adv_t[k]  = alpha_{t-1}[k] * p[t][sigma_k][y_k] * beta_t[k+1] / P          (k < L)
+ *   occ[t][s][0] = sum_{k: sigma_k = s} stay_t[k]
+ *   occ[t][s][a] = sum_{k: sigma_k = s, y_k = a} adv_t[k]                       (a >= 1)
+ * over the cells live in both rows' windows ("row -1" is state 0 holding 1): exact at band = 0.  Several states of a row may
+ * share an entry (S = 4: sigma_k = y_{k-1} - 1); their sum is taken in an unspecified order.  Every row of occ sums to 1.
+ * Output: fcd_occupancy.  Labelling row = r * n_hyp + i has its own (T, S, N) block of f32, dense (S, N) rows, row t at
+ * occ + row * stride_row + t * stride_t (64-bit offsets; with n_hyp = 1 a marg buffer of fcd_crf_marginals_*, time-major
+ * included).  accumulate = 0: block[t][s][a] = scale * occ;  accumulate = 1: block[t][s][a] += scale * occ (one f32 product,
+ * one f32 sum).  An entry whose occupancy is 0 is not read under accumulate = 1.  logp (nullable): fcd_crf_score_*'s value,
+ * the same forward recurrence, bit for bit (NaN for a labelling the walk gives up, below).
+ * Rows without a value: logp follows fcd_crf_score_*'s order and values.  Whenever P(y | x) is not a positive finite number
+ * nothing of the labelling's block is written (accumulate = 0: not even the zeros); rows t >= T_r and the blocks of
+ * i >= n_valid[r] are never touched.  L = 0 is a labelling like any other: occupancy 1 on (sigma_0, 0) in every row.
+ * Arithmetic: pass 1 is fcd_crf_score_*'s forward recurrence with every row stored; pass 2 walks the rows backwards with
+ * beta alone (f32, one integer exponent per row, exact power-of-two scales).  A term is two mantissa products, the exact
+ * power of two 2^(Ea(t-1) + Eb(t) + e - floor(log2 P)) and the division by P's mantissa -- three roundings; no fused
+ * multiply-add; every term non-negative.  Error bound, by roundings along the longest chain: alpha_{t-1} 3 t, beta_t
+ * 3 (T_r - 1 - t), the term 3, P 3 T_r and its mantissa 1, the sum of an entry's terms at most W - 1 (W: the window's states):
+ *   |occ - exact| <= (6 T_r + W + 1) 2^-24 * occ;   accumulate = 1 adds 2^-24 |block| for the final sum.
+ * What the rows can hold.  alpha and beta keep one f32 exponent per row, and a cell below 2^-160 of its row's maximum may
+ * be dropped, as in fcd_crf_posterior_*.  Where the read supports its labelling (the read it was decoded from does; so does
+ * any band around its path) the two rows' maxima meet on the alignments that carry the probability and the dropped cells
+ * carry less than 2^-100 of occupancy.  Where it does not -- near-uniform or random posteriors against a labelling with
+ * many rows per label -- the maxima sit at opposite ends of the window and cells that carry probability fall out of
+ * range.  The walk checks every row: its terms must sum to 1 within
+ *   lost(T_r) = 2 (6 T_r + 64 K + 2 K + 8) 2^-24        (K = 1, 2, 4, 8: the states a lane holds; twice the roundings above)
+ * and a labelling with a row that does not is given up: logp = NaN (not fcd_crf_score_*'s value) and NaN in every row
+ * t < T_r of its block, accumulate = 1 included.  So for every labelling with a finite logp every row of occ sums to 1
+ * within lost(T_r), and an entry is within the relative bound above plus, at worst, the mass its row may have lost, an
+ * absolute lost(T_r) + (6 T_r + W + 1) 2^-24.  Measured range at S = 4, N = 5, exact lattice:
+ * uniform random posteriors hold (T, L) = (330, 300), (600, 511), (1000, 511), (1500, 511) and are given up at (1500, 255),
+ * (1500, 127), (4000, 127); past about 2000 rows fcd_crf_score_*'s own value is no longer right for such reads.
+ * FCD_E_INVALID: fcd_crf_score_*'s cases; a null out or out->occ; stride_t < S N; stride_row < 0; accumulate not 0 or 1;
+ * with more than one labelling, blocks that overlap: either stride_row >= (T - 1) stride_t + S N (whole blocks apart) or
+ * stride_row >= S N and stride_t >= (n_reads n_hyp - 1) stride_row + S N (time-major: the blocks interleaved row by row).
+ * Limits (FCD_E_UNSUPPORTED; the message says which): fcd_crf_score_*'s (windows up to 512 states, the band named beyond);
+ *   N - 1 <= 8;  the labelling and an S * N float row live in the 160 KiB of LDS a workgroup is granted:
+ *   4 (min(T, stride) + 1) + 4 S N + 4480 <= 163840 -- S = 1024 and S = 4096 at N = 5 fit (S N up to about 39800 for a short labelling).
+ *   No S = nb^m is asked for: any S fcd_crf_score_* takes.
+ * _dev: device pointers, enqueue-only on the handle's stream, behind every overlapping call in flight, as
+ * fcd_crf_posterior_*; the stored forward rows live in the handle's workspace and the labellings are launched in groups
+ * of whole reads that fit it, forward then backward per group.  _host: host pointers; stages (the block travels both ways),
+ * runs and copies back in one piece. */
+typedef struct fcd_occupancy {
+    float *occ;          /* the first labelling's block */
+    int64_t stride_row;  /* floats between the blocks of two labellings */
+    int64_t stride_t;    /* floats between two rows of a block, >= S * N */
+    float scale;
+    int32_t accumulate;  /* 0: block = scale * occ; 1: block += scale * occ */
+    double *logp;        /* [n_reads * n_hyp], nullable */
+} fcd_occupancy;
+int fcd_crf_occupancy_dev(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init, int64_t init_stride,
+                          const fcd_labellings *y, int64_t band, const fcd_occupancy *out);
+int fcd_crf_occupancy_host(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init, int64_t init_stride,
+                           const fcd_labellings *y, int64_t band, const fcd_occupancy *out);
+
 /* ---- search::crf_greedy_search (src/search.rs:385-423) ---- */
 int fcd_crf_greedy_search_dev(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init,
                               int64_t init_stride, const fcd_result *out);
