@@ -61,6 +61,7 @@ SYMBOLS = [
     "fcd_crf_transition_probs_dev", "fcd_crf_transition_probs_host",
     "fcd_crf_marginals_dev", "fcd_crf_marginals_host",
     "fcd_crf_occupancy_dev", "fcd_crf_occupancy_host",
+    "fcd_ctc_occupancy_dev", "fcd_ctc_occupancy_host",
 ]
 JOB_PATH, JOB_QUAL, JOB_AMBIGUOUS, JOB_DONE = 1, 2, 4, 1
 
@@ -108,7 +109,7 @@ class Edits(C.Structure):
 
 
 class Occupancy(C.Structure):
-    """fcd_occupancy: what fcd_crf_occupancy_* writes (include/fcd.h)."""
+    """fcd_occupancy: what fcd_crf_occupancy_* and fcd_ctc_occupancy_* write (include/fcd.h)."""
     _fields_ = [("occ", C.c_void_p), ("stride_row", C.c_int64), ("stride_t", C.c_int64), ("scale", C.c_float),
                 ("accumulate", C.c_int32), ("logp", C.c_void_p)]
 
@@ -283,6 +284,7 @@ def bind(lib):
         getattr(lib, "fcd_ctc_align_" + sfx).argtypes = [P, BP, C.POINTER(Labellings), i32, i64, C.POINTER(Alignment)]
         getattr(lib, "fcd_ctc_posterior_" + sfx).argtypes = [P, BP, C.POINTER(Labellings), i32, i64, C.POINTER(Posterior)]
         getattr(lib, "fcd_ctc_edits_" + sfx).argtypes = [P, BP, C.POINTER(Labellings), i32, i64, C.POINTER(Edits)]
+        getattr(lib, "fcd_ctc_occupancy_" + sfx).argtypes = [P, BP, C.POINTER(Labellings), i32, i64, C.POINTER(Occupancy)]
     lib.fcd_debug_set_align_workspace_cap.argtypes = [P, i64]
     lib.fcd_debug_workspace_bytes.argtypes = [P]
     lib.fcd_debug_workspace_bytes.restype = i64

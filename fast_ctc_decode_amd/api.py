@@ -1225,6 +1225,18 @@ class BatchResult:
                                    self.path if band else None, band, None, input_dtype,
                                    getattr(self, "_handle", None))
 
+    def ctc_occupancy(self, network_outputs, collapse_repeats=True, lengths=None, band=0, input_dtype=None):
+        """The label occupancies of every read's result -> OccupancyResult, occupancy (n_reads, 1, T, N):
+        ctc_occupancy_batch_raw on this result's own arrays (device results stay on the device).  Arguments as
+        ctc_posterior.  CRF results are refused (transition-scored models: a different lattice)."""
+        if isinstance(self, _CrfBatchResult) or getattr(network_outputs, "ndim", 3) != 3:
+            raise ValueError("ctc_occupancy covers the plain CTC searches, not CRF results")
+        if band and self.path is None:
+            raise ValueError("a band needs the result's path")
+        return ctc_occupancy_batch_raw(network_outputs, self.labels, self.out_len, collapse_repeats, lengths,
+                                       self.path if band else None, band, None, input_dtype=input_dtype,
+                                       handle=getattr(self, "_handle", None))
+
     def crf_score(self, network_outputs, init_states, lengths=None, band=0, input_dtype=None):
         """ln P(labelling | posteriors) under the CRF model of every read's result, float64 (n_reads, 1):
         crf_score_batch_raw on this result's own arrays.  For the results of the CRF searches, with the (B,T,S,N)
@@ -1612,6 +1624,15 @@ class NBestResult:
         return ctc_edits_batch_raw(network_outputs, self.labels, self.out_len, collapse_repeats, lengths,
                                    self.path if band else None, band, self.n_hyp, input_dtype,
                                    getattr(self, "_handle", None))
+
+    def ctc_occupancy(self, network_outputs, collapse_repeats=True, lengths=None, band=0, input_dtype=None):
+        """The label occupancies of every hypothesis -> OccupancyResult, occupancy (n_reads, n_best, T, N), zeros and logp
+        NaN where i >= n_hyp[r].  ctc_occupancy_batch_raw on this result's own arrays; CRF results are refused."""
+        if self.crf or getattr(network_outputs, "ndim", 3) != 3:
+            raise ValueError("ctc_occupancy covers the plain CTC searches, not CRF results")
+        return ctc_occupancy_batch_raw(network_outputs, self.labels, self.out_len, collapse_repeats, lengths,
+                                       self.path if band else None, band, self.n_hyp, input_dtype=input_dtype,
+                                       handle=getattr(self, "_handle", None))
 
     def crf_score(self, network_outputs, init_states, lengths=None, band=0, input_dtype=None):
         """ln P(labelling | posteriors) under the CRF model of every hypothesis, float64 (n_reads, n_best); NaN where
@@ -2402,7 +2423,8 @@ class OccupancyResult:
     """crf_occupancy_batch_raw's result: occupancy (B, n_hyp, T, S, N) float32 -- scale times the probability, over the
     alignments of labelling (b, i), that the model leaves state s by symbol a at row t (the caller's `out` where one was
     given; a view of a (T, B, n_hyp, S, N) array under time_major_out) -- and logp (B, n_hyp) float64, crf_score's value.
-    numpy arrays, or torch tensors on the input's device."""
+    ctc_occupancy_batch_raw's result: occupancy (B, n_hyp, T, N), the probability that row t emits symbol c, and ctc_score's
+    logp.  numpy arrays, or torch tensors on the input's device."""
 
     def __init__(self, occupancy, logp):
         self.occupancy, self.logp = occupancy, logp
@@ -2493,6 +2515,150 @@ def crf_occupancy_batch_raw(network_outputs, init_states, labels, label_lengths,
     h.check(h.lib.fcd_crf_occupancy_host(h.ptr, C.byref(b), init.ctypes.data, init.shape[1], init.shape[1], C.byref(y), band,
                                          C.byref(o)))
     return OccupancyResult(occ, logp)
+
+
+def ctc_occupancy_batch_raw(network_outputs, labels, label_lengths, collapse_repeats=True, lengths=None, paths=None, band=0,
+                            n_valid=None, out=None, scale=1.0, accumulate=False, time_major_out=False, input_dtype=None,
+                            handle=None):
+    """The label occupancies of every labelling under plain CTC: occupancy[b][i][t][c] is the probability, over the
+    alignments of labelling (b, i) to its read, that row t emits symbol c (0: the blank) -- the soft version of
+    ctc_align_batch_raw's spans, and the gradient of ln P(labelling | x) by ln x[t][c]: at the logits of a softmax the
+    gradient of -ln P is softmax - occupancy (include/fcd.h, fcd_ctc_occupancy_*; ctc_loss is that composition).
+    -> OccupancyResult with occupancy (B, n_hyp, T, N) float32 and logp (B, n_hyp) float64, ctc_score's value bit for bit.
+    For every labelling with a finite logp every row t < lengths[b] sums to 1.  The walks keep one float32 exponent per
+    row: a long read that does not support its labelling (near-uniform posteriors, many rows per label) is outside what
+    they hold; the walk checks every row's sum and gives such a labelling up -- logp NaN and NaN in its rows -- rather than
+    return occupancies that do not add up (include/fcd.h has the rule, INTEGRATION.md section 2n the measured range).
+
+    Arguments as ctc_posterior_batch_raw, and its limits: windows of at most 510 states (bands up to 126, exact mode up to
+    254 rows or labels) and N - 1 <= 8.  out: a float32 buffer of that shape (or (B, T, N), the shape of the input, when
+    n_hyp is 1) with dense rows of N, written in place and returned; required with accumulate=True.  The call writes
+    scale * occupancy, or adds it to what `out` holds with accumulate=True: out=softmax.clone(), scale=-1,
+    accumulate=True leaves the logit gradient of -ln P.  Rows at and beyond lengths[b], the blocks of labellings without a
+    positive finite probability and of i >= n_valid[b] are not touched (zeros where the call allocates).  time_major_out:
+    the array the call allocates is (T, B, n_hyp, N) and its (B, n_hyp, T, N) view is returned.
+    Device tensors in: torch tensors on the same device, enqueued on torch's current stream, not synchronised.
+    numpy in: numpy out."""
+    band = _check_band(band, paths)
+    if accumulate and out is None:
+        raise ValueError("accumulate=True needs the buffer to add to: pass out")
+    if out is not None and time_major_out:
+        raise ValueError("time_major_out shapes the array the call allocates: pass either out or time_major_out")
+    h, b, y, (B, n_hyp, stride), dev, keep = _lattice_inputs(network_outputs, labels, label_lengths, lengths, paths, band,
+                                                             n_valid, input_dtype, handle)
+    T, N = int(b.T), int(b.N)
+    shape4 = (B, n_hyp, T, N)
+
+    def block(occ, elem_strides):  # (fcd_occupancy's layout with S = 1: the (S, N) row is the row of N)
+        if occ.ndim not in (3, 4):
+            raise ValueError("out must have shape (n_reads, n_hyp, T, N) (or (n_reads, T, N) for one labelling per read)")
+        shp, st = tuple(occ.shape), tuple(elem_strides)
+        return _occupancy_block(_Shaped(shp[:-1] + (1, shp[-1])), (B, n_hyp, T, 1, N), st[:-1] + (N, st[-1]))
+    col = int(bool(collapse_repeats))
+    if dev is not None:
+        import torch
+        if out is None:
+            buf = torch.zeros((T, B, n_hyp, N) if time_major_out else shape4, dtype=torch.float32, device=dev)
+            occ = buf.permute(1, 2, 0, 3) if time_major_out else buf
+        else:
+            if not _is_torch_cuda(out) or out.device != dev or out.dtype != torch.float32:
+                raise TypeError("out must be a float32 tensor on the inputs' device")
+            occ = out
+        sr, stt = block(occ, occ.stride())
+        logp = torch.empty((B, n_hyp), dtype=torch.float64, device=dev)
+        o = nat.Occupancy(occ.data_ptr(), sr, stt, float(scale), int(bool(accumulate)), logp.data_ptr())
+        h.check(h.lib.fcd_ctc_occupancy_dev(h.ptr, C.byref(b), C.byref(y), col, band, C.byref(o)))
+        h.hold_in_flight(occ, logp, *keep)
+        return OccupancyResult(occ, logp)
+    if out is None:
+        buf = np.zeros((T, B, n_hyp, N) if time_major_out else shape4, np.float32)
+        occ = buf.transpose(1, 2, 0, 3) if time_major_out else buf
+    else:
+        if not isinstance(out, np.ndarray) or out.dtype != np.float32 or not out.flags.writeable:
+            raise TypeError("out must be a writable float32 numpy array")
+        occ = out
+    sr, stt = block(occ, tuple(v // 4 for v in occ.strides))
+    logp = np.empty((B, n_hyp), np.float64)
+    o = nat.Occupancy(occ.ctypes.data, sr, stt, float(scale), int(bool(accumulate)), logp.ctypes.data)
+    h.check(h.lib.fcd_ctc_occupancy_host(h.ptr, C.byref(b), C.byref(y), col, band, C.byref(o)))
+    return OccupancyResult(occ, logp)
+
+
+class _Shaped:
+    """what _occupancy_block reads of a buffer: its shape"""
+
+    def __init__(self, shape):
+        self.shape = shape
+
+
+def ctc_occupancy(network_output, sequence, alphabet, collapse_repeats=True):
+    """The label occupancies of one string against one (T, N) float32 posterior matrix, exact lattice: -> (occupancy,
+    logp) with occupancy a (T, N) float32 array (entry [t][c]: the probability, over the string's alignments, that row t
+    emits alphabet[c]; every row sums to 1) and logp = ln P(sequence | network_output).  RuntimeError where the string has
+    no alignment of positive finite probability.  Argument checks as ctc_score."""
+    x = _as_f32(network_output, 2, "network_output")
+    alpha = _seq_to_vec(alphabet)
+    _check_greedy_alphabet(len(alpha), x.shape[1])
+    y = _sequence_labels(sequence, alpha, "ctc_occupancy")
+    lab = np.zeros((1, max(len(y), 1)), np.uint8)
+    lab[0, :len(y)] = y
+    r = ctc_occupancy_batch_raw(_dense(x)[None], lab, np.array([len(y)], np.uint32), collapse_repeats)
+    logp = float(r.logp[0, 0])
+    if not np.isfinite(logp):
+        raise RuntimeError("ctc_occupancy: the sequence has no alignment of positive finite probability (ln P = %r)" % logp)
+    return r.occupancy[0, 0].copy(), logp
+
+
+_CTC_LOSS_FN = []
+
+
+def _ctc_loss_function():
+    if _CTC_LOSS_FN:
+        return _CTC_LOSS_FN[0]
+    import torch
+
+    class CtcLoss(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, log_probs, labels, label_lengths, lengths, collapse_repeats, paths, band):
+            probs = log_probs.detach().exp()
+            occ = ctc_occupancy_batch_raw(probs, labels, label_lengths, collapse_repeats, lengths, paths, band, scale=-1.0)
+            logp = occ.logp[:, 0]
+            ctx.save_for_backward(occ.occupancy[:, 0], logp)  # -occupancy: zeros beyond lengths[b] and where P = 0
+            ctx.in_dtype = log_probs.dtype
+            return -logp
+
+        @staticmethod
+        def backward(ctx, grad_loss):
+            neg_occ, logp = ctx.saved_tensors
+            g = grad_loss.to(torch.float32)[:, None, None] * neg_occ
+            # (a given-up labelling holds NaN already; any other NaN loss has a NaN gradient too -- selected on the device)
+            g = torch.where(torch.isnan(logp)[:, None, None], torch.full_like(g, float("nan")), g)
+            return g.to(ctx.in_dtype), None, None, None, None, None, None
+
+    _CTC_LOSS_FN.append(CtcLoss.apply)
+    return CtcLoss.apply
+
+
+def ctc_loss(log_probs, labels, label_lengths, lengths=None, collapse_repeats=True, paths=None, band=0):
+    """The CTC training loss on ctc_score's own lattice.  log_probs: (B, T, N) log-posteriors (the output of log_softmax), a
+    torch ROCm tensor (float32 / float16 / bfloat16) of any non-negative strides -- a (T, B, N) tensor's .permute(1, 0, 2)
+    is taken as it is; labels (B, Lmax) uint8 with values 1 .. N-1, label_lengths (B,); lengths (B,) rows per read.
+    -> loss (B,) float64, differentiable:  loss_b = -ln P(y_b | x_b), ctc_score_batch_raw's value negated.  The caller
+    reduces.  collapse_repeats=False, and band=W > 0 with paths (the banded sum and its own exact gradient), as ctc_score.
+
+    Forward: one elementwise exp, then one ctc_occupancy_batch_raw call, which yields ln P and the occupancies that are
+    saved.  Backward: grad_log_probs = -grad_out[:, None, None] * occupancy in the dtype of log_probs, 0 on rows at and
+    beyond lengths[b]; no loop over rows or reads, nothing synchronises.  A read without an alignment (P = 0: more labels
+    than rows) has loss +inf and gradient 0; a labelling the occupancy walk gives up (a long read that does not support it:
+    ctc_occupancy_batch_raw) has a NaN loss and a NaN gradient, as has a NaN posterior or a label outside 1 .. N-1.
+    Limits: ctc_occupancy_batch_raw's -- exact up to 254 rows or labels, a band up to 126 beyond."""
+    if not _is_torch_cuda(log_probs):
+        raise TypeError("ctc_loss takes a torch ROCm tensor")
+    if log_probs.ndim != 3:
+        raise TypeError("expected a tensor of rank 3")
+    if getattr(labels, "ndim", 2) != 2:
+        raise ValueError("labels must have shape (n_reads, Lmax): one labelling per read")
+    return _ctc_loss_function()(log_probs, labels, label_lengths, lengths, bool(collapse_repeats), paths, band)
 
 
 def _crf_sequence_labels(sequence, alpha, what):

@@ -1926,7 +1926,7 @@ struct LatticeCall {
     const fcd_posterior *post = nullptr;
     bool edit = false;
     const fcd_edits *edits = nullptr;
-    bool occupancy = false;  // (CRF)
+    bool occupancy = false;
     const fcd_occupancy *occ = nullptr;
 };
 
@@ -1940,7 +1940,8 @@ int lattice_check(fcd_handle *h, const LatticeCall &c) {
     if (c.align && !c.out) return fail(h, FCD_E_INVALID, "null alignment");
     if (c.posterior && !c.post) return fail(h, FCD_E_INVALID, "null posterior");
     if (c.edit && !c.edits) return fail(h, FCD_E_INVALID, c.crf ? "crf_edits: null output" : "ctc_edits: null output");
-    if (c.occupancy && !c.occ) return fail(h, FCD_E_INVALID, "crf_occupancy: null output");
+    const std::string occ_who = c.crf ? "crf_occupancy" : "ctc_occupancy";
+    if (c.occupancy && !c.occ) return fail(h, FCD_E_INVALID, (occ_who + ": null output").c_str());
     const fcd_batch *in = c.in;
     const fcd_labellings *y = c.y;
     int rc = check_batch(h, in, c.crf);
@@ -1959,7 +1960,7 @@ int lattice_check(fcd_handle *h, const LatticeCall &c) {
     if (in->n_reads > 0 && (!y->labels || !y->len ||
                             !(c.occupancy ? (const void *)c.occ->occ : c.edit ? (const void *)c.edits->deletion : c.posterior ? (const void *)c.post->post
                               : c.align ? (const void *)c.out->start : (const void *)c.logp)))
-        return fail(h, FCD_E_INVALID, c.occupancy ? "crf_occupancy: null labels/len/occ" : c.edit ? (c.crf ? "crf_edits: null labels/len/deletion" : "ctc_edits: null labels/len/deletion") : c.posterior ? "null labels/len/post"
+        return fail(h, FCD_E_INVALID, c.occupancy ? (c.crf ? "crf_occupancy: null labels/len/occ" : "ctc_occupancy: null labels/len/occ") : c.edit ? (c.crf ? "crf_edits: null labels/len/deletion" : "ctc_edits: null labels/len/deletion") : c.posterior ? "null labels/len/post"
                                       : c.align ? "null labels/len/start" : "null labels/len/logp");
     if (c.edit && in->n_reads > 0 && !c.edits->insertion) return fail(h, FCD_E_INVALID, c.crf ? "crf_edits: null insertion" : "ctc_edits: null insertion");
     if (in->n_reads * y->n_hyp >= (1ll << 31)) return fail(h, FCD_E_UNSUPPORTED, "more than 2^31 labellings in one call");
@@ -1976,16 +1977,19 @@ int lattice_check(fcd_handle *h, const LatticeCall &c) {
                                                      : "ctc_score: the exact lattice does not fit the 160 KiB of LDS: use a band");
     }
     if (c.align && in->n_reads > 0 && !c.out->count) return fail(h, FCD_E_INVALID, "null count");
-    if (c.occupancy) {
+    if (c.occupancy) {  // (a CTC batch has S = 1: its rows are N floats)
         if (c.occ->stride_row < 0 || c.occ->stride_t < in->S * in->N)
-            return fail(h, FCD_E_INVALID, "crf_occupancy: stride_t must hold a dense (S, N) row, stride_row must not be negative");
-        if (c.occ->accumulate != 0 && c.occ->accumulate != 1) return fail(h, FCD_E_INVALID, "crf_occupancy: accumulate must be 0 or 1");
+            return fail(h, FCD_E_INVALID, (occ_who + (c.crf ? ": stride_t must hold a dense (S, N) row, stride_row must not be negative"
+                                                            : ": stride_t must hold a dense row of N, stride_row must not be negative")).c_str());
+        if (c.occ->accumulate != 0 && c.occ->accumulate != 1) return fail(h, FCD_E_INVALID, (occ_who + ": accumulate must be 0 or 1").c_str());
         {  // every labelling's block to itself: whole blocks apart (read-major), or rows apart with the blocks interleaved (time-major)
             const int64_t rows = in->n_reads * y->n_hyp, SN = in->S * in->N, sr = c.occ->stride_row, st = c.occ->stride_t;
             const bool apart = sr >= (in->T - 1) * st + SN, interleaved = sr >= SN && st >= (rows - 1) * sr + SN;
             if (rows > 1 && in->T > 0 && !apart && !interleaved)
-                return fail(h, FCD_E_INVALID, "crf_occupancy: the labellings' blocks overlap (stride_row, stride_t)");
+                return fail(h, FCD_E_INVALID, (occ_who + ": the labellings' blocks overlap (stride_row, stride_t)").c_str());
         }
+    }
+    if (c.occupancy && c.crf) {
         switch (crf_occupancy_unsupported(in->T, in->S, in->N, y->stride)) {
         case 2: return fail(h, FCD_E_UNSUPPORTED, "crf_occupancy: more than 8 labels besides the blank");
         case 6: return fail(h, FCD_E_UNSUPPORTED, "crf_occupancy: the labelling and the S * N accumulation row do not fit the 160 KiB "
@@ -2006,8 +2010,8 @@ int lattice_check(fcd_handle *h, const LatticeCall &c) {
                                                    "(S = (N - 1)^m with m <= 6 and m (N - 1) <= 24, or m <= 4 at N = 3)").c_str());
         default: break;
         }
-    } else if (c.edit || c.posterior) {  // (one set of limits: both walk ctc_posterior.hip's register-resident window)
-        const std::string who = c.edit ? "ctc_edits" : "ctc_posterior";
+    } else if (c.edit || c.posterior || c.occupancy) {  // (one set of limits: all walk ctc_posterior.hip's register-resident window)
+        const std::string who = c.occupancy ? occ_who : c.edit ? "ctc_edits" : "ctc_posterior";
         switch (ctc_posterior_unsupported(in->T, y->stride, c.band, in->N)) {
         case 1: return fail(h, FCD_E_UNSUPPORTED, (who + (c.band > 0 ? ": the band's window exceeds 510 states: use a narrower band"
                                                                      : ": the exact lattice exceeds 510 states: use a band")).c_str());
@@ -2153,12 +2157,15 @@ int lattice_occupancy(fcd_handle *h, const LatticeCall &c) {
     const fcd_labellings *y = c.y;
     const fcd_occupancy *out = c.occ;
     const int64_t bnd = std::min<int64_t>(c.band, 1ll << 28);
+    // (the CTC kernels size their rows by the band as given, the CRF kernels by the band the launch gets)
+    const size_t row_bytes = c.crf ? crf_occupancy_row_bytes(in->T, y->stride, bnd) : ctc_posterior_row_bytes(in->T, y->stride, c.band);
     return lattice_grouped(
-        h, c, crf_occupancy_row_bytes(in->T, y->stride, bnd), std::min<int64_t>(4ll << 30, workspace_budget(h)), out->logp,
+        h, c, row_bytes, std::min<int64_t>(4ll << 30, workspace_budget(h)), out->logp,
         [&](CallScope &sc) { sc.add(out->occ, occupancy_span(in, y, out) * 4); },
         [&](const BatchDesc &d, const ScoreDesc &yd, int64_t r0, int64_t row0, double *logp, unsigned char *alpha, hipStream_t stream) {
             const OccupancyDesc od{out->occ + row0 * out->stride_row, out->stride_row, out->stride_t, out->scale, out->accumulate};
-            return launch_crf_occupancy(d, yd, c.init + r0 * c.init_stride, c.n_init, c.init_stride, bnd, od, logp, alpha, stream);
+            return c.crf ? launch_crf_occupancy(d, yd, c.init + r0 * c.init_stride, c.n_init, c.init_stride, bnd, od, logp, alpha, stream)
+                         : launch_ctc_occupancy(d, yd, c.collapse, bnd, od, logp, alpha, stream);
         });
 }
 
@@ -2370,6 +2377,26 @@ int fcd_crf_occupancy_host(fcd_handle *h, const fcd_batch *in, const float *init
     if (!h) return FCD_E_INVALID;
     std::lock_guard<std::recursive_mutex> whole_call(h->mu);  // staging .. copy-back, see run_host
     LatticeCall c{true, false, in, y, band, 0, init, n_init, init_stride, nullptr, nullptr};
+    c.occupancy = true;
+    c.occ = out;
+    return lattice_host(h, c);
+}
+
+int fcd_ctc_occupancy_dev(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int collapse_repeats, int64_t band,
+                          const fcd_occupancy *out) {
+    if (!h) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> g(h->mu);
+    LatticeCall c{false, false, in, y, band, collapse_repeats != 0, nullptr, 0, 0, nullptr, nullptr};
+    c.occupancy = true;
+    c.occ = out;
+    return lattice_dev(h, c);
+}
+
+int fcd_ctc_occupancy_host(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int collapse_repeats, int64_t band,
+                           const fcd_occupancy *out) {
+    if (!h) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> whole_call(h->mu);  // staging .. copy-back, see run_host
+    LatticeCall c{false, false, in, y, band, collapse_repeats != 0, nullptr, 0, 0, nullptr, nullptr};
     c.occupancy = true;
     c.occ = out;
     return lattice_host(h, c);

@@ -496,20 +496,7 @@ __device__ __forceinline__ void crfp_back_walk(const CrfPostParams &q, unsigned 
 // roundings, so a row whose computed terms are further than kOccLost(T_r) = 2 (6 T_r + 64 K + 2 K + 8) 2^-24 from 1 has lost
 // cells (or P has, in the forward walk): the walk then gives up -- logp = NaN and NaN in every row t < T_r of the block --
 // rather than hand out occupancies that do not add up.
-// the sum of a non-negative value over the wavefront, the same in every lane (wave_imax's network with + for max)
-__device__ __forceinline__ float wave_fsum(float x) {
-    float t = x;
-#define FCD_DPP_FSUM(CTRL, RM) t = t + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(t), CTRL, RM, 0xf, false));
-    FCD_DPP_FSUM(0x111, 0xf)  // row_shr:1
-    FCD_DPP_FSUM(0x112, 0xf)  // row_shr:2
-    FCD_DPP_FSUM(0x114, 0xf)  // row_shr:4
-    FCD_DPP_FSUM(0x118, 0xf)  // row_shr:8   -> lane 15 of every row holds the row's sum
-    FCD_DPP_FSUM(0x142, 0xa)  // row_bcast:15 into rows 1 and 3
-    FCD_DPP_FSUM(0x143, 0xc)  // row_bcast:31 into rows 2 and 3 -> lane 63 holds the sum
-#undef FCD_DPP_FSUM
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t), 63));
-}
-
+// (wave_fsum, the sum of a non-negative value over the wavefront: device_utils.h)
 template <int K>
 __device__ __forceinline__ void crfp_occ_walk(const CrfPostParams &q, unsigned char *smem) {
     constexpr int C = 64 * K;

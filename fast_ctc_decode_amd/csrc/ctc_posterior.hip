@@ -38,6 +38,10 @@
 // the number of slots, is what it was.  No alignment of y passes through such a cell, so a NaN or an infinity there must not
 // reach y's own values: where nothing enters a cell outside the unrelaxed cuts (the sum is exactly 0) the posterior is not
 // multiplied in (core_states); likewise u where nothing leaves the gap, and a term where nothing enters it.
+//
+// fcd_ctc_occupancy_* (the label occupancies of the labelling's own alignments, row by row) is post_fwd_kernel<K> at slack 0
+// and a second walk, ctc_occ_walk below, compiled into post_back_kernel<K, 8> only and chosen by the wave-uniform
+// PostParams::walk: b alone, no w, no accumulator that lives across rows.
 #include <math.h>
 
 #include <algorithm>
@@ -57,7 +61,14 @@ struct PostParams {
     float *del, *ins;     // [.. * stride], [.. * (stride + 1) * (N - 1)]                     (fcd_ctc_edits_*)
     float *alpha;         // the stored forward rows, alpha_words per labelling of this launch
     int64_t alpha_words;
+    int walk;             // what post_back_kernel<K, 8> walks (wave-uniform): kWalkSub, kWalkOcc
+    // (fcd_ctc_occupancy_*) a (T, N) block per labelling of this launch, at row * occ_stride_row + t * occ_stride_t
+    float *occ;
+    int64_t occ_stride_row, occ_stride_t;
+    float occ_scale;
+    int occ_accumulate;
 };
+constexpr int kWalkSub = 0, kWalkOcc = 1;
 
 // bit r: the lane's state r (the one >= lo) lies inside window_k's unrelaxed cuts -- a cell an alignment of y can pass
 // through.  p.slack = 0: every live state.
@@ -251,9 +262,145 @@ __device__ __forceinline__ int term_shift(int64_t x_t, int64_t xmax) { return (i
 // u * 2^(e + sh): a cell at the row's scale
 __device__ __forceinline__ float at_row_scale(float u, int e, int sh) { return ldexpf(u, min(max(e + sh, -512), 512)); }
 
+// ---- the label occupancies of the labelling's own alignments (fcd_ctc_occupancy_*; include/fcd.h) ----
+// The second walk of post_back_kernel<K, 8>.  Row t = T_r - 1 .. 0, with b_{t+1} in the registers ("row T_r": all mass on
+// state 2L) and alpha_t in the stored rows -- the row of the SAME index, so the window both are read by is row t's own and
+// k(t - 1) is never asked for:
+//   beta_t[s]  = b_{t+1}[s] [blank, or collapse] + b_{t+1}[s+1] + [allowed] b_{t+1}[s+2]     what the backward step sums
+//   gamma_t[s] = alpha_t[s] * beta_t[s] / P                                                  before p[t][z[s]] enters
+// one product, the exact power of two 2^(Ea(t) + Eb(t+1) - floor(log2 P)) and the division by P's mantissa -- two roundings;
+// then b_t = beta_t * p[t][z[s]] in place at the row's own scale, as the substitution walk forms it.  A slot's parity is its
+// state's (K is even): the even slots are the blank.  occ[t][c] is the sum of gamma_t over the states of label c: each lane
+// adds up its own slots (at most K / 2 - 1 sums), wave_fsum the lanes (6 deep), once per label of the alphabet -- the same
+// order in every call, so the same bits.  Every lane then holds the whole row; lane c stores cell c.  No LDS, no atomics.
+// Where nothing leaves a cell (a dead end beside a band's jump: beta is exactly 0) neither the posterior nor alpha is
+// multiplied in: no alignment of y reads them.
+// The lattice the rows cannot hold.  alpha and b keep one exponent per row; where a long read does not support its
+// labelling their maxima sit at opposite ends of the window and the cells that carry the probability fall out of range.
+// The row's occupancies sum to 1 exactly; each is within (6 T_r + K / 2 + 11) 2^-24 of its value and the sum over the
+// labels adds N - 1 <= 8 roundings, so a row whose sum is further than kOccLost(T_r) = 2 (6 T_r + K / 2 + 19) 2^-24 from 1
+// has lost cells: the walk gives the labelling up -- logp = NaN and NaN in every row t < T_r of its block.
+template <int K>
+__device__ __forceinline__ void ctc_occ_walk(const PostParams &q, unsigned char *smem) {
+    constexpr int C = 64 * K, NL = 9;  // (NL: the blank and the 8 labels)
+    const ScoreParams &p = q.s;
+    const Lds lds = carve(smem, p.lab_cap);
+    Row rw;
+    if (!prologue(p, lds, &rw)) return;  // (the forward launch wrote this row's logp already; the same value again)
+    const double lp = p.logp[blockIdx.x];
+    if (lp - lp != 0.0) return;  // P = 0, or a NaN on the way: nothing of the block is written
+    const int lane = threadIdx.x, N = rw.N, L = rw.L;
+    const float *am = q.alpha + (int64_t)blockIdx.x * q.alpha_words;
+    const int *ae = reinterpret_cast<const int *>(am + (int64_t)p.in.T * C);
+    float *out = q.occ + (int64_t)blockIdx.x * q.occ_stride_row;
+    float b[K];
+#pragma unroll
+    for (int r = 0; r < K; ++r) b[r] = 0.0f;
+    int64_t eb = 0;
+    const int64_t xp = (int64_t)floor(lp * 1.44269504088896340735992468100189214);  // floor(log2 P(y | x))
+    const float pman = (float)exp(lp - (double)xp * kLn2);                          // P / 2^xp, in [1, 2]
+    const float lost = 2.0f * (6.0f * (float)rw.Tr + (float)(K / 2 + 19)) * 5.9604644775390625e-8f;  // kOccLost(T_r)
+    bool first = true;
+    int lo = 0, hi = 0, lo_n = 0;
+    for (int t0 = last_tile(rw); t0 >= 0; t0 -= rw.rows_per_tile) {
+        const int rc = min(rw.rows_per_tile, rw.Tr - t0);
+        fill_tile(p, lds, rw, t0, rc);
+        for (int i = rc - 1; i >= 0; --i) {
+            const int t = t0 + i;
+            window(p, lds, rw, t, i, &lo, &hi);
+            if (first) {
+                start_beyond_last_row<K>(b, lo, L);
+                first = false;
+                lo_n = lo;
+            }
+            const float *arow = am + (int64_t)t * C + lane * K;  // alpha_t, by slot (a slot outside the window is masked below)
+            float av[K];
+#pragma unroll
+            for (int r = 0; r < K; ++r) av[r] = arow[r];
+            // the exponent of this row's terms: alpha of row t times b of row t + 1, over 2^floor(log2 P)
+            const int dt = (int)min(max((int64_t)ae[t] + eb - xp, (int64_t)-512), (int64_t)512);
+            const float n1 = from_next_lane(b[0]), n2 = from_next_lane(b[1]);
+            const float pm0 = lds.pm[i * N];
+            const int pe0 = lds.pe[i * N];
+            float u[K], g[K];
+            int ex[K], yk[K / 2];
+            uint32_t live = 0;
+            int emax = kNoExp;
+#pragma unroll
+            for (int r = 0; r < K; ++r) {
+                const int s = slot_state<K>(lane, r, lo);
+                const bool in = s <= hi;
+                live |= (in ? 1u : 0u) << r;
+                const Above y = b_above<K>(b, r, s, lo_n, n1, n2);
+                float sum, pm;
+                if (r & 1) {
+                    const int k = in ? (s >> 1) : 0;  // (a dead slot reads valid addresses and is masked below)
+                    const int info = lds.lab[k], inext = lds.lab[min(k + 1, max(L - 1, 0))];
+                    yk[r / 2] = in ? (info & 0xFF) : 0;
+                    sum = label_state_sum(p.collapse, y, k, L, inext);
+                    pm = lds.pm[i * N + yk[r / 2]];
+                    ex[r] = lds.pe[i * N + yk[r / 2]];
+                } else {
+                    sum = y.y0 + y.y1;
+                    pm = pm0;
+                    ex[r] = pe0;
+                }
+                const bool leaves = in && sum != 0.0f;
+                u[r] = leaves ? sum * pm : 0.0f;
+                g[r] = leaves ? ldexpf(av[r] * sum, dt) / pman : 0.0f;
+                const int e = finite_exp(u[r]);
+                emax = max(emax, e != kNoExp ? e + ex[r] : kNoExp);
+            }
+            int64_t unused = 0;
+            const int sh = back_row_shift(emax, eb, unused);
+#pragma unroll
+            for (int r = 0; r < K; ++r) b[r] = ((live >> r) & 1) ? at_row_scale(u[r], ex[r], sh) : 0.0f;
+            // ---- the row's N occupancies, the same in every lane ----
+            float v[NL];
+            {
+                float x = g[0];
+#pragma unroll
+                for (int r = 2; r < K; r += 2) x += g[r];
+                v[0] = wave_fsum(x);
+            }
+            float mass = v[0];
+#pragma unroll
+            for (int c = 1; c < NL; ++c) {
+                v[c] = 0.0f;
+                if (c < N) {  // (wave-uniform)
+                    float x = yk[0] == c ? g[1] : 0.0f;
+#pragma unroll
+                    for (int r = 3; r < K; r += 2) x += yk[r / 2] == c ? g[r] : 0.0f;
+                    v[c] = wave_fsum(x);
+                    mass += v[c];
+                }
+            }
+            if (!(fabsf(mass - 1.0f) <= lost)) {  // (wave-uniform) the rows cannot hold this lattice
+                __syncthreads();  // the rows stored so far are behind the NaN that replaces them
+                for (int tt = 0; tt < rw.Tr; ++tt)
+                    if (lane < N) out[(int64_t)tt * q.occ_stride_t + lane] = NAN;
+                if (lane == 0) p.logp[blockIdx.x] = (double)NAN;
+                return;
+            }
+            float mine = v[0];
+#pragma unroll
+            for (int c = 1; c < NL; ++c) mine = lane == c ? v[c] : mine;
+            if (lane < N) {
+                float *cell = out + (int64_t)t * q.occ_stride_t + lane;
+                if (!q.occ_accumulate) *cell = mine == 0.0f ? 0.0f : q.occ_scale * mine;
+                else if (mine != 0.0f) *cell = *cell + q.occ_scale * mine;  // (a cell of occupancy 0 is not read)
+            }
+            lo_n = lo;
+        }
+    }
+}
+
 template <int K, int NC>
 __global__ __launch_bounds__(64) void post_back_kernel(PostParams q) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    if constexpr (NC == 8) {  // (the occupancy walk rides in these four only)
+        if (q.walk == kWalkOcc) return ctc_occ_walk<K>(q, smem);
+    }
     constexpr int C = 64 * K, H = K / 2;
     const ScoreParams &p = q.s;
     const Lds lds = carve(smem, p.lab_cap);
@@ -612,6 +759,11 @@ PostParams post_params(const BatchDesc &in, const ScoreDesc &y, int collapse, in
     q.s.cap = 0;
     q.s.lab_cap = (int)std::max<int64_t>(std::min(in.T, y.stride), 1);
     q.post = q.del = q.ins = nullptr;
+    q.walk = kWalkSub;
+    q.occ = nullptr;
+    q.occ_stride_row = q.occ_stride_t = 0;
+    q.occ_scale = 0.0f;
+    q.occ_accumulate = 0;
     q.alpha = reinterpret_cast<float *>(alpha);
     q.alpha_words = (int64_t)(ctc_posterior_row_bytes(in.T, y.stride, band) / 4);
     return q;
@@ -628,6 +780,13 @@ void launch_pair(const PostParams &q, dim3 grid, size_t lds, hipStream_t stream)
         if (q.s.in.N - 1 <= 4) hipLaunchKernelGGL((post_back_kernel<K, 4>), grid, dim3(64), lds, stream, q);
         else hipLaunchKernelGGL((post_back_kernel<K, 8>), grid, dim3(64), lds, stream, q);
     }
+}
+
+// fcd_ctc_occupancy_*: the forward launch, then the occupancy walk in post_back_kernel<K, 8> whatever the alphabet
+template <int K>
+void launch_occupancy_pair(const PostParams &q, dim3 grid, size_t lds, hipStream_t stream) {
+    hipLaunchKernelGGL(post_fwd_kernel<K>, grid, dim3(64), lds, stream, q);
+    hipLaunchKernelGGL((post_back_kernel<K, 8>), grid, dim3(64), lds, stream, q);
 }
 
 template <bool EDIT>
@@ -661,6 +820,28 @@ hipError_t launch_ctc_edits(const BatchDesc &in, const ScoreDesc &y, int collaps
     q.del = deletion;
     q.ins = insertion;
     return launch_walks<true>(q, band, stream);
+}
+
+hipError_t launch_ctc_occupancy(const BatchDesc &in, const ScoreDesc &y, int collapse, int64_t band, const OccupancyDesc &out,
+                                double *logp, unsigned char *alpha, hipStream_t stream) {
+    if (in.n_reads * y.n_hyp <= 0) return hipSuccess;
+    PostParams q = post_params(in, y, collapse, band, logp, alpha);
+    q.walk = kWalkOcc;
+    q.occ = out.occ;
+    q.occ_stride_row = out.stride_row;
+    q.occ_stride_t = out.stride_t;
+    q.occ_scale = out.scale;
+    q.occ_accumulate = out.accumulate;
+    const dim3 grid((unsigned)(in.n_reads * y.n_hyp));
+    const size_t lds = lds_bytes(q.s.lab_cap, 0);
+    switch (reg_states_per_lane(in.T, y.stride, band)) {
+    case 2: launch_occupancy_pair<2>(q, grid, lds, stream); break;
+    case 4: launch_occupancy_pair<4>(q, grid, lds, stream); break;
+    case 6: launch_occupancy_pair<6>(q, grid, lds, stream); break;
+    case 8: launch_occupancy_pair<8>(q, grid, lds, stream); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
 }
 
 }  // namespace fcd

@@ -389,6 +389,20 @@ __device__ __forceinline__ int wave_imax(int x) {
     return __builtin_amdgcn_readlane(t, 63);
 }
 
+// the sum of a non-negative value over the wavefront, the same in every lane (wave_imax's network with + for max)
+__device__ __forceinline__ float wave_fsum(float x) {
+    float t = x;
+#define FCD_DPP_FSUM(CTRL, RM) t = t + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(t), CTRL, RM, 0xf, false));
+    FCD_DPP_FSUM(0x111, 0xf)  // row_shr:1
+    FCD_DPP_FSUM(0x112, 0xf)  // row_shr:2
+    FCD_DPP_FSUM(0x114, 0xf)  // row_shr:4
+    FCD_DPP_FSUM(0x118, 0xf)  // row_shr:8   -> lane 15 of every row holds the row's sum
+    FCD_DPP_FSUM(0x142, 0xa)  // row_bcast:15 into rows 1 and 3
+    FCD_DPP_FSUM(0x143, 0xc)  // row_bcast:31 into rows 2 and 3 -> lane 63 holds the sum
+#undef FCD_DPP_FSUM
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t), 63));
+}
+
 __device__ __forceinline__ void crf_split(float v, float *m, int *e) {
     int ex = 0;
     float mm = v;

@@ -343,6 +343,11 @@ int crf_occupancy_unsupported(int64_t T, int64_t S, int64_t N, int64_t stride);
 size_t crf_occupancy_row_bytes(int64_t T, int64_t stride, int64_t band);
 hipError_t launch_crf_occupancy(const BatchDesc &in, const ScoreDesc &y, const float *init, int64_t n_init, int64_t init_stride,
                                 int64_t band, const OccupancyDesc &out, double *logp, unsigned char *alpha, hipStream_t stream);
+// CTC label occupancies of the same labellings (ctc_posterior.hip; fcd_ctc_occupancy_* in include/fcd.h): post_fwd_kernel<K>
+// and a second walk inside post_back_kernel<K, 8>.  The limits and the workspace are launch_ctc_posterior's
+// (ctc_posterior_unsupported, ctc_posterior_row_bytes); out.occ: the first labelling's (T, N) block; logp must not be null.
+hipError_t launch_ctc_occupancy(const BatchDesc &in, const ScoreDesc &y, int collapse, int64_t band, const OccupancyDesc &out,
+                                double *logp, unsigned char *alpha, hipStream_t stream);
 
 hipError_t launch_logspace_probe(const float *a, const float *b, float *out_add, float *out_ln,
                                  int64_t n, int mode, hipStream_t stream);

@@ -749,6 +749,56 @@ int fcd_crf_occupancy_dev(fcd_handle *h, const fcd_batch *in, const float *init,
 int fcd_crf_occupancy_host(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init, int64_t init_stride,
                            const fcd_labellings *y, int64_t band, const fcd_occupancy *out);
 
+/* ---- CTC label occupancies of given labellings (csrc/ctc_posterior.hip) ----
+ * NOT a reference function.  The soft version of fcd_ctc_align_*'s spans and the gradient of the CTC loss: the probability,
+ * over the alignments of labelling y, that row t emits symbol c.
+ * Everything is as fcd_ctc_posterior_* defines it: batch (n_reads, T, N) with in->S = 1, y of L labels, z its 2L + 1
+ * extended states, collapse_repeats, under band = W the window from y->path (the labelling's own, slack 0).  alpha is
+ * fcd_ctc_score_*'s forward value, b fcd_ctc_posterior_*'s backward value, "row T_r" holding all of b on state 2L:
+ *   beta_t[s]  = b_{t+1}[s] (a blank, or collapse_repeats) + b_{t+1}[s+1] + b_{t+1}[s+2] (where the step is allowed)
+ *   b_t[s]     = beta_t[s] * p[t][z[s]]
+ *   gamma_t[s] = alpha_t[s] * beta_t[s] / P(y | x)                       for s live at row t (alpha_t: the row of the same index)
+ *   occ[t][c]  = sum over the s live at row t with z[s] = c of gamma_t[s]        c = 0 .. N-1, t < T_r
+ * Every row of occ sums to 1.  d ln P / d ln p[t][c] = occ[t][c]; at the logits of a softmax d(-ln P)/dx = p - occ.
+ * Output: fcd_occupancy as above with N for S * N.  Labelling row = r * n_hyp + i has its own (T, N) block of f32, row t at
+ * occ + row * stride_row + t * stride_t (64-bit offsets), stride_t >= N; with n_hyp = 1 a buffer of the batch's own shape,
+ * time-major included.  accumulate = 0: block[t][c] = scale * occ (a cell of occupancy 0 holds +0);  accumulate = 1:
+ * block[t][c] += scale * occ (one f32 product, one f32 sum), and a cell whose occupancy is 0 is not read.  logp (nullable):
+ * fcd_ctc_score_*'s value, bit for bit (NaN for a labelling the walk gives up, below).
+ * Rows without a value: logp follows fcd_ctc_score_*'s order and values.  Whenever P(y | x) is not a positive finite number
+ * nothing of the labelling's block is written; rows t >= T_r and the blocks of i >= n_valid[r] are never touched.  L = 0 is a
+ * labelling like any other: occupancy 1 on the blank in every row.
+ * Arithmetic: pass 1 is fcd_ctc_posterior_*'s forward launch with every row stored; pass 2 walks the rows backwards with b
+ * alone (f32, one integer exponent per row, exact power-of-two scales).  A term gamma is one product, the exact power of two
+ * 2^(Ea(t) + Eb(t+1) - floor(log2 P)) and the division by P's mantissa; no fused multiply-add; every term non-negative.  A
+ * label's sum is taken in a fixed order -- a lane's own states, then the lanes of the wavefront, 6 sums deep -- so two calls
+ * on the same input give the same bits.  Error bound, by roundings along the longest chain: alpha_t 3 (t + 1), beta_t
+ * 3 (T_r - 1 - t) + 2, the term and the division 2, P 3 T_r + 1 and its mantissa 1, a label's sum K / 2 - 1 + 6 with
+ * K = 2, 4, 6, 8 the states a lane holds (windows up to 126, 254, 382, 510 states):
+ *   bound(T_r) = (6 T_r + K / 2 + 11) 2^-24,   |occ - exact| <= bound(T_r) * occ;
+ *   accumulate = 1 adds 2^-24 |block| for the final sum.
+ * What the rows can hold.  alpha and b keep one f32 exponent per row, and a cell below 2^-160 of its row's maximum may be
+ * dropped, as in fcd_ctc_posterior_*.  Where the read supports its labelling the two rows' maxima meet on the alignments
+ * that carry the probability.  Where it does not -- near-uniform posteriors against a labelling with many rows per label --
+ * the maxima sit at opposite ends of the window and cells that carry probability fall out of range.  The walk sums every
+ * row (the N label sums, N - 1 <= 8 more roundings); the sum must be 1 within
+ *   lost(T_r) = 2 (6 T_r + K / 2 + 19) 2^-24
+ * and a labelling with a row that is not is given up: logp = NaN (not fcd_ctc_score_*'s value) and NaN in every row
+ * t < T_r of its block, accumulate = 1 included.  So for every labelling with a finite logp every row of occ sums to 1
+ * within lost(T_r) and |occ - exact| <= bound(T_r) * occ + lost(T_r).  The measured range is in INTEGRATION.md section 2n.
+ * FCD_E_INVALID: fcd_ctc_posterior_*'s cases; a null out or out->occ; stride_t < N; stride_row < 0; accumulate not 0 or 1;
+ * with more than one labelling, blocks that overlap: either stride_row >= (T - 1) stride_t + N (whole blocks apart) or
+ * stride_row >= N and stride_t >= (n_reads n_hyp - 1) stride_row + N (time-major: the blocks interleaved row by row).
+ * Limits (FCD_E_UNSUPPORTED; the message names ctc_occupancy): fcd_ctc_posterior_*'s -- windows up to 510 states (use a
+ * band), N - 1 <= 8, min(T, stride) <= 28480.
+ * _dev: device pointers, enqueue-only on the handle's stream, behind every overlapping call in flight, as
+ * fcd_ctc_posterior_*; the stored forward rows live in the handle's workspace and the labellings are launched in groups of
+ * whole reads that fit it.  _host: host pointers; stages (the block travels both ways), runs and copies back in one piece. */
+int fcd_ctc_occupancy_dev(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int collapse_repeats, int64_t band,
+                          const fcd_occupancy *out);
+int fcd_ctc_occupancy_host(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int collapse_repeats, int64_t band,
+                           const fcd_occupancy *out);
+
 /* ---- search::crf_greedy_search (src/search.rs:385-423) ---- */
 int fcd_crf_greedy_search_dev(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init,
                               int64_t init_stride, const fcd_result *out);

@@ -1,0 +1,180 @@
+"""CTC label occupancies (include/fcd.h, fcd_ctc_occupancy_*) next to ctc_posterior, which walks the same lattice; ctc_loss
+next to torch.nn.functional.ctc_loss on the same device; ctc_posterior at N = 9 alone (the post_back_kernel<K, 8>
+instantiations that carry the occupancy walk -- to be run on two checkouts); and which uniform-posterior shapes the walk
+holds or gives up.  From one run each, on one GPU.
+
+    python tools/probe_ctc_occupancy.py [--what occupancy,loss,posterior9,boundary] [--passes 5] [--reads 4096]
+                                        [--package-root DIR] [--out FILE]
+
+occupancy: BASELINE config 2's shape (4096 x 4000 x 5, beam 5, threshold 0.1), every read's result at band 16 and band 64,
+    and 4096 reads of 250 rows with 120 random labels, exact: ctc_posterior and ctc_occupancy (into a buffer held across
+    the calls) and their ratio.
+loss: 256 reads x T in {250, 1000} x N = 5, random logits, T // 2 - 5 random labels: ctc_loss forward + backward -- exact
+    at T = 250, band 64 around ctc_align's path at T = 1000 (the banded sum and its gradient) -- next to
+    torch.nn.functional.ctc_loss forward + backward on the same device (always exact), both from the logits through
+    log_softmax; the largest difference between the two gradients at the logits, and of each to the same loss in float64
+    on the CPU.
+posterior9: ctc_posterior at 4096 x 1000 x 9, band 16 and band 64.  --package-root times another checkout of the project.
+boundary: N = 5, uniform random posteriors, random labels, exact lattice: per (T, L) whether logp is finite (held) or NaN.
+Milliseconds: device events around one device-resident call; after one warm-up call, --passes such calls, the median as
+*_ms and all of them as *_all.  A GPU is required; there is no fall-back.  One JSON line."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--what", default="occupancy,loss,posterior9,boundary")
+    ap.add_argument("--passes", type=int, default=5)
+    ap.add_argument("--reads", type=int, default=4096)
+    ap.add_argument("--package-root", default=ROOT)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    sys.path.insert(0, os.path.abspath(args.package_root))
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import numpy as np
+    import torch
+
+    import fast_ctc_decode_amd as fcd
+    from test_gpu_parity import gen_batch
+
+    if not torch.cuda.is_available():
+        raise SystemExit("probe_ctc_occupancy needs the GPU")
+    what = set(args.what.split(","))
+    row = {"what": sorted(what), "passes": args.passes, "package": os.path.dirname(os.path.abspath(fcd.__file__))}
+
+    def timed(fn):
+        fn()
+        torch.cuda.synchronize()
+        ms = []
+        for _ in range(args.passes):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ms.append(round(e0.elapsed_time(e1), 3))
+        return ms
+
+    def put(name, fn):
+        ms = timed(fn)
+        row[name + "_ms"], row[name + "_all"] = statistics.median(ms), ms
+
+    if "occupancy" in what:
+        T, B = 4000, args.reads
+        x = torch.from_numpy(gen_batch(2024, B, T, 5)).cuda()
+        r = fcd.beam_search_batch_raw(x, 5, 0.1)
+        row["config2_reads"], row["config2_mean_labels"] = B, float(r.out_len.float().mean())
+        out = torch.zeros((B, 1, T, 5), dtype=torch.float32, device="cuda")
+        for band in (16, 64):
+            key = "config2_band%d" % band
+            put(key + "_posterior", lambda: r.ctc_posterior(x, band=band))
+            put(key + "_occupancy", lambda: fcd.ctc_occupancy_batch_raw(x, r.labels, r.out_len, True, None, r.path, band, out=out))
+            row[key + "_occupancy_over_posterior"] = round(row[key + "_occupancy_ms"] / row[key + "_posterior_ms"], 3)
+            row[key + "_given_up"] = int(torch.isnan(fcd.ctc_occupancy_batch_raw(x, r.labels, r.out_len, True, None, r.path, band,
+                                                                                 out=out).logp).sum())
+        del x, r, out
+        torch.cuda.empty_cache()
+        T, L = 250, 120
+        x = torch.from_numpy(gen_batch(7, B, T, 5)).cuda()
+        g = torch.Generator(device="cuda").manual_seed(1)
+        labels = torch.randint(1, 5, (B, L), generator=g, device="cuda").to(torch.uint8)
+        lens = torch.full((B,), L, dtype=torch.int32, device="cuda")
+        out = torch.zeros((B, 1, T, 5), dtype=torch.float32, device="cuda")
+        put("exact_t250_l120_posterior", lambda: fcd.ctc_posterior_batch_raw(x, labels, lens))
+        put("exact_t250_l120_occupancy", lambda: fcd.ctc_occupancy_batch_raw(x, labels, lens, out=out))
+        row["exact_t250_l120_occupancy_over_posterior"] = round(row["exact_t250_l120_occupancy_ms"] / row["exact_t250_l120_posterior_ms"], 3)
+        row["exact_t250_l120_given_up"] = int(torch.isnan(fcd.ctc_occupancy_batch_raw(x, labels, lens, out=out).logp).sum())
+        del x, out
+        torch.cuda.empty_cache()
+
+    if "loss" in what:
+        B, N = 256, 5
+        for T in (250, 1000):
+            L = T // 2 - 5
+            tag = "loss_t%d" % T
+            g = torch.Generator(device="cuda").manual_seed(T)
+            logits = 2.0 * torch.randn((B, T, N), generator=g, device="cuda")
+            labels = torch.randint(1, N, (B, L), generator=g, device="cuda").to(torch.uint8)
+            lens = torch.full((B,), L, dtype=torch.int32, device="cuda")
+            lp0 = torch.log_softmax(logits, -1)
+            band, paths = 0, None
+            if T > 254:  # beyond the exact lattice's limit: band 64 around the best alignment's rows
+                band = 64
+                paths = fcd.ctc_align_batch_raw(lp0.exp(), labels, lens).start[:, 0].contiguous()
+            row[tag + "_computation"] = "exact" if band == 0 else "band %d around ctc_align's path" % band
+            row[tag + "_torch_computation"] = "exact"
+            row[tag + "_labels"] = L
+
+            def ours():
+                lg = logits.detach().requires_grad_(True)
+                fcd.ctc_loss(torch.log_softmax(lg, -1), labels, lens, None, True, paths, band).sum().backward()
+                return lg.grad
+            tl, il = torch.full((B,), L, dtype=torch.long, device="cuda"), torch.full((B,), T, dtype=torch.long, device="cuda")
+            lab64 = labels.long()
+
+            def theirs():
+                lg = logits.detach().requires_grad_(True)
+                lp = torch.log_softmax(lg, -1)
+                torch.nn.functional.ctc_loss(lp.permute(1, 0, 2), lab64, il, tl, blank=0, reduction="none").sum().backward()
+                return lg.grad
+            put(tag, ours)
+            put(tag + "_torch", theirs)
+            row[tag + "_torch_over_ours"] = round(row[tag + "_torch_ms"] / row[tag + "_ms"], 2)
+            mine = fcd.ctc_loss(lp0, labels, lens, None, True, paths, band)
+            row[tag + "_nan_losses"] = int(torch.isnan(mine).sum())
+            ref = torch.nn.functional.ctc_loss(lp0.permute(1, 0, 2), lab64, il, tl, blank=0, reduction="none")
+            row[tag + "_max_abs_loss_difference"] = float((mine - ref.double()).abs().nan_to_num(0.0).max())
+            ga, gb = ours(), theirs()
+            row[tag + "_max_abs_grad_difference"] = float((ga - gb).abs().nan_to_num(0.0).max())  # (at the logits)
+            # both against the same computation in float64 on the CPU (exact: a banded ctc_loss differs by the band's cut too)
+            lg = logits.detach().cpu().double().requires_grad_(True)
+            l64 = torch.nn.functional.ctc_loss(torch.log_softmax(lg, -1).permute(1, 0, 2), lab64.cpu(), il.cpu(), tl.cpu(), blank=0,
+                                               reduction="none")
+            l64.sum().backward()
+            g64 = lg.grad.cuda()
+            row[tag + "_max_abs_grad_vs_float64"] = float((ga.double() - g64).abs().nan_to_num(0.0).max())
+            row[tag + "_torch_max_abs_grad_vs_float64"] = float((gb.double() - g64).abs().max())
+            row[tag + "_max_abs_loss_vs_float64"] = float((mine.cpu() - l64.detach()).abs().nan_to_num(0.0).max())
+            row[tag + "_torch_max_abs_loss_vs_float64"] = float((ref.double().cpu() - l64.detach()).abs().max())
+        torch.cuda.empty_cache()
+
+    if "posterior9" in what:
+        T, B = 1000, args.reads
+        x = torch.from_numpy(gen_batch(99, B, T, 9)).cuda()
+        r = fcd.beam_search_batch_raw(x, 5, 0.1)
+        row["posterior9_reads"], row["posterior9_mean_labels"] = B, float(r.out_len.float().mean())
+        for band in (16, 64):
+            put("posterior9_band%d" % band, lambda: r.ctc_posterior(x, band=band))
+        del x, r
+        torch.cuda.empty_cache()
+
+    if "boundary" in what:
+        rng = np.random.default_rng(41)
+        table = []
+        for T, L in ((250, 20), (250, 120), (500, 50), (500, 120), (700, 50), (1000, 20), (1000, 50), (1000, 120), (1000, 250),
+                     (2000, 10), (2000, 50), (2000, 250), (4000, 5), (4000, 50), (4000, 250)):
+            x = rng.random((8, T, 5))
+            x = torch.from_numpy((x / x.sum(-1, keepdims=True)).astype(np.float32)).cuda()
+            y = torch.from_numpy(rng.integers(1, 5, (8, L)).astype(np.uint8)).cuda()
+            got = fcd.ctc_occupancy_batch_raw(x, y, torch.full((8,), L, dtype=torch.int32, device="cuda"))
+            held = int(torch.isfinite(got.logp).sum())
+            table.append({"T": T, "L": L, "held_of_8": held,
+                          "max_row_sum_error": float((got.occupancy[:, 0].sum(-1) - 1.0).abs().nan_to_num(0.0).max())})
+        row["boundary"] = table
+
+    line = json.dumps(row)
+    print(line, flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
