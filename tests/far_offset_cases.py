@@ -13,6 +13,14 @@ Every case runs the same inputs twice, COMPACT (the layout the other tests use) 
      logp / posterior / edit values as bit patterns).
 "Far" always means: read, row or labelling 1 starts beyond the boundary while read 0 starts at offset 0.
 
+What the table holds: the searches (far reads, far rows, far outputs), sessions, the duplex searches and the band estimator,
+pack / offsets / unpack, the tree arena; the ten lattice entry points -- ctc / crf x score, align, posterior, edits,
+occupancy -- with far labellings (y.stride), far reads and far rows, and the occupancy blocks far apart (stride_row) or
+interleaved with far rows (stride_t), written and accumulated, in one launch group and in one per read; the two walks over
+all labellings (crf_transition_probs, crf_marginals) with each of their strides far alone, in every code form, both score
+layouts and both output types.  ONE quantity is far per case, so that a failure names the offset that broke.  COVERED and
+EXEMPT (at the end) list every fcd_*_dev of include/fcd.h; tests/test_far_offsets_emu.py holds the header to them.
+
 Memory: Env.region() hands out the big arrays; on the GPU they are slices of ONE pool made once per module (never filled,
 never copied as a whole: put() and get() move the touched rows only), on the CPU an np.empty each, dropped by reset()."""
 import ctypes as C
@@ -287,7 +295,7 @@ class Got:
 
 def bits(a):
     a = np.ascontiguousarray(a)
-    return a.view({4: np.uint32, 8: np.uint64}[a.dtype.itemsize]) if a.dtype.kind == "f" else a
+    return a.view({2: np.uint16, 4: np.uint32, 8: np.uint64}[a.dtype.itemsize]) if a.dtype.kind == "f" else a
 
 
 def assert_same(far, compact, where, fields=("labels", "path", "qual")):
@@ -536,7 +544,12 @@ SEARCHES = {s.name: s for s in searches()}
 FAR_READS = [("f16", 2 ** 31 + 16, False), ("bf16", 2 ** 31 + 16, False), ("f32", 2 ** 30 + 16, False), ("f32", 2 ** 31 + 16, True),
              ("f16", 2 ** 31 + 17, False)]
 FAR_ROW_STRIDE = 2 ** 25 + 8  # f16 elements; T = 70 puts rows 64 .. 69 above 2^31 elements
+FAR_ROW_STRIDE_32 = 2 ** 26 + 8  # ... and above 2^32 elements, where an offset kept in 32 unsigned bits wraps (rows 32 .. above 2^31)
 TS = (70, 300)
+# the lattice families' far reads: (dtype, stride_read, B) -- FAR_READS with two reads, and three float16 reads 2^31 + 16 apart:
+# read 2 starts above 2^32 elements (a span of 8 GiB), where an offset kept in 32 unsigned bits wraps
+LATTICE_FAR_READS = [(dt, sr, 2) for dt, sr, _ in FAR_READS] + [("f16", 2 ** 31 + 16, 3)]
+LATTICE_FAR_READS_GPU = [(dt, sr, 2) for dt, sr, emu_only in FAR_READS if not emu_only] + [("f16", 2 ** 31 + 16, 3)]
 
 
 def far_rows_dtype(s):
@@ -589,7 +602,8 @@ def far_outputs_case(env, s, runs, T=70, B=2, dtype="f16"):
 
 # ---- the lattice families: far labellings and far outputs (y.stride) ---------------------------------------------------
 LATTICE_T = 70
-FAMILIES = ("score", "align", "posterior", "edits")
+FAMILIES = ("score", "align", "posterior", "edits")  # the families whose outputs y.stride addresses
+ALL_FAMILIES = FAMILIES + ("occupancy",)            # ... and the one with strides of its own (fcd_occupancy)
 
 
 def lattice_case(env, kind, B, n_hyp, dtype="f16", T=LATTICE_T):
@@ -621,19 +635,86 @@ def lattice_case(env, kind, B, n_hyp, dtype="f16", T=LATTICE_T):
 _lattice_cases = {}
 
 
-def lattice_run(env, c, family, band, y_stride=None):
-    """one call of fcd_{ctc,crf}_<family>_dev on compact reads with the labellings and outputs at y_stride (None: compact, T)
-    -> dict of numpy arrays shaped as the host layer returns them, entries beyond a labelling 0"""
+class OccLayout:
+    """where fcd_{ctc,crf}_occupancy_dev writes: the strides of fcd_occupancy in floats (None: dense rows, whole blocks one
+    after the other) and the accumulate flag.  stride_row far with dense rows: whole blocks apart; stride_row = S N (or a
+    little more) with stride_t far: time-major, the blocks interleaved row by row"""
+
+    def __init__(self, stride_row=None, stride_t=None, accumulate=0):
+        self.stride_row, self.stride_t, self.accumulate = stride_row, stride_t, accumulate
+
+    def strides(self, T, SN):
+        st = SN if self.stride_t is None else self.stride_t
+        return (T * SN if self.stride_row is None else self.stride_row), st
+
+
+ACC_FILL = np.float32(0.25)  # what the blocks hold before an accumulate = 1 call (PATTERN as a float swallows the sum)
+
+
+class _OccBuffer:
+    """the occ array of a call: every row the call may write prefilled (PATTERN bytes, or ACC_FILL under accumulate = 1), and
+    PATTERN in a STRIP behind every block (behind the last row where the blocks interleave) and between interleaved rows"""
+
+    def __init__(self, env, rows, T, SN, occ):
+        self.rows, self.T, self.SN = rows, T, SN
+        self.sr, self.st = occ.strides(T, SN)
+        self.dense = self.st == SN
+        assert self.dense or self.sr < self.st, "time-major: the blocks interleave row by row"
+        self.reg = env.region(((rows - 1) * self.sr + (T - 1) * self.st + SN + STRIP) * 4)
+        self.before = np.full(T * SN, ACC_FILL, np.float32) if occ.accumulate else np.full(T * SN * 4, PATTERN, np.uint8).view(np.float32)
+        self.width = (rows - 1) * self.sr + SN  # of an interleaved row: every labelling's row t and what lies between them
+        strip = np.full(STRIP * 4, PATTERN, np.uint8)
+        if self.dense:
+            self.guarded = [r for r in range(rows) if r == rows - 1 or self.sr >= T * SN + STRIP]
+            for r in range(rows):
+                self.reg.put(r * self.sr * 4, self.before)
+            for r in self.guarded:
+                self.reg.put((r * self.sr + T * SN) * 4, strip)
+        else:
+            line = np.full(self.width * 4, PATTERN, np.uint8).view(np.float32).copy()
+            for r in range(rows):
+                line[r * self.sr:r * self.sr + SN] = self.before[:SN]
+            for t in range(T):
+                self.reg.put(t * self.st * 4, line)
+            self.reg.put(((T - 1) * self.st + self.width) * 4, strip)
+
+    def read(self):
+        """-> (rows, T, SN) float32; the strips and what lies between interleaved rows must be untouched"""
+        rows, T, SN = self.rows, self.T, self.SN
+        got = np.zeros((rows, T, SN), np.float32)
+        if self.dense:
+            for r in range(rows):
+                got[r] = self.reg.get(r * self.sr * 4, np.float32, T * SN).reshape(T, SN)
+            for r in self.guarded:
+                tail = self.reg.get((r * self.sr + T * SN) * 4, np.uint8, STRIP * 4)
+                assert (tail == PATTERN).all(), ("occ: written behind block", r)
+        else:
+            for t in range(T):
+                line = self.reg.get(t * self.st * 4, np.float32, self.width)
+                for r in range(rows):
+                    got[r, t] = line[r * self.sr:r * self.sr + SN]
+                    gap = line[r * self.sr + SN:(r + 1) * self.sr] if r + 1 < rows else line[:0]
+                    assert (gap.view(np.uint8) == PATTERN).all(), ("occ: written between the rows", t, r)
+            tail = self.reg.get(((T - 1) * self.st + self.width) * 4, np.uint8, STRIP * 4)
+            assert (tail == PATTERN).all(), "occ: written behind the last row"
+        return got
+
+
+def lattice_run(env, c, family, band, y_stride=None, layout=None, occ=None):
+    """one call of fcd_{ctc,crf}_<family>_dev on reads at `layout` (None: compact) with the labellings and the outputs
+    addressed by y.stride at y_stride (None: compact, T) and -- family "occupancy" -- the blocks at `occ` (an OccLayout;
+    None: compact) -> dict of numpy arrays shaped as the host layer returns them, entries beyond a labelling 0; occupancy:
+    "occ" with all T rows of every block as the call left them, "before" what they held"""
     n = nat()
     B, n_hyp, T = c["B"], c["n_hyp"], c["T"]
     rows, W = B * n_hyp, (T if y_stride is None else y_stride)
-    batch, keep = place_batch(env, c["xin"], Layout(), c["dtype"], c["lengths"], c["S"])
+    batch, keep = place_batch(env, c["xin"], layout or Layout(), c["dtype"], c["lengths"], c["S"])
     init = env.small(c["init"]) if c["kind"] == "crf" else None
     # the arrays addressed with y.stride: (name, dtype, elements per unit of stride, extra units)
     arrays = [("labels", np.uint8, 1, 0)] + ([("path", np.uint32, 1, 0)] if band else [])
     arrays += {"score": [], "align": [("start", np.uint32, 1, 0), ("count", np.uint32, 1, 0), ("qual", np.float32, 1, 0)],
                "posterior": [("post", np.float32, N - 1, 0)],
-               "edits": [("deletion", np.float32, 1, 0), ("insertion", np.float32, N - 1, 1)]}[family]
+               "edits": [("deletion", np.float32, 1, 0), ("insertion", np.float32, N - 1, 1)], "occupancy": []}[family]
     subs = {}
     if y_stride is None:
         for name, dt, per, extra in arrays:
@@ -654,11 +735,15 @@ def lattice_run(env, c, family, band, y_stride=None):
             subs[name].put(r * step[name], np.full((T + extra) * per * np.dtype(dt).itemsize, PATTERN, np.uint8))
     lens, nv = env.small(c["out_len"]), env.small(c["n_valid"])
     logp = env.small(np.full(rows, 7.0))
+    if family == "occupancy":
+        occ = occ or OccLayout()
+        ob = _OccBuffer(env, rows, T, c["S"] * N, occ)
     y = n.Labellings(subs["labels"].ptr, lens.ptr, nv.ptr, subs["path"].ptr if band else None, n_hyp, W)
     out = {"score": C.c_void_p(logp.ptr),
            "align": lambda: n.Alignment(subs["start"].ptr, subs["count"].ptr, subs["qual"].ptr, logp.ptr),
            "posterior": lambda: n.Posterior(subs["post"].ptr, logp.ptr),
-           "edits": lambda: n.Edits(subs["deletion"].ptr, subs["insertion"].ptr, logp.ptr)}[family]
+           "edits": lambda: n.Edits(subs["deletion"].ptr, subs["insertion"].ptr, logp.ptr),
+           "occupancy": lambda: n.Occupancy(ob.reg.ptr, ob.sr, ob.st, 1.0, occ.accumulate, logp.ptr)}[family]
     out = out if family == "score" else C.byref(out())
     fn = getattr(env.lib, "fcd_%s_%s_dev" % (c["kind"], family))
     if c["kind"] == "ctc":
@@ -676,16 +761,48 @@ def lattice_run(env, c, family, band, y_stride=None):
             L = int(c["out_len"][b, i])
             a[r, :(L + extra) * per] = subs[name].get(r * step[name], dt, (L + extra) * per)
         got[name] = a.reshape((B, n_hyp, T + extra) + ((per,) if per > 1 else ()))
+    if family == "occupancy":
+        shape = (B, n_hyp, T) + ((c["S"], N) if c["kind"] == "crf" else (N,))
+        got["occ"] = ob.read().reshape(shape)
+        got["before"] = np.broadcast_to(ob.before.reshape(shape[2:]), shape).copy()
     del keep
     return got
 
 
-def lattice_check(got, c, family, band):
+def occupancy_refs(c, band):
+    """the float64 occupancies of the case's labellings (tests/{ctc,crf}_occupancy_reference.py), computed once per band"""
+    refs = c.setdefault("occ_refs", {})
+    if band not in refs:
+        O = __import__("%s_occupancy_reference" % c["kind"])
+        refs[band] = {}
+        for b in range(c["B"]):
+            Tr = int(c["lengths"][b])
+            for i in range(c["n_hyp"]):
+                L = int(c["out_len"][b, i])
+                y, path = c["labels"][b, i, :L], (c["paths"][b, i, :L] if band else None)
+                refs[band][(b, i)] = (O.occupancy64(c["x32"][b, :Tr], c["init"][b], y, band, path) if c["kind"] == "crf" else
+                                      O.occupancy64(c["x32"][b, :Tr], y, True, band, path))
+    return refs[band]
+
+
+def occupancy_check(got, c, band, accumulate, score):
+    """the table's case dict as tests/{ctc,crf}_occupancy_cases.py's check takes it: that checker, its bounds, its rules on
+    what stays untouched; score: the logp of the score family on the same case (the same bits)"""
+    M = __import__("%s_occupancy_cases" % c["kind"])
+    cc = dict(c, band=band, refs=occupancy_refs(c, band), accumulate=bool(accumulate))
+    if c["kind"] == "ctc":
+        cc["k"] = M.states_per_lane(c["T"], c["T"], band)  # (the labellings are compact here: y.stride = T)
+    M.check(cc, got["occ"], got["logp"], score, got["before"])
+
+
+def lattice_check(got, c, family, band, accumulate=0, score=None):
     """the compact result against the family's restatement, with the family's own checker and bounds"""
     from fast_ctc_decode_amd import api
     kind = c["kind"]
     args = (c["lengths"], c["labels"], c["paths"], c["out_len"], c["n_valid"])
-    if family in ("score", "align") and kind == "crf":
+    if family == "occupancy":
+        occupancy_check(got, c, band, accumulate, score)
+    elif family in ("score", "align") and kind == "crf":
         import crf_lattice_cases as CC
         if family == "score":  # (CC.check takes the alignment too: the score alone against the restatement here)
             import crf_lattice_reference as R
@@ -713,21 +830,249 @@ def lattice_check(got, c, family, band):
         M.check(res, c, band) if kind == "crf" else M.check(res, c, band, verbose=False)
 
 
-def lattice_far_case(env, kind, family, band, B, n_hyp, y_stride, T=LATTICE_T):
-    """compact against the restatement, far == compact bit for bit, and a workspace that does not grow with y.stride"""
-    c = lattice_case(env, kind, B, n_hyp, T=T)
+def lattice_far_case(env, kind, family, band, B, n_hyp, y_stride=None, T=LATTICE_T, layout=None, dtype="f16", occ=None, launched=None,
+                     c=None):
+    """compact against the restatement, far == compact bit for bit, and a workspace that does not grow with a stride.  ONE
+    of y_stride (labellings and the outputs they address), layout (the reads) and occ (an OccLayout: the occupancy blocks) is
+    far.  launched: the emulator runner's look at the launch log -- the far call launches what the compact call did.
+    -> the far result"""
+    c = c or lattice_case(env, kind, B, n_hyp, dtype, T)
+    where = (c["name"], family, band, y_stride, layout and layout.strides(T, c["S"] * N), occ and (occ.strides(T, c["S"] * N), occ.accumulate))
+    accumulate = occ.accumulate if occ else 0
+    score = None
+    if family == "occupancy":  # (logp must be the score family's bits on the same case)
+        score = lattice_run(env, c, "score", band)["logp"]
+        env.reset()
     env.h.release_workspace()
-    compact = lattice_run(env, c, family, band)
+    if launched:
+        launched()
+    compact = lattice_run(env, c, family, band, occ=OccLayout(accumulate=accumulate))
     ws_compact = env.workspace_bytes()
-    lattice_check(compact, c, family, band)
+    lattice_check(compact, c, family, band, accumulate, score)
     env.reset()
-    far = lattice_run(env, c, family, band, y_stride)
+    ran = launched() if launched else None
+    far = lattice_run(env, c, family, band, y_stride, layout, occ)
     ws_far = env.workspace_bytes()
     env.reset()
+    if launched:
+        ran_far = launched()
+        assert ran_far == ran, (where, "the far call launched other instantiations", sorted(ran ^ ran_far))
     for name in compact:
-        assert np.array_equal(bits(far[name]), bits(compact[name])), (c["name"], family, band, y_stride, name)
-    assert ws_far == ws_compact, ("the workspace grew with y.stride", ws_compact, ws_far)
-    return ws_far
+        assert np.array_equal(bits(far[name]), bits(compact[name])), (where, name)
+    assert ws_far == ws_compact, (where, "the workspace grew with a stride", ws_compact, ws_far)
+    return far
+
+
+# ---- the occupancy blocks (fcd_occupancy.stride_row / stride_t) ----------------------------------------------------------
+OCC_FAR_ROW = 2 ** 31 + 4  # floats between two dense blocks: block 1 above 2^31 elements (8 GiB)
+# time-major, T = 70: rows 64 .. 69 of both labellings above 2^31 elements; (stride_row extra, ...) once dense, once padded
+OCC_FAR_T = FAR_ROW_STRIDE
+
+
+def occupancy_grouped_case(env, kind, band, stride_row=OCC_FAR_ROW):
+    """a workspace limit of one byte: every read is a launch group of its own and the host adds row0 * stride_row to the base
+    -- the same bits as the far call in one group"""
+    c = lattice_case(env, kind, 2, 1)
+    occ = OccLayout(stride_row=stride_row)
+    whole = lattice_far_case(env, kind, "occupancy", band, 2, 1, occ=occ)
+    env.h.set_workspace_limit(1)
+    try:
+        parts = lattice_run(env, c, "occupancy", band, occ=occ)
+    finally:
+        env.h.set_workspace_limit(0)
+        env.reset()
+    for name in whole:
+        assert np.array_equal(bits(parts[name]), bits(whole[name])), (c["name"], band, "one read per group", name)
+
+
+def occupancy_no_value_case(env, kind, accumulate, stride_row=OCC_FAR_ROW):
+    """the labelling at the far block has more labels than its read has rows: P(y | x) = 0, logp = -inf, and nothing of its
+    block is written, in either accumulate mode"""
+    key = (kind, "more labels than rows")
+    if key not in _lattice_cases:
+        c = dict(lattice_case(env, kind, 2, 1))
+        Tr = int(c["lengths"][1])
+        assert Tr + 1 <= c["T"]
+        c["labels"], c["out_len"] = c["labels"].copy(), c["out_len"].copy()
+        c["labels"][1, 0, :Tr + 1] = np.random.default_rng(5).integers(1, N, Tr + 1)
+        c["out_len"][1, 0] = Tr + 1
+        c["name"] += "_long"
+        c.pop("occ_refs", None)
+        _lattice_cases[key] = c
+    c = _lattice_cases[key]
+    far = lattice_far_case(env, kind, "occupancy", 0, 2, 1, occ=OccLayout(stride_row=stride_row, accumulate=accumulate), c=c)
+    assert occupancy_refs(c, 0)[(1, 0)]["occ"] is None and far["logp"][1, 0] == -np.inf
+    assert np.array_equal(bits(far["occ"][1]), bits(far["before"][1])), "the block of a labelling without a value was written"
+    assert np.isfinite(far["logp"][0, 0])
+
+
+# ---- the walks over all labellings: fcd_crf_transition_probs_dev and fcd_crf_marginals_dev -------------------------------
+# one shape per code form (tests/instantiation_cases.py): a lane per element (S N <= 64), one chunk of 64 states, many chunks
+WALK_SHAPES = ((4, 7), (64, 9), (256, 7))
+WALK_AXES = ("scores_read", "scores_t", "out_read", "out_t", "init", "emit")
+
+
+def walk_case(which, S, T, dtype="f32", layout="source", out="f32"):
+    """a case of tests/crf_transitions_cases.py / crf_marginals_cases.py (inputs and references built once there), of which
+    the table runs reads 0 and 1: lengths T and T - 3"""
+    import crf_marginals_cases as MC
+    import crf_transitions_cases as TC
+    case = TC._case("far_s%d_t%d_%s_%s_%s" % (S, T, dtype, layout, out), S, N, T, dtype=dtype, layout=layout, out=out)
+    if which == "marginals":
+        case = dict(case, name="m_" + case["name"])
+        return MC.build_case(case)
+    return TC.build_case(case)
+
+
+def _rows(reg, B, T, sr, st, inner, dtype):
+    """(B, T, inner) read back from a region at the strides sr, st (elements)"""
+    e = np.dtype(dtype).itemsize
+    got = np.zeros((B, T, inner), dtype)
+    if st == inner:
+        for b in range(B):
+            got[b] = reg.get(b * sr * e, dtype, T * inner).reshape(T, inner)
+    else:
+        assert sr == inner, "time-major"
+        for t in range(T):
+            got[:, t] = reg.get(t * st * e, dtype, B * inner).reshape(B, inner)
+    return got
+
+
+def walk_run(env, which, c, axis=None, stride=None):
+    """one call of fcd_crf_transition_probs_dev / fcd_crf_marginals_dev on reads 0 and 1 of the case with ONE quantity at
+    `stride` (elements): axis "scores_read" / "scores_t" (time-major) the input, "out_read" / "out_t" (time-major) probs or
+    marg, "init" init_stride, "emit" emit_stride; None: everything compact.  Every output row is PATTERN beforehand, with a
+    STRIP behind the last; the scores must be what they were.  -> dict of numpy arrays, all T rows of every read"""
+    n = nat()
+    B, T, S = 2, c["T"], c["S"]
+    SN = S * N
+    marg = which == "marginals"
+    assert axis is None or axis in WALK_AXES and not (axis == "init" and marg) and not (axis == "emit" and not marg)
+    xin, lengths = c["xin"][:B], c["lengths"][:B]
+    lay = Layout(stride_read=stride) if axis == "scores_read" else Layout(stride_read=SN, stride_t=stride) if axis == "scores_t" else Layout()
+    batch, keep = place_batch(env, xin, lay, c["dtype"], lengths, S)
+    in_sr, in_st = lay.strides(T, SN)
+    odt = np.float16 if c["out"] == "f16" else np.float32
+    e = np.dtype(odt).itemsize
+    sr, st = (stride, SN) if axis == "out_read" else (SN, stride) if axis == "out_t" else (T * SN, SN)
+
+    def filled(count, row, step, esz):
+        """a region of `count` rows of `row` elements `step` apart: PATTERN in every row and in a STRIP behind the last"""
+        reg = env.region(((count - 1) * step + row + STRIP) * esz)
+        for k in range(count):
+            reg.fill(k * step * esz, (row + (STRIP if k == count - 1 else 0)) * esz)
+        return reg
+    if st == SN:
+        main = filled(B, T * SN, sr, e)
+    else:
+        main = filled(T, B * SN, st, e)
+    init_stride = stride if axis == "init" else S
+    emit_stride = stride if axis == "emit" else T * N
+    init = None if marg else filled(B, S, init_stride, 4)
+    emit = filled(B, T * N, emit_stride, 4) if marg else None
+    logz, status = env.small(np.full(B, 7.0)), env.small(np.full(B, -7, np.int32))
+    lcode = n.LAYOUT_DEST if c["layout"] == "dest" else n.LAYOUT_SOURCE
+    if marg:
+        out = n.Marginals(main.ptr, sr, st, emit.ptr, emit_stride, logz.ptr, status.ptr)
+        rc = env.lib.fcd_crf_marginals_dev(env.h.ptr, C.byref(batch), lcode, C.byref(out))
+    else:
+        out = n.Transitions(main.ptr, n.DTYPE_F16 if c["out"] == "f16" else n.DTYPE_F32, sr, st, init.ptr, init_stride, logz.ptr, status.ptr)
+        rc = env.lib.fcd_crf_transition_probs_dev(env.h.ptr, C.byref(batch), lcode, C.byref(out))
+    assert rc == n.OK, (which, c["name"], axis, stride, rc, env.lib.fcd_last_error(env.h.ptr))
+    env.sync()
+    got = dict(main=_rows(main, B, T, sr, st, SN, odt).reshape(B, T, S, N), logz=logz.get(0, np.float64, B), status=status.get(0, np.int32, B))
+    last = ((B - 1) * sr + T * SN) if st == SN else ((T - 1) * st + B * SN)
+    assert (main.get(last * e, np.uint8, STRIP * e) == PATTERN).all(), (which, c["name"], axis, "written behind the last row")
+    for name, reg, row, step in (("init", init, S, init_stride), ("emit", emit, T * N, emit_stride)):
+        if reg is not None:
+            got[name] = np.stack([reg.get(b * step * 4, np.float32, row) for b in range(B)])
+            assert (reg.get(((B - 1) * step + row) * 4, np.uint8, STRIP * 4) == PATTERN).all(), (which, c["name"], axis, name, "written behind the last row")
+    if marg:
+        got["emit"] = got["emit"].reshape(B, T, N)
+    back = _rows(keep[0], B, T, in_sr, in_st, SN, xin.dtype)
+    assert np.array_equal(back, xin.reshape(B, T, SN)), (which, c["name"], axis, "the scores were written")
+    for b in range(B):  # rows t >= T_r are not written
+        for name in ("main", "emit") if marg else ("main",):
+            assert (np.ascontiguousarray(got[name][b, int(lengths[b]):]).view(np.uint8) == PATTERN).all(), (which, c["name"], axis, name, b)
+    del keep
+    return got
+
+
+def walk_check(which, c, got):
+    """the compact result against the float64 restatement: check_read of tests/crf_transitions_cases.py /
+    crf_marginals_cases.py with its bounds (it wants its own sentinel in the rows t >= T_r, which walk_run found untouched)"""
+    import crf_marginals_cases as MC
+    import crf_transitions_cases as TC
+    for b in range(2):
+        Tr = int(c["lengths"][b])
+        main = got["main"][b].copy()
+        main[Tr:] = TC.SENTINEL
+        if which == "marginals":
+            emit = got["emit"][b].copy()
+            emit[Tr:] = TC.SENTINEL
+            MC.check_read(c, b, main, emit, float(got["logz"][b]), got["status"][b], (c["name"], b))
+        else:
+            TC.check_read(c, b, main, got["init"][b], float(got["logz"][b]), got["status"][b], (c["name"], b))
+
+
+def walk_far_case(env, which, S, T, axis, stride, dtype="f32", layout="source", out="f32", launched=None):
+    """compact against the restatement; far == compact bit for bit on every row t < T_r, init / emit, logz and status; no
+    workspace either way"""
+    c = walk_case(which, S, T, dtype, layout, out)
+    env.h.release_workspace()
+    if launched:
+        launched()
+    compact = walk_run(env, which, c)
+    walk_check(which, c, compact)
+    env.reset()
+    ran = launched() if launched else None
+    far = walk_run(env, which, c, axis, stride)
+    ws = env.workspace_bytes()
+    env.reset()
+    where = (which, c["name"], axis, stride)
+    if launched:
+        ran_far = launched()
+        assert ran_far == ran, (where, "the far call launched other instantiations", sorted(ran ^ ran_far))
+    assert ws == 0, (where, "the walks take no workspace", ws)
+    for name in compact:
+        for b in range(2):
+            rows = slice(0, int(c["lengths"][b])) if name in ("main", "emit") else Ellipsis  # (rows t >= T_r: found untouched)
+            assert np.array_equal(bits(np.atleast_1d(far[name][b])[rows]), bits(np.atleast_1d(compact[name][b])[rows])), (where, name, b)
+    return far
+
+
+def walk_row_stride(T, esize, elements=True):
+    """the stride_t of a time-major far-rows case: T = 70 takes FAR_ROW_STRIDE for float32 rows (rows 64 .. 69 above 2^31
+    elements) and FAR_ROW_STRIDE_32 for two-byte rows; the short T of S = 256 a stride that puts rows T // 2 and up above 2^31
+    elements, or -- elements False: where that span does not fit the GPU's pool -- above 2^32 bytes"""
+    if T >= 70:  # (two-byte elements: rows 64 .. 69 above 2^32 elements as well, in the same 8.63 GiB)
+        return FAR_ROW_STRIDE_32 if esize == 2 else FAR_ROW_STRIDE
+    boundary = 2 ** 31 if elements else 2 ** 32 // esize
+    return -(-boundary // (T // 2)) // 8 * 8 + 8
+
+
+def walk_table(gpu):
+    """(which, S, T, axis, stride, dtype, layout, out) of every far case of the two walks.  Each axis is far alone.  gpu: the
+    strides whose span fits the GPU runner's pool -- bytes past 2^32 where elements past 2^31 do not fit"""
+    rows = []
+    for which in ("transitions", "marginals"):
+        outs = ("f32", "f16") if which == "transitions" else ("f32",)
+        for S, T in WALK_SHAPES:
+            for dtype, stride, emu_only in (("f16", 2 ** 31 + 16, False), ("f32", 2 ** 30 + 16, False), ("f32", 2 ** 31 + 16, True)):
+                if not (gpu and emu_only):
+                    rows += [(which, S, T, "scores_read", stride, dtype, lay, "f32") for lay in ("source", "dest")]
+            Tt = T if S > 64 else 70  # (far rows: T = 70, S = 256 at its short T)
+            rows += [(which, S, Tt, "scores_t", walk_row_stride(Tt, 2), "f16", lay, "f32") for lay in ("source", "dest")]
+            for out in outs:
+                e = 2 if out == "f16" else 4
+                rows.append((which, S, T, "out_read", 2 ** 31 + 4, "f32", "source", out))
+                rows.append((which, S, Tt, "out_t", walk_row_stride(Tt, e, not (gpu and e == 4)), "f32", "source", out))
+            rows.append((which, S, T, "init" if which == "transitions" else "emit", 2 ** 31 + 4, "f32", "source", "f32"))
+    return rows
+
+
+def walk_id(row):
+    return "%s-s%d-t%d-%s-%d-%s-%s-%s" % row
 
 
 # ---- pack / offsets / unpack of a far result -------------------------------------------------------------------------
@@ -1014,3 +1359,44 @@ def envelope_case(env, stride, env_stride, band=8):
         want = em.envelope(vit[0][i][0], vit[0][i][1], int(d["l1"][i]), vit[1][i][0], vit[1][i][1], int(d["l2"][i]), band)
         assert np.array_equal(got[0][i], np.asarray(want, np.uint64)), ("envelope", i)
         assert np.array_equal(got[1][i], got[0][i]), ("envelope, far", i, stride, env_stride)
+
+
+# ---- what the table holds, entry point by entry point ------------------------------------------------------------------
+# tests/test_far_offsets_emu.py reads include/fcd.h: every fcd_*_dev declared there is a key of COVERED (the quantities its
+# cases take far) or of EXEMPT (why it has none)
+_SEARCH = ("in.stride_read", "in.stride_t", "out.out_stride")
+_LATTICE = ("in.stride_read", "in.stride_t", "y.stride")
+COVERED = {
+    "fcd_viterbi_search_dev": _SEARCH,
+    "fcd_beam_search_dev": _SEARCH + ("the tree arena",),
+    "fcd_crf_beam_search_dev": _SEARCH,
+    "fcd_beam_search_nbest_dev": _SEARCH,
+    "fcd_crf_beam_search_nbest_dev": _SEARCH,
+    "fcd_crf_greedy_search_dev": _SEARCH,
+    "fcd_crf_viterbi_search_dev": _SEARCH,
+    "fcd_beam_session_push_dev": ("chunk.stride_read",),
+    "fcd_beam_session_result_dev": ("the result of chunks pushed from a far buffer",),
+    "fcd_ctc_score_dev": _LATTICE,
+    "fcd_ctc_align_dev": _LATTICE,
+    "fcd_ctc_posterior_dev": _LATTICE,
+    "fcd_ctc_edits_dev": _LATTICE,
+    "fcd_ctc_occupancy_dev": ("in.stride_read", "in.stride_t", "out.stride_row", "out.stride_t"),
+    "fcd_crf_score_dev": _LATTICE,
+    "fcd_crf_align_dev": _LATTICE,
+    "fcd_crf_posterior_dev": _LATTICE,
+    "fcd_crf_edits_dev": _LATTICE,
+    "fcd_crf_occupancy_dev": ("in.stride_read", "in.stride_t", "out.stride_row", "out.stride_t"),
+    "fcd_crf_transition_probs_dev": ("scores.stride_read", "scores.stride_t", "out.stride_read", "out.stride_t", "out.init_stride"),
+    "fcd_crf_marginals_dev": ("scores.stride_read", "scores.stride_t", "out.stride_read", "out.stride_t", "out.emit_stride"),
+    "fcd_beam_search_duplex_dev": ("in1 / in2 stride_read", "in1 / in2 stride_t"),
+    "fcd_crf_beam_search_duplex_dev": ("in1 / in2 stride_read", "in1 / in2 stride_t"),
+    "fcd_duplex_envelope_dev": ("stride1 / stride2", "env_stride"),
+    "fcd_result_offsets_dev": ("out_stride",),
+    "fcd_pack_results_dev": ("res.out_stride",),
+    "fcd_unpack_results_dev": ("out.out_stride",),
+}
+EXEMPT = {
+    "fcd_crf_beam_search_dev_k": "fcd_crf_beam_search_dev is this call with FCD_KERNEL_AUTO: one body, in the table under that name",
+    "fcd_gather_results_dev": "needs a communicator and a second rank; its offsets and pack steps are the kernels of fcd_result_offsets_dev / fcd_pack_results_dev",
+    "fcd_unpack_gathered_dev": "the unpack step of a gather over several ranks' shards, driven by the distributed tests; no far case yet",
+}

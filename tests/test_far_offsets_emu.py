@@ -3,8 +3,15 @@ wave64 emulation, on layouts whose element offsets pass 2^31 and whose byte offs
 the table, the builders and the checkers).  The backing arrays are np.empty and only the rows a case reads are ever
 written, so the gaps are never committed; the largest single array is 16 GiB of virtual memory.
 
+Beside the searches, sessions, duplex searches, the band estimator and pack / unpack: the ten lattice entry points with far
+labellings, far reads and far rows, the occupancy blocks far apart and interleaved with far rows, and the two walks over all
+labellings with each stride far alone.  The emulator also maps what the GPU's pool cannot: offsets past 2^32 ELEMENTS of
+float32 (three occupancy blocks, time-major occupancy rows 2^26 + 8 apart), where an offset kept in 32 unsigned bits wraps.
+test_every_dev_entry_point_is_in_the_table holds include/fcd.h to the table: every fcd_*_dev is covered or exempt with a
+reason.
+
 The launch log says which instantiation a far call launched: a dispatch change cannot quietly turn the table into a test
-of the strided fallbacks."""
+of the strided fallbacks; for the lattice families and the walks the far call must launch exactly what the compact call did."""
 import ctypes as C
 
 import numpy as np
@@ -131,6 +138,112 @@ LATTICE_300 = [(kind, fam, band, Y_STRIDES[fam][0]) for kind, fam, band in F.LAT
 def test_far_labellings_t300(env, kind, family, band, y_stride):
     """T = 300: labellings of about 150 labels, windows that cross 256 rows at the far address"""
     F.lattice_far_case(env, kind, family, band, 2, 1, y_stride, T=300)
+
+
+# ---- far reads and far rows under the lattice families: labellings and outputs compact ----------------------------------
+LATTICE_READS = [(kind, fam, band, dt, sr, B) for kind in ("ctc", "crf") for fam in F.ALL_FAMILIES for band in (0, 6)
+                 for dt, sr, B in F.LATTICE_FAR_READS]
+
+
+@pytest.mark.parametrize("kind,family,band,dtype,stride_read,B", LATTICE_READS, ids=["%s_%s-band%d-%s-%d-b%d" % c for c in LATTICE_READS])
+def test_far_lattice_reads(env, kind, family, band, dtype, stride_read, B):
+    """read 1 starts stride_read elements behind read 0 (+ 17: elements that are not 8-aligned take other load paths); B = 3:
+    read 2 starts above 2^32 elements"""
+    F.lattice_far_case(env, kind, family, band, B, 1, layout=F.Layout(stride_read=stride_read), dtype=dtype, launched=lambda: launched(env))
+
+
+LATTICE_ROWS = [(kind, fam, band, st) for kind in ("ctc", "crf") for fam in F.ALL_FAMILIES for band in (0, 6)
+                for st in (F.FAR_ROW_STRIDE, F.FAR_ROW_STRIDE_32)]
+
+
+@pytest.mark.parametrize("kind,family,band,stride_t", LATTICE_ROWS, ids=["%s_%s-band%d-%d" % c for c in LATTICE_ROWS])
+def test_far_lattice_rows(env, kind, family, band, stride_t):
+    """time-major, float16, T = 70, read 1 ragged: stride_t = 2^25 + 8 puts rows 64 .. 69 above 2^31 elements, 2^26 + 8 above
+    2^32"""
+    S = 4 if kind == "crf" else 1
+    F.lattice_far_case(env, kind, family, band, 2, 1, layout=F.Layout(stride_read=S * F.N, stride_t=stride_t), dtype="f16",
+                       launched=lambda: launched(env))
+
+
+# ---- the occupancy blocks: whole blocks far apart, and interleaved with far rows ----------------------------------------
+OCC_BLOCKS = [(kind, band, B, n_hyp, acc) for kind in ("ctc", "crf") for band in (0, 6) for B, n_hyp in ((2, 1), (1, 2)) for acc in (0, 1)]
+
+
+@pytest.mark.parametrize("kind,band,B,n_hyp,accumulate", OCC_BLOCKS, ids=["%s-band%d-b%dh%d-acc%d" % c for c in OCC_BLOCKS])
+def test_far_occupancy_blocks(env, kind, band, B, n_hyp, accumulate):
+    """dense rows (stride_t = S N: crfp_occ_walk's dense clear), block 1 stride_row = 2^31 + 4 floats behind block 0"""
+    F.lattice_far_case(env, kind, "occupancy", band, B, n_hyp, occ=F.OccLayout(stride_row=F.OCC_FAR_ROW, accumulate=accumulate),
+                       launched=lambda: launched(env))
+
+
+OCC_ROWS = [(kind, band, pad, acc) for kind in ("ctc", "crf") for band in (0, 6) for pad, acc in ((0, 0), (0, 1), (4, 0))]
+
+
+@pytest.mark.parametrize("kind,band,pad,accumulate", OCC_ROWS, ids=["%s-band%d-pad%d-acc%d" % c for c in OCC_ROWS])
+def test_far_occupancy_rows(env, kind, band, pad, accumulate):
+    """the time-major layout of a training step: stride_row = S N (+ pad), stride_t = 2^25 + 8 floats, two reads, T = 70 --
+    rows 64 .. 69 of both blocks above 2^31 elements (the strided clear and the row stores)"""
+    SN = (4 if kind == "crf" else 1) * F.N
+    F.lattice_far_case(env, kind, "occupancy", band, 2, 1, occ=F.OccLayout(stride_row=SN + pad, stride_t=F.OCC_FAR_T, accumulate=accumulate),
+                       launched=lambda: launched(env))
+
+
+@pytest.mark.parametrize("kind", ["ctc", "crf"])
+def test_far_occupancy_t300(env, kind):
+    """T = 300 under the band, as the posterior and edits families (far_offset_cases.LATTICE_300)"""
+    F.lattice_far_case(env, kind, "occupancy", 6, 2, 1, T=300, occ=F.OccLayout(stride_row=F.OCC_FAR_ROW), launched=lambda: launched(env))
+
+
+@pytest.mark.parametrize("kind", ["ctc", "crf"])
+@pytest.mark.parametrize("band", [0, 6])
+def test_far_occupancy_beyond_2_32_elements(env, kind, band):
+    """what only the emulator can map (16 GiB each): three dense blocks, block 2 above 2^32 floats; and time-major rows
+    2^26 + 8 floats apart at T = 65, row 64 above 2^32 floats -- where an offset kept in 32 unsigned bits wraps"""
+    F.lattice_far_case(env, kind, "occupancy", band, 3, 1, occ=F.OccLayout(stride_row=F.OCC_FAR_ROW), launched=lambda: launched(env))
+    SN = (4 if kind == "crf" else 1) * F.N
+    F.lattice_far_case(env, kind, "occupancy", band, 2, 1, T=65, occ=F.OccLayout(stride_row=SN, stride_t=F.FAR_ROW_STRIDE_32),
+                       launched=lambda: launched(env))
+
+
+@pytest.mark.parametrize("kind", ["ctc", "crf"])
+@pytest.mark.parametrize("band", [0, 6])
+def test_far_occupancy_one_read_per_group(env, kind, band):
+    F.occupancy_grouped_case(env, kind, band)
+
+
+@pytest.mark.parametrize("kind", ["ctc", "crf"])
+@pytest.mark.parametrize("accumulate", [0, 1])
+def test_far_occupancy_no_value(env, kind, accumulate):
+    F.occupancy_no_value_case(env, kind, accumulate)
+
+
+# ---- the walks over all labellings ---------------------------------------------------------------------------------------
+WALKS = F.walk_table(gpu=False)
+
+
+@pytest.mark.parametrize("which,S,T,axis,stride,dtype,layout,out", WALKS, ids=[F.walk_id(c) for c in WALKS])
+def test_far_walks(env, which, S, T, axis, stride, dtype, layout, out):
+    F.walk_far_case(env, which, S, T, axis, stride, dtype, layout, out, launched=lambda: launched(env))
+
+
+# ---- every entry point ---------------------------------------------------------------------------------------------------
+def test_every_dev_entry_point_is_in_the_table():
+    """include/fcd.h against far_offset_cases.COVERED / EXEMPT: an entry point added without a far case fails here"""
+    import os
+    import re
+    header = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "include", "fcd.h")
+    with open(header) as f:
+        names = set(re.findall(r"\b(fcd_\w+_dev\w*)\s*\(", f.read()))
+    assert len(names) >= 30, sorted(names)
+    assert not set(F.COVERED) & set(F.EXEMPT)
+    missing = sorted(names - set(F.COVERED) - set(F.EXEMPT))
+    assert not missing, ("no far-offset case and no exemption", missing)
+    stale = sorted((set(F.COVERED) | set(F.EXEMPT)) - names)
+    assert not stale, ("not declared in include/fcd.h", stale)
+    for name, axes in F.COVERED.items():
+        assert axes and all(isinstance(a, str) and a for a in axes), name
+    for name, reason in F.EXEMPT.items():
+        assert isinstance(reason, str) and len(reason) > 20 and "\n" not in reason, name
 
 
 # ---- pack / offsets / unpack -------------------------------------------------------------------------------------------

@@ -2,11 +2,9 @@
 on the device.  The table of tests/crf_marginals_cases.py on torch device tensors (fcd_crf_marginals_dev and
 crf_marginals_batch_raw) against the float64 restatement (tests/crf_marginals_reference.py), the case whose LDS passes 64 KiB,
 the edge cases, the argument errors and limits, the nullable outputs, host and device entry points bit for bit, torch tensors
-in and out without a synchronise, one call between overlapping beam searches under set_overlap(4), one call whose input and
-output offsets pass 2^31 elements (the memory helpers of tests/far_offset_cases.py), and crf_logz against torch autograd of
-the float64 recurrence."""
-import ctypes as C
-
+in and out without a synchronise, one call between overlapping beam searches under set_overlap(4), and crf_logz against torch
+autograd of the float64 recurrence.  Offsets past 2^31 elements and 2^32 bytes: tests/test_gpu_far_offsets.py,
+test_far_walks."""
 import numpy as np
 import pytest
 
@@ -117,50 +115,6 @@ def test_one_call_between_overlapping_beam_searches(fcd):
     for b in (0, 17):
         ref = M.marginals64(x0[b])
         assert np.abs(in_order[0][0].marginals[b] - ref["marg"]).max() < 1e-5
-
-
-def test_offsets_beyond_2_31_elements(fcd):
-    """read 1 of the float16 scores and of the float32 marginals starts 2^31 + 8 elements behind read 0 (4 GiB and 8 GiB):
-    the same bits as the compact call.  One uninitialised region holds both arrays; only the rows are touched."""
-    import torch
-    import far_offset_cases as F
-    from fast_ctc_decode_amd import _native as nat
-    free, _ = torch.cuda.mem_get_info()
-    if free < 24 * 2 ** 30:
-        pytest.skip("needs 24 GiB of free device memory")
-    S, N, T, B = 64, 5, 9, 2
-    stride = 2 ** 31 + 8
-    rng = np.random.default_rng(79)
-    x = (2.0 * rng.standard_normal((B, T, S, N))).astype(np.float16)
-    compact = fcd.crf_marginals_batch_raw(torch.from_numpy(x).cuda()).cpu()
-    for b in range(B):
-        ref = M.marginals64(x[b].astype(np.float32))
-        assert np.abs(compact.marginals[b] - ref["marg"]).max() < 1e-5
-    out_at = 32 * 2 ** 20  # bytes: the marginals start 32 MiB into the region, read 1 of both `stride` elements on
-    pool = torch.empty(4 * stride + 64 * 2 ** 20, dtype=torch.uint8, device="cuda")
-    env = F.Env("cuda", pool)
-    try:
-        reg = env.region(4 * stride + out_at + 4 * T * S * N + 256)
-        small = {k: env.small(v) for k, v in (("emit", np.full((B, T, N), 7.5, np.float32)), ("logz", np.zeros(B)),
-                                              ("status", np.full(B, -1, np.int32)))}
-        for b in range(B):
-            reg.put(2 * b * stride, x[b])
-            reg.fill(out_at + 4 * b * stride, 4 * T * S * N)
-        batch = nat.Batch(reg.ptr, B, T, S, N, stride, S * N, N, 1, None, nat.DTYPE_F16)
-        out = nat.Marginals(reg.ptr + out_at, stride, S * N, small["emit"].ptr, T * N, small["logz"].ptr, small["status"].ptr)
-        assert env.lib.fcd_crf_marginals_dev(env.h.ptr, C.byref(batch), nat.LAYOUT_SOURCE, C.byref(out)) == nat.OK
-        env.sync()
-        for b in range(B):
-            got = reg.get(out_at + 4 * b * stride, np.float32, T * S * N).reshape(T, S, N)
-            assert np.array_equal(got, compact.marginals[b]), b
-            assert np.array_equal(reg.get(2 * b * stride, np.float16, T * S * N).reshape(T, S, N), x[b]), "the scores were written"
-        assert np.array_equal(small["emit"].get(0, np.float32, B * T * N).reshape(B, T, N), compact.emit)
-        assert np.array_equal(small["logz"].get(0, np.float64, B), compact.logz)
-        assert small["status"].get(0, np.int32, B).tolist() == [0, 0]
-    finally:
-        env.close()
-        del env, pool
-        torch.cuda.empty_cache()
 
 
 def _torch_logz64(torch, x, lengths, d):

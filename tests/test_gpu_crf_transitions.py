@@ -3,10 +3,8 @@ device.  The table of tests/crf_transitions_cases.py on torch device tensors (fc
 crf_transition_probs_batch_raw) against the float64 restatement (tests/crf_transitions_reference.py), the case whose LDS
 passes 64 KiB (the launch that raises the kernel's limit), the edge cases, the argument errors and limits, the nullable logz,
 host and device entry points bit for bit, torch tensors in and out without a synchronise, the pipeline scores -> probs ->
-crf_beam_search -> crf_score under set_overlap(4) with no join in between, and one call whose input and output offsets pass
-2^31 elements (the memory helpers of tests/far_offset_cases.py)."""
-import ctypes as C
-
+crf_beam_search -> crf_score under set_overlap(4) with no join in between.  Offsets past 2^31 elements and 2^32 bytes:
+tests/test_gpu_far_offsets.py, test_far_walks."""
 import numpy as np
 import pytest
 
@@ -116,45 +114,3 @@ def test_scores_to_beam_search_to_crf_score_under_overlap(fcd):
         ref = R.transitions64(x0[b])
         p = in_order[0][0].probs[b].astype(np.float64)
         assert np.abs(p - ref["probs"]).max() <= 2.0 ** -11 and abs(in_order[0][0].logz[b] - ref["logz"]) <= TC.logz_bound(ref["logz"])
-
-
-def test_offsets_beyond_2_31_elements(fcd):
-    """read 1 of the float16 scores and of the float16 probabilities starts 2^31 + 8 elements (4 GiB) behind read 0: the same
-    bits as the compact call.  One uninitialised region of 4 GiB + 64 MiB holds both arrays; only the rows are touched."""
-    import torch
-    import far_offset_cases as F
-    from fast_ctc_decode_amd import _native as nat
-    free, _ = torch.cuda.mem_get_info()
-    if free < 24 * 2 ** 30:
-        pytest.skip("needs 24 GiB of free device memory")
-    S, N, T, B = 64, 5, 9, 2
-    stride = 2 ** 31 + 8
-    rng = np.random.default_rng(77)
-    x = (2.0 * rng.standard_normal((B, T, S, N))).astype(np.float16)
-    compact = fcd.crf_transition_probs_batch_raw(torch.from_numpy(x).cuda(), out_dtype="float16").cpu()
-    for b in range(B):
-        ref = R.transitions64(x[b].astype(np.float32))
-        assert np.abs(compact.probs[b].astype(np.float64) - ref["probs"]).max() <= 2.0 ** -11
-    out_at = 32 * 2 ** 20  # bytes: the probabilities start 32 MiB into the region, read 1 of both `stride` elements on
-    pool = torch.empty(2 * stride + 64 * 2 ** 20, dtype=torch.uint8, device="cuda")
-    env = F.Env("cuda", pool)
-    try:
-        reg = env.region(2 * stride + out_at + 2 * T * S * N + 256)
-        small = {k: env.small(v) for k, v in (("init", np.zeros((B, S), np.float32)), ("logz", np.zeros(B)), ("status", np.full(B, -1, np.int32)))}
-        for b in range(B):
-            reg.put(2 * b * stride, x[b])
-            reg.fill(out_at + 2 * b * stride, 2 * T * S * N)
-        batch = nat.Batch(reg.ptr, B, T, S, N, stride, S * N, N, 1, None, nat.DTYPE_F16)
-        out = nat.Transitions(reg.ptr + out_at, nat.DTYPE_F16, stride, S * N, small["init"].ptr, S, small["logz"].ptr, small["status"].ptr)
-        assert env.lib.fcd_crf_transition_probs_dev(env.h.ptr, C.byref(batch), nat.LAYOUT_SOURCE, C.byref(out)) == nat.OK
-        env.sync()
-        for b in range(B):
-            got = reg.get(out_at + 2 * b * stride, np.float16, T * S * N).reshape(T, S, N)
-            assert np.array_equal(got, compact.probs[b]), b
-        assert np.array_equal(small["init"].get(0, np.float32, B * S).reshape(B, S), compact.init)
-        assert np.array_equal(small["logz"].get(0, np.float64, B), compact.logz)
-        assert small["status"].get(0, np.int32, B).tolist() == [0, 0]
-    finally:
-        env.close()
-        del env, pool
-        torch.cuda.empty_cache()

@@ -1,6 +1,9 @@
 """GPU twin of tests/test_far_offsets_emu.py: every entry point of the C ABI on device buffers whose element offsets pass
 2^31 and whose byte offsets pass 2^32 (tests/far_offset_cases.py: the table, the builders and the checkers) -- where the
-kernels' 32-bit address tricks (byte-offset slabs, wave-uniform bases with one vector offset) actually run.
+kernels' 32-bit address tricks (byte-offset slabs, wave-uniform bases with one vector offset) actually run.  The lattice
+families (occupancy included) take far labellings, far reads and far rows, the occupancy blocks lie 8 GiB apart or interleave
+with far rows, and the walks over all labellings (crf_transition_probs, crf_marginals) take each of their strides far alone:
+ONE far quantity per case.
 
 Memory: ONE pool of 8.75 GiB, made once with torch.empty and never filled or copied as a whole; every case carves its arrays
 from it and writes / reads back only the rows it touches.  The arena tests swap it for a pool of 1 GiB (whichever order the
@@ -109,6 +112,76 @@ LATTICE_300 = [(kind, fam, band, y_strides(fam, band)[0]) for kind, fam, band in
 def test_far_labellings_t300(env, kind, family, band, y_stride):
     """T = 300: labellings of about 150 labels, windows that cross 256 rows at the far address"""
     F.lattice_far_case(env, kind, family, band, 2, 1, y_stride, T=300)
+
+
+# ---- far reads and far rows under the lattice families: labellings and outputs compact (a span of 4 to 4.3 GiB) ----------
+LATTICE_READS = [(kind, fam, band, dt, sr, B) for kind in ("ctc", "crf") for fam in F.ALL_FAMILIES for band in (0, 6)
+                 for dt, sr, B in F.LATTICE_FAR_READS_GPU]
+
+
+@pytest.mark.parametrize("kind,family,band,dtype,stride_read,B", LATTICE_READS, ids=["%s_%s-band%d-%s-%d-b%d" % c for c in LATTICE_READS])
+def test_far_lattice_reads(env, kind, family, band, dtype, stride_read, B):
+    """B = 3: read 2 starts above 2^32 elements, a span of 8 GiB"""
+    F.lattice_far_case(env, kind, family, band, B, 1, layout=F.Layout(stride_read=stride_read), dtype=dtype)
+
+
+LATTICE_ROWS = [(kind, fam, band, st) for kind in ("ctc", "crf") for fam in F.ALL_FAMILIES for band in (0, 6)
+                for st in (F.FAR_ROW_STRIDE, F.FAR_ROW_STRIDE_32)]
+
+
+@pytest.mark.parametrize("kind,family,band,stride_t", LATTICE_ROWS, ids=["%s_%s-band%d-%d" % c for c in LATTICE_ROWS])
+def test_far_lattice_rows(env, kind, family, band, stride_t):
+    """time-major, float16, T = 70, read 1 ragged: stride_t = 2^25 + 8 puts rows 64 .. 69 above 2^31 elements, 2^26 + 8 above
+    2^32 (8.63 GiB)"""
+    S = 4 if kind == "crf" else 1
+    F.lattice_far_case(env, kind, family, band, 2, 1, layout=F.Layout(stride_read=S * F.N, stride_t=stride_t), dtype="f16")
+
+
+# ---- the occupancy blocks: 2^31 + 4 floats apart (a span of 8 GiB), or interleaved with rows 2^25 + 8 floats apart (8.63
+# GiB: with far float32 rows of crf_greedy_search the widest span of the table) ---------------------------------------------
+OCC_BLOCKS = [(kind, band, B, n_hyp, acc) for kind in ("ctc", "crf") for band in (0, 6) for B, n_hyp in ((2, 1), (1, 2)) for acc in (0, 1)]
+
+
+@pytest.mark.parametrize("kind,band,B,n_hyp,accumulate", OCC_BLOCKS, ids=["%s-band%d-b%dh%d-acc%d" % c for c in OCC_BLOCKS])
+def test_far_occupancy_blocks(env, kind, band, B, n_hyp, accumulate):
+    F.lattice_far_case(env, kind, "occupancy", band, B, n_hyp, occ=F.OccLayout(stride_row=F.OCC_FAR_ROW, accumulate=accumulate))
+
+
+OCC_ROWS = [(kind, band, pad, acc) for kind in ("ctc", "crf") for band in (0, 6) for pad, acc in ((0, 0), (0, 1), (4, 0))]
+
+
+@pytest.mark.parametrize("kind,band,pad,accumulate", OCC_ROWS, ids=["%s-band%d-pad%d-acc%d" % c for c in OCC_ROWS])
+def test_far_occupancy_rows(env, kind, band, pad, accumulate):
+    """the time-major layout of a training step: stride_row = S N (+ pad), stride_t far, two reads, T = 70"""
+    SN = (4 if kind == "crf" else 1) * F.N
+    F.lattice_far_case(env, kind, "occupancy", band, 2, 1, occ=F.OccLayout(stride_row=SN + pad, stride_t=F.OCC_FAR_T, accumulate=accumulate))
+
+
+@pytest.mark.parametrize("kind", ["ctc", "crf"])
+def test_far_occupancy_t300(env, kind):
+    F.lattice_far_case(env, kind, "occupancy", 6, 2, 1, T=300, occ=F.OccLayout(stride_row=F.OCC_FAR_ROW))
+
+
+@pytest.mark.parametrize("kind", ["ctc", "crf"])
+@pytest.mark.parametrize("band", [0, 6])
+def test_far_occupancy_one_read_per_group(env, kind, band):
+    F.occupancy_grouped_case(env, kind, band)
+
+
+@pytest.mark.parametrize("kind", ["ctc", "crf"])
+@pytest.mark.parametrize("accumulate", [0, 1])
+def test_far_occupancy_no_value(env, kind, accumulate):
+    F.occupancy_no_value_case(env, kind, accumulate)
+
+
+# ---- the walks over all labellings: one stride far per case; float32 rows of S = 256 at bytes past 2^32 (the emulator twin
+# takes them past 2^31 elements, 16 GiB) ------------------------------------------------------------------------------------
+WALKS = F.walk_table(gpu=True)
+
+
+@pytest.mark.parametrize("which,S,T,axis,stride,dtype,layout,out", WALKS, ids=[F.walk_id(c) for c in WALKS])
+def test_far_walks(env, which, S, T, axis, stride, dtype, layout, out):
+    F.walk_far_case(env, which, S, T, axis, stride, dtype, layout, out)
 
 
 @pytest.mark.parametrize("T", F.TS)
