@@ -242,6 +242,12 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_pe
     // lane holds it, not its sort-key word: rank 0's is the step's divisor and is read as it is.  The key word is a bijection of
     // it, so two tie words are equal exactly when the two key words were.
     constexpr bool kRawTop = HL;
+    // RAWK (the R32 members of HL, i.e. all of them): the probability table holds the RAW word as well -- bits(prob + 0.0f), 0
+    // for a lane without a candidate -- and the every-step path writes that one word only.  The f32 count wants the
+    // probabilities themselves (device_utils.h, FCD_RANKP4), validity is the mask m_val, and the node table is read only by
+    // the clash recount and the quicksort replay's list builder: the keyed probability word and the node word are formed, and
+    // both tables written keyed, inside the rare block that reads them (beam_wave_step.inc).
+    constexpr bool RAWK = R32 && HL;
     static_assert(!PDQ || BCAP * N > 20, "the tie order only matters above 20 candidates");
     static_assert(!PDQ || BCAP * N <= HALF - 2, "the last two entries of a half's table are never written (i_src below)");
     int n_amb = 0, n_crit = 0;

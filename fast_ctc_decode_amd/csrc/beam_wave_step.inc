@@ -50,8 +50,9 @@
         const uint64_t m_blank = HL ? ballot(pr0 > thr) : 0ull;
         const uint64_t m_stay = HL ? (collapse_m & ballot(tipf != 0) & ballot(!(ptip < thr))) : 0ull;
         const uint64_t m_inc = HL ? (self_m & ballot(incv != 0)) : 0ull;
-        // HL: the mask of this step's candidates.  The key below is formed under exactly this mask and make_key() is never
-        // 0, so it IS the vote "key != 0" (m_valid) the step takes behind the rank.
+        // HL: the mask of this step's candidates.  It IS the vote "key != 0" (m_valid) the other instantiations take behind
+        // the rank: their key is formed under exactly this mask and make_key() is never 0.  (RAWK: the table word below is
+        // written under it and may well be 0 for a candidate -- p = 0 -- so nothing reads validity off a word.)
         const uint64_t m_val = HL ? ((m_grp & self_m & (m_blank | m_stay | m_inc)) | (m_cv & ~m_ib)) : 0ull;
         const bool blank = HL ? lane_in(m_blank, lane) : (pr0 > thr);
         const float gpn = (lp + gp) * pr0;
@@ -77,6 +78,8 @@
         // lane, exactly like the index it is about to receive -- so the key does not wait for the numbering below.
         // (A NaN key is garbage but non-zero: it only ever ranks when it is the read's lone candidate, :262.  Its
         // probability word may be 0 -- the negative NaN with an all-ones payload -- so "is a candidate" stays key != 0.)
+        // (RAWK: idk is not formed.  The rare block takes the node word from `id`, where a new node carries the index the
+        // numbering gave it: the same order as (t << KS) + q, by the argument above -- stated again where it is formed.)
         const int idk = is_self ? node : (is_new ? tks + q : cid);
         // kRawTop (HL): what the candidate leaves next to its survivor-table entry is its probability as make_key() takes it,
         // prob + 0.0f -- formed once, in front of the key's exec region, for both (formed again from the key where a tie replay
@@ -84,12 +87,20 @@
         float pcanon = prob + 0.0f;
         if (kRawTop) FCD_OPAQUE_VQ(pcanon);
         int pword = kRawTop ? __float_as_int(pcanon) : 0;
-        uint64_t key = (UNI ? valid : (valid && act)) ? (kRawTop ? make_key_canonical(pcanon, idk) : make_key(prob, idk)) : 0ull;
+        // RAWK: no key here at all.  The every-step path ranks on the RAW probability word (below) and reads neither the
+        // keyed word nor the node word; the step's rare block forms both, for every lane, when it is entered for a recount.
+        uint64_t key = RAWK ? 0ull
+                            : ((UNI ? valid : (valid && act)) ? (kRawTop ? make_key_canonical(pcanon, idk) : make_key(prob, idk)) : 0ull);
         // R32: the probability word and the node word go to two tables (beam_wave.hip), one ds_write2_b32; the rank below
         // is taken on the probability word alone, and candidates of equal probability are told apart only in the step's
         // rare branch, when the survivor table shows that two KEPT ones met (settle_table).
-        const uint32_t kp = (uint32_t)(key >> 32);
-        if (R32) {
+        // RAWK: ONE table word per step, the candidate's probability itself -- bits(pcanon), 0 on a lane without a candidate
+        // (device_utils.h, FCD_RANKP4: what the count, the guard, an empty slot and a candidate of probability 0 make of it).
+        // pcanon, not prob: the survivor table's tie words compare bit patterns, and -0.0 must not appear there.
+        const uint32_t kp = RAWK ? (valid ? (uint32_t)pword : 0u) : (uint32_t)(key >> 32);
+        if (RAWK) {
+            kwords[kslot] = kp;
+        } else if (R32) {
             kwords[kslot] = kp;
             kwords[kslot + kNodeTab] = (uint32_t)key;
         } else {
@@ -184,7 +195,7 @@
 
         // ---- prune, second half: count the larger keys ----
         int rank = 0;
-        const float fown_g = (R32 && HL) ? fcd_rankf_own(kp) : 0.0f;  // (HL: the count's own term; the guard votes on it as well)
+        const float fown_g = RAWK ? fcd_rankp_own(kp) : 0.0f;  // (HL: the count's own term; the guard votes on it as well)
         int n_eq = 0, n_gt = 0;  // AMB: candidates of exactly this probability (itself included) / of a greater one
         if (AMB) {
 #pragma unroll
@@ -198,7 +209,7 @@
             // j + kAhead behind the count of block j - 1 (left alone, the scheduler hoists every load to the top again)
             int r0, r1 = 0, r2 = 0, r3 = 0;
             static_assert(!STREAM || NC >= 4, "at least one block of four comparands");
-            // HL: the count as a sum of clamped f32 differences (device_utils.h, FCD_RANKF4): own word scaled once
+            // HL: the count as a sum of clamped f32 differences (device_utils.h, FCD_RANKP4): own word scaled once
             const float fown = fown_g;
             float facc;
 #pragma unroll
@@ -207,12 +218,12 @@
                 if (j + kAhead < NBLK) load_blk(j + kAhead);
                 if (R32 && HL) {  // the same count in ONE accumulator, in f32: v_fma_f32 + v_add_f32 per comparand
                     if (j == 0) {
-                        FCD_RANKF4_FIRST(fown, kw[0], kw[1], kw[2], kw[3], facc);
+                        FCD_RANKP4_FIRST(fown, kw[0], kw[1], kw[2], kw[3], facc);
                     } else if (4 * j + 4 <= NC) {
-                        FCD_RANKF4(fown, kw[4 * j], kw[4 * j + 1], kw[4 * j + 2], kw[4 * j + 3], facc);
+                        FCD_RANKP4(fown, kw[4 * j], kw[4 * j + 1], kw[4 * j + 2], kw[4 * j + 3], facc);
                     } else {
 #pragma unroll
-                        for (int u = 4 * j; u < NC; ++u) FCD_RANKF1(fown, kw[u], facc);
+                        for (int u = 4 * j; u < NC; ++u) FCD_RANKP1(fown, kw[u], facc);
                     }
                 } else if (R32) {  // r32 = #(probability word > own): candidates of equal probability share it
                     if (j == 0) {
@@ -517,6 +528,25 @@
         if (__builtin_expect((m_k2 | m_hint | m_clash) != 0ull, 0)) {
             uint64_t m_tied = m_hint;
             if (R32 && m_clash != 0ull) {
+                if (RAWK) {
+                    // The recount, the PDQ hint's list builder, the quicksort replay and the read-back of `key` behind it
+                    // work on KEYED tables: every lane forms its keyed probability word (make_key_canonical's high word of
+                    // pcanon; 0 without a candidate) and its node word HERE and writes both, one two-word write, as the
+                    // top of the step did before.  The next step's top overwrites the probability table with raw words
+                    // again, so two tied steps in a row each rebuild; a step that is here for a returning node only
+                    // (m_k2) rebuilds nothing and reads neither table.
+                    // The node word is taken from `id` -- a slot's own node, or the id field of the child entry as the
+                    // step sees it, a new node's REAL id included.  Only the ORDER of node words is read (the recount and
+                    // the list builder count the larger ones), and a new id exceeds every existing one and grows with the
+                    // lane exactly as tks + q does (see the comment on the key's node index above).
+                    key = valid ? make_key_canonical(__int_as_float(pword), id) : 0ull;
+                    kwords[kslot] = (uint32_t)(key >> 32);
+                    kwords[kslot + kNodeTab] = (uint32_t)key;
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                    __builtin_amdgcn_wave_barrier();
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                }
+                const uint32_t kp = (uint32_t)(key >> 32);  // (RAWK: the keyed word, not the raw one of the first pass)
                 const uint32_t kn = (uint32_t)key;
                 int ex = 0;
 #pragma unroll 1
@@ -648,7 +678,8 @@
                         statec = park[64 * (kFifo + 8)];
                         }
                         // the lane's own key, from the two word tables it wrote at the top of the step (a lane without a
-                        // candidate reads the idle word: 0, 0)
+                        // candidate reads the idle word: 0, 0; RAWK: the tables the recount above wrote KEYED in this very block
+                        // -- m_tied is set only behind it -- so the second settling reads a key, never a raw word)
                         if (R32) key = ((uint64_t)kwords[kslot] << 32) | kwords[kslot + kNodeTab];
                         if (kRawTop) pword = __float_as_int(key_prob((uint32_t)(key >> 32)));
                     } else {

@@ -214,7 +214,8 @@ __device__ __forceinline__ int32_t load_i32_l2(const int32_t *p) {
     } while (0)
 #endif
 
-// The same count as FCD_RANK4_32_ONE in the cheapest instruction class (tools/microbench/issue_cost.hip,
+// The same count as FCD_RANK4_32_ONE in the cheapest instruction class (the KEYED form of r12 - r16 first; the form the kernel
+// runs, FCD_RANKP4 on raw words, is stated against it below) (tools/microbench/issue_cost.hip,
 // profiles/r12a_issue_cost.txt: at six wavefronts per SIMD a compare into a scalar register pair and the add that reads it
 // as its carry hold the SIMD for 4.9 cycles each, v_fma_f32 and v_add_f32 for 2.6 - 2.8).  The word of a non-negative probability
 // p is bits(p) | 0x80000000: read as a float it is -p, an empty slot's word 0 is +0.0.  With A = as_float(own word) * 2^100,
@@ -230,6 +231,20 @@ __device__ __forceinline__ int32_t load_i32_l2(const int32_t *p) {
 constexpr uint32_t kRankfLo = 0x80000000u | (uint32_t)(127 - 76) << 23;  // word of 2^-76
 constexpr uint32_t kRankfHi = 0x80000000u | (uint32_t)(127 + 27) << 23;  // word of 2^27
 __device__ __forceinline__ float fcd_rankf_own(uint32_t word) { return __uint_as_float(word) * 0x1p100f; }
+// The count on RAW words (the headline family's table since r17: bits(p + 0.0f) of a candidate, 0 otherwise).  Own term
+// A = as_float(word) * -2^100, comparand term t = clamp(fma(as_float(w), +2^100, A)) = clamp((p_w - p_own) * 2^100): for
+// every p >= 0 the very floats the keyed form multiplies out (its word read as a float is -p, its two factors have the
+// opposite signs), so everything said above holds word for word, and:
+//  - a lane without a candidate holds word 0, A = -0.0: its count is a sum of 25 values in [0, 1] like any other, and nobody
+//    reads it (m_val);
+//  - an empty slot and a candidate of probability 0 both hold word 0 (keyed: 0 and 0x80000000, +0.0 and -0.0 as floats):
+//    neither is "greater" than anything, t = clamp(0 * 2^100 + A) with A <= 0 -- the same outcome as the keyed pair;
+//  - the guard is fed A = -p * 2^100 for EVERY p now, not only for p >= 0, and fcd_rankf_outside_a / _m still say of p what
+//    fcd_rankf_outside() says of p's keyed word, for all 2^32 patterns (tests/test_headline_rawword_emu.py walks them):
+//    a negative p (-0.0 is not one: its word is that of +0.0, and the third vote, p != 0, takes it out) gives A > 0 and the second vote
+//    fires; a NaN of either sign gives a NaN A and the first vote fires; +inf, p > 2^27 and 0 < p < 2^-76 give the A they
+//    gave.  Raw order and keyed order differ exactly on negative words, and a step that holds one is recounted on keyed tables.
+__device__ __forceinline__ float fcd_rankp_own(uint32_t raw) { return __uint_as_float(raw) * -0x1p100f; }
 __device__ __forceinline__ bool fcd_rankf_outside(uint32_t word) {
     return word - kRankfLo > kRankfHi - kRankfLo && word != 0x80000000u;
 }
@@ -260,17 +275,17 @@ __device__ __forceinline__ uint64_t fcd_rankf_outside_m(float p, float a, float 
 #define FCD_OPAQUE_S(x) asm volatile("" : "+s"(x))
 #endif
 #ifdef FCD_HIPEMU  // (lockstep emulation, tests/hipemu: plain C++)
-static inline float fcd_rankf_t(float a, uint32_t w) {
-    const float t = fmaf(__uint_as_float(w), -0x1p100f, a);
+static inline float fcd_rankp_t(float a, uint32_t w) {
+    const float t = fmaf(__uint_as_float(w), 0x1p100f, a);
     return t > 0.0f ? (t < 1.0f ? t : 1.0f) : 0.0f;  // v_fma_f32 ... clamp: [0, 1], a NaN -> 0
 }
-#define FCD_RANKF4(a, wa, wb, wc, wd, acc) \
-    do { (acc) += fcd_rankf_t(a, wa); (acc) += fcd_rankf_t(a, wb); (acc) += fcd_rankf_t(a, wc); (acc) += fcd_rankf_t(a, wd); } while (0)
-#define FCD_RANKF4_FIRST(a, wa, wb, wc, wd, acc) \
-    do { (acc) = fcd_rankf_t(a, wa) + fcd_rankf_t(a, wb); (acc) += fcd_rankf_t(a, wc); (acc) += fcd_rankf_t(a, wd); } while (0)
-#define FCD_RANKF1(a, w, acc) do { (acc) += fcd_rankf_t(a, w); } while (0)
+#define FCD_RANKP4(a, wa, wb, wc, wd, acc) \
+    do { (acc) += fcd_rankp_t(a, wa); (acc) += fcd_rankp_t(a, wb); (acc) += fcd_rankp_t(a, wc); (acc) += fcd_rankp_t(a, wd); } while (0)
+#define FCD_RANKP4_FIRST(a, wa, wb, wc, wd, acc) \
+    do { (acc) = fcd_rankp_t(a, wa) + fcd_rankp_t(a, wb); (acc) += fcd_rankp_t(a, wc); (acc) += fcd_rankp_t(a, wd); } while (0)
+#define FCD_RANKP1(a, w, acc) do { (acc) += fcd_rankp_t(a, w); } while (0)
 #else
-#define FCD_RANKF4(a, wa, wb, wc, wd, acc)                                                     \
+#define FCD_RANKP4(a, wa, wb, wc, wd, acc)                                                     \
     do {                                                                                       \
         float t0__, t1__, t2__, t3__;                                                          \
         asm("v_fma_f32 %1, %6, %10, %5 clamp\n\t"                                              \
@@ -282,10 +297,10 @@ static inline float fcd_rankf_t(float a, uint32_t w) {
             "v_add_f32 %0, %0, %3\n\t"                                                         \
             "v_add_f32 %0, %0, %4"                                                             \
             : "+v"(acc), "=&v"(t0__), "=&v"(t1__), "=&v"(t2__), "=&v"(t3__)                    \
-            : "v"(a), "v"(wa), "v"(wb), "v"(wc), "v"(wd), "s"(-0x1p100f));                     \
+            : "v"(a), "v"(wa), "v"(wb), "v"(wc), "v"(wd), "s"(0x1p100f));                      \
     } while (0)
 // (the first block: the accumulator STARTS as the sum of two of its four -- one add fewer, nothing to clear)
-#define FCD_RANKF4_FIRST(a, wa, wb, wc, wd, acc)                                               \
+#define FCD_RANKP4_FIRST(a, wa, wb, wc, wd, acc)                                               \
     do {                                                                                       \
         float t0__, t1__, t2__, t3__;                                                          \
         asm("v_fma_f32 %1, %6, %10, %5 clamp\n\t"                                              \
@@ -296,15 +311,15 @@ static inline float fcd_rankf_t(float a, uint32_t w) {
             "v_add_f32 %0, %0, %3\n\t"                                                         \
             "v_add_f32 %0, %0, %4"                                                             \
             : "=&v"(acc), "=&v"(t0__), "=&v"(t1__), "=&v"(t2__), "=&v"(t3__)                   \
-            : "v"(a), "v"(wa), "v"(wb), "v"(wc), "v"(wd), "s"(-0x1p100f));                     \
+            : "v"(a), "v"(wa), "v"(wb), "v"(wc), "v"(wd), "s"(0x1p100f));                      \
     } while (0)
-#define FCD_RANKF1(a, w, acc)                                                                  \
+#define FCD_RANKP1(a, w, acc)                                                                  \
     do {                                                                                       \
         float t0__;                                                                            \
         asm("v_fma_f32 %1, %3, %4, %2 clamp\n\t"                                               \
             "v_add_f32 %0, %0, %1"                                                             \
             : "+v"(acc), "=&v"(t0__)                                                           \
-            : "v"(a), "v"(w), "s"(-0x1p100f));                                                 \
+            : "v"(a), "v"(w), "s"(0x1p100f));                                                  \
     } while (0)
 #endif
 

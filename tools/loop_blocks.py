@@ -4,7 +4,8 @@ family), from the gfx950 disassembly of a hipcc object file; no GPU needed.  Wit
 profiles/TAG_isa_table.txt.
 
 The time loop is the backward scalar branch with the shortest body that holds, in this order, the step's push
-(ds_permute_b32), its key write (ds_write2st64_b32), the count's own term (v_mul_f32 by 2^100) and its division (v_div_fixup_f32).
+(ds_permute_b32), its key write (ds_write2st64_b32 of the two key words, or -- r17: the raw probability word alone --
+ds_write_b32), the count's own term (v_mul_f32 by 2^100, r17: by -2^100) and its division (v_div_fixup_f32).
 The every-step path is its body in address order, minus what a FORWARD scalar branch inside the body jumps over when its
 target is inside the body as well: the row-FIFO rotation (one step in six) and the inline block that ends a failing read.
 Forward branches that leave the body (the rare blocks behind the loop) are counted as not taken, exec branches
@@ -14,8 +15,8 @@ exec region are counted once, in address order.
 Blocks, by landmarks in address order (the scheduler moves single instructions across them: the totals are exact, the
 split is as good as the landmarks):
   extension + push          loop head .. the second ds_permute_b32
-  key + table write         .. the ds_write2st64_b32 of the two key words
-  numbering + record stores .. the instruction in front of the count's own term (v_mul_f32 by 2^100)
+  key + table write         .. the ds_write2st64_b32 of the two key words (r17: the ds_write_b32 of the raw probability word)
+  numbering + record stores .. the instruction in front of the count's own term (v_mul_f32 by 2^100 or -2^100)
   rank                      .. the add behind the last v_fma_f32 ... clamp
   end-of-read test          .. the instruction in front of v_cvt_i32_f32 (the rank as an integer)
   survivor table            .. the second ds_bpermute_b32 behind the table's ds_write2_b32
@@ -37,6 +38,8 @@ import sys
 import tempfile
 
 B = "/opt/rocm/lib/llvm/bin"
+KEY_WRITES = ("ds_write2st64_b32", "ds_write_b32")  # two key words (up to r16) / the raw probability word alone (r17)
+OWN_TERMS = ("0x71800000", "0xf1800000")            # the literal of the count's own term: 2^100 / -2^100
 CHEAP = {"v_add_f32", "v_sub_f32", "v_subrev_f32", "v_mul_f32", "v_fma_f32", "v_fmac_f32", "v_mac_f32", "v_add_u32", "v_sub_u32",
          "v_subrev_u32", "v_and_b32", "v_or_b32", "v_xor_b32", "v_not_b32", "v_mov_b32"}
 BLOCKS = ["extension + push", "key + table write", "numbering + record stores", "rank", "end-of-read test", "survivor table",
@@ -73,9 +76,9 @@ def every_step_path(ins):
         if op in ("s_cbranch_scc0", "s_cbranch_scc1", "s_branch") and target(addr, args) <= addr:
             body = [x for x in ins if target(addr, args) <= x[0] <= addr]
             marks = []  # the step's landmarks must appear in the step's order (a rare block that jumps back into the loop fails this)
-            for want in ("ds_permute_b32", "ds_write2st64_b32", "0x71800000", "v_div_fixup_f32"):
+            for want in (("ds_permute_b32",), KEY_WRITES, OWN_TERMS, ("v_div_fixup_f32",)):
                 start = marks[-1] + 1 if marks else 0
-                hit = next((j for j in range(start, len(body)) if want == body[j][1] or want in body[j][2]), None)
+                hit = next((j for j in range(start, len(body)) if body[j][1] in want or any(w in body[j][2] for w in want)), None)
                 if hit is None:
                     break
                 marks.append(hit)
@@ -128,8 +131,8 @@ def split(path):
     e = []
     p1 = first(lambda i: ops[i] == "ds_permute_b32")
     e.append(first(lambda i: ops[i] == "ds_permute_b32", p1 + 1))
-    e.append(first(lambda i: ops[i] == "ds_write2st64_b32", e[-1]))
-    e.append(first(lambda i: ops[i] == "v_mul_f32" and "0x71800000" in txt[i], e[-1]) - 1)
+    e.append(first(lambda i: ops[i] in KEY_WRITES, e[-1]))
+    e.append(first(lambda i: ops[i] == "v_mul_f32" and any(w in txt[i] for w in OWN_TERMS), e[-1]) - 1)
     lf = last(lambda i: ops[i] == "v_fma_f32" and "clamp" in txt[i], len(path))
     e.append(first(lambda i: ops[i] == "v_add_f32", lf))
     cvt = first(lambda i: ops[i] == "v_cvt_i32_f32", e[-1])
