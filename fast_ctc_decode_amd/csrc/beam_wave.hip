@@ -461,6 +461,10 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_pe
     // HL: the lane-constant masks the step's votes are joined with (beam_wave_step.inc)
     const uint64_t child_m = HL ? ballot(is_child) : 0ull;
     const uint64_t self_m = HL ? ballot(is_self) : 0ull;
+    // HL: all ones on the lower half's lanes, 0 on the upper half's -- what half_prefix_count() joins with the mask's low word.
+    // (Opaque: as a known select the optimiser forms it again in every step.)
+    uint32_t low_half_v = (HL && lane < HALF) ? ~0u : 0u;
+    if (HL) FCD_OPAQUE_V(low_half_v);
     // (all ones or zero.  Opaque: the optimiser knows the two values and joins a vote with it by s_and_b64 ..., exec and two
     // s_cselect_b32 -- three scalar instructions per use where one s_and_b64 does)
     int collapse_w = (HL && !CRF) ? __builtin_amdgcn_readfirstlane(collapse ? -1 : 0) : 0;

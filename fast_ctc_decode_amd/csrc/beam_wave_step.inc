@@ -54,6 +54,13 @@
         // the rank: their key is formed under exactly this mask and make_key() is never 0.  (RAWK: the table word below is
         // written under it and may well be 0 for a candidate -- p = 0 -- so nothing reads validity off a word.)
         const uint64_t m_val = HL ? ((m_grp & self_m & (m_blank | m_stay | m_inc)) | (m_cv & ~m_ib)) : 0ull;
+#ifdef FCD_HIPEMU  // (lockstep emulation, tests/hipemu)
+        // what the eviction mask below rests on: a candidate lane that is no child lane is a slot's own lane
+        if (HL && (m_val & ~child_m) != (m_val & self_m)) {
+            fprintf(stderr, "beam_wave: a candidate on a lane that is neither a slot's own nor a child lane\n");
+            abort();
+        }
+#endif
         const bool blank = HL ? lane_in(m_blank, lane) : (pr0 > thr);
         const float gpn = (lp + gp) * pr0;
         const bool stay = HL ? lane_in(m_stay, lane) : (collapse && tipf != 0 && !(ptip < thr));
@@ -170,7 +177,7 @@
             pre_new = __builtin_popcount(w_new & ((1u << q) - 1u));
         }
         // < cap: the host sizes every slab for (T << KS) ids (capi.hip)
-        const int newid = HL ? half_prefix_count(m_new, lane, tks) : tks + pre_new;
+        const int newid = HL ? half_prefix_count(m_new, lane, low_half_v, tks) : tks + pre_new;
         // (beam_lane.hip writes a node's record when it first ENTERS THE BEAM -- a sixth of the stores.  Tried here, r05:
         // the stores ride for free under the LDS reads above, while next to the survivor gather they cost the PDQ
         // instantiation 8 B of scratch and 1 % -- the write traffic is not what bounds this kernel.)
@@ -304,7 +311,7 @@
         // field of a child entry (kInBeam == 16 << kSlotShift), so following an entry needs no compare
         static_assert(kInBeam == (16 << kSlotShift) && kSlotMask == 15, "child-entry bit layout");
         // Survivor table: entry r = the lane whose candidate took rank r.  LDS executes a wavefront's operations
-        // in order, so the store, the read-back and the two look-ups below share ONE round trip (a ds_permute
+        // in order, so the store, the read-back and the look-ups below (HL: one, `fate`) share ONE round trip (a ds_permute
         // to the new slot followed by a broadcast to its group were two dependent ones).
         const int depc = depth + (is_child ? (1 << kDsh) : 0);  // (HL: depth and depc are shifted up by kDsh = 8)
         bool sel;
@@ -365,7 +372,7 @@
                 clash = sel && back != ent;
                 if (HL) m_clash_t = m_sel & ballot(back != ent);
             }
-            // (HL: the two look-ups are written behind the table's reads, below -- the reads of neighbouring words are merged
+            // (HL: its one look-up, `fate`, is written behind the table's reads, below -- the reads of neighbouring words are merged
             // only while no other LDS operation stands between them)
             if (!HL) {
             fate = HL ? __builtin_amdgcn_ds_bpermute(tgt_a, selflag) : bperm(hbase + mslot * GW, selflag);
@@ -409,8 +416,9 @@
             for (int j = 1; j < BCAP; ++j) e_min = min(e_min, srcs[j]);
             }
             if (HL) {
+                // (`own` is not looked up: "this group's own candidate was dropped" is a function of m_sel -- settle_gather)
                 fate = __builtin_amdgcn_ds_bpermute(tgt_a, selflag);
-                own = bperm(grp0, selflag);
+                own = 0;
             }
             if (PDQ) {
                 tie0 = (uint32_t)srcs[kTie + i_src];
@@ -459,7 +467,36 @@
                 // deep as the node, and then none ever will (its ancestors have left for good, top-down from the
                 // root).  Three evicted rows in four are dead by this test and are never written.
                 if (HL) {  // ONE exec region, its mask joined in scalar registers
-                    if (lane_in(child_m & m_grp & ballot(own == 0) & ballot(depth > e_min), lane))
+                    // "This group's own candidate was dropped" without an LDS look-up of the own lane's selflag: the kept
+                    // own candidates are the bits of m_sel on the slots' own lanes, GW * i of a half; times 2 + 4 + 8 + 16
+                    // each lands on its group's child lanes GW * i + 1 .. + 4.  The bits sit GW = 6 apart and the multiplier
+                    // spans four, so no two products meet and nothing carries; the last group reaches bit GW * (BCAP - 1) + 4
+                    // of its 32-bit half.  Two s_mul_i32 and the complement under child_m for a ds_bpermute_b32, its wait
+                    // and a vector compare.
+                    static_assert(!HL || (GW == 6 && NL <= 4 && GW * (BCAP - 1) + 4 < 32 && HALF == 32),
+                                  "the own-lane bits replicate onto the child lanes without collision or carry");
+                    // (m_sel & ~child_m: a candidate lane that is no child lane is a slot's own.  Not "& self_m": this lambda
+                    // would capture one variable more, and the closure's layout reaches the code of every other instantiation.)
+                    const uint64_t m_kept0 = m_sel & ~child_m;
+                    const uint64_t m_own1 = (uint64_t)((uint32_t)m_kept0 * 30u) | ((uint64_t)((uint32_t)(m_kept0 >> 32) * 30u) << 32);
+#ifdef FCD_HIPEMU  // (lockstep emulation, tests/hipemu: the multiple against its definition, group by group)
+                    {
+                        uint64_t by_group = 0ull;
+                        for (int h = 0; h < 2; ++h)
+                            for (int g = 0; g < BCAP; ++g)
+                                if ((m_kept0 >> (32 * h + GW * g)) & 1ull) by_group |= 0x1Eull << (32 * h + GW * g);
+                        if (by_group != m_own1) {
+                            fprintf(stderr, "beam_wave: own-candidate bits %016llx replicate to %016llx, not %016llx\n",
+                                    (unsigned long long)m_kept0, (unsigned long long)m_own1, (unsigned long long)by_group);
+                            abort();
+                        }
+                    }
+#endif
+                    const uint64_t m_evict = child_m & m_grp & ~m_own1;
+                    // (named, not read: the lambda captures its variables in the order it names them, and that order reaches
+                    // the register allocation of every other instantiation.  `own` stood here.)
+                    (void)own;
+                    if (lane_in(m_evict & ballot(depth > e_min), lane))
                         *at32(rows_w, (hoff + (uint32_t)(node + 1)) * RW + l) = child_s;
                 } else {
                 const bool dead = (depth << 8) <= e_min;  // e_min = (minimum depth << 8) | a lane address

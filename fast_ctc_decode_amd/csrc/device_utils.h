@@ -325,12 +325,14 @@ static inline float fcd_rankp_t(float a, uint32_t w) {
 
 // Set bits of a half's word of a wave-wide vote below this lane's place in its half, counted onto `base`: the lower half
 // counts in the low word (v_mbcnt_lo), the upper half in the high word (v_mbcnt_hi adds nothing for a lane below 32).
-__device__ __forceinline__ int half_prefix_count(uint64_t m, int lane, int base) {
+// `low_half` is lane-constant, all ones on a lane below 32 and 0 above: the caller keeps it in a register, and "the low word,
+// or 0 for the upper half" is one v_and_b32 with the mask word as its scalar operand instead of a move and a select.
+__device__ __forceinline__ int half_prefix_count(uint64_t m, int lane, uint32_t low_half, int base) {
 #ifdef FCD_HIPEMU  // (lockstep emulation, tests/hipemu: plain C++)
-    const uint32_t w = lane >= 32 ? (uint32_t)(m >> 32) : (uint32_t)m;
+    const uint32_t w = lane >= 32 ? (uint32_t)(m >> 32) : (low_half & (uint32_t)m);
     return base + __builtin_popcount(w & ((1u << (lane & 31)) - 1u));
 #else
-    const uint32_t lo = lane >= 32 ? 0u : (uint32_t)m;
+    const uint32_t lo = low_half & (uint32_t)m;
     return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo(lo, (uint32_t)base));
 #endif
 }

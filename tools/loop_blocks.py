@@ -19,7 +19,9 @@ split is as good as the landmarks):
   numbering + record stores .. the instruction in front of the count's own term (v_mul_f32 by 2^100 or -2^100)
   rank                      .. the add behind the last v_fma_f32 ... clamp
   end-of-read test          .. the instruction in front of v_cvt_i32_f32 (the rank as an integer)
-  survivor table            .. the second ds_bpermute_b32 behind the table's ds_write2_b32
+  survivor table            .. the last ds_bpermute_b32 between the table's ds_write2_b32 and the eviction's
+                               global_store_dword (up to r17 the second of two look-ups, `fate` and `own`; r18: `fate`, the only
+                               one left -- the same instructions fall into the same blocks on both)
   child fate + eviction     .. the s_or_b64 exec behind the eviction's global_store_dword
   gather + division         .. the last ds_bpermute_b32 in front of the kind field's v_and_b32 ..., 3, ...
   rare-branch vote          .. the scalar branch to the rare block
@@ -138,9 +140,9 @@ def split(path):
     cvt = first(lambda i: ops[i] == "v_cvt_i32_f32", e[-1])
     e.append(cvt - 1)
     w2 = first(lambda i: ops[i] == "ds_write2_b32", cvt)
-    b1 = first(lambda i: ops[i] == "ds_bpermute_b32", w2)
-    e.append(first(lambda i: ops[i] == "ds_bpermute_b32", b1 + 1))
-    st = first(lambda i: ops[i] == "global_store_dword", e[-1])
+    st = first(lambda i: ops[i] == "global_store_dword", w2)
+    e.append(last(lambda i: ops[i] == "ds_bpermute_b32", st))
+    assert e[-1] > w2, "no look-up between the table's write and the eviction store"
     e.append(first(lambda i: ops[i] == "s_or_b64" and "exec" in txt[i], st))
     kind = first(lambda i: ops[i] == "v_and_b32" and re.search(r", 3, v\d+$", txt[i]), e[-1])
     lastperm = max(i for i in range(len(path)) if ops[i] == "ds_bpermute_b32" and i < first(

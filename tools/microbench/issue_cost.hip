@@ -80,6 +80,22 @@
 #define I_RCP(d, m, s)          "v_rcp_f32 %" #d ", %" #d "\n\t"
 #define I_DIV_FMAS(d, m, s)     "v_div_fmas_f32 %" #d ", %" #d ", %12, %13\n\t"
 #define I_DIV_FIXUP(d, m, s)    "v_div_fixup_f32 %" #d ", %" #d ", %12, %13\n\t"
+// r18: the scalar forms that replace wave-uniform vector work in the headline step (a half's candidate count, beam width and
+// group mask; "own candidate dropped" as a multiple of the kept own-lane bits), each 1:1 beside a v_add_u32 stream as the rows
+// of s_and/s_xor and s_bcnt1/s_cselect above; v_and_b32 with the mask word as its scalar operand (half_prefix_count); and the
+// LDS look-up the multiple replaces -- ds_bpermute_b32, its wait and the compare that reads it -- against the three scalar
+// instructions, both beside two v_add_u32.
+#define I_SMUL_VALU(d, m, s) "s_mul_i32 %" #s ", %" #s ", 30\n\tv_add_u32 %" #d ", %12, %" #d "\n\t" \
+                             "s_mul_i32 %" #s ", %" #s ", 30\n\tv_add_u32 %" #d ", %13, %" #d "\n\t"  // 2 + 2
+#define I_SBFM_VALU(d, m, s) "s_bfm_b32 %" #s ", %" #s ", 0\n\tv_add_u32 %" #d ", %12, %" #d "\n\t" \
+                             "s_bfm_b32 %" #s ", %" #s ", 0\n\tv_add_u32 %" #d ", %13, %" #d "\n\t"  // 2 + 2
+#define I_SBCNT_MIN_VALU(d, m, s) "s_bcnt1_i32_b32 %" #s ", %" #s "\n\tv_add_u32 %" #d ", %12, %" #d "\n\t" \
+                                  "s_min_i32 %" #s ", %" #s ", 5\n\tv_add_u32 %" #d ", %13, %" #d "\n\t"  // 2 + 2
+#define I_AND_SGPR(d, m, s)  "v_and_b32 %" #d ", %" #s ", %" #d "\n\t"
+#define I_BPERM_CMP(d, m, s) "ds_bpermute_b32 %" #d ", %12, %" #d "\n\tv_add_u32 %" #d ", %12, %" #d "\n\ts_waitcnt lgkmcnt(0)\n\t" \
+                             "v_cmp_eq_u32_e64 %" #m ", 0, %" #d "\n\tv_add_u32 %" #d ", %13, %" #d "\n\t"  // (1 LDS + 1 compare) + 2
+#define I_SMUL2_ANDN2(d, m, s) "s_mul_i32 %" #s ", %" #s ", 30\n\tv_add_u32 %" #d ", %12, %" #d "\n\ts_mul_i32 %" #s ", %" #s ", 30\n\t" \
+                               "s_andn2_b64 %" #m ", exec, %" #m "\n\tv_add_u32 %" #d ", %13, %" #d "\n\t"  // 3 scalar + 2
 // a scalar compare and its branch to the next instruction: taken (the compare holds) against not taken
 #define I_BR_TAKEN(d, m, s)     "s_cmp_eq_u32 %" #s ", %" #s "\n\ts_cbranch_scc1 1f\n\t1:\n\t"  // 2
 #define I_BR_NOT(d, m, s)       "s_cmp_lg_u32 %" #s ", %" #s "\n\ts_cbranch_scc1 1f\n\t1:\n\t"  // 2
@@ -104,7 +120,8 @@ enum {
     C_DPP, C_SALU, C_SALU_VALU, C_MIN_U32, C_MAX_U32, C_CMP_CLASS, C_BFI, C_BCNT1_CSEL, C_SAVEEXEC, C_CMP_ADDC, C_FDIV, C_RANK_NOW,
     C_RANK_F, C_RANK_I, C_RANK_S, C_RANK_P,
     C_CMP_CND_VCC, C_SAND_CND_VCC, C_CMP_CND_SGPR, C_CND_E64_VCC, C_MUL_LO, C_DIV_SCALE, C_RCP, C_DIV_FMAS, C_DIV_FIXUP, C_BR_TAKEN, C_BR_NOT,
-    C_LSHR_B64_S, C_LSHR_B64_V, C_MOV_B64, C_MAD_U64, C_LSHL_ADD_U64, C_COUNT
+    C_LSHR_B64_S, C_LSHR_B64_V, C_MOV_B64, C_MAD_U64, C_LSHL_ADD_U64,
+    C_SMUL_VALU, C_SBFM_VALU, C_SBCNT_MIN_VALU, C_AND_SGPR, C_BPERM_CMP, C_SMUL2_ANDN2, C_COUNT
 };
 struct Cls { const char *name; int per_trip_ind, per_trip_dep; const char *unit; };
 // instructions (or units) one loop trip issues per wavefront
@@ -133,6 +150,10 @@ static const Cls kCls[C_COUNT] = {
     {"s_cmp + s_cbranch_scc1 taken (per pair)", 16, 0, "pair"}, {"s_cmp + s_cbranch_scc1 not taken (per pair)", 16, 0, "pair"},
     {"v_lshrrev_b64 <- sgpr pair", 16, 0, "inst"}, {"v_lshrrev_b64 <- vgpr pair", 16, 16, "inst"}, {"v_mov_b64 <- sgpr pair", 16, 0, "inst"},
     {"v_mad_u64_u32", 16, 16, "inst"}, {"v_lshl_add_u64", 16, 16, "inst"},
+    {"s_mul_i32 by 30 1:1 with v_add_u32 (per v_add_u32)", 32, 32, "v_add"}, {"s_bfm_b32 1:1 with v_add_u32 (per v_add_u32)", 32, 32, "v_add"},
+    {"s_bcnt1_i32_b32/s_min_i32 1:1 with v_add_u32 (per v_add_u32)", 32, 32, "v_add"}, {"v_and_b32 <- sgpr operand", 16, 16, "inst"},
+    {"ds_bpermute_b32 + wait + v_cmp_eq_u32_e64 beside 2 v_add_u32 (per group)", 16, 0, "group"},
+    {"2 s_mul_i32 + s_andn2_b64 beside 2 v_add_u32 (per group)", 16, 0, "group"},
 };
 
 #define T0 asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t0) : : "memory")
@@ -171,6 +192,8 @@ __global__ __launch_bounds__(256) void k(uint32_t *cyc, int trips, uint32_t a, f
     STREAM_CASE(C_CMP_CND_VCC, I_CMP_CND_VCC) STREAM_CASE(C_SAND_CND_VCC, I_SAND_CND_VCC) STREAM_CASE(C_CMP_CND_SGPR, I_CMP_CND_SGPR)
     STREAM_CASE(C_CND_E64_VCC, I_CND_E64_VCC) STREAM_CASE(C_MUL_LO, I_MUL_LO) STREAM_CASE(C_DIV_SCALE, I_DIV_SCALE) STREAM_CASE(C_RCP, I_RCP)
     STREAM_CASE(C_DIV_FMAS, I_DIV_FMAS) STREAM_CASE(C_DIV_FIXUP, I_DIV_FIXUP) STREAM_CASE(C_BR_TAKEN, I_BR_TAKEN) STREAM_CASE(C_BR_NOT, I_BR_NOT)
+    STREAM_CASE(C_SMUL_VALU, I_SMUL_VALU) STREAM_CASE(C_SBFM_VALU, I_SBFM_VALU) STREAM_CASE(C_SBCNT_MIN_VALU, I_SBCNT_MIN_VALU)
+    STREAM_CASE(C_AND_SGPR, I_AND_SGPR) STREAM_CASE(C_BPERM_CMP, I_BPERM_CMP) STREAM_CASE(C_SMUL2_ANDN2, I_SMUL2_ANDN2)
     if (C >= C_LSHR_B64_S && C <= C_LSHL_ADD_U64) {
         uint64_t w0 = z0, w1 = z1, w2 = z0 + 5, w3 = z1 + 7;
         STREAM_CASE64(C_LSHR_B64_S, J_LSHR_B64_S) STREAM_CASE64(C_LSHR_B64_V, J_LSHR_B64_V) STREAM_CASE64(C_MOV_B64, J_MOV_B64)
