@@ -63,6 +63,7 @@ SYMBOLS = [
     "fcd_crf_occupancy_dev", "fcd_crf_occupancy_host",
     "fcd_ctc_occupancy_dev", "fcd_ctc_occupancy_host",
     "fcd_set_ctc_occupancy_wide",
+    "fcd_set_crf_lattice_wide",
 ]
 JOB_PATH, JOB_QUAL, JOB_AMBIGUOUS, JOB_DONE = 1, 2, 4, 1
 
@@ -195,6 +196,7 @@ def bind(lib):
     lib.fcd_status_string.restype = C.c_char_p
     lib.fcd_set_workspace_limit.argtypes = [P, i64]
     lib.fcd_set_ctc_occupancy_wide.argtypes = [P, i32]
+    lib.fcd_set_crf_lattice_wide.argtypes = [P, i32]
     lib.fcd_release_workspace.argtypes = [P]
     lib.fcd_set_tie_order.argtypes = [P, i32]
     lib.fcd_get_tie_order.argtypes = [P]
@@ -384,6 +386,11 @@ class Handle:
     def set_ctc_occupancy_wide(self, on):
         """fcd_ctc_occupancy_* on this handle takes windows beyond 510 states (include/fcd.h: fcd_set_ctc_occupancy_wide)."""
         self.check(self.lib.fcd_set_ctc_occupancy_wide(self.ptr, int(bool(on))))
+
+    def set_crf_lattice_wide(self, on):
+        """fcd_crf_score_* and fcd_crf_occupancy_* on this handle take windows beyond 512 states (include/fcd.h:
+        fcd_set_crf_lattice_wide)."""
+        self.check(self.lib.fcd_set_crf_lattice_wide(self.ptr, int(bool(on))))
 
     def set_host_pipeline(self, lanes=0, chunk_reads=0, min_bytes=-1):
         """Tuning of the chunked host path (include/fcd.h: fcd_set_host_pipeline)."""

@@ -696,7 +696,8 @@ def _crf_ctc_loss_function():
                 init = torch.zeros_like(tr.init).scatter_(1, at, 1.0)
                 start = tr.init.gather(1, at)[:, 0]
             # grad = marginals - occupancy, the gradient of logz - ln(sum over the labelling's alignments of exp(score))
-            occ = crf_occupancy_batch_raw(tr.probs, init, labels, label_lengths, lengths, out=grad, scale=-1.0, accumulate=True)
+            occ = crf_occupancy_batch_raw(tr.probs, init, labels, label_lengths, lengths, out=grad, scale=-1.0, accumulate=True,
+                                          wide=True)
             logp = occ.logp[:, 0]
             loss = -(logp + torch.log(start.to(torch.float64)))
             # (a labelling whose lattice the occupancy walk gave up comes back with logp NaN: its loss and gradient are NaN)
@@ -737,7 +738,10 @@ def crf_ctc_loss(scores, labels, label_lengths, lengths=None, start_states=None)
     measured boundary); train on chunks of that size.
     Cost of composing existing launches: the backward pass over all labellings runs twice (once for the posteriors, once
     inside the marginals launch), and two (B,T,S,N) float32 buffers are held (the posteriors until the call returns, the
-    gradient until backward).  Limits: crf_occupancy_batch_raw's, exact lattice: labellings up to 511 labels."""
+    gradient until backward).  Limits: crf_occupancy_batch_raw's with wide=True, exact lattice: labellings up to 4095 rows
+    or labels at N - 1 <= 8 whose copy, tile, window rows and S * N row fit the 160 KiB of LDS (S = 1024 and S = 4096 at
+    N = 5: 2047 labels and more).  Up to 511 labels the register-resident walks run, as before; beyond, the LDS-resident
+    ones."""
     if not _is_torch_cuda(scores):
         raise TypeError("crf_ctc_loss takes a torch ROCm tensor")
     if scores.ndim != 4:
@@ -1238,16 +1242,18 @@ class BatchResult:
                                        self.path if band else None, band, None, input_dtype=input_dtype,
                                        handle=getattr(self, "_handle", None), wide=wide)
 
-    def crf_score(self, network_outputs, init_states, lengths=None, band=0, input_dtype=None):
+    def crf_score(self, network_outputs, init_states, lengths=None, band=0, input_dtype=None, wide=False):
         """ln P(labelling | posteriors) under the CRF model of every read's result, float64 (n_reads, 1):
-        crf_score_batch_raw on this result's own arrays.  For the results of the CRF searches, with the (B,T,S,N)
-        posteriors and init rows they decoded (a session: the concatenated posteriors); plain CTC results are refused."""
+        crf_score_batch_raw on this result's own arrays (wide included).  For the results of the CRF searches, with the
+        (B,T,S,N) posteriors and init rows they decoded (a session: the concatenated posteriors); plain CTC results are
+        refused."""
         if getattr(network_outputs, "ndim", 4) != 4:
             raise ValueError("crf_score covers the results of the CRF searches, (n_reads, T, S, N) posteriors, not plain CTC results")
         if band and self.path is None:
             raise ValueError("a band needs the result's path")
         return crf_score_batch_raw(network_outputs, init_states, self.labels, self.out_len, lengths,
-                                   self.path if band else None, band, None, input_dtype, getattr(self, "_handle", None))
+                                   self.path if band else None, band, None, input_dtype, getattr(self, "_handle", None),
+                                   wide=wide)
 
     def crf_align(self, network_outputs, init_states, lengths=None, band=0, input_dtype=None):
         """The best alignment of every read's result under the CRF model -> AlignResult, arrays (n_reads, 1, stride):
@@ -1281,17 +1287,17 @@ class BatchResult:
         return crf_edits_batch_raw(network_outputs, init_states, self.labels, self.out_len, lengths,
                                    self.path if band else None, band, None, input_dtype, getattr(self, "_handle", None))
 
-    def crf_occupancy(self, network_outputs, init_states, lengths=None, band=0, input_dtype=None):
+    def crf_occupancy(self, network_outputs, init_states, lengths=None, band=0, input_dtype=None, wide=False):
         """The edge occupancies under the CRF model of every read's result -> OccupancyResult, occupancy
         (n_reads, 1, T, S, N): crf_occupancy_batch_raw on this result's own arrays (device results stay on the device).
-        Arguments as crf_score."""
+        Arguments as crf_score; wide as crf_occupancy_batch_raw."""
         if getattr(network_outputs, "ndim", 4) != 4:
             raise ValueError("crf_occupancy covers the results of the CRF searches, (n_reads, T, S, N) posteriors, not plain CTC results")
         if band and self.path is None:
             raise ValueError("a band needs the result's path")
         return crf_occupancy_batch_raw(network_outputs, init_states, self.labels, self.out_len, lengths,
                                        self.path if band else None, band, None, input_dtype=input_dtype,
-                                       handle=getattr(self, "_handle", None))
+                                       handle=getattr(self, "_handle", None), wide=wide)
 
     def sequences(self, alphabet, raise_on_error=True, paths="list"):
         """-> list of (str, path) per read, exactly what the single-read functions return.
@@ -1636,14 +1642,14 @@ class NBestResult:
                                        self.path if band else None, band, self.n_hyp, input_dtype=input_dtype,
                                        handle=getattr(self, "_handle", None), wide=wide)
 
-    def crf_score(self, network_outputs, init_states, lengths=None, band=0, input_dtype=None):
+    def crf_score(self, network_outputs, init_states, lengths=None, band=0, input_dtype=None, wide=False):
         """ln P(labelling | posteriors) under the CRF model of every hypothesis, float64 (n_reads, n_best); NaN where
-        i >= n_hyp[r].  crf_score_batch_raw on this result's own arrays; plain CTC results are refused."""
+        i >= n_hyp[r].  crf_score_batch_raw on this result's own arrays (wide included); plain CTC results are refused."""
         if not self.crf or getattr(network_outputs, "ndim", 4) != 4:
             raise ValueError("crf_score covers the results of the CRF searches, not plain CTC results")
         return crf_score_batch_raw(network_outputs, init_states, self.labels, self.out_len, lengths,
                                    self.path if band else None, band, self.n_hyp, input_dtype,
-                                   getattr(self, "_handle", None))
+                                   getattr(self, "_handle", None), wide=wide)
 
     def crf_align(self, network_outputs, init_states, lengths=None, band=0, input_dtype=None):
         """The best alignment of every hypothesis under the CRF model -> AlignResult, arrays (n_reads, n_best, stride);
@@ -1674,15 +1680,15 @@ class NBestResult:
                                    self.path if band else None, band, self.n_hyp, input_dtype,
                                    getattr(self, "_handle", None))
 
-    def crf_occupancy(self, network_outputs, init_states, lengths=None, band=0, input_dtype=None):
+    def crf_occupancy(self, network_outputs, init_states, lengths=None, band=0, input_dtype=None, wide=False):
         """The edge occupancies under the CRF model of every hypothesis -> OccupancyResult, occupancy
         (n_reads, n_best, T, S, N), zeros and logp NaN where i >= n_hyp[r].  crf_occupancy_batch_raw on this result's own
-        arrays; plain CTC results are refused."""
+        arrays (wide included); plain CTC results are refused."""
         if not self.crf or getattr(network_outputs, "ndim", 4) != 4:
             raise ValueError("crf_occupancy covers the results of the CRF searches, not plain CTC results")
         return crf_occupancy_batch_raw(network_outputs, init_states, self.labels, self.out_len, lengths,
                                        self.path if band else None, band, self.n_hyp, input_dtype=input_dtype,
-                                       handle=getattr(self, "_handle", None))
+                                       handle=getattr(self, "_handle", None), wide=wide)
 
     def hypotheses(self, alphabet, raise_on_error=True):
         """-> per read, a list of (seq, path, score), best first (None for a failed read when not raise_on_error)."""
@@ -2296,7 +2302,7 @@ def ctc_edits(network_output, sequence, alphabet, collapse_repeats=True):
 # CRF scoring and forced alignment of given labellings (include/fcd.h, fcd_crf_score_* / fcd_crf_align_*)
 # ---------------------------------------------------------------------------------------------
 def crf_score_batch_raw(network_outputs, init_states, labels, label_lengths, lengths=None, paths=None, band=0,
-                        n_valid=None, input_dtype=None, handle=None):
+                        n_valid=None, input_dtype=None, handle=None, wide=False):
     """ln of the sum, over every alignment of labelling y to the rows of its read, of the product of the (B,T,S,N) CRF
     posteriors along it, the model state following the labelling from the init row's first maximum as crf_beam_search's
     does (include/fcd.h, fcd_crf_score_*).  -> (B, n_hyp) float64, comparable between the hypotheses of a read and
@@ -2304,6 +2310,9 @@ def crf_score_batch_raw(network_outputs, init_states, labels, label_lengths, len
 
     labels / label_lengths / paths / band / n_valid as ctc_score_batch_raw; init_states (B, n_init).  band=0 scores the
     whole lattice (labellings up to 511 labels), band=W > 0 the alignments within W labels of `paths` (W <= 255).
+    wide=True lifts both (include/fcd.h, fcd_set_crf_lattice_wide): windows up to 4096 states -- 4095 rows or labels, bands
+    up to 2047 -- at N - 1 <= 8, walked in LDS beyond 512 states; a window within 512 states runs the same launch and
+    returns the same bits as wide=False.
     Device tensors in: a torch tensor on the same device, enqueued on torch's current stream, not synchronised.
     numpy in: numpy out."""
     band = _check_band(band, paths)
@@ -2313,12 +2322,24 @@ def crf_score_batch_raw(network_outputs, init_states, labels, label_lengths, len
     if dev is not None:
         import torch
         out = torch.empty((B, n_hyp), dtype=torch.float64, device=dev)
-        h.check(h.lib.fcd_crf_score_dev(h.ptr, C.byref(b), C.c_void_p(init.data_ptr()), int(init.shape[1]),
-                                        int(init.shape[1]), C.byref(y), band, C.c_void_p(out.data_ptr())))
+        if wide:  # (the handle is this thread's: nothing else calls between the switch and the call)
+            h.set_crf_lattice_wide(True)
+        try:
+            h.check(h.lib.fcd_crf_score_dev(h.ptr, C.byref(b), C.c_void_p(init.data_ptr()), int(init.shape[1]),
+                                            int(init.shape[1]), C.byref(y), band, C.c_void_p(out.data_ptr())))
+        finally:
+            if wide:
+                h.set_crf_lattice_wide(False)
         return out
     out = np.empty((B, n_hyp), np.float64)
-    h.check(h.lib.fcd_crf_score_host(h.ptr, C.byref(b), init.ctypes.data, init.shape[1], init.shape[1], C.byref(y), band,
-                                     out.ctypes.data))
+    if wide:
+        h.set_crf_lattice_wide(True)
+    try:
+        h.check(h.lib.fcd_crf_score_host(h.ptr, C.byref(b), init.ctypes.data, init.shape[1], init.shape[1], C.byref(y), band,
+                                         out.ctypes.data))
+    finally:
+        if wide:
+            h.set_crf_lattice_wide(False)
     return out
 
 
@@ -2458,7 +2479,7 @@ def _occupancy_block(out, shape5, elem_strides):
 
 def crf_occupancy_batch_raw(network_outputs, init_states, labels, label_lengths, lengths=None, paths=None, band=0,
                             n_valid=None, out=None, scale=1.0, accumulate=False, time_major_out=False, input_dtype=None,
-                            handle=None):
+                            handle=None, wide=False):
     """The edge occupancies of every labelling's own lattice under the CRF model: occupancy[b][i][t][s][a] is the
     probability, over the alignments of labelling (b, i) to its read, that the model leaves state s by symbol a at row t
     -- a soft alignment, and the labelled counterpart of crf_marginals_batch_raw's marginals: for raw
@@ -2471,6 +2492,9 @@ def crf_occupancy_batch_raw(network_outputs, init_states, labels, label_lengths,
     return occupancies that do not add up (include/fcd.h has the rule and the measured range).
 
     Arguments as crf_score_batch_raw; any S it takes, N - 1 <= 8, windows up to 512 states, S * N up to about 39800.
+    wide=True lifts the window's limit (include/fcd.h, fcd_set_crf_lattice_wide): up to 4096 states, walked in LDS beyond
+    512 -- the labelling, the tile, the window's three rows and the S * N row within 160 KiB -- to the same bounds with
+    ceil(states / 64) states per lane; a window within 512 states runs the same launches as wide=False.
     out: a float32 buffer of that shape (or (B, T, S, N) when n_hyp is 1) with dense (S, N) rows, written in place and
     returned; required with accumulate=True.  The call writes scale * occupancy, or adds it to what `out` holds with
     accumulate=True.  Rows at and beyond lengths[b], the blocks of labellings without a positive finite probability and
@@ -2500,8 +2524,14 @@ def crf_occupancy_batch_raw(network_outputs, init_states, labels, label_lengths,
         sr, stt = _occupancy_block(occ, shape5, occ.stride())
         logp = torch.empty((B, n_hyp), dtype=torch.float64, device=dev)
         o = nat.Occupancy(occ.data_ptr(), sr, stt, float(scale), int(bool(accumulate)), logp.data_ptr())
-        h.check(h.lib.fcd_crf_occupancy_dev(h.ptr, C.byref(b), C.c_void_p(init.data_ptr()), int(init.shape[1]),
-                                            int(init.shape[1]), C.byref(y), band, C.byref(o)))
+        if wide:  # (the handle is this thread's: nothing else calls between the switch and the call)
+            h.set_crf_lattice_wide(True)
+        try:
+            h.check(h.lib.fcd_crf_occupancy_dev(h.ptr, C.byref(b), C.c_void_p(init.data_ptr()), int(init.shape[1]),
+                                                int(init.shape[1]), C.byref(y), band, C.byref(o)))
+        finally:
+            if wide:
+                h.set_crf_lattice_wide(False)
         h.hold_in_flight(occ, logp, *keep)
         return OccupancyResult(occ, logp)
     if out is None:
@@ -2514,8 +2544,14 @@ def crf_occupancy_batch_raw(network_outputs, init_states, labels, label_lengths,
     sr, stt = _occupancy_block(occ, shape5, tuple(v // 4 for v in occ.strides))
     logp = np.empty((B, n_hyp), np.float64)
     o = nat.Occupancy(occ.ctypes.data, sr, stt, float(scale), int(bool(accumulate)), logp.ctypes.data)
-    h.check(h.lib.fcd_crf_occupancy_host(h.ptr, C.byref(b), init.ctypes.data, init.shape[1], init.shape[1], C.byref(y), band,
-                                         C.byref(o)))
+    if wide:
+        h.set_crf_lattice_wide(True)
+    try:
+        h.check(h.lib.fcd_crf_occupancy_host(h.ptr, C.byref(b), init.ctypes.data, init.shape[1], init.shape[1], C.byref(y), band,
+                                             C.byref(o)))
+    finally:
+        if wide:
+            h.set_crf_lattice_wide(False)
     return OccupancyResult(occ, logp)
 
 
@@ -2719,11 +2755,12 @@ def _crf_one_read(network_output, init_state, sequence, alphabet, what):
     return _dense(x)[None], np.ascontiguousarray(init)[None], lab, np.array([len(y)], np.uint32), len(y)
 
 
-def crf_score(network_output, init_state, sequence, alphabet):
+def crf_score(network_output, init_state, sequence, alphabet, wide=False):
     """ln P(sequence | network_output) under the CRF model: every alignment of one string (as crf_beam_search returns
-    it) to one (T, S, N) float32 posterior array, exact, as a float.  More than 511 labels: RuntimeError."""
+    it) to one (T, S, N) float32 posterior array, exact, as a float.  More than 511 labels: RuntimeError -- unless
+    wide=True (crf_score_batch_raw: up to 4095 rows or labels)."""
     x, init, lab, n, _ = _crf_one_read(network_output, init_state, sequence, alphabet, "crf_score")
-    return float(crf_score_batch_raw(x, init, lab, n)[0, 0])
+    return float(crf_score_batch_raw(x, init, lab, n, wide=wide)[0, 0])
 
 
 def crf_align(network_output, init_state, sequence, alphabet):
@@ -2757,14 +2794,14 @@ def crf_edits(network_output, init_state, sequence, alphabet):
     return r.deletion[0, 0, :L].copy(), r.insertion[0, 0, :L + 1].copy(), float(r.logp[0, 0])
 
 
-def crf_occupancy(network_output, init_state, sequence, alphabet):
+def crf_occupancy(network_output, init_state, sequence, alphabet, wide=False):
     """The edge occupancies of one string (as crf_beam_search returns it) against one (T, S, N) float32 posterior array
     under the CRF model, exact lattice: -> (occupancy, logp) with occupancy a (T, S, N) float32 array (entry [t][s][a]: the
     probability, over the string's alignments, of leaving state s by alphabet[a] at row t; every row sums to 1) and logp =
     ln P(sequence | network_output).  RuntimeError where the string has no alignment of positive finite probability.
-    Argument checks as crf_score."""
+    Argument checks as crf_score; wide as crf_occupancy_batch_raw -- strings beyond 511 rows or characters."""
     x, init, lab, n, _ = _crf_one_read(network_output, init_state, sequence, alphabet, "crf_occupancy")
-    r = crf_occupancy_batch_raw(x, init, lab, n)
+    r = crf_occupancy_batch_raw(x, init, lab, n, wide=wide)
     logp = float(r.logp[0, 0])
     if not np.isfinite(logp):
         raise RuntimeError("crf_occupancy: the sequence has no alignment of positive finite probability (ln P = %r)" % logp)

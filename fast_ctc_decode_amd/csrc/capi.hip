@@ -863,6 +863,13 @@ int fcd_set_ctc_occupancy_wide(fcd_handle *h, int on) {
     return FCD_OK;
 }
 
+int fcd_set_crf_lattice_wide(fcd_handle *h, int on) {
+    if (!h || (on != 0 && on != 1)) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> g(h->mu);
+    h->crf_wide = on != 0;
+    return FCD_OK;
+}
+
 int fcd_release_workspace(fcd_handle *h) {
     if (!h) return FCD_E_INVALID;
     std::lock_guard<std::recursive_mutex> g(h->mu);
@@ -1936,7 +1943,15 @@ struct LatticeCall {
     bool occupancy = false;
     const fcd_occupancy *occ = nullptr;
     bool wide = false;  // (CTC occupancy) fcd_set_ctc_occupancy_wide: windows beyond the registers walk score_lds_kernel
+    bool crf_wide = false;  // (CRF score, occupancy) fcd_set_crf_lattice_wide: windows beyond 512 states walk in LDS
 };
+
+// the call is one of those the CRF switch covers AND its window is beyond the registers: every other call is what it is
+// with the switch off (in and y checked by then)
+bool crf_wide_call(const LatticeCall &c) {
+    return c.crf && c.crf_wide && !c.align && !c.posterior && !c.edit &&
+           crf_lattice_is_wide(c.in->T, c.y->stride, std::min<int64_t>(c.band, 1ll << 28));
+}
 
 // floats from the first to the last element the call may address in out->occ (0: none)
 size_t occupancy_span(const fcd_batch *in, const fcd_labellings *y, const fcd_occupancy *o) {
@@ -1972,7 +1987,20 @@ int lattice_check(fcd_handle *h, const LatticeCall &c) {
                                       : c.align ? "null labels/len/start" : "null labels/len/logp");
     if (c.edit && in->n_reads > 0 && !c.edits->insertion) return fail(h, FCD_E_INVALID, c.crf ? "crf_edits: null insertion" : "ctc_edits: null insertion");
     if (in->n_reads * y->n_hyp >= (1ll << 31)) return fail(h, FCD_E_UNSUPPORTED, "more than 2^31 labellings in one call");
-    if (c.crf) {
+    if (c.crf && crf_wide_call(c)) {
+        const std::string who = c.occupancy ? "crf_occupancy_wide" : "crf_score_wide";
+        size_t lds = 0;
+        switch (crf_lattice_wide_unsupported(in->T, in->S, in->N, y->stride, std::min<int64_t>(c.band, 1ll << 28), c.occupancy, &lds)) {
+        case 1: return fail(h, FCD_E_UNSUPPORTED, (who + (c.band > 0 ? ": the band's window exceeds the 4096 states of 64 cells per lane: use a narrower band"
+                                                                     : ": the exact lattice exceeds the 4096 states of 64 cells per lane: use a band")).c_str());
+        case 2: return fail(h, FCD_E_UNSUPPORTED, (who + ": more than 8 labels besides the blank").c_str());
+        case 3: return fail(h, FCD_E_UNSUPPORTED, (who + ": S must be below 2^24 - 1").c_str());
+        case 4: return fail(h, FCD_E_UNSUPPORTED, (who + ": the labelling, the tile, the window's three rows" + (c.occupancy ? " and the S * N accumulation row" : "") +
+                                                   " do not fit the 160 KiB of LDS (4 (min(T, stride) + 1) + 4480 + 768 ceil(states / 64)" +
+                                                   (c.occupancy ? " + 4 S N" : "") + " = " + std::to_string(lds) + " bytes): use a band or a smaller stride").c_str());
+        default: break;
+        }
+    } else if (c.crf) {
         switch (crf_lattice_unsupported(in->T, in->S, y->stride, std::min<int64_t>(c.band, 1ll << 28))) {
         case 1: return fail(h, FCD_E_UNSUPPORTED, c.band > 0 ? "crf lattice: the band's window exceeds 512 states: use a narrower band"
                                                              : "crf lattice: the exact lattice exceeds 512 states: use a band");
@@ -1997,7 +2025,8 @@ int lattice_check(fcd_handle *h, const LatticeCall &c) {
                 return fail(h, FCD_E_INVALID, (occ_who + ": the labellings' blocks overlap (stride_row, stride_t)").c_str());
         }
     }
-    if (c.occupancy && c.crf) {
+    if (c.occupancy && c.crf && crf_wide_call(c)) {  // (its limits: above)
+    } else if (c.occupancy && c.crf) {
         switch (crf_occupancy_unsupported(in->T, in->S, in->N, y->stride)) {
         case 2: return fail(h, FCD_E_UNSUPPORTED, "crf_occupancy: more than 8 labels besides the blank");
         case 6: return fail(h, FCD_E_UNSUPPORTED, "crf_occupancy: the labelling and the S * N accumulation row do not fit the 160 KiB "
@@ -2063,7 +2092,9 @@ int lattice_score(fcd_handle *h, const LatticeCall &c) {
     const ScoreDesc yd{y->labels, y->len, y->n_valid, c.band > 0 ? y->path : nullptr, y->n_hyp, y->stride};
     const int64_t bnd = std::min<int64_t>(c.band, 1ll << 28);
     sc.time();
-    if (c.crf)
+    if (c.crf && crf_wide_call(c))
+        FCD_HIP(h, launch_crf_score_wide(to_desc(in, true), yd, c.init, c.n_init, c.init_stride, bnd, c.logp, sc.stream));
+    else if (c.crf)
         FCD_HIP(h, launch_crf_score(to_desc(in, true), yd, c.init, c.n_init, c.init_stride, bnd, c.logp, sc.stream));
     else
         FCD_HIP(h, launch_ctc_score(to_desc(in, false), yd, c.collapse, bnd, c.logp, sc.stream));
@@ -2178,7 +2209,9 @@ int lattice_occupancy(fcd_handle *h, const LatticeCall &c) {
     const fcd_occupancy *out = c.occ;
     const int64_t bnd = std::min<int64_t>(c.band, 1ll << 28);
     // (the CTC kernels size their rows by the band as given, the CRF kernels by the band the launch gets)
-    const size_t row_bytes = c.crf    ? crf_occupancy_row_bytes(in->T, y->stride, bnd)
+    const bool crf_wide = crf_wide_call(c);
+    const size_t row_bytes = crf_wide ? crf_lattice_wide_row_bytes(in->T, y->stride, bnd)
+                             : c.crf  ? crf_occupancy_row_bytes(in->T, y->stride, bnd)
                              : c.wide ? ctc_occupancy_wide_row_bytes(in->T, y->stride, c.band)
                                       : ctc_posterior_row_bytes(in->T, y->stride, c.band);
     return lattice_grouped(
@@ -2186,7 +2219,8 @@ int lattice_occupancy(fcd_handle *h, const LatticeCall &c) {
         [&](CallScope &sc) { sc.add(out->occ, occupancy_span(in, y, out) * 4); },
         [&](const BatchDesc &d, const ScoreDesc &yd, int64_t r0, int64_t row0, double *logp, unsigned char *alpha, hipStream_t stream) {
             const OccupancyDesc od{out->occ + row0 * out->stride_row, out->stride_row, out->stride_t, out->scale, out->accumulate};
-            return c.crf ? launch_crf_occupancy(d, yd, c.init + r0 * c.init_stride, c.n_init, c.init_stride, bnd, od, logp, alpha, stream)
+            return crf_wide ? launch_crf_occupancy_wide(d, yd, c.init + r0 * c.init_stride, c.n_init, c.init_stride, bnd, od, logp, alpha, stream)
+                   : c.crf  ? launch_crf_occupancy(d, yd, c.init + r0 * c.init_stride, c.n_init, c.init_stride, bnd, od, logp, alpha, stream)
                          : c.wide ? launch_ctc_occupancy_wide(d, yd, c.collapse, bnd, od, logp, alpha, stream)
                                   : launch_ctc_occupancy(d, yd, c.collapse, bnd, od, logp, alpha, stream);
         });
@@ -2333,14 +2367,18 @@ int fcd_crf_score_dev(fcd_handle *h, const fcd_batch *in, const float *init, int
                       const fcd_labellings *y, int64_t band, double *logp) {
     if (!h) return FCD_E_INVALID;
     std::lock_guard<std::recursive_mutex> g(h->mu);
-    return lattice_dev(h, LatticeCall{true, false, in, y, band, 0, init, n_init, init_stride, logp, nullptr});
+    LatticeCall c{true, false, in, y, band, 0, init, n_init, init_stride, logp, nullptr};
+    c.crf_wide = h->crf_wide;
+    return lattice_dev(h, c);
 }
 
 int fcd_crf_score_host(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init, int64_t init_stride,
                        const fcd_labellings *y, int64_t band, double *logp) {
     if (!h) return FCD_E_INVALID;
     std::lock_guard<std::recursive_mutex> whole_call(h->mu);  // staging .. copy-back, see run_host
-    return lattice_host(h, LatticeCall{true, false, in, y, band, 0, init, n_init, init_stride, logp, nullptr});
+    LatticeCall c{true, false, in, y, band, 0, init, n_init, init_stride, logp, nullptr};
+    c.crf_wide = h->crf_wide;
+    return lattice_host(h, c);
 }
 
 int fcd_crf_align_dev(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init, int64_t init_stride,
@@ -2391,6 +2429,7 @@ int fcd_crf_occupancy_dev(fcd_handle *h, const fcd_batch *in, const float *init,
     std::lock_guard<std::recursive_mutex> g(h->mu);
     LatticeCall c{true, false, in, y, band, 0, init, n_init, init_stride, nullptr, nullptr};
     c.occupancy = true;
+    c.crf_wide = h->crf_wide;
     c.occ = out;
     return lattice_dev(h, c);
 }
@@ -2401,6 +2440,7 @@ int fcd_crf_occupancy_host(fcd_handle *h, const fcd_batch *in, const float *init
     std::lock_guard<std::recursive_mutex> whole_call(h->mu);  // staging .. copy-back, see run_host
     LatticeCall c{true, false, in, y, band, 0, init, n_init, init_stride, nullptr, nullptr};
     c.occupancy = true;
+    c.crf_wide = h->crf_wide;
     c.occ = out;
     return lattice_host(h, c);
 }

@@ -2,7 +2,8 @@
 // sum and best alignment) and crf_posterior.hip (forward and backward).  Parameter block, LDS layout, everything before
 // the time loop (the rows without a value, the labelling and its state trajectory), the staging of the posteriors, the
 // live window of a row, what a lane reads for one forward row -- and the FORWARD WALK itself (crf_forward_walk: sum, max
-// with back-pointer ballots, sum with stored rows).  What this lattice has in common with the CTC one (k(t), the rotations,
+// with back-pointer ballots, sum with stored rows) and its twin for a window that lives in LDS (crf_forward_walk_lds: beyond
+// 512 states, sum and stored rows).  What this lattice has in common with the CTC one (k(t), the rotations,
 // ln P, the stored rows, the backward walks' stores) is ctc_lattice.h's.  Included by those translation units only.
 #pragma once
 
@@ -327,6 +328,130 @@ __device__ __forceinline__ float crf_forward_walk(const CrfParams &p, const CrfL
     __syncthreads();
     *eacc_out = eacc;
     return __int_as_float(lds.misc[18]);
+}
+
+// ---- the LDS-resident window: J = 9 .. 64 states per lane, state k in slot k mod 64J, lane l owns slots lJ .. lJ + J - 1 ----
+// (fcd_set_crf_lattice_wide of include/fcd.h: windows beyond the 512 states eight registers per lane hold).  Three rows of
+// 64J words behind what the launch's other users of LDS take: the cells, the advance products, the packed exponents.  A
+// slot's word sits at (slot mod J) * 64 + slot / J in its row -- a lane's J cells are 64 words apart, so the 64 lanes of one
+// access touch 64 consecutive words -- and the stored rows of the workspace keep that order.
+struct CrfWideLds {
+    float *cell;    // alpha (forward), beta (backward) of the state each slot holds; between a row's two passes the stay products
+    float *up;      // the products that leave their slot: the advance products (forward), beta[s + 1] P(u, s, y_s) (backward)
+    uint32_t *exp;  // per slot: both products' posterior exponents, and the occupancy walk's two "a term was added" bits
+};
+
+__device__ __forceinline__ CrfWideLds crf_wide_carve(void *behind, int J) {
+    CrfWideLds w;
+    w.cell = reinterpret_cast<float *>(behind);
+    w.up = w.cell + 64 * J;
+    w.exp = reinterpret_cast<uint32_t *>(w.up + 64 * J);
+    return w;
+}
+
+inline size_t crf_wide_lds_bytes(int J) { return (size_t)3 * 64 * (size_t)J * 4; }
+
+__device__ __forceinline__ int crf_wide_at(int lane, int j) { return j * 64 + lane; }
+
+__device__ __forceinline__ int crf_wide_state(int slot, int lo, int C) {  // the state >= lo that lives in the slot
+    const int s = lo / C * C + slot;
+    return s < lo ? s + C : s;
+}
+
+// the exponents of a split posterior lie in -148 .. 128 (0 for a value that is not finite): nine bits each, biased by 256
+__device__ __forceinline__ uint32_t crf_wide_pack(int e0, int ey) { return (uint32_t)(e0 + 256) | ((uint32_t)(ey + 256) << 9); }
+__device__ __forceinline__ int crf_wide_e0(uint32_t w) { return (int)(w & 511u) - 256; }
+__device__ __forceinline__ int crf_wide_ey(uint32_t w) { return (int)((w >> 9) & 511u) - 256; }
+
+// crf_forward_walk for such a window, kCrfSum and kCrfStore: the same products, the same exponent and the same sum per cell,
+// so the same numerics.  A row is two passes over the lane's J cells.  The first forms both products of the state each slot
+// held in the previous row, leaves the stay product in the cell, the advance product in `up` and takes the row's largest
+// exponent; the second rescales and adds its own stay product and the advance product of the slot below -- the alpha row is
+// updated IN PLACE, and what a lane reads of its neighbour (the top slot's advance product) is in a row the second pass only
+// reads.  Posteriors: from the staged tile, or (S * N beyond it) gathered from global memory as the first pass needs them.
+// Stored rows: T * 64J cells, a slot's at crf_wide_at, scaled by 2^-kAlphaDown, then T exponent words -- stored_rows_bytes(T, J).
+// kCrfStore with a null `am` stores nothing, decided at run time: crfp_fwd_kernel<8> compiles this one body for both of its
+// uses (half the cold code next to its register walk); kCrfSum is the same decision at compile time.
+template <int MODE>
+__device__ __forceinline__ float crf_forward_walk_lds(const CrfParams &p, const CrfLds &lds, const CrfRow &rw, const CrfWideLds &w,
+                                                      int J, float *am, int *ae, int64_t *eacc_out) {
+    static_assert(MODE == kCrfSum || MODE == kCrfStore, "the best alignment keeps its 512 states");
+    const int C = 64 * J;
+    const int lane = threadIdx.x;
+    const int SN = p.in.S * p.in.N;
+    for (int j = 0; j < J; ++j) w.cell[crf_wide_at(lane, j)] = 0.0f;
+    if (lane == 0) w.cell[0] = 1.0f;  // "row -1": state 0, the one live state
+    int64_t eacc = 0;
+    int lo = 0, hi = 0;  // the window of the previous row
+    for (int t0 = 0; t0 < rw.Tr; t0 += p.rows_per_tile) {
+        const int rc = min(p.rows_per_tile, rw.Tr - t0);
+        crf_fill_tile(p, lds, rw, t0, rc);
+        for (int i = 0; i < rc; ++i) {
+            const int t = t0 + i;
+            int lo_t, hi_t;
+            crf_window(p, lds, rw, t, i, &lo_t, &hi_t);
+            int emax = kNoExp;
+            for (int j = 0; j < J; ++j) {
+                const int at = crf_wide_at(lane, j);
+                const int kp = crf_wide_state(lane * J + j, lo, C);
+                const bool src = kp <= hi;
+                const uint32_t info = lds.info[src ? kp : 0];  // (a dead slot reads a valid address and is masked below)
+                const uint32_t sig = info & 0xFFFFFFu, y = info >> 24;
+                const bool table = sig != kNoState;
+                const bool stay = src && kp >= lo_t && kp <= hi_t;
+                const bool adv = src && kp < rw.L && kp + 1 >= lo_t && kp + 1 <= hi_t;
+                float v0 = 0.0f, vy = 0.0f;  // (a state outside the table reads 0, as in crf_load_step)
+                if (p.staged) {
+                    const int base = i * SN + (int)(table ? sig : 0u) * p.in.N;
+                    if (stay && table) v0 = lds.tile[base];
+                    if (adv && table) vy = lds.tile[base + (int)y];
+                } else {
+                    const int64_t base = (int64_t)t * p.in.stride_t + (int64_t)(table ? sig : 0u) * p.in.stride_s;
+                    if (stay && table) v0 = load_post(rw.post, base, p.in.dtype);
+                    if (adv && table) vy = load_post(rw.post, base + (int64_t)y * p.in.stride_n, p.in.dtype);
+                }
+                float m0, my;
+                int e0, ey;
+                crf_split(v0, &m0, &e0);
+                crf_split(vy, &my, &ey);
+                const float a = w.cell[at];
+                const float s = stay ? a * m0 : 0.0f;
+                const float v = adv ? a * my : 0.0f;
+                const int x0 = finite_exp(s), x1 = finite_exp(v);
+                emax = max(emax, x0 != kNoExp ? x0 + e0 : kNoExp);
+                emax = max(emax, x1 != kNoExp ? x1 + ey : kNoExp);
+                w.cell[at] = s;
+                w.up[at] = v;
+                w.exp[at] = crf_wide_pack(e0, ey);
+            }
+            emax = wave_imax(emax);
+            const int sh = emax == kNoExp ? 0 : kTarget - emax;
+            eacc -= sh;
+            __syncthreads();  // every advance product is in its slot
+            float *row = MODE == kCrfStore && am ? am + (int64_t)t * C : nullptr;
+            // the slot below the lane's first: the previous lane's top (lane 0: the top slot of the window)
+            int below = crf_wide_at((lane + 63) & 63, J - 1);
+            for (int j = 0; j < J; ++j) {
+                const int at = crf_wide_at(lane, j);
+                const float c0 = ldexpf(w.cell[at], min(max(crf_wide_e0(w.exp[at]) + sh, -512), 512));
+                const float c1 = ldexpf(w.up[below], min(max(crf_wide_ey(w.exp[below]) + sh, -512), 512));
+                const float a = c0 + c1;
+                w.cell[at] = a;
+                if (MODE == kCrfStore && am) row[at] = ldexpf(a, -kAlphaDown);
+                below = at;
+            }
+            if (MODE == kCrfStore && am) {
+                if (lane == 0) ae[t] = (int)(eacc + kAlphaDown);
+            }
+            lo = lo_t;
+            hi = hi_t;
+            __syncthreads();  // ... and read before the next row writes over it
+        }
+    }
+    const int slot = rw.L % C;
+    const float last = (rw.L >= lo && rw.L <= hi) ? w.cell[crf_wide_at(slot / J, slot % J)] : 0.0f;  // (every lane reads the one word)
+    *eacc_out = eacc;
+    return last;
 }
 
 CrfParams crf_params(const BatchDesc &in, const ScoreDesc &y, const float *init, int64_t n_init, int64_t init_stride,

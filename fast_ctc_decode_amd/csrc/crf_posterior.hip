@@ -38,6 +38,11 @@
 // fcd_crf_occupancy_* (the edge occupancies of the labelling's own lattice) is the forward launch at crf_lattice.hip's K and a
 // fourth walk, crfp_occ_walk below, compiled into crfp_back_kernel<K, 2, 4> only: beta alone, no chains, any S.
 //
+// fcd_set_crf_lattice_wide (windows beyond 512 states, for the forward sum and the occupancies): the window lives in LDS, J =
+// 9 .. 64 states per lane, and two more loop bodies walk it -- crf_forward_walk_lds of crf_lattice.h inside crfp_fwd_kernel<8>
+// (alpha null: the sum alone, fcd_crf_score_*) and crfp_occ_walk_lds below inside crfp_back_kernel<8, 2, 4> -- selected by the
+// wave-uniform q.wide_j.  No instantiation of their own; the other instantiations do not compile them.
+//
 // Scales.  beta and every V share one integer exponent per row.  The step is two passes over the row's posteriors: the
 // first takes only exponents -- the largest frexp(old) + frexp(posterior) over every product of the row, E, reduced as an
 // integer (wave_imax); a product is below 2^E and the largest at least 2^(E-2), so with every product rescaled by the exact
@@ -76,14 +81,50 @@ struct CrfPostParams {
     int64_t occ_stride_row, occ_stride_t;
     float occ_scale;
     int occ_clear;  // accumulate = 0: rows t < T_r of a labelling with a value are zeroed before the walk adds to them
+    // (fcd_set_crf_lattice_wide) states per lane of a window that lives in LDS, 9 .. 64; 0: the register-resident walks.
+    // Read by crfp_fwd_kernel<8> and crfp_back_kernel<8, 2, 4> only.  With it a null alpha is "sum only": the wide crf_score
+    int wide_j;
 };
 constexpr int kWalkSub = 0, kWalkIns = 1, kWalkDel = 2, kWalkOcc = 3;
 
+// ---- the LDS-resident walks share nothing with the register walks of their kernels ----
+// Inlined next to a register walk, a wide walk that reads the same parameter block keeps the block's scalar registers live
+// across both, and the allocator then spills the register walk's own (4.2 % on the gathered
+// occupancy call).  So a wide walk is entered by one wave-uniform branch ahead of everything the register walk computes, runs
+// the prologue for itself, and reads the parameter block AGAIN, through the kernarg segment's pointer -- the block is the
+// kernels' one argument -- with scalar loads of its own: no value is live in both paths.  (The emulator has no kernarg
+// segment and no registers: there it is the block the kernel was handed.)
+__device__ __forceinline__ const CrfPostParams &crfp_params_again(const CrfPostParams &q) {
+#ifdef FCD_HIPEMU
+    return q;
+#else
+    return *(const CrfPostParams *)__builtin_amdgcn_kernarg_segment_ptr();
+#endif
+}
+
 // ---- pass 1: crf_lattice.hip's forward sum, storing what it computes (crf_forward_walk of crf_lattice.h) ----
 template <int K>
-__global__ __launch_bounds__(64) void crfp_fwd_kernel(CrfPostParams q) {
+__global__ __launch_bounds__(64) void crfp_fwd_kernel(CrfPostParams q0) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int C = 64 * K;
+    if constexpr (K == 8) {  // (the one instantiation that hosts the LDS-resident window: wave-uniform)
+        if (q0.wide_j > 0) {
+            const CrfPostParams &q = crfp_params_again(q0);
+            const CrfParams &p = q.c;
+            const CrfLds lds = crf_carve(smem);
+            CrfRow rw;
+            if (!crf_prologue(p, lds, &rw)) return;
+            const int J = q.wide_j;
+            const CrfWideLds w = crf_wide_carve(lds.info + p.lab_cap, J);
+            int64_t eacc;
+            float *am = q.alpha ? q.alpha + (int64_t)blockIdx.x * q.alpha_words : nullptr;  // (null: the sum alone)
+            int *ae = am ? reinterpret_cast<int *>(am + (int64_t)p.in.T * 64 * J) : nullptr;
+            const float m = crf_forward_walk_lds<kCrfStore>(p, lds, rw, w, J, am, ae, &eacc);
+            if (threadIdx.x == 0) p.logp[blockIdx.x] = ln_p((double)m, eacc);
+            return;
+        }
+    }
+    const CrfPostParams &q = q0;
     const CrfParams &p = q.c;
     const CrfLds lds = crf_carve(smem);
     CrfRow rw;
@@ -621,9 +662,149 @@ __device__ __forceinline__ void crfp_occ_walk(const CrfPostParams &q, unsigned c
     }
 }
 
+// The same walk for a window that lives in LDS (fcd_set_crf_lattice_wide; crf_lattice.h has the layout): J = q.wide_j states
+// per lane, compiled into crfp_back_kernel<8, 2, 4> only.  The terms, their roundings, the S * N row and its add-then-exchange,
+// the give-up rule and everything around the time loop are crfp_occ_walk's.  A step is two passes over the lane's J cells.
+// The first reads beta_u -- the lane's own cells in ascending order, the slot above its last one (the next lane's first)
+// ahead of the loop, before that lane writes over it --, adds the terms to their entries and to the row's mass (lane-serial,
+// in slot order; then wave_fsum: 2 J + 6 roundings, lost(T_r) with J in K's place) and leaves both products of beta_{u-1} and
+// their exponents where crf_forward_walk_lds leaves its own; the second rescales and adds them into the cell.  The bits "a
+// term went into the entry" ride with the exponents to the exchange.
+constexpr uint32_t kWideStay = 1u << 18, kWideAdv = 1u << 19;
+
+__device__ __forceinline__ void crfp_occ_walk_lds(const CrfPostParams &q, unsigned char *smem) {
+    const CrfParams &p = q.c;
+    const int J = q.wide_j, C = 64 * J;
+    const CrfLds lds = crf_carve(smem);
+    float *sum = reinterpret_cast<float *>(lds.info + p.lab_cap);  // [S * N], behind crf_lds_bytes(lab_cap)
+    CrfRow rw;
+    if (!crf_prologue(p, lds, &rw)) return;
+    const double lp = p.logp[blockIdx.x];
+    if (lp - lp != 0.0) return;  // P = 0, or a NaN on the way: nothing of the block is written
+    const int lane = threadIdx.x, L = rw.L, N = p.in.N, SN = p.in.S * N;
+    const CrfWideLds w = crf_wide_carve(sum + SN, J);
+    float *out = q.occ + (int64_t)blockIdx.x * q.occ_stride_row;
+    for (int e = lane; e < SN; e += 64) sum[e] = 0.0f;
+    if (q.occ_clear) {
+        if (q.occ_stride_t == (int64_t)SN) {
+            for (int64_t e = lane; e < (int64_t)rw.Tr * SN; e += 64) out[e] = 0.0f;
+        } else {
+            for (int t = 0; t < rw.Tr; ++t)
+                for (int e = lane; e < SN; e += 64) out[(int64_t)t * q.occ_stride_t + e] = 0.0f;
+        }
+    }
+    const float *am = q.alpha + (int64_t)blockIdx.x * q.alpha_words;
+    const int *ae = reinterpret_cast<const int *>(am + (int64_t)p.in.T * C);
+    int64_t eb = 0;
+    const int64_t xp = (int64_t)floor(lp * 1.44269504088896340735992468100189214);  // floor(log2 P(y | x))
+    const float pman = (float)exp(lp - (double)xp * kLn2);                          // P / 2^xp, in [1, 2]
+    const float lost = 2.0f * (6.0f * (float)rw.Tr + (float)(C + 2 * J + 8)) * 5.9604644775390625e-8f;  // kOccLost(T_r)
+    bool first = true;
+    for (int t0 = (rw.Tr - 1) / p.rows_per_tile * p.rows_per_tile; t0 >= 0; t0 -= p.rows_per_tile) {
+        const int rc = min(p.rows_per_tile, rw.Tr - t0);
+        crf_fill_tile(p, lds, rw, t0, rc);  // (its barriers: the zeros above are in place before a lane adds to them)
+        stage_krow_before(lds.misc, rw.path, L, p.band, t0);  // the window of the row before the tile
+        for (int i = rc - 1; i >= 0; --i) {
+            const int u = t0 + i;
+            int lo_u, hi_u;  // the window of row u: the states whose beta the cells hold
+            crf_window(p, lds, rw, u, i, &lo_u, &hi_u);
+            int lo_p = 0, hi_p = 0;  // the window of row u - 1 ("row -1": state 0): the states the terms leave from
+            int64_t x_u = 0;
+            if (u > 0) {
+                crf_window_k(p, rw, u - 1, krow_before(lds.krow, lds.misc, p.band, i), &lo_p, &hi_p);
+                x_u = ae[u - 1];
+            }
+            const float *arow = am + (int64_t)max(u - 1, 0) * C;  // alpha_{u-1}, a slot's at crf_wide_at
+            if (first) {  // row T_r - 1: state L
+                for (int j = 0; j < J; ++j) w.cell[crf_wide_at(lane, j)] = crf_wide_state(lane * J + j, lo_u, C) == L ? 1.0f : 0.0f;
+                first = false;
+                __syncthreads();
+            }
+            x_u += eb;  // the exponent of this step's terms: alpha of row u - 1 times beta of row u
+            const int dt = (int)min(max(x_u - xp, (int64_t)-(1 << 20)), (int64_t)(1 << 20));
+            // ---- the occupancies of row u, the products of beta of row u - 1 and the largest of their exponents ----
+            const float nb0 = w.cell[crf_wide_at((lane + 1) & 63, 0)];  // the next lane's first slot, as it stands at row u
+            __syncthreads();                                            // ... read before that lane's first pass writes it
+            int emax = kNoExp;
+            float mass = 0.0f;
+            float b_own = w.cell[crf_wide_at(lane, 0)];
+            for (int j = 0; j < J; ++j) {
+                const int at = crf_wide_at(lane, j);
+                const float b_up = j + 1 < J ? w.cell[crf_wide_at(lane, j + 1 < J ? j + 1 : 0)] : nb0;
+                const int s = crf_wide_state(lane * J + j, lo_p, C);
+                const bool live = s <= hi_p;
+                const bool own = live && s >= lo_u && s <= hi_u;          // state s holds a value at row u
+                const bool nxt = live && s + 1 >= lo_u && s + 1 <= hi_u;  // state s + 1 does (s < L: hi_u <= L)
+                const uint32_t info = lds.info[live ? s : 0];  // (a dead slot reads a valid address and is masked below)
+                const uint32_t sg = info & 0xFFFFFFu;
+                const bool table = sg != kNoState;
+                const int sig = table ? (int)sg : 0;
+                const int ys = (int)(info >> 24), ent = sig * N;
+                const float bo = own ? b_own : 0.0f;
+                const float bn = nxt ? b_up : 0.0f;
+                const float p0 = (own && table) ? crf_post_value(p, lds, rw, u, i, sig, 0) : 0.0f;
+                const float py = (nxt && table) ? crf_post_value(p, lds, rw, u, i, sig, ys) : 0.0f;
+                const float av = u > 0 ? (live ? arow[at] : 0.0f) : 1.0f;  // ("row -1": state 0, the one live state, holds 1)
+                emax = max(emax, crf_term_exp(bo, p0));
+                emax = max(emax, crf_term_exp(bn, py));
+                float m0, my;
+                int e0, ey;
+                crf_split(p0, &m0, &e0);
+                crf_split(py, &my, &ey);
+                const float stay = ldexpf((av * m0) * bo, min(max(dt + e0, -512), 512)) / pman;
+                const float adv = ldexpf((av * my) * bn, min(max(dt + ey, -512), 512)) / pman;
+                mass += stay + adv;
+                if (stay > 0.0f) atomicAdd(&sum[ent], stay);
+                if (adv > 0.0f) atomicAdd(&sum[ent + ys], adv);
+                w.cell[at] = bo * m0;  // (crf_term's mantissa products; the power of two waits for the row's exponent)
+                w.up[at] = bn * my;
+                w.exp[at] = crf_wide_pack(e0, ey) | (stay > 0.0f ? kWideStay : 0u) | (adv > 0.0f ? kWideAdv : 0u);
+                b_own = b_up;
+            }
+            emax = wave_imax(emax);
+            const int sh = emax == kNoExp ? 0 : kTargetB - emax;
+            eb -= sh;
+            mass = wave_fsum(mass);
+            if (!(fabsf(mass - 1.0f) <= lost)) {  // (wave-uniform) the rows cannot hold this lattice
+                __syncthreads();
+                for (int t = 0; t < rw.Tr; ++t)
+                    for (int e = lane; e < SN; e += 64) out[(int64_t)t * q.occ_stride_t + e] = NAN;
+                if (lane == 0) p.logp[blockIdx.x] = (double)NAN;
+                return;
+            }
+            __syncthreads();  // every term of the row is in its entry
+            float *orow = out + (int64_t)u * q.occ_stride_t;
+            for (int j = 0; j < J; ++j) {
+                const int at = crf_wide_at(lane, j);
+                const uint32_t word = w.exp[at];
+                w.cell[at] = ldexpf(w.cell[at], min(max(crf_wide_e0(word) + sh, -512), 512)) +
+                             ldexpf(w.up[at], min(max(crf_wide_ey(word) + sh, -512), 512));  // beta of row u - 1
+                if (word & (kWideStay | kWideAdv)) {
+                    const int s = crf_wide_state(lane * J + j, lo_p, C);
+                    const uint32_t info = lds.info[s <= hi_p ? s : 0];
+                    const uint32_t sg = info & 0xFFFFFFu;
+                    const int ent = (sg != kNoState ? (int)sg : 0) * N, ys = (int)(info >> 24);
+                    if (word & kWideStay) {
+                        const float v = atomicExch(&sum[ent], 0.0f);  // the first lane here takes the sum and leaves the entry clear
+                        if (v != 0.0f) orow[ent] = orow[ent] + q.occ_scale * v;
+                    }
+                    if (word & kWideAdv) {
+                        const float v = atomicExch(&sum[ent + ys], 0.0f);
+                        if (v != 0.0f) orow[ent + ys] = orow[ent + ys] + q.occ_scale * v;
+                    }
+                }
+            }
+            __syncthreads();  // ... and clear again before the next row adds; beta of row u - 1 in every cell
+        }
+    }
+}
+
 template <int K, int MM, int NB>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void crfp_back_kernel(CrfPostParams q) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    if constexpr (K == 8 && MM == 2 && NB == 4) {  // (the LDS-resident window rides in this one only)
+        if (q.walk == kWalkOcc && q.wide_j > 0) return crfp_occ_walk_lds(crfp_params_again(q), smem);
+    }
     // (every instantiation carries these three walks within its 256 registers: a kernel's count is its widest walk's)
     if constexpr (MM == 2 && NB == 4) {  // (the occupancy walk rides in these four only)
         if (q.walk == kWalkOcc) return crfp_occ_walk<K>(q, smem);
@@ -819,6 +1000,89 @@ hipError_t launch_crf_occupancy(const BatchDesc &in, const ScoreDesc &y, const f
     case 8: return launch_occupancy_pair<8>(q, grid, lds_fwd, lds_back, stream);
     default: return hipErrorInvalidValue;
     }
+}
+
+// ---- fcd_set_crf_lattice_wide: windows beyond 512 states, walked in LDS inside crfp_fwd_kernel<8> / crfp_back_kernel<8, 2, 4> ----
+namespace {
+int crf_wide_states_per_lane(int64_t T, int64_t stride, int64_t band) {
+    return (int)((crf_lattice_window_states(T, stride, band) + 63) / 64);
+}
+
+size_t crf_wide_launch_lds(int64_t T, int64_t S, int64_t N, int64_t stride, int64_t band, bool occupancy) {
+    return crf_lds_bytes((int)std::min<int64_t>(std::min(T, stride) + 1, 1 << 24)) + (occupancy ? (size_t)S * (size_t)N * 4 : 0) +
+           crf_wide_lds_bytes(crf_wide_states_per_lane(T, stride, band));
+}
+}  // namespace
+
+bool crf_lattice_is_wide(int64_t T, int64_t stride, int64_t band) { return crf_lattice_window_states(T, stride, band) > 512; }
+
+int crf_lattice_wide_unsupported(int64_t T, int64_t S, int64_t N, int64_t stride, int64_t band, bool occupancy, size_t *lds_bytes) {
+    *lds_bytes = 0;
+    if (N - 1 > 8) return 2;
+    if (crf_lattice_window_states(T, stride, band) > 4096) return 1;
+    if (S >= (int64_t)kNoState) return 3;
+    *lds_bytes = crf_wide_launch_lds(T, S, N, stride, band, occupancy);
+    return *lds_bytes > kOccLdsLimit ? 4 : 0;
+}
+
+size_t crf_lattice_wide_row_bytes(int64_t T, int64_t stride, int64_t band) {
+    if (!crf_lattice_is_wide(T, stride, band)) return crf_occupancy_row_bytes(T, stride, band);
+    return stored_rows_bytes(T, (size_t)crf_wide_states_per_lane(T, stride, band));
+}
+
+namespace {
+CrfPostParams crf_wide_params(const BatchDesc &in, const ScoreDesc &y, const float *init, int64_t n_init, int64_t init_stride,
+                              int64_t band, double *logp) {
+    CrfPostParams q = {};
+    q.c = crf_params(in, y, init, n_init, init_stride, band);
+    q.c.logp = logp;
+    q.m = 1;  // (no chain values: neither walk asks)
+    q.walk = kWalkSub;
+    q.wide_j = crf_wide_states_per_lane(in.T, y.stride, band);
+    return q;
+}
+}  // namespace
+
+hipError_t launch_crf_score_wide(const BatchDesc &in, const ScoreDesc &y, const float *init, int64_t n_init, int64_t init_stride,
+                                 int64_t band, double *logp, hipStream_t stream) {
+    if (!crf_lattice_is_wide(in.T, y.stride, band)) return launch_crf_score(in, y, init, n_init, init_stride, band, logp, stream);
+    const int64_t rows = in.n_reads * y.n_hyp;
+    if (rows <= 0) return hipSuccess;
+    const CrfPostParams q = crf_wide_params(in, y, init, n_init, init_stride, band, logp);  // (alpha null: the sum alone)
+    const size_t lds = crf_wide_launch_lds(in.T, in.S, in.N, y.stride, band, false);
+    const hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(crfp_fwd_kernel<8>), (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(crfp_fwd_kernel<8>, dim3((unsigned)rows), dim3(64), lds, stream, q);
+    return hipGetLastError();
+}
+
+hipError_t launch_crf_occupancy_wide(const BatchDesc &in, const ScoreDesc &y, const float *init, int64_t n_init, int64_t init_stride,
+                                     int64_t band, const OccupancyDesc &out, double *logp, unsigned char *alpha, hipStream_t stream) {
+    if (!crf_lattice_is_wide(in.T, y.stride, band))
+        return launch_crf_occupancy(in, y, init, n_init, init_stride, band, out, logp, alpha, stream);
+    const int64_t rows = in.n_reads * y.n_hyp;
+    if (rows <= 0) return hipSuccess;
+    CrfPostParams q[2];
+    for (int w = 0; w < 2; ++w) {
+        q[w] = crf_wide_params(in, y, init, n_init, init_stride, band, logp);
+        q[w].alpha = reinterpret_cast<float *>(alpha);
+        q[w].alpha_words = (int64_t)(crf_lattice_wide_row_bytes(in.T, y.stride, band) / 4);
+        q[w].walk = w ? kWalkOcc : kWalkSub;
+        q[w].occ = out.occ;
+        q[w].occ_stride_row = out.stride_row;
+        q[w].occ_stride_t = out.stride_t;
+        q[w].occ_scale = out.scale;
+        q[w].occ_clear = out.accumulate ? 0 : 1;
+    }
+    const size_t lds_fwd = crf_wide_launch_lds(in.T, in.S, in.N, y.stride, band, false);
+    const size_t lds_back = crf_wide_launch_lds(in.T, in.S, in.N, y.stride, band, true);
+    hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(crfp_fwd_kernel<8>), (int)lds_fwd);
+    if (e == hipSuccess) e = allow_dynamic_lds(reinterpret_cast<const void *>(crfp_back_kernel<8, 2, 4>), (int)lds_back);
+    if (e != hipSuccess) return e;
+    const dim3 grid((unsigned)rows);
+    hipLaunchKernelGGL(crfp_fwd_kernel<8>, grid, dim3(64), lds_fwd, stream, q[0]);
+    hipLaunchKernelGGL((crfp_back_kernel<8, 2, 4>), grid, dim3(64), lds_back, stream, q[1]);
+    return hipGetLastError();
 }
 
 }  // namespace fcd

@@ -343,6 +343,21 @@ int crf_occupancy_unsupported(int64_t T, int64_t S, int64_t N, int64_t stride);
 size_t crf_occupancy_row_bytes(int64_t T, int64_t stride, int64_t band);
 hipError_t launch_crf_occupancy(const BatchDesc &in, const ScoreDesc &y, const float *init, int64_t n_init, int64_t init_stride,
                                 int64_t band, const OccupancyDesc &out, double *logp, unsigned char *alpha, hipStream_t stream);
+// The CRF forward sum and the occupancies for windows beyond 512 states (crf_posterior.hip; fcd_set_crf_lattice_wide in
+// include/fcd.h): the window lives in LDS, J = ceil(states / 64) = 9 .. 64 states per lane, walked by loop bodies inside
+// crfp_fwd_kernel<8> (sum only when alpha is null: the score) and crfp_back_kernel<8, 2, 4>.  A window within 512 states
+// (crf_lattice_is_wide false) goes to launch_crf_score / launch_crf_occupancy unchanged.
+// crf_lattice_wide_unsupported: 0 = the kernels hold the call; 1 = the window exceeds 4096 states, 2 = more than 8 labels,
+// 3 = S beyond the state word, 4 = the labelling's copy, the tile, the window's three rows and (occupancy) the S * N row
+// exceed the 160 KiB of a workgroup; *lds_bytes: what the widest launch takes (0 where 1 .. 3 answered first).
+// alpha: crf_lattice_wide_row_bytes() per labelling of the launch -- stored_rows_bytes(T, J); logp must not be null.
+bool crf_lattice_is_wide(int64_t T, int64_t stride, int64_t band);
+int crf_lattice_wide_unsupported(int64_t T, int64_t S, int64_t N, int64_t stride, int64_t band, bool occupancy, size_t *lds_bytes);
+size_t crf_lattice_wide_row_bytes(int64_t T, int64_t stride, int64_t band);
+hipError_t launch_crf_score_wide(const BatchDesc &in, const ScoreDesc &y, const float *init, int64_t n_init, int64_t init_stride,
+                                 int64_t band, double *logp, hipStream_t stream);
+hipError_t launch_crf_occupancy_wide(const BatchDesc &in, const ScoreDesc &y, const float *init, int64_t n_init, int64_t init_stride,
+                                     int64_t band, const OccupancyDesc &out, double *logp, unsigned char *alpha, hipStream_t stream);
 // CTC label occupancies of the same labellings (ctc_posterior.hip; fcd_ctc_occupancy_* in include/fcd.h): post_fwd_kernel<K>
 // and a second walk inside post_back_kernel<K, 8>.  The limits and the workspace are launch_ctc_posterior's
 // (ctc_posterior_unsupported, ctc_posterior_row_bytes); out.occ: the first labelling's (T, N) block; logp must not be null.
@@ -482,6 +497,7 @@ struct fcd_handle {
     bool job_active = false;  // a host job owns the lanes from begin to end
     int live_sessions = 0;    // fcd_beam_session_create .. _destroy
     bool occ_wide = false;    // fcd_set_ctc_occupancy_wide: fcd_ctc_occupancy_* takes windows beyond 510 states
+    bool crf_wide = false;    // fcd_set_crf_lattice_wide: fcd_crf_score_* and fcd_crf_occupancy_* take windows beyond 512 states
     int64_t align_ws_cap = 0; // fcd_debug_set_align_workspace_cap: back-pointer bytes one launch of fcd_ctc_align_* may take, 0 = default
     bool is_lane = false;
     uint32_t *duplex_prof = nullptr;  // fcd_debug_set_duplex_profile

@@ -749,6 +749,32 @@ int fcd_crf_occupancy_dev(fcd_handle *h, const fcd_batch *in, const float *init,
 int fcd_crf_occupancy_host(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init, int64_t init_stride,
                            const fcd_labellings *y, int64_t band, const fcd_occupancy *out);
 
+/* ---- the CRF forward sum and the occupancies for windows beyond 512 states ----
+ * fcd_set_crf_lattice_wide(h, 1) makes fcd_crf_score_dev / _host and fcd_crf_occupancy_dev / _host on this handle take them,
+ * (h, 0) -- the state of a new handle -- restores the limits above; any other value is FCD_E_INVALID.  The switch is read
+ * when a call is made, under the handle's lock.  No new entry point: arguments, outputs, rows without a value, the
+ * FCD_E_INVALID cases and the give-up rule are unchanged.  Every other CRF lattice call (fcd_crf_align_*,
+ * fcd_crf_posterior_*, fcd_crf_edits_*) ignores the switch and keeps its limit.  With W = min(T, stride) + 1 states
+ * (band > 0: at most 2 band + 1) the widest window of the call:
+ *   W <= 512   the call is what it is with the switch off: the same launches, the same bits, the same messages.
+ *   W >  512   the window lives in LDS: J = ceil(W / 64) = 9 .. 64 states per lane, still one wavefront per labelling, walked
+ *              by loop bodies inside the forward and the occupancy kernels of eight states per lane.  The arithmetic is
+ *              that of the register-resident walks -- the same products, one exponent per row, exact powers of two, one
+ *              rounding per product and per sum, no fused multiply-add -- so fcd_crf_occupancy_*'s logp is fcd_crf_score_*'s
+ *              bit for bit (the same code), and the bounds above hold with J in K's place:
+ *                |occ - exact| <= (6 T_r + W + 1) 2^-24 occ,   lost(T_r) = 2 (6 T_r + 64 J + 2 J + 8) 2^-24
+ *              (an entry's colliding terms meet in the S * N row as before, W - 1 sums at most; a row's mass is summed
+ *              lane-serially over the J cells, one sum per term pair and one per cell, then across the wavefront: 2 J + 6).
+ * What the rows can hold is unchanged -- one f32 exponent per row -- and a wider window does not hold more: INTEGRATION.md
+ * section 2p has the measured range.
+ * Workspace (occupancy; the score takes none): the stored rows, T (64 J + 1) 4 bytes per labelling rounded up to 256, in
+ * groups of whole reads under the 4 GiB cap and the handle's workspace limit.
+ * Limits (FCD_E_UNSUPPORTED; the message starts with "crf_score_wide:" / "crf_occupancy_wide:" and says which): N - 1 <= 8;
+ * W <= 4096 (64 cells per lane: exact lattices up to 4095 rows or labels, bands up to 2047); S < 2^24 - 1; the labelling's
+ * copy, the tile, the window's three rows (cells, products, exponents) and -- occupancy -- the S * N row within the 160 KiB
+ * of LDS: 4 (min(T, stride) + 1) + 4480 + 768 J [+ 4 S N] <= 163840.  S = 1024 and S = 4096 at N = 5 fit with 2048 states. */
+int fcd_set_crf_lattice_wide(fcd_handle *h, int on);
+
 /* ---- CTC label occupancies of given labellings (csrc/ctc_posterior.hip) ----
  * NOT a reference function.  The soft version of fcd_ctc_align_*'s spans and the gradient of the CTC loss: the probability,
  * over the alignments of labelling y, that row t emits symbol c.

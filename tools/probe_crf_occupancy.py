@@ -4,6 +4,9 @@ loops of T dependent steps each, and autograd's .backward() through both.  From 
 
     python tools/probe_crf_occupancy.py [--passes 5] [--torch-passes 2] [--rows 4000] [--reads 4096] [--large-reads 256]
                                         [--loss-reads-s4 8192] [--loss-reads-s64 4096] [--loss-reads-s1024 256] [--out FILE]
+    python tools/probe_crf_occupancy.py --wide [--register-only] [--wide-reads 256] [--wide-loss-reads 64] [--root TREE]
+
+--wide times only the shapes of the windows beyond 512 states and of what shares their kernels (wide_shapes below).
 
 Occupancy: BASELINE config 4's shape (4096 x 4000 x 4 states x 5, beam 5), every read's result at band 16 and band 64:
 crf_score, crf_posterior and crf_occupancy (into a buffer held across the calls; the call clears the rows it writes), and
@@ -53,8 +56,82 @@ def torch_numerator(torch, x, labels, start):
     return total + a[:, L].double()
 
 
+def lattice_cells(T, L):
+    """cells of the exact lattice of L labels in T rows: the states of every row's window (the cone)"""
+    return sum(min(L, t + 1) - max(0, L - (T - 1 - t)) + 1 for t in range(T))
+
+
+def wide_shapes(torch, fcd, args, row, put):
+    """--wide: the shapes behind INTEGRATION.md section 2p.
+    Register-resident, eight states per lane (T = 1000, 495 labels, --wide-reads reads): what ran before the LDS-resident
+    walks joined crfp_fwd_kernel<8> and crfp_back_kernel<8, 2, 4> must not get slower -- crf_occupancy at S = 1024 and S = 16,
+    crf_posterior and crf_edits at S = 16 (m = 2: the chain tier that runs crfp_back_kernel<8, 2, 4>; S = 1024 is m = 5, three
+    states per lane).  Nothing here passes wide=, so the same lines time a build without it (--root).
+    LDS-resident (skipped with --register-only): crf_ctc_loss forward and backward and crf_occupancy alone at T = 1600, 800
+    labels, S = 1024, --wide-loss-reads reads, and the register walk at its limit, 511 labels in 1022 rows, for the cost per
+    lattice cell."""
+    N = 5
+
+    def case(S, B, T, L, seed):
+        g = torch.Generator(device="cuda").manual_seed(seed)
+        x = torch.softmax(2.0 * torch.randn((B, T, S, N), generator=g, device="cuda"), dim=-1)
+        init = torch.rand((B, S), generator=g, device="cuda")
+        labels = torch.randint(1, N, (B, L), generator=g, device="cuda").to(torch.uint8)
+        lens = torch.full((B,), L, dtype=torch.int32, device="cuda")
+        return x, init, labels, lens
+
+    def per_cell(key, B, T, L):
+        row[key + "_ns_per_cell"] = round(row[key + "_ms"] * 1e6 / (B * lattice_cells(T, L)), 4)
+
+    B, T, L = args.wide_reads, 1000, 495
+    row["reg_shape"] = {"T": T, "labels": L, "reads": B}
+    for S in (1024, 16):
+        x, init, labels, lens = case(S, B, T, L, S)
+        out = torch.zeros((B, 1, T, S, N), dtype=torch.float32, device="cuda")
+        put("reg_s%d_occupancy" % S, lambda: fcd.crf_occupancy_batch_raw(x, init, labels, lens, out=out))
+        per_cell("reg_s%d_occupancy" % S, B, T, L)
+        row["reg_s%d_nan" % S] = int(torch.isnan(fcd.crf_occupancy_batch_raw(x, init, labels, lens, out=out).logp).sum())
+        if S == 16:
+            put("reg_s16_posterior", lambda: fcd.crf_posterior_batch_raw(x, init, labels, lens))
+            put("reg_s16_edits", lambda: fcd.crf_edits_batch_raw(x, init, labels, lens))
+        del x, out
+        torch.cuda.empty_cache()
+    if args.register_only:
+        return
+    S, B = 1024, args.wide_loss_reads
+    for tag, T, L, wide in (("reg511", 1022, 511, False), ("wide", 1600, 800, True)):
+        x, init, labels, lens = case(S, B, T, L, T)
+        out = torch.zeros((B, 1, T, S, N), dtype=torch.float32, device="cuda")
+        row[tag + "_shape"] = {"T": T, "labels": L, "reads": B, "S": S, "cells": lattice_cells(T, L),
+                               "states_per_lane": -(-(L + 1) // 64)}
+        put(tag + "_occupancy", lambda: fcd.crf_occupancy_batch_raw(x, init, labels, lens, out=out, wide=wide))
+        per_cell(tag + "_occupancy", B, T, L)
+        put(tag + "_score", lambda: fcd.crf_score_batch_raw(x, init, labels, lens, wide=wide))
+        per_cell(tag + "_score", B, T, L)
+        row[tag + "_nan"] = int(torch.isnan(fcd.crf_occupancy_batch_raw(x, init, labels, lens, out=out, wide=wide).logp).sum())
+        del x, out
+        torch.cuda.empty_cache()
+        g = torch.Generator(device="cuda").manual_seed(T + 1)
+        scores = torch.randn((B, T, S, N), generator=g, device="cuda")
+
+        def loss_and_backward():
+            xs = scores.detach().requires_grad_(True)
+            fcd.crf_ctc_loss(xs, labels, lens).sum().backward()
+            return xs.grad
+        put(tag + "_loss", loss_and_backward)
+        per_cell(tag + "_loss", B, T, L)
+        row[tag + "_loss_nan"] = int(torch.isnan(fcd.crf_ctc_loss(scores, labels, lens)).sum())
+        del scores
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--wide", action="store_true", help="only the shapes of INTEGRATION.md section 2p (wide_shapes)")
+    ap.add_argument("--register-only", action="store_true", help="--wide: the register-resident shapes alone")
+    ap.add_argument("--wide-reads", type=int, default=256)
+    ap.add_argument("--wide-loss-reads", type=int, default=64)
+    ap.add_argument("--root", default=None, help="import fast_ctc_decode_amd from this tree (another build of the package)")
     ap.add_argument("--passes", type=int, default=5)
     ap.add_argument("--torch-passes", type=int, default=2)
     ap.add_argument("--rows", type=int, default=4000)
@@ -65,6 +142,8 @@ def main():
     ap.add_argument("--loss-reads-s1024", type=int, default=256)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.root:
+        sys.path.insert(0, os.path.abspath(args.root))
     import torch
 
     import fast_ctc_decode_amd as fcd
@@ -92,6 +171,19 @@ def main():
     def put(name, fn, passes=None):
         ms = timed(fn, passes or args.passes)
         row[name + "_ms"], row[name + "_all"] = min(ms), ms
+
+    def finish():
+        line = json.dumps(row)
+        print(line, flush=True)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write(line + "\n")
+
+    if args.wide:
+        row = {"passes": args.passes, "package": os.path.dirname(os.path.abspath(fcd.__file__))}
+        wide_shapes(torch, fcd, args, row, put)
+        return finish()
 
     # ---- occupancy next to score and posterior ----
     for tag, S, B, dtype, bands in (("config4", 4, args.reads, torch.float32, (16, 64)),
@@ -155,12 +247,7 @@ def main():
         row[tag + "_max_abs_grad_vs_torch"] = float((xs.grad - torch_once(x[:nsmall], labels[:nsmall], start[:nsmall])).abs().max())
         del x, xs
         torch.cuda.empty_cache()
-    line = json.dumps(row)
-    print(line, flush=True)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    finish()
 
 
 if __name__ == "__main__":
