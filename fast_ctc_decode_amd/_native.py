@@ -116,6 +116,10 @@ class Occupancy(C.Structure):
                 ("accumulate", C.c_int32), ("logp", C.c_void_p)]
 
 
+# what each kind of labelling-lattice call writes through its last argument (None: an array of float64 scores)
+LATTICE_OUT = {"score": None, "align": Alignment, "posterior": Posterior, "edits": Edits, "occupancy": Occupancy}
+
+
 class Transitions(C.Structure):
     """fcd_transitions (include/fcd.h): the outputs of fcd_crf_transition_probs_*"""
     _fields_ = [("probs", C.c_void_p), ("dtype", C.c_int32), ("stride_read", C.c_int64), ("stride_t", C.c_int64),
@@ -283,21 +287,17 @@ def bind(lib):
     lib.fcd_beam_session_bytes.argtypes = [P]
     lib.fcd_beam_session_bytes.restype = i64
     lib.fcd_beam_session_destroy.argtypes = [P]
-    for sfx in ("dev", "host"):
-        getattr(lib, "fcd_ctc_score_" + sfx).argtypes = [P, BP, C.POINTER(Labellings), i32, i64, P]
-        getattr(lib, "fcd_ctc_align_" + sfx).argtypes = [P, BP, C.POINTER(Labellings), i32, i64, C.POINTER(Alignment)]
-        getattr(lib, "fcd_ctc_posterior_" + sfx).argtypes = [P, BP, C.POINTER(Labellings), i32, i64, C.POINTER(Posterior)]
-        getattr(lib, "fcd_ctc_edits_" + sfx).argtypes = [P, BP, C.POINTER(Labellings), i32, i64, C.POINTER(Edits)]
-        getattr(lib, "fcd_ctc_occupancy_" + sfx).argtypes = [P, BP, C.POINTER(Labellings), i32, i64, C.POINTER(Occupancy)]
+    # the labelling-lattice calls fcd_<model>_<kind>_<dev|host>: (handle, batch, [init, n_init, init_stride,] labellings,
+    # [collapse_repeats,] band, the kind's outputs)
+    LP = C.POINTER(Labellings)
+    for model, head in (("ctc", [P, BP, LP, i32, i64]), ("crf", [P, BP, P, i64, i64, LP, i64])):
+        for kind, out in LATTICE_OUT.items():
+            for sfx in ("dev", "host"):
+                getattr(lib, "fcd_%s_%s_%s" % (model, kind, sfx)).argtypes = head + [C.POINTER(out) if out else P]
     lib.fcd_debug_set_align_workspace_cap.argtypes = [P, i64]
     lib.fcd_debug_workspace_bytes.argtypes = [P]
     lib.fcd_debug_workspace_bytes.restype = i64
     for sfx in ("dev", "host"):
-        getattr(lib, "fcd_crf_score_" + sfx).argtypes = [P, BP, P, i64, i64, C.POINTER(Labellings), i64, P]
-        getattr(lib, "fcd_crf_align_" + sfx).argtypes = [P, BP, P, i64, i64, C.POINTER(Labellings), i64, C.POINTER(Alignment)]
-        getattr(lib, "fcd_crf_posterior_" + sfx).argtypes = [P, BP, P, i64, i64, C.POINTER(Labellings), i64, C.POINTER(Posterior)]
-        getattr(lib, "fcd_crf_edits_" + sfx).argtypes = [P, BP, P, i64, i64, C.POINTER(Labellings), i64, C.POINTER(Edits)]
-        getattr(lib, "fcd_crf_occupancy_" + sfx).argtypes = [P, BP, P, i64, i64, C.POINTER(Labellings), i64, C.POINTER(Occupancy)]
         getattr(lib, "fcd_crf_viterbi_search_" + sfx).argtypes = [P, BP, P, i64, i64, RP, P]
         getattr(lib, "fcd_crf_transition_probs_" + sfx).argtypes = [P, BP, i32, C.POINTER(Transitions)]
         getattr(lib, "fcd_crf_marginals_" + sfx).argtypes = [P, BP, i32, C.POINTER(Marginals)]

@@ -7,6 +7,7 @@ they decode many reads per launch (numpy -> staged through the C ABI's *_host en
 torch tensors on an AMD GPU -> zero-copy through the *_dev entry points on the tensor's
 current stream).  All searching happens on the GPU: there is no CPU fallback.
 """
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -1155,7 +1156,95 @@ def _is_torch_cuda(x):
     return hasattr(x, "data_ptr") and hasattr(x, "is_cuda") and bool(x.is_cuda)
 
 
-class BatchResult:
+def _to_host(a):
+    """numpy (and None, and anything that is no device array) as it is; a torch tensor as a numpy array: waits for it"""
+    return a if a is None or isinstance(a, np.ndarray) or not hasattr(a, "cpu") else a.cpu().numpy()
+
+
+class _LatticeMethods:
+    """The labelling-lattice calls (ctc_score_batch_raw ... crf_occupancy_batch_raw) on a search result's own arrays, for
+    BatchResult (one labelling per read: arrays (n_reads, 1, ...)) and NBestResult (n_hyp as n_valid: arrays
+    (n_reads, n_best, ...), and NaN / nothing where i >= n_hyp[r]).  Device results stay on the device: no host round
+    trip.  A class says which results it refuses (_lattice_refuses) and which rows count (_lattice_n_valid)."""
+
+    def _lattice(self, model, kind, network_outputs, lengths, band, input_dtype, **kw):
+        rank = 4 if model == "crf" else 3
+        if self._lattice_refuses(model) or getattr(network_outputs, "ndim", rank) != rank:
+            if model == "crf":
+                raise ValueError("crf_%s covers the results of the CRF searches, (n_reads, T, S, N) posteriors, not plain CTC results" % kind)
+            raise ValueError("ctc_%s covers the plain CTC searches, not CRF results" % kind)
+        n_valid = self._lattice_n_valid(band)
+        return _lattice_call(model, kind, network_outputs, self.labels, self.out_len, lengths, self.path if band else None,
+                             band, n_valid, input_dtype, getattr(self, "_handle", None), **kw)
+
+    def ctc_score(self, network_outputs, collapse_repeats=True, lengths=None, band=0, input_dtype=None):
+        """ln P(labelling | posteriors) of every read's result, float64 (n_reads, 1) -- of every hypothesis,
+        (n_reads, n_best), NaN where i >= n_hyp[r]: ctc_score_batch_raw on this result's own arrays.  `network_outputs`,
+        `lengths` and `collapse_repeats` as given to the search.  A failed read has an empty labelling and scores as one.
+        CRF results are refused (transition-scored models: a different lattice)."""
+        return self._lattice("ctc", "score", network_outputs, lengths, band, input_dtype, collapse_repeats=collapse_repeats)
+
+    def ctc_align(self, network_outputs, collapse_repeats=True, lengths=None, band=0, input_dtype=None):
+        """The best alignment of every read's result to its rows -> AlignResult, arrays (n_reads, 1, stride) -- of every
+        hypothesis, (n_reads, n_best, stride), logp NaN and count 0 where i >= n_hyp[r]: ctc_align_batch_raw on this
+        result's own arrays.  Arguments as ctc_score.  CRF results are refused."""
+        return self._lattice("ctc", "align", network_outputs, lengths, band, input_dtype, collapse_repeats=collapse_repeats)
+
+    def ctc_posterior(self, network_outputs, collapse_repeats=True, lengths=None, band=0, input_dtype=None):
+        """The substitution posteriors of every read's result -> PosteriorResult, post (n_reads, 1, stride, N-1) -- of
+        every hypothesis, (n_reads, n_best, stride, N-1), logp NaN where i >= n_hyp[r]: ctc_posterior_batch_raw on this
+        result's own arrays.  Arguments as ctc_score.  CRF results are refused."""
+        return self._lattice("ctc", "posterior", network_outputs, lengths, band, input_dtype, collapse_repeats=collapse_repeats)
+
+    def ctc_edits(self, network_outputs, collapse_repeats=True, lengths=None, band=0, input_dtype=None):
+        """The deletion and insertion likelihoods of every read's result -> EditResult, deletion (n_reads, 1, stride),
+        insertion (n_reads, 1, stride + 1, N-1) -- of every hypothesis, (n_reads, n_best, stride) and
+        (n_reads, n_best, stride + 1, N-1), logp NaN where i >= n_hyp[r]: ctc_edits_batch_raw on this result's own arrays.
+        Arguments as ctc_score.  CRF results are refused."""
+        return self._lattice("ctc", "edits", network_outputs, lengths, band, input_dtype, collapse_repeats=collapse_repeats)
+
+    def ctc_occupancy(self, network_outputs, collapse_repeats=True, lengths=None, band=0, input_dtype=None, wide=False):
+        """The label occupancies of every read's result -> OccupancyResult, occupancy (n_reads, 1, T, N) -- of every
+        hypothesis, (n_reads, n_best, T, N), zeros and logp NaN where i >= n_hyp[r]: ctc_occupancy_batch_raw on this
+        result's own arrays.  Arguments as ctc_posterior; wide as ctc_occupancy_batch_raw.  CRF results are refused."""
+        return self._lattice("ctc", "occupancy", network_outputs, lengths, band, input_dtype,
+                             collapse_repeats=collapse_repeats, wide=wide)
+
+    def crf_score(self, network_outputs, init_states, lengths=None, band=0, input_dtype=None, wide=False):
+        """ln P(labelling | posteriors) under the CRF model of every read's result, float64 (n_reads, 1) -- of every
+        hypothesis, (n_reads, n_best), NaN where i >= n_hyp[r]: crf_score_batch_raw on this result's own arrays (wide
+        included).  For the results of the CRF searches, with the (B,T,S,N) posteriors and init rows they decoded (a
+        session: the concatenated posteriors); plain CTC results are refused."""
+        return self._lattice("crf", "score", network_outputs, lengths, band, input_dtype, init_states=init_states, wide=wide)
+
+    def crf_align(self, network_outputs, init_states, lengths=None, band=0, input_dtype=None):
+        """The best alignment of every read's result under the CRF model -> AlignResult, arrays (n_reads, 1, stride) -- of
+        every hypothesis, (n_reads, n_best, stride), logp NaN and count 0 where i >= n_hyp[r]: crf_align_batch_raw on this
+        result's own arrays.  Arguments as crf_score."""
+        return self._lattice("crf", "align", network_outputs, lengths, band, input_dtype, init_states=init_states)
+
+    def crf_posterior(self, network_outputs, init_states, lengths=None, band=0, input_dtype=None):
+        """The substitution posteriors under the CRF model of every read's result -> PosteriorResult, post
+        (n_reads, 1, stride, N-1) -- of every hypothesis, (n_reads, n_best, stride, N-1), logp NaN where i >= n_hyp[r]:
+        crf_posterior_batch_raw on this result's own arrays.  Arguments as crf_score."""
+        return self._lattice("crf", "posterior", network_outputs, lengths, band, input_dtype, init_states=init_states)
+
+    def crf_edits(self, network_outputs, init_states, lengths=None, band=0, input_dtype=None):
+        """The deletion and insertion likelihoods under the CRF model of every read's result -> EditResult, deletion
+        (n_reads, 1, stride), insertion (n_reads, 1, stride + 1, N-1) -- of every hypothesis, (n_reads, n_best, stride) and
+        (n_reads, n_best, stride + 1, N-1), logp NaN where i >= n_hyp[r]: crf_edits_batch_raw on this result's own arrays.
+        Arguments as crf_score."""
+        return self._lattice("crf", "edits", network_outputs, lengths, band, input_dtype, init_states=init_states)
+
+    def crf_occupancy(self, network_outputs, init_states, lengths=None, band=0, input_dtype=None, wide=False):
+        """The edge occupancies under the CRF model of every read's result -> OccupancyResult, occupancy
+        (n_reads, 1, T, S, N) -- of every hypothesis, (n_reads, n_best, T, S, N), zeros and logp NaN where i >= n_hyp[r]:
+        crf_occupancy_batch_raw on this result's own arrays.  Arguments as crf_score; wide as crf_occupancy_batch_raw."""
+        return self._lattice("crf", "occupancy", network_outputs, lengths, band, input_dtype, init_states=init_states,
+                             wide=wide)
+
+
+class BatchResult(_LatticeMethods):
     """Raw outcome of a batched search: label indices, paths, lengths and per-read status.
     Arrays are numpy for host inputs, torch tensors (same device) for device inputs."""
 
@@ -1174,130 +1263,16 @@ class BatchResult:
             import torch
             h.set_stream(torch.cuda.current_stream(self.labels.device).cuda_stream)
             h.overlap_join()
+        return BatchResult(*map(_to_host, (self.labels, self.path, self.out_len, self.status, self.qual, self.ambiguous)))
 
-        def c(a):
-            return a if a is None or isinstance(a, np.ndarray) else a.cpu().numpy()
-        return BatchResult(c(self.labels), c(self.path), c(self.out_len), c(self.status), c(self.qual),
-                           c(self.ambiguous))
+    def _lattice_refuses(self, model):
+        # (crf_*: the posteriors' rank alone tells -- the CRF beam searches return BatchResults as the plain ones do)
+        return model == "ctc" and isinstance(self, _CrfBatchResult)
 
-    def ctc_score(self, network_outputs, collapse_repeats=True, lengths=None, band=0, input_dtype=None):
-        """ln P(labelling | posteriors) of every read's result, float64 (n_reads, 1): ctc_score_batch_raw on this
-        result's own arrays (device results stay on the device; no host round trip).  `network_outputs`, `lengths`
-        and `collapse_repeats` as given to the search.  A failed read has an empty labelling and scores as one.
-        CRF results are refused (transition-scored models: a different lattice)."""
-        if isinstance(self, _CrfBatchResult) or getattr(network_outputs, "ndim", 3) != 3:
-            raise ValueError("ctc_score covers the plain CTC searches, not CRF results")
+    def _lattice_n_valid(self, band):
         if band and self.path is None:
             raise ValueError("a band needs the result's path")
-        return ctc_score_batch_raw(network_outputs, self.labels, self.out_len, collapse_repeats, lengths,
-                                   self.path if band else None, band, None, input_dtype,
-                                   getattr(self, "_handle", None))
-
-    def ctc_align(self, network_outputs, collapse_repeats=True, lengths=None, band=0, input_dtype=None):
-        """The best alignment of every read's result to its rows -> AlignResult, arrays (n_reads, 1, stride):
-        ctc_align_batch_raw on this result's own arrays (device results stay on the device).  Arguments as ctc_score.
-        CRF results are refused (transition-scored models: a different lattice)."""
-        if isinstance(self, _CrfBatchResult) or getattr(network_outputs, "ndim", 3) != 3:
-            raise ValueError("ctc_align covers the plain CTC searches, not CRF results")
-        if band and self.path is None:
-            raise ValueError("a band needs the result's path")
-        return ctc_align_batch_raw(network_outputs, self.labels, self.out_len, collapse_repeats, lengths,
-                                   self.path if band else None, band, None, input_dtype,
-                                   getattr(self, "_handle", None))
-
-    def ctc_posterior(self, network_outputs, collapse_repeats=True, lengths=None, band=0, input_dtype=None):
-        """The substitution posteriors of every read's result -> PosteriorResult, post (n_reads, 1, stride, N-1):
-        ctc_posterior_batch_raw on this result's own arrays (device results stay on the device).  Arguments as
-        ctc_score.  CRF results are refused (transition-scored models: a different lattice)."""
-        if isinstance(self, _CrfBatchResult) or getattr(network_outputs, "ndim", 3) != 3:
-            raise ValueError("ctc_posterior covers the plain CTC searches, not CRF results")
-        if band and self.path is None:
-            raise ValueError("a band needs the result's path")
-        return ctc_posterior_batch_raw(network_outputs, self.labels, self.out_len, collapse_repeats, lengths,
-                                       self.path if band else None, band, None, input_dtype,
-                                       getattr(self, "_handle", None))
-
-    def ctc_edits(self, network_outputs, collapse_repeats=True, lengths=None, band=0, input_dtype=None):
-        """The deletion and insertion likelihoods of every read's result -> EditResult, deletion (n_reads, 1, stride),
-        insertion (n_reads, 1, stride + 1, N-1): ctc_edits_batch_raw on this result's own arrays (device results stay on
-        the device).  Arguments as ctc_score.  CRF results are refused (transition-scored models: a different lattice)."""
-        if isinstance(self, _CrfBatchResult) or getattr(network_outputs, "ndim", 3) != 3:
-            raise ValueError("ctc_edits covers the plain CTC searches, not CRF results")
-        if band and self.path is None:
-            raise ValueError("a band needs the result's path")
-        return ctc_edits_batch_raw(network_outputs, self.labels, self.out_len, collapse_repeats, lengths,
-                                   self.path if band else None, band, None, input_dtype,
-                                   getattr(self, "_handle", None))
-
-    def ctc_occupancy(self, network_outputs, collapse_repeats=True, lengths=None, band=0, input_dtype=None, wide=False):
-        """The label occupancies of every read's result -> OccupancyResult, occupancy (n_reads, 1, T, N):
-        ctc_occupancy_batch_raw on this result's own arrays (device results stay on the device).  Arguments as
-        ctc_posterior; wide as ctc_occupancy_batch_raw.  CRF results are refused (transition-scored models: a different
-        lattice)."""
-        if isinstance(self, _CrfBatchResult) or getattr(network_outputs, "ndim", 3) != 3:
-            raise ValueError("ctc_occupancy covers the plain CTC searches, not CRF results")
-        if band and self.path is None:
-            raise ValueError("a band needs the result's path")
-        return ctc_occupancy_batch_raw(network_outputs, self.labels, self.out_len, collapse_repeats, lengths,
-                                       self.path if band else None, band, None, input_dtype=input_dtype,
-                                       handle=getattr(self, "_handle", None), wide=wide)
-
-    def crf_score(self, network_outputs, init_states, lengths=None, band=0, input_dtype=None, wide=False):
-        """ln P(labelling | posteriors) under the CRF model of every read's result, float64 (n_reads, 1):
-        crf_score_batch_raw on this result's own arrays (wide included).  For the results of the CRF searches, with the
-        (B,T,S,N) posteriors and init rows they decoded (a session: the concatenated posteriors); plain CTC results are
-        refused."""
-        if getattr(network_outputs, "ndim", 4) != 4:
-            raise ValueError("crf_score covers the results of the CRF searches, (n_reads, T, S, N) posteriors, not plain CTC results")
-        if band and self.path is None:
-            raise ValueError("a band needs the result's path")
-        return crf_score_batch_raw(network_outputs, init_states, self.labels, self.out_len, lengths,
-                                   self.path if band else None, band, None, input_dtype, getattr(self, "_handle", None),
-                                   wide=wide)
-
-    def crf_align(self, network_outputs, init_states, lengths=None, band=0, input_dtype=None):
-        """The best alignment of every read's result under the CRF model -> AlignResult, arrays (n_reads, 1, stride):
-        crf_align_batch_raw on this result's own arrays.  Arguments as crf_score."""
-        if getattr(network_outputs, "ndim", 4) != 4:
-            raise ValueError("crf_align covers the results of the CRF searches, (n_reads, T, S, N) posteriors, not plain CTC results")
-        if band and self.path is None:
-            raise ValueError("a band needs the result's path")
-        return crf_align_batch_raw(network_outputs, init_states, self.labels, self.out_len, lengths,
-                                   self.path if band else None, band, None, input_dtype, getattr(self, "_handle", None))
-
-    def crf_posterior(self, network_outputs, init_states, lengths=None, band=0, input_dtype=None):
-        """The substitution posteriors under the CRF model of every read's result -> PosteriorResult, post
-        (n_reads, 1, stride, N-1): crf_posterior_batch_raw on this result's own arrays (device results stay on the
-        device).  Arguments as crf_score."""
-        if getattr(network_outputs, "ndim", 4) != 4:
-            raise ValueError("crf_posterior covers the results of the CRF searches, (n_reads, T, S, N) posteriors, not plain CTC results")
-        if band and self.path is None:
-            raise ValueError("a band needs the result's path")
-        return crf_posterior_batch_raw(network_outputs, init_states, self.labels, self.out_len, lengths,
-                                       self.path if band else None, band, None, input_dtype, getattr(self, "_handle", None))
-
-    def crf_edits(self, network_outputs, init_states, lengths=None, band=0, input_dtype=None):
-        """The deletion and insertion likelihoods under the CRF model of every read's result -> EditResult, deletion
-        (n_reads, 1, stride), insertion (n_reads, 1, stride + 1, N-1): crf_edits_batch_raw on this result's own arrays
-        (device results stay on the device).  Arguments as crf_score."""
-        if getattr(network_outputs, "ndim", 4) != 4:
-            raise ValueError("crf_edits covers the results of the CRF searches, (n_reads, T, S, N) posteriors, not plain CTC results")
-        if band and self.path is None:
-            raise ValueError("a band needs the result's path")
-        return crf_edits_batch_raw(network_outputs, init_states, self.labels, self.out_len, lengths,
-                                   self.path if band else None, band, None, input_dtype, getattr(self, "_handle", None))
-
-    def crf_occupancy(self, network_outputs, init_states, lengths=None, band=0, input_dtype=None, wide=False):
-        """The edge occupancies under the CRF model of every read's result -> OccupancyResult, occupancy
-        (n_reads, 1, T, S, N): crf_occupancy_batch_raw on this result's own arrays (device results stay on the device).
-        Arguments as crf_score; wide as crf_occupancy_batch_raw."""
-        if getattr(network_outputs, "ndim", 4) != 4:
-            raise ValueError("crf_occupancy covers the results of the CRF searches, (n_reads, T, S, N) posteriors, not plain CTC results")
-        if band and self.path is None:
-            raise ValueError("a band needs the result's path")
-        return crf_occupancy_batch_raw(network_outputs, init_states, self.labels, self.out_len, lengths,
-                                       self.path if band else None, band, None, input_dtype=input_dtype,
-                                       handle=getattr(self, "_handle", None), wide=wide)
+        return None
 
     def sequences(self, alphabet, raise_on_error=True, paths="list"):
         """-> list of (str, path) per read, exactly what the single-read functions return.
@@ -1572,7 +1547,7 @@ def _check_n_best(n_best, beam_size):
     return int(n_best)
 
 
-class NBestResult:
+class NBestResult(_LatticeMethods):
     """Raw outcome of an n-best beam search: hypothesis i of read r is labels[r, i, :out_len[r, i]] (path likewise),
     its score score[r, i] = label_prob + gap_prob of beam entry i after the last step -- relative to the best entry,
     not a log-likelihood.  n_hyp[r] hypotheses per read (0 when the read's search failed: status[r] says why).
@@ -1589,106 +1564,14 @@ class NBestResult:
             import torch  # (as BatchResult.cpu: the copies wait for every overlapping call)
             h.set_stream(torch.cuda.current_stream(self.labels.device).cuda_stream)
             h.overlap_join()
+        return NBestResult(*map(_to_host, (self.labels, self.path, self.out_len, self.score, self.n_hyp, self.status,
+                                           self.ambiguous)), self.crf)
 
-        def c(a):
-            return a if a is None or isinstance(a, np.ndarray) else a.cpu().numpy()
-        return NBestResult(c(self.labels), c(self.path), c(self.out_len), c(self.score), c(self.n_hyp), c(self.status),
-                           c(self.ambiguous), self.crf)
+    def _lattice_refuses(self, model):
+        return self.crf != (model == "crf")
 
-    def ctc_score(self, network_outputs, collapse_repeats=True, lengths=None, band=0, input_dtype=None):
-        """ln P(labelling | posteriors) of every hypothesis, float64 (n_reads, n_best); NaN where i >= n_hyp[r].
-        ctc_score_batch_raw on this result's own arrays (n_hyp as n_valid); CRF results are refused."""
-        if self.crf or getattr(network_outputs, "ndim", 3) != 3:
-            raise ValueError("ctc_score covers the plain CTC searches, not CRF results")
-        return ctc_score_batch_raw(network_outputs, self.labels, self.out_len, collapse_repeats, lengths,
-                                   self.path if band else None, band, self.n_hyp, input_dtype,
-                                   getattr(self, "_handle", None))
-
-    def ctc_align(self, network_outputs, collapse_repeats=True, lengths=None, band=0, input_dtype=None):
-        """The best alignment of every hypothesis -> AlignResult, arrays (n_reads, n_best, stride); logp NaN and count 0
-        where i >= n_hyp[r].  ctc_align_batch_raw on this result's own arrays; CRF results are refused."""
-        if self.crf or getattr(network_outputs, "ndim", 3) != 3:
-            raise ValueError("ctc_align covers the plain CTC searches, not CRF results")
-        return ctc_align_batch_raw(network_outputs, self.labels, self.out_len, collapse_repeats, lengths,
-                                   self.path if band else None, band, self.n_hyp, input_dtype,
-                                   getattr(self, "_handle", None))
-
-    def ctc_posterior(self, network_outputs, collapse_repeats=True, lengths=None, band=0, input_dtype=None):
-        """The substitution posteriors of every hypothesis -> PosteriorResult, post (n_reads, n_best, stride, N-1); logp
-        NaN where i >= n_hyp[r].  ctc_posterior_batch_raw on this result's own arrays; CRF results are refused."""
-        if self.crf or getattr(network_outputs, "ndim", 3) != 3:
-            raise ValueError("ctc_posterior covers the plain CTC searches, not CRF results")
-        return ctc_posterior_batch_raw(network_outputs, self.labels, self.out_len, collapse_repeats, lengths,
-                                       self.path if band else None, band, self.n_hyp, input_dtype,
-                                       getattr(self, "_handle", None))
-
-    def ctc_edits(self, network_outputs, collapse_repeats=True, lengths=None, band=0, input_dtype=None):
-        """The deletion and insertion likelihoods of every hypothesis -> EditResult, deletion (n_reads, n_best, stride),
-        insertion (n_reads, n_best, stride + 1, N-1); logp NaN where i >= n_hyp[r].  ctc_edits_batch_raw on this result's
-        own arrays; CRF results are refused."""
-        if self.crf or getattr(network_outputs, "ndim", 3) != 3:
-            raise ValueError("ctc_edits covers the plain CTC searches, not CRF results")
-        return ctc_edits_batch_raw(network_outputs, self.labels, self.out_len, collapse_repeats, lengths,
-                                   self.path if band else None, band, self.n_hyp, input_dtype,
-                                   getattr(self, "_handle", None))
-
-    def ctc_occupancy(self, network_outputs, collapse_repeats=True, lengths=None, band=0, input_dtype=None, wide=False):
-        """The label occupancies of every hypothesis -> OccupancyResult, occupancy (n_reads, n_best, T, N), zeros and logp
-        NaN where i >= n_hyp[r].  ctc_occupancy_batch_raw on this result's own arrays (wide included); CRF results are
-        refused."""
-        if self.crf or getattr(network_outputs, "ndim", 3) != 3:
-            raise ValueError("ctc_occupancy covers the plain CTC searches, not CRF results")
-        return ctc_occupancy_batch_raw(network_outputs, self.labels, self.out_len, collapse_repeats, lengths,
-                                       self.path if band else None, band, self.n_hyp, input_dtype=input_dtype,
-                                       handle=getattr(self, "_handle", None), wide=wide)
-
-    def crf_score(self, network_outputs, init_states, lengths=None, band=0, input_dtype=None, wide=False):
-        """ln P(labelling | posteriors) under the CRF model of every hypothesis, float64 (n_reads, n_best); NaN where
-        i >= n_hyp[r].  crf_score_batch_raw on this result's own arrays (wide included); plain CTC results are refused."""
-        if not self.crf or getattr(network_outputs, "ndim", 4) != 4:
-            raise ValueError("crf_score covers the results of the CRF searches, not plain CTC results")
-        return crf_score_batch_raw(network_outputs, init_states, self.labels, self.out_len, lengths,
-                                   self.path if band else None, band, self.n_hyp, input_dtype,
-                                   getattr(self, "_handle", None), wide=wide)
-
-    def crf_align(self, network_outputs, init_states, lengths=None, band=0, input_dtype=None):
-        """The best alignment of every hypothesis under the CRF model -> AlignResult, arrays (n_reads, n_best, stride);
-        logp NaN and count 0 where i >= n_hyp[r].  crf_align_batch_raw on this result's own arrays."""
-        if not self.crf or getattr(network_outputs, "ndim", 4) != 4:
-            raise ValueError("crf_align covers the results of the CRF searches, not plain CTC results")
-        return crf_align_batch_raw(network_outputs, init_states, self.labels, self.out_len, lengths,
-                                   self.path if band else None, band, self.n_hyp, input_dtype,
-                                   getattr(self, "_handle", None))
-
-    def crf_posterior(self, network_outputs, init_states, lengths=None, band=0, input_dtype=None):
-        """The substitution posteriors under the CRF model of every hypothesis -> PosteriorResult, post
-        (n_reads, n_best, stride, N-1); logp NaN where i >= n_hyp[r].  crf_posterior_batch_raw on this result's own arrays;
-        plain CTC results are refused."""
-        if not self.crf or getattr(network_outputs, "ndim", 4) != 4:
-            raise ValueError("crf_posterior covers the results of the CRF searches, not plain CTC results")
-        return crf_posterior_batch_raw(network_outputs, init_states, self.labels, self.out_len, lengths,
-                                       self.path if band else None, band, self.n_hyp, input_dtype,
-                                       getattr(self, "_handle", None))
-
-    def crf_edits(self, network_outputs, init_states, lengths=None, band=0, input_dtype=None):
-        """The deletion and insertion likelihoods under the CRF model of every hypothesis -> EditResult, deletion
-        (n_reads, n_best, stride), insertion (n_reads, n_best, stride + 1, N-1); logp NaN where i >= n_hyp[r].
-        crf_edits_batch_raw on this result's own arrays; plain CTC results are refused."""
-        if not self.crf or getattr(network_outputs, "ndim", 4) != 4:
-            raise ValueError("crf_edits covers the results of the CRF searches, not plain CTC results")
-        return crf_edits_batch_raw(network_outputs, init_states, self.labels, self.out_len, lengths,
-                                   self.path if band else None, band, self.n_hyp, input_dtype,
-                                   getattr(self, "_handle", None))
-
-    def crf_occupancy(self, network_outputs, init_states, lengths=None, band=0, input_dtype=None, wide=False):
-        """The edge occupancies under the CRF model of every hypothesis -> OccupancyResult, occupancy
-        (n_reads, n_best, T, S, N), zeros and logp NaN where i >= n_hyp[r].  crf_occupancy_batch_raw on this result's own
-        arrays (wide included); plain CTC results are refused."""
-        if not self.crf or getattr(network_outputs, "ndim", 4) != 4:
-            raise ValueError("crf_occupancy covers the results of the CRF searches, not plain CTC results")
-        return crf_occupancy_batch_raw(network_outputs, init_states, self.labels, self.out_len, lengths,
-                                       self.path if band else None, band, self.n_hyp, input_dtype=input_dtype,
-                                       handle=getattr(self, "_handle", None), wide=wide)
+    def _lattice_n_valid(self, band):
+        return self.n_hyp
 
     def hypotheses(self, alphabet, raise_on_error=True):
         """-> per read, a list of (seq, path, score), best first (None for a failed read when not raise_on_error)."""
@@ -1971,6 +1854,163 @@ def _lattice_inputs(network_outputs, labels, label_lengths, lengths, paths, band
     return h, b, y, (B, n_hyp, stride), None, (x, lab, ylen, pth, nv, l, init)
 
 
+class _Arrays:
+    """Where a lattice call's outputs live: torch tensors on `dev`, numpy arrays for dev=None.  zeros / empty(shape, kind)
+    with kind u32 (an int32 tensor on the device: the same 32 bits), f32 or f64; ptr(a): the address the C ABI takes."""
+
+    def __init__(self, dev):
+        self.dev = dev
+
+    def _new(self, how, shape, kind):
+        if self.dev is None:
+            return getattr(np, how)(shape, {"u32": np.uint32, "f32": np.float32, "f64": np.float64}[kind])
+        import torch
+        dtype = {"u32": torch.int32, "f32": torch.float32, "f64": torch.float64}[kind]
+        return getattr(torch, how)(shape, dtype=dtype, device=self.dev)
+
+    def zeros(self, shape, kind):
+        return self._new("zeros", shape, kind)
+
+    def empty(self, shape, kind):
+        return self._new("empty", shape, kind)
+
+    def ptr(self, a):
+        return a.ctypes.data if self.dev is None else a.data_ptr()
+
+
+# The outputs of each kind of lattice call: (xp, the call's nat.Batch, (B, n_hyp, stride)) -> (the C ABI's last argument,
+# what the Python call returns).  logp and the scores are written for every labelling (empty), the rest only where there is
+# something to say (zeros).
+def _score_out(xp, b, shape):
+    out = xp.empty(shape[:2], "f64")
+    return C.c_void_p(xp.ptr(out)), out
+
+
+def _align_out(xp, b, shape):
+    start, count, qual = xp.zeros(shape, "u32"), xp.zeros(shape, "u32"), xp.zeros(shape, "f32")
+    logp = xp.empty(shape[:2], "f64")
+    out = nat.Alignment(xp.ptr(start), xp.ptr(count), xp.ptr(qual), xp.ptr(logp))
+    return C.byref(out), AlignResult(start, count, qual, logp)
+
+
+def _posterior_out(xp, b, shape):
+    post = xp.zeros(shape + (int(b.N) - 1,), "f32")
+    logp = xp.empty(shape[:2], "f64")
+    return C.byref(nat.Posterior(xp.ptr(post), xp.ptr(logp))), PosteriorResult(post, logp)
+
+
+def _edits_out(xp, b, shape):
+    B, n_hyp, stride = shape
+    dele = xp.zeros(shape, "f32")
+    ins = xp.zeros((B, n_hyp, stride + 1, int(b.N) - 1), "f32")
+    logp = xp.empty(shape[:2], "f64")
+    return C.byref(nat.Edits(xp.ptr(dele), xp.ptr(ins), xp.ptr(logp))), EditResult(dele, ins, logp)
+
+
+def _occupancy_block(out_shape, shape5, elem_strides):
+    """the caller's buffer as fcd_occupancy sees it -> (stride_row, stride_t); shape5 = (B, n_hyp, T, S, N)"""
+    B, n_hyp, T, S, N = shape5
+    if tuple(out_shape) == (B, T, S, N) and n_hyp == 1:
+        st = (elem_strides[0], elem_strides[0]) + tuple(elem_strides[1:])
+    elif tuple(out_shape) == shape5:
+        st = tuple(elem_strides)
+    else:
+        raise ValueError("out must have shape (n_reads, n_hyp, T, S, N) (or (n_reads, T, S, N) for one labelling per read)")
+    if B * n_hyp * T == 0:
+        return S * N, S * N
+    if (N > 1 and st[4] != 1) or (S > 1 and st[3] != N):
+        raise ValueError("out: the (S, N) rows must be dense")
+    if any(v < 0 for v in st) or (T > 1 and st[2] < S * N) or (n_hyp > 1 and B > 1 and st[0] != n_hyp * st[1]):
+        raise ValueError("out: labelling blocks must be evenly spaced, rows at least S * N floats apart")
+    return (st[1] if n_hyp > 1 or B == 1 else st[0]), max(st[2], S * N)
+
+
+def _check_occupancy_out(out=None, scale=1.0, accumulate=False, time_major_out=False):
+    """what the occupancy calls refuse before they look at their inputs (arguments: _occupancy_out's)"""
+    if accumulate and out is None:
+        raise ValueError("accumulate=True needs the buffer to add to: pass out")
+    if out is not None and time_major_out:
+        raise ValueError("time_major_out shapes the array the call allocates: pass either out or time_major_out")
+
+
+def _occupancy_out(xp, b, shape, has_S, out=None, scale=1.0, accumulate=False, time_major_out=False):
+    """has_S: (B, n_hyp, T, S, N) occupancies of a CRF model; else (B, n_hyp, T, N), which fcd_occupancy takes as S = 1 --
+    its (S, N) row is the row of N"""
+    B, n_hyp = shape[:2]
+    T, S, N = int(b.T), int(b.S), int(b.N)
+    cell = (S, N) if has_S else (N,)
+    if out is None:
+        occ = xp.zeros(((T, B, n_hyp) if time_major_out else (B, n_hyp, T)) + cell, "f32")
+        if time_major_out:
+            order = (1, 2, 0) + tuple(range(3, occ.ndim))
+            occ = occ.transpose(order) if xp.dev is None else occ.permute(order)
+    elif xp.dev is not None:
+        import torch
+        if not _is_torch_cuda(out) or out.device != xp.dev or out.dtype != torch.float32:
+            raise TypeError("out must be a float32 tensor on the inputs' device")
+        occ = out
+    else:
+        if not isinstance(out, np.ndarray) or out.dtype != np.float32 or not out.flags.writeable:
+            raise TypeError("out must be a writable float32 numpy array")
+        occ = out
+    shp = tuple(occ.shape)
+    st = tuple(v // 4 for v in occ.strides) if xp.dev is None else tuple(occ.stride())  # (in elements)
+    if not has_S:
+        if occ.ndim not in (3, 4):
+            raise ValueError("out must have shape (n_reads, n_hyp, T, N) (or (n_reads, T, N) for one labelling per read)")
+        shp, st = shp[:-1] + (1, shp[-1]), st[:-1] + (N, st[-1])
+    sr, stt = _occupancy_block(shp, (B, n_hyp, T, S, N), st)
+    logp = xp.empty((B, n_hyp), "f64")
+    o = nat.Occupancy(xp.ptr(occ), sr, stt, float(scale), int(bool(accumulate)), xp.ptr(logp))
+    return C.byref(o), OccupancyResult(occ, logp)
+
+
+_LATTICE_BUILDERS = {"score": _score_out, "align": _align_out, "posterior": _posterior_out, "edits": _edits_out,
+                     "occupancy": _occupancy_out}
+
+
+@contextlib.contextmanager
+def _wide_switch(h, model, wide):
+    """The handle's wide switch of `model` (include/fcd.h: fcd_set_ctc_occupancy_wide, fcd_set_crf_lattice_wide) on around
+    one call and off behind it, whatever the call raised; nothing where wide is false.  The handle is this thread's:
+    nothing else calls between the switch and the call."""
+    if not wide:
+        yield
+        return
+    switch = h.set_crf_lattice_wide if model == "crf" else h.set_ctc_occupancy_wide
+    switch(True)
+    try:
+        yield
+    finally:
+        switch(False)
+
+
+def _lattice_call(model, kind, network_outputs, labels, label_lengths, lengths, paths, band, n_valid, input_dtype, handle,
+                  init_states=None, collapse_repeats=True, wide=False, **out_args):
+    """The one body of the ten labelling-lattice calls: fcd_<model>_<kind>_dev for device tensors, _host for numpy, with
+    model "ctc" (network_outputs (B,T,N), collapse_repeats) or "crf" ((B,T,S,N) and init_states), kind one of
+    _LATTICE_BUILDERS; out_args: the occupancy calls' out, scale, accumulate and time_major_out.  -> what the call returns."""
+    band = _check_band(band, paths)
+    if kind == "occupancy":
+        _check_occupancy_out(**out_args)
+        out_args["has_S"] = model == "crf"
+    h, b, y, shape, dev, keep = _lattice_inputs(network_outputs, labels, label_lengths, lengths, paths, band, n_valid,
+                                                input_dtype, handle, init_states)
+    xp = _Arrays(dev)
+    out, result = _LATTICE_BUILDERS[kind](xp, b, shape, **out_args)
+    if model == "crf":
+        init = keep[-1]
+        args = (C.byref(b), C.c_void_p(xp.ptr(init)), int(init.shape[1]), int(init.shape[1]), C.byref(y), band, out)
+    else:
+        args = (C.byref(b), C.byref(y), int(bool(collapse_repeats)), band, out)
+    fn = getattr(h.lib, "fcd_%s_%s_%s" % (model, kind, "host" if dev is None else "dev"))
+    with _wide_switch(h, model, wide):
+        h.check(fn(h.ptr, *args))
+    if kind == "occupancy" and dev is not None:
+        h.hold_in_flight(result.occupancy, result.logp, *keep)
+    return result
+
+
 def ctc_score_batch_raw(network_outputs, labels, label_lengths, collapse_repeats=True, lengths=None, paths=None,
                         band=0, n_valid=None, input_dtype=None, handle=None):
     """CTC forward log-likelihood ln P(y | x) of labellings y against the (B,T,N) posteriors x: the sum over every
@@ -1983,32 +2023,39 @@ def ctc_score_batch_raw(network_outputs, labels, label_lengths, collapse_repeats
     lower bound that rises with W, at a cost that no longer grows with the labelling's length.  n_valid (B,): rows
     i >= n_valid[r] are not scored (NaN).  Device tensors in: a torch tensor on the same device, enqueued on torch's
     current stream, not synchronised.  numpy in: numpy out."""
-    band = _check_band(band, paths)
-    h, b, y, (B, n_hyp, stride), dev, keep = _lattice_inputs(network_outputs, labels, label_lengths, lengths, paths, band,
-                                                             n_valid, input_dtype, handle)
-    if dev is not None:
-        import torch
-        out = torch.empty((B, n_hyp), dtype=torch.float64, device=dev)
-        h.check(h.lib.fcd_ctc_score_dev(h.ptr, C.byref(b), C.byref(y), int(bool(collapse_repeats)), band,
-                                        C.c_void_p(out.data_ptr())))
-        return out
-    out = np.empty((B, n_hyp), np.float64)
-    h.check(h.lib.fcd_ctc_score_host(h.ptr, C.byref(b), C.byref(y), int(bool(collapse_repeats)), band,
-                                     out.ctypes.data))
-    return out
+    return _lattice_call("ctc", "score", network_outputs, labels, label_lengths, lengths, paths, band, n_valid, input_dtype,
+                         handle, collapse_repeats=collapse_repeats)
+
+
+def _sequence_labels(sequence, alpha, what):
+    if not isinstance(sequence, str):
+        raise TypeError("argument 'sequence': expected str")
+    if any(len(a) != 1 for a in alpha[1:]):
+        raise ValueError("%s needs single-character labels" % what)
+    index = {a: i for i, a in enumerate(alpha) if i > 0}
+    try:
+        return [index[c] for c in sequence]
+    except KeyError as e:
+        raise ValueError("sequence holds %r, which is not a label of the alphabet" % e.args[0])
+
+
+def _ctc_one_read(network_output, sequence, alphabet, what):
+    """One (T, N) matrix and one string as the batch calls take them -> (x (1, T, N), labels (1, max(L, 1)), lengths (1,), L)"""
+    x = _as_f32(network_output, 2, "network_output")
+    alpha = _seq_to_vec(alphabet)
+    _check_greedy_alphabet(len(alpha), x.shape[1])
+    y = _sequence_labels(sequence, alpha, what)
+    lab = np.zeros((1, max(len(y), 1)), np.uint8)
+    lab[0, :len(y)] = y
+    return _dense(x)[None], lab, np.array([len(y)], np.uint32), len(y)
 
 
 def ctc_score(network_output, sequence, alphabet, collapse_repeats=True):
     """ln P(sequence | network_output): the CTC forward log-likelihood of one string against one (T, N) float32
     posterior matrix, exact (every alignment), as a float.  alphabet[0] is the blank; every label must be one
     character (a multi-character alphabet cannot be split back unambiguously: ValueError)."""
-    x = _as_f32(network_output, 2, "network_output")
-    alpha = _seq_to_vec(alphabet)
-    _check_greedy_alphabet(len(alpha), x.shape[1])
-    y = _sequence_labels(sequence, alpha, "ctc_score")
-    lab = np.zeros((1, max(len(y), 1)), np.uint8)
-    lab[0, :len(y)] = y
-    return float(ctc_score_batch_raw(_dense(x)[None], lab, np.array([len(y)], np.uint32), collapse_repeats)[0, 0])
+    x, lab, n, _ = _ctc_one_read(network_output, sequence, alphabet, "ctc_score")
+    return float(ctc_score_batch_raw(x, lab, n, collapse_repeats)[0, 0])
 
 
 # ---------------------------------------------------------------------------------------------
@@ -2025,19 +2072,16 @@ class AlignResult:
         self.start, self.count, self.qual, self.logp = start, count, qual, logp
 
     def cpu(self):
-        def c(a):
-            return a if isinstance(a, np.ndarray) else a.cpu().numpy()
-        start, count = c(self.start), c(self.count)
+        start, count = _to_host(self.start), _to_host(self.count)
         if start.dtype != np.uint32:  # (device results are int32 tensors: the same 32 bits)
             start, count = start.view(np.uint32), count.view(np.uint32)
-        return AlignResult(start, count, c(self.qual), c(self.logp))
+        return AlignResult(start, count, _to_host(self.qual), _to_host(self.logp))
 
     def qstrings(self, out_len, qscale=1.0, qbias=0.0):
         """-> per read, per hypothesis, the phred quality string of its first out_len[r, i] labels (fcd_phred: the
         reference's phred(), src/search.rs:21-36); "" for a labelling without an alignment."""
         r = self.cpu()
-        n = np.asarray(out_len if isinstance(out_len, np.ndarray) or not hasattr(out_len, "cpu") else out_len.cpu().numpy())
-        n = n.reshape(r.logp.shape)
+        n = np.asarray(_to_host(out_len)).reshape(r.logp.shape)
         return [[_qual_chars(r.qual[b, i, :int(n[b, i])], qscale, qbias) if np.isfinite(r.logp[b, i]) else ""
                  for i in range(r.logp.shape[1])] for b in range(r.logp.shape[0])]
 
@@ -2051,56 +2095,21 @@ def ctc_align_batch_raw(network_outputs, labels, label_lengths, collapse_repeats
     Arguments as ctc_score_batch_raw: band=0 aligns in the exact lattice, band=W > 0 within W labels of `paths`.
     Device tensors in: torch tensors on the same device, enqueued on torch's current stream, not synchronised.
     numpy in: numpy out."""
-    band = _check_band(band, paths)
-    h, b, y, (B, n_hyp, stride), dev, keep = _lattice_inputs(network_outputs, labels, label_lengths, lengths, paths, band,
-                                                             n_valid, input_dtype, handle)
-    if dev is not None:
-        import torch
-        start = torch.zeros((B, n_hyp, stride), dtype=torch.int32, device=dev)
-        count = torch.zeros((B, n_hyp, stride), dtype=torch.int32, device=dev)
-        qual = torch.zeros((B, n_hyp, stride), dtype=torch.float32, device=dev)
-        logp = torch.empty((B, n_hyp), dtype=torch.float64, device=dev)
-        out = nat.Alignment(start.data_ptr(), count.data_ptr(), qual.data_ptr(), logp.data_ptr())
-        h.check(h.lib.fcd_ctc_align_dev(h.ptr, C.byref(b), C.byref(y), int(bool(collapse_repeats)), band, C.byref(out)))
-        return AlignResult(start, count, qual, logp)
-    start = np.zeros((B, n_hyp, stride), np.uint32)
-    count = np.zeros((B, n_hyp, stride), np.uint32)
-    qual = np.zeros((B, n_hyp, stride), np.float32)
-    logp = np.empty((B, n_hyp), np.float64)
-    out = nat.Alignment(start.ctypes.data, count.ctypes.data, qual.ctypes.data, logp.ctypes.data)
-    h.check(h.lib.fcd_ctc_align_host(h.ptr, C.byref(b), C.byref(y), int(bool(collapse_repeats)), band, C.byref(out)))
-    return AlignResult(start, count, qual, logp)
-
-
-def _sequence_labels(sequence, alpha, what):
-    if not isinstance(sequence, str):
-        raise TypeError("argument 'sequence': expected str")
-    if any(len(a) != 1 for a in alpha[1:]):
-        raise ValueError("%s needs single-character labels" % what)
-    index = {a: i for i, a in enumerate(alpha) if i > 0}
-    try:
-        return [index[c] for c in sequence]
-    except KeyError as e:
-        raise ValueError("sequence holds %r, which is not a label of the alphabet" % e.args[0])
+    return _lattice_call("ctc", "align", network_outputs, labels, label_lengths, lengths, paths, band, n_valid, input_dtype,
+                         handle, collapse_repeats=collapse_repeats)
 
 
 def ctc_align(network_output, sequence, alphabet, collapse_repeats=True):
     """The best alignment of one string to one (T, N) float32 posterior matrix, exact lattice: -> (spans, quals, logp)
     with spans = [(start, count)] per character, quals = the mean posterior of each over its rows, logp = ln of the
     alignment's probability.  No alignment (more characters than rows, ...): ([], [], -inf)."""
-    x = _as_f32(network_output, 2, "network_output")
-    alpha = _seq_to_vec(alphabet)
-    _check_greedy_alphabet(len(alpha), x.shape[1])
-    y = _sequence_labels(sequence, alpha, "ctc_align")
-    lab = np.zeros((1, max(len(y), 1)), np.uint8)
-    lab[0, :len(y)] = y
-    r = ctc_align_batch_raw(_dense(x)[None], lab, np.array([len(y)], np.uint32), collapse_repeats)
+    x, lab, n, L = _ctc_one_read(network_output, sequence, alphabet, "ctc_align")
+    r = ctc_align_batch_raw(x, lab, n, collapse_repeats)
     logp = float(r.logp[0, 0])
     if not np.isfinite(logp):
         return [], [], logp
-    n = len(y)
-    return ([(int(s), int(c)) for s, c in zip(r.start[0, 0, :n], r.count[0, 0, :n])],
-            [float(q) for q in r.qual[0, 0, :n]], logp)
+    return ([(int(s), int(c)) for s, c in zip(r.start[0, 0, :L], r.count[0, 0, :L])],
+            [float(q) for q in r.qual[0, 0, :L]], logp)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -2117,16 +2126,13 @@ class PosteriorResult:
         self.post, self.logp = post, logp
 
     def cpu(self):
-        def c(a):
-            return a if isinstance(a, np.ndarray) else a.cpu().numpy()
-        return PosteriorResult(c(self.post), c(self.logp))
+        return PosteriorResult(_to_host(self.post), _to_host(self.logp))
 
     def conf(self, labels):
         """-> (B, n_hyp, stride) float32 numpy: the called label's share, post[r, i, k, labels[r, i, k] - 1]; 0 where the
         entry of `labels` is no label (the padding behind a labelling)."""
         post = self.cpu().post
-        lab = labels if isinstance(labels, np.ndarray) or not hasattr(labels, "cpu") else labels.cpu().numpy()
-        lab = np.asarray(lab).astype(np.int64).reshape(post.shape[:3])
+        lab = np.asarray(_to_host(labels)).astype(np.int64).reshape(post.shape[:3])
         ok = (lab >= 1) & (lab <= post.shape[3])
         col = np.where(ok, lab - 1, 0)
         return np.where(ok, np.take_along_axis(post, col[..., None], 3)[..., 0], np.float32(0.0)).astype(np.float32)
@@ -2136,8 +2142,7 @@ class PosteriorResult:
         conversion AlignResult.qstrings uses (fcd_phred); "" for a labelling without a posterior."""
         logp = self.cpu().logp
         conf = self.conf(labels)
-        n = np.asarray(out_len if isinstance(out_len, np.ndarray) or not hasattr(out_len, "cpu") else out_len.cpu().numpy())
-        n = n.reshape(logp.shape)
+        n = np.asarray(_to_host(out_len)).reshape(logp.shape)
         return [[_qual_chars(conf[b, i, :int(n[b, i])], qscale, qbias) if np.isfinite(logp[b, i]) else ""
                  for i in range(logp.shape[1])] for b in range(logp.shape[0])]
 
@@ -2153,46 +2158,23 @@ def ctc_posterior_batch_raw(network_outputs, labels, label_lengths, collapse_rep
     Limits: windows of at most 510 states (bands up to 126, exact mode up to 254 rows or labels) and N - 1 <= 8.
     Device tensors in: torch tensors on the same device, enqueued on torch's current stream, not synchronised.
     numpy in: numpy out."""
-    band = _check_band(band, paths)
-    h, b, y, (B, n_hyp, stride), dev, keep = _lattice_inputs(network_outputs, labels, label_lengths, lengths, paths, band,
-                                                             n_valid, input_dtype, handle)
-    nc = int(b.N) - 1
-    if dev is not None:
-        import torch
-        post = torch.zeros((B, n_hyp, stride, nc), dtype=torch.float32, device=dev)
-        logp = torch.empty((B, n_hyp), dtype=torch.float64, device=dev)
-        out = nat.Posterior(post.data_ptr(), logp.data_ptr())
-        h.check(h.lib.fcd_ctc_posterior_dev(h.ptr, C.byref(b), C.byref(y), int(bool(collapse_repeats)), band, C.byref(out)))
-        return PosteriorResult(post, logp)
-    post = np.zeros((B, n_hyp, stride, nc), np.float32)
-    logp = np.empty((B, n_hyp), np.float64)
-    out = nat.Posterior(post.ctypes.data, logp.ctypes.data)
-    h.check(h.lib.fcd_ctc_posterior_host(h.ptr, C.byref(b), C.byref(y), int(bool(collapse_repeats)), band, C.byref(out)))
-    return PosteriorResult(post, logp)
+    return _lattice_call("ctc", "posterior", network_outputs, labels, label_lengths, lengths, paths, band, n_valid,
+                         input_dtype, handle, collapse_repeats=collapse_repeats)
 
 
 def ctc_posterior(network_output, sequence, alphabet, collapse_repeats=True):
     """The substitution posteriors of one string against one (T, N) float32 posterior matrix, exact lattice:
     -> (post, logp) with post an (L, N-1) float32 array (row k: the posterior over alphabet[1:] at character k) and
     logp = ln P(sequence | network_output).  Argument checks as ctc_score."""
-    x = _as_f32(network_output, 2, "network_output")
-    alpha = _seq_to_vec(alphabet)
-    _check_greedy_alphabet(len(alpha), x.shape[1])
-    y = _sequence_labels(sequence, alpha, "ctc_posterior")
-    lab = np.zeros((1, max(len(y), 1)), np.uint8)
-    lab[0, :len(y)] = y
-    r = ctc_posterior_batch_raw(_dense(x)[None], lab, np.array([len(y)], np.uint32), collapse_repeats)
-    return r.post[0, 0, :len(y)].copy(), float(r.logp[0, 0])
+    x, lab, n, L = _ctc_one_read(network_output, sequence, alphabet, "ctc_posterior")
+    r = ctc_posterior_batch_raw(x, lab, n, collapse_repeats)
+    return r.post[0, 0, :L].copy(), float(r.logp[0, 0])
 
 
 # ---------------------------------------------------------------------------------------------
 # CTC deletion and insertion likelihoods of given labellings (include/fcd.h, fcd_ctc_edits_*)
 # ---------------------------------------------------------------------------------------------
 EDIT_NONE, EDIT_DELETION, EDIT_INSERTION, EDIT_SUBSTITUTION = 0, 1, 2, 3
-
-
-def _host_array(a):
-    return np.asarray(a if isinstance(a, np.ndarray) or not hasattr(a, "cpu") else a.cpu().numpy())
 
 
 class EditResult:
@@ -2207,9 +2189,7 @@ class EditResult:
         self.deletion, self.insertion, self.logp = deletion, insertion, logp
 
     def cpu(self):
-        def c(a):
-            return a if isinstance(a, np.ndarray) else a.cpu().numpy()
-        return EditResult(c(self.deletion), c(self.insertion), c(self.logp))
+        return EditResult(_to_host(self.deletion), _to_host(self.insertion), _to_host(self.logp))
 
     def best(self, out_len, posterior=None, labels=None):
         """The best single edit of every labelling -> (kind, position, label, log_ratio), numpy arrays of shape
@@ -2222,7 +2202,7 @@ class EditResult:
         r = self.cpu()
         B, H, S = r.deletion.shape
         nc = r.insertion.shape[3]
-        n = _host_array(out_len).astype(np.int64).reshape(B, H)
+        n = np.asarray(_to_host(out_len)).astype(np.int64).reshape(B, H)
         with np.errstate(all="ignore"):
             d = np.where((np.arange(S) < n[..., None]) & ~np.isnan(r.deletion), r.deletion.astype(np.float64), -np.inf)
             ok = (np.arange(S + 1) <= n[..., None])[..., None] & ~np.isnan(r.insertion)
@@ -2231,7 +2211,7 @@ class EditResult:
                 if labels is None:
                     raise ValueError("substitutions need the labels next to the PosteriorResult")
                 post = posterior.cpu().post.astype(np.float64)
-                lab = _host_array(labels).astype(np.int64).reshape(B, H, S)
+                lab = np.asarray(_to_host(labels)).astype(np.int64).reshape(B, H, S)
                 own = (lab >= 1) & (lab <= nc) & (np.arange(S) < n[..., None])
                 conf = np.take_along_axis(post, np.where(own, lab - 1, 0)[..., None], 3)
                 sub = np.log(post) - np.log(conf)
@@ -2263,24 +2243,8 @@ def ctc_edits_batch_raw(network_outputs, labels, label_lengths, collapse_repeats
     Limits: windows of at most 510 states (bands up to 126, exact mode up to 254 rows or labels) and N - 1 <= 8.
     Device tensors in: torch tensors on the same device, enqueued on torch's current stream, not synchronised.
     numpy in: numpy out."""
-    band = _check_band(band, paths)
-    h, b, y, (B, n_hyp, stride), dev, keep = _lattice_inputs(network_outputs, labels, label_lengths, lengths, paths, band,
-                                                             n_valid, input_dtype, handle)
-    nc = int(b.N) - 1
-    if dev is not None:
-        import torch
-        dele = torch.zeros((B, n_hyp, stride), dtype=torch.float32, device=dev)
-        ins = torch.zeros((B, n_hyp, stride + 1, nc), dtype=torch.float32, device=dev)
-        logp = torch.empty((B, n_hyp), dtype=torch.float64, device=dev)
-        out = nat.Edits(dele.data_ptr(), ins.data_ptr(), logp.data_ptr())
-        h.check(h.lib.fcd_ctc_edits_dev(h.ptr, C.byref(b), C.byref(y), int(bool(collapse_repeats)), band, C.byref(out)))
-        return EditResult(dele, ins, logp)
-    dele = np.zeros((B, n_hyp, stride), np.float32)
-    ins = np.zeros((B, n_hyp, stride + 1, nc), np.float32)
-    logp = np.empty((B, n_hyp), np.float64)
-    out = nat.Edits(dele.ctypes.data, ins.ctypes.data, logp.ctypes.data)
-    h.check(h.lib.fcd_ctc_edits_host(h.ptr, C.byref(b), C.byref(y), int(bool(collapse_repeats)), band, C.byref(out)))
-    return EditResult(dele, ins, logp)
+    return _lattice_call("ctc", "edits", network_outputs, labels, label_lengths, lengths, paths, band, n_valid, input_dtype,
+                         handle, collapse_repeats=collapse_repeats)
 
 
 def ctc_edits(network_output, sequence, alphabet, collapse_repeats=True):
@@ -2288,14 +2252,9 @@ def ctc_edits(network_output, sequence, alphabet, collapse_repeats=True):
     -> (deletion, insertion, logp) with deletion an (L,) and insertion an (L + 1, N-1) float32 array of log-ratios
     (insertion[g, c - 1]: alphabet[c] inserted before character g) and logp = ln P(sequence | network_output).  Argument
     checks as ctc_score."""
-    x = _as_f32(network_output, 2, "network_output")
-    alpha = _seq_to_vec(alphabet)
-    _check_greedy_alphabet(len(alpha), x.shape[1])
-    y = _sequence_labels(sequence, alpha, "ctc_edits")
-    lab = np.zeros((1, max(len(y), 1)), np.uint8)
-    lab[0, :len(y)] = y
-    r = ctc_edits_batch_raw(_dense(x)[None], lab, np.array([len(y)], np.uint32), collapse_repeats)
-    return r.deletion[0, 0, :len(y)].copy(), r.insertion[0, 0, :len(y) + 1].copy(), float(r.logp[0, 0])
+    x, lab, n, L = _ctc_one_read(network_output, sequence, alphabet, "ctc_edits")
+    r = ctc_edits_batch_raw(x, lab, n, collapse_repeats)
+    return r.deletion[0, 0, :L].copy(), r.insertion[0, 0, :L + 1].copy(), float(r.logp[0, 0])
 
 
 # ---------------------------------------------------------------------------------------------
@@ -2315,32 +2274,8 @@ def crf_score_batch_raw(network_outputs, init_states, labels, label_lengths, len
     returns the same bits as wide=False.
     Device tensors in: a torch tensor on the same device, enqueued on torch's current stream, not synchronised.
     numpy in: numpy out."""
-    band = _check_band(band, paths)
-    h, b, y, (B, n_hyp, stride), dev, keep = _lattice_inputs(network_outputs, labels, label_lengths, lengths, paths, band,
-                                                             n_valid, input_dtype, handle, init_states)
-    init = keep[-1]
-    if dev is not None:
-        import torch
-        out = torch.empty((B, n_hyp), dtype=torch.float64, device=dev)
-        if wide:  # (the handle is this thread's: nothing else calls between the switch and the call)
-            h.set_crf_lattice_wide(True)
-        try:
-            h.check(h.lib.fcd_crf_score_dev(h.ptr, C.byref(b), C.c_void_p(init.data_ptr()), int(init.shape[1]),
-                                            int(init.shape[1]), C.byref(y), band, C.c_void_p(out.data_ptr())))
-        finally:
-            if wide:
-                h.set_crf_lattice_wide(False)
-        return out
-    out = np.empty((B, n_hyp), np.float64)
-    if wide:
-        h.set_crf_lattice_wide(True)
-    try:
-        h.check(h.lib.fcd_crf_score_host(h.ptr, C.byref(b), init.ctypes.data, init.shape[1], init.shape[1], C.byref(y), band,
-                                         out.ctypes.data))
-    finally:
-        if wide:
-            h.set_crf_lattice_wide(False)
-    return out
+    return _lattice_call("crf", "score", network_outputs, labels, label_lengths, lengths, paths, band, n_valid, input_dtype,
+                         handle, init_states, wide=wide)
 
 
 def crf_align_batch_raw(network_outputs, init_states, labels, label_lengths, lengths=None, paths=None, band=0,
@@ -2349,28 +2284,8 @@ def crf_align_batch_raw(network_outputs, init_states, labels, label_lengths, len
     is 1), the posterior of that emission (qual: what crf_greedy_search turns into its quality string) and ln of the
     alignment's probability (include/fcd.h, fcd_crf_align_*).  -> AlignResult, arrays (B, n_hyp, stride) and logp
     (B, n_hyp).  Arguments as crf_score_batch_raw."""
-    band = _check_band(band, paths)
-    h, b, y, (B, n_hyp, stride), dev, keep = _lattice_inputs(network_outputs, labels, label_lengths, lengths, paths, band,
-                                                             n_valid, input_dtype, handle, init_states)
-    init = keep[-1]
-    if dev is not None:
-        import torch
-        start = torch.zeros((B, n_hyp, stride), dtype=torch.int32, device=dev)
-        count = torch.zeros((B, n_hyp, stride), dtype=torch.int32, device=dev)
-        qual = torch.zeros((B, n_hyp, stride), dtype=torch.float32, device=dev)
-        logp = torch.empty((B, n_hyp), dtype=torch.float64, device=dev)
-        out = nat.Alignment(start.data_ptr(), count.data_ptr(), qual.data_ptr(), logp.data_ptr())
-        h.check(h.lib.fcd_crf_align_dev(h.ptr, C.byref(b), C.c_void_p(init.data_ptr()), int(init.shape[1]),
-                                        int(init.shape[1]), C.byref(y), band, C.byref(out)))
-        return AlignResult(start, count, qual, logp)
-    start = np.zeros((B, n_hyp, stride), np.uint32)
-    count = np.zeros((B, n_hyp, stride), np.uint32)
-    qual = np.zeros((B, n_hyp, stride), np.float32)
-    logp = np.empty((B, n_hyp), np.float64)
-    out = nat.Alignment(start.ctypes.data, count.ctypes.data, qual.ctypes.data, logp.ctypes.data)
-    h.check(h.lib.fcd_crf_align_host(h.ptr, C.byref(b), init.ctypes.data, init.shape[1], init.shape[1], C.byref(y), band,
-                                     C.byref(out)))
-    return AlignResult(start, count, qual, logp)
+    return _lattice_call("crf", "align", network_outputs, labels, label_lengths, lengths, paths, band, n_valid, input_dtype,
+                         handle, init_states)
 
 
 def crf_posterior_batch_raw(network_outputs, init_states, labels, label_lengths, lengths=None, paths=None, band=0,
@@ -2385,25 +2300,8 @@ def crf_posterior_batch_raw(network_outputs, init_states, labels, label_lengths,
     (S = 64, 1024, 4096 at N = 5).
     Device tensors in: torch tensors on the same device, enqueued on torch's current stream, not synchronised.
     numpy in: numpy out."""
-    band = _check_band(band, paths)
-    h, b, y, (B, n_hyp, stride), dev, keep = _lattice_inputs(network_outputs, labels, label_lengths, lengths, paths, band,
-                                                             n_valid, input_dtype, handle, init_states)
-    init = keep[-1]
-    nc = int(b.N) - 1
-    if dev is not None:
-        import torch
-        post = torch.zeros((B, n_hyp, stride, nc), dtype=torch.float32, device=dev)
-        logp = torch.empty((B, n_hyp), dtype=torch.float64, device=dev)
-        out = nat.Posterior(post.data_ptr(), logp.data_ptr())
-        h.check(h.lib.fcd_crf_posterior_dev(h.ptr, C.byref(b), C.c_void_p(init.data_ptr()), int(init.shape[1]),
-                                            int(init.shape[1]), C.byref(y), band, C.byref(out)))
-        return PosteriorResult(post, logp)
-    post = np.zeros((B, n_hyp, stride, nc), np.float32)
-    logp = np.empty((B, n_hyp), np.float64)
-    out = nat.Posterior(post.ctypes.data, logp.ctypes.data)
-    h.check(h.lib.fcd_crf_posterior_host(h.ptr, C.byref(b), init.ctypes.data, init.shape[1], init.shape[1], C.byref(y), band,
-                                         C.byref(out)))
-    return PosteriorResult(post, logp)
+    return _lattice_call("crf", "posterior", network_outputs, labels, label_lengths, lengths, paths, band, n_valid,
+                         input_dtype, handle, init_states)
 
 
 def crf_edits_batch_raw(network_outputs, init_states, labels, label_lengths, lengths=None, paths=None, band=0,
@@ -2419,27 +2317,8 @@ def crf_edits_batch_raw(network_outputs, init_states, labels, label_lengths, len
     Arguments and limits as crf_posterior_batch_raw.
     Device tensors in: torch tensors on the same device, enqueued on torch's current stream, not synchronised.
     numpy in: numpy out."""
-    band = _check_band(band, paths)
-    h, b, y, (B, n_hyp, stride), dev, keep = _lattice_inputs(network_outputs, labels, label_lengths, lengths, paths, band,
-                                                             n_valid, input_dtype, handle, init_states)
-    init = keep[-1]
-    nc = int(b.N) - 1
-    if dev is not None:
-        import torch
-        dele = torch.zeros((B, n_hyp, stride), dtype=torch.float32, device=dev)
-        ins = torch.zeros((B, n_hyp, stride + 1, nc), dtype=torch.float32, device=dev)
-        logp = torch.empty((B, n_hyp), dtype=torch.float64, device=dev)
-        out = nat.Edits(dele.data_ptr(), ins.data_ptr(), logp.data_ptr())
-        h.check(h.lib.fcd_crf_edits_dev(h.ptr, C.byref(b), C.c_void_p(init.data_ptr()), int(init.shape[1]),
-                                        int(init.shape[1]), C.byref(y), band, C.byref(out)))
-        return EditResult(dele, ins, logp)
-    dele = np.zeros((B, n_hyp, stride), np.float32)
-    ins = np.zeros((B, n_hyp, stride + 1, nc), np.float32)
-    logp = np.empty((B, n_hyp), np.float64)
-    out = nat.Edits(dele.ctypes.data, ins.ctypes.data, logp.ctypes.data)
-    h.check(h.lib.fcd_crf_edits_host(h.ptr, C.byref(b), init.ctypes.data, init.shape[1], init.shape[1], C.byref(y), band,
-                                     C.byref(out)))
-    return EditResult(dele, ins, logp)
+    return _lattice_call("crf", "edits", network_outputs, labels, label_lengths, lengths, paths, band, n_valid, input_dtype,
+                         handle, init_states)
 
 
 class OccupancyResult:
@@ -2457,24 +2336,6 @@ class OccupancyResult:
         if isinstance(self.logp, np.ndarray):
             return self
         return OccupancyResult(self.occupancy.cpu().numpy(), self.logp.cpu().numpy())
-
-
-def _occupancy_block(out, shape5, elem_strides):
-    """the caller's buffer as fcd_occupancy sees it -> (stride_row, stride_t); shape5 = (B, n_hyp, T, S, N)"""
-    B, n_hyp, T, S, N = shape5
-    if tuple(out.shape) == (B, T, S, N) and n_hyp == 1:
-        st = (elem_strides[0], elem_strides[0]) + tuple(elem_strides[1:])
-    elif tuple(out.shape) == shape5:
-        st = tuple(elem_strides)
-    else:
-        raise ValueError("out must have shape (n_reads, n_hyp, T, S, N) (or (n_reads, T, S, N) for one labelling per read)")
-    if B * n_hyp * T == 0:
-        return S * N, S * N
-    if (N > 1 and st[4] != 1) or (S > 1 and st[3] != N):
-        raise ValueError("out: the (S, N) rows must be dense")
-    if any(v < 0 for v in st) or (T > 1 and st[2] < S * N) or (n_hyp > 1 and B > 1 and st[0] != n_hyp * st[1]):
-        raise ValueError("out: labelling blocks must be evenly spaced, rows at least S * N floats apart")
-    return (st[1] if n_hyp > 1 or B == 1 else st[0]), max(st[2], S * N)
 
 
 def crf_occupancy_batch_raw(network_outputs, init_states, labels, label_lengths, lengths=None, paths=None, band=0,
@@ -2502,57 +2363,9 @@ def crf_occupancy_batch_raw(network_outputs, init_states, labels, label_lengths,
     (T, B, n_hyp, S, N) and its (B, n_hyp, T, S, N) view is returned.
     Device tensors in: torch tensors on the same device, enqueued on torch's current stream, not synchronised.
     numpy in: numpy out."""
-    band = _check_band(band, paths)
-    if accumulate and out is None:
-        raise ValueError("accumulate=True needs the buffer to add to: pass out")
-    if out is not None and time_major_out:
-        raise ValueError("time_major_out shapes the array the call allocates: pass either out or time_major_out")
-    h, b, y, (B, n_hyp, stride), dev, keep = _lattice_inputs(network_outputs, labels, label_lengths, lengths, paths, band,
-                                                             n_valid, input_dtype, handle, init_states)
-    init = keep[-1]
-    T, S, N = int(b.T), int(b.S), int(b.N)
-    shape5 = (B, n_hyp, T, S, N)
-    if dev is not None:
-        import torch
-        if out is None:
-            buf = torch.zeros((T, B, n_hyp, S, N) if time_major_out else shape5, dtype=torch.float32, device=dev)
-            occ = buf.permute(1, 2, 0, 3, 4) if time_major_out else buf
-        else:
-            if not _is_torch_cuda(out) or out.device != dev or out.dtype != torch.float32:
-                raise TypeError("out must be a float32 tensor on the inputs' device")
-            occ = out
-        sr, stt = _occupancy_block(occ, shape5, occ.stride())
-        logp = torch.empty((B, n_hyp), dtype=torch.float64, device=dev)
-        o = nat.Occupancy(occ.data_ptr(), sr, stt, float(scale), int(bool(accumulate)), logp.data_ptr())
-        if wide:  # (the handle is this thread's: nothing else calls between the switch and the call)
-            h.set_crf_lattice_wide(True)
-        try:
-            h.check(h.lib.fcd_crf_occupancy_dev(h.ptr, C.byref(b), C.c_void_p(init.data_ptr()), int(init.shape[1]),
-                                                int(init.shape[1]), C.byref(y), band, C.byref(o)))
-        finally:
-            if wide:
-                h.set_crf_lattice_wide(False)
-        h.hold_in_flight(occ, logp, *keep)
-        return OccupancyResult(occ, logp)
-    if out is None:
-        buf = np.zeros((T, B, n_hyp, S, N) if time_major_out else shape5, np.float32)
-        occ = buf.transpose(1, 2, 0, 3, 4) if time_major_out else buf
-    else:
-        if not isinstance(out, np.ndarray) or out.dtype != np.float32 or not out.flags.writeable:
-            raise TypeError("out must be a writable float32 numpy array")
-        occ = out
-    sr, stt = _occupancy_block(occ, shape5, tuple(v // 4 for v in occ.strides))
-    logp = np.empty((B, n_hyp), np.float64)
-    o = nat.Occupancy(occ.ctypes.data, sr, stt, float(scale), int(bool(accumulate)), logp.ctypes.data)
-    if wide:
-        h.set_crf_lattice_wide(True)
-    try:
-        h.check(h.lib.fcd_crf_occupancy_host(h.ptr, C.byref(b), init.ctypes.data, init.shape[1], init.shape[1], C.byref(y), band,
-                                             C.byref(o)))
-    finally:
-        if wide:
-            h.set_crf_lattice_wide(False)
-    return OccupancyResult(occ, logp)
+    return _lattice_call("crf", "occupancy", network_outputs, labels, label_lengths, lengths, paths, band, n_valid,
+                         input_dtype, handle, init_states, wide=wide, out=out, scale=scale, accumulate=accumulate,
+                         time_major_out=time_major_out)
 
 
 def ctc_occupancy_batch_raw(network_outputs, labels, label_lengths, collapse_repeats=True, lengths=None, paths=None, band=0,
@@ -2580,68 +2393,9 @@ def ctc_occupancy_batch_raw(network_outputs, labels, label_lengths, collapse_rep
     the array the call allocates is (T, B, n_hyp, N) and its (B, n_hyp, T, N) view is returned.
     Device tensors in: torch tensors on the same device, enqueued on torch's current stream, not synchronised.
     numpy in: numpy out."""
-    band = _check_band(band, paths)
-    if accumulate and out is None:
-        raise ValueError("accumulate=True needs the buffer to add to: pass out")
-    if out is not None and time_major_out:
-        raise ValueError("time_major_out shapes the array the call allocates: pass either out or time_major_out")
-    h, b, y, (B, n_hyp, stride), dev, keep = _lattice_inputs(network_outputs, labels, label_lengths, lengths, paths, band,
-                                                             n_valid, input_dtype, handle)
-    T, N = int(b.T), int(b.N)
-    shape4 = (B, n_hyp, T, N)
-
-    def block(occ, elem_strides):  # (fcd_occupancy's layout with S = 1: the (S, N) row is the row of N)
-        if occ.ndim not in (3, 4):
-            raise ValueError("out must have shape (n_reads, n_hyp, T, N) (or (n_reads, T, N) for one labelling per read)")
-        shp, st = tuple(occ.shape), tuple(elem_strides)
-        return _occupancy_block(_Shaped(shp[:-1] + (1, shp[-1])), (B, n_hyp, T, 1, N), st[:-1] + (N, st[-1]))
-    col = int(bool(collapse_repeats))
-    if dev is not None:
-        import torch
-        if out is None:
-            buf = torch.zeros((T, B, n_hyp, N) if time_major_out else shape4, dtype=torch.float32, device=dev)
-            occ = buf.permute(1, 2, 0, 3) if time_major_out else buf
-        else:
-            if not _is_torch_cuda(out) or out.device != dev or out.dtype != torch.float32:
-                raise TypeError("out must be a float32 tensor on the inputs' device")
-            occ = out
-        sr, stt = block(occ, occ.stride())
-        logp = torch.empty((B, n_hyp), dtype=torch.float64, device=dev)
-        o = nat.Occupancy(occ.data_ptr(), sr, stt, float(scale), int(bool(accumulate)), logp.data_ptr())
-        if wide:  # (the handle is this thread's: nothing else calls between the switch and the call)
-            h.set_ctc_occupancy_wide(True)
-        try:
-            h.check(h.lib.fcd_ctc_occupancy_dev(h.ptr, C.byref(b), C.byref(y), col, band, C.byref(o)))
-        finally:
-            if wide:
-                h.set_ctc_occupancy_wide(False)
-        h.hold_in_flight(occ, logp, *keep)
-        return OccupancyResult(occ, logp)
-    if out is None:
-        buf = np.zeros((T, B, n_hyp, N) if time_major_out else shape4, np.float32)
-        occ = buf.transpose(1, 2, 0, 3) if time_major_out else buf
-    else:
-        if not isinstance(out, np.ndarray) or out.dtype != np.float32 or not out.flags.writeable:
-            raise TypeError("out must be a writable float32 numpy array")
-        occ = out
-    sr, stt = block(occ, tuple(v // 4 for v in occ.strides))
-    logp = np.empty((B, n_hyp), np.float64)
-    o = nat.Occupancy(occ.ctypes.data, sr, stt, float(scale), int(bool(accumulate)), logp.ctypes.data)
-    if wide:
-        h.set_ctc_occupancy_wide(True)
-    try:
-        h.check(h.lib.fcd_ctc_occupancy_host(h.ptr, C.byref(b), C.byref(y), col, band, C.byref(o)))
-    finally:
-        if wide:
-            h.set_ctc_occupancy_wide(False)
-    return OccupancyResult(occ, logp)
-
-
-class _Shaped:
-    """what _occupancy_block reads of a buffer: its shape"""
-
-    def __init__(self, shape):
-        self.shape = shape
+    return _lattice_call("ctc", "occupancy", network_outputs, labels, label_lengths, lengths, paths, band, n_valid,
+                         input_dtype, handle, collapse_repeats=collapse_repeats, wide=wide, out=out, scale=scale,
+                         accumulate=accumulate, time_major_out=time_major_out)
 
 
 def ctc_occupancy(network_output, sequence, alphabet, collapse_repeats=True, wide=False):
@@ -2650,13 +2404,8 @@ def ctc_occupancy(network_output, sequence, alphabet, collapse_repeats=True, wid
     emits alphabet[c]; every row sums to 1) and logp = ln P(sequence | network_output).  RuntimeError where the string has
     no alignment of positive finite probability.  Argument checks as ctc_score.  wide: as ctc_occupancy_batch_raw --
     strings beyond 254 rows or characters."""
-    x = _as_f32(network_output, 2, "network_output")
-    alpha = _seq_to_vec(alphabet)
-    _check_greedy_alphabet(len(alpha), x.shape[1])
-    y = _sequence_labels(sequence, alpha, "ctc_occupancy")
-    lab = np.zeros((1, max(len(y), 1)), np.uint8)
-    lab[0, :len(y)] = y
-    r = ctc_occupancy_batch_raw(_dense(x)[None], lab, np.array([len(y)], np.uint32), collapse_repeats, wide=wide)
+    x, lab, n, _ = _ctc_one_read(network_output, sequence, alphabet, "ctc_occupancy")
+    r = ctc_occupancy_batch_raw(x, lab, n, collapse_repeats, wide=wide)
     logp = float(r.logp[0, 0])
     if not np.isfinite(logp):
         raise RuntimeError("ctc_occupancy: the sequence has no alignment of positive finite probability (ln P = %r)" % logp)
@@ -2845,9 +2594,7 @@ class _CrfViterbiResult(_CrfBatchResult):
 
     def cpu(self):
         r = BatchResult.cpu(self)  # (joins the handle's internal streams first)
-        lp = self.logp
-        return _CrfViterbiResult(r.labels, r.path, r.out_len, r.status, r.qual, r.ambiguous,
-                                 lp if lp is None or isinstance(lp, np.ndarray) else lp.cpu().numpy())
+        return _CrfViterbiResult(r.labels, r.path, r.out_len, r.status, r.qual, r.ambiguous, _to_host(self.logp))
 
 
 class BeamSearchSession:
