@@ -117,6 +117,9 @@ __device__ __forceinline__ void fifo_shift(float (&win)[kFifo], float incoming) 
 #endif
 }
 constexpr int kSeg = 64;  // nodes per traceback segment (jump-pointer spacing)
+#ifndef FCD_HL_PARTS  // (the headline step's separable forms, a bit each: ZSEL 1, WSC 2, CHB 4 -- see the kernel below)
+#define FCD_HL_PARTS 7
+#endif
 
 // Wavefronts per SIMD the register allocator is asked to leave room for (amdgpu_waves_per_eu on the kernel below; the value
 // is spelt out there: the emulator's host compiler does not take a function call inside an attribute it does not know).
@@ -248,6 +251,17 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_pe
     // the clash recount and the quicksort replay's list builder: the keyed probability word and the node word are formed, and
     // both tables written keyed, inside the rare block that reads them (beam_wave_step.inc).
     constexpr bool RAWK = R32 && HL;
+    // Three forms of the HL step that can each be put back on its own (FCD_HL_PARTS, a bit per form, for pricing one against
+    // the others; beam_wave_step.inc says at each what it replaces):
+    // ZSEL: no select where the value is already zero -- the pushed extension of a slot nobody pushed to, and the gap
+    //       probability of the slot's own and the group's spare lane under ONE mask;
+    // WSC:  the beam width is loop-carried SCALAR state -- the group mask m_grp and the two halves' widths -- recomputed in the
+    //       step's first rare block when a running half's capped candidate count differs from its width;
+    // CHB:  the new slot's child entry is gathered through bit 0 of the survivor-table entry ("the source is a child lane")
+    //       instead of being replaced behind the gather after a look at the source's kind.
+    constexpr bool ZSEL = HL && (FCD_HL_PARTS & 1) != 0;
+    constexpr bool WSC = HL && (FCD_HL_PARTS & 2) != 0;
+    constexpr bool CHB = HL && (FCD_HL_PARTS & 4) != 0;
     static_assert(!PDQ || BCAP * N > 20, "the tie order only matters above 20 candidates");
     static_assert(!PDQ || BCAP * N <= HALF - 2, "the last two entries of a half's table are never written (i_src below)");
     int n_amb = 0, n_crit = 0;
@@ -461,6 +475,15 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_pe
     // HL: the lane-constant masks the step's votes are joined with (beam_wave_step.inc)
     const uint64_t child_m = HL ? ballot(is_child) : 0ull;
     const uint64_t self_m = HL ? ballot(is_self) : 0ull;
+    // ZSEL: the lanes that hold a gap probability of their slot's own candidate -- its own lane, and the group's spare lane,
+    // which divides it (DSRC).  One lane-constant pair, joined here and not in the step.
+    const uint64_t gap_m = ZSEL ? (self_m | ballot(spare)) : 0ull;
+    // WSC: the beam width as scalar state, carried round the time loop in place of the per-lane B: the lanes q < GW * B of
+    // each half (what the step's votes are joined with as m_grp) and the two halves' widths.  The step compares each half's
+    // capped candidate count with its width and forms all three afresh, in its first rare block, only when one differs.
+    uint64_t grp_m = WSC ? ballot(i < B) : 0ull;
+    int width0 = WSC ? __builtin_amdgcn_readlane(B, 0) : 0;
+    int width1 = WSC ? __builtin_amdgcn_readlane(B, HALF & 63) : 0;
     // HL: all ones on the lower half's lanes, 0 on the upper half's -- what half_prefix_count() joins with the mask's low word.
     // (Opaque: as a known select the optimiser forms it again in every step.)
     uint32_t low_half_v = (HL && lane < HALF) ? ~0u : 0u;

@@ -17,7 +17,16 @@
         // (beam_wave.hip: child_m, self_m, collapse_m) -- and read back as lane flags with lane_in(), which costs nothing.
         // A vote on a flag DERIVED from several compares costs two vector instructions (a 0 / 1 word and its compare with 0):
         // that is what m_new, m_valid, the clash vote and the rank-domain guard were.
-        const uint64_t m_grp = HL ? ballot(i < B) : 0ull;
+        // WSC: m_grp is not voted on: it is the carried mask (beam_wave.hip: grp_m), set behind the rank of the step that last
+        // changed a half's width.  The step reads this copy to its end; grp_m itself may already belong to the next one.
+        const uint64_t m_grp = HL ? (WSC ? grp_m : ballot(i < B)) : 0ull;
+#ifdef FCD_HIPEMU  // (lockstep emulation, tests/hipemu: there the per-lane B is carried along with the scalar state)
+        if (WSC && (m_grp != ballot(i < B) || B != (hbase ? width1 : width0))) {
+            fprintf(stderr, "beam_wave: carried group mask %016llx / widths %d, %d, but lane %d holds beam width %d\n",
+                    (unsigned long long)m_grp, width0, width1, lane, B);
+            abort();
+        }
+#endif
         const uint64_t m_rep = HL ? (collapse_m & ballot((k << 2) == tipf)) : 0ull;
         const uint64_t m_ex = HL ? ballot(child >= 0) : 0ull;
         // (exists && IN-BEAM in one compare: the sign bit clear and the flag set)
@@ -66,14 +75,27 @@
         const bool stay = HL ? lane_in(m_stay, lane) : (collapse && tipf != 0 && !(ptip < thr));
         const float lpn = lp * ptip;
         const bool has_inc = HL ? lane_in(m_inc, lane) : (is_self && incv != 0);
-        const float slp = (stay ? lpn : 0.0f) + (has_inc ? inc : 0.0f);
-        const float sgp = blank ? gpn : 0.0f;
+        // ZSEL: `inc` as it arrived.  Only a slot's own lane reads slp (clp, below), and a slot's own lane is the push target of
+        // merged extensions alone -- every other lane pushes to its group's spare lane or, an idle lane, to itself (dummy_a) --
+        // so one that nobody pushed to is a lane no ds_permute source addresses, and such a lane receives 0: bit pattern 0, the
+        // +0.0f the select put there.  (tests/hipemu's ds_permute does the same.)
+#ifdef FCD_HIPEMU  // (lockstep emulation, tests/hipemu)
+        if (ZSEL && is_self && incv == 0 && __float_as_int(inc) != 0) {
+            fprintf(stderr, "beam_wave: lane %d received no extension but holds the word %08x\n", lane, (unsigned)__float_as_int(inc));
+            abort();
+        }
+#endif
+        const float slp = (stay ? lpn : 0.0f) + (ZSEL ? inc : (has_inc ? inc : 0.0f));
+        // ZSEL: sgp under "a slot's own or a group's spare lane, and the blank passes" -- zero on child and idle lanes by the mask,
+        // so it IS cgp on every lane, and the spare lane's arm of dv (below) as before.  (A spare lane's prob is then
+        // contrib + sgp instead of contrib: no lane but a candidate's has its prob read, and a spare lane holds none.)
+        const float sgp = (ZSEL ? lane_in(gap_m & m_blank, lane) : blank) ? gpn : 0.0f;
         const bool svalid = grp && is_self && (blank || stay || has_inc);
 
         // (svalid / cvalid already carry is_self / is_child)
         const bool valid = HL ? lane_in(m_val, lane) : (svalid || (cvalid && !merged));
         const float clp = is_self ? slp : contrib;
-        const float cgp = is_self ? sgp : 0.0f;
+        const float cgp = ZSEL ? sgp : (is_self ? sgp : 0.0f);
         const float prob = clp + cgp;
 
         const uint64_t m_isnew = m_cv & ~m_ex;  // (HL)
@@ -269,8 +291,17 @@
         // ---- search.rs:261-277 ----
         // (key != 0 <=> valid && act: a vote on a compare costs one instruction, a vote on a derived flag two)
         const uint64_t m_valid = HL ? m_val : ballot(key != 0ull);
+        // (WSC: read only inside the rare blocks, where the compiler forms it)
         int n_valid = RPW == 1 ? popc64(m_valid)
                                : __builtin_popcount(hbase ? (uint32_t)(m_valid >> 32) : (uint32_t)m_valid);
+        // WSC: what the every-step path keeps of the width -- the two halves' candidate counts, capped, against the carried
+        // widths: four scalar counts and minima, two scalar differences.  A half whose width changes has a non-zero word.
+        const int cap0 = WSC ? min(__builtin_popcount((uint32_t)m_valid), beam_size) : 0;
+        const int cap1 = WSC ? min(__builtin_popcount((uint32_t)(m_valid >> 32)), beam_size) : 0;
+        // (WSC: the one later reader of m_grp, the eviction mask, takes its part here, so that the carried mask is dead when the
+        // block below forms the next step's and the two need not live side by side)
+        const uint64_t m_cgrp = WSC ? (child_m & m_grp) : 0ull;
+        const uint64_t m_width = WSC ? (((uint64_t)(uint32_t)(cap1 ^ width1) << 32) | (uint32_t)(cap0 ^ width0)) : 0ull;
         // Everything that ends a read is rare: one wave-wide test, the bookkeeping behind it.
         const bool is_nan = valid && prob != prob;
         // HL: a candidate whose probability word is outside the range on which the f32 count is exact (device_utils.h,
@@ -281,9 +312,19 @@
         // its sign and payload (fcd_rankf_outside_m), so the guard's vote stands in for "some candidate is a NaN" here and the
         // every-step path takes no vote on prob != prob: a guarded step without a NaN enters the block and leaves it unchanged.
         // (HL: marked unlikely, so that the block sits behind the loop and the every-step path falls through)
-        if (HL ? __builtin_expect((((ballot(n_valid == 0)) | m_guard) & alive_m) != 0ull, 0)
+        // WSC: "some running half's width changes" takes the place of the vote on n_valid == 0 -- an empty half's capped count
+        // is 0, and a running half's width is at least 1 (it starts at 1, and a half left with none stops running in that
+        // very step).  A half that does not run never changes: its group mask is empty, so it has no candidates and width 0.
+        if (HL ? __builtin_expect((((WSC ? m_width : ballot(n_valid == 0)) | m_guard) & alive_m) != 0ull, 0)
                : (ballot(act && (n_valid == 0 || is_nan)) != 0ull)) {
             const bool act = HL ? lane_in(alive_m, lane) : act0;
+            if (WSC) {
+                // the per-lane count, formed HERE from a word the optimiser cannot see through: shared with the count behind
+                // the block, it is computed in front of the branch, in every step
+                uint32_t half_w = hbase ? (uint32_t)(m_valid >> 32) : (uint32_t)m_valid;
+                FCD_OPAQUE_V(half_w);
+                n_valid = __builtin_popcount(half_w);
+            }
             const uint64_t m_nan = ballot(is_nan);
             const bool any_nan = RPW == 1 ? m_nan != 0ull
                                           : (hbase ? (uint32_t)(m_nan >> 32) : (uint32_t)m_nan) != 0u;
@@ -301,10 +342,20 @@
                 if (UNI) n_valid = 0;  // the failed read keeps an empty beam from here on
             }
             if (HL) alive_m &= ~ballot(f_nan || f_empty);
+            if (WSC) {
+                // the next step's width, per half, from the per-lane count (0 by now for a half that has just failed); a
+                // half whose width stays is written over with what it holds
+                const int bn = n_valid < beam_size ? n_valid : beam_size;
+                grp_m = ballot(i < bn);
+                width0 = __builtin_amdgcn_readlane(bn, 0);
+                width1 = __builtin_amdgcn_readlane(bn, HALF & 63);
+            }
         }
         const bool go = UNI ? true : (act && alive);  // this half completes the step
 
-        const int Bn = n_valid < beam_size ? n_valid : beam_size;
+        // WSC: the count and the width the later rare blocks read (the returning-node reload, the recount, the replay) are
+        // functions of masks and scalar state the step holds anyway, and are formed where those blocks are entered (below)
+        const int Bn = WSC ? (hbase ? width1 : width0) : (n_valid < beam_size ? n_valid : beam_size);
         // ---- keep the IN-BEAM/slot bits of every child entry current ----
         // an entry whose node is a beam entry follows that entry's own candidate: where did it go?
         // selflag = rank | 16 for a kept candidate, 0 otherwise: shifted to kSlotShift it IS the (slot, IN-BEAM)
@@ -318,6 +369,9 @@
         int selflag, fate, own, src_a, e_min, top_a, gp_a;
         int child_s;  // the entry after this step's bookkeeping
         int n_node, n_meta, n_state, n_jump, n_child;
+#ifdef FCD_HIPEMU
+        int n_child_kind = -1;
+#endif
         float n_lp, n_gp, top;
         float dv = 0.0f;  // DSRC: what this lane divides by the top probability (not const: PARK)
         uint32_t tie0 = 0, tie1 = 1;
@@ -329,6 +383,7 @@
         // ranks and settles again.  (An eviction store of the first pass that the second does not repeat leaves a row
         // in HBM nobody reads before it is written again: rows are read back only after their node's LAST eviction.)
         auto settle_table = [&]() __attribute__((always_inline)) {
+            int m_chw = 0;  // (CHB: bit 0 of this lane's source entry, spread over the word)
             sel = valid && go && rank < beam_size;
             if (HL) {  // (a statement of its own: folded into the line above it changed the code of every other instantiation)
                 m_sel = m_val & ballot(rank < beam_size);
@@ -407,6 +462,7 @@
                     int m_ch = (int)((uint32_t)e_src << 31) >> 31;
                     FCD_OPAQUE_VQ(m_ch);
                     gp_a = (m_ch & zero_a) | (~m_ch & (src_a + ((GW - 1) << 2)));
+                    if (CHB) m_chw = m_ch;
                 } else {
                     gp_a = (e_src & 1) ? zero_a : src_a + ((GW - 1) << 2);
                 }
@@ -418,14 +474,28 @@
             if (HL) {
                 // (`own` is not looked up: "this group's own candidate was dropped" is a function of m_sel -- settle_gather)
                 fate = __builtin_amdgcn_ds_bpermute(tgt_a, selflag);
-                own = 0;
+                own = m_chw;  // (0 without CHB)
             }
             if (PDQ) {
                 tie0 = (uint32_t)srcs[kTie + i_src];
                 tie1 = (uint32_t)srcs[kTie + i_src + 1];
             }
         };
+        // CHB: where the new slot's child entry is gathered from, picked by the same spread bit as gp_a.  The bit is set exactly
+        // on the entries of child lanes (ent_lo, beam_wave.hip; a candidate sits on a slot's own lane or on a child lane, checked
+        // at the top of the step), and a child lane's candidate -- a node entering the beam for the first time, or one coming
+        // back, whose row the reload block below fetches -- hands over a child entry of -1.  That is what the first lane of the
+        // half holds in `child` at all times: a slot's own lane and a spare lane start with -1 and, here, only ever gather from
+        // that lane or from the source group's own / spare lane.  A source that is a slot's own lane is read at the source
+        // group's lane k as before.
+        // (The spread bit leaves settle_table() in `own`, which the HL step does not look up and both lambdas already name, and
+        // the address takes its place here, in a lambda of its own: a variable more in settle_table() or settle_gather() would
+        // change their closures' layout, which reaches the code of every other instantiation.)
+        auto child_source = [&]() __attribute__((always_inline)) {
+            if (CHB) own = (own & hbase_a) | (~own & (src_a + (k << 2)));
+        };
         settle_table();
+        child_source();
         // What a candidate hands to its new slot is packed HERE, behind the survivor table's wave barrier: the barrier is
         // a scheduling boundary, and ahead of it these dozen instructions sit on the step's dependent chain in front of
         // the table's LDS round trip instead of under it (r06: +2.4 % of the kernel when they moved ahead of it in r04,
@@ -492,7 +562,7 @@
                         }
                     }
 #endif
-                    const uint64_t m_evict = child_m & m_grp & ~m_own1;
+                    const uint64_t m_evict = (WSC ? m_cgrp : (child_m & m_grp)) & ~m_own1;
                     // (named, not read: the lambda captures its variables in the order it names them, and that order reaches
                     // the register allocation of every other instantiation.  `own` stood here.)
                     (void)own;
@@ -513,7 +583,10 @@
                 n_node = __builtin_amdgcn_ds_bpermute(src_a, id);
                 n_state = CRF ? __builtin_amdgcn_ds_bpermute(src_a, statec) : 0;
                 n_jump = __builtin_amdgcn_ds_bpermute(src_a, jumpc);
-                n_child = __builtin_amdgcn_ds_bpermute(src_a + (k << 2), child_s);  // meaningful when the source is a self lane
+                n_child = __builtin_amdgcn_ds_bpermute(CHB ? own : src_a + (k << 2), child_s);  // (without CHB: meaningful when the source is a self lane)
+#ifdef FCD_HIPEMU  // (lockstep emulation, tests/hipemu: the gather without CHB, for the check in kinds())
+                n_child_kind = __builtin_amdgcn_ds_bpermute(src_a + (k << 2), child_s);
+#endif
                 stamp_i(5, n_meta);  // survivors gathered into rank order
                 const float quot = dv / top;
                 n_lp = __int_as_float(__builtin_amdgcn_ds_bpermute(src_a, __float_as_int(quot)));
@@ -533,10 +606,20 @@
         settle_gather();
         int n_kind;
         bool reload;
+        // (CHB: n_child arrives final -- the gather's address has looked at the source, so nothing here looks at its kind)
         auto kinds = [&]() __attribute__((always_inline)) {
             n_kind = n_meta & 3;
-            if (n_kind == 1 || !is_child) n_child = -1;
+            if (CHB) {
+            } else if (n_kind == 1 || !is_child) n_child = -1;
             reload = go && i < Bn && n_kind == 2 && is_child;
+#ifdef FCD_HIPEMU  // (lockstep emulation, tests/hipemu: CHB against the look at the kind, on every lane of a running group
+                   // that the reload block does not overwrite)
+            if (CHB && !idle && i < Bn && !reload && n_child != ((n_kind == 1 || !is_child) ? -1 : n_child_kind)) {
+                fprintf(stderr, "beam_wave: lane %d gathered the child entry %08x, the source's kind %d says %08x\n", lane,
+                        (unsigned)n_child, n_kind, (unsigned)((n_kind == 1 || !is_child) ? -1 : n_child_kind));
+                abort();
+            }
+#endif
         };
         kinds();
         // Two rare things share ONE branch (every instruction and, more so, every wait added to the step shows in the
@@ -564,6 +647,13 @@
         const uint64_t m_hint = (PDQ && !R32) ? (ballot(tie0 == tie1) & ballot(tie_lim < n_valid)) : 0ull;
         if (__builtin_expect((m_k2 | m_hint | m_clash) != 0ull, 0)) {
             uint64_t m_tied = m_hint;
+            if (WSC) {
+                // the per-lane count as the first rare block left it: the count of a half that runs, 0 for one that does not or
+                // has just failed (alive_m).  (From an opaque word, like the first block's: otherwise it is formed in every step.)
+                uint32_t half_w = hbase ? (uint32_t)(m_valid >> 32) : (uint32_t)m_valid;
+                FCD_OPAQUE_V(half_w);
+                n_valid = lane_in(alive_m, lane) ? __builtin_popcount(half_w) : 0;
+            }
             if (R32 && m_clash != 0ull) {
                 if (RAWK) {
                     // The recount, the PDQ hint's list builder, the quicksort replay and the read-back of `key` behind it
@@ -599,6 +689,7 @@
                 }
                 rank = ex;
                 settle_table();
+                child_source();
                 settle_gather();
                 kinds();
                 if (PDQ) m_tied = ballot(tie0 == tie1) & ballot(tie_lim < n_valid);
@@ -793,6 +884,7 @@
                     if (mine && key != 0ull) rank = newrank[lane_r];
                     }
                     settle_table();
+                    child_source();
                     settle_gather();
                     kinds();
                 }
@@ -848,6 +940,13 @@
             depth = HL ? (n_meta & ~0xFF) : (n_meta >> 5);  // (HL: still shifted up by 8)
             jump = n_jump;
             child = n_child;
-            B = Bn;
+            if (!WSC) B = Bn;
+#ifdef FCD_HIPEMU  // (lockstep emulation, tests/hipemu: the per-lane width, formed from the count as without WSC, for the check
+                   // of the carried scalar state at the top of the next step)
+            if (WSC) {
+                const int n_now = lane_in(alive_m, lane) ? __builtin_popcount(hbase ? (uint32_t)(m_valid >> 32) : (uint32_t)m_valid) : 0;
+                B = n_now < beam_size ? n_now : beam_size;
+            }
+#endif
         }
         stamp_f(6, lp);  // row reload, top, the two divisions, state update
