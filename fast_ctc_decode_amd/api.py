@@ -7,8 +7,11 @@ they decode many reads per launch (numpy -> staged through the C ABI's *_host en
 torch tensors on an AMD GPU -> zero-copy through the *_dev entry points on the tensor's
 current stream).  All searching happens on the GPU: there is no CPU fallback.
 """
+import collections
 import contextlib
 import ctypes as C
+import math
+import operator
 
 import numpy as np
 
@@ -1776,6 +1779,10 @@ def _check_band(band, paths):
     return int(band)
 
 
+# the arrays a lattice call's structs point into (what _lattice_inputs keeps alive); lengths: the read lengths as resolved
+_Kept = collections.namedtuple("_Kept", "x labels label_lengths paths n_valid lengths init")
+
+
 def _lattice_inputs(network_outputs, labels, label_lengths, lengths, paths, band, n_valid, input_dtype, handle,
                     init_states=None):
     """The argument handling ctc_score_batch_raw, ctc_align_batch_raw and their CRF counterparts share.  -> (handle,
@@ -1826,7 +1833,7 @@ def _lattice_inputs(network_outputs, labels, label_lengths, lengths, paths, band
         y = nat.Labellings(lab.data_ptr(), ylen.data_ptr(), nv.data_ptr() if nv is not None else None,
                            pth.data_ptr() if pth is not None else None, n_hyp, stride)
         h.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-        return h, b, y, (B, n_hyp, stride), dev, (x, lab, ylen, pth, nv, lengths, init)
+        return h, b, y, (B, n_hyp, stride), dev, _Kept(x, lab, ylen, pth, nv, lengths, init)
     network_outputs, lengths = _ragged(network_outputs, lengths, nd)
     x = _stack_host(network_outputs, nd)
     B, T, N = x.shape[0], x.shape[1], x.shape[-1]
@@ -1851,7 +1858,7 @@ def _lattice_inputs(network_outputs, labels, label_lengths, lengths, paths, band
     b = _host_batch(x, crf, l, input_dtype)
     y = nat.Labellings(lab.ctypes.data, ylen.ctypes.data, nv.ctypes.data if nv is not None else None,
                        pth.ctypes.data if pth is not None else None, n_hyp, stride)
-    return h, b, y, (B, n_hyp, stride), None, (x, lab, ylen, pth, nv, l, init)
+    return h, b, y, (B, n_hyp, stride), None, _Kept(x, lab, ylen, pth, nv, l, init)
 
 
 class _Arrays:
@@ -1874,6 +1881,11 @@ class _Arrays:
     def empty(self, shape, kind):
         return self._new("empty", shape, kind)
 
+    def full(self, shape, kind, value):
+        a = self.empty(shape, kind)
+        a[...] = value
+        return a
+
     def ptr(self, a):
         return a.ctypes.data if self.dev is None else a.data_ptr()
 
@@ -1891,6 +1903,39 @@ def _align_out(xp, b, shape):
     logp = xp.empty(shape[:2], "f64")
     out = nat.Alignment(xp.ptr(start), xp.ptr(count), xp.ptr(qual), xp.ptr(logp))
     return C.byref(out), AlignResult(start, count, qual, logp)
+
+
+def _spot_rows(xp, b, B, lengths, rows):
+    """rows = (lo, hi) with Python-slice semantics on every read's own length (negatives count from its end) -> the
+    (row_begin, row_end) arrays of fcd_spot, u32 (B,); rows None: (None, None), the whole read"""
+    if rows is None:
+        return None, None
+    lo, hi = rows
+    T = int(b.T)
+    if xp.dev is None:
+        Tr = np.full(B, T, np.int64) if lengths is None else np.clip(lengths, 0, T)
+    else:
+        import torch
+        Tr = torch.full((B,), T, dtype=torch.int64, device=xp.dev) if lengths is None else lengths.clamp(0, T)
+
+    def edge(v, default):
+        if v is None:
+            return default
+        v = operator.index(v)
+        e = (Tr + v).clip(0) if v < 0 else Tr.clip(max=v)
+        return e.astype(np.uint32) if xp.dev is None else e.to(torch.int32)
+    return edge(lo, xp.zeros((B,), "u32")), edge(hi, Tr.astype(np.uint32) if xp.dev is None else Tr.to(torch.int32))
+
+
+def _spot_out(xp, b, shape, lengths=None, rows=None, track=False):
+    start, count, qual = xp.zeros(shape, "u32"), xp.zeros(shape, "u32"), xp.zeros(shape, "f32")
+    logp, end = xp.empty(shape[:2], "f64"), xp.empty(shape[:2], "u32")
+    trk = xp.full(shape[:2] + (int(b.T),), "f32", -math.inf) if track else None  # (rows outside the range stay -inf)
+    begin, stop = _spot_rows(xp, b, shape[0], lengths, rows)
+    out = nat.Spot(xp.ptr(start), xp.ptr(count), xp.ptr(qual), xp.ptr(logp), xp.ptr(end),
+                   xp.ptr(trk) if track else None, int(b.T), xp.ptr(begin) if rows is not None else None,
+                   xp.ptr(stop) if rows is not None else None)
+    return C.byref(out), SpotResult(AlignResult(start, count, qual, logp), end, trk, (begin, stop))
 
 
 def _posterior_out(xp, b, shape):
@@ -1966,7 +2011,7 @@ def _occupancy_out(xp, b, shape, has_S, out=None, scale=1.0, accumulate=False, t
 
 
 _LATTICE_BUILDERS = {"score": _score_out, "align": _align_out, "posterior": _posterior_out, "edits": _edits_out,
-                     "occupancy": _occupancy_out}
+                     "occupancy": _occupancy_out, "spot": _spot_out}
 
 
 @contextlib.contextmanager
@@ -1987,9 +2032,10 @@ def _wide_switch(h, model, wide):
 
 def _lattice_call(model, kind, network_outputs, labels, label_lengths, lengths, paths, band, n_valid, input_dtype, handle,
                   init_states=None, collapse_repeats=True, wide=False, **out_args):
-    """The one body of the ten labelling-lattice calls: fcd_<model>_<kind>_dev for device tensors, _host for numpy, with
+    """The one body of the labelling-lattice calls: fcd_<model>_<kind>_dev for device tensors, _host for numpy, with
     model "ctc" (network_outputs (B,T,N), collapse_repeats) or "crf" ((B,T,S,N) and init_states), kind one of
-    _LATTICE_BUILDERS; out_args: the occupancy calls' out, scale, accumulate and time_major_out.  -> what the call returns."""
+    _LATTICE_BUILDERS ("spot": CTC only); out_args: the occupancy calls' out, scale, accumulate and time_major_out, the
+    spotting call's rows and track.  -> what the call returns."""
     band = _check_band(band, paths)
     if kind == "occupancy":
         _check_occupancy_out(**out_args)
@@ -1997,15 +2043,25 @@ def _lattice_call(model, kind, network_outputs, labels, label_lengths, lengths, 
     h, b, y, shape, dev, keep = _lattice_inputs(network_outputs, labels, label_lengths, lengths, paths, band, n_valid,
                                                 input_dtype, handle, init_states)
     xp = _Arrays(dev)
+    if kind == "spot":
+        out_args["lengths"] = keep.lengths  # (rows counts from every read's own length)
     out, result = _LATTICE_BUILDERS[kind](xp, b, shape, **out_args)
     if model == "crf":
         init = keep[-1]
         args = (C.byref(b), C.c_void_p(xp.ptr(init)), int(init.shape[1]), int(init.shape[1]), C.byref(y), band, out)
     else:
         args = (C.byref(b), C.byref(y), int(bool(collapse_repeats)), band, out)
-    fn = getattr(h.lib, "fcd_%s_%s_%s" % (model, kind, "host" if dev is None else "dev"))
+    spot_dev = kind == "spot" and dev is not None  # (include/fcd.h: fcd_ctc_align_dev under the handle's fcd_set_ctc_spot)
+    fn = getattr(h.lib, "fcd_%s_%s_%s" % (model, "align" if spot_dev else kind, "host" if dev is None else "dev"))
     with _wide_switch(h, model, wide):
-        h.check(fn(h.ptr, *args))
+        if spot_dev:
+            h.check(h.lib.fcd_set_ctc_spot(h.ptr, out))
+            args = args[:-1] + (C.cast(out, C.POINTER(nat.Alignment)),)  # (fcd_spot begins with fcd_alignment's four pointers)
+        try:
+            h.check(fn(h.ptr, *args))
+        finally:
+            if spot_dev:
+                h.lib.fcd_set_ctc_spot(h.ptr, None)
     if kind == "occupancy" and dev is not None:
         h.hold_in_flight(result.occupancy, result.logp, *keep)
     return result
@@ -2110,6 +2166,76 @@ def ctc_align(network_output, sequence, alphabet, collapse_repeats=True):
         return [], [], logp
     return ([(int(s), int(c)) for s, c in zip(r.start[0, 0, :L], r.count[0, 0, :L])],
             [float(q) for q in r.qual[0, 0, :L]], logp)
+
+
+# ---------------------------------------------------------------------------------------------
+# CTC motif spotting: where a known sequence sits in a read (include/fcd.h, fcd_ctc_spot_*)
+# ---------------------------------------------------------------------------------------------
+NO_HIT = 0xFFFFFFFF
+
+
+class SpotResult:
+    """Outcome of ctc_spot_batch_raw, for motif i of read r: the best hit spans rows start[r, i] .. end[r, i] (both
+    inclusive, absolute rows of the read; NO_HIT -- -1 in a device result's int32, the same 32 bits -- where there is
+    none), logp[r, i] (float64) is ln of its probability, mean_logp[r, i] = logp / (end - start + 1) the same per row;
+    spans is the hit's AlignResult (start, count, qual of every label of the motif, (B, M, stride)); track[r, i, t]
+    (float32, (B, M, T), None unless asked for) is ln of the best hit that ENDS at row t, -inf where there is none and
+    outside the range.  numpy for host inputs, torch tensors (same device) for device inputs."""
+
+    def __init__(self, spans, end, track, rows=(None, None)):
+        self.spans, self.end, self.track, self.logp = spans, end, track, spans.logp
+        self._rows = rows  # (row_begin, row_end): alive as long as the result
+
+    @property
+    def start(self):
+        first = self.spans.start[..., 0]
+        if isinstance(first, np.ndarray):
+            return np.where(self.end == NO_HIT, self.end, first)
+        return first.where(self.end != -1, self.end)
+
+    @property
+    def mean_logp(self):
+        # (no hit: start = end = NO_HIT, one "row", logp as it is)
+        wide = (lambda a: a.astype(np.float64)) if isinstance(self.end, np.ndarray) else (lambda a: a.double())
+        return self.logp / (wide(self.end) - wide(self.start) + 1.0)
+
+    def cpu(self):
+        end = _to_host(self.end)
+        return SpotResult(self.spans.cpu(), end if end.dtype == np.uint32 else end.view(np.uint32), _to_host(self.track))
+
+
+def ctc_spot_batch_raw(network_outputs, motifs, motif_lengths, collapse_repeats=True, lengths=None, rows=None,
+                       track=False, input_dtype=None, handle=None):
+    """CTC motif spotting: where each of M known sequences sits in every read -- the best alignment of the motif to ANY
+    run of consecutive rows, both ends free (include/fcd.h, fcd_ctc_spot_*).  -> SpotResult, arrays (B, M, ...).
+
+    motifs (M, stride) uint8 label indices 1 .. N-1 with motif_lengths (M,), shared by all reads.  rows=(lo, hi) looks
+    only in network_outputs[r, lo:hi] of every read, Python-slice semantics on the read's own length (lengths):
+    rows=(0, 400) is the head of every read, rows=(-400, None) its tail.  track=True also returns ln of the best hit
+    ending at every row: threshold it to find every occurrence.  Device tensors in: torch tensors on the same device,
+    enqueued on torch's current stream, not synchronised.  numpy in: numpy out."""
+    m = np.asarray(_to_host(motifs), np.uint8)
+    if m.ndim != 2:
+        raise ValueError("motifs must have shape (n_motifs, stride)")
+    if rows is not None and (not isinstance(rows, (tuple, list)) or len(rows) != 2):
+        raise ValueError("rows must be a pair (lo, hi)")
+    B = len(network_outputs)
+    n = np.asarray(_to_host(motif_lengths), np.uint32).reshape(-1)
+    if n.size != m.shape[0]:
+        raise ValueError("motif_lengths must have one entry per motif")
+    return _lattice_call("ctc", "spot", network_outputs, np.tile(m[None], (B, 1, 1)), np.tile(n[None], (B, 1)), lengths,
+                         None, 0, None, input_dtype, handle, collapse_repeats=collapse_repeats, rows=rows, track=bool(track))
+
+
+def ctc_spot(network_output, motif, alphabet, collapse_repeats=True, rows=None):
+    """Where one string sits in one (T, N) float32 posterior matrix: -> (start, end, logp), the rows (inclusive) of its
+    best occurrence and ln of that alignment's probability; None where there is none (an empty motif, more characters
+    than rows, ...).  rows=(lo, hi): look in network_output[lo:hi] only."""
+    x, lab, n, _ = _ctc_one_read(network_output, motif, alphabet, "ctc_spot")
+    r = ctc_spot_batch_raw(x, lab, n, collapse_repeats, rows=rows)
+    if int(r.end[0, 0]) == NO_HIT:
+        return None
+    return int(r.start[0, 0]), int(r.end[0, 0]), float(r.logp[0, 0])
 
 
 # ---------------------------------------------------------------------------------------------

@@ -1944,6 +1944,7 @@ struct LatticeCall {
     const fcd_occupancy *occ = nullptr;
     bool wide = false;  // (CTC occupancy) fcd_set_ctc_occupancy_wide: windows beyond the registers walk score_lds_kernel
     bool crf_wide = false;  // (CRF score, occupancy) fcd_set_crf_lattice_wide: windows beyond 512 states walk in LDS
+    const fcd_spot *spot = nullptr;  // (CTC align) fcd_ctc_spot_*: `out` holds its first four pointers
 };
 
 // the call is one of those the CRF switch covers AND its window is beyond the registers: every other call is what it is
@@ -1959,8 +1960,15 @@ size_t occupancy_span(const fcd_batch *in, const fcd_labellings *y, const fcd_oc
     return (size_t)((in->n_reads * y->n_hyp - 1) * o->stride_row + (in->T - 1) * o->stride_t + in->S * in->N);
 }
 
+// floats from the first to the last element the call may address in spot->track (0: none)
+size_t track_span(const fcd_batch *in, const fcd_labellings *y, const fcd_spot *s) {
+    const size_t n_rows = (size_t)in->n_reads * (size_t)y->n_hyp;
+    return n_rows && s->track ? (n_rows - 1) * (size_t)s->track_stride + (size_t)in->T : 0;
+}
+
 int lattice_check(fcd_handle *h, const LatticeCall &c) {
     if (c.align && !c.out) return fail(h, FCD_E_INVALID, "null alignment");
+    if (c.spot && c.band != 0) return fail(h, FCD_E_INVALID, "ctc_spot: band must be 0 (the motif is looked for in the exact lattice)");
     if (c.posterior && !c.post) return fail(h, FCD_E_INVALID, "null posterior");
     if (c.edit && !c.edits) return fail(h, FCD_E_INVALID, c.crf ? "crf_edits: null output" : "ctc_edits: null output");
     const std::string occ_who = c.crf ? "crf_occupancy" : (c.wide ? "ctc_occupancy_wide" : "ctc_occupancy");
@@ -2013,6 +2021,8 @@ int lattice_check(fcd_handle *h, const LatticeCall &c) {
                                                      : "ctc_score: the exact lattice does not fit the 160 KiB of LDS: use a band");
     }
     if (c.align && in->n_reads > 0 && !c.out->count) return fail(h, FCD_E_INVALID, "null count");
+    if (c.spot && in->n_reads > 0 && !c.spot->end) return fail(h, FCD_E_INVALID, "ctc_spot: null end");
+    if (c.spot && c.spot->track && c.spot->track_stride < in->T) return fail(h, FCD_E_INVALID, "ctc_spot: track_stride must hold the T rows of a read");
     if (c.occupancy) {  // (a CTC batch has S = 1: its rows are N floats)
         if (c.occ->stride_row < 0 || c.occ->stride_t < in->S * in->N)
             return fail(h, FCD_E_INVALID, (occ_who + (c.crf ? ": stride_t must hold a dense (S, N) row, stride_row must not be negative"
@@ -2105,9 +2115,15 @@ int lattice_score(fcd_handle *h, const LatticeCall &c) {
 // row_bytes each.  Whole reads per launch, as many as `cap` bytes hold (at least one), every launch in the same memory, one
 // after the other on the stream; logp lent from the workspace when the caller wants none.  add_outputs(sc): the arrays the
 // call writes; launch(d, yd, r0, row0, logp, ws, stream): one group -- reads r0 .., labellings row0 .., its slice of logp.
+// tail_bytes > 0 (fcd_ctc_spot_*'s parameter blocks): that many more bytes of the workspace for EVERY group, behind
+// everything else.  fill(r0, row0, block) writes a group's block on the host -- into the handle's tail_host, which stays
+// as it is until the next such call -- all of them go to the device in ONE copy ahead of the launches, and *tail is the
+// device address of the block of the group being launched.
+using GroupBlock = std::function<void(int64_t, int64_t, void *)>;
 using GroupLaunch = std::function<hipError_t(const BatchDesc &, const ScoreDesc &, int64_t, int64_t, double *, unsigned char *, hipStream_t)>;
 int lattice_grouped(fcd_handle *h, const LatticeCall &c, size_t row_bytes, int64_t cap, double *out_logp,
-                    const std::function<void(CallScope &)> &add_outputs, const GroupLaunch &launch) {
+                    const std::function<void(CallScope &)> &add_outputs, const GroupLaunch &launch, size_t tail_bytes = 0,
+                    const GroupBlock &fill = nullptr, char **tail = nullptr) {
     const fcd_batch *in = c.in;
     const fcd_labellings *y = c.y;
     const size_t n_rows = (size_t)in->n_reads * (size_t)y->n_hyp;
@@ -2121,13 +2137,22 @@ int lattice_grouped(fcd_handle *h, const LatticeCall &c, size_t row_bytes, int64
     int rc = sc.begin(false, true);  // (exclusive: the workspace from its start, behind every overlapping call in flight)
     if (rc) return rc;
     char *ws = nullptr;
-    rc = sc.arena(o_logp + (out_logp ? 0 : n_rows * 8), &ws);
+    const size_t used = o_logp + (out_logp ? 0 : n_rows * 8);
+    const size_t o_tail = tail_bytes ? (used + 255) & ~(size_t)255 : used;  // (no tail: the request as it always was)
+    const size_t all_tails = tail_bytes * (size_t)((in->n_reads + group - 1) / group);
+    rc = sc.arena(o_tail + all_tails, &ws);
     if (rc) return rc;
+    if (tail_bytes) {
+        h->tail_host.resize(all_tails);
+        for (int64_t r0 = 0, gi = 0; r0 < in->n_reads; r0 += group, ++gi) fill(r0, r0 * y->n_hyp, h->tail_host.data() + gi * tail_bytes);
+        FCD_HIP(h, hipMemcpyAsync(ws + o_tail, h->tail_host.data(), all_tails, hipMemcpyHostToDevice, sc.stream));
+    }
     double *logp = out_logp ? out_logp : reinterpret_cast<double *>(ws + o_logp);
     const int64_t esz = in->dtype == FCD_DTYPE_F32 ? 4 : 2;
     sc.time();
     for (int64_t r0 = 0; r0 < in->n_reads; r0 += group) {
         const int64_t row0 = r0 * y->n_hyp;
+        if (tail) *tail = ws + o_tail + (size_t)(r0 / group) * tail_bytes;
         BatchDesc d = to_desc(in, c.crf);
         d.post = reinterpret_cast<const float *>(reinterpret_cast<const char *>(in->post) + r0 * in->stride_read * esz);
         d.lengths = in->lengths ? in->lengths + r0 : nullptr;
@@ -2148,19 +2173,34 @@ int lattice_align(fcd_handle *h, const LatticeCall &c) {
     const int64_t bnd = std::min<int64_t>(c.band, 1ll << 28);
     const size_t row_bytes = c.crf ? crf_align_row_bytes(in->T, y->stride, bnd) : ctc_align_row_bytes(in->T, y->stride, c.band);
     const int64_t cap = h->align_ws_cap > 0 ? h->align_ws_cap : std::min<int64_t>(4ll << 30, workspace_budget(h));
+    const fcd_spot *s = c.spot;
+    char *block = nullptr;  // (spotting) the SpotOut of the group being launched, in the workspace
     return lattice_grouped(
         h, c, row_bytes, cap, out->logp,
         [&](CallScope &sc) {
             sc.add(out->start, cells * 4);
             sc.add(out->count, cells * 4);
             sc.add(out->qual, cells * 4);
+            if (s) {
+                sc.add(s->end, (size_t)in->n_reads * (size_t)y->n_hyp * 4);
+                sc.add(s->track, track_span(in, y, s) * 4);
+                sc.add(s->row_begin, (size_t)in->n_reads * 4);
+                sc.add(s->row_end, (size_t)in->n_reads * 4);
+            }
         },
         [&](const BatchDesc &d, const ScoreDesc &yd, int64_t r0, int64_t row0, double *logp, unsigned char *bp, hipStream_t stream) {
             const AlignOut od{out->start + row0 * y->stride, out->count + row0 * y->stride,
                               out->qual ? out->qual + row0 * y->stride : nullptr, logp};
+            if (s) return launch_ctc_align(d, yd, c.collapse, bnd, od, bp, stream, reinterpret_cast<const SpotOut *>(block));
             return c.crf ? launch_crf_align(d, yd, c.init + r0 * c.init_stride, c.n_init, c.init_stride, bnd, od, bp, stream)
                          : launch_ctc_align(d, yd, c.collapse, bnd, od, bp, stream);
-        });
+        },
+        s ? 256 : 0,
+        [&](int64_t r0, int64_t row0, void *host) {
+            *static_cast<SpotOut *>(host) = SpotOut{s->end + row0, s->track ? s->track + row0 * s->track_stride : nullptr, s->track_stride,
+                                                    s->row_begin ? s->row_begin + r0 : nullptr, s->row_end ? s->row_end + r0 : nullptr};
+        },
+        &block);
 }
 
 int lattice_posterior(fcd_handle *h, const LatticeCall &c) {
@@ -2265,6 +2305,11 @@ int lattice_host(fcd_handle *h, const LatticeCall &c) {
     const int i_start = c.align ? st.out(c.out->start, cells * 4, true) : -1;
     const int i_count = c.align ? st.out(c.out->count, cells * 4, true) : -1;
     const int i_qual = c.align ? st.out(c.out->qual, cells * 4, true) : -1;
+    // (the track is written inside every read's range only: it travels both ways)
+    const int i_end = c.spot ? st.out(c.spot->end, n_rows * 4) : -1;
+    const int i_track = c.spot ? st.inout(c.spot->track, track_span(in, y, c.spot) * 4) : -1;
+    const int i_rb = c.spot ? st.in(c.spot->row_begin, B * 4) : -1;
+    const int i_re = c.spot ? st.in(c.spot->row_end, B * 4) : -1;
     // (posterior entries the kernel does not write -- k >= len -- come back as 0)
     const int i_sub = c.posterior ? st.out(c.post->post, cells * ((size_t)in->N - 1) * 4, true) : -1;
     // (edit entries the kernel does not write -- k >= len, g > len -- come back as 0)
@@ -2290,6 +2335,15 @@ int lattice_host(fcd_handle *h, const LatticeCall &c) {
     d.init = st.at<float>(i_init);
     d.logp = st.at<double>(i_logp);
     d.out = &dout;
+    fcd_spot dspot{};
+    if (c.spot) {
+        dspot = *c.spot;
+        dspot.end = st.at<uint32_t>(i_end);
+        dspot.track = st.at<float>(i_track);
+        dspot.row_begin = st.at<uint32_t>(i_rb);
+        dspot.row_end = st.at<uint32_t>(i_re);
+        d.spot = &dspot;
+    }
     const fcd_posterior dpost{st.at<float>(i_sub), st.at<double>(i_logp)};
     d.post = &dpost;
     const fcd_edits dedits{st.at<float>(i_del), st.at<float>(i_ins), st.at<double>(i_logp)};
@@ -2321,10 +2375,27 @@ int fcd_ctc_score_host(fcd_handle *h, const fcd_batch *in, const fcd_labellings 
     return lattice_host(h, LatticeCall{false, false, in, y, band, collapse_repeats != 0, nullptr, 0, 0, logp, nullptr});
 }
 
+namespace {
+// fcd_ctc_spot_*: an alignment call with the spotting outputs behind it
+int spot_call(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int collapse_repeats, int64_t band, const fcd_spot *out,
+              int (*run)(fcd_handle *, const LatticeCall &)) {
+    if (!out) return fail(h, FCD_E_INVALID, "ctc_spot: null output");
+    const fcd_alignment al{out->start, out->count, out->qual, out->logp};
+    LatticeCall c{false, true, in, y, band, collapse_repeats != 0, nullptr, 0, 0, nullptr, &al};
+    c.spot = out;
+    return run(h, c);
+}
+}  // namespace
+
 int fcd_ctc_align_dev(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int collapse_repeats, int64_t band,
                       const fcd_alignment *out) {
     if (!h) return FCD_E_INVALID;
     std::lock_guard<std::recursive_mutex> g(h->mu);
+    if (h->spot_on && out) {  // fcd_set_ctc_spot: the spotting call, the four shared arrays from this call's own `out`
+        fcd_spot s = h->spot;
+        s.start = out->start, s.count = out->count, s.qual = out->qual, s.logp = out->logp;
+        return spot_call(h, in, y, collapse_repeats, band, &s, lattice_dev);
+    }
     return lattice_dev(h, LatticeCall{false, true, in, y, band, collapse_repeats != 0, nullptr, 0, 0, nullptr, out});
 }
 
@@ -2333,6 +2404,21 @@ int fcd_ctc_align_host(fcd_handle *h, const fcd_batch *in, const fcd_labellings 
     if (!h) return FCD_E_INVALID;
     std::lock_guard<std::recursive_mutex> whole_call(h->mu);  // staging .. copy-back, see run_host
     return lattice_host(h, LatticeCall{false, true, in, y, band, collapse_repeats != 0, nullptr, 0, 0, nullptr, out});
+}
+
+int fcd_set_ctc_spot(fcd_handle *h, const fcd_spot *spot) {
+    if (!h) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> g(h->mu);
+    h->spot_on = spot != nullptr;
+    h->spot = spot ? *spot : fcd_spot{};
+    return FCD_OK;
+}
+
+int fcd_ctc_spot_host(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int collapse_repeats, int64_t band,
+                      const fcd_spot *out) {
+    if (!h) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> whole_call(h->mu);  // staging .. copy-back, see run_host
+    return spot_call(h, in, y, collapse_repeats, band, out, lattice_host);
 }
 
 int fcd_ctc_posterior_dev(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int collapse_repeats, int64_t band,

@@ -36,7 +36,12 @@ struct AlignParams {
     float *qual;          // nullable
     unsigned char *bp;    // back-pointers, bp_row_bytes per labelling of this launch
     int64_t bp_row_bytes;
+    const SpotOut *spot;  // motif spotting (s.spot; fcd_ctc_spot_*): its outputs and ranges, a block in device memory read
+                          // only by the spotting walks; null in an alignment, whose parameters grow by this pointer alone
 };
+
+constexpr uint32_t kNoHit = 0xFFFFFFFFu;
+constexpr float kLn2f = 0.693147180559945309f;
 
 template <int K> struct BpWord { typedef uint16_t type; };
 template <> struct BpWord<2> { typedef uint8_t type; };
@@ -67,6 +72,97 @@ __device__ __forceinline__ void no_alignment(const AlignParams &q) {
     const int64_t row = blockIdx.x;
     const int64_t n = min((int64_t)q.s.y.len[row], q.s.y.stride);
     for (int64_t k = threadIdx.x; k < n; k += blockDim.x) q.count[row * q.s.y.stride + k] = 0u;
+    if (q.spot && threadIdx.x == 0) q.spot->end[row] = kNoHit;
+}
+
+// ---- motif spotting: the alignment free at both ends (fcd_ctc_spot_*, include/fcd.h) ----
+// State 0 is no cell: it holds 1 at every row, 2^-eacc in the walk's units, so state 1 sees a fresh start as its s-1
+// candidate at every row; a hit ends in state 2L - 1 at any row, and the best of those end cells is the result.
+// Why the pinned state bounds the row maximum: a cell is a product of posteriors that starts from the 1 of state 0, and
+// x * p rounded to f32 is at most x for p <= 1 (x is itself an f32: rounding is monotone), so with posteriors <= 1 no cell
+// exceeds 1.  State 0 takes part in the row maximum (exponent 1 - eacc), the shift is then the same at every row, eacc
+// stays at 1 - kTarget and state 0 at 2^(kTarget - 1); a cell below 2^-245 -- a TRUE probability, not one relative to its
+// row -- is below f32's range and counts as 0.  Posteriors above 1: a cell may exceed 1, the row maximum is that cell,
+// eacc rises and state 0 falls below 2^(kTarget - 1) by as much; nothing is lost until the cells pass 2^245, where fresh
+// starts underflow to 0 as any cell that far below its row's maximum does.
+
+// the rows [b, e) of the read the motif is looked for in take the read's place: Row::post advanced to row b (*tb), Tr
+// shrunk to e - b.  Returns false when the row's result is written already (every work-item agrees).
+__device__ __forceinline__ bool spot_range(const AlignParams &q, Row *rw, int *tb) {
+    const ScoreParams &p = q.s;
+    const int64_t row = blockIdx.x, read = row / p.y.n_hyp;
+    const int64_t Tr = rw->Tr;
+    const uint32_t *row_begin = q.spot->row_begin, *row_end = q.spot->row_end;
+    const int b = row_begin ? (int)min((int64_t)row_begin[read], Tr) : 0;
+    const int e = row_end ? (int)min((int64_t)row_end[read], Tr) : rw->Tr;
+    const int rows = max(e - b, 0);
+    if (rw->L == 0 || rw->L > rows) {  // no motif: 0.0; more labels than rows: no hit
+        if (threadIdx.x == 0) p.logp[row] = rw->L == 0 ? 0.0 : -(double)INFINITY;
+        return false;
+    }
+    rw->post = post_at(rw->post, (int64_t)b * p.in.stride_t, p.in.dtype);
+    rw->Tr = rows;
+    *tb = b;
+    return true;
+}
+
+// what a spotting walk carries: wave-uniform but for the staged pair
+struct Spot {
+    float bm;  // the best end cell so far, normalised: mantissa in [0.5, 1) ...
+    int be;    // ... its exponent in true scale ...
+    int bt;    // ... and its row (of the range); -1: none yet
+    float tm;  // lane j: the pair of row c0 + j of the 64 rows of `track` being staged
+    int te;
+};
+
+// state 0 in the walk's units (eacc is at least 1 - kTarget in a spotting walk, and an int)
+__device__ __forceinline__ float spot_one(int64_t eacc) {
+    const int e = (int)eacc;
+    return ldexpf(1.0f, e > 512 ? -512 : -e);
+}
+
+// row t of the range is done: v, its cell of state 2L - 1 in the walk's units (wave-uniform).  The running best takes a
+// later row only if it is strictly greater, compared as (exponent, mantissa): no logarithm.  track: work-item t mod 64
+// keeps the row's pair; at the end of every 64 rows (and of the range) each takes ONE logf and one multiply-add for its
+// own row and the first wavefront stores the 64 rows at once.
+__device__ __forceinline__ void spot_row(const AlignParams &q, Spot &sp, float v, int64_t eacc, int t, int Tr, int tb) {
+    float m = 0.0f;
+    int e = 0;
+    const bool live = v > 0.0f && v - v == 0.0f;
+    if (live) {
+        m = frexpf(v, &e);
+        e += (int)eacc;
+        if (sp.bt < 0 || e > sp.be || (e == sp.be && m > sp.bm)) {
+            sp.bm = m;
+            sp.be = e;
+            sp.bt = t;
+        }
+    }
+    float *track = q.spot->track;
+    if (track) {
+        const int j = threadIdx.x;
+        if (j == (t & 63)) {
+            sp.tm = m;
+            sp.te = e;
+        }
+        if ((t & 63) == 63 || t == Tr - 1) {
+            const int c0 = t & ~63;
+            if (j < 64 && c0 + j <= t)
+                track[(int64_t)blockIdx.x * q.spot->track_stride + tb + c0 + j] =
+                    sp.tm > 0.0f ? fmaf((float)sp.te, kLn2f, logf(sp.tm)) : -INFINITY;
+        }
+    }
+}
+
+// logp and end of the row; returns the state the hit ends in, -1 when there is none (count zeroed by the caller)
+__device__ __forceinline__ int spot_finish(const AlignParams &q, const Lds &lds, const Row &rw, const Spot &sp, int tb) {
+    const bool bad = lds.misc[kBadPost] != 0;
+    const bool hit = !bad && sp.bt >= 0;
+    if (threadIdx.x == 0) {
+        q.s.logp[blockIdx.x] = bad ? (double)NAN : (sp.bt < 0 ? -(double)INFINITY : ln_p((double)sp.bm, sp.be));
+        if (hit) q.spot->end[blockIdx.x] = (uint32_t)(tb + sp.bt);
+    }
+    return hit ? 2 * rw.L - 1 : -1;
 }
 
 // the walk, last row first: the alignment is in state s at the row at hand, cnt rows of its label seen so far
@@ -101,13 +197,14 @@ __device__ __forceinline__ int finish(const AlignParams &q, const Lds &lds, cons
 }
 
 // one label per work-item: the mean posterior of its rows, summed in f32 in row order (search.rs:337-376)
-__device__ __forceinline__ void qualities(const AlignParams &q, const Row &rw) {
+// (tb: the row of the read Row::post stands at -- 0 but in a spotting walk)
+__device__ __forceinline__ void qualities(const AlignParams &q, const Row &rw, int tb) {
     if (!q.qual) return;
     const ScoreParams &p = q.s;
     const int64_t base = (int64_t)blockIdx.x * p.y.stride;
     __syncthreads();  // start / count as the walk left them
     for (int k = threadIdx.x; k < rw.L; k += blockDim.x) {
-        const int64_t t = q.start[base + k];
+        const int64_t t = (int64_t)q.start[base + k] - tb;
         const int c = (int)q.count[base + k];
         const int64_t col = (int64_t)rw.labels[k] * p.in.stride_n;
         float sum = load_post(rw.post, t * p.in.stride_t + col, p.in.dtype);
@@ -117,15 +214,17 @@ __device__ __forceinline__ void qualities(const AlignParams &q, const Row &rw) {
 }
 
 // ---- the register-resident window ----
-template <int K>
-__global__ __launch_bounds__(64) void align_reg_kernel(AlignParams q) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+// SPOT: the kernels' run-time mode q.s.spot as a compile-time copy -- a kernel branches on it ONCE, so that an
+// alignment's rows run the instructions they ran before spotting existed
+template <int K, bool SPOT>
+__device__ __forceinline__ void align_reg_walk(const AlignParams &q, unsigned char *smem) {
     typedef typename BpWord<K>::type BpT;
     constexpr int C = 64 * K;
     const ScoreParams &p = q.s;
     const Lds lds = carve(smem, p.lab_cap);
     Row rw;
-    if (!prologue(p, lds, &rw)) {
+    int tb = 0;  // (spotting: the first row of the range)
+    if (!prologue(p, lds, &rw) || (SPOT && !spot_range(q, &rw, &tb))) {
         no_alignment(q);
         return;
     }
@@ -138,13 +237,15 @@ __global__ __launch_bounds__(64) void align_reg_kernel(AlignParams q) {
     if (lane == 0) a[0] = 1.0f;  // "row -1": state 0
     int64_t eacc = 0;
     int lo_prev = 0, lo = 0, hi = 0;
+    Spot sp{0.0f, 0, -1, 0.0f, 0};
+    const int spot_lane = (2 * rw.L - 1) / K, spot_r = (2 * rw.L - 1) % K;  // where state 2L - 1 lives (spotting: lo stays 1)
     for (int t0 = 0; t0 < rw.Tr; t0 += rw.rows_per_tile) {
         const int rc = min(rw.rows_per_tile, rw.Tr - t0);
         fill_tile_checked(p, lds, rw, t0, rc);
-        StepIn<K> in = load_step<K>(p, lds, rw, t0, 0);
+        StepIn<K> in = load_step<K, SPOT>(p, lds, rw, t0, 0);
         for (int i = 0; i < rc; ++i) {
             StepIn<K> nx = in;
-            if (i + 1 < rc) nx = load_step<K>(p, lds, rw, t0 + i + 1, i + 1);
+            if (i + 1 < rc) nx = load_step<K, SPOT>(p, lds, rw, t0 + i + 1, i + 1);
             lo = in.lo;
             hi = in.hi;
             if (hi - lo_prev >= C) {  // the window jumped: slots it re-enters start from 0
@@ -192,26 +293,41 @@ __global__ __launch_bounds__(64) void align_reg_kernel(AlignParams q) {
                 emax = max(emax, ((in.in_mask >> r) & 1) && e != kNoExp ? e + ex[r] : kNoExp);
             }
             bp[(int64_t)(t0 + i) * 64 + lane] = (BpT)bits;
+            if (SPOT) emax = max(emax, 1 - (int)eacc);  // state 0: 2^-eacc in the units the row was computed in
             emax = wave_imax(emax);
             const int sh = emax == kNoExp ? 0 : kTarget - emax;
             eacc -= sh;
 #pragma unroll
             for (int r = 0; r < K; ++r)
                 a[r] = ((in.in_mask >> r) & 1) ? ldexpf(u[r], min(max(ex[r] + sh, -512), 512)) : 0.0f;
+            if (SPOT) {
+                if (lane == 0) a[0] = spot_one(eacc);  // the slot of state 0 (outside the window: no cell), after the rescale
+                float mine = 0.0f;
+#pragma unroll
+                for (int r = 1; r < K; r += 2)
+                    if (r == spot_r) mine = a[r];
+                const float v = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine), spot_lane));
+                spot_row(q, sp, v, eacc, t0 + i, rw.Tr, tb);
+            }
             lo_prev = lo;
             in = nx;
         }
     }
-    if (lane == 0) lds.misc[18] = lds.misc[19] = 0;
-    __syncthreads();
+    int end;
+    if (SPOT) {
+        end = spot_finish(q, lds, rw, sp, tb);
+    } else {
+        if (lane == 0) lds.misc[18] = lds.misc[19] = 0;
+        __syncthreads();
 #pragma unroll
-    for (int r = 0; r < K; ++r) {
-        const int s = slot_state<K>(lane, r, lo);
-        if (s <= hi && s == 2 * rw.L) lds.misc[18] = __float_as_int(a[r]);
-        if (s <= hi && s == 2 * rw.L - 1) lds.misc[19] = __float_as_int(a[r]);
+        for (int r = 0; r < K; ++r) {
+            const int s = slot_state<K>(lane, r, lo);
+            if (s <= hi && s == 2 * rw.L) lds.misc[18] = __float_as_int(a[r]);
+            if (s <= hi && s == 2 * rw.L - 1) lds.misc[19] = __float_as_int(a[r]);
+        }
+        __syncthreads();
+        end = finish(q, lds, rw, __int_as_float(lds.misc[18]), __int_as_float(lds.misc[19]), eacc);
     }
-    __syncthreads();
-    const int end = finish(q, lds, rw, __int_as_float(lds.misc[18]), __int_as_float(lds.misc[19]), eacc);
     if (end < 0) {
         no_alignment(q);
         return;
@@ -220,8 +336,10 @@ __global__ __launch_bounds__(64) void align_reg_kernel(AlignParams q) {
     uint32_t *start = q.start + (int64_t)blockIdx.x * p.y.stride, *count = q.count + (int64_t)blockIdx.x * p.y.stride;
     BpT *sbp = reinterpret_cast<BpT *>(smem);
     Walk w{end, 0};
-    for (int c0 = (rw.Tr - 1) / kTraceRows * kTraceRows; c0 >= 0; c0 -= kTraceRows) {
-        const int n = min(kTraceRows, rw.Tr - c0);
+    // (spotting: from the hit's last row, in the chunk that holds it, down to the chunk in which the walk enters state 0)
+    const int t_last = SPOT ? sp.bt : rw.Tr - 1;
+    for (int c0 = t_last / kTraceRows * kTraceRows; c0 >= 0 && !(SPOT && w.s == 0); c0 -= kTraceRows) {
+        const int n = min(kTraceRows, t_last + 1 - c0);
         __syncthreads();
         for (int i = 0; i < n; ++i) sbp[i * 64 + lane] = bp[(int64_t)(c0 + i) * 64 + lane];
         __syncthreads();
@@ -229,19 +347,32 @@ __global__ __launch_bounds__(64) void align_reg_kernel(AlignParams q) {
             const int slot = w.s % C;
             const int word = sbp[i * 64 + slot / K];
             const int d = __builtin_amdgcn_readfirstlane((word >> (2 * (slot % K))) & 3);
-            walk_row(w, c0 + i, d, start, count, lane == 0);
+            walk_row(w, tb + c0 + i, d, start, count, lane == 0);
         }
     }
-    qualities(q, rw);
+    qualities(q, rw, tb);
+}
+
+// (Both copies live in one kernel, so every launch, alignments included, reserves the larger copy's registers: up to 96
+// VGPRs at K = 8.  That costs an alignment nothing TODAY because 8.6 KiB of LDS a workgroup hold the kernel at 4
+// wavefronts a SIMD, which 96 VGPRs allow; a change that lowers the LDS use makes the spotting copy's registers the bound.)
+template <int K>
+__global__ __launch_bounds__(64) void align_reg_kernel(AlignParams q) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    if (q.s.spot) align_reg_walk<K, true>(q, smem);
+    else align_reg_walk<K, false>(q, smem);
 }
 
 // ---- the LDS-resident window ----
+// (spotting is a run-time mode here: next to twenty cells and two barriers a row its scalar branches do not show, and two
+// copies of this body do not fit the 128 registers of 1024 work-items)
 __global__ __launch_bounds__(1024) void align_lds_kernel(AlignParams q) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const ScoreParams &p = q.s;
     const Lds lds = carve(smem, p.lab_cap);
     Row rw;
-    if (!prologue(p, lds, &rw)) {
+    int tb = 0;  // (spotting: the first row of the range)
+    if (!prologue(p, lds, &rw) || (p.spot && !spot_range(q, &rw, &tb))) {
         no_alignment(q);
         return;
     }
@@ -253,6 +384,7 @@ __global__ __launch_bounds__(1024) void align_lds_kernel(AlignParams q) {
     if (tid == 0) lds.alpha[0] = 1.0f;  // "row -1": state 0
     int64_t eacc = 0;
     int lo_prev = 0, hi_prev = 0, base = 0, which = 0;
+    Spot sp{0.0f, 0, -1, 0.0f, 0};
     auto rd = [&](const float *buf, int n) -> float {
         if (n < lo_prev || n > hi_prev) return 0.0f;
         int idx = n - base;
@@ -265,6 +397,10 @@ __global__ __launch_bounds__(1024) void align_lds_kernel(AlignParams q) {
         for (int i = 0; i < rc; ++i) {
             int lo, hi;
             window(p, lds, rw, t0 + i, i, &lo, &hi);
+            if (p.spot) {  // window_k<true>
+                lo = 1;
+                hi = min(hi, 2 * rw.L - 1);
+            }
             const float *prev = lds.alpha + which * cap;
             float *next = lds.alpha + (which ^ 1) * cap;
             const float pm0 = lds.pm[i * rw.N];
@@ -314,6 +450,7 @@ __global__ __launch_bounds__(1024) void align_lds_kernel(AlignParams q) {
                     emax = max(emax, e != kNoExp ? e + ex[c] : kNoExp);
                 }
             }
+            if (p.spot) emax = max(emax, 1 - (int)eacc);  // state 0: 2^-eacc in the units the row was computed in
             emax = wave_imax(emax);
             if ((tid & 63) == 0) lds.misc[tid >> 6] = emax;
             __syncthreads();  // every read of `prev` is done, the waves' maxima are in place
@@ -332,14 +469,22 @@ __global__ __launch_bounds__(1024) void align_lds_kernel(AlignParams q) {
                     bp_row[idx] = (unsigned char)((args >> (2 * c)) & 3u);
                 }
             }
+            if (p.spot && tid == 0) next[0] = spot_one(eacc);  // state 0 (below the window, base stays 0: no cell), after the rescale
             lo_prev = lo;
             hi_prev = hi;
             which ^= 1;
             __syncthreads();
+            if (p.spot) {  // (the next step writes the other buffer: `next` stands until the barrier inside it)
+                lo_prev = 0;  // state 0 is read like a cell
+                const float mine = 2 * rw.L - 1 <= hi ? next[2 * rw.L - 1] : 0.0f;
+                const float v = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(mine)));
+                spot_row(q, sp, v, eacc, t0 + i, rw.Tr, tb);
+            }
         }
     }
     const float *last = lds.alpha + which * cap;
-    const int end = finish(q, lds, rw, rd(last, 2 * rw.L), rd(last, 2 * rw.L - 1), eacc);
+    const int end = p.spot ? spot_finish(q, lds, rw, sp, tb)
+                           : finish(q, lds, rw, rd(last, 2 * rw.L), rd(last, 2 * rw.L - 1), eacc);
     if (end < 0) {
         no_alignment(q);
         return;
@@ -348,8 +493,9 @@ __global__ __launch_bounds__(1024) void align_lds_kernel(AlignParams q) {
     uint32_t *start = q.start + (int64_t)blockIdx.x * p.y.stride, *count = q.count + (int64_t)blockIdx.x * p.y.stride;
     unsigned char *sbp = smem;
     Walk w{end, 0};
-    for (int c0 = (rw.Tr - 1) / kTraceRows * kTraceRows; c0 >= 0; c0 -= kTraceRows) {
-        const int n = min(kTraceRows, rw.Tr - c0);
+    const int t_last = p.spot ? sp.bt : rw.Tr - 1;  // (spotting: as in the register kernel)
+    for (int c0 = t_last / kTraceRows * kTraceRows; c0 >= 0 && !(p.spot && w.s == 0); c0 -= kTraceRows) {
+        const int n = min(kTraceRows, t_last + 1 - c0);
         const int s0 = w.s - (kTraceSpan - 1);  // the state in column 0
         __syncthreads();
         for (int e = tid; e < n * kTraceSpan; e += bd) {
@@ -359,10 +505,10 @@ __global__ __launch_bounds__(1024) void align_lds_kernel(AlignParams q) {
         __syncthreads();
         for (int i = n - 1; i >= 0; --i) {
             const int d = __builtin_amdgcn_readfirstlane((int)sbp[i * kTraceSpan + (w.s - s0)] & 3);
-            walk_row(w, c0 + i, d, start, count, tid == 0);
+            walk_row(w, tb + c0 + i, d, start, count, tid == 0);
         }
     }
-    qualities(q, rw);
+    qualities(q, rw, tb);
 }
 
 // the shape of a call's kernel: states per lane of the register kernel (0: the LDS kernel) and the LDS kernel's states
@@ -391,7 +537,7 @@ size_t ctc_align_row_bytes(int64_t T, int64_t stride, int64_t band) {
 }
 
 hipError_t launch_ctc_align(const BatchDesc &in, const ScoreDesc &y, int collapse, int64_t band, const AlignOut &out,
-                            unsigned char *bp, hipStream_t stream) {
+                            unsigned char *bp, hipStream_t stream, const SpotOut *spot) {
     const int64_t rows = in.n_reads * y.n_hyp;
     if (rows <= 0) return hipSuccess;
     AlignParams q;
@@ -405,6 +551,8 @@ hipError_t launch_ctc_align(const BatchDesc &in, const ScoreDesc &y, int collaps
     q.count = out.count;
     q.qual = out.qual;
     q.bp = bp;
+    q.spot = spot;  // (spotting: band is 0, the caller's check)
+    q.s.spot = spot != nullptr;
     q.bp_row_bytes = (int64_t)ctc_align_row_bytes(in.T, y.stride, band);
     int k;
     int64_t cap;

@@ -33,6 +33,7 @@ struct ScoreParams {
     int cap;      // LDS kernel: states per alpha buffer
     int lab_cap;  // labels the LDS copy of a labelling holds
     int slack = 0;  // states by which window_k's two reachability cuts are relaxed (ctc_posterior.hip's edit walk: 2)
+    int spot = 0;   // ctc_align.hip's motif spotting (fcd_ctc_spot_*): its kernels walk with window_k<true>
 };
 
 struct Lds {
@@ -161,7 +162,9 @@ __device__ __forceinline__ void fill_tile(const ScoreParams &p, const Lds &lds, 
 
 // live states of row t: the band around the path (k = k(t), read only when banded), cut to what can be reached and can
 // still reach the end -- in the labelling itself; p.slack more states on either side for a walk that also follows
-// labellings one label shorter (their alignments reach a state a row earlier and may leave it a row later)
+// labellings one label shorter (their alignments reach a state a row earlier and may leave it a row later).
+// SPOT (ScoreParams::spot, a compile-time copy: the other walks keep their instructions): free-ended, see below
+template <bool SPOT = false>
 __device__ __forceinline__ void window_k(const ScoreParams &p, const Row &rw, int t, int k, int *lo, int *hi) {
     int l = 0, h = 2 * rw.L;
     if (p.band > 0) {
@@ -170,11 +173,16 @@ __device__ __forceinline__ void window_k(const ScoreParams &p, const Row &rw, in
     }
     *hi = min(h, 2 * t + 1 + p.slack);
     *lo = max(l, 2 * rw.L - 2 * (rw.Tr - 1 - t) - 2 - p.slack);
+    if (SPOT) {  // free-ended: no cut from the end of the read; state 0 is no cell (pinned to 1) and state 2L plays no part
+        *lo = 1;
+        *hi = min(*hi, 2 * rw.L - 1);
+    }
 }
 
 // ... of row t, the tile's row i
+template <bool SPOT = false>
 __device__ __forceinline__ void window(const ScoreParams &p, const Lds &lds, const Row &rw, int t, int i, int *lo, int *hi) {
-    window_k(p, rw, t, p.band > 0 ? lds.krow[i] : 0, lo, hi);
+    window_k<SPOT>(p, rw, t, p.band > 0 ? lds.krow[i] : 0, lo, hi);
 }
 
 // (finite_exp and wave_imax: device_utils.h, shared with the CRF Viterbi search of crf_viterbi.hip)
@@ -205,11 +213,11 @@ struct StepIn {
     int lo, hi;
 };
 
-template <int K>
+template <int K, bool SPOT = false>
 __device__ __forceinline__ StepIn<K> load_step(const ScoreParams &p, const Lds &lds, const Row &rw, int t, int i) {
     StepIn<K> in;
     const int lane = threadIdx.x;
-    window(p, lds, rw, t, i, &in.lo, &in.hi);
+    window<SPOT>(p, lds, rw, t, i, &in.lo, &in.hi);
     in.pm0 = lds.pm[i * rw.N];
     in.pe0 = lds.pe[i * rw.N];
     in.in_mask = 0;

@@ -285,9 +285,18 @@ struct AlignOut {
     float *qual;  // nullable
     double *logp;
 };
+// spot non-null (band 0): motif spotting, the same kernels free-ended (fcd_spot in include/fcd.h) -- the hit's last row,
+// the per-row track and the range of rows of every read of the launch, a block in DEVICE memory (stream-ordered before
+// the launch), so that an alignment's kernel arguments grow by one pointer.
+struct SpotOut {
+    uint32_t *end;
+    float *track;  // nullable
+    int64_t track_stride;
+    const uint32_t *row_begin, *row_end;  // nullable
+};
 size_t ctc_align_row_bytes(int64_t T, int64_t stride, int64_t band);
 hipError_t launch_ctc_align(const BatchDesc &in, const ScoreDesc &y, int collapse, int64_t band, const AlignOut &out,
-                            unsigned char *bp, hipStream_t stream);
+                            unsigned char *bp, hipStream_t stream, const SpotOut *spot = nullptr);
 // CTC forward-backward substitution posteriors of given labellings (ctc_posterior.hip; fcd_posterior in include/fcd.h).
 // ctc_posterior_unsupported: 0 = the kernels hold the call; 1 = the widest window exceeds the 510 register-resident states,
 // 2 = more than 8 labels, 3 = min(T, stride) beyond the 28480 labels whose LDS copy fits 64 KiB next to the tile.  alpha: ctc_posterior_row_bytes() of device memory per labelling of the launch (the stored
@@ -476,7 +485,7 @@ struct fcd_handle {
     uint64_t ov_seq = 0;
     int ov_last_slot = -1;  // the internal stream the latest overlapping call went to
     struct Range { uintptr_t lo, hi; };
-    static constexpr int kMaxRanges = 10;  // arrays one call reads or writes (fcd_unpack_gathered_dev: 10)
+    static constexpr int kMaxRanges = 12;  // arrays one call reads or writes (fcd_ctc_align_dev under fcd_set_ctc_spot: 11)
     // the calls each internal stream has not finished yet, oldest first: what they write, and an event behind each (so that
     // a stream that never idles does not accumulate ranges: finished calls are dropped from the front)
     struct Flight {
@@ -498,6 +507,9 @@ struct fcd_handle {
     int live_sessions = 0;    // fcd_beam_session_create .. _destroy
     bool occ_wide = false;    // fcd_set_ctc_occupancy_wide: fcd_ctc_occupancy_* takes windows beyond 510 states
     bool crf_wide = false;    // fcd_set_crf_lattice_wide: fcd_crf_score_* and fcd_crf_occupancy_* take windows beyond 512 states
+    std::vector<char> tail_host;  // lattice_grouped: the host copy of a call's per-group parameter blocks, kept until the next
+    bool spot_on = false;     // fcd_set_ctc_spot: fcd_ctc_align_dev spots, with ...
+    fcd_spot spot{};          // ... these outputs and ranges next to its own fcd_alignment
     int64_t align_ws_cap = 0; // fcd_debug_set_align_workspace_cap: back-pointer bytes one launch of fcd_ctc_align_* may take, 0 = default
     bool is_lane = false;
     uint32_t *duplex_prof = nullptr;  // fcd_debug_set_duplex_profile

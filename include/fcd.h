@@ -426,6 +426,61 @@ int fcd_ctc_align_dev(fcd_handle *h, const fcd_batch *in, const fcd_labellings *
 int fcd_ctc_align_host(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int collapse_repeats, int64_t band,
                        const fcd_alignment *out);
 
+/* ---- CTC motif spotting: where a known sequence sits in a read (csrc/ctc_align.hip, the align kernels free-ended) ----
+ * NOT a reference function.  fcd_ctc_align_* pins the first label near row 0 and the last near row T_r - 1; this call
+ * frees both ends: of every alignment of the motif y (labelling i of read r, row = r * n_hyp + i; `path` unused) to ANY
+ * run of consecutive rows inside the read's range [b_r, e_r), the best one.  Adapter and primer trimming, barcode
+ * demultiplexing (the motifs of a read are its n_hyp rows), the adapter in the middle of a chimeric read.
+ * It is fcd_ctc_align_*'s exact lattice (band = 0) -- extended sequence z of 2L + 1 states, transitions under
+ * collapse_repeats, a cell = max(candidates) * p with ONE f32 rounding, power-of-two rescaling only, candidates in the
+ * order stay, s-1, s-2, a later one only if strictly greater -- over the rows t in [b_r, e_r), with two changes:
+ *   free start  state 0 is no cell: it holds the value 1 at every row, "row b_r - 1" included.  State 1 so sees a fresh
+ *               start as its s-1 candidate at every row, taken only if strictly greater than staying.
+ *   free end    a hit ends at row t in state 2L - 1, the last label's own row; with v_t that cell,
+ *               hit = argmax_t v_t, ties to the earliest row.  State 2L plays no part.
+ * Of the window only the cut from the start stays (s <= 2 (t - b_r) + 1).  Because state 0 holds a true 1 in f32 next to
+ * the cells, a cell below 2^-245 -- a true probability, not one relative to its row -- counts as 0.
+ * Per labelling row:
+ *   start, count, qual  the best hit's rows for each label, ABSOLUTE row numbers of the read, as fcd_alignment defines
+ *                       them: the hit spans rows start[0] .. start[L-1] + count[L-1] - 1.
+ *   logp [row]          ln v_hit, ln(m) + E ln 2 in float64.  Nullable.
+ *   end  [row]          the hit's last row; 0xFFFFFFFF when there is no hit.  Not null.
+ *   track[row * track_stride + t]   ln v_t in f32 for every t in [b_r, e_r), -inf where v_t = 0: what a caller
+ *                       thresholds to find every occurrence.  Rows outside the range are not written.  Nullable;
+ *                       track_stride >= in->T.  ln v_t is logf(m) + E * ln 2 in f32 (one multiply-add).
+ * row_begin / row_end: [n_reads], nullable (null: 0 and T_r), clamped to [0, T_r]; e_r <= b_r is an empty range.
+ * Rows without a hit, tested in fcd_ctc_align_*'s order and with its logp: i >= n_valid[r], len > stride, a label
+ * outside 1 .. N-1: NaN; L > e_r - b_r (an empty range included): -inf; a NaN, infinite or negative posterior in the rows
+ * of the RANGE (only those are looked at): NaN; v_t = 0 everywhere: -inf.  In all of them end = 0xFFFFFFFF, count = 0
+ * for every k < min(len, stride), start / qual are left alone; track is written only by the last two (the rows that
+ * walk), and for a row with a bad posterior its values are undefined.  L = 0: logp = 0, end = 0xFFFFFFFF, nothing else is written.
+ * Shapes, limits (the kernel is chosen from stride as fcd_ctc_align_* does at band 0: motifs beyond 254 labels walk in
+ * LDS), in->S, in->lengths and the workspace are fcd_ctc_align_*'s.  FCD_E_INVALID before anything is
+ * enqueued: band != 0, end null, track given with track_stride < in->T, and fcd_ctc_align_*'s cases.
+ * Out of scope: the sum over alignments (a soft hit score), the k best hits on the device, CRF models, bands. */
+typedef struct fcd_spot {
+    uint32_t *start;            /* [n_reads * n_hyp * stride] */
+    uint32_t *count;            /* [n_reads * n_hyp * stride] */
+    float    *qual;             /* [n_reads * n_hyp * stride], nullable */
+    double   *logp;             /* [n_reads * n_hyp], nullable */
+    uint32_t *end;              /* [n_reads * n_hyp] */
+    float    *track;            /* [n_reads * n_hyp * track_stride], nullable */
+    int64_t   track_stride;
+    const uint32_t *row_begin;  /* [n_reads], nullable */
+    const uint32_t *row_end;    /* [n_reads], nullable */
+} fcd_spot;
+int fcd_ctc_spot_host(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int collapse_repeats, int64_t band,
+                      const fcd_spot *out);
+/* Device arrays: a handle switch in front of the alignment's own device entry point, as fcd_set_ctc_occupancy_wide is in
+ * front of the occupancies' (one device body, one set of far-offset cases).  fcd_set_ctc_spot(h, spot) copies *spot into
+ * the handle; while it is set, fcd_ctc_align_dev on that handle IS the spotting call: band must be 0, start / count /
+ * qual / logp are written through the call's own fcd_alignment (those four members of *spot are ignored), end, track and
+ * the range come from *spot -- enqueue-only on the handle's stream, behind overlapping searches, as ever.  spot = NULL
+ * turns it off.  fcd_ctc_align_host is not affected.  The switch changes what a call MEANS, not only its limits: between
+ * setting and clearing it the handle must not be shared with another thread (its fcd_ctc_align_dev would spot into this
+ * caller's end and track); the Python layer sets, calls and clears on the calling thread's own handle. */
+int fcd_set_ctc_spot(fcd_handle *h, const fcd_spot *spot);
+
 /* ---- CTC forward-backward substitution posteriors of given labellings (csrc/ctc_posterior.hip) ----
  * NOT a reference function.  For a labelling y of L labels (hypothesis i of read r, row = r * n_hyp + i), label position
  * k < L and label c in 1 .. N-1, let y[k:=c] be y with label k replaced by c.  With P as fcd_ctc_score_* defines it -- same
