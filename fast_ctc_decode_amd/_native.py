@@ -53,7 +53,7 @@ SYMBOLS = [
     "fcd_beam_session_bytes", "fcd_beam_session_destroy",
     "fcd_ctc_score_dev", "fcd_ctc_score_host",
     "fcd_ctc_align_dev", "fcd_ctc_align_host", "fcd_debug_set_align_workspace_cap", "fcd_debug_workspace_bytes",
-    "fcd_ctc_spot_host", "fcd_set_ctc_spot",
+    "fcd_ctc_spot_host", "fcd_set_ctc_spot", "fcd_ctc_detect_host", "fcd_set_ctc_detect",
     "fcd_ctc_posterior_dev", "fcd_ctc_posterior_host",
     "fcd_ctc_edits_dev", "fcd_ctc_edits_host",
     "fcd_crf_score_dev", "fcd_crf_score_host", "fcd_crf_align_dev", "fcd_crf_align_host",
@@ -105,6 +105,12 @@ class Spot(C.Structure):
     """fcd_spot: what fcd_ctc_spot_* writes, and the range of rows it looks in (include/fcd.h)."""
     _fields_ = Alignment._fields_ + [("end", C.c_void_p), ("track", C.c_void_p), ("track_stride", C.c_int64),
                                      ("row_begin", C.c_void_p), ("row_end", C.c_void_p)]
+
+
+class Detect(C.Structure):
+    """fcd_detect: what fcd_ctc_detect_* writes, and the range of rows it looks in (include/fcd.h)."""
+    _fields_ = [("count", C.c_void_p), ("end", C.c_void_p), ("logp", C.c_void_p), ("track", C.c_void_p),
+                ("track_stride", C.c_int64), ("row_begin", C.c_void_p), ("row_end", C.c_void_p)]
 
 
 class Posterior(C.Structure):
@@ -303,6 +309,8 @@ def bind(lib):
                 getattr(lib, "fcd_%s_%s_%s" % (model, kind, sfx)).argtypes = head + [C.POINTER(out) if out else P]
     lib.fcd_ctc_spot_host.argtypes = [P, BP, LP, i32, i64, C.POINTER(Spot)]  # (CTC only: no CRF counterpart)
     lib.fcd_set_ctc_spot.argtypes = [P, C.POINTER(Spot)]  # (device arrays: fcd_ctc_align_dev under this switch)
+    lib.fcd_ctc_detect_host.argtypes = [P, BP, LP, i32, i64, C.POINTER(Detect)]  # (CTC only)
+    lib.fcd_set_ctc_detect.argtypes = [P, C.POINTER(Detect)]  # (device arrays: fcd_ctc_score_dev under this switch)
     lib.fcd_debug_set_align_workspace_cap.argtypes = [P, i64]
     lib.fcd_debug_workspace_bytes.argtypes = [P]
     lib.fcd_debug_workspace_bytes.restype = i64

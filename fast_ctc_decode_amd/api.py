@@ -1938,6 +1938,15 @@ def _spot_out(xp, b, shape, lengths=None, rows=None, track=False):
     return C.byref(out), SpotResult(AlignResult(start, count, qual, logp), end, trk, (begin, stop))
 
 
+def _detect_out(xp, b, shape, lengths=None, rows=None, track=False):
+    count, logp, end = xp.empty(shape[:2], "f64"), xp.empty(shape[:2], "f64"), xp.empty(shape[:2], "u32")
+    trk = xp.full(shape[:2] + (int(b.T),), "f32", -math.inf) if track else None  # (rows outside the range stay -inf)
+    begin, stop = _spot_rows(xp, b, shape[0], lengths, rows)
+    out = nat.Detect(xp.ptr(count), xp.ptr(end), xp.ptr(logp), xp.ptr(trk) if track else None, int(b.T),
+                     xp.ptr(begin) if rows is not None else None, xp.ptr(stop) if rows is not None else None)
+    return C.byref(out), DetectResult(count, end, logp, trk, (begin, stop))
+
+
 def _posterior_out(xp, b, shape):
     post = xp.zeros(shape + (int(b.N) - 1,), "f32")
     logp = xp.empty(shape[:2], "f64")
@@ -2011,7 +2020,7 @@ def _occupancy_out(xp, b, shape, has_S, out=None, scale=1.0, accumulate=False, t
 
 
 _LATTICE_BUILDERS = {"score": _score_out, "align": _align_out, "posterior": _posterior_out, "edits": _edits_out,
-                     "occupancy": _occupancy_out, "spot": _spot_out}
+                     "occupancy": _occupancy_out, "spot": _spot_out, "detect": _detect_out}
 
 
 @contextlib.contextmanager
@@ -2034,8 +2043,8 @@ def _lattice_call(model, kind, network_outputs, labels, label_lengths, lengths, 
                   init_states=None, collapse_repeats=True, wide=False, **out_args):
     """The one body of the labelling-lattice calls: fcd_<model>_<kind>_dev for device tensors, _host for numpy, with
     model "ctc" (network_outputs (B,T,N), collapse_repeats) or "crf" ((B,T,S,N) and init_states), kind one of
-    _LATTICE_BUILDERS ("spot": CTC only); out_args: the occupancy calls' out, scale, accumulate and time_major_out, the
-    spotting call's rows and track.  -> what the call returns."""
+    _LATTICE_BUILDERS ("spot", "detect": CTC only); out_args: the occupancy calls' out, scale, accumulate and
+    time_major_out, the spotting and detecting calls' rows and track.  -> what the call returns."""
     band = _check_band(band, paths)
     if kind == "occupancy":
         _check_occupancy_out(**out_args)
@@ -2043,7 +2052,7 @@ def _lattice_call(model, kind, network_outputs, labels, label_lengths, lengths, 
     h, b, y, shape, dev, keep = _lattice_inputs(network_outputs, labels, label_lengths, lengths, paths, band, n_valid,
                                                 input_dtype, handle, init_states)
     xp = _Arrays(dev)
-    if kind == "spot":
+    if kind in ("spot", "detect"):
         out_args["lengths"] = keep.lengths  # (rows counts from every read's own length)
     out, result = _LATTICE_BUILDERS[kind](xp, b, shape, **out_args)
     if model == "crf":
@@ -2052,16 +2061,23 @@ def _lattice_call(model, kind, network_outputs, labels, label_lengths, lengths, 
     else:
         args = (C.byref(b), C.byref(y), int(bool(collapse_repeats)), band, out)
     spot_dev = kind == "spot" and dev is not None  # (include/fcd.h: fcd_ctc_align_dev under the handle's fcd_set_ctc_spot)
-    fn = getattr(h.lib, "fcd_%s_%s_%s" % (model, "align" if spot_dev else kind, "host" if dev is None else "dev"))
+    detect_dev = kind == "detect" and dev is not None  # (likewise: fcd_ctc_score_dev under fcd_set_ctc_detect)
+    fn = getattr(h.lib, "fcd_%s_%s_%s" % (model, "align" if spot_dev else "score" if detect_dev else kind,
+                                          "host" if dev is None else "dev"))
     with _wide_switch(h, model, wide):
         if spot_dev:
             h.check(h.lib.fcd_set_ctc_spot(h.ptr, out))
             args = args[:-1] + (C.cast(out, C.POINTER(nat.Alignment)),)  # (fcd_spot begins with fcd_alignment's four pointers)
+        if detect_dev:
+            h.check(h.lib.fcd_set_ctc_detect(h.ptr, out))
+            args = args[:-1] + (C.c_void_p(xp.ptr(result.logp)),)  # (the score's own logp array)
         try:
             h.check(fn(h.ptr, *args))
         finally:
             if spot_dev:
                 h.lib.fcd_set_ctc_spot(h.ptr, None)
+            if detect_dev:
+                h.lib.fcd_set_ctc_detect(h.ptr, None)
     if kind == "occupancy" and dev is not None:
         h.hold_in_flight(result.occupancy, result.logp, *keep)
     return result
@@ -2236,6 +2252,59 @@ def ctc_spot(network_output, motif, alphabet, collapse_repeats=True, rows=None):
     if int(r.end[0, 0]) == NO_HIT:
         return None
     return int(r.start[0, 0]), int(r.end[0, 0]), float(r.logp[0, 0])
+
+
+# ---------------------------------------------------------------------------------------------
+# CTC motif occurrence posteriors: soft spotting, expected counts (include/fcd.h, fcd_ctc_detect_*)
+# ---------------------------------------------------------------------------------------------
+class DetectResult:
+    """Outcome of ctc_detect_batch_raw, for motif i of read r: count[r, i] (float64) is the expected number of occurrences
+    of the motif in the labelling of the read's range of rows -- a probability scale shared by motifs of every length, an
+    upper bound of P(at least one); end[r, i] is the row at which an occurrence most probably ends (NO_HIT -- -1 in a
+    device result's int32, the same 32 bits -- where no row has any mass) and logp[r, i] (float64) ln of that
+    probability; track[r, i, t] (float32, (B, M, T), None unless asked for) is ln P(an occurrence ends at row t), -inf
+    where it is 0 and outside the range.  numpy for host inputs, torch tensors (same device) for device inputs."""
+
+    def __init__(self, count, end, logp, track, rows=(None, None)):
+        self.count, self.end, self.logp, self.track = count, end, logp, track
+        self._rows = rows  # (row_begin, row_end): alive as long as the result
+
+    def cpu(self):
+        end = _to_host(self.end)
+        return DetectResult(_to_host(self.count), end if end.dtype == np.uint32 else end.view(np.uint32),
+                            _to_host(self.logp), _to_host(self.track))
+
+
+def ctc_detect_batch_raw(network_outputs, motifs, motif_lengths, collapse_repeats=True, lengths=None, rows=None,
+                         track=False, input_dtype=None, handle=None):
+    """CTC motif occurrence posteriors: how probable it is that each of M known sequences occurs in every read -- the sum
+    over ALL alignments of the motif to any run of consecutive rows, weighted so that every occurrence is counted once
+    (include/fcd.h, fcd_ctc_detect_*).  -> DetectResult, arrays (B, M[, T]).
+
+    motifs, motif_lengths, rows and track as ctc_spot_batch_raw takes them.  Demultiplexing: count.argmax(1) is the
+    barcode of every read, count.max(1) what to threshold.  Device tensors in: torch tensors on the same device,
+    enqueued on torch's current stream, not synchronised.  numpy in: numpy out."""
+    m = np.asarray(_to_host(motifs), np.uint8)
+    if m.ndim != 2:
+        raise ValueError("motifs must have shape (n_motifs, stride)")
+    if rows is not None and (not isinstance(rows, (tuple, list)) or len(rows) != 2):
+        raise ValueError("rows must be a pair (lo, hi)")
+    B = len(network_outputs)
+    n = np.asarray(_to_host(motif_lengths), np.uint32).reshape(-1)
+    if n.size != m.shape[0]:
+        raise ValueError("motif_lengths must have one entry per motif")
+    return _lattice_call("ctc", "detect", network_outputs, np.tile(m[None], (B, 1, 1)), np.tile(n[None], (B, 1)), lengths,
+                         None, 0, None, input_dtype, handle, collapse_repeats=collapse_repeats, rows=rows, track=bool(track))
+
+
+def ctc_detect(network_output, motif, alphabet, rows=None):
+    """One string in one (T, N) float32 posterior matrix: -> (count, end, logp), the expected number of its occurrences,
+    the row at which one most probably ends (None where there is none) and ln of that probability.
+    rows=(lo, hi): look in network_output[lo:hi] only."""
+    x, lab, n, _ = _ctc_one_read(network_output, motif, alphabet, "ctc_detect")
+    r = ctc_detect_batch_raw(x, lab, n, rows=rows)
+    end = int(r.end[0, 0])
+    return float(r.count[0, 0]), (None if end == NO_HIT else end), float(r.logp[0, 0])
 
 
 # ---------------------------------------------------------------------------------------------

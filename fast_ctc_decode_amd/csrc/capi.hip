@@ -1945,6 +1945,7 @@ struct LatticeCall {
     bool wide = false;  // (CTC occupancy) fcd_set_ctc_occupancy_wide: windows beyond the registers walk score_lds_kernel
     bool crf_wide = false;  // (CRF score, occupancy) fcd_set_crf_lattice_wide: windows beyond 512 states walk in LDS
     const fcd_spot *spot = nullptr;  // (CTC align) fcd_ctc_spot_*: `out` holds its first four pointers
+    const fcd_detect *detect = nullptr;  // (CTC score) fcd_ctc_detect_*: `logp` is its logp
 };
 
 // the call is one of those the CRF switch covers AND its window is beyond the registers: every other call is what it is
@@ -1960,15 +1961,18 @@ size_t occupancy_span(const fcd_batch *in, const fcd_labellings *y, const fcd_oc
     return (size_t)((in->n_reads * y->n_hyp - 1) * o->stride_row + (in->T - 1) * o->stride_t + in->S * in->N);
 }
 
-// floats from the first to the last element the call may address in spot->track (0: none)
-size_t track_span(const fcd_batch *in, const fcd_labellings *y, const fcd_spot *s) {
+// floats from the first to the last element the call may address in spot->track / detect->track (0: none)
+size_t track_floats(const fcd_batch *in, const fcd_labellings *y, const float *track, int64_t track_stride) {
     const size_t n_rows = (size_t)in->n_reads * (size_t)y->n_hyp;
-    return n_rows && s->track ? (n_rows - 1) * (size_t)s->track_stride + (size_t)in->T : 0;
+    return n_rows && track ? (n_rows - 1) * (size_t)track_stride + (size_t)in->T : 0;
 }
+size_t track_span(const fcd_batch *in, const fcd_labellings *y, const fcd_spot *s) { return track_floats(in, y, s->track, s->track_stride); }
+size_t detect_track_span(const fcd_batch *in, const fcd_labellings *y, const fcd_detect *s) { return track_floats(in, y, s->track, s->track_stride); }
 
 int lattice_check(fcd_handle *h, const LatticeCall &c) {
     if (c.align && !c.out) return fail(h, FCD_E_INVALID, "null alignment");
     if (c.spot && c.band != 0) return fail(h, FCD_E_INVALID, "ctc_spot: band must be 0 (the motif is looked for in the exact lattice)");
+    if (c.detect && c.band != 0) return fail(h, FCD_E_INVALID, "ctc_detect: band must be 0 (the motif is looked for in the exact lattice)");
     if (c.posterior && !c.post) return fail(h, FCD_E_INVALID, "null posterior");
     if (c.edit && !c.edits) return fail(h, FCD_E_INVALID, c.crf ? "crf_edits: null output" : "ctc_edits: null output");
     const std::string occ_who = c.crf ? "crf_occupancy" : (c.wide ? "ctc_occupancy_wide" : "ctc_occupancy");
@@ -1990,9 +1994,9 @@ int lattice_check(fcd_handle *h, const LatticeCall &c) {
     if (y->stride < 0) return fail(h, FCD_E_INVALID, "negative stride");
     if (in->n_reads > 0 && (!y->labels || !y->len ||
                             !(c.occupancy ? (const void *)c.occ->occ : c.edit ? (const void *)c.edits->deletion : c.posterior ? (const void *)c.post->post
-                              : c.align ? (const void *)c.out->start : (const void *)c.logp)))
+                              : c.align ? (const void *)c.out->start : c.detect ? (const void *)c.detect->count : (const void *)c.logp)))
         return fail(h, FCD_E_INVALID, c.occupancy ? (c.crf ? "crf_occupancy: null labels/len/occ" : c.wide ? "ctc_occupancy_wide: null labels/len/occ" : "ctc_occupancy: null labels/len/occ") : c.edit ? (c.crf ? "crf_edits: null labels/len/deletion" : "ctc_edits: null labels/len/deletion") : c.posterior ? "null labels/len/post"
-                                      : c.align ? "null labels/len/start" : "null labels/len/logp");
+                                      : c.align ? "null labels/len/start" : c.detect ? "ctc_detect: null labels/len/count" : "null labels/len/logp");
     if (c.edit && in->n_reads > 0 && !c.edits->insertion) return fail(h, FCD_E_INVALID, c.crf ? "crf_edits: null insertion" : "ctc_edits: null insertion");
     if (in->n_reads * y->n_hyp >= (1ll << 31)) return fail(h, FCD_E_UNSUPPORTED, "more than 2^31 labellings in one call");
     if (c.crf && crf_wide_call(c)) {
@@ -2023,6 +2027,10 @@ int lattice_check(fcd_handle *h, const LatticeCall &c) {
     if (c.align && in->n_reads > 0 && !c.out->count) return fail(h, FCD_E_INVALID, "null count");
     if (c.spot && in->n_reads > 0 && !c.spot->end) return fail(h, FCD_E_INVALID, "ctc_spot: null end");
     if (c.spot && c.spot->track && c.spot->track_stride < in->T) return fail(h, FCD_E_INVALID, "ctc_spot: track_stride must hold the T rows of a read");
+    if (c.detect && in->n_reads > 0 && !c.detect->end) return fail(h, FCD_E_INVALID, "ctc_detect: null end");
+    if (c.detect && c.detect->track && c.detect->track_stride < in->T) return fail(h, FCD_E_INVALID, "ctc_detect: track_stride must hold the T rows of a read");
+    if (c.detect && !ctc_detect_supported(in->T, y->stride))
+        return fail(h, FCD_E_UNSUPPORTED, "ctc_detect: motifs beyond 5119 labels exceed the 10240 states of 1024 work-items: use a smaller stride");
     if (c.occupancy) {  // (a CTC batch has S = 1: its rows are N floats)
         if (c.occ->stride_row < 0 || c.occ->stride_t < in->S * in->N)
             return fail(h, FCD_E_INVALID, (occ_who + (c.crf ? ": stride_t must hold a dense (S, N) row, stride_row must not be negative"
@@ -2115,7 +2123,7 @@ int lattice_score(fcd_handle *h, const LatticeCall &c) {
 // row_bytes each.  Whole reads per launch, as many as `cap` bytes hold (at least one), every launch in the same memory, one
 // after the other on the stream; logp lent from the workspace when the caller wants none.  add_outputs(sc): the arrays the
 // call writes; launch(d, yd, r0, row0, logp, ws, stream): one group -- reads r0 .., labellings row0 .., its slice of logp.
-// tail_bytes > 0 (fcd_ctc_spot_*'s parameter blocks): that many more bytes of the workspace for EVERY group, behind
+// tail_bytes > 0 (fcd_ctc_spot_*'s and fcd_ctc_detect_*'s parameter blocks): that many more bytes of the workspace for EVERY group, behind
 // everything else.  fill(r0, row0, block) writes a group's block on the host -- into the handle's tail_host, which stays
 // as it is until the next such call -- all of them go to the device in ONE copy ahead of the launches, and *tail is the
 // device address of the block of the group being launched.
@@ -2128,7 +2136,8 @@ int lattice_grouped(fcd_handle *h, const LatticeCall &c, size_t row_bytes, int64
     const fcd_labellings *y = c.y;
     const size_t n_rows = (size_t)in->n_reads * (size_t)y->n_hyp;
     const int64_t read_bytes = (int64_t)(row_bytes * (size_t)y->n_hyp);
-    const int64_t group = std::max<int64_t>(1, std::min<int64_t>(in->n_reads, cap / read_bytes));
+    // (row_bytes 0 -- fcd_ctc_detect_*, which needs the parameter blocks alone: one group)
+    const int64_t group = std::max<int64_t>(1, read_bytes ? std::min<int64_t>(in->n_reads, cap / read_bytes) : in->n_reads);
     const size_t o_logp = (size_t)group * (size_t)read_bytes;
     CallScope sc(h);
     add_labellings(sc, c, n_rows);
@@ -2162,6 +2171,33 @@ int lattice_grouped(fcd_handle *h, const LatticeCall &c, size_t row_bytes, int64
         FCD_HIP(h, launch(d, yd, r0, row0, logp + row0, reinterpret_cast<unsigned char *>(ws), sc.stream));
     }
     return sc.finish();
+}
+
+// fcd_ctc_detect_*: the score's launch with the detect outputs and ranges, one block per launch group, behind it
+int lattice_detect(fcd_handle *h, const LatticeCall &c) {
+    const fcd_batch *in = c.in;
+    const fcd_labellings *y = c.y;
+    const fcd_detect *s = c.detect;
+    char *block = nullptr;  // the DetectOut of the group being launched, in the workspace
+    return lattice_grouped(
+        h, c, 0, 0, c.logp,
+        [&](CallScope &sc) {
+            sc.add(s->count, (size_t)in->n_reads * (size_t)y->n_hyp * 8);
+            sc.add(s->end, (size_t)in->n_reads * (size_t)y->n_hyp * 4);
+            sc.add(s->track, detect_track_span(in, y, s) * 4);
+            sc.add(s->row_begin, (size_t)in->n_reads * 4);
+            sc.add(s->row_end, (size_t)in->n_reads * 4);
+        },
+        [&](const BatchDesc &d, const ScoreDesc &yd, int64_t, int64_t, double *logp, unsigned char *, hipStream_t stream) {
+            return launch_ctc_score(d, yd, c.collapse, 0, logp, stream, reinterpret_cast<const DetectOut *>(block));
+        },
+        256,
+        [&](int64_t r0, int64_t row0, void *host) {
+            *static_cast<DetectOut *>(host) = DetectOut{s->count + row0, s->end + row0, s->track ? s->track + row0 * s->track_stride : nullptr,
+                                                        s->track_stride, s->row_begin ? s->row_begin + r0 : nullptr,
+                                                        s->row_end ? s->row_end + r0 : nullptr};
+        },
+        &block);
 }
 
 int lattice_align(fcd_handle *h, const LatticeCall &c) {
@@ -2269,6 +2305,7 @@ int lattice_occupancy(fcd_handle *h, const LatticeCall &c) {
 int lattice_run(fcd_handle *h, const LatticeCall &c) {
     if (c.occupancy) return lattice_occupancy(h, c);
     if (c.edit) return lattice_edits(h, c);
+    if (c.detect) return lattice_detect(h, c);
     return c.posterior ? lattice_posterior(h, c) : (c.align ? lattice_align(h, c) : lattice_score(h, c));
 }
 
@@ -2310,6 +2347,12 @@ int lattice_host(fcd_handle *h, const LatticeCall &c) {
     const int i_track = c.spot ? st.inout(c.spot->track, track_span(in, y, c.spot) * 4) : -1;
     const int i_rb = c.spot ? st.in(c.spot->row_begin, B * 4) : -1;
     const int i_re = c.spot ? st.in(c.spot->row_end, B * 4) : -1;
+    const fcd_detect *det = c.detect;
+    const int i_dcount = det ? st.out(det->count, n_rows * 8) : -1;
+    const int i_dend = det ? st.out(det->end, n_rows * 4) : -1;
+    const int i_dtrack = det ? st.inout(det->track, detect_track_span(in, y, det) * 4) : -1;
+    const int i_drb = det ? st.in(det->row_begin, B * 4) : -1;
+    const int i_dre = det ? st.in(det->row_end, B * 4) : -1;
     // (posterior entries the kernel does not write -- k >= len -- come back as 0)
     const int i_sub = c.posterior ? st.out(c.post->post, cells * ((size_t)in->N - 1) * 4, true) : -1;
     // (edit entries the kernel does not write -- k >= len, g > len -- come back as 0)
@@ -2344,6 +2387,17 @@ int lattice_host(fcd_handle *h, const LatticeCall &c) {
         dspot.row_end = st.at<uint32_t>(i_re);
         d.spot = &dspot;
     }
+    fcd_detect ddet{};
+    if (det) {
+        ddet = *det;
+        ddet.count = st.at<double>(i_dcount);
+        ddet.end = st.at<uint32_t>(i_dend);
+        ddet.logp = st.at<double>(i_logp);
+        ddet.track = st.at<float>(i_dtrack);
+        ddet.row_begin = st.at<uint32_t>(i_drb);
+        ddet.row_end = st.at<uint32_t>(i_dre);
+        d.detect = &ddet;
+    }
     const fcd_posterior dpost{st.at<float>(i_sub), st.at<double>(i_logp)};
     d.post = &dpost;
     const fcd_edits dedits{st.at<float>(i_del), st.at<float>(i_ins), st.at<double>(i_logp)};
@@ -2361,10 +2415,41 @@ int lattice_host(fcd_handle *h, const LatticeCall &c) {
 }
 }  // namespace
 
+namespace {
+// fcd_ctc_detect_*: a scoring call with the detect outputs behind it
+int detect_call(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int collapse_repeats, int64_t band, const fcd_detect *out,
+                int (*run)(fcd_handle *, const LatticeCall &)) {
+    if (!out) return fail(h, FCD_E_INVALID, "ctc_detect: null output");
+    LatticeCall c{false, false, in, y, band, collapse_repeats != 0, nullptr, 0, 0, out->logp, nullptr};
+    c.detect = out;
+    return run(h, c);
+}
+}  // namespace
+
+int fcd_set_ctc_detect(fcd_handle *h, const fcd_detect *detect) {
+    if (!h) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> g(h->mu);
+    h->detect_on = detect != nullptr;
+    h->detect = detect ? *detect : fcd_detect{};
+    return FCD_OK;
+}
+
+int fcd_ctc_detect_host(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int collapse_repeats, int64_t band,
+                        const fcd_detect *out) {
+    if (!h) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> whole_call(h->mu);  // staging .. copy-back, see run_host
+    return detect_call(h, in, y, collapse_repeats, band, out, lattice_host);
+}
+
 int fcd_ctc_score_dev(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int collapse_repeats, int64_t band,
                       double *logp) {
     if (!h) return FCD_E_INVALID;
     std::lock_guard<std::recursive_mutex> g(h->mu);
+    if (h->detect_on) {  // fcd_set_ctc_detect: the detecting call, ln c_end into this call's own `logp`
+        fcd_detect s = h->detect;
+        s.logp = logp;
+        return detect_call(h, in, y, collapse_repeats, band, &s, lattice_dev);
+    }
     return lattice_dev(h, LatticeCall{false, false, in, y, band, collapse_repeats != 0, nullptr, 0, 0, logp, nullptr});
 }
 

@@ -47,25 +47,7 @@ template <int K> struct BpWord { typedef uint16_t type; };
 template <> struct BpWord<2> { typedef uint8_t type; };
 template <> struct BpWord<4> { typedef uint8_t type; };
 
-// fill_tile of ctc_lattice.h, and the flag
-__device__ __forceinline__ void fill_tile_checked(const ScoreParams &p, const Lds &lds, const Row &rw, int t0, int rc) {
-    const int tid = threadIdx.x, bd = blockDim.x;
-    __syncthreads();  // the previous tile's readers are done
-    bool bad = false;
-    for (int e = tid; e < rc * rw.N; e += bd) {
-        const int i = e / rw.N, j = e - i * rw.N;
-        const float v = load_post(rw.post, (int64_t)(t0 + i) * p.in.stride_t + (int64_t)j * p.in.stride_n, p.in.dtype);
-        int ex = 0;
-        float m = v;
-        if (v - v == 0.0f) m = frexpf(v, &ex);
-        bad |= !(v >= 0.0f && v - v == 0.0f);
-        lds.pm[e] = m;
-        lds.pe[e] = ex;
-    }
-    if (bad) lds.misc[kBadPost] = 1;
-    if (p.band > 0 && tid < rc) lds.krow[tid] = labels_up_to(rw.path, rw.L, (uint32_t)(t0 + tid));
-    __syncthreads();
-}
+// (fill_tile_checked -- fill_tile and the bad-posterior flag -- and row_range: ctc_lattice.h, shared with ctc_score.hip's detecting walks)
 
 // a row without an alignment: count = 0 for the labels the row holds (its logp is written already)
 __device__ __forceinline__ void no_alignment(const AlignParams &q) {
@@ -86,24 +68,9 @@ __device__ __forceinline__ void no_alignment(const AlignParams &q) {
 // eacc rises and state 0 falls below 2^(kTarget - 1) by as much; nothing is lost until the cells pass 2^245, where fresh
 // starts underflow to 0 as any cell that far below its row's maximum does.
 
-// the rows [b, e) of the read the motif is looked for in take the read's place: Row::post advanced to row b (*tb), Tr
-// shrunk to e - b.  Returns false when the row's result is written already (every work-item agrees).
+// the rows [b, e) of the read the motif is looked for in take the read's place (row_range of ctc_lattice.h)
 __device__ __forceinline__ bool spot_range(const AlignParams &q, Row *rw, int *tb) {
-    const ScoreParams &p = q.s;
-    const int64_t row = blockIdx.x, read = row / p.y.n_hyp;
-    const int64_t Tr = rw->Tr;
-    const uint32_t *row_begin = q.spot->row_begin, *row_end = q.spot->row_end;
-    const int b = row_begin ? (int)min((int64_t)row_begin[read], Tr) : 0;
-    const int e = row_end ? (int)min((int64_t)row_end[read], Tr) : rw->Tr;
-    const int rows = max(e - b, 0);
-    if (rw->L == 0 || rw->L > rows) {  // no motif: 0.0; more labels than rows: no hit
-        if (threadIdx.x == 0) p.logp[row] = rw->L == 0 ? 0.0 : -(double)INFINITY;
-        return false;
-    }
-    rw->post = post_at(rw->post, (int64_t)b * p.in.stride_t, p.in.dtype);
-    rw->Tr = rows;
-    *tb = b;
-    return true;
+    return row_range(q.s, q.spot->row_begin, q.spot->row_end, rw, tb);
 }
 
 // what a spotting walk carries: wave-uniform but for the staged pair

@@ -21,7 +21,7 @@ constexpr int kTileRows = 64;         // ... at most this many rows (one lane pe
 constexpr int kLdsCells = 20;         // LDS kernel: cells per work-item and step
 constexpr int kMiscWords = 32;        // [0..15] per-wave maxima, [16] bad-label flag, [17] kBadPost, [18] [19] the two final cells,
                                       // [20] kKrowBefore
-constexpr int kBadPost = 17;          // misc word of ctc_align.hip: the read holds a posterior no comparison can order
+constexpr int kBadPost = 17;          // misc word of fill_tile_checked: the read holds a posterior no comparison can order
 constexpr int kKrowBefore = 20;       // misc word of ctc_posterior.hip: k(t) of the row before the tile
 
 struct ScoreParams {
@@ -158,6 +158,46 @@ __device__ __forceinline__ void fill_tile(const ScoreParams &p, const Lds &lds, 
     }
     if (p.band > 0 && tid < rc) lds.krow[tid] = labels_up_to(rw.path, rw.L, (uint32_t)(t0 + tid));
     __syncthreads();
+}
+
+// fill_tile, and the flag: a NaN, infinite or negative posterior among the staged rows sets misc[kBadPost] (cleared by the
+// walk before its first tile)
+__device__ __forceinline__ void fill_tile_checked(const ScoreParams &p, const Lds &lds, const Row &rw, int t0, int rc) {
+    const int tid = threadIdx.x, bd = blockDim.x;
+    __syncthreads();  // the previous tile's readers are done
+    bool bad = false;
+    for (int e = tid; e < rc * rw.N; e += bd) {
+        const int i = e / rw.N, j = e - i * rw.N;
+        const float v = load_post(rw.post, (int64_t)(t0 + i) * p.in.stride_t + (int64_t)j * p.in.stride_n, p.in.dtype);
+        int ex = 0;
+        float m = v;
+        if (v - v == 0.0f) m = frexpf(v, &ex);
+        bad |= !(v >= 0.0f && v - v == 0.0f);
+        lds.pm[e] = m;
+        lds.pe[e] = ex;
+    }
+    if (bad) lds.misc[kBadPost] = 1;
+    if (p.band > 0 && tid < rc) lds.krow[tid] = labels_up_to(rw.path, rw.L, (uint32_t)(t0 + tid));
+    __syncthreads();
+}
+
+// A free-ended walk (fcd_ctc_spot_*, fcd_ctc_detect_*): the rows [b, e) of the read the motif is looked for in take the
+// read's place: Row::post advanced to row b (*tb), Tr shrunk to e - b.  row_begin / row_end: per read, nullable.  Returns
+// false when the row's logp is written already (every work-item agrees).
+__device__ __forceinline__ bool row_range(const ScoreParams &p, const uint32_t *row_begin, const uint32_t *row_end, Row *rw, int *tb) {
+    const int64_t row = blockIdx.x, read = row / p.y.n_hyp;
+    const int64_t Tr = rw->Tr;
+    const int b = row_begin ? (int)min((int64_t)row_begin[read], Tr) : 0;
+    const int e = row_end ? (int)min((int64_t)row_end[read], Tr) : rw->Tr;
+    const int rows = max(e - b, 0);
+    if (rw->L == 0 || rw->L > rows) {  // no motif: 0.0; more labels than rows: no hit
+        if (threadIdx.x == 0) p.logp[row] = rw->L == 0 ? 0.0 : -(double)INFINITY;
+        return false;
+    }
+    rw->post = post_at(rw->post, (int64_t)b * p.in.stride_t, p.in.dtype);
+    rw->Tr = rows;
+    *tb = b;
+    return true;
 }
 
 // live states of row t: the band around the path (k = k(t), read only when banded), cut to what can be reached and can

@@ -36,14 +36,114 @@ __device__ __forceinline__ void write_result(const ScoreParams &p, float c0, flo
     p.logp[blockIdx.x] = ln_p((double)c0 + (double)c1, eacc);
 }
 
+// ---- motif occurrence posteriors: the forward sum free at both ends (fcd_ctc_detect_*, include/fcd.h) ----
+// The walk is the score's over the rows [b, e) of the read and the states 1 .. 2L - 1 (window_k<true>), with
+//   entry  state 0 is no cell: its slot holds g_t * 2^-eacc, g_b = 1 and g_t = max(0, 1 - p[t-1][y_0]) under collapse (1
+//          without), written after row t - 1's rescale from the tile that row was read from.  Like ctc_align.hip's pinned
+//          state a TRUE 1 (not g) takes part in the row maximum: with posteriors <= 1 the cells are probabilities of disjoint
+//          events, eacc stays at 1 - kTarget, and a cell below 2^-245 as a probability is below f32's range and counts as 0.
+//   exit   v_t = a_t[2L - 1] is read with one readlane; c_t = v_t * h_t, h_t = max(0, 1 - p[t+1][y_{L-1}]) under collapse,
+//          needs the NEXT row: (v_t, eacc) wait in two registers (across a tile boundary too) and c_t is completed at row
+//          t + 1, the range's last row at once with h = 1.
+// Every c_t, in row order: added to a float64 sum (ldexp by the row's exponent: exact), compared with the running best as
+// (exponent, mantissa) -- a later row only if strictly greater, no logarithm -- and, with a track, kept as a pair by
+// work-item t mod 64 until 64 rows are stored at once (ctc_align.hip's spot_row).  Wave-uniform but for that pair.
+constexpr uint32_t kNoHit = 0xFFFFFFFFu;
+constexpr float kLn2f = 0.693147180559945309f;
+
+struct Detect {
+    double sum;  // c_b + .. so far
+    float bm;    // the best c so far, normalised: mantissa in [0.5, 1) ...
+    int be;      // ... its exponent in true scale ...
+    int bt;      // ... and its row (of the range); -1: none yet
+    float vp;    // v of the row before, in that row's units ...
+    int ep;      // ... 2^ep
+    float tm;    // lane j: the pair of row c0 + j of the 64 rows of `track` being staged
+    int te;
+};
+
+// max(0, 1 - p) of a staged posterior (one f32 rounding)
+__device__ __forceinline__ float one_minus(const Lds &lds, int at) {
+    return fmaxf(0.0f, 1.0f - ldexpf(lds.pm[at], lds.pe[at]));
+}
+
+// state 0's slot in the walk's units (eacc is at least 1 - kTarget in a free-ended walk, and an int)
+__device__ __forceinline__ float entry_cell(float g, int64_t eacc) {
+    const int e = (int)eacc;
+    return ldexpf(g, e > 512 ? -512 : -e);
+}
+
+// c_t = c * 2^e is complete (t: row of the range)
+__device__ __forceinline__ void detect_cell(const DetectOut *det, Detect &dt, float c, int e, int t, int Tr, int tb) {
+    float m = 0.0f;
+    int ex = 0;
+    if (c > 0.0f && c - c == 0.0f) {
+        dt.sum += ldexp((double)c, e);
+        m = frexpf(c, &ex);
+        ex += e;
+        if (dt.bt < 0 || ex > dt.be || (ex == dt.be && m > dt.bm)) {
+            dt.bm = m;
+            dt.be = ex;
+            dt.bt = t;
+        }
+    }
+    float *track = det->track;
+    if (track) {
+        const int j = threadIdx.x;
+        if (j == (t & 63)) {
+            dt.tm = m;
+            dt.te = ex;
+        }
+        if ((t & 63) == 63 || t == Tr - 1) {
+            const int c0 = t & ~63;
+            if (j < 64 && c0 + j <= t)
+                track[(int64_t)blockIdx.x * det->track_stride + tb + c0 + j] =
+                    dt.tm > 0.0f ? fmaf((float)dt.te, kLn2f, logf(dt.tm)) : -INFINITY;
+        }
+    }
+}
+
+// row t of the range is done: v, its cell of state 2L - 1 in units 2^eacc; h, the exit weight of the row BEFORE, which
+// is completed now (the range's last row: by detect_finish)
+__device__ __forceinline__ void detect_row(const DetectOut *det, Detect &dt, float v, int64_t eacc, float h, int t, int Tr, int tb) {
+    if (t > 0) detect_cell(det, dt, dt.vp * h, dt.ep, t - 1, Tr, tb);
+    dt.vp = v;
+    dt.ep = (int)eacc;
+}
+
+// a row that does not walk: its logp is written already (NaN, -inf, or 0 for an empty motif)
+__device__ __forceinline__ void no_detect(const ScoreParams &p, const DetectOut *det) {
+    if (threadIdx.x == 0) {
+        const double lp = p.logp[blockIdx.x];
+        det->count[blockIdx.x] = lp != lp ? lp : 0.0;
+        det->end[blockIdx.x] = kNoHit;
+    }
+}
+
+__device__ __forceinline__ void detect_finish(const ScoreParams &p, const DetectOut *det, const Lds &lds, Detect &dt, int Tr, int tb) {
+    detect_cell(det, dt, dt.vp, dt.ep, Tr - 1, Tr, tb);  // the last row: h = 1
+    if (threadIdx.x == 0) {
+        const bool bad = lds.misc[kBadPost] != 0;
+        p.logp[blockIdx.x] = bad ? (double)NAN : (dt.bt < 0 ? -(double)INFINITY : ln_p((double)dt.bm, dt.be));
+        det->count[blockIdx.x] = bad ? (double)NAN : dt.sum;
+        det->end[blockIdx.x] = bad || dt.bt < 0 ? kNoHit : (uint32_t)(tb + dt.bt);
+    }
+}
+
 // ---- the register-resident window ----
-template <int K>
-__global__ __launch_bounds__(64) void score_reg_kernel(ScoreParams p) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+// DETECT: `det` non-null as a compile-time copy -- the kernel branches on it ONCE, so that a score's rows run the
+// instructions they ran before the detecting walk existed
+template <int K, bool DETECT>
+__device__ __forceinline__ void score_reg_walk(const ScoreParams &p, const DetectOut *det, unsigned char *smem) {
     constexpr int C = 64 * K;
     const Lds lds = carve(smem, p.lab_cap);
     Row rw;
-    if (!prologue(p, lds, &rw)) return;
+    int tb = 0;  // (detecting: the first row of the range)
+    if (DETECT) {
+        if (!prologue(p, lds, &rw) || !row_range(p, det->row_begin, det->row_end, &rw, &tb)) return no_detect(p, det);
+    } else {
+        if (!prologue(p, lds, &rw)) return;
+    }
     const int lane = threadIdx.x;
     float a[K];  // alpha of the lane's K states, scaled by 2^-eacc
 #pragma unroll
@@ -51,13 +151,24 @@ __global__ __launch_bounds__(64) void score_reg_kernel(ScoreParams p) {
     if (lane == 0) a[0] = 1.0f;  // "row -1": all mass on state 0, so that row 0 comes out as p[0][0], p[0][y0]
     int64_t eacc = 0;
     int lo_prev = 0, lo = 0, hi = 0;
+    Detect dt{0.0, 0.0f, 0, -1, 0.0f, 0, 0.0f, 0};
+    // (detecting: lo stays 1) the first and the last label, and where state 2L - 1 lives
+    const int y_first = DETECT ? lds.lab[0] & 0xFF : 0, y_last = DETECT ? lds.lab[rw.L - 1] & 0xFF : 0;
+    const int end_lane = DETECT ? (2 * rw.L - 1) / K : 0, end_r = DETECT ? (2 * rw.L - 1) % K : 0;
+    if (DETECT && lane == 0) lds.misc[kBadPost] = 0;
     for (int t0 = 0; t0 < rw.Tr; t0 += rw.rows_per_tile) {
         const int rc = min(rw.rows_per_tile, rw.Tr - t0);
-        fill_tile(p, lds, rw, t0, rc);
-        StepIn<K> in = load_step<K>(p, lds, rw, t0, 0);
+        if (DETECT) fill_tile_checked(p, lds, rw, t0, rc);
+        else fill_tile(p, lds, rw, t0, rc);
+        StepIn<K> in = load_step<K, DETECT>(p, lds, rw, t0, 0);
         for (int i = 0; i < rc; ++i) {
             StepIn<K> nx = in;
-            if (i + 1 < rc) nx = load_step<K>(p, lds, rw, t0 + i + 1, i + 1);
+            if (i + 1 < rc) nx = load_step<K, DETECT>(p, lds, rw, t0 + i + 1, i + 1);
+            float g = 1.0f, h = 1.0f;  // (detecting) the entry weight of the NEXT row, the exit weight of the row BEFORE
+            if (DETECT && p.collapse) {
+                g = one_minus(lds, i * rw.N + y_first);
+                h = one_minus(lds, i * rw.N + y_last);
+            }
             lo = in.lo;
             hi = in.hi;
             if (hi - lo_prev >= C) {  // the window jumped (several labels on one row): slots it re-enters start from 0
@@ -84,19 +195,31 @@ __global__ __launch_bounds__(64) void score_reg_kernel(ScoreParams p) {
                     u[r] = sum * in.pm0;
                     ex[r] = in.pe0;
                 }
+                if (DETECT) FCD_OPAQUE_VQ(u[r]);  // (the detecting copy's cells stay scalar f32 operations: see score_reg_kernel)
                 const int e = finite_exp(u[r]);
                 emax = max(emax, ((in.in_mask >> r) & 1) && e != kNoExp ? e + ex[r] : kNoExp);
             }
+            if (DETECT) emax = max(emax, 1 - (int)eacc);  // state 0's 1: 2^-eacc in the units the row was computed in
             emax = wave_imax(emax);
             const int sh = emax == kNoExp ? 0 : kTarget - emax;
             eacc -= sh;
 #pragma unroll
             for (int r = 0; r < K; ++r)
                 a[r] = ((in.in_mask >> r) & 1) ? ldexpf(u[r], min(max(ex[r] + sh, -512), 512)) : 0.0f;
+            if (DETECT) {
+                if (lane == 0) a[0] = entry_cell(g, eacc);  // the slot of state 0 (outside the window: no cell), after the rescale
+                float mine = 0.0f;
+#pragma unroll
+                for (int r = 1; r < K; r += 2)
+                    if (r == end_r) mine = a[r];
+                const float v = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine), end_lane));
+                detect_row(det, dt, v, eacc, h, t0 + i, rw.Tr, tb);
+            }
             lo_prev = lo;
             in = nx;
         }
     }
+    if (DETECT) return detect_finish(p, det, lds, dt, rw.Tr, tb);
     // P = alpha[2L] + alpha[2L - 1] of the last row, where they lie in its window
     if (lane == 0) lds.misc[18] = lds.misc[19] = 0;
     __syncthreads();
@@ -110,14 +233,30 @@ __global__ __launch_bounds__(64) void score_reg_kernel(ScoreParams p) {
     if (lane == 0) write_result(p, __int_as_float(lds.misc[18]), __int_as_float(lds.misc[19]), eacc);
 }
 
+// Both copies live in one kernel, so every launch, scores included, reserves the detecting copy's registers (63 / 73 /
+// 83 / 94 VGPRs at K = 2 / 4 / 6 / 8 against the score copy's 28 / 40 / 50 / 60).  8.6 KiB of LDS a one-wavefront
+// workgroup hold the kernel at 18 workgroups a CU, 4.5 wavefronts a SIMD, so five wavefronts a SIMD are all a score can
+// use: amdgpu_waves_per_eu(5) makes the compiler keep both copies within the 96 VGPRs that allow them (it spills, and
+// the resource report shows scratch, before a later change can take wavefronts from a score unnoticed).
+// The detecting copy's cells go through FCD_OPAQUE_VQ: the compiler forms no packed f32 operations (v_pk_add_f32,
+// v_pk_mul_f32) in that copy; the score copy keeps the 3 / 6 / 9 / 12 it had.
+template <int K>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) void score_reg_kernel(ScoreParams p, const DetectOut *det) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    if (det) score_reg_walk<K, true>(p, det, smem);
+    else score_reg_walk<K, false>(p, det, smem);
+}
+
 // ---- the LDS-resident window ----
-// One kernel, three walks, chosen once per block by LdsWalkParams::walk before any time loop (the instantiation ledger
+// One kernel, four walks, chosen once per block by LdsWalkParams::walk before any time loop (the instantiation ledger
 // admits no new kernel symbol, as PostParams::walk of ctc_posterior.hip):
 //   kLdsScore  fcd_ctc_score_*: the forward sum.
 //   kLdsStore  the same forward step; every live cell of row t also goes to the workspace by slot (s mod cap, as in LDS),
 //              scaled by 2^-kAlphaDown (exact), and the row's exponent word behind the T * cap cells, as post_fwd_kernel
 //              stores the register window's rows.  logp is kLdsScore's bit for bit.
 //   kLdsOcc    fcd_ctc_occupancy_* under fcd_set_ctc_occupancy_wide: rows T_r - 1 .. 0 (lds_occ_walk below).
+//   kLdsDetect fcd_ctc_detect_* of motifs beyond 254 labels: the forward step free-ended (the detecting walk above: state 0's
+//              slot is alpha[0] of the buffer a row writes, v_t is read back from that buffer behind the row's barrier).
 struct LdsWalkParams {
     ScoreParams s;
     int walk;
@@ -128,24 +267,35 @@ struct LdsWalkParams {
     int64_t occ_stride_row, occ_stride_t;
     float occ_scale;
     int occ_accumulate;
+    const DetectOut *detect;  // (kLdsDetect) null in every other walk
 };
-constexpr int kLdsScore = 0, kLdsStore = 1, kLdsOcc = 2;
+constexpr int kLdsScore = 0, kLdsStore = 1, kLdsOcc = 2, kLdsDetect = 3;
 constexpr int kWideCells = 10;  // cells per work-item and step of kLdsOcc: 20 would take the kernel from 77 to 117 VGPRs and
                                 // ctc_score's walk from 6 to 4 wavefronts per SIMD; at 10 it stays at 6
 constexpr int kWideLabels = 9;         // the blank and the 8 labels
 constexpr int kRedWords = 16 * kWideLabels;  // kLdsOcc: a word per wavefront and label behind the two alpha buffers
 constexpr int kTargetBack = 60;        // b: row maximum in [2^59, 2^60), as ctc_posterior.hip's kTargetB
 
-template <bool STORE>
+template <bool STORE, bool DETECT = false>
 __device__ __forceinline__ void lds_forward(const LdsWalkParams &q, unsigned char *smem) {
+    // (the detecting copy at the occupancy walks' cells per work-item: at 20 its bookkeeping takes the kernel past 80 VGPRs)
+    constexpr int kCells = DETECT ? kWideCells : kLdsCells;
     const ScoreParams &p = q.s;
     const Lds lds = carve(smem, p.lab_cap);
     Row rw;
-    if (!prologue(p, lds, &rw)) return;
+    int tb = 0;  // (detecting: the first row of the range)
+    if (DETECT) {
+        if (!prologue(p, lds, &rw) || !row_range(p, q.detect->row_begin, q.detect->row_end, &rw, &tb)) return no_detect(p, q.detect);
+    } else {
+        if (!prologue(p, lds, &rw)) return;
+    }
     const int tid = threadIdx.x, bd = blockDim.x, cap = p.cap, nw = bd >> 6;
     for (int s = tid; s < 2 * cap; s += bd) lds.alpha[s] = 0.0f;
     __syncthreads();
     if (tid == 0) lds.alpha[0] = 1.0f;  // "row -1": all mass on state 0
+    if (DETECT && tid == 0) lds.misc[kBadPost] = 0;
+    Detect dt{0.0, 0.0f, 0, -1, 0.0f, 0, 0.0f, 0};
+    const int y_first = DETECT ? lds.lab[0] & 0xFF : 0, y_last = DETECT ? lds.lab[rw.L - 1] & 0xFF : 0;
     int64_t eacc = 0;
     int lo_prev = 0, hi_prev = 0, base = 0, which = 0;  // base: the multiple of cap at or below the window's start
     // alpha_{t-1}[n] as the previous row left it: 0 outside that row's window (state n lives at n mod cap)
@@ -163,19 +313,26 @@ __device__ __forceinline__ void lds_forward(const LdsWalkParams &q, unsigned cha
     }
     for (int t0 = 0; t0 < rw.Tr; t0 += rw.rows_per_tile) {
         const int rc = min(rw.rows_per_tile, rw.Tr - t0);
-        fill_tile(p, lds, rw, t0, rc);
+        if (DETECT) fill_tile_checked(p, lds, rw, t0, rc);
+        else fill_tile(p, lds, rw, t0, rc);
         for (int i = 0; i < rc; ++i) {
             int lo, hi;
-            window(p, lds, rw, t0 + i, i, &lo, &hi);
+            window<DETECT>(p, lds, rw, t0 + i, i, &lo, &hi);
+            if (DETECT) FCD_OPAQUE_S(lo);  // (a constant 1: kept from hoisting every cell's label and addresses out of the time loop)
             const float *prev = lds.alpha + which * cap;
             float *next = lds.alpha + (which ^ 1) * cap;
             const float pm0 = lds.pm[i * rw.N];
             const int pe0 = lds.pe[i * rw.N];
-            float u[kLdsCells];
-            int ex[kLdsCells];
+            float g = 1.0f, h = 1.0f;  // (detecting) the entry weight of the NEXT row, the exit weight of the row BEFORE
+            if (DETECT && p.collapse) {
+                g = one_minus(lds, i * rw.N + y_first);
+                h = one_minus(lds, i * rw.N + y_last);
+            }
+            float u[kCells];
+            int ex[kCells];
             int emax = kNoExp;
 #pragma unroll
-            for (int c = 0; c < kLdsCells; ++c) {
+            for (int c = 0; c < kCells; ++c) {
                 const int s = lo + tid + c * bd;
                 u[c] = 0.0f;
                 ex[c] = 0;
@@ -195,6 +352,7 @@ __device__ __forceinline__ void lds_forward(const LdsWalkParams &q, unsigned cha
                     emax = max(emax, e != kNoExp ? e + ex[c] : kNoExp);
                 }
             }
+            if (DETECT) emax = max(emax, 1 - (int)eacc);  // state 0's 1: 2^-eacc in the units the row was computed in
             emax = wave_imax(emax);
             if ((tid & 63) == 0) lds.misc[tid >> 6] = emax;
             __syncthreads();  // every read of `prev` is done, the waves' maxima are in place
@@ -205,7 +363,7 @@ __device__ __forceinline__ void lds_forward(const LdsWalkParams &q, unsigned cha
             float *row = nullptr;
             if constexpr (STORE) row = am + (int64_t)(t0 + i) * cap;
 #pragma unroll
-            for (int c = 0; c < kLdsCells; ++c) {
+            for (int c = 0; c < kCells; ++c) {
                 const int s = lo + tid + c * bd;
                 if (s <= hi) {
                     int idx = s - base;
@@ -218,12 +376,20 @@ __device__ __forceinline__ void lds_forward(const LdsWalkParams &q, unsigned cha
             if constexpr (STORE) {
                 if (tid == 0) ae[t0 + i] = (int)(eacc + kAlphaDown);
             }
+            if (DETECT && tid == 0) next[0] = entry_cell(g, eacc);  // state 0 (below the window, base stays 0: no cell), after the rescale
             lo_prev = lo;
             hi_prev = hi;
             which ^= 1;
             __syncthreads();
+            if (DETECT) {  // (the next step writes the other buffer: `next` stands until the barrier inside it)
+                lo_prev = 0;  // state 0 is read like a cell
+                const float mine = 2 * rw.L - 1 <= hi ? next[2 * rw.L - 1] : 0.0f;
+                const float v = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(mine)));
+                detect_row(q.detect, dt, v, eacc, h, t0 + i, rw.Tr, tb);
+            }
         }
     }
+    if (DETECT) return detect_finish(p, q.detect, lds, dt, rw.Tr, tb);
     if (tid == 0) {
         const float *last = lds.alpha + which * cap;
         write_result(p, rd(last, 2 * rw.L), rd(last, 2 * rw.L - 1), eacc);
@@ -389,6 +555,7 @@ __global__ __launch_bounds__(1024) void score_lds_kernel(LdsWalkParams q) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     if (q.walk == kLdsOcc) return lds_occ_walk(q, smem);
     if (q.walk == kLdsStore) return lds_forward<true>(q, smem);
+    if (q.walk == kLdsDetect) return lds_forward<false, true>(q, smem);
     lds_forward<false>(q, smem);
 }
 
@@ -405,6 +572,12 @@ bool ctc_score_supported(int64_t T, int64_t stride, int64_t band) {
     const int64_t lab_cap = std::max<int64_t>(std::min(T, stride), 1);
     const int64_t cap = states + 2 <= 512 ? 0 : states;  // (register-resident windows keep no alpha in LDS)
     return lab_cap <= 80 * 1024 && cap <= 1024 * kLdsCells && lds_bytes((int)lab_cap, (int)cap) <= 160 * 1024;
+}
+
+// fcd_ctc_detect_*'s LDS walk holds kWideCells cells per work-item
+bool ctc_detect_supported(int64_t T, int64_t stride) {
+    const int64_t states = ctc_score_window_states(T, stride, 0);
+    return states + 2 <= 512 || states <= 1024 * kWideCells;
 }
 
 namespace {
@@ -473,6 +646,7 @@ hipError_t launch_ctc_occupancy_wide(const BatchDesc &in, const ScoreDesc &y, in
     q.occ_stride_t = out.stride_t;
     q.occ_scale = out.scale;
     q.occ_accumulate = out.accumulate;
+    q.detect = nullptr;
     const size_t lds = wide_lds_bytes(q.s.lab_cap, q.s.cap);
     q.walk = kLdsStore;
     hipError_t e = launch_lds_walk(q, rows, lds, stream);
@@ -482,11 +656,12 @@ hipError_t launch_ctc_occupancy_wide(const BatchDesc &in, const ScoreDesc &y, in
 }
 
 hipError_t launch_ctc_score(const BatchDesc &in, const ScoreDesc &y, int collapse, int64_t band, double *logp,
-                            hipStream_t stream) {
+                            hipStream_t stream, const DetectOut *detect) {
     const int64_t rows = in.n_reads * y.n_hyp;
     if (rows <= 0) return hipSuccess;
     LdsWalkParams q;
-    q.walk = kLdsScore;
+    q.walk = detect ? kLdsDetect : kLdsScore;  // (detecting: band is 0, the caller's check)
+    q.detect = detect;
     q.alpha = q.occ = nullptr;
     q.alpha_words = q.occ_stride_row = q.occ_stride_t = 0;
     q.occ_scale = 0.0f;
@@ -503,10 +678,10 @@ hipError_t launch_ctc_score(const BatchDesc &in, const ScoreDesc &y, int collaps
     if (states + 2 <= 512) {  // the slots must exceed the widest window by two states (the s-1 / s-2 reads below it)
         p.cap = 0;
         const size_t lds = lds_bytes(p.lab_cap, 0);
-        if (states + 2 <= 128) hipLaunchKernelGGL(score_reg_kernel<2>, grid, dim3(64), lds, stream, p);
-        else if (states + 2 <= 256) hipLaunchKernelGGL(score_reg_kernel<4>, grid, dim3(64), lds, stream, p);
-        else if (states + 2 <= 384) hipLaunchKernelGGL(score_reg_kernel<6>, grid, dim3(64), lds, stream, p);
-        else hipLaunchKernelGGL(score_reg_kernel<8>, grid, dim3(64), lds, stream, p);
+        if (states + 2 <= 128) hipLaunchKernelGGL(score_reg_kernel<2>, grid, dim3(64), lds, stream, p, detect);
+        else if (states + 2 <= 256) hipLaunchKernelGGL(score_reg_kernel<4>, grid, dim3(64), lds, stream, p, detect);
+        else if (states + 2 <= 384) hipLaunchKernelGGL(score_reg_kernel<6>, grid, dim3(64), lds, stream, p, detect);
+        else hipLaunchKernelGGL(score_reg_kernel<8>, grid, dim3(64), lds, stream, p, detect);
     } else {
         p.cap = (int)states;
         return launch_lds_walk(q, rows, lds_bytes(p.lab_cap, p.cap), stream);

@@ -275,8 +275,19 @@ struct ScoreDesc {
 // the most states a live window of such a call can hold, and whether the kernels hold it (LDS: 160 KiB per workgroup)
 int64_t ctc_score_window_states(int64_t T, int64_t stride, int64_t band);
 bool ctc_score_supported(int64_t T, int64_t stride, int64_t band);
+bool ctc_detect_supported(int64_t T, int64_t stride);  // (within ctc_score_supported: the LDS walk's 10 cells per work-item)
+// detect non-null (band 0): motif occurrence posteriors, the same kernels free-ended with a sum (fcd_detect in
+// include/fcd.h) -- the expected count, the best end row, the per-row track and the range of rows of every read of the
+// launch, a block in DEVICE memory (stream-ordered before the launch); logp receives ln c_end.
+struct DetectOut {
+    double *count;
+    uint32_t *end;
+    float *track;  // nullable
+    int64_t track_stride;
+    const uint32_t *row_begin, *row_end;  // nullable
+};
 hipError_t launch_ctc_score(const BatchDesc &in, const ScoreDesc &y, int collapse, int64_t band, double *logp,
-                            hipStream_t stream);
+                            hipStream_t stream, const DetectOut *detect = nullptr);
 // CTC forced alignment of given labellings (ctc_align.hip; fcd_alignment in include/fcd.h): what ctc_score supports.
 // bp: ctc_align_row_bytes() of device memory per labelling of the launch (the back-pointers); logp must not be null.
 struct AlignOut {
@@ -510,6 +521,8 @@ struct fcd_handle {
     std::vector<char> tail_host;  // lattice_grouped: the host copy of a call's per-group parameter blocks, kept until the next
     bool spot_on = false;     // fcd_set_ctc_spot: fcd_ctc_align_dev spots, with ...
     fcd_spot spot{};          // ... these outputs and ranges next to its own fcd_alignment
+    bool detect_on = false;   // fcd_set_ctc_detect: fcd_ctc_score_dev detects, with ...
+    fcd_detect detect{};      // ... these outputs and ranges next to its own logp
     int64_t align_ws_cap = 0; // fcd_debug_set_align_workspace_cap: back-pointer bytes one launch of fcd_ctc_align_* may take, 0 = default
     bool is_lane = false;
     uint32_t *duplex_prof = nullptr;  // fcd_debug_set_duplex_profile

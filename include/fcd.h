@@ -457,7 +457,7 @@ int fcd_ctc_align_host(fcd_handle *h, const fcd_batch *in, const fcd_labellings 
  * Shapes, limits (the kernel is chosen from stride as fcd_ctc_align_* does at band 0: motifs beyond 254 labels walk in
  * LDS), in->S, in->lengths and the workspace are fcd_ctc_align_*'s.  FCD_E_INVALID before anything is
  * enqueued: band != 0, end null, track given with track_stride < in->T, and fcd_ctc_align_*'s cases.
- * Out of scope: the sum over alignments (a soft hit score), the k best hits on the device, CRF models, bands. */
+ * Out of scope: the k best hits on the device, CRF models, bands.  (The sum over alignments: fcd_ctc_detect_* below.) */
 typedef struct fcd_spot {
     uint32_t *start;            /* [n_reads * n_hyp * stride] */
     uint32_t *count;            /* [n_reads * n_hyp * stride] */
@@ -480,6 +480,61 @@ int fcd_ctc_spot_host(fcd_handle *h, const fcd_batch *in, const fcd_labellings *
  * setting and clearing it the handle must not be shared with another thread (its fcd_ctc_align_dev would spot into this
  * caller's end and track); the Python layer sets, calls and clears on the calling thread's own handle. */
 int fcd_set_ctc_spot(fcd_handle *h, const fcd_spot *spot);
+
+/* ---- CTC motif occurrence posteriors: soft spotting, expected counts (csrc/ctc_score.hip, the score kernels free-ended) ----
+ * NOT a reference function.  fcd_ctc_spot_* finds the best single alignment of a motif; this call sums over them, with
+ * entry and exit weights that make the sum a probability on a scale shared by motifs of every length.  For the motif y of
+ * L labels (labelling i of read r, row = r * n_hyp + i; `path` unused) and the read's range of rows [b, e) (row_begin /
+ * row_end as fcd_spot defines them), it is fcd_ctc_score_*'s forward recurrence at band 0 -- extended sequence z, state
+ * 2k + 1 is label y_k, even states are blanks, a cell = (a[s] + a[s-1] + a[s-2]) * p in f32, transitions under
+ * collapse_repeats, power-of-two rescaling only -- over the rows t in [b, e) and the states 1 .. 2L - 1, with:
+ *   entry  state 0 is no cell.  As the s-1 candidate of state 1 at row t it holds g_t: g_b = 1; for t > b,
+ *          g_t = max(0, 1 - p[t-1][y_0]) under collapse_repeats and 1 without.  A fresh start is counted only where the
+ *          motif's first run really begins.
+ *   exit   state 2L is not walked.  v_t = a_t[2L - 1], c_t = v_t * h_t with h_t = max(0, 1 - p[t+1][y_{L-1}]) under
+ *          collapse_repeats for t < e - 1; h_t = 1 at t = e - 1 and without collapse_repeats.  An occurrence is counted
+ *          once, at the row where its last run ends.
+ * Meaning.  The rows are independent under CTC.  Where every row of the range sums to 1, c_t is the probability that an
+ * occurrence of the motif -- a run of consecutive labels of the collapsed labelling of the range -- ends exactly at row t;
+ * the events for different starts and ends are disjoint, so sum_t c_t is the EXPECTED NUMBER OF OCCURRENCES of the motif in
+ * the range's labelling (overlapping ones included), an upper bound of P(at least one).  For rows that do not sum to 1 the
+ * arithmetic above is the definition.  Because a true 1 stands next to the cells in f32, a cell below 2^-245 -- as a
+ * probability, not relative to its row -- may count as 0.
+ * Per labelling row:
+ *   count[row]          sum_t c_t, float64, accumulated in row order: the same bits on every call.  Not null.
+ *   end  [row]          argmax_t c_t, ties to the earliest row; 0xFFFFFFFF where every c_t is 0.  Not null.
+ *   logp [row]          ln c_end, ln(m) + E ln 2 in float64.  Nullable.
+ *   track[row * track_stride + t]   ln c_t in f32 for every t in [b, e), -inf where c_t = 0: logf(m) + E * ln 2 in f32
+ *                       (one multiply-add).  Rows outside the range are not written.  Nullable; track_stride >= in->T.
+ * Rows without a value, tested in fcd_ctc_spot_*'s order and with its logp: i >= n_valid[r], len > stride, a label
+ * outside 1 .. N-1: logp = count = NaN; L > e - b (an empty range included): logp = -inf, count = 0; a NaN, infinite or
+ * negative posterior in the rows of the RANGE (only those are looked at): logp = count = NaN, the track's values undefined;
+ * c_t = 0 everywhere: logp = -inf, count = 0.  L = 0: logp = 0 (fcd_ctc_spot_*'s), count = 0.  In all of them
+ * end = 0xFFFFFFFF, and only the last two kinds of row (those that walk) write the track.
+ * Shapes, in->S, in->lengths are fcd_ctc_score_*'s; the kernel is chosen from stride as fcd_ctc_score_* does at band 0:
+ * motifs beyond 254 labels walk in LDS, at 10 cells per work-item, so FCD_E_UNSUPPORTED beyond stride (or T) 5119 -- half of what the score itself takes.  The
+ * workspace: 256 bytes of parameters, and logp where it is null.  FCD_E_INVALID before anything is enqueued: band != 0,
+ * count or end null, track given with track_stride < in->T, and fcd_ctc_score_*'s cases.
+ * Out of scope: CRF models, bands, the k best ends on the device, the start-row distribution of an occurrence, P(at
+ * least one occurrence), several short motifs packed into one wavefront. */
+typedef struct fcd_detect {
+    double   *count;            /* [n_reads * n_hyp] */
+    uint32_t *end;              /* [n_reads * n_hyp] */
+    double   *logp;             /* [n_reads * n_hyp], nullable */
+    float    *track;            /* [n_reads * n_hyp * track_stride], nullable */
+    int64_t   track_stride;
+    const uint32_t *row_begin;  /* [n_reads], nullable */
+    const uint32_t *row_end;    /* [n_reads], nullable */
+} fcd_detect;
+int fcd_ctc_detect_host(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int collapse_repeats, int64_t band,
+                        const fcd_detect *out);
+/* Device arrays: a handle switch in front of the score's own device entry point, as fcd_set_ctc_spot is in front of the
+ * alignment's.  fcd_set_ctc_detect(h, detect) copies *detect into the handle; while it is set, the score's device call
+ * on that handle IS the detecting call: band must be 0, ln c_end is written through the call's own logp (detect->logp is
+ * ignored), count, end, track and the range come from *detect.  detect = NULL turns it off.  fcd_ctc_score_host is not
+ * affected.  The threading caveat is fcd_set_ctc_spot's: between setting and clearing the switch the handle must not be
+ * shared with another thread; the Python layer sets, calls and clears on the calling thread's own handle. */
+int fcd_set_ctc_detect(fcd_handle *h, const fcd_detect *detect);
 
 /* ---- CTC forward-backward substitution posteriors of given labellings (csrc/ctc_posterior.hip) ----
  * NOT a reference function.  For a labelling y of L labels (hypothesis i of read r, row = r * n_hyp + i), label position
