@@ -53,7 +53,7 @@ SYMBOLS = [
     "fcd_beam_session_bytes", "fcd_beam_session_destroy",
     "fcd_ctc_score_dev", "fcd_ctc_score_host",
     "fcd_ctc_align_dev", "fcd_ctc_align_host", "fcd_debug_set_align_workspace_cap", "fcd_debug_workspace_bytes",
-    "fcd_ctc_spot_host", "fcd_set_ctc_spot", "fcd_ctc_detect_host", "fcd_set_ctc_detect",
+    "fcd_ctc_spot_host", "fcd_set_ctc_spot", "fcd_ctc_detect_host", "fcd_set_ctc_detect", "fcd_set_ctc_detect_packed",
     "fcd_ctc_posterior_dev", "fcd_ctc_posterior_host",
     "fcd_ctc_edits_dev", "fcd_ctc_edits_host",
     "fcd_crf_score_dev", "fcd_crf_score_host", "fcd_crf_align_dev", "fcd_crf_align_host",
@@ -311,6 +311,7 @@ def bind(lib):
     lib.fcd_set_ctc_spot.argtypes = [P, C.POINTER(Spot)]  # (device arrays: fcd_ctc_align_dev under this switch)
     lib.fcd_ctc_detect_host.argtypes = [P, BP, LP, i32, i64, C.POINTER(Detect)]  # (CTC only)
     lib.fcd_set_ctc_detect.argtypes = [P, C.POINTER(Detect)]  # (device arrays: fcd_ctc_score_dev under this switch)
+    lib.fcd_set_ctc_detect_packed.argtypes = [P, i32]
     lib.fcd_debug_set_align_workspace_cap.argtypes = [P, i64]
     lib.fcd_debug_workspace_bytes.argtypes = [P]
     lib.fcd_debug_workspace_bytes.restype = i64
@@ -399,6 +400,10 @@ class Handle:
 
     def set_workspace_limit(self, nbytes):
         self.check(self.lib.fcd_set_workspace_limit(self.ptr, int(nbytes)))
+
+    def set_ctc_detect_packed(self, on):
+        """fcd_ctc_detect_* on this handle takes motifs shared by all reads, one pair per lane (include/fcd.h: fcd_set_ctc_detect_packed)."""
+        self.check(self.lib.fcd_set_ctc_detect_packed(self.ptr, int(bool(on))))
 
     def set_ctc_occupancy_wide(self, on):
         """fcd_ctc_occupancy_* on this handle takes windows beyond 510 states (include/fcd.h: fcd_set_ctc_occupancy_wide)."""

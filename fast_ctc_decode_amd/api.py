@@ -1784,10 +1784,12 @@ _Kept = collections.namedtuple("_Kept", "x labels label_lengths paths n_valid le
 
 
 def _lattice_inputs(network_outputs, labels, label_lengths, lengths, paths, band, n_valid, input_dtype, handle,
-                    init_states=None):
+                    init_states=None, shared=False):
     """The argument handling ctc_score_batch_raw, ctc_align_batch_raw and their CRF counterparts share.  -> (handle,
     nat.Batch, nat.Labellings, (B, n_hyp, stride), device or None for numpy input, the arrays the two structs point into);
-    init_states given (the CRF calls: (B, T, S, N) posteriors): the init rows (B, n_init) are the last of those arrays."""
+    init_states given (the CRF calls: (B, T, S, N) posteriors): the init rows (B, n_init) are the last of those arrays.
+    shared (ctc_detect_batch_raw's packed mode): labels (n_hyp, stride) and label_lengths (n_hyp,) describe labellings
+    every read shares."""
     crf = init_states is not None
     nd = 4 if crf else 3
     dev_x = _device_tensor(network_outputs)
@@ -1806,9 +1808,9 @@ def _lattice_inputs(network_outputs, labels, label_lengths, lengths, paths, band
             a = torch.as_tensor(a, device=dev)
             return (a if a.dtype == dtype else a.to(dtype)).contiguous()
         lab = as_dev(labels, torch.uint8)
-        n_hyp, stride = _score_shapes(tuple(lab.shape), B)
+        n_hyp, stride = tuple(lab.shape) if shared else _score_shapes(tuple(lab.shape), B)
         ylen = as_dev(label_lengths, torch.int32)
-        if ylen.numel() != B * n_hyp:
+        if ylen.numel() != (1 if shared else B) * n_hyp:
             raise ValueError("label_lengths must have one entry per labelling")
         pth = as_dev(paths, torch.int32) if band else None
         if pth is not None and tuple(pth.shape) != tuple(lab.shape):
@@ -1838,9 +1840,9 @@ def _lattice_inputs(network_outputs, labels, label_lengths, lengths, paths, band
     x = _stack_host(network_outputs, nd)
     B, T, N = x.shape[0], x.shape[1], x.shape[-1]
     lab = np.ascontiguousarray(np.asarray(labels), np.uint8)
-    n_hyp, stride = _score_shapes(lab.shape, B)
+    n_hyp, stride = lab.shape if shared else _score_shapes(lab.shape, B)
     ylen = np.ascontiguousarray(np.asarray(label_lengths), np.uint32)
-    if ylen.size != B * n_hyp:
+    if ylen.size != (1 if shared else B) * n_hyp:
         raise ValueError("label_lengths must have one entry per labelling")
     pth = np.ascontiguousarray(np.asarray(paths), np.uint32) if band else None
     if pth is not None and pth.shape != lab.shape:
@@ -2040,17 +2042,18 @@ def _wide_switch(h, model, wide):
 
 
 def _lattice_call(model, kind, network_outputs, labels, label_lengths, lengths, paths, band, n_valid, input_dtype, handle,
-                  init_states=None, collapse_repeats=True, wide=False, **out_args):
+                  init_states=None, collapse_repeats=True, wide=False, packed=False, **out_args):
     """The one body of the labelling-lattice calls: fcd_<model>_<kind>_dev for device tensors, _host for numpy, with
     model "ctc" (network_outputs (B,T,N), collapse_repeats) or "crf" ((B,T,S,N) and init_states), kind one of
     _LATTICE_BUILDERS ("spot", "detect": CTC only); out_args: the occupancy calls' out, scale, accumulate and
-    time_major_out, the spotting and detecting calls' rows and track.  -> what the call returns."""
+    time_major_out, the spotting and detecting calls' rows and track.  packed ("detect"): labels and label_lengths are
+    motifs shared by all reads, under the handle's fcd_set_ctc_detect_packed.  -> what the call returns."""
     band = _check_band(band, paths)
     if kind == "occupancy":
         _check_occupancy_out(**out_args)
         out_args["has_S"] = model == "crf"
     h, b, y, shape, dev, keep = _lattice_inputs(network_outputs, labels, label_lengths, lengths, paths, band, n_valid,
-                                                input_dtype, handle, init_states)
+                                                input_dtype, handle, init_states, shared=packed)
     xp = _Arrays(dev)
     if kind in ("spot", "detect"):
         out_args["lengths"] = keep.lengths  # (rows counts from every read's own length)
@@ -2071,9 +2074,13 @@ def _lattice_call(model, kind, network_outputs, labels, label_lengths, lengths, 
         if detect_dev:
             h.check(h.lib.fcd_set_ctc_detect(h.ptr, out))
             args = args[:-1] + (C.c_void_p(xp.ptr(result.logp)),)  # (the score's own logp array)
+        if packed:
+            h.set_ctc_detect_packed(True)
         try:
             h.check(fn(h.ptr, *args))
         finally:
+            if packed:
+                h.set_ctc_detect_packed(False)
             if spot_dev:
                 h.lib.fcd_set_ctc_spot(h.ptr, None)
             if detect_dev:
@@ -2276,14 +2283,18 @@ class DetectResult:
 
 
 def ctc_detect_batch_raw(network_outputs, motifs, motif_lengths, collapse_repeats=True, lengths=None, rows=None,
-                         track=False, input_dtype=None, handle=None):
+                         track=False, input_dtype=None, handle=None, packed=False):
     """CTC motif occurrence posteriors: how probable it is that each of M known sequences occurs in every read -- the sum
     over ALL alignments of the motif to any run of consecutive rows, weighted so that every occurrence is counted once
     (include/fcd.h, fcd_ctc_detect_*).  -> DetectResult, arrays (B, M[, T]).
 
     motifs, motif_lengths, rows and track as ctc_spot_batch_raw takes them.  Demultiplexing: count.argmax(1) is the
     barcode of every read, count.max(1) what to threshold.  Device tensors in: torch tensors on the same device,
-    enqueued on torch's current stream, not synchronised.  numpy in: numpy out."""
+    enqueued on torch's current stream, not synchronised.  numpy in: numpy out.
+
+    packed=True: the walk for many short motifs (include/fcd.h, fcd_set_ctc_detect_packed) -- one (read, motif) pair per
+    lane, every read's rows staged once for all its motifs, the motifs passed once and not per read.  The same values
+    within the same bound; motifs of at most 24 labels (RuntimeError beyond), no track (ValueError)."""
     m = np.asarray(_to_host(motifs), np.uint8)
     if m.ndim != 2:
         raise ValueError("motifs must have shape (n_motifs, stride)")
@@ -2293,6 +2304,12 @@ def ctc_detect_batch_raw(network_outputs, motifs, motif_lengths, collapse_repeat
     n = np.asarray(_to_host(motif_lengths), np.uint32).reshape(-1)
     if n.size != m.shape[0]:
         raise ValueError("motif_lengths must have one entry per motif")
+    if packed:
+        if track:
+            raise ValueError("packed=True writes no track")
+        m = m[:, :max(int(n.max(initial=0)), 1)] if m.shape[1] else np.zeros((m.shape[0], 1), np.uint8)  # (the stride the longest motif needs)
+        return _lattice_call("ctc", "detect", network_outputs, m, n, lengths, None, 0, None, input_dtype, handle,
+                             collapse_repeats=collapse_repeats, packed=True, rows=rows, track=False)
     return _lattice_call("ctc", "detect", network_outputs, np.tile(m[None], (B, 1, 1)), np.tile(n[None], (B, 1)), lengths,
                          None, 0, None, input_dtype, handle, collapse_repeats=collapse_repeats, rows=rows, track=bool(track))
 

@@ -1946,7 +1946,11 @@ struct LatticeCall {
     bool crf_wide = false;  // (CRF score, occupancy) fcd_set_crf_lattice_wide: windows beyond 512 states walk in LDS
     const fcd_spot *spot = nullptr;  // (CTC align) fcd_ctc_spot_*: `out` holds its first four pointers
     const fcd_detect *detect = nullptr;  // (CTC score) fcd_ctc_detect_*: `logp` is its logp
+    bool packed = false;  // (detect) fcd_set_ctc_detect_packed: y holds n_hyp motifs shared by all reads
 };
+
+// the labellings y->labels / y->len describe: one per (read, hypothesis), or (packed) the n_hyp shared motifs
+size_t labelling_rows(const LatticeCall &c) { return c.packed ? (size_t)c.y->n_hyp : (size_t)c.in->n_reads * (size_t)c.y->n_hyp; }
 
 // the call is one of those the CRF switch covers AND its window is beyond the registers: every other call is what it is
 // with the switch off (in and y checked by then)
@@ -1992,6 +1996,14 @@ int lattice_check(fcd_handle *h, const LatticeCall &c) {
     if (c.band < 0) return fail(h, FCD_E_INVALID, "band must be >= 0");
     if (c.band > 0 && !y->path) return fail(h, FCD_E_INVALID, "a band needs the labellings' path");
     if (y->stride < 0) return fail(h, FCD_E_INVALID, "negative stride");
+    if (c.packed) {
+        if (c.detect->track) return fail(h, FCD_E_INVALID, "ctc_detect_packed: the packed walk writes no track");
+        if (y->n_valid) return fail(h, FCD_E_INVALID, "ctc_detect_packed: the motifs are shared by all reads: n_valid must be null");
+        if (y->stride > ctc_detect_packed_labels())
+            return fail(h, FCD_E_UNSUPPORTED, ("ctc_detect_packed: motifs beyond " + std::to_string(ctc_detect_packed_labels()) +
+                                               " labels do not fit a lane's registers: use a smaller stride or the unpacked call").c_str());
+        if (in->N > 1984) return fail(h, FCD_E_UNSUPPORTED, "ctc_detect_packed: a row beyond 1984 labels does not fit a slot of the tile");
+    }
     if (in->n_reads > 0 && (!y->labels || !y->len ||
                             !(c.occupancy ? (const void *)c.occ->occ : c.edit ? (const void *)c.edits->deletion : c.posterior ? (const void *)c.post->post
                               : c.align ? (const void *)c.out->start : c.detect ? (const void *)c.detect->count : (const void *)c.logp)))
@@ -2091,8 +2103,8 @@ int lattice_check(fcd_handle *h, const LatticeCall &c) {
 }
 
 void add_labellings(CallScope &sc, const LatticeCall &c, size_t n_rows) {
-    sc.add(c.y->labels, n_rows * (size_t)c.y->stride);
-    sc.add(c.y->len, n_rows * 4);
+    sc.add(c.y->labels, labelling_rows(c) * (size_t)c.y->stride);
+    sc.add(c.y->len, labelling_rows(c) * 4);
     sc.add(c.y->n_valid, (size_t)c.in->n_reads * 4);
     sc.add(c.y->path, n_rows * (size_t)c.y->stride * 4);
 }
@@ -2189,6 +2201,7 @@ int lattice_detect(fcd_handle *h, const LatticeCall &c) {
             sc.add(s->row_end, (size_t)in->n_reads * 4);
         },
         [&](const BatchDesc &d, const ScoreDesc &yd, int64_t, int64_t, double *logp, unsigned char *, hipStream_t stream) {
+            if (c.packed) return launch_ctc_detect_packed(d, yd, c.collapse, logp, stream, reinterpret_cast<const DetectOut *>(block));
             return launch_ctc_score(d, yd, c.collapse, 0, logp, stream, reinterpret_cast<const DetectOut *>(block));
         },
         256,
@@ -2196,6 +2209,13 @@ int lattice_detect(fcd_handle *h, const LatticeCall &c) {
             *static_cast<DetectOut *>(host) = DetectOut{s->count + row0, s->end + row0, s->track ? s->track + row0 * s->track_stride : nullptr,
                                                         s->track_stride, s->row_begin ? s->row_begin + r0 : nullptr,
                                                         s->row_end ? s->row_end + r0 : nullptr};
+            if (c.packed) {  // (one group: the motifs as the caller's y describes them, no copy per read)
+                DetectOut *o = static_cast<DetectOut *>(host);
+                o->pack_labels = y->labels;
+                o->pack_len = y->len;
+                o->pack_m = (int)y->n_hyp;
+                o->pack_reads = ctc_detect_packed_reads(y->n_hyp, in->N);
+            }
         },
         &block);
 }
@@ -2334,8 +2354,8 @@ int lattice_host(fcd_handle *h, const LatticeCall &c) {
     const int i_post = st.in(in->post, (size_t)span_elems(in, c.crf) * (in->dtype == FCD_DTYPE_F32 ? 4 : 2));
     const int i_init = st.in(c.crf ? c.init : nullptr, (size_t)((in->n_reads - 1) * c.init_stride + c.n_init) * 4);
     const int i_len = st.in(in->lengths, B * 8);
-    const int i_lab = st.in(y->labels, cells);
-    const int i_ylen = st.in(y->len, n_rows * 4);
+    const int i_lab = st.in(y->labels, labelling_rows(c) * (size_t)y->stride);
+    const int i_ylen = st.in(y->len, labelling_rows(c) * 4);
     const int i_nv = st.in(y->n_valid, B * 4);
     const int i_path = st.in(c.band > 0 ? y->path : nullptr, cells * 4);
     // (alignment entries the kernel does not write -- k >= len -- come back as 0)
@@ -2422,6 +2442,7 @@ int detect_call(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int
     if (!out) return fail(h, FCD_E_INVALID, "ctc_detect: null output");
     LatticeCall c{false, false, in, y, band, collapse_repeats != 0, nullptr, 0, 0, out->logp, nullptr};
     c.detect = out;
+    c.packed = h->detect_packed;
     return run(h, c);
 }
 }  // namespace
@@ -2431,6 +2452,13 @@ int fcd_set_ctc_detect(fcd_handle *h, const fcd_detect *detect) {
     std::lock_guard<std::recursive_mutex> g(h->mu);
     h->detect_on = detect != nullptr;
     h->detect = detect ? *detect : fcd_detect{};
+    return FCD_OK;
+}
+
+int fcd_set_ctc_detect_packed(fcd_handle *h, int on) {
+    if (!h) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> g(h->mu);
+    h->detect_packed = on != 0;
     return FCD_OK;
 }
 

@@ -233,6 +233,266 @@ __device__ __forceinline__ void score_reg_walk(const ScoreParams &p, const Detec
     if (lane == 0) write_result(p, __int_as_float(lds.misc[18]), __int_as_float(lds.misc[19]), eacc);
 }
 
+// ---- the packed detecting walk: one (read, motif) pair per LANE (fcd_set_ctc_detect_packed, include/fcd.h) ----
+// M short motifs shared by all reads.  Lane q * Mp + m of a wavefront walks motif m of the wavefront's read slot q (Mp: M
+// rounded up to a power of two, R = 64 / Mp slots; beyond 32 motifs one read and a block of 64 motifs), every cell of its
+// lattice in a register of its own: a[0] is state 0's pinned g * 2^-E, a[s] state s <= 2L - 1, updated in place from the
+// highest state down -- no value crosses a lane in the row loop.  States above 2L - 1 hold garbage nothing reads: a state
+// only feeds the states above it, v_t is picked by a select on L, the maximum is masked.
+//   rows   relative: row i of every lane is row b_r + i of its own read's range.  The wavefront stages, per slot, the next
+//          rows of that slot's range as plain f32 (load_post: exact f16 / bf16, 64-bit offsets, any strides) at
+//          tile[q * S + i * N + j], S = 31 * 64 / R words: the N values of a row lie in N consecutive banks, the rows of
+//          the slots start 64 / R banks apart (-q * 64 / R mod 64; R = 64: 31 q mod 64, a permutation).  A NaN, infinite or
+//          negative value sets the SLOT's word: a bad read leaves the reads next to it alone.  A lane whose range is over
+//          sits out the rest under its predicate; the pending c of its last row is completed behind the loop with h = 1.
+//   scale  a cell is value * 2^-E with a per-lane integer E; state 0's 1 starts as 2^64 (E = -64), so a cell stays a normal
+//          f32 down to 2^-190 as a probability.  With posteriors <= 1 a row grows max(cells, 2^-E) at most threefold, so the
+//          lane looks at that maximum every kPackCheck = 32 rows only (3^32 < 2^51: below 2^116 from [2^64, 2^65)) and
+//          multiplies cells, pinned value and 2^-E by the power of two that puts it back: exact.  Where rows that do not
+//          sum to 1 outgrow f32, E carries them; once 2^-E leaves f32 (values beyond 2^213) a fresh start counts as 0.
+//   result detect_cell's arithmetic per lane: count a float64 sum in row order, the best c as (mantissa, exponent, row),
+//          a later row only if strictly greater, one ln at the end; each lane stores its own three values.
+// The cell arithmetic is the wave-wide walk's -- (a[s] + a[s-1] + a[s-2]) * p, one rounding each -- so its bound holds.
+constexpr int kPackLabels = 24;   // 47 cells: the K = 2 instantiation stays under its 96 VGPRs (the resource report)
+constexpr int kPackCheck = 32;    // rows between two looks at a lane's maximum
+constexpr int kPackUnit = 65;     // frexp exponent the maximum is put back to: [2^64, 2^65)
+constexpr int kPackTileWords = 31 * 64;  // of the 2048 words of pm / pe; the 64 behind them: the slots' bad-posterior words
+
+constexpr int kPackGroup = 4;     // labels whose posteriors are read from the tile at a time
+#ifdef FCD_HIPEMU  // (lockstep emulation, tests/hipemu: plain C++)
+#define FCD_PACK_FENCE(x, y) ((void)0)
+#else
+#define FCD_PACK_FENCE(x, y) asm("" : "+v"(x), "+v"(y))
+#endif
+
+struct PackBest {
+    double sum;
+    float bm;
+    int be, bt;
+};
+
+__device__ __forceinline__ void pack_cell(PackBest &r, float c, int e, int t) {
+    if (c > 0.0f && c - c == 0.0f) {
+        r.sum += ldexp((double)c, e);
+        int ex;
+        const float m = frexpf(c, &ex);
+        ex += e;
+        if (r.bt < 0 || ex > r.be || (ex == r.be && m > r.bm)) {
+            r.bm = m;
+            r.be = ex;
+            r.bt = t;
+        }
+    }
+}
+
+// the rows [b, b + rows) of `read` that its motifs are looked for in (row_range's clamping); rows = 0 beyond the batch
+__device__ __forceinline__ void pack_range(const ScoreParams &p, const DetectOut *det, int64_t read, int *b, int *rows) {
+    *b = *rows = 0;
+    if (read >= p.in.n_reads) return;
+    int64_t Tr = p.in.lengths ? p.in.lengths[read] : p.in.T;
+    Tr = Tr < 0 ? 0 : (Tr > p.in.T ? p.in.T : Tr);
+    const int lo = det->row_begin ? (int)min((int64_t)det->row_begin[read], Tr) : 0;
+    const int hi = det->row_end ? (int)min((int64_t)det->row_end[read], Tr) : (int)Tr;
+    *b = lo;
+    *rows = max(hi - lo, 0);
+}
+
+template <bool COLLAPSE>
+__device__ __forceinline__ void pack_walk(const ScoreParams &p, const DetectOut *det, unsigned char *smem) {
+    constexpr int NL = kPackLabels, NW = (NL + 3) / 4, GS = kPackGroup;
+    static_assert(NL % GS == 0 && NL <= 32, "whole groups; the select tree has five levels");
+    float *tile = reinterpret_cast<float *>(smem);
+    int *badw = reinterpret_cast<int *>(smem) + kPackTileWords;
+    int *slot_rows = reinterpret_cast<int *>(smem + kTileElems * 8);  // (krow's 64 words)
+    const int lane = threadIdx.x, N = p.in.N, M = det->pack_m, R = det->pack_reads;
+    const int G = 64 / R, S = 31 * G, rpt = min(kTileRows, S / N);  // lanes and words of a slot, rows of a tile
+    const int Mp = M > 32 ? 64 : G;                                 // (the host takes fewer slots where N wants longer rows)
+    const int nblk = (M + 63) >> 6;
+    const int64_t group = blockIdx.x / nblk;
+    {  // ---- the slot this lane stages (lane / G: its G lanes write the same value)
+        int b_s, rows_s;
+        pack_range(p, det, group * R + lane / G, &b_s, &rows_s);
+        slot_rows[lane / G] = rows_s;
+        badw[lane / G] = 0;
+    }
+    // ---- the pair this lane walks
+    const int q = lane / Mp, m = (int)(blockIdx.x - group * nblk) * 64 + (lane - q * Mp);
+    const int64_t read = group * R + q;
+    const bool mine = q < R && m < M && read < p.in.n_reads;
+    int b = 0, rows = 0, L = 0;
+    uint32_t w[NW], dmask = 0;
+#pragma unroll
+    for (int k = 0; k < NW; ++k) w[k] = 0;
+    double early = (double)NAN;
+    if (mine) {
+        pack_range(p, det, read, &b, &rows);
+        const uint32_t len = det->pack_len[m];
+        const uint8_t *lab = det->pack_labels + (int64_t)m * p.y.stride;
+        bool bad = (int64_t)len > p.y.stride || len > (uint32_t)NL;
+        L = bad ? 0 : (int)len;
+        int yp = 0;
+#pragma unroll
+        for (int k = 0; k < NL; ++k) {
+            if (k < L) {
+                const int y = lab[k];
+                bad |= y < 1 || y >= N;
+                w[k >> 2] |= (uint32_t)y << (8 * (k & 3));
+                dmask |= (k > 0 && (!COLLAPSE || y != yp) ? 1u : 0u) << k;
+                yp = y;
+            }
+        }
+        if (!bad) early = L == 0 ? 0.0 : -(double)INFINITY;
+        if (bad) L = 0;
+    }
+    const bool walks = mine && L > 0 && L <= rows;
+    if (mine && !walks) {
+        const int64_t out = read * M + m;  // a pair without a value: NaN; no motif: 0; more labels than rows: -inf
+        p.logp[out] = early;
+        det->count[out] = early != early ? early : 0.0;
+        det->end[out] = kNoHit;
+    }
+    const int nrows = walks ? rows : 0;
+    if (!walks) {
+#pragma unroll
+        for (int k = 0; k < NW; ++k) w[k] = 0;
+    }
+    // L, the first and the last label in one register (unpacked again in every row: three registers fewer across the loop)
+    uint32_t meta = (uint32_t)L | (w[0] & 0xFF) << 8;
+#pragma unroll
+    for (int k = 0; k < NL; ++k)
+        if (walks && k == L - 1) meta |= ((w[k >> 2] >> (8 * (k & 3))) & 0xFF) << 16;
+    __syncthreads();
+    int most = 0;
+    for (int s = 0; s < R; ++s) most = max(most, slot_rows[s]);
+    most = __builtin_amdgcn_readfirstlane(most);  // (the same in every lane)
+    float a[2 * NL];
+#pragma unroll
+    for (int s = 0; s < 2 * NL; ++s) a[s] = 0.0f;
+    int E = 1 - kPackUnit;
+    a[0] = ldexpf(1.0f, -E);  // state 0's 1
+    PackBest best{0.0, 0.0f, 0, -1};
+    float vp = 0.0f;
+    const float *slot = tile + (walks ? q : 0) * S;
+    // (from here to the results the lane keeps its cells, labels, meta, nrows, slot and the running result: nothing else)
+    for (int i0 = 0; i0 < most; i0 += rpt) {
+        __syncthreads();  // the tile's readers are done
+        {  // (what staging needs is worked out again for every tile: it holds no register while the rows are walked)
+            int ln = lane;
+            FCD_OPAQUE_VQ(ln);
+            const int qs = ln / G, sub = ln - qs * G;
+            int b_s, rows_s;
+            pack_range(p, det, group * R + qs, &b_s, &rows_s);
+            const float *post_s = post_at(p.in.post, (group * R + qs) * p.in.stride_read + (int64_t)b_s * p.in.stride_t, p.in.dtype);
+            const int di = G / N, dj = G - di * N;
+            const int cnt = min(rpt, rows_s - i0) * N;
+            bool bad = false;
+            int i = sub / N, j = sub - i * N;
+            for (int e = sub; e < cnt; e += G) {
+                const float v = load_post(post_s, (int64_t)(i0 + i) * p.in.stride_t + (int64_t)j * p.in.stride_n, p.in.dtype);
+                bad |= !(v >= 0.0f && v - v == 0.0f);
+                tile[qs * S + e] = v;
+                i += di;
+                j += dj;
+                if (j >= N) {
+                    j -= N;
+                    ++i;
+                }
+            }
+            if (bad) badw[qs] = 1;
+        }
+        __syncthreads();
+        const int rc = min(rpt, most - i0);
+        for (int i = 0; i < rc; ++i) {
+            const int t = i0 + i;
+            if (t < nrows) {
+                const float *row = slot + i * N;
+                const float p0 = row[0];
+                FCD_OPAQUE_VQ(meta);
+                const int L = meta & 0xFF, last = 2 * L - 1, y_first = (meta >> 8) & 0xFF, y_last = meta >> 16;
+                if (t > 0) pack_cell(best, COLLAPSE ? vp * fmaxf(0.0f, 1.0f - row[y_last]) : vp, E, t - 1);  // c of the row before
+                if (t > 0 && (t & (kPackCheck - 1)) == 0) {  // (behind it: the cells, v among them, share ONE exponent)
+                    float mx = ldexpf(1.0f, max(-E, -200));
+#pragma unroll
+                    for (int s = 1; s < 2 * NL; ++s) mx = fmaxf(mx, s <= last ? a[s] : 0.0f);
+                    int ex;
+                    (void)frexpf(mx, &ex);
+                    const int sh = mx > 0.0f && mx - mx == 0.0f ? min(max(kPackUnit - ex, -100), 100) : 0;
+                    if (sh != 0) {
+                        const float f = ldexpf(1.0f, sh);
+#pragma unroll
+                        for (int s = 0; s < 2 * NL; ++s) a[s] *= f;
+                        E -= sh;
+                    }
+                }
+                const float g = COLLAPSE ? fmaxf(0.0f, 1.0f - row[y_first]) : 1.0f;  // the entry weight of the NEXT row
+                // (kept from hoisting 24 LDS offsets out of the time loop, into registers the cells need)
+#pragma unroll
+                for (int k = 0; k < NW; ++k) FCD_OPAQUE_VQ(w[k]);
+                FCD_OPAQUE_VQ(dmask);
+                // the labels' posteriors kPackGroup at a time, a group ahead of its use: the reads of group n + 1 wait for
+                // the cells of group n - 1 (the fence), so that two groups' values are live, not 24
+                int at = i * N;
+                float pn[GS], pc[GS];
+#pragma unroll
+                for (int c = 0; c < GS; ++c) pn[c] = slot[at + ((w[(NL - 1 - c) >> 2] >> (8 * ((NL - 1 - c) & 3))) & 0xFF)];
+#pragma unroll
+                for (int k1 = NL - 1; k1 >= 0; k1 -= GS) {
+#pragma unroll
+                    for (int c = 0; c < GS; ++c) pc[c] = pn[c];
+                    if (k1 - GS >= 0) {
+                        if (k1 + 1 < NL) FCD_PACK_FENCE(at, a[2 * k1 + 2]);
+#pragma unroll
+                        for (int c = 0; c < GS; ++c) pn[c] = slot[at + ((w[(k1 - GS - c) >> 2] >> (8 * ((k1 - GS - c) & 3))) & 0xFF)];
+                    }
+                    // (every sum reads cells of the row before only: unfenced, all 47 are formed ahead of the first write)
+                    if (k1 + 1 < NL) FCD_PACK_FENCE(a[2 * k1 + 1], a[2 * k1 + 2]);
+#pragma unroll
+                    for (int c = 0; c < GS; ++c) {
+                        const int k = k1 - c, s = 2 * k + 1;
+                        float sum = COLLAPSE ? a[s] + a[s - 1] : a[s - 1];
+                        if (k > 0) sum += ((dmask >> k) & 1) ? a[s - 2] : 0.0f;
+                        a[s] = sum * pc[c];
+                        FCD_OPAQUE_VQ(a[s]);  // (scalar f32 operations: packed ones want register pairs the cells cannot spare)
+                        if (k > 0) {
+                            a[s - 1] = (a[s - 1] + a[s - 2]) * p0;
+                            FCD_OPAQUE_VQ(a[s - 1]);
+                        }
+                    }
+                }
+                // v = a[2L - 1]: a tree of selects on the five bits of L - 1
+                float v;
+                {
+                    float x[32];
+#pragma unroll
+                    for (int k = 0; k < 32; ++k) x[k] = k < NL ? a[2 * k + 1] : 0.0f;
+#pragma unroll
+                    for (int bit = 0; bit < 5; ++bit) {
+                        const bool up = ((L - 1) >> bit) & 1;
+#pragma unroll
+                        for (int k = 0; k < (16 >> bit); ++k) x[k] = up ? x[2 * k + 1] : x[2 * k];
+                    }
+                    v = x[0];
+                }
+                vp = v;
+                a[0] = ldexpf(g, max(-E, -200));
+            }
+        }
+    }
+    if (nrows > 0) {  // (the lane walked: who it is, worked out again)
+        pack_cell(best, vp, E, nrows - 1);  // the last row: h = 1
+        int ln = lane;
+        FCD_OPAQUE_VQ(ln);
+        const int q = ln / Mp, m = (int)(blockIdx.x - group * nblk) * 64 + (ln - q * Mp);
+        const int64_t read = group * R + q, out = read * M + m;
+        int b, rows;
+        pack_range(p, det, read, &b, &rows);
+        const bool bad = badw[q] != 0;
+        p.logp[out] = bad ? (double)NAN : (best.bt < 0 ? -(double)INFINITY : ln_p((double)best.bm, best.be));
+        det->count[out] = bad ? (double)NAN : best.sum;
+        det->end[out] = bad || best.bt < 0 ? kNoHit : (uint32_t)(b + best.bt);
+    }
+}
+
 // Both copies live in one kernel, so every launch, scores included, reserves the detecting copy's registers (63 / 73 /
 // 83 / 94 VGPRs at K = 2 / 4 / 6 / 8 against the score copy's 28 / 40 / 50 / 60).  8.6 KiB of LDS a one-wavefront
 // workgroup hold the kernel at 18 workgroups a CU, 4.5 wavefronts a SIMD, so five wavefronts a SIMD are all a score can
@@ -240,9 +500,14 @@ __device__ __forceinline__ void score_reg_walk(const ScoreParams &p, const Detec
 // the resource report shows scratch, before a later change can take wavefronts from a score unnoticed).
 // The detecting copy's cells go through FCD_OPAQUE_VQ: the compiler forms no packed f32 operations (v_pk_add_f32,
 // v_pk_mul_f32) in that copy; the score copy keeps the 3 / 6 / 9 / 12 it had.
+// K = 2 also carries the packed detecting walk (pack_walk): 91 VGPRs, no scratch, chosen once at the kernel's top by the
+// parameter block's pack_reads; the other three instantiations do not compile it.
 template <int K>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) void score_reg_kernel(ScoreParams p, const DetectOut *det) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    if constexpr (K == 2) {  // (the packed walk: in the instantiation short motifs launch anyway, the one with the most registers to spare)
+        if (det && det->pack_reads) return p.collapse ? pack_walk<true>(p, det, smem) : pack_walk<false>(p, det, smem);
+    }
     if (det) score_reg_walk<K, true>(p, det, smem);
     else score_reg_walk<K, false>(p, det, smem);
 }
@@ -653,6 +918,37 @@ hipError_t launch_ctc_occupancy_wide(const BatchDesc &in, const ScoreDesc &y, in
     if (e != hipSuccess) return e;
     q.walk = kLdsOcc;
     return launch_lds_walk(q, rows, lds, stream);
+}
+
+// The packed detecting walk (pack_walk above): y describes y.n_hyp motifs shared by all reads; *detect (device memory) holds
+// them again with pack_reads = ctc_detect_packed_reads(): one wavefront per pack_reads reads, or per read and 64 motifs.
+int ctc_detect_packed_labels() { return kPackLabels; }
+
+int ctc_detect_packed_reads(int64_t n_motifs, int64_t N) {
+    if (n_motifs > 32) return 1;
+    int mp = 1;
+    while (mp < n_motifs) mp *= 2;
+    int reads = 64 / mp;
+    while (reads > 1 && 31 * (64 / reads) / N < 2) reads /= 2;  // (a slot's 31 * 64 / reads words hold two rows at least)
+    return reads;
+}
+
+hipError_t launch_ctc_detect_packed(const BatchDesc &in, const ScoreDesc &y, int collapse, double *logp, hipStream_t stream,
+                                    const DetectOut *detect) {
+    const int64_t reads = ctc_detect_packed_reads(y.n_hyp, in.N);
+    const int64_t blocks = (in.n_reads + reads - 1) / reads * ((y.n_hyp + 63) / 64);
+    if (blocks <= 0) return hipSuccess;
+    if (y.stride > kPackLabels || in.N > kPackTileWords || blocks >= (1ll << 31)) return hipErrorInvalidValue;
+    ScoreParams p;
+    p.in = in;
+    p.y = y;
+    p.collapse = collapse;
+    p.band = 0;
+    p.logp = logp;
+    p.lab_cap = 1;
+    p.cap = 0;
+    hipLaunchKernelGGL(score_reg_kernel<2>, dim3((unsigned)blocks), dim3(64), lds_bytes(1, 0), stream, p, detect);
+    return hipGetLastError();
 }
 
 hipError_t launch_ctc_score(const BatchDesc &in, const ScoreDesc &y, int collapse, int64_t band, double *logp,

@@ -285,7 +285,18 @@ struct DetectOut {
     float *track;  // nullable
     int64_t track_stride;
     const uint32_t *row_begin, *row_end;  // nullable
+    // (fcd_set_ctc_detect_packed) pack_reads > 0: the packed walk -- pack_m motifs shared by all reads, pack_labels
+    // [pack_m * stride] and pack_len [pack_m] in device memory, pack_reads reads per wavefront
+    const uint8_t *pack_labels = nullptr;
+    const uint32_t *pack_len = nullptr;
+    int pack_m = 0, pack_reads = 0;
 };
+// the packed walk: the labels a motif may have, the reads a wavefront holds, and the launch (y: the shared motifs; *detect
+// as above, in device memory)
+int ctc_detect_packed_labels();
+int ctc_detect_packed_reads(int64_t n_motifs, int64_t N);
+hipError_t launch_ctc_detect_packed(const BatchDesc &in, const ScoreDesc &y, int collapse, double *logp, hipStream_t stream,
+                                    const DetectOut *detect);
 hipError_t launch_ctc_score(const BatchDesc &in, const ScoreDesc &y, int collapse, int64_t band, double *logp,
                             hipStream_t stream, const DetectOut *detect = nullptr);
 // CTC forced alignment of given labellings (ctc_align.hip; fcd_alignment in include/fcd.h): what ctc_score supports.
@@ -523,6 +534,7 @@ struct fcd_handle {
     fcd_spot spot{};          // ... these outputs and ranges next to its own fcd_alignment
     bool detect_on = false;   // fcd_set_ctc_detect: fcd_ctc_score_dev detects, with ...
     fcd_detect detect{};      // ... these outputs and ranges next to its own logp
+    bool detect_packed = false;  // fcd_set_ctc_detect_packed: the detecting calls take shared motifs, one pair per lane
     int64_t align_ws_cap = 0; // fcd_debug_set_align_workspace_cap: back-pointer bytes one launch of fcd_ctc_align_* may take, 0 = default
     bool is_lane = false;
     uint32_t *duplex_prof = nullptr;  // fcd_debug_set_duplex_profile

@@ -516,7 +516,7 @@ int fcd_set_ctc_spot(fcd_handle *h, const fcd_spot *spot);
  * workspace: 256 bytes of parameters, and logp where it is null.  FCD_E_INVALID before anything is enqueued: band != 0,
  * count or end null, track given with track_stride < in->T, and fcd_ctc_score_*'s cases.
  * Out of scope: CRF models, bands, the k best ends on the device, the start-row distribution of an occurrence, P(at
- * least one occurrence), several short motifs packed into one wavefront. */
+ * least one occurrence).  (Several short motifs packed into one wavefront: fcd_set_ctc_detect_packed below.) */
 typedef struct fcd_detect {
     double   *count;            /* [n_reads * n_hyp] */
     uint32_t *end;              /* [n_reads * n_hyp] */
@@ -535,6 +535,21 @@ int fcd_ctc_detect_host(fcd_handle *h, const fcd_batch *in, const fcd_labellings
  * affected.  The threading caveat is fcd_set_ctc_spot's: between setting and clearing the switch the handle must not be
  * shared with another thread; the Python layer sets, calls and clears on the calling thread's own handle. */
 int fcd_set_ctc_detect(fcd_handle *h, const fcd_detect *detect);
+/* The packed mode: many short motifs, shared by all reads, one (read, motif) pair per LANE -- barcode demultiplexing.
+ * fcd_set_ctc_detect_packed(h, 1) makes fcd_ctc_detect_host, and fcd_ctc_score_dev under fcd_set_ctc_detect, on this handle
+ * take it; (h, 0) -- the state of a new handle -- turns it off.  The definition is fcd_ctc_detect_*'s, unchanged: the
+ * recurrence, g_t, h_t, count, end, logp, the rows without a value, row_begin / row_end.  While the switch is on
+ *   y describes n_hyp motifs shared by ALL reads: labels [n_hyp * stride], len [n_hyp]; n_valid and path null.  Motif i of
+ *   read r is row r * n_hyp + i of count, end and logp, which stay [n_reads * n_hyp].  No track is written.
+ * Limits: stride <= 24 (the cells of a motif live in one lane's registers), N <= 1984, any n_hyp >= 1.  A wavefront walks
+ * 64 / Mp consecutive reads (Mp: n_hyp rounded up to a power of two) or, beyond 32 motifs, one read and 64 motifs, and
+ * stages every read's rows once for all its motifs.  The arithmetic per cell is the unpacked call's; the scale is a
+ * per-lane integer exponent looked at every 32 rows: a cell below 2^-190 as a probability may count as 0, and where rows
+ * that do not sum to 1 carry the cells beyond 2^213 a fresh start counts as 0.  Posteriors above 1 give some value.
+ * FCD_E_INVALID before anything is enqueued: track given, n_valid given, band != 0, and fcd_ctc_detect_*'s cases;
+ * FCD_E_UNSUPPORTED: stride > 24, N > 1984.  The device call is enqueue-only on the handle's stream: 256 bytes of
+ * parameters are uploaded, the motifs are read where y points.  The threading caveat is fcd_set_ctc_spot's. */
+int fcd_set_ctc_detect_packed(fcd_handle *h, int on);
 
 /* ---- CTC forward-backward substitution posteriors of given labellings (csrc/ctc_posterior.hip) ----
  * NOT a reference function.  For a labelling y of L labels (hypothesis i of read r, row = r * n_hyp + i), label position
