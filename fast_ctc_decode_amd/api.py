@@ -1784,13 +1784,13 @@ _Kept = collections.namedtuple("_Kept", "x labels label_lengths paths n_valid le
 
 
 def _lattice_inputs(network_outputs, labels, label_lengths, lengths, paths, band, n_valid, input_dtype, handle,
-                    init_states=None, shared=False):
+                    init_states=None, shared=False, crf=None):
     """The argument handling ctc_score_batch_raw, ctc_align_batch_raw and their CRF counterparts share.  -> (handle,
     nat.Batch, nat.Labellings, (B, n_hyp, stride), device or None for numpy input, the arrays the two structs point into);
     init_states given (the CRF calls: (B, T, S, N) posteriors): the init rows (B, n_init) are the last of those arrays.
     shared (ctc_detect_batch_raw's packed mode): labels (n_hyp, stride) and label_lengths (n_hyp,) describe labellings
-    every read shares."""
-    crf = init_states is not None
+    every read shares.  crf=True without init_states (crf_detect_batch_raw): (B, T, S, N) posteriors, no init rows."""
+    crf = init_states is not None if crf is None else crf
     nd = 4 if crf else 3
     dev_x = _device_tensor(network_outputs)
     if dev_x is not None:
@@ -1821,9 +1821,10 @@ def _lattice_inputs(network_outputs, labels, label_lengths, lengths, paths, band
         st = x.stride()
         init = None
         if crf:
-            init = torch.as_tensor(init_states, dtype=torch.float32, device=dev).contiguous()
-            if init.ndim != 2 or init.shape[0] != B or init.shape[1] < 1:
-                raise ValueError("init_states must have shape (n_reads, n_init)")
+            if init_states is not None:
+                init = torch.as_tensor(init_states, dtype=torch.float32, device=dev).contiguous()
+                if init.ndim != 2 or init.shape[0] != B or init.shape[1] < 1:
+                    raise ValueError("init_states must have shape (n_reads, n_init)")
             b = nat.Batch(x.data_ptr(), B, T, x.shape[2], N, st[0], st[1], st[2], st[3], None, _torch_dtype_code(x))
         else:
             b = nat.Batch(x.data_ptr(), B, T, 1, N, st[0], st[1], 0, st[2], None, _torch_dtype_code(x))
@@ -1853,7 +1854,7 @@ def _lattice_inputs(network_outputs, labels, label_lengths, lengths, paths, band
     h = nat.default_handle()  # (host arrays: the calling thread's own handle, whatever handle the search ran on)
     l = _np_lengths(lengths, B)
     init = None
-    if crf:
+    if crf and init_states is not None:
         init = np.ascontiguousarray(np.asarray(init_states, np.float32))
         if init.ndim != 2 or init.shape[0] != B or init.shape[1] < 1:
             raise ValueError("init_states must have shape (n_reads, n_init)")
@@ -1949,6 +1950,31 @@ def _detect_out(xp, b, shape, lengths=None, rows=None, track=False):
     return C.byref(out), DetectResult(count, end, logp, trk, (begin, stop))
 
 
+def _crf_detect_out(xp, b, shape, marginals=None, **detect_args):
+    """_detect_out's arrays, and the edge marginals: a float32 (B, T, S, N) array where the posteriors live, (S, N) rows
+    dense in N"""
+    _, result = _detect_out(xp, b, shape, **detect_args)
+    want = (shape[0], int(b.T), int(b.S), int(b.N))
+    if xp.dev is None:
+        marg = np.asarray(marginals, np.float32)
+        marg = marg if marg.ndim == 4 and marg.strides[3] == 4 and min(marg.strides) >= 0 else np.ascontiguousarray(marg)
+        st = tuple(v // 4 for v in marg.strides)
+    else:
+        import torch
+        marg = torch.as_tensor(marginals, dtype=torch.float32, device=xp.dev)
+        marg = marg if marg.ndim == 4 and marg.stride(3) == 1 else marg.contiguous()
+        st = tuple(marg.stride())
+    if tuple(marg.shape) != want:
+        raise ValueError("marginals must have the posteriors' shape (n_reads, T, S, N)")
+    begin, stop = result._rows
+    out = nat.CrfDetect(xp.ptr(result.count), xp.ptr(result.end), xp.ptr(result.logp),
+                        xp.ptr(result.track) if result.track is not None else None, int(b.T),
+                        xp.ptr(begin) if begin is not None else None, xp.ptr(stop) if stop is not None else None,
+                        xp.ptr(marg), st[0], st[1], st[2])
+    result._marginals = marg  # (alive as long as the result)
+    return C.byref(out), result
+
+
 def _posterior_out(xp, b, shape):
     post = xp.zeros(shape + (int(b.N) - 1,), "f32")
     logp = xp.empty(shape[:2], "f64")
@@ -2022,7 +2048,7 @@ def _occupancy_out(xp, b, shape, has_S, out=None, scale=1.0, accumulate=False, t
 
 
 _LATTICE_BUILDERS = {"score": _score_out, "align": _align_out, "posterior": _posterior_out, "edits": _edits_out,
-                     "occupancy": _occupancy_out, "spot": _spot_out, "detect": _detect_out}
+                     "occupancy": _occupancy_out, "spot": _spot_out, "detect": _detect_out, "crf_detect": _crf_detect_out}
 
 
 @contextlib.contextmanager
@@ -2045,7 +2071,7 @@ def _lattice_call(model, kind, network_outputs, labels, label_lengths, lengths, 
                   init_states=None, collapse_repeats=True, wide=False, packed=False, **out_args):
     """The one body of the labelling-lattice calls: fcd_<model>_<kind>_dev for device tensors, _host for numpy, with
     model "ctc" (network_outputs (B,T,N), collapse_repeats) or "crf" ((B,T,S,N) and init_states), kind one of
-    _LATTICE_BUILDERS ("spot", "detect": CTC only); out_args: the occupancy calls' out, scale, accumulate and
+    _LATTICE_BUILDERS ("spot": CTC only; "detect" under "crf": _crf_detect_out, marginals in place of init_states); out_args: the occupancy calls' out, scale, accumulate and
     time_major_out, the spotting and detecting calls' rows and track.  packed ("detect"): labels and label_lengths are
     motifs shared by all reads, under the handle's fcd_set_ctc_detect_packed.  -> what the call returns."""
     band = _check_band(band, paths)
@@ -2053,12 +2079,15 @@ def _lattice_call(model, kind, network_outputs, labels, label_lengths, lengths, 
         _check_occupancy_out(**out_args)
         out_args["has_S"] = model == "crf"
     h, b, y, shape, dev, keep = _lattice_inputs(network_outputs, labels, label_lengths, lengths, paths, band, n_valid,
-                                                input_dtype, handle, init_states, shared=packed)
+                                                input_dtype, handle, init_states, shared=packed, crf=model == "crf")
     xp = _Arrays(dev)
     if kind in ("spot", "detect"):
         out_args["lengths"] = keep.lengths  # (rows counts from every read's own length)
-    out, result = _LATTICE_BUILDERS[kind](xp, b, shape, **out_args)
-    if model == "crf":
+    crf_detect = model == "crf" and kind == "detect"
+    out, result = _LATTICE_BUILDERS["crf_detect" if crf_detect else kind](xp, b, shape, **out_args)
+    if crf_detect:  # (no init row: the device call passes none, the host call has no such arguments)
+        args = (C.byref(b), None, 0, 0, C.byref(y), band, out) if dev is not None else (C.byref(b), C.byref(y), band, out)
+    elif model == "crf":
         init = keep[-1]
         args = (C.byref(b), C.c_void_p(xp.ptr(init)), int(init.shape[1]), int(init.shape[1]), C.byref(y), band, out)
     else:
@@ -2072,7 +2101,7 @@ def _lattice_call(model, kind, network_outputs, labels, label_lengths, lengths, 
             h.check(h.lib.fcd_set_ctc_spot(h.ptr, out))
             args = args[:-1] + (C.cast(out, C.POINTER(nat.Alignment)),)  # (fcd_spot begins with fcd_alignment's four pointers)
         if detect_dev:
-            h.check(h.lib.fcd_set_ctc_detect(h.ptr, out))
+            h.check((h.lib.fcd_set_crf_detect if crf_detect else h.lib.fcd_set_ctc_detect)(h.ptr, out))
             args = args[:-1] + (C.c_void_p(xp.ptr(result.logp)),)  # (the score's own logp array)
         if packed:
             h.set_ctc_detect_packed(True)
@@ -2084,7 +2113,7 @@ def _lattice_call(model, kind, network_outputs, labels, label_lengths, lengths, 
             if spot_dev:
                 h.lib.fcd_set_ctc_spot(h.ptr, None)
             if detect_dev:
-                h.lib.fcd_set_ctc_detect(h.ptr, None)
+                (h.lib.fcd_set_crf_detect if crf_detect else h.lib.fcd_set_ctc_detect)(h.ptr, None)
     if kind == "occupancy" and dev is not None:
         h.hold_in_flight(result.occupancy, result.logp, *keep)
     return result
@@ -2320,6 +2349,53 @@ def ctc_detect(network_output, motif, alphabet, rows=None):
     rows=(lo, hi): look in network_output[lo:hi] only."""
     x, lab, n, _ = _ctc_one_read(network_output, motif, alphabet, "ctc_detect")
     r = ctc_detect_batch_raw(x, lab, n, rows=rows)
+    end = int(r.end[0, 0])
+    return float(r.count[0, 0]), (None if end == NO_HIT else end), float(r.logp[0, 0])
+
+
+# ---------------------------------------------------------------------------------------------
+# CRF motif occurrence posteriors: expected counts under the CRF (include/fcd.h, fcd_crf_detect_*)
+# ---------------------------------------------------------------------------------------------
+def crf_detect_batch_raw(probs, marginals, motifs, motif_lengths, lengths=None, rows=None, track=False, input_dtype=None,
+                         handle=None):
+    """CRF motif occurrence posteriors: the expected number of occurrences of each of M known sequences in every read,
+    over ALL labellings and alignments under the CRF -- an exact expectation, no boundary weights (include/fcd.h,
+    fcd_crf_detect_*).  -> DetectResult, arrays (B, M[, T]).
+
+    probs (B,T,S,N): the transition posteriors of crf_transition_probs_batch_raw ("source" layout; float32, float16 or
+    bfloat16 bits, any strides); marginals (B,T,S,N) float32: crf_marginals_batch_raw's edge marginals of the same
+    scores, where probs lives.  motifs (M, stride) uint8 labels 1 .. N-1 and motif_lengths (M,), shared by all reads;
+    lengths, rows and track as ctc_detect_batch_raw takes them.  S = (N-1)^m; motifs up to 511 + m labels.
+    Demultiplexing: count.argmax(1) is the barcode of every read, count.max(1) what to threshold.  Device tensors in:
+    torch tensors on the same device, enqueued on torch's current stream, not synchronised.  numpy in: numpy out."""
+    m = np.asarray(_to_host(motifs), np.uint8)
+    if m.ndim != 2:
+        raise ValueError("motifs must have shape (n_motifs, stride)")
+    if rows is not None and (not isinstance(rows, (tuple, list)) or len(rows) != 2):
+        raise ValueError("rows must be a pair (lo, hi)")
+    B = len(probs)
+    n = np.asarray(_to_host(motif_lengths), np.uint32).reshape(-1)
+    if n.size != m.shape[0]:
+        raise ValueError("motif_lengths must have one entry per motif")
+    return _lattice_call("crf", "detect", probs, np.tile(m[None], (B, 1, 1)), np.tile(n[None], (B, 1)), lengths, None, 0,
+                         None, input_dtype, handle, rows=rows, track=bool(track), marginals=marginals)
+
+
+def crf_detect(scores, motif, alphabet, rows=None):
+    """One string in one read, from the network's raw (T, S, N) float32 CRF scores: -> (count, end, logp), the expected
+    number of its occurrences over all labellings, the row at which one most probably ends (None where there is none) and
+    ln of that probability.  Calls crf_transition_probs and crf_marginals itself.  rows=(lo, hi): occurrences whose
+    min(L, m)-th label is emitted in scores[lo:hi]."""
+    x = _as_f32(scores, 3, "scores")
+    alpha = _seq_to_vec(alphabet)
+    _check_greedy_alphabet(len(alpha), x.shape[2])
+    y = _crf_sequence_labels(motif, alpha, "crf_detect")
+    lab = np.zeros((1, max(len(y), 1)), np.uint8)
+    lab[0, :len(y)] = y
+    tr = crf_transition_probs_batch_raw(_dense(x)[None])
+    _raise_status(int(tr.status[0]))
+    mg = crf_marginals_batch_raw(_dense(x)[None], emit=False)
+    r = crf_detect_batch_raw(tr.probs, mg.marginals, lab, np.array([len(y)], np.uint32), rows=rows)
     end = int(r.end[0, 0])
     return float(r.count[0, 0]), (None if end == NO_HIT else end), float(r.logp[0, 0])
 

@@ -1947,6 +1947,9 @@ struct LatticeCall {
     const fcd_spot *spot = nullptr;  // (CTC align) fcd_ctc_spot_*: `out` holds its first four pointers
     const fcd_detect *detect = nullptr;  // (CTC score) fcd_ctc_detect_*: `logp` is its logp
     bool packed = false;  // (detect) fcd_set_ctc_detect_packed: y holds n_hyp motifs shared by all reads
+    // (CRF detect) fcd_crf_detect_*: `detect` holds its first seven members, these the edge marginals; no init is read
+    const float *marg = nullptr;
+    int64_t marg_stride_read = 0, marg_stride_t = 0, marg_stride_s = 0;
 };
 
 // the labellings y->labels / y->len describe: one per (read, hypothesis), or (packed) the n_hyp shared motifs
@@ -1972,11 +1975,19 @@ size_t track_floats(const fcd_batch *in, const fcd_labellings *y, const float *t
 }
 size_t track_span(const fcd_batch *in, const fcd_labellings *y, const fcd_spot *s) { return track_floats(in, y, s->track, s->track_stride); }
 size_t detect_track_span(const fcd_batch *in, const fcd_labellings *y, const fcd_detect *s) { return track_floats(in, y, s->track, s->track_stride); }
+// floats from the first to the last element the call may address in the marginals of fcd_crf_detect_*
+size_t marg_span(const LatticeCall &c) {
+    const fcd_batch *in = c.in;
+    if (in->n_reads <= 0 || in->T <= 0) return 0;
+    return (size_t)((in->n_reads - 1) * c.marg_stride_read + (in->T - 1) * c.marg_stride_t + (in->S - 1) * c.marg_stride_s + in->N);
+}
 
 int lattice_check(fcd_handle *h, const LatticeCall &c) {
     if (c.align && !c.out) return fail(h, FCD_E_INVALID, "null alignment");
     if (c.spot && c.band != 0) return fail(h, FCD_E_INVALID, "ctc_spot: band must be 0 (the motif is looked for in the exact lattice)");
-    if (c.detect && c.band != 0) return fail(h, FCD_E_INVALID, "ctc_detect: band must be 0 (the motif is looked for in the exact lattice)");
+    if (c.detect && c.band != 0)
+        return fail(h, FCD_E_INVALID, c.crf ? "crf_detect: band must be 0 (the motif is looked for over all labellings)"
+                                            : "ctc_detect: band must be 0 (the motif is looked for in the exact lattice)");
     if (c.posterior && !c.post) return fail(h, FCD_E_INVALID, "null posterior");
     if (c.edit && !c.edits) return fail(h, FCD_E_INVALID, c.crf ? "crf_edits: null output" : "ctc_edits: null output");
     const std::string occ_who = c.crf ? "crf_occupancy" : (c.wide ? "ctc_occupancy_wide" : "ctc_occupancy");
@@ -1985,7 +1996,10 @@ int lattice_check(fcd_handle *h, const LatticeCall &c) {
     const fcd_labellings *y = c.y;
     int rc = check_batch(h, in, c.crf);
     if (rc) return rc;
-    if (c.crf) {
+    if (c.crf && c.detect) {  // (no init row is read)
+        if (in->n_reads > 0 && !c.marg) return fail(h, FCD_E_INVALID, "crf_detect: null marg");
+        if (c.marg_stride_read < 0 || c.marg_stride_t < 0 || c.marg_stride_s < 0) return fail(h, FCD_E_INVALID, "crf_detect: negative marg stride");
+    } else if (c.crf) {
         if (!c.init || c.n_init < 1) return fail(h, FCD_E_INVALID, "init_state missing");
         if (c.init_stride < 0) return fail(h, FCD_E_INVALID, "negative stride");
     } else if (in->S != 1) {
@@ -2008,7 +2022,7 @@ int lattice_check(fcd_handle *h, const LatticeCall &c) {
                             !(c.occupancy ? (const void *)c.occ->occ : c.edit ? (const void *)c.edits->deletion : c.posterior ? (const void *)c.post->post
                               : c.align ? (const void *)c.out->start : c.detect ? (const void *)c.detect->count : (const void *)c.logp)))
         return fail(h, FCD_E_INVALID, c.occupancy ? (c.crf ? "crf_occupancy: null labels/len/occ" : c.wide ? "ctc_occupancy_wide: null labels/len/occ" : "ctc_occupancy: null labels/len/occ") : c.edit ? (c.crf ? "crf_edits: null labels/len/deletion" : "ctc_edits: null labels/len/deletion") : c.posterior ? "null labels/len/post"
-                                      : c.align ? "null labels/len/start" : c.detect ? "ctc_detect: null labels/len/count" : "null labels/len/logp");
+                                      : c.align ? "null labels/len/start" : c.detect ? (c.crf ? "crf_detect: null labels/len/count" : "ctc_detect: null labels/len/count") : "null labels/len/logp");
     if (c.edit && in->n_reads > 0 && !c.edits->insertion) return fail(h, FCD_E_INVALID, c.crf ? "crf_edits: null insertion" : "ctc_edits: null insertion");
     if (in->n_reads * y->n_hyp >= (1ll << 31)) return fail(h, FCD_E_UNSUPPORTED, "more than 2^31 labellings in one call");
     if (c.crf && crf_wide_call(c)) {
@@ -2022,6 +2036,15 @@ int lattice_check(fcd_handle *h, const LatticeCall &c) {
         case 4: return fail(h, FCD_E_UNSUPPORTED, (who + ": the labelling, the tile, the window's three rows" + (c.occupancy ? " and the S * N accumulation row" : "") +
                                                    " do not fit the 160 KiB of LDS (4 (min(T, stride) + 1) + 4480 + 768 ceil(states / 64)" +
                                                    (c.occupancy ? " + 4 S N" : "") + " = " + std::to_string(lds) + " bytes): use a band or a smaller stride").c_str());
+        default: break;
+        }
+    } else if (c.crf && c.detect) {
+        switch (crf_detect_unsupported(to_desc(in, true), y->stride)) {
+        case 1: return fail(h, FCD_E_UNSUPPORTED, "crf_detect: S must be a power of N - 1 (the model state is the last labels)");
+        case 2: return fail(h, FCD_E_UNSUPPORTED, "crf_detect: more than 8 labels besides the blank");
+        case 3: return fail(h, FCD_E_UNSUPPORTED, "crf_detect: motifs beyond 511 + m labels (S = (N - 1)^m) exceed the 512 register-resident cells: use a smaller stride");
+        case 4: return fail(h, FCD_E_UNSUPPORTED, "crf_detect: S must be below 2^24 - 1");
+        case 5: return fail(h, FCD_E_UNSUPPORTED, "crf_detect: a row of more than 1024 values must span less than 2^31 bytes, with no negative stride");
         default: break;
         }
     } else if (c.crf) {
@@ -2039,9 +2062,10 @@ int lattice_check(fcd_handle *h, const LatticeCall &c) {
     if (c.align && in->n_reads > 0 && !c.out->count) return fail(h, FCD_E_INVALID, "null count");
     if (c.spot && in->n_reads > 0 && !c.spot->end) return fail(h, FCD_E_INVALID, "ctc_spot: null end");
     if (c.spot && c.spot->track && c.spot->track_stride < in->T) return fail(h, FCD_E_INVALID, "ctc_spot: track_stride must hold the T rows of a read");
-    if (c.detect && in->n_reads > 0 && !c.detect->end) return fail(h, FCD_E_INVALID, "ctc_detect: null end");
-    if (c.detect && c.detect->track && c.detect->track_stride < in->T) return fail(h, FCD_E_INVALID, "ctc_detect: track_stride must hold the T rows of a read");
-    if (c.detect && !ctc_detect_supported(in->T, y->stride))
+    if (c.detect && in->n_reads > 0 && !c.detect->end) return fail(h, FCD_E_INVALID, c.crf ? "crf_detect: null end" : "ctc_detect: null end");
+    if (c.detect && c.detect->track && c.detect->track_stride < in->T)
+        return fail(h, FCD_E_INVALID, c.crf ? "crf_detect: track_stride must hold the T rows of a read" : "ctc_detect: track_stride must hold the T rows of a read");
+    if (c.detect && !c.crf && !ctc_detect_supported(in->T, y->stride))
         return fail(h, FCD_E_UNSUPPORTED, "ctc_detect: motifs beyond 5119 labels exceed the 10240 states of 1024 work-items: use a smaller stride");
     if (c.occupancy) {  // (a CTC batch has S = 1: its rows are N floats)
         if (c.occ->stride_row < 0 || c.occ->stride_t < in->S * in->N)
@@ -2199,13 +2223,22 @@ int lattice_detect(fcd_handle *h, const LatticeCall &c) {
             sc.add(s->track, detect_track_span(in, y, s) * 4);
             sc.add(s->row_begin, (size_t)in->n_reads * 4);
             sc.add(s->row_end, (size_t)in->n_reads * 4);
+            sc.add(c.marg, marg_span(c) * 4);
         },
         [&](const BatchDesc &d, const ScoreDesc &yd, int64_t, int64_t, double *logp, unsigned char *, hipStream_t stream) {
+            if (c.crf) return launch_crf_detect(d, yd, logp, stream, reinterpret_cast<const CrfDetectOut *>(block));
             if (c.packed) return launch_ctc_detect_packed(d, yd, c.collapse, logp, stream, reinterpret_cast<const DetectOut *>(block));
             return launch_ctc_score(d, yd, c.collapse, 0, logp, stream, reinterpret_cast<const DetectOut *>(block));
         },
         256,
         [&](int64_t r0, int64_t row0, void *host) {
+            if (c.crf) {
+                *static_cast<CrfDetectOut *>(host) = CrfDetectOut{s->count + row0, s->end + row0, s->track ? s->track + row0 * s->track_stride : nullptr,
+                                                                  s->track_stride, s->row_begin ? s->row_begin + r0 : nullptr,
+                                                                  s->row_end ? s->row_end + r0 : nullptr, c.marg + r0 * c.marg_stride_read,
+                                                                  c.marg_stride_read, c.marg_stride_t, c.marg_stride_s};
+                return;
+            }
             *static_cast<DetectOut *>(host) = DetectOut{s->count + row0, s->end + row0, s->track ? s->track + row0 * s->track_stride : nullptr,
                                                         s->track_stride, s->row_begin ? s->row_begin + r0 : nullptr,
                                                         s->row_end ? s->row_end + r0 : nullptr};
@@ -2373,6 +2406,7 @@ int lattice_host(fcd_handle *h, const LatticeCall &c) {
     const int i_dtrack = det ? st.inout(det->track, detect_track_span(in, y, det) * 4) : -1;
     const int i_drb = det ? st.in(det->row_begin, B * 4) : -1;
     const int i_dre = det ? st.in(det->row_end, B * 4) : -1;
+    const int i_marg = det ? st.in(c.marg, marg_span(c) * 4) : -1;
     // (posterior entries the kernel does not write -- k >= len -- come back as 0)
     const int i_sub = c.posterior ? st.out(c.post->post, cells * ((size_t)in->N - 1) * 4, true) : -1;
     // (edit entries the kernel does not write -- k >= len, g > len -- come back as 0)
@@ -2417,6 +2451,7 @@ int lattice_host(fcd_handle *h, const LatticeCall &c) {
         ddet.row_begin = st.at<uint32_t>(i_drb);
         ddet.row_end = st.at<uint32_t>(i_dre);
         d.detect = &ddet;
+        d.marg = st.at<float>(i_marg);
     }
     const fcd_posterior dpost{st.at<float>(i_sub), st.at<double>(i_logp)};
     d.post = &dpost;
@@ -2562,10 +2597,43 @@ int fcd_ctc_edits_host(fcd_handle *h, const fcd_batch *in, const fcd_labellings 
     return lattice_host(h, LatticeCall{false, false, in, y, band, collapse_repeats != 0, nullptr, 0, 0, nullptr, nullptr, false, nullptr, true, out});
 }
 
+namespace {
+// fcd_crf_detect_*: a scoring call without an init row, the detect outputs and the marginals behind it
+int crf_detect_call(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int64_t band, const fcd_crf_detect *out,
+                    int (*run)(fcd_handle *, const LatticeCall &)) {
+    if (!out) return fail(h, FCD_E_INVALID, "crf_detect: null output");
+    const fcd_detect head{out->count, out->end, out->logp, out->track, out->track_stride, out->row_begin, out->row_end};
+    LatticeCall c{true, false, in, y, band, 0, nullptr, 0, 0, out->logp, nullptr};
+    c.detect = &head;
+    c.marg = out->marg;
+    c.marg_stride_read = out->marg_stride_read, c.marg_stride_t = out->marg_stride_t, c.marg_stride_s = out->marg_stride_s;
+    return run(h, c);
+}
+}  // namespace
+
+int fcd_set_crf_detect(fcd_handle *h, const fcd_crf_detect *detect) {
+    if (!h) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> g(h->mu);
+    h->crf_detect_on = detect != nullptr;
+    h->crf_detect = detect ? *detect : fcd_crf_detect{};
+    return FCD_OK;
+}
+
+int fcd_crf_detect_host(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int64_t band, const fcd_crf_detect *out) {
+    if (!h) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> whole_call(h->mu);  // staging .. copy-back, see run_host
+    return crf_detect_call(h, in, y, band, out, lattice_host);
+}
+
 int fcd_crf_score_dev(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init, int64_t init_stride,
                       const fcd_labellings *y, int64_t band, double *logp) {
     if (!h) return FCD_E_INVALID;
     std::lock_guard<std::recursive_mutex> g(h->mu);
+    if (h->crf_detect_on) {  // fcd_set_crf_detect: the detecting call, ln c_end into this call's own `logp`; init is not read
+        fcd_crf_detect s = h->crf_detect;
+        s.logp = logp;
+        return crf_detect_call(h, in, y, band, &s, lattice_dev);
+    }
     LatticeCall c{true, false, in, y, band, 0, init, n_init, init_stride, logp, nullptr};
     c.crf_wide = h->crf_wide;
     return lattice_dev(h, c);

@@ -37,6 +37,8 @@ struct CrfParams {
     float *qual;
     unsigned char *bp;
     int64_t bp_row_bytes;
+    // motif occurrence posteriors (fcd_crf_detect_*: crf_detect_walk below); null in every other launch
+    const CrfDetectOut *det;
 };
 
 struct CrfLds {
@@ -328,6 +330,277 @@ __device__ __forceinline__ float crf_forward_walk(const CrfParams &p, const CrfL
     __syncthreads();
     *eacc_out = eacc;
     return __int_as_float(lds.misc[18]);
+}
+
+// ---- kCrfDetect: motif occurrence posteriors, the expected number of occurrences under the CRF (fcd_crf_detect_*) ----
+// A fourth forward walk, with a body of its own: it shares the tile, the slots and the source-lane products with the three
+// above and none of their bookkeeping.  With h = min(L, m), cell k = h .. L - 1 ("k labels of the motif emitted") lives in
+// slot k - h from the first row of the range to the last: the window never slides, so a slot's model state sigma_k and label
+// y_k are loop invariants in one register (slot_state, the window of a row and its masks are not needed).
+//   scale    every cell is a probability and an entry weight e_u is at most nb^(m-h+1) <= S < 2^24, so a cell stays below
+//            T * S < 2^55 whatever the marginals add up to: the cells carry the FIXED factor 2^kDetScale = 2^64 (below 2^119,
+//            no overflow) instead of a per-row exponent -- no wave_imax, no mantissa / exponent split, no reduction in the
+//            row loop.  The price is a floor: a cell below 2^-190 as a probability is subnormal at that scale and loses
+//            bits, one below 2^-213 counts as 0.
+//   entry    e_u = the sum over the nb^(m-h+1) states whose last h - 1 labels are the motif's first of marg[u][sigma][y_(h-1)],
+//            f32, in ascending order of the state: lane i sums row u0 + i of the next 64 rows into LDS (the k(t) words, which
+//            a walk without a band does not use), and lane 0 reads one word a row into slot 0's advance.
+//   step     s = a * p[u][sigma_k][0] and v = a * p[u][sigma_k][y_k] at the source lane, v one slot up (in the lane or by one
+//            wave rotation), a = s + v: one rounding per product and per sum.  The posteriors come from the staged tile
+//            or, S * N beyond it, from global memory a row ahead: crf_fill_tile's rule.
+//   exit     c_u = the last cell's advance product (cell L is not walked): one readlane a row.  A slot above the last cell
+//            reads its posteriors as 0; what travels into it never travels on.
+//   result   c_u into a float64 sum in row order, into the running best (value, row) -- strictly greater only, so ties go
+//            to the earliest row; both wave-uniform -- and, with a track, into lane u mod 64 until 64 rows are stored at
+//            once: one logf and one store per lane.  L <= m: no cells, c_u = e_u straight from the LDS words.
+// The range's first row takes the read's place: rows [b, e) are rows 0 .. e - b - 1 here.
+constexpr int kCrfDetect = 3;
+constexpr int kDetScale = 64;
+constexpr uint32_t kCrfNoHit = 0xFFFFFFFFu;
+constexpr float kCrfLn2f = 0.693147180559945309f;
+
+// a row that does not walk
+__device__ __forceinline__ void crf_detect_none(const CrfParams &p, double count, double logp) {
+    if (threadIdx.x == 0) {
+        p.det->count[blockIdx.x] = count;
+        p.det->end[blockIdx.x] = kCrfNoHit;
+        p.logp[blockIdx.x] = logp;
+    }
+}
+
+struct CrfDetectAcc {
+    double sum;  // c_b + .. so far, at the walk's scale
+    float bv;    // the best c so far (0: none yet) ...
+    int bt;      // ... and its row of the range
+    float tv;    // lane j: c of row c0 + j of the 64 rows of `track` being staged
+};
+
+// The block's fields, a read's length and range come from global memory the kernel also writes: loaded once, ahead of the
+// time loop, and pinned in scalar registers -- every loop bound derived from them stays scalar too.
+__device__ __forceinline__ int wave_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ int64_t wave_uniform(int64_t v) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)v >> 32));
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+template <class T>
+__device__ __forceinline__ T *wave_uniform(T *ptr) {
+    return reinterpret_cast<T *>((uintptr_t)wave_uniform((int64_t)(uintptr_t)ptr));
+}
+
+// c_t (times 2^sc) is complete; t: row of the range, whose first row `track` points at (null: no track)
+__device__ __forceinline__ void crf_detect_row(float *track, CrfDetectAcc &acc, float c, int sc, int t, int rows) {
+    acc.sum += (double)c;
+    if (c > acc.bv) {
+        acc.bv = c;
+        acc.bt = t;
+    }
+    if (track) {
+        const int j = threadIdx.x;
+        if (j == (t & 63)) acc.tv = c;
+        if ((t & 63) == 63 || t == rows - 1) {
+            const int c0 = t & ~63;
+            if (c0 + j <= t) {
+                int ex = 0;
+                const float m = frexpf(acc.tv, &ex);
+                track[c0 + j] = acc.tv > 0.0f ? fmaf((float)(ex - sc), kCrfLn2f, logf(m)) : -INFINITY;
+            }
+        }
+    }
+}
+
+// What a lane reads for one row, a row ahead of its use: the two posteriors of the state each of its slots holds.  Where
+// they sit in a row never changes, so a slot keeps two 32-bit offsets for the whole walk -- words into the staged tile's
+// row, or bytes into the read's row in global memory (the launch's check: a row spans less than 2^31 bytes), which the
+// load adds to a wave-uniform row address.  -1: a slot above the last cell, or a state outside the table: both read 0.
+template <int K>
+struct CrfDetectStep {
+    float p0[K], py[K];
+};
+
+template <int K, bool STAGED>
+__device__ __forceinline__ CrfDetectStep<K> crf_detect_load(const CrfParams &p, const CrfLds &lds, const float *post, const int (&off0)[K],
+                                                            const int (&offy)[K], int t, int i, uint32_t *bad) {
+    CrfDetectStep<K> in;
+    const float *tile_row = lds.tile + i * (p.in.S * p.in.N);
+    const uintptr_t post_row = (uintptr_t)post_at(post, (int64_t)t * p.in.stride_t, p.in.dtype);
+#pragma unroll
+    for (int r = 0; r < K; ++r) {
+        float v0 = 0.0f, vy = 0.0f;
+        if (off0[r] >= 0) {
+            if (STAGED) {
+                v0 = tile_row[off0[r]];
+                vy = tile_row[offy[r]];
+            } else {  // (opaque: the 64-bit sums are formed at the load, not kept in a register pair per value across rows)
+                uint32_t o0 = (uint32_t)off0[r], oy = (uint32_t)offy[r];
+                FCD_OPAQUE_VQ(o0);
+                FCD_OPAQUE_VQ(oy);
+                v0 = load_post_global(post_row + o0, p.in.dtype);
+                vy = load_post_global(post_row + oy, p.in.dtype);
+            }
+        }
+        *bad |= (!(v0 >= 0.0f && v0 - v0 == 0.0f) || !(vy >= 0.0f && vy - vy == 0.0f)) ? 1u : 0u;
+        in.p0[r] = v0;
+        in.py[r] = vy;
+    }
+    return in;
+}
+
+__device__ __forceinline__ float *crf_detect_etile(const CrfLds &lds) {  // (band 0: no k(t) in these 64 words)
+    return reinterpret_cast<float *>(lds.krow);
+}
+
+// the entry weights of rows t0 .. t0 + 63 of the range: lane i sums row t0 + i, in ascending order of the state
+__device__ __forceinline__ void crf_detect_entries(const CrfLds &lds, int t0, int rows, uint32_t *bad) {
+    const int lane = threadIdx.x;
+    __syncthreads();  // the previous 64 words' readers are done (and misc is written)
+    if (t0 + lane < rows) {
+        const int *w = lds.misc;
+        const auto word = [w](int i) { return (int64_t)(((uint64_t)(uint32_t)w[2 * i + 1] << 32) | (uint32_t)w[2 * i]); };
+        const int64_t stride_s = word(2);
+        const float *at = reinterpret_cast<const float *>((uintptr_t)word(0)) + (int64_t)(t0 + lane) * word(1) + (int64_t)w[7] * stride_s;
+        const int64_t step = (int64_t)w[6] * stride_s;
+        float e = 0.0f;
+        for (int d = 0; d < w[8]; ++d, at += step) {
+            const float v = *at;
+            *bad |= !(v >= 0.0f && v - v == 0.0f) ? 1u : 0u;
+            e += v;
+        }
+        crf_detect_etile(lds)[lane] = e;
+    }
+}
+
+// STAGED: CrfParams::staged as a compile-time copy of the function (not of the kernel): each copy keeps one kind of offset
+template <int K, bool STAGED>
+__device__ __forceinline__ void crf_detect_walk(const CrfParams &p, const CrfLds &lds) {
+    const CrfDetectOut *det = p.det;
+    const int lane = threadIdx.x;
+    const int64_t row = blockIdx.x;
+    const int64_t read = row / p.y.n_hyp;
+    const int64_t hyp = row - read * p.y.n_hyp;
+    const double nan = (double)NAN;
+    // the rows without a value, in fcd_crf_score_*'s order
+    if (p.y.n_valid && hyp >= (int64_t)p.y.n_valid[read]) return crf_detect_none(p, nan, nan);
+    int64_t Tr = p.in.lengths ? wave_uniform(p.in.lengths[read]) : p.in.T;
+    Tr = Tr < 0 ? 0 : (Tr > p.in.T ? p.in.T : Tr);
+    const uint32_t len = (uint32_t)wave_uniform((int)p.y.len[row]);
+    if ((int64_t)len > p.y.stride) return crf_detect_none(p, nan, nan);
+    const int L = (int)len;
+    const uint8_t *labels = p.y.labels + row * p.y.stride;
+    if (lane == 0) lds.misc[16] = lds.misc[kBadPost] = 0;
+    __syncthreads();
+    bool bad_label = false;
+    for (int k = lane; k < L; k += 64) {
+        const int y = labels[k];
+        bad_label |= y < 1 || y >= p.in.N;
+    }
+    if (bad_label) lds.misc[16] = 1;
+    __syncthreads();
+    if (lds.misc[16]) return crf_detect_none(p, nan, nan);
+    if (L == 0) return crf_detect_none(p, 0.0, 0.0);
+    const uint32_t *row_begin = wave_uniform(det->row_begin), *row_end = wave_uniform(det->row_end);
+    const int tb = row_begin ? (int)min((int64_t)(uint32_t)wave_uniform((int)row_begin[read]), Tr) : 0;
+    const int te = row_end ? (int)min((int64_t)(uint32_t)wave_uniform((int)row_end[read]), Tr) : (int)Tr;
+    const int rows = te - tb;
+    if (rows <= 0) return crf_detect_none(p, 0.0, -(double)INFINITY);
+    // the entry states d * q + prefix, d = 0 .. ne - 1, and the label they emit; the cells' trajectory, from the motif alone
+    const int S = p.in.S, nb = p.in.N - 1;
+    const int m = p.pow_m > 0 ? p.pow_m : 1;  // (S = 1 walks as m = 1: a state outside the table reads 0)
+    const int h = min(L, m), nc = L - h;
+    int q = 1, prefix = 0;
+    for (int j = 0; j < h - 1; ++j) {
+        prefix = prefix * nb + ((int)labels[j] - 1);
+        q *= nb;
+    }
+    for (int j = lane; j < nc; j += 64) {  // (nc > 0: h = m, so the m labels behind cell k = m + j exist)
+        int64_t s = 0;
+        for (int g = j; g < j + m; ++g) s = s * nb + ((int64_t)labels[g] - 1);
+        lds.info[j] = (s < S ? (uint32_t)s : kNoState) | ((uint32_t)labels[j + m] << 24);
+    }
+    __syncthreads();
+    int off0[K], offy[K];
+    const int esz = p.in.dtype == kF32 ? 4 : 2;
+#pragma unroll
+    for (int r = 0; r < K; ++r) {
+        const uint32_t info = lane * K + r < nc ? lds.info[lane * K + r] : kNoState;
+        const int sig = (int)(info & 0xFFFFFFu), y = (int)(info >> 24);
+        off0[r] = STAGED ? sig * p.in.N : (int)(sig * p.in.stride_s) * esz;
+        offy[r] = off0[r] + (STAGED ? y : (int)(y * p.in.stride_n) * esz);
+        if ((uint32_t)sig == kNoState) off0[r] = offy[r] = -1;
+    }
+    // the entry weights' parameters wait in LDS (misc[0 .. 8], free in a CRF walk): read once per 64 rows, they take no
+    // scalar registers from the row loop
+    if (lane == 0) {
+        const float *marg = det->marg + read * det->marg_stride_read + (int64_t)tb * det->marg_stride_t + labels[h - 1];
+        const int64_t words[3] = {(int64_t)(uintptr_t)marg, det->marg_stride_t, det->marg_stride_s};
+        for (int w = 0; w < 3; ++w) {
+            lds.misc[2 * w] = (int)(uint32_t)words[w];
+            lds.misc[2 * w + 1] = (int)(uint32_t)((uint64_t)words[w] >> 32);
+        }
+        lds.misc[6] = q;
+        lds.misc[7] = prefix;
+        lds.misc[8] = (S - prefix + q - 1) / q;  // the states below S among them: all nb^(m-h+1) where S = nb^m
+    }
+    float *track = wave_uniform(det->track);
+    if (track) track += row * wave_uniform(det->track_stride) + tb;
+    CrfDetectAcc acc{0.0, 0.0f, -1, 0.0f};
+    uint32_t bad = 0;
+    int sc = 0;
+    if (nc == 0) {  // L <= m: c_u = e_u, 64 rows at a time
+        for (int t0 = 0; t0 < rows; t0 += 64) {
+            crf_detect_entries(lds, t0, rows, &bad);
+            __syncthreads();
+            for (int i = 0; i < min(64, rows - t0); ++i) crf_detect_row(track, acc, crf_detect_etile(lds)[i], 0, t0 + i, rows);
+        }
+    } else {
+        sc = kDetScale;
+        CrfRow rw;
+        rw.post = post_at(p.in.post, read * p.in.stride_read + (int64_t)tb * p.in.stride_t, p.in.dtype);
+        rw.path = nullptr;
+        rw.Tr = rows;
+        rw.L = L;
+        const int end_lane = (nc - 1) / K, end_r = (nc - 1) % K;
+        float a[K];
+#pragma unroll
+        for (int r = 0; r < K; ++r) a[r] = 0.0f;
+        for (int t0 = 0; t0 < rows;) {
+            // a tile ends where the staged rows end and where the next 64 entry weights begin
+            const int rc = min(min(p.rows_per_tile, rows - t0), 64 - (t0 & 63));
+            if ((t0 & 63) == 0) crf_detect_entries(lds, t0, rows, &bad);
+            crf_fill_tile(p, lds, rw, t0, rc);  // (its barriers order the 64 words too)
+            CrfDetectStep<K> in = crf_detect_load<K, STAGED>(p, lds, rw.post, off0, offy, t0, 0, &bad);
+            for (int i = 0; i < rc; ++i) {
+                const float e = crf_detect_etile(lds)[(t0 + i) & 63];
+                float s[K], v[K];
+#pragma unroll
+                for (int r = 0; r < K; ++r) {
+                    s[r] = a[r] * in.p0[r];
+                    v[r] = a[r] * in.py[r];
+                }
+                // the next row's posteriors, into the registers the products have just freed: their latency is the rest of this row
+                if (i + 1 < rc) in = crf_detect_load<K, STAGED>(p, lds, rw.post, off0, offy, t0 + i + 1, i + 1, &bad);
+                float mine = 0.0f;
+#pragma unroll
+                for (int r = 0; r < K; ++r)
+                    if (r == end_r) mine = v[r];
+                const float c = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine), end_lane));
+                float v_in = from_prev_lane(v[K - 1]);
+                if (lane == 0) v_in = e * 0x1p64f;  // slot 0's advance is the entry weight, at the walk's scale (exact)
+#pragma unroll
+                for (int r = 0; r < K; ++r) a[r] = s[r] + (r >= 1 ? v[r - 1] : v_in);
+                crf_detect_row(track, acc, c, kDetScale, t0 + i, rows);
+            }
+            t0 += rc;
+        }
+    }
+    if (bad) lds.misc[kBadPost] = 1;
+    __syncthreads();
+    if (lane == 0) {
+        const bool flagged = lds.misc[kBadPost] != 0, hit = acc.bt >= 0;
+        det->count[row] = flagged ? nan : ldexp(acc.sum, -sc);
+        det->end[row] = flagged || !hit ? kCrfNoHit : (uint32_t)(tb + acc.bt);
+        p.logp[row] = flagged ? nan : (hit ? ln_p((double)acc.bv, -sc) : -(double)INFINITY);
+    }
 }
 
 // ---- the LDS-resident window: J = 9 .. 64 states per lane, state k in slot k mod 64J, lane l owns slots lJ .. lJ + J - 1 ----

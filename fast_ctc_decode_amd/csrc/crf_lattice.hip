@@ -21,6 +21,10 @@
 //
 // Align: one back-pointer BIT per row and slot (advance won, strictly), a row is K 64-bit ballots = 8K bytes in the
 // caller's workspace; the workgroup walks them back in the same launch, 64 rows at a time through LDS.
+//
+// Detect (fcd_crf_detect_*): the expected number of occurrences of a motif over all labellings -- crf_detect_walk of
+// crf_lattice.h, a walk of its own (fixed window, fixed scale, entry weights from the edge marginals) compiled into the
+// score's kernels and chosen once, at their top, by CrfParams::det.
 #include <math.h>
 
 #include <algorithm>
@@ -48,6 +52,9 @@ __global__ __launch_bounds__(64) void crf_lattice_kernel(CrfParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int C = 64 * K;
     const CrfLds lds = crf_carve(smem);
+    // fcd_crf_detect_*: a second, compile-time copy of the walk in the score's kernels, chosen ONCE by a pointer that is null
+    // in a score -- whose rows run the instructions they ran before the copy existed
+    if (!MAX && p.det) return p.staged ? crf_detect_walk<K, true>(p, lds) : crf_detect_walk<K, false>(p, lds);
     CrfRow rw;
     if (!crf_prologue(p, lds, &rw)) {
         if (MAX) crf_no_alignment(p);
@@ -140,6 +147,40 @@ hipError_t launch_crf_score(const BatchDesc &in, const ScoreDesc &y, const float
     CrfParams p = crf_params(in, y, init, n_init, init_stride, band);
     p.logp = logp;
     return launch_crf<false>(p, crf_states_per_lane(in.T, y.stride, band), rows, stream);
+}
+
+// fcd_crf_detect_*: m of S = nb^m (S = 1: 1), 0 where S is no such power
+static int crf_detect_history(int64_t S, int64_t N) {
+    if (S == 1) return 1;
+    BatchDesc in{};
+    in.S = (int)S;
+    in.N = (int)N;
+    return crf_params(in, ScoreDesc{}, nullptr, 0, 0, 0).pow_m;
+}
+
+int crf_detect_unsupported(const BatchDesc &in, int64_t stride) {
+    if (in.N - 1 > 8) return 2;
+    if (in.S >= (int)kNoState) return 4;
+    const int m = crf_detect_history(in.S, in.N);
+    if (m == 0) return 1;
+    if (std::max<int64_t>(stride - m + 1, 1) > 512) return 3;
+    // a gathered row: a lane's two byte offsets into it are 32-bit
+    if ((int64_t)in.S * in.N > kTileElems &&
+        (in.stride_s < 0 || in.stride_n < 0 || ((in.S - 1) * in.stride_s + (in.N - 1) * in.stride_n) * 4 >= (1ll << 31))) return 5;
+    return 0;
+}
+
+// K from the L - h + 1 states the longest motif of the call can have (stride - m + 1; its last, cell L, is not walked).
+// lab_cap: a word per cell, whatever T is.
+hipError_t launch_crf_detect(const BatchDesc &in, const ScoreDesc &y, double *logp, hipStream_t stream, const CrfDetectOut *detect) {
+    const int64_t rows = in.n_reads * y.n_hyp;
+    if (rows <= 0) return hipSuccess;
+    CrfParams p = crf_params(in, y, nullptr, 0, 0, 0);
+    p.logp = logp;
+    p.det = detect;
+    p.lab_cap = (int)y.stride + 1;
+    const int64_t states = std::max<int64_t>(y.stride - crf_detect_history(in.S, in.N) + 1, 1);
+    return launch_crf<false>(p, states <= 64 ? 1 : (states <= 128 ? 2 : (states <= 256 ? 4 : 8)), rows, stream);
 }
 
 hipError_t launch_crf_align(const BatchDesc &in, const ScoreDesc &y, const float *init, int64_t n_init, int64_t init_stride,

@@ -69,6 +69,17 @@ __device__ __forceinline__ float load_post(const float *base, int64_t idx, int d
 #define FCD_GLOBAL_F32(addr) (*(const __attribute__((address_space(1))) float *)(addr))
 #endif
 
+// load_post at such an address: a wave-uniform base plus a lane's 32-bit byte offset stays one scalar pair and one VGPR
+__device__ __forceinline__ float load_post_global(uintptr_t addr, int dtype) {
+    if (dtype == kF32) return FCD_GLOBAL_F32(addr);
+#ifdef FCD_HIPEMU
+    const uint16_t h = *reinterpret_cast<const uint16_t *>(addr);
+#else
+    const uint16_t h = *(const __attribute__((address_space(1))) uint16_t *)(addr);
+#endif
+    return dtype == kF16 ? f16_bits_to_f32(h) : bf16_bits_to_f32(h);
+}
+
 // Sort key for the prune step: descending probability, ties -> ascending node index
 // (src/search.rs:245 stable sort by node followed by :262-269 sort by probability; see
 // SURVEY.md 8a A4).  Larger key == earlier in the beam.  prob must not be NaN.

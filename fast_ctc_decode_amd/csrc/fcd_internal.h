@@ -343,6 +343,23 @@ hipError_t launch_crf_score(const BatchDesc &in, const ScoreDesc &y, const float
                             int64_t band, double *logp, hipStream_t stream);
 hipError_t launch_crf_align(const BatchDesc &in, const ScoreDesc &y, const float *init, int64_t n_init, int64_t init_stride,
                             int64_t band, const AlignOut &out, unsigned char *bp, hipStream_t stream);
+// CRF motif occurrence posteriors (crf_lattice.h's crf_detect_walk inside crf_lattice_kernel<false, K>; fcd_crf_detect in
+// include/fcd.h): the outputs, the range of rows of every read and the edge marginals of the launch, a block in DEVICE memory
+// (stream-ordered before the launch), so that a score's kernel arguments grow by one pointer.  `in` holds the transition
+// posteriors; no init row is read.  crf_detect_unsupported: 0 = the kernels hold the call; 1 = S is neither 1 nor a power of
+// N - 1, 2 = more than 8 labels, 3 = stride - m + 1 exceeds the 512 register-resident cells, 4 = S beyond the state word,
+// 5 = a row that is gathered (S * N beyond the tile) spans 2^31 bytes or has a negative stride.
+struct CrfDetectOut {
+    double *count;
+    uint32_t *end;
+    float *track;  // nullable
+    int64_t track_stride;
+    const uint32_t *row_begin, *row_end;  // nullable
+    const float *marg;                    // the first read's marginals, f32; [r][t][s][a] at r * stride_read + t * stride_t + s * stride_s + a
+    int64_t marg_stride_read, marg_stride_t, marg_stride_s;
+};
+int crf_detect_unsupported(const BatchDesc &in, int64_t stride);
+hipError_t launch_crf_detect(const BatchDesc &in, const ScoreDesc &y, double *logp, hipStream_t stream, const CrfDetectOut *detect);
 // CRF forward-backward substitution posteriors of given labellings (crf_posterior.hip; fcd_crf_posterior_* in include/fcd.h),
 // on top of crf_lattice_unsupported.  crf_posterior_unsupported: 0 = the kernels hold the call; 1 = the window exceeds the
 // *max_states register-resident states of the chain's tier, 2 = more than 8 labels, 4 = S is no power of N - 1, 5 = a
@@ -535,6 +552,8 @@ struct fcd_handle {
     bool detect_on = false;   // fcd_set_ctc_detect: fcd_ctc_score_dev detects, with ...
     fcd_detect detect{};      // ... these outputs and ranges next to its own logp
     bool detect_packed = false;  // fcd_set_ctc_detect_packed: the detecting calls take shared motifs, one pair per lane
+    bool crf_detect_on = false;      // fcd_set_crf_detect: fcd_crf_score_dev detects, with ...
+    fcd_crf_detect crf_detect{};     // ... these outputs, ranges and marginals next to its own logp
     int64_t align_ws_cap = 0; // fcd_debug_set_align_workspace_cap: back-pointer bytes one launch of fcd_ctc_align_* may take, 0 = default
     bool is_lane = false;
     uint32_t *duplex_prof = nullptr;  // fcd_debug_set_duplex_profile

@@ -695,6 +695,77 @@ int fcd_crf_align_dev(fcd_handle *h, const fcd_batch *in, const float *init, int
 int fcd_crf_align_host(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init, int64_t init_stride,
                        const fcd_labellings *y, int64_t band, const fcd_alignment *out);
 
+/* ---- CRF motif occurrence posteriors: expected counts under the CRF (csrc/crf_lattice.h, crf_detect_walk) ----
+ * NOT a reference function.  fcd_ctc_detect_*'s question -- does this motif occur in this read, and where -- for a CRF
+ * model, answered as an exact expectation: the model state carries the last m labels, so there is no free start, but the
+ * edge marginals of fcd_crf_marginals_* say how probable it is to be in any state at any row over ALL labellings.
+ * Inputs per read r:
+ *   p    = in: the locally normalised transition posteriors of fcd_crf_transition_probs_*, p[t][s][a], source-indexed;
+ *          fcd_crf_score_*'s batch (f32 / f16 / bf16, any strides, ragged lengths).  No init row is read.
+ *   marg = out->marg: fcd_crf_marginals_*'s edge marginals of the same scores, f32; marg[r][t][s][a] at
+ *          r * marg_stride_read + t * marg_stride_t + s * marg_stride_s + a (a time-major buffer is a pair of strides).
+ *   nb = N - 1, S = nb^m (S = 1 walks as m = 1; a state outside 0 .. S-1 reads as 0, fcd_crf_score_*'s rule).
+ *   A motif y_0 .. y_(L-1), L >= 1, labels 1 .. N-1 (labelling i of read r, row = r * n_hyp + i; `path` unused), and the
+ *   read's range of rows [b, e): row_begin / row_end as fcd_spot defines them.
+ * Let h = min(L, m).
+ *   entry       the model emits y_(h-1) at row u from a state whose last h - 1 labels are y_0 .. y_(h-2):
+ *               e_u = sum of marg[u][sigma][y_(h-1)] over the nb^(m-h+1) states sigma = d * nb^(h-1) + prefix, d ascending,
+ *               prefix = sum_{j < h-1} (y_j - 1) nb^(h-2-j).  For L >= m these are nb states.
+ *   trajectory  fixed by the motif alone (no init row): sigma_m = sum_{j < m} (y_j - 1) nb^(m-1-j), then
+ *               sigma_(k+1) = (sigma_k nb) mod S + (y_k - 1), fcd_crf_score_*'s rule.
+ *   recurrence  over the rows u in [b, e) and the cells k = h .. L - 1 ("k labels of the motif emitted"), a_(b-1) = 0:
+ *               a_u[h] = a_(u-1)[h] * p[u][sigma_h][0] + e_u
+ *               a_u[k] = a_(u-1)[k] * p[u][sigma_k][0] + a_(u-1)[k-1] * p[u][sigma_(k-1)][y_(k-1)]      for k > h
+ *   exit        cell L is not walked: c_u = a_(u-1)[L-1] * p[u][sigma_(L-1)][y_(L-1)] for L > h; c_u = e_u for L = h (no
+ *               walk at all when L <= m).
+ * Meaning.  p is the probability of an edge given its source state, marg the joint probability of being there and taking
+ * it.  So c_u is exactly the probability, over all labellings and alignments, that an occurrence of the motif -- a run of
+ * consecutive emitted labels -- has its last label emitted at row u and its h-th label emitted inside the range; the
+ * events for different rows are disjoint per occurrence, and count = sum_u c_u is the EXPECTED NUMBER OF OCCURRENCES,
+ * overlapping ones included: no boundary approximation (fcd_ctc_detect_*'s g_b = 1 and 1 - p weights have no counterpart).
+ * The pseudo-history of the model's start state counts as labels, as in every CRF entry point here: an occurrence may
+ * begin in it (its first h - 1 labels, never its h-th).
+ * Per labelling row, with fcd_detect's shapes and types:
+ *   count[row]   sum_u c_u, float64, accumulated in row order: the same bits on every call.  Not null.
+ *   end  [row]   argmax_u c_u, ties to the earliest row; 0xFFFFFFFF where every c_u is 0.  Not null.
+ *   logp [row]   ln c_end, float64.  Nullable.
+ *   track[row * track_stride + u]   ln c_u in f32 for u in [b, e), -inf where c_u = 0; rows outside the range are not
+ *                written.  Nullable; track_stride >= in->T.
+ * Arithmetic: f32, one rounding per product and per sum, no fused multiply-add; e_u is summed in f32 in ascending order
+ * of the state.  The cells carry a FIXED factor 2^64 instead of a per-row exponent (a cell is a probability, e_u at most
+ * nb^(m-h+1) < 2^24, so T * S < 2^55 of them cannot overflow): a cell below 2^-190 as a probability loses bits and one
+ * below 2^-213 counts as 0.  Inputs that are not probabilities (marg or p above 1) give some value.
+ * Rows without a value, tested in this order: i >= n_valid[r], len > stride, a label outside 1 .. N-1: count = logp = NaN;
+ * L = 0: count = 0, logp = 0; an empty range: count = 0, logp = -inf; a NaN, infinite or negative value among those the
+ * walk reads in the range (the marg entries of e_u, p[u][sigma_k][0] and p[u][sigma_k][y_k] of every cell): count = logp =
+ * NaN, the track's values undefined; c_u = 0 everywhere (a range shorter than L - h + 1 rows included): count = 0,
+ * logp = -inf.  In all of them end = 0xFFFFFFFF, and only the last two kinds of row write the track.
+ * FCD_E_INVALID before anything is enqueued: band != 0, a null out, count, end or marg, a negative marg stride, track
+ * given with track_stride < in->T, and fcd_crf_score_*'s cases but for init.  FCD_E_UNSUPPORTED (the message says which):
+ * S neither 1 nor a power of N - 1; N - 1 > 8; stride - m + 1 > 512 (the cells live in registers, 64 x 8: motifs up to
+ * 511 + m labels); S >= 2^24 - 1.  The workspace: 256 bytes of parameters, and logp where it is null.
+ * Out of scope: the best single occurrence (a crf_spot), a packed one-pair-per-lane form, bands, f16 marginals. */
+typedef struct fcd_crf_detect {
+    double   *count;            /* [n_reads * n_hyp] */
+    uint32_t *end;              /* [n_reads * n_hyp] */
+    double   *logp;             /* [n_reads * n_hyp], nullable */
+    float    *track;            /* [n_reads * n_hyp * track_stride], nullable */
+    int64_t   track_stride;
+    const uint32_t *row_begin;  /* [n_reads], nullable */
+    const uint32_t *row_end;    /* [n_reads], nullable */
+    const float *marg;          /* the edge marginals, f32 */
+    int64_t   marg_stride_read, marg_stride_t, marg_stride_s;  /* in elements */
+} fcd_crf_detect;
+int fcd_crf_detect_host(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int64_t band, const fcd_crf_detect *out);
+/* Device arrays: a handle switch in front of the score's own device entry point, as fcd_set_ctc_detect is in front of
+ * fcd_ctc_score_dev.  fcd_set_crf_detect(h, detect) copies *detect into the handle; while it is set, fcd_crf_score_dev on
+ * that handle IS the detecting call: its init arguments are ignored and may be null, band must be 0, ln c_end is written
+ * through the call's own logp (detect->logp is ignored), everything else comes from *detect.  detect = NULL turns it off.
+ * fcd_crf_score_host is not affected.  The threading caveat is fcd_set_ctc_spot's: between setting and clearing the switch
+ * the handle must not be shared with another thread; the Python layer sets, calls and clears on the calling thread's own
+ * handle. */
+int fcd_set_crf_detect(fcd_handle *h, const fcd_crf_detect *detect);
+
 /* ---- CRF forward-backward substitution posteriors of given labellings (csrc/crf_posterior.hip) ----
  * NOT a reference function.  Everything is as fcd_crf_score_* defines it: batch (n_reads, T, S, N), init, nb = N - 1, the
  * trajectory sigma_0 = first maximum of the init row, sigma_{k+1} = (sigma_k * nb) mod S + (y_k - 1), the reading rule
