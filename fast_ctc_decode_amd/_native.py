@@ -57,7 +57,7 @@ SYMBOLS = [
     "fcd_ctc_posterior_dev", "fcd_ctc_posterior_host",
     "fcd_ctc_edits_dev", "fcd_ctc_edits_host",
     "fcd_crf_score_dev", "fcd_crf_score_host", "fcd_crf_align_dev", "fcd_crf_align_host",
-    "fcd_crf_detect_host", "fcd_set_crf_detect",
+    "fcd_crf_detect_host", "fcd_set_crf_detect", "fcd_crf_spot_host", "fcd_set_crf_spot",
     "fcd_crf_posterior_dev", "fcd_crf_posterior_host", "fcd_crf_edits_dev", "fcd_crf_edits_host",
     "fcd_crf_viterbi_search_dev", "fcd_crf_viterbi_search_host",
     "fcd_crf_transition_probs_dev", "fcd_crf_transition_probs_host",
@@ -118,6 +118,12 @@ class CrfDetect(C.Structure):
     """fcd_crf_detect: fcd_detect's members, then the edge marginals and their strides in elements (include/fcd.h)."""
     _fields_ = Detect._fields_ + [("marg", C.c_void_p), ("marg_stride_read", C.c_int64), ("marg_stride_t", C.c_int64),
                                   ("marg_stride_s", C.c_int64)]
+
+
+class CrfSpot(C.Structure):
+    """fcd_crf_spot: fcd_spot's members, then the hit's first row, the edge marginals and their strides in elements (include/fcd.h)."""
+    _fields_ = Spot._fields_ + [("first", C.c_void_p), ("marg", C.c_void_p), ("marg_stride_read", C.c_int64),
+                                ("marg_stride_t", C.c_int64), ("marg_stride_s", C.c_int64)]
 
 
 class Posterior(C.Structure):
@@ -314,13 +320,15 @@ def bind(lib):
         for kind, out in LATTICE_OUT.items():
             for sfx in ("dev", "host"):
                 getattr(lib, "fcd_%s_%s_%s" % (model, kind, sfx)).argtypes = head + [C.POINTER(out) if out else P]
-    lib.fcd_ctc_spot_host.argtypes = [P, BP, LP, i32, i64, C.POINTER(Spot)]  # (CTC only: no CRF counterpart)
+    lib.fcd_ctc_spot_host.argtypes = [P, BP, LP, i32, i64, C.POINTER(Spot)]  # (the CRF counterpart: fcd_crf_spot_host below)
     lib.fcd_set_ctc_spot.argtypes = [P, C.POINTER(Spot)]  # (device arrays: fcd_ctc_align_dev under this switch)
     lib.fcd_ctc_detect_host.argtypes = [P, BP, LP, i32, i64, C.POINTER(Detect)]  # (CTC only)
     lib.fcd_set_ctc_detect.argtypes = [P, C.POINTER(Detect)]  # (device arrays: fcd_ctc_score_dev under this switch)
     lib.fcd_set_ctc_detect_packed.argtypes = [P, i32]
     lib.fcd_crf_detect_host.argtypes = [P, BP, LP, i64, C.POINTER(CrfDetect)]  # (no init row)
     lib.fcd_set_crf_detect.argtypes = [P, C.POINTER(CrfDetect)]  # (device arrays: fcd_crf_score_dev under this switch)
+    lib.fcd_crf_spot_host.argtypes = [P, BP, LP, i64, C.POINTER(CrfSpot)]  # (no init row)
+    lib.fcd_set_crf_spot.argtypes = [P, C.POINTER(CrfSpot)]  # (device arrays: fcd_crf_align_dev under this switch)
     lib.fcd_debug_set_align_workspace_cap.argtypes = [P, i64]
     lib.fcd_debug_workspace_bytes.argtypes = [P]
     lib.fcd_debug_workspace_bytes.restype = i64

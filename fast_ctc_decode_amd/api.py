@@ -1954,7 +1954,19 @@ def _crf_detect_out(xp, b, shape, marginals=None, **detect_args):
     """_detect_out's arrays, and the edge marginals: a float32 (B, T, S, N) array where the posteriors live, (S, N) rows
     dense in N"""
     _, result = _detect_out(xp, b, shape, **detect_args)
-    want = (shape[0], int(b.T), int(b.S), int(b.N))
+    marg, st = _crf_marginals_arg(xp, b, shape, marginals)
+    begin, stop = result._rows
+    out = nat.CrfDetect(xp.ptr(result.count), xp.ptr(result.end), xp.ptr(result.logp),
+                        xp.ptr(result.track) if result.track is not None else None, int(b.T),
+                        xp.ptr(begin) if begin is not None else None, xp.ptr(stop) if stop is not None else None,
+                        xp.ptr(marg), st[0], st[1], st[2])
+    result._marginals = marg  # (alive as long as the result)
+    return C.byref(out), result
+
+
+def _crf_marginals_arg(xp, b, shape, marginals):
+    """the edge marginals of the CRF motif calls: a float32 (B, T, S, N) array where the posteriors live, (S, N) rows dense
+    in N -> (array, its strides in elements)"""
     if xp.dev is None:
         marg = np.asarray(marginals, np.float32)
         marg = marg if marg.ndim == 4 and marg.strides[3] == 4 and min(marg.strides) >= 0 else np.ascontiguousarray(marg)
@@ -1964,13 +1976,23 @@ def _crf_detect_out(xp, b, shape, marginals=None, **detect_args):
         marg = torch.as_tensor(marginals, dtype=torch.float32, device=xp.dev)
         marg = marg if marg.ndim == 4 and marg.stride(3) == 1 else marg.contiguous()
         st = tuple(marg.stride())
-    if tuple(marg.shape) != want:
+    if tuple(marg.shape) != (shape[0], int(b.T), int(b.S), int(b.N)):
         raise ValueError("marginals must have the posteriors' shape (n_reads, T, S, N)")
-    begin, stop = result._rows
-    out = nat.CrfDetect(xp.ptr(result.count), xp.ptr(result.end), xp.ptr(result.logp),
-                        xp.ptr(result.track) if result.track is not None else None, int(b.T),
-                        xp.ptr(begin) if begin is not None else None, xp.ptr(stop) if stop is not None else None,
-                        xp.ptr(marg), st[0], st[1], st[2])
+    return marg, st
+
+
+def _crf_spot_out(xp, b, shape, marginals=None, lengths=None, rows=None, track=False, spans=False):
+    """fcd_crf_spot's arrays: end, first and logp always; the track and the spans (start, count, qual) on request"""
+    al = AlignResult(xp.zeros(shape, "u32"), xp.zeros(shape, "u32"), xp.zeros(shape, "f32"), xp.empty(shape[:2], "f64")) if spans else None
+    logp = al.logp if spans else xp.empty(shape[:2], "f64")
+    end, first = xp.empty(shape[:2], "u32"), xp.empty(shape[:2], "u32")
+    trk = xp.full(shape[:2] + (int(b.T),), "f32", -math.inf) if track else None  # (rows outside the range stay -inf)
+    begin, stop = _spot_rows(xp, b, shape[0], lengths, rows)
+    marg, st = _crf_marginals_arg(xp, b, shape, marginals)
+    ptr = lambda a: None if a is None else xp.ptr(a)  # noqa: E731
+    out = nat.CrfSpot(*([ptr(al.start), ptr(al.count), ptr(al.qual)] if spans else [None] * 3), ptr(logp), ptr(end), ptr(trk),
+                      int(b.T), ptr(begin), ptr(stop), ptr(first), ptr(marg), st[0], st[1], st[2])
+    result = SpotResult(al, end, trk, (begin, stop), first=first, logp=logp)
     result._marginals = marg  # (alive as long as the result)
     return C.byref(out), result
 
@@ -2048,7 +2070,8 @@ def _occupancy_out(xp, b, shape, has_S, out=None, scale=1.0, accumulate=False, t
 
 
 _LATTICE_BUILDERS = {"score": _score_out, "align": _align_out, "posterior": _posterior_out, "edits": _edits_out,
-                     "occupancy": _occupancy_out, "spot": _spot_out, "detect": _detect_out, "crf_detect": _crf_detect_out}
+                     "occupancy": _occupancy_out, "spot": _spot_out, "detect": _detect_out, "crf_detect": _crf_detect_out,
+                     "crf_spot": _crf_spot_out}
 
 
 @contextlib.contextmanager
@@ -2071,7 +2094,7 @@ def _lattice_call(model, kind, network_outputs, labels, label_lengths, lengths, 
                   init_states=None, collapse_repeats=True, wide=False, packed=False, **out_args):
     """The one body of the labelling-lattice calls: fcd_<model>_<kind>_dev for device tensors, _host for numpy, with
     model "ctc" (network_outputs (B,T,N), collapse_repeats) or "crf" ((B,T,S,N) and init_states), kind one of
-    _LATTICE_BUILDERS ("spot": CTC only; "detect" under "crf": _crf_detect_out, marginals in place of init_states); out_args: the occupancy calls' out, scale, accumulate and
+    _LATTICE_BUILDERS ("spot" and "detect" under "crf": _crf_spot_out and _crf_detect_out, marginals in place of init_states); out_args: the occupancy calls' out, scale, accumulate and
     time_major_out, the spotting and detecting calls' rows and track.  packed ("detect"): labels and label_lengths are
     motifs shared by all reads, under the handle's fcd_set_ctc_detect_packed.  -> what the call returns."""
     band = _check_band(band, paths)
@@ -2083,9 +2106,9 @@ def _lattice_call(model, kind, network_outputs, labels, label_lengths, lengths, 
     xp = _Arrays(dev)
     if kind in ("spot", "detect"):
         out_args["lengths"] = keep.lengths  # (rows counts from every read's own length)
-    crf_detect = model == "crf" and kind == "detect"
-    out, result = _LATTICE_BUILDERS["crf_detect" if crf_detect else kind](xp, b, shape, **out_args)
-    if crf_detect:  # (no init row: the device call passes none, the host call has no such arguments)
+    crf_detect, crf_spot = model == "crf" and kind == "detect", model == "crf" and kind == "spot"
+    out, result = _LATTICE_BUILDERS["crf_" + kind if crf_detect or crf_spot else kind](xp, b, shape, **out_args)
+    if crf_detect or crf_spot:  # (no init row: the device call passes none, the host call has no such arguments)
         args = (C.byref(b), None, 0, 0, C.byref(y), band, out) if dev is not None else (C.byref(b), C.byref(y), band, out)
     elif model == "crf":
         init = keep[-1]
@@ -2098,7 +2121,7 @@ def _lattice_call(model, kind, network_outputs, labels, label_lengths, lengths, 
                                           "host" if dev is None else "dev"))
     with _wide_switch(h, model, wide):
         if spot_dev:
-            h.check(h.lib.fcd_set_ctc_spot(h.ptr, out))
+            h.check((h.lib.fcd_set_crf_spot if crf_spot else h.lib.fcd_set_ctc_spot)(h.ptr, out))
             args = args[:-1] + (C.cast(out, C.POINTER(nat.Alignment)),)  # (fcd_spot begins with fcd_alignment's four pointers)
         if detect_dev:
             h.check((h.lib.fcd_set_crf_detect if crf_detect else h.lib.fcd_set_ctc_detect)(h.ptr, out))
@@ -2111,7 +2134,7 @@ def _lattice_call(model, kind, network_outputs, labels, label_lengths, lengths, 
             if packed:
                 h.set_ctc_detect_packed(False)
             if spot_dev:
-                h.lib.fcd_set_ctc_spot(h.ptr, None)
+                (h.lib.fcd_set_crf_spot if crf_spot else h.lib.fcd_set_ctc_spot)(h.ptr, None)
             if detect_dev:
                 (h.lib.fcd_set_crf_detect if crf_detect else h.lib.fcd_set_ctc_detect)(h.ptr, None)
     if kind == "occupancy" and dev is not None:
@@ -2232,14 +2255,20 @@ class SpotResult:
     none), logp[r, i] (float64) is ln of its probability, mean_logp[r, i] = logp / (end - start + 1) the same per row;
     spans is the hit's AlignResult (start, count, qual of every label of the motif, (B, M, stride)); track[r, i, t]
     (float32, (B, M, T), None unless asked for) is ln of the best hit that ENDS at row t, -inf where there is none and
-    outside the range.  numpy for host inputs, torch tensors (same device) for device inputs."""
+    outside the range.  numpy for host inputs, torch tensors (same device) for device inputs.
 
-    def __init__(self, spans, end, track, rows=(None, None)):
-        self.spans, self.end, self.track, self.logp = spans, end, track, spans.logp
+    crf_spot_batch_raw: start[r, i] is the emission row of label min(L, m) - 1 of the motif, the hit's first LOCATED row
+    (the labels before it lie in the model's history); spans is None unless asked for."""
+
+    def __init__(self, spans, end, track, rows=(None, None), first=None, logp=None):
+        self.spans, self.end, self.track, self.logp = spans, end, track, spans.logp if logp is None else logp
         self._rows = rows  # (row_begin, row_end): alive as long as the result
+        self._first = first  # (crf_spot_batch_raw) the hit's first row as the call wrote it, NO_HIT where there is none
 
     @property
     def start(self):
+        if self._first is not None:
+            return self._first
         first = self.spans.start[..., 0]
         if isinstance(first, np.ndarray):
             return np.where(self.end == NO_HIT, self.end, first)
@@ -2253,7 +2282,10 @@ class SpotResult:
 
     def cpu(self):
         end = _to_host(self.end)
-        return SpotResult(self.spans.cpu(), end if end.dtype == np.uint32 else end.view(np.uint32), _to_host(self.track))
+        first = None if self._first is None else _to_host(self._first)
+        return SpotResult(None if self.spans is None else self.spans.cpu(), end if end.dtype == np.uint32 else end.view(np.uint32),
+                          _to_host(self.track), first=first if first is None or first.dtype == np.uint32 else first.view(np.uint32),
+                          logp=_to_host(self.logp))
 
 
 def ctc_spot_batch_raw(network_outputs, motifs, motif_lengths, collapse_repeats=True, lengths=None, rows=None,
@@ -2398,6 +2430,54 @@ def crf_detect(scores, motif, alphabet, rows=None):
     r = crf_detect_batch_raw(tr.probs, mg.marginals, lab, np.array([len(y)], np.uint32), rows=rows)
     end = int(r.end[0, 0])
     return float(r.count[0, 0]), (None if end == NO_HIT else end), float(r.logp[0, 0])
+
+
+# ---------------------------------------------------------------------------------------------
+# CRF motif spotting: the best single occurrence and its rows under the CRF (include/fcd.h, fcd_crf_spot_*)
+# ---------------------------------------------------------------------------------------------
+def crf_spot_batch_raw(probs, marginals, motifs, motif_lengths, lengths=None, rows=None, track=False, spans=False,
+                       input_dtype=None, handle=None):
+    """CRF motif spotting: where the best single occurrence of each of M known sequences sits in every read -- its first
+    and last row and ln of its probability, the CRF counterpart of ctc_spot_batch_raw with no boundary approximation
+    (include/fcd.h, fcd_crf_spot_*).  -> SpotResult, arrays (B, M[, ...]).
+
+    probs, marginals, motifs, motif_lengths, lengths and rows as crf_detect_batch_raw takes them.  start[r, i] is the row
+    that emits label min(L, m) - 1 of the motif (S = (N-1)^m: the labels before it lie in the model's history and are not
+    located), end[r, i] the row that emits its last label, both NO_HIT where there is no hit; mean_logp compares motifs
+    of different lengths.  track=True also returns ln of the best occurrence ending at every row.  spans=True also
+    returns the emission row of every located label and its quality as an AlignResult (.spans; None otherwise) -- only
+    then does the call take workspace that grows with T x motifs x reads.  Device tensors in: torch tensors on the same
+    device, enqueued on torch's current stream, not synchronised.  numpy in: numpy out."""
+    m = np.asarray(_to_host(motifs), np.uint8)
+    if m.ndim != 2:
+        raise ValueError("motifs must have shape (n_motifs, stride)")
+    if rows is not None and (not isinstance(rows, (tuple, list)) or len(rows) != 2):
+        raise ValueError("rows must be a pair (lo, hi)")
+    B = len(probs)
+    n = np.asarray(_to_host(motif_lengths), np.uint32).reshape(-1)
+    if n.size != m.shape[0]:
+        raise ValueError("motif_lengths must have one entry per motif")
+    return _lattice_call("crf", "spot", probs, np.tile(m[None], (B, 1, 1)), np.tile(n[None], (B, 1)), lengths, None, 0,
+                         None, input_dtype, handle, rows=rows, track=bool(track), spans=bool(spans), marginals=marginals)
+
+
+def crf_spot(scores, motif, alphabet, rows=None):
+    """Where one string sits in one read, from the network's raw (T, S, N) float32 CRF scores: -> (start, end, logp), the
+    first located and the last row (inclusive) of its best occurrence and ln of that alignment's probability; None where
+    there is none.  Calls crf_transition_probs and crf_marginals itself.  rows=(lo, hi): look in scores[lo:hi] only."""
+    x = _as_f32(scores, 3, "scores")
+    alpha = _seq_to_vec(alphabet)
+    _check_greedy_alphabet(len(alpha), x.shape[2])
+    y = _crf_sequence_labels(motif, alpha, "crf_spot")
+    lab = np.zeros((1, max(len(y), 1)), np.uint8)
+    lab[0, :len(y)] = y
+    tr = crf_transition_probs_batch_raw(_dense(x)[None])
+    _raise_status(int(tr.status[0]))
+    mg = crf_marginals_batch_raw(_dense(x)[None], emit=False)
+    r = crf_spot_batch_raw(tr.probs, mg.marginals, lab, np.array([len(y)], np.uint32), rows=rows)
+    if int(r.end[0, 0]) == NO_HIT:
+        return None
+    return int(r.start[0, 0]), int(r.end[0, 0]), float(r.logp[0, 0])
 
 
 # ---------------------------------------------------------------------------------------------

@@ -1950,6 +1950,9 @@ struct LatticeCall {
     // (CRF detect) fcd_crf_detect_*: `detect` holds its first seven members, these the edge marginals; no init is read
     const float *marg = nullptr;
     int64_t marg_stride_read = 0, marg_stride_t = 0, marg_stride_s = 0;
+    // (CRF align) fcd_crf_spot_*: `out` holds its first four pointers (start, count, qual all null: no spans), the marginals
+    // are above; no init is read
+    const fcd_crf_spot *cspot = nullptr;
 };
 
 // the labellings y->labels / y->len describe: one per (read, hypothesis), or (packed) the n_hyp shared motifs
@@ -1988,6 +1991,7 @@ int lattice_check(fcd_handle *h, const LatticeCall &c) {
     if (c.detect && c.band != 0)
         return fail(h, FCD_E_INVALID, c.crf ? "crf_detect: band must be 0 (the motif is looked for over all labellings)"
                                             : "ctc_detect: band must be 0 (the motif is looked for in the exact lattice)");
+    if (c.cspot && c.band != 0) return fail(h, FCD_E_INVALID, "crf_spot: band must be 0 (the motif is looked for over all labellings)");
     if (c.posterior && !c.post) return fail(h, FCD_E_INVALID, "null posterior");
     if (c.edit && !c.edits) return fail(h, FCD_E_INVALID, c.crf ? "crf_edits: null output" : "ctc_edits: null output");
     const std::string occ_who = c.crf ? "crf_occupancy" : (c.wide ? "ctc_occupancy_wide" : "ctc_occupancy");
@@ -1996,9 +2000,11 @@ int lattice_check(fcd_handle *h, const LatticeCall &c) {
     const fcd_labellings *y = c.y;
     int rc = check_batch(h, in, c.crf);
     if (rc) return rc;
-    if (c.crf && c.detect) {  // (no init row is read)
-        if (in->n_reads > 0 && !c.marg) return fail(h, FCD_E_INVALID, "crf_detect: null marg");
-        if (c.marg_stride_read < 0 || c.marg_stride_t < 0 || c.marg_stride_s < 0) return fail(h, FCD_E_INVALID, "crf_detect: negative marg stride");
+    const bool crf_motif = c.crf && (c.detect || c.cspot);  // fcd_crf_detect_* / fcd_crf_spot_*: one set of inputs and limits
+    const std::string motif_who = c.cspot ? "crf_spot" : "crf_detect";
+    if (crf_motif) {  // (no init row is read)
+        if (in->n_reads > 0 && !c.marg) return fail(h, FCD_E_INVALID, (motif_who + ": null marg").c_str());
+        if (c.marg_stride_read < 0 || c.marg_stride_t < 0 || c.marg_stride_s < 0) return fail(h, FCD_E_INVALID, (motif_who + ": negative marg stride").c_str());
     } else if (c.crf) {
         if (!c.init || c.n_init < 1) return fail(h, FCD_E_INVALID, "init_state missing");
         if (c.init_stride < 0) return fail(h, FCD_E_INVALID, "negative stride");
@@ -2020,9 +2026,9 @@ int lattice_check(fcd_handle *h, const LatticeCall &c) {
     }
     if (in->n_reads > 0 && (!y->labels || !y->len ||
                             !(c.occupancy ? (const void *)c.occ->occ : c.edit ? (const void *)c.edits->deletion : c.posterior ? (const void *)c.post->post
-                              : c.align ? (const void *)c.out->start : c.detect ? (const void *)c.detect->count : (const void *)c.logp)))
+                              : c.cspot ? (const void *)c.cspot->end : c.align ? (const void *)c.out->start : c.detect ? (const void *)c.detect->count : (const void *)c.logp)))
         return fail(h, FCD_E_INVALID, c.occupancy ? (c.crf ? "crf_occupancy: null labels/len/occ" : c.wide ? "ctc_occupancy_wide: null labels/len/occ" : "ctc_occupancy: null labels/len/occ") : c.edit ? (c.crf ? "crf_edits: null labels/len/deletion" : "ctc_edits: null labels/len/deletion") : c.posterior ? "null labels/len/post"
-                                      : c.align ? "null labels/len/start" : c.detect ? (c.crf ? "crf_detect: null labels/len/count" : "ctc_detect: null labels/len/count") : "null labels/len/logp");
+                                      : c.cspot ? "crf_spot: null labels/len/end" : c.align ? "null labels/len/start" : c.detect ? (c.crf ? "crf_detect: null labels/len/count" : "ctc_detect: null labels/len/count") : "null labels/len/logp");
     if (c.edit && in->n_reads > 0 && !c.edits->insertion) return fail(h, FCD_E_INVALID, c.crf ? "crf_edits: null insertion" : "ctc_edits: null insertion");
     if (in->n_reads * y->n_hyp >= (1ll << 31)) return fail(h, FCD_E_UNSUPPORTED, "more than 2^31 labellings in one call");
     if (c.crf && crf_wide_call(c)) {
@@ -2038,13 +2044,13 @@ int lattice_check(fcd_handle *h, const LatticeCall &c) {
                                                    (c.occupancy ? " + 4 S N" : "") + " = " + std::to_string(lds) + " bytes): use a band or a smaller stride").c_str());
         default: break;
         }
-    } else if (c.crf && c.detect) {
+    } else if (crf_motif) {
         switch (crf_detect_unsupported(to_desc(in, true), y->stride)) {
-        case 1: return fail(h, FCD_E_UNSUPPORTED, "crf_detect: S must be a power of N - 1 (the model state is the last labels)");
-        case 2: return fail(h, FCD_E_UNSUPPORTED, "crf_detect: more than 8 labels besides the blank");
-        case 3: return fail(h, FCD_E_UNSUPPORTED, "crf_detect: motifs beyond 511 + m labels (S = (N - 1)^m) exceed the 512 register-resident cells: use a smaller stride");
-        case 4: return fail(h, FCD_E_UNSUPPORTED, "crf_detect: S must be below 2^24 - 1");
-        case 5: return fail(h, FCD_E_UNSUPPORTED, "crf_detect: a row of more than 1024 values must span less than 2^31 bytes, with no negative stride");
+        case 1: return fail(h, FCD_E_UNSUPPORTED, (motif_who + ": S must be a power of N - 1 (the model state is the last labels)").c_str());
+        case 2: return fail(h, FCD_E_UNSUPPORTED, (motif_who + ": more than 8 labels besides the blank").c_str());
+        case 3: return fail(h, FCD_E_UNSUPPORTED, (motif_who + ": motifs beyond 511 + m labels (S = (N - 1)^m) exceed the 512 register-resident cells: use a smaller stride").c_str());
+        case 4: return fail(h, FCD_E_UNSUPPORTED, (motif_who + ": S must be below 2^24 - 1").c_str());
+        case 5: return fail(h, FCD_E_UNSUPPORTED, (motif_who + ": a row of more than 1024 values must span less than 2^31 bytes, with no negative stride").c_str());
         default: break;
         }
     } else if (c.crf) {
@@ -2059,7 +2065,14 @@ int lattice_check(fcd_handle *h, const LatticeCall &c) {
         return fail(h, FCD_E_UNSUPPORTED, c.band > 0 ? "ctc_score: the band's window does not fit the 160 KiB of LDS: use a narrower band"
                                                      : "ctc_score: the exact lattice does not fit the 160 KiB of LDS: use a band");
     }
-    if (c.align && in->n_reads > 0 && !c.out->count) return fail(h, FCD_E_INVALID, "null count");
+    if (c.cspot) {
+        const int given = (c.out->start != nullptr) + (c.out->count != nullptr) + (c.out->qual != nullptr);
+        if (given != 0 && given != 3) return fail(h, FCD_E_INVALID, "crf_spot: start, count and qual are given together or not at all");
+        if (in->n_reads > 0 && !c.cspot->first) return fail(h, FCD_E_INVALID, "crf_spot: null first");
+        if (c.cspot->track && c.cspot->track_stride < in->T) return fail(h, FCD_E_INVALID, "crf_spot: track_stride must hold the T rows of a read");
+    } else if (c.align && in->n_reads > 0 && !c.out->count) {
+        return fail(h, FCD_E_INVALID, "null count");
+    }
     if (c.spot && in->n_reads > 0 && !c.spot->end) return fail(h, FCD_E_INVALID, "ctc_spot: null end");
     if (c.spot && c.spot->track && c.spot->track_stride < in->T) return fail(h, FCD_E_INVALID, "ctc_spot: track_stride must hold the T rows of a read");
     if (c.detect && in->n_reads > 0 && !c.detect->end) return fail(h, FCD_E_INVALID, c.crf ? "crf_detect: null end" : "ctc_detect: null end");
@@ -2260,10 +2273,12 @@ int lattice_align(fcd_handle *h, const LatticeCall &c) {
     const size_t cells = (size_t)in->n_reads * (size_t)y->n_hyp * (size_t)y->stride;
     // (the CTC kernels size their rows by the band as given, the CRF kernels by the band the launch gets)
     const int64_t bnd = std::min<int64_t>(c.band, 1ll << 28);
-    const size_t row_bytes = c.crf ? crf_align_row_bytes(in->T, y->stride, bnd) : ctc_align_row_bytes(in->T, y->stride, c.band);
+    const fcd_crf_spot *cs = c.cspot;  // (no spans: no back-pointers, one group)
+    const size_t row_bytes = cs ? (out->start ? crf_spot_row_bytes(to_desc(in, true), y->stride) : 0)
+                             : c.crf ? crf_align_row_bytes(in->T, y->stride, bnd) : ctc_align_row_bytes(in->T, y->stride, c.band);
     const int64_t cap = h->align_ws_cap > 0 ? h->align_ws_cap : std::min<int64_t>(4ll << 30, workspace_budget(h));
     const fcd_spot *s = c.spot;
-    char *block = nullptr;  // (spotting) the SpotOut of the group being launched, in the workspace
+    char *block = nullptr;  // (spotting) the SpotOut / CrfSpotOut of the group being launched, in the workspace
     return lattice_grouped(
         h, c, row_bytes, cap, out->logp,
         [&](CallScope &sc) {
@@ -2276,16 +2291,32 @@ int lattice_align(fcd_handle *h, const LatticeCall &c) {
                 sc.add(s->row_begin, (size_t)in->n_reads * 4);
                 sc.add(s->row_end, (size_t)in->n_reads * 4);
             }
+            if (cs) {
+                sc.add(cs->end, (size_t)in->n_reads * (size_t)y->n_hyp * 4);
+                sc.add(cs->first, (size_t)in->n_reads * (size_t)y->n_hyp * 4);
+                sc.add(cs->track, track_floats(in, y, cs->track, cs->track_stride) * 4);
+                sc.add(cs->row_begin, (size_t)in->n_reads * 4);
+                sc.add(cs->row_end, (size_t)in->n_reads * 4);
+                sc.add(c.marg, marg_span(c) * 4);
+            }
         },
         [&](const BatchDesc &d, const ScoreDesc &yd, int64_t r0, int64_t row0, double *logp, unsigned char *bp, hipStream_t stream) {
-            const AlignOut od{out->start + row0 * y->stride, out->count + row0 * y->stride,
+            const AlignOut od{out->start ? out->start + row0 * y->stride : nullptr, out->count ? out->count + row0 * y->stride : nullptr,
                               out->qual ? out->qual + row0 * y->stride : nullptr, logp};
+            if (cs) return launch_crf_spot(d, yd, od, bp, stream, reinterpret_cast<const CrfSpotOut *>(block));
             if (s) return launch_ctc_align(d, yd, c.collapse, bnd, od, bp, stream, reinterpret_cast<const SpotOut *>(block));
             return c.crf ? launch_crf_align(d, yd, c.init + r0 * c.init_stride, c.n_init, c.init_stride, bnd, od, bp, stream)
                          : launch_ctc_align(d, yd, c.collapse, bnd, od, bp, stream);
         },
-        s ? 256 : 0,
+        s || cs ? 256 : 0,
         [&](int64_t r0, int64_t row0, void *host) {
+            if (cs) {
+                *static_cast<CrfSpotOut *>(host) = CrfSpotOut{cs->end + row0, cs->first + row0, cs->track ? cs->track + row0 * cs->track_stride : nullptr,
+                                                              cs->track_stride, cs->row_begin ? cs->row_begin + r0 : nullptr,
+                                                              cs->row_end ? cs->row_end + r0 : nullptr, c.marg + r0 * c.marg_stride_read,
+                                                              c.marg_stride_read, c.marg_stride_t, c.marg_stride_s};
+                return;
+            }
             *static_cast<SpotOut *>(host) = SpotOut{s->end + row0, s->track ? s->track + row0 * s->track_stride : nullptr, s->track_stride,
                                                     s->row_begin ? s->row_begin + r0 : nullptr, s->row_end ? s->row_end + r0 : nullptr};
         },
@@ -2385,7 +2416,7 @@ int lattice_host(fcd_handle *h, const LatticeCall &c) {
     Staging st(h);
     // the posteriors keep their strides: the span from the first to the last addressed element is staged as it is
     const int i_post = st.in(in->post, (size_t)span_elems(in, c.crf) * (in->dtype == FCD_DTYPE_F32 ? 4 : 2));
-    const int i_init = st.in(c.crf ? c.init : nullptr, (size_t)((in->n_reads - 1) * c.init_stride + c.n_init) * 4);
+    const int i_init = st.in(c.crf && !c.cspot ? c.init : nullptr, (size_t)((in->n_reads - 1) * c.init_stride + c.n_init) * 4);
     const int i_len = st.in(in->lengths, B * 8);
     const int i_lab = st.in(y->labels, labelling_rows(c) * (size_t)y->stride);
     const int i_ylen = st.in(y->len, labelling_rows(c) * 4);
@@ -2406,7 +2437,13 @@ int lattice_host(fcd_handle *h, const LatticeCall &c) {
     const int i_dtrack = det ? st.inout(det->track, detect_track_span(in, y, det) * 4) : -1;
     const int i_drb = det ? st.in(det->row_begin, B * 4) : -1;
     const int i_dre = det ? st.in(det->row_end, B * 4) : -1;
-    const int i_marg = det ? st.in(c.marg, marg_span(c) * 4) : -1;
+    const int i_marg = det || c.cspot ? st.in(c.marg, marg_span(c) * 4) : -1;
+    const fcd_crf_spot *cs = c.cspot;
+    const int i_cend = cs ? st.out(cs->end, n_rows * 4) : -1;
+    const int i_cfirst = cs ? st.out(cs->first, n_rows * 4) : -1;
+    const int i_ctrack = cs ? st.inout(cs->track, track_floats(in, y, cs->track, cs->track_stride) * 4) : -1;
+    const int i_crb = cs ? st.in(cs->row_begin, B * 4) : -1;
+    const int i_cre = cs ? st.in(cs->row_end, B * 4) : -1;
     // (posterior entries the kernel does not write -- k >= len -- come back as 0)
     const int i_sub = c.posterior ? st.out(c.post->post, cells * ((size_t)in->N - 1) * 4, true) : -1;
     // (edit entries the kernel does not write -- k >= len, g > len -- come back as 0)
@@ -2440,6 +2477,17 @@ int lattice_host(fcd_handle *h, const LatticeCall &c) {
         dspot.row_begin = st.at<uint32_t>(i_rb);
         dspot.row_end = st.at<uint32_t>(i_re);
         d.spot = &dspot;
+    }
+    fcd_crf_spot dcs{};
+    if (cs) {
+        dcs = *cs;
+        dcs.end = st.at<uint32_t>(i_cend);
+        dcs.first = st.at<uint32_t>(i_cfirst);
+        dcs.track = st.at<float>(i_ctrack);
+        dcs.row_begin = st.at<uint32_t>(i_crb);
+        dcs.row_end = st.at<uint32_t>(i_cre);
+        d.cspot = &dcs;
+        d.marg = st.at<float>(i_marg);
     }
     fcd_detect ddet{};
     if (det) {
@@ -2648,10 +2696,43 @@ int fcd_crf_score_host(fcd_handle *h, const fcd_batch *in, const float *init, in
     return lattice_host(h, c);
 }
 
+namespace {
+// fcd_crf_spot_*: an alignment call without an init row, the spotting outputs and the marginals behind it
+int crf_spot_call(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int64_t band, const fcd_crf_spot *out,
+                  int (*run)(fcd_handle *, const LatticeCall &)) {
+    if (!out) return fail(h, FCD_E_INVALID, "crf_spot: null output");
+    const fcd_alignment al{out->start, out->count, out->qual, out->logp};
+    LatticeCall c{true, true, in, y, band, 0, nullptr, 0, 0, nullptr, &al};
+    c.cspot = out;
+    c.marg = out->marg;
+    c.marg_stride_read = out->marg_stride_read, c.marg_stride_t = out->marg_stride_t, c.marg_stride_s = out->marg_stride_s;
+    return run(h, c);
+}
+}  // namespace
+
+int fcd_set_crf_spot(fcd_handle *h, const fcd_crf_spot *spot) {
+    if (!h) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> g(h->mu);
+    h->crf_spot_on = spot != nullptr;
+    h->crf_spot = spot ? *spot : fcd_crf_spot{};
+    return FCD_OK;
+}
+
+int fcd_crf_spot_host(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int64_t band, const fcd_crf_spot *out) {
+    if (!h) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> whole_call(h->mu);  // staging .. copy-back, see run_host
+    return crf_spot_call(h, in, y, band, out, lattice_host);
+}
+
 int fcd_crf_align_dev(fcd_handle *h, const fcd_batch *in, const float *init, int64_t n_init, int64_t init_stride,
                       const fcd_labellings *y, int64_t band, const fcd_alignment *out) {
     if (!h) return FCD_E_INVALID;
     std::lock_guard<std::recursive_mutex> g(h->mu);
+    if (h->crf_spot_on && out) {  // fcd_set_crf_spot: the spotting call, the four shared arrays from this call's own `out`; init is not read
+        fcd_crf_spot s = h->crf_spot;
+        s.start = out->start, s.count = out->count, s.qual = out->qual, s.logp = out->logp;
+        return crf_spot_call(h, in, y, band, &s, lattice_dev);
+    }
     return lattice_dev(h, LatticeCall{true, true, in, y, band, 0, init, n_init, init_stride, nullptr, out});
 }
 

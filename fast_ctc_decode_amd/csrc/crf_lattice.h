@@ -39,6 +39,9 @@ struct CrfParams {
     int64_t bp_row_bytes;
     // motif occurrence posteriors (fcd_crf_detect_*: crf_detect_walk below); null in every other launch
     const CrfDetectOut *det;
+    // motif spotting (fcd_crf_spot_*: crf_spot_walk below); null in every other launch.  start / count / qual / bp above are
+    // its spans, all null when none are asked for
+    const CrfSpotOut *spot;
 };
 
 struct CrfLds {
@@ -388,6 +391,21 @@ __device__ __forceinline__ T *wave_uniform(T *ptr) {
     return reinterpret_cast<T *>((uintptr_t)wave_uniform((int64_t)(uintptr_t)ptr));
 }
 
+// The track of a walk whose rows are complete one at a time: c (times 2^sc) of row t of the range, whose first row `track`
+// points at, into lane t mod 64 (tv) until 64 rows -- or the range's last -- are stored at once, ln c in f32
+__device__ __forceinline__ void crf_track_row(float *track, float &tv, float c, int sc, int t, int rows) {
+    const int j = threadIdx.x;
+    if (j == (t & 63)) tv = c;
+    if ((t & 63) == 63 || t == rows - 1) {
+        const int c0 = t & ~63;
+        if (c0 + j <= t) {
+            int ex = 0;
+            const float m = frexpf(tv, &ex);
+            track[c0 + j] = tv > 0.0f ? fmaf((float)(ex - sc), kCrfLn2f, logf(m)) : -INFINITY;
+        }
+    }
+}
+
 // c_t (times 2^sc) is complete; t: row of the range, whose first row `track` points at (null: no track)
 __device__ __forceinline__ void crf_detect_row(float *track, CrfDetectAcc &acc, float c, int sc, int t, int rows) {
     acc.sum += (double)c;
@@ -395,18 +413,7 @@ __device__ __forceinline__ void crf_detect_row(float *track, CrfDetectAcc &acc, 
         acc.bv = c;
         acc.bt = t;
     }
-    if (track) {
-        const int j = threadIdx.x;
-        if (j == (t & 63)) acc.tv = c;
-        if ((t & 63) == 63 || t == rows - 1) {
-            const int c0 = t & ~63;
-            if (c0 + j <= t) {
-                int ex = 0;
-                const float m = frexpf(acc.tv, &ex);
-                track[c0 + j] = acc.tv > 0.0f ? fmaf((float)(ex - sc), kCrfLn2f, logf(m)) : -INFINITY;
-            }
-        }
-    }
+    if (track) crf_track_row(track, acc.tv, c, sc, t, rows);
 }
 
 // What a lane reads for one row, a row ahead of its use: the two posteriors of the state each of its slots holds.  Where
@@ -467,6 +474,96 @@ __device__ __forceinline__ void crf_detect_entries(const CrfLds &lds, int t0, in
             e += v;
         }
         crf_detect_etile(lds)[lane] = e;
+    }
+}
+
+// What crf_spot_walk does before its time loop, crf_detect_walk's statements: the rows without a value in
+// fcd_crf_score_*'s order, the range of rows, the cells' trajectory in lds.info and the entry weights' parameters in
+// lds.misc.  (Functions of their own, and crf_detect_walk keeps its text, so that the score kernels' detect copy compiles to
+// what it was: sharing them moved crf_detect by 1.7 % on an MI355X at unchanged register counts.)
+struct CrfMotif {
+    int64_t read;
+    int L, h, nc;  // labels; min(L, m); cells h .. L - 1
+    int tb, rows;  // the range's first row and its length
+};
+
+// false: the row does not walk and *early is its logp (NaN; 0 for an empty motif; -inf for an empty range)
+template <class OUT>
+__device__ __forceinline__ bool crf_motif_prologue(const CrfParams &p, const CrfLds &lds, const OUT *out, CrfMotif *mo, double *early) {
+    const int lane = threadIdx.x;
+    const int64_t row = blockIdx.x;
+    const int64_t read = row / p.y.n_hyp;
+    const int64_t hyp = row - read * p.y.n_hyp;
+    *early = (double)NAN;
+    if (p.y.n_valid && hyp >= (int64_t)p.y.n_valid[read]) return false;
+    int64_t Tr = p.in.lengths ? wave_uniform(p.in.lengths[read]) : p.in.T;
+    Tr = Tr < 0 ? 0 : (Tr > p.in.T ? p.in.T : Tr);
+    const uint32_t len = (uint32_t)wave_uniform((int)p.y.len[row]);
+    if ((int64_t)len > p.y.stride) return false;
+    const int L = (int)len;
+    const uint8_t *labels = p.y.labels + row * p.y.stride;
+    if (lane == 0) lds.misc[16] = lds.misc[kBadPost] = 0;
+    __syncthreads();
+    bool bad_label = false;
+    for (int k = lane; k < L; k += 64) {
+        const int y = labels[k];
+        bad_label |= y < 1 || y >= p.in.N;
+    }
+    if (bad_label) lds.misc[16] = 1;
+    __syncthreads();
+    if (lds.misc[16]) return false;
+    *early = 0.0;
+    if (L == 0) return false;
+    const uint32_t *row_begin = wave_uniform(out->row_begin), *row_end = wave_uniform(out->row_end);
+    const int tb = row_begin ? (int)min((int64_t)(uint32_t)wave_uniform((int)row_begin[read]), Tr) : 0;
+    const int te = row_end ? (int)min((int64_t)(uint32_t)wave_uniform((int)row_end[read]), Tr) : (int)Tr;
+    const int rows = te - tb;
+    *early = -(double)INFINITY;
+    if (rows <= 0) return false;
+    // the entry states d * q + prefix, d = 0 .. ne - 1, and the label they emit; the cells' trajectory, from the motif alone
+    const int S = p.in.S, nb = p.in.N - 1;
+    const int m = p.pow_m > 0 ? p.pow_m : 1;  // (S = 1 walks as m = 1: a state outside the table reads 0)
+    const int h = min(L, m), nc = L - h;
+    int q = 1, prefix = 0;
+    for (int j = 0; j < h - 1; ++j) {
+        prefix = prefix * nb + ((int)labels[j] - 1);
+        q *= nb;
+    }
+    for (int j = lane; j < nc; j += 64) {  // (nc > 0: h = m, so the m labels behind cell k = m + j exist)
+        int64_t s = 0;
+        for (int g = j; g < j + m; ++g) s = s * nb + ((int64_t)labels[g] - 1);
+        lds.info[j] = (s < S ? (uint32_t)s : kNoState) | ((uint32_t)labels[j + m] << 24);
+    }
+    __syncthreads();
+    // the entry weights' parameters wait in LDS (misc[0 .. 8], free in a CRF walk): read once per 64 rows, they take no
+    // scalar registers from the row loop
+    if (lane == 0) {
+        const float *marg = out->marg + read * out->marg_stride_read + (int64_t)tb * out->marg_stride_t + labels[h - 1];
+        const int64_t words[3] = {(int64_t)(uintptr_t)marg, out->marg_stride_t, out->marg_stride_s};
+        for (int w = 0; w < 3; ++w) {
+            lds.misc[2 * w] = (int)(uint32_t)words[w];
+            lds.misc[2 * w + 1] = (int)(uint32_t)((uint64_t)words[w] >> 32);
+        }
+        lds.misc[6] = q;
+        lds.misc[7] = prefix;
+        lds.misc[8] = (S - prefix + q - 1) / q;  // the states below S among them: all nb^(m-h+1) where S = nb^m
+    }
+    *mo = CrfMotif{read, L, h, nc, tb, rows};
+    return true;
+}
+
+// a slot's two constant offsets (crf_detect_load), from lds.info as the prologue left it
+template <int K, bool STAGED>
+__device__ __forceinline__ void crf_motif_offsets(const CrfParams &p, const CrfLds &lds, int nc, int (&off0)[K], int (&offy)[K]) {
+    const int lane = threadIdx.x;
+    const int esz = p.in.dtype == kF32 ? 4 : 2;
+#pragma unroll
+    for (int r = 0; r < K; ++r) {
+        const uint32_t info = lane * K + r < nc ? lds.info[lane * K + r] : kNoState;
+        const int sig = (int)(info & 0xFFFFFFu), y = (int)(info >> 24);
+        off0[r] = STAGED ? sig * p.in.N : (int)(sig * p.in.stride_s) * esz;
+        offy[r] = off0[r] + (STAGED ? y : (int)(y * p.in.stride_n) * esz);
+        if ((uint32_t)sig == kNoState) off0[r] = offy[r] = -1;
     }
 }
 
@@ -600,6 +697,196 @@ __device__ __forceinline__ void crf_detect_walk(const CrfParams &p, const CrfLds
         det->count[row] = flagged ? nan : ldexp(acc.sum, -sc);
         det->end[row] = flagged || !hit ? kCrfNoHit : (uint32_t)(tb + acc.bt);
         p.logp[row] = flagged ? nan : (hit ? ln_p((double)acc.bv, -sc) : -(double)INFINITY);
+    }
+}
+
+// ---- kCrfSpot: motif spotting, the best single occurrence and its rows under the CRF (fcd_crf_spot_*) ----
+// crf_detect_walk's lattice with max in the place of +, compiled into the ALIGNMENT's kernels (crf_lattice_kernel<true, K>)
+// and chosen once by CrfParams::spot.  Window, slots, offsets, scale, entry weights, source-lane products and the exit are
+// the detect walk's, word for word; what is its own:
+//   first    every cell carries, next to its value, the row at which its best path entered (u0, K more registers): the
+//            compare that picks the max picks it too, and it travels one slot up with the advance product.  The lane that
+//            owns cell L - 1 so knows the hit's first row at the exit: (first, end, logp, track) need no back-pointer and
+//            no workspace.  The exit stays one readlane a row; the second one (u0) is read only where the row is a new best.
+//   ballots  only where spans are asked for (bp, wave-uniform, tested outside the products): K 64-bit words a row, bit `lane`
+//            of word r = "the advance or the entry won, strictly" in slot lane * K + r -- the kCrfMax walk's layout.
+//   trace    after the walk, from cell L - 1 at row end - 1 down to the entry bit of cell h, 64 rows at a time through the
+//            tile area: rows first .. end - 1 only.  A set bit in slot j at row t is the emission row of y_(h+j-1).
+// Candidates in the order stay, then advance or entry: the later one only if strictly greater.
+struct CrfSpotAcc {
+    float bv;    // the best v so far (0: none yet) ...
+    int bt, bf;  // ... its row of the range, and the row its path entered at
+    float tv;    // crf_track_row's staging word
+};
+
+// a row that does not walk
+__device__ __forceinline__ void crf_spot_none(const CrfParams &p, double logp) {
+    const int64_t row = blockIdx.x;
+    if (threadIdx.x == 0) {
+        p.spot->end[row] = kCrfNoHit;
+        p.spot->first[row] = kCrfNoHit;
+        p.logp[row] = logp;
+    }
+    if (p.count) {
+        const int64_t n = min((int64_t)p.y.len[row], p.y.stride);
+        for (int64_t k = threadIdx.x; k < n; k += 64) p.count[row * p.y.stride + k] = 0u;
+    }
+}
+
+template <int K, bool STAGED>
+__device__ __forceinline__ void crf_spot_walk(const CrfParams &p, const CrfLds &lds) {
+    const CrfSpotOut *sp = p.spot;
+    const int lane = threadIdx.x;
+    const int64_t row = blockIdx.x;
+    CrfMotif mo;
+    double early;
+    if (!crf_motif_prologue(p, lds, sp, &mo, &early)) return crf_spot_none(p, early);
+    const int L = mo.L, h = mo.h, nc = mo.nc, tb = mo.tb, rows = mo.rows;
+    int off0[K], offy[K];
+    crf_motif_offsets<K, STAGED>(p, lds, nc, off0, offy);
+    float *track = wave_uniform(sp->track);
+    if (track) track += row * wave_uniform(sp->track_stride) + tb;
+    uint64_t *bp = p.start ? reinterpret_cast<uint64_t *>(p.bp + row * p.bp_row_bytes) : nullptr;
+    CrfSpotAcc acc{0.0f, -1, -1, 0.0f};
+    uint32_t bad = 0;
+    int sc = 0;
+    if (nc == 0) {  // L <= m: v_u = e_u, the hit is one row
+        for (int t0 = 0; t0 < rows; t0 += 64) {
+            crf_detect_entries(lds, t0, rows, &bad);
+            __syncthreads();
+            for (int i = 0; i < min(64, rows - t0); ++i) {
+                const float c = crf_detect_etile(lds)[i];
+                if (c > acc.bv) {
+                    acc.bv = c;
+                    acc.bt = acc.bf = t0 + i;
+                }
+                if (track) crf_track_row(track, acc.tv, c, 0, t0 + i, rows);
+            }
+        }
+    } else {
+        sc = kDetScale;
+        CrfRow rw;
+        rw.post = post_at(p.in.post, mo.read * p.in.stride_read + (int64_t)tb * p.in.stride_t, p.in.dtype);
+        rw.path = nullptr;
+        rw.Tr = rows;
+        rw.L = L;
+        const int end_lane = (nc - 1) / K, end_r = (nc - 1) % K;
+        float a[K];
+        int u0[K];
+#pragma unroll
+        for (int r = 0; r < K; ++r) {
+            a[r] = 0.0f;
+            u0[r] = 0;
+        }
+        for (int t0 = 0; t0 < rows;) {
+            // a tile ends where the staged rows end and where the next 64 entry weights begin
+            const int rc = min(min(p.rows_per_tile, rows - t0), 64 - (t0 & 63));
+            if ((t0 & 63) == 0) crf_detect_entries(lds, t0, rows, &bad);
+            crf_fill_tile(p, lds, rw, t0, rc);  // (its barriers order the 64 words too)
+            CrfDetectStep<K> in = crf_detect_load<K, STAGED>(p, lds, rw.post, off0, offy, t0, 0, &bad);
+            for (int i = 0; i < rc; ++i) {
+                const int t = t0 + i;
+                const float e = crf_detect_etile(lds)[t & 63];
+                float s[K], v[K];
+#pragma unroll
+                for (int r = 0; r < K; ++r) {
+                    s[r] = a[r] * in.p0[r];
+                    v[r] = a[r] * in.py[r];
+                }
+                if (i + 1 < rc) in = crf_detect_load<K, STAGED>(p, lds, rw.post, off0, offy, t + 1, i + 1, &bad);
+                float mine = 0.0f;
+                int mine_u = 0;
+#pragma unroll
+                for (int r = 0; r < K; ++r)
+                    if (r == end_r) {
+                        mine = v[r];
+                        mine_u = u0[r];
+                    }
+                const float c = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine), end_lane));
+                if (c > acc.bv) {  // (wave-uniform) strictly greater only: ties go to the earliest row
+                    acc.bv = c;
+                    acc.bt = t;
+                    acc.bf = __builtin_amdgcn_readlane(mine_u, end_lane);
+                }
+                float v_in = from_prev_lane(v[K - 1]);
+                int u_in = int_from_prev_lane(u0[K - 1]);
+                if (lane == 0) {  // slot 0's advance is the entry, at the walk's scale (exact), and it enters here
+                    v_in = e * 0x1p64f;
+                    u_in = t;
+                }
+                bool up[K];
+#pragma unroll
+                for (int r = K - 1; r >= 0; --r) {  // (from the top: u0[r - 1] is still the previous row's)
+                    const float adv = r >= 1 ? v[r - 1] : v_in;
+                    up[r] = adv > s[r];
+                    a[r] = up[r] ? adv : s[r];
+                    u0[r] = up[r] ? (r >= 1 ? u0[r - 1] : u_in) : u0[r];
+                }
+                if (bp) {
+                    uint64_t word = 0;
+#pragma unroll
+                    for (int r = 0; r < K; ++r) {
+                        const uint64_t w = __ballot(up[r]);
+                        if (lane == r) word = w;
+                    }
+                    if (lane < K) bp[(int64_t)t * K + lane] = word;
+                }
+                if (track) crf_track_row(track, acc.tv, c, kDetScale, t, rows);
+            }
+            t0 += rc;
+        }
+    }
+    if (bad) lds.misc[kBadPost] = 1;
+    __syncthreads();
+    const bool flagged = lds.misc[kBadPost] != 0;
+    if (flagged || acc.bt < 0) return crf_spot_none(p, flagged ? (double)NAN : -(double)INFINITY);
+    if (lane == 0) {
+        sp->end[row] = (uint32_t)(tb + acc.bt);
+        sp->first[row] = (uint32_t)(tb + acc.bf);
+        p.logp[row] = ln_p((double)acc.bv, -sc);
+    }
+    if (!p.start) return;
+    // the spans: labels 0 .. h - 2 lie in the model's history and are not located; y_(h-1) is emitted at the entry, y_(L-1)
+    // at the hit's last row, the others where the trace finds their cells entered
+    uint32_t *start = p.start + row * p.y.stride, *count = p.count + row * p.y.stride;
+    float *qual = p.qual + row * p.y.stride;
+    for (int k = lane; k < L; k += 64) {
+        const bool located = k >= h - 1;
+        count[k] = located ? 1u : 0u;
+        start[k] = located ? (uint32_t)(tb + acc.bt) : kCrfNoHit;  // (a row of the read, whatever the trace finds)
+        if (!located) qual[k] = 0.0f;
+    }
+    __syncthreads();
+    if (lane == 0) {
+        start[h - 1] = (uint32_t)(tb + acc.bf);
+        start[L - 1] = (uint32_t)(tb + acc.bt);
+    }
+    uint64_t *sbp = reinterpret_cast<uint64_t *>(lds.tile);
+    int j = nc - 1;  // the cell the path is in at row t: (nc == 0: no walk, no trace)
+    for (int c0 = (acc.bt - 1) & ~63; j >= 0 && c0 >= 0 && c0 + 63 >= acc.bf; c0 -= 64) {
+        const int n = min(64, acc.bt - c0);  // rows c0 .. end - 1
+        __syncthreads();
+        for (int e = lane; e < n * K; e += 64) sbp[e] = bp[(int64_t)c0 * K + e];
+        __syncthreads();
+        for (int i = n - 1; i >= 0 && j >= 0 && c0 + i >= acc.bf; --i) {
+            const uint64_t word = sbp[i * K + j % K];
+            const int d = __builtin_amdgcn_readfirstlane((int)((word >> (j / K)) & 1u));
+            if (d) {  // cell h + j was entered at this row: y_(h+j-1) is emitted here (j = 0: the entry, written above)
+                if (lane == 0 && j > 0) start[h + j - 1] = (uint32_t)(tb + c0 + i);
+                j -= 1;
+            }
+        }
+    }
+    // the qualities, as the alignment writes them: p[start_k][sigma_k][y_k] for k >= h, the entry weight for k = h - 1
+    crf_detect_entries(lds, acc.bf & ~63, rows, &bad);
+    __syncthreads();  // ... and start as the trace left it
+    if (lane == 0) qual[h - 1] = crf_detect_etile(lds)[acc.bf & 63];
+    const float *post = post_at(p.in.post, mo.read * p.in.stride_read, p.in.dtype);
+    for (int k = h + lane; k < L; k += 64) {
+        const uint32_t info = lds.info[k - h];
+        const uint32_t sig = info & 0xFFFFFFu;
+        const int64_t at = (int64_t)start[k] * p.in.stride_t + (int64_t)sig * p.in.stride_s + (int64_t)(info >> 24) * p.in.stride_n;
+        qual[k] = sig != kNoState ? load_post(post, at, p.in.dtype) : 0.0f;
     }
 }
 

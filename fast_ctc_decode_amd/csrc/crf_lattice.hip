@@ -25,6 +25,10 @@
 // Detect (fcd_crf_detect_*): the expected number of occurrences of a motif over all labellings -- crf_detect_walk of
 // crf_lattice.h, a walk of its own (fixed window, fixed scale, entry weights from the edge marginals) compiled into the
 // score's kernels and chosen once, at their top, by CrfParams::det.
+//
+// Spot (fcd_crf_spot_*): the best single occurrence of a motif and its rows -- crf_spot_walk of crf_lattice.h, the detect
+// walk's lattice with max for +, the entry row riding with every cell, back-pointer ballots only where spans are asked for;
+// compiled into the alignment's kernels and chosen by CrfParams::spot.
 #include <math.h>
 
 #include <algorithm>
@@ -54,7 +58,11 @@ __global__ __launch_bounds__(64) void crf_lattice_kernel(CrfParams p) {
     const CrfLds lds = crf_carve(smem);
     // fcd_crf_detect_*: a second, compile-time copy of the walk in the score's kernels, chosen ONCE by a pointer that is null
     // in a score -- whose rows run the instructions they ran before the copy existed
-    if (!MAX && p.det) return p.staged ? crf_detect_walk<K, true>(p, lds) : crf_detect_walk<K, false>(p, lds);
+    if constexpr (!MAX) {
+        if (p.det) return p.staged ? crf_detect_walk<K, true>(p, lds) : crf_detect_walk<K, false>(p, lds);
+    } else {  // fcd_crf_spot_*: the same in the alignment's kernels, by a pointer that is null in an alignment
+        if (p.spot) return p.staged ? crf_spot_walk<K, true>(p, lds) : crf_spot_walk<K, false>(p, lds);
+    }
     CrfRow rw;
     if (!crf_prologue(p, lds, &rw)) {
         if (MAX) crf_no_alignment(p);
@@ -181,6 +189,35 @@ hipError_t launch_crf_detect(const BatchDesc &in, const ScoreDesc &y, double *lo
     p.lab_cap = (int)y.stride + 1;
     const int64_t states = std::max<int64_t>(y.stride - crf_detect_history(in.S, in.N) + 1, 1);
     return launch_crf<false>(p, states <= 64 ? 1 : (states <= 128 ? 2 : (states <= 256 ? 4 : 8)), rows, stream);
+}
+
+// fcd_crf_spot_*: K as launch_crf_detect chooses it; the back-pointers of a labelling, where spans are asked for, are K
+// 64-bit ballots for every row of T
+static int crf_spot_states_per_lane(const BatchDesc &in, int64_t stride) {
+    const int64_t states = std::max<int64_t>(stride - crf_detect_history(in.S, in.N) + 1, 1);
+    return states <= 64 ? 1 : (states <= 128 ? 2 : (states <= 256 ? 4 : 8));
+}
+
+size_t crf_spot_row_bytes(const BatchDesc &in, int64_t stride) {
+    const size_t per_row = 8 * (size_t)crf_spot_states_per_lane(in, stride);
+    return ((size_t)std::max<int64_t>(in.T, 1) * per_row + 255) & ~(size_t)255;
+}
+
+// out.start null (then count and qual are): no spans, bp is not read
+hipError_t launch_crf_spot(const BatchDesc &in, const ScoreDesc &y, const AlignOut &out, unsigned char *bp, hipStream_t stream,
+                           const CrfSpotOut *spot) {
+    const int64_t rows = in.n_reads * y.n_hyp;
+    if (rows <= 0) return hipSuccess;
+    CrfParams p = crf_params(in, y, nullptr, 0, 0, 0);
+    p.logp = out.logp;
+    p.start = out.start;
+    p.count = out.count;
+    p.qual = out.qual;
+    p.bp = bp;
+    p.bp_row_bytes = (int64_t)crf_spot_row_bytes(in, y.stride);
+    p.spot = spot;
+    p.lab_cap = (int)y.stride + 1;
+    return launch_crf<true>(p, crf_spot_states_per_lane(in, y.stride), rows, stream);
 }
 
 hipError_t launch_crf_align(const BatchDesc &in, const ScoreDesc &y, const float *init, int64_t n_init, int64_t init_stride,

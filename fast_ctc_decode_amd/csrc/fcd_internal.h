@@ -360,6 +360,21 @@ struct CrfDetectOut {
 };
 int crf_detect_unsupported(const BatchDesc &in, int64_t stride);
 hipError_t launch_crf_detect(const BatchDesc &in, const ScoreDesc &y, double *logp, hipStream_t stream, const CrfDetectOut *detect);
+// CRF motif spotting (crf_lattice.h's crf_spot_walk inside crf_lattice_kernel<true, K>; fcd_crf_spot in include/fcd.h): the
+// same kind of block in DEVICE memory, so that an alignment's kernel arguments grow by one pointer.  The limits are
+// crf_detect_unsupported's.  out.start / count / qual all null: no spans, and bp is not read; otherwise bp holds
+// crf_spot_row_bytes() per labelling of the launch.  out.logp must not be null.
+struct CrfSpotOut {
+    uint32_t *end, *first;
+    float *track;  // nullable
+    int64_t track_stride;
+    const uint32_t *row_begin, *row_end;  // nullable
+    const float *marg;                    // as CrfDetectOut's
+    int64_t marg_stride_read, marg_stride_t, marg_stride_s;
+};
+size_t crf_spot_row_bytes(const BatchDesc &in, int64_t stride);
+hipError_t launch_crf_spot(const BatchDesc &in, const ScoreDesc &y, const AlignOut &out, unsigned char *bp, hipStream_t stream,
+                           const CrfSpotOut *spot);
 // CRF forward-backward substitution posteriors of given labellings (crf_posterior.hip; fcd_crf_posterior_* in include/fcd.h),
 // on top of crf_lattice_unsupported.  crf_posterior_unsupported: 0 = the kernels hold the call; 1 = the window exceeds the
 // *max_states register-resident states of the chain's tier, 2 = more than 8 labels, 4 = S is no power of N - 1, 5 = a
@@ -554,6 +569,8 @@ struct fcd_handle {
     bool detect_packed = false;  // fcd_set_ctc_detect_packed: the detecting calls take shared motifs, one pair per lane
     bool crf_detect_on = false;      // fcd_set_crf_detect: fcd_crf_score_dev detects, with ...
     fcd_crf_detect crf_detect{};     // ... these outputs, ranges and marginals next to its own logp
+    bool crf_spot_on = false;        // fcd_set_crf_spot: fcd_crf_align_dev spots, with ...
+    fcd_crf_spot crf_spot{};         // ... these outputs, ranges and marginals next to its own fcd_alignment
     int64_t align_ws_cap = 0; // fcd_debug_set_align_workspace_cap: back-pointer bytes one launch of fcd_ctc_align_* may take, 0 = default
     bool is_lane = false;
     uint32_t *duplex_prof = nullptr;  // fcd_debug_set_duplex_profile

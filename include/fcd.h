@@ -744,7 +744,7 @@ int fcd_crf_align_host(fcd_handle *h, const fcd_batch *in, const float *init, in
  * given with track_stride < in->T, and fcd_crf_score_*'s cases but for init.  FCD_E_UNSUPPORTED (the message says which):
  * S neither 1 nor a power of N - 1; N - 1 > 8; stride - m + 1 > 512 (the cells live in registers, 64 x 8: motifs up to
  * 511 + m labels); S >= 2^24 - 1.  The workspace: 256 bytes of parameters, and logp where it is null.
- * Out of scope: the best single occurrence (a crf_spot), a packed one-pair-per-lane form, bands, f16 marginals. */
+ * Out of scope: a packed one-pair-per-lane form, bands, f16 marginals.  (The best single occurrence: fcd_crf_spot_* below.) */
 typedef struct fcd_crf_detect {
     double   *count;            /* [n_reads * n_hyp] */
     uint32_t *end;              /* [n_reads * n_hyp] */
@@ -765,6 +765,71 @@ int fcd_crf_detect_host(fcd_handle *h, const fcd_batch *in, const fcd_labellings
  * the handle must not be shared with another thread; the Python layer sets, calls and clears on the calling thread's own
  * handle. */
 int fcd_set_crf_detect(fcd_handle *h, const fcd_crf_detect *detect);
+
+/* ---- CRF motif spotting: the best single occurrence and its rows under the CRF (csrc/crf_lattice.h, crf_spot_walk) ----
+ * NOT a reference function.  fcd_ctc_spot_*'s question -- where does this motif sit in this read -- for a CRF model.
+ * fcd_crf_detect_* says how often a motif occurs and where an occurrence most probably ends; this call says where the best
+ * single occurrence begins and ends and which rows emit its labels: adapter and primer trimming, chimera splitting.
+ * Inputs are fcd_crf_detect_*'s, word for word: p = in (source-indexed transition posteriors, f32 / f16 / bf16, any
+ * strides, ragged lengths; no init row is read), marg and its three strides, nb = N - 1, S = nb^m (S = 1 walks as m = 1, a
+ * state outside the table reads 0), a motif y_0 .. y_(L-1) (labelling i of read r), the read's range [b, e).
+ * Let h = min(L, m).  The entry weight e_u (the sum of marg[u][sigma][y_(h-1)] over the entry states, f32, ascending) and
+ * the trajectory sigma_k are fcd_crf_detect_*'s; the recurrence is its with max in the place of +, a_(b-1) = 0:
+ *   a_u[h] = max( a_(u-1)[h] * p[u][sigma_h][0] ,  e_u )
+ *   a_u[k] = max( a_(u-1)[k] * p[u][sigma_k][0] ,  a_(u-1)[k-1] * p[u][sigma_(k-1)][y_(k-1)] )      k = h+1 .. L-1
+ *   v_u    = a_(u-1)[L-1] * p[u][sigma_(L-1)][y_(L-1)]   (L > h);    v_u = e_u   (L = h, no walk)
+ *   hit    = argmax_u v_u, ties to the earliest row
+ * Candidates in the order stay, then advance or entry: the later one wins only if strictly greater.
+ * Meaning.  marg is the joint probability, over all labellings, of being in a state and taking an edge; after the entry
+ * edge the model state is sigma_h, fully determined by the motif when L >= m, and p is conditional on the state.  So v_u is
+ * exactly the probability of the best single alignment of the occurrence: the model emits y_(h-1) at some row u0 from a
+ * state whose last h - 1 labels are the motif's first, then follows one particular run of stays and emissions that ends
+ * with y_(L-1) emitted at row u.  It is fcd_ctc_spot_*'s v_t for a CRF, with no boundary approximation, and never greater
+ * than fcd_crf_detect_*'s c_u of the same inputs.  The first h - 1 labels of the motif lie in the model's history at the
+ * entry: their rows are no part of the event and are NOT LOCATED.
+ * Per labelling row:
+ *   end  [row]   the hit's last row, absolute; 0xFFFFFFFF when there is no hit.  Not null.
+ *   first[row]   the emission row of y_(h-1), the first located row of the hit; 0xFFFFFFFF with no hit.  Not null.
+ *   logp [row]   ln v_hit, float64, ln(m) + E ln 2.  Nullable.
+ *   track[row * track_stride + u]   ln v_u in f32 for u in [b, e), -inf where 0; rows outside the range are not written.
+ *                Nullable; track_stride >= in->T.
+ *   start, count, qual [row * stride + k]   nullable, all three TOGETHER: null, no spans are formed and no back-pointer is
+ *                written.  For k >= h - 1: start is the label's emission row, absolute, and count = 1, as fcd_crf_align_*
+ *                writes them; qual[k] = p[start_k][sigma_k][y_k] for k >= h and qual[h-1] = e_first, the entry weight.
+ *                For k < h - 1: start = 0xFFFFFFFF, count = 0, qual = 0.  No hit: count = 0 for every k < min(len, stride),
+ *                start / qual are left alone.
+ * Arithmetic: f32, one rounding per product, max exact; the cells carry fcd_crf_detect_*'s fixed factor 2^64 and its floor
+ * (a cell below 2^-190 loses bits, one below 2^-213 counts as 0).
+ * Rows without a value, their order, FCD_E_INVALID, FCD_E_UNSUPPORTED and the limits (stride - m + 1 <= 512, nb <= 8,
+ * S < 2^24 - 1, a gathered row below 2^31 bytes) are fcd_crf_detect_*'s: logp = NaN / 0 / -inf where it writes them, with
+ * end = first = 0xFFFFFFFF.  FCD_E_INVALID also for band != 0, a null end, first or marg, and exactly one or two of start /
+ * count / qual given.  The workspace: 256 bytes of parameters and logp where it is null; with spans 8 K bytes (K = 1, 2, 4, 8
+ * cells a lane, from stride - m + 1) per row of T and labelling, launched in groups of whole reads as fcd_crf_align_*.
+ * Out of scope: a packed one-pair-per-lane form, the k best hits on the device, bands, f16 marginals, locating the h - 1
+ * history labels. */
+typedef struct fcd_crf_spot {
+    uint32_t *start;            /* [n_reads * n_hyp * stride], nullable with count and qual */
+    uint32_t *count;            /* [n_reads * n_hyp * stride] */
+    float    *qual;             /* [n_reads * n_hyp * stride] */
+    double   *logp;             /* [n_reads * n_hyp], nullable */
+    uint32_t *end;              /* [n_reads * n_hyp] */
+    float    *track;            /* [n_reads * n_hyp * track_stride], nullable */
+    int64_t   track_stride;
+    const uint32_t *row_begin;  /* [n_reads], nullable */
+    const uint32_t *row_end;    /* [n_reads], nullable */
+    uint32_t *first;            /* [n_reads * n_hyp] */
+    const float *marg;          /* the edge marginals, f32 */
+    int64_t   marg_stride_read, marg_stride_t, marg_stride_s;  /* in elements */
+} fcd_crf_spot;
+int fcd_crf_spot_host(fcd_handle *h, const fcd_batch *in, const fcd_labellings *y, int64_t band, const fcd_crf_spot *out);
+/* Device arrays: a handle switch in front of the alignment's own device entry point, as fcd_set_ctc_spot is in front of
+ * fcd_ctc_align_dev.  fcd_set_crf_spot(h, spot) copies *spot into the handle; while it is set, fcd_crf_align_dev on that
+ * handle IS the spotting call: its init arguments are ignored and may be null, band must be 0, start / count / qual / logp
+ * come from the call's own fcd_alignment (all three of start / count / qual may be null there; those four members of *spot
+ * are ignored), everything else comes from *spot.  spot = NULL turns it off.  fcd_crf_align_host is not affected.  The
+ * threading caveat is fcd_set_ctc_spot's: between setting and clearing the switch the handle must not be shared with
+ * another thread; the Python layer sets, calls and clears on the calling thread's own handle. */
+int fcd_set_crf_spot(fcd_handle *h, const fcd_crf_spot *spot);
 
 /* ---- CRF forward-backward substitution posteriors of given labellings (csrc/crf_posterior.hip) ----
  * NOT a reference function.  Everything is as fcd_crf_score_* defines it: batch (n_reads, T, S, N), init, nb = N - 1, the
