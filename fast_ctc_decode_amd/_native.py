@@ -37,7 +37,7 @@ SYMBOLS = [
     "fcd_crf_greedy_search_dev", "fcd_crf_greedy_search_host",
     "fcd_beam_search_duplex_dev", "fcd_beam_search_duplex_host",
     "fcd_crf_beam_search_duplex_dev", "fcd_crf_beam_search_duplex_host",
-    "fcd_duplex_envelope_dev", "fcd_duplex_envelope_host",
+    "fcd_duplex_envelope_dev", "fcd_duplex_envelope_host", "fcd_edit_distance_host", "fcd_set_edit_distance",
     "fcd_logspace_probe_dev", "fcd_debug_glibc235_dev", "fcd_logadd_latency_probe_dev", "fcd_logadd_sweep_dev", "fcd_phred",
     "fcd_packed_result_bytes", "fcd_result_offsets_dev", "fcd_pack_results_dev", "fcd_unpack_results_dev",
     "fcd_coalescer_create", "fcd_coalescer_destroy", "fcd_coalescer_beam_search", "fcd_coalescer_viterbi_search",
@@ -106,6 +106,11 @@ class Spot(C.Structure):
     """fcd_spot: what fcd_ctc_spot_* writes, and the range of rows it looks in (include/fcd.h)."""
     _fields_ = Alignment._fields_ + [("end", C.c_void_p), ("track", C.c_void_p), ("track_stride", C.c_int64),
                                      ("row_begin", C.c_void_p), ("row_end", C.c_void_p)]
+
+
+class EditDistance(C.Structure):
+    """fcd_edit_distance: what fcd_edit_distance_* writes, and its mode (include/fcd.h)."""
+    _fields_ = [("distance", C.c_void_p), ("end", C.c_void_p), ("mode", C.c_int32)]
 
 
 class Detect(C.Structure):
@@ -264,6 +269,8 @@ def bind(lib):
     for sfx in ("dev", "host"):
         getattr(lib, "fcd_duplex_envelope_" + sfx).argtypes = [
             P, i64, P, P, P, i64, P, i64, P, P, P, i64, P, i64, i64, P, i64]
+    lib.fcd_edit_distance_host.argtypes = [P, i64, P, P, i64, i64, P, P, i64, i64, C.POINTER(EditDistance)]
+    lib.fcd_set_edit_distance.argtypes = [P, C.POINTER(EditDistance)]  # (device arrays: fcd_duplex_envelope_dev under this switch)
     lib.fcd_logspace_probe_dev.argtypes = [P, P, P, P, P, i64, i32]
     lib.fcd_debug_glibc235_dev.argtypes = [P, i32, P, P, i64]
     lib.fcd_logadd_latency_probe_dev.argtypes = [P, i32, i32, P, P]

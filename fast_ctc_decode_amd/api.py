@@ -1020,6 +1020,94 @@ def estimate_envelope(network_output_1, network_output_2, band=64):
     return estimate_envelope_batch(_dense(x1)[None], _dense(x2)[None], band)[0]
 
 
+_EDIT_MODES = {"global": 0, "infix": 1}  # FCD_EDIT_GLOBAL, FCD_EDIT_INFIX
+
+
+def _edit_rows(labels, lengths, name, torch_dev):
+    """(n_pairs, cap) uint8 rows, unit stride inside a row, and their lengths -> (labels, uint32 / int32 lengths, stride)"""
+    if getattr(labels, "ndim", 0) != 2 or str(labels.dtype).split(".")[-1] != "uint8":
+        raise TypeError("argument '%s': expected a 2-dimensional uint8 array" % name)
+    n = int(labels.shape[0])
+    if torch_dev is None:
+        lens = np.clip(np.asarray(lengths).astype(np.int64), 0, 0xFFFFFFFF).astype(np.uint32)
+        st = tuple(int(v) for v in labels.strides)
+    else:
+        import torch
+        if not hasattr(lengths, "is_cuda"):
+            lengths = np.clip(np.asarray(lengths).astype(np.int64), 0, 0x7FFFFFFF).astype(np.int32)
+        lens = torch.as_tensor(lengths, device=torch_dev)
+        if lens.dtype == getattr(torch, "uint32", None):
+            lens = lens.view(torch.int32)  # (the same 32 bits: the kernel reads them unsigned)
+        elif lens.dtype != torch.int32:  # (out_len of a search is int32 already: taken as it is)
+            lens = lens.clamp(0, 0x7FFFFFFF).to(torch.int32)
+        lens = lens.contiguous()
+        st = tuple(int(v) for v in labels.stride())
+    if tuple(lens.shape) != (n,):
+        raise ValueError("argument '%s': %d rows need %d lengths" % (name, n, n))
+    if labels.shape[1] and n and (st[1] != 1 or st[0] < labels.shape[1]):
+        labels = np.ascontiguousarray(labels) if torch_dev is None else labels.contiguous()
+        st = (int(labels.shape[1]), 1)
+    return labels, lens, max(st[0], int(labels.shape[1])) if n > 1 else int(labels.shape[1])
+
+
+def edit_distance_batch_raw(labels_1, lengths_1, labels_2, lengths_2, mode="global", return_end=False, handle=None):
+    """Unit-cost edit distance of n_pairs pairs of labellings, on the device (include/fcd.h, fcd_edit_distance_*): pair r is
+    a = labels_1[r, :lengths_1[r]] against b = labels_2[r, :lengths_2[r]].  mode="global": the Levenshtein distance of a
+    and b (label error rate = distance / len(truth)); mode="infix": the least distance of b to any a[s:e] -- b found inside
+    a -- and, with return_end=True, the smallest such e.  -> int32 (n_pairs,), or (distance, end) with return_end=True.
+
+    labels_1 / labels_2: (n_pairs, cap) uint8, label values below 16, rows need not be dense (a view of a wider array is
+    read in place); at most 32768 columns in labels_2.  Both numpy (staged through the handle: numpy out) or both torch
+    tensors on the GPU (enqueued on torch's current stream, not synchronised: tensors out).  A pair that holds a label of
+    16 or more inside its lengths gets -1 in both outputs."""
+    if mode not in _EDIT_MODES:
+        raise ValueError("mode must be 'global' or 'infix'")
+    on_dev = _is_torch_cuda(labels_1)
+    if on_dev != _is_torch_cuda(labels_2) or not (on_dev or (isinstance(labels_1, np.ndarray) and isinstance(labels_2, np.ndarray))):
+        raise TypeError("labels_1 and labels_2 must both be numpy arrays or both be torch tensors on the GPU")
+    dev = labels_1.device if on_dev else None
+    a, n1, s1 = _edit_rows(labels_1, lengths_1, "labels_1", dev)
+    b, n2, s2 = _edit_rows(labels_2, lengths_2, "labels_2", dev)
+    n = int(a.shape[0])
+    if int(b.shape[0]) != n:
+        raise ValueError("labels_1 and labels_2 must hold the same number of rows")
+    xp = _Arrays(dev)
+    dist, end = xp.empty((n,), "u32"), xp.empty((n,), "u32") if return_end else None  # (0xFFFFFFFF reads as -1)
+    h = handle if handle is not None else nat.default_handle((dev.index or 0) if on_dev else 0)
+    out = nat.EditDistance(xp.ptr(dist), None if end is None else xp.ptr(end), _EDIT_MODES[mode])
+    seq1, seq2 = (xp.ptr(a), xp.ptr(n1), s1, int(a.shape[1])), (xp.ptr(b), xp.ptr(n2), s2, int(b.shape[1]))
+    try:
+        if on_dev:
+            import torch
+            h.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+            h.check(h.lib.fcd_set_edit_distance(h.ptr, C.byref(out)))
+            try:
+                (l1, p1, _, c1), (l2, p2, _, c2) = seq1, seq2
+                h.check(h.lib.fcd_duplex_envelope_dev(h.ptr, n, l1, None, p1, s1, None, c1, l2, None, p2, s2, None, c2, 0, None, 0))
+            finally:
+                h.lib.fcd_set_edit_distance(h.ptr, None)
+            h.hold_in_flight(a, b, n1, n2, dist, end)
+        else:
+            h.check(h.lib.fcd_edit_distance_host(h.ptr, n, *seq1, *seq2, C.byref(out)))
+    except nat.NativeError as e:
+        if e.code == nat.E_INVALID:
+            raise ValueError(str(e)) from None
+        raise
+    if not on_dev:
+        dist, end = dist.view(np.int32), None if end is None else end.view(np.int32)
+    return (dist, end) if return_end else dist
+
+
+def edit_distance(sequence_1, sequence_2, alphabet="NACGT", mode="global"):
+    """One pair of strings over alphabet[1:] (alphabet[0] is the blank; at most 15 labels) -> the edit distance as an int:
+    edit_distance_batch_raw on one pair.  mode="infix": sequence_2 found inside sequence_1."""
+    alpha = _seq_to_vec(alphabet)
+    if len(alpha) > 16:
+        raise ValueError("edit_distance takes alphabets of at most 16 symbols")
+    y = [np.asarray(_sequence_labels(s, alpha, "edit_distance"), np.uint8).reshape(1, -1) for s in (sequence_1, sequence_2)]
+    return int(edit_distance_batch_raw(y[0], [y[0].shape[1]], y[1], [y[1].shape[1]], mode)[0])
+
+
 def crf_beam_search_duplex_batch_raw(network_outputs_1, init_states_1, network_outputs_2,
                                      init_states_2, envelopes=None, beam_size=5,
                                      beam_cut_threshold=0.0, lengths_1=None, lengths_2=None,
@@ -1276,6 +1364,15 @@ class BatchResult(_LatticeMethods):
         if band and self.path is None:
             raise ValueError("a band needs the result's path")
         return None
+
+    def edit_distance(self, labels, label_lengths, mode="global", return_end=False):
+        """The edit distance of every read's result to a truth labelling: edit_distance_batch_raw with the given labellings
+        (n_reads, stride) as sequence 1 and this result's own labels as sequence 2 -- mode="infix" finds a decoded chunk
+        inside a longer reference.  A device result stays on the device (the truth is moved there), numpy stays numpy."""
+        if not isinstance(self.labels, np.ndarray) and not _is_torch_cuda(labels):
+            import torch
+            labels = torch.as_tensor(np.ascontiguousarray(labels, np.uint8)).to(self.labels.device)
+        return edit_distance_batch_raw(labels, label_lengths, self.labels, self.out_len, mode, return_end, getattr(self, "_handle", None))
 
     def sequences(self, alphabet, raise_on_error=True, paths="list"):
         """-> list of (str, path) per read, exactly what the single-read functions return.

@@ -1701,6 +1701,48 @@ int fcd_crf_beam_search_duplex_host(fcd_handle *h, const fcd_batch *in1, const f
                        logadd_mode, out);
 }
 
+namespace {
+// what fcd_edit_distance_host checks before it stages anything, and the device call again
+int edit_check(fcd_handle *h, int64_t n_pairs, const void *labels1, const void *len1, int64_t stride1, int64_t cap1,
+               const void *labels2, const void *len2, int64_t stride2, int64_t cap2, const fcd_edit_distance *out) {
+    if (n_pairs < 0 || cap1 < 0 || cap2 < 0) return fail(h, FCD_E_INVALID, "edit_distance: negative size");
+    if (!out || !out->distance) return fail(h, FCD_E_INVALID, "edit_distance: null distance");
+    if (out->mode != FCD_EDIT_GLOBAL && out->mode != FCD_EDIT_INFIX) return fail(h, FCD_E_INVALID, "edit_distance: unknown mode");
+    if (!labels1 || !len1 || !labels2 || !len2) return fail(h, FCD_E_INVALID, "edit_distance: null array");
+    if (stride1 < cap1 || stride2 < cap2) return fail(h, FCD_E_INVALID, "edit_distance: label strides shorter than the caps");
+    if (cap2 > kEditMaxPattern) return fail(h, FCD_E_UNSUPPORTED, "edit_distance: sequence 2 holds more than 32768 labels");
+    if (cap1 > INT32_MAX) return fail(h, FCD_E_UNSUPPORTED, "edit_distance: sequence 1 holds more than 2147483647 labels");
+    if (n_pairs > (int64_t)INT32_MAX) return fail(h, FCD_E_UNSUPPORTED, "edit_distance: more than 2147483647 pairs");
+    return FCD_OK;
+}
+
+// fcd_duplex_envelope_dev under fcd_set_edit_distance: one launch, no workspace, nothing read back
+int edit_distance_dev(fcd_handle *h, int64_t n_pairs, const uint8_t *labels1, const uint32_t *len1, int64_t stride1, int64_t cap1,
+                      const uint8_t *labels2, const uint32_t *len2, int64_t stride2, int64_t cap2) {
+    const fcd_edit_distance &o = h->edit;
+    int rc = edit_check(h, n_pairs, labels1, len1, stride1, cap1, labels2, len2, stride2, cap2, &o);
+    if (rc || n_pairs == 0) return rc;
+    FCD_DEVICE(h);
+    CallScope sc(h);
+    sc.add(labels1, (size_t)(n_pairs - 1) * stride1 + cap1);
+    sc.add(labels2, (size_t)(n_pairs - 1) * stride2 + cap2);
+    sc.add(len1, (size_t)n_pairs * 4);
+    sc.add(len2, (size_t)n_pairs * 4);
+    sc.add(o.distance, (size_t)n_pairs * 4);
+    sc.add(o.end, (size_t)n_pairs * 4);
+    rc = sc.begin(false, false);
+    if (rc) return rc;
+    EditArgs a;
+    a.labels1 = labels1; a.labels2 = labels2; a.len1 = len1; a.len2 = len2;
+    a.stride1 = stride1; a.stride2 = stride2; a.n_pairs = n_pairs; a.cap1 = (int)cap1; a.cap2 = (int)cap2;
+    a.distance = o.distance; a.end = o.end; a.mode = o.mode;
+    edit_tier(cap2, &a.W, &a.gshift);
+    sc.time();
+    FCD_HIP(h, launch_edit_distance(a, sc.stream));
+    return sc.finish();
+}
+}  // namespace
+
 // ---- alignment-band estimator (envelope.hip) ----
 int fcd_duplex_envelope_dev(fcd_handle *h, int64_t n_pairs,
                             const uint8_t *labels1, const uint32_t *path1, const uint32_t *len1,
@@ -1710,6 +1752,8 @@ int fcd_duplex_envelope_dev(fcd_handle *h, int64_t n_pairs,
                             int64_t band, uint64_t *envelope, int64_t env_stride) {
     if (!h) return FCD_E_INVALID;
     std::lock_guard<std::recursive_mutex> g(h->mu);
+    if (h->edit_on)  // fcd_set_edit_distance: the edit-distance call
+        return edit_distance_dev(h, n_pairs, labels1, len1, stride1, T1cap, labels2, len2, stride2, T2cap);
     if (n_pairs < 0 || T1cap < 0 || T2cap < 0 || band < 0) return fail(h, FCD_E_INVALID, "negative size");
     if (n_pairs == 0 || T1cap == 0) return FCD_OK;
     if (!labels1 || !path1 || !len1 || !labels2 || !path2 || !len2 || !envelope)
@@ -1789,6 +1833,39 @@ int fcd_duplex_envelope_host(fcd_handle *h, int64_t n_pairs,
                                  st.at<int64_t>(i_t1), T1cap, st.at<uint8_t>(i_l2), st.at<uint32_t>(i_p2),
                                  st.at<uint32_t>(i_n2), stride2, st.at<int64_t>(i_t2), T2cap, band, st.at<uint64_t>(i_env),
                                  env_stride);
+    if (rc) return rc;
+    return st.fetch();
+}
+
+// ---- batched edit distance (envelope.hip, the kernel's second body) ----
+int fcd_set_edit_distance(fcd_handle *h, const fcd_edit_distance *ed) {
+    if (!h) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> g(h->mu);
+    h->edit_on = ed != nullptr;
+    h->edit = ed ? *ed : fcd_edit_distance{};
+    return FCD_OK;
+}
+
+int fcd_edit_distance_host(fcd_handle *h, int64_t n_pairs, const uint8_t *labels1, const uint32_t *len1, int64_t stride1,
+                           int64_t cap1, const uint8_t *labels2, const uint32_t *len2, int64_t stride2, int64_t cap2,
+                           const fcd_edit_distance *out) {
+    if (!h) return FCD_E_INVALID;
+    std::lock_guard<std::recursive_mutex> whole_call(h->mu);  // staging .. copy-back, see run_host
+    int rc = edit_check(h, n_pairs, labels1, len1, stride1, cap1, labels2, len2, stride2, cap2, out);
+    if (rc || n_pairs == 0) return rc;
+    FCD_DEVICE(h);
+    // (the last row is read as far as its cap, not its stride: the arrays may be views of wider ones)
+    Staging st(h);
+    const int i_l1 = st.in(labels1, (size_t)(n_pairs - 1) * stride1 + cap1), i_l2 = st.in(labels2, (size_t)(n_pairs - 1) * stride2 + cap2);
+    const int i_n1 = st.in(len1, (size_t)n_pairs * 4), i_n2 = st.in(len2, (size_t)n_pairs * 4);
+    const int i_d = st.out(out->distance, (size_t)n_pairs * 4), i_e = st.out(out->end, (size_t)n_pairs * 4);
+    rc = st.commit();
+    if (rc) return rc;
+    const fcd_edit_distance staged{st.at<uint32_t>(i_d), st.at<uint32_t>(i_e), out->mode};
+    fcd_set_edit_distance(h, &staged);
+    rc = fcd_duplex_envelope_dev(h, n_pairs, st.at<uint8_t>(i_l1), nullptr, st.at<uint32_t>(i_n1), stride1, nullptr, cap1,
+                                 st.at<uint8_t>(i_l2), nullptr, st.at<uint32_t>(i_n2), stride2, nullptr, cap2, 0, nullptr, 0);
+    fcd_set_edit_distance(h, nullptr);  // (on every way out)
     if (rc) return rc;
     return st.fetch();
 }

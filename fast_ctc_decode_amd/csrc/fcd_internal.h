@@ -249,6 +249,21 @@ struct EnvelopeArgs {
 size_t envelope_lds_bytes(int64_t L2cap);
 hipError_t launch_max_u32(const uint32_t *a, const uint32_t *b, int64_t n, uint32_t *out2, hipStream_t stream);
 hipError_t launch_envelope(const EnvelopeArgs &a, int64_t pair_begin, int64_t n_pairs, hipStream_t stream);
+// batched edit distance (fcd_edit_distance_*): the second body of envelope_kernel; all pointers are device memory
+struct EditArgs {
+    const uint8_t *labels1, *labels2;  // [pair][stride] label indices below 16: sequence 1 is the text, sequence 2 the pattern
+    const uint32_t *len1, *len2;       // labels per sequence, clipped to cap1 / cap2
+    int64_t stride1, stride2;
+    int64_t n_pairs;
+    int cap1, cap2;
+    uint32_t *distance, *end;          // [pair]; end nullable
+    int mode;                          // FCD_EDIT_GLOBAL / FCD_EDIT_INFIX
+    int W;                             // 64-label blocks of the pattern a lane holds: 1, 2, 4 or 8
+    int gshift;                        // a pattern spreads over a group of 1 << gshift adjacent lanes (W = 8 beyond one lane)
+};
+constexpr int64_t kEditMaxPattern = 32768;  // 64 lanes of 8 blocks of 64 labels
+void edit_tier(int64_t cap2, int *W, int *gshift);  // the tier a cap on sequence 2 selects
+hipError_t launch_edit_distance(const EditArgs &a, hipStream_t stream);
 
 // compact wire format of decoded results (pack.hip)
 hipError_t launch_result_offsets(const uint32_t *len, int64_t n, int64_t stride, uint64_t *offsets, hipStream_t stream);
@@ -571,6 +586,8 @@ struct fcd_handle {
     fcd_crf_detect crf_detect{};     // ... these outputs, ranges and marginals next to its own logp
     bool crf_spot_on = false;        // fcd_set_crf_spot: fcd_crf_align_dev spots, with ...
     fcd_crf_spot crf_spot{};         // ... these outputs, ranges and marginals next to its own fcd_alignment
+    bool edit_on = false;            // fcd_set_edit_distance: fcd_duplex_envelope_dev is the edit-distance call, with ...
+    fcd_edit_distance edit{};        // ... these outputs and this mode
     int64_t align_ws_cap = 0; // fcd_debug_set_align_workspace_cap: back-pointer bytes one launch of fcd_ctc_align_* may take, 0 = default
     bool is_lane = false;
     uint32_t *duplex_prof = nullptr;  // fcd_debug_set_duplex_profile

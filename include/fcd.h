@@ -1315,6 +1315,44 @@ int fcd_duplex_envelope_host(fcd_handle *h, int64_t n_pairs,
                              int64_t stride2, const int64_t *T2, int64_t T2cap,
                              int64_t band, uint64_t *envelope, int64_t env_stride);
 
+/* ---- batched edit distance of labellings: label error rate on the device (csrc/envelope.hip, the kernel's second body) ----
+ * NOT a reference function.  Integer work, exact.  Per pair r: a = the first len1[r] labels of row r of labels1 (rows
+ * stride1 apart), b = the first len2[r] labels of row r of labels2; lengths are clipped to cap1 / cap2.
+ *   FCD_EDIT_GLOBAL: distance = the unit-cost Levenshtein distance of a and b, end = len(a).
+ *   FCD_EDIT_INFIX:  distance = the minimum over 0 <= s <= e <= len(a) of the Levenshtein distance of a[s:e] and b -- b found
+ *                    inside a, the ends of a free -- and end = the smallest e that attains it.  len(b) = 0: distance 0,
+ *                    end 0; len(a) = 0: distance len(b), end 0.
+ * Label values are below 16 (four bit-planes).  A pair that holds a label of 16 or more inside its clipped lengths gets
+ * distance = end = 0xFFFFFFFF; the other pairs are not affected (found on the device: the call stays enqueue-only).
+ * The kernel is Myers' bit-parallel recurrence, one pair per lane with the pattern b in registers; the tier follows from
+ * cap2 alone, no length is read on the host: up to 64 / 128 / 256 / 512 labels a lane holds 1 / 2 / 4 / 8 blocks of 64,
+ * beyond that a pair takes a group of 2, 4, .. 64 lanes of 8 blocks (cap2 <= 1024, 2048, .. 32768), 64 / g pairs per
+ * wavefront, len(a) + g - 1 steps.  No workspace.
+ * Limits (FCD_E_UNSUPPORTED; the message names the limit): cap2 <= 32768; cap1 < 2^31.
+ * FCD_E_INVALID before anything is enqueued: a null array, a null out or out->distance, a negative size, stride1 < cap1 or
+ * stride2 < cap2, an unknown mode.  n_pairs = 0 is FCD_OK. */
+enum { FCD_EDIT_GLOBAL = 0, FCD_EDIT_INFIX = 1 };
+typedef struct fcd_edit_distance {
+    uint32_t *distance;   /* [n_pairs] */
+    uint32_t *end;        /* [n_pairs], nullable */
+    int32_t   mode;       /* FCD_EDIT_GLOBAL = 0, FCD_EDIT_INFIX = 1 */
+} fcd_edit_distance;
+int fcd_edit_distance_host(fcd_handle *h, int64_t n_pairs,
+                           const uint8_t *labels1, const uint32_t *len1,
+                           int64_t stride1, int64_t cap1,
+                           const uint8_t *labels2, const uint32_t *len2,
+                           int64_t stride2, int64_t cap2,
+                           const fcd_edit_distance *out);
+/* Device arrays: a handle switch in front of fcd_duplex_envelope_dev, as fcd_set_ctc_spot is in front of
+ * fcd_ctc_align_dev.  fcd_set_edit_distance(h, ed) copies *ed into the handle; while it is set, fcd_duplex_envelope_dev on
+ * that handle IS the edit-distance call: it reads labels1, len1, stride1, T1cap (= cap1), labels2, len2, stride2 and T2cap
+ * (= cap2); path1, path2, T1, T2, band, envelope and env_stride are ignored and may be null or 0; distance and end are
+ * written through the copied struct -- enqueue-only on the handle's stream, behind overlapping searches that write any of
+ * the arrays, no host synchronisation.  ed = NULL turns it off.  fcd_duplex_envelope_host is not affected.  The threading
+ * caveat is fcd_set_ctc_spot's: between setting and clearing the switch the handle must not be shared with another thread;
+ * the Python layer sets, calls and clears on the calling thread's own handle. */
+int fcd_set_edit_distance(fcd_handle *h, const fcd_edit_distance *ed);
+
 
 /* ---- compact wire format of a shard's results, for the ONE gather of the multi-GPU path ----
  * The searches write fixed-stride rows; only out_len[r] entries of row r are meaningful (~48 % at BASELINE
